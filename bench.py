@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- NN queries/s of the obstacle-cloud engine on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic queries: the batched 1-NN (pct_nn_batch_dev,
 include/pct_engine.h) of Q = 1,048,576 queries against the cloud resident in HBM, cell-pruned kernel (device-side query
 binning + nn_grid_coop_kernel).  FOUR distinct query batches (seeds 5, 1005, 2005, 3005) are resident and step k answers
 batch k mod 4, so a step is never a replay of the previous one.  W warmup steps, then exactly K timed steps (barrier +
-synchronize on both sides); there is no other untimed repetition of the step -- the secondary probes of the line (streaming
-kernel, brute force, radius count, index build: GPU work the program does anyway) run BEFORE the warmup steps instead of after
-the timed region, so the card is not measured straight out of the idle state the host-side input generation leaves it in.
+synchronize on both sides); there is no other untimed repetition of the step.  With --full the secondary probes of the line
+(streaming kernel, brute force, radius count, index build: GPU work the program does anyway) run BEFORE the warmup steps instead
+of after the timed region, so the card is not measured straight out of the idle state the host-side input generation leaves it in.
+
+A plain run is set-up, the W warmup steps and the K timed steps, then the headline line (value, ms_per_step, config).
+--full adds everything else, as before: the instrumented passes and the roofline, the probes, the CPU baseline and, at N > 1,
+config C4's own batch and the one-card reference.  --dump-outputs DIR writes the answers of the last timed step (N = 1) for
+output-for-output comparison of two builds; the inputs are seeded, so the same arguments give the same inputs.
 
 N = 1 (config C3-throughput of SURVEY.md section 8(d), the configuration the metric is quoted on): 10,000,000 uniform points in
 [0,100)^3 (seed 3).
@@ -421,7 +426,17 @@ def parse():
     ap.add_argument("--routed", type=int, default=1, help="N > 1: the routed form through the C ABI is the headline (0 = index-range shards only)")
     ap.add_argument("--spatial-leg", type=int, default=1, help="N > 1: also time the batch with spatially routed queries (0 = skip)")
     ap.add_argument("--one-gpu-ref", type=int, default=1, help="N > 1: rank 0 also times the batch against the whole cloud on its one card (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the instrumented passes and the roofline, the secondary probes, the CPU "
+                         "baseline, config C4's own batch and the one-card reference at N > 1 (the --*-probe / --cpu-* / --one-gpu-ref options "
+                         "select among them).  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write the answers of the last timed step as DIR/nn_d2.npy and DIR/nn_index.npy (float64, one row per "
+                         "query; -1 = no point); above 60 MB a fixed seeded sample of the rows, whose positions go to DIR/nn_rows.npy")
+    a = ap.parse_args()
+    if a.dump_outputs and a.gpus > 1:
+        ap.error("--dump-outputs covers the one-GPU step (--gpus 1)")
+    return a
 
 
 def self_launch(a) -> int:
@@ -622,6 +637,20 @@ def gpu_probes(a, E, synth, torch, sc, q, local_pts, Q):
 
 
 QUERY_SEEDS = (5, 1005, 2005, 3005)        # the step's batches: step k answers batch k mod 4
+DUMP_BYTES = 60_000_000                     # --dump-outputs: at most this much in all (files stay under 64 MB)
+
+
+def dump_outputs(out_dir: str, d2: np.ndarray, idx: np.ndarray) -> None:
+    """--dump-outputs: one step's answers as float64 arrays (indices < 2^53 are exact); a batch larger than DUMP_BYTES is cut to a
+    fixed sample of rows (seed 0, ascending), whose positions go beside them"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"nn_d2": d2.astype(np.float64), "nn_index": idx.astype(np.float64)}
+    if 16 * len(d2) > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(len(d2), DUMP_BYTES // 24, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["nn_rows"] = rows.astype(np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def main():
@@ -635,6 +664,8 @@ def main():
     rank, local, world = D.init_process_group_from_env()
     if world != a.gpus and world > 1:
         a.gpus = world
+    if a.dump_outputs and world > 1:
+        sys.exit("bench.py: --dump-outputs covers the one-GPU step")
     # one GPU per rank; PCT_DIST_BACKEND=gloo rehearses the multi-rank path with several ranks on one card
     ncards = max(torch.cuda.device_count(), 1)
     dev = (local % ncards) if world > 1 else 0
@@ -663,27 +694,29 @@ def main():
             tdist.barrier()
         torch.cuda.synchronize()
 
-    # ---- N = 1: the secondary probes on the same cloud, and the instrumented (work-counting) pass of every batch ----
+    # ---- --full: the secondary probes on the same cloud (N = 1), and the instrumented (work-counting) pass of every batch ----
     pre = {}
-    if a.stream_probe and world == 1 and not a.probes_directly_before_warmup:
+    if a.full and a.stream_probe and world == 1 and not a.probes_directly_before_warmup:
         pre = gpu_probes(a, E, synth, torch, sc, q, local_pts, Q)
-    sc.cloud.set_work_counters(True)
-    pts_scanned = runs = 0.0
-    for b in range(len(qs)):
-        sc.nn_local(qs[b], algo)
-        torch.cuda.synchronize()
-        w = sc.cloud.last_work()
-        pts_scanned += w[0] / len(qs)
-        runs += w[1] / len(qs)
-    sc.cloud.set_work_counters(False)
-    if a.stream_probe and world == 1 and a.probes_directly_before_warmup:
+    if a.full:
+        sc.cloud.set_work_counters(True)
+        pts_scanned = runs = 0.0
+        for b in range(len(qs)):
+            sc.nn_local(qs[b], algo)
+            torch.cuda.synchronize()
+            w = sc.cloud.last_work()
+            pts_scanned += w[0] / len(qs)
+            runs += w[1] / len(qs)
+        sc.cloud.set_work_counters(False)
+    if a.full and a.stream_probe and world == 1 and a.probes_directly_before_warmup:
         try:
             pre = gpu_probes(a, E, synth, torch, sc, q, local_pts, Q)
         except Exception as ex:      # noqa: BLE001  (secondary figures: the headline must still be measured and printed)
             pre = {"secondary_probes_error": f"{type(ex).__name__}: {ex}"}
 
     # ---- the measured region: W warmup steps, then exactly K timed steps; the dominant kernel's duration is sampled on every 4th
-    # timed launch (the kernel's own begin / end timestamps, read after the closing barrier) ----
+    # timed launch (the kernel's own begin / end timestamps, read after the closing barrier; only --full reports it, but every run
+    # times the same steps) ----
     preheat = max(a.preheat_steps, 0)                 # opt-in extra untimed steps (default none); reported in the line
     for k in range(preheat + a.warmup):
         sc.nn_submit(qs[k % len(qs)], algo)
@@ -694,7 +727,7 @@ def main():
     for k in range(a.steps):
         # at N > 1 the exchange step of batch k runs on a side stream under the kernels of batch k+1 (dist.nn_submit);
         # the closing barrier + synchronize waits for every batch's merged answer
-        sc.nn_submit(qs[k % len(qs)], algo)
+        last = sc.nn_submit(qs[k % len(qs)], algo)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -706,18 +739,24 @@ def main():
     kern_ms = sc.cloud.kernel_ms_history(max(1, min(n_samples, 64)))
     sc.cloud.set_timing_stride(1)
     k_ms = float(np.mean(kern_ms))
-    # answers of batch 0 for the parity checks below (untimed)
-    d2, idx, done = sc.nn_submit(q, algo)
-    barrier()
-    d2_keep, idx_keep = d2.clone(), idx.clone()       # the result slots are reused by the probes below
-    # 12 B per point scanned (3 x fp32) + 8 B per examined cell run + 12 B per query in + 12 B out
-    bytes_alg = 12 * pts_scanned + 8 * runs + 24 * Q if algo == E.ALGO_GRID else 12 * len(local_pts) * ((Q + 7) // 8) + 24 * Q
-    bytes_rec = 16 * pts_scanned + 8 * runs + 24 * Q if algo == E.ALGO_GRID else bytes_alg   # what the 16-byte {x,y,z,index} records move
-    achieved = bytes_alg / (k_ms * 1e-3) / 1e9
+    if a.dump_outputs:
+        # what the caller of the step received in the last timed step (N = 1: the engine's own result buffers, which later
+        # batches reuse, so they are read out here)
+        dump_outputs(a.dump_outputs, last[0].cpu().numpy(), last[1].cpu().numpy())
+    if a.full or c4:
+        # answers of batch 0 for the parity checks below (untimed)
+        d2, idx, done = sc.nn_submit(q, algo)
+        barrier()
+        d2_keep, idx_keep = d2.clone(), idx.clone()       # the result slots are reused by the probes below
+    if a.full:
+        # 12 B per point scanned (3 x fp32) + 8 B per examined cell run + 12 B per query in + 12 B out
+        bytes_alg = 12 * pts_scanned + 8 * runs + 24 * Q if algo == E.ALGO_GRID else 12 * len(local_pts) * ((Q + 7) // 8) + 24 * Q
+        bytes_rec = 16 * pts_scanned + 8 * runs + 24 * Q if algo == E.ALGO_GRID else bytes_alg   # what the 16-byte {x,y,z,index} records move
+        achieved = bytes_alg / (k_ms * 1e-3) / 1e9
 
     # ---- N > 1: config C4's own batch (Q = 4096, seed 7) through both kernel families, merged ------------------------------
     c4_legs = None
-    if c4:
+    if c4 and a.full:
         q4 = torch.from_numpy(synth.uniform_points(7, 4096, 0.0, side)).to(sc.device)
         brute_ms = timed_batches(sc, q4, E.ALGO_STREAM, 3, barrier)
         index_ms = timed_batches(sc, q4, E.ALGO_GRID, 10, barrier) if algo == E.ALGO_GRID else None
@@ -823,7 +862,7 @@ def main():
         except Exception as ex:      # noqa: BLE001  (the index-range figure then stays the headline)
             routed = {"error": f"{type(ex).__name__}: {ex}"}
     one_gpu = None
-    if c4 and a.one_gpu_ref:
+    if c4 and a.full and a.one_gpu_ref:
         # strong-scaling base in the same run: rank 0's card alone holds the WHOLE cloud and answers the same batch
         if rank == 0:
             with E.Cloud(n_total) as whole:
@@ -854,12 +893,6 @@ def main():
             tdist.destroy_process_group()
         return
 
-    kname = "nn_grid_coop_kernel" if algo == E.ALGO_GRID else "nn_tile_candidates_kernel"
-    cnt, cnt_src = measured_counters(kname, threads=8 * Q)
-    traffic = cnt.get("derived_hbm_traffic_bytes_per_launch")
-    if c4:
-        cnt, cnt_src, traffic = {}, None, None       # the committed PMC passes are of the N = 1 command
-    bound, bound_detail = bound_from_counters(cnt, k_ms)
     value = Q / elapsed * a.steps                    # merged answers per second (never multiplied by the rank count)
     scaling_kind = "strong" if c4 else "weak"
     index_range = None
@@ -903,7 +936,8 @@ def main():
             "points_per_gpu": sc.end - sc.begin, "total_points": n_total, "queries_per_step": Q, "algo": a.algo,
             "query_batches_in_rotation": len(qs), "extra_untimed_steps_before_warmup": preheat,
             "gpu_work_before_the_warmup_steps": ("one instrumented pass per query batch, then the line's secondary probes on the same cloud (streaming kernel, "
-                                                 "brute force, radius count, C2, index rebuild)" if pre else "one instrumented pass per query batch"),
+                                                 "brute force, radius count, C2, index rebuild)" if pre else "one instrumented pass per query batch" if a.full else "none"),
+            "full": a.full,
             "query_shard_evaluations_per_s": world * value,
             "parallelism": (f"cloud sharded by contiguous index range over {world} GPU(s), queries replicated, all_reduce(min) merge"
                             if world > 1 else "single GPU"),
@@ -912,7 +946,15 @@ def main():
             "grid": sc.cloud.grid_info() if sc.cloud.has_grid else None,
             "grid_build_s": round(t_grid, 4),
         },
-        "roofline": {
+    }
+    if a.full:
+        kname = "nn_grid_coop_kernel" if algo == E.ALGO_GRID else "nn_tile_candidates_kernel"
+        cnt, cnt_src = measured_counters(kname, threads=8 * Q)
+        traffic = cnt.get("derived_hbm_traffic_bytes_per_launch")
+        if c4:
+            cnt, cnt_src, traffic = {}, None, None       # the committed PMC passes are of the N = 1 command
+        bound, bound_detail = bound_from_counters(cnt, k_ms)
+        out["roofline"] = {
             "bound": bound or "hbm", "roofline": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
             "traffic": traffic, "traffic_source": cnt_src,
             "frac_of_measured_traffic": (traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
@@ -925,8 +967,7 @@ def main():
             "note": ("gather kernel: `frac` = algorithmic bytes / kernel time / 8 TB/s; the 10 M-point cloud (160 MB cell-sorted) stays in the 256 MiB "
                      "Infinity Cache, so the bytes that reach the fabric are `traffic` (frac_of_measured_traffic) and `bound` says what the SQ counters "
                      "of the committed profile say; the DRAM-resident figures are in c4_probe (100 M-point cloud) and stream_probe"),
-        },
-    }
+        }
     out.update(pre)
     if index_range:
         out["index_range_shards"] = index_range
@@ -943,7 +984,7 @@ def main():
     if one_gpu:
         out["one_gpu_whole_cloud"] = dict(one_gpu, speedup_of_this_run=value / one_gpu["answers_per_s"])
 
-    if a.replan_probe and world == 1:
+    if a.replan_probe and a.full and world == 1:
         guarded(out, "replan_probe", lambda: replan_probe(E, synth))
         guarded(out, "replan_probe_clustered", lambda: replan_probe(E, synth, ticks=100, clustered=True))
         # corridor generation per replan (config C1 scenario: seed-6 pillar map seen from the start pose, clean_demo.launch constants,
@@ -959,7 +1000,7 @@ def main():
         guarded(out, "corridor_replan_probe", corridor_scenario)
         guarded(out, "c1_stated_probe", lambda: c1_stated_probe(E, None))    # config C1 exactly as SURVEY 8(d) states it
 
-    if a.replan_probe and world == 1:
+    if a.replan_probe and a.full and world == 1:
         # ingest stage in front of the cloud: voxel de-duplication of the 10 M-point cloud at res 0.25
         def ingest():
             from pointcloudtraj_amd import voxel
@@ -979,14 +1020,14 @@ def main():
             return res
         guarded(out, "ingest_probe", ingest)
 
-    if a.clustered_probe and world == 1:
+    if a.clustered_probe and a.full and world == 1:
         guarded(out, "clustered_probe", lambda: clustered_probe(E, synth, torch, sc.device, Q))
 
-    if a.c4_probe and world == 1:
+    if a.c4_probe and a.full and world == 1:
         guarded(out, "c4_probe", lambda: c4_probe(E, synth, torch, sc.device, Q))
 
     O = None
-    if a.cpu_queries > 0 and world == 1:
+    if a.cpu_queries > 0 and a.full and world == 1:
         from oracle import oracle as O
         ncpu = a.cpu_points or a.points
         try:

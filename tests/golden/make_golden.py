@@ -12,6 +12,9 @@ What is recorded, and from which implementation:
   kd_general_k.npz
       the same library through kd_create(k) for k = 1, 2, 3 (doubles fp32 cannot hold), 4, 5, 7, 17: nearest ids (the walk's winner
       on ties) and range ids in iteration order.
+  kd_random_seeds.npz
+      the same library on two seeded clouds (seeds 41 and 42: 5,000 uniform points plus 50 duplicates, 500 queries around them):
+      nearest ids and d2, and range ids in iteration order for 40 of the queries at radii 1.0, 1.25, ..., 10.75.
   binomials.npz
       the 13 x 13 table c(n, k) of the REFERENCE's own Planner/src/binomial_coefs.cpp (the one planner source that compiles
       stand-alone; oracle/_ref/libbinomial_ref.so).  Pins the three ways the oracle and the two ways the device write "n choose k".
@@ -374,6 +377,37 @@ def gen_binomials():
     save("binomials.npz", c_n_k=tab)
 
 
+RANDOM_SEEDS = (41, 42)
+
+
+def random_seed_case(seed):
+    """the cloud and queries of kd_random_seeds.npz for one seed (regenerated from pointcloudtraj_amd.synth, not stored)"""
+    pts = synth.uniform_points(seed, 5000, 0, 50)
+    pts = np.concatenate([pts, pts[:50]])           # some duplicates
+    q = synth.uniform_points(seed + 100, 500, -5, 55)
+    radii = np.array([np.float32(1.0 + 0.25 * k) for k in range(40)], np.float32)
+    return pts, q, radii
+
+
+def gen_random_seeds():
+    print("seeded random clouds (reference kdtree.c):")
+    kw = dict(seeds=np.array(RANDOM_SEEDS), ref_idx=[], ref_d2=[], range_ids=[], range_off=[])
+    for seed in RANDOM_SEEDS:
+        pts, q, radii = random_seed_case(seed)
+        R = O.RefKD()
+        R.insert(pts)
+        idx, d2 = R.nearest(q)
+        kw["ref_idx"].append(idx)
+        kw["ref_d2"].append(d2)
+        ids = [np.asarray(R.range_ids(q[k], float(r)), np.int64) for k, r in enumerate(radii)]
+        kw["range_off"].append(np.cumsum([0] + [len(i) for i in ids]))
+        kw["range_ids"].append(np.concatenate(ids))
+        R.close()
+    off = np.cumsum([0] + [len(i) for i in kw["range_ids"]])
+    save("kd_random_seeds.npz", seeds=kw["seeds"], ref_idx=np.stack(kw["ref_idx"]), ref_d2=np.stack(kw["ref_d2"]),
+         range_ids=np.concatenate(kw["range_ids"]), range_off=np.stack(kw["range_off"]), seed_off=off)
+
+
 if __name__ == "__main__":
     O.build(force=True)
     assert O.have_ref(), "needs /root/reference to build oracle/_ref"
@@ -383,7 +417,11 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "general_k":      # only the general-k fixture
         gen_general_k()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "random_seeds":   # only the seeded random clouds
+        gen_random_seeds()
+        sys.exit(0)
     gen_binomials()
+    gen_random_seeds()
     gen_general_k()
     gen_nn()
     gen_range()

@@ -105,7 +105,7 @@ def test_bench_two_ranks_on_one_card():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--points-total", "4000000",
-                        "--queries", "65536", "--preheat-steps", "10"], env=env, capture_output=True, text=True, timeout=900)
+                        "--queries", "65536", "--preheat-steps", "10", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -119,6 +119,28 @@ def test_bench_two_ranks_on_one_card():
     assert "error" not in sp, sp
     assert sp["same_answers_as_index_range_shards"] is True
     assert 0.3 * 65536 < sp["owned_queries_rank0_per_batch"] < 0.7 * 65536 and sp["uncertified_rank0_per_batch"] < 0.02 * 65536
+
+
+def test_bench_two_ranks_on_one_card_plain():
+    """The same launch without --full: the headline path alone (index-range shards and the routed candidates the headline is chosen
+    from), one line of the same shape, and none of the legs that only --full runs."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--points-total", "4000000",
+                        "--queries", "65536"], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["config"]["backend"] == "gloo"
+    assert d["config"]["total_points"] == 4000000 and d["config"]["points_per_gpu"] == 2000000 and d["config"]["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["config"]["query_shard_evaluations_per_s"] - 2 * d["value"]) < 1e-6 * d["value"]
+    assert d["index_range_shards"]["merged_answers_per_s"] > 0
+    assert d["spatial_routing"]["same_answers_as_index_range_shards"] is True
+    assert not {"roofline", "one_gpu_whole_cloud", "c4_q4096", "cpu_baseline"} & set(d)
 
 
 def test_cpp_shard_client_over_rccl():
