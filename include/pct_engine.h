@@ -327,7 +327,7 @@ int pct_plan_replan_run(pct_plan *p, const pct_inflate_params *prm, const double
 int pct_plan_last_run_us(pct_plan *p, double us[4]);
 
 /* ---- measurement hooks (bench.py): HIP events recorded on the stream the kernels ran on.
- * pct_last_kernel_ms: the last batch's DOMINANT kernel alone (nn_grid_kernel, nn_tile_filter_kernel
+ * pct_last_kernel_ms: the last batch's DOMINANT kernel alone (nn_grid_coop_kernel, the brute-force filter
  * or the nn_stream_kernel passes) -- the same quantity rocprofv3 --kernel-trace averages;
  * pct_last_batch_ms: every kernel of the batch (binning, bounds, reduction included). ---------- */
 int pct_last_kernel_ms(pct_cloud *c, float *ms);

@@ -74,103 +74,14 @@ __device__ __forceinline__ void group_pp(const PointGroup &g, v2f &pp01, v2f &pp
     pp23 = __builtin_elementwise_fma(g.z23, g.z23, pp23);
 }
 
-// Same structure as nn_tile_candidates_kernel: a block stages its chunk of the cloud in LDS once (here: CENTRED), walks its slice
-// of the batch in tiles of 8 wave-uniform queries; a lane whose group passes a query's threshold evaluates it exactly (fp64, the
-// original coordinates re-read from global memory) and appends (d2, index) to that query's candidate list.
-// kGroupsPerIter = point groups per lane and loop iteration: independent LDS reads and FMA chains in flight
-template <int kGroupsPerIter>
-__global__ __launch_bounds__(256) void nn_tile_candidates2_kernel(const float *__restrict__ x, const float *__restrict__ y,
-                                                                  const float *__restrict__ z, uint32_t n, uint32_t chunk_groups,
-                                                                  CentreDesc C, const float4 *__restrict__ qprep, const double *__restrict__ q64,
-                                                                  int Q, int qslice, uint32_t *__restrict__ cand_count,
-                                                                  double *__restrict__ cand_d2, uint32_t *__restrict__ cand_idx)
-{
-    extern __shared__ float4 s_pts[];                 // [3][chunk_groups], centred
-    const uint32_t ngroups = n >> 2;
-    const uint32_t g0 = blockIdx.x * chunk_groups;
-    const uint32_t ng = min(chunk_groups, ngroups > g0 ? ngroups - g0 : 0u);
-    float4 *sx = s_pts, *sy = s_pts + chunk_groups, *sz = s_pts + 2 * chunk_groups;
-    for (uint32_t i = threadIdx.x; i < ng; i += 256) {
-        float4 X = reinterpret_cast<const float4 *>(x)[g0 + i], Y = reinterpret_cast<const float4 *>(y)[g0 + i], Z = reinterpret_cast<const float4 *>(z)[g0 + i];
-        X.x -= C.cx; X.y -= C.cx; X.z -= C.cx; X.w -= C.cx;
-        Y.x -= C.cy; Y.y -= C.cy; Y.z -= C.cy; Y.w -= C.cy;
-        Z.x -= C.cz; Z.y -= C.cz; Z.z -= C.cz; Z.w -= C.cz;
-        sx[i] = X; sy[i] = Y; sz[i] = Z;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const bool tail_owner = (blockIdx.x == gridDim.x - 1) && threadIdx.x < (n & 3u);   // n % 4 leftover points
-
-    const int q_end = min(Q, ((int)blockIdx.y + 1) * qslice);
-    for (int q0 = (int)blockIdx.y * qslice; q0 < q_end; q0 += kTileQ) {
-        const int qcount = min(kTileQ, q_end - q0);
-        float ax[kTileQ], ay[kTileQ], az[kTileQ], thr[kTileQ];
-#pragma unroll
-        for (int j = 0; j < kTileQ; j++) {
-            const float4 P = qprep[q0 + (j < qcount ? j : qcount - 1)];
-            ax[j] = P.x; ay[j] = P.y; az[j] = P.z; thr[j] = P.w;
-        }
-        for (uint32_t i0 = threadIdx.x; i0 < ng; i0 += 256 * kGroupsPerIter) {
-            PointGroup pg[kGroupsPerIter];
-            v2f pp01[kGroupsPerIter], pp23[kGroupsPerIter];
-#pragma unroll
-            for (int u = 0; u < kGroupsPerIter; u++) {
-                const uint32_t i = min(i0 + 256u * (uint32_t)u, ng - 1);           // past the end: repeat the last group (its hits are masked below)
-                pg[u] = make_group(sx[i], sy[i], sz[i]);
-                group_pp(pg[u], pp01[u], pp23[u]);
-            }
-            unsigned long long hit[kGroupsPerIter];
-#pragma unroll
-            for (int u = 0; u < kGroupsPerIter; u++) hit[u] = 0ull;
-#pragma unroll
-            for (int j = 0; j < kTileQ; j++) {
-#pragma unroll
-                for (int u = 0; u < kGroupsPerIter; u++)
-                    hit[u] |= __builtin_amdgcn_ballot_w64(group_min_t(pg[u], pp01[u], pp23[u], ax[j], ay[j], az[j]) <= thr[j]);
-            }
-#pragma unroll
-            for (int u = 0; u < kGroupsPerIter; u++) {
-                const uint32_t i = i0 + 256u * (uint32_t)u;
-                if (hit[u] != 0ull && i < ng && ((hit[u] >> lane) & 1ull)) {       // rare: this lane's group may hold a winner for some query of the tile
-                    const uint32_t g = g0 + i;
-                    const float4 X = reinterpret_cast<const float4 *>(x)[g], Y = reinterpret_cast<const float4 *>(y)[g], Z = reinterpret_cast<const float4 *>(z)[g];
-                    const float xs[4] = { X.x, X.y, X.z, X.w }, ys[4] = { Y.x, Y.y, Y.z, Y.w }, zs[4] = { Z.x, Z.y, Z.z, Z.w };
-#pragma unroll 1
-                    for (int j = 0; j < qcount; j++) {
-                        if (!(group_min_t(pg[u], pp01[u], pp23[u], ax[j], ay[j], az[j]) <= thr[j])) continue;
-                        const int qi = q0 + j;
-                        const double Qx = q64[3 * qi], Qy = q64[3 * qi + 1], Qz = q64[3 * qi + 2];
-                        double bd = __builtin_huge_val();
-                        uint32_t bi = kNoIndex;
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const double d2 = dist2((double)xs[k], (double)ys[k], (double)zs[k], Qx, Qy, Qz);
-                            if (d2 < bd) { bd = d2; bi = 4u * g + (uint32_t)k; }       // ids grow with k: lowest index on ties
-                        }
-                        const uint32_t slot = atomicAdd(&cand_count[qi], 1u);
-                        if (slot < kCandCap) { cand_d2[(size_t)qi * kCandCap + slot] = bd; cand_idx[(size_t)qi * kCandCap + slot] = bi; }
-                    }
-                }
-            }
-        }
-        if (tail_owner) {       // the n % 4 leftover points: always candidates (at most 3 per query)
-            const uint32_t id = 4u * ngroups + threadIdx.x;
-            const double px = (double)x[id], py = (double)y[id], pz = (double)z[id];
-            for (int j = 0; j < qcount; j++) {
-                const int qi = q0 + j;
-                const double d2 = dist2(px, py, pz, q64[3 * qi], q64[3 * qi + 1], q64[3 * qi + 2]);
-                const uint32_t slot = atomicAdd(&cand_count[qi], 1u);
-                if (slot < kCandCap) { cand_d2[(size_t)qi * kCandCap + slot] = d2; cand_idx[(size_t)qi * kCandCap + slot] = id; }
-            }
-        }
-    }
-}
-
-// The same filter with the block's points held in REGISTERS instead of LDS: every thread keeps kRegGroups groups (4 points each,
-// centred, with their |pc|^2) for the whole launch and the query tiles stream past as scalars.  No LDS reads in the loop, |pc|^2
-// computed once per launch instead of once per tile, and occupancy set by registers alone (the LDS form holds 3 blocks per CU).
-// kRegGroups = groups per thread: a block covers 256 * kRegGroups groups (4 -> 4096 points)
-template <bool COUNT, int kRegGroups>
+// The filter with the block's points held in REGISTERS: every thread keeps kRegGroups groups (4 points each, centred, with their
+// |pc|^2) for the whole launch and the query tiles stream past as scalars.  No LDS reads in the loop, |pc|^2 computed once per
+// launch, and occupancy set by registers alone (an LDS-staged form held 3 blocks per CU and measured slower: DESIGN.md, retired
+// variants).  A lane whose group passes a query's threshold evaluates it exactly (fp64, the original coordinates re-read from
+// global memory) and appends (d2, index) to that query's candidate list (COUNT: adds the group's points inside the ball instead).
+// kRegGroups = groups per thread: a block covers 256 * kRegGroups groups (3072 points)
+constexpr int kRegGroups = 3;
+template <bool COUNT>
 __global__ __launch_bounds__(256) void tile_reg_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, uint32_t n,
                                                        CentreDesc C, const float4 *__restrict__ qprep, const double *__restrict__ q64,
                                                        const double *__restrict__ r2, int Q, int qslice, uint32_t *__restrict__ cand_count,

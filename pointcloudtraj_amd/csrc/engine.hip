@@ -163,15 +163,8 @@ struct pct_cloud {
     size_t coarse_cells_cap[kMaxCoarse] = { 0, 0, 0 };
     float4 *coarse_sorted[kMaxCoarse] = { nullptr, nullptr, nullptr };
     size_t coarse_sorted_cap[kMaxCoarse] = { 0, 0, 0 };
-    uint32_t *bin_start = nullptr, *bin_fill = nullptr, *bin_tiles = nullptr;   // query binning (sized at grid build)
-    size_t bins_cap = 0;
-    uint32_t *d_qbin = nullptr, *d_perm = nullptr;                              // sized by reserve_queries
-    float4 *d_qsorted = nullptr;
-    uint32_t *d_inv = nullptr, *d_sres_idx = nullptr;                           // inverse permutation and sorted-order results
-    double *d_sres_d2 = nullptr;
-    float4 *d_sorttmp = nullptr;                                                // {x,y,z,id} records of the two-level sort
-    uint32_t *d_sortkey = nullptr;                                              // their keys
-    uint32_t *d_sort1 = nullptr;                                                // total1 | start1(+1) | fill1 | total1 (second set)
+    float4 *d_qsorted = nullptr;                                                // {x,y,z,id} records of the sorted batch (reserve_queries)
+    uint32_t *d_sort1 = nullptr;                                                // total1 | total1 (second set) | fill1
     int sort_phase = 0;                                                         // which set of totals the next batch adds into
     // query workspaces
     int64_t qcap = 0;
@@ -385,20 +378,16 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G, uint32_t **cell_start, size
     if ((size_t)n > *sorted_cap) {
         dev_free(*sorted);
         *sorted_cap = 0;
-        PCTCHK(dev_alloc(sorted, (size_t)n + kGridPad));         // + the inert records behind the last one (gb_pad_kernel)
+        PCTCHK(dev_alloc(sorted, (size_t)n + kGridPad));         // + spare records behind the last one (gridbuild.hpp)
         *sorted_cap = (size_t)n;
     }
-#ifdef PCT_AB_OPEN_STAGE0
-    gb_pad_kernel<<<1, 64, 0, s>>>(*sorted + n);                  // only the open-ended stage 0 reads behind the last record
-#endif
     // ---- two-level counting sort on LDS histograms (gridbuild.hpp): no device-scope atomic per point ----
-    static const bool lds_build = [] { const char *e = std::getenv("PCT_LDS_GRID_BUILD"); return e ? std::atoi(e) != 0 : true; }();
     // slabs of 2^s1 consecutive cells, sized for ~2-6 k points each (level 2 then holds a whole slab in LDS), at most kGbMaxSlabs;
     // more, smaller slabs make level 1 slower (more open write streams, more LDS per block) faster than they help level 2
     const uint64_t want_slabs = std::min<uint64_t>((uint64_t)kGbMaxSlabs, std::max<uint64_t>(64, (uint64_t)n / 2048));
     int s1 = 0;
     while (((ncells + (1ull << s1) - 1) >> s1) > want_slabs) s1++;
-    if (lds_build && n >= 4096 && (1u << s1) <= (uint32_t)kGbMaxSlabCells && (uint64_t)n < 0xFFFFFFF0ull) {
+    if (n >= 4096 && (1u << s1) <= (uint32_t)kGbMaxSlabCells && (uint64_t)n < 0xFFFFFFF0ull) {
         GbDesc D{};
         D.s1 = s1;
         D.nslabs = (uint32_t)((ncells + (1ull << s1) - 1) >> s1);
@@ -406,12 +395,11 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G, uint32_t **cell_start, size
         D.chunk = (uint32_t)((((n + nblk - 1) / nblk) + 3) & ~3ll);
         const int blocks = (int)((n + D.chunk - 1) / D.chunk);
         // level-2 block size by the mean slab: a block holds up to 8 records per thread in LDS (larger slabs stream through twice)
-        static const int stage_on = [] { const char *e = std::getenv("PCT_GB_STAGE"); return e ? std::atoi(e) : 1; }();
         const double mean_slab = (double)n / D.nslabs;
         const int cthreads = mean_slab <= 1400 ? 256 : mean_slab <= 3000 ? 512 : 1024;
         const size_t lds1 = sizeof(uint32_t) * ((size_t)D.nslabs + 1);
         const size_t lds_cnt = sizeof(uint32_t) * ((((size_t)1 << s1) + 1 + 3) & ~(size_t)3);
-        const uint32_t stage_cap = stage_on ? (uint32_t)std::min<size_t>((size_t)kGbStagePerThread * cthreads, (150 * 1024 - lds_cnt) / sizeof(float4)) : 0u;
+        const uint32_t stage_cap = (uint32_t)std::min<size_t>((size_t)kGbStagePerThread * cthreads, (150 * 1024 - lds_cnt) / sizeof(float4));
         const size_t lds2 = lds_cnt + sizeof(float4) * stage_cap;
         static bool attr = false;
         if (!attr) {      // more than the default 64 KiB of LDS per block (gfx950: 160 KiB per CU)
@@ -438,10 +426,9 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G, uint32_t **cell_start, size
         }
         // level 1 in two passes of fan-out <= 128 when there are many slabs (gridbuild.hpp): pass A sorts by super-slab into the final
         // array (unused until level 2 writes it), pass B by slab inside every super-slab's region into gb_tmp
-        static const bool two_pass_on = [] { const char *e = std::getenv("PCT_GB_TWO_PASS"); return e ? std::atoi(e) != 0 : true; }();
         uint32_t two_pass_min = 4096;                 // read per build: the tests lower it to reach this path with small clouds
         if (const char *e = std::getenv("PCT_GB_TWO_PASS_MIN_SLABS")) two_pass_min = (uint32_t)std::max(2, std::atoi(e));
-        if (two_pass_on && D.nslabs >= two_pass_min) {
+        if (D.nslabs >= two_pass_min) {
             Gb2Desc DB{};
             DB.s1 = s1;
             int lg = 0;
@@ -732,103 +719,39 @@ int nn_stream_q64(pct_cloud *c, int64_t Q, uint32_t *d_idx, double *d_d2, hipStr
     return PCT_OK;
 }
 
-bool lds_sort_on()
+// counting sort of the batch by coarse cell (kernels.hpp qsort_*) -> c->d_qsorted; *recs_out = nullptr: small batch, arrival order
+int bin_queries(pct_cloud *c, const float *d_q, int64_t Q, hipStream_t s, const float4 **recs_out)
 {
-    static const bool v = [] { const char *e = std::getenv("PCT_LDS_SORT"); return e ? std::atoi(e) != 0 : true; }();
-    return v;
-}
-
-// counting sort of the batch by coarse cell -> c->d_perm (nullptr result = keep arrival order)
-// need_perm / need_inv: the 8-lanes-per-query kernels read the sorted records only; the lane-per-query kernels read perm, the
-// sorted-result gather reads inv -- 4 B per query of scattered (perm) or streamed (inv) writes that the default path does not pay
-int bin_queries(pct_cloud *c, const float *d_q, int64_t Q, hipStream_t s, const uint32_t **perm_out, bool need_perm = true, bool need_inv = false)
-{
-    *perm_out = nullptr;
-    int64_t min_q = 16384;
-    if (const char *e = std::getenv("PCT_SORT_MIN_Q")) min_q = std::atoll(e);
-    if (Q < min_q) return PCT_OK;
+    *recs_out = nullptr;
+    if (Q < 16384) return PCT_OK;
     const BinDesc &B = c->B;
-    if (lds_sort_on()) {
-        // two-level counting sort on LDS histograms (kernels.hpp)
-        int key_shift = 0;
-        while ((((uint64_t)B.nbins - 1) >> key_shift) >= (1ull << 20)) key_shift++;
-        // two sets of bucket totals used in turn: a batch's histogram pass zeroes the set the NEXT batch will add into (a captured
-        // graph replays one set, so it keeps the memset behind its scatter pass instead)
-        static const bool pingpong_on = [] { const char *e = std::getenv("PCT_SORT_PINGPONG"); return e ? std::atoi(e) != 0 : true; }();
-        const bool pingpong = pingpong_on && !c->capturing;
-        uint32_t *total1 = c->d_sort1 + (c->sort_phase ? 3 * kSortBuckets + 8 : 0), *start1 = c->d_sort1 + kSortBuckets, *fill1 = c->d_sort1 + 2 * kSortBuckets + 4;
-        uint32_t *total1_next = c->d_sort1 + (c->sort_phase ? 0 : 3 * kSortBuckets + 8);
-        // PCT_SORT_LEVELS: 1 (default) = one counting pass into <= 1024 spatial buckets, queries left in arrival order inside a
-        // bucket; 2 = a second pass orders every bucket by the remaining key bits.  With the block-first search the finer order
-        // no longer pays for its pass (same-box: 0.198-0.204 ms per step with it, 0.168 without).
-        static const int levels = [] { const char *e = std::getenv("PCT_SORT_LEVELS"); return e ? std::max(1, std::min(2, std::atoi(e))) : 1; }();
-        int lshift = 10;                         // level-1 bucket = key >> 10 (keys < 2^20): finer buckets (key >> 8, >> 9) measured the same
-        if (const char *e = std::getenv("PCT_SORT_LSHIFT")) {           // tuning, single-level mode: finer or coarser buckets (always <= 1024 of them)
-            lshift = std::max(0, std::atoi(e));
-            while (((((uint64_t)B.nbins - 1) >> key_shift) >> lshift) >= (uint64_t)kSortBuckets) lshift++;
-        }
-        static const int per_block_env = [] { const char *e = std::getenv("PCT_SORT_PER_BLOCK"); return e ? std::min(kSortPerBlock, std::max(1024, std::atoi(e) / 1024 * 1024)) : 0; }();
-        // ~128 blocks: small batches want parallelism (64 K queries: 21 us at 1024 per block, 36 us at 8192), large ones
-        // want long per-block bucket slices (1 M: 67 us at 8192, 87 us at 1024)
-        const uint32_t per_block = per_block_env ? (uint32_t)per_block_env
-                                                 : (uint32_t)std::min<int64_t>(kSortPerBlock, std::max<int64_t>(1024, (Q / 128 + 1023) / 1024 * 1024));
-        const int nb = ceil_div(Q, (int64_t)per_block);
-        // the key array costs 4 B per query written by one pass and read by the next: the scatter pass recomputes keys instead
-        static const bool store_keys = [] { const char *e = std::getenv("PCT_SORT_STORE_KEYS"); return e ? std::atoi(e) != 0 : false; }();
-        uint32_t *keys = store_keys ? c->d_qbin : nullptr;
-        // the histogram pass only adds into the global totals, so it can use shorter slices than the scatter pass (whose writes want
-        // long per-block runs); more blocks measured SLOWER though (PCT_SORT_HIST_DIV = 1 / 2 / 4 / 8: 0.165 / 0.167 / 0.169 / 0.179 ms
-        // per step, same box), so the default keeps one slice size for both
-        static const int hist_div = [] { const char *e = std::getenv("PCT_SORT_HIST_DIV"); return e ? std::max(1, std::min(8, std::atoi(e))) : 1; }();
-        const uint32_t hist_per_block = std::max<uint32_t>(1024u, (per_block / (uint32_t)hist_div) / 1024u * 1024u);
-        // 16-byte aligned query arrays are fetched four queries (three float4) at a time (kernels.hpp sort_load_items)
-        static const bool vec_on = [] { const char *e = std::getenv("PCT_SORT_VEC"); return e ? std::atoi(e) != 0 : true; }();
-        const bool vec = vec_on && (reinterpret_cast<uintptr_t>(d_q) & 15u) == 0;
-        if (vec) qsort_hist_kernel<true><<<ceil_div(Q, (int64_t)hist_per_block), 1024, 0, s>>>(c->G, B, key_shift, lshift, d_q, (uint32_t)Q, hist_per_block, keys, total1, fill1,
-                                                                                             pingpong ? total1_next : nullptr);
-        else qsort_hist_kernel<false><<<ceil_div(Q, (int64_t)hist_per_block), 1024, 0, s>>>(c->G, B, key_shift, lshift, d_q, (uint32_t)Q, hist_per_block, keys, total1, fill1,
-                                                                                           pingpong ? total1_next : nullptr);
-        if (levels == 1) {
-            if (vec) qsort_scatter1_kernel<true><<<nb, 1024, 0, s>>>(c->G, B, key_shift, keys, d_q, (uint32_t)Q, per_block, lshift, total1, fill1, start1, c->d_sortkey, c->d_qsorted, need_perm ? c->d_perm : nullptr,
-                                                                    need_inv ? c->d_inv : nullptr, 1);
-            else qsort_scatter1_kernel<false><<<nb, 1024, 0, s>>>(c->G, B, key_shift, keys, d_q, (uint32_t)Q, per_block, lshift, total1, fill1, start1, c->d_sortkey, c->d_qsorted, need_perm ? c->d_perm : nullptr,
-                                                      need_inv ? c->d_inv : nullptr, 1);
-            if (pingpong) c->sort_phase ^= 1;
-            else HIPCHK(hipMemsetAsync(total1, 0, sizeof(uint32_t) * kSortBuckets, s));   // the fine pass would have re-zeroed it
-        } else {
-            qsort_scatter1_kernel<false><<<nb, 1024, 0, s>>>(c->G, B, key_shift, keys, d_q, (uint32_t)Q, per_block, lshift, total1, fill1, start1, c->d_sortkey, c->d_sorttmp, nullptr, nullptr, 0);
-            qsort_fine_kernel<<<kSortBuckets, kFineThreads, 0, s>>>(c->d_sortkey, c->d_sorttmp, start1, total1, (1u << lshift) - 1u, need_perm ? c->d_perm : nullptr,
-                                                                    c->d_qsorted, need_inv ? c->d_inv : nullptr);
-        }
-        HIPCHK(hipGetLastError());
-        *perm_out = c->d_perm;
-        return PCT_OK;
+    int key_shift = 0;
+    while ((((uint64_t)B.nbins - 1) >> key_shift) >= (1ull << 20)) key_shift++;
+    // two sets of bucket totals used in turn: a batch's histogram pass zeroes the set the NEXT batch will add into (a captured
+    // graph replays one set, so it keeps the memset behind its scatter pass instead)
+    const bool pingpong = !c->capturing;
+    uint32_t *total1 = c->d_sort1 + (c->sort_phase ? kSortBuckets : 0), *total1_next = c->d_sort1 + (c->sort_phase ? 0 : kSortBuckets);
+    uint32_t *fill1 = c->d_sort1 + 2 * kSortBuckets;
+    // ~128 blocks: small batches want parallelism (64 K queries: 21 us at 1024 per block, 36 us at 8192), large ones
+    // want long per-block bucket slices (1 M: 67 us at 8192, 87 us at 1024)
+    const uint32_t per_block = (uint32_t)std::min<int64_t>(kSortPerBlock, std::max<int64_t>(1024, (Q / 128 + 1023) / 1024 * 1024));
+    const int nb = ceil_div(Q, (int64_t)per_block);
+    // 16-byte aligned query arrays are fetched four queries (three float4) at a time (kernels.hpp sort_load_items)
+    if ((reinterpret_cast<uintptr_t>(d_q) & 15u) == 0) {
+        qsort_hist_kernel<true><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, pingpong ? total1_next : nullptr);
+        qsort_scatter1_kernel<true><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, c->d_qsorted);
+    } else {
+        qsort_hist_kernel<false><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, pingpong ? total1_next : nullptr);
+        qsort_scatter1_kernel<false><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, c->d_qsorted);
     }
-    const uint32_t ntiles = (B.nbins + kScanTile - 1) / kScanTile;
-    HIPCHK(hipMemsetAsync(c->bin_fill, 0, sizeof(uint32_t) * B.nbins, s));
-    query_bin_count_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(c->G, B, d_q, (uint32_t)Q, c->bin_fill, c->d_qbin);
-    scan_tiles_kernel<<<ntiles, 256, 0, s>>>(c->bin_fill, B.nbins, c->bin_start, c->bin_tiles);
-    scan_tile_sums_kernel<<<1, 256, 0, s>>>(c->bin_tiles, ntiles);
-    scan_add_kernel<<<ceil_div(B.nbins, 256), 256, 0, s>>>(c->bin_start, B.nbins, c->bin_tiles, (uint32_t)Q);
-    HIPCHK(hipMemsetAsync(c->bin_fill, 0, sizeof(uint32_t) * B.nbins, s));
-    query_bin_scatter_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(c->d_qbin, (uint32_t)Q, c->bin_start, c->bin_fill, d_q, c->d_perm, c->d_qsorted);
+    if (pingpong) c->sort_phase ^= 1;
+    else HIPCHK(hipMemsetAsync(total1, 0, sizeof(uint32_t) * kSortBuckets, s));
     HIPCHK(hipGetLastError());
-    *perm_out = c->d_perm;
+    *recs_out = c->d_qsorted;
     return PCT_OK;
 }
 
-int g_filter_mode = -2;        // -2 = not read yet
-int filter_mode()
-{
-    if (g_filter_mode == -2) { const char *e = std::getenv("PCT_TILE_EXPANDED"); g_filter_mode = e ? std::atoi(e) : -1; }
-    return g_filter_mode;
-}
-
-int reg_groups()
-{
-    static const int v = [] { const char *e = std::getenv("PCT_TILE_REG_GROUPS"); const int g = e ? std::atoi(e) : 3; return (g == 2 || g == 4 || g == 6) ? g : 3; }();
-    return v;
-}
+int g_filter_mode = -1;        // pct_debug_set_filter_mode: 0 = never, 1 = whenever valid, -1 = auto
 
 // bounding box of the cloud's current contents, cached per contents version (one reduction + one read-back when stale)
 int cloud_bbox_cached(pct_cloud *c)
@@ -858,7 +781,7 @@ int cloud_bbox_cached(pct_cloud *c)
 // the sampled bound, decides how many pairs pass.  Fills the centre / R^2 the kernels need.
 bool use_expanded_filter(pct_cloud *c, CentreDesc *out)
 {
-    const int mode = filter_mode();                              // 0 = never, 1 = whenever valid, -1 = auto
+    const int mode = g_filter_mode;
     if (mode == 0 || c->host_mapped || c->capturing || c->count < 4) return false;
     if (mode < 0 && c->count < 200000) return false;             // small clouds: the bounding-box pass would cost more than it saves
     if (cloud_bbox_cached(c) != PCT_OK) return false;
@@ -883,8 +806,9 @@ bool use_expanded_filter(pct_cloud *c, CentreDesc *out)
 constexpr int kMaxTileParts = 8192;      // tile kernel: at most this many point chunks per launch
 constexpr uint32_t kChunkGroupsMax = 3072;   // 3 * 3072 * 16 B = 144 KiB of the CU's 160 KiB LDS
 
-// Default brute-force path: packed-fp32 filter + exact fp64 recheck over LDS-staged chunks
-// (kernels.hpp).  d_qf: the fp32 queries; c->d_q64 must already hold their widened copies.
+// Default brute-force path: sampled fp32 bound, packed-fp32 filter (expanded form in registers, brute2.hpp, or direct form over
+// LDS-staged chunks, kernels.hpp) + exact fp64 recheck of the survivors.  d_qf: the fp32 queries; c->d_q64 must already hold
+// their widened copies.
 int nn_stream_filtered_slice(pct_cloud *c, const float *d_qf, int64_t qoff, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
 {
     d_qf += 3 * qoff;
@@ -892,16 +816,9 @@ int nn_stream_filtered_slice(pct_cloud *c, const float *d_qf, int64_t qoff, int6
     d_d2 += qoff;
     const double *d_q64 = c->d_q64 + 3 * qoff;
     uint32_t *d_bound = c->d_bound + qoff;
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_tile_filter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(3 * kChunkGroupsMax * sizeof(float4))));
-        attr_set = true;
-    }
     const int64_t ngroups = c->count >> 2;
     // chunk = 1024 groups (4096 points, 48 KiB LDS -> 3 blocks per CU); larger only for huge clouds
     uint32_t chunk = 1024;
-    if (const char *e = std::getenv("PCT_TILE_CHUNK")) chunk = (uint32_t)std::max(256, std::min((int)kChunkGroupsMax, std::atoi(e)));
     if ((ngroups + chunk - 1) / chunk > kMaxTileParts) chunk = (uint32_t)std::min<int64_t>(kChunkGroupsMax, ((ngroups + kMaxTileParts - 1) / kMaxTileParts + 255) / 256 * 256);
     const int nblocks = (int)std::max<int64_t>(1, (ngroups + chunk - 1) / chunk);
     if (nblocks > kMaxTileParts) return fail(PCT_ERR_INVALID, "cloud of %lld points is too large for the brute-force path", (long long)c->count);
@@ -911,7 +828,6 @@ int nn_stream_filtered_slice(pct_cloud *c, const float *d_qf, int64_t qoff, int6
                                 : 1u;
     const int64_t schunks = std::max<int64_t>(1, (ngroups + 256ll * stride - 1) / (256ll * stride));
     const int sblocks = (int)((schunks + kSampleGroups - 1) / kSampleGroups);
-    const int64_t part_cap = c->part_q * kMaxParts;        // entries in d_part_d2 / d_part_idx
     begin_timing(c, s);
     // the sample partials borrow d_part_idx (u32 and float have the same size; [Q][sblocks], sblocks <= kMaxParts);
     // bound_reduce_kernel consumes them before the filter pass overwrites the buffer
@@ -927,62 +843,25 @@ int nn_stream_filtered_slice(pct_cloud *c, const float *d_qf, int64_t qoff, int6
     nn_sample_bounds_kernel<<<dim3(sblocks, sslices), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, stride, d_qf, (int)Q, sq,
                                                                    reinterpret_cast<float *>(c->d_part_idx), sblocks);
     bound_reduce_kernel<<<(int)Q, 256, 0, s>>>(reinterpret_cast<const float *>(c->d_part_idx), sblocks, d_bound);
-    static const bool candidates = [] { const char *e = std::getenv("PCT_TILE_CANDIDATES"); return e ? std::atoi(e) != 0 : true; }();
     CentreDesc CD{};
-    if (candidates && use_expanded_filter(c, &CD)) {
-        // expanded form (brute2.hpp): 3 FMAs per pair on centred coordinates, thresholds widened by the proven error band
-        static const int gpi = [] { const char *e = std::getenv("PCT_TILE_GROUPS"); return e ? std::atoi(e) : 2; }();
-        static bool attr3 = false;
-        if (!attr3) {
-            const int lds = (int)(3 * kChunkGroupsMax * sizeof(float4));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_tile_candidates2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_tile_candidates2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_tile_candidates2_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            attr3 = true;
-        }
+    if (use_expanded_filter(c, &CD)) {
+        // expanded form (brute2.hpp): 3 FMAs per pair on centred coordinates, thresholds widened by the proven error band; the points
+        // held in registers (tile_reg_kernel), a block covers 256 * kRegGroups point groups, no LDS
         float4 *qprep = c->d_qsorted + qoff;                     // the query-sort records are idle on this path
         brute2_prep_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(CD, d_qf, d_bound, (uint32_t)Q, qprep);
         dom_begin(c, s);
-        int cq = 0;
-        const int cslices = slices_for(nblocks, &cq);
-        const dim3 grid(nblocks, cslices);
-        const size_t lds = 3 * (size_t)chunk * sizeof(float4);
-        static const bool reg_points = [] { const char *e = std::getenv("PCT_TILE_REG"); return e ? std::atoi(e) != 0 : true; }();
-        if (reg_points) {       // points held in registers (brute2.hpp tile_reg_kernel): a block covers 4096 points, no LDS
-            const int rg = reg_groups();
-            const int rblocks = (int)std::max<int64_t>(1, (ngroups + 256 * rg - 1) / (256 * rg));
-            int rq = 0;
-            const int rslices = slices_for(rblocks, &rq);
-            const dim3 rgrid(rblocks, rslices);
-            switch (rg) {
-            case 2: tile_reg_kernel<false, 2><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, qprep, d_q64, nullptr, (int)Q, rq, c->d_cand_count, c->d_cand_d2, c->d_cand_idx, nullptr); break;
-            case 4: tile_reg_kernel<false, 4><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, qprep, d_q64, nullptr, (int)Q, rq, c->d_cand_count, c->d_cand_d2, c->d_cand_idx, nullptr); break;
-            case 6: tile_reg_kernel<false, 6><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, qprep, d_q64, nullptr, (int)Q, rq, c->d_cand_count, c->d_cand_d2, c->d_cand_idx, nullptr); break;
-            default: tile_reg_kernel<false, 3><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, qprep, d_q64, nullptr, (int)Q, rq, c->d_cand_count, c->d_cand_d2, c->d_cand_idx, nullptr); break;
-            }
-        } else if (gpi == 1)
-            nn_tile_candidates2_kernel<1><<<grid, 256, lds, s>>>(c->x, c->y, c->z, (uint32_t)c->count, chunk, CD, qprep, d_q64, (int)Q, cq, c->d_cand_count, c->d_cand_d2, c->d_cand_idx);
-        else if (gpi == 4)
-            nn_tile_candidates2_kernel<4><<<grid, 256, lds, s>>>(c->x, c->y, c->z, (uint32_t)c->count, chunk, CD, qprep, d_q64, (int)Q, cq, c->d_cand_count, c->d_cand_d2, c->d_cand_idx);
-        else
-            nn_tile_candidates2_kernel<2><<<grid, 256, lds, s>>>(c->x, c->y, c->z, (uint32_t)c->count, chunk, CD, qprep, d_q64, (int)Q, cq, c->d_cand_count, c->d_cand_d2, c->d_cand_idx);
-        dom_end(c, s);
-        HIPCHK(hipMemsetAsync(c->d_ovf, 0, sizeof(uint32_t), s));
-        nn_reduce_candidates_kernel<<<(int)Q, 256, 0, s>>>(c->d_cand_count, c->d_cand_d2, c->d_cand_idx, (uint32_t)c->index_base, c->d_ovf, d_idx, d_d2);
-        nn_overflow_scan_kernel<<<kOvfBlocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q64, c->d_ovf, c->d_part_d2, c->d_part_idx);
-        nn_overflow_fold_kernel<<<(int)Q, 256, 0, s>>>(c->d_ovf, c->d_part_d2, c->d_part_idx, kOvfBlocks, (uint32_t)c->index_base, d_idx, d_d2);
-        end_timing(c, s);
-        HIPCHK(hipGetLastError());
-        c->host_work = true;
-        c->host_points = (uint64_t)Q * (uint64_t)c->count;
-        return PCT_OK;
-    }
-    if (candidates) {       // survivors of the bound go to per-query candidate lists: no per-tile block reductions, no partial arrays
-        static bool attr2 = false;
-        if (!attr2) {
+        const int rblocks = (int)std::max<int64_t>(1, (ngroups + 256 * kRegGroups - 1) / (256 * kRegGroups));
+        int rq = 0;
+        const int rslices = slices_for(rblocks, &rq);
+        tile_reg_kernel<false><<<dim3(rblocks, rslices), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, qprep, d_q64, nullptr, (int)Q, rq,
+                                                                       c->d_cand_count, c->d_cand_d2, c->d_cand_idx, nullptr);
+    } else {
+        // survivors of the bound go to per-query candidate lists: no per-tile block reductions, no partial arrays
+        static bool attr = false;
+        if (!attr) {
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_tile_candidates_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)(3 * kChunkGroupsMax * sizeof(float4))));
-            attr2 = true;
+            attr = true;
         }
         dom_begin(c, s);
         int cq = 0;
@@ -990,27 +869,13 @@ int nn_stream_filtered_slice(pct_cloud *c, const float *d_qf, int64_t qoff, int6
         nn_tile_candidates_kernel<<<dim3(nblocks, cslices), 256, 3 * (size_t)chunk * sizeof(float4), s>>>(c->x, c->y, c->z, (uint32_t)c->count, chunk, d_qf,
                                                                                                           d_q64, d_bound, (int)Q, cq, c->d_cand_count,
                                                                                                           c->d_cand_d2, c->d_cand_idx);
-        dom_end(c, s);
-        HIPCHK(hipMemsetAsync(c->d_ovf, 0, sizeof(uint32_t), s));
-        nn_reduce_candidates_kernel<<<(int)Q, 256, 0, s>>>(c->d_cand_count, c->d_cand_d2, c->d_cand_idx, (uint32_t)c->index_base, c->d_ovf, d_idx, d_d2);
-        // overflowed lists (bulk exact ties): exact scan by the whole grid; both kernels return at once when there are none
-        nn_overflow_scan_kernel<<<kOvfBlocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q64, c->d_ovf, c->d_part_d2, c->d_part_idx);
-        nn_overflow_fold_kernel<<<(int)Q, 256, 0, s>>>(c->d_ovf, c->d_part_d2, c->d_part_idx, kOvfBlocks, (uint32_t)c->index_base, d_idx, d_d2);
-        end_timing(c, s);
-        HIPCHK(hipGetLastError());
-        c->host_work = true;
-        c->host_points = (uint64_t)Q * (uint64_t)c->count;
-        return PCT_OK;
     }
-    const int64_t qb_max = std::max<int64_t>(kTileQ, part_cap / nblocks / kTileQ * kTileQ);
-    for (int64_t qbase = 0; qbase < Q; qbase += qb_max) {
-        const int qb = (int)std::min<int64_t>(qb_max, Q - qbase);
-        if (qbase == 0) dom_begin(c, s);
-        nn_tile_filter_kernel<<<nblocks, 256, 3 * (size_t)chunk * sizeof(float4), s>>>(c->x, c->y, c->z, (uint32_t)c->count, chunk, d_qf, d_q64,
-                                                                                       d_bound, (int)qbase, qb, c->d_part_d2, c->d_part_idx, nblocks);
-        if (qbase == 0) dom_end(c, s);
-        nn_reduce_partials_kernel<<<qb, 256, 0, s>>>(c->d_part_d2, c->d_part_idx, nblocks, (uint32_t)c->index_base, d_idx + qbase, d_d2 + qbase);
-    }
+    dom_end(c, s);
+    HIPCHK(hipMemsetAsync(c->d_ovf, 0, sizeof(uint32_t), s));
+    nn_reduce_candidates_kernel<<<(int)Q, 256, 0, s>>>(c->d_cand_count, c->d_cand_d2, c->d_cand_idx, (uint32_t)c->index_base, c->d_ovf, d_idx, d_d2);
+    // overflowed lists (bulk exact ties): exact scan by the whole grid; both kernels return at once when there are none
+    nn_overflow_scan_kernel<<<kOvfBlocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q64, c->d_ovf, c->d_part_d2, c->d_part_idx);
+    nn_overflow_fold_kernel<<<(int)Q, 256, 0, s>>>(c->d_ovf, c->d_part_d2, c->d_part_idx, kOvfBlocks, (uint32_t)c->index_base, d_idx, d_d2);
     end_timing(c, s);
     HIPCHK(hipGetLastError());
     c->host_work = true;
@@ -1044,77 +909,35 @@ int nn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, uint32_t *d_idx,
         c->host_work = false;
         if (c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
         begin_timing(c, s);
-        const uint32_t *perm = nullptr;
-        static const bool coop = [] { const char *e = std::getenv("PCT_GRID_COOP"); return e ? std::atoi(e) != 0 : true; }();
-        static const bool sorted_writes_on = [] { const char *e = std::getenv("PCT_SORTED_WRITES"); return e ? std::atoi(e) != 0 : false; }();
-        PCTCHK(bin_queries(c, d_q, Q, s, &perm, !coop, coop && sorted_writes_on));
-        dom_begin(c, s, coop && !c->count_work);
-        if (coop) {   // 8 lanes per query (default)
-            const int blocks = ceil_div(Q, 256 / kCoop);
-            // sorted batches: the kernel writes its results in sorted order (full lines) and one gather pass puts them back into
-            // arrival order -- scattering 4 + 8 bytes per query from here cost 5.6x the result bytes in fabric writes
-            static const bool sorted_writes = [] { const char *e = std::getenv("PCT_SORTED_WRITES"); return e ? std::atoi(e) != 0 : false; }();
-            const bool so = perm != nullptr && sorted_writes && lds_sort_on();
-            uint32_t *k_idx = so ? c->d_sres_idx : d_idx;
-            double *k_d2 = so ? c->d_sres_d2 : d_d2;
-            // wave-cooperative fallback for the queries the 2x2x2 block leaves undecided (kernels.hpp, default) or the 8-lane cube
-            static const bool wave_cube = [] { const char *e = std::getenv("PCT_COOP_WAVE_CUBE"); return e ? std::atoi(e) != 0 : true; }();
-            const float4 *recs = perm ? c->d_qsorted : nullptr;
-            if (c->has_pyr) {     // sparse occupancy: stage 0, then the bounding-box pyramid instead of cube + shells (pyramid.hpp)
-                // fp32 walk for everybody, then the exact walk for the (few) queries it lists as undecided; PCT_PYRAMID_EXACT=1:
-                // the exact walk for everybody (tests)
-                static const bool exact_only = [] { const char *e = std::getenv("PCT_PYRAMID_EXACT"); return e ? std::atoi(e) != 0 : false; }();
-                const int so_i = so ? 1 : 0;
-                if (exact_only) {
-                    if (c->count_work)
-                        nn_grid_pyr_kernel<true, false><<<blocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so_i, nullptr);
-                    else
-                        nn_grid_pyr_kernel<false, false><<<blocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so_i, nullptr);
-                } else {
-                    if (c->count_work)
-                        nn_grid_pyr_kernel<true, true><<<blocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so_i, c->d_todo);
-                    else if (c->dom_valid && dom_ext_on()) {
-                        hipExtLaunchKernelGGL((nn_grid_pyr_kernel<false, true>), dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q,
-                                              (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so_i, c->d_todo);
-                        dom_done(c);
-                    } else
-                        nn_grid_pyr_kernel<false, true><<<blocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so_i, c->d_todo);
-                    const int tblocks = (int)std::min<int64_t>(256, blocks);
-                    if (c->count_work)
-                        nn_grid_pyr_todo_kernel<true><<<tblocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so_i, c->d_todo);
-                    else
-                        nn_grid_pyr_todo_kernel<false><<<tblocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so_i, c->d_todo);
-                }
-            } else if (c->count_work) {
-                if (wave_cube) nn_grid_coop_kernel<true, true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so ? 1 : 0);
-                else nn_grid_coop_kernel<true, false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so ? 1 : 0);
-            } else if (c->dom_valid && dom_ext_on()) {
-                // the kernel's own begin / end timestamps (hipExtLaunchKernel): no marker packets on the stream -- the two
-                // hipEventRecord calls of dom_begin / dom_end cost ~10 us of a 160 us step
-                if (wave_cube)
-                    hipExtLaunchKernelGGL((nn_grid_coop_kernel<false, true>), dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, c->G, c->sorted, c->cell_start, d_q,
-                                          (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so ? 1 : 0);
-                else
-                    hipExtLaunchKernelGGL((nn_grid_coop_kernel<false, false>), dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, c->G, c->sorted, c->cell_start, d_q,
-                                          (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so ? 1 : 0);
+        const float4 *recs = nullptr;
+        PCTCHK(bin_queries(c, d_q, Q, s, &recs));
+        dom_begin(c, s, !c->count_work);
+        const int blocks = ceil_div(Q, 256 / kCoop);      // 8 lanes per query
+        if (c->has_pyr) {     // sparse occupancy: stage 0, then the bounding-box pyramid instead of cube + shells (pyramid.hpp)
+            // fp32 walk for everybody, then the exact walk for the (few) queries it lists as undecided
+            if (c->count_work)
+                nn_grid_pyr_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
+            else if (c->dom_valid && dom_ext_on()) {
+                hipExtLaunchKernelGGL((nn_grid_pyr_kernel<false>), dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q,
+                                      (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
                 dom_done(c);
-            } else if (wave_cube)
-                nn_grid_coop_kernel<false, true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so ? 1 : 0);
+            } else
+                nn_grid_pyr_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
+            const int tblocks = (int)std::min<int64_t>(256, blocks);
+            if (c->count_work)
+                nn_grid_pyr_todo_kernel<true><<<tblocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
             else
-                nn_grid_coop_kernel<false, false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, k_idx, k_d2, c->d_work, so ? 1 : 0);
-            if (so) {
-                dom_end(c, s);
-                unpermute_results_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(c->d_inv, c->d_sres_idx, c->d_sres_d2, (uint32_t)Q, d_idx, d_d2);
-                end_timing(c, s);
-                HIPCHK(hipGetLastError());
-                return PCT_OK;
-            }
-        } else if (c->count_work)
-            nn_grid_kernel<true><<<ceil_div(Q, 256), 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q,
-                                                                   (uint32_t)c->index_base, perm, d_idx, d_d2, c->d_work);
-        else
-            nn_grid_kernel<false><<<ceil_div(Q, 256), 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q,
-                                                                    (uint32_t)c->index_base, perm, d_idx, d_d2, c->d_work);
+                nn_grid_pyr_todo_kernel<false><<<tblocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
+        } else if (c->count_work) {
+            nn_grid_coop_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
+        } else if (c->dom_valid && dom_ext_on()) {
+            // the kernel's own begin / end timestamps (hipExtLaunchKernel): no marker packets on the stream -- the two
+            // hipEventRecord calls of dom_begin / dom_end cost ~10 us of a 160 us step
+            hipExtLaunchKernelGGL((nn_grid_coop_kernel<false>), dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, c->G, c->sorted, c->cell_start, d_q,
+                                  (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
+            dom_done(c);
+        } else
+            nn_grid_coop_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
         dom_end(c, s);
         end_timing(c, s);
         HIPCHK(hipGetLastError());
@@ -1124,8 +947,7 @@ int nn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, uint32_t *d_idx,
     widen_queries_kernel<<<ceil_div(3 * Q, 256), 256, 0, s>>>(d_q, (uint32_t)(3 * Q), c->d_q64);
     // <= 4 queries: the all-fp64 kernel is already HBM-bound (50-62 % of peak); beyond that the
     // packed-fp32 filter wins
-    static const int64_t exact_max_q = [] { const char *e = std::getenv("PCT_EXACT_MAX_Q"); return e ? std::atoll(e) : 4ll; }();
-    if (algo == PCT_ALGO_STREAM_EXACT || Q <= exact_max_q) return nn_stream_q64(c, Q, d_idx, d_d2, s);
+    if (algo == PCT_ALGO_STREAM_EXACT || Q <= 4) return nn_stream_q64(c, Q, d_idx, d_d2, s);
     return nn_stream_filtered(c, d_q, Q, d_idx, d_d2, s);
 }
 
@@ -1141,21 +963,14 @@ int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_
         c->host_work = false;
         if (c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
         begin_timing(c, s);
-        const uint32_t *perm = nullptr;
-        static const bool coop = [] { const char *e = std::getenv("PCT_GRID_COOP"); return e ? std::atoi(e) != 0 : true; }();
-        PCTCHK(bin_queries(c, d_q, Q, s, &perm, !coop, false));
-        dom_begin(c, s, coop && !c->count_work);
-        if (coop) {   // 8 lanes per query (default)
-            const int blocks = ceil_div(Q, 256 / kCoop);
-            const float4 *qs = perm ? c->d_qsorted : nullptr;
-            if (c->count_work)
-                count_grid_coop_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, qs, d_count, c->d_work);
-            else
-                count_grid_coop_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, qs, d_count, c->d_work);
-        } else if (c->count_work)
-            count_grid_kernel<true><<<ceil_div(Q, 256), 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, perm, d_count, c->d_work);
+        const float4 *qs = nullptr;
+        PCTCHK(bin_queries(c, d_q, Q, s, &qs));
+        dom_begin(c, s, !c->count_work);
+        const int blocks = ceil_div(Q, 256 / kCoop);      // 8 lanes per query
+        if (c->count_work)
+            count_grid_coop_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, qs, d_count, c->d_work);
         else
-            count_grid_kernel<false><<<ceil_div(Q, 256), 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, perm, d_count, c->d_work);
+            count_grid_coop_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, qs, d_count, c->d_work);
         dom_end(c, s);
         end_timing(c, s);
         HIPCHK(hipGetLastError());
@@ -1164,12 +979,10 @@ int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_
     if (algo != PCT_ALGO_STREAM) return fail(PCT_ERR_INVALID, "unknown algo %d", algo);
     widen_queries_kernel<<<ceil_div(3 * Q, 256), 256, 0, s>>>(d_q, (uint32_t)(3 * Q), c->d_q64);
     CentreDesc CD{};
-    static const int64_t count_filter_min_q = [] { const char *e = std::getenv("PCT_COUNT_FILTER_MIN_Q"); return e ? std::atoll(e) : 16ll; }();
-    if (Q >= count_filter_min_q && use_expanded_filter(c, &CD)) {
+    if (Q >= 16 && use_expanded_filter(c, &CD)) {
         // packed-fp32 filter in expanded form + exact fp64 test of whatever may lie inside the ball (brute2.hpp tile_reg_kernel<true>)
         const int64_t ngroups = c->count >> 2;
-        const int rg = reg_groups();
-        const int rblocks = (int)std::max<int64_t>(1, (ngroups + 256 * rg - 1) / (256 * rg));
+        const int rblocks = (int)std::max<int64_t>(1, (ngroups + 256 * kRegGroups - 1) / (256 * kRegGroups));
         const int tiles = (int)((Q + kTileQ - 1) / kTileQ);
         const int slices = std::max(1, std::min(tiles, (2048 + rblocks - 1) / rblocks));
         const int rq = ((tiles + slices - 1) / slices) * kTileQ;
@@ -1178,12 +991,7 @@ int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_
         brute2_prep_count_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(CD, d_q, d_r, (uint32_t)Q, c->d_qsorted, c->d_r2);
         dom_begin(c, s);
         const dim3 rgrid(rblocks, rslices);
-        switch (rg) {
-        case 2: tile_reg_kernel<true, 2><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, c->d_qsorted, c->d_q64, c->d_r2, (int)Q, rq, nullptr, nullptr, nullptr, d_count); break;
-        case 4: tile_reg_kernel<true, 4><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, c->d_qsorted, c->d_q64, c->d_r2, (int)Q, rq, nullptr, nullptr, nullptr, d_count); break;
-        case 6: tile_reg_kernel<true, 6><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, c->d_qsorted, c->d_q64, c->d_r2, (int)Q, rq, nullptr, nullptr, nullptr, d_count); break;
-        default: tile_reg_kernel<true, 3><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, c->d_qsorted, c->d_q64, c->d_r2, (int)Q, rq, nullptr, nullptr, nullptr, d_count); break;
-        }
+        tile_reg_kernel<true><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, c->d_qsorted, c->d_q64, c->d_r2, (int)Q, rq, nullptr, nullptr, nullptr, d_count);
         dom_end(c, s);
         end_timing(c, s);
         HIPCHK(hipGetLastError());
@@ -1363,10 +1171,9 @@ int pct_cloud_destroy(pct_cloud *c)
     if (c->h_bpos) (void)hipHostFree(c->h_bpos);
     dev_free(c->x); dev_free(c->y); dev_free(c->z); dev_free(c->d_stage); dev_free(c->gb_tmp); dev_free(c->gb_small);
     dev_free(c->blocks);
-    dev_free(c->cell_start); dev_free(c->sorted); dev_free(c->bin_start); dev_free(c->bin_fill); dev_free(c->bin_tiles);
+    dev_free(c->cell_start); dev_free(c->sorted);
     for (int l = 0; l < kMaxCoarse; l++) { dev_free(c->coarse_cell_start[l]); dev_free(c->coarse_sorted[l]); }
-    dev_free(c->d_qbin); dev_free(c->d_perm); dev_free(c->d_qsorted); dev_free(c->d_sorttmp); dev_free(c->d_sortkey); dev_free(c->d_sort1);
-    dev_free(c->d_inv); dev_free(c->d_sres_idx); dev_free(c->d_sres_d2); dev_free(c->d_todo);
+    dev_free(c->d_qsorted); dev_free(c->d_sort1); dev_free(c->d_todo);
     dev_free(c->d_q); dev_free(c->d_r); dev_free(c->d_q64); dev_free(c->d_r2); dev_free(c->d_d2); dev_free(c->d_radius);
     dev_free(c->d_pts64); dev_free(c->d_idx); dev_free(c->d_count); dev_free(c->d_skip); dev_free(c->d_bound);
     dev_free(c->d_part_d2); dev_free(c->d_part_idx); dev_free(c->d_cand_count); dev_free(c->d_cand_d2); dev_free(c->d_cand_idx); dev_free(c->d_ovf);
@@ -1471,8 +1278,7 @@ int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)
     const int64_t q = std::max<int64_t>(Q, 256);
     dev_free(c->d_q); dev_free(c->d_r); dev_free(c->d_q64); dev_free(c->d_r2); dev_free(c->d_d2); dev_free(c->d_radius);
     dev_free(c->d_pts64); dev_free(c->d_idx); dev_free(c->d_count); dev_free(c->d_skip); dev_free(c->d_bound);
-    dev_free(c->d_part_d2); dev_free(c->d_part_idx); dev_free(c->d_cand_count); dev_free(c->d_cand_d2); dev_free(c->d_cand_idx); dev_free(c->d_ovf); dev_free(c->d_qbin); dev_free(c->d_perm); dev_free(c->d_qsorted); dev_free(c->d_sorttmp); dev_free(c->d_sortkey);
-    dev_free(c->d_inv); dev_free(c->d_sres_idx); dev_free(c->d_sres_d2); dev_free(c->d_todo);
+    dev_free(c->d_part_d2); dev_free(c->d_part_idx); dev_free(c->d_cand_count); dev_free(c->d_cand_d2); dev_free(c->d_cand_idx); dev_free(c->d_ovf); dev_free(c->d_qsorted); dev_free(c->d_todo);
     c->qcap = 0;
     c->generation++;                    // captured plans hold these pointers
     PCTCHK(dev_alloc(&c->d_q, 3 * q));
@@ -1486,19 +1292,12 @@ int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)
     PCTCHK(dev_alloc(&c->d_count, q));
     PCTCHK(dev_alloc(&c->d_skip, q));
     PCTCHK(dev_alloc(&c->d_bound, q));
-    PCTCHK(dev_alloc(&c->d_qbin, q));
-    PCTCHK(dev_alloc(&c->d_perm, q));
     PCTCHK(dev_alloc(&c->d_qsorted, q));
-    PCTCHK(dev_alloc(&c->d_sorttmp, q));
-    PCTCHK(dev_alloc(&c->d_sortkey, q));
-    PCTCHK(dev_alloc(&c->d_inv, q));
-    PCTCHK(dev_alloc(&c->d_sres_idx, q));
-    PCTCHK(dev_alloc(&c->d_sres_d2, q));
     PCTCHK(dev_alloc(&c->d_todo, 2 * q + 16));
     HIPCHK(hipMemset(c->d_todo, 0, sizeof(uint32_t) * 16));            // count and ticket: the exact-walk kernel leaves them zero after every batch
     if (!c->d_sort1) {
-        PCTCHK(dev_alloc(&c->d_sort1, 4 * kSortBuckets + 8));
-        HIPCHK(hipMemset(c->d_sort1, 0, sizeof(uint32_t) * (4 * kSortBuckets + 8)));   // the sort keeps both sets of totals zero between batches
+        PCTCHK(dev_alloc(&c->d_sort1, 3 * kSortBuckets));
+        HIPCHK(hipMemset(c->d_sort1, 0, sizeof(uint32_t) * 3 * kSortBuckets));   // the sort keeps both sets of totals zero between batches
     }
     c->part_q = std::min<int64_t>(q, kPartQueries);
     PCTCHK(dev_alloc(&c->d_part_d2, (size_t)c->part_q * kMaxParts));
@@ -1669,14 +1468,6 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     if (const char *es = std::getenv("PCT_BIN_STRIP")) B.strip = std::max(1, std::atoi(es));
     B.strip = std::min(B.strip, B.by);
     B.nbins = (uint32_t)B.bx * (uint32_t)(((B.by + B.strip - 1) / B.strip) * B.strip) * (uint32_t)B.bz;
-    if ((size_t)B.nbins + 1 > c->bins_cap) {
-        dev_free(c->bin_start); dev_free(c->bin_fill); dev_free(c->bin_tiles);
-        c->bins_cap = 0;
-        PCTCHK(dev_alloc(&c->bin_start, (size_t)B.nbins + 1));
-        PCTCHK(dev_alloc(&c->bin_fill, (size_t)B.nbins));
-        PCTCHK(dev_alloc(&c->bin_tiles, (size_t)(B.nbins + kScanTile - 1) / kScanTile));
-        c->bins_cap = (size_t)B.nbins + 1;
-    }
     c->B = B;
     c->has_grid = true;
     c->generation++;

@@ -140,12 +140,13 @@ __global__ __launch_bounds__(256) void nn_stream_kernel(const float *__restrict_
 // 1.8e12 pairs/s.  Exactness only matters for the few points that can win, so:
 //   1. nn_sample_bounds_kernel: packed-fp32 minimum over a 1/16 sample of the cloud per query.
 //      ANY upper bound of the true minimum is a valid threshold; the sample only makes it tight.
-//   2. nn_tile_filter_kernel: each block stages its contiguous chunk of the SoA cloud in LDS
+//   2. nn_tile_candidates_kernel: each block stages its contiguous chunk of the SoA cloud in LDS
 //      ONCE (HBM is read once per launch whatever Q is), then walks the query batch in tiles of
-//      QT wave-uniform queries.  Every pair is evaluated in packed fp32 on two points at a time
+//      kTileQ wave-uniform queries.  Every pair is evaluated in packed fp32 on two points at a time
 //      (per 4 points and query: 6 pk_add, 2 pk_mul, 4 pk_fma, min3+min, one compare).  When the
 //      smallest of the four fp32 distances is <= thr = bound * (1 + 2^-19) + 2^-90 the group is
-//      re-evaluated in the exact fp64 arithmetic and competes by (d2, index).
+//      re-evaluated in the exact fp64 arithmetic and competes by (d2, index).  (brute2.hpp holds
+//      the expanded form of the same filter, taken on large clouds.)
 // Why nothing is lost: the fp32 value d32 of a pair differs from the exact d2 by < 4e-7 relative
 // (correctly rounded differences, three non-negative products, two sums: no cancellation) plus
 // underflow (< 2^-120 absolute).  The true winner w satisfies d2(w) <= d2(p) for the sample point
@@ -261,106 +262,10 @@ __global__ __launch_bounds__(256) void bound_reduce_kernel(const float *__restri
     if (threadIdx.x == 0) bound_bits[blockIdx.x] = __float_as_uint(fminf(fminf(s[0], s[1]), fminf(s[2], s[3])));
 }
 
-// grid = chunks of `chunk_groups` 4-point groups; dynamic LDS = 3 * chunk_groups float4.
-// Queries [qbase, qbase+Q) of the batch; partials at part[(q - qbase) * nparts + block].
-__global__ __launch_bounds__(256) void nn_tile_filter_kernel(const float *__restrict__ x, const float *__restrict__ y,
-                                                             const float *__restrict__ z, uint32_t n, uint32_t chunk_groups,
-                                                             const float *__restrict__ qf, const double *__restrict__ q64,
-                                                             const uint32_t *__restrict__ bound_bits, int qbase, int Q,
-                                                             double *__restrict__ part_d2, uint32_t *__restrict__ part_idx,
-                                                             int nparts)
-{
-    extern __shared__ float4 s_pts[];                 // [3][chunk_groups]
-    __shared__ double s_d[4][kTileQ];
-    __shared__ uint32_t s_i[4][kTileQ];
-    const uint32_t ngroups = n >> 2;
-    const uint32_t g0 = blockIdx.x * chunk_groups;
-    const uint32_t ng = min(chunk_groups, ngroups > g0 ? ngroups - g0 : 0u);
-    float4 *sx = s_pts, *sy = s_pts + chunk_groups, *sz = s_pts + 2 * chunk_groups;
-    for (uint32_t i = threadIdx.x; i < ng; i += 256) {
-        sx[i] = reinterpret_cast<const float4 *>(x)[g0 + i];
-        sy[i] = reinterpret_cast<const float4 *>(y)[g0 + i];
-        sz[i] = reinterpret_cast<const float4 *>(z)[g0 + i];
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool tail_owner = (blockIdx.x == gridDim.x - 1) && threadIdx.x < (n & 3u);   // n % 4 leftover points
-
-    for (int q0 = 0; q0 < Q; q0 += kTileQ) {
-        const int qcount = min(kTileQ, Q - q0);
-        float qx[kTileQ], qy[kTileQ], qz[kTileQ], thr[kTileQ];
-#pragma unroll
-        for (int j = 0; j < kTileQ; j++) {
-            const int qi = qbase + q0 + (j < qcount ? j : qcount - 1);
-            qx[j] = qf[3 * qi]; qy[j] = qf[3 * qi + 1]; qz[j] = qf[3 * qi + 2];
-            thr[j] = __uint_as_float(bound_bits[qi]) * (1.0f + 0x1p-19f) + 0x1p-90f;   // FLT_MAX bound -> +inf: recheck everything
-        }
-        double bd[kTileQ];
-        uint32_t bi[kTileQ];
-#pragma unroll
-        for (int j = 0; j < kTileQ; j++) { bd[j] = __builtin_huge_val(); bi[j] = kNoIndex; }
-
-        for (uint32_t i = threadIdx.x; i < ng; i += 256) {
-            const float4 X = sx[i], Y = sy[i], Z = sz[i];
-            const PointGroup pg = make_group(X, Y, Z);
-            // the compare results stay in scalar registers (one s_or per query, no per-lane flags)
-            unsigned long long hit = 0ull;
-#pragma unroll
-            for (int j = 0; j < kTileQ; j++) hit |= __builtin_amdgcn_ballot_w64(group_min_d32(pg, qx[j], qy[j], qz[j]) <= thr[j]);
-            // wave-uniform branch: taken only when some lane holds a possible winner for some query
-            if (hit != 0ull) {
-                if ((hit >> lane) & 1ull) {
-                    const float xs[4] = { X.x, X.y, X.z, X.w }, ys[4] = { Y.x, Y.y, Y.z, Y.w }, zs[4] = { Z.x, Z.y, Z.z, Z.w };
-#pragma unroll
-                    for (int j = 0; j < kTileQ; j++) {
-                        const int qi = qbase + q0 + (j < qcount ? j : qcount - 1);
-                        const double Qx = q64[3 * qi], Qy = q64[3 * qi + 1], Qz = q64[3 * qi + 2];
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const double d2 = dist2((double)xs[k], (double)ys[k], (double)zs[k], Qx, Qy, Qz);
-                            if (d2 < bd[j]) { bd[j] = d2; bi[j] = 4u * (g0 + i) + (uint32_t)k; }   // ids grow within a thread
-                        }
-                    }
-                }
-            }
-        }
-        if (tail_owner) {
-            const uint32_t id = 4u * ngroups + threadIdx.x;
-            const double px = (double)x[id], py = (double)y[id], pz = (double)z[id];
-#pragma unroll
-            for (int j = 0; j < kTileQ; j++) {
-                const int qi = qbase + q0 + (j < qcount ? j : qcount - 1);
-                const double d2 = dist2(px, py, pz, q64[3 * qi], q64[3 * qi + 1], q64[3 * qi + 2]);
-                if (better(d2, id, bd[j], bi[j])) { bd[j] = d2; bi[j] = id; }
-            }
-        }
-        // block winner per query; almost every lane holds (+inf, none), so skip the exchange then
-#pragma unroll
-        for (int j = 0; j < kTileQ; j++) {
-            double d = bd[j];
-            uint32_t ix = bi[j];
-            if (__builtin_amdgcn_ballot_w64(ix != kNoIndex) != 0ull) wave_argmin(d, ix);
-            if (lane == 0) { s_d[wave][j] = d; s_i[wave][j] = ix; }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < qcount) {
-            const int j = threadIdx.x;
-            double d = s_d[0][j];
-            uint32_t ix = s_i[0][j];
-#pragma unroll
-            for (int w = 1; w < 4; w++)
-                if (better(s_d[w][j], s_i[w][j], d, ix)) { d = s_d[w][j]; ix = s_i[w][j]; }
-            part_d2[(size_t)(q0 + j) * nparts + blockIdx.x] = d;
-            part_idx[(size_t)(q0 + j) * nparts + blockIdx.x] = ix;
-        }
-        __syncthreads();
-    }
-}
-
-// Candidate-list form of the filter (default).  The kernel above keeps a running (d2, index) per lane and query and folds it
-// per block and per tile of 8 queries -- two __syncthreads, a wave argmin and 8 partial writes for every tile, which at
-// 4096 queries is 512 block reductions per block and, for clouds under a few million points, most of the run time; it also
-// needs the [query][block] partial arrays and a second kernel to fold them.  But survivors of the fp32 bound are rare (about
+// Candidate-list form of the filter.  Keeping a running (d2, index) per lane and query and folding it per block and per tile
+// of 8 queries costs two __syncthreads, a wave argmin and 8 partial writes for every tile, which at 4096 queries is 512 block
+// reductions per block and, for clouds under a few million points, most of the run time; it also needs [query][block] partial
+// arrays and a second kernel to fold them (retired variants).  But survivors of the fp32 bound are rare (about
 // as many points as the sample stride lie closer than the closest SAMPLED point), so here a lane that holds one evaluates it
 // exactly and appends (d2, index) to its query's candidate list in global memory; nothing else leaves the tile loop.
 // nn_reduce_candidates_kernel then folds each list by (d2, index).  A list that overflows kCandCap entries (exact ties in
@@ -1136,41 +1041,17 @@ __device__ __forceinline__ uint32_t query_bin(const GridDesc &G, const BinDesc &
     return ((s * (uint32_t)B.bz + (uint32_t)cz) * (uint32_t)B.strip + yin) * (uint32_t)B.bx + (uint32_t)cx;
 }
 
-__global__ __launch_bounds__(256) void query_bin_count_kernel(GridDesc G, BinDesc B, const float *__restrict__ q, uint32_t Q,
-                                                              uint32_t *__restrict__ bin_count, uint32_t *__restrict__ qbin)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= Q) return;
-    const uint32_t b = query_bin(G, B, q[3 * t], q[3 * t + 1], q[3 * t + 2]);
-    qbin[t] = b;
-    atomicAdd(&bin_count[b], 1u);
-}
-
-// perm[pos] = original query id; qsorted[pos] = {qx, qy, qz, bitcast(id)} so the NN kernel gets a
-// query and its output slot with ONE 16-byte load instead of a perm -> q dependent pair
-__global__ __launch_bounds__(256) void query_bin_scatter_kernel(const uint32_t *__restrict__ qbin, uint32_t Q,
-                                                                const uint32_t *__restrict__ bin_start,
-                                                                uint32_t *__restrict__ bin_fill, const float *__restrict__ q,
-                                                                uint32_t *__restrict__ perm, float4 *__restrict__ qsorted)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= Q) return;
-    const uint32_t b = qbin[t];
-    const uint32_t pos = bin_start[b] + atomicAdd(&bin_fill[b], 1u);
-    perm[pos] = t;
-    qsorted[pos] = make_float4(q[3 * t], q[3 * t + 1], q[3 * t + 2], __uint_as_float(t));
-}
-
-// Counting sort of the batch on LDS histograms, one or two levels (replaces the global-atomic version
-// above for large batches: 2 M scattered device-scope atomics ran at ~20 G/s = 100 us per 1 M
-// queries).  key = bin >> key_shift (< 2^20); level 1 = key >> 10 (<= 1024
-// buckets), level 2 = key & 1023 inside a bucket.  Global atomics are one per (block, non-empty
-// bucket); everything else is LDS atomics and coalesced traffic.
+// Counting sort of the batch on LDS histograms (a global-atomic version ran 2 M scattered
+// device-scope atomics at ~20 G/s = 100 us per 1 M queries).  key = bin >> key_shift (< 2^20);
+// bucket = key >> kSortLShift (<= 1024 buckets), queries left in arrival order inside a bucket.
+// Global atomics are one per (block, non-empty bucket); everything else is LDS atomics and
+// coalesced traffic.
 constexpr int kSortBuckets = 1024;
-constexpr int kSortItems = 8;            // queries per thread in the level-1 kernels
-constexpr int kSortPerBlock = 1024 * kSortItems;      // most queries per block in the level-1 kernels (engine.hip picks 1024..8192 by batch size)
+constexpr int kSortLShift = 10;          // finer buckets (key >> 8, >> 9) measured the same
+constexpr int kSortItems = 8;            // queries per thread in the sort kernels
+constexpr int kSortPerBlock = 1024 * kSortItems;      // most queries per block in the sort kernels (engine.hip picks 1024..8192 by batch size)
 
-// A thread's kSortItems queries of the level-1 kernels.  VEC (the query array is 16-byte aligned): the thread owns chunks of 4 CONSECUTIVE
+// A thread's kSortItems queries of the sort kernels.  VEC (the query array is 16-byte aligned): the thread owns chunks of 4 CONSECUTIVE
 // queries and fetches each chunk as three float4 (48 contiguous bytes) instead of twelve dwords at a stride of 12 bytes: a quarter of the
 // load instructions.  Item k of thread `tid` is query sort_item<VEC>(base, k, tid); an item is live when sort_item_live says so.
 template <bool VEC>
@@ -1218,14 +1099,13 @@ __device__ __forceinline__ void sort_load_items(const float *__restrict__ q, uin
     }
 }
 
-//
-// Three dependent launches per batch (hist -> scatter1 -> fine); at <= 256 K queries the sort is launch-latency-bound
-// (~40 us for five dependent operations, measured), so the bucket scan lives inside scatter1 and the two counter
-// arrays are re-zeroed without extra launches where possible: total1 is zero on entry (zeroed at allocation, then by the fine
-// kernel or, in single-level mode, a memset behind scatter1), fill1 is zeroed here, before any scatter1 block can touch it.
+// Two dependent launches per batch (hist -> scatter1); at <= 256 K queries the sort is launch-latency-bound, so the bucket scan
+// lives inside scatter1 and the counter arrays are re-zeroed without extra launches where possible: total1 is zero on entry
+// (zeroed at allocation, then by the previous batch's hist pass through total1_next, or by a memset behind scatter1 when the
+// batch is captured), fill1 is zeroed here, before any scatter1 block can touch it.
 template <bool VEC>
-__global__ __launch_bounds__(1024) void qsort_hist_kernel(GridDesc G, BinDesc B, int key_shift, int lshift, const float *__restrict__ q,
-                                                          uint32_t Q, uint32_t per_block, uint32_t *__restrict__ keys,
+__global__ __launch_bounds__(1024) void qsort_hist_kernel(GridDesc G, BinDesc B, int key_shift, const float *__restrict__ q,
+                                                          uint32_t Q, uint32_t per_block,
                                                           uint32_t *__restrict__ total1, uint32_t *__restrict__ fill1,
                                                           uint32_t *__restrict__ total1_next)
 {
@@ -1244,11 +1124,9 @@ __global__ __launch_bounds__(1024) void qsort_hist_kernel(GridDesc G, BinDesc B,
     sort_load_items<VEC>(q, base, threadIdx.x, items, Q, qv);
 #pragma unroll
     for (int k = 0; k < kSortItems; k++) {
-        const uint32_t t = sort_item<VEC>(base, k, threadIdx.x);
         if (sort_item_live<VEC>(base, k, threadIdx.x, items, Q)) {
-            const uint32_t key = query_bin(G, B, qv[k][0], qv[k][1], qv[k][2]) >> key_shift;
-            if (keys) keys[t] = key;                 // nullptr: the scatter pass recomputes the key from the query it reads anyway
-            atomicAdd(&h[key >> lshift], 1u);
+            const uint32_t key = query_bin(G, B, qv[k][0], qv[k][1], qv[k][2]) >> key_shift;     // recomputed by the scatter pass
+            atomicAdd(&h[key >> kSortLShift], 1u);
         }
     }
     __syncthreads();
@@ -1256,15 +1134,12 @@ __global__ __launch_bounds__(1024) void qsort_hist_kernel(GridDesc G, BinDesc B,
         if (h[i]) atomicAdd(&total1[i], h[i]);
 }
 
-// level 1 scatter: the query record {x, y, z, bitcast(id)} travels with its key, so the fine pass
-// never gathers from the (randomly ordered) input again.  Every block scans the 1024 bucket totals itself
-// (thread i = bucket i) instead of waiting for a one-block scan kernel; block 0 publishes the starts for the fine pass.
+// scatter: qsorted[pos] = {qx, qy, qz, bitcast(id)}, so the search kernels get a query and its output slot with ONE 16-byte load.
+// Every block scans the 1024 bucket totals itself (thread i = bucket i) instead of waiting for a one-block scan kernel.
 template <bool VEC>
-__global__ __launch_bounds__(1024) void qsort_scatter1_kernel(GridDesc G, BinDesc B, int key_shift, const uint32_t *__restrict__ keys, const float *__restrict__ q,
-                                                              uint32_t Q, uint32_t per_block, int lshift, const uint32_t *__restrict__ total1,
-                                                              uint32_t *__restrict__ fill1, uint32_t *__restrict__ start1,
-                                                              uint32_t *__restrict__ tmp_key, float4 *__restrict__ tmp_rec,
-                                                              uint32_t *__restrict__ perm, uint32_t *__restrict__ inv, int final_level)
+__global__ __launch_bounds__(1024) void qsort_scatter1_kernel(GridDesc G, BinDesc B, int key_shift, const float *__restrict__ q,
+                                                              uint32_t Q, uint32_t per_block, const uint32_t *__restrict__ total1,
+                                                              uint32_t *__restrict__ fill1, float4 *__restrict__ qsorted)
 {
     static_assert(kSortBuckets == 1024, "one thread per bucket");
     __shared__ uint32_t h[kSortBuckets];
@@ -1283,32 +1158,20 @@ __global__ __launch_bounds__(1024) void qsort_scatter1_kernel(GridDesc G, BinDes
     __syncthreads();
     uint32_t start = inc - tot;
     for (int w = 0; w < wave; w++) start += s_wave[w];
-    if (blockIdx.x == 0) {
-        start1[threadIdx.x] = start;
-        if (threadIdx.x == kSortBuckets - 1) start1[kSortBuckets] = start + tot;
-    }
     const uint32_t base = blockIdx.x * per_block;
     const int items = (int)(per_block >> 10);
-    // keys and queries of all of a thread's items are requested up front (one round trip for each array instead of one per item)
+    // all of a thread's queries are requested up front (one round trip instead of one per item)
     uint32_t key[kSortItems];
     float qv[kSortItems][3];
-#pragma unroll
-    for (int k = 0; k < kSortItems; k++) {
-        const uint32_t t = sort_item<VEC>(base, k, threadIdx.x);
-        const bool ok = sort_item_live<VEC>(base, k, threadIdx.x, items, Q);
-        key[k] = ok ? (keys ? keys[t] : 0u) : 0xFFFFFFFFu;
-    }
     sort_load_items<VEC>(q, base, threadIdx.x, items, Q, qv);
-    if (!keys) {
 #pragma unroll
-        for (int k = 0; k < kSortItems; k++)
-            if (key[k] != 0xFFFFFFFFu) key[k] = query_bin(G, B, qv[k][0], qv[k][1], qv[k][2]) >> key_shift;
-    }
+    for (int k = 0; k < kSortItems; k++)
+        key[k] = sort_item_live<VEC>(base, k, threadIdx.x, items, Q) ? query_bin(G, B, qv[k][0], qv[k][1], qv[k][2]) >> key_shift : 0xFFFFFFFFu;
     // the histogram atomic's return value IS the query's rank inside (block, bucket): one LDS atomic per query, not two
     uint32_t rank[kSortItems];
 #pragma unroll
     for (int k = 0; k < kSortItems; k++)
-        if (key[k] != 0xFFFFFFFFu) rank[k] = atomicAdd(&h[key[k] >> lshift], 1u);
+        if (key[k] != 0xFFFFFFFFu) rank[k] = atomicAdd(&h[key[k] >> kSortLShift], 1u);
     __syncthreads();
     {
         const uint32_t mine = h[threadIdx.x];
@@ -1319,74 +1182,14 @@ __global__ __launch_bounds__(1024) void qsort_scatter1_kernel(GridDesc G, BinDes
     for (int k = 0; k < kSortItems; k++) {
         if (key[k] != 0xFFFFFFFFu) {
             const uint32_t t = sort_item<VEC>(base, k, threadIdx.x);
-            const uint32_t pos = basepos[key[k] >> lshift] + rank[k];
-            if (!final_level) tmp_key[pos] = key[k];  // a fine pass follows and needs the key
-            else if (perm) perm[pos] = t;             // single-level mode: this IS the final order; perm only for the kernels that read it
-            if (inv) inv[t] = pos;                    // where query t went (coalesced): results come back through it
-            tmp_rec[pos] = make_float4(qv[k][0], qv[k][1], qv[k][2], __uint_as_float(t));
+            const uint32_t pos = basepos[key[k] >> kSortLShift] + rank[k];
+            qsorted[pos] = make_float4(qv[k][0], qv[k][1], qv[k][2], __uint_as_float(t));
         }
     }
 }
 
-// one block per level-1 bucket: counting sort by the low 10 key bits, then emit perm / qsorted.  1024 threads: a bucket holds
-// Q / (occupied level-1 buckets) records (~5000 at 1 M queries over 211 buckets), and the three passes are latency-bound
-// (same-box A/B: 256 threads 0.2068 ms per step, 1024 threads 0.2008; spreading the keys over more level-1 buckets instead,
-// key >> 8 = 844 buckets, gained nothing)
-constexpr int kFineThreads = 1024;
-__global__ __launch_bounds__(kFineThreads) void qsort_fine_kernel(const uint32_t *__restrict__ tmp_key, const float4 *__restrict__ tmp_rec,
-                                                                  const uint32_t *__restrict__ start1, uint32_t *__restrict__ total1,
-                                                                  uint32_t lmask, uint32_t *__restrict__ perm, float4 *__restrict__ qsorted,
-                                                                  uint32_t *__restrict__ inv)
-{
-    static_assert(kSortBuckets == kFineThreads, "one histogram entry per thread");
-    __shared__ uint32_t h[kSortBuckets];
-    __shared__ uint32_t s_wave[kFineThreads / 64];
-    const uint32_t s = start1[blockIdx.x], e = start1[blockIdx.x + 1];
-    if (threadIdx.x == 0) total1[blockIdx.x] = 0;      // its last reader (scatter1) has finished: ready for the next batch
-    if (s == e) return;
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint32_t i = s + threadIdx.x; i < e; i += kFineThreads) atomicAdd(&h[tmp_key[i] & lmask], 1u);
-    __syncthreads();
-    // exclusive scan of h[1024] in place: one entry per thread
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t v = h[threadIdx.x];
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t run = inc - v;
-    for (int w = 0; w < wave; w++) run += s_wave[w];
-    h[threadIdx.x] = run;
-    __syncthreads();
-    for (uint32_t i = s + threadIdx.x; i < e; i += kFineThreads) {
-        const float4 rec = tmp_rec[i];
-        const uint32_t pos = s + atomicAdd(&h[tmp_key[i] & lmask], 1u);
-        if (perm) perm[pos] = __float_as_uint(rec.w);
-        qsorted[pos] = rec;
-        if (inv) inv[__float_as_uint(rec.w)] = pos;
-    }
-}
-
-// results of a sorted batch back into arrival order: out[t] = sorted[inv[t]] -- a gather from the 12 MB of sorted results
-// (cache resident) with coalesced writes, instead of 2 x Q scattered partial-line writes from the search kernel
-__global__ __launch_bounds__(256) void unpermute_results_kernel(const uint32_t *__restrict__ inv, const uint32_t *__restrict__ sidx,
-                                                                const double *__restrict__ sd2, uint32_t Q,
-                                                                uint32_t *__restrict__ out_idx, double *__restrict__ out_d2)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= Q) return;
-    const uint32_t p = inv[t];
-    out_idx[t] = sidx[p];
-    out_d2[t] = sd2[p];
-}
-
 // =====================================================================================
-// 4. Cell-pruned kernels: one lane per query walks an expanding cube of cells.
+// 4. Cell-pruned kernels: the search walks an expanding cube of cells around the query.
 //    Termination is exact: a point outside the scanned cube of cells is at least
 //    `bound` away (distance to the cube's faces, minus a slack covering the fp32 cell
 //    assignment rounding), so the search stops once best_d2 <= bound^2.
@@ -1420,194 +1223,15 @@ __device__ __forceinline__ double cube_bound(const GridDesc &G, int cx, int cy, 
     return bound == __builtin_huge_val() ? bound : bound - G.hd * (1.0 / 256.0);
 }
 
-// Points [s, e) of the cell-sorted array against one query.  Four independent 16-byte loads are
-// issued before the first compare (the tail repeats the last point: a repeated (d2, index) never
-// changes the winner), so a short run costs one memory round trip instead of one per point.
-__device__ __forceinline__ void scan_points(const float4 *__restrict__ pts, uint32_t s, uint32_t e, double qx, double qy,
-                                            double qz, double &bd, uint32_t &bi)
-{
-    for (uint32_t p = s; p < e; p += 4) {
-        const uint32_t last = e - 1;
-        const float4 P0 = pts[p], P1 = pts[min(p + 1, last)], P2 = pts[min(p + 2, last)], P3 = pts[min(p + 3, last)];
-        const float4 P[4] = { P0, P1, P2, P3 };
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const double d2 = dist2((double)P[k].x, (double)P[k].y, (double)P[k].z, qx, qy, qz);
-            const uint32_t id = __float_as_uint(P[k].w);
-            if (better(d2, id, bd, bi)) { bd = d2; bi = id; }
-        }
-    }
-}
-
-// fp32 screening of points [s, e): tracks the smallest and second-smallest fp32 distance and the
-// array position of the smallest.  Tail slots of the 4-wide load group count as +inf (a repeated
-// point would fake a tie).
-__device__ __forceinline__ void screen_points(const float4 *__restrict__ pts, uint32_t s, uint32_t e, float qx, float qy,
-                                              float qz, float &m1, float &m2, uint32_t &p1)
-{
-    for (uint32_t p = s; p < e; p += 4) {
-        const uint32_t last = e - 1;
-        const float4 P0 = pts[p], P1 = pts[min(p + 1, last)], P2 = pts[min(p + 2, last)], P3 = pts[min(p + 3, last)];
-        const float4 P[4] = { P0, P1, P2, P3 };
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float dx = P[k].x - qx, dy = P[k].y - qy, dz = P[k].z - qz;
-            float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-            if (k > 0) d = (p + k <= last) ? d : __builtin_huge_valf();
-            const bool lt = d < m1;
-            m2 = lt ? m1 : fminf(m2, d);
-            p1 = lt ? p + (uint32_t)k : p1;
-            m1 = fminf(m1, d);
-        }
-    }
-}
-
-template <bool COUNT>
-__device__ __forceinline__ void scan_run(const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
-                                         uint32_t lin0, uint32_t lin1, double qx, double qy, double qz, double &bd,
-                                         uint32_t &bi, uint32_t &npts, uint32_t &nruns)
-{
-    const uint32_t s = cell_start[lin0], e = cell_start[lin1 + 1];
-    if (COUNT) { npts += e - s; nruns += 1; }
-    scan_points(pts, s, e, qx, qy, qz, bd, bi);
-}
-
-template <bool COUNT>
-__global__ __launch_bounds__(256) void nn_grid_kernel(GridDesc G, const float4 *__restrict__ pts,
-                                                      const uint32_t *__restrict__ cell_start,
-                                                      const float *__restrict__ q, uint32_t Q, uint32_t index_base,
-                                                      const uint32_t *__restrict__ perm,
-                                                      uint32_t *__restrict__ out_idx, double *__restrict__ out_d2,
-                                                      WorkCounters *__restrict__ work)
-{
-    const uint32_t slot = (perm ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x) * blockDim.x + threadIdx.x;
-    uint32_t npts = 0, nruns = 0;
-    if (slot < Q) {
-        const uint32_t t = perm ? perm[slot] : slot;     // binned order in, original order out
-        const float qxf = q[3 * t], qyf = q[3 * t + 1], qzf = q[3 * t + 2];
-        const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-        const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
-        const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
-        const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
-        double bd = __builtin_huge_val();
-        uint32_t bi = kNoIndex;
-        const double slack = G.hd * (1.0 / 256.0);
-        for (int r = 1;; r++) {
-            const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
-            const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
-            if (r == 1) {
-                // first cube (3x3x3 cells = 9 contiguous x-runs; almost every query ends here): the 18
-                // cell_start reads are independent, so issue them all before touching any point
-                uint32_t rs[9], re[9];
-#pragma unroll
-                for (int k = 0; k < 9; k++) {
-                    const int zz = cz + k / 3 - 1, yy = cy + k % 3 - 1;
-                    const bool ok = zz >= 0 && zz < G.gz && yy >= 0 && yy < G.gy;    // rows outside the grid hold nothing
-                    const uint32_t row = ok ? cell_lin(G, 0, yy, zz) : 0u;
-                    const uint32_t a = cell_start[row + x0], b = cell_start[row + x1 + 1];
-                    rs[k] = a;
-                    re[k] = ok ? b : a;
-                    if (COUNT) { npts += re[k] - rs[k]; nruns += ok ? 1u : 0u; }
-                }
-                // fp32 screening first: fp64 costs ~3x per point, and 53 points are looked at per query.
-                // If the runner-up is farther than the fp32 error band the fp32 argmin IS the exact
-                // winner (every other point p has d2(p) >= d32(p)/(1+e) > d2(best); e < 4e-7, band 2^-19)
-                // and one exact evaluation finishes the query; otherwise (near-ties, duplicates) the
-                // runs are re-scanned in the exact arithmetic so the (d2, index) order decides.
-                float m1 = __builtin_huge_valf(), m2 = __builtin_huge_valf();
-                uint32_t p1 = 0;
-                // one z-plane (3 rows) at a time: the first 4 points of each row are requested together
-                // (12 independent 16-byte loads in flight), rows longer than 4 continue 4 at a time.
-                // The kernel is bound by dependent memory round trips, not by arithmetic.
-#pragma unroll
-                for (int g = 0; g < 3; g++) {
-                    float4 P[3][4];
-#pragma unroll
-                    for (int j = 0; j < 3; j++) {
-                        const uint32_t a = rs[3 * g + j], b = re[3 * g + j];
-                        const uint32_t last = b > a ? b - 1 : 0u;      // empty row: read slot 0, masked below
-#pragma unroll
-                        for (int k = 0; k < 4; k++) P[j][k] = pts[min(a + (uint32_t)k, last)];
-                    }
-#pragma unroll
-                    for (int j = 0; j < 3; j++) {
-                        const uint32_t a = rs[3 * g + j], b = re[3 * g + j];
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const float dx = P[j][k].x - qxf, dy = P[j][k].y - qyf, dz = P[j][k].z - qzf;
-                            float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                            d = (a + (uint32_t)k < b) ? d : __builtin_huge_valf();
-                            const bool lt = d < m1;
-                            m2 = lt ? m1 : fminf(m2, d);
-                            p1 = lt ? a + (uint32_t)k : p1;
-                            m1 = fminf(m1, d);
-                        }
-                    }
-#pragma unroll
-                    for (int j = 0; j < 3; j++)
-                        if (re[3 * g + j] > rs[3 * g + j] + 4u) screen_points(pts, rs[3 * g + j] + 4u, re[3 * g + j], qxf, qyf, qzf, m1, m2, p1);
-                }
-                if (m1 < __builtin_huge_valf()) {
-                    if (m2 > m1 * (1.0f + 0x1p-19f) + 0x1p-90f) {
-                        const float4 P = pts[p1];
-                        bd = dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz);
-                        bi = __float_as_uint(P.w);
-                    } else {
-#pragma unroll 1
-                        for (int k = 0; k < 9; k++) scan_points(pts, rs[k], re[k], qx, qy, qz, bd, bi);
-                    }
-                }
-            } else
-            for (int zz = z0; zz <= z1; zz++) {
-                const bool zface = (zz == cz - r) || (zz == cz + r);
-                for (int yy = y0; yy <= y1; yy++) {
-                    const uint32_t row = cell_lin(G, 0, yy, zz);
-                    if (r == 1 || zface || yy == cy - r || yy == cy + r) {
-                        scan_run<COUNT>(pts, cell_start, row + x0, row + x1, qx, qy, qz, bd, bi, npts, nruns);
-                    } else {
-                        if (cx - r >= 0) scan_run<COUNT>(pts, cell_start, row + cx - r, row + cx - r, qx, qy, qz, bd, bi, npts, nruns);
-                        if (cx + r <= G.gx - 1) scan_run<COUNT>(pts, cell_start, row + cx + r, row + cx + r, qx, qy, qz, bd, bi, npts, nruns);
-                    }
-                }
-            }
-            // distance from q to the nearest face of the scanned cube that still has cells behind it
-            double bound = __builtin_huge_val();
-            if (cx - r > 0) bound = fmin(bound, qx - (G.oxd + (double)(cx - r) * G.hd));
-            if (cx + r < G.gx - 1) bound = fmin(bound, (G.oxd + (double)(cx + r + 1) * G.hd) - qx);
-            if (cy - r > 0) bound = fmin(bound, qy - (G.oyd + (double)(cy - r) * G.hd));
-            if (cy + r < G.gy - 1) bound = fmin(bound, (G.oyd + (double)(cy + r + 1) * G.hd) - qy);
-            if (cz - r > 0) bound = fmin(bound, qz - (G.ozd + (double)(cz - r) * G.hd));
-            if (cz + r < G.gz - 1) bound = fmin(bound, (G.ozd + (double)(cz + r + 1) * G.hd) - qz);
-            if (bound == __builtin_huge_val()) break;          // the cube covers the whole grid
-            bound -= slack;
-            if (bound > 0.0 && bd <= bound * bound) break;
-        }
-        out_idx[t] = (bi == kNoIndex) ? kNoIndex : bi + index_base;
-        out_d2[t] = bd;
-    }
-    if (COUNT) {
-        unsigned long long a = npts, b = nruns;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            a += (unsigned long long)__shfl_xor((long long)a, off, kWave);
-            b += (unsigned long long)__shfl_xor((long long)b, off, kWave);
-        }
-        if ((threadIdx.x & 63) == 0) { WorkCounters *w = work + (blockIdx.x & (kWorkSlots - 1)); atomicAdd(&w->points, a); atomicAdd(&w->cells, b); }
-    }
-}
-
 // -------------------------------------------------------------------------------------
 // Cooperative form of the cell-pruned NN: EIGHT lanes per query (8 queries per wave).
 //
-// The lane-per-query kernel above is bound by the vector L1's address path, not by arithmetic or
-// DRAM (measured: ~150 L1 accesses per query, texture-address unit busy 65 % of the kernel):
-// a lane reading the 6 points of a run one after the other issues 6 separate 16-byte accesses to
-// the SAME 128-byte line.  Here the 8 lanes of a group read 8 consecutive points of a run with one
+// A lane-per-query search is bound by the vector L1's address path, not by arithmetic or DRAM
+// (measured: ~150 L1 accesses per query, texture-address unit busy 65 % of the kernel): a lane
+// reading the 6 points of a run one after the other issues 6 separate 16-byte accesses to the
+// SAME 128-byte line.  Here the 8 lanes of a group read 8 consecutive points of a run with one
 // coalesced 128-byte access, the 9 rows' cell_start entries are fetched by 9 different lanes at
 // once, and the three rows of a z-plane are requested before any is consumed.
-// Arithmetic and results are identical to nn_grid_kernel (same screening rule, same exact fp64
-// winner by (d2, index), same termination bound).
 // -------------------------------------------------------------------------------------
 constexpr int kCoop = 8;
 
@@ -1621,14 +1245,7 @@ constexpr int kDppQuadBcast0 = 0x00, kDppQuadBcast1 = 0x55, kDppQuadBcast2 = 0xA
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_u32(uint32_t v)
 {
-#ifdef PCT_AB_NO_DPP        // A/B switch (scripts/ab_build.sh): the same data movement through ds_bpermute
-    const int lane = (int)(threadIdx.x & 63u), l8 = lane & 7, q = lane & 3;
-    const int src = CTRL == kDppXor1 ? (lane ^ 1) : CTRL == kDppXor2 ? (lane ^ 2) : CTRL == kDppHalfMirror ? ((lane & ~7) | (7 - l8)) :
-                    (lane - q + (CTRL == kDppQuadBcast0 ? 0 : CTRL == kDppQuadBcast1 ? 1 : CTRL == kDppQuadBcast2 ? 2 : 3));
-    return (uint32_t)__shfl((int)v, src, kWave);
-#else
     return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-#endif
 }
 template <int CTRL>
 __device__ __forceinline__ float dpp_f32(float v) { return __uint_as_float(dpp_u32<CTRL>(__float_as_uint(v))); }
@@ -1704,14 +1321,9 @@ __device__ __forceinline__ void coop_scan_cube_or_shell(const GridDesc &G, const
 // runner-up lies outside the fp32 error band the minimum IS the exact winner and is evaluated once in fp64, otherwise the
 // runs are rescanned in exact arithmetic.  All NR rows are requested before any is consumed (the kernel is bound by
 // dependent memory round trips: one for the bounds, one for the points).  Leaves (bd, bi) = (+inf, none) for empty runs.
-// OPEN = true (A/B switch PCT_AB_OPEN_STAGE0, NOT the default): the 8 * DEPTH slots behind a run's first record are read and
-// screened whatever the run's length -- what lies behind a short run are the records of the following cells, real points of the cloud
-// (or the +inf pad records behind the last one, gb_pad_kernel), and the nearest neighbour over a superset of the block is still a
-// valid candidate.  It removes the clamp, the empty-run select and the validity masks (~4 of ~17 vector instructions per slot) -- and
-// measured SLOWER on the headline step: 0.146 ms (72 VGPRs, 7 waves) / 0.132 ms (77 VGPRs, 6 waves) / 0.21 ms (64 VGPRs: 60 B of
-// scratch) against 0.120 ms masked (profiles/r03_ab_open_stage0.txt).  The clamp is what keeps the lanes beyond a run on the run's last
-// cache line; without it every run costs two full lines more often, and this kernel pays for lines before it pays for instructions.
-template <int NR, int DEPTH, bool OPEN = false>
+// The clamp keeps the lanes beyond a run on the run's last cache line (reading the slots behind the run unclamped measured slower:
+// DESIGN.md, retired variants).
+template <int NR, int DEPTH>
 __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts, const uint32_t (&rs)[NR], const uint32_t (&re)[NR],
                                                  uint32_t sub, float qxf, float qyf, float qzf, double qx, double qy, double qz,
                                                  double &bd, uint32_t &bi)
@@ -1725,11 +1337,8 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
         const uint32_t a = rs[k], b = re[k];
         const uint32_t last = b > a ? b - 1 : 0u;               // empty row: read slot 0, masked below
 #pragma unroll
-        for (int j = 0; j < DEPTH; j++) P[k][j] = pts[OPEN ? a + sub + kCoop * j : min(a + sub + kCoop * j, last)];
+        for (int j = 0; j < DEPTH; j++) P[k][j] = pts[min(a + sub + kCoop * j, last)];
     }
-#ifdef PCT_AB_SCHED_BARRIER
-    __builtin_amdgcn_sched_barrier(0);                           // nothing moves across: every load above is issued before the first use below
-#endif
 #pragma unroll
     for (int k = 0; k < NR; k++) {
         const uint32_t a = rs[k], b = re[k];
@@ -1738,7 +1347,7 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
             const uint32_t p = a + sub + kCoop * j;
             const float dx = P[k][j].x - qxf, dy = P[k][j].y - qyf, dz = P[k][j].z - qzf;
             float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-            if (!OPEN) d = (p < b) ? d : __builtin_huge_valf();
+            d = (p < b) ? d : __builtin_huge_valf();
             const bool lt = d < m1;
             m2 = __builtin_amdgcn_fmed3f(m1, m2, d);            // second smallest of {m1 <= m2, d}
             p1 = lt ? p : p1;
@@ -1957,11 +1566,7 @@ __device__ __forceinline__ bool coop_stage0(const GridDesc &G, const float4 *__r
 #pragma unroll
         for (int k = 0; k < 4; k++) { rs[k] = (uint32_t)__shfl((int)my_s, k, kCoop); re[k] = (uint32_t)__shfl((int)my_e, k, kCoop); }
     }
-#ifdef PCT_AB_OPEN_STAGE0          // measured slower: see coop_screen_rows
-    coop_screen_rows<4, 2, true>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
-#else
     coop_screen_rows<4, 2>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
-#endif
     return block_leaves_undecided(G, cx, cy, cz, xa, xb, ya, yb, za, zb, fx, fy, fz, qx, qy, qz, bd);
 }
 
@@ -2100,36 +1705,30 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
     if (live && undecided) coop_finish_shells<COUNT>(G, pts, cell_start, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
 }
 
-template <bool COUNT, bool WAVE = false>
 // Occupancy target 7 waves per SIMD, as minimum AND maximum: with 8 allowed the scheduler keeps the kernel at 64 VGPRs by issuing the
 // eight record loads of stage 0 two at a time (four dependent round trips); capped at 7 it takes 72 VGPRs and issues all eight before the
 // first use.  Headline step 0.1198-0.1210 -> 0.1163-0.1179 ms (6 waves: 0.122, 5: 0.134; profiles/r03_ab_occupancy_cap.txt).  Raising
 // only the minimum (round 2's "7 waves" experiment) never changed the code: the scheduler still aimed for 8.
-#ifndef PCT_AB_COOP_WAVES
-#define PCT_AB_COOP_WAVES 7
-#endif
-#ifndef PCT_AB_COOP_WAVES_MAX
-#define PCT_AB_COOP_WAVES_MAX 7
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PCT_AB_COOP_WAVES, PCT_AB_COOP_WAVES_MAX))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
+template <bool COUNT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
                                                            const uint32_t *__restrict__ cell_start,
                                                            const float *__restrict__ q, uint32_t Q, uint32_t index_base,
                                                            const float4 *__restrict__ qsorted,
                                                            uint32_t *__restrict__ out_idx, double *__restrict__ out_d2,
-                                                           WorkCounters *__restrict__ work, int sorted_out)
+                                                           WorkCounters *__restrict__ work)
 {
     const uint32_t sub = threadIdx.x & (kCoop - 1);
     const uint32_t bslot = qsorted ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
     const uint32_t slot = bslot * (256 / kCoop) + (threadIdx.x / kCoop);
     uint32_t npts = 0, nruns = 0;
-    if (WAVE && G.octant_first) {                     // wave-cooperative fallback (see above); every lane of the wave stays in step
+    if (G.octant_first) {                             // wave-cooperative fallback (see above); every lane of the wave stays in step
         const bool live = slot < Q;
         uint32_t t = slot;
         float qxf = 0.0f, qyf = 0.0f, qzf = 0.0f;
         if (live) {
             if (qsorted) {
                 const float4 R = qsorted[slot];
-                qxf = R.x; qyf = R.y; qzf = R.z; t = sorted_out ? slot : __float_as_uint(R.w);
+                qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
             } else {
                 qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
             }
@@ -2146,7 +1745,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PCT_AB_COOP
         float qxf, qyf, qzf;
         if (qsorted) {                                // binned batch: query and output slot in one record
             const float4 R = qsorted[slot];
-            qxf = R.x; qyf = R.y; qzf = R.z; t = sorted_out ? slot : __float_as_uint(R.w);     // sorted_out: results stay in sorted order
+            qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
         } else {
             qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
         }
@@ -2254,52 +1853,6 @@ __global__ __launch_bounds__(256) void count_grid_coop_kernel(GridDesc G, const 
 #pragma unroll
         for (int off = 1; off < kCoop; off <<= 1) c += (uint32_t)__shfl_xor((int)c, off, kWave);
         if (sub == 0) count[t] = c;
-    }
-    if (COUNT) {
-        unsigned long long a = npts, b = nruns;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            a += (unsigned long long)__shfl_xor((long long)a, off, kWave);
-            b += (unsigned long long)__shfl_xor((long long)b, off, kWave);
-        }
-        if ((threadIdx.x & 63) == 0) { WorkCounters *w = work + (blockIdx.x & (kWorkSlots - 1)); atomicAdd(&w->points, a); atomicAdd(&w->cells, b); }
-    }
-}
-
-// radius count through the grid, one lane per query (PCT_GRID_COOP=0): every cell row overlapping the ball's bounding box.
-template <bool COUNT>
-__global__ __launch_bounds__(256) void count_grid_kernel(GridDesc G, const float4 *__restrict__ pts,
-                                                         const uint32_t *__restrict__ cell_start,
-                                                         const float *__restrict__ q, const float *__restrict__ rad,
-                                                         uint32_t Q, const uint32_t *__restrict__ perm,
-                                                         uint32_t *__restrict__ count, WorkCounters *__restrict__ work)
-{
-    const uint32_t slot = (perm ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x) * blockDim.x + threadIdx.x;
-    uint32_t npts = 0, nruns = 0;
-    if (slot < Q) {
-        const uint32_t t = perm ? perm[slot] : slot;
-        const float qxf = q[3 * t], qyf = q[3 * t + 1], qzf = q[3 * t + 2], rf = rad[t];
-        const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-        const double r2 = (double)rf * (double)rf;
-        uint32_t c = 0;
-        {
-            const float pad = fabsf(rf) + 0.01f * (1.0f / G.inv_h);   // r enters only squared (kdtree.c:273)
-            int x0 = cell_coord(qxf - pad, G.ox, G.inv_h, G.gx), x1 = cell_coord(qxf + pad, G.ox, G.inv_h, G.gx);
-            int y0 = cell_coord(qyf - pad, G.oy, G.inv_h, G.gy), y1 = cell_coord(qyf + pad, G.oy, G.inv_h, G.gy);
-            int z0 = cell_coord(qzf - pad, G.oz, G.inv_h, G.gz), z1 = cell_coord(qzf + pad, G.oz, G.inv_h, G.gz);
-            // (no extra cell of margin: pad's h/100 already covers the < 4e-4-cell error of the fp32 cell assignment)
-            for (int zz = z0; zz <= z1; zz++)
-                for (int yy = y0; yy <= y1; yy++) {
-                    const uint32_t row = cell_lin(G, 0, yy, zz);
-                    const uint32_t s = cell_start[row + x0], e = cell_start[row + x1 + 1];
-                    if (COUNT) { npts += e - s; nruns += 1; }
-                    for (uint32_t p = s; p < e; p++) {
-                        const float4 P = pts[p];
-                        c += dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz) <= r2 ? 1u : 0u;
-                    }
-                }
-        }
-        count[t] = c;
     }
     if (COUNT) {
         unsigned long long a = npts, b = nruns;

@@ -477,23 +477,19 @@ __device__ __forceinline__ bool pyr_nn_search_fast(const GridDesc &G, int nlev, 
 // The batch kernels for clouds that carry the pyramid: stage 0 of the cell-pruned search (the 2x2x2 block on the query's side of
 // its cell, as coop_stage0 in kernels.hpp -- it decides nearly every query that sits inside a dense region; skipped when the block
 // holds no point), then a walk for whatever it leaves undecided.  Same launch shape and arguments as nn_grid_coop_kernel: 8 lanes
-// per query, 32 queries per block, XCD-contiguous block order over the sorted batch.
-//   FAST = true : the fp32 walk; queries it cannot decide (near-ties) are appended to `todo` ({count, ticket, slots...})
-//   FAST = false: the exact walk, for every query (todo == nullptr) or for the listed slots only (a fixed grid strides over the
-//                 list; its last block to finish clears count and ticket for the next batch: no memset between batches, and a
-//                 captured graph replays correctly)
-template <bool COUNT, bool FAST>
+// per query, 32 queries per block, XCD-contiguous block order over the sorted batch.  The walk is the fp32 one; queries it cannot
+// decide (near-ties) are appended to `todo` ({count, ticket, slots...}) for nn_grid_pyr_todo_kernel's exact walk
+template <bool COUNT>
 __device__ __forceinline__ void pyr_answer(const GridDesc &G, const PyrDesc &PD, const uint32_t *s_off, const PyrNode *__restrict__ nodes,
                                            const unsigned char *__restrict__ hint, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
                                            const float *__restrict__ q, uint32_t index_base, const float4 *__restrict__ qsorted, uint32_t slot,
-                                           uint32_t sub, uint32_t *__restrict__ out_idx, double *__restrict__ out_d2, int sorted_out,
-                                           uint32_t *__restrict__ todo, uint32_t &npts, uint32_t &nruns, uint32_t &nnodes)
+                                           uint32_t sub, uint32_t *__restrict__ out_idx, double *__restrict__ out_d2, uint32_t *__restrict__ todo, uint32_t &npts, uint32_t &nruns, uint32_t &nnodes)
 {
     uint32_t t = slot;
     float qxf, qyf, qzf;
     if (qsorted) {
         const float4 R = qsorted[slot];
-        qxf = R.x; qyf = R.y; qzf = R.z; t = sorted_out ? slot : __float_as_uint(R.w);
+        qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
     } else {
         qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
     }
@@ -536,19 +532,15 @@ __device__ __forceinline__ void pyr_answer(const GridDesc &G, const PyrDesc &PD,
         }
     }
     if (undecided) {
-        if (FAST) {
-            float lim;
-            if (!pyr_nn_search_fast<COUNT>(G, PD.nlev, s_off, nodes, pts, qxf, qyf, qzf, sub, cx, cy, cz, L0, xa, xb, ya, yb, za, zb, bd, bi, lim, npts, nruns, nnodes)) {
-                // (measured: the exact walk right here instead of a list costs the kernel its registers: 1.15 against 1.18e9 q/s)
-                if (sub == 0) {
-                    const uint32_t e = atomicAdd(&todo[0], 1u);
-                    todo[2u + 2u * e] = slot;
-                    todo[3u + 2u * e] = __float_as_uint(lim);
-                }
-                return;
+        float lim;
+        if (!pyr_nn_search_fast<COUNT>(G, PD.nlev, s_off, nodes, pts, qxf, qyf, qzf, sub, cx, cy, cz, L0, xa, xb, ya, yb, za, zb, bd, bi, lim, npts, nruns, nnodes)) {
+            // (measured: the exact walk right here instead of a list costs the kernel its registers: 1.15 against 1.18e9 q/s)
+            if (sub == 0) {
+                const uint32_t e = atomicAdd(&todo[0], 1u);
+                todo[2u + 2u * e] = slot;
+                todo[3u + 2u * e] = __float_as_uint(lim);
             }
-        } else {
-            pyr_nn_search<COUNT>(G, PD.nlev, s_off, nodes, pts, qxf, qyf, qzf, sub, cx, cy, cz, L0, xa, xb, ya, yb, za, zb, bd, bi, npts, nruns, nnodes);
+            return;
         }
     }
     if (sub == 0) {
@@ -575,20 +567,14 @@ __device__ __forceinline__ void pyr_commit_work(uint32_t npts, uint32_t nruns, u
     }
 }
 
-#ifndef PCT_AB_PYR_WAVES
-#define PCT_AB_PYR_WAVES 6      // minimum 6, maximum 8: the current text lands at 63 VGPRs = 8 waves; CAPPING it at 7 / 6 / 5 waves per SIMD gives
-                                // 1.14 / 1.07 / 0.97e9 q/s against 1.19-1.20e9 on the 10 M pillar cloud (profiles/r03_ab_occupancy_cap.txt)
-#endif
-template <bool COUNT, bool FAST>
-#ifndef PCT_AB_PYR_WAVES_MAX
-#define PCT_AB_PYR_WAVES_MAX 8
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PCT_AB_PYR_WAVES, PCT_AB_PYR_WAVES_MAX))) void nn_grid_pyr_kernel(GridDesc G, PyrDesc PD, const PyrNode *__restrict__ nodes, const unsigned char *__restrict__ hint,
+// waves per SIMD: minimum 6, maximum 8.  The kernel lands at 63 VGPRs = 8 waves; CAPPING it at 7 / 6 / 5 waves per SIMD gives
+// 1.14 / 1.07 / 0.97e9 q/s against 1.19-1.20e9 on the 10 M pillar cloud (profiles/r03_ab_occupancy_cap.txt)
+template <bool COUNT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void nn_grid_pyr_kernel(GridDesc G, PyrDesc PD, const PyrNode *__restrict__ nodes, const unsigned char *__restrict__ hint,
                                                           const float4 *__restrict__ pts,
                                                           const uint32_t *__restrict__ cell_start, const float *__restrict__ q, uint32_t Q,
                                                           uint32_t index_base, const float4 *__restrict__ qsorted, uint32_t *__restrict__ out_idx,
-                                                          double *__restrict__ out_d2, WorkCounters *__restrict__ work, int sorted_out,
-                                                          uint32_t *__restrict__ todo)
+                                                          double *__restrict__ out_d2, WorkCounters *__restrict__ work, uint32_t *__restrict__ todo)
 {
     __shared__ uint32_t s_off[kPyrMaxLevels];
     if (threadIdx.x < (uint32_t)kPyrMaxLevels) s_off[threadIdx.x] = PD.off[threadIdx.x];
@@ -598,7 +584,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PCT_AB_PYR_
     const uint32_t slot = bslot * (256 / kCoop) + (threadIdx.x / kCoop);
     uint32_t npts = 0, nruns = 0, nnodes = 0;
     if (slot < Q)                                     // uniform within a group of 8 lanes
-        pyr_answer<COUNT, FAST>(G, PD, s_off, nodes, hint, pts, cell_start, q, index_base, qsorted, slot, sub, out_idx, out_d2, sorted_out, todo, npts, nruns, nnodes);
+        pyr_answer<COUNT>(G, PD, s_off, nodes, hint, pts, cell_start, q, index_base, qsorted, slot, sub, out_idx, out_d2, todo, npts, nruns, nnodes);
 #ifdef PCT_AB_ITERSTAT
     if (COUNT) {                                      // `runs` := 8 x the longest walk of the wave (what the wave pays), `points` := the walks' own lengths
         uint32_t m = npts;
@@ -616,7 +602,7 @@ __global__ __launch_bounds__(256) void nn_grid_pyr_todo_kernel(GridDesc G, PyrDe
                                                                const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
                                                                const float *__restrict__ q, uint32_t index_base, const float4 *__restrict__ qsorted,
                                                                uint32_t *__restrict__ out_idx, double *__restrict__ out_d2, WorkCounters *__restrict__ work,
-                                                               int sorted_out, uint32_t *__restrict__ todo)
+                                                               uint32_t *__restrict__ todo)
 {
     __shared__ uint32_t s_off[kPyrMaxLevels];
     __shared__ uint32_t s_count;
@@ -634,7 +620,7 @@ __global__ __launch_bounds__(256) void nn_grid_pyr_todo_kernel(GridDesc G, PyrDe
         float qxf, qyf, qzf;
         if (qsorted) {
             const float4 R = qsorted[slot];
-            qxf = R.x; qyf = R.y; qzf = R.z; t = sorted_out ? slot : __float_as_uint(R.w);
+            qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
         } else {
             qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
         }

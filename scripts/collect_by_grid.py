@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-launch-shape summary of one kernel from a rocprofv3 output directory made by scripts/prof_r2.sh: the same kernel name covers
+"""Per-launch-shape summary of one kernel from a rocprofv3 --kernel-trace output directory: the same kernel name covers
 very different launches (a 4096-query and a 1 M-query batch, the 10 M- and the 100 M-point cloud), so durations and PMC counters
 are grouped by (kernel, grid size).  usage: collect_by_grid.py <dir> <kernel substring> [...]  -> JSON on stdout"""
 import collections, csv, glob, json, os, sys

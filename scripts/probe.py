@@ -86,7 +86,7 @@ if what == "sort":   # batch vs kernel-only time with the default grid (env knob
     for Q in (1 << 16, 1 << 18, 1 << 20):
         med, mn = timeit(Q, E.ALGO_GRID, reps=20)
         kmed, kmn = timeit(Q, E.ALGO_GRID, reps=20, batch=False)
-        print(f"sort probe fine={os.environ.get('PCT_SORT_FINE', '1')} shift={os.environ.get('PCT_BIN_SHIFT', '1')} Q={Q:8d} batch median={med*1e3:7.1f}us min={mn*1e3:7.1f}us  kernel median={kmed*1e3:7.1f}us min={kmn*1e3:7.1f}us", flush=True)
+        print(f"sort probe shift={os.environ.get('PCT_BIN_SHIFT', '1')} Q={Q:8d} batch median={med*1e3:7.1f}us min={mn*1e3:7.1f}us  kernel median={kmed*1e3:7.1f}us min={kmn*1e3:7.1f}us", flush=True)
 
 if what == "octant":   # 2x2x2-block-first search vs cube-first, over cell sizes
     for ppc in (1.0, 2.0, 3.0, 4.0, 6.0, 8.0):

@@ -1,5 +1,5 @@
 """Index build time (pct_cloud_build_grid: bounding box + counting sort into cells) for the C2 / C3 / C4 clouds, wall clock around the
-call (it ends with a stream synchronise).  PCT_LDS_GRID_BUILD=0 selects the per-point-atomic build for comparison."""
+call (it ends with a stream synchronise)."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
