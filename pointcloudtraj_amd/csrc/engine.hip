@@ -157,12 +157,6 @@ struct pct_cloud {
     uint4 *blocks = nullptr;                 // block table (kernels.hpp block_corner_kernel): 2 x uint4 per lattice corner
     size_t blocks_cap = 0;
     BinDesc B{};
-    // optional coarser copies of the index (clouds with sparse occupancy), see kernels.hpp CoarseLevels
-    CoarseLevels C{};
-    uint32_t *coarse_cell_start[kMaxCoarse] = { nullptr, nullptr, nullptr };
-    size_t coarse_cells_cap[kMaxCoarse] = { 0, 0, 0 };
-    float4 *coarse_sorted[kMaxCoarse] = { nullptr, nullptr, nullptr };
-    size_t coarse_sorted_cap[kMaxCoarse] = { 0, 0, 0 };
     float4 *d_qsorted = nullptr;                                                // {x,y,z,id} records of the sorted batch (reserve_queries)
     uint32_t *d_sort1 = nullptr;                                                // total1 | total1 (second set) | fill1
     int sort_phase = 0;                                                         // which set of totals the next batch adds into
@@ -363,23 +357,23 @@ int finish_build(pct_cloud *c, const GridDesc &G, hipError_t e, hipStream_t s)
     return PCT_OK;
 }
 
-// counting sort of the cloud into the cells of G: cell_start (ncells+1 prefix) and the float4 {x,y,z,index} copy in cell order
-int sort_into_cells(pct_cloud *c, const GridDesc &G, uint32_t **cell_start, size_t *cells_cap, float4 **sorted, size_t *sorted_cap)
+// counting sort of the cloud into the cells of G: c->cell_start (ncells+1 prefix) and c->sorted, the float4 {x,y,z,index} copy in cell order
+int sort_into_cells(pct_cloud *c, const GridDesc &G)
 {
     hipStream_t s = g_stream;
     const int64_t n = c->count;
     const uint64_t ncells = G.ncells;
-    if (ncells + 1 > *cells_cap) {
-        dev_free(*cell_start);
-        *cells_cap = 0;
-        PCTCHK(dev_alloc(cell_start, ncells + 1));
-        *cells_cap = ncells + 1;
+    if (ncells + 1 > c->cells_cap) {
+        dev_free(c->cell_start);
+        c->cells_cap = 0;
+        PCTCHK(dev_alloc(&c->cell_start, ncells + 1));
+        c->cells_cap = ncells + 1;
     }
-    if ((size_t)n > *sorted_cap) {
-        dev_free(*sorted);
-        *sorted_cap = 0;
-        PCTCHK(dev_alloc(sorted, (size_t)n + kGridPad));         // + spare records behind the last one (gridbuild.hpp)
-        *sorted_cap = (size_t)n;
+    if ((size_t)n > c->sorted_cap) {
+        dev_free(c->sorted);
+        c->sorted_cap = 0;
+        PCTCHK(dev_alloc(&c->sorted, (size_t)n + kGridPad));         // + spare records behind the last one (gridbuild.hpp)
+        c->sorted_cap = (size_t)n;
     }
     // ---- two-level counting sort on LDS histograms (gridbuild.hpp): no device-scope atomic per point ----
     // slabs of 2^s1 consecutive cells, sized for ~2-6 k points each (level 2 then holds a whole slab in LDS), at most kGbMaxSlabs;
@@ -457,13 +451,13 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G, uint32_t **cell_start, size
             {
                 const size_t ldsA = sizeof(uint32_t) * ((size_t)DA.nslabs + 1);
                 gb_hist_kernel<<<blocks, kGbThreads, ldsA, s>>>(G, DA, c->x, c->y, c->z, (uint32_t)n, tableA, super_total);
-                gb_scatter_kernel<<<blocks, kGbThreads, ldsA, s>>>(G, DA, c->x, c->y, c->z, (uint32_t)n, tableA, super_total, super_cursor, super_start, *sorted);
+                gb_scatter_kernel<<<blocks, kGbThreads, ldsA, s>>>(G, DA, c->x, c->y, c->z, (uint32_t)n, tableA, super_total, super_cursor, super_start, c->sorted);
                 const dim3 g2(DB.parts, DB.nsuper);
-                gb_hist2_kernel<<<g2, kGbThreads, 0, s>>>(G, DB, super_start, *sorted, table2, slab_total);
-                gb_scatter2_kernel<<<g2, kGbThreads, 0, s>>>(G, DB, super_start, *sorted, table2, slab_total, slab_cursor, slab_start, (uint32_t)n, c->gb_tmp);
-                if (cthreads == 256) gb_cells_kernel<256><<<(int)D.nslabs, 256, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, *cell_start, *sorted, c->d_gbcheck);
-                else if (cthreads == 512) gb_cells_kernel<512><<<(int)D.nslabs, 512, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, *cell_start, *sorted, c->d_gbcheck);
-                else gb_cells_kernel<1024><<<(int)D.nslabs, 1024, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, *cell_start, *sorted, c->d_gbcheck);
+                gb_hist2_kernel<<<g2, kGbThreads, 0, s>>>(G, DB, super_start, c->sorted, table2, slab_total);
+                gb_scatter2_kernel<<<g2, kGbThreads, 0, s>>>(G, DB, super_start, c->sorted, table2, slab_total, slab_cursor, slab_start, (uint32_t)n, c->gb_tmp);
+                if (cthreads == 256) gb_cells_kernel<256><<<(int)D.nslabs, 256, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, c->cell_start, c->sorted, c->d_gbcheck);
+                else if (cthreads == 512) gb_cells_kernel<512><<<(int)D.nslabs, 512, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, c->cell_start, c->sorted, c->d_gbcheck);
+                else gb_cells_kernel<1024><<<(int)D.nslabs, 1024, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, c->cell_start, c->sorted, c->d_gbcheck);
                 e = hipGetLastError();
             }
             return finish_build(c, G, e, s);
@@ -475,9 +469,9 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G, uint32_t **cell_start, size
         {
             gb_hist_kernel<<<blocks, kGbThreads, lds1, s>>>(G, D, c->x, c->y, c->z, (uint32_t)n, table, slab_total);
             gb_scatter_kernel<<<blocks, kGbThreads, lds1, s>>>(G, D, c->x, c->y, c->z, (uint32_t)n, table, slab_total, slab_cursor, slab_start, c->gb_tmp);
-            if (cthreads == 256) gb_cells_kernel<256><<<(int)D.nslabs, 256, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, *cell_start, *sorted, c->d_gbcheck);
-            else if (cthreads == 512) gb_cells_kernel<512><<<(int)D.nslabs, 512, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, *cell_start, *sorted, c->d_gbcheck);
-            else gb_cells_kernel<1024><<<(int)D.nslabs, 1024, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, *cell_start, *sorted, c->d_gbcheck);
+            if (cthreads == 256) gb_cells_kernel<256><<<(int)D.nslabs, 256, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, c->cell_start, c->sorted, c->d_gbcheck);
+            else if (cthreads == 512) gb_cells_kernel<512><<<(int)D.nslabs, 512, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, c->cell_start, c->sorted, c->d_gbcheck);
+            else gb_cells_kernel<1024><<<(int)D.nslabs, 1024, lds2, s>>>(G, D, slab_start, c->gb_tmp, (uint32_t)n, stage_cap, c->cell_start, c->sorted, c->d_gbcheck);
             e = hipGetLastError();
         }
         return finish_build(c, G, e, s);
@@ -493,15 +487,15 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G, uint32_t **cell_start, size
     const int pblocks = (int)std::min<int64_t>(4096, (n + 255) / 256);
     if (e == hipSuccess) {
         cell_histogram_kernel<<<pblocks, 256, 0, s>>>(G, c->x, c->y, c->z, (uint32_t)n, d_cnt, d_pcell);
-        scan_tiles_kernel<<<ntiles, 256, 0, s>>>(d_cnt, (uint32_t)ncells, *cell_start, d_tiles);
+        scan_tiles_kernel<<<ntiles, 256, 0, s>>>(d_cnt, (uint32_t)ncells, c->cell_start, d_tiles);
         scan_tile_sums_kernel<<<1, 256, 0, s>>>(d_tiles, ntiles);
-        scan_add_kernel<<<ceil_div((int64_t)ncells, 256), 256, 0, s>>>(*cell_start, (uint32_t)ncells, d_tiles, (uint32_t)n);
+        scan_add_kernel<<<ceil_div((int64_t)ncells, 256), 256, 0, s>>>(c->cell_start, (uint32_t)ncells, d_tiles, (uint32_t)n);
         e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * ncells, s);
     }
     if (e == hipSuccess) {
-        cell_scatter_kernel<<<pblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_pcell, *cell_start, d_cnt, *sorted);
+        cell_scatter_kernel<<<pblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_pcell, c->cell_start, d_cnt, c->sorted);
         gb_zero_kernel<<<1, 64, 0, s>>>(nullptr, 0, c->d_gbcheck);
-        gb_check_kernel<<<(int)std::min<int64_t>(1024, (std::max<int64_t>(n, (int64_t)ncells) + 255) / 256), 256, 0, s>>>(G, *sorted, *cell_start, (uint32_t)n, c->d_gbcheck);
+        gb_check_kernel<<<(int)std::min<int64_t>(1024, (std::max<int64_t>(n, (int64_t)ncells) + 255) / 256), 256, 0, s>>>(G, c->sorted, c->cell_start, (uint32_t)n, c->d_gbcheck);
         e = hipGetLastError();
     }
     st = finish_build(c, G, e, s);
@@ -1172,7 +1166,6 @@ int pct_cloud_destroy(pct_cloud *c)
     dev_free(c->x); dev_free(c->y); dev_free(c->z); dev_free(c->d_stage); dev_free(c->gb_tmp); dev_free(c->gb_small);
     dev_free(c->blocks);
     dev_free(c->cell_start); dev_free(c->sorted);
-    for (int l = 0; l < kMaxCoarse; l++) { dev_free(c->coarse_cell_start[l]); dev_free(c->coarse_sorted[l]); }
     dev_free(c->d_qsorted); dev_free(c->d_sort1); dev_free(c->d_todo);
     dev_free(c->d_q); dev_free(c->d_r); dev_free(c->d_q64); dev_free(c->d_r2); dev_free(c->d_d2); dev_free(c->d_radius);
     dev_free(c->d_pts64); dev_free(c->d_idx); dev_free(c->d_count); dev_free(c->d_skip); dev_free(c->d_bound);
@@ -1395,43 +1388,8 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     G.ncells = (uint32_t)ncells;
 
     // 3. counting sort
-    PCTCHK(sort_into_cells(c, G, &c->cell_start, &c->cells_cap, &c->sorted, &c->sorted_cap));
+    PCTCHK(sort_into_cells(c, G));
     PCTCHK(build_pyramid(c, G));
-    // 4. sparse occupancy (points on surfaces): add coarser levels so free-space queries do not walk empty fine shells
-    c->C.n = 0;
-    {
-        // OFF by default (threshold > 1): measured on the seed-6 pillar map the coarse cubes cut the cell rows visited per
-        // free-space query from 307 to 17 but raise the points examined from 869 to 18 000 (a cube four times wider holds
-        // sixteen times more SURFACE points), 3.5x slower overall -- walking fine shells is the better trade for surface
-        // clouds.  Kept selectable (PCT_PYRAMID_EMPTY_FRAC=0.5) and covered by tests for volumetric sparse clouds.
-        double sparse_at = 2.0;
-        if (const char *ev = std::getenv("PCT_PYRAMID_EMPTY_FRAC")) sparse_at = std::atof(ev);
-        uint32_t n_empty = 0;
-        if (sparse_at < 1.0) {                 // the occupancy count (a launch + a host round trip) only when the levels can be asked for
-            uint32_t *d_empty = nullptr;
-            PCTCHK(dev_alloc(&d_empty, 1));
-            hipError_t e2 = hipMemsetAsync(d_empty, 0, sizeof(uint32_t), s);
-            count_empty_cells_kernel<<<(int)std::min<uint64_t>(1024, (ncells + 255) / 256), 256, 0, s>>>(c->cell_start, (uint32_t)ncells, d_empty);
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(&n_empty, d_empty, sizeof n_empty, hipMemcpyDeviceToHost, s);
-            if (e2 == hipSuccess) e2 = hipStreamSynchronize(s);
-            dev_free(d_empty);
-            if (e2 != hipSuccess) return fail(PCT_ERR_HIP, "occupancy count failed: %s", hipGetErrorString(e2));
-        }
-        if ((double)n_empty > sparse_at * (double)ncells && ncells > 512) {
-            GridDesc L = G;
-            for (int l = 0; l < kMaxCoarse && std::max({ L.gx, L.gy, L.gz }) > 3; l++) {
-                L.hd *= 4.0;
-                L.inv_h = (float)(1.0 / L.hd);
-                L.gx = (L.gx + 3) / 4; L.gy = (L.gy + 3) / 4; L.gz = (L.gz + 3) / 4;
-                L.ncells = (uint32_t)L.gx * (uint32_t)L.gy * (uint32_t)L.gz;
-                PCTCHK(sort_into_cells(c, L, &c->coarse_cell_start[l], &c->coarse_cells_cap[l], &c->coarse_sorted[l], &c->coarse_sorted_cap[l]));
-                c->C.G[l] = L;
-                c->C.pts[l] = c->coarse_sorted[l];
-                c->C.cell_start[l] = c->coarse_cell_start[l];
-                c->C.n = l + 1;
-            }
-        }
-    }
     G.octant_first = 1;
     if (const char *eo = std::getenv("PCT_OCTANT_FIRST")) G.octant_first = std::atoi(eo) != 0;
     // block table for stage 0 of the dense batch kernel (kernels.hpp block_corner_kernel).  OFF by default -- measured slower on the
@@ -1507,7 +1465,7 @@ int pct_nn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, uint32_
     if (Q <= kExpressMaxQ && c->has_grid && c->count > 0 && (algo == PCT_ALGO_AUTO || algo == PCT_ALGO_GRID)) {
         // small batch on an indexed cloud: one launch, a block per query, arguments/results in mapped memory
         for (int64_t i = 0; i < 3 * Q; i++) c->h_xin[i] = (double)q[i];
-        inflate_block_kernel<false><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, c->C, InflateParams{}, c->d_xin, (double)INFINITY,
+        inflate_block_kernel<false><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, InflateParams{}, c->d_xin, (double)INFINITY,
                                                                    (uint32_t)c->index_base, c->d_xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
@@ -1810,7 +1768,7 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
         // idx / d2 not wanted: the search may stop once everything unseen is beyond max_radius + search_margin
         const double reach = p->max_radius + p->search_margin;
         const double stop_d2 = (idx || d2) ? (double)INFINITY : reach * reach;
-        inflate_block_kernel<true><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, c->C, to_dev(p), c->d_xin, stop_d2, (uint32_t)c->index_base, c->d_xout, next_signal(c));
+        inflate_block_kernel<true><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, to_dev(p), c->d_xin, stop_d2, (uint32_t)c->index_base, c->d_xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
         for (int64_t i = 0; i < Q; i++) {
@@ -1864,7 +1822,7 @@ int pct_rrt_expand_batch(pct_cloud *nodes, pct_cloud *obstacles, const pct_infla
     std::memcpy(nodes->h_xin, samples, sizeof(double) * 3 * K);
     const double reach = p->max_radius + p->search_margin;       // only the radius is wanted: stop once everything unseen is beyond it
     rrt_expand_kernel<<<(int)K, 256, 0, g_stream>>>(nodes->x, nodes->y, nodes->z, (uint32_t)nodes->count, nodes->d_aux, nodes->d_xin,
-                                                    obstacles->G, obstacles->sorted, obstacles->cell_start, obstacles->C,
+                                                    obstacles->G, obstacles->sorted, obstacles->cell_start,
                                                     obstacles->count == 0 ? 1 : 0, to_dev(p), reach * reach, nodes->d_xids, cap, nodes->d_eout,
                                                     K <= 8 ? next_signal(nodes) : ExpressSignal{});
     HIPCHK(hipGetLastError());
@@ -1938,7 +1896,7 @@ int pct_bezier_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflat
             if (c->has_grid && c->count > 0) {        // indexed cloud: everything in ONE launch
                 const double reach = p->max_radius + p->search_margin;
                 const double stop_d2 = (idx || d2) ? (double)INFINITY : reach * reach;
-                bezier_block_kernel<<<(int)m, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, c->C, to_dev(p), c->d_xin, (int)traj->row_stride,
+                bezier_block_kernel<<<(int)m, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, to_dev(p), c->d_xin, (int)traj->row_stride,
                                                                    c->d_xin + ncoef, c->d_xids, c->d_xids + traj->nseg, c->d_xin + ncoef + traj->nseg,
                                                                    stop_d2, (uint32_t)c->index_base, c->d_xout, c->d_bpos, next_signal(c));
                 HIPCHK(hipGetLastError());

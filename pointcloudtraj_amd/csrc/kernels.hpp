@@ -868,28 +868,6 @@ __global__ __launch_bounds__(256) void block_corner_kernel(GridDesc G, const uin
     blocks[2u * i + 1u] = make_uint4(e[0], e[1], e[2], e[3]);
 }
 
-// OPTIONAL coarser copies of the index (cell size x4 per level, same origin), used only by the block-per-query
-// express kernel: a query that finds nothing decisive in its 3x3x3 fine cells tries the 3x3x3 cells of each coarser
-// level before expanding shell by shell at the coarsest level.  n = 0: no pyramid (the default, see engine.hip).
-constexpr int kMaxCoarse = 3;
-struct CoarseLevels {
-    int n;
-    GridDesc G[kMaxCoarse];
-    const float4 *pts[kMaxCoarse];
-    const uint32_t *cell_start[kMaxCoarse];
-};
-
-__global__ __launch_bounds__(256) void count_empty_cells_kernel(const uint32_t *__restrict__ cell_start, uint32_t ncells,
-                                                                uint32_t *__restrict__ n_empty)
-{
-    uint32_t c = 0;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ncells; i += stride) c += cell_start[i + 1] == cell_start[i] ? 1u : 0u;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off, kWave);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(n_empty, c);
-}
-
 // per-block min/max -> partials[block][6]
 __global__ __launch_bounds__(256) void bbox_partial_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                            const float *__restrict__ z, uint32_t n,
@@ -2113,25 +2091,20 @@ __device__ __forceinline__ void block_argmin256(double &d, uint32_t &i, double *
 // Same arithmetic and the same termination bound as coop_nn_search.
 // INFLATE = false: plain nearest neighbour of the (fp32-valued) points in qpts -- no early-out, no radius.
 // The block-wide search itself: nearest obstacle point of the fp32-narrowed (px, py, pz); every thread returns the winner.
-__device__ __forceinline__ void block_nn_search(const GridDesc &G0, const float4 *__restrict__ pts0, const uint32_t *__restrict__ cs0,
-                                                const CoarseLevels &C, double px, double py, double pz, double stop_d2,
-                                                double *s_d, uint32_t *s_i, double &bd, uint32_t &bi)
+__device__ __forceinline__ void block_nn_search(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
+                                                double px, double py, double pz, double stop_d2, double *s_d, uint32_t *s_i, double &bd,
+                                                uint32_t &bi)
 {
     const uint32_t sub = threadIdx.x & (kCoop - 1), grp = threadIdx.x / kCoop;   // 32 groups
     const float qxf = (float)px, qyf = (float)py, qzf = (float)pz;                    // searchPoint.x = search_Pt(0), :125-128
     const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
+    const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
+    const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
+    const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
     bd = __builtin_huge_val();
     bi = kNoIndex;
-    // steps: cube r=1 of the fine level, cube r=1 of every coarser level, then shells r=2,3,.. of the coarsest level
-    for (int step = 0;; step++) {
-        const int lvl = min(step, C.n);                       // 0 = fine, 1..C.n = coarse level lvl-1
-        const int r = step <= C.n ? 1 : step - C.n + 1;
-        const GridDesc &G = lvl == 0 ? G0 : C.G[lvl - 1];
-        const float4 *pts = lvl == 0 ? pts0 : C.pts[lvl - 1];
-        const uint32_t *cell_start = lvl == 0 ? cs0 : C.cell_start[lvl - 1];
-        const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
-        const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
-        const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
+    // the cube r = 1, then the shells r = 2, 3, ..
+    for (int r = 1;; r++) {
         const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
         const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
         const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
@@ -2154,8 +2127,8 @@ __device__ __forceinline__ void block_nn_search(const GridDesc &G0, const float4
 }
 
 template <bool INFLATE>
-__global__ __launch_bounds__(256) void inflate_block_kernel(GridDesc G0, const float4 *__restrict__ pts0,
-                                                            const uint32_t *__restrict__ cs0, CoarseLevels C, InflateParams P,
+__global__ __launch_bounds__(256) void inflate_block_kernel(GridDesc G, const float4 *__restrict__ pts,
+                                                            const uint32_t *__restrict__ cell_start, InflateParams P,
                                                             const double *__restrict__ qpts, double stop_d2, uint32_t index_base,
                                                             ExpressOut *__restrict__ out, ExpressSignal sig)
 {
@@ -2172,7 +2145,7 @@ __global__ __launch_bounds__(256) void inflate_block_kernel(GridDesc G0, const f
     }
     double bd;
     uint32_t bi;
-    block_nn_search(G0, pts0, cs0, C, px, py, pz, stop_d2, s_d, s_i, bd, bi);
+    block_nn_search(G, pts, cell_start, px, py, pz, stop_d2, s_d, s_i, bd, bi);
     if (threadIdx.x == 0) {
         if (INFLATE) {
             const double rr = sqrt(bd) - P.search_margin;
@@ -2198,8 +2171,8 @@ struct ExpandOut { double cx, cy, cz, radius; uint32_t near_idx, count; };
 __global__ __launch_bounds__(256) void rrt_expand_kernel(const float *__restrict__ nx, const float *__restrict__ ny,
                                                          const float *__restrict__ nz, uint32_t n_nodes,
                                                          const double *__restrict__ node_aux, const double *__restrict__ samples,
-                                                         GridDesc G0, const float4 *__restrict__ pts0, const uint32_t *__restrict__ cs0,
-                                                         CoarseLevels C, int obstacles_empty, InflateParams P, double stop_d2,
+                                                         GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
+                                                         int obstacles_empty, InflateParams P, double stop_d2,
                                                          uint32_t *__restrict__ ids, uint32_t cap_per_query, ExpandOut *__restrict__ out,
                                                          ExpressSignal sig)
 {
@@ -2242,7 +2215,7 @@ __global__ __launch_bounds__(256) void rrt_expand_kernel(const float *__restrict
         } else {
             double od;
             uint32_t oi;
-            block_nn_search(G0, pts0, cs0, C, cx, cy, cz, stop_d2, s_d, s_i, od, oi);
+            block_nn_search(G, pts, cell_start, cx, cy, cz, stop_d2, s_d, s_i, od, oi);
             const double rr = sqrt(od) - P.search_margin;
             radius = rr < P.max_radius ? rr : P.max_radius;
         }
@@ -2352,8 +2325,8 @@ __global__ __launch_bounds__(256) void bezier_samples_kernel(BezierDesc B, doubl
 // per sample; the block evaluates getPosFromBezier with one thread per Bernstein term (two pow calls each, the terms then
 // summed by one thread in the reference's j order), applies the inflation early-out and runs the block-wide cell search.
 // Arguments and results live in host-mapped memory; the host picks the first sample with a negative radius.
-__global__ __launch_bounds__(256) void bezier_block_kernel(GridDesc G0, const float4 *__restrict__ pts0, const uint32_t *__restrict__ cs0,
-                                                           CoarseLevels C, InflateParams P, const double *__restrict__ coef, int row_stride,
+__global__ __launch_bounds__(256) void bezier_block_kernel(GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
+                                                           InflateParams P, const double *__restrict__ coef, int row_stride,
                                                            const double *__restrict__ seg_time, const uint32_t *__restrict__ orders,
                                                            const uint32_t *__restrict__ sample_seg, const double *__restrict__ sample_t,
                                                            double stop_d2, uint32_t index_base, ExpressOut *__restrict__ out,
@@ -2390,7 +2363,7 @@ __global__ __launch_bounds__(256) void bezier_block_kernel(GridDesc G0, const fl
     }
     double bd;
     uint32_t bi;
-    block_nn_search(G0, pts0, cs0, C, px, py, pz, stop_d2, s_d, s_i, bd, bi);
+    block_nn_search(G, pts, cell_start, px, py, pz, stop_d2, s_d, s_i, bd, bi);
     if (threadIdx.x == 0) {
         const double rr = sqrt(bd) - P.search_margin;
         out[slot].radius = rr < P.max_radius ? rr : P.max_radius;

@@ -381,8 +381,8 @@ struct ReplanMeet { uint32_t ticket; int32_t first_sample, first_ctrl; uint32_t 
 constexpr size_t kReplanHdrSlot = 256;          // bytes per header slot in the argument block
 
 template <bool RING>
-__global__ __launch_bounds__(256) void replan_block_kernel(RingView V, GridDesc G0, const float4 *__restrict__ pts0,
-                                                           const uint32_t *__restrict__ cs0, CoarseLevels C, int static_count,
+__global__ __launch_bounds__(256) void replan_block_kernel(RingView V, GridDesc G, const float4 *__restrict__ pts,
+                                                           const uint32_t *__restrict__ cell_start, int static_count,
                                                            const ReplanHeader *__restrict__ hdr, const double *__restrict__ f64a,
                                                            const uint32_t *__restrict__ u32a, uint32_t index_base,
                                                            ExpressOut *__restrict__ out, double *__restrict__ pos_out,
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(256) void replan_block_kernel(RingView V, GridDesc 
         const double reach = P.max_radius + P.search_margin;
         const double stop_d2 = H.want_nn ? __builtin_huge_val() : reach * reach;
         if (RING) ring_block_nn_search(V, px, py, pz, stop_d2, s_d, s_i, bd, bi);
-        else block_nn_search(G0, pts0, cs0, C, px, py, pz, stop_d2, s_d, s_i, bd, bi);
+        else block_nn_search(G, pts, cell_start, px, py, pz, stop_d2, s_d, s_i, bd, bi);
         const double rr = sqrt(bd) - P.search_margin;
         radius = rr < P.max_radius ? rr : P.max_radius;
     }

@@ -415,10 +415,10 @@ int replan_enqueue(pct_cloud *c, ReplanCtx *x, hipStream_t s)
     // ONE kernel: every block writes its result where the caller reads it (d_res_host: host-mapped memory, or the device buffer
     // the copies below take) and the last one to finish adds the summary and the sequence word
     if (c->ring_ready)
-        replan_block_kernel<true><<<blocks, 256, 0, s>>>(ring_view(c), GridDesc{}, nullptr, nullptr, CoarseLevels{}, 0, dh, f64a, u32a, (uint32_t)c->index_base,
+        replan_block_kernel<true><<<blocks, 256, 0, s>>>(ring_view(c), GridDesc{}, nullptr, nullptr, 0, dh, f64a, u32a, (uint32_t)c->index_base,
                                                          x->d_res_host, x->d_pos, x->d_meet, x->d_sum);
     else
-        replan_block_kernel<false><<<blocks, 256, 0, s>>>(RingView{}, c->G, c->sorted, c->cell_start, c->C, (int)std::min<int64_t>(c->count, 1), dh, f64a, u32a,
+        replan_block_kernel<false><<<blocks, 256, 0, s>>>(RingView{}, c->G, c->sorted, c->cell_start, (int)std::min<int64_t>(c->count, 1), dh, f64a, u32a,
                                                           (uint32_t)c->index_base, x->d_res_host, x->d_pos, x->d_meet, x->d_sum);
     replan_empty_kernel<<<1, 1, 0, s>>>(dh, x->d_meet, x->d_sum);
     if (x->copies) {

@@ -488,16 +488,14 @@ def test_pointcloud2_payload(E, oracle):
     c.close()
 
 
-@pytest.mark.parametrize("mode", ["boxes", "shells", "coarse"])
+@pytest.mark.parametrize("mode", ["boxes", "shells"])
 def test_sparse_occupancy_clouds(E, oracle, mode, monkeypatch):
     """Clouds whose points sit on surfaces (the reference's real input, map_generator.cpp:16-125): queries in free space (far from
     every point) and far outside the box must still return the exact neighbour, through the batch kernel and the express path --
-    with the bounding-box pyramid such clouds get by default (pyramid.hpp; it must also keep the work per query small), with plain
-    shell expansion (PCT_PYRAMID=0) and with the optional coarser index levels of the express kernel (PCT_PYRAMID_EMPTY_FRAC)."""
+    with the bounding-box pyramid such clouds get by default (pyramid.hpp; it must also keep the work per query small) and with plain
+    shell expansion (PCT_PYRAMID=0)."""
     if mode != "boxes":
         monkeypatch.setenv("PCT_PYRAMID", "0")
-    if mode == "coarse":
-        monkeypatch.setenv("PCT_PYRAMID_EMPTY_FRAC", "0.5")
     for pts in (synth.pillar_map(), synth.clustered_points(131, 300000, 0, 60)):
         lo, hi = pts.min(0), pts.max(0)
         u = synth.uniform01_f32(132, 3 * 30000).reshape(-1, 3)
