@@ -31,6 +31,25 @@
  * wins (the reference's winner on exact ties depends on tree shape).  Radius count:
  * d2 <= (double)r * (double)r, inclusive (kdtree.c:273).
  *
+ * Domain: ANY finite fp32 cloud and query, on every path.  The fp64 value above is finite for every pair of finite floats (at most
+ * ~1.4e78), so magnitudes decide nothing but speed: where the fp32 screening of a kernel overflows (separations beyond
+ * sqrt(FLT_MAX) = 1.8447e19) or underflows, the pairs concerned are decided in fp64 (parity section).
+ *
+ * Non-finite input (tests/test_numeric_edges.py, tests/test_gpu_numeric_edges.py) follows from the same comparisons, a NaN or
+ * infinite d2 being neither < +inf nor <= a finite r*r:
+ *   - a query with a NaN or infinite coordinate: status PCT_OK, idx = PCT_NO_INDEX, d2 = +inf, count 0 (under r*r = +inf: the
+ *     number of points whose d2 is +inf rather than NaN -- every finite point when the query holds no NaN); the other queries of
+ *     the batch are answered as without it.
+ *     Planner points (fp64) are narrowed to fp32 first, so |p| > FLT_MAX is such a query; pct_inflate_batch applies the
+ *     reference's early-out to it before any search (|p - start| = +inf > sample_range + max_radius: radius = max_radius -
+ *     search_margin; a NaN compares false there and yields radius = max_radius).
+ *   - a radius: r enters only as r*r -- a negative r counts as |r|, r = +/-inf counts every point at a finite d2, NaN counts none.
+ *   - a cloud row with a NaN or infinite coordinate is never a nearest neighbour and is counted only under r*r = +inf (and no NaN):
+ *     the brute-force paths (PCT_ALGO_STREAM, PCT_ALGO_STREAM_EXACT) and a rolling-map index created with an extent accept such
+ *     rows; pct_cloud_build_grid, and pct_cloud_ring_index without an extent on a cloud that already holds such a row, need the
+ *     data's bounding box and return PCT_ERR_INVALID ("cloud holds non-finite coordinates"), leaving the cloud as it was, without
+ *     an index.
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H

@@ -50,6 +50,9 @@ __global__ __launch_bounds__(256) void brute2_prep_kernel(CentreDesc C, const fl
         if (tf == 0.0f && tw > 0.0) tf = 1e-45f;
         thr = tf;
     }
+    // no finite bound (every sampled fp32 distance overflowed: a query beyond sqrt(FLT_MAX) of the cloud; a NaN query): everything is a
+    // candidate -- and the products pc * (-2 qc) would overflow to +/-inf and cancel to NaN, which passes no threshold: t := |pc|^2
+    if (!(thr < __builtin_huge_valf())) { qprep[i] = make_float4(0.0f, 0.0f, 0.0f, __builtin_huge_valf()); return; }
     qprep[i] = make_float4(-2.0f * qx, -2.0f * qy, -2.0f * qz, thr);
 }
 
@@ -204,6 +207,9 @@ __global__ __launch_bounds__(256) void brute2_prep_count_kernel(CentreDesc C, co
     if ((double)tf < tw) tf = __uint_as_float(__float_as_uint(tf) + (tf >= 0.0f ? 1u : 0xFFFFFFFFu));
     if (tf == 0.0f && tw > 0.0) tf = 1e-45f;
     if (!(B >= 0.0)) tf = -__builtin_huge_valf();                      // NaN radius: nothing is inside
+    // |qc| >= 1e18 (or not finite): pc * (-2 qc) may overflow and cancel to NaN (R <= 1e15, engine.hip use_expanded_filter), and so may
+    // sb * sb - Qc.  Such a query takes every point to the exact test (t := |pc|^2 against +inf) -- arbitrarily slow, never wrong
+    if (!(Qc < 1e36)) { qprep[i] = make_float4(0.0f, 0.0f, 0.0f, B >= 0.0 ? __builtin_huge_valf() : -__builtin_huge_valf()); return; }
     qprep[i] = make_float4(-2.0f * qx, -2.0f * qy, -2.0f * qz, tf);
 }
 

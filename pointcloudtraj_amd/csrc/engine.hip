@@ -1374,15 +1374,23 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     const double max_ext = std::max({ ext[0], ext[1], ext[2] });
     h = std::max(h, max_ext / 1023.0);
     if (!(h > 0)) h = 1.0;   // all points identical
+    // The fp32 cell assignment floor((v - o) * inv_h) must stay monotone in v and agree with the fp64 face positions the termination
+    // bounds use, whatever the magnitudes:
+    //  * inv_h = 1 / h must be finite and h a normal float: cells below 2^-120 are widened to that (coarser cells, same answers);
+    //  * v - o overflows to +inf beyond FLT_MAX (a bounding box wider than FLT_MAX: sentinel rows at both ends of the range) and is
+    //    clamped into the last cell, so the last cell must BEGIN at or below that threshold: at most floor(3.4e38 / h) + 1 cells per
+    //    axis.  The last cell is unbounded above for the search (no face beyond it), so it may hold everything from there on.
+    h = std::min(std::max(h, 0x1p-120), 0x1p120);
     const float hf = (float)h;
     GridDesc G{};
     G.ox = lo[0]; G.oy = lo[1]; G.oz = lo[2];
     G.inv_h = 1.0f / hf;
     G.oxd = lo[0]; G.oyd = lo[1]; G.ozd = lo[2];
     G.hd = (double)hf;
-    G.gx = std::max(1, std::min(1024, (int)std::floor(ext[0] / G.hd) + 1));
-    G.gy = std::max(1, std::min(1024, (int)std::floor(ext[1] / G.hd) + 1));
-    G.gz = std::max(1, std::min(1024, (int)std::floor(ext[2] / G.hd) + 1));
+    const int gmax = (int)std::min(1024.0, std::floor(3.4e38 / G.hd) + 1.0);
+    G.gx = std::max(1, std::min(gmax, (int)std::min(1024.0, std::floor(ext[0] / G.hd)) + 1));
+    G.gy = std::max(1, std::min(gmax, (int)std::min(1024.0, std::floor(ext[1] / G.hd)) + 1));
+    G.gz = std::max(1, std::min(gmax, (int)std::min(1024.0, std::floor(ext[2] / G.hd)) + 1));
     const uint64_t ncells = (uint64_t)G.gx * G.gy * G.gz;
     if (ncells > 0x7FFFFFF0ull) return fail(PCT_ERR_INVALID, "grid of %llu cells is too large", (unsigned long long)ncells);
     G.ncells = (uint32_t)ncells;

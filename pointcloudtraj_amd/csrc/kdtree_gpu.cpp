@@ -452,6 +452,7 @@ struct kdres *kd_nearest(struct kdtree *t, const double *q)
             if (pct_nodeset_radius_indices_r2(t->nodes, q, d2, tied.data(), (int64_t)tied.size(), &nt) != PCT_OK) { complain("kd_nearest (tie set)"); return nullptr; }
             if (nt > 1) idx = (uint32_t)reference_tie_winner(t, q, tied.data(), std::min<int64_t>(nt, (int64_t)tied.size()));
         }
+        if (idx == PCT_NO_INDEX) idx = 0;                 // non-finite query: see below
         kdres *r = new (std::nothrow) kdres();
         if (!r) return nullptr;
         r->tree = t;
@@ -469,6 +470,9 @@ struct kdres *kd_nearest(struct kdtree *t, const double *q)
         if (pct_radius_indices_r2_q64(t->cloud, q, d2, tied.data(), (int64_t)tied.size(), &nt) != PCT_OK) { complain("kd_nearest (tie set)"); return nullptr; }
         if (nt > 1) idx = (uint32_t)reference_tie_winner(t, q, tied.data(), std::min<int64_t>(nt, (int64_t)tied.size()));
     }
+    // a NaN / infinite query has no node at d2 < +inf (PCT_NO_INDEX): the reference keeps its initial guess, the root = node 0
+    // (kdtree.c:432-436), as host_nearest above does
+    if (idx == PCT_NO_INDEX) idx = 0;
     kdres *r = new (std::nothrow) kdres();
     if (!r) return nullptr;
     r->tree = t;

@@ -33,6 +33,14 @@ __device__ __forceinline__ bool better(double d2a, uint32_t ia, double d2b, uint
     return d2a < d2b || (d2a == d2b && ia < ib);
 }
 
+// What a query reports: a point only when its distance is < +inf.  Finite operands always have a finite d2 (at most ~1.4e78); a query
+// with a NaN or infinite coordinate has no point at d2 < +inf and reports (PCT_NO_INDEX, +inf) on every path (pct_engine.h, non-finite
+// input) -- the exact scans would otherwise hand such a query the lowest index they met, because better() orders +inf ties by index.
+__device__ __forceinline__ uint32_t reported_index(double d2, uint32_t i, uint32_t index_base)
+{
+    return (i == kNoIndex || !(d2 < __builtin_huge_val())) ? kNoIndex : i + index_base;
+}
+
 __device__ __forceinline__ void wave_argmin(double &d, uint32_t &i)
 {
 #pragma unroll
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(256) void nn_reduce_candidates_kernel(uint32_t *__r
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; w++)
             if (better(s_d[w], s_i[w], d, i)) { d = s_d[w]; i = s_i[w]; }
-        out_idx[q] = (i == kNoIndex) ? kNoIndex : i + index_base;
+        out_idx[q] = reported_index(d, i, index_base);
         out_d2[q] = d;
         cand_count[q] = 0;
     }
@@ -437,7 +445,7 @@ __global__ __launch_bounds__(256) void nn_overflow_fold_kernel(const uint32_t *_
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; w++)
             if (better(s_d[w], s_i[w], d, i)) { d = s_d[w]; i = s_i[w]; }
-        out_idx[q] = (i == kNoIndex) ? kNoIndex : i + index_base;
+        out_idx[q] = reported_index(d, i, index_base);
         out_d2[q] = d;
     }
 }
@@ -624,7 +632,7 @@ __global__ __launch_bounds__(256) void nn_reduce_partials_kernel(const double *_
 #pragma unroll
         for (int w = 1; w < 4; w++)
             if (better(s_d[w], s_i[w], d, i)) { d = s_d[w]; i = s_i[w]; }
-        out_idx[q] = (i == kNoIndex) ? kNoIndex : i + index_base;
+        out_idx[q] = reported_index(d, i, index_base);
         out_d2[q] = d;
     }
 }
@@ -879,7 +887,7 @@ __global__ __launch_bounds__(256) void bbox_partial_kernel(const float *__restri
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float v[3] = { x[i], y[i], z[i] };
 #pragma unroll
-        for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], v[k]); hi[k] = fmaxf(hi[k], v[k]); }
+        for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], v[k]); hi[k] = fmaxf(hi[k], v[k] == v[k] ? v[k] : __builtin_huge_valf()); }   // fmin / fmax drop a NaN: it shows as hi = +inf
     }
     __shared__ float s[4][6];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1365,16 +1373,17 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
     }
     bd = __builtin_huge_val();
     bi = kNoIndex;
-    if (m1 < __builtin_huge_valf()) {
-        if (m2 > m1 * (1.0f + 0x1p-19f) + 0x1p-90f) {            // unique within the fp32 error band: it is the exact winner
-            const float4 W = pts[p1];
-            bd = dist2((double)W.x, (double)W.y, (double)W.z, qx, qy, qz);
-            bi = __float_as_uint(W.w);
-        } else {                                                  // near-ties / duplicates: exact (d2, index) order decides
+    // m1 == +inf: the runs are empty, OR every fp32 distance overflowed (points farther than sqrt(FLT_MAX) = 1.8447e19 from the query:
+    // far queries, clouds of huge extent).  Their fp64 distances are finite and must compete, so that case takes the exact scan too
+    // (over empty runs it does nothing).
+    if (m1 < __builtin_huge_valf() && m2 > m1 * (1.0f + 0x1p-19f) + 0x1p-90f) {   // unique within the fp32 error band: it is the exact winner
+        const float4 W = pts[p1];
+        bd = dist2((double)W.x, (double)W.y, (double)W.z, qx, qy, qz);
+        bi = __float_as_uint(W.w);
+    } else {                                                      // near-ties / duplicates / overflow: exact (d2, index) order decides
 #pragma unroll 1
-            for (int k = 0; k < NR; k++) coop_scan_exact(pts, rs[k], re[k], sub, qx, qy, qz, bd, bi);
-            coop_argmin8(bd, bi);
-        }
+        for (int k = 0; k < NR; k++) coop_scan_exact(pts, rs[k], re[k], sub, qx, qy, qz, bd, bi);
+        coop_argmin8(bd, bi);
     }
 }
 
@@ -1618,22 +1627,22 @@ __device__ __forceinline__ void wave_cube_search(const GridDesc &G, const float4
     }
     bd = __builtin_huge_val();
     bi = kNoIndex;
-    if (m1 < __builtin_huge_valf()) {                                 // wave-uniform
-        if (m2 > m1 * (1.0f + 0x1p-19f) + 0x1p-90f) {                // unique within the fp32 error band: it is the exact winner
-            const float4 W = pts[p1];
-            bd = dist2((double)W.x, (double)W.y, (double)W.z, qx, qy, qz);
-            bi = __float_as_uint(W.w);
-        } else {                                                      // near-ties / duplicates: exact (d2, index) order decides
+    // (wave-uniform)  m1 == +inf: an empty cube, OR every fp32 distance overflowed -- as in coop_screen_rows that case takes the exact
+    // scan, where the points compete by their (finite) fp64 distances
+    if (m1 < __builtin_huge_valf() && m2 > m1 * (1.0f + 0x1p-19f) + 0x1p-90f) {   // unique within the fp32 error band: it is the exact winner
+        const float4 W = pts[p1];
+        bd = dist2((double)W.x, (double)W.y, (double)W.z, qx, qy, qz);
+        bi = __float_as_uint(W.w);
+    } else {                                                          // near-ties / duplicates / overflow: exact (d2, index) order decides
 #pragma unroll 1
-            for (int k = 0; k < 9; k++)
-                for (uint32_t p = rs[k] + lane; p < re[k]; p += 64u) {
-                    const float4 Pp = pts[p];
-                    const double d2 = dist2((double)Pp.x, (double)Pp.y, (double)Pp.z, qx, qy, qz);
-                    const uint32_t id = __float_as_uint(Pp.w);
-                    if (better(d2, id, bd, bi)) { bd = d2; bi = id; }
-                }
-            wave_argmin(bd, bi);
-        }
+        for (int k = 0; k < 9; k++)
+            for (uint32_t p = rs[k] + lane; p < re[k]; p += 64u) {
+                const float4 Pp = pts[p];
+                const double d2 = dist2((double)Pp.x, (double)Pp.y, (double)Pp.z, qx, qy, qz);
+                const uint32_t id = __float_as_uint(Pp.w);
+                if (better(d2, id, bd, bi)) { bd = d2; bi = id; }
+            }
+        wave_argmin(bd, bi);
     }
 }
 
@@ -1715,7 +1724,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
         uint32_t bi;
         coop_wave_search<COUNT>(G, pts, cell_start, live, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
         if (live && sub == 0) {
-            out_idx[t] = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+            out_idx[t] = reported_index(bd, bi, index_base);
             out_d2[t] = bd;
         }
     } else if (slot < Q) {                            // uniform within a group of 8 lanes
@@ -1731,7 +1740,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
         uint32_t bi;
         coop_nn_search<COUNT>(G, pts, cell_start, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
         if (sub == 0) {
-            out_idx[t] = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+            out_idx[t] = reported_index(bd, bi, index_base);
             out_d2[t] = bd;
         }
     }
@@ -1774,10 +1783,18 @@ __global__ __launch_bounds__(256) void count_grid_coop_kernel(GridDesc G, const 
         const float rf = rad[t];
         const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
         const double r2 = (double)rf * (double)rf;
-        const float pad = fabsf(rf) + 0.01f * (1.0f / G.inv_h);   // r enters only squared (kdtree.c:273)
-        const int x0 = cell_coord(qxf - pad, G.ox, G.inv_h, G.gx), x1 = cell_coord(qxf + pad, G.ox, G.inv_h, G.gx);
-        const int y0 = cell_coord(qyf - pad, G.oy, G.inv_h, G.gy), y1 = cell_coord(qyf + pad, G.oy, G.inv_h, G.gy);
-        const int z0 = cell_coord(qzf - pad, G.oz, G.inv_h, G.gz), z1 = cell_coord(qzf + pad, G.oz, G.inv_h, G.gz);
+        // r enters only squared (kdtree.c:273).  The box edges q -/+ pad are fp32 sums: each is off by up to 2^-24 (|q| + pad), and the
+        // fp64 test itself admits points up to r (1 + 2^-50) away, so the pad carries 2^-22 (|q| + |r|) per axis on top of h/100 --
+        // nothing at ordinary magnitudes, everything for a query 1e18 away whose ball reaches back to the cloud.  An edge that comes
+        // out NaN (inf - inf: infinite query or radius) opens the box to that side (cell_coord sends NaN to cell 0: right for the
+        // lower edge only).
+        const float pad0 = fabsf(rf) + 0.01f * (1.0f / G.inv_h);
+        const float padx = pad0 + 0x1p-22f * (fabsf(qxf) + fabsf(rf)), pady = pad0 + 0x1p-22f * (fabsf(qyf) + fabsf(rf)),
+                    padz = pad0 + 0x1p-22f * (fabsf(qzf) + fabsf(rf));
+        const float hx = qxf + padx, hy = qyf + pady, hz = qzf + padz;
+        const int x0 = cell_coord(qxf - padx, G.ox, G.inv_h, G.gx), x1 = hx == hx ? cell_coord(hx, G.ox, G.inv_h, G.gx) : G.gx - 1;
+        const int y0 = cell_coord(qyf - pady, G.oy, G.inv_h, G.gy), y1 = hy == hy ? cell_coord(hy, G.oy, G.inv_h, G.gy) : G.gy - 1;
+        const int z0 = cell_coord(qzf - padz, G.oz, G.inv_h, G.gz), z1 = hz == hz ? cell_coord(hz, G.oz, G.inv_h, G.gz) : G.gz - 1;
         const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
         uint32_t c = 0;
         // Rows of the box: the run bounds of up to 16 rows in ONE trip (two per lane), then the rows two at a time with 32 points of each
@@ -1934,7 +1951,7 @@ __global__ __launch_bounds__(1024) void nn_small_kernel(const float *__restrict_
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; w++) tie_merge(bd, bi, bc, s_d[w], s_i[w], s_c[w]);
         out->d2 = bd;
-        out->idx = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+        out->idx = reported_index(bd, bi, index_base);
         out->count = bc;
         express_done(sig);
     }
@@ -1984,7 +2001,7 @@ __global__ __launch_bounds__(256) void nn_small_batch_kernel(const float *__rest
         for (int w = 1; w < 4; w++)
             if (better(s_d[w], s_i[w], bd, bi)) { bd = s_d[w]; bi = s_i[w]; }
         out[blockIdx.x].d2 = bd;
-        out[blockIdx.x].idx = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+        out[blockIdx.x].idx = reported_index(bd, bi, index_base);
         express_done(sig);
     }
 }
@@ -2151,7 +2168,7 @@ __global__ __launch_bounds__(256) void inflate_block_kernel(GridDesc G, const fl
             const double rr = sqrt(bd) - P.search_margin;
             out[slot].radius = rr < P.max_radius ? rr : P.max_radius;
         }
-        out[slot].idx = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+        out[slot].idx = reported_index(bd, bi, index_base);
         out[slot].d2 = bd;
         express_done(sig);
     }
@@ -2367,7 +2384,7 @@ __global__ __launch_bounds__(256) void bezier_block_kernel(GridDesc G, const flo
     if (threadIdx.x == 0) {
         const double rr = sqrt(bd) - P.search_margin;
         out[slot].radius = rr < P.max_radius ? rr : P.max_radius;
-        out[slot].idx = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+        out[slot].idx = reported_index(bd, bi, index_base);
         out[slot].d2 = bd;
         express_done(sig);
     }

@@ -295,7 +295,9 @@ __device__ __forceinline__ void pyr_nn_search(const GridDesc &G, int nlev, const
             // slack: the fp32 cell assignment places a point at most 4e-4 cells across a face (cube_bound, kernels.hpp), the fp32
             // products and differences above err by < 3e-4 cells inside the grid; outside it (|q| large) the bound is negative anyway
             bound -= hf * (1.0f / 128.0f);
-            if (near_grid && bound > 0.0f && bd32 <= bound * bound * (1.0f - 0x1p-20f)) break;
+            // (bd32 < inf: a best beyond FLT_MAX -- clouds of huge extent -- compares as +inf <= +inf against a squared bound that
+            // overflowed too; such a walk ends at the root instead)
+            if (near_grid && bound > 0.0f && bd32 < inf && bd32 <= bound * bound * (1.0f - 0x1p-20f)) break;
             const uint32_t from = (uint32_t)((X & 1) | ((Y & 1) << 1) | ((Z & 1) << 2));
             mypend |= 1u << L;                   // a later visit to this level starts with all children pending
             X >>= 1; Y >>= 1; Z >>= 1; L++;
@@ -544,7 +546,7 @@ __device__ __forceinline__ void pyr_answer(const GridDesc &G, const PyrDesc &PD,
         }
     }
     if (sub == 0) {
-        out_idx[t] = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+        out_idx[t] = reported_index(bd, bi, index_base);
         out_d2[t] = bd;
     }
 }
@@ -630,7 +632,7 @@ __global__ __launch_bounds__(256) void nn_grid_pyr_todo_kernel(GridDesc G, PyrDe
         uint32_t bi = kNoIndex;
         pyr_nn_search<COUNT>(G, PD.nlev, s_off, nodes, pts, qxf, qyf, qzf, sub, cx, cy, cz, L0, 1, 0, 1, 0, 1, 0, bd, bi, npts, nruns, nnodes);
         if (sub == 0) {
-            out_idx[t] = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+            out_idx[t] = reported_index(bd, bi, index_base);
             out_d2[t] = (bi == kNoIndex) ? __builtin_huge_val() : bd;
         }
     }

@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void replan_block_kernel(RingView V, GridDesc 
     // No second kernel: a separate one-block "finish" launch cost 8.9 us of a 23 us batch (profiles/r02_c5_kernel_stats.csv).
     if (threadIdx.x == 0) {
         out[slot].radius = radius;
-        out[slot].idx = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+        out[slot].idx = reported_index(bd, bi, index_base);
         out[slot].d2 = bd;
         out[slot].count = 0;
         if (slot >= H.n_nodes) { double *po = pos_out + 3 * (size_t)(slot - H.n_nodes); po[0] = px; po[1] = py; po[2] = pz; }
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(256) void ring_batch_kernel(RingView V, InflatePara
         }
     }
     if (threadIdx.x == 0) {
-        const uint32_t gi = (bi == kNoIndex) ? kNoIndex : bi + index_base;
+        const uint32_t gi = reported_index(bd, bi, index_base);
         if (out_idx) out_idx[slot] = gi;
         if (out_d2) out_d2[slot] = bd;
         if (out_radius) out_radius[slot] = radius;
