@@ -11,6 +11,7 @@
  *                           (rcvPointCloudCallBack                Planner/src/sim_planning_demo.cpp:159-167)
  *   pct_nn_batch            kdtreeForMap.nearestKSearch(p,1,..)   Planner/src/corridor_finder.cpp:130
  *                           with kd_nearestf arithmetic           Utils/kdtree/src/kdtree.c:345-491
+ *   pct_knn_batch           the same nearestKSearch(p, k, ..) for k > 1 (PCL's k-NN interface, called with k = 1 at :130)
  *   pct_radius_count_batch  kd_nearest_rangef + kd_res_size       Utils/kdtree/src/kdtree.c:262-293,561-593,620-623
  *   pct_inflate_batch       safeRegionRrtStar::radiusSearch       Planner/src/corridor_finder.cpp:113-133
  *                           (+ checkRadius :656-659, checkTrajPtCol :412-416), batched over the loops at
@@ -49,6 +50,15 @@
  *     rows; pct_cloud_build_grid, and pct_cloud_ring_index without an extent on a cloud that already holds such a row, need the
  *     data's bounding box and return PCT_ERR_INVALID ("cloud holds non-finite coordinates"), leaving the cloud as it was, without
  *     an index.
+ *
+ * k nearest neighbours (pct_knn_batch*, 1 <= k <= PCT_KNN_MAX_K): row i of idx / d2 (row-major Q x k) holds the k smallest points of
+ * query i in the total order of the nearest-neighbour contract -- smaller fp64 d2 first, among equal d2 the lower index first -- and
+ * lists them in that order.  Every d2 is the arithmetic above, bit-identical to what pct_nn_batch reports for the same pair; idx is
+ * index_base + local index (the ring slot on a rolling map); k = 1 equals pct_nn_batch on every path.  Slots beyond the number of
+ * points at a finite d2 hold PCT_NO_INDEX / +inf: the tail of a row when k exceeds the cloud's size; the whole row of a query with a
+ * NaN or infinite coordinate (the other rows of the batch are as without it); and the place of cloud rows with a NaN or infinite
+ * coordinate on the paths that accept them (above), which are never listed.  k < 1 or k > PCT_KNN_MAX_K: PCT_ERR_INVALID.  Q = 0:
+ * PCT_OK.  Empty cloud: every slot padded; the host forms return PCT_ERR_EMPTY, pct_knn_batch_dev PCT_OK, as for pct_nn_batch*.
  *
  * All entry points need a HIP device; there is no host fallback.
  */
@@ -162,6 +172,15 @@ int pct_cloud_grid_info(const pct_cloud *c, int32_t dims[3], float *cell_size, f
 /* q: Q x 3 fp32.  idx[Q] (index_base + local index), d2[Q] fp64. */
 int pct_nn_batch(pct_cloud *c, const float *q, int64_t Q, uint32_t *idx, double *d2);
 int pct_nn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, uint32_t *idx, double *d2);
+/* The k nearest points of every query (contract: top of this file).  idx / d2: Q x k, row-major, each row nearest first.
+ * PCT_ALGO_GRID: the cell-pruned k-NN kernel (needs pct_cloud_build_grid, PCT_ERR_INVALID otherwise); PCT_ALGO_STREAM and
+ * PCT_ALGO_STREAM_EXACT: the streaming k-NN kernel, all fp64, which reads the cloud once per tile of 8 queries whatever k is;
+ * PCT_ALGO_AUTO: the cell-pruned kernel when a grid is built, otherwise the streaming one -- that covers a rolling-map
+ * (ring-indexed) cloud and a small host-mapped cloud, where the answer is exact but NOT index-accelerated: every query
+ * examines every point of the window. */
+#define PCT_KNN_MAX_K 64
+int pct_knn_batch(pct_cloud *c, const float *q, int64_t Q, int32_t k, uint32_t *idx, double *d2);
+int pct_knn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, int32_t k, uint32_t *idx, double *d2);
 /* same with fp64 query coordinates (kd_nearest's double positions); streaming kernel */
 int pct_nn_batch_q64(pct_cloud *c, const double *q, int64_t Q, uint32_t *idx, double *d2);
 /* the same, also reporting how many points attain the minimum: ties[i] >= 1 where counted (single queries against clouds of up
@@ -270,6 +289,9 @@ int pct_ctrl_points_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_i
  * graph capture.  An empty shard yields idx=PCT_NO_INDEX, d2=+inf and PCT_OK. ---------------------- */
 int pct_nn_batch_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, void *stream);
 int pct_radius_count_batch_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, uint32_t *d_count, void *stream);
+/* pct_knn_batch_algo on device buffers (d_idx / d_d2: Q x k); reserve the batch size first (pct_cloud_reserve_queries).  The streaming
+ * kernel's scratch (96 MiB) is allocated by the first call that needs it. */
+int pct_knn_batch_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int32_t k, uint32_t *d_idx, double *d_d2, void *stream);
 /* Stream variants of the planner arithmetic (same results as pct_inflate_batch / pct_bezier_check, nothing crosses the bus but the
  * trajectory's coefficients): d_pts = Q x 3 fp64 planner points on the device; d_radius[Q] required, d_idx / d_d2 optional.
  * Reserve the batch size first (pct_cloud_reserve_queries). */

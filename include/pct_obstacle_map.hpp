@@ -141,6 +141,12 @@ public:
     {
         check(pct_nn_batch(cloud_, queries, n, index, d2), "pct_nn_batch");
     }
+    // the k > 1 form of the same call (kdtreeForMap.nearestKSearch(p, k, ..), corridor_finder.cpp:130): index / d2 are n x k row-major,
+    // each row nearest first, ties in ascending index, padded with PCT_NO_INDEX / +inf beyond the cloud's size; 1 <= k <= PCT_KNN_MAX_K
+    void nearestKSearch(const float *queries, int64_t n, int k, uint32_t *index, double *d2)
+    {
+        check(pct_knn_batch(cloud_, queries, n, (int32_t)k, index, d2), "pct_knn_batch");
+    }
     std::vector<uint32_t> radiusIndices(const float center[3], float radius)
     {
         std::vector<uint32_t> out((size_t)std::max<int64_t>(pct_cloud_size(cloud_), 1));

@@ -27,6 +27,7 @@
 #include "pyramid.hpp"
 #include "ring.hpp"
 #include "brute2.hpp"
+#include "knn.hpp"
 
 using namespace pct;
 
@@ -173,6 +174,10 @@ struct pct_cloud {
     uint32_t *d_ovf = nullptr;                                 // [0] = number of overflowed candidate lists, [1..] = their queries
     uint32_t *d_cand_count = nullptr, *d_cand_idx = nullptr;   // candidate lists of the brute-force filter: part_q x kCandCap
     double *d_cand_d2 = nullptr;
+    // k-NN batches (knn.hpp): the host entry points' Q x k result rows and the streaming kernel's per-block partial lists (grow-only)
+    uint32_t *d_knn_idx = nullptr, *d_knn_pidx = nullptr;
+    double *d_knn_d2 = nullptr, *d_knn_pd2 = nullptr;
+    size_t knn_out_cap = 0, knn_part_cap = 0;
     // order-preserving crop (lidar): tile counts and the compacted {index, d2, x, y, z} of the last crop
     uint32_t *crop_tile = nullptr, *crop_idx = nullptr;
     double *crop_d2 = nullptr;
@@ -1010,6 +1015,84 @@ int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_
     return PCT_OK;
 }
 
+constexpr size_t kKnnPartEntries = 8u << 20;      // partial lists of the streaming k-NN kernel: 96 MiB; larger batches go through in slices
+
+template <int KCAP>
+void launch_knn_grid(pct_cloud *c, const float *d_q, int64_t Q, int k, const float4 *recs, uint32_t *d_idx, double *d_d2, hipStream_t s)
+{
+    knn_grid_kernel<KCAP><<<ceil_div(Q, kKnnGroups), 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, k, (uint32_t)c->index_base, recs,
+                                                                   d_idx, d_d2, c->count_work ? c->d_work : nullptr);
+}
+
+template <int KCAP>
+void launch_knn_stream(pct_cloud *c, const float *d_q, int Q, int k, int nparts, hipStream_t s)
+{
+    knn_stream_kernel<KCAP><<<dim3(nparts, ceil_div(Q, kKnnTile)), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q, Q, k, c->d_knn_pd2, c->d_knn_pidx);
+}
+
+// k-NN rows of a device-resident batch: d_idx / d_d2 are Q x k
+int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t *d_idx, double *d_d2, hipStream_t s)
+{
+    if (Q == 0) return PCT_OK;
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    if (Q * (int64_t)k > 0xFFFFFFFFll) return fail(PCT_ERR_INVALID, "k-NN batch of %lld x %d entries is too large", (long long)Q, k);
+    if (c->count == 0) {
+        fill_empty_kernel<<<ceil_div(Q * k, 256), 256, 0, s>>>(d_idx, d_d2, (uint32_t)(Q * k));
+        HIPCHK(hipGetLastError());
+        return PCT_OK;
+    }
+    if (algo == PCT_ALGO_AUTO) algo = c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    const int kcap = k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64;
+    if (algo == PCT_ALGO_GRID) {
+        if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
+        c->host_work = false;
+        if (c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
+        begin_timing(c, s);
+        const float4 *recs = nullptr;
+        PCTCHK(bin_queries(c, d_q, Q, s, &recs));
+        dom_begin(c, s);
+        switch (kcap) {
+        case 8: launch_knn_grid<8>(c, d_q, Q, k, recs, d_idx, d_d2, s); break;
+        case 16: launch_knn_grid<16>(c, d_q, Q, k, recs, d_idx, d_d2, s); break;
+        case 32: launch_knn_grid<32>(c, d_q, Q, k, recs, d_idx, d_d2, s); break;
+        default: launch_knn_grid<64>(c, d_q, Q, k, recs, d_idx, d_d2, s); break;
+        }
+        dom_end(c, s);
+        end_timing(c, s);
+        HIPCHK(hipGetLastError());
+        return PCT_OK;
+    }
+    if (algo != PCT_ALGO_STREAM && algo != PCT_ALGO_STREAM_EXACT) return fail(PCT_ERR_INVALID, "unknown algo %d", algo);
+    if (c->capturing) return fail(PCT_ERR_INVALID, "the streaming k-NN kernel is not available during graph capture");
+    if (!c->d_knn_pd2) {
+        PCTCHK(dev_alloc(&c->d_knn_pd2, kKnnPartEntries));
+        PCTCHK(dev_alloc(&c->d_knn_pidx, kKnnPartEntries));
+        c->knn_part_cap = kKnnPartEntries;
+    }
+    // one block per 4096 points, at most 256: a block's four waves then see enough points for their lists to settle
+    const int nparts = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->count + 4095) / 4096));
+    const int64_t qslice = std::max<int64_t>(kKnnTile, (int64_t)(c->knn_part_cap / ((size_t)nparts * (size_t)k)) / kKnnTile * kKnnTile);
+    begin_timing(c, s);
+    dom_begin(c, s);
+    for (int64_t off = 0; off < Q; off += qslice) {
+        const int qn = (int)std::min<int64_t>(qslice, Q - off);
+        const float *qs = d_q + 3 * off;
+        switch (kcap) {
+        case 8: launch_knn_stream<8>(c, qs, qn, k, nparts, s); break;
+        case 16: launch_knn_stream<16>(c, qs, qn, k, nparts, s); break;
+        case 32: launch_knn_stream<32>(c, qs, qn, k, nparts, s); break;
+        default: launch_knn_stream<64>(c, qs, qn, k, nparts, s); break;
+        }
+        knn_merge_kernel<<<qn, 64, 0, s>>>(c->d_knn_pd2, c->d_knn_pidx, nparts, k, (uint32_t)c->index_base, d_idx + off * k, d_d2 + off * k);
+    }
+    dom_end(c, s);
+    end_timing(c, s);
+    HIPCHK(hipGetLastError());
+    c->host_work = true;                    // the streaming kernel examines every point for every query
+    c->host_points = (uint64_t)Q * (uint64_t)c->count;
+    return PCT_OK;
+}
+
 InflateParams to_dev(const pct_inflate_params *p)
 {
     return InflateParams{ p->start[0], p->start[1], p->start[2], p->sample_range, p->search_margin, p->max_radius };
@@ -1172,6 +1255,7 @@ int pct_cloud_destroy(pct_cloud *c)
     dev_free(c->d_part_d2); dev_free(c->d_part_idx); dev_free(c->d_cand_count); dev_free(c->d_cand_d2); dev_free(c->d_cand_idx); dev_free(c->d_ovf);
     dev_free(c->d_coef); dev_free(c->d_segtime); dev_free(c->d_orders); dev_free(c->d_nsamples); dev_free(c->d_first_hit);
     dev_free(c->d_work);
+    dev_free(c->d_knn_idx); dev_free(c->d_knn_d2); dev_free(c->d_knn_pidx); dev_free(c->d_knn_pd2);
     dev_free(c->d_bbox); dev_free(c->d_gbcheck); dev_free(c->pyr_nodes); dev_free(c->pyr_hint);
     if (c->h_gbcheck) (void)hipHostFree(c->h_gbcheck);
     dev_free(c->ring_ht); dev_free(c->ring_slots); dev_free(c->ring_ovf); dev_free(c->ring_where); dev_free(c->ring_st);
@@ -1508,6 +1592,44 @@ int pct_nn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, uint32_
 int pct_nn_batch(pct_cloud *c, const float *q, int64_t Q, uint32_t *idx, double *d2)
 {
     return pct_nn_batch_algo(c, PCT_ALGO_AUTO, q, Q, idx, d2);
+}
+
+// ---- k nearest neighbours ----------------------------------------------------------------
+int pct_knn_batch_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int32_t k, uint32_t *d_idx, double *d_d2, void *stream)
+{
+    if (!c || Q < 0 || (Q > 0 && (!d_q || !d_idx || !d_d2))) return fail(PCT_ERR_INVALID, "bad knn_batch_dev arguments");
+    if (k < 1 || k > PCT_KNN_MAX_K) return fail(PCT_ERR_INVALID, "k = %d is outside 1 .. %d", (int)k, PCT_KNN_MAX_K);
+    PCTCHK(order_after_mutations(c, (hipStream_t)stream));
+    return knn_dev(c, algo, d_q, Q, (int)k, d_idx, d_d2, (hipStream_t)stream);
+}
+
+int pct_knn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, int32_t k, uint32_t *idx, double *d2)
+{
+    if (!c || Q < 0 || (Q > 0 && (!q || !idx || !d2))) return fail(PCT_ERR_INVALID, "bad knn_batch arguments");
+    if (k < 1 || k > PCT_KNN_MAX_K) return fail(PCT_ERR_INVALID, "k = %d is outside 1 .. %d", (int)k, PCT_KNN_MAX_K);
+    if (Q == 0) return PCT_OK;
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    const size_t rows = (size_t)Q * (size_t)k;
+    if (rows > c->knn_out_cap) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        dev_free(c->d_knn_idx); dev_free(c->d_knn_d2);
+        c->knn_out_cap = 0;
+        PCTCHK(dev_alloc(&c->d_knn_idx, rows));
+        PCTCHK(dev_alloc(&c->d_knn_d2, rows));
+        c->knn_out_cap = rows;
+    }
+    HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
+    PCTCHK(knn_dev(c, algo, c->d_q, Q, (int)k, c->d_knn_idx, c->d_knn_d2, g_stream));
+    HIPCHK(hipMemcpyAsync(idx, c->d_knn_idx, sizeof(uint32_t) * rows, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(d2, c->d_knn_d2, sizeof(double) * rows, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    if (c->count == 0) return fail(PCT_ERR_EMPTY, "k-nearest-neighbour query against an empty cloud");
+    return PCT_OK;
+}
+
+int pct_knn_batch(pct_cloud *c, const float *q, int64_t Q, int32_t k, uint32_t *idx, double *d2)
+{
+    return pct_knn_batch_algo(c, PCT_ALGO_AUTO, q, Q, k, idx, d2);
 }
 
 int pct_nn_batch_q64(pct_cloud *c, const double *q, int64_t Q, uint32_t *idx, double *d2)

@@ -14,6 +14,7 @@ from . import build as _build
 
 NO_INDEX = 0xFFFFFFFF
 ALGO_AUTO, ALGO_STREAM, ALGO_GRID, ALGO_STREAM_EXACT = 0, 1, 2, 3
+KNN_MAX_K = 64                  # PCT_KNN_MAX_K
 
 _lib = None
 
@@ -96,6 +97,9 @@ def lib():
         L.pct_cloud_ring_bucket_records.argtypes = [vp]
         L.pct_nn_batch.argtypes = [vp, f32p, i64, u32p, f64p]
         L.pct_nn_batch_algo.argtypes = [vp, i32, f32p, i64, u32p, f64p]
+        L.pct_knn_batch.argtypes = [vp, f32p, i64, C.c_int32, u32p, f64p]
+        L.pct_knn_batch_algo.argtypes = [vp, i32, f32p, i64, C.c_int32, u32p, f64p]
+        L.pct_knn_batch_dev.argtypes = [vp, i32, vp, i64, C.c_int32, vp, vp, vp]
         L.pct_radius_count_batch.argtypes = [vp, f32p, f32p, i64, u32p]
         L.pct_radius_count_batch_algo.argtypes = [vp, i32, f32p, f32p, i64, u32p]
         L.pct_radius_indices.argtypes = [vp, f32p, C.c_float, u32p, i64, C.POINTER(i64)]
@@ -298,6 +302,16 @@ class Cloud:
         _chk(lib().pct_nn_batch_algo(self._h, algo, _ptr(q), len(q), _ptr(idx), _ptr(d2)))
         return idx, d2
 
+    def knn(self, queries, k: int, algo: int = ALGO_AUTO):
+        """the k nearest points of every query (pct_knn_batch_algo): (idx uint32 [Q, k], d2 float64 [Q, k]), each row nearest first,
+        ties in ascending index, padded with NO_INDEX / +inf where fewer than k points lie at a finite distance"""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, 3)
+        kk = max(int(k), 0)
+        idx = np.empty((len(q), kk), np.uint32)
+        d2 = np.empty((len(q), kk), np.float64)
+        _chk(lib().pct_knn_batch_algo(self._h, algo, _ptr(q), len(q), int(k), _ptr(idx), _ptr(d2)))
+        return idx, d2
+
     def radius_count(self, queries, radii, algo: int = ALGO_AUTO):
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, 3)
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, np.float32), (len(q),)))
@@ -369,6 +383,10 @@ class Cloud:
     # device-buffer variants: raw pointers (e.g. torch tensor .data_ptr()) and a hipStream_t handle
     def nn_device(self, q_ptr: int, Q: int, idx_ptr: int, d2_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         _chk(lib().pct_nn_batch_dev(self._h, algo, q_ptr, int(Q), idx_ptr, d2_ptr, stream))
+
+    def knn_device(self, q_ptr: int, Q: int, k: int, idx_ptr: int, d2_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
+        """pct_knn_batch_dev: idx / d2 are Q x k device buffers; reserve_queries(Q) first"""
+        _chk(lib().pct_knn_batch_dev(self._h, algo, q_ptr, int(Q), int(k), idx_ptr, d2_ptr, stream))
 
     def inflate_device(self, params: InflateParams, pts_ptr: int, Q: int, radius_ptr: int, idx_ptr: int = 0, d2_ptr: int = 0, stream: int = 0):
         _chk(lib().pct_inflate_batch_dev(self._h, C.byref(params), pts_ptr, int(Q), radius_ptr, idx_ptr or None, d2_ptr or None, stream))
