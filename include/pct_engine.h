@@ -13,6 +13,7 @@
  *                           with kd_nearestf arithmetic           Utils/kdtree/src/kdtree.c:345-491
  *   pct_knn_batch           the same nearestKSearch(p, k, ..) for k > 1 (PCL's k-NN interface, called with k = 1 at :130)
  *   pct_radius_count_batch  kd_nearest_rangef + kd_res_size       Utils/kdtree/src/kdtree.c:262-293,561-593,620-623
+ *   pct_radius_search_batch kdtree.radiusSearch(p, r, idx, dist) per marked point  Planner/src/cone_keeper.cpp:92-153
  *   pct_inflate_batch       safeRegionRrtStar::radiusSearch       Planner/src/corridor_finder.cpp:113-133
  *                           (+ checkRadius :656-659, checkTrajPtCol :412-416), batched over the loops at
  *                           :829-835 (SafeRegionEvaluate) and :958-974 (treeRepair)
@@ -60,6 +61,30 @@
  * coordinate on the paths that accept them (above), which are never listed.  k < 1 or k > PCT_KNN_MAX_K: PCT_ERR_INVALID.  Q = 0:
  * PCT_OK.  Empty cloud: every slot padded; the host forms return PCT_ERR_EMPTY, pct_knn_batch_dev PCT_OK, as for pct_nn_batch*.
  *
+ * Radius search with lists (pct_radius_search_batch*): PCL's radiusSearch(p, r, indices, sqr_distances) for a batch, the sibling of
+ * pct_knn_batch.  The result is a CSR: row i = entries [offsets[i], offsets[i + 1]), offsets has Q + 1 entries, offsets[0] = 0 and
+ * offsets[Q] is the total.  Row i lists exactly the points pct_radius_count_batch counts for (q_i, r_i) -- the same fp64 test
+ * ((dx*dx + dy*dy) + dz*dz) <= (double)r * (double)r, inclusive, and the same non-finite rules: a negative r counts as |r|, a NaN r
+ * gives an empty row, r = +/-inf lists every point whose d2 is not NaN, a query with a NaN coordinate gives an empty row, and the
+ * other rows of the batch are unaffected -- so offsets[i + 1] - offsets[i] equals that count on every path.  idx is index_base +
+ * local index (the ring slot on a rolling map); d2 is bit-identical to what pct_nn_batch / pct_knn_batch report for the same pair.
+ * Order: PCT_ORDER_INDEX lists each row in ascending index (the order of pct_radius_indices, and of the reference's kd_nearest_range
+ * result once sorted); PCT_ORDER_DISTANCE lists nearest first, among equal d2 the lower index first (the engine's total order: that
+ * of pct_knn_batch and of pct_radius_crop(sort_by_distance)).  Both are deterministic: two runs give identical bytes.
+ * Algorithms: PCT_ALGO_GRID uses the cell index and returns PCT_ERR_INVALID without one; PCT_ALGO_STREAM is exhaustive, for any
+ * cloud (PCT_ALGO_STREAM_EXACT is accepted as STREAM); PCT_ALGO_AUTO takes the grid when one is built and the streaming form
+ * otherwise -- on a rolling-map (ring-indexed) cloud and on a small host-mapped cloud the answer is therefore exact but NOT
+ * index-accelerated: every query examines every point of the window.  An unknown algo, or an order other than 0 / 1:
+ * PCT_ERR_INVALID.  Host form: the lists stay in a cloud-owned device buffer of 12 B per entry, grown on demand; offsets and total
+ * are copied out and pct_radius_search_read then copies any range of the lists, so a caller sizes its buffers from total without a
+ * second search.  A result lasts until the next radius search (either form), upload, append, grid build or drop, or destroy on that
+ * cloud: a read after any of those, a read before any search, or a range outside [0, total] returns PCT_ERR_INVALID; n = 0 is
+ * PCT_OK.  Q = 0: PCT_OK, offsets[0] = 0, total = 0.  Empty cloud: PCT_OK with every row empty (as the count and
+ * pct_radius_indices).  More than 2^32 - 1 entries: PCT_ERR_CAPACITY.  If the list buffer cannot be allocated: PCT_ERR_ALLOC with
+ * offsets / total still valid.  Device form: d_offsets[Q + 1] is always written; the lists are written only when
+ * d_offsets[Q] <= cap -- the kernels test this on the device and leave d_idx / d_d2 untouched otherwise, the caller reads
+ * d_offsets[Q] to find out.  There is no max_nn: a bounded list is pct_knn_batch cut at r*r.
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -92,6 +117,11 @@ enum pct_algo {
     PCT_ALGO_STREAM = 1,     /* brute-force SoA streaming kernels: fp32 filter + exact fp64 recheck (no index needed) */
     PCT_ALGO_GRID = 2,       /* cell-pruned kernel (needs pct_cloud_build_grid) */
     PCT_ALGO_STREAM_EXACT = 3 /* brute force with every pair in fp64 (the filter's reference; same results) */
+};
+
+enum pct_order {
+    PCT_ORDER_INDEX = 0,     /* each row in ascending index */
+    PCT_ORDER_DISTANCE = 1   /* each row nearest first, equal d2 in ascending index */
 };
 
 /* ---- process / device ---------------------------------------------------------------- */
@@ -189,6 +219,11 @@ int pct_nn_batch_q64_ties(pct_cloud *c, const double *q, int64_t Q, uint32_t *id
 /* count[Q] = #points with d2 <= r*r */
 int pct_radius_count_batch(pct_cloud *c, const float *q, const float *r, int64_t Q, uint32_t *count);
 int pct_radius_count_batch_algo(pct_cloud *c, int algo, const float *q, const float *r, int64_t Q, uint32_t *count);
+/* Which points lie within r, for many queries at once (contract: top of this file).
+ * rows of a CSR: row i = entries [offsets[i], offsets[i+1]) ; offsets has Q + 1 entries, offsets[0] = 0, *total = offsets[Q] */
+int pct_radius_search_batch(pct_cloud *c, int algo, const float *q, const float *r, int64_t Q, int order, int64_t *offsets, int64_t *total);
+/* entries [first, first + n) of the lists of the LAST pct_radius_search_batch on this cloud; idx or d2 may be NULL */
+int pct_radius_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2);
 /* lidar-style crop (camera_sensor.cpp:133-145): indices of all points within r of ONE centre,
  * ascending index order; returns the count through *n_out (may exceed cap; only cap written). */
 int pct_radius_indices(pct_cloud *c, const float q[3], float r, uint32_t *idx_out, int64_t cap, int64_t *n_out);
@@ -292,6 +327,11 @@ int pct_radius_count_batch_dev(pct_cloud *c, int algo, const float *d_q, const f
 /* pct_knn_batch_algo on device buffers (d_idx / d_d2: Q x k); reserve the batch size first (pct_cloud_reserve_queries).  The streaming
  * kernel's scratch (96 MiB) is allocated by the first call that needs it. */
 int pct_knn_batch_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int32_t k, uint32_t *d_idx, double *d_d2, void *stream);
+/* pct_radius_search_batch on device buffers, asynchronous on `stream`, no host synchronisation inside; d_d2 may be NULL (with
+ * PCT_ORDER_DISTANCE the sort keys then live in the cloud's own list buffer, grown to cap entries by the call).  Reserve the batch
+ * size first (pct_cloud_reserve_queries). */
+int pct_radius_search_batch_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, int order, int64_t *d_offsets,
+                                int64_t cap, uint32_t *d_idx, double *d_d2, void *stream);
 /* Stream variants of the planner arithmetic (same results as pct_inflate_batch / pct_bezier_check, nothing crosses the bus but the
  * trajectory's coefficients): d_pts = Q x 3 fp64 planner points on the device; d_radius[Q] required, d_idx / d_d2 optional.
  * Reserve the batch size first (pct_cloud_reserve_queries). */

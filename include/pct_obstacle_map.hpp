@@ -147,6 +147,21 @@ public:
     {
         check(pct_knn_batch(cloud_, queries, n, (int32_t)k, index, d2), "pct_knn_batch");
     }
+    // PCL's radiusSearch(p, r, indices, sqr_distances) for n queries at once (cone_keeper.cpp:120-126 asks it once per marked point):
+    // row i of the result = index / d2 entries [offsets[i], offsets[i + 1]), offsets has n + 1 entries.  sorted: nearest first, ties in
+    // ascending index (what PCL returns with sorted results); otherwise ascending index.  Not to be confused with radiusSearch(const
+    // double[3]) above, the planner's sphere inflation, which keeps its name.
+    void radiusSearchBatch(const float *queries, const float *radii, int64_t n, std::vector<int64_t> &offsets, std::vector<uint32_t> &index,
+                           std::vector<double> &d2, bool sorted = true)
+    {
+        offsets.assign((size_t)n + 1, 0);
+        int64_t total = 0;
+        check(pct_radius_search_batch(cloud_, PCT_ALGO_AUTO, queries, radii, n, sorted ? PCT_ORDER_DISTANCE : PCT_ORDER_INDEX, offsets.data(), &total),
+              "pct_radius_search_batch");
+        index.resize((size_t)total);
+        d2.resize((size_t)total);
+        check(pct_radius_search_read(cloud_, 0, total, index.data(), d2.data()), "pct_radius_search_read");
+    }
     std::vector<uint32_t> radiusIndices(const float center[3], float radius)
     {
         std::vector<uint32_t> out((size_t)std::max<int64_t>(pct_cloud_size(cloud_), 1));

@@ -40,7 +40,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
             os.path.join(ROOT, "include", "kdtree", "kdtree_ext.h")]
     hdrs += [os.path.join(ROOT, "include", "pct_voxel.h"), os.path.join(ROOT, "include", "pct_traj.h")]
     eng_units = [os.path.join(CSRC, "engine.hip"), os.path.join(CSRC, "voxel.hip"), os.path.join(CSRC, "traj.hip"), os.path.join(CSRC, "nodeset.hip")]
-    eng_src = eng_units + [os.path.join(CSRC, f) for f in ("kernels.hpp", "gridbuild.hpp", "pyramid.hpp", "bernstein.hpp", "brute2.hpp", "knn.hpp", "ring.hpp", "ring_host.inc", "engine_internal.hpp")]
+    eng_src = eng_units + [os.path.join(CSRC, f) for f in ("kernels.hpp", "gridbuild.hpp", "pyramid.hpp", "bernstein.hpp", "brute2.hpp", "knn.hpp", "rsearch.hpp", "ring.hpp", "ring_host.inc", "engine_internal.hpp")]
     if force or _stale(ENGINE_SO, eng_src + hdrs):
         cmd = [HIPCC, *COMMON, "-o", ENGINE_SO, *eng_units]
         if verbose:
@@ -112,6 +112,15 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
         cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-o", lat_bin, lat_src,
                "-L" + LIB, "-lkdtree", "-lpct_engine", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + LIB,
                "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+    rows_src = os.path.join(ROOT, "examples", "radius_search_rows.cpp")
+    rows_bin = os.path.join(LIB, "radius_search_rows")
+    if os.path.exists(rows_src) and os.path.exists(ENGINE_SO) and (force or _stale(rows_bin, [rows_src, ENGINE_SO] + hdrs + [os.path.join(ROOT, "include", "pct_obstacle_map.hpp")])):
+        # the cone keeper's radiusSearch loop as one batch (cone_keeper.cpp:92-153); needs the engine alone
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-o", rows_bin, rows_src,
+               "-L" + LIB, "-lpct_engine", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + LIB, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)

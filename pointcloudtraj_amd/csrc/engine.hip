@@ -28,6 +28,7 @@
 #include "ring.hpp"
 #include "brute2.hpp"
 #include "knn.hpp"
+#include "rsearch.hpp"
 
 using namespace pct;
 
@@ -178,6 +179,17 @@ struct pct_cloud {
     uint32_t *d_knn_idx = nullptr, *d_knn_pidx = nullptr;
     double *d_knn_d2 = nullptr, *d_knn_pd2 = nullptr;
     size_t knn_out_cap = 0, knn_part_cap = 0;
+    // radius-search batches (rsearch.hpp): scan / cursor / queue workspaces sized with the query workspaces, the host form's offsets
+    // and the lists of its last result (12 B per entry, grow-only), valid until the cloud or its index changes
+    long long *rs_off = nullptr;
+    uint64_t *rs_tiles = nullptr;
+    uint32_t *rs_cursor = nullptr, *rs_queue = nullptr;
+    int64_t rs_qcap = 0;
+    uint32_t *rs_idx = nullptr;
+    double *rs_d2 = nullptr;
+    size_t rs_cap = 0;
+    int64_t rs_total = 0;
+    bool rs_valid = false;
     // order-preserving crop (lidar): tile counts and the compacted {index, d2, x, y, z} of the last crop
     uint32_t *crop_tile = nullptr, *crop_idx = nullptr;
     double *crop_d2 = nullptr;
@@ -512,6 +524,7 @@ void drop_grid(pct_cloud *c)
 {
     if (c->has_grid) c->generation++;
     c->has_grid = false;
+    c->rs_valid = false;                // every upload, append, build and drop comes through here: the last radius-search result ends
     c->has_pyr = false;
 }
 
@@ -1093,6 +1106,95 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
     return PCT_OK;
 }
 
+// ---- radius search with lists (rsearch.hpp) ----------------------------------------------------------------------------------
+// scan / cursor / queue workspaces, sized with the query workspaces (pct_cloud_reserve_queries)
+int rs_ensure_work(pct_cloud *c)
+{
+    if (c->rs_qcap >= c->qcap && c->rs_off) return PCT_OK;
+    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow workspaces during graph capture");
+    const size_t q = (size_t)std::max<int64_t>(c->qcap, 256);
+    dev_free(c->rs_off); dev_free(c->rs_tiles); dev_free(c->rs_cursor); dev_free(c->rs_queue);
+    c->rs_qcap = 0;
+    PCTCHK(dev_alloc(&c->rs_off, q + 1));
+    PCTCHK(dev_alloc(&c->rs_tiles, q / kRsScanTile + 2));
+    PCTCHK(dev_alloc(&c->rs_cursor, q));
+    PCTCHK(dev_alloc(&c->rs_queue, q + 1));
+    c->rs_qcap = (int64_t)q;
+    return PCT_OK;
+}
+
+// the cloud-owned lists: room for n entries of 12 B (grow-only; a failed growth leaves none)
+int rs_ensure_lists(pct_cloud *c, size_t n)
+{
+    if (n <= c->rs_cap) return PCT_OK;
+    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the radius-search lists during graph capture");
+    dev_free(c->rs_idx); dev_free(c->rs_d2);
+    c->rs_cap = 0;
+    PCTCHK(dev_alloc(&c->rs_idx, n));
+    PCTCHK(dev_alloc(&c->rs_d2, n));
+    c->rs_cap = n;
+    return PCT_OK;
+}
+
+// AUTO / STREAM_EXACT -> the path taken; PCT_ERR_INVALID for an unknown algo or PCT_ALGO_GRID without a grid
+int rs_pick_algo(pct_cloud *c, int *algo)
+{
+    if (*algo == PCT_ALGO_AUTO) *algo = c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    if (*algo == PCT_ALGO_STREAM_EXACT) *algo = PCT_ALGO_STREAM;
+    if (*algo == PCT_ALGO_GRID && !c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
+    if (*algo != PCT_ALGO_GRID && *algo != PCT_ALGO_STREAM) return fail(PCT_ERR_INVALID, "unknown algo %d", *algo);
+    return PCT_OK;
+}
+
+// steps 1 and 2: row lengths (the radius-count batch, into c->d_count) and their exclusive scan into d_offsets[Q + 1]; the rows the
+// sort will take are queued in c->rs_queue.  algo: as rs_pick_algo left it.  Q >= 1.
+int rs_count_scan(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, long long *d_offsets, hipStream_t s)
+{
+    if (Q > c->rs_qcap || !d_offsets) return fail(PCT_ERR_INTERNAL, "radius search without its workspaces");      // rs_ensure_work comes first
+    PCTCHK(count_dev(c, algo, d_q, d_r, Q, c->d_count, s));
+    const int ntiles = ceil_div(Q, kRsScanTile);
+    HIPCHK(hipMemsetAsync(c->rs_queue, 0, sizeof(uint32_t), s));
+    rs_scan_tiles_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles);
+    rs_scan_top_kernel<<<1, 256, 0, s>>>(c->rs_tiles, (uint32_t)ntiles);
+    rs_scan_final_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles, d_offsets, algo == PCT_ALGO_GRID ? (uint32_t)kRsShort : 1u,
+                                                c->rs_queue);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// step 3: the lists, written only when d_offsets[Q] <= cap (tested on the device), then the queued rows put into final order
+int rs_fill_sort(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, int order, const long long *d_offsets, int64_t cap,
+                 uint32_t *d_idx, double *d_d2, hipStream_t s)
+{
+    if (c->count == 0 || cap <= 0) return PCT_OK;            // every row is empty, or there is no room for a single entry
+    const bool by_dist = order == PCT_ORDER_DISTANCE;
+    if (algo == PCT_ALGO_GRID) {
+        const float4 *recs = nullptr;
+        PCTCHK(bin_queries(c, d_q, Q, s, &recs));
+        const int blocks = ceil_div(Q, kKnnGroups);
+        if (by_dist)
+            rs_fill_grid_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, recs, (uint32_t)c->index_base, d_offsets,
+                                                             (long long)cap, d_idx, d_d2);
+        else
+            rs_fill_grid_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, recs, (uint32_t)c->index_base, d_offsets,
+                                                              (long long)cap, d_idx, d_d2);
+    } else {
+        HIPCHK(hipMemsetAsync(c->rs_cursor, 0, sizeof(uint32_t) * Q, s));
+        const int nparts = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->count + 4095) / 4096));
+        const int64_t tiles = (Q + kRsTile - 1) / kRsTile;
+        for (int64_t t0 = 0; t0 < tiles; t0 += 32768) {      // grid.y stays within every HIP limit
+            const int nt = (int)std::min<int64_t>(32768, tiles - t0);
+            rs_fill_stream_kernel<<<dim3(nparts, nt), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q, d_r, (uint32_t)Q, (uint32_t)t0,
+                                                                   (uint32_t)c->index_base, d_offsets, (long long)cap, c->rs_cursor, d_idx, d_d2);
+        }
+    }
+    const int sblocks = (int)std::min<int64_t>(Q, 8192);
+    if (by_dist) rs_sort_rows_kernel<true><<<sblocks, 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
+    else rs_sort_rows_kernel<false><<<sblocks, 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
 InflateParams to_dev(const pct_inflate_params *p)
 {
     return InflateParams{ p->start[0], p->start[1], p->start[2], p->sample_range, p->search_margin, p->max_radius };
@@ -1256,6 +1358,7 @@ int pct_cloud_destroy(pct_cloud *c)
     dev_free(c->d_coef); dev_free(c->d_segtime); dev_free(c->d_orders); dev_free(c->d_nsamples); dev_free(c->d_first_hit);
     dev_free(c->d_work);
     dev_free(c->d_knn_idx); dev_free(c->d_knn_d2); dev_free(c->d_knn_pidx); dev_free(c->d_knn_pd2);
+    dev_free(c->rs_off); dev_free(c->rs_tiles); dev_free(c->rs_cursor); dev_free(c->rs_queue); dev_free(c->rs_idx); dev_free(c->rs_d2);
     dev_free(c->d_bbox); dev_free(c->d_gbcheck); dev_free(c->pyr_nodes); dev_free(c->pyr_hint);
     if (c->h_gbcheck) (void)hipHostFree(c->h_gbcheck);
     dev_free(c->ring_ht); dev_free(c->ring_slots); dev_free(c->ring_ovf); dev_free(c->ring_where); dev_free(c->ring_st);
@@ -1630,6 +1733,70 @@ int pct_knn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, int32_
 int pct_knn_batch(pct_cloud *c, const float *q, int64_t Q, int32_t k, uint32_t *idx, double *d2)
 {
     return pct_knn_batch_algo(c, PCT_ALGO_AUTO, q, Q, k, idx, d2);
+}
+
+// ---- radius search with lists --------------------------------------------------------------
+int pct_radius_search_batch_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, int order, int64_t *d_offsets, int64_t cap,
+                                uint32_t *d_idx, double *d_d2, void *stream)
+{
+    if (!c || Q < 0 || !d_offsets || cap < 0 || (Q > 0 && (!d_q || !d_r)) || (cap > 0 && !d_idx))
+        return fail(PCT_ERR_INVALID, "bad radius_search_batch_dev arguments");
+    if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
+    PCTCHK(rs_pick_algo(c, &algo));
+    hipStream_t s = (hipStream_t)stream;
+    c->rs_valid = false;                                     // the host form's result ends with the next search of either form
+    if (Q == 0) {
+        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
+        return PCT_OK;
+    }
+    if (order == PCT_ORDER_DISTANCE && !d_d2 && cap > 0) {   // the sort key needs a home: the cloud's own list buffer
+        PCTCHK(rs_ensure_lists(c, (size_t)cap));
+        d_d2 = c->rs_d2;
+    }
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(rs_ensure_work(c));
+    PCTCHK(order_after_mutations(c, s));
+    PCTCHK(rs_count_scan(c, algo, d_q, d_r, Q, reinterpret_cast<long long *>(d_offsets), s));
+    return rs_fill_sort(c, algo, d_q, d_r, Q, order, reinterpret_cast<long long *>(d_offsets), cap, d_idx, d_d2, s);
+}
+
+int pct_radius_search_batch(pct_cloud *c, int algo, const float *q, const float *r, int64_t Q, int order, int64_t *offsets, int64_t *total)
+{
+    if (!c || Q < 0 || !offsets || !total || (Q > 0 && (!q || !r))) return fail(PCT_ERR_INVALID, "bad radius_search_batch arguments");
+    if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
+    PCTCHK(rs_pick_algo(c, &algo));
+    c->rs_valid = false;
+    c->rs_total = 0;
+    offsets[0] = 0;
+    *total = 0;
+    if (Q == 0) { c->rs_valid = true; return PCT_OK; }
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    PCTCHK(rs_ensure_work(c));                               // before c->rs_off is handed on
+    HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(c->d_r, r, sizeof(float) * Q, hipMemcpyHostToDevice, g_stream));
+    PCTCHK(rs_count_scan(c, algo, c->d_q, c->d_r, Q, c->rs_off, g_stream));
+    HIPCHK(hipMemcpyAsync(offsets, c->rs_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));                  // the one host read: the total sizes the lists
+    *total = offsets[Q];
+    if (*total > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "radius search lists %lld entries, more than 2^32 - 1", (long long)*total);
+    PCTCHK(rs_ensure_lists(c, (size_t)*total));
+    PCTCHK(rs_fill_sort(c, algo, c->d_q, c->d_r, Q, order, c->rs_off, *total, c->rs_idx, c->rs_d2, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    c->rs_total = *total;
+    c->rs_valid = true;
+    return PCT_OK;
+}
+
+int pct_radius_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2)
+{
+    if (!c || !c->rs_valid) return fail(PCT_ERR_INVALID, "no radius-search result to read (none yet, or the cloud changed since)");
+    if (first < 0 || n < 0 || first > c->rs_total || n > c->rs_total - first)
+        return fail(PCT_ERR_INVALID, "entries [%lld, %lld) lie outside [0, %lld]", (long long)first, (long long)(first + n), (long long)c->rs_total);
+    if (n == 0) return PCT_OK;
+    if (idx) HIPCHK(hipMemcpyAsync(idx, c->rs_idx + first, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g_stream));
+    if (d2) HIPCHK(hipMemcpyAsync(d2, c->rs_d2 + first, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return PCT_OK;
 }
 
 int pct_nn_batch_q64(pct_cloud *c, const double *q, int64_t Q, uint32_t *idx, double *d2)

@@ -15,6 +15,7 @@ from . import build as _build
 NO_INDEX = 0xFFFFFFFF
 ALGO_AUTO, ALGO_STREAM, ALGO_GRID, ALGO_STREAM_EXACT = 0, 1, 2, 3
 KNN_MAX_K = 64                  # PCT_KNN_MAX_K
+ORDER_INDEX, ORDER_DISTANCE = 0, 1      # enum pct_order: rows of a radius search in ascending index / nearest first
 
 _lib = None
 
@@ -100,6 +101,9 @@ def lib():
         L.pct_knn_batch.argtypes = [vp, f32p, i64, C.c_int32, u32p, f64p]
         L.pct_knn_batch_algo.argtypes = [vp, i32, f32p, i64, C.c_int32, u32p, f64p]
         L.pct_knn_batch_dev.argtypes = [vp, i32, vp, i64, C.c_int32, vp, vp, vp]
+        L.pct_radius_search_batch.argtypes = [vp, i32, f32p, f32p, i64, i32, vp, C.POINTER(i64)]
+        L.pct_radius_search_read.argtypes = [vp, i64, i64, u32p, f64p]
+        L.pct_radius_search_batch_dev.argtypes = [vp, i32, vp, vp, i64, i32, vp, i64, vp, vp, vp]
         L.pct_radius_count_batch.argtypes = [vp, f32p, f32p, i64, u32p]
         L.pct_radius_count_batch_algo.argtypes = [vp, i32, f32p, f32p, i64, u32p]
         L.pct_radius_indices.argtypes = [vp, f32p, C.c_float, u32p, i64, C.POINTER(i64)]
@@ -319,6 +323,27 @@ class Cloud:
         _chk(lib().pct_radius_count_batch_algo(self._h, algo, _ptr(q), _ptr(r), len(q), _ptr(cnt)))
         return cnt
 
+    def radius_search(self, queries, radii, order: int = ORDER_DISTANCE, algo: int = ALGO_AUTO):
+        """which points lie within radii[i] of queries[i] (pct_radius_search_batch + pct_radius_search_read): (offsets int64 [Q + 1],
+        idx uint32 [total], d2 float64 [total]); row i = entries offsets[i] .. offsets[i + 1], nearest first with ties in ascending
+        index (ORDER_DISTANCE) or in ascending index (ORDER_INDEX).  A scalar radius broadcasts."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, np.float32), (len(q),)))
+        offsets = np.zeros(len(q) + 1, np.int64)
+        total = C.c_int64()
+        _chk(lib().pct_radius_search_batch(self._h, algo, _ptr(q), _ptr(r), len(q), int(order), _ptr(offsets), C.byref(total)))
+        idx = np.empty(total.value, np.uint32)
+        d2 = np.empty(total.value, np.float64)
+        _chk(lib().pct_radius_search_read(self._h, 0, total.value, _ptr(idx), _ptr(d2)))
+        return offsets, idx, d2
+
+    def radius_search_read(self, first: int, n: int, want_idx: bool = True, want_d2: bool = True):
+        """entries [first, first + n) of the last radius_search on this cloud (pct_radius_search_read): (idx or None, d2 or None)"""
+        idx = np.empty(max(int(n), 0), np.uint32) if want_idx else None
+        d2 = np.empty(max(int(n), 0), np.float64) if want_d2 else None
+        _chk(lib().pct_radius_search_read(self._h, int(first), int(n), None if idx is None else _ptr(idx), None if d2 is None else _ptr(d2)))
+        return idx, d2
+
     def radius_indices(self, center, radius, cap=None):
         q = np.ascontiguousarray(center, np.float32).reshape(3)
         cap = int(cap if cap is not None else max(len(self), 1))
@@ -400,6 +425,13 @@ class Cloud:
 
     def radius_count_device(self, q_ptr: int, r_ptr: int, Q: int, cnt_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         _chk(lib().pct_radius_count_batch_dev(self._h, algo, q_ptr, r_ptr, int(Q), cnt_ptr, stream))
+
+    def radius_search_device(self, q_ptr: int, r_ptr: int, Q: int, order: int, offsets_ptr: int, cap: int, idx_ptr: int, d2_ptr: int,
+                             stream: int = 0, algo: int = ALGO_AUTO):
+        """pct_radius_search_batch_dev: offsets int64 [Q + 1] always written, idx / d2 (d2_ptr may be 0) only when offsets[Q] <= cap;
+        reserve_queries(Q) first"""
+        _chk(lib().pct_radius_search_batch_dev(self._h, algo, q_ptr, r_ptr, int(Q), int(order), offsets_ptr, int(cap), idx_ptr or None,
+                                               d2_ptr or None, stream))
 
     def set_timing(self, level: int):
         """0 = no events, 1 = dominant kernel only (default), 2 = + whole batch (needed by last_batch_ms)"""
