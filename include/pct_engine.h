@@ -60,6 +60,9 @@
  * NaN or infinite coordinate (the other rows of the batch are as without it); and the place of cloud rows with a NaN or infinite
  * coordinate on the paths that accept them (above), which are never listed.  k < 1 or k > PCT_KNN_MAX_K: PCT_ERR_INVALID.  Q = 0:
  * PCT_OK.  Empty cloud: every slot padded; the host forms return PCT_ERR_EMPTY, pct_knn_batch_dev PCT_OK, as for pct_nn_batch*.
+ * On a rolling map PCT_ALGO_RING (and PCT_ALGO_AUTO, which takes it there) walks the rolling-map index: the expanding cube of buckets
+ * around the query until the list holds k entries and no unseen bucket can hold a closer point -- same rows, bit for bit, as the
+ * exhaustive PCT_ALGO_STREAM over the window.
  *
  * Radius search with lists (pct_radius_search_batch*): PCL's radiusSearch(p, r, indices, sqr_distances) for a batch, the sibling of
  * pct_knn_batch.  The result is a CSR: row i = entries [offsets[i], offsets[i + 1]), offsets has Q + 1 entries, offsets[0] = 0 and
@@ -71,11 +74,13 @@
  * Order: PCT_ORDER_INDEX lists each row in ascending index (the order of pct_radius_indices, and of the reference's kd_nearest_range
  * result once sorted); PCT_ORDER_DISTANCE lists nearest first, among equal d2 the lower index first (the engine's total order: that
  * of pct_knn_batch and of pct_radius_crop(sort_by_distance)).  Both are deterministic: two runs give identical bytes.
- * Algorithms: PCT_ALGO_GRID uses the cell index and returns PCT_ERR_INVALID without one; PCT_ALGO_STREAM is exhaustive, for any
- * cloud (PCT_ALGO_STREAM_EXACT is accepted as STREAM); PCT_ALGO_AUTO takes the grid when one is built and the streaming form
- * otherwise -- on a rolling-map (ring-indexed) cloud and on a small host-mapped cloud the answer is therefore exact but NOT
- * index-accelerated: every query examines every point of the window.  An unknown algo, or an order other than 0 / 1:
- * PCT_ERR_INVALID.  Host form: the lists stay in a cloud-owned device buffer of 12 B per entry, grown on demand; offsets and total
+ * Algorithms: PCT_ALGO_GRID uses the cell index and returns PCT_ERR_INVALID without one; PCT_ALGO_RING uses the rolling-map index
+ * (the buckets of the ball's bounding box, each read once, and the overflow queue) and returns PCT_ERR_INVALID on a cloud without
+ * pct_cloud_ring_index; PCT_ALGO_STREAM is exhaustive, for any cloud (PCT_ALGO_STREAM_EXACT is accepted as STREAM); PCT_ALGO_AUTO
+ * takes the rolling-map index on a rolling map, the grid when one is built and the streaming form otherwise -- under
+ * PCT_ALGO_STREAM, and on a small host-mapped cloud under any algo, the answer is therefore exact but NOT index-accelerated: every
+ * query examines every point of the window.  pct_radius_count_batch* dispatches the same way.  An unknown algo, or an order other
+ * than 0 / 1: PCT_ERR_INVALID.  Host form: the lists stay in a cloud-owned device buffer of 12 B per entry, grown on demand; offsets and total
  * are copied out and pct_radius_search_read then copies any range of the lists, so a caller sizes its buffers from total without a
  * second search.  A result lasts until the next radius search (either form), upload, append, grid build or drop, or destroy on that
  * cloud: a read after any of those, a read before any search, or a range outside [0, total] returns PCT_ERR_INVALID; n = 0 is
@@ -84,6 +89,11 @@
  * offsets / total still valid.  Device form: d_offsets[Q + 1] is always written; the lists are written only when
  * d_offsets[Q] <= cap -- the kernels test this on the device and leave d_idx / d_d2 untouched otherwise, the caller reads
  * d_offsets[Q] to find out.  There is no max_nn: a bounded list is pct_knn_batch cut at r*r.
+ *
+ * Rolling-map index and the overflow-queue overrun: the append kernels flag a queue that would overrun (ring.hpp: cannot happen by the
+ * queue's sizing; a point is then missing from the table although it is in the window).  The host forms of the calls that search the
+ * table look at the flag after their wait, file the window again and ask once more; the device forms (*_dev) return before their
+ * kernels have run and cannot repair -- the next host-form call or append on the cloud does.
  *
  * All entry points need a HIP device; there is no host fallback.
  */
@@ -113,10 +123,11 @@ enum pct_status {
 #define PCT_NO_INDEX 0xFFFFFFFFu
 
 enum pct_algo {
-    PCT_ALGO_AUTO = 0,       /* grid kernel when a grid is built, streaming kernel otherwise */
+    PCT_ALGO_AUTO = 0,       /* rolling-map index when the cloud has one, grid kernel when a grid is built, streaming kernel otherwise */
     PCT_ALGO_STREAM = 1,     /* brute-force SoA streaming kernels: fp32 filter + exact fp64 recheck (no index needed) */
     PCT_ALGO_GRID = 2,       /* cell-pruned kernel (needs pct_cloud_build_grid) */
-    PCT_ALGO_STREAM_EXACT = 3 /* brute force with every pair in fp64 (the filter's reference; same results) */
+    PCT_ALGO_STREAM_EXACT = 3, /* brute force with every pair in fp64 (the filter's reference; same results) */
+    PCT_ALGO_RING = 4        /* the rolling-map index (needs pct_cloud_ring_index; PCT_ERR_INVALID without a live one) */
 };
 
 enum pct_order {
@@ -161,8 +172,10 @@ int pct_cloud_append_aos(pct_cloud *c, const void *pts, int64_t n, int64_t strid
  * rebuilds its search tree per frame -- safeRegionRrtStar::setInput, Planner/src/corridor_finder.cpp:93-99 called from
  * rcvPointCloudCallBack, Planner/src/sim_planning_demo.cpp:159-167).  After this call pct_cloud_append_aos no longer drops an
  * index: it retires the points it overwrites from a world-anchored bucket table and files the new frame, in place, and
- * pct_nn_batch / pct_inflate_batch / pct_bezier_check / pct_ctrl_points_check / the replan plan search that table (ALGO_AUTO
- * and ALGO_GRID; ALGO_STREAM still scans the whole window).  Results are the same as on any other cloud: exact fp64
+ * pct_nn_batch / pct_inflate_batch / pct_bezier_check / pct_ctrl_points_check / the replan plan search that table (ALGO_AUTO,
+ * ALGO_RING and, for these nearest-point calls, ALGO_GRID), and so do pct_knn_batch*, pct_radius_count_batch* and
+ * pct_radius_search_batch* (ALGO_AUTO and ALGO_RING; ALGO_GRID is PCT_ERR_INVALID there, as on any cloud without a grid).
+ * ALGO_STREAM still scans the whole window.  Results are the same as on any other cloud: exact fp64
  * distances, lowest ring slot on ties.  cell_size <= 0: chosen from the first data (about 6 points per cell at capacity);
  * extent (may be NULL): the window's size per axis, when the caller knows it (e.g. the sensing range) -- the table is then
  * allocated at once.  Memory: 512 B per bucket (32 records of 16 B), buckets = the extent / cell_size per axis plus a quarter,
@@ -205,9 +218,10 @@ int pct_nn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, uint32_
 /* The k nearest points of every query (contract: top of this file).  idx / d2: Q x k, row-major, each row nearest first.
  * PCT_ALGO_GRID: the cell-pruned k-NN kernel (needs pct_cloud_build_grid, PCT_ERR_INVALID otherwise); PCT_ALGO_STREAM and
  * PCT_ALGO_STREAM_EXACT: the streaming k-NN kernel, all fp64, which reads the cloud once per tile of 8 queries whatever k is;
- * PCT_ALGO_AUTO: the cell-pruned kernel when a grid is built, otherwise the streaming one -- that covers a rolling-map
- * (ring-indexed) cloud and a small host-mapped cloud, where the answer is exact but NOT index-accelerated: every query
- * examines every point of the window. */
+ * PCT_ALGO_RING: the rolling-map index (needs pct_cloud_ring_index, PCT_ERR_INVALID otherwise), a block per query;
+ * PCT_ALGO_AUTO: the rolling-map index on a rolling map, the cell-pruned kernel when a grid is built, otherwise the streaming
+ * one -- that covers a small host-mapped cloud, where (as under PCT_ALGO_STREAM on any cloud) the answer is exact but NOT
+ * index-accelerated: every query examines every point of the window. */
 #define PCT_KNN_MAX_K 64
 int pct_knn_batch(pct_cloud *c, const float *q, int64_t Q, int32_t k, uint32_t *idx, double *d2);
 int pct_knn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, int32_t k, uint32_t *idx, double *d2);
@@ -216,7 +230,8 @@ int pct_nn_batch_q64(pct_cloud *c, const double *q, int64_t Q, uint32_t *idx, do
 /* the same, also reporting how many points attain the minimum: ties[i] >= 1 where counted (single queries against clouds of up
  * to 16384 points -- the RRT* node sets of the kd_* drop-in), 0 = not counted on the path taken.  ties may be NULL. */
 int pct_nn_batch_q64_ties(pct_cloud *c, const double *q, int64_t Q, uint32_t *idx, double *d2, uint32_t *ties);
-/* count[Q] = #points with d2 <= r*r */
+/* count[Q] = #points with d2 <= r*r.  algo as for pct_radius_search_batch: the rolling-map index (PCT_ALGO_RING, and PCT_ALGO_AUTO
+ * on a rolling map), the grid, or the exhaustive streaming kernels */
 int pct_radius_count_batch(pct_cloud *c, const float *q, const float *r, int64_t Q, uint32_t *count);
 int pct_radius_count_batch_algo(pct_cloud *c, int algo, const float *q, const float *r, int64_t Q, uint32_t *count);
 /* Which points lie within r, for many queries at once (contract: top of this file).
@@ -320,7 +335,8 @@ int pct_ctrl_points_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_i
  * sees the results.  One batch at a time per cloud: the cloud's scratch buffers are shared, so do not
  * issue batches on the same cloud from two streams concurrently.  A rolling-map append that is still running on the library's
  * own stream (pct_cloud_append_aos returns once its launches are queued) is waited for through an event, so a batch issued right
- * after it on `stream` sees the appended frame.  For torch.distributed sharding and
+ * after it on `stream` sees the appended frame.  algo as for the host forms, PCT_ALGO_RING included; on a rolling map the device
+ * forms search the table as it is and cannot repair an overflow-queue overrun (top of this file).  For torch.distributed sharding and
  * graph capture.  An empty shard yields idx=PCT_NO_INDEX, d2=+inf and PCT_OK. ---------------------- */
 int pct_nn_batch_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, void *stream);
 int pct_radius_count_batch_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, uint32_t *d_count, void *stream);

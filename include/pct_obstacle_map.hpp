@@ -142,7 +142,8 @@ public:
         check(pct_nn_batch(cloud_, queries, n, index, d2), "pct_nn_batch");
     }
     // the k > 1 form of the same call (kdtreeForMap.nearestKSearch(p, k, ..), corridor_finder.cpp:130): index / d2 are n x k row-major,
-    // each row nearest first, ties in ascending index, padded with PCT_NO_INDEX / +inf beyond the cloud's size; 1 <= k <= PCT_KNN_MAX_K
+    // each row nearest first, ties in ascending index, padded with PCT_NO_INDEX / +inf beyond the cloud's size; 1 <= k <= PCT_KNN_MAX_K.
+    // Index-accelerated on every indexed map: the cell index, or -- after enableRollingIndex -- the rolling-map bucket table
     void nearestKSearch(const float *queries, int64_t n, int k, uint32_t *index, double *d2)
     {
         check(pct_knn_batch(cloud_, queries, n, (int32_t)k, index, d2), "pct_knn_batch");
@@ -150,7 +151,8 @@ public:
     // PCL's radiusSearch(p, r, indices, sqr_distances) for n queries at once (cone_keeper.cpp:120-126 asks it once per marked point):
     // row i of the result = index / d2 entries [offsets[i], offsets[i + 1]), offsets has n + 1 entries.  sorted: nearest first, ties in
     // ascending index (what PCL returns with sorted results); otherwise ascending index.  Not to be confused with radiusSearch(const
-    // double[3]) above, the planner's sphere inflation, which keeps its name.
+    // double[3]) above, the planner's sphere inflation, which keeps its name.  On a rolling map (enableRollingIndex) the rows come
+    // from the buckets of each ball's bounding box, not from a scan of the window.
     void radiusSearchBatch(const float *queries, const float *radii, int64_t n, std::vector<int64_t> &offsets, std::vector<uint32_t> &index,
                            std::vector<double> &d2, bool sorted = true)
     {

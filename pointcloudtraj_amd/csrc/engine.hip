@@ -29,6 +29,7 @@
 #include "brute2.hpp"
 #include "knn.hpp"
 #include "rsearch.hpp"
+#include "ring_search.hpp"
 
 using namespace pct;
 
@@ -904,17 +905,42 @@ int nn_stream_filtered(pct_cloud *c, const float *d_qf, int64_t Q, uint32_t *d_i
 }
 
 int ring_nn_dev(pct_cloud *c, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s);
+RingView ring_view(const pct_cloud *c);
+
+// PCT_ALGO_RING names the rolling-map index: it needs a live table, except on a cloud that asked for the index and holds no point
+// yet (the table is sized from the first data: the answer is the empty cloud's)
+int ring_algo_check(const pct_cloud *c, int algo)
+{
+    if (algo != PCT_ALGO_RING || c->ring_ready || (c->ring_on && c->count == 0)) return PCT_OK;
+    return fail(PCT_ERR_INVALID, "PCT_ALGO_RING without a rolling-map index (call pct_cloud_ring_index)");
+}
+
+// the launches of a batch over the bucket table (ring_search.hpp) share this frame: work counters cleared, timing events around
+template <typename L>
+int ring_search_launch(pct_cloud *c, hipStream_t s, L launch)
+{
+    c->host_work = false;
+    if (c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
+    begin_timing(c, s);
+    dom_begin(c, s);
+    launch(c->count_work ? c->d_work : nullptr);
+    dom_end(c, s);
+    end_timing(c, s);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
 
 int nn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
 {
     if (Q == 0) return PCT_OK;
     if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(ring_algo_check(c, algo));
     if (c->count == 0) {
         fill_empty_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_idx, d_d2, (uint32_t)Q);
         HIPCHK(hipGetLastError());
         return PCT_OK;
     }
-    if (c->ring_ready && (algo == PCT_ALGO_AUTO || algo == PCT_ALGO_GRID)) return ring_nn_dev(c, d_q, Q, d_idx, d_d2, s);   // rolling-map index
+    if (c->ring_ready && (algo == PCT_ALGO_AUTO || algo == PCT_ALGO_GRID || algo == PCT_ALGO_RING)) return ring_nn_dev(c, d_q, Q, d_idx, d_d2, s);   // rolling-map index
     if (algo == PCT_ALGO_AUTO) algo = c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
     if (algo == PCT_ALGO_GRID) {
         if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
@@ -967,9 +993,12 @@ int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_
 {
     if (Q == 0) return PCT_OK;
     if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld", (long long)Q, (long long)c->qcap);
+    PCTCHK(ring_algo_check(c, algo));
     HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint32_t) * Q, s));
     if (c->count == 0) return PCT_OK;
-    if (algo == PCT_ALGO_AUTO) algo = c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    if (algo == PCT_ALGO_RING)       // rolling-map index: a block per query over the buckets of the ball's box
+        return ring_search_launch(c, s, [&](WorkCounters *work) { ring_count_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, d_r, d_count, work); });
     if (algo == PCT_ALGO_GRID) {
         if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid");
         c->host_work = false;
@@ -1049,13 +1078,23 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
     if (Q == 0) return PCT_OK;
     if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
     if (Q * (int64_t)k > 0xFFFFFFFFll) return fail(PCT_ERR_INVALID, "k-NN batch of %lld x %d entries is too large", (long long)Q, k);
+    PCTCHK(ring_algo_check(c, algo));
     if (c->count == 0) {
         fill_empty_kernel<<<ceil_div(Q * k, 256), 256, 0, s>>>(d_idx, d_d2, (uint32_t)(Q * k));
         HIPCHK(hipGetLastError());
         return PCT_OK;
     }
-    if (algo == PCT_ALGO_AUTO) algo = c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
     const int kcap = k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64;
+    if (algo == PCT_ALGO_RING)       // rolling-map index: a block per query over the expanding cube of buckets
+        return ring_search_launch(c, s, [&](WorkCounters *work) {
+            switch (kcap) {
+            case 8: ring_knn_kernel<8><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2, work); break;
+            case 16: ring_knn_kernel<16><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2, work); break;
+            case 32: ring_knn_kernel<32><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2, work); break;
+            default: ring_knn_kernel<64><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2, work); break;
+            }
+        });
     if (algo == PCT_ALGO_GRID) {
         if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
         c->host_work = false;
@@ -1136,13 +1175,15 @@ int rs_ensure_lists(pct_cloud *c, size_t n)
     return PCT_OK;
 }
 
-// AUTO / STREAM_EXACT -> the path taken; PCT_ERR_INVALID for an unknown algo or PCT_ALGO_GRID without a grid
+// AUTO / STREAM_EXACT -> the path taken; PCT_ERR_INVALID for an unknown algo, PCT_ALGO_GRID without a grid or PCT_ALGO_RING without
+// a rolling-map index
 int rs_pick_algo(pct_cloud *c, int *algo)
 {
-    if (*algo == PCT_ALGO_AUTO) *algo = c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    if (*algo == PCT_ALGO_AUTO) *algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
     if (*algo == PCT_ALGO_STREAM_EXACT) *algo = PCT_ALGO_STREAM;
     if (*algo == PCT_ALGO_GRID && !c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
-    if (*algo != PCT_ALGO_GRID && *algo != PCT_ALGO_STREAM) return fail(PCT_ERR_INVALID, "unknown algo %d", *algo);
+    PCTCHK(ring_algo_check(c, *algo));
+    if (*algo != PCT_ALGO_GRID && *algo != PCT_ALGO_STREAM && *algo != PCT_ALGO_RING) return fail(PCT_ERR_INVALID, "unknown algo %d", *algo);
     return PCT_OK;
 }
 
@@ -1178,6 +1219,13 @@ int rs_fill_sort(pct_cloud *c, int algo, const float *d_q, const float *d_r, int
         else
             rs_fill_grid_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, recs, (uint32_t)c->index_base, d_offsets,
                                                               (long long)cap, d_idx, d_d2);
+    } else if (algo == PCT_ALGO_RING) {
+        // the count's walk once more, behind it on the same stream; its work is added to the count's (pct_last_work)
+        WorkCounters *work = c->count_work ? c->d_work : nullptr;
+        if (by_dist)
+            ring_fill_kernel<true><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, d_r, (uint32_t)Q, (uint32_t)c->index_base, d_offsets, (long long)cap, d_idx, d_d2, work);
+        else
+            ring_fill_kernel<false><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, d_r, (uint32_t)Q, (uint32_t)c->index_base, d_offsets, (long long)cap, d_idx, d_d2, work);
     } else {
         HIPCHK(hipMemsetAsync(c->rs_cursor, 0, sizeof(uint32_t) * Q, s));
         const int nparts = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->count + 4095) / 4096));
@@ -1647,7 +1695,7 @@ int pct_nn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, uint32_
 {
     if (!c || Q < 0 || (Q > 0 && (!q || !idx || !d2))) return fail(PCT_ERR_INVALID, "bad nn_batch arguments");
     if (Q == 0) return PCT_OK;
-    if (Q <= kExpressMaxQ && c->ring_ready && c->count > 0 && (algo == PCT_ALGO_AUTO || algo == PCT_ALGO_GRID)) {
+    if (Q <= kExpressMaxQ && c->ring_ready && c->count > 0 && (algo == PCT_ALGO_AUTO || algo == PCT_ALGO_GRID || algo == PCT_ALGO_RING)) {
         // small batch on the rolling map: one launch, a block per query, arguments/results in mapped memory
         for (int64_t i = 0; i < 3 * Q; i++) c->h_xin[i] = (double)q[i];
         ring_batch_kernel<false><<<(int)Q, 256, 0, g_stream>>>(ring_view(c), InflateParams{}, nullptr, c->d_xin, (double)INFINITY, (uint32_t)c->index_base,
@@ -1722,10 +1770,15 @@ int pct_knn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, int32_
         c->knn_out_cap = rows;
     }
     HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(knn_dev(c, algo, c->d_q, Q, (int)k, c->d_knn_idx, c->d_knn_d2, g_stream));
-    HIPCHK(hipMemcpyAsync(idx, c->d_knn_idx, sizeof(uint32_t) * rows, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemcpyAsync(d2, c->d_knn_d2, sizeof(double) * rows, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
+    for (int attempt = 0;; attempt++) {
+        PCTCHK(knn_dev(c, algo, c->d_q, Q, (int)k, c->d_knn_idx, c->d_knn_d2, g_stream));
+        HIPCHK(hipMemcpyAsync(idx, c->d_knn_idx, sizeof(uint32_t) * rows, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipMemcpyAsync(d2, c->d_knn_d2, sizeof(double) * rows, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        bool again = false;
+        PCTCHK(ring_overrun_repair(c, &again));          // the rolling-map index lost points (overflow-queue overrun): refiled, ask once more
+        if (!again || attempt) break;
+    }
     if (c->count == 0) return fail(PCT_ERR_EMPTY, "k-nearest-neighbour query against an empty cloud");
     return PCT_OK;
 }
@@ -1774,9 +1827,14 @@ int pct_radius_search_batch(pct_cloud *c, int algo, const float *q, const float 
     PCTCHK(rs_ensure_work(c));                               // before c->rs_off is handed on
     HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(c->d_r, r, sizeof(float) * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(rs_count_scan(c, algo, c->d_q, c->d_r, Q, c->rs_off, g_stream));
-    HIPCHK(hipMemcpyAsync(offsets, c->rs_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));                  // the one host read: the total sizes the lists
+    for (int attempt = 0;; attempt++) {
+        PCTCHK(rs_count_scan(c, algo, c->d_q, c->d_r, Q, c->rs_off, g_stream));
+        HIPCHK(hipMemcpyAsync(offsets, c->rs_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));              // the one host read: the total sizes the lists
+        bool again = false;
+        PCTCHK(ring_overrun_repair(c, &again));              // before the lists are sized: count and fill must see the same table
+        if (!again || attempt) break;
+    }
     *total = offsets[Q];
     if (*total > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "radius search lists %lld entries, more than 2^32 - 1", (long long)*total);
     PCTCHK(rs_ensure_lists(c, (size_t)*total));
@@ -1862,18 +1920,28 @@ int pct_radius_count_batch_algo(pct_cloud *c, int algo, const float *q, const fl
         std::memcpy(c->h_mq + 3 * Q, r, sizeof(float) * (size_t)Q);
         import_floats_kernel<<<ceil_div(3 * Q, 256), 256, 0, g_stream>>>(c->d_mq, (uint32_t)(3 * Q), c->d_q);
         import_floats_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->d_mq + 3 * Q, (uint32_t)Q, c->d_r);
-        PCTCHK(count_dev(c, algo, c->d_q, c->d_r, Q, c->d_count, g_stream));
-        export_results_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->d_count, nullptr, (uint32_t)Q, c->d_mi, nullptr, next_signal(c));
-        HIPCHK(hipGetLastError());
-        PCTCHK(express_wait(c));
+        for (int attempt = 0;; attempt++) {
+            PCTCHK(count_dev(c, algo, c->d_q, c->d_r, Q, c->d_count, g_stream));
+            export_results_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->d_count, nullptr, (uint32_t)Q, c->d_mi, nullptr, next_signal(c));
+            HIPCHK(hipGetLastError());
+            PCTCHK(express_wait(c));
+            bool again = false;
+            PCTCHK(ring_overrun_repair(c, &again));      // the rolling-map index lost points (overflow-queue overrun): refiled, ask once more
+            if (!again || attempt) break;
+        }
         std::memcpy(count, c->h_mi, sizeof(uint32_t) * (size_t)Q);
         return PCT_OK;
     }
     HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(c->d_r, r, sizeof(float) * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(count_dev(c, algo, c->d_q, c->d_r, Q, c->d_count, g_stream));
-    HIPCHK(hipMemcpyAsync(count, c->d_count, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
+    for (int attempt = 0;; attempt++) {
+        PCTCHK(count_dev(c, algo, c->d_q, c->d_r, Q, c->d_count, g_stream));
+        HIPCHK(hipMemcpyAsync(count, c->d_count, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        bool again = false;
+        PCTCHK(ring_overrun_repair(c, &again));
+        if (!again || attempt) break;
+    }
     return PCT_OK;
 }
 

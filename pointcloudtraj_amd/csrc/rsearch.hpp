@@ -6,6 +6,8 @@
 //              tile sums scanned by one block that loops), so Q is not limited.  The last pass also queues the rows step 3b sorts.
 //   3a. fill   rs_fill_grid_kernel (8 lanes per query over the box of rows the count walked) or rs_fill_stream_kernel (lanes own
 //              points, a tile of 8 queries is wave-uniform); the ball test is the count's: fp64 dist2() <= (double)r * (double)r.
+//              On a rolling map: ring_count_kernel / ring_fill_kernel over the bucket table (ring_search.hpp), rows queued as for the
+//              streaming fill.
 //   3b. sort   rs_sort_rows_kernel: a block per queued row, bitonic network in LDS (up to kRsSortLds entries) or in place in global
 //              memory (any length: a row may be the whole cloud).  (A wave per row of up to 512 entries, four rows per block and no
 //              block barrier, was measured and lost: 24.0 against 16.8 ms on 1 M rows of ~250 entries -- DESIGN.md.)

@@ -13,7 +13,7 @@ import numpy as np
 from . import build as _build
 
 NO_INDEX = 0xFFFFFFFF
-ALGO_AUTO, ALGO_STREAM, ALGO_GRID, ALGO_STREAM_EXACT = 0, 1, 2, 3
+ALGO_AUTO, ALGO_STREAM, ALGO_GRID, ALGO_STREAM_EXACT, ALGO_RING = 0, 1, 2, 3, 4
 KNN_MAX_K = 64                  # PCT_KNN_MAX_K
 ORDER_INDEX, ORDER_DISTANCE = 0, 1      # enum pct_order: rows of a radius search in ascending index / nearest first
 
