@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pct_engine.h"
@@ -83,6 +84,38 @@ void dev_free(T *&p)
 }
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// ---- run-time value -> template parameter --------------------------------------------------------------------------------------
+// f receives the value as a std::integral_constant and names the kernel instance with it: one argument list per call site
+template <typename F>
+void with_bool(bool b, F f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// list capacity of the k-NN kernels (knn.hpp): the smallest of 8 / 16 / 32 / 64 that holds k
+template <typename F>
+void with_kcap(int k, F f)
+{
+    if (k <= 8) f(std::integral_constant<int, 8>{});
+    else if (k <= 16) f(std::integral_constant<int, 16>{});
+    else if (k <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+// the streaming kernels take a batch in tiles of 8 / 4 / 2 / 1 queries: f(tile size as a constant, first query, queries in the tile)
+template <typename F>
+void for_each_query_tile(int64_t Q, F f)
+{
+    for (int64_t q0 = 0; q0 < Q;) {
+        const int64_t left = Q - q0;
+        if (left >= 8) { f(std::integral_constant<int, 8>{}, (int)q0, 8); q0 += 8; }
+        else if (left > 2) { const int n = (int)std::min<int64_t>(4, left); f(std::integral_constant<int, 4>{}, (int)q0, n); q0 += n; }
+        else if (left == 2) { f(std::integral_constant<int, 2>{}, (int)q0, 2); q0 += 2; }
+        else { f(std::integral_constant<int, 1>{}, (int)q0, 1); q0 += 1; }
+    }
+}
 
 constexpr int kExpressMaxQ = 1024;        // queries per express (block-per-query) launch
 constexpr int64_t kMappedMaxQ = 65536;    // host-buffer batches up to this size travel through host-mapped memory, larger ones by DMA
@@ -626,27 +659,6 @@ int stream_blocks(int64_t n, int64_t Q = 0)
     return (int)std::min<int64_t>(cap, (groups + 255) / 256);
 }
 
-template <int QT>
-void launch_nn_stream(pct_cloud *c, const double *d_q64, int blocks, int q0, int qcount, hipStream_t s)
-{
-    nn_stream_kernel<QT><<<blocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q64, q0, qcount, c->d_part_d2,
-                                                 c->d_part_idx, blocks);
-}
-
-template <int QT>
-void launch_count_stream(pct_cloud *c, int blocks, int q0, int qcount, uint32_t *d_count, hipStream_t s)
-{
-    count_stream_kernel<QT><<<blocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_q64, c->d_r2, q0, qcount, d_count);
-}
-
-int pick_tile(int64_t remaining)
-{
-    if (remaining >= 8) return 8;
-    if (remaining > 2) return 4;
-    if (remaining == 2) return 2;
-    return 1;
-}
-
 void begin_timing(pct_cloud *c, hipStream_t s)
 {
     c->ev_valid = false;
@@ -696,6 +708,74 @@ void dom_end(pct_cloud *c, hipStream_t s)
     else dom_done(c);
 }
 
+// ---- the launch frame -------------------------------------------------------------------------------------------------------
+// Every batch search queues its kernels through launch_frame, the one place that says where pct_last_work finds the batch's work,
+// zeroes the device counters, records the timing events and asks hipGetLastError.  On the stream, in this order:
+//   [memset of the work counters]  [ev0]  prologue  [ev2]  dominant  [ev3]  epilogue  [ev1]
+enum class Work {
+    Device,        // the kernels add to c->d_work, zeroed here when counting is on
+    DeviceKept,    // the NN batch over the bucket table: read from c->d_work as well, but its kernel does not count and the counters are not
+                   // zeroed, so pct_last_work reports the last instrumented batch (kept as found; looks like an oversight)
+    EveryPoint,    // streaming kernels: every point for every query, Q x n, known on the host
+    Untouched      // the streaming radius count says nothing: pct_last_work keeps reporting the batch before it (kept as found)
+};
+enum class Dom {
+    None,          // no events around a dominant kernel
+    Events,        // dom_begin / dom_end record them
+    Ext            // as Events, but when work is not counted the region is opened for a kernel that carries its own timestamps (launch_dominant)
+};
+struct Frame { Work work; Dom dom = Dom::Events; };
+
+inline void no_step() {}
+
+// a step of the frame: a callable that returns a status, or nothing when all it does is launch
+template <typename F>
+int run_step(F step)
+{
+    if constexpr (std::is_void_v<decltype(step())>) { step(); return PCT_OK; }
+    else return step();
+}
+
+// prologue / epilogue: inside the timed batch, outside the dominant region.  Q: the batch's size, for Work::EveryPoint.
+template <typename P, typename D, typename E>
+int launch_frame(pct_cloud *c, hipStream_t s, int64_t Q, Frame f, P prologue, D dominant, E epilogue)
+{
+    if (f.work == Work::Device || f.work == Work::DeviceKept) c->host_work = false;
+    if (f.work == Work::Device && c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
+    begin_timing(c, s);
+    PCTCHK(run_step(prologue));
+    if (f.dom != Dom::None) dom_begin(c, s, f.dom == Dom::Ext && !c->count_work);
+    PCTCHK(run_step(dominant));
+    if (f.dom != Dom::None) dom_end(c, s);
+    PCTCHK(run_step(epilogue));
+    end_timing(c, s);
+    HIPCHK(hipGetLastError());
+    if (f.work == Work::EveryPoint) {
+        c->host_work = true;
+        c->host_points = (uint64_t)Q * (uint64_t)c->count;
+    }
+    return PCT_OK;
+}
+
+template <typename D>
+int launch_frame(pct_cloud *c, hipStream_t s, int64_t Q, Frame f, D dominant)
+{
+    return launch_frame(c, s, Q, f, no_step, dominant, no_step);
+}
+
+// The dominant kernel of a Dom::Ext frame (blocks of 256 threads).  Where dom_begin left the region to the kernel, it is launched
+// with its own begin / end timestamps (hipExtLaunchKernel): no marker packets on the stream -- the two hipEventRecord calls of
+// dom_begin / dom_end cost ~10 us of a 160 us step.
+template <typename... P, typename... A>
+void launch_dominant(pct_cloud *c, hipStream_t s, void (*kernel)(P...), int blocks, A... args)
+{
+    if (!c->count_work && c->dom_valid && dom_ext_on()) {
+        hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, args...);
+        dom_done(c);
+    } else
+        kernel<<<blocks, 256, 0, s>>>(args...);
+}
+
 // streaming NN over the fp64 queries already in c->d_q64: one slice of at most c->part_q queries starting at qoff
 int nn_stream_q64_slice(pct_cloud *c, int64_t qoff, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
 {
@@ -703,26 +783,16 @@ int nn_stream_q64_slice(pct_cloud *c, int64_t qoff, int64_t Q, uint32_t *d_idx, 
     d_idx += qoff;
     d_d2 += qoff;
     const int blocks = stream_blocks(c->count, Q);
-    begin_timing(c, s);
-    dom_begin(c, s);
-    for (int64_t q0 = 0; q0 < Q;) {
-        const int qt = pick_tile(Q - q0);
-        const int qcount = (int)std::min<int64_t>(qt, Q - q0);
-        switch (qt) {
-        case 8: launch_nn_stream<8>(c, d_q64, blocks, (int)q0, qcount, s); break;
-        case 4: launch_nn_stream<4>(c, d_q64, blocks, (int)q0, qcount, s); break;
-        case 2: launch_nn_stream<2>(c, d_q64, blocks, (int)q0, qcount, s); break;
-        default: launch_nn_stream<1>(c, d_q64, blocks, (int)q0, qcount, s); break;
-        }
-        q0 += qcount;
-    }
-    dom_end(c, s);
-    nn_reduce_partials_kernel<<<(int)Q, 256, 0, s>>>(c->d_part_d2, c->d_part_idx, blocks, (uint32_t)c->index_base, d_idx, d_d2);
-    end_timing(c, s);
-    HIPCHK(hipGetLastError());
-    c->host_work = true;                    // the streaming kernel examines every point for every query
-    c->host_points = (uint64_t)Q * (uint64_t)c->count;
-    return PCT_OK;
+    return launch_frame(c, s, Q, { Work::EveryPoint }, no_step,
+        [&] {
+            for_each_query_tile(Q, [&](auto qt, int q0, int qcount) {
+                nn_stream_kernel<decltype(qt)::value><<<blocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q64, q0, qcount, c->d_part_d2,
+                                                                             c->d_part_idx, blocks);
+            });
+        },
+        [&] {
+            nn_reduce_partials_kernel<<<(int)Q, 256, 0, s>>>(c->d_part_d2, c->d_part_idx, blocks, (uint32_t)c->index_base, d_idx, d_d2);
+        });
 }
 
 int nn_stream_q64(pct_cloud *c, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
@@ -750,13 +820,11 @@ int bin_queries(pct_cloud *c, const float *d_q, int64_t Q, hipStream_t s, const 
     const uint32_t per_block = (uint32_t)std::min<int64_t>(kSortPerBlock, std::max<int64_t>(1024, (Q / 128 + 1023) / 1024 * 1024));
     const int nb = ceil_div(Q, (int64_t)per_block);
     // 16-byte aligned query arrays are fetched four queries (three float4) at a time (kernels.hpp sort_load_items)
-    if ((reinterpret_cast<uintptr_t>(d_q) & 15u) == 0) {
-        qsort_hist_kernel<true><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, pingpong ? total1_next : nullptr);
-        qsort_scatter1_kernel<true><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, c->d_qsorted);
-    } else {
-        qsort_hist_kernel<false><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, pingpong ? total1_next : nullptr);
-        qsort_scatter1_kernel<false><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, c->d_qsorted);
-    }
+    with_bool((reinterpret_cast<uintptr_t>(d_q) & 15u) == 0, [&](auto aligned) {
+        constexpr bool A = decltype(aligned)::value;
+        qsort_hist_kernel<A><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, pingpong ? total1_next : nullptr);
+        qsort_scatter1_kernel<A><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, c->d_qsorted);
+    });
     if (pingpong) c->sort_phase ^= 1;
     else HIPCHK(hipMemsetAsync(total1, 0, sizeof(uint32_t) * kSortBuckets, s));
     HIPCHK(hipGetLastError());
@@ -841,7 +909,6 @@ int nn_stream_filtered_slice(pct_cloud *c, const float *d_qf, int64_t qoff, int6
                                 : 1u;
     const int64_t schunks = std::max<int64_t>(1, (ngroups + 256ll * stride - 1) / (256ll * stride));
     const int sblocks = (int)((schunks + kSampleGroups - 1) / kSampleGroups);
-    begin_timing(c, s);
     // the sample partials borrow d_part_idx (u32 and float have the same size; [Q][sblocks], sblocks <= kMaxParts);
     // bound_reduce_kernel consumes them before the filter pass overwrites the buffer
     // slices of the batch in grid.y until ~2048 blocks are in flight (the kernels' tile loops are sequential)
@@ -851,49 +918,54 @@ int nn_stream_filtered_slice(pct_cloud *c, const float *d_qf, int64_t qoff, int6
         *qslice = ((tiles + slices - 1) / slices) * kTileQ;
         return (int)((Q + *qslice - 1) / *qslice);
     };
-    int sq = 0;
-    const int sslices = slices_for(sblocks, &sq);
-    nn_sample_bounds_kernel<<<dim3(sblocks, sslices), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, stride, d_qf, (int)Q, sq,
-                                                                   reinterpret_cast<float *>(c->d_part_idx), sblocks);
-    bound_reduce_kernel<<<(int)Q, 256, 0, s>>>(reinterpret_cast<const float *>(c->d_part_idx), sblocks, d_bound);
     CentreDesc CD{};
-    if (use_expanded_filter(c, &CD)) {
-        // expanded form (brute2.hpp): 3 FMAs per pair on centred coordinates, thresholds widened by the proven error band; the points
-        // held in registers (tile_reg_kernel), a block covers 256 * kRegGroups point groups, no LDS
-        float4 *qprep = c->d_qsorted + qoff;                     // the query-sort records are idle on this path
-        brute2_prep_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(CD, d_qf, d_bound, (uint32_t)Q, qprep);
-        dom_begin(c, s);
-        const int rblocks = (int)std::max<int64_t>(1, (ngroups + 256 * kRegGroups - 1) / (256 * kRegGroups));
-        int rq = 0;
-        const int rslices = slices_for(rblocks, &rq);
-        tile_reg_kernel<false><<<dim3(rblocks, rslices), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, qprep, d_q64, nullptr, (int)Q, rq,
-                                                                       c->d_cand_count, c->d_cand_d2, c->d_cand_idx, nullptr);
-    } else {
-        // survivors of the bound go to per-query candidate lists: no per-tile block reductions, no partial arrays
-        static bool attr = false;
-        if (!attr) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_tile_candidates_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(3 * kChunkGroupsMax * sizeof(float4))));
-            attr = true;
-        }
-        dom_begin(c, s);
-        int cq = 0;
-        const int cslices = slices_for(nblocks, &cq);
-        nn_tile_candidates_kernel<<<dim3(nblocks, cslices), 256, 3 * (size_t)chunk * sizeof(float4), s>>>(c->x, c->y, c->z, (uint32_t)c->count, chunk, d_qf,
-                                                                                                          d_q64, d_bound, (int)Q, cq, c->d_cand_count,
-                                                                                                          c->d_cand_d2, c->d_cand_idx);
-    }
-    dom_end(c, s);
-    HIPCHK(hipMemsetAsync(c->d_ovf, 0, sizeof(uint32_t), s));
-    nn_reduce_candidates_kernel<<<(int)Q, 256, 0, s>>>(c->d_cand_count, c->d_cand_d2, c->d_cand_idx, (uint32_t)c->index_base, c->d_ovf, d_idx, d_d2);
-    // overflowed lists (bulk exact ties): exact scan by the whole grid; both kernels return at once when there are none
-    nn_overflow_scan_kernel<<<kOvfBlocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q64, c->d_ovf, c->d_part_d2, c->d_part_idx);
-    nn_overflow_fold_kernel<<<(int)Q, 256, 0, s>>>(c->d_ovf, c->d_part_d2, c->d_part_idx, kOvfBlocks, (uint32_t)c->index_base, d_idx, d_d2);
-    end_timing(c, s);
-    HIPCHK(hipGetLastError());
-    c->host_work = true;
-    c->host_points = (uint64_t)Q * (uint64_t)c->count;
-    return PCT_OK;
+    bool expanded = false;
+    float4 *qprep = c->d_qsorted + qoff;                         // the query-sort records are idle on this path
+    return launch_frame(c, s, Q, { Work::EveryPoint },
+        [&]() -> int {
+            int sq = 0;
+            const int sslices = slices_for(sblocks, &sq);
+            nn_sample_bounds_kernel<<<dim3(sblocks, sslices), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, stride, d_qf, (int)Q, sq,
+                                                                           reinterpret_cast<float *>(c->d_part_idx), sblocks);
+            bound_reduce_kernel<<<(int)Q, 256, 0, s>>>(reinterpret_cast<const float *>(c->d_part_idx), sblocks, d_bound);
+            expanded = use_expanded_filter(c, &CD);
+            if (expanded) {
+                // expanded form (brute2.hpp): 3 FMAs per pair on centred coordinates, thresholds widened by the proven error band; the
+                // points held in registers (tile_reg_kernel), a block covers 256 * kRegGroups point groups, no LDS
+                brute2_prep_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(CD, d_qf, d_bound, (uint32_t)Q, qprep);
+                return PCT_OK;
+            }
+            // survivors of the bound go to per-query candidate lists: no per-tile block reductions, no partial arrays
+            static bool attr = false;
+            if (!attr) {
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_tile_candidates_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)(3 * kChunkGroupsMax * sizeof(float4))));
+                attr = true;
+            }
+            return PCT_OK;
+        },
+        [&] {
+            int qs = 0;
+            if (expanded) {
+                const int rblocks = (int)std::max<int64_t>(1, (ngroups + 256 * kRegGroups - 1) / (256 * kRegGroups));
+                const int rslices = slices_for(rblocks, &qs);
+                tile_reg_kernel<false><<<dim3(rblocks, rslices), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, qprep, d_q64, nullptr, (int)Q, qs,
+                                                                               c->d_cand_count, c->d_cand_d2, c->d_cand_idx, nullptr);
+            } else {
+                const int cslices = slices_for(nblocks, &qs);
+                nn_tile_candidates_kernel<<<dim3(nblocks, cslices), 256, 3 * (size_t)chunk * sizeof(float4), s>>>(c->x, c->y, c->z, (uint32_t)c->count, chunk,
+                                                                                                                  d_qf, d_q64, d_bound, (int)Q, qs, c->d_cand_count,
+                                                                                                                  c->d_cand_d2, c->d_cand_idx);
+            }
+        },
+        [&]() -> int {
+            HIPCHK(hipMemsetAsync(c->d_ovf, 0, sizeof(uint32_t), s));
+            nn_reduce_candidates_kernel<<<(int)Q, 256, 0, s>>>(c->d_cand_count, c->d_cand_d2, c->d_cand_idx, (uint32_t)c->index_base, c->d_ovf, d_idx, d_d2);
+            // overflowed lists (bulk exact ties): exact scan by the whole grid; both kernels return at once when there are none
+            nn_overflow_scan_kernel<<<kOvfBlocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q64, c->d_ovf, c->d_part_d2, c->d_part_idx);
+            nn_overflow_fold_kernel<<<(int)Q, 256, 0, s>>>(c->d_ovf, c->d_part_d2, c->d_part_idx, kOvfBlocks, (uint32_t)c->index_base, d_idx, d_d2);
+            return PCT_OK;
+        });
 }
 
 int nn_stream_filtered(pct_cloud *c, const float *d_qf, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
@@ -904,120 +976,135 @@ int nn_stream_filtered(pct_cloud *c, const float *d_qf, int64_t Q, uint32_t *d_i
     return PCT_OK;
 }
 
-int ring_nn_dev(pct_cloud *c, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s);
 RingView ring_view(const pct_cloud *c);
 
-// PCT_ALGO_RING names the rolling-map index: it needs a live table, except on a cloud that asked for the index and holds no point
-// yet (the table is sized from the first data: the answer is the empty cloud's)
-int ring_algo_check(const pct_cloud *c, int algo)
+// ---- which path a batch takes ------------------------------------------------------------------------------------------------
+enum class Op { NN, Count, KNN, RadiusSearch };
+enum class Path {
+    Table,         // the rolling-map index (ring.hpp, ring_search.hpp)
+    Grid,          // the cell index
+    Stream,        // brute force; for NN the fp32 filter + exact fp64 recheck
+    StreamExact,   // NN only: brute force with every pair in fp64
+    Empty          // the cloud holds no point: pad the outputs (PCT_NO_INDEX / +inf, zero counts, empty rows)
+};
+
+// The one place that turns a caller's `algo` into the path of a batch of Q queries, or into PCT_ERR_INVALID with its message
+// ("Dispatch of the batch searches").  The four searches grew their rules one by one and differ in corners nobody chose;
+// each such corner is marked "quirk" here and pinned by tests/test_gpu_dispatch.py, so that changing one is a decision, not an accident.
+int resolve_algo(const pct_cloud *c, Op op, int algo, int64_t Q, Path *path)
 {
-    if (algo != PCT_ALGO_RING || c->ring_ready || (c->ring_on && c->count == 0)) return PCT_OK;
-    return fail(PCT_ERR_INVALID, "PCT_ALGO_RING without a rolling-map index (call pct_cloud_ring_index)");
+    // PCT_ALGO_RING names the rolling-map index: it needs a live table, except on a cloud that asked for the index and holds no point
+    // yet (the table is sized from the first data: the answer is the empty cloud's)
+    if (algo == PCT_ALGO_RING && !c->ring_ready && !(c->ring_on && c->count == 0))
+        return fail(PCT_ERR_INVALID, "PCT_ALGO_RING without a rolling-map index (call pct_cloud_ring_index)");
+    // quirk: NN, count and k-NN pad an empty cloud's outputs before they look at any other algo value (an unknown one is PCT_OK from
+    // the device forms); the radius search validates algo first
+    if (op != Op::RadiusSearch && c->count == 0) { *path = Path::Empty; return PCT_OK; }
+    // quirk: on a rolling map NN takes PCT_ALGO_GRID to mean the bucket table; the other three answer "without a grid"
+    if (op == Op::NN && c->ring_ready && algo == PCT_ALGO_GRID) algo = PCT_ALGO_RING;
+    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    switch (algo) {
+    case PCT_ALGO_RING:
+        *path = Path::Table;
+        break;
+    case PCT_ALGO_GRID:
+        // quirk: the count's message is the short one
+        if (!c->has_grid) return fail(PCT_ERR_INVALID, op == Op::Count ? "PCT_ALGO_GRID without a grid" : "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
+        *path = Path::Grid;
+        break;
+    case PCT_ALGO_STREAM:
+        // NN, <= 4 queries: the all-fp64 kernel is already HBM-bound (50-62 % of peak); beyond that the packed-fp32 filter wins
+        *path = op == Op::NN && Q <= 4 ? Path::StreamExact : Path::Stream;
+        break;
+    case PCT_ALGO_STREAM_EXACT:
+        // quirk: the count called directly rejects STREAM_EXACT; k-NN and the radius search (whose first step is the count) run STREAM
+        if (op == Op::Count) return fail(PCT_ERR_INVALID, "unknown algo %d", algo);
+        *path = op == Op::NN ? Path::StreamExact : Path::Stream;
+        break;
+    default:
+        return fail(PCT_ERR_INVALID, "unknown algo %d", algo);
+    }
+    if (op == Op::KNN && *path == Path::Stream && c->capturing)
+        return fail(PCT_ERR_INVALID, "the streaming k-NN kernel is not available during graph capture");
+    if (c->count == 0) *path = Path::Empty;          // the radius search, its algo found valid
+    return PCT_OK;
 }
 
-// the launches of a batch over the bucket table (ring_search.hpp) share this frame: work counters cleared, timing events around
-template <typename L>
-int ring_search_launch(pct_cloud *c, hipStream_t s, L launch)
+// NN of a device-resident batch along `path` (resolve_algo, Op::NN); Q >= 1, within the reserved batch size
+int nn_run(pct_cloud *c, Path path, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
 {
-    c->host_work = false;
-    if (c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
-    begin_timing(c, s);
-    dom_begin(c, s);
-    launch(c->count_work ? c->d_work : nullptr);
-    dom_end(c, s);
-    end_timing(c, s);
-    HIPCHK(hipGetLastError());
-    return PCT_OK;
+    switch (path) {
+    case Path::Empty:
+        fill_empty_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_idx, d_d2, (uint32_t)Q);
+        HIPCHK(hipGetLastError());
+        return PCT_OK;
+    case Path::Table:        // rolling-map index: a block per query
+        return launch_frame(c, s, Q, { Work::DeviceKept }, [&] {
+            ring_batch_kernel<false><<<(int)Q, 256, 0, s>>>(ring_view(c), InflateParams{}, d_q, nullptr, (double)INFINITY, (uint32_t)c->index_base, d_idx, d_d2,
+                                                            nullptr, nullptr, ExpressSignal{});
+        });
+    case Path::Grid: {
+        const float4 *recs = nullptr;
+        const int blocks = ceil_div(Q, 256 / kCoop);      // 8 lanes per query
+        return launch_frame(c, s, Q, { Work::Device, Dom::Ext }, [&] { return bin_queries(c, d_q, Q, s, &recs); },
+            [&] {
+                with_bool(c->count_work, [&](auto count_work) {
+                    constexpr bool CW = decltype(count_work)::value;
+                    if (c->has_pyr) {     // sparse occupancy: stage 0, then the bounding-box pyramid instead of cube + shells (pyramid.hpp)
+                        // fp32 walk for everybody, then the exact walk for the (few) queries it lists as undecided
+                        launch_dominant(c, s, nn_grid_pyr_kernel<CW>, blocks, c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q,
+                                        (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
+                        nn_grid_pyr_todo_kernel<CW><<<(int)std::min<int64_t>(256, blocks), 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q,
+                                                                                                        (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
+                    } else
+                        launch_dominant(c, s, nn_grid_coop_kernel<CW>, blocks, c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx,
+                                        d_d2, c->d_work);
+                });
+            }, no_step);
+    }
+    default:
+        widen_queries_kernel<<<ceil_div(3 * Q, 256), 256, 0, s>>>(d_q, (uint32_t)(3 * Q), c->d_q64);
+        if (path == Path::StreamExact) return nn_stream_q64(c, Q, d_idx, d_d2, s);
+        return nn_stream_filtered(c, d_q, Q, d_idx, d_d2, s);
+    }
 }
 
 int nn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
 {
     if (Q == 0) return PCT_OK;
     if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
-    PCTCHK(ring_algo_check(c, algo));
-    if (c->count == 0) {
-        fill_empty_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_idx, d_d2, (uint32_t)Q);
-        HIPCHK(hipGetLastError());
-        return PCT_OK;
-    }
-    if (c->ring_ready && (algo == PCT_ALGO_AUTO || algo == PCT_ALGO_GRID || algo == PCT_ALGO_RING)) return ring_nn_dev(c, d_q, Q, d_idx, d_d2, s);   // rolling-map index
-    if (algo == PCT_ALGO_AUTO) algo = c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
-    if (algo == PCT_ALGO_GRID) {
-        if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
-        c->host_work = false;
-        if (c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
-        begin_timing(c, s);
-        const float4 *recs = nullptr;
-        PCTCHK(bin_queries(c, d_q, Q, s, &recs));
-        dom_begin(c, s, !c->count_work);
-        const int blocks = ceil_div(Q, 256 / kCoop);      // 8 lanes per query
-        if (c->has_pyr) {     // sparse occupancy: stage 0, then the bounding-box pyramid instead of cube + shells (pyramid.hpp)
-            // fp32 walk for everybody, then the exact walk for the (few) queries it lists as undecided
-            if (c->count_work)
-                nn_grid_pyr_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
-            else if (c->dom_valid && dom_ext_on()) {
-                hipExtLaunchKernelGGL((nn_grid_pyr_kernel<false>), dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q,
-                                      (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
-                dom_done(c);
-            } else
-                nn_grid_pyr_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
-            const int tblocks = (int)std::min<int64_t>(256, blocks);
-            if (c->count_work)
-                nn_grid_pyr_todo_kernel<true><<<tblocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
-            else
-                nn_grid_pyr_todo_kernel<false><<<tblocks, 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
-        } else if (c->count_work) {
-            nn_grid_coop_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
-        } else if (c->dom_valid && dom_ext_on()) {
-            // the kernel's own begin / end timestamps (hipExtLaunchKernel): no marker packets on the stream -- the two
-            // hipEventRecord calls of dom_begin / dom_end cost ~10 us of a 160 us step
-            hipExtLaunchKernelGGL((nn_grid_coop_kernel<false>), dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, c->G, c->sorted, c->cell_start, d_q,
-                                  (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
-            dom_done(c);
-        } else
-            nn_grid_coop_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
-        dom_end(c, s);
-        end_timing(c, s);
-        HIPCHK(hipGetLastError());
-        return PCT_OK;
-    }
-    if (algo != PCT_ALGO_STREAM && algo != PCT_ALGO_STREAM_EXACT) return fail(PCT_ERR_INVALID, "unknown algo %d", algo);
-    widen_queries_kernel<<<ceil_div(3 * Q, 256), 256, 0, s>>>(d_q, (uint32_t)(3 * Q), c->d_q64);
-    // <= 4 queries: the all-fp64 kernel is already HBM-bound (50-62 % of peak); beyond that the
-    // packed-fp32 filter wins
-    if (algo == PCT_ALGO_STREAM_EXACT || Q <= 4) return nn_stream_q64(c, Q, d_idx, d_d2, s);
-    return nn_stream_filtered(c, d_q, Q, d_idx, d_d2, s);
+    Path path;
+    PCTCHK(resolve_algo(c, Op::NN, algo, Q, &path));
+    return nn_run(c, path, d_q, Q, d_idx, d_d2, s);
 }
 
-int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, uint32_t *d_count, hipStream_t s)
+// radius counts of a device-resident batch along `path` (resolve_algo, Op::Count or Op::RadiusSearch); Q >= 1, within the reserved size
+int count_run(pct_cloud *c, Path path, const float *d_q, const float *d_r, int64_t Q, uint32_t *d_count, hipStream_t s)
 {
-    if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld", (long long)Q, (long long)c->qcap);
-    PCTCHK(ring_algo_check(c, algo));
     HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint32_t) * Q, s));
-    if (c->count == 0) return PCT_OK;
-    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
-    if (algo == PCT_ALGO_RING)       // rolling-map index: a block per query over the buckets of the ball's box
-        return ring_search_launch(c, s, [&](WorkCounters *work) { ring_count_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, d_r, d_count, work); });
-    if (algo == PCT_ALGO_GRID) {
-        if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid");
-        c->host_work = false;
-        if (c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
-        begin_timing(c, s);
-        const float4 *qs = nullptr;
-        PCTCHK(bin_queries(c, d_q, Q, s, &qs));
-        dom_begin(c, s, !c->count_work);
-        const int blocks = ceil_div(Q, 256 / kCoop);      // 8 lanes per query
-        if (c->count_work)
-            count_grid_coop_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, qs, d_count, c->d_work);
-        else
-            count_grid_coop_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, qs, d_count, c->d_work);
-        dom_end(c, s);
-        end_timing(c, s);
-        HIPCHK(hipGetLastError());
+    switch (path) {
+    case Path::Empty:
         return PCT_OK;
+    case Path::Table:        // rolling-map index: a block per query over the buckets of the ball's box
+        return launch_frame(c, s, Q, { Work::Device }, [&] {
+            ring_count_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, d_r, d_count, c->count_work ? c->d_work : nullptr);
+        });
+    case Path::Grid: {
+        const float4 *qs = nullptr;
+        const int blocks = ceil_div(Q, 256 / kCoop);      // 8 lanes per query
+        // Dom::Ext, yet the launch is a plain one: where the region is left to the kernel no begin event is recorded for this batch, and
+        // pct_last_kernel_ms pairs its end event with an older begin (kept as found; looks like an oversight)
+        return launch_frame(c, s, Q, { Work::Device, Dom::Ext }, [&] { return bin_queries(c, d_q, Q, s, &qs); },
+            [&] {
+                with_bool(c->count_work, [&](auto count_work) {
+                    count_grid_coop_kernel<decltype(count_work)::value><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, qs, d_count,
+                                                                                               c->d_work);
+                });
+            }, no_step);
     }
-    if (algo != PCT_ALGO_STREAM) return fail(PCT_ERR_INVALID, "unknown algo %d", algo);
+    default:
+        break;
+    }
     widen_queries_kernel<<<ceil_div(3 * Q, 256), 256, 0, s>>>(d_q, (uint32_t)(3 * Q), c->d_q64);
     CentreDesc CD{};
     if (Q >= 16 && use_expanded_filter(c, &CD)) {
@@ -1028,49 +1115,32 @@ int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_
         const int slices = std::max(1, std::min(tiles, (2048 + rblocks - 1) / rblocks));
         const int rq = ((tiles + slices - 1) / slices) * kTileQ;
         const int rslices = (int)((Q + rq - 1) / rq);
-        begin_timing(c, s);
-        brute2_prep_count_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(CD, d_q, d_r, (uint32_t)Q, c->d_qsorted, c->d_r2);
-        dom_begin(c, s);
-        const dim3 rgrid(rblocks, rslices);
-        tile_reg_kernel<true><<<rgrid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, c->d_qsorted, c->d_q64, c->d_r2, (int)Q, rq, nullptr, nullptr, nullptr, d_count);
-        dom_end(c, s);
-        end_timing(c, s);
-        HIPCHK(hipGetLastError());
-        return PCT_OK;
+        return launch_frame(c, s, Q, { Work::Untouched },
+            [&] { brute2_prep_count_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(CD, d_q, d_r, (uint32_t)Q, c->d_qsorted, c->d_r2); },
+            [&] {
+                tile_reg_kernel<true><<<dim3(rblocks, rslices), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, CD, c->d_qsorted, c->d_q64, c->d_r2, (int)Q, rq,
+                                                                             nullptr, nullptr, nullptr, d_count);
+            }, no_step);
     }
     square_radii_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_r, (uint32_t)Q, c->d_r2);
     const int blocks = stream_blocks(c->count);
-    begin_timing(c, s);
-    for (int64_t q0 = 0; q0 < Q;) {
-        const int qt = pick_tile(Q - q0);
-        const int qcount = (int)std::min<int64_t>(qt, Q - q0);
-        switch (qt) {
-        case 8: launch_count_stream<8>(c, blocks, (int)q0, qcount, d_count, s); break;
-        case 4: launch_count_stream<4>(c, blocks, (int)q0, qcount, d_count, s); break;
-        case 2: launch_count_stream<2>(c, blocks, (int)q0, qcount, d_count, s); break;
-        default: launch_count_stream<1>(c, blocks, (int)q0, qcount, d_count, s); break;
-        }
-        q0 += qcount;
-    }
-    end_timing(c, s);
-    HIPCHK(hipGetLastError());
-    return PCT_OK;
+    return launch_frame(c, s, Q, { Work::Untouched, Dom::None }, [&] {
+        for_each_query_tile(Q, [&](auto qt, int q0, int qcount) {
+            count_stream_kernel<decltype(qt)::value><<<blocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_q64, c->d_r2, q0, qcount, d_count);
+        });
+    });
+}
+
+int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, uint32_t *d_count, hipStream_t s)
+{
+    if (Q == 0) return PCT_OK;
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld", (long long)Q, (long long)c->qcap);
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Count, algo, Q, &path));
+    return count_run(c, path, d_q, d_r, Q, d_count, s);
 }
 
 constexpr size_t kKnnPartEntries = 8u << 20;      // partial lists of the streaming k-NN kernel: 96 MiB; larger batches go through in slices
-
-template <int KCAP>
-void launch_knn_grid(pct_cloud *c, const float *d_q, int64_t Q, int k, const float4 *recs, uint32_t *d_idx, double *d_d2, hipStream_t s)
-{
-    knn_grid_kernel<KCAP><<<ceil_div(Q, kKnnGroups), 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, k, (uint32_t)c->index_base, recs,
-                                                                   d_idx, d_d2, c->count_work ? c->d_work : nullptr);
-}
-
-template <int KCAP>
-void launch_knn_stream(pct_cloud *c, const float *d_q, int Q, int k, int nparts, hipStream_t s)
-{
-    knn_stream_kernel<KCAP><<<dim3(nparts, ceil_div(Q, kKnnTile)), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q, Q, k, c->d_knn_pd2, c->d_knn_pidx);
-}
 
 // k-NN rows of a device-resident batch: d_idx / d_d2 are Q x k
 int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t *d_idx, double *d_d2, hipStream_t s)
@@ -1078,44 +1148,34 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
     if (Q == 0) return PCT_OK;
     if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
     if (Q * (int64_t)k > 0xFFFFFFFFll) return fail(PCT_ERR_INVALID, "k-NN batch of %lld x %d entries is too large", (long long)Q, k);
-    PCTCHK(ring_algo_check(c, algo));
-    if (c->count == 0) {
+    Path path;
+    PCTCHK(resolve_algo(c, Op::KNN, algo, Q, &path));
+    switch (path) {
+    case Path::Empty:
         fill_empty_kernel<<<ceil_div(Q * k, 256), 256, 0, s>>>(d_idx, d_d2, (uint32_t)(Q * k));
         HIPCHK(hipGetLastError());
         return PCT_OK;
-    }
-    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
-    const int kcap = k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64;
-    if (algo == PCT_ALGO_RING)       // rolling-map index: a block per query over the expanding cube of buckets
-        return ring_search_launch(c, s, [&](WorkCounters *work) {
-            switch (kcap) {
-            case 8: ring_knn_kernel<8><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2, work); break;
-            case 16: ring_knn_kernel<16><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2, work); break;
-            case 32: ring_knn_kernel<32><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2, work); break;
-            default: ring_knn_kernel<64><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2, work); break;
-            }
+    case Path::Table:        // rolling-map index: a block per query over the expanding cube of buckets
+        return launch_frame(c, s, Q, { Work::Device }, [&] {
+            with_kcap(k, [&](auto kcap) {
+                ring_knn_kernel<decltype(kcap)::value><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, k, (uint32_t)c->index_base, d_idx, d_d2,
+                                                                              c->count_work ? c->d_work : nullptr);
+            });
         });
-    if (algo == PCT_ALGO_GRID) {
-        if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
-        c->host_work = false;
-        if (c->count_work) HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
-        begin_timing(c, s);
+    case Path::Grid: {
         const float4 *recs = nullptr;
-        PCTCHK(bin_queries(c, d_q, Q, s, &recs));
-        dom_begin(c, s);
-        switch (kcap) {
-        case 8: launch_knn_grid<8>(c, d_q, Q, k, recs, d_idx, d_d2, s); break;
-        case 16: launch_knn_grid<16>(c, d_q, Q, k, recs, d_idx, d_d2, s); break;
-        case 32: launch_knn_grid<32>(c, d_q, Q, k, recs, d_idx, d_d2, s); break;
-        default: launch_knn_grid<64>(c, d_q, Q, k, recs, d_idx, d_d2, s); break;
-        }
-        dom_end(c, s);
-        end_timing(c, s);
-        HIPCHK(hipGetLastError());
-        return PCT_OK;
+        return launch_frame(c, s, Q, { Work::Device }, [&] { return bin_queries(c, d_q, Q, s, &recs); },
+            [&] {
+                with_kcap(k, [&](auto kcap) {
+                    knn_grid_kernel<decltype(kcap)::value><<<ceil_div(Q, kKnnGroups), 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, k,
+                                                                                                   (uint32_t)c->index_base, recs, d_idx, d_d2,
+                                                                                                   c->count_work ? c->d_work : nullptr);
+                });
+            }, no_step);
     }
-    if (algo != PCT_ALGO_STREAM && algo != PCT_ALGO_STREAM_EXACT) return fail(PCT_ERR_INVALID, "unknown algo %d", algo);
-    if (c->capturing) return fail(PCT_ERR_INVALID, "the streaming k-NN kernel is not available during graph capture");
+    default:
+        break;
+    }
     if (!c->d_knn_pd2) {
         PCTCHK(dev_alloc(&c->d_knn_pd2, kKnnPartEntries));
         PCTCHK(dev_alloc(&c->d_knn_pidx, kKnnPartEntries));
@@ -1124,25 +1184,16 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
     // one block per 4096 points, at most 256: a block's four waves then see enough points for their lists to settle
     const int nparts = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->count + 4095) / 4096));
     const int64_t qslice = std::max<int64_t>(kKnnTile, (int64_t)(c->knn_part_cap / ((size_t)nparts * (size_t)k)) / kKnnTile * kKnnTile);
-    begin_timing(c, s);
-    dom_begin(c, s);
-    for (int64_t off = 0; off < Q; off += qslice) {
-        const int qn = (int)std::min<int64_t>(qslice, Q - off);
-        const float *qs = d_q + 3 * off;
-        switch (kcap) {
-        case 8: launch_knn_stream<8>(c, qs, qn, k, nparts, s); break;
-        case 16: launch_knn_stream<16>(c, qs, qn, k, nparts, s); break;
-        case 32: launch_knn_stream<32>(c, qs, qn, k, nparts, s); break;
-        default: launch_knn_stream<64>(c, qs, qn, k, nparts, s); break;
+    return launch_frame(c, s, Q, { Work::EveryPoint }, [&] {
+        for (int64_t off = 0; off < Q; off += qslice) {
+            const int qn = (int)std::min<int64_t>(qslice, Q - off);
+            with_kcap(k, [&](auto kcap) {
+                knn_stream_kernel<decltype(kcap)::value><<<dim3(nparts, ceil_div(qn, kKnnTile)), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q + 3 * off, qn, k,
+                                                                                                              c->d_knn_pd2, c->d_knn_pidx);
+            });
+            knn_merge_kernel<<<qn, 64, 0, s>>>(c->d_knn_pd2, c->d_knn_pidx, nparts, k, (uint32_t)c->index_base, d_idx + off * k, d_d2 + off * k);
         }
-        knn_merge_kernel<<<qn, 64, 0, s>>>(c->d_knn_pd2, c->d_knn_pidx, nparts, k, (uint32_t)c->index_base, d_idx + off * k, d_d2 + off * k);
-    }
-    dom_end(c, s);
-    end_timing(c, s);
-    HIPCHK(hipGetLastError());
-    c->host_work = true;                    // the streaming kernel examines every point for every query
-    c->host_points = (uint64_t)Q * (uint64_t)c->count;
-    return PCT_OK;
+    });
 }
 
 // ---- radius search with lists (rsearch.hpp) ----------------------------------------------------------------------------------
@@ -1175,57 +1226,41 @@ int rs_ensure_lists(pct_cloud *c, size_t n)
     return PCT_OK;
 }
 
-// AUTO / STREAM_EXACT -> the path taken; PCT_ERR_INVALID for an unknown algo, PCT_ALGO_GRID without a grid or PCT_ALGO_RING without
-// a rolling-map index
-int rs_pick_algo(pct_cloud *c, int *algo)
-{
-    if (*algo == PCT_ALGO_AUTO) *algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
-    if (*algo == PCT_ALGO_STREAM_EXACT) *algo = PCT_ALGO_STREAM;
-    if (*algo == PCT_ALGO_GRID && !c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
-    PCTCHK(ring_algo_check(c, *algo));
-    if (*algo != PCT_ALGO_GRID && *algo != PCT_ALGO_STREAM && *algo != PCT_ALGO_RING) return fail(PCT_ERR_INVALID, "unknown algo %d", *algo);
-    return PCT_OK;
-}
-
 // steps 1 and 2: row lengths (the radius-count batch, into c->d_count) and their exclusive scan into d_offsets[Q + 1]; the rows the
-// sort will take are queued in c->rs_queue.  algo: as rs_pick_algo left it.  Q >= 1.
-int rs_count_scan(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, long long *d_offsets, hipStream_t s)
+// sort will take are queued in c->rs_queue.  path: from resolve_algo(Op::RadiusSearch).  Q >= 1.
+int rs_count_scan(pct_cloud *c, Path path, const float *d_q, const float *d_r, int64_t Q, long long *d_offsets, hipStream_t s)
 {
     if (Q > c->rs_qcap || !d_offsets) return fail(PCT_ERR_INTERNAL, "radius search without its workspaces");      // rs_ensure_work comes first
-    PCTCHK(count_dev(c, algo, d_q, d_r, Q, c->d_count, s));
+    PCTCHK(count_run(c, path, d_q, d_r, Q, c->d_count, s));
     const int ntiles = ceil_div(Q, kRsScanTile);
     HIPCHK(hipMemsetAsync(c->rs_queue, 0, sizeof(uint32_t), s));
     rs_scan_tiles_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles);
     rs_scan_top_kernel<<<1, 256, 0, s>>>(c->rs_tiles, (uint32_t)ntiles);
-    rs_scan_final_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles, d_offsets, algo == PCT_ALGO_GRID ? (uint32_t)kRsShort : 1u,
+    rs_scan_final_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles, d_offsets, path == Path::Grid ? (uint32_t)kRsShort : 1u,
                                                 c->rs_queue);
     HIPCHK(hipGetLastError());
     return PCT_OK;
 }
 
 // step 3: the lists, written only when d_offsets[Q] <= cap (tested on the device), then the queued rows put into final order
-int rs_fill_sort(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, int order, const long long *d_offsets, int64_t cap,
+int rs_fill_sort(pct_cloud *c, Path path, const float *d_q, const float *d_r, int64_t Q, int order, const long long *d_offsets, int64_t cap,
                  uint32_t *d_idx, double *d_d2, hipStream_t s)
 {
-    if (c->count == 0 || cap <= 0) return PCT_OK;            // every row is empty, or there is no room for a single entry
+    if (path == Path::Empty || cap <= 0) return PCT_OK;      // every row is empty, or there is no room for a single entry
     const bool by_dist = order == PCT_ORDER_DISTANCE;
-    if (algo == PCT_ALGO_GRID) {
+    if (path == Path::Grid) {
         const float4 *recs = nullptr;
         PCTCHK(bin_queries(c, d_q, Q, s, &recs));
-        const int blocks = ceil_div(Q, kKnnGroups);
-        if (by_dist)
-            rs_fill_grid_kernel<true><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, recs, (uint32_t)c->index_base, d_offsets,
-                                                             (long long)cap, d_idx, d_d2);
-        else
-            rs_fill_grid_kernel<false><<<blocks, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, recs, (uint32_t)c->index_base, d_offsets,
-                                                              (long long)cap, d_idx, d_d2);
-    } else if (algo == PCT_ALGO_RING) {
+        with_bool(by_dist, [&](auto bd) {
+            rs_fill_grid_kernel<decltype(bd)::value><<<ceil_div(Q, kKnnGroups), 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_q, d_r, (uint32_t)Q, recs,
+                                                                                             (uint32_t)c->index_base, d_offsets, (long long)cap, d_idx, d_d2);
+        });
+    } else if (path == Path::Table) {
         // the count's walk once more, behind it on the same stream; its work is added to the count's (pct_last_work)
-        WorkCounters *work = c->count_work ? c->d_work : nullptr;
-        if (by_dist)
-            ring_fill_kernel<true><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, d_r, (uint32_t)Q, (uint32_t)c->index_base, d_offsets, (long long)cap, d_idx, d_d2, work);
-        else
-            ring_fill_kernel<false><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, d_r, (uint32_t)Q, (uint32_t)c->index_base, d_offsets, (long long)cap, d_idx, d_d2, work);
+        with_bool(by_dist, [&](auto bd) {
+            ring_fill_kernel<decltype(bd)::value><<<(int)Q, 256, 0, s>>>(ring_view(c), d_q, d_r, (uint32_t)Q, (uint32_t)c->index_base, d_offsets, (long long)cap, d_idx,
+                                                                         d_d2, c->count_work ? c->d_work : nullptr);
+        });
     } else {
         HIPCHK(hipMemsetAsync(c->rs_cursor, 0, sizeof(uint32_t) * Q, s));
         const int nparts = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->count + 4095) / 4096));
@@ -1236,9 +1271,9 @@ int rs_fill_sort(pct_cloud *c, int algo, const float *d_q, const float *d_r, int
                                                                    (uint32_t)c->index_base, d_offsets, (long long)cap, c->rs_cursor, d_idx, d_d2);
         }
     }
-    const int sblocks = (int)std::min<int64_t>(Q, 8192);
-    if (by_dist) rs_sort_rows_kernel<true><<<sblocks, 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
-    else rs_sort_rows_kernel<false><<<sblocks, 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
+    with_bool(by_dist, [&](auto bd) {
+        rs_sort_rows_kernel<decltype(bd)::value><<<(int)std::min<int64_t>(Q, 8192), 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
+    });
     HIPCHK(hipGetLastError());
     return PCT_OK;
 }
@@ -1265,6 +1300,76 @@ int inflate_dev(pct_cloud *c, const pct_inflate_params *p, int64_t Q, hipStream_
     else
         inflate_epilogue_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(P, (uint32_t)Q, c->d_skip, c->count == 0 ? 1 : 0, o_idx, o_d2, o_radius);
     HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// ---- host buffers of the batch entry points ------------------------------------------------------------------------------------
+// A host batch of Q queries (and radii, r != nullptr) into c->d_q (c->d_r).  Up to kMappedMaxQ queries go through host-mapped memory:
+// imported by a kernel here, results exported by a kernel and completion by polling in fetch_results -- no DMA copy, no stream
+// synchronise (C2's 4096-query batch: 0.63 -> 0.5x ms).  Larger batches by DMA.  *mapped: which, for fetch_results.
+int stage_queries(pct_cloud *c, const float *q, const float *r, int64_t Q, bool *mapped)
+{
+    *mapped = Q <= kMappedMaxQ && mapped_io_on();
+    if (!*mapped) {
+        HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
+        if (r) HIPCHK(hipMemcpyAsync(c->d_r, r, sizeof(float) * Q, hipMemcpyHostToDevice, g_stream));
+        return PCT_OK;
+    }
+    PCTCHK(ensure_mapped_io(c, Q));
+    std::memcpy(c->h_mq, q, sizeof(float) * 3 * (size_t)Q);
+    if (r) std::memcpy(c->h_mq + 3 * Q, r, sizeof(float) * (size_t)Q);
+    import_floats_kernel<<<ceil_div(3 * Q, 256), 256, 0, g_stream>>>(c->d_mq, (uint32_t)(3 * Q), c->d_q);
+    if (r) import_floats_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->d_mq + 3 * Q, (uint32_t)Q, c->d_r);
+    return PCT_OK;
+}
+
+// n uint32 results (and doubles, d_f64 != nullptr) back to the host by the transport stage_queries chose (DMA for buffers it did not
+// stage), and the wait for them
+int fetch_results(pct_cloud *c, bool mapped, const uint32_t *d_u32, uint32_t *u32, const double *d_f64, double *f64, int64_t n)
+{
+    if (!mapped) {
+        HIPCHK(hipMemcpyAsync(u32, d_u32, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g_stream));
+        if (d_f64) HIPCHK(hipMemcpyAsync(f64, d_f64, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return PCT_OK;
+    }
+    export_results_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(d_u32, d_f64, (uint32_t)n, c->d_mi, d_f64 ? c->d_md : nullptr, next_signal(c));
+    HIPCHK(hipGetLastError());
+    PCTCHK(express_wait(c));
+    std::memcpy(u32, c->h_mi, sizeof(uint32_t) * (size_t)n);
+    if (d_f64) std::memcpy(f64, c->h_md, sizeof(double) * (size_t)n);
+    return PCT_OK;
+}
+
+// the records of an express launch (c->h_xout, host-mapped) into the caller's arrays; a null array is not wanted
+void read_express_out(const pct_cloud *c, int64_t n, double *radius, uint32_t *idx, double *d2)
+{
+    for (int64_t i = 0; i < n; i++) {
+        if (radius) radius[i] = c->h_xout[i].radius;
+        if (idx) idx[i] = c->h_xout[i].idx;
+        if (d2) d2[i] = c->h_xout[i].d2;
+    }
+}
+
+// (re)capture p's graph: `enqueue` queues the batch on the library's stream, which is under capture meanwhile
+template <typename F>
+int plan_capture(pct_plan *p, F enqueue)
+{
+    pct_cloud *c = p->c;
+    if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
+    if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
+    HIPCHK(hipStreamSynchronize(g_stream));
+    hipError_t e = hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) return fail(PCT_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e));
+    c->capturing = true;
+    const int st = enqueue();
+    c->capturing = false;
+    e = hipStreamEndCapture(g_stream, &p->graph);
+    if (st != PCT_OK) return st;
+    if (e != hipSuccess || !p->graph) return fail(PCT_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+    e = hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) return fail(PCT_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+    p->generation = c->generation;
     return PCT_OK;
 }
 
@@ -1695,48 +1800,28 @@ int pct_nn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, uint32_
 {
     if (!c || Q < 0 || (Q > 0 && (!q || !idx || !d2))) return fail(PCT_ERR_INVALID, "bad nn_batch arguments");
     if (Q == 0) return PCT_OK;
-    if (Q <= kExpressMaxQ && c->ring_ready && c->count > 0 && (algo == PCT_ALGO_AUTO || algo == PCT_ALGO_GRID || algo == PCT_ALGO_RING)) {
-        // small batch on the rolling map: one launch, a block per query, arguments/results in mapped memory
-        for (int64_t i = 0; i < 3 * Q; i++) c->h_xin[i] = (double)q[i];
-        ring_batch_kernel<false><<<(int)Q, 256, 0, g_stream>>>(ring_view(c), InflateParams{}, nullptr, c->d_xin, (double)INFINITY, (uint32_t)c->index_base,
-                                                               nullptr, nullptr, nullptr, c->d_xout, next_signal(c));
-        HIPCHK(hipGetLastError());
-        PCTCHK(express_wait(c));
-        for (int64_t i = 0; i < Q; i++) { idx[i] = c->h_xout[i].idx; d2[i] = c->h_xout[i].d2; }
-        return PCT_OK;
-    }
-    if (Q <= kExpressMaxQ && c->has_grid && c->count > 0 && (algo == PCT_ALGO_AUTO || algo == PCT_ALGO_GRID)) {
+    Path path;
+    PCTCHK(resolve_algo(c, Op::NN, algo, Q, &path));
+    if (Q <= kExpressMaxQ && (path == Path::Table || path == Path::Grid)) {
         // small batch on an indexed cloud: one launch, a block per query, arguments/results in mapped memory
         for (int64_t i = 0; i < 3 * Q; i++) c->h_xin[i] = (double)q[i];
-        inflate_block_kernel<false><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, InflateParams{}, c->d_xin, (double)INFINITY,
-                                                                   (uint32_t)c->index_base, c->d_xout, next_signal(c));
+        if (path == Path::Table)
+            ring_batch_kernel<false><<<(int)Q, 256, 0, g_stream>>>(ring_view(c), InflateParams{}, nullptr, c->d_xin, (double)INFINITY, (uint32_t)c->index_base,
+                                                                   nullptr, nullptr, nullptr, c->d_xout, next_signal(c));
+        else
+            inflate_block_kernel<false><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, InflateParams{}, c->d_xin, (double)INFINITY,
+                                                                       (uint32_t)c->index_base, c->d_xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
-        for (int64_t i = 0; i < Q; i++) { idx[i] = c->h_xout[i].idx; d2[i] = c->h_xout[i].d2; }
+        read_express_out(c, Q, nullptr, idx, d2);
         return PCT_OK;
     }
     PCTCHK(pct_cloud_reserve_queries(c, Q));
-    if (Q <= kMappedMaxQ && mapped_io_on()) {
-        // queries imported from host-mapped memory by a kernel, results exported by a kernel, completion by polling:
-        // no DMA copy, no stream synchronise (C2's 4096-query batch: 0.63 -> 0.5x ms)
-        PCTCHK(ensure_mapped_io(c, Q));
-        std::memcpy(c->h_mq, q, sizeof(float) * 3 * (size_t)Q);
-        import_floats_kernel<<<ceil_div(3 * Q, 256), 256, 0, g_stream>>>(c->d_mq, (uint32_t)(3 * Q), c->d_q);
-        PCTCHK(nn_dev(c, algo, c->d_q, Q, c->d_idx, c->d_d2, g_stream));
-        export_results_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->d_idx, c->d_d2, (uint32_t)Q, c->d_mi, c->d_md, next_signal(c));
-        HIPCHK(hipGetLastError());
-        PCTCHK(express_wait(c));
-        std::memcpy(idx, c->h_mi, sizeof(uint32_t) * (size_t)Q);
-        std::memcpy(d2, c->h_md, sizeof(double) * (size_t)Q);
-        if (c->count == 0) return fail(PCT_ERR_EMPTY, "nearest-neighbour query against an empty cloud");
-        return PCT_OK;
-    }
-    HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(nn_dev(c, algo, c->d_q, Q, c->d_idx, c->d_d2, g_stream));
-    HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemcpyAsync(d2, c->d_d2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    if (c->count == 0) return fail(PCT_ERR_EMPTY, "nearest-neighbour query against an empty cloud");
+    bool mapped = false;
+    PCTCHK(stage_queries(c, q, nullptr, Q, &mapped));
+    PCTCHK(nn_run(c, path, c->d_q, Q, c->d_idx, c->d_d2, g_stream));
+    PCTCHK(fetch_results(c, mapped, c->d_idx, idx, c->d_d2, d2, Q));
+    if (path == Path::Empty) return fail(PCT_ERR_EMPTY, "nearest-neighbour query against an empty cloud");
     return PCT_OK;
 }
 
@@ -1770,15 +1855,10 @@ int pct_knn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, int32_
         c->knn_out_cap = rows;
     }
     HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
-    for (int attempt = 0;; attempt++) {
+    PCTCHK(ask_twice_after_overrun(c, [&] {
         PCTCHK(knn_dev(c, algo, c->d_q, Q, (int)k, c->d_knn_idx, c->d_knn_d2, g_stream));
-        HIPCHK(hipMemcpyAsync(idx, c->d_knn_idx, sizeof(uint32_t) * rows, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipMemcpyAsync(d2, c->d_knn_d2, sizeof(double) * rows, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        bool again = false;
-        PCTCHK(ring_overrun_repair(c, &again));          // the rolling-map index lost points (overflow-queue overrun): refiled, ask once more
-        if (!again || attempt) break;
-    }
+        return fetch_results(c, false, c->d_knn_idx, idx, c->d_knn_d2, d2, (int64_t)rows);
+    }));
     if (c->count == 0) return fail(PCT_ERR_EMPTY, "k-nearest-neighbour query against an empty cloud");
     return PCT_OK;
 }
@@ -1795,7 +1875,8 @@ int pct_radius_search_batch_dev(pct_cloud *c, int algo, const float *d_q, const 
     if (!c || Q < 0 || !d_offsets || cap < 0 || (Q > 0 && (!d_q || !d_r)) || (cap > 0 && !d_idx))
         return fail(PCT_ERR_INVALID, "bad radius_search_batch_dev arguments");
     if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
-    PCTCHK(rs_pick_algo(c, &algo));
+    Path path;
+    PCTCHK(resolve_algo(c, Op::RadiusSearch, algo, Q, &path));
     hipStream_t s = (hipStream_t)stream;
     c->rs_valid = false;                                     // the host form's result ends with the next search of either form
     if (Q == 0) {
@@ -1809,15 +1890,16 @@ int pct_radius_search_batch_dev(pct_cloud *c, int algo, const float *d_q, const 
     if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
     PCTCHK(rs_ensure_work(c));
     PCTCHK(order_after_mutations(c, s));
-    PCTCHK(rs_count_scan(c, algo, d_q, d_r, Q, reinterpret_cast<long long *>(d_offsets), s));
-    return rs_fill_sort(c, algo, d_q, d_r, Q, order, reinterpret_cast<long long *>(d_offsets), cap, d_idx, d_d2, s);
+    PCTCHK(rs_count_scan(c, path, d_q, d_r, Q, reinterpret_cast<long long *>(d_offsets), s));
+    return rs_fill_sort(c, path, d_q, d_r, Q, order, reinterpret_cast<long long *>(d_offsets), cap, d_idx, d_d2, s);
 }
 
 int pct_radius_search_batch(pct_cloud *c, int algo, const float *q, const float *r, int64_t Q, int order, int64_t *offsets, int64_t *total)
 {
     if (!c || Q < 0 || !offsets || !total || (Q > 0 && (!q || !r))) return fail(PCT_ERR_INVALID, "bad radius_search_batch arguments");
     if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
-    PCTCHK(rs_pick_algo(c, &algo));
+    Path path;
+    PCTCHK(resolve_algo(c, Op::RadiusSearch, algo, Q, &path));
     c->rs_valid = false;
     c->rs_total = 0;
     offsets[0] = 0;
@@ -1827,18 +1909,16 @@ int pct_radius_search_batch(pct_cloud *c, int algo, const float *q, const float 
     PCTCHK(rs_ensure_work(c));                               // before c->rs_off is handed on
     HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(c->d_r, r, sizeof(float) * Q, hipMemcpyHostToDevice, g_stream));
-    for (int attempt = 0;; attempt++) {
-        PCTCHK(rs_count_scan(c, algo, c->d_q, c->d_r, Q, c->rs_off, g_stream));
+    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {          // before the lists are sized: count and fill must see the same table
+        PCTCHK(rs_count_scan(c, path, c->d_q, c->d_r, Q, c->rs_off, g_stream));
         HIPCHK(hipMemcpyAsync(offsets, c->rs_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
         HIPCHK(hipStreamSynchronize(g_stream));              // the one host read: the total sizes the lists
-        bool again = false;
-        PCTCHK(ring_overrun_repair(c, &again));              // before the lists are sized: count and fill must see the same table
-        if (!again || attempt) break;
-    }
+        return PCT_OK;
+    }));
     *total = offsets[Q];
     if (*total > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "radius search lists %lld entries, more than 2^32 - 1", (long long)*total);
     PCTCHK(rs_ensure_lists(c, (size_t)*total));
-    PCTCHK(rs_fill_sort(c, algo, c->d_q, c->d_r, Q, order, c->rs_off, *total, c->rs_idx, c->rs_d2, g_stream));
+    PCTCHK(rs_fill_sort(c, path, c->d_q, c->d_r, Q, order, c->rs_off, *total, c->rs_idx, c->rs_d2, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     c->rs_total = *total;
     c->rs_valid = true;
@@ -1877,7 +1957,7 @@ int pct_nn_batch_q64_ties(pct_cloud *c, const double *q, int64_t Q, uint32_t *id
         nn_small_batch_kernel<<<(int)Q, 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_xin, (uint32_t)c->index_base, c->d_xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
-        for (int64_t i = 0; i < Q; i++) { idx[i] = c->h_xout[i].idx; d2[i] = c->h_xout[i].d2; }
+        read_express_out(c, Q, nullptr, idx, d2);
         return PCT_OK;
     }
     if (Q == 1 && c->count <= kSmallNNMax) {   // express: one one-block launch, query by value, result in mapped memory
@@ -1903,10 +1983,7 @@ int pct_nn_batch_q64_ties(pct_cloud *c, const double *q, int64_t Q, uint32_t *id
     } else {
         PCTCHK(nn_stream_q64(c, Q, c->d_idx, c->d_d2, g_stream));
     }
-    HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipMemcpyAsync(d2, c->d_d2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return PCT_OK;
+    return fetch_results(c, false, c->d_idx, idx, c->d_d2, d2, Q);
 }
 
 int pct_radius_count_batch_algo(pct_cloud *c, int algo, const float *q, const float *r, int64_t Q, uint32_t *count)
@@ -1914,35 +1991,12 @@ int pct_radius_count_batch_algo(pct_cloud *c, int algo, const float *q, const fl
     if (!c || Q < 0 || (Q > 0 && (!q || !r || !count))) return fail(PCT_ERR_INVALID, "bad radius_count arguments");
     if (Q == 0) return PCT_OK;
     PCTCHK(pct_cloud_reserve_queries(c, Q));
-    if (Q <= kMappedMaxQ && mapped_io_on()) {          // as pct_nn_batch_algo: kernels move the arguments and the counts, the host polls
-        PCTCHK(ensure_mapped_io(c, Q));
-        std::memcpy(c->h_mq, q, sizeof(float) * 3 * (size_t)Q);
-        std::memcpy(c->h_mq + 3 * Q, r, sizeof(float) * (size_t)Q);
-        import_floats_kernel<<<ceil_div(3 * Q, 256), 256, 0, g_stream>>>(c->d_mq, (uint32_t)(3 * Q), c->d_q);
-        import_floats_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->d_mq + 3 * Q, (uint32_t)Q, c->d_r);
-        for (int attempt = 0;; attempt++) {
-            PCTCHK(count_dev(c, algo, c->d_q, c->d_r, Q, c->d_count, g_stream));
-            export_results_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->d_count, nullptr, (uint32_t)Q, c->d_mi, nullptr, next_signal(c));
-            HIPCHK(hipGetLastError());
-            PCTCHK(express_wait(c));
-            bool again = false;
-            PCTCHK(ring_overrun_repair(c, &again));      // the rolling-map index lost points (overflow-queue overrun): refiled, ask once more
-            if (!again || attempt) break;
-        }
-        std::memcpy(count, c->h_mi, sizeof(uint32_t) * (size_t)Q);
-        return PCT_OK;
-    }
-    HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(c->d_r, r, sizeof(float) * Q, hipMemcpyHostToDevice, g_stream));
-    for (int attempt = 0;; attempt++) {
+    bool mapped = false;
+    PCTCHK(stage_queries(c, q, r, Q, &mapped));
+    return ask_twice_after_overrun(c, [&] {
         PCTCHK(count_dev(c, algo, c->d_q, c->d_r, Q, c->d_count, g_stream));
-        HIPCHK(hipMemcpyAsync(count, c->d_count, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        bool again = false;
-        PCTCHK(ring_overrun_repair(c, &again));
-        if (!again || attempt) break;
-    }
-    return PCT_OK;
+        return fetch_results(c, mapped, c->d_count, count, nullptr, nullptr, Q);
+    });
 }
 
 int pct_radius_count_batch(pct_cloud *c, const float *q, const float *r, int64_t Q, uint32_t *count)
@@ -2101,20 +2155,17 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
 {
     if (!c || !p || Q < 0 || (Q > 0 && (!pts || !radius))) return fail(PCT_ERR_INVALID, "bad inflate arguments");
     if (Q == 0) return PCT_OK;
+    // idx / d2 not wanted: the index searches may stop once everything unseen is beyond max_radius + search_margin
+    const double reach = p->max_radius + p->search_margin;
+    const double stop_d2 = (idx || d2) ? (double)INFINITY : reach * reach;
     if (c->ring_ready) {          // rolling map: a block per point over the bucket table; small batches through mapped memory
-        const double reach = p->max_radius + p->search_margin;
-        const double stop_d2 = (idx || d2) ? (double)INFINITY : reach * reach;
         if (Q <= kExpressMaxQ) {
             std::memcpy(c->h_xin, pts, sizeof(double) * 3 * Q);
             ring_batch_kernel<true><<<(int)Q, 256, 0, g_stream>>>(ring_view(c), to_dev(p), nullptr, c->d_xin, stop_d2, (uint32_t)c->index_base, nullptr, nullptr,
                                                                   nullptr, c->d_xout, next_signal(c));
             HIPCHK(hipGetLastError());
             PCTCHK(express_wait(c));
-            for (int64_t i = 0; i < Q; i++) {
-                radius[i] = c->h_xout[i].radius;
-                if (idx) idx[i] = c->h_xout[i].idx;
-                if (d2) d2[i] = c->h_xout[i].d2;
-            }
+            read_express_out(c, Q, radius, idx, d2);
             return PCT_OK;
         }
         PCTCHK(pct_cloud_reserve_queries(c, Q));
@@ -2130,17 +2181,10 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
     }
     if (Q <= kExpressMaxQ && c->has_grid && c->count > 0) {   // express: one fused launch (a block per point), arguments and results in mapped memory
         std::memcpy(c->h_xin, pts, sizeof(double) * 3 * Q);
-        // idx / d2 not wanted: the search may stop once everything unseen is beyond max_radius + search_margin
-        const double reach = p->max_radius + p->search_margin;
-        const double stop_d2 = (idx || d2) ? (double)INFINITY : reach * reach;
         inflate_block_kernel<true><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, to_dev(p), c->d_xin, stop_d2, (uint32_t)c->index_base, c->d_xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
-        for (int64_t i = 0; i < Q; i++) {
-            radius[i] = c->h_xout[i].radius;
-            if (idx) idx[i] = c->h_xout[i].idx;
-            if (d2) d2[i] = c->h_xout[i].d2;
-        }
+        read_express_out(c, Q, radius, idx, d2);
         return PCT_OK;
     }
     PCTCHK(pct_cloud_reserve_queries(c, Q));
@@ -2148,11 +2192,7 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
         std::memcpy(c->h_xin, pts, sizeof(double) * 3 * Q);
         PCTCHK(inflate_dev(c, p, Q, g_stream, c->d_xin, c->d_xout));
         HIPCHK(hipStreamSynchronize(g_stream));
-        for (int64_t i = 0; i < Q; i++) {
-            radius[i] = c->h_xout[i].radius;
-            if (idx) idx[i] = c->h_xout[i].idx;
-            if (d2) d2[i] = c->h_xout[i].d2;
-        }
+        read_express_out(c, Q, radius, idx, d2);
         return PCT_OK;
     }
     HIPCHK(hipMemcpyAsync(c->d_pts64, pts, sizeof(double) * 3 * Q, hipMemcpyHostToDevice, g_stream));
@@ -2378,25 +2418,14 @@ int pct_bezier_check_dev(pct_cloud *c, const pct_bezier_traj *traj, const pct_in
 static int plan_capture_nn(pct_plan *p)
 {
     pct_cloud *c = p->c;
-    if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
-    if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
     PCTCHK(pct_cloud_reserve_queries(c, p->Q));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    hipError_t e = hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return fail(PCT_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e));
-    c->capturing = true;
-    (void)hipMemcpyAsync(p->d_q, p->h_q, sizeof(float) * 3 * p->Q, hipMemcpyHostToDevice, g_stream);
-    const int st = nn_dev(c, p->algo, p->d_q, p->Q, p->d_idx, p->d_d2, g_stream);
-    (void)hipMemcpyAsync(p->h_idx, p->d_idx, sizeof(uint32_t) * p->Q, hipMemcpyDeviceToHost, g_stream);
-    (void)hipMemcpyAsync(p->h_d2, p->d_d2, sizeof(double) * p->Q, hipMemcpyDeviceToHost, g_stream);
-    c->capturing = false;
-    e = hipStreamEndCapture(g_stream, &p->graph);
-    if (st != PCT_OK) return st;
-    if (e != hipSuccess || !p->graph) return fail(PCT_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-    e = hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) return fail(PCT_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-    p->generation = c->generation;
-    return PCT_OK;
+    return plan_capture(p, [&] {
+        (void)hipMemcpyAsync(p->d_q, p->h_q, sizeof(float) * 3 * p->Q, hipMemcpyHostToDevice, g_stream);
+        const int st = nn_dev(c, p->algo, p->d_q, p->Q, p->d_idx, p->d_d2, g_stream);
+        (void)hipMemcpyAsync(p->h_idx, p->d_idx, sizeof(uint32_t) * p->Q, hipMemcpyDeviceToHost, g_stream);
+        (void)hipMemcpyAsync(p->h_d2, p->d_d2, sizeof(double) * p->Q, hipMemcpyDeviceToHost, g_stream);
+        return st;
+    });
 }
 
 int pct_plan_create_nn(pct_cloud *c, int algo, int64_t Q, pct_plan **out)
@@ -2674,17 +2703,10 @@ int pct_set_work_counters(pct_cloud *c, int enabled)
 int pct_last_work(pct_cloud *c, uint64_t *points_scanned, uint64_t *cells_scanned)
 {
     if (!c) return fail(PCT_ERR_INVALID, "null cloud");
-    WorkCounters w{};
-    if (c->host_work) {
-        w.points = c->host_points;
-    } else {
-        WorkCounters slots[kWorkSlots];
-        HIPCHK(hipStreamSynchronize(g_stream));
-        HIPCHK(hipMemcpy(slots, c->d_work, sizeof slots, hipMemcpyDeviceToHost));
-        for (const WorkCounters &k : slots) { w.points += k.points; w.cells += k.cells; }
-    }
-    if (points_scanned) *points_scanned = w.points;
-    if (cells_scanned) *cells_scanned = w.cells;
+    uint64_t w[3];
+    PCTCHK(pct_last_work_ex(c, w));
+    if (points_scanned) *points_scanned = w[0];
+    if (cells_scanned) *cells_scanned = w[1];
     return PCT_OK;
 }
 

@@ -192,6 +192,19 @@ int ring_overrun_repair(pct_cloud *c, bool *again)
     return PCT_OK;
 }
 
+// ask: queues a batch that may have searched the rolling-map index and waits for it.  If the index had lost points meanwhile
+// (overflow-queue overrun) it has been refiled by now and the batch is asked once more -- once: a second overrun is repaired, not re-asked.
+template <typename F>
+int ask_twice_after_overrun(pct_cloud *c, F ask)
+{
+    bool again = false;
+    PCTCHK(ask());
+    PCTCHK(ring_overrun_repair(c, &again));
+    if (!again) return PCT_OK;
+    PCTCHK(ask());
+    return ring_overrun_repair(c, &again);
+}
+
 // an append that returned before its insert kernel had finished (ring_append): wait for it and run its checks
 int ring_finish_pending(pct_cloud *c)
 {
@@ -292,20 +305,6 @@ RingView ring_view(const pct_cloud *c)
     V.ovf = c->ring_ovf;
     V.st = c->ring_st;
     return V;
-}
-
-// device batch over a ring-indexed cloud (block per query)
-int ring_nn_dev(pct_cloud *c, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
-{
-    begin_timing(c, s);
-    dom_begin(c, s);
-    ring_batch_kernel<false><<<(int)Q, 256, 0, s>>>(ring_view(c), InflateParams{}, d_q, nullptr, (double)INFINITY, (uint32_t)c->index_base, d_idx, d_d2,
-                                                    nullptr, nullptr, ExpressSignal{});
-    dom_end(c, s);
-    end_timing(c, s);
-    HIPCHK(hipGetLastError());
-    c->host_work = false;
-    return PCT_OK;
 }
 
 }  // namespace
@@ -495,8 +494,7 @@ int replan_fill(ReplanCtx *x, const pct_inflate_params *p, const double *nodes, 
 // wait for the batch: the finish kernel's sequence word in host-mapped memory (a stream sync costs ~20 us more), or the stream
 int replan_wait(ReplanCtx *x, hipStream_t s)
 {
-    static const bool poll = [] { const char *e = std::getenv("PCT_POLL_RESULTS"); return e ? std::atoi(e) != 0 : true; }();
-    if (!x->copies && poll) {
+    if (!x->copies && poll_results()) {
         const volatile uint32_t *seq = &x->h_sum->seq;
         for (long spins = 0; spins < 40000000l; spins++) {
             if (*seq == x->seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); return PCT_OK; }
@@ -560,14 +558,11 @@ int replan_direct(pct_cloud *c, const pct_inflate_params *p, const double *nodes
         PCTCHK(replan_ctx_create((int)std::max<int64_t>(n_nodes, 64), std::max(max_samples, 128), std::max(need_seg, 4), false, &c->rp));
     }
     int64_t ntot = 0;
-    for (int attempt = 0;; attempt++) {
+    PCTCHK(ask_twice_after_overrun(c, [&] {
         PCTCHK(replan_fill(c->rp, p, nodes, n_nodes, traj, t_start, stop_time, dt, want_nn, with_ctrl, &ntot));
         if (const int st = replan_enqueue(c, c->rp, g_stream)) { c->rp->seq--; return st; }     // nothing ran: the slot is filled again
-        PCTCHK(replan_wait(c->rp, g_stream));
-        bool again = false;
-        PCTCHK(ring_overrun_repair(c, &again));
-        if (!again || attempt) break;
-    }
+        return replan_wait(c->rp, g_stream);
+    }));
     replan_read(c->rp, ntot, o, max_samples);
     return PCT_OK;
 }
@@ -724,23 +719,8 @@ int pct_ctrl_points_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_i
 // ---- the captured replan batch ---------------------------------------------------------------------------------------------
 static int plan_capture_replan(pct_plan *p)
 {
-    pct_cloud *c = p->c;
-    if (p->exec) { (void)hipGraphExecDestroy(p->exec); p->exec = nullptr; }
-    if (p->graph) { (void)hipGraphDestroy(p->graph); p->graph = nullptr; }
-    if (!cloud_indexed(c)) return fail(PCT_ERR_INVALID, "the replan plan needs an index on the cloud (pct_cloud_ring_index or pct_cloud_build_grid)");
-    HIPCHK(hipStreamSynchronize(g_stream));
-    hipError_t e = hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return fail(PCT_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e));
-    c->capturing = true;
-    const int st = replan_enqueue(c, p->rx, g_stream);
-    c->capturing = false;
-    e = hipStreamEndCapture(g_stream, &p->graph);
-    if (st != PCT_OK) return st;
-    if (e != hipSuccess || !p->graph) return fail(PCT_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-    e = hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) return fail(PCT_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-    p->generation = c->generation;
-    return PCT_OK;
+    if (!cloud_indexed(p->c)) return fail(PCT_ERR_INVALID, "the replan plan needs an index on the cloud (pct_cloud_ring_index or pct_cloud_build_grid)");
+    return plan_capture(p, [&] { return replan_enqueue(p->c, p->rx, g_stream); });
 }
 
 int pct_plan_create_replan(pct_cloud *c, int32_t max_nodes, int32_t max_samples, int32_t max_segments, pct_plan **out)
@@ -769,7 +749,7 @@ int pct_plan_replan_run(pct_plan *p, const pct_inflate_params *prm, const double
     pct_cloud *c = p->c;
     if (p->generation != c->generation) PCTCHK(plan_capture_replan(p));       // the cloud's index was rebuilt / replaced: capture again
     int64_t ntot = 0;
-    for (int attempt = 0;; attempt++) {
+    return ask_twice_after_overrun(c, [&]() -> int {        // the index lost points (overflow-queue overrun): refiled, asked once more
         const auto t0 = std::chrono::steady_clock::now();
         PCTCHK(replan_fill(p->rx, prm, nodes, n_nodes, traj, t_start, stop_time, dt, want_nn, 1, &ntot));
         const auto t1 = std::chrono::steady_clock::now();
@@ -784,11 +764,8 @@ int pct_plan_replan_run(pct_plan *p, const pct_inflate_params *prm, const double
         const auto t4 = std::chrono::steady_clock::now();
         const auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         p->run_us[0] = us(t0, t1); p->run_us[1] = us(t1, t2); p->run_us[2] = us(t2, t3); p->run_us[3] = us(t3, t4);
-        bool again = false;
-        PCTCHK(ring_overrun_repair(c, &again));          // the index lost points (overflow-queue overrun): refiled, ask once more
-        if (!again || attempt) break;
-    }
-    return PCT_OK;
+        return PCT_OK;
+    });
 }
 
 /* host wall time of the last pct_plan_replan_run, microseconds: argument fill, hipGraphLaunch, wait for the results, read-out */
