@@ -50,8 +50,9 @@ int kdx_set_node_aux(struct kdtree *tree, int32_t node, const double aux[4]);
 /* K RRT* iterations' queries in ONE launch against the tree as it is now (pct_rrt_expand_batch): for sample i the nearest
  * node (as kd_nearestf on the fp32-narrowed sample), the steered centre, its inflation radius against `obstacles`, and the
  * candidate list kdx_range_from_candidates() needs for kd_nearest_rangef(centre, 2 * float(radius)).
- * Returns 0 on success, -1 when the fused path cannot serve this tree (more than 65536 nodes, obstacle cloud without its
- * cell index): the caller then issues the three queries separately. */
+ * `obstacles` may carry either index, the cell index or the rolling-map one.
+ * Returns 0 on success, -1 when the fused path cannot serve this tree (more than 65536 nodes, a non-empty obstacle cloud with
+ * no index at all): the caller then issues the three queries separately. */
 int kdx_expand_batch(struct kdtree *tree, pct_cloud *obstacles, const pct_inflate_params *prm, const double *samples, int k,
                      int cap_per_query, pct_expand_result *out, uint32_t *ids);
 

@@ -28,6 +28,13 @@ int pct_corridor_reset(pct_corridor *c);
  * that are replayed in order and give the identical corridor */
 int pct_corridor_set_speculation(pct_corridor *c, int k);
 int pct_corridor_set_input(pct_corridor *c, const void *points, int64_t n, int64_t stride_bytes, int build_index);
+/* Rolling map (config C5): the obstacle cloud becomes a sliding window of cloud_capacity points over the rolling-map index
+ * (pct_cloud_ring_index: cell_size <= 0 = chosen from the first data; extent may be NULL).  Call once before the first frame; a
+ * sensor tick is then pct_corridor_append_input (the newest frame overwrites the oldest points, the index is updated in place) ->
+ * evaluate -> refine, where the reference's is set_input of the whole cloud.  pct_corridor_set_input still replaces the window.
+ * stride_bytes = 16 for pcl::PointXYZ records, 12 for packed xyz. */
+int pct_corridor_enable_rolling(pct_corridor *c, float cell_size, const float extent[3]);
+int pct_corridor_append_input(pct_corridor *c, const void *points, int64_t n, int64_t stride_bytes);
 int pct_corridor_set_pt(pct_corridor *c, const double start[3], const double end[3], double xl, double xh, double yl, double yh,
                         double zl, double zh, double local_range, int max_iter, double sample_portion, double goal_portion);
 int pct_corridor_set_start_pt(pct_corridor *c, const double start[3], const double end[3]);
@@ -45,8 +52,8 @@ int pct_corridor_check_traj_pt_col(pct_corridor *c, const double p[3], int *coll
 int pct_corridor_get_path(pct_corridor *c, double *path, double *radius, int64_t cap, int64_t *n_out);
 int pct_corridor_status(pct_corridor *c, int *path_exists, int *global_navi, int64_t *n_nodes, uint64_t *inflation_queries);
 int pct_corridor_speculation_stats(pct_corridor *c, uint64_t *replayed_from_batch, uint64_t *fell_back);
-/* on (default): one fused launch per speculative batch (nearest node -> steer -> inflation -> neighbourhood);
- * off: the same three stages as three batched launches.  The corridor does not depend on it. */
+/* on (default): one fused launch per speculative batch (nearest node -> steer -> inflation -> neighbourhood), over the cell index
+ * of a static cloud or the rolling-map index; off: the same three stages as three batched launches.  The corridor does not depend on it. */
 int pct_corridor_set_fused_expansion(pct_corridor *c, int on);
 int pct_corridor_expansion_launches(pct_corridor *c, uint64_t *launches);
 /* GPU round trips treeRepair (corridor_finder.cpp:938-1021) has made: two per pass -- one launch for every failed node's neighbourhood,

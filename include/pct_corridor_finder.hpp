@@ -205,6 +205,13 @@ public:
     {
         map_.setInput(points, n, stride_bytes, build_index);
     }
+    // Rolling map (config C5): the obstacle cloud becomes a sliding window of the constructor's cloud_capacity points over the
+    // rolling-map index (ObstacleMap::enableRollingIndex; cell_size 0 = chosen from the first data, extent = the window's size per
+    // axis when known, e.g. twice the sensing range).  Call once, before the first frame.  The planner's tick is then
+    // appendInput(frame) -> SafeRegionEvaluate -> SafeRegionRefine where the reference's is setInput(whole cloud) -> ... :
+    // the newest frame overwrites the oldest points and the index is updated in place.  setInput still replaces the whole window.
+    void enableRollingMap(float cell_size = 0.0f, const float *extent = nullptr) { map_.enableRollingIndex(cell_size, extent); }
+    void appendInput(const void *points, int64_t n, int64_t stride_bytes = 16) { map_.appendInput(points, n, stride_bytes); }
 
     // ---- queries ----
     bool checkTrajPtCol(const Vec3 &pt) { return clearance(pt) < 0.0; }                     // :412-416
@@ -843,7 +850,7 @@ private:
             const int m = K - pos;
             for (int i = 0; i < m; i++) { const Vec3 &s = la.sample[(size_t)(pos + i)]; flat[3 * (size_t)i] = s.x; flat[3 * (size_t)i + 1] = s.y; flat[3 * (size_t)i + 2] = s.z; }
             if (kdx_expand_batch(kd_, map_.handle(), &map_.params(), flat.data(), m, cap, res.data(), ids.data()) != 0) {
-                fused_ = false;                                       // e.g. obstacle cloud without its cell index: staged path from here on
+                fused_ = false;                                       // obstacle cloud with no index at all (neither cells nor rolling map): staged path from here on
                 rng_.setState(la.rng_before[(size_t)pos]);
                 return pos > 0 ? pos : grow_staged(K, refine);
             }

@@ -172,7 +172,7 @@ int pct_cloud_append_aos(pct_cloud *c, const void *pts, int64_t n, int64_t strid
  * rebuilds its search tree per frame -- safeRegionRrtStar::setInput, Planner/src/corridor_finder.cpp:93-99 called from
  * rcvPointCloudCallBack, Planner/src/sim_planning_demo.cpp:159-167).  After this call pct_cloud_append_aos no longer drops an
  * index: it retires the points it overwrites from a world-anchored bucket table and files the new frame, in place, and
- * pct_nn_batch / pct_inflate_batch / pct_bezier_check / pct_ctrl_points_check / the replan plan search that table (ALGO_AUTO,
+ * pct_nn_batch / pct_inflate_batch / pct_bezier_check / pct_ctrl_points_check / pct_rrt_expand_batch / the replan plan search that table (ALGO_AUTO,
  * ALGO_RING and, for these nearest-point calls, ALGO_GRID), and so do pct_knn_batch*, pct_radius_count_batch* and
  * pct_radius_search_batch* (ALGO_AUTO and ALGO_RING; ALGO_GRID is PCT_ERR_INVALID there, as on any cloud without a grid).
  * ALGO_STREAM still scans the whole window.  Results are the same as on any other cloud: exact fp64
@@ -296,7 +296,14 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
  * centre.  `nodes` is the small (host-mapped) cloud of node coordinates; pct_cloud_small_aux() hands out its per-node
  * planner data, 4 doubles per node {x, y, z, radius} (the node's fp64 centre and float radius, as the steer step reads
  * them), which the caller keeps current with plain stores.  ids[k*cap_per_query ...] = candidate node numbers (unordered);
- * out[k].count < 0 means -(count) hits of which only part were stored.  near_idx = -1 for an empty node set (centre = sample). */
+ * out[k].count < 0 means -(count) hits of which only part were stored.  near_idx = -1 for an empty node set (centre = sample).
+ * `obstacles` needs an index, either kind: the cell index (pct_cloud_build_grid) or the rolling-map index (pct_cloud_ring_index),
+ * whose bucket table the inflation then searches -- same arithmetic, same radii.  A non-empty cloud with neither is
+ * PCT_ERR_INVALID (the staged queries pct_nn_batch / pct_inflate_batch / pct_radius_* still answer on it).  An empty cloud -- a
+ * rolling window nothing has been appended to, with or without its table, included -- gives every centre
+ * the radius max_radius - search_margin (corridor_finder.cpp:115-116).  An append still in flight on `obstacles` is finished first and
+ * the answer sees its frame; this is a host form in the sense of the overflow-queue overrun paragraph at the top of this file.
+ * At most 1024 samples per call. */
 typedef struct pct_expand_result { double center[3]; double radius; int32_t near_idx; int32_t count; } pct_expand_result;
 int pct_cloud_small_aux(pct_cloud *nodes, double **host_aux);
 int pct_rrt_expand_batch(pct_cloud *nodes, pct_cloud *obstacles, const pct_inflate_params *p, const double *samples, int64_t K,

@@ -34,6 +34,8 @@ def lib():
         L.pct_corridor_expansion_launches.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.pct_corridor_repair_batches.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.pct_corridor_set_input.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int]
+        L.pct_corridor_enable_rolling.argtypes = [vp, C.c_float, vp]
+        L.pct_corridor_append_input.argtypes = [vp, vp, C.c_int64, C.c_int64]
         L.pct_corridor_set_pt.argtypes = [vp, d3, d3] + [C.c_double] * 7 + [C.c_int, C.c_double, C.c_double]
         L.pct_corridor_set_start_pt.argtypes = [vp, d3, d3]
         L.pct_corridor_reset_root.argtypes = [vp, d3]
@@ -101,6 +103,17 @@ class SafeRegionRrtStar:
     def setInput(self, points, build_index=True):
         a = np.ascontiguousarray(points, np.float32)
         self._chk(self.L.pct_corridor_set_input(self.h, a.ctypes.data_as(C.c_void_p), len(a), a.shape[1] * 4, int(build_index)))
+
+    def enableRollingMap(self, cell_size: float = 0.0, extent=None):
+        """rolling map (config C5): the cloud becomes a sliding window of cloud_capacity points over the rolling-map index; call once,
+        before the first frame.  extent = the window's size per axis when known (the table is then allocated at once)"""
+        ext = None if extent is None else np.ascontiguousarray(extent, np.float32).reshape(3)
+        self._chk(self.L.pct_corridor_enable_rolling(self.h, float(cell_size), None if ext is None else ext.ctypes.data_as(C.c_void_p)))
+
+    def appendInput(self, points):
+        """append one sensor frame: the newest points overwrite the oldest, the index is updated in place"""
+        a = np.ascontiguousarray(points, np.float32)
+        self._chk(self.L.pct_corridor_append_input(self.h, a.ctypes.data_as(C.c_void_p), len(a), a.shape[1] * 4))
 
     def setPt(self, start, end, xl, xh, yl, yh, zl, zh, local_range, max_iter, sample_portion, goal_portion):
         self._chk(self.L.pct_corridor_set_pt(self.h, _d3(start), _d3(end), xl, xh, yl, yh, zl, zh, local_range, int(max_iter),

@@ -66,6 +66,14 @@ int pct_corridor_set_input(pct_corridor *c, const void *points, int64_t n, int64
 {
     return guarded([&] { c->impl->setInput(points, n, stride_bytes, build_index != 0); });
 }
+int pct_corridor_enable_rolling(pct_corridor *c, float cell_size, const float extent[3])
+{
+    return guarded([&] { c->impl->enableRollingMap(cell_size, extent); });
+}
+int pct_corridor_append_input(pct_corridor *c, const void *points, int64_t n, int64_t stride_bytes)
+{
+    return guarded([&] { c->impl->appendInput(points, n, stride_bytes); });
+}
 int pct_corridor_set_pt(pct_corridor *c, const double start[3], const double end[3], double xl, double xh, double yl, double yh,
                         double zl, double zh, double local_range, int max_iter, double sample_portion, double goal_portion)
 {

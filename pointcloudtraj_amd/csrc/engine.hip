@@ -2221,20 +2221,38 @@ int pct_rrt_expand_batch(pct_cloud *nodes, pct_cloud *obstacles, const pct_infla
     if (K == 0) return PCT_OK;
     if (K > kExpressMaxQ) return fail(PCT_ERR_INVALID, "at most %d samples per expansion launch", kExpressMaxQ);
     if (!nodes->host_mapped || (nodes->count > 0 && !nodes->h_aux)) return fail(PCT_ERR_INVALID, "the node set must be a small cloud with per-node planner data (pct_cloud_small_aux)");
-    if (obstacles->count > 0 && !obstacles->has_grid) return fail(PCT_ERR_INVALID, "the obstacle cloud needs its cell index (pct_cloud_build_grid)");
+    // Rolling map: an append that returned with its insert kernel still queued is finished first -- its status words are read and the
+    // bookkeeping they ask for (larger buckets, a re-sized table: new pointers, a new generation) happens BEFORE the view below is
+    // taken.  The completion word this call waits on is the node cloud's; it says nothing about the obstacle cloud's append.
+    PCTCHK(ring_finish_pending(obstacles));
+    const bool ring = obstacles->ring_ready;
+    if (!ring && obstacles->count > 0 && !obstacles->has_grid)
+        return fail(PCT_ERR_INVALID, "the obstacle cloud has no index (pct_cloud_build_grid or pct_cloud_ring_index): the fused step searches one; "
+                                     "the staged queries (pct_nn_batch, pct_inflate_batch, pct_radius_*) answer without");
     if (!nodes->h_eout) PCTCHK(mapped_alloc(&nodes->h_eout, &nodes->d_eout, (size_t)kExpressMaxQ));
     const uint32_t cap = (uint32_t)std::min<int64_t>(cap_per_query, kExpressIdsCap / K);
     std::memcpy(nodes->h_xin, samples, sizeof(double) * 3 * K);
     const double reach = p->max_radius + p->search_margin;       // only the radius is wanted: stop once everything unseen is beyond it
-    rrt_expand_kernel<<<(int)K, 256, 0, g_stream>>>(nodes->x, nodes->y, nodes->z, (uint32_t)nodes->count, nodes->d_aux, nodes->d_xin,
-                                                    obstacles->G, obstacles->sorted, obstacles->cell_start,
-                                                    obstacles->count == 0 ? 1 : 0, to_dev(p), reach * reach, nodes->d_xids, cap, nodes->d_eout,
-                                                    K <= 8 ? next_signal(nodes) : ExpressSignal{});
-    HIPCHK(hipGetLastError());
-    // one or a few samples: the completion word (1500 one-sample iterations 37 -> 32 ms); speculative batches of 16-256 blocks:
-    // a system-scope fence per block costs more than the stream synchronise saves (2.85 vs 2.60 ms per 1500 iterations at K = 64)
-    if (K <= 8) PCTCHK(express_wait(nodes));
-    else HIPCHK(hipStreamSynchronize(g_stream));
+    // a rolling window that holds nothing (table sized from an extent, nothing appended) is empty by the device's own count; a ring
+    // index that has no table yet (no extent, no data) has ring_ready == false and count == 0: the static form's empty rule
+    PCTCHK(ask_twice_after_overrun(obstacles, [&]() -> int {     // the table lost points (overflow-queue overrun): refiled, asked once more
+        const ExpressSignal sig = K <= 8 ? next_signal(nodes) : ExpressSignal{};
+        if (ring)
+            rrt_expand_kernel<true><<<(int)K, 256, 0, g_stream>>>(nodes->x, nodes->y, nodes->z, (uint32_t)nodes->count, nodes->d_aux, nodes->d_xin,
+                                                                  ring_view(obstacles), GridDesc{}, nullptr, nullptr, 0, to_dev(p), reach * reach,
+                                                                  nodes->d_xids, cap, nodes->d_eout, sig);
+        else
+            rrt_expand_kernel<false><<<(int)K, 256, 0, g_stream>>>(nodes->x, nodes->y, nodes->z, (uint32_t)nodes->count, nodes->d_aux, nodes->d_xin,
+                                                                   RingView{}, obstacles->G, obstacles->sorted, obstacles->cell_start,
+                                                                   obstacles->count == 0 ? 1 : 0, to_dev(p), reach * reach, nodes->d_xids, cap,
+                                                                   nodes->d_eout, sig);
+        HIPCHK(hipGetLastError());
+        // one or a few samples: the completion word (1500 one-sample iterations 37 -> 32 ms); speculative batches of 16-256 blocks:
+        // a system-scope fence per block costs more than the stream synchronise saves (2.85 vs 2.60 ms per 1500 iterations at K = 64)
+        if (K <= 8) PCTCHK(express_wait(nodes));
+        else HIPCHK(hipStreamSynchronize(g_stream));
+        return PCT_OK;
+    }));
     for (int64_t k = 0; k < K; k++) {
         const ExpandOut &e = nodes->h_eout[k];
         out[k].center[0] = e.cx; out[k].center[1] = e.cy; out[k].center[2] = e.cz;

@@ -2185,95 +2185,7 @@ __global__ __launch_bounds__(256) void inflate_block_kernel(GridDesc G, const fl
 // (fp64 coordinates, float radius widened), in host-mapped memory like the node coordinates themselves.
 struct ExpandOut { double cx, cy, cz, radius; uint32_t near_idx, count; };
 
-__global__ __launch_bounds__(256) void rrt_expand_kernel(const float *__restrict__ nx, const float *__restrict__ ny,
-                                                         const float *__restrict__ nz, uint32_t n_nodes,
-                                                         const double *__restrict__ node_aux, const double *__restrict__ samples,
-                                                         GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
-                                                         int obstacles_empty, InflateParams P, double stop_d2,
-                                                         uint32_t *__restrict__ ids, uint32_t cap_per_query, ExpandOut *__restrict__ out,
-                                                         ExpressSignal sig)
-{
-    __shared__ double s_d[4];
-    __shared__ uint32_t s_i[4];
-    __shared__ uint32_t s_n;
-    __shared__ uint32_t s_ids[256];                // the neighbourhood is gathered here and handed to the host by ONE wave (below)
-    const uint32_t slot = blockIdx.x;
-    const double sx = samples[3 * slot], sy = samples[3 * slot + 1], sz = samples[3 * slot + 2];
-    if (threadIdx.x == 0) s_n = 0;
-    // ---- A: nearest node -------------------------------------------------------------------------------------------
-    double bd = __builtin_huge_val();
-    uint32_t near = kNoIndex;
-    {
-        const double qx = (double)(float)sx, qy = (double)(float)sy, qz = (double)(float)sz;
-        for (uint32_t i = threadIdx.x; i < n_nodes; i += 256) {
-            const double d2 = dist2((double)nx[i], (double)ny[i], (double)nz[i], qx, qy, qz);
-            if (d2 < bd) { bd = d2; near = i; }
-        }
-        block_argmin256(bd, near, s_d, s_i);
-    }
-    // ---- B: steer + inflate (every thread computes the same centre) ------------------------------------------------
-    double cx = sx, cy = sy, cz = sz;
-    if (near != kNoIndex) {
-        const double ax = node_aux[4 * near], ay = node_aux[4 * near + 1], az = node_aux[4 * near + 2], ar = node_aux[4 * near + 3];
-        const double dx = ax - sx, dy = ay - sy, dz = az - sz;
-        const double dis = sqrt(dx * dx + dy * dy + dz * dz);                    // getDis(nearest->coord, pt_sample)
-        if (dis > ar) {                                                          // :392-400
-            const double steer_dis = ar / dis;
-            cx = ax + (sx - ax) * steer_dis;
-            cy = ay + (sy - ay) * steer_dis;
-            cz = az + (sz - az) * steer_dis;
-        }
-    }
-    double radius;
-    {
-        const double dx = cx - P.sx, dy = cy - P.sy, dz = cz - P.sz;
-        if (obstacles_empty || sqrt(dx * dx + dy * dy + dz * dz) > P.sample_range + P.max_radius) {
-            radius = P.max_radius - P.search_margin;                             // :115-116
-        } else {
-            double od;
-            uint32_t oi;
-            block_nn_search(G, pts, cell_start, cx, cy, cz, stop_d2, s_d, s_i, od, oi);
-            const double rr = sqrt(od) - P.search_margin;
-            radius = rr < P.max_radius ? rr : P.max_radius;
-        }
-    }
-    // ---- C: neighbourhood candidates ---------------------------------------------------------------------------------
-    {
-        const float rf = fmaxf((float)radius, 0.0f) * 2.0f;                      // range = radius * 2 on the float member (:462)
-        const double r = (double)rf, r2 = r * r;
-        const double qx = (double)(float)cx, qy = (double)(float)cy, qz = (double)(float)cz;
-        __syncthreads();                                                         // s_n = 0 is visible
-        for (uint32_t i = threadIdx.x; i < n_nodes; i += 256)
-            if (dist2((double)nx[i], (double)ny[i], (double)nz[i], qx, qy, qz) <= r2) {
-                const uint32_t pos = atomicAdd(&s_n, 1u);
-                if (pos < 256u) s_ids[pos] = i;
-                else if (pos < cap_per_query) ids[(size_t)slot * cap_per_query + pos] = i;     // a neighbourhood beyond 256 nodes: straight to the host
-            }
-        __syncthreads();
-    }
-    const uint32_t n_hits = s_n;
-    if (n_hits > 256u) {                           // rare: many threads stored host-visible data, all of them fence
-        for (uint32_t k = threadIdx.x; k < min(256u, cap_per_query); k += 256) ids[(size_t)slot * cap_per_query + k] = s_ids[k];
-        if (threadIdx.x == 0) {
-            out[slot].cx = cx; out[slot].cy = cy; out[slot].cz = cz; out[slot].radius = radius;
-            out[slot].near_idx = near;
-            out[slot].count = n_hits;
-        }
-        express_done_block(sig);
-        return;
-    }
-    // the usual case: wave 0 alone writes everything the host reads, so one wave fences instead of four
-    if (threadIdx.x < 64) {
-        for (uint32_t k = threadIdx.x; k < min(n_hits, cap_per_query); k += 64) ids[(size_t)slot * cap_per_query + k] = s_ids[k];
-        if (threadIdx.x == 0) {
-            out[slot].cx = cx; out[slot].cy = cy; out[slot].cz = cz; out[slot].radius = radius;
-            out[slot].near_idx = near;
-            out[slot].count = n_hits;
-        }
-        if (sig.seq) __threadfence_system();         // the wave's stores (ids by up to 64 lanes) before lane 0 takes the ticket
-        if (threadIdx.x == 0) express_done(sig);
-    }
-}
+// (the kernel itself, rrt_expand_kernel<RING>, is in ring.hpp: it searches either index kind)
 
 constexpr int kMaxBezierOrder = 12;
 

@@ -349,6 +349,106 @@ __device__ __forceinline__ void ring_block_nn_search(const RingView &V, double p
     }
 }
 
+// ---- the fused RRT* expansion step over either index kind ------------------------------------------------------------------
+// One RRT* iteration's three dependent queries in ONE launch, a 256-thread block per sample (stages A-C and ExpandOut: kernels.hpp,
+// above block_nn_search's users).  RING = the obstacle cloud is a rolling map: stage B searches the bucket table (V) with
+// ring_block_nn_search -- same fp32-narrowed centre, same fp64 ((dx*dx + dy*dy) + dz*dz), same stop_d2 -- where the static form
+// searches the cell-sorted index (G, pts, cell_start); the arguments of the other kind are ignored.  Stages A and C and the
+// host-visible stores with their fences do not depend on RING.
+template <bool RING>
+__global__ __launch_bounds__(256) void rrt_expand_kernel(const float *__restrict__ nx, const float *__restrict__ ny,
+                                                         const float *__restrict__ nz, uint32_t n_nodes,
+                                                         const double *__restrict__ node_aux, const double *__restrict__ samples,
+                                                         RingView V, GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
+                                                         int static_empty, InflateParams P, double stop_d2,
+                                                         uint32_t *__restrict__ ids, uint32_t cap_per_query, ExpandOut *__restrict__ out,
+                                                         ExpressSignal sig)
+{
+    __shared__ double s_d[4];
+    __shared__ uint32_t s_i[4];
+    __shared__ uint32_t s_n;
+    __shared__ uint32_t s_ids[256];                // the neighbourhood is gathered here and handed to the host by ONE wave (below)
+    const uint32_t slot = blockIdx.x;
+    const double sx = samples[3 * slot], sy = samples[3 * slot + 1], sz = samples[3 * slot + 2];
+    if (threadIdx.x == 0) s_n = 0;
+    // ---- A: nearest node -------------------------------------------------------------------------------------------
+    double bd = __builtin_huge_val();
+    uint32_t near = kNoIndex;
+    {
+        const double qx = (double)(float)sx, qy = (double)(float)sy, qz = (double)(float)sz;
+        for (uint32_t i = threadIdx.x; i < n_nodes; i += 256) {
+            const double d2 = dist2((double)nx[i], (double)ny[i], (double)nz[i], qx, qy, qz);
+            if (d2 < bd) { bd = d2; near = i; }
+        }
+        block_argmin256(bd, near, s_d, s_i);
+    }
+    // ---- B: steer + inflate (every thread computes the same centre) ------------------------------------------------
+    double cx = sx, cy = sy, cz = sz;
+    if (near != kNoIndex) {
+        const double ax = node_aux[4 * near], ay = node_aux[4 * near + 1], az = node_aux[4 * near + 2], ar = node_aux[4 * near + 3];
+        const double dx = ax - sx, dy = ay - sy, dz = az - sz;
+        const double dis = sqrt(dx * dx + dy * dy + dz * dz);                    // getDis(nearest->coord, pt_sample)
+        if (dis > ar) {                                                          // :392-400
+            const double steer_dis = ar / dis;
+            cx = ax + (sx - ax) * steer_dis;
+            cy = ay + (sy - ay) * steer_dis;
+            cz = az + (sz - az) * steer_dis;
+        }
+    }
+    double radius;
+    {
+        const double dx = cx - P.sx, dy = cy - P.sy, dz = cz - P.sz;
+        // a rolling window's size lives on the device (the append kernels publish it): an empty window is an empty cloud
+        const bool obstacles_empty = RING ? V.st->count == 0 : static_empty != 0;
+        if (obstacles_empty || sqrt(dx * dx + dy * dy + dz * dz) > P.sample_range + P.max_radius) {
+            radius = P.max_radius - P.search_margin;                             // :115-116
+        } else {
+            double od;
+            uint32_t oi;
+            if (RING) ring_block_nn_search(V, cx, cy, cz, stop_d2, s_d, s_i, od, oi);
+            else block_nn_search(G, pts, cell_start, cx, cy, cz, stop_d2, s_d, s_i, od, oi);
+            const double rr = sqrt(od) - P.search_margin;
+            radius = rr < P.max_radius ? rr : P.max_radius;
+        }
+    }
+    // ---- C: neighbourhood candidates ---------------------------------------------------------------------------------
+    {
+        const float rf = fmaxf((float)radius, 0.0f) * 2.0f;                      // range = radius * 2 on the float member (:462)
+        const double r = (double)rf, r2 = r * r;
+        const double qx = (double)(float)cx, qy = (double)(float)cy, qz = (double)(float)cz;
+        __syncthreads();                                                         // s_n = 0 is visible
+        for (uint32_t i = threadIdx.x; i < n_nodes; i += 256)
+            if (dist2((double)nx[i], (double)ny[i], (double)nz[i], qx, qy, qz) <= r2) {
+                const uint32_t pos = atomicAdd(&s_n, 1u);
+                if (pos < 256u) s_ids[pos] = i;
+                else if (pos < cap_per_query) ids[(size_t)slot * cap_per_query + pos] = i;     // a neighbourhood beyond 256 nodes: straight to the host
+            }
+        __syncthreads();
+    }
+    const uint32_t n_hits = s_n;
+    if (n_hits > 256u) {                           // rare: many threads stored host-visible data, all of them fence
+        for (uint32_t k = threadIdx.x; k < min(256u, cap_per_query); k += 256) ids[(size_t)slot * cap_per_query + k] = s_ids[k];
+        if (threadIdx.x == 0) {
+            out[slot].cx = cx; out[slot].cy = cy; out[slot].cz = cz; out[slot].radius = radius;
+            out[slot].near_idx = near;
+            out[slot].count = n_hits;
+        }
+        express_done_block(sig);
+        return;
+    }
+    // the usual case: wave 0 alone writes everything the host reads, so one wave fences instead of four
+    if (threadIdx.x < 64) {
+        for (uint32_t k = threadIdx.x; k < min(n_hits, cap_per_query); k += 64) ids[(size_t)slot * cap_per_query + k] = s_ids[k];
+        if (threadIdx.x == 0) {
+            out[slot].cx = cx; out[slot].cy = cy; out[slot].cz = cz; out[slot].radius = radius;
+            out[slot].near_idx = near;
+            out[slot].count = n_hits;
+        }
+        if (sig.seq) __threadfence_system();         // the wave's stores (ids by up to 64 lanes) before lane 0 takes the ticket
+        if (threadIdx.x == 0) express_done(sig);
+    }
+}
+
 // ---- the fused planner batch ----------------------------------------------------------------------------------------------
 // One launch answers everything a replan tick asks of the obstacle cloud (sim_planning_demo.cpp:159-178 -> :729-781, and
 // SafeRegionEvaluate's re-check loop corridor_finder.cpp:829-835): a 256-thread block per planner point, three kinds of blocks:

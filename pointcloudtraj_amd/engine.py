@@ -38,6 +38,11 @@ class ReplanOut(C.Structure):
                 ("nsamples", C.c_int64), ("first_hit_sample", C.c_int64), ("nctrl", C.c_int64), ("first_hit_ctrl", C.c_int64)]
 
 
+class ExpandResult(C.Structure):
+    """pct_expand_result: the steered centre, its inflated radius, the nearest node and the neighbourhood's size"""
+    _fields_ = [("center", C.c_double * 3), ("radius", C.c_double), ("near_idx", C.c_int32), ("count", C.c_int32)]
+
+
 class BezierTraj(C.Structure):
     _fields_ = [("polycoef", C.POINTER(C.c_double)), ("row_stride", C.c_int64), ("seg_time", C.POINTER(C.c_double)),
                 ("orders", C.POINTER(C.c_int32)), ("nseg", C.c_int32)]
@@ -73,6 +78,9 @@ def lib():
         L.pct_init.argtypes = [i32]
         L.pct_cloud_create.argtypes = [i64, C.POINTER(vp)]
         L.pct_cloud_destroy.argtypes = [vp]
+        L.pct_cloud_create_small.argtypes = [i64, C.POINTER(vp)]
+        L.pct_cloud_small_aux.argtypes = [vp, C.POINTER(C.POINTER(C.c_double))]
+        L.pct_rrt_expand_batch.argtypes = [vp, vp, C.POINTER(InflateParams), f64p, i64, i64, C.POINTER(ExpandResult), u32p]
         L.pct_cloud_size.restype = i64
         L.pct_cloud_size.argtypes = [vp]
         L.pct_cloud_capacity.restype = i64

@@ -81,6 +81,94 @@ def run_commit_scenario(finder, cloud1, expand=800, refine=300, commits=3):
     return out
 
 
+class RingMirror:
+    """host copy of a rolling window: the slot discipline of pct_cloud_append_aos (the newest frame overwrites the oldest slots,
+    index of a point = its slot)"""
+
+    def __init__(self, cap):
+        self.cap, self.count, self.nxt, self.passed = int(cap), 0, 0, 0
+        self.xyz = np.zeros((self.cap, 3), np.float32)
+
+    def append(self, f):
+        idx = (self.nxt + np.arange(len(f))) % self.cap
+        self.xyz[idx] = f
+        self.nxt = (self.nxt + len(f)) % self.cap
+        self.count = min(self.cap, self.count + len(f))
+        self.passed += len(f)
+
+    def live(self):
+        return self.xyz[:self.count]
+
+
+def rolling_frame(full, centre, seed, radius=8.0):
+    """what a `radius` m sensor at `centre` sees of the map `full`, in the shuffled order a stream of returns has"""
+    crop = synth.crop_ball(full, centre, radius)
+    return crop[synth.shuffled_order(seed, len(crop))]
+
+
+def run_rolling_commit_scenario(finder, window=40000, expand=800, refine=300, commits=5, radius=8.0, feed="append", info=None, clock=None):
+    """The planner's tick on a ROLLING map (rcvPointCloudCallBack -> SafeRegionEvaluate + SafeRegionRefine,
+    sim_planning_demo.cpp:159-178, 381-422, with the frame appended to a window of `window` points instead of replacing the cloud):
+    first frame = the seed-6 map within `radius` of START (order seed 7), Expansion + Refine; then `commits` times: commit to the
+    centre of the corridor's third sphere (setStartPt, resetRoot, Refine(refine / 2)), sense the map within `radius` of that point
+    (order seed 8 + k), append the frame, Evaluate, Refine(refine / 2).  Returns (Path, Radius, status) after every phase.
+
+    `finder` is any object with the finder's method names.  feed = "append": one with appendInput gets the frames (the caller has
+    enabled its rolling map); one without (the CPU oracle) gets setInput of a host mirror of the window.  feed = "replace": setInput
+    of the mirror either way.  info (a dict, optional) receives the frame sizes, the points that passed through the window and
+    whether it wrapped; clock (a list, optional) receives (phase name, seconds) per call into the finder."""
+    import time
+    p = PARAMS
+    out = []
+    full = synth.pillar_map()
+    mirror = RingMirror(window)
+    appends = feed == "append" and hasattr(finder, "appendInput")
+    sizes = []
+
+    def timed(name, fn, *a):
+        t0 = time.perf_counter()
+        fn(*a)
+        if clock is not None:
+            clock.append((name, time.perf_counter() - t0))
+
+    def feed_frame(frame):
+        sizes.append(len(frame))
+        mirror.append(frame)
+        if appends:
+            timed("append", finder.appendInput, frame)
+        else:
+            timed("set_input", finder.setInput, mirror.live())
+
+    def snap():
+        out.append((*finder.getPath(), finder.status()))
+
+    finder.setParam(p["safety_margin"], p["search_margin"], p["max_radius"], p["sensing_range"])
+    feed_frame(rolling_frame(full, START, 7, radius))
+    finder.reset()
+    finder.setPt(START, GOAL, *BOUNDS, p["sensing_range"], p["max_samples"], p["sample_portion"], p["goal_portion"])
+    timed("expansion", finder.SafeRegionExpansion, expand)
+    snap()
+    timed("refine", finder.SafeRegionRefine, refine)
+    snap()
+    for k in range(commits):
+        path, _ = finder.getPath()
+        if not finder.status()["path_exists"] or len(path) < 4:
+            break
+        target = tuple(float(v) for v in path[2])
+        finder.setStartPt(target, GOAL)
+        finder.resetRoot(target)
+        timed("refine", finder.SafeRegionRefine, refine // 2)
+        snap()
+        feed_frame(rolling_frame(full, target, 8 + k, radius))
+        timed("evaluate", finder.SafeRegionEvaluate)
+        snap()
+        timed("refine", finder.SafeRegionRefine, refine // 2)
+        snap()
+    if info is not None:
+        info.update(frames=sizes, passed=mirror.passed, wrapped=mirror.passed > mirror.cap, window=mirror.live().copy())
+    return out
+
+
 def timed_scenario(finder, cloud1, expand=1500, refine=400):
     """run_scenario with wall-clock milliseconds per planner phase (bench.py / scripts/probe_corridor.py)"""
     import time
