@@ -35,6 +35,9 @@ int pct_corridor_set_input(pct_corridor *c, const void *points, int64_t n, int64
  * stride_bytes = 16 for pcl::PointXYZ records, 12 for packed xyz. */
 int pct_corridor_enable_rolling(pct_corridor *c, float cell_size, const float extent[3]);
 int pct_corridor_append_input(pct_corridor *c, const void *points, int64_t n, int64_t stride_bytes);
+/* after pct_corridor_enable_rolling: res > 0 makes pct_corridor_append_input keep only the points whose voxel of that size is new
+ * to the window (pct_cloud_ring_dedup: a window of unique voxels); res = 0 turns it off. */
+int pct_corridor_set_rolling_dedup(pct_corridor *c, double res);
 int pct_corridor_set_pt(pct_corridor *c, const double start[3], const double end[3], double xl, double xh, double yl, double yh,
                         double zl, double zh, double local_range, int max_iter, double sample_portion, double goal_portion);
 int pct_corridor_set_start_pt(pct_corridor *c, const double start[3], const double end[3]);

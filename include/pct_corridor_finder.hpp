@@ -212,6 +212,9 @@ public:
     // the newest frame overwrites the oldest points and the index is updated in place.  setInput still replaces the whole window.
     void enableRollingMap(float cell_size = 0.0f, const float *extent = nullptr) { map_.enableRollingIndex(cell_size, extent); }
     void appendInput(const void *points, int64_t n, int64_t stride_bytes = 16) { map_.appendInput(points, n, stride_bytes); }
+    // after enableRollingMap: appendInput keeps only points whose voxel of size res is new to the window (ObstacleMap::setRollingDedup;
+    // 0 = off).  The corridor is the one the reference finds over the window's contents, which then hold each voxel once.
+    void setRollingDedup(double res) { map_.setRollingDedup(res); }
 
     // ---- queries ----
     bool checkTrajPtCol(const Vec3 &pt) { return clearance(pt) < 0.0; }                     // :412-416

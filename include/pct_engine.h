@@ -95,6 +95,22 @@
  * table look at the flag after their wait, file the window again and ask once more; the device forms (*_dev) return before their
  * kernels have run and cannot repair -- the next host-form call or append on the cloud does.
  *
+ * De-duplicating appends (pct_cloud_ring_dedup): a rolling map that holds a window of UNIQUE voxels.  key(p) is pct_voxel.h's voxel
+ * coordinate per axis, (int) round((double) p / res), fp64 division, half away from zero; a point is keyless if a coordinate is
+ * non-finite or a voxel coordinate falls outside [-2^20, 2^20) -- a keyless point is always kept and matches nothing, so one NaN
+ * never rejects a frame.  An append of the frame F[0..n) onto a window with cap, count, next (n <= cap, judged on the offered n):
+ * the doomed slots are (next + j) mod cap for j < n, those below count -- what a plain append of all n points would overwrite; the
+ * holders are the keys of the keyed points in the other slots below count; F[i] is kept iff it is keyless, or its key is no holder
+ * and no earlier point of the frame has it (first occurrence wins, as in voxel_map).  The n' kept points, in frame order and with
+ * their coordinates unchanged, are appended exactly as pct_cloud_append_aos appends a frame made of them; n' = 0 changes nothing.
+ * Invariant: after an append, the key of every keyed point of that frame is present in the window (only doomed slots are evicted,
+ * and a point is dropped only for an earlier point of the frame or a holder outside the doomed slots -- asking the whole window
+ * would drop a re-sensed obstacle for a holder the same append evicts).  Copies: a key gains a second copy only when all its
+ * holders lie among the n oldest slots; no bound is promised (frames of half the window: up to 3 seen).  Host wait: such an append
+ * waits once on the host for the survivor count n' (a host-mapped word, polled) before it can queue the unchanged eviction and
+ * insert launches; those stay asynchronous as for any copied frame, their source being a device buffer the library owns.
+ * Uploads (pct_cloud_upload_*) are not filtered.  Captured plans are unaffected by such appends.
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -191,6 +207,18 @@ int pct_cloud_ring_info(pct_cloud *c, int32_t dims[3], double *cell_size, int64_
  * sits in the overflow queue although the cells were sized from the window -- surfaces on a lattice finer than the cell, the same points sensed
  * frame after frame (the reference's rgbd mode, camera_sensor.cpp:160-166).  0 = no rolling-map index. */
 int pct_cloud_ring_bucket_records(const pct_cloud *c);
+/* res > 0: appends (pct_cloud_append_aos / pct_cloud_append_frame) on this rolling-map cloud keep only points whose voxel is new
+ * to the window (the rule in the paragraph "De-duplicating appends" above); res == 0: off (default; appends exactly as before).
+ * PCT_ERR_INVALID unless pct_cloud_ring_index was asked for on the cloud, or for res < 0 / non-finite.  A cell size chosen
+ * automatically is at least res; an explicit cell_size < res / 2 is PCT_ERR_INVALID from whichever of pct_cloud_ring_index /
+ * pct_cloud_ring_dedup comes second (a table already sized automatically with smaller cells is sized again here).
+ * pct_cloud_ring_drop turns the mode off.  On a cloud whose table does not exist yet the first append applies the in-frame rule alone
+ * (the window is empty) and the compacted frame sizes the table.  Each filtered append waits once on the host, see above. */
+int pct_cloud_ring_dedup(pct_cloud *c, double res);
+/* the last append: points offered, points kept; flags[min(offered, cap)] = 1 kept / 0 dropped (may be NULL); totals since enabled.
+ * PCT_ERR_INVALID while the mode is off. */
+int pct_cloud_ring_dedup_last(pct_cloud *c, int64_t *offered, int64_t *kept, uint8_t *flags, int64_t cap,
+                              uint64_t *total_offered, uint64_t *total_kept);
 /* Zero-copy ingest.  pct_cloud_frame_buffer hands out a host-mapped staging buffer of at least `bytes` bytes (valid until the next
  * call that asks for a larger one, or pct_cloud_destroy); the producer -- a sensor driver, the deserialiser of a
  * sensor_msgs/PointCloud2 -- writes the frame's records there (x, y, z floats at the start of each stride-byte record) and

@@ -61,6 +61,10 @@ public:
                 pct_cloud_destroy(bigger);
                 check(PCT_ERR_HIP, "pct_cloud_ring_index");
             }
+            if (rolling_ && dedup_res_ > 0 && pct_cloud_ring_dedup(bigger, dedup_res_) != PCT_OK) {     // the larger cloud keeps the mode
+                pct_cloud_destroy(bigger);
+                check(PCT_ERR_HIP, "pct_cloud_ring_dedup");
+            }
             pct_cloud_destroy(cloud_);
             cloud_ = bigger;
             capacity_ = cap;
@@ -75,6 +79,15 @@ public:
     {
         check(pct_cloud_ring_index(cloud_, cell_size, extent), "pct_cloud_ring_index");
         rolling_ = true;
+    }
+    // rolling map as a window of UNIQUE voxels (pct_cloud_ring_dedup): after enableRollingIndex; res > 0: appendInput keeps only the
+    // points whose voxel (pct_voxel.h's round(p / res)) is new to the window -- a sensor that re-emits the same surface lattice frame
+    // after frame (the reference's rgbd mode) then fills the window with geometry instead of copies; res = 0: off.  Every keyed
+    // point of a frame has its voxel in the window after that frame's append.  setInput (replace) is not filtered.
+    void setRollingDedup(double res)
+    {
+        check(pct_cloud_ring_dedup(cloud_, res), "pct_cloud_ring_dedup");
+        dedup_res_ = res;
     }
     // rolling map (config C5): append the newest sensor frame, evicting the oldest points
     void appendInput(const void *points, int64_t n, int64_t stride_bytes = 16)
@@ -206,6 +219,7 @@ private:
     int64_t capacity_ = 0;
     bool cloud_empty_ = true;
     bool rolling_ = false;
+    double dedup_res_ = 0.0;
     double safety_margin_ = 0.0;
     pct_inflate_params prm_{ { 0, 0, 0 }, 0.0, 0.0, 0.0 };
 };

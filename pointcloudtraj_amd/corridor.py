@@ -36,6 +36,7 @@ def lib():
         L.pct_corridor_set_input.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int]
         L.pct_corridor_enable_rolling.argtypes = [vp, C.c_float, vp]
         L.pct_corridor_append_input.argtypes = [vp, vp, C.c_int64, C.c_int64]
+        L.pct_corridor_set_rolling_dedup.argtypes = [vp, C.c_double]
         L.pct_corridor_set_pt.argtypes = [vp, d3, d3] + [C.c_double] * 7 + [C.c_int, C.c_double, C.c_double]
         L.pct_corridor_set_start_pt.argtypes = [vp, d3, d3]
         L.pct_corridor_reset_root.argtypes = [vp, d3]
@@ -114,6 +115,10 @@ class SafeRegionRrtStar:
         """append one sensor frame: the newest points overwrite the oldest, the index is updated in place"""
         a = np.ascontiguousarray(points, np.float32)
         self._chk(self.L.pct_corridor_append_input(self.h, a.ctypes.data_as(C.c_void_p), len(a), a.shape[1] * 4))
+
+    def setRollingDedup(self, res: float):
+        """after enableRollingMap: appendInput keeps only points whose voxel of size res is new to the window (0 = off)"""
+        self._chk(self.L.pct_corridor_set_rolling_dedup(self.h, float(res)))
 
     def setPt(self, start, end, xl, xh, yl, yh, zl, zh, local_range, max_iter, sample_portion, goal_portion):
         self._chk(self.L.pct_corridor_set_pt(self.h, _d3(start), _d3(end), xl, xh, yl, yh, zl, zh, local_range, int(max_iter),

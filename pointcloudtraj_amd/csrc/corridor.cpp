@@ -74,6 +74,7 @@ int pct_corridor_append_input(pct_corridor *c, const void *points, int64_t n, in
 {
     return guarded([&] { c->impl->appendInput(points, n, stride_bytes); });
 }
+int pct_corridor_set_rolling_dedup(pct_corridor *c, double res) { return guarded([&] { c->impl->setRollingDedup(res); }); }
 int pct_corridor_set_pt(pct_corridor *c, const double start[3], const double end[3], double xl, double xh, double yl, double yh,
                         double zl, double zh, double local_range, int max_iter, double sample_portion, double goal_portion)
 {

@@ -27,6 +27,7 @@
 #include "gridbuild.hpp"
 #include "pyramid.hpp"
 #include "ring.hpp"
+#include "ring_dedup.hpp"
 #include "brute2.hpp"
 #include "knn.hpp"
 #include "rsearch.hpp"
@@ -272,6 +273,19 @@ struct pct_cloud {
     uint32_t *h_ring_status = nullptr, *d_ring_status = nullptr;      // host-mapped {overrun flag, overflow-queue length}
     int64_t ring_cfg_count = 0;                                       // points in the window when the table was last sized
     int ring_appends_since_cfg = 0;
+    // de-duplicating appends (ring_dedup.hpp, pct_cloud_ring_dedup): voxel size (0 = off), the frame filter's scratch -- key table,
+    // per-point table slot / rank, tile totals, kept flags, the compacted frame -- and the host-mapped {sequence, survivors} pair
+    double dd_res = 0.0;
+    unsigned long long *dd_keys = nullptr;
+    uint32_t *dd_vals = nullptr, *dd_pslot = nullptr, *dd_rank = nullptr, *dd_tile = nullptr;
+    uint8_t *dd_flags = nullptr;
+    float *dd_out = nullptr;
+    uint32_t dd_tcap = 0;                    // entries of the key table
+    int64_t dd_ncap = 0;                     // points the per-point scratch holds
+    uint32_t *h_dd_word = nullptr, *d_dd_word = nullptr;
+    uint32_t dd_seq = 0;
+    int64_t dd_last_offered = 0, dd_last_kept = 0;
+    uint64_t dd_total_offered = 0, dd_total_kept = 0;
     struct ReplanCtx *rp = nullptr;              // lazily created context of the un-captured fused planner batch
 };
 
@@ -1516,6 +1530,8 @@ int pct_cloud_destroy(pct_cloud *c)
     if (c->h_gbcheck) (void)hipHostFree(c->h_gbcheck);
     dev_free(c->ring_ht); dev_free(c->ring_slots); dev_free(c->ring_ovf); dev_free(c->ring_where); dev_free(c->ring_st);
     if (c->h_ring_status) (void)hipHostFree(c->h_ring_status);
+    dev_free(c->dd_keys); dev_free(c->dd_vals); dev_free(c->dd_pslot); dev_free(c->dd_rank); dev_free(c->dd_tile); dev_free(c->dd_flags); dev_free(c->dd_out);
+    if (c->h_dd_word) (void)hipHostFree(c->h_dd_word);
     replan_ctx_free(c->rp);
     dev_free(c->crop_tile); dev_free(c->crop_idx); dev_free(c->crop_d2); dev_free(c->crop_x); dev_free(c->crop_y); dev_free(c->crop_z);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1583,13 +1599,13 @@ int pct_cloud_upload_soa_dev(pct_cloud *c, const float *d_x, const float *d_y, c
     return after_replace(c);
 }
 
-int pct_cloud_append_aos(pct_cloud *c, const void *pts, int64_t n, int64_t stride_bytes)
+}  // extern "C"
+
+namespace {
+
+// append on a cloud without a live rolling-map table: plain stores into the ring slots; a rolling-map cloud gets its table from this first data
+int append_unindexed(pct_cloud *c, const void *pts, int64_t n, int64_t stride_bytes)
 {
-    if (!c || n < 0 || (n > 0 && !pts) || stride_bytes < 12 || (stride_bytes & 3)) return fail(PCT_ERR_INVALID, "bad append arguments");
-    if (n > c->cap) return fail(PCT_ERR_CAPACITY, "appending %lld points to a ring of %lld", (long long)n, (long long)c->cap);
-    if (n == 0) return PCT_OK;
-    drop_grid(c);
-    if (c->ring_ready) return ring_append(c, pts, n, stride_bytes);     // rolling-map index: updated in place
     const int64_t first = std::min(n, c->cap - c->ring_next);
     PCTCHK(upload_range(c, pts, first, stride_bytes, c->ring_next));
     HIPCHK(hipStreamSynchronize(g_stream));   // the staging buffer is reused by the wrapped part
@@ -1600,6 +1616,21 @@ int pct_cloud_append_aos(pct_cloud *c, const void *pts, int64_t n, int64_t strid
     c->ring_next = (c->ring_next + n) % c->cap;
     c->count = std::min(c->cap, c->count + n);
     return after_replace(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pct_cloud_append_aos(pct_cloud *c, const void *pts, int64_t n, int64_t stride_bytes)
+{
+    if (!c || n < 0 || (n > 0 && !pts) || stride_bytes < 12 || (stride_bytes & 3)) return fail(PCT_ERR_INVALID, "bad append arguments");
+    if (n > c->cap) return fail(PCT_ERR_CAPACITY, "appending %lld points to a ring of %lld", (long long)n, (long long)c->cap);
+    if (c->ring_on && c->dd_res > 0) return ring_append_dedup(c, pts, n, stride_bytes);     // a window of unique voxels (pct_cloud_ring_dedup)
+    if (n == 0) return PCT_OK;
+    drop_grid(c);
+    if (c->ring_ready) return ring_append(c, pts, n, stride_bytes);     // rolling-map index: updated in place
+    return append_unindexed(c, pts, n, stride_bytes);
 }
 
 int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)

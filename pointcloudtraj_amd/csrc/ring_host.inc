@@ -57,6 +57,7 @@ int ring_configure(pct_cloud *c, const double ext_in[3])
         h = std::cbrt(vol * ppc / (double)std::max<int64_t>(c->cap, 1));
     }
     if (!(h > 0) || !std::isfinite(h)) h = 1.0;
+    if (c->dd_res > 0 && !(c->ring_cell_req > 0)) h = std::max(h, c->dd_res);      // de-dup: a voxel's box then touches at most 3 cells per axis
     // table: the window's extent plus a quarter of slack per axis, rounded up to a power of two; at most 2^24 buckets
     // (8 GiB of records at 32 x 16 B each; only the buckets in use are ever touched)
     int g[3], lg[3];
@@ -215,8 +216,10 @@ int ring_finish_pending(pct_cloud *c)
     return ring_after_append(c);
 }
 
-// append on a cloud whose ring index is live: evict what the overwritten slots held, store and file the new frame
-int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride)
+// append on a cloud whose ring index is live: evict what the overwritten slots held, store and file the new frame.
+// d_own != nullptr: the frame is already in a device buffer the library owns (the survivors of the de-dup filter, below) and `pts`
+// is not looked at -- same launches, no staging; the call may return before they have run, as for a frame copied to the staging buffer.
+int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride, const unsigned char *d_own = nullptr)
 {
     hipStream_t s = g_stream;
     const size_t bytes = (size_t)n * (size_t)stride;
@@ -227,10 +230,11 @@ int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride)
     // either way -- the 600 KB cross the bus in ~35 us whether the copy engine or the kernel moves them; what the path buys is a tighter
     // p99 and the zero-copy entry point (pct_cloud_append_frame), not the median.
     // in_place: the producer wrote the frame straight into the staging buffer (pct_cloud_frame_buffer / pct_cloud_append_frame)
-    const bool in_place = pts == c->h_frame && c->h_frame != nullptr && bytes <= c->frame_cap;
-    const bool mapped = in_place || (bytes <= ((size_t)4 << 20) && mapped_io_on());
+    const bool in_place = !d_own && pts == c->h_frame && c->h_frame != nullptr && bytes <= c->frame_cap;
+    const bool mapped = in_place || ((d_own || bytes <= ((size_t)4 << 20)) && mapped_io_on());
     const unsigned char *d_src = nullptr;
-    if (in_place) d_src = c->d_frame;
+    if (d_own) d_src = d_own;
+    else if (in_place) d_src = c->d_frame;
     else if (mapped) {
         // copies go through a staging buffer of their own: the producer of zero-copy frames owns c->h_frame and may be writing
         // the next frame into it while the previous (asynchronous) copy append is still being read
@@ -260,7 +264,7 @@ int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride)
             ring_evict_kernel<<<ceil_div(old_valid, 256), 256, 0, s>>>(c->R, c->x, c->y, c->z, (uint32_t)s0, (uint32_t)old_valid, c->ring_ht, c->ring_slots,
                                                                        c->ring_ovf, c->ring_where, c->ring_st);
     }
-    if (mapped && !in_place) std::memcpy(c->h_astage, pts, bytes);
+    if (mapped && !in_place && !d_own) std::memcpy(c->h_astage, pts, bytes);
     for (int k = 0; k < 2; k++) {
         const int64_t cnt = part_n[k], s0 = part_slot0[k];
         if (cnt <= 0) continue;
@@ -283,6 +287,122 @@ int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride)
     if (mapped) PCTCHK(express_wait(c));        // zero-copy frames: the producer may rewrite the staging buffer as soon as we return
     else HIPCHK(hipStreamSynchronize(s));
     return ring_after_append(c);
+}
+
+// ---- de-duplicating appends (ring_dedup.hpp) ---------------------------------------------------------------------------------
+int append_unindexed(pct_cloud *c, const void *pts, int64_t n, int64_t stride_bytes);     // engine.hip: the first-data path
+
+// scratch of the frame filter for a frame of n points (grow-only)
+int dedup_ensure(pct_cloud *c, int64_t n)
+{
+    if (!c->h_dd_word) {
+        PCTCHK(mapped_alloc(&c->h_dd_word, &c->d_dd_word, 4));
+        c->h_dd_word[0] = c->h_dd_word[1] = 0;
+    }
+    uint32_t T = 1024;
+    while ((uint64_t)T < 2ull * (uint64_t)n) T <<= 1;
+    if (T > c->dd_tcap) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        dev_free(c->dd_keys); dev_free(c->dd_vals);
+        c->dd_tcap = 0;
+        PCTCHK(dev_alloc(&c->dd_keys, T));
+        PCTCHK(dev_alloc(&c->dd_vals, T));
+        c->dd_tcap = T;
+    }
+    if (n > c->dd_ncap) {
+        HIPCHK(hipStreamSynchronize(g_stream));       // the previous append's insert kernel may still be reading the compacted frame
+        const int64_t cap = std::min<int64_t>(std::max<int64_t>(c->cap, 1), std::max<int64_t>(n, 2 * c->dd_ncap));
+        dev_free(c->dd_pslot); dev_free(c->dd_rank); dev_free(c->dd_tile); dev_free(c->dd_flags); dev_free(c->dd_out);
+        c->dd_ncap = 0;
+        PCTCHK(dev_alloc(&c->dd_pslot, (size_t)cap));
+        PCTCHK(dev_alloc(&c->dd_rank, (size_t)cap));
+        PCTCHK(dev_alloc(&c->dd_tile, (size_t)ceil_div(cap, kDdTile)));
+        PCTCHK(dev_alloc(&c->dd_flags, (size_t)cap));
+        PCTCHK(dev_alloc(&c->dd_out, 3 * (size_t)cap));
+        c->dd_ncap = cap;
+    }
+    return PCT_OK;
+}
+
+// The filter's launches over the frame at d_src (device-visible), then the ONE host wait of a de-dup append: the survivor count,
+// polled in host-mapped memory as express_wait polls its word.  probe = false: the window is empty, the in-frame rule alone.
+int dedup_filter(pct_cloud *c, const unsigned char *d_src, int64_t n, int64_t stride, bool probe, int64_t *kept)
+{
+    hipStream_t s = g_stream;
+    uint32_t T = 1024;
+    while ((uint64_t)T < 2ull * (uint64_t)n) T <<= 1;
+    const uint32_t un = (uint32_t)n;
+    const int ntiles = ceil_div(n, kDdTile);
+    const DdWindow W{ (uint32_t)c->ring_next, (uint32_t)c->cap, un };
+    const uint32_t seq = ++c->dd_seq;
+    pct_vox::vox_table_init_kernel<<<std::min(ceil_div(T, 256), 2048), 256, 0, s>>>(c->dd_keys, c->dd_vals, T);
+    dd_key_kernel<<<ceil_div(n, 256), 256, 0, s>>>(d_src, un, (uint32_t)stride, c->dd_res, c->dd_keys, c->dd_vals, T - 1u, c->dd_pslot);
+    if (probe)
+        dd_probe_kernel<true><<<ceil_div(n, kDdPointsPerBlock), 256, 0, s>>>(ring_view(c), W, c->dd_res, un, c->dd_keys, c->dd_vals, c->dd_pslot, c->dd_flags);
+    else
+        dd_probe_kernel<false><<<ceil_div(n, kDdPointsPerBlock), 256, 0, s>>>(RingView{}, W, c->dd_res, un, c->dd_keys, c->dd_vals, c->dd_pslot, c->dd_flags);
+    dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dd_flags, un, c->dd_rank, c->dd_tile);
+    dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dd_tile, (uint32_t)ntiles, c->d_dd_word, seq);
+    dd_compact_kernel<<<ceil_div(n, 256), 256, 0, s>>>(d_src, un, (uint32_t)stride, c->dd_flags, c->dd_rank, c->dd_tile, c->dd_out);
+    HIPCHK(hipGetLastError());
+    bool seen = false;
+    if (poll_results()) {
+        const volatile uint32_t *w = c->h_dd_word;
+        for (long spins = 0; spins < 200000000l && !seen; spins++) {
+            if (w[0] == seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); seen = true; }
+            else __builtin_ia32_pause();
+        }
+    }
+    if (!seen) HIPCHK(hipStreamSynchronize(s));
+    if (c->h_dd_word[0] != seq) return fail(PCT_ERR_HIP, "the de-dup filter finished without its sequence word (%u != %u)", c->h_dd_word[0], seq);
+    *kept = (int64_t)c->h_dd_word[1];
+    if (*kept > n) return fail(PCT_ERR_INTERNAL, "the de-dup filter kept %lld of %lld points", (long long)*kept, (long long)n);
+    return PCT_OK;
+}
+
+// pct_cloud_append_aos on a rolling-map cloud with de-dup on: filter the frame against itself and the window, append the survivors
+int ring_append_dedup(pct_cloud *c, const void *pts, int64_t n, int64_t stride)
+{
+    hipStream_t s = g_stream;
+    PCTCHK(ring_finish_pending(c));
+    c->dd_last_offered = n;
+    c->dd_last_kept = 0;
+    c->dd_total_offered += (uint64_t)n;
+    if (n == 0) return PCT_OK;
+    drop_grid(c);
+    // a cloud that holds points but lost its table (an allocation failed) gets it back first: the filter searches the table
+    if (!c->ring_ready && c->count > 0) { PCTCHK(ring_setup_from_cloud(c)); HIPCHK(hipStreamSynchronize(s)); }
+    PCTCHK(dedup_ensure(c, n));
+    const size_t bytes = (size_t)n * (size_t)stride;
+    const bool in_place = pts == c->h_frame && c->h_frame != nullptr && bytes <= c->frame_cap;
+    const unsigned char *d_src = c->d_frame;
+    if (!in_place) {
+        PCTCHK(ensure_stage(c, bytes + 64));
+        HIPCHK(hipMemcpyAsync(c->d_stage, pts, bytes, hipMemcpyHostToDevice, s));
+        d_src = c->d_stage;
+    }
+    int64_t kept = 0;
+    PCTCHK(dedup_filter(c, d_src, n, stride, c->ring_ready, &kept));
+    // (a copied frame has left the caller's buffer by now: the copy precedes the kernel that released the count.  The compaction
+    // kernel may still be reading the frame where the filter found it -- the library's staging buffer, or the producer's, below)
+    c->dd_last_kept = kept;
+    c->dd_total_kept += (uint64_t)kept;
+    if (kept == 0) {                            // nothing changes; a producer's buffer is its own again once the compaction has read it
+        if (in_place) HIPCHK(hipStreamSynchronize(s));
+        return PCT_OK;
+    }
+    if (c->ring_ready) {
+        PCTCHK(ring_append(c, nullptr, kept, 12, reinterpret_cast<const unsigned char *>(c->dd_out)));
+        // zero-copy frames: the producer may rewrite the staging buffer as soon as we return, and the compaction kernel read it
+        if (in_place) PCTCHK(ring_finish_pending(c));
+        return PCT_OK;
+    }
+    // first data (the window is empty and has no table yet): the compacted frame takes the first-data path, which sizes the table from it
+    std::vector<float> host;
+    try { host.resize(3 * (size_t)kept); } catch (const std::bad_alloc &) { return fail(PCT_ERR_ALLOC, "host allocation failed"); }
+    HIPCHK(hipMemcpyAsync(host.data(), c->dd_out, sizeof(float) * host.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return append_unindexed(c, host.data(), kept, 12);
 }
 
 // the cloud's contents were replaced (upload) or grew on a cloud whose ring table does not exist yet
@@ -577,6 +697,8 @@ int pct_cloud_ring_index(pct_cloud *c, float cell_size, const float extent[3])
     if (!c) return fail(PCT_ERR_INVALID, "null cloud");
     if (c->host_mapped) return fail(PCT_ERR_INVALID, "small (host-mapped) clouds take no index");
     if (cell_size < 0 || !std::isfinite(cell_size)) return fail(PCT_ERR_INVALID, "bad cell size");
+    if (c->ring_on && c->dd_res > 0 && cell_size > 0 && (double)cell_size < c->dd_res / 2)
+        return fail(PCT_ERR_INVALID, "cell size %g is less than half the de-dup voxel %g (pct_cloud_ring_dedup)", (double)cell_size, c->dd_res);
     HIPCHK(hipStreamSynchronize(g_stream));
     drop_grid(c);
     c->ring_on = true;
@@ -616,7 +738,46 @@ int pct_cloud_ring_drop(pct_cloud *c)
     HIPCHK(hipStreamSynchronize(g_stream));
     ring_free(c);
     c->ring_on = false;
+    c->dd_res = 0.0;
     c->generation++;
+    return PCT_OK;
+}
+
+int pct_cloud_ring_dedup(pct_cloud *c, double res)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (!(res >= 0) || !std::isfinite(res)) return fail(PCT_ERR_INVALID, "the de-dup voxel size must be finite and >= 0");
+    if (res == 0) { c->dd_res = 0.0; return PCT_OK; }
+    if (!c->ring_on) return fail(PCT_ERR_INVALID, "de-duplicating appends need the rolling-map index (pct_cloud_ring_index)");
+    if (c->ring_cell_req > 0 && (double)c->ring_cell_req < res / 2)
+        return fail(PCT_ERR_INVALID, "the de-dup voxel %g is more than twice the cell size %g asked of pct_cloud_ring_index", res, (double)c->ring_cell_req);
+    PCTCHK(ring_finish_pending(c));
+    c->dd_res = res;
+    c->dd_last_offered = c->dd_last_kept = 0;
+    c->dd_total_offered = c->dd_total_kept = 0;
+    // a table whose cell size was chosen automatically is sized again if its cells are smaller than the voxel
+    if (c->ring_ready && !(c->ring_cell_req > 0) && c->R.h < res) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        PCTCHK(ring_setup_from_cloud(c));
+        HIPCHK(hipStreamSynchronize(g_stream));
+    }
+    return PCT_OK;
+}
+
+int pct_cloud_ring_dedup_last(pct_cloud *c, int64_t *offered, int64_t *kept, uint8_t *flags, int64_t cap, uint64_t *total_offered,
+                              uint64_t *total_kept)
+{
+    if (!c || (flags && cap < 0)) return fail(PCT_ERR_INVALID, "bad ring_dedup_last arguments");
+    if (!(c->dd_res > 0)) return fail(PCT_ERR_INVALID, "de-duplicating appends are off on this cloud (pct_cloud_ring_dedup)");
+    if (offered) *offered = c->dd_last_offered;
+    if (kept) *kept = c->dd_last_kept;
+    if (total_offered) *total_offered = c->dd_total_offered;
+    if (total_kept) *total_kept = c->dd_total_kept;
+    const int64_t nf = std::min(c->dd_last_offered, cap);
+    if (flags && nf > 0) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        HIPCHK(hipMemcpy(flags, c->dd_flags, (size_t)nf, hipMemcpyDeviceToHost));
+    }
     return PCT_OK;
 }
 

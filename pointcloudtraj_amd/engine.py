@@ -133,6 +133,8 @@ def lib():
         L.pct_cloud_ring_drop.argtypes = [vp]
         L.pct_cloud_has_ring_index.argtypes = [vp]
         L.pct_cloud_ring_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(i64)]
+        L.pct_cloud_ring_dedup.argtypes = [vp, C.c_double]
+        L.pct_cloud_ring_dedup_last.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), vp, i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.pct_ctrl_points_check.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                             i64, f64p, f64p, f64p, u32p]
         L.pct_plan_create_replan.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
@@ -303,6 +305,20 @@ class Cloud:
         ov = C.c_int64()
         _chk(lib().pct_cloud_ring_info(self._h, dims, C.byref(h), C.byref(ov)))
         return dict(dims=tuple(dims), cell_size=h.value, overflow_entries=ov.value, bucket_records=int(lib().pct_cloud_ring_bucket_records(self._h)))
+
+    def ring_dedup(self, res: float):
+        """de-duplicating appends (pct_cloud_ring_dedup): res > 0 keeps only points whose voxel is new to the window, 0 turns it off"""
+        _chk(lib().pct_cloud_ring_dedup(self._h, float(res)))
+
+    def ring_dedup_last(self):
+        """the last filtered append: offered / kept counts, the kept flag per offered point, totals since the mode was enabled"""
+        off, kept = C.c_int64(), C.c_int64()
+        toff, tkept = C.c_uint64(), C.c_uint64()
+        _chk(lib().pct_cloud_ring_dedup_last(self._h, C.byref(off), C.byref(kept), None, 0, C.byref(toff), C.byref(tkept)))
+        flags = np.zeros(off.value, np.uint8)
+        if off.value:
+            _chk(lib().pct_cloud_ring_dedup_last(self._h, None, None, flags.ctypes.data, len(flags), None, None))
+        return dict(offered=off.value, kept=kept.value, flags=flags.astype(bool), total_offered=toff.value, total_kept=tkept.value)
 
     def reserve_queries(self, Q: int):
         _chk(lib().pct_cloud_reserve_queries(self._h, int(Q)))
