@@ -348,7 +348,12 @@ typedef struct pct_bezier_traj {
 /* Sample the trajectory every dt from t_start over stop_time (reference loop semantics),
  * inflate every sample, report the first one with negative radius (NN distance <
  * search_margin).  first_hit = -1 when none.  Optional per-sample outputs (capacity cap):
- * pos (cap x 3 fp64), radius, d2, idx. */
+ * pos (cap x 3 fp64), radius, d2, idx.
+ * Contract, the same on every kind of cloud and whatever was called before: *nsamples is the UNCLIPPED count, the number of samples
+ * the reference's loops would evaluate; *first_hit and the arrays cover the first min(nsamples, cap, 4096) samples and nothing
+ * else -- a collision further on is not reported, entries behind them are not written.  No sample at all (t_start at or past the
+ * end, stop_time < dt): PCT_OK, nsamples = 0, first_hit = -1.  cap <= 0, dt not > 0, nseg <= 0, an order outside 0..12 or a
+ * row_stride below 3 * (order + 1): PCT_ERR_INVALID. */
 int pct_bezier_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflate_params *p,
                      double t_start, double stop_time, double dt,
                      int64_t *first_hit, int64_t *nsamples,

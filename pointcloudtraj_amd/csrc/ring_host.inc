@@ -552,9 +552,12 @@ int replan_enqueue(pct_cloud *c, ReplanCtx *x, hipStream_t s)
 
 // Fill the argument block: header, corridor nodes, trajectory, the sample times (the reference's nested loops,
 // sim_planning_demo.cpp:729-771) and the control-point list (segments from the one holding t_start on).
+// sample_cap: the caller's sample capacity.  Only the first min(context capacity, sample_cap) samples are handed to the kernel, so
+// the first hit it reports covers exactly the samples the caller reads, whatever capacity an earlier call left the context with.
 int replan_fill(ReplanCtx *x, const pct_inflate_params *p, const double *nodes, int64_t n_nodes, const pct_bezier_traj *traj, double t_start,
-                double stop_time, double dt, int want_nn, int with_ctrl, int64_t *nsamples_total)
+                double stop_time, double dt, int want_nn, int with_ctrl, int64_t sample_cap, int64_t *nsamples_total)
 {
+    const int64_t room = std::min<int64_t>(x->max_samples, std::max<int64_t>(sample_cap, 0));
     ReplanHeader H = x->hdr;
     H.P = to_dev(p);
     H.n_nodes = (int32_t)n_nodes;
@@ -592,12 +595,12 @@ int replan_fill(ReplanCtx *x, const pct_inflate_params *p, const double *nodes, 
             for (double t = (i == first_seg) ? t_s : 0.0; t < T; t += dt) {
                 t_accu += dt;
                 if (t_accu > stop_time) break;
-                if (n < x->max_samples) { f64a[H.off_sample_t + n] = t; u32a[H.off_sample_seg + n] = (uint32_t)i; }
+                if (n < room) { f64a[H.off_sample_t + n] = t; u32a[H.off_sample_seg + n] = (uint32_t)i; }
                 n++;
             }
         }
         *nsamples_total = n;
-        H.n_samples = (int32_t)std::min<int64_t>(n, x->max_samples);
+        H.n_samples = (int32_t)std::min<int64_t>(n, room);
         if (with_ctrl) {
             int k = 0;
             for (int i = first_seg; i < traj->nseg; i++)
@@ -627,7 +630,8 @@ int replan_wait(ReplanCtx *x, hipStream_t s)
 }
 
 // sample_cap: how many sample entries the caller's arrays hold (the captured plan documents "max_samples"; pct_bezier_check hands
-// its own `cap` down).  first_hit / nsamples always cover every evaluated sample.
+// its own `cap` down).  replan_fill was given the same figure, so the evaluated samples are the first min(nsamples, sample_cap) and
+// first_hit covers exactly those; nsamples is the unclipped count.
 void replan_read(const ReplanCtx *x, int64_t nsamples_total, pct_replan_out *o, int64_t sample_cap)
 {
     const ReplanHeader &H = x->hdr_sent;
@@ -679,7 +683,7 @@ int replan_direct(pct_cloud *c, const pct_inflate_params *p, const double *nodes
     }
     int64_t ntot = 0;
     PCTCHK(ask_twice_after_overrun(c, [&] {
-        PCTCHK(replan_fill(c->rp, p, nodes, n_nodes, traj, t_start, stop_time, dt, want_nn, with_ctrl, &ntot));
+        PCTCHK(replan_fill(c->rp, p, nodes, n_nodes, traj, t_start, stop_time, dt, want_nn, with_ctrl, max_samples, &ntot));
         if (const int st = replan_enqueue(c, c->rp, g_stream)) { c->rp->seq--; return st; }     // nothing ran: the slot is filled again
         return replan_wait(c->rp, g_stream);
     }));
@@ -912,7 +916,7 @@ int pct_plan_replan_run(pct_plan *p, const pct_inflate_params *prm, const double
     int64_t ntot = 0;
     return ask_twice_after_overrun(c, [&]() -> int {        // the index lost points (overflow-queue overrun): refiled, asked once more
         const auto t0 = std::chrono::steady_clock::now();
-        PCTCHK(replan_fill(p->rx, prm, nodes, n_nodes, traj, t_start, stop_time, dt, want_nn, 1, &ntot));
+        PCTCHK(replan_fill(p->rx, prm, nodes, n_nodes, traj, t_start, stop_time, dt, want_nn, 1, p->rx->max_samples, &ntot));
         const auto t1 = std::chrono::steady_clock::now();
         if (const hipError_t le = hipGraphLaunch(p->exec, g_stream); le != hipSuccess) {
             p->rx->seq--;                                        // nothing ran: host and device tick counts stay in step

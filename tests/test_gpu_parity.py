@@ -7,11 +7,17 @@ Bars: indices bit-exact (uint32), squared distances bit-exact (fp64 ==; the nort
 Tie policy: where the fixture marks a tie (several points at the same fp64 d2) the engine must
 return the LOWEST index (fixture field lowest_idx); elsewhere it must equal the reference's index.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from conftest import load_golden
 from pointcloudtraj_amd import synth
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from bezier_model import bezier_samples_exact_powers  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -122,45 +128,6 @@ def test_inflate_empty_cloud(E):
     c.close()
 
 
-def _bezier_samples_exact_powers(polycoef, seg_time, orders, t_start, stop, dt=0.02):
-    """checkSafeTrajectory's sample enumeration (sim_planning_demo.cpp:735-771) and getPosFromBezier (:715-727) restated in Python
-    floats (IEEE doubles, one rounding per operation: the same arithmetic as the C restatement) with the Bernstein powers taken
-    EXACTLY (rational arithmetic) and rounded once.  Returns (positions, per-sample flag "libm's pow gave the correctly rounded
-    power for every term")."""
-    import math
-    from fractions import Fraction
-    T, nseg = [float(v) for v in seg_time], len(seg_time)
-    t_s, first = float(t_start), 0
-    for first in range(nseg):
-        if t_s > T[first] and first + 1 < nseg:
-            t_s -= T[first]
-        else:
-            break
-    pos, libm_exact = [], []
-    acc, done = 0.0, False
-    for sgm in range(first, nseg):
-        t = t_s if sgm == first else 0.0
-        while t < T[sgm]:
-            acc += dt
-            if acc > stop:
-                done = True
-                break
-            n = int(orders[sgm]); m = n + 1; u = t / T[sgm]
-            ok, p = True, []
-            for d in range(3):
-                a = 0.0
-                for j in range(m):
-                    pu, pv = float(Fraction(u) ** j), float(Fraction(1.0 - u) ** (n - j))
-                    ok = ok and pu == math.pow(u, j) and pv == math.pow(1.0 - u, n - j)
-                    a += float(math.comb(n, j)) * float(polycoef[sgm, d * m + j]) * pu * pv
-                p.append(a * T[sgm])
-            pos.append(p); libm_exact.append(ok)
-            t += dt
-        if done:
-            break
-    return np.asarray(pos, np.float64).reshape(-1, 3), np.asarray(libm_exact, bool)
-
-
 @pytest.mark.parametrize("grid", [False, True])
 def test_bezier_golden(E, grid):
     """The sampled collision check against the fixture (oracle/corridor_port.c over the pinned NN): sample enumeration and first-hit
@@ -178,7 +145,7 @@ def test_bezier_golden(E, grid):
                            float(g[f"case{i}_stop_time"]))
         want_pos = g[f"case{i}_pos"]
         assert r["n"] == len(want_pos)
-        exact_pos, libm_ok = _bezier_samples_exact_powers(g[f"case{i}_polycoef"], g["seg_time"], g["orders"], float(g[f"case{i}_t_start"]), float(g[f"case{i}_stop_time"]))
+        exact_pos, libm_ok = bezier_samples_exact_powers(g[f"case{i}_polycoef"], g["seg_time"], g["orders"], float(g[f"case{i}_t_start"]), float(g[f"case{i}_stop_time"]))[:2]
         assert len(exact_pos) == len(want_pos)
         assert np.array_equal(r["pos"], exact_pos), f"case {i}: device positions != the formula with exactly rounded powers"
         assert np.array_equal(exact_pos[libm_ok], want_pos[libm_ok]), f"case {i}: fixture != formula where libm's pow is exact"
