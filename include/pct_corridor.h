@@ -38,6 +38,14 @@ int pct_corridor_append_input(pct_corridor *c, const void *points, int64_t n, in
 /* after pct_corridor_enable_rolling: res > 0 makes pct_corridor_append_input keep only the points whose voxel of that size is new
  * to the window (pct_cloud_ring_dedup: a window of unique voxels); res = 0 turns it off. */
 int pct_corridor_set_rolling_dedup(pct_corridor *c, double res);
+/* after pct_corridor_enable_rolling: take points out of the window (pct_engine.h, paragraph "Removing points"); *removed (may be
+ * NULL) = the number of points removed.  forget_outside removes everything farther than r from centre: the lidar-mode tick is
+ * append_input -> forget_outside(drone, sensing range) -> evaluate -> refine, and with set_rolling_dedup on the window then holds
+ * exactly the frame's points, the cloud the reference's lidar mode replaces its map with every frame.  clear_ball / clear_box
+ * withdraw a stale obstacle.  A window left without a point is the empty cloud.  Radii that may now grow are re-checked by evaluate. */
+int pct_corridor_forget_outside(pct_corridor *c, const double centre[3], double r, int64_t *removed);
+int pct_corridor_clear_ball(pct_corridor *c, const double centre[3], double r, int64_t *removed);
+int pct_corridor_clear_box(pct_corridor *c, const double lo[3], const double hi[3], int64_t *removed);
 int pct_corridor_set_pt(pct_corridor *c, const double start[3], const double end[3], double xl, double xh, double yl, double yh,
                         double zl, double zh, double local_range, int max_iter, double sample_portion, double goal_portion);
 int pct_corridor_set_start_pt(pct_corridor *c, const double start[3], const double end[3]);

@@ -215,6 +215,18 @@ public:
     // after enableRollingMap: appendInput keeps only points whose voxel of size res is new to the window (ObstacleMap::setRollingDedup;
     // 0 = off).  The corridor is the one the reference finds over the window's contents, which then hold each voxel once.
     void setRollingDedup(double res) { map_.setRollingDedup(res); }
+    // after enableRollingMap: take points out of the window (ObstacleMap::forgetOutside / clearBall / clearBox; each returns the
+    // number removed).  The lidar-mode tick is appendInput -> forgetOutside -> SafeRegionEvaluate -> SafeRegionRefine: with
+    // setRollingDedup on and forgetOutside(drone, sensing range) after every frame the window holds exactly the frame's points --
+    // the cloud the reference's lidar mode hands setInput every frame (camera_sensor.cpp:133-145, sim_planning_demo.cpp:159-167)
+    // -- without replacing it.  Radii that may now grow are re-checked by SafeRegionEvaluate, as after a setInput of a smaller cloud.
+    int64_t forgetOutside(const Vec3 &centre, double r) { const double c[3] = { centre.x, centre.y, centre.z }; return map_.forgetOutside(c, r); }
+    int64_t clearBall(const Vec3 &centre, double r) { const double c[3] = { centre.x, centre.y, centre.z }; return map_.clearBall(c, r); }
+    int64_t clearBox(const Vec3 &lo, const Vec3 &hi)
+    {
+        const double a[3] = { lo.x, lo.y, lo.z }, b[3] = { hi.x, hi.y, hi.z };
+        return map_.clearBox(a, b);
+    }
 
     // ---- queries ----
     bool checkTrajPtCol(const Vec3 &pt) { return clearance(pt) < 0.0; }                     // :412-416

@@ -111,6 +111,28 @@
  * insert launches; those stay asynchronous as for any copied frame, their source being a device buffer the library owns.
  * Uploads (pct_cloud_upload_*) are not filtered.  Captured plans are unaffected by such appends.
  *
+ * Removing points (pct_cloud_ring_remove_ball / _box / _indices): on a rolling-map cloud -- one with a live pct_cloud_ring_index -- a
+ * removal turns chosen slots below pct_cloud_size into REMOVED slots: the slot's three coordinates read back as NaN and its record
+ * is retired from the bucket table or the overflow queue.  From then on the cloud is observably the cloud that an upload of the same
+ * rows, with NaN in those rows, would have produced (the NaN-row equivalence), on every path and every algorithm: nearest neighbour,
+ * k-NN, radius counts (r = +/-inf included), radius lists, crop, inflation, the Bezier check, the control-point check,
+ * pct_rrt_expand_batch, the replan plan and the de-dup holders (a removed row is keyless and holds no voxel: the next append that
+ * offers its voxel keeps the point).  Nothing else changes: every other point keeps its index (ring slot + index_base);
+ * pct_cloud_size, the capacity and the ring cursor are unchanged; a later append overwrites a removed slot like any other (evicting
+ * it touches nothing); appends do not prefer removed slots.  A row that already holds a NaN coordinate -- removed, or the caller's
+ * own -- is left alone and not counted: *removed counts the rows this call changed.  Ball: inside <=> ((dx*dx + dy*dy) + dz*dz) <=
+ * r*r with dx = (double)x - centre[0] and so on, fp64 without contraction -- exactly the rows pct_radius_indices_q64(centre, r)
+ * lists; a negative r counts as |r|, a NaN r puts nothing inside.  Box: inside <=> lo[k] <= (double)p[k] <= hi[k] on all three
+ * axes.  A row with an infinite coordinate and no NaN is outside every finite region.  outside == 0 removes the rows inside the
+ * region, outside != 0 those outside it ("forget").  The empty-window rule: a removal that changes a row and leaves no row without
+ * a NaN coordinate makes the cloud empty -- size 0, cursor at slot 0, tables cleared, the index still configured, the de-dup mode
+ * kept -- so the reference's empty-cloud rule applies again (radius = max_radius - search_margin, corridor_finder.cpp:115-116).
+ * All forms are host forms ordered on the library's stream: an append still in flight is finished first and the removal sees its
+ * frame; each waits once on the host for {removed, live after} (a host-mapped word, polled).  Captured plans stay valid across
+ * removals, the reset included.  Records now die out of arrival order: dead records behind a live bucket head take bucket room
+ * until the head passes them (a bucket that looks full spills newcomers to the overflow queue: correct, slower); nothing is
+ * compacted.  A table sized automatically ignores removed rows when it is sized again.
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -219,6 +241,16 @@ int pct_cloud_ring_dedup(pct_cloud *c, double res);
  * PCT_ERR_INVALID while the mode is off. */
 int pct_cloud_ring_dedup_last(pct_cloud *c, int64_t *offered, int64_t *kept, uint8_t *flags, int64_t cap,
                               uint64_t *total_offered, uint64_t *total_kept);
+/* Removing points from a rolling-map cloud (the paragraph "Removing points" above).  PCT_ERR_INVALID: no rolling-map index, a NULL
+ * argument, a NaN in centre / lo / hi, or an index outside [index_base, index_base + size) -- the list is judged on the host first and
+ * nothing is removed then.  n = 0 or an empty cloud: PCT_OK with *removed = 0.  `removed` may be NULL.
+ * outside == 0: remove the points INSIDE the region; != 0: remove those OUTSIDE it ("forget") */
+int pct_cloud_ring_remove_ball(pct_cloud *c, const double centre[3], double r, int outside, int64_t *removed);
+int pct_cloud_ring_remove_box(pct_cloud *c, const double lo[3], const double hi[3], int outside, int64_t *removed);
+/* idx: n indices as the searches report them (index_base + slot), host memory; a slot named twice counts once */
+int pct_cloud_ring_remove_indices(pct_cloud *c, const uint32_t *idx, int64_t n, int64_t *removed);
+/* rows below size without a NaN coordinate, and size - that (one launch, one wait) */
+int pct_cloud_ring_live(pct_cloud *c, int64_t *live, int64_t *not_live);
 /* Zero-copy ingest.  pct_cloud_frame_buffer hands out a host-mapped staging buffer of at least `bytes` bytes (valid until the next
  * call that asks for a larger one, or pct_cloud_destroy); the producer -- a sensor driver, the deserialiser of a
  * sensor_msgs/PointCloud2 -- writes the frame's records there (x, y, z floats at the start of each stride-byte record) and
@@ -228,7 +260,8 @@ int pct_cloud_frame_buffer(pct_cloud *c, int64_t bytes, void **host_ptr);
 int pct_cloud_append_frame(pct_cloud *c, int64_t n, int64_t stride_bytes);
 
 /* diagnostics (tests): where ring slot `slot`'s record is filed: out = {where word, bucket of the slot's coordinates, head, tail of
- * that bucket (or of the overflow queue, bit 31 of the where word), id word stored at the filed position, overflow queue length} */
+ * that bucket (or of the overflow queue, bit 31 of the where word), id word stored at the filed position, overflow queue length}.
+ * A removed slot's where word is 0xFFFFFFFF (no record; the other words then mean nothing). */
 int pct_debug_ring_slot(pct_cloud *c, int64_t slot, uint32_t out[6]);
 
 /* Build / drop the uniform-cell index used by PCT_ALGO_GRID.  cell_size <= 0 picks one from

@@ -96,6 +96,40 @@ public:
         cloud_empty_ = pct_cloud_size(cloud_) == 0;
     }
 
+    // Removing points from the rolling map (pct_engine.h, paragraph "Removing points"): a removed point becomes a NaN row -- never a
+    // neighbour on any path -- and every other point keeps its index; a window left without a point becomes the empty cloud.  Each
+    // call returns the number of points it removed and needs enableRollingIndex.
+    //   forgetOutside   the window follows the drone: what the reference's lidar mode gets by replacing the planner's cloud with
+    //                   crop(global map, drone, max_dist) every frame (camera_sensor.cpp:133-145, sim_planning_demo.cpp:159-167)
+    //   clearBall / clearBox   withdraw a stale obstacle: a region the sensor now sees as free
+    //   removePoints    the indices a search reported (radiusSearchBatch, radiusIndices, nearest); a point named twice counts once
+    int64_t forgetOutside(const double centre[3], double r) { return removeBall(centre, r, 1); }
+    int64_t clearBall(const double centre[3], double r) { return removeBall(centre, r, 0); }
+    int64_t clearBox(const double lo[3], const double hi[3])
+    {
+        needRolling("clearBox");
+        int64_t removed = 0;
+        check(pct_cloud_ring_remove_box(cloud_, lo, hi, 0, &removed), "pct_cloud_ring_remove_box");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return removed;
+    }
+    int64_t removePoints(const uint32_t *indices, int64_t n)
+    {
+        needRolling("removePoints");
+        int64_t removed = 0;
+        check(pct_cloud_ring_remove_indices(cloud_, indices, n, &removed), "pct_cloud_ring_remove_indices");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return removed;
+    }
+    // points of the window that are still there (rows without a NaN coordinate); size() counts the removed slots too
+    int64_t liveSize()
+    {
+        needRolling("liveSize");
+        int64_t live = 0, gone = 0;
+        check(pct_cloud_ring_live(cloud_, &live, &gone), "pct_cloud_ring_live");
+        return live;
+    }
+
     // corridor_finder.cpp:113-133
     double radiusSearch(const double p[3])
     {
@@ -214,6 +248,18 @@ private:
     {
         if (status != PCT_OK && status != PCT_ERR_EMPTY)
             throw std::runtime_error(std::string(what) + ": " + pct_last_error());
+    }
+    void needRolling(const char *what) const
+    {
+        if (!rolling_) throw std::runtime_error(std::string(what) + ": the map has no rolling index (enableRollingIndex)");
+    }
+    int64_t removeBall(const double centre[3], double r, int outside)
+    {
+        needRolling(outside ? "forgetOutside" : "clearBall");
+        int64_t removed = 0;
+        check(pct_cloud_ring_remove_ball(cloud_, centre, r, outside, &removed), "pct_cloud_ring_remove_ball");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return removed;
     }
     pct_cloud *cloud_ = nullptr;
     int64_t capacity_ = 0;

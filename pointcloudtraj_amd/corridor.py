@@ -37,6 +37,9 @@ def lib():
         L.pct_corridor_enable_rolling.argtypes = [vp, C.c_float, vp]
         L.pct_corridor_append_input.argtypes = [vp, vp, C.c_int64, C.c_int64]
         L.pct_corridor_set_rolling_dedup.argtypes = [vp, C.c_double]
+        L.pct_corridor_forget_outside.argtypes = [vp, d3, C.c_double, C.POINTER(C.c_int64)]
+        L.pct_corridor_clear_ball.argtypes = [vp, d3, C.c_double, C.POINTER(C.c_int64)]
+        L.pct_corridor_clear_box.argtypes = [vp, d3, d3, C.POINTER(C.c_int64)]
         L.pct_corridor_set_pt.argtypes = [vp, d3, d3] + [C.c_double] * 7 + [C.c_int, C.c_double, C.c_double]
         L.pct_corridor_set_start_pt.argtypes = [vp, d3, d3]
         L.pct_corridor_reset_root.argtypes = [vp, d3]
@@ -119,6 +122,25 @@ class SafeRegionRrtStar:
     def setRollingDedup(self, res: float):
         """after enableRollingMap: appendInput keeps only points whose voxel of size res is new to the window (0 = off)"""
         self._chk(self.L.pct_corridor_set_rolling_dedup(self.h, float(res)))
+
+    def forgetOutside(self, centre, r: float) -> int:
+        """after enableRollingMap: remove every point farther than r from centre (the lidar-mode tick: appendInput -> forgetOutside
+        -> SafeRegionEvaluate -> SafeRegionRefine); returns the number of points removed"""
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_forget_outside(self.h, _d3(centre), float(r), C.byref(n)))
+        return n.value
+
+    def clearBall(self, centre, r: float) -> int:
+        """after enableRollingMap: remove the points within r of centre (a stale obstacle); returns the number removed"""
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_clear_ball(self.h, _d3(centre), float(r), C.byref(n)))
+        return n.value
+
+    def clearBox(self, lo, hi) -> int:
+        """after enableRollingMap: remove the points inside the axis-aligned box [lo, hi]; returns the number removed"""
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_clear_box(self.h, _d3(lo), _d3(hi), C.byref(n)))
+        return n.value
 
     def setPt(self, start, end, xl, xh, yl, yh, zl, zh, local_range, max_iter, sample_portion, goal_portion):
         self._chk(self.L.pct_corridor_set_pt(self.h, _d3(start), _d3(end), xl, xh, yl, yh, zl, zh, local_range, int(max_iter),

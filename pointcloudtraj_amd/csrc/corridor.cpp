@@ -75,6 +75,18 @@ int pct_corridor_append_input(pct_corridor *c, const void *points, int64_t n, in
     return guarded([&] { c->impl->appendInput(points, n, stride_bytes); });
 }
 int pct_corridor_set_rolling_dedup(pct_corridor *c, double res) { return guarded([&] { c->impl->setRollingDedup(res); }); }
+int pct_corridor_forget_outside(pct_corridor *c, const double centre[3], double r, int64_t *removed)
+{
+    return guarded([&] { const int64_t n = c->impl->forgetOutside(v3(centre), r); if (removed) *removed = n; });
+}
+int pct_corridor_clear_ball(pct_corridor *c, const double centre[3], double r, int64_t *removed)
+{
+    return guarded([&] { const int64_t n = c->impl->clearBall(v3(centre), r); if (removed) *removed = n; });
+}
+int pct_corridor_clear_box(pct_corridor *c, const double lo[3], const double hi[3], int64_t *removed)
+{
+    return guarded([&] { const int64_t n = c->impl->clearBox(v3(lo), v3(hi)); if (removed) *removed = n; });
+}
 int pct_corridor_set_pt(pct_corridor *c, const double start[3], const double end[3], double xl, double xh, double yl, double yh,
                         double zl, double zh, double local_range, int max_iter, double sample_portion, double goal_portion)
 {

@@ -28,6 +28,7 @@
 #include "pyramid.hpp"
 #include "ring.hpp"
 #include "ring_dedup.hpp"
+#include "ring_remove.hpp"
 #include "brute2.hpp"
 #include "knn.hpp"
 #include "rsearch.hpp"
@@ -273,6 +274,15 @@ struct pct_cloud {
     uint32_t *h_ring_status = nullptr, *d_ring_status = nullptr;      // host-mapped {overrun flag, overflow-queue length}
     int64_t ring_cfg_count = 0;                                       // points in the window when the table was last sized
     int ring_appends_since_cfg = 0;
+    // removing points (ring_remove.hpp, pct_cloud_ring_remove_*): removals since the last upload (the sizing box and a refile then
+    // leave the removed rows out), the device words a removal's blocks meet on, the host-mapped {sequence, removed, live} the host
+    // polls, and the staging of an index list
+    bool ring_removed_any = false;
+    RingRemoveMeet *d_rm_meet = nullptr;
+    uint32_t *h_rm_word = nullptr, *d_rm_word = nullptr;
+    uint32_t rm_seq = 0;
+    uint32_t *d_rm_list = nullptr;
+    size_t rm_list_cap = 0;
     // de-duplicating appends (ring_dedup.hpp, pct_cloud_ring_dedup): voxel size (0 = off), the frame filter's scratch -- key table,
     // per-point table slot / rank, tile totals, kept flags, the compacted frame -- and the host-mapped {sequence, survivors} pair
     double dd_res = 0.0;
@@ -856,7 +866,7 @@ int cloud_bbox_cached(pct_cloud *c)
     const int64_t n = c->count;
     const int bblocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
     float *d_part = c->d_bbox;                                         // 1024 x 6 floats, allocated with the cloud
-    bbox_partial_kernel<<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
+    bbox_partial_kernel<false><<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
     std::vector<float> part((size_t)bblocks * 6);
     hipError_t e = hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(float), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -1530,6 +1540,8 @@ int pct_cloud_destroy(pct_cloud *c)
     if (c->h_gbcheck) (void)hipHostFree(c->h_gbcheck);
     dev_free(c->ring_ht); dev_free(c->ring_slots); dev_free(c->ring_ovf); dev_free(c->ring_where); dev_free(c->ring_st);
     if (c->h_ring_status) (void)hipHostFree(c->h_ring_status);
+    dev_free(c->d_rm_meet); dev_free(c->d_rm_list);
+    if (c->h_rm_word) (void)hipHostFree(c->h_rm_word);
     dev_free(c->dd_keys); dev_free(c->dd_vals); dev_free(c->dd_pslot); dev_free(c->dd_rank); dev_free(c->dd_tile); dev_free(c->dd_flags); dev_free(c->dd_out);
     if (c->h_dd_word) (void)hipHostFree(c->h_dd_word);
     replan_ctx_free(c->rp);
@@ -1560,6 +1572,7 @@ int pct_cloud_upload_aos(pct_cloud *c, const void *pts, int64_t n, int64_t strid
     HIPCHK(hipStreamSynchronize(g_stream));    // the host buffer is the caller's again
     c->count = n;
     c->ring_next = n % std::max<int64_t>(c->cap, 1);
+    c->ring_removed_any = false;
     return after_replace(c);
 }
 
@@ -1596,6 +1609,7 @@ int pct_cloud_upload_soa_dev(pct_cloud *c, const float *d_x, const float *d_y, c
     }
     c->count = n;
     c->ring_next = n % std::max<int64_t>(c->cap, 1);
+    c->ring_removed_any = false;
     return after_replace(c);
 }
 
@@ -1708,7 +1722,7 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     const int bblocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
     PCTCHK(ensure_stage(c, sizeof(float) * (size_t)bblocks * 6));     // the upload staging buffer is idle here: no allocation per build
     float *d_part = reinterpret_cast<float *>(c->d_stage);
-    bbox_partial_kernel<<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
+    bbox_partial_kernel<false><<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
     std::vector<float> part((size_t)bblocks * 6);
     hipError_t e = hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(float), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -2575,6 +2589,7 @@ int pct_cloud_upload_aos_dev(pct_cloud *c, const void *d_pts, int64_t n, int64_t
     }
     c->count = n;
     c->ring_next = n % std::max<int64_t>(c->cap, 1);
+    c->ring_removed_any = false;
     return after_replace(c);
 }
 

@@ -877,6 +877,8 @@ __global__ __launch_bounds__(256) void block_corner_kernel(GridDesc G, const uin
 }
 
 // per-block min/max -> partials[block][6]
+// SKIP_REMOVED: rows whose three coordinates are all NaN (points removed from a rolling map, ring_remove.hpp) are left out
+template <bool SKIP_REMOVED = false>
 __global__ __launch_bounds__(256) void bbox_partial_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                            const float *__restrict__ z, uint32_t n,
                                                            float *__restrict__ partials)
@@ -886,6 +888,7 @@ __global__ __launch_bounds__(256) void bbox_partial_kernel(const float *__restri
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float v[3] = { x[i], y[i], z[i] };
+        if (SKIP_REMOVED && v[0] != v[0] && v[1] != v[1] && v[2] != v[2]) continue;
 #pragma unroll
         for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], v[k]); hi[k] = fmaxf(hi[k], v[k] == v[k] ? v[k] : __builtin_huge_valf()); }   // fmin / fmax drop a NaN: it shows as hi = +inf
     }

@@ -36,11 +36,15 @@ struct RingDesc {
     int gx, gy, gz;          // bucket table dimensions, powers of two
     int lx, ly;              // log2(gx), log2(gy)
     uint32_t K;              // records per bucket (power of two)
-    // overflow queue capacity - 1.  The queue holds one entry per live spilled point plus dead entries its head has not passed yet;
-    // the head is blocked only by a live entry, and entries behind a live head that are already dead can only belong to the same
-    // insert launch as that head entry (younger launches are evicted later), so its length never exceeds capacity + one launch
-    // <= 2 x cloud capacity: the table is a power of two >= 2 x capacity + 16.  `status` (host-mapped, two words) still gets
-    // {1, length} from a launch that would overrun it and {0, length} otherwise: the host rebuilds the index from the SoA arrays.
+    // overflow queue capacity - 1.  The queue holds one entry per live spilled point plus dead entries its head has not passed yet.
+    // Only appends (and a refile of the whole window, onto cleared tables) file records, and they file in ring order: a record filed
+    // after the entry E was filed belongs to one of the cap - 1 slots the cursor visits before it returns to E's slot and E is
+    // evicted.  Every retiring launch (an append's eviction pass, a removal: ring_remove.hpp) leaves the head on a live entry or on
+    // the tail, so while E is the head and alive the queue holds at most cap entries, whatever order the records behind E died in
+    // -- removal kills records out of arrival order, and that argument never asked for the order; and an insert launch that finds
+    // the head on the tail adds at most its own n <= cap.  Removal files nothing, so it cannot lengthen the queue.  The table is a
+    // power of two >= 2 x capacity + 16.  `status` (host-mapped, two words) still gets {1, length} from a launch that would overrun
+    // it and {0, length} otherwise: the host rebuilds the index from the SoA arrays.
     uint32_t ovf_mask;
     uint32_t *status;
 };
@@ -79,7 +83,8 @@ __device__ __forceinline__ uint32_t ring_bucket_of(const RingDesc &R, float x, f
 // inside its bucket.  Eviction goes straight to the record (no search) and marks it dead; heads then advance past dead records.
 constexpr uint32_t kRingInOvf = 0x80000000u;
 constexpr uint32_t kRingDead = 0xFFFFFFFFu;      // a record's id word once its point has left the window
-constexpr uint32_t kRingUnfiled = 0xFFFFFFFFu;   // where[] of a point the overflow queue had no room for (an error state the host repairs)
+constexpr uint32_t kRingUnfiled = 0xFFFFFFFFu;   // where[] of a slot that has no record: a point the overflow queue had no room for (an error state the
+                                                 // host repairs), or a removed point (ring_remove.hpp: its record was retired when it was removed)
 
 // file one point under its bucket (or the overflow queue when the bucket is full); heads do not move while this runs
 __device__ __forceinline__ void ring_file(const RingDesc &R, float px, float py, float pz, uint32_t slot, uint2 *__restrict__ ht,
@@ -113,45 +118,41 @@ __device__ __forceinline__ void ring_file(const RingDesc &R, float px, float py,
     where[slot] = (pos & ~kRingInOvf) | kRingInOvf;
 }
 
-// Pass 1 of an append: one thread per ring slot about to be overwritten retires the point the slot holds -- its record is
-// marked dead where it was filed, then the owning bucket's head moves past every dead record in front (several threads may try:
-// the compare-and-swap lets each step happen once; a bucket holds at most 32 records).  The overflow queue's head is moved once
-// per launch, by the last block (below).  No record is filed while this runs.
-__global__ __launch_bounds__(256) void ring_evict_kernel(RingDesc R, const float *__restrict__ x, const float *__restrict__ y,
-                                                         const float *__restrict__ z, uint32_t slot0, uint32_t n,
-                                                         uint2 *__restrict__ ht, float4 *__restrict__ slots, float4 *__restrict__ ovf,
-                                                         const uint32_t *__restrict__ where, RingState *__restrict__ st)
+// Retire the record of ring slot `slot`, whose where word is w and whose coordinates (as they were filed) are (px, py, pz): the
+// record is marked dead where it was filed (no search), then the owning bucket's head moves past every dead record in front
+// (several threads may try: the compare-and-swap lets each step happen once).  The overflow queue's head is not moved here: the
+// launch's last block does that (ring_queue_head_advance).  No record may be filed while this runs.  Shared by the eviction pass
+// of an append and by the removal kernels (ring_remove.hpp).
+__device__ __forceinline__ void ring_retire_record(const RingDesc &R, uint32_t w, float px, float py, float pz, uint2 *__restrict__ ht,
+                                                   float4 *__restrict__ slots, float4 *__restrict__ ovf)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    // the overflow queue is either empty for the whole launch (nothing is filed while it runs) or needs its head moved afterwards
-    const uint32_t q_tail = st->ovf_tail;
-    const bool queue_in_use = q_tail != st->ovf_head;
-    if (i < n) {
-        const uint32_t slot = slot0 + i;
-        const uint32_t w = where[slot];
-        if (w == kRingUnfiled) {
-            // never filed (queue overrun): nothing to retire
-        } else if (w & kRingInOvf) {
-            uint32_t *idw = reinterpret_cast<uint32_t *>(&ovf[w & R.ovf_mask].w);
-            __hip_atomic_store(idw, kRingDead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            const uint32_t b = ring_bucket_of(R, x[slot], y[slot], z[slot]);
-            float4 *base = slots + (size_t)b * R.K;
-            __hip_atomic_store(reinterpret_cast<uint32_t *>(&base[w & (R.K - 1)].w), kRingDead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t tail = ht[b].y;
-            uint32_t h = __hip_atomic_load(&ht[b].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            while (h != tail) {
-                const uint32_t *hw = reinterpret_cast<const uint32_t *>(&base[h & (R.K - 1)].w);
-                if (__hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kRingDead) break;
-                const uint32_t seen = atomicCAS(&ht[b].x, h, h + 1u);
-                h = seen == h ? h + 1u : seen;
-            }
+    if (w == kRingUnfiled) {
+        // never filed (queue overrun), or removed already: nothing to retire
+    } else if (w & kRingInOvf) {
+        uint32_t *idw = reinterpret_cast<uint32_t *>(&ovf[w & R.ovf_mask].w);
+        __hip_atomic_store(idw, kRingDead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        const uint32_t b = ring_bucket_of(R, px, py, pz);
+        float4 *base = slots + (size_t)b * R.K;
+        __hip_atomic_store(reinterpret_cast<uint32_t *>(&base[w & (R.K - 1)].w), kRingDead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t tail = ht[b].y;
+        uint32_t h = __hip_atomic_load(&ht[b].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        while (h != tail) {
+            const uint32_t *hw = reinterpret_cast<const uint32_t *>(&base[h & (R.K - 1)].w);
+            if (__hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kRingDead) break;
+            const uint32_t seen = atomicCAS(&ht[b].x, h, h + 1u);
+            h = seen == h ? h + 1u : seen;
         }
     }
-    if (!queue_in_use) return;
-    // The queue's head is moved by ONE block, the last to finish marking (a ticket per block): 256 entries per step, the dead
-    // prefix measured with ballots.  (Every evicting thread advancing the head itself, as the buckets do, serialises tens of
-    // thousands of compare-and-swaps on one word once the queue is long: 59 s for a 150 k-entry queue in the fuzz test.)
+}
+
+// The overflow queue's head is moved by ONE block of a retiring launch, the last to finish marking (a ticket per block): 256
+// entries per step, the dead prefix measured block-wide.  Every thread of every block of the launch calls this after its marking,
+// with the queue's tail as the launch found it.  (Every retiring thread advancing the head itself, as the buckets do, serialises
+// tens of thousands of compare-and-swaps on one word once the queue is long: 59 s for a 150 k-entry queue in the fuzz test.)
+__device__ __forceinline__ void ring_queue_head_advance(const RingDesc &R, const float4 *__restrict__ ovf, RingState *__restrict__ st,
+                                                        uint32_t q_tail)
+{
     __shared__ uint32_t s_last, s_head;
     __threadfence();
     __syncthreads();
@@ -181,6 +182,26 @@ __global__ __launch_bounds__(256) void ring_evict_kernel(RingDesc R, const float
         if (adv < 256u) break;
     }
     if (threadIdx.x == 0) __hip_atomic_store(&st->ovf_head, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Pass 1 of an append: one thread per ring slot about to be overwritten retires the point the slot holds (ring_retire_record; a
+// bucket holds at most R.K records).  The overflow queue's head is moved once per launch, by the last block.  No record is filed
+// while this runs.
+__global__ __launch_bounds__(256) void ring_evict_kernel(RingDesc R, const float *__restrict__ x, const float *__restrict__ y,
+                                                         const float *__restrict__ z, uint32_t slot0, uint32_t n,
+                                                         uint2 *__restrict__ ht, float4 *__restrict__ slots, float4 *__restrict__ ovf,
+                                                         const uint32_t *__restrict__ where, RingState *__restrict__ st)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    // the overflow queue is either empty for the whole launch (nothing is filed while it runs) or needs its head moved afterwards
+    const uint32_t q_tail = st->ovf_tail;
+    const bool queue_in_use = q_tail != st->ovf_head;
+    if (i < n) {
+        const uint32_t slot = slot0 + i;
+        ring_retire_record(R, where[slot], x[slot], y[slot], z[slot], ht, slots, ovf);
+    }
+    if (!queue_in_use) return;
+    ring_queue_head_advance(R, ovf, st, q_tail);
 }
 
 // Pass 2: store the new frame in the SoA arrays and file it.  `src` = the frame, array of structures (x,y,z at byte offsets
@@ -216,12 +237,16 @@ __global__ __launch_bounds__(256) void ring_insert_kernel(RingDesc R, float *__r
 __global__ __launch_bounds__(256) void ring_refile_kernel(RingDesc R, const float *__restrict__ x, const float *__restrict__ y,
                                                           const float *__restrict__ z, uint32_t slot0, uint32_t n,
                                                           uint2 *__restrict__ ht, float4 *__restrict__ slots, float4 *__restrict__ ovf,
-                                                          uint32_t *__restrict__ where, RingState *__restrict__ st)
+                                                          uint32_t *__restrict__ where, RingState *__restrict__ st, int skip_removed)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t slot = slot0 + i;
-    ring_file(R, x[slot], y[slot], z[slot], slot, ht, slots, ovf, where, st);
+    const float px = x[slot], py = y[slot], pz = z[slot];
+    // skip_removed: points have been removed from this window since its last upload (ring_remove.hpp).  A removed slot -- three
+    // NaN coordinates -- keeps no record (a NaN record answers no query; thousands of them would share one bucket and spill)
+    if (skip_removed && px != px && py != py && pz != pz) { where[slot] = kRingUnfiled; return; }
+    ring_file(R, px, py, pz, slot, ht, slots, ovf, where, st);
 }
 
 __global__ void ring_set_count_kernel(RingState *st, uint32_t count) { st->count = count; }

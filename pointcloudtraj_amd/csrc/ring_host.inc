@@ -18,7 +18,7 @@ int log2_ceil_pow2(int64_t v, int *lg)
     return 1 << l;
 }
 
-// bounding box of the points currently in the SoA arrays (device reduction, one read-back)
+// bounding box of the points currently in the SoA arrays (device reduction, one read-back); lo > hi: no row was looked at
 int cloud_bbox(pct_cloud *c, float lo[3], float hi[3])
 {
     const int64_t n = c->count;
@@ -26,7 +26,9 @@ int cloud_bbox(pct_cloud *c, float lo[3], float hi[3])
     const int bblocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
     float *d_part = nullptr;
     PCTCHK(dev_alloc(&d_part, (size_t)bblocks * 6));
-    bbox_partial_kernel<<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
+    // removals since the last upload: the removed rows (three NaNs) are no data to size a table from
+    if (c->ring_removed_any) bbox_partial_kernel<true><<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
+    else bbox_partial_kernel<false><<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
     std::vector<float> part((size_t)bblocks * 6);
     hipError_t e = hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(float), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -106,7 +108,7 @@ int ring_refile_all(pct_cloud *c)
     HIPCHK(hipMemsetAsync(c->ring_st, 0, sizeof(RingState), s));
     if (c->count > 0)
         ring_refile_kernel<<<ceil_div(c->count, 256), 256, 0, s>>>(c->R, c->x, c->y, c->z, 0u, (uint32_t)c->count, c->ring_ht, c->ring_slots,
-                                                                   c->ring_ovf, c->ring_where, c->ring_st);
+                                                                   c->ring_ovf, c->ring_where, c->ring_st, c->ring_removed_any ? 1 : 0);
     ring_set_count_kernel<<<1, 1, 0, s>>>(c->ring_st, (uint32_t)c->count);
     HIPCHK(hipGetLastError());
     return PCT_OK;
@@ -122,6 +124,7 @@ int ring_setup_from_cloud(pct_cloud *c)
         float lo[3], hi[3];
         PCTCHK(cloud_bbox(c, lo, hi));
         for (int k = 0; k < 3; k++) {
+            if (c->ring_removed_any && lo[k] > hi[k]) { ext[k] = 0.0; continue; }     // nothing but removed rows
             if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(PCT_ERR_INVALID, "cloud holds non-finite coordinates: give pct_cloud_ring_index an extent");
             ext[k] = std::max((double)hi[k] - (double)lo[k], 0.0);
         }
@@ -938,6 +941,170 @@ int pct_plan_last_run_us(pct_plan *p, double us[4])
 {
     if (!p || !us) return fail(PCT_ERR_INVALID, "bad arguments");
     for (int k = 0; k < 4; k++) us[k] = p->run_us[k];
+    return PCT_OK;
+}
+
+}  // extern "C"
+
+// ---- removing points from the rolling map (ring_remove.hpp) ----------------------------------------------------------------------
+namespace {
+
+int ring_remove_ensure(pct_cloud *c)
+{
+    if (!c->h_rm_word) {
+        PCTCHK(mapped_alloc(&c->h_rm_word, &c->d_rm_word, 4));
+        for (int k = 0; k < 4; k++) c->h_rm_word[k] = 0;
+    }
+    if (!c->d_rm_meet) {
+        PCTCHK(dev_alloc(&c->d_rm_meet, 1));
+        HIPCHK(hipMemsetAsync(c->d_rm_meet, 0, sizeof(RingRemoveMeet), g_stream));
+    }
+    return PCT_OK;
+}
+
+// the ONE host wait of a removal: {removed, live after}, polled in host-mapped memory as the de-dup filter's survivor count is
+int ring_remove_wait(pct_cloud *c, uint32_t seq, int64_t *removed, int64_t *live)
+{
+    bool seen = false;
+    if (poll_results()) {
+        const volatile uint32_t *w = c->h_rm_word;
+        for (long spins = 0; spins < 200000000l && !seen; spins++) {
+            if (w[0] == seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); seen = true; }
+            else __builtin_ia32_pause();
+        }
+    }
+    if (!seen) HIPCHK(hipStreamSynchronize(g_stream));
+    if (c->h_rm_word[0] != seq) return fail(PCT_ERR_HIP, "the removal finished without its sequence word (%u != %u)", c->h_rm_word[0], seq);
+    *removed = (int64_t)c->h_rm_word[1];
+    *live = (int64_t)c->h_rm_word[2];
+    if (*removed + *live > c->count) return fail(PCT_ERR_INTERNAL, "a removal counted %lld + %lld rows of %lld", (long long)*removed, (long long)*live, (long long)c->count);
+    return PCT_OK;
+}
+
+// what every removal entry point asks first: a live rolling-map index, the append in flight finished (the removal sees its frame)
+int ring_remove_begin(pct_cloud *c, const char *what)
+{
+    if (!c->ring_on) return fail(PCT_ERR_INVALID, "%s needs the rolling-map index (pct_cloud_ring_index)", what);
+    PCTCHK(ring_finish_pending(c));
+    if (!c->ring_ready && c->count > 0) return fail(PCT_ERR_INVALID, "%s: the cloud has no live rolling-map index", what);
+    return PCT_OK;
+}
+
+// bookkeeping behind a removal's wait.  A window left without a single row free of NaN becomes the empty cloud: what an upload of
+// zero points does to a rolling-map cloud (size 0, cursor at slot 0, tables cleared; the index stays configured and de-dup stays on,
+// captured plans stay valid: no pointer, table shape or workspace changes).
+int ring_remove_finish(pct_cloud *c, int64_t removed, int64_t live)
+{
+    if (removed > 0) {
+        c->ring_removed_any = true;
+        c->content_epoch++;
+        if (live == 0) {
+            c->count = 0;
+            c->ring_next = 0;
+            c->ring_removed_any = false;
+            PCTCHK(ring_refile_all(c));
+            HIPCHK(hipStreamSynchronize(g_stream));
+        }
+    }
+    return note_mutation(c);
+}
+
+int ring_remove_region(pct_cloud *c, const RingRegion &G, int64_t *removed_out)
+{
+    if (removed_out) *removed_out = 0;
+    if (c->count == 0) return PCT_OK;
+    PCTCHK(ring_remove_ensure(c));
+    const uint32_t seq = ++c->rm_seq;
+    ring_remove_region_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, G, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht, c->ring_slots,
+                                                                            c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->d_rm_word, seq);
+    HIPCHK(hipGetLastError());
+    int64_t removed = 0, live = 0;
+    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
+    if (removed_out) *removed_out = removed;
+    return ring_remove_finish(c, removed, live);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pct_cloud_ring_remove_ball(pct_cloud *c, const double centre[3], double r, int outside, int64_t *removed)
+{
+    if (!c || !centre) return fail(PCT_ERR_INVALID, "bad ring_remove_ball arguments");
+    if (std::isnan(centre[0]) || std::isnan(centre[1]) || std::isnan(centre[2])) return fail(PCT_ERR_INVALID, "ring_remove_ball: the centre holds a NaN");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_remove_ball"));
+    RingRegion G{};
+    for (int k = 0; k < 3; k++) G.a[k] = centre[k];
+    G.r2 = r * r;                               // a negative r counts as |r|; a NaN r puts nothing inside
+    G.kind = 0;
+    G.outside = outside ? 1 : 0;
+    return ring_remove_region(c, G, removed);
+}
+
+int pct_cloud_ring_remove_box(pct_cloud *c, const double lo[3], const double hi[3], int outside, int64_t *removed)
+{
+    if (!c || !lo || !hi) return fail(PCT_ERR_INVALID, "bad ring_remove_box arguments");
+    for (int k = 0; k < 3; k++)
+        if (std::isnan(lo[k]) || std::isnan(hi[k])) return fail(PCT_ERR_INVALID, "ring_remove_box: a corner holds a NaN");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_remove_box"));
+    RingRegion G{};
+    for (int k = 0; k < 3; k++) { G.a[k] = lo[k]; G.b[k] = hi[k]; }
+    G.kind = 1;
+    G.outside = outside ? 1 : 0;
+    return ring_remove_region(c, G, removed);
+}
+
+int pct_cloud_ring_remove_indices(pct_cloud *c, const uint32_t *idx, int64_t n, int64_t *removed_out)
+{
+    if (!c || n < 0 || (n > 0 && !idx)) return fail(PCT_ERR_INVALID, "bad ring_remove_indices arguments");
+    if (removed_out) *removed_out = 0;
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_remove_indices"));
+    if (n == 0) return PCT_OK;
+    // the whole list is judged before anything is removed
+    for (int64_t i = 0; i < n; i++)
+        if ((int64_t)idx[i] < c->index_base || (int64_t)idx[i] >= c->index_base + c->count)
+            return fail(PCT_ERR_INVALID, "ring_remove_indices: entry %lld = %u is outside [%lld, %lld)", (long long)i, idx[i], (long long)c->index_base,
+                        (long long)(c->index_base + c->count));
+    if (n > 0xFFFFFFF0ll) return fail(PCT_ERR_INVALID, "ring_remove_indices: the list is too long");
+    PCTCHK(ring_remove_ensure(c));
+    if ((size_t)n > c->rm_list_cap) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        dev_free(c->d_rm_list);
+        c->rm_list_cap = 0;
+        size_t cap = 1024;
+        while (cap < (size_t)n) cap <<= 1;
+        PCTCHK(dev_alloc(&c->d_rm_list, cap));
+        c->rm_list_cap = cap;
+    }
+    std::vector<uint32_t> slots;
+    try { slots.resize((size_t)n); } catch (const std::bad_alloc &) { return fail(PCT_ERR_ALLOC, "host allocation failed"); }
+    for (int64_t i = 0; i < n; i++) slots[(size_t)i] = idx[i] - (uint32_t)c->index_base;
+    HIPCHK(hipMemcpyAsync(c->d_rm_list, slots.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, g_stream));
+    const uint32_t seq = ++c->rm_seq;
+    ring_remove_list_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(c->R, c->d_rm_list, (uint32_t)n, c->x, c->y, c->z, c->ring_ht, c->ring_slots, c->ring_ovf,
+                                                                   c->ring_where, c->ring_st, c->d_rm_meet);
+    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_rm_meet, c->d_rm_word, seq);
+    HIPCHK(hipGetLastError());
+    int64_t removed = 0, live = 0;
+    PCTCHK(ring_remove_wait(c, seq, &removed, &live));         // (the list has left `slots` by now: the copy precedes the kernels)
+    if (removed_out) *removed_out = removed;
+    return ring_remove_finish(c, removed, live);
+}
+
+int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
+{
+    if (!c || !live_out || !not_live) return fail(PCT_ERR_INVALID, "bad ring_live arguments");
+    *live_out = *not_live = 0;
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_live"));
+    if (c->count == 0) return PCT_OK;
+    PCTCHK(ring_remove_ensure(c));
+    const uint32_t seq = ++c->rm_seq;
+    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_rm_meet, c->d_rm_word, seq);
+    HIPCHK(hipGetLastError());
+    int64_t removed = 0, live = 0;
+    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
+    *live_out = live;
+    *not_live = c->count - live;
     return PCT_OK;
 }
 

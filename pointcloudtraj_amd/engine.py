@@ -135,6 +135,11 @@ def lib():
         L.pct_cloud_ring_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(i64)]
         L.pct_cloud_ring_dedup.argtypes = [vp, C.c_double]
         L.pct_cloud_ring_dedup_last.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), vp, i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.pct_cloud_ring_remove_ball.argtypes = [vp, f64p, C.c_double, C.c_int, C.POINTER(i64)]
+        L.pct_cloud_ring_remove_box.argtypes = [vp, f64p, f64p, C.c_int, C.POINTER(i64)]
+        L.pct_cloud_ring_remove_indices.argtypes = [vp, u32p, i64, C.POINTER(i64)]
+        L.pct_cloud_ring_live.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+        L.pct_debug_ring_slot.argtypes = [vp, i64, C.POINTER(C.c_uint32)]
         L.pct_ctrl_points_check.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                             i64, f64p, f64p, f64p, u32p]
         L.pct_plan_create_replan.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
@@ -319,6 +324,41 @@ class Cloud:
         if off.value:
             _chk(lib().pct_cloud_ring_dedup_last(self._h, None, None, flags.ctypes.data, len(flags), None, None))
         return dict(offered=off.value, kept=kept.value, flags=flags.astype(bool), total_offered=toff.value, total_kept=tkept.value)
+
+    def ring_remove_ball(self, centre, r: float, outside: bool = False) -> int:
+        """remove the points within r of centre from the rolling map (outside = True: those farther than r, "forget"); the removed
+        points become NaN rows, every other point keeps its index (pct_cloud_ring_remove_ball); returns the number removed"""
+        q = np.ascontiguousarray(centre, np.float64).reshape(3)
+        n = C.c_int64()
+        _chk(lib().pct_cloud_ring_remove_ball(self._h, _ptr(q), float(r), int(bool(outside)), C.byref(n)))
+        return n.value
+
+    def ring_remove_box(self, lo, hi, outside: bool = False) -> int:
+        """remove the points with lo <= p <= hi on all three axes (outside = True: every other point); returns the number removed"""
+        a, b = np.ascontiguousarray(lo, np.float64).reshape(3), np.ascontiguousarray(hi, np.float64).reshape(3)
+        n = C.c_int64()
+        _chk(lib().pct_cloud_ring_remove_box(self._h, _ptr(a), _ptr(b), int(bool(outside)), C.byref(n)))
+        return n.value
+
+    def ring_remove_indices(self, indices) -> int:
+        """remove the points with these indices (as the searches report them); a point named twice counts once; returns the number
+        removed.  An index outside the window raises and removes nothing."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        n = C.c_int64()
+        _chk(lib().pct_cloud_ring_remove_indices(self._h, _ptr(idx), len(idx), C.byref(n)))
+        return n.value
+
+    def ring_live(self):
+        """(live, not live): rows of the window without a NaN coordinate, and len(self) minus that (pct_cloud_ring_live)"""
+        a, b = C.c_int64(), C.c_int64()
+        _chk(lib().pct_cloud_ring_live(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def debug_ring_slot(self, slot: int):
+        """pct_debug_ring_slot: (where word, bucket, head, tail, id word at the filed position, overflow-queue length) -- test hook"""
+        out = (C.c_uint32 * 6)()
+        _chk(lib().pct_debug_ring_slot(self._h, int(slot), out))
+        return tuple(int(v) for v in out)
 
     def reserve_queries(self, Q: int):
         _chk(lib().pct_cloud_reserve_queries(self._h, int(Q)))

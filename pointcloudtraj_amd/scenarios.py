@@ -169,6 +169,68 @@ def run_rolling_commit_scenario(finder, window=40000, expand=800, refine=300, co
     return out
 
 
+def run_lidar_window_scenario(finder, window=40000, expand=800, refine=300, commits=5, radius=8.0, info=None, clock=None):
+    """The planner's tick in the reference's LIDAR mode: every frame the planner's cloud is crop(global map, drone, max_dist)
+    (camera_sensor.cpp:133-145), handed to setInput as a replacement (sim_planning_demo.cpp:159-167), so points that leave the
+    sensing range vanish.  Same phases, frames and commit points as run_rolling_commit_scenario.
+
+    A finder with forgetOutside (its rolling map enabled by the caller, with setRollingDedup on) keeps a window instead: per frame
+    appendInput(frame) -> forgetOutside(sensor position, radius) -> Evaluate -> Refine -- the window then holds that frame's points
+    without being replaced.  A finder without it (the CPU oracle) gets setInput(frame): the reference's lidar mode itself.
+    info (a dict, optional) receives the frame sizes and the points forgotten per frame; clock as in run_rolling_commit_scenario."""
+    import time
+    p = PARAMS
+    out = []
+    full = synth.pillar_map()
+    rolling = hasattr(finder, "forgetOutside")
+    sizes, forgotten = [], []
+
+    def timed(name, fn, *a):
+        t0 = time.perf_counter()
+        r = fn(*a)
+        if clock is not None:
+            clock.append((name, time.perf_counter() - t0))
+        return r
+
+    def feed_frame(centre, seed):
+        frame = rolling_frame(full, centre, seed, radius)
+        sizes.append(len(frame))
+        if rolling:
+            timed("append", finder.appendInput, frame)
+            forgotten.append(timed("forget", finder.forgetOutside, centre, radius))
+        else:
+            timed("set_input", finder.setInput, frame)
+
+    def snap():
+        out.append((*finder.getPath(), finder.status()))
+
+    finder.setParam(p["safety_margin"], p["search_margin"], p["max_radius"], p["sensing_range"])
+    feed_frame(START, 7)
+    finder.reset()
+    finder.setPt(START, GOAL, *BOUNDS, p["sensing_range"], p["max_samples"], p["sample_portion"], p["goal_portion"])
+    timed("expansion", finder.SafeRegionExpansion, expand)
+    snap()
+    timed("refine", finder.SafeRegionRefine, refine)
+    snap()
+    for k in range(commits):
+        path, _ = finder.getPath()
+        if not finder.status()["path_exists"] or len(path) < 4:
+            break
+        target = tuple(float(v) for v in path[2])
+        finder.setStartPt(target, GOAL)
+        finder.resetRoot(target)
+        timed("refine", finder.SafeRegionRefine, refine // 2)
+        snap()
+        feed_frame(target, 8 + k)
+        timed("evaluate", finder.SafeRegionEvaluate)
+        snap()
+        timed("refine", finder.SafeRegionRefine, refine // 2)
+        snap()
+    if info is not None:
+        info.update(frames=sizes, forgotten=forgotten)
+    return out
+
+
 def timed_scenario(finder, cloud1, expand=1500, refine=400):
     """run_scenario with wall-clock milliseconds per planner phase (bench.py / scripts/probe_corridor.py)"""
     import time
