@@ -12,6 +12,8 @@
 #ifndef PCT_CORRIDOR_H
 #define PCT_CORRIDOR_H
 #include <stdint.h>
+
+#include "pct_engine.h"     /* pct_depth_view */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -46,6 +48,15 @@ int pct_corridor_set_rolling_dedup(pct_corridor *c, double res);
 int pct_corridor_forget_outside(pct_corridor *c, const double centre[3], double r, int64_t *removed);
 int pct_corridor_clear_ball(pct_corridor *c, const double centre[3], double r, int64_t *removed);
 int pct_corridor_clear_box(pct_corridor *c, const double lo[3], const double hi[3], int64_t *removed);
+/* after pct_corridor_enable_rolling: depth images as the map's input (pct_engine.h, paragraph "Depth images").  The rgbd tick is
+ * clear_seen_through -> append_depth -> evaluate -> refine with the same image: the carve removes what the image sees through
+ * (*removed, may be NULL), the append un-projects the valid pixels on the device and files them as append_input files a point
+ * frame (*kept, may be NULL = the points the window took). */
+int pct_corridor_clear_seen_through(pct_corridor *c, const pct_depth_view *view, const float *image, double margin, int64_t *removed);
+int pct_corridor_append_depth(pct_corridor *c, const pct_depth_view *view, const float *image, double max_depth, int64_t *kept);
+/* the engine's handle of the finder's obstacle cloud (SafeRegionRrtStar::obstacleMap().handle()), for the read-only calls of
+ * pct_engine.h -- pct_radius_crop reads the window back; owned by the finder, replaced by a set_input that has to grow the map */
+int pct_corridor_cloud(pct_corridor *c, pct_cloud **cloud);
 int pct_corridor_set_pt(pct_corridor *c, const double start[3], const double end[3], double xl, double xh, double yl, double yh,
                         double zl, double zh, double local_range, int max_iter, double sample_portion, double goal_portion);
 int pct_corridor_set_start_pt(pct_corridor *c, const double start[3], const double end[3]);

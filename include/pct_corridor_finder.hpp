@@ -227,6 +227,12 @@ public:
         const double a[3] = { lo.x, lo.y, lo.z }, b[3] = { hi.x, hi.y, hi.z };
         return map_.clearBox(a, b);
     }
+    // after enableRollingMap: depth images as the map's input (ObstacleMap::clearSeenThrough / appendDepthImage).  The rgbd tick is
+    // clearSeenThrough -> appendDepthImage -> SafeRegionEvaluate -> SafeRegionRefine with the same image in both calls: the carve
+    // withdraws what the image sees through (an obstacle that left), the append files what it hits; appendDepthImage does for its
+    // frame everything appendInput does for a point frame.  Radii that may now grow are re-checked by SafeRegionEvaluate.
+    int64_t clearSeenThrough(const pct_depth_view &view, const float *image, double margin) { return map_.clearSeenThrough(view, image, margin); }
+    int64_t appendDepthImage(const pct_depth_view &view, const float *image, double max_depth) { return map_.appendDepthImage(view, image, max_depth); }
 
     // ---- queries ----
     bool checkTrajPtCol(const Vec3 &pt) { return clearance(pt) < 0.0; }                     // :412-416

@@ -133,6 +133,38 @@
  * until the head passes them (a bucket that looks full spills newcomers to the overflow queue: correct, slower); nothing is
  * compacted.  A table sized automatically ignores removed rows when it is sized again.
  *
+ * Depth images (pct_cloud_ring_carve_depth, pct_cloud_append_depth, pct_depth_classify): the consumer side of the reference's rgbd and
+ * camera modes -- img_pcl_map_observer::save_point back-projects a rendered depth image to the observed cloud (map_observer.cpp:92-100),
+ * safety_controller::check_image_for_point decides whether a point lies in observed free space (safety_controller.cpp:102-130).  One
+ * projection serves all three calls (struct pct_depth_view below); all arithmetic is fp64 from float-widened operands, one rounding
+ * per operation, no contraction, in the order written here.  Projection of a point p (an fp32 row): d = (double)p - t;
+ * c_k = (d0*R[0][k] + d1*R[1][k]) + d2*R[2][k] for the camera axes k = x, y, z (R[i][k] = R[3*i + k]).  The point is IN THE IMAGE iff
+ * c_z >= near_z (a NaN fails) and, with scale = focal / c_z * width (the same scale on both axes, as in the reference),
+ * u = c_x*scale + width/2.0, v = c_y*scale + height/2.0, ru = round(u), rv = round(v), half away from zero,
+ * 0 <= ru <= width - 1 and 0 <= rv <= height - 1 -- compared in fp64 before any conversion to int.  Its pixel value is
+ * val = (double)image[rv*width + ru].  The point is SEEN THROUGH by the image iff it is in the image, val is finite (a +inf pixel proves
+ * nothing: nothing was rendered there, as in the reference; NaN and -inf likewise) and, with w = val - margin: c_z < w (PCT_DEPTH_Z), or
+ * w > 0 && ((d0*d0 + d1*d1) + d2*d2) < w*w (PCT_DEPTH_RANGE: no square root, so the test stays exact).  The comparison is strict: a
+ * point at exactly val - margin stays.  Un-projection of pixel (x, y) holding dep, PCT_DEPTH_Z only: the pixel is valid iff dep is
+ * finite, dep >= near_z and dep <= max_depth; a = ((double)x/width - 0.5)/focal, b = ((double)y - 0.5*height)/width/focal,
+ * p_k = t[k] + dep*((a*R[k][0] + b*R[k][1]) + R[k][2]), narrowed to fp32 with round-to-nearest; valid pixels are emitted in row-major
+ * order.  (Un-projecting a range image would need a normalisation whose rounding this contract would have to pin: PCT_ERR_INVALID.)
+ * pct_cloud_ring_carve_depth removes every point the image sees through and is a removal in every sense of the paragraph above: it
+ * needs a live rolling-map index, finishes an append in flight first, makes one pass over the slots below pct_cloud_size and waits
+ * once on the host for {removed, live after}; rows that hold a NaN are left alone and not counted; removed rows become NaN rows
+ * whose records are retired, so the NaN-row equivalence holds on every path, the empty-window rule applies and captured plans stay
+ * valid.  pct_cloud_append_depth un-projects the image on the device, compacts the valid pixels in row-major order into a device
+ * buffer the library owns and appends that frame exactly as pct_cloud_append_aos appends the same points (through the de-dup filter
+ * when de-dup is on; pct_cloud_ring_dedup_last reports it like any other append): no point list crosses the bus; the call waits
+ * once on the host for the number of valid pixels and, with de-dup on, once more for the survivor count.  pct_depth_classify needs no
+ * cloud: each planner point (fp64) is narrowed to fp32 first, as every planner point is; seen_by[i] is the lowest view whose image
+ * sees point i through, or -1; pixel[2i], pixel[2i + 1] are (ru, rv) of the point in the LAST view, or -1, -1 when it is not in that
+ * image (the reference's `good` flag).  Order of operations and the margin: carve first, then append the same image.  The points an
+ * image appends project back onto their own pixel at a z-depth within fp32 narrowing of the pixel value (numpy restatement, 40 random
+ * poses with |t| <= 100 m, fov 40 to 120 degrees, 8 x 6 and 64 x 48 images, depths in [0.1, 30]: every point on its own pixel,
+ * |c_z - val| <= 6.1e-6), so with margin = 0 the next carve by the same image could remove some of them; with a small positive margin
+ * (1e-3 on that domain) it cannot.  Sensor simulation -- rendering a world into an image -- is not part of the library.
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -251,6 +283,32 @@ int pct_cloud_ring_remove_box(pct_cloud *c, const double lo[3], const double hi[
 int pct_cloud_ring_remove_indices(pct_cloud *c, const uint32_t *idx, int64_t n, int64_t *removed);
 /* rows below size without a NaN coordinate, and size - that (one launch, one wait) */
 int pct_cloud_ring_live(pct_cloud *c, int64_t *live, int64_t *not_live);
+/* Depth images (the paragraph "Depth images" above).  One pinned projection for the three calls below. */
+enum pct_depth_metric { PCT_DEPTH_Z = 0, PCT_DEPTH_RANGE = 1 };
+typedef struct pct_depth_view {
+    double t[3];      /* camera position, world */
+    double R[9];      /* row-major; column k = camera axis k in world: x image right, y image down, z optical
+                         (Eigen Affine3f::rotation().col(k)); not checked for orthonormality */
+    double focal;     /* focal distance in image widths, 0.5 / tan(fov_hor / 2) (map_observer::get_focal_distance) */
+    double near_z;    /* a point with z-depth < near_z is not in the image (reference: 0.01) */
+    int32_t width, height;
+    int32_t metric;   /* what a pixel holds: depth along the optical axis (save_point) or range along the ray (check_image_for_point) */
+    int32_t reserved; /* 0 */
+} pct_depth_view;
+/* `image`: host memory, width*height floats, row-major, the caller's again when the call returns (it is copied through a staging
+ * buffer the library owns).  PCT_ERR_INVALID, with the cloud left as it was: a NULL argument; width or height < 1 or
+ * width*height > 2^24; focal or near_z not finite and > 0; a NaN or infinity in t or R; a NaN margin; a NaN max_depth (+inf is
+ * allowed); metric outside {0, 1}; reserved != 0; a cloud without pct_cloud_ring_index.
+ * carve: removes every point the image sees through (strict; margin in the pixel's unit); *removed = rows this call changed; an
+ * empty cloud: PCT_OK, *removed = 0.
+ * append: metric PCT_DEPTH_Z only (PCT_DEPTH_RANGE: PCT_ERR_INVALID).  *offered = valid pixels, *kept = what the window took (equal
+ * without de-dup).  More valid pixels than the capacity: PCT_ERR_CAPACITY, nothing changed. */
+int pct_cloud_ring_carve_depth(pct_cloud *c, const pct_depth_view *v, const float *image, double margin, int64_t *removed);
+int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *image, double max_depth, int64_t *offered, int64_t *kept);
+/* views[k] and images[k], 1 <= n_views <= 16, each view with its own size; pts: n planner points (fp64 xyz); seen_by[n];
+ * pixel[2n] may be NULL.  n = 0: PCT_OK. */
+int pct_depth_classify(const pct_depth_view *views, const float *const *images, int32_t n_views, const double *pts, int64_t n,
+                       double margin, int32_t *seen_by, int32_t *pixel);
 /* Zero-copy ingest.  pct_cloud_frame_buffer hands out a host-mapped staging buffer of at least `bytes` bytes (valid until the next
  * call that asks for a larger one, or pct_cloud_destroy); the producer -- a sensor driver, the deserialiser of a
  * sensor_msgs/PointCloud2 -- writes the frame's records there (x, y, z floats at the start of each stride-byte record) and

@@ -130,6 +130,32 @@ public:
         return live;
     }
 
+    // Depth images on the rolling map (pct_engine.h, paragraph "Depth images"; both need enableRollingIndex).  The rgbd tick is
+    // clearSeenThrough(image) then appendDepthImage(the same image): carve first, then append, with a small positive margin so that
+    // the next frame's carve leaves the points this frame appended alone.
+    //   clearSeenThrough   free-space clearing: removes every point the image sees through -- a point in the image whose pixel is
+    //                      finite and shows a surface strictly farther than the point plus margin
+    //                      (safety_controller::check_image_for_point, safety_controller.cpp:102-130); returns the number removed
+    //   appendDepthImage   un-projects the valid pixels (finite, near_z <= depth <= max_depth) on the device
+    //                      (img_pcl_map_observer::save_point, map_observer.cpp:92-100) and appends them as appendInput appends the
+    //                      same points; returns the number of points the window took
+    int64_t clearSeenThrough(const pct_depth_view &view, const float *image, double margin)
+    {
+        needRolling("clearSeenThrough");
+        int64_t removed = 0;
+        check(pct_cloud_ring_carve_depth(cloud_, &view, image, margin, &removed), "pct_cloud_ring_carve_depth");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return removed;
+    }
+    int64_t appendDepthImage(const pct_depth_view &view, const float *image, double max_depth)
+    {
+        needRolling("appendDepthImage");
+        int64_t offered = 0, kept = 0;
+        check(pct_cloud_append_depth(cloud_, &view, image, max_depth, &offered, &kept), "pct_cloud_append_depth");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return kept;
+    }
+
     // corridor_finder.cpp:113-133
     double radiusSearch(const double p[3])
     {

@@ -40,6 +40,9 @@ def lib():
         L.pct_corridor_forget_outside.argtypes = [vp, d3, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_ball.argtypes = [vp, d3, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_box.argtypes = [vp, d3, d3, C.POINTER(C.c_int64)]
+        L.pct_corridor_clear_seen_through.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
+        L.pct_corridor_append_depth.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
+        L.pct_corridor_cloud.argtypes = [vp, C.POINTER(vp)]
         L.pct_corridor_set_pt.argtypes = [vp, d3, d3] + [C.c_double] * 7 + [C.c_int, C.c_double, C.c_double]
         L.pct_corridor_set_start_pt.argtypes = [vp, d3, d3]
         L.pct_corridor_reset_root.argtypes = [vp, d3]
@@ -141,6 +144,32 @@ class SafeRegionRrtStar:
         n = C.c_int64()
         self._chk(self.L.pct_corridor_clear_box(self.h, _d3(lo), _d3(hi), C.byref(n)))
         return n.value
+
+    def clearSeenThrough(self, view, image, margin: float) -> int:
+        """after enableRollingMap: remove every point the depth image sees through (engine.DepthView; the rgbd tick:
+        clearSeenThrough -> appendDepthImage -> SafeRegionEvaluate -> SafeRegionRefine); returns the number of points removed"""
+        from . import engine
+        img = engine.depth_image(view, image)
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_clear_seen_through(self.h, C.addressof(view), img.ctypes.data, float(margin), C.byref(n)))
+        return n.value
+
+    def appendDepthImage(self, view, image, max_depth: float = float("inf")) -> int:
+        """after enableRollingMap: un-project the image's valid pixels on the device and append them as appendInput appends a point
+        frame; returns the number of points the window took"""
+        from . import engine
+        img = engine.depth_image(view, image)
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_append_depth(self.h, C.addressof(view), img.ctypes.data, float(max_depth), C.byref(n)))
+        return n.value
+
+    def cloud(self):
+        """the finder's obstacle cloud as an engine.Cloud that does not own it (pct_corridor_cloud): for reading the window back
+        (radius_crop, ring_live); replaced by a setInput that has to grow the map"""
+        from . import engine
+        h = C.c_void_p()
+        self._chk(self.L.pct_corridor_cloud(self.h, C.byref(h)))
+        return engine.Cloud.borrowed(h)
 
     def setPt(self, start, end, xl, xh, yl, yh, zl, zh, local_range, max_iter, sample_portion, goal_portion):
         self._chk(self.L.pct_corridor_set_pt(self.h, _d3(start), _d3(end), xl, xh, yl, yh, zl, zh, local_range, int(max_iter),

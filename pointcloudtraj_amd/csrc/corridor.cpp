@@ -87,6 +87,29 @@ int pct_corridor_clear_box(pct_corridor *c, const double lo[3], const double hi[
 {
     return guarded([&] { const int64_t n = c->impl->clearBox(v3(lo), v3(hi)); if (removed) *removed = n; });
 }
+int pct_corridor_clear_seen_through(pct_corridor *c, const pct_depth_view *view, const float *image, double margin, int64_t *removed)
+{
+    return guarded([&] {
+        if (!view) throw std::runtime_error("pct_corridor_clear_seen_through: null view");
+        const int64_t n = c->impl->clearSeenThrough(*view, image, margin);
+        if (removed) *removed = n;
+    });
+}
+int pct_corridor_append_depth(pct_corridor *c, const pct_depth_view *view, const float *image, double max_depth, int64_t *kept)
+{
+    return guarded([&] {
+        if (!view) throw std::runtime_error("pct_corridor_append_depth: null view");
+        const int64_t n = c->impl->appendDepthImage(*view, image, max_depth);
+        if (kept) *kept = n;
+    });
+}
+int pct_corridor_cloud(pct_corridor *c, pct_cloud **cloud)
+{
+    return guarded([&] {
+        if (!cloud) throw std::runtime_error("pct_corridor_cloud: null argument");
+        *cloud = c->impl->obstacleMap().handle();
+    });
+}
 int pct_corridor_set_pt(pct_corridor *c, const double start[3], const double end[3], double xl, double xh, double yl, double yh,
                         double zl, double zh, double local_range, int max_iter, double sample_portion, double goal_portion)
 {

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -29,6 +30,7 @@
 #include "ring.hpp"
 #include "ring_dedup.hpp"
 #include "ring_remove.hpp"
+#include "ring_depth.hpp"
 #include "brute2.hpp"
 #include "knn.hpp"
 #include "rsearch.hpp"
@@ -296,8 +298,18 @@ struct pct_cloud {
     uint32_t dd_seq = 0;
     int64_t dd_last_offered = 0, dd_last_kept = 0;
     uint64_t dd_total_offered = 0, dd_total_kept = 0;
+    // depth images (ring_depth.hpp, pct_cloud_ring_carve_depth / pct_cloud_append_depth): the image's pinned staging and its device copy,
+    // and the un-projection's scratch -- validity flags, ranks, tile totals and the packed frame the insert kernel reads (grow-only)
+    float *dp_himg = nullptr, *dp_dimg = nullptr;
+    size_t dp_img_cap = 0;
+    uint8_t *dp_flags = nullptr;
+    uint32_t *dp_rank = nullptr, *dp_tile = nullptr;
+    float *dp_out = nullptr;
+    int64_t dp_ncap = 0;
     struct ReplanCtx *rp = nullptr;              // lazily created context of the un-captured fused planner batch
 };
+
+void depth_cloud_free(pct_cloud *c);             // ring_host.inc
 
 struct ReplanCtx;
 void replan_ctx_free(ReplanCtx *x);
@@ -1544,6 +1556,7 @@ int pct_cloud_destroy(pct_cloud *c)
     if (c->h_rm_word) (void)hipHostFree(c->h_rm_word);
     dev_free(c->dd_keys); dev_free(c->dd_vals); dev_free(c->dd_pslot); dev_free(c->dd_rank); dev_free(c->dd_tile); dev_free(c->dd_flags); dev_free(c->dd_out);
     if (c->h_dd_word) (void)hipHostFree(c->h_dd_word);
+    depth_cloud_free(c);
     replan_ctx_free(c->rp);
     dev_free(c->crop_tile); dev_free(c->crop_idx); dev_free(c->crop_d2); dev_free(c->crop_x); dev_free(c->crop_y); dev_free(c->crop_z);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

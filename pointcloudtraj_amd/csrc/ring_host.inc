@@ -293,15 +293,39 @@ int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride, const 
 }
 
 // ---- de-duplicating appends (ring_dedup.hpp) ---------------------------------------------------------------------------------
-int append_unindexed(pct_cloud *c, const void *pts, int64_t n, int64_t stride_bytes);     // engine.hip: the first-data path
+int after_replace(pct_cloud *c);
+
+// the host-mapped {sequence, total} pair dd_tile_scan_kernel publishes
+int dd_word_ensure(pct_cloud *c)
+{
+    if (c->h_dd_word) return PCT_OK;
+    PCTCHK(mapped_alloc(&c->h_dd_word, &c->d_dd_word, 4));
+    c->h_dd_word[0] = c->h_dd_word[1] = 0;
+    return PCT_OK;
+}
+
+// the host wait behind dd_tile_scan_kernel: the grand total of the scan launched with `seq`, polled in host-mapped memory as
+// express_wait polls its word
+int dd_scan_wait(pct_cloud *c, uint32_t seq, int64_t *total)
+{
+    bool seen = false;
+    if (poll_results()) {
+        const volatile uint32_t *w = c->h_dd_word;
+        for (long spins = 0; spins < 200000000l && !seen; spins++) {
+            if (w[0] == seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); seen = true; }
+            else __builtin_ia32_pause();
+        }
+    }
+    if (!seen) HIPCHK(hipStreamSynchronize(g_stream));
+    if (c->h_dd_word[0] != seq) return fail(PCT_ERR_HIP, "the frame filter finished without its sequence word (%u != %u)", c->h_dd_word[0], seq);
+    *total = (int64_t)c->h_dd_word[1];
+    return PCT_OK;
+}
 
 // scratch of the frame filter for a frame of n points (grow-only)
 int dedup_ensure(pct_cloud *c, int64_t n)
 {
-    if (!c->h_dd_word) {
-        PCTCHK(mapped_alloc(&c->h_dd_word, &c->d_dd_word, 4));
-        c->h_dd_word[0] = c->h_dd_word[1] = 0;
-    }
+    PCTCHK(dd_word_ensure(c));
     uint32_t T = 1024;
     while ((uint64_t)T < 2ull * (uint64_t)n) T <<= 1;
     if (T > c->dd_tcap) {
@@ -348,23 +372,28 @@ int dedup_filter(pct_cloud *c, const unsigned char *d_src, int64_t n, int64_t st
     dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dd_tile, (uint32_t)ntiles, c->d_dd_word, seq);
     dd_compact_kernel<<<ceil_div(n, 256), 256, 0, s>>>(d_src, un, (uint32_t)stride, c->dd_flags, c->dd_rank, c->dd_tile, c->dd_out);
     HIPCHK(hipGetLastError());
-    bool seen = false;
-    if (poll_results()) {
-        const volatile uint32_t *w = c->h_dd_word;
-        for (long spins = 0; spins < 200000000l && !seen; spins++) {
-            if (w[0] == seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); seen = true; }
-            else __builtin_ia32_pause();
-        }
-    }
-    if (!seen) HIPCHK(hipStreamSynchronize(s));
-    if (c->h_dd_word[0] != seq) return fail(PCT_ERR_HIP, "the de-dup filter finished without its sequence word (%u != %u)", c->h_dd_word[0], seq);
-    *kept = (int64_t)c->h_dd_word[1];
+    PCTCHK(dd_scan_wait(c, seq, kept));
     if (*kept > n) return fail(PCT_ERR_INTERNAL, "the de-dup filter kept %lld of %lld points", (long long)*kept, (long long)n);
     return PCT_OK;
 }
 
-// pct_cloud_append_aos on a rolling-map cloud with de-dup on: filter the frame against itself and the window, append the survivors
-int ring_append_dedup(pct_cloud *c, const void *pts, int64_t n, int64_t stride)
+// first data on a rolling-map cloud (the window has no table yet) from a packed frame in a device buffer the library owns: the
+// rows go into the ring slots as append_unindexed stores a host frame, and the table is sized from them
+int append_unindexed_dev(pct_cloud *c, const float *d_pts, int64_t n)
+{
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(d_pts);
+    const int64_t first = std::min(n, c->cap - c->ring_next);
+    if (first > 0) deinterleave_kernel<<<ceil_div(first, 256), 256, 0, g_stream>>>(src, 12u, (uint32_t)first, c->x, c->y, c->z, (uint32_t)c->ring_next);
+    if (first < n) deinterleave_kernel<<<ceil_div(n - first, 256), 256, 0, g_stream>>>(src + first * 12, 12u, (uint32_t)(n - first), c->x, c->y, c->z, 0u);
+    HIPCHK(hipGetLastError());
+    c->ring_next = (c->ring_next + n) % c->cap;
+    c->count = std::min(c->cap, c->count + n);
+    return after_replace(c);
+}
+
+// pct_cloud_append_aos on a rolling-map cloud with de-dup on: filter the frame against itself and the window, append the survivors.
+// d_own != nullptr: the frame (packed, stride 12) is already in a device buffer the library owns and `pts` is not looked at
+int ring_append_dedup(pct_cloud *c, const void *pts, int64_t n, int64_t stride, const unsigned char *d_own = nullptr)
 {
     hipStream_t s = g_stream;
     PCTCHK(ring_finish_pending(c));
@@ -377,9 +406,9 @@ int ring_append_dedup(pct_cloud *c, const void *pts, int64_t n, int64_t stride)
     if (!c->ring_ready && c->count > 0) { PCTCHK(ring_setup_from_cloud(c)); HIPCHK(hipStreamSynchronize(s)); }
     PCTCHK(dedup_ensure(c, n));
     const size_t bytes = (size_t)n * (size_t)stride;
-    const bool in_place = pts == c->h_frame && c->h_frame != nullptr && bytes <= c->frame_cap;
-    const unsigned char *d_src = c->d_frame;
-    if (!in_place) {
+    const bool in_place = !d_own && pts == c->h_frame && c->h_frame != nullptr && bytes <= c->frame_cap;
+    const unsigned char *d_src = d_own ? d_own : c->d_frame;
+    if (!in_place && !d_own) {
         PCTCHK(ensure_stage(c, bytes + 64));
         HIPCHK(hipMemcpyAsync(c->d_stage, pts, bytes, hipMemcpyHostToDevice, s));
         d_src = c->d_stage;
@@ -401,11 +430,7 @@ int ring_append_dedup(pct_cloud *c, const void *pts, int64_t n, int64_t stride)
         return PCT_OK;
     }
     // first data (the window is empty and has no table yet): the compacted frame takes the first-data path, which sizes the table from it
-    std::vector<float> host;
-    try { host.resize(3 * (size_t)kept); } catch (const std::bad_alloc &) { return fail(PCT_ERR_ALLOC, "host allocation failed"); }
-    HIPCHK(hipMemcpyAsync(host.data(), c->dd_out, sizeof(float) * host.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return append_unindexed(c, host.data(), kept, 12);
+    return append_unindexed_dev(c, c->dd_out, kept);
 }
 
 // the cloud's contents were replaced (upload) or grew on a cloud whose ring table does not exist yet
@@ -1105,6 +1130,233 @@ int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
     PCTCHK(ring_remove_wait(c, seq, &removed, &live));
     *live_out = live;
     *not_live = c->count - live;
+    return PCT_OK;
+}
+
+}  // extern "C"
+
+// ---- depth images on the rolling map (ring_depth.hpp) ----------------------------------------------------------------------------
+namespace {
+
+// what the three depth entry points refuse in a view (pct_engine.h)
+int depth_view_check(const pct_depth_view *v, const char *what)
+{
+    if (!v) return fail(PCT_ERR_INVALID, "%s: null view", what);
+    if (v->width < 1 || v->height < 1 || (int64_t)v->width * (int64_t)v->height > (1ll << 24))
+        return fail(PCT_ERR_INVALID, "%s: bad image size %d x %d (at most 2^24 pixels)", what, v->width, v->height);
+    if (!(std::isfinite(v->focal) && v->focal > 0) || !(std::isfinite(v->near_z) && v->near_z > 0))
+        return fail(PCT_ERR_INVALID, "%s: focal and near_z must be finite and > 0", what);
+    for (int k = 0; k < 3; k++) if (!std::isfinite(v->t[k])) return fail(PCT_ERR_INVALID, "%s: the camera position is not finite", what);
+    for (int k = 0; k < 9; k++) if (!std::isfinite(v->R[k])) return fail(PCT_ERR_INVALID, "%s: the camera rotation is not finite", what);
+    if (v->metric != PCT_DEPTH_Z && v->metric != PCT_DEPTH_RANGE) return fail(PCT_ERR_INVALID, "%s: unknown depth metric %d", what, v->metric);
+    if (v->reserved != 0) return fail(PCT_ERR_INVALID, "%s: the reserved field must be 0", what);
+    return PCT_OK;
+}
+
+// An image on its way to the device: the caller's floats are copied into pinned memory the library owns and from there to a device
+// buffer on the library's stream (both grow-only), so the caller's buffer is its own again at once and the kernels gather from HBM
+// / L2, not across the bus.  Every user waits for a kernel behind the copy before it returns: the pinned buffer is free by then.
+struct DepthStage {
+    float *h = nullptr, *d = nullptr;
+    size_t cap = 0;                              // floats
+};
+
+int depth_stage_image(DepthStage *S, const float *image, size_t off, size_t npix)
+{
+    std::memcpy(S->h + off, image, sizeof(float) * npix);
+    HIPCHK(hipMemcpyAsync(S->d + off, S->h + off, sizeof(float) * npix, hipMemcpyHostToDevice, g_stream));
+    return PCT_OK;
+}
+
+int depth_stage_ensure(DepthStage *S, size_t floats)
+{
+    if (floats <= S->cap) return PCT_OK;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    if (S->h) (void)hipHostFree(S->h);
+    dev_free(S->d);
+    S->h = nullptr; S->cap = 0;
+    size_t cap = (size_t)1 << 14;
+    while (cap < floats) cap <<= 1;
+    void *h = nullptr;
+    if (hipHostMalloc(&h, cap * sizeof(float), hipHostMallocDefault) != hipSuccess) return fail(PCT_ERR_ALLOC, "hipHostMalloc(%zu bytes) failed", cap * sizeof(float));
+    S->h = static_cast<float *>(h);
+    if (const int st = dev_alloc(&S->d, cap)) { (void)hipHostFree(S->h); S->h = nullptr; return st; }
+    S->cap = cap;
+    return PCT_OK;
+}
+
+void depth_stage_free(DepthStage *S)
+{
+    if (S->h) (void)hipHostFree(S->h);
+    dev_free(S->d);
+    S->h = nullptr; S->cap = 0;
+}
+
+// scratch of pct_cloud_append_depth for an image of npix pixels (grow-only): validity flags, ranks, tile totals, the packed frame
+int depth_scratch_ensure(pct_cloud *c, int64_t npix)
+{
+    PCTCHK(dd_word_ensure(c));
+    if (npix <= c->dp_ncap) return PCT_OK;
+    HIPCHK(hipStreamSynchronize(g_stream));       // the previous append's insert kernel may still be reading the packed frame
+    dev_free(c->dp_flags); dev_free(c->dp_rank); dev_free(c->dp_tile); dev_free(c->dp_out);
+    c->dp_ncap = 0;
+    int64_t cap = 4096;
+    while (cap < npix) cap <<= 1;
+    PCTCHK(dev_alloc(&c->dp_flags, (size_t)cap));
+    PCTCHK(dev_alloc(&c->dp_rank, (size_t)cap));
+    PCTCHK(dev_alloc(&c->dp_tile, (size_t)ceil_div(cap, kDdTile)));
+    PCTCHK(dev_alloc(&c->dp_out, 3 * (size_t)cap));
+    c->dp_ncap = cap;
+    return PCT_OK;
+}
+
+// pct_depth_classify has no cloud to keep its buffers in: one grow-only set for the process, used under a lock
+struct DepthClassifyWork {
+    std::mutex lock;
+    DepthStage images;
+    double *d_pts = nullptr;
+    int32_t *d_seen = nullptr, *d_pixel = nullptr;
+    int64_t ncap = 0;
+};
+DepthClassifyWork g_depth_work;
+
+}  // namespace
+
+void depth_cloud_free(pct_cloud *c)
+{
+    DepthStage S{ c->dp_himg, c->dp_dimg, c->dp_img_cap };
+    depth_stage_free(&S);
+    c->dp_himg = nullptr; c->dp_dimg = nullptr; c->dp_img_cap = 0;
+    dev_free(c->dp_flags); dev_free(c->dp_rank); dev_free(c->dp_tile); dev_free(c->dp_out);
+    c->dp_ncap = 0;
+}
+
+namespace {
+
+// the cloud's image staging: copy `image` in and hand back where the kernels read it
+int depth_cloud_image(pct_cloud *c, const pct_depth_view *v, const float *image, const float **d_image)
+{
+    const size_t npix = (size_t)v->width * (size_t)v->height;
+    DepthStage S{ c->dp_himg, c->dp_dimg, c->dp_img_cap };
+    const int st = depth_stage_ensure(&S, npix);
+    c->dp_himg = S.h; c->dp_dimg = S.d; c->dp_img_cap = S.cap;
+    PCTCHK(st);
+    PCTCHK(depth_stage_image(&S, image, 0, npix));
+    *d_image = S.d;
+    return PCT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pct_cloud_ring_carve_depth(pct_cloud *c, const pct_depth_view *v, const float *image, double margin, int64_t *removed_out)
+{
+    if (!c || !image || !removed_out) return fail(PCT_ERR_INVALID, "bad ring_carve_depth arguments");
+    PCTCHK(depth_view_check(v, "pct_cloud_ring_carve_depth"));
+    if (std::isnan(margin)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_carve_depth: the margin is a NaN");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_carve_depth"));
+    *removed_out = 0;
+    if (c->count == 0) return PCT_OK;
+    PCTCHK(ring_remove_ensure(c));
+    const float *d_image = nullptr;
+    PCTCHK(depth_cloud_image(c, v, image, &d_image));
+    const uint32_t seq = ++c->rm_seq;
+    depth_carve_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, *v, d_image, margin, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht,
+                                                                     c->ring_slots, c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->d_rm_word, seq);
+    HIPCHK(hipGetLastError());
+    int64_t removed = 0, live = 0;
+    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
+    *removed_out = removed;
+    return ring_remove_finish(c, removed, live);
+}
+
+int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *image, double max_depth, int64_t *offered, int64_t *kept)
+{
+    if (!c || !image || !offered || !kept) return fail(PCT_ERR_INVALID, "bad append_depth arguments");
+    PCTCHK(depth_view_check(v, "pct_cloud_append_depth"));
+    if (std::isnan(max_depth)) return fail(PCT_ERR_INVALID, "pct_cloud_append_depth: max_depth is a NaN");
+    if (v->metric != PCT_DEPTH_Z) return fail(PCT_ERR_INVALID, "pct_cloud_append_depth: only z-depth images are un-projected (PCT_DEPTH_Z)");
+    if (!c->ring_on) return fail(PCT_ERR_INVALID, "pct_cloud_append_depth needs the rolling-map index (pct_cloud_ring_index)");
+    hipStream_t s = g_stream;
+    PCTCHK(ring_finish_pending(c));             // the previous frame's insert kernel has read the packed frame below
+    *offered = *kept = 0;
+    const int64_t npix = (int64_t)v->width * (int64_t)v->height;
+    PCTCHK(depth_scratch_ensure(c, npix));
+    const float *d_image = nullptr;
+    PCTCHK(depth_cloud_image(c, v, image, &d_image));
+    // flags of the valid pixels, their ranks in row-major order, and the FIRST host wait: the valid count -- the capacity test, the
+    // slots the append takes and the filter's table size all need it before anything is queued that changes the window
+    const uint32_t un = (uint32_t)npix, seq = ++c->dd_seq;
+    const int ntiles = ceil_div(npix, kDdTile);
+    depth_valid_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, max_depth, c->dp_flags);
+    dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dp_flags, un, c->dp_rank, c->dp_tile);
+    dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dp_tile, (uint32_t)ntiles, c->d_dd_word, seq);
+    depth_unproject_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, c->dp_flags, c->dp_rank, c->dp_tile, c->dp_out);
+    HIPCHK(hipGetLastError());
+    int64_t n = 0;
+    PCTCHK(dd_scan_wait(c, seq, &n));
+    if (n > npix) return fail(PCT_ERR_INTERNAL, "the depth un-projection counted %lld valid pixels of %lld", (long long)n, (long long)npix);
+    if (n > c->cap) return fail(PCT_ERR_CAPACITY, "appending %lld valid pixels to a ring of %lld", (long long)n, (long long)c->cap);
+    *offered = n;
+    // from here on: pct_cloud_append_aos of the n un-projected points, their source being the packed device frame
+    const unsigned char *d_frame = reinterpret_cast<const unsigned char *>(c->dp_out);
+    if (c->dd_res > 0) {
+        PCTCHK(ring_append_dedup(c, nullptr, n, 12, d_frame));          // the SECOND host wait: the survivor count
+        *kept = c->dd_last_kept;
+        return PCT_OK;
+    }
+    *kept = n;
+    if (n == 0) return PCT_OK;
+    drop_grid(c);
+    if (c->ring_ready) return ring_append(c, nullptr, n, 12, d_frame);
+    return append_unindexed_dev(c, c->dp_out, n);
+}
+
+int pct_depth_classify(const pct_depth_view *views, const float *const *images, int32_t n_views, const double *pts, int64_t n, double margin,
+                       int32_t *seen_by, int32_t *pixel)
+{
+    if (!views || !images || n_views < 1 || n_views > kDepthMaxViews || n < 0 || !pts || !seen_by || n > 0xFFFFFFF0ll)
+        return fail(PCT_ERR_INVALID, "bad depth_classify arguments (1 <= n_views <= %d)", kDepthMaxViews);
+    if (std::isnan(margin)) return fail(PCT_ERR_INVALID, "pct_depth_classify: the margin is a NaN");
+    size_t total = 0;
+    for (int k = 0; k < n_views; k++) {
+        if (!images[k]) return fail(PCT_ERR_INVALID, "pct_depth_classify: image %d is NULL", k);
+        PCTCHK(depth_view_check(&views[k], "pct_depth_classify"));
+        total += (size_t)views[k].width * (size_t)views[k].height;
+    }
+    if (n == 0) return PCT_OK;
+    PCTCHK(require_init());
+    DepthClassifyWork &W = g_depth_work;
+    std::lock_guard<std::mutex> guard(W.lock);
+    PCTCHK(depth_stage_ensure(&W.images, total));
+    if (n > W.ncap) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        dev_free(W.d_pts); dev_free(W.d_seen); dev_free(W.d_pixel);
+        W.ncap = 0;
+        int64_t cap = 1024;
+        while (cap < n) cap <<= 1;
+        PCTCHK(dev_alloc(&W.d_pts, 3 * (size_t)cap));
+        PCTCHK(dev_alloc(&W.d_seen, (size_t)cap));
+        PCTCHK(dev_alloc(&W.d_pixel, 2 * (size_t)cap));
+        W.ncap = cap;
+    }
+    DepthViews S{};
+    S.n = n_views;
+    size_t off = 0;
+    for (int k = 0; k < n_views; k++) {
+        const size_t npix = (size_t)views[k].width * (size_t)views[k].height;
+        S.v[k] = views[k];
+        S.image[k] = W.images.d + off;
+        PCTCHK(depth_stage_image(&W.images, images[k], off, npix));
+        off += npix;
+    }
+    HIPCHK(hipMemcpyAsync(W.d_pts, pts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, g_stream));
+    depth_classify_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(S, W.d_pts, (uint32_t)n, margin, W.d_seen, pixel ? W.d_pixel : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(seen_by, W.d_seen, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    if (pixel) HIPCHK(hipMemcpyAsync(pixel, W.d_pixel, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
     return PCT_OK;
 }
 

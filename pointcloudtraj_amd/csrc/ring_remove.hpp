@@ -62,13 +62,14 @@ __device__ __forceinline__ void ring_remove_count(bool removed, bool live, RingR
     __hip_atomic_store(&host_word[0], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// One thread per slot below `count`: a row without a NaN that the region condemns is retired, becomes a NaN row and is marked
-// unfiled.  No record is filed while this runs (appends are ordered before and after it on the stream).
-__global__ __launch_bounds__(256) void ring_remove_region_kernel(RingDesc R, RingRegion G, float *__restrict__ x, float *__restrict__ y,
-                                                                 float *__restrict__ z, uint32_t count, uint2 *__restrict__ ht,
-                                                                 float4 *__restrict__ slots, float4 *__restrict__ ovf,
-                                                                 uint32_t *__restrict__ where, RingState *__restrict__ st,
-                                                                 RingRemoveMeet *__restrict__ meet, uint32_t *__restrict__ host_word, uint32_t seq)
+// One thread per slot below `count`: a row without a NaN that `condemned(px, py, pz)` names is retired, becomes a NaN row and is
+// marked unfiled.  No record is filed while this runs (appends are ordered before and after it on the stream).  The body of every
+// one-pass removal: the region kernel below and the depth-image carve (ring_depth.hpp) differ in the predicate alone.
+template <typename Pred>
+__device__ __forceinline__ void ring_remove_where(const Pred &condemned, const RingDesc &R, float *__restrict__ x, float *__restrict__ y,
+                                                  float *__restrict__ z, uint32_t count, uint2 *__restrict__ ht, float4 *__restrict__ slots,
+                                                  float4 *__restrict__ ovf, uint32_t *__restrict__ where, RingState *__restrict__ st,
+                                                  RingRemoveMeet *__restrict__ meet, uint32_t *__restrict__ host_word, uint32_t seq)
 {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t q_tail = st->ovf_tail;
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void ring_remove_region_kernel(RingDesc R, Rin
     if (slot < count) {
         const float px = x[slot], py = y[slot], pz = z[slot];
         if (px == px && py == py && pz == pz) {
-            removed = ring_region_inside(G, px, py, pz) != (G.outside != 0);
+            removed = condemned(px, py, pz);
             live = !removed;
             if (removed) {
                 ring_retire_record(R, where[slot], px, py, pz, ht, slots, ovf);
@@ -89,6 +90,16 @@ __global__ __launch_bounds__(256) void ring_remove_region_kernel(RingDesc R, Rin
     }
     if (queue_in_use) ring_queue_head_advance(R, ovf, st, q_tail);
     ring_remove_count(removed, live, meet, host_word, seq, 1);
+}
+
+__global__ __launch_bounds__(256) void ring_remove_region_kernel(RingDesc R, RingRegion G, float *__restrict__ x, float *__restrict__ y,
+                                                                 float *__restrict__ z, uint32_t count, uint2 *__restrict__ ht,
+                                                                 float4 *__restrict__ slots, float4 *__restrict__ ovf,
+                                                                 uint32_t *__restrict__ where, RingState *__restrict__ st,
+                                                                 RingRemoveMeet *__restrict__ meet, uint32_t *__restrict__ host_word, uint32_t seq)
+{
+    ring_remove_where([&](float px, float py, float pz) { return ring_region_inside(G, px, py, pz) != (G.outside != 0); }, R, x, y, z, count, ht,
+                      slots, ovf, where, st, meet, host_word, seq);
 }
 
 // One thread per list entry (ring slots, already validated against the window by the host).  A slot named twice is claimed once:

@@ -48,6 +48,53 @@ class BezierTraj(C.Structure):
                 ("orders", C.POINTER(C.c_int32)), ("nseg", C.c_int32)]
 
 
+DEPTH_Z, DEPTH_RANGE = 0, 1             # enum pct_depth_metric: a pixel holds the depth along the optical axis / the range along the ray
+
+
+class DepthView(C.Structure):
+    """pct_depth_view: the pinned projection of a depth image (include/pct_engine.h, paragraph "Depth images")"""
+    _fields_ = [("t", C.c_double * 3), ("R", C.c_double * 9), ("focal", C.c_double), ("near_z", C.c_double),
+                ("width", C.c_int32), ("height", C.c_int32), ("metric", C.c_int32), ("reserved", C.c_int32)]
+
+
+def depth_view(t, R, width, height, fov_hor_deg=None, focal=None, metric=DEPTH_Z, near_z=0.01) -> DepthView:
+    """t: camera position; R: 3 x 3, column k = camera axis k in world (x image right, y image down, z optical); the focal distance in
+    image widths is given directly or as 0.5 / tan(fov_hor / 2) of a horizontal field of view in degrees"""
+    if (fov_hor_deg is None) == (focal is None):
+        raise ValueError("give exactly one of fov_hor_deg and focal")
+    v = DepthView()
+    v.t[:] = [float(x) for x in np.asarray(t, np.float64).reshape(3)]
+    v.R[:] = [float(x) for x in np.asarray(R, np.float64).reshape(9)]
+    v.focal = float(focal) if focal is not None else 0.5 / float(np.tan(np.float64(fov_hor_deg) * np.pi / 180.0 / 2.0))
+    v.near_z = float(near_z)
+    v.width, v.height, v.metric, v.reserved = int(width), int(height), int(metric), 0
+    return v
+
+
+def depth_image(view: DepthView, image):
+    """the image as the library reads it: float32, C-contiguous, height x width"""
+    a = np.ascontiguousarray(image, np.float32)
+    if a.size != view.width * view.height:
+        raise ValueError(f"the image has {a.size} pixels, the view {view.width} x {view.height}")
+    return a
+
+
+def depth_classify(views, images, points, margin, want_pixel=True):
+    """pct_depth_classify: (seen_by int32 [n], pixel int32 [n, 2] or None) -- the lowest view whose image sees each planner point
+    through (or -1), and the point's pixel (ru, rv) in the LAST view (or -1, -1 when it is not in that image)"""
+    views = list(views)
+    imgs = [depth_image(v, im) for v, im in zip(views, images)]
+    if len(imgs) != len(views):
+        raise ValueError("one image per view")
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    varr = (DepthView * max(len(views), 1))(*views)
+    iarr = (C.c_void_p * max(len(views), 1))(*[im.ctypes.data for im in imgs])
+    seen = np.empty(len(p), np.int32)
+    pix = np.empty((len(p), 2), np.int32) if want_pixel else None
+    _chk(lib().pct_depth_classify(varr, iarr, len(views), _ptr(p), len(p), float(margin), _ptr(seen), None if pix is None else _ptr(pix)))
+    return seen, pix
+
+
 def _preload_hip_runtime():
     """One HIP runtime per process.  PyTorch-ROCm wheels bundle their own libamdhip64.so (soname
     libamdhip64.so.7, the same as /opt/rocm's); two copies in one process each open the KFD device
@@ -139,6 +186,9 @@ def lib():
         L.pct_cloud_ring_remove_box.argtypes = [vp, f64p, f64p, C.c_int, C.POINTER(i64)]
         L.pct_cloud_ring_remove_indices.argtypes = [vp, u32p, i64, C.POINTER(i64)]
         L.pct_cloud_ring_live.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+        L.pct_cloud_ring_carve_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64)]
+        L.pct_cloud_append_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64), C.POINTER(i64)]
+        L.pct_depth_classify.argtypes = [vp, vp, C.c_int32, f64p, i64, C.c_double, vp, vp]
         L.pct_debug_ring_slot.argtypes = [vp, i64, C.POINTER(C.c_uint32)]
         L.pct_ctrl_points_check.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                             i64, f64p, f64p, f64p, u32p]
@@ -212,9 +262,17 @@ class Cloud:
         self._h = C.c_void_p()
         _chk(lib().pct_cloud_create(int(capacity), C.byref(self._h)))
 
+    @classmethod
+    def borrowed(cls, handle):
+        """a Cloud over a pct_cloud that someone else owns (the corridor finder's map): close() leaves it alone"""
+        c = cls.__new__(cls)
+        c._h, c._owned = handle, False
+        return c
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value and _lib is not None:
-            _lib.pct_cloud_destroy(self._h)
+            if getattr(self, "_owned", True):
+                _lib.pct_cloud_destroy(self._h)
             self._h = C.c_void_p()
 
     __del__ = close
@@ -353,6 +411,22 @@ class Cloud:
         a, b = C.c_int64(), C.c_int64()
         _chk(lib().pct_cloud_ring_live(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def ring_carve_depth(self, view: DepthView, image, margin: float) -> int:
+        """free-space clearing (pct_cloud_ring_carve_depth): remove every point the depth image sees through -- in the image, its
+        pixel finite and strictly farther than the point plus margin; the removed points become NaN rows; returns the number removed"""
+        img = depth_image(view, image)
+        n = C.c_int64()
+        _chk(lib().pct_cloud_ring_carve_depth(self._h, C.byref(view), _ptr(img), float(margin), C.byref(n)))
+        return n.value
+
+    def append_depth(self, view: DepthView, image, max_depth: float = float("inf")):
+        """un-project the valid pixels of a z-depth image on the device and append them as append() appends the same points
+        (pct_cloud_append_depth); returns (offered = valid pixels, kept = points the window took)"""
+        img = depth_image(view, image)
+        off, kept = C.c_int64(), C.c_int64()
+        _chk(lib().pct_cloud_append_depth(self._h, C.byref(view), _ptr(img), float(max_depth), C.byref(off), C.byref(kept)))
+        return off.value, kept.value
 
     def debug_ring_slot(self, slot: int):
         """pct_debug_ring_slot: (where word, bucket, head, tail, id word at the filed position, overflow-queue length) -- test hook"""

@@ -231,6 +231,69 @@ def run_lidar_window_scenario(finder, window=40000, expand=800, refine=300, comm
     return out
 
 
+# ---- the rgbd window: a camera at the origin looking along +x, a back wall, and an obstacle that leaves ---------------------------
+RGBD = dict(width=64, height=48, fov_hor_deg=90.0, wall_x=8.0, wall_size=(16.0, 12.0), obstacle_x=5.0, obstacle_size=2.0, lattice=0.1,
+            obstacle_frames=3, cap=40000, res=0.1, margin=1.0e-3, extent=(10.0, 18.0, 14.0))
+# camera axes in world, one per column: image right = -y, image down = -z, optical axis = +x
+RGBD_R = ((0.0, 0.0, 1.0), (-1.0, 0.0, 0.0), (0.0, -1.0, 0.0))
+
+
+def rgbd_view():
+    """the scenario's pct_depth_view (engine.DepthView), metric Z"""
+    from . import engine
+    return engine.depth_view((0.0, 0.0, 0.0), RGBD_R, RGBD["width"], RGBD["height"], fov_hor_deg=RGBD["fov_hor_deg"])
+
+
+def _lattice(x, size_y, size_z, step):
+    ny, nz = int(round(size_y / step)), int(round(size_z / step))
+    y = (np.arange(ny + 1) - ny / 2.0) * step
+    z = (np.arange(nz + 1) - nz / 2.0) * step
+    yy, zz = np.meshgrid(y, z, indexing="ij")
+    return np.stack([np.full(yy.size, x), yy.ravel(), zz.ravel()], axis=1).astype(np.float32)
+
+
+def rgbd_wall():
+    """the back wall: a 0.1 m lattice at x = 8 covering the frustum, 16 m x 12 m"""
+    return _lattice(RGBD["wall_x"], *RGBD["wall_size"], RGBD["lattice"])
+
+
+def rgbd_obstacle():
+    """the obstacle: a 2 m x 2 m lattice at x = 5, centred on the optical axis"""
+    return _lattice(RGBD["obstacle_x"], RGBD["obstacle_size"], RGBD["obstacle_size"], RGBD["lattice"])
+
+
+def rgbd_scene(frame):
+    """the world at frame `frame`: the wall, and the obstacle while it is there (frames 0 to 2)"""
+    return np.concatenate([rgbd_wall(), rgbd_obstacle()]) if frame < RGBD["obstacle_frames"] else rgbd_wall()
+
+
+def run_rgbd_window_scenario(window, render, frames=6, carve=True, images=None, each=None):
+    """The reference's rgbd mode on a window that is never replaced: every frame the sensor hands over a depth image of the scene
+    (render(view, points) -> float32 [height, width], +inf where nothing is seen: a test-side renderer, the library renders
+    nothing), and the window takes it as clearSeenThrough(view, image, margin) then appendDepthImage(view, image) with de-dup on --
+    carve first, then append.  `window` is a SafeRegionRrtStar with its rolling map and setRollingDedup on, or anything with the
+    same two members and live_set().  carve = False leaves the carve out: the window then keeps the obstacle after it has left.
+    Returns the live set (a set of (x, y, z) tuples) after every frame; `images` (a list, optional) receives the images; `each`
+    (optional) is called as each(frame index, window) after every frame."""
+    view = rgbd_view()
+    out = []
+    for k in range(frames):
+        image = render(view, rgbd_scene(k))
+        if images is not None:
+            images.append(image)
+        if carve:
+            window.clearSeenThrough(view, image, RGBD["margin"])
+        window.appendDepthImage(view, image, float("inf"))
+        if hasattr(window, "live_set"):
+            out.append(window.live_set())
+        else:
+            _, _, xyz = window.cloud().radius_crop((0.0, 0.0, 0.0), 1.0e4)
+            out.append(set(map(tuple, xyz.tolist())))
+        if each is not None:
+            each(k, window)
+    return out
+
+
 def timed_scenario(finder, cloud1, expand=1500, refine=400):
     """run_scenario with wall-clock milliseconds per planner phase (bench.py / scripts/probe_corridor.py)"""
     import time
