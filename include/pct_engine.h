@@ -589,6 +589,9 @@ int pct_debug_read_grid(pct_cloud *c, uint32_t *cell_start, float *records);
  * out = {ids out of range, duplicated ids, records outside their cell's run, decreasing cell_start steps, cell_start[0],
  * cell_start[ncells]} -- a sound index gives {0, 0, 0, 0, 0, n} */
 int pct_debug_verify_grid(pct_cloud *c, uint64_t out[6]);
+/* the buffers the library holds at this moment, over every handle and its process-wide workspaces: blocks allocated and not yet
+ * freed, and their bytes (device, pinned and host-mapped memory together).  A handle that is closed gives all of its own back. */
+int pct_debug_live_buffers(int64_t *blocks, int64_t *bytes);
 /* work counters of the last instrumented batch: {points scanned, cell runs scanned, pyramid node visits (8 boxes of 32 B each)} */
 int pct_last_work_ex(pct_cloud *c, uint64_t out[3]);
 /* bounding-box pyramid over the cell index (built for sparsely occupied clouds; PCT_PYRAMID=0/1 never / always):

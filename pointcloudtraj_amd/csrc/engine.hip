@@ -12,6 +12,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -37,6 +38,10 @@
 #include "ring_search.hpp"
 
 using namespace pct;
+using pct_host::pow2_at_least;
+using pct_internal::DevBuf;
+using pct_internal::MappedBuf;
+using pct_internal::PinnedBuf;
 
 namespace {
 
@@ -69,23 +74,6 @@ constexpr int kMaxParts = 2048;       // streaming kernel: at most 8 blocks of 2
 constexpr int64_t kPartQueries = 16384;   // the partial buffers hold this many queries (400 MB); a 1 M-query reservation used to
                                           // take 26 GB of HBM for them
 constexpr int kBezierCapMax = 4096;
-
-template <typename T>
-int dev_alloc(T **p, size_t count)
-{
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(PCT_ERR_ALLOC, "hipMalloc(%zu bytes) -> %s", count * sizeof(T), hipGetErrorString(e));
-    *p = static_cast<T *>(v);
-    return PCT_OK;
-}
-
-template <typename T>
-void dev_free(T *&p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
@@ -126,118 +114,171 @@ constexpr int64_t kMappedMaxQ = 65536;    // host-buffer batches up to this size
 constexpr int64_t kSmallNNMax = 16384;    // clouds up to this size answer single queries with one-block kernels
 constexpr uint32_t kExpressIdsCap = 1u << 16;
 
-template <typename T>
-int mapped_alloc(T **host, T **dev, size_t count)
+bool poll_results()
 {
-    void *h = nullptr, *d = nullptr;
-    hipError_t e = hipHostMalloc(&h, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&d, h, 0);
-    if (e != hipSuccess) { if (h) (void)hipHostFree(h); return fail(PCT_ERR_ALLOC, "hipHostMalloc(mapped, %zu bytes) -> %s", count * sizeof(T), hipGetErrorString(e)); }
-    *host = static_cast<T *>(h);
-    *dev = static_cast<T *>(d);
+    static const bool v = [] { const char *e = std::getenv("PCT_POLL_RESULTS"); return e ? std::atoi(e) != 0 : true; }();
+    return v;
+}
+
+int sync_library_stream()
+{
+    HIPCHK(hipStreamSynchronize(g_stream));
     return PCT_OK;
 }
 
+// A {sequence, results...} completion word in host-mapped memory: the last block of a launch stores the launch's number into [0]
+// behind its results, and the host polls it (a stream synchronise costs ~20 us of host time more), falling back to the stream after
+// ~2 s of spinning or when polling is off.
+struct SeqWord {
+    MappedBuf<uint32_t> w;
+    uint32_t seq = 0;                            // the number of the last launch handed one
+    int ensure(size_t words)
+    {
+        if (w) return PCT_OK;
+        PCTCHK(w.reset(words));
+        for (size_t k = 0; k < words; k++) w.host()[k] = 0;
+        return PCT_OK;
+    }
+    uint32_t next() { return ++seq; }
+    // what: the launch stores its word whether polling is on or off, so a word that still differs behind the stream is an error
+    // named after it; nullptr: the launch is handed no word when polling is off, and the stream is the whole wait
+    int wait(uint32_t want, const char *what)
+    {
+        int st = PCT_OK;
+        const bool seen = pct_host::wait_word(w.host(), want, poll_results() ? 200000000l : 0l, [&] { st = sync_library_stream(); });
+        PCTCHK(st);
+        if (!seen && what) return fail(PCT_ERR_HIP, "%s finished without its sequence word (%u != %u)", what, w.host()[0], want);
+        return PCT_OK;
+    }
+};
+
+// Scratch of one order-preserving compaction of a frame (ring_dedup.hpp dd_rank / dd_tile_scan and a compacting kernel): keep flags,
+// ranks, tile totals and the packed xyz rows the insert kernel then reads.  ensure() allocates for exactly `cap` points; the caller
+// has chosen cap and synchronised.  A failure part-way leaves ncap 0.
+struct CompactScratch {
+    DevBuf<uint8_t> flags;
+    DevBuf<uint32_t> rank, tile;
+    DevBuf<float> out;
+    int64_t ncap = 0;                            // points the scratch holds
+    int ensure(int64_t cap)
+    {
+        ncap = 0;
+        flags.release(); rank.release(); tile.release(); out.release();
+        PCTCHK(flags.reset((size_t)cap));
+        PCTCHK(rank.reset((size_t)cap));
+        PCTCHK(tile.reset((size_t)ceil_div(cap, kDdTile)));
+        PCTCHK(out.reset(3 * (size_t)cap));
+        ncap = cap;
+        return PCT_OK;
+    }
+};
+
+// An image on its way to the device: the caller's floats are copied into pinned memory the library owns and from there to a device
+// buffer on the library's stream (both grow-only), so the caller's buffer is its own again at once and the kernels gather from HBM
+// / L2, not across the bus.  Every user waits for a kernel behind the copy before it returns: the pinned buffer is free by then.
+struct DepthStage {
+    PinnedBuf<float> h;
+    DevBuf<float> d;
+    size_t cap = 0;                              // floats
+};
+
 }  // namespace
+
+struct ReplanCtx;
 
 struct pct_cloud {
     int64_t cap = 0, cap4 = 0, count = 0, ring_next = 0;
     int64_t index_base = 0;
+    // coordinates: views of xyz_dev, or of xyz_map on "small" clouds, which keep them in host-mapped memory (kernels read them over
+    // the bus; the host appends with plain stores through hx / hy / hz and no launch) -- the RRT* node sets of the kd_* drop-in
     float *x = nullptr, *y = nullptr, *z = nullptr;
-    float4 *gb_tmp = nullptr;                   // index build scratch (gridbuild.hpp): slab-ordered records, kept between builds
-    size_t gb_tmp_cap = 0;
-    uint32_t *gb_small = nullptr;               // per-block slab table + slab totals / cursors / starts
-    size_t gb_small_cap = 0;
-    // "small" clouds keep their coordinates in host-mapped memory (kernels read them over the bus; the host
-    // appends with plain stores and no launch) -- the RRT* node sets of the kd_* drop-in
     bool host_mapped = false;
     float *hx = nullptr, *hy = nullptr, *hz = nullptr;
+    DevBuf<float> xyz_dev[3];
+    MappedBuf<float> xyz_map[3];
+    DevBuf<float4> gb_tmp;                      // index build scratch (gridbuild.hpp): slab-ordered records, kept between builds
+    DevBuf<uint32_t> gb_small;                  // per-block slab table + slab totals / cursors / starts
     // express path: host-mapped result / argument / id buffers
-    ExpressOut *h_xout = nullptr, *d_xout = nullptr;
-    double *h_xin = nullptr, *d_xin = nullptr, *h_xr = nullptr, *d_xr = nullptr;
-    uint32_t *h_xids = nullptr, *d_xids = nullptr;
-    uint32_t *h_xseq = nullptr, *d_xseq = nullptr, *d_xcounter = nullptr;     // completion word of the express launches (kernels.hpp ExpressSignal)
+    MappedBuf<ExpressOut> xout;
+    MappedBuf<double> xin, xr;
+    MappedBuf<uint32_t> xids;
+    SeqWord xseq;                               // completion word of the express launches (kernels.hpp ExpressSignal)
+    DevBuf<uint32_t> d_xcounter;
     // host-buffer batches of up to kMappedMaxQ queries: queries read from, results exported to, host-mapped memory (no DMA copies)
-    float *h_mq = nullptr, *d_mq = nullptr;
-    uint32_t *h_mi = nullptr, *d_mi = nullptr;
-    double *h_md = nullptr, *d_md = nullptr;
+    MappedBuf<float> mq;
+    MappedBuf<uint32_t> mi;
+    MappedBuf<double> md;
     int64_t mcap = 0;
-    unsigned char *h_frame = nullptr, *d_frame = nullptr;       // host-mapped staging of appended sensor frames (ring_append)
-    size_t frame_cap = 0;
-    unsigned char *h_astage = nullptr, *d_astage = nullptr;     // the library's own staging of copied frames
-    size_t astage_cap = 0;
+    MappedBuf<unsigned char> frame;             // host-mapped staging of appended sensor frames (ring_append)
+    MappedBuf<unsigned char> astage;            // the library's own staging of copied frames
     hipEvent_t ev_mut = nullptr;                                // recorded on the library's stream behind an asynchronous mutation
     bool mut_pending = false;                                   // ... which a call on another stream has to order itself behind
     bool append_pending = false;                                // ring_append returned before its insert kernel finished (ring_host.inc)
-    uint32_t xseq = 0;
     // fused RRT* expansion (small clouds = node sets): per-node {x, y, z, radius} as the planner holds them, and the results
-    double *h_aux = nullptr, *d_aux = nullptr;
-    ExpandOut *h_eout = nullptr, *d_eout = nullptr;
-    double *h_bpos = nullptr, *d_bpos = nullptr;        // express Bezier check: sample positions
-    unsigned char *d_stage = nullptr;
-    size_t stage_bytes = 0;
-    float *d_bbox = nullptr;                    // bounding-box partials of the index build (a buffer of their own, not the upload staging)
-    GbCheck *d_gbcheck = nullptr, *h_gbcheck = nullptr;     // the build's self-check (gridbuild.hpp): device words + pinned read-back
+    MappedBuf<double> aux;
+    MappedBuf<ExpandOut> eout;
+    MappedBuf<double> bpos;                     // express Bezier check: sample positions
+    DevBuf<unsigned char> d_stage;
+    DevBuf<float> d_bbox;                       // bounding-box partials of the index build (a buffer of their own, not the upload staging)
+    DevBuf<GbCheck> d_gbcheck;                  // the build's self-check (gridbuild.hpp): device words + pinned read-back
+    PinnedBuf<GbCheck> h_gbcheck;
     GbCheck last_check{};                       // as read back by the last build
     // bounding-box pyramid over the cell index (pyramid.hpp): built for clouds with sparse occupancy
     bool has_pyr = false;
     PyrDesc P{};
-    PyrNode *pyr_nodes = nullptr;
-    unsigned char *pyr_hint = nullptr;          // start level of the walk per level-0 cell
-    size_t pyr_cap = 0, pyr_total = 0, pyr_hint_cap = 0;
+    DevBuf<PyrNode> pyr_nodes;
+    DevBuf<unsigned char> pyr_hint;             // start level of the walk per level-0 cell
+    size_t pyr_total = 0;
     double empty_frac = 0.0;
     bool was_sparse = false;                    // the previous build found most cells empty: this one uses smaller cells
     // grid
     bool has_grid = false;
     GridDesc G{};
-    uint32_t *cell_start = nullptr;
-    size_t cells_cap = 0;
-    float4 *sorted = nullptr;
-    size_t sorted_cap = 0;
-    uint4 *blocks = nullptr;                 // block table (kernels.hpp block_corner_kernel): 2 x uint4 per lattice corner
-    size_t blocks_cap = 0;
+    DevBuf<uint32_t> cell_start;
+    DevBuf<float4> sorted;
+    DevBuf<uint4> blocks;                    // block table (kernels.hpp block_corner_kernel): 2 x uint4 per lattice corner
     BinDesc B{};
-    float4 *d_qsorted = nullptr;                                                // {x,y,z,id} records of the sorted batch (reserve_queries)
-    uint32_t *d_sort1 = nullptr;                                                // total1 | total1 (second set) | fill1
+    DevBuf<float4> d_qsorted;                                                   // {x,y,z,id} records of the sorted batch (reserve_queries)
+    DevBuf<uint32_t> d_sort1;                                                   // total1 | total1 (second set) | fill1
     int sort_phase = 0;                                                         // which set of totals the next batch adds into
-    // query workspaces
+    // query workspaces (one group: pct_cloud_reserve_queries)
     int64_t qcap = 0;
-    float *d_q = nullptr, *d_r = nullptr;
-    double *d_q64 = nullptr, *d_r2 = nullptr, *d_d2 = nullptr, *d_radius = nullptr, *d_pts64 = nullptr;
-    uint32_t *d_idx = nullptr, *d_count = nullptr, *d_bound = nullptr;
-    uint32_t *d_todo = nullptr;                                 // {count, ticket, slots...}: queries the fp32 pyramid walk leaves to the exact one
-    unsigned char *d_skip = nullptr;
-    double *d_part_d2 = nullptr;      // per-(query, block) partial minima of the streaming kernels: part_q x kMaxParts entries;
-    uint32_t *d_part_idx = nullptr;   // larger batches go through them in slices of part_q queries
+    DevBuf<float> d_q, d_r;
+    DevBuf<double> d_q64, d_r2, d_d2, d_radius, d_pts64;
+    DevBuf<uint32_t> d_idx, d_count, d_bound;
+    DevBuf<uint32_t> d_todo;                                    // {count, ticket, slots...}: queries the fp32 pyramid walk leaves to the exact one
+    DevBuf<unsigned char> d_skip;
+    DevBuf<double> d_part_d2;         // per-(query, block) partial minima of the streaming kernels: part_q x kMaxParts entries;
+    DevBuf<uint32_t> d_part_idx;      // larger batches go through them in slices of part_q queries
     int64_t part_q = 0;
-    uint32_t *d_ovf = nullptr;                                 // [0] = number of overflowed candidate lists, [1..] = their queries
-    uint32_t *d_cand_count = nullptr, *d_cand_idx = nullptr;   // candidate lists of the brute-force filter: part_q x kCandCap
-    double *d_cand_d2 = nullptr;
+    DevBuf<uint32_t> d_ovf;                                    // [0] = number of overflowed candidate lists, [1..] = their queries
+    DevBuf<uint32_t> d_cand_count, d_cand_idx;                 // candidate lists of the brute-force filter: part_q x kCandCap
+    DevBuf<double> d_cand_d2;
     // k-NN batches (knn.hpp): the host entry points' Q x k result rows and the streaming kernel's per-block partial lists (grow-only)
-    uint32_t *d_knn_idx = nullptr, *d_knn_pidx = nullptr;
-    double *d_knn_d2 = nullptr, *d_knn_pd2 = nullptr;
+    DevBuf<uint32_t> d_knn_idx, d_knn_pidx;
+    DevBuf<double> d_knn_d2, d_knn_pd2;
     size_t knn_out_cap = 0, knn_part_cap = 0;
     // radius-search batches (rsearch.hpp): scan / cursor / queue workspaces sized with the query workspaces, the host form's offsets
     // and the lists of its last result (12 B per entry, grow-only), valid until the cloud or its index changes
-    long long *rs_off = nullptr;
-    uint64_t *rs_tiles = nullptr;
-    uint32_t *rs_cursor = nullptr, *rs_queue = nullptr;
+    DevBuf<long long> rs_off;
+    DevBuf<uint64_t> rs_tiles;
+    DevBuf<uint32_t> rs_cursor, rs_queue;
     int64_t rs_qcap = 0;
-    uint32_t *rs_idx = nullptr;
-    double *rs_d2 = nullptr;
+    DevBuf<uint32_t> rs_idx;
+    DevBuf<double> rs_d2;
     size_t rs_cap = 0;
     int64_t rs_total = 0;
     bool rs_valid = false;
     // order-preserving crop (lidar): tile counts and the compacted {index, d2, x, y, z} of the last crop
-    uint32_t *crop_tile = nullptr, *crop_idx = nullptr;
-    double *crop_d2 = nullptr;
-    float *crop_x = nullptr, *crop_y = nullptr, *crop_z = nullptr;
-    size_t crop_tiles_cap = 0, crop_cap = 0;
+    DevBuf<uint32_t> crop_tile, crop_idx;
+    DevBuf<double> crop_d2;
+    DevBuf<float> crop_x, crop_y, crop_z;
+    size_t crop_cap = 0;
     // bezier
-    double *d_coef = nullptr, *d_segtime = nullptr;
-    int *d_orders = nullptr, *d_nsamples = nullptr;
-    long long *d_first_hit = nullptr;
-    size_t coef_cap = 0, seg_cap = 0;
+    DevBuf<double> d_coef, d_segtime;
+    DevBuf<int> d_orders, d_nsamples;
+    DevBuf<long long> d_first_hit;
+    size_t seg_cap = 0;
     // measurement
     hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the whole batch (all kernels of one query call)
     hipEvent_t ev2 = nullptr, ev3 = nullptr;    // around the batch's dominant kernel only (aliases of the ring's current pair)
@@ -251,7 +292,7 @@ struct pct_cloud {
     hipEvent_t last2 = nullptr, last3 = nullptr;    // the most recent COMPLETE pair (pct_last_kernel_ms)
     bool ev_valid = false, dom_valid = false;
     int timing_level = 1;                       // 0 = no events, 1 = dominant kernel only (default), 2 = + the whole batch
-    WorkCounters *d_work = nullptr;
+    DevBuf<WorkCounters> d_work;
     bool count_work = false;
     bool host_work = false;        // last batch's work is known on the host (streaming kernel)
     uint64_t host_points = 0;
@@ -269,50 +310,38 @@ struct pct_cloud {
     float ring_extent_req[3] = { 0.0f, 0.0f, 0.0f };
     RingDesc R{};
     size_t ring_cells = 0;
-    uint2 *ring_ht = nullptr;
-    float4 *ring_slots = nullptr, *ring_ovf = nullptr;
-    uint32_t *ring_where = nullptr;
-    RingState *ring_st = nullptr;
-    uint32_t *h_ring_status = nullptr, *d_ring_status = nullptr;      // host-mapped {overrun flag, overflow-queue length}
+    DevBuf<uint2> ring_ht;
+    DevBuf<float4> ring_slots, ring_ovf;
+    DevBuf<uint32_t> ring_where;
+    DevBuf<RingState> ring_st;
+    MappedBuf<uint32_t> ring_status;                                  // host-mapped {overrun flag, overflow-queue length}
     int64_t ring_cfg_count = 0;                                       // points in the window when the table was last sized
     int ring_appends_since_cfg = 0;
     // removing points (ring_remove.hpp, pct_cloud_ring_remove_*): removals since the last upload (the sizing box and a refile then
     // leave the removed rows out), the device words a removal's blocks meet on, the host-mapped {sequence, removed, live} the host
     // polls, and the staging of an index list
     bool ring_removed_any = false;
-    RingRemoveMeet *d_rm_meet = nullptr;
-    uint32_t *h_rm_word = nullptr, *d_rm_word = nullptr;
-    uint32_t rm_seq = 0;
-    uint32_t *d_rm_list = nullptr;
-    size_t rm_list_cap = 0;
+    DevBuf<RingRemoveMeet> d_rm_meet;
+    SeqWord rm_word;
+    DevBuf<uint32_t> d_rm_list;
     // de-duplicating appends (ring_dedup.hpp, pct_cloud_ring_dedup): voxel size (0 = off), the frame filter's scratch -- key table,
-    // per-point table slot / rank, tile totals, kept flags, the compacted frame -- and the host-mapped {sequence, survivors} pair
+    // per-point table slot, the compaction scratch (sized with it) -- and the host-mapped {sequence, survivors} pair
     double dd_res = 0.0;
-    unsigned long long *dd_keys = nullptr;
-    uint32_t *dd_vals = nullptr, *dd_pslot = nullptr, *dd_rank = nullptr, *dd_tile = nullptr;
-    uint8_t *dd_flags = nullptr;
-    float *dd_out = nullptr;
+    DevBuf<unsigned long long> dd_keys;
+    DevBuf<uint32_t> dd_vals, dd_pslot;
     uint32_t dd_tcap = 0;                    // entries of the key table
-    int64_t dd_ncap = 0;                     // points the per-point scratch holds
-    uint32_t *h_dd_word = nullptr, *d_dd_word = nullptr;
-    uint32_t dd_seq = 0;
+    CompactScratch dd;
+    SeqWord dd_word;
     int64_t dd_last_offered = 0, dd_last_kept = 0;
     uint64_t dd_total_offered = 0, dd_total_kept = 0;
-    // depth images (ring_depth.hpp, pct_cloud_ring_carve_depth / pct_cloud_append_depth): the image's pinned staging and its device copy,
-    // and the un-projection's scratch -- validity flags, ranks, tile totals and the packed frame the insert kernel reads (grow-only)
-    float *dp_himg = nullptr, *dp_dimg = nullptr;
-    size_t dp_img_cap = 0;
-    uint8_t *dp_flags = nullptr;
-    uint32_t *dp_rank = nullptr, *dp_tile = nullptr;
-    float *dp_out = nullptr;
-    int64_t dp_ncap = 0;
-    struct ReplanCtx *rp = nullptr;              // lazily created context of the un-captured fused planner batch
+    // depth images (ring_depth.hpp, pct_cloud_ring_carve_depth / pct_cloud_append_depth): the image's staging and the un-projection's
+    // compaction scratch.  Two instances: a depth append with de-dup on reads dp.out while the filter writes dd.out.
+    DepthStage dp_img;
+    CompactScratch dp;
+    ReplanCtx *rp = nullptr;                     // lazily created context of the un-captured fused planner batch
 };
 
-void depth_cloud_free(pct_cloud *c);             // ring_host.inc
-
-struct ReplanCtx;
-void replan_ctx_free(ReplanCtx *x);
+void replan_ctx_free(ReplanCtx *x);              // ring_host.inc
 
 struct pct_plan {
     int kind = 0;                                // 0 = NN batch, 1 = fused replan batch
@@ -322,59 +351,38 @@ struct pct_plan {
     double run_us[4] = { 0, 0, 0, 0 };
     pct_cloud *c = nullptr;
     int64_t Q = 0;
-    float *h_q = nullptr;
-    uint32_t *h_idx = nullptr;
-    double *h_d2 = nullptr;
-    float *d_q = nullptr;
-    uint32_t *d_idx = nullptr;
-    double *d_d2 = nullptr;
+    PinnedBuf<float> h_q;
+    PinnedBuf<uint32_t> h_idx;
+    PinnedBuf<double> h_d2;
+    DevBuf<float> d_q;
+    DevBuf<uint32_t> d_idx;
+    DevBuf<double> d_d2;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
 };
 
 namespace {
 
-bool poll_results()
-{
-    static const bool v = [] { const char *e = std::getenv("PCT_POLL_RESULTS"); return e ? std::atoi(e) != 0 : true; }();
-    return v;
-}
-
 // completion word for the next express launch on this cloud (seq = nullptr when polling is off: express_wait then synchronises)
 ExpressSignal next_signal(pct_cloud *c)
 {
-    ++c->xseq;
-    return ExpressSignal{ c->d_xcounter, poll_results() ? c->d_xseq : nullptr, c->xseq };
+    const uint32_t seq = c->xseq.next();
+    return ExpressSignal{ c->d_xcounter, poll_results() ? c->xseq.w.get() : nullptr, seq };
 }
 
-// wait for the express launch that carried next_signal(): spin on the host-mapped word its last block stores (a stream
-// synchronise costs ~20 us of host time more), falling back to the stream after ~2 s of spinning
-int express_wait(pct_cloud *c)
-{
-    if (poll_results()) {
-        const volatile uint32_t *seq = c->h_xseq;
-        for (long spins = 0; spins < 200000000l; spins++) {
-            if (*seq == c->xseq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); return PCT_OK; }
-            __builtin_ia32_pause();
-        }
-    }
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return PCT_OK;
-}
+// wait for the express launch that carried next_signal()
+int express_wait(pct_cloud *c) { return c->xseq.wait(c->xseq.seq, nullptr); }
 
 // host-mapped query / result buffers of the mid-size host-buffer batches (grow-only, power of two)
 int ensure_mapped_io(pct_cloud *c, int64_t Q)
 {
     if (Q <= c->mcap) return PCT_OK;
-    int64_t cap = 4096;
-    while (cap < Q) cap <<= 1;
-    if (c->h_mq) (void)hipHostFree(c->h_mq);
-    if (c->h_mi) (void)hipHostFree(c->h_mi);
-    if (c->h_md) (void)hipHostFree(c->h_md);
-    c->h_mq = nullptr; c->h_mi = nullptr; c->h_md = nullptr; c->mcap = 0;
-    PCTCHK(mapped_alloc(&c->h_mq, &c->d_mq, (size_t)(4 * cap)));          // 3 floats per query + a radius
-    PCTCHK(mapped_alloc(&c->h_mi, &c->d_mi, (size_t)cap));
-    PCTCHK(mapped_alloc(&c->h_md, &c->d_md, (size_t)cap));
+    const int64_t cap = pow2_at_least<int64_t>(4096, Q);
+    c->mcap = 0;
+    c->mq.release(); c->mi.release(); c->md.release();
+    PCTCHK(c->mq.reset((size_t)(4 * cap)));          // 3 floats per query + a radius
+    PCTCHK(c->mi.reset((size_t)cap));
+    PCTCHK(c->md.reset((size_t)cap));
     c->mcap = cap;
     return PCT_OK;
 }
@@ -411,15 +419,7 @@ int require_init()
     return PCT_OK;
 }
 
-int ensure_stage(pct_cloud *c, size_t bytes)
-{
-    if (bytes <= c->stage_bytes) return PCT_OK;
-    dev_free(c->d_stage);
-    c->stage_bytes = 0;
-    PCTCHK(dev_alloc(&c->d_stage, bytes));
-    c->stage_bytes = bytes;
-    return PCT_OK;
-}
+int ensure_stage(pct_cloud *c, size_t bytes) { return c->d_stage.reserve(bytes); }
 
 // Close a build: read the self-check back behind the last launch, synchronise, compare.  The ids of the records must sum and xor
 // to those of 0..n-1 and no record may sit outside its slab / cell; anything else is a wrong index and is reported, not served.
@@ -450,18 +450,8 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G)
     hipStream_t s = g_stream;
     const int64_t n = c->count;
     const uint64_t ncells = G.ncells;
-    if (ncells + 1 > c->cells_cap) {
-        dev_free(c->cell_start);
-        c->cells_cap = 0;
-        PCTCHK(dev_alloc(&c->cell_start, ncells + 1));
-        c->cells_cap = ncells + 1;
-    }
-    if ((size_t)n > c->sorted_cap) {
-        dev_free(c->sorted);
-        c->sorted_cap = 0;
-        PCTCHK(dev_alloc(&c->sorted, (size_t)n + kGridPad));         // + spare records behind the last one (gridbuild.hpp)
-        c->sorted_cap = (size_t)n;
-    }
+    PCTCHK(c->cell_start.reserve(ncells + 1));
+    if (n > 0) PCTCHK(c->sorted.reserve((size_t)n + kGridPad));      // + spare records behind the last one (gridbuild.hpp)
     // ---- two-level counting sort on LDS histograms (gridbuild.hpp): no device-scope atomic per point ----
     // slabs of 2^s1 consecutive cells, sized for ~2-6 k points each (level 2 then holds a whole slab in LDS), at most kGbMaxSlabs;
     // more, smaller slabs make level 1 slower (more open write streams, more LDS per block) faster than they help level 2
@@ -492,19 +482,8 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G)
             attr = true;
         }
         // scratch kept with the cloud (a rebuild per sensor frame must not pay hipMalloc / hipFree): records + table + slab counters
-        if ((size_t)n > c->gb_tmp_cap) {
-            dev_free(c->gb_tmp);
-            c->gb_tmp_cap = 0;
-            PCTCHK(dev_alloc(&c->gb_tmp, (size_t)n));
-            c->gb_tmp_cap = (size_t)n;
-        }
-        const size_t small_need = (size_t)blocks * D.nslabs + 3 * (size_t)D.nslabs + 8;
-        if (small_need > c->gb_small_cap) {
-            dev_free(c->gb_small);
-            c->gb_small_cap = 0;
-            PCTCHK(dev_alloc(&c->gb_small, small_need));
-            c->gb_small_cap = small_need;
-        }
+        PCTCHK(c->gb_tmp.reserve((size_t)n));
+        PCTCHK(c->gb_small.reserve((size_t)blocks * D.nslabs + 3 * (size_t)D.nslabs + 8));
         // level 1 in two passes of fan-out <= 128 when there are many slabs (gridbuild.hpp): pass A sorts by super-slab into the final
         // array (unused until level 2 writes it), pass B by slab inside every super-slab's region into gb_tmp
         uint32_t two_pass_min = 4096;                 // read per build: the tests lower it to reach this path with small clouds
@@ -523,12 +502,7 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G)
             DA.nslabs = DB.nsuper;
             const size_t nsub = (size_t)1 << DB.sb;
             const size_t need2 = (size_t)blocks * DA.nslabs + 3 * (size_t)DA.nslabs + 8 + (size_t)DB.nsuper * DB.parts * nsub + 3 * (size_t)D.nslabs + 8;
-            if (need2 > c->gb_small_cap) {
-                dev_free(c->gb_small);
-                c->gb_small_cap = 0;
-                PCTCHK(dev_alloc(&c->gb_small, need2));
-                c->gb_small_cap = need2;
-            }
+            PCTCHK(c->gb_small.reserve(need2));
             uint32_t *tableA = c->gb_small, *super_total = tableA + (size_t)blocks * DA.nslabs, *super_cursor = super_total + DA.nslabs,
                      *super_start = super_cursor + DA.nslabs, *table2 = super_start + DA.nslabs + 1,
                      *slab_total = table2 + (size_t)DB.nsuper * DB.parts * nsub, *slab_cursor = slab_total + D.nslabs, *slab_start = slab_cursor + D.nslabs;
@@ -564,12 +538,11 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G)
         return finish_build(c, G, e, s);
     }
     // ---- small clouds / very fine user-given cells: one device atomic per point and pass ----
-    uint32_t *d_cnt = nullptr, *d_pcell = nullptr, *d_tiles = nullptr;
+    DevBuf<uint32_t> d_cnt, d_pcell, d_tiles;          // (freed on every return; finish_build has synchronised by then)
     const uint32_t ntiles = (uint32_t)((ncells + kScanTile - 1) / kScanTile);
-    int st = dev_alloc(&d_cnt, ncells);
-    if (!st) st = dev_alloc(&d_pcell, (size_t)n);
-    if (!st) st = dev_alloc(&d_tiles, ntiles);
-    if (st) { dev_free(d_cnt); dev_free(d_pcell); dev_free(d_tiles); return st; }
+    PCTCHK(d_cnt.reset(ncells));
+    PCTCHK(d_pcell.reset((size_t)n));
+    PCTCHK(d_tiles.reset(ntiles));
     hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * ncells, s);
     const int pblocks = (int)std::min<int64_t>(4096, (n + 255) / 256);
     if (e == hipSuccess) {
@@ -585,9 +558,7 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G)
         gb_check_kernel<<<(int)std::min<int64_t>(1024, (std::max<int64_t>(n, (int64_t)ncells) + 255) / 256), 256, 0, s>>>(G, c->sorted, c->cell_start, (uint32_t)n, c->d_gbcheck);
         e = hipGetLastError();
     }
-    st = finish_build(c, G, e, s);
-    dev_free(d_cnt); dev_free(d_pcell); dev_free(d_tiles);
-    return st;
+    return finish_build(c, G, e, s);
 }
 
 void drop_grid(pct_cloud *c)
@@ -623,22 +594,12 @@ int build_pyramid(pct_cloud *c, const GridDesc &G)
         total += nslots[l];
     }
     if (total > 0xFFFFFFF0ull) return PCT_OK;      // cannot be addressed with 32-bit slot offsets: stay with the shell walk
-    if (total > c->pyr_cap) {
-        dev_free(c->pyr_nodes);
-        c->pyr_cap = 0;
-        PCTCHK(dev_alloc(&c->pyr_nodes, total));
-        c->pyr_cap = total;
-    }
+    PCTCHK(c->pyr_nodes.reserve(total));
     hipStream_t s = g_stream;
     pyr_leaf_kernel<<<ceil_div((int64_t)nslots[0], 32), 256, 0, s>>>(G, P, c->sorted, c->cell_start, c->pyr_nodes, (uint32_t)nslots[0]);
     for (int l = 1; l < nlev; l++)
         pyr_up_kernel<<<ceil_div((int64_t)nslots[l], 256), 256, 0, s>>>(G, P, l, c->pyr_nodes, (uint32_t)nslots[l]);
-    if ((size_t)G.ncells > c->pyr_hint_cap) {
-        dev_free(c->pyr_hint);
-        c->pyr_hint_cap = 0;
-        PCTCHK(dev_alloc(&c->pyr_hint, (size_t)G.ncells));
-        c->pyr_hint_cap = (size_t)G.ncells;
-    }
+    PCTCHK(c->pyr_hint.reserve((size_t)G.ncells));
     pyr_hint_kernel<<<ceil_div((int64_t)G.ncells, 256), 256, 0, s>>>(G, P, c->pyr_nodes, c->pyr_hint);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -665,7 +626,7 @@ int upload_range(pct_cloud *c, const void *pts, int64_t n, int64_t stride, int64
     HIPCHK(hipMemcpyAsync(c->d_stage, pts, (size_t)n * stride, hipMemcpyHostToDevice, g_stream));
     if (stride == 12 && (dst0 & 3) == 0 && n >= 4) {
         const uint32_t ng = (uint32_t)(n >> 2);
-        deinterleave12_kernel<<<ceil_div(ng, 256), 256, 0, g_stream>>>(reinterpret_cast<const float4 *>(c->d_stage), ng,
+        deinterleave12_kernel<<<ceil_div(ng, 256), 256, 0, g_stream>>>(reinterpret_cast<const float4 *>(c->d_stage.get()), ng,
                                                                         reinterpret_cast<float4 *>(c->x + dst0),
                                                                         reinterpret_cast<float4 *>(c->y + dst0),
                                                                         reinterpret_cast<float4 *>(c->z + dst0));
@@ -802,8 +763,10 @@ int launch_frame(pct_cloud *c, hipStream_t s, int64_t Q, Frame f, D dominant)
 // The dominant kernel of a Dom::Ext frame (blocks of 256 threads).  Where dom_begin left the region to the kernel, it is launched
 // with its own begin / end timestamps (hipExtLaunchKernel): no marker packets on the stream -- the two hipEventRecord calls of
 // dom_begin / dom_end cost ~10 us of a 160 us step.
-template <typename... P, typename... A>
-void launch_dominant(pct_cloud *c, hipStream_t s, void (*kernel)(P...), int blocks, A... args)
+// (the arguments arrive as the kernel's own parameter types: a buffer is handed over as its device pointer)
+template <typename T> struct as_declared { using type = T; };
+template <typename... P>
+void launch_dominant(pct_cloud *c, hipStream_t s, void (*kernel)(P...), int blocks, typename as_declared<P>::type... args)
 {
     if (!c->count_work && c->dom_valid && dom_ext_on()) {
         hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, args...);
@@ -962,8 +925,8 @@ int nn_stream_filtered_slice(pct_cloud *c, const float *d_qf, int64_t qoff, int6
             int sq = 0;
             const int sslices = slices_for(sblocks, &sq);
             nn_sample_bounds_kernel<<<dim3(sblocks, sslices), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, stride, d_qf, (int)Q, sq,
-                                                                           reinterpret_cast<float *>(c->d_part_idx), sblocks);
-            bound_reduce_kernel<<<(int)Q, 256, 0, s>>>(reinterpret_cast<const float *>(c->d_part_idx), sblocks, d_bound);
+                                                                           reinterpret_cast<float *>(c->d_part_idx.get()), sblocks);
+            bound_reduce_kernel<<<(int)Q, 256, 0, s>>>(reinterpret_cast<const float *>(c->d_part_idx.get()), sblocks, d_bound);
             expanded = use_expanded_filter(c, &CD);
             if (expanded) {
                 // expanded form (brute2.hpp): 3 FMAs per pair on centred coordinates, thresholds widened by the proven error band; the
@@ -1213,8 +1176,8 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
         break;
     }
     if (!c->d_knn_pd2) {
-        PCTCHK(dev_alloc(&c->d_knn_pd2, kKnnPartEntries));
-        PCTCHK(dev_alloc(&c->d_knn_pidx, kKnnPartEntries));
+        PCTCHK(c->d_knn_pd2.reset(kKnnPartEntries));
+        PCTCHK(c->d_knn_pidx.reset(kKnnPartEntries));
         c->knn_part_cap = kKnnPartEntries;
     }
     // one block per 4096 points, at most 256: a block's four waves then see enough points for their lists to settle
@@ -1239,12 +1202,12 @@ int rs_ensure_work(pct_cloud *c)
     if (c->rs_qcap >= c->qcap && c->rs_off) return PCT_OK;
     if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow workspaces during graph capture");
     const size_t q = (size_t)std::max<int64_t>(c->qcap, 256);
-    dev_free(c->rs_off); dev_free(c->rs_tiles); dev_free(c->rs_cursor); dev_free(c->rs_queue);
     c->rs_qcap = 0;
-    PCTCHK(dev_alloc(&c->rs_off, q + 1));
-    PCTCHK(dev_alloc(&c->rs_tiles, q / kRsScanTile + 2));
-    PCTCHK(dev_alloc(&c->rs_cursor, q));
-    PCTCHK(dev_alloc(&c->rs_queue, q + 1));
+    c->rs_off.release(); c->rs_tiles.release(); c->rs_cursor.release(); c->rs_queue.release();
+    PCTCHK(c->rs_off.reset(q + 1));
+    PCTCHK(c->rs_tiles.reset(q / kRsScanTile + 2));
+    PCTCHK(c->rs_cursor.reset(q));
+    PCTCHK(c->rs_queue.reset(q + 1));
     c->rs_qcap = (int64_t)q;
     return PCT_OK;
 }
@@ -1254,10 +1217,10 @@ int rs_ensure_lists(pct_cloud *c, size_t n)
 {
     if (n <= c->rs_cap) return PCT_OK;
     if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the radius-search lists during graph capture");
-    dev_free(c->rs_idx); dev_free(c->rs_d2);
     c->rs_cap = 0;
-    PCTCHK(dev_alloc(&c->rs_idx, n));
-    PCTCHK(dev_alloc(&c->rs_d2, n));
+    c->rs_idx.release(); c->rs_d2.release();
+    PCTCHK(c->rs_idx.reset(n));
+    PCTCHK(c->rs_d2.reset(n));
     c->rs_cap = n;
     return PCT_OK;
 }
@@ -1352,10 +1315,10 @@ int stage_queries(pct_cloud *c, const float *q, const float *r, int64_t Q, bool 
         return PCT_OK;
     }
     PCTCHK(ensure_mapped_io(c, Q));
-    std::memcpy(c->h_mq, q, sizeof(float) * 3 * (size_t)Q);
-    if (r) std::memcpy(c->h_mq + 3 * Q, r, sizeof(float) * (size_t)Q);
-    import_floats_kernel<<<ceil_div(3 * Q, 256), 256, 0, g_stream>>>(c->d_mq, (uint32_t)(3 * Q), c->d_q);
-    if (r) import_floats_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->d_mq + 3 * Q, (uint32_t)Q, c->d_r);
+    std::memcpy(c->mq.host(), q, sizeof(float) * 3 * (size_t)Q);
+    if (r) std::memcpy(c->mq.host() + 3 * Q, r, sizeof(float) * (size_t)Q);
+    import_floats_kernel<<<ceil_div(3 * Q, 256), 256, 0, g_stream>>>(c->mq, (uint32_t)(3 * Q), c->d_q);
+    if (r) import_floats_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(c->mq + 3 * Q, (uint32_t)Q, c->d_r);
     return PCT_OK;
 }
 
@@ -1369,21 +1332,21 @@ int fetch_results(pct_cloud *c, bool mapped, const uint32_t *d_u32, uint32_t *u3
         HIPCHK(hipStreamSynchronize(g_stream));
         return PCT_OK;
     }
-    export_results_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(d_u32, d_f64, (uint32_t)n, c->d_mi, d_f64 ? c->d_md : nullptr, next_signal(c));
+    export_results_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(d_u32, d_f64, (uint32_t)n, c->mi, d_f64 ? c->md : nullptr, next_signal(c));
     HIPCHK(hipGetLastError());
     PCTCHK(express_wait(c));
-    std::memcpy(u32, c->h_mi, sizeof(uint32_t) * (size_t)n);
-    if (d_f64) std::memcpy(f64, c->h_md, sizeof(double) * (size_t)n);
+    std::memcpy(u32, c->mi.host(), sizeof(uint32_t) * (size_t)n);
+    if (d_f64) std::memcpy(f64, c->md.host(), sizeof(double) * (size_t)n);
     return PCT_OK;
 }
 
-// the records of an express launch (c->h_xout, host-mapped) into the caller's arrays; a null array is not wanted
+// the records of an express launch (c->xout.host(), host-mapped) into the caller's arrays; a null array is not wanted
 void read_express_out(const pct_cloud *c, int64_t n, double *radius, uint32_t *idx, double *d2)
 {
     for (int64_t i = 0; i < n; i++) {
-        if (radius) radius[i] = c->h_xout[i].radius;
-        if (idx) idx[i] = c->h_xout[i].idx;
-        if (d2) d2[i] = c->h_xout[i].d2;
+        if (radius) radius[i] = c->xout.host()[i].radius;
+        if (idx) idx[i] = c->xout.host()[i].idx;
+        if (d2) d2[i] = c->xout.host()[i].d2;
     }
 }
 
@@ -1409,6 +1372,72 @@ int plan_capture(pct_plan *p, F enqueue)
     return PCT_OK;
 }
 
+// ---- host side of the sampled Bezier check, shared by its entry points (pinned bit for bit by tests/test_gpu_bezier_paths.py) ----
+int bezier_check_orders(const pct_bezier_traj *traj)
+{
+    for (int i = 0; i < traj->nseg; i++)
+        if (traj->orders[i] < 0 || traj->orders[i] > kMaxBezierOrder || 3 * (traj->orders[i] + 1) > traj->row_stride)
+            return fail(PCT_ERR_INVALID, "segment %d: order %d unsupported", i, traj->orders[i]);
+    return PCT_OK;
+}
+
+// the segment that holds t_start and the time into it (the segment search of checkSafeTrajectory, sim_planning_demo.cpp:729-771)
+int bezier_first_segment(const pct_bezier_traj *traj, double t_start, double *t_s_out)
+{
+    double t_s = t_start;
+    int first_seg;
+    for (first_seg = 0; first_seg < traj->nseg; ++first_seg) {
+        if (t_s > traj->seg_time[first_seg] && first_seg + 1 < traj->nseg) t_s -= traj->seg_time[first_seg];
+        else break;
+    }
+    *t_s_out = t_s;
+    return first_seg;
+}
+
+// the reference's nested sample loops (the same sequential fp64 additions as bezier_samples_kernel): emit(k, t, segment) for the
+// first `room` samples; returns the unclipped count
+template <typename Emit>
+int64_t bezier_enumerate_samples(const pct_bezier_traj *traj, double t_start, double stop_time, double dt, int64_t room, Emit emit)
+{
+    double t_s;
+    const int first_seg = bezier_first_segment(traj, t_start, &t_s);
+    int64_t n = 0;
+    double t_accu = 0.0;
+    for (int i = first_seg; i < traj->nseg; i++) {
+        const double T = traj->seg_time[i];
+        for (double t = (i == first_seg) ? t_s : 0.0; t < T; t += dt) {
+            t_accu += dt;
+            if (t_accu > stop_time) break;
+            if (n < room) emit(n, t, i);
+            n++;
+        }
+    }
+    return n;
+}
+
+// coefficients, segment times and orders into the cloud's device copies (grow-only) on stream s.  dev_form: earlier work on the
+// caller's streams may still read the old buffers, so the device is synchronised before they grow; the host form's earlier
+// work has been waited for by the call that queued it.
+int bezier_stage_coef(pct_cloud *c, const pct_bezier_traj *traj, hipStream_t s, bool dev_form)
+{
+    const size_t ncoef = (size_t)traj->nseg * traj->row_stride, nseg = (size_t)traj->nseg;
+    if (ncoef > c->d_coef.capacity() || nseg > c->seg_cap) {
+        if (dev_form) HIPCHK(hipDeviceSynchronize());
+        PCTCHK(c->d_coef.reserve(ncoef));
+        if (nseg > c->seg_cap) {
+            c->seg_cap = 0;
+            c->d_segtime.release(); c->d_orders.release();
+            PCTCHK(c->d_segtime.reset(nseg));
+            PCTCHK(c->d_orders.reset(nseg));
+            c->seg_cap = nseg;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(c->d_coef, traj->polycoef, sizeof(double) * ncoef, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_segtime, traj->seg_time, sizeof(double) * nseg, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_orders, traj->orders, sizeof(int) * nseg, hipMemcpyHostToDevice, s));
+    return PCT_OK;
+}
+
 }  // namespace
 
 #include "ring_host.inc"
@@ -1419,6 +1448,64 @@ int plan_capture(pct_plan *p, F enqueue)
 namespace pct_internal {
 hipStream_t stream() { return g_stream; }
 int require_init() { return ::require_init(); }
+
+// ---- the three kinds of memory (engine_internal.hpp); the only HIP allocation and free calls of the engine's host side ----
+namespace {
+std::atomic<int64_t> g_live_blocks{ 0 }, g_live_bytes{ 0 };
+void count_block(size_t bytes, int sign)
+{
+    g_live_blocks.fetch_add(sign, std::memory_order_relaxed);
+    g_live_bytes.fetch_add(sign * (int64_t)bytes, std::memory_order_relaxed);
+}
+}  // namespace
+
+int DeviceMem::alloc(size_t bytes, void **host, void **dev)
+{
+    *host = *dev = nullptr;
+    const hipError_t e = hipMalloc(dev, bytes);
+    if (e != hipSuccess) { *dev = nullptr; return fail(PCT_ERR_ALLOC, "hipMalloc(%zu bytes) -> %s", bytes, hipGetErrorString(e)); }
+    count_block(bytes, 1);
+    return PCT_OK;
+}
+void DeviceMem::release(void *, void *dev, size_t bytes)
+{
+    (void)hipFree(dev);
+    count_block(bytes, -1);
+}
+
+int PinnedMem::alloc(size_t bytes, void **host, void **dev)
+{
+    *host = *dev = nullptr;
+    const hipError_t e = hipHostMalloc(host, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) { *host = nullptr; return fail(PCT_ERR_ALLOC, "hipHostMalloc(%zu bytes) -> %s", bytes, hipGetErrorString(e)); }
+    *dev = *host;
+    count_block(bytes, 1);
+    return PCT_OK;
+}
+void PinnedMem::release(void *host, void *, size_t bytes)
+{
+    (void)hipHostFree(host);
+    count_block(bytes, -1);
+}
+
+int MappedMem::alloc(size_t bytes, void **host, void **dev)
+{
+    *host = *dev = nullptr;
+    hipError_t e = hipHostMalloc(host, bytes, hipHostMallocMapped);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(dev, *host, 0);
+    if (e != hipSuccess) {
+        if (*host) (void)hipHostFree(*host);
+        *host = *dev = nullptr;
+        return fail(PCT_ERR_ALLOC, "hipHostMalloc(mapped, %zu bytes) -> %s", bytes, hipGetErrorString(e));
+    }
+    count_block(bytes, 1);
+    return PCT_OK;
+}
+void MappedMem::release(void *host, void *, size_t bytes)
+{
+    (void)hipHostFree(host);
+    count_block(bytes, -1);
+}
 int fail(int code, const char *fmt, ...)
 {
     va_list ap;
@@ -1432,6 +1519,14 @@ int fail(int code, const char *fmt, ...)
 extern "C" {
 
 const char *pct_last_error(void) { return g_err; }
+
+int pct_debug_live_buffers(int64_t *blocks, int64_t *bytes)
+{
+    if (!blocks || !bytes) return fail(PCT_ERR_INVALID, "null output");
+    *blocks = pct_internal::g_live_blocks.load(std::memory_order_relaxed);
+    *bytes = pct_internal::g_live_bytes.load(std::memory_order_relaxed);
+    return PCT_OK;
+}
 
 
 int pct_device_count(void)
@@ -1471,23 +1566,25 @@ static int cloud_create_impl(int64_t capacity, bool host_mapped, pct_cloud **out
     c->cap = capacity;
     c->cap4 = (capacity + 3) & ~3ll;
     c->host_mapped = host_mapped;
-    int s;
-    if (host_mapped)
-        s = mapped_alloc(&c->hx, &c->x, (size_t)c->cap4 + 4) || mapped_alloc(&c->hy, &c->y, (size_t)c->cap4 + 4) ||
-            mapped_alloc(&c->hz, &c->z, (size_t)c->cap4 + 4);
-    else
-        s = dev_alloc(&c->x, (size_t)c->cap4 + 4) || dev_alloc(&c->y, (size_t)c->cap4 + 4) || dev_alloc(&c->z, (size_t)c->cap4 + 4);
-    if (!s) s = dev_alloc(&c->d_work, kWorkSlots);
-    if (!s) s = dev_alloc(&c->d_bbox, (size_t)1024 * 6);
-    if (!s) s = dev_alloc(&c->d_gbcheck, kGbCheckSlots);
-    if (!s && hipHostMalloc((void **)&c->h_gbcheck, sizeof(GbCheck) * kGbCheckSlots, hipHostMallocDefault) != hipSuccess) s = fail(PCT_ERR_ALLOC, "hipHostMalloc failed");
-    if (!s) s = mapped_alloc(&c->h_xout, &c->d_xout, kExpressMaxQ);
-    if (!s) s = mapped_alloc(&c->h_xin, &c->d_xin, 3 * kExpressMaxQ);
-    if (!s) s = mapped_alloc(&c->h_xr, &c->d_xr, kExpressMaxQ);
-    if (!s) s = mapped_alloc(&c->h_xids, &c->d_xids, kExpressIdsCap);
-    if (!s) s = mapped_alloc(&c->h_xseq, &c->d_xseq, 16);
-    if (!s) s = dev_alloc(&c->d_xcounter, 16);
-    if (!s) { *c->h_xseq = 0; if (hipMemset(c->d_xcounter, 0, 16 * sizeof(uint32_t)) != hipSuccess) s = fail(PCT_ERR_HIP, "hipMemset failed"); }
+    int s = PCT_OK;
+    for (int k = 0; k < 3 && !s; k++) s = host_mapped ? c->xyz_map[k].reset((size_t)c->cap4 + 4) : c->xyz_dev[k].reset((size_t)c->cap4 + 4);
+    if (host_mapped) {
+        c->hx = c->xyz_map[0].host(); c->hy = c->xyz_map[1].host(); c->hz = c->xyz_map[2].host();
+        c->x = c->xyz_map[0]; c->y = c->xyz_map[1]; c->z = c->xyz_map[2];
+    } else {
+        c->x = c->xyz_dev[0]; c->y = c->xyz_dev[1]; c->z = c->xyz_dev[2];
+    }
+    if (!s) s = c->d_work.reset(kWorkSlots);
+    if (!s) s = c->d_bbox.reset((size_t)1024 * 6);
+    if (!s) s = c->d_gbcheck.reset(kGbCheckSlots);
+    if (!s) s = c->h_gbcheck.reset(kGbCheckSlots);
+    if (!s) s = c->xout.reset(kExpressMaxQ);
+    if (!s) s = c->xin.reset(3 * kExpressMaxQ);
+    if (!s) s = c->xr.reset(kExpressMaxQ);
+    if (!s) s = c->xids.reset(kExpressIdsCap);
+    if (!s) s = c->xseq.ensure(16);
+    if (!s) s = c->d_xcounter.reset(16);
+    if (!s && hipMemset(c->d_xcounter, 0, 16 * sizeof(uint32_t)) != hipSuccess) s = fail(PCT_ERR_HIP, "hipMemset failed");
     if (s) {
         pct_cloud_destroy(c);
         return PCT_ERR_ALLOC;
@@ -1516,49 +1613,8 @@ int pct_cloud_destroy(pct_cloud *c)
 {
     if (!c) return PCT_OK;
     if (g_stream) (void)hipStreamSynchronize(g_stream);
-    if (c->host_mapped) {
-        if (c->hx) (void)hipHostFree(c->hx);
-        if (c->hy) (void)hipHostFree(c->hy);
-        if (c->hz) (void)hipHostFree(c->hz);
-        c->x = c->y = c->z = nullptr;
-    }
-    if (c->h_xout) (void)hipHostFree(c->h_xout);
-    if (c->h_xin) (void)hipHostFree(c->h_xin);
-    if (c->h_xr) (void)hipHostFree(c->h_xr);
-    if (c->h_xids) (void)hipHostFree(c->h_xids);
-    if (c->h_xseq) (void)hipHostFree(c->h_xseq);
     if (c->ev_mut) (void)hipEventDestroy(c->ev_mut);
-    if (c->h_frame) (void)hipHostFree(c->h_frame);
-    if (c->h_astage) (void)hipHostFree(c->h_astage);
-    if (c->h_mq) (void)hipHostFree(c->h_mq);
-    if (c->h_mi) (void)hipHostFree(c->h_mi);
-    if (c->h_md) (void)hipHostFree(c->h_md);
-    dev_free(c->d_xcounter);
-    if (c->h_aux) (void)hipHostFree(c->h_aux);
-    if (c->h_eout) (void)hipHostFree(c->h_eout);
-    if (c->h_bpos) (void)hipHostFree(c->h_bpos);
-    dev_free(c->x); dev_free(c->y); dev_free(c->z); dev_free(c->d_stage); dev_free(c->gb_tmp); dev_free(c->gb_small);
-    dev_free(c->blocks);
-    dev_free(c->cell_start); dev_free(c->sorted);
-    dev_free(c->d_qsorted); dev_free(c->d_sort1); dev_free(c->d_todo);
-    dev_free(c->d_q); dev_free(c->d_r); dev_free(c->d_q64); dev_free(c->d_r2); dev_free(c->d_d2); dev_free(c->d_radius);
-    dev_free(c->d_pts64); dev_free(c->d_idx); dev_free(c->d_count); dev_free(c->d_skip); dev_free(c->d_bound);
-    dev_free(c->d_part_d2); dev_free(c->d_part_idx); dev_free(c->d_cand_count); dev_free(c->d_cand_d2); dev_free(c->d_cand_idx); dev_free(c->d_ovf);
-    dev_free(c->d_coef); dev_free(c->d_segtime); dev_free(c->d_orders); dev_free(c->d_nsamples); dev_free(c->d_first_hit);
-    dev_free(c->d_work);
-    dev_free(c->d_knn_idx); dev_free(c->d_knn_d2); dev_free(c->d_knn_pidx); dev_free(c->d_knn_pd2);
-    dev_free(c->rs_off); dev_free(c->rs_tiles); dev_free(c->rs_cursor); dev_free(c->rs_queue); dev_free(c->rs_idx); dev_free(c->rs_d2);
-    dev_free(c->d_bbox); dev_free(c->d_gbcheck); dev_free(c->pyr_nodes); dev_free(c->pyr_hint);
-    if (c->h_gbcheck) (void)hipHostFree(c->h_gbcheck);
-    dev_free(c->ring_ht); dev_free(c->ring_slots); dev_free(c->ring_ovf); dev_free(c->ring_where); dev_free(c->ring_st);
-    if (c->h_ring_status) (void)hipHostFree(c->h_ring_status);
-    dev_free(c->d_rm_meet); dev_free(c->d_rm_list);
-    if (c->h_rm_word) (void)hipHostFree(c->h_rm_word);
-    dev_free(c->dd_keys); dev_free(c->dd_vals); dev_free(c->dd_pslot); dev_free(c->dd_rank); dev_free(c->dd_tile); dev_free(c->dd_flags); dev_free(c->dd_out);
-    if (c->h_dd_word) (void)hipHostFree(c->h_dd_word);
-    depth_cloud_free(c);
     replan_ctx_free(c->rp);
-    dev_free(c->crop_tile); dev_free(c->crop_idx); dev_free(c->crop_d2); dev_free(c->crop_x); dev_free(c->crop_y); dev_free(c->crop_z);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->dom_ring) if (e) (void)hipEventDestroy(e);
@@ -1667,36 +1723,37 @@ int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)
     if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow workspaces during graph capture");
     HIPCHK(hipStreamSynchronize(g_stream));
     const int64_t q = std::max<int64_t>(Q, 256);
-    dev_free(c->d_q); dev_free(c->d_r); dev_free(c->d_q64); dev_free(c->d_r2); dev_free(c->d_d2); dev_free(c->d_radius);
-    dev_free(c->d_pts64); dev_free(c->d_idx); dev_free(c->d_count); dev_free(c->d_skip); dev_free(c->d_bound);
-    dev_free(c->d_part_d2); dev_free(c->d_part_idx); dev_free(c->d_cand_count); dev_free(c->d_cand_d2); dev_free(c->d_cand_idx); dev_free(c->d_ovf); dev_free(c->d_qsorted); dev_free(c->d_todo);
     c->qcap = 0;
     c->generation++;                    // captured plans hold these pointers
-    PCTCHK(dev_alloc(&c->d_q, 3 * q));
-    PCTCHK(dev_alloc(&c->d_r, q));
-    PCTCHK(dev_alloc(&c->d_q64, 3 * q));
-    PCTCHK(dev_alloc(&c->d_r2, q));
-    PCTCHK(dev_alloc(&c->d_d2, q));
-    PCTCHK(dev_alloc(&c->d_radius, q));
-    PCTCHK(dev_alloc(&c->d_pts64, 3 * q));
-    PCTCHK(dev_alloc(&c->d_idx, q));
-    PCTCHK(dev_alloc(&c->d_count, q));
-    PCTCHK(dev_alloc(&c->d_skip, q));
-    PCTCHK(dev_alloc(&c->d_bound, q));
-    PCTCHK(dev_alloc(&c->d_qsorted, q));
-    PCTCHK(dev_alloc(&c->d_todo, 2 * q + 16));
+    c->d_q.release(); c->d_r.release(); c->d_q64.release(); c->d_r2.release(); c->d_d2.release(); c->d_radius.release();
+    c->d_pts64.release(); c->d_idx.release(); c->d_count.release(); c->d_skip.release(); c->d_bound.release();
+    c->d_part_d2.release(); c->d_part_idx.release(); c->d_cand_count.release(); c->d_cand_d2.release(); c->d_cand_idx.release();
+    c->d_ovf.release(); c->d_qsorted.release(); c->d_todo.release();
+    PCTCHK(c->d_q.reset(3 * q));
+    PCTCHK(c->d_r.reset(q));
+    PCTCHK(c->d_q64.reset(3 * q));
+    PCTCHK(c->d_r2.reset(q));
+    PCTCHK(c->d_d2.reset(q));
+    PCTCHK(c->d_radius.reset(q));
+    PCTCHK(c->d_pts64.reset(3 * q));
+    PCTCHK(c->d_idx.reset(q));
+    PCTCHK(c->d_count.reset(q));
+    PCTCHK(c->d_skip.reset(q));
+    PCTCHK(c->d_bound.reset(q));
+    PCTCHK(c->d_qsorted.reset(q));
+    PCTCHK(c->d_todo.reset(2 * q + 16));
     HIPCHK(hipMemset(c->d_todo, 0, sizeof(uint32_t) * 16));            // count and ticket: the exact-walk kernel leaves them zero after every batch
     if (!c->d_sort1) {
-        PCTCHK(dev_alloc(&c->d_sort1, 3 * kSortBuckets));
+        PCTCHK(c->d_sort1.reset(3 * kSortBuckets));
         HIPCHK(hipMemset(c->d_sort1, 0, sizeof(uint32_t) * 3 * kSortBuckets));   // the sort keeps both sets of totals zero between batches
     }
     c->part_q = std::min<int64_t>(q, kPartQueries);
-    PCTCHK(dev_alloc(&c->d_part_d2, (size_t)c->part_q * kMaxParts));
-    PCTCHK(dev_alloc(&c->d_part_idx, (size_t)c->part_q * kMaxParts));
-    PCTCHK(dev_alloc(&c->d_ovf, (size_t)c->part_q + 1));
-    PCTCHK(dev_alloc(&c->d_cand_count, (size_t)c->part_q));
-    PCTCHK(dev_alloc(&c->d_cand_d2, (size_t)c->part_q * kCandCap));
-    PCTCHK(dev_alloc(&c->d_cand_idx, (size_t)c->part_q * kCandCap));
+    PCTCHK(c->d_part_d2.reset((size_t)c->part_q * kMaxParts));
+    PCTCHK(c->d_part_idx.reset((size_t)c->part_q * kMaxParts));
+    PCTCHK(c->d_ovf.reset((size_t)c->part_q + 1));
+    PCTCHK(c->d_cand_count.reset((size_t)c->part_q));
+    PCTCHK(c->d_cand_d2.reset((size_t)c->part_q * kCandCap));
+    PCTCHK(c->d_cand_idx.reset((size_t)c->part_q * kCandCap));
     HIPCHK(hipMemset(c->d_cand_count, 0, sizeof(uint32_t) * (size_t)c->part_q));     // the reduce kernel keeps it zero between slices
     c->qcap = q;
     return PCT_OK;
@@ -1734,7 +1791,7 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     // 1. bounding box
     const int bblocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
     PCTCHK(ensure_stage(c, sizeof(float) * (size_t)bblocks * 6));     // the upload staging buffer is idle here: no allocation per build
-    float *d_part = reinterpret_cast<float *>(c->d_stage);
+    float *d_part = reinterpret_cast<float *>(c->d_stage.get());
     bbox_partial_kernel<false><<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
     std::vector<float> part((size_t)bblocks * 6);
     hipError_t e = hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(float), hipMemcpyDeviceToHost, s);
@@ -1808,12 +1865,7 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
         const bool table_on = et ? std::atoi(et) != 0 : false;
         const uint64_t ncorners = (uint64_t)(G.gx + 1) * (uint64_t)(G.gy + 1) * (uint64_t)(G.gz + 1);
         if (table_on && G.octant_first && !c->has_pyr && ncorners < 0x7FFFFFF0ull) {
-            if ((size_t)(2 * ncorners) > c->blocks_cap) {
-                dev_free(c->blocks);
-                c->blocks_cap = 0;
-                PCTCHK(dev_alloc(&c->blocks, (size_t)(2 * ncorners)));
-                c->blocks_cap = (size_t)(2 * ncorners);
-            }
+            PCTCHK(c->blocks.reserve((size_t)(2 * ncorners)));
             block_corner_kernel<<<ceil_div((int64_t)ncorners, 256), 256, 0, s>>>(G, c->cell_start, c->blocks, (uint32_t)ncorners);
             HIPCHK(hipGetLastError());
             PCTCHK(note_mutation(c));            // queued, not awaited: a *_dev call on another stream waits on the event
@@ -1862,13 +1914,13 @@ int pct_nn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, uint32_
     PCTCHK(resolve_algo(c, Op::NN, algo, Q, &path));
     if (Q <= kExpressMaxQ && (path == Path::Table || path == Path::Grid)) {
         // small batch on an indexed cloud: one launch, a block per query, arguments/results in mapped memory
-        for (int64_t i = 0; i < 3 * Q; i++) c->h_xin[i] = (double)q[i];
+        for (int64_t i = 0; i < 3 * Q; i++) c->xin.host()[i] = (double)q[i];
         if (path == Path::Table)
-            ring_batch_kernel<false><<<(int)Q, 256, 0, g_stream>>>(ring_view(c), InflateParams{}, nullptr, c->d_xin, (double)INFINITY, (uint32_t)c->index_base,
-                                                                   nullptr, nullptr, nullptr, c->d_xout, next_signal(c));
+            ring_batch_kernel<false><<<(int)Q, 256, 0, g_stream>>>(ring_view(c), InflateParams{}, nullptr, c->xin, (double)INFINITY, (uint32_t)c->index_base,
+                                                                   nullptr, nullptr, nullptr, c->xout, next_signal(c));
         else
-            inflate_block_kernel<false><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, InflateParams{}, c->d_xin, (double)INFINITY,
-                                                                       (uint32_t)c->index_base, c->d_xout, next_signal(c));
+            inflate_block_kernel<false><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, InflateParams{}, c->xin, (double)INFINITY,
+                                                                       (uint32_t)c->index_base, c->xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
         read_express_out(c, Q, nullptr, idx, d2);
@@ -1906,10 +1958,10 @@ int pct_knn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, int32_
     const size_t rows = (size_t)Q * (size_t)k;
     if (rows > c->knn_out_cap) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        dev_free(c->d_knn_idx); dev_free(c->d_knn_d2);
         c->knn_out_cap = 0;
-        PCTCHK(dev_alloc(&c->d_knn_idx, rows));
-        PCTCHK(dev_alloc(&c->d_knn_d2, rows));
+        c->d_knn_idx.release(); c->d_knn_d2.release();
+        PCTCHK(c->d_knn_idx.reset(rows));
+        PCTCHK(c->d_knn_d2.reset(rows));
         c->knn_out_cap = rows;
     }
     HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
@@ -2011,20 +2063,20 @@ int pct_nn_batch_q64_ties(pct_cloud *c, const double *q, int64_t Q, uint32_t *id
         return fail(PCT_ERR_EMPTY, "nearest-neighbour query against an empty cloud");
     }
     if (Q > 1 && Q <= kExpressMaxQ && c->count <= kSmallNNMax) {   // express batch: a block per query, everything in mapped memory
-        std::memcpy(c->h_xin, q, sizeof(double) * 3 * Q);
-        nn_small_batch_kernel<<<(int)Q, 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_xin, (uint32_t)c->index_base, c->d_xout, next_signal(c));
+        std::memcpy(c->xin.host(), q, sizeof(double) * 3 * Q);
+        nn_small_batch_kernel<<<(int)Q, 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->xin, (uint32_t)c->index_base, c->xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
         read_express_out(c, Q, nullptr, idx, d2);
         return PCT_OK;
     }
     if (Q == 1 && c->count <= kSmallNNMax) {   // express: one one-block launch, query by value, result in mapped memory
-        nn_small_kernel<<<1, 1024, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, q[0], q[1], q[2], (uint32_t)c->index_base, c->d_xout, next_signal(c));
+        nn_small_kernel<<<1, 1024, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, q[0], q[1], q[2], (uint32_t)c->index_base, c->xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
-        idx[0] = c->h_xout[0].idx;
-        d2[0] = c->h_xout[0].d2;
-        if (ties) ties[0] = c->h_xout[0].count;
+        idx[0] = c->xout.host()[0].idx;
+        d2[0] = c->xout.host()[0].d2;
+        if (ties) ties[0] = c->xout.host()[0].count;
         return PCT_OK;
     }
     // The fp32 filter is only valid when the query coordinates themselves are fp32 values
@@ -2067,18 +2119,13 @@ static int crop_device(pct_cloud *c, const double q[3], double rr, int64_t *tota
 {
     const uint32_t n = (uint32_t)c->count;
     const uint32_t ntiles = (n + kCropTile - 1) / kCropTile;
-    if ((size_t)ntiles + 1 > c->crop_tiles_cap) {
-        dev_free(c->crop_tile);
-        c->crop_tiles_cap = 0;
-        PCTCHK(dev_alloc(&c->crop_tile, (size_t)ntiles + 1));
-        c->crop_tiles_cap = (size_t)ntiles + 1;
-    }
+    PCTCHK(c->crop_tile.reserve((size_t)ntiles + 1));
     if ((size_t)n > c->crop_cap) {
-        dev_free(c->crop_idx); dev_free(c->crop_d2); dev_free(c->crop_x); dev_free(c->crop_y); dev_free(c->crop_z);
         c->crop_cap = 0;
+        c->crop_idx.release(); c->crop_d2.release(); c->crop_x.release(); c->crop_y.release(); c->crop_z.release();
         const size_t cap = std::max<size_t>((size_t)c->cap, n);
-        PCTCHK(dev_alloc(&c->crop_idx, cap)); PCTCHK(dev_alloc(&c->crop_d2, cap));
-        PCTCHK(dev_alloc(&c->crop_x, cap)); PCTCHK(dev_alloc(&c->crop_y, cap)); PCTCHK(dev_alloc(&c->crop_z, cap));
+        PCTCHK(c->crop_idx.reset(cap)); PCTCHK(c->crop_d2.reset(cap));
+        PCTCHK(c->crop_x.reset(cap)); PCTCHK(c->crop_y.reset(cap)); PCTCHK(c->crop_z.reset(cap));
         c->crop_cap = cap;
     }
     begin_timing(c, g_stream);
@@ -2115,11 +2162,11 @@ int pct_radius_indices_r2_q64(pct_cloud *c, const double q[3], double r2, uint32
     if (c->count == 0) return PCT_OK;
     if (c->count <= 4 * kSmallNNMax && c->count <= (int64_t)kExpressIdsCap) {   // express: one launch, ids in mapped memory
         radius_small_kernel<<<1, 1024, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, q[0], q[1], q[2], r2, (uint32_t)c->index_base,
-                                                       c->d_xids, kExpressIdsCap, c->d_xout, next_signal(c));
+                                                       c->xids, kExpressIdsCap, c->xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
-        const int64_t total = c->h_xout[0].count, got = std::min<int64_t>(total, cap);
-        std::copy(c->h_xids, c->h_xids + std::min<int64_t>(got, kExpressIdsCap), idx_out);
+        const int64_t total = c->xout.host()[0].count, got = std::min<int64_t>(total, cap);
+        std::copy(c->xids.host(), c->xids.host() + std::min<int64_t>(got, kExpressIdsCap), idx_out);
         std::sort(idx_out, idx_out + got);
         *n_out = total;
         return PCT_OK;
@@ -2194,16 +2241,16 @@ int pct_radius_indices_batch_q64(pct_cloud *c, const double *q, const double *r,
     for (int64_t k = 0; k < K; k++) counts_out[k] = 0;
     if (c->count == 0) return PCT_OK;
     const uint32_t cap = (uint32_t)std::min<int64_t>(cap_per_query, kExpressIdsCap / K);
-    std::memcpy(c->h_xin, q, sizeof(double) * 3 * K);
-    std::memcpy(c->h_xr, r, sizeof(double) * K);
-    radius_small_batch_kernel<<<(int)K, 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_xin, c->d_xr, (uint32_t)c->index_base,
-                                                            c->d_xids, cap, c->d_xout, next_signal(c));
+    std::memcpy(c->xin.host(), q, sizeof(double) * 3 * K);
+    std::memcpy(c->xr.host(), r, sizeof(double) * K);
+    radius_small_batch_kernel<<<(int)K, 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->xin, c->xr, (uint32_t)c->index_base,
+                                                            c->xids, cap, c->xout, next_signal(c));
     HIPCHK(hipGetLastError());
     PCTCHK(express_wait(c));
     for (int64_t k = 0; k < K; k++) {
-        counts_out[k] = c->h_xout[k].count;
+        counts_out[k] = c->xout.host()[k].count;
         const int64_t got = std::min<int64_t>(counts_out[k], cap);
-        std::copy(c->h_xids + k * cap, c->h_xids + k * cap + got, ids_out + k * cap_per_query);
+        std::copy(c->xids.host() + k * cap, c->xids.host() + k * cap + got, ids_out + k * cap_per_query);
         if (counts_out[k] > cap) counts_out[k] = -counts_out[k];      // negative = truncated: the caller must re-ask that query alone
     }
     return PCT_OK;
@@ -2218,9 +2265,9 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
     const double stop_d2 = (idx || d2) ? (double)INFINITY : reach * reach;
     if (c->ring_ready) {          // rolling map: a block per point over the bucket table; small batches through mapped memory
         if (Q <= kExpressMaxQ) {
-            std::memcpy(c->h_xin, pts, sizeof(double) * 3 * Q);
-            ring_batch_kernel<true><<<(int)Q, 256, 0, g_stream>>>(ring_view(c), to_dev(p), nullptr, c->d_xin, stop_d2, (uint32_t)c->index_base, nullptr, nullptr,
-                                                                  nullptr, c->d_xout, next_signal(c));
+            std::memcpy(c->xin.host(), pts, sizeof(double) * 3 * Q);
+            ring_batch_kernel<true><<<(int)Q, 256, 0, g_stream>>>(ring_view(c), to_dev(p), nullptr, c->xin, stop_d2, (uint32_t)c->index_base, nullptr, nullptr,
+                                                                  nullptr, c->xout, next_signal(c));
             HIPCHK(hipGetLastError());
             PCTCHK(express_wait(c));
             read_express_out(c, Q, radius, idx, d2);
@@ -2238,8 +2285,8 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
         return PCT_OK;
     }
     if (Q <= kExpressMaxQ && c->has_grid && c->count > 0) {   // express: one fused launch (a block per point), arguments and results in mapped memory
-        std::memcpy(c->h_xin, pts, sizeof(double) * 3 * Q);
-        inflate_block_kernel<true><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, to_dev(p), c->d_xin, stop_d2, (uint32_t)c->index_base, c->d_xout, next_signal(c));
+        std::memcpy(c->xin.host(), pts, sizeof(double) * 3 * Q);
+        inflate_block_kernel<true><<<(int)Q, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, to_dev(p), c->xin, stop_d2, (uint32_t)c->index_base, c->xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
         read_express_out(c, Q, radius, idx, d2);
@@ -2247,8 +2294,8 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
     }
     PCTCHK(pct_cloud_reserve_queries(c, Q));
     if (Q <= kExpressMaxQ) {      // small batch on an un-indexed (e.g. rolling) cloud: brute-force kernels, arguments and results in mapped memory
-        std::memcpy(c->h_xin, pts, sizeof(double) * 3 * Q);
-        PCTCHK(inflate_dev(c, p, Q, g_stream, c->d_xin, c->d_xout));
+        std::memcpy(c->xin.host(), pts, sizeof(double) * 3 * Q);
+        PCTCHK(inflate_dev(c, p, Q, g_stream, c->xin, c->xout));
         HIPCHK(hipStreamSynchronize(g_stream));
         read_express_out(c, Q, radius, idx, d2);
         return PCT_OK;
@@ -2267,8 +2314,8 @@ int pct_cloud_small_aux(pct_cloud *nodes, double **host_aux)
 {
     if (!nodes || !host_aux) return fail(PCT_ERR_INVALID, "null argument");
     if (!nodes->host_mapped) return fail(PCT_ERR_INVALID, "per-node planner data lives beside small (host-mapped) clouds only");
-    if (!nodes->h_aux) PCTCHK(mapped_alloc(&nodes->h_aux, &nodes->d_aux, (size_t)4 * (size_t)nodes->cap));
-    *host_aux = nodes->h_aux;
+    if (!nodes->aux) PCTCHK(nodes->aux.reset((size_t)4 * (size_t)nodes->cap));
+    *host_aux = nodes->aux.host();
     return PCT_OK;
 }
 
@@ -2278,7 +2325,7 @@ int pct_rrt_expand_batch(pct_cloud *nodes, pct_cloud *obstacles, const pct_infla
     if (!nodes || !obstacles || !p || K < 0 || (K > 0 && (!samples || !out || !ids)) || cap_per_query <= 0) return fail(PCT_ERR_INVALID, "bad expand arguments");
     if (K == 0) return PCT_OK;
     if (K > kExpressMaxQ) return fail(PCT_ERR_INVALID, "at most %d samples per expansion launch", kExpressMaxQ);
-    if (!nodes->host_mapped || (nodes->count > 0 && !nodes->h_aux)) return fail(PCT_ERR_INVALID, "the node set must be a small cloud with per-node planner data (pct_cloud_small_aux)");
+    if (!nodes->host_mapped || (nodes->count > 0 && !nodes->aux.host())) return fail(PCT_ERR_INVALID, "the node set must be a small cloud with per-node planner data (pct_cloud_small_aux)");
     // Rolling map: an append that returned with its insert kernel still queued is finished first -- its status words are read and the
     // bookkeeping they ask for (larger buckets, a re-sized table: new pointers, a new generation) happens BEFORE the view below is
     // taken.  The completion word this call waits on is the node cloud's; it says nothing about the obstacle cloud's append.
@@ -2287,23 +2334,23 @@ int pct_rrt_expand_batch(pct_cloud *nodes, pct_cloud *obstacles, const pct_infla
     if (!ring && obstacles->count > 0 && !obstacles->has_grid)
         return fail(PCT_ERR_INVALID, "the obstacle cloud has no index (pct_cloud_build_grid or pct_cloud_ring_index): the fused step searches one; "
                                      "the staged queries (pct_nn_batch, pct_inflate_batch, pct_radius_*) answer without");
-    if (!nodes->h_eout) PCTCHK(mapped_alloc(&nodes->h_eout, &nodes->d_eout, (size_t)kExpressMaxQ));
+    if (!nodes->eout) PCTCHK(nodes->eout.reset((size_t)kExpressMaxQ));
     const uint32_t cap = (uint32_t)std::min<int64_t>(cap_per_query, kExpressIdsCap / K);
-    std::memcpy(nodes->h_xin, samples, sizeof(double) * 3 * K);
+    std::memcpy(nodes->xin.host(), samples, sizeof(double) * 3 * K);
     const double reach = p->max_radius + p->search_margin;       // only the radius is wanted: stop once everything unseen is beyond it
     // a rolling window that holds nothing (table sized from an extent, nothing appended) is empty by the device's own count; a ring
     // index that has no table yet (no extent, no data) has ring_ready == false and count == 0: the static form's empty rule
     PCTCHK(ask_twice_after_overrun(obstacles, [&]() -> int {     // the table lost points (overflow-queue overrun): refiled, asked once more
         const ExpressSignal sig = K <= 8 ? next_signal(nodes) : ExpressSignal{};
         if (ring)
-            rrt_expand_kernel<true><<<(int)K, 256, 0, g_stream>>>(nodes->x, nodes->y, nodes->z, (uint32_t)nodes->count, nodes->d_aux, nodes->d_xin,
+            rrt_expand_kernel<true><<<(int)K, 256, 0, g_stream>>>(nodes->x, nodes->y, nodes->z, (uint32_t)nodes->count, nodes->aux, nodes->xin,
                                                                   ring_view(obstacles), GridDesc{}, nullptr, nullptr, 0, to_dev(p), reach * reach,
-                                                                  nodes->d_xids, cap, nodes->d_eout, sig);
+                                                                  nodes->xids, cap, nodes->eout, sig);
         else
-            rrt_expand_kernel<false><<<(int)K, 256, 0, g_stream>>>(nodes->x, nodes->y, nodes->z, (uint32_t)nodes->count, nodes->d_aux, nodes->d_xin,
+            rrt_expand_kernel<false><<<(int)K, 256, 0, g_stream>>>(nodes->x, nodes->y, nodes->z, (uint32_t)nodes->count, nodes->aux, nodes->xin,
                                                                    RingView{}, obstacles->G, obstacles->sorted, obstacles->cell_start,
-                                                                   obstacles->count == 0 ? 1 : 0, to_dev(p), reach * reach, nodes->d_xids, cap,
-                                                                   nodes->d_eout, sig);
+                                                                   obstacles->count == 0 ? 1 : 0, to_dev(p), reach * reach, nodes->xids, cap,
+                                                                   nodes->eout, sig);
         HIPCHK(hipGetLastError());
         // one or a few samples: the completion word (1500 one-sample iterations 37 -> 32 ms); speculative batches of 16-256 blocks:
         // a system-scope fence per block costs more than the stream synchronise saves (2.85 vs 2.60 ms per 1500 iterations at K = 64)
@@ -2312,13 +2359,13 @@ int pct_rrt_expand_batch(pct_cloud *nodes, pct_cloud *obstacles, const pct_infla
         return PCT_OK;
     }));
     for (int64_t k = 0; k < K; k++) {
-        const ExpandOut &e = nodes->h_eout[k];
+        const ExpandOut &e = nodes->eout.host()[k];
         out[k].center[0] = e.cx; out[k].center[1] = e.cy; out[k].center[2] = e.cz;
         out[k].radius = e.radius;
         out[k].near_idx = e.near_idx == kNoIndex ? -1 : (int32_t)e.near_idx;
         const int64_t got = std::min<int64_t>(e.count, cap);
         out[k].count = e.count > cap ? -(int32_t)e.count : (int32_t)e.count;     // negative = list truncated: ask that range query alone
-        std::copy(nodes->h_xids + k * cap, nodes->h_xids + k * cap + got, ids + k * cap_per_query);
+        std::copy(nodes->xids.host() + k * cap, nodes->xids.host() + k * cap + got, ids + k * cap_per_query);
     }
     return PCT_OK;
 }
@@ -2330,9 +2377,7 @@ int pct_bezier_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflat
         !(dt > 0) || cap <= 0)
         return fail(PCT_ERR_INVALID, "bad bezier_check arguments");
     if (cap > kBezierCapMax) cap = kBezierCapMax;
-    for (int i = 0; i < traj->nseg; i++)
-        if (traj->orders[i] < 0 || traj->orders[i] > kMaxBezierOrder || 3 * (traj->orders[i] + 1) > traj->row_stride)
-            return fail(PCT_ERR_INVALID, "segment %d: order %d unsupported", i, traj->orders[i]);
+    PCTCHK(bezier_check_orders(traj));
     if (c->ring_ready) {          // rolling map: the fused planner batch with samples only
         pct_replan_out o{};
         o.sample_pos = pos; o.sample_radius = radius; o.sample_d2 = d2; o.sample_idx = idx;
@@ -2345,79 +2390,54 @@ int pct_bezier_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflat
     if (ncoef + (size_t)traj->nseg <= 3 * (size_t)kExpressMaxQ - 64) {
         // express: the host enumerates the sample times (sim_planning_demo.cpp:729-771, the same sequential fp64 additions as
         // bezier_samples_kernel), then ONE launch evaluates, inflates and searches every sample (bezier_block_kernel)
-        double *hd = c->h_xin;                                  // [coef | seg_time | sample_t]
-        uint32_t *hu = c->h_xids;                               // [orders | sample_seg]
+        double *hd = c->xin.host();                                  // [coef | seg_time | sample_t]
+        uint32_t *hu = c->xids.host();                               // [orders | sample_seg]
         std::memcpy(hd, traj->polycoef, sizeof(double) * ncoef);
         std::memcpy(hd + ncoef, traj->seg_time, sizeof(double) * traj->nseg);
         for (int i = 0; i < traj->nseg; i++) hu[i] = (uint32_t)traj->orders[i];
         double *ht = hd + ncoef + traj->nseg;
         uint32_t *hs = hu + traj->nseg;
         const int64_t room = std::min<int64_t>({ cap, (int64_t)kExpressMaxQ, (int64_t)(3 * (size_t)kExpressMaxQ - ncoef - (size_t)traj->nseg) });
-        double t_s = t_start;
-        int first_seg;
-        for (first_seg = 0; first_seg < traj->nseg; ++first_seg) {
-            if (t_s > traj->seg_time[first_seg] && first_seg + 1 < traj->nseg) t_s -= traj->seg_time[first_seg];
-            else break;
-        }
-        int64_t n = 0;
-        double t_accu = 0.0;
-        for (int i = first_seg; i < traj->nseg; i++) {
-            const double T = traj->seg_time[i];
-            for (double t = (i == first_seg) ? t_s : 0.0; t < T; t += dt) {
-                t_accu += dt;
-                if (t_accu > stop_time) break;
-                if (n < room) { ht[n] = t; hs[n] = (uint32_t)i; }
-                n++;
-            }
-        }
+        const int64_t n = bezier_enumerate_samples(traj, t_start, stop_time, dt, room, [&](int64_t k, double t, int seg) { ht[k] = t; hs[k] = (uint32_t)seg; });
         const int64_t m = std::min<int64_t>(n, room);
         const bool fits = n <= room || room == cap;             // more samples than one express launch holds: staged path below
         if (fits && m > 0) {
-            if (!c->h_bpos) PCTCHK(mapped_alloc(&c->h_bpos, &c->d_bpos, (size_t)3 * kExpressMaxQ));
+            if (!c->bpos) PCTCHK(c->bpos.reset((size_t)3 * kExpressMaxQ));
             if (c->has_grid && c->count > 0) {        // indexed cloud: everything in ONE launch
                 const double reach = p->max_radius + p->search_margin;
                 const double stop_d2 = (idx || d2) ? (double)INFINITY : reach * reach;
-                bezier_block_kernel<<<(int)m, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, to_dev(p), c->d_xin, (int)traj->row_stride,
-                                                                   c->d_xin + ncoef, c->d_xids, c->d_xids + traj->nseg, c->d_xin + ncoef + traj->nseg,
-                                                                   stop_d2, (uint32_t)c->index_base, c->d_xout, c->d_bpos, next_signal(c));
+                bezier_block_kernel<<<(int)m, 256, 0, g_stream>>>(c->G, c->sorted, c->cell_start, to_dev(p), c->xin, (int)traj->row_stride,
+                                                                   c->xin + ncoef, c->xids, c->xids + traj->nseg, c->xin + ncoef + traj->nseg,
+                                                                   stop_d2, (uint32_t)c->index_base, c->xout, c->bpos, next_signal(c));
                 HIPCHK(hipGetLastError());
                 PCTCHK(express_wait(c));
             } else {                                      // un-indexed (rolling) cloud: evaluate, then the brute-force inflation; still no copies
                 PCTCHK(pct_cloud_reserve_queries(c, m));
-                bezier_eval_kernel<<<ceil_div(m, 128), 128, 0, g_stream>>>(c->d_xin, (int)traj->row_stride, c->d_xin + ncoef, c->d_xids, c->d_xids + traj->nseg,
-                                                                           c->d_xin + ncoef + traj->nseg, (int)m, c->d_pts64, c->d_bpos);
-                PCTCHK(inflate_dev(c, p, m, g_stream, c->d_pts64, c->d_xout));
+                bezier_eval_kernel<<<ceil_div(m, 128), 128, 0, g_stream>>>(c->xin, (int)traj->row_stride, c->xin + ncoef, c->xids, c->xids + traj->nseg,
+                                                                           c->xin + ncoef + traj->nseg, (int)m, c->d_pts64, c->bpos);
+                PCTCHK(inflate_dev(c, p, m, g_stream, c->d_pts64, c->xout));
                 HIPCHK(hipStreamSynchronize(g_stream));
             }
         }
         if (fits) {
             int64_t fh = -1;
             for (int64_t i = 0; i < m; i++) {
-                if (fh < 0 && c->h_xout[i].radius < 0.0) fh = i;
-                if (radius) radius[i] = c->h_xout[i].radius;
-                if (d2) d2[i] = c->h_xout[i].d2;
-                if (idx) idx[i] = c->h_xout[i].idx;
+                if (fh < 0 && c->xout.host()[i].radius < 0.0) fh = i;
+                if (radius) radius[i] = c->xout.host()[i].radius;
+                if (d2) d2[i] = c->xout.host()[i].d2;
+                if (idx) idx[i] = c->xout.host()[i].idx;
             }
-            if (pos && m) std::memcpy(pos, c->h_bpos, sizeof(double) * 3 * m);
+            if (pos && m) std::memcpy(pos, c->bpos.host(), sizeof(double) * 3 * m);
             *nsamples = n;
             *first_hit = fh;
             return PCT_OK;
         }
     }
     PCTCHK(pct_cloud_reserve_queries(c, cap));
-    if (ncoef > c->coef_cap) { dev_free(c->d_coef); c->coef_cap = 0; PCTCHK(dev_alloc(&c->d_coef, ncoef)); c->coef_cap = ncoef; }
-    if ((size_t)traj->nseg > c->seg_cap) {
-        dev_free(c->d_segtime); dev_free(c->d_orders); c->seg_cap = 0;
-        PCTCHK(dev_alloc(&c->d_segtime, traj->nseg));
-        PCTCHK(dev_alloc(&c->d_orders, traj->nseg));
-        c->seg_cap = traj->nseg;
-    }
-    if (!c->d_nsamples) PCTCHK(dev_alloc(&c->d_nsamples, 1));
-    if (!c->d_first_hit) PCTCHK(dev_alloc(&c->d_first_hit, 1));
+    if (!c->d_nsamples) PCTCHK(c->d_nsamples.reset(1));
+    if (!c->d_first_hit) PCTCHK(c->d_first_hit.reset(1));
     hipStream_t s = g_stream;
-    HIPCHK(hipMemcpyAsync(c->d_coef, traj->polycoef, sizeof(double) * ncoef, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_segtime, traj->seg_time, sizeof(double) * traj->nseg, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_orders, traj->orders, sizeof(int) * traj->nseg, hipMemcpyHostToDevice, s));
+    PCTCHK(bezier_stage_coef(c, traj, s, false));
     HIPCHK(hipMemsetAsync(c->d_pts64, 0, sizeof(double) * 3 * cap, s));
     BezierDesc B{ c->d_coef, c->d_segtime, c->d_orders, (int)traj->row_stride, traj->nseg, t_start, stop_time, dt, (int)cap };
     const size_t smem = (size_t)cap * (sizeof(double) + sizeof(int));
@@ -2460,25 +2480,10 @@ int pct_bezier_check_dev(pct_cloud *c, const pct_bezier_traj *traj, const pct_in
         return fail(PCT_ERR_INVALID, "bad bezier_check_dev arguments");
     if (cap > kBezierCapMax || cap > c->qcap) return fail(PCT_ERR_INVALID, "cap %lld exceeds %lld (4096, and the reserved batch size)", (long long)cap,
                                                           (long long)std::min<int64_t>(kBezierCapMax, c->qcap));
-    for (int i = 0; i < traj->nseg; i++)
-        if (traj->orders[i] < 0 || traj->orders[i] > kMaxBezierOrder || 3 * (traj->orders[i] + 1) > traj->row_stride)
-            return fail(PCT_ERR_INVALID, "segment %d: order %d unsupported", i, traj->orders[i]);
-    const size_t ncoef = (size_t)traj->nseg * traj->row_stride;
+    PCTCHK(bezier_check_orders(traj));
     hipStream_t s = (hipStream_t)stream;
     PCTCHK(order_after_mutations(c, s));
-    if (ncoef > c->coef_cap || (size_t)traj->nseg > c->seg_cap) {       // grow the coefficient buffers (earlier work may still read the old ones)
-        HIPCHK(hipDeviceSynchronize());
-        if (ncoef > c->coef_cap) { dev_free(c->d_coef); c->coef_cap = 0; PCTCHK(dev_alloc(&c->d_coef, ncoef)); c->coef_cap = ncoef; }
-        if ((size_t)traj->nseg > c->seg_cap) {
-            dev_free(c->d_segtime); dev_free(c->d_orders); c->seg_cap = 0;
-            PCTCHK(dev_alloc(&c->d_segtime, traj->nseg));
-            PCTCHK(dev_alloc(&c->d_orders, traj->nseg));
-            c->seg_cap = traj->nseg;
-        }
-    }
-    HIPCHK(hipMemcpyAsync(c->d_coef, traj->polycoef, sizeof(double) * ncoef, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_segtime, traj->seg_time, sizeof(double) * traj->nseg, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_orders, traj->orders, sizeof(int) * traj->nseg, hipMemcpyHostToDevice, s));
+    PCTCHK(bezier_stage_coef(c, traj, s, true));
     double *pos = d_pos ? d_pos : c->d_pts64;
     HIPCHK(hipMemsetAsync(pos, 0, sizeof(double) * 3 * cap, s));
     BezierDesc B{ c->d_coef, c->d_segtime, c->d_orders, (int)traj->row_stride, traj->nseg, t_start, stop_time, dt, (int)cap };
@@ -2513,14 +2518,12 @@ int pct_plan_create_nn(pct_cloud *c, int algo, int64_t Q, pct_plan **out)
     p->c = c;
     p->Q = Q;
     p->algo = algo;
-    hipError_t e = hipHostMalloc((void **)&p->h_q, sizeof(float) * 3 * Q, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&p->h_idx, sizeof(uint32_t) * Q, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&p->h_d2, sizeof(double) * Q, hipHostMallocDefault);
-    int st = PCT_OK;
-    if (e != hipSuccess) st = fail(PCT_ERR_ALLOC, "hipHostMalloc: %s", hipGetErrorString(e));
-    if (!st) st = dev_alloc(&p->d_q, 3 * Q);
-    if (!st) st = dev_alloc(&p->d_idx, Q);
-    if (!st) st = dev_alloc(&p->d_d2, Q);
+    int st = p->h_q.reset(3 * Q);
+    if (!st) st = p->h_idx.reset(Q);
+    if (!st) st = p->h_d2.reset(Q);
+    if (!st) st = p->d_q.reset(3 * Q);
+    if (!st) st = p->d_idx.reset(Q);
+    if (!st) st = p->d_d2.reset(Q);
     if (!st) st = plan_capture_nn(p);
     if (st) { pct_plan_destroy(p); return st; }
     *out = p;
@@ -2548,10 +2551,6 @@ int pct_plan_destroy(pct_plan *p)
     if (g_stream) (void)hipStreamSynchronize(g_stream);
     if (p->exec) (void)hipGraphExecDestroy(p->exec);
     if (p->graph) (void)hipGraphDestroy(p->graph);
-    if (p->h_q) (void)hipHostFree(p->h_q);
-    if (p->h_idx) (void)hipHostFree(p->h_idx);
-    if (p->h_d2) (void)hipHostFree(p->h_d2);
-    dev_free(p->d_q); dev_free(p->d_idx); dev_free(p->d_d2);
     replan_ctx_free(p->rx);
     delete p;
     return PCT_OK;
@@ -2812,11 +2811,11 @@ int pct_debug_verify_grid(pct_cloud *c, uint64_t out[6])
 {
     if (!c || !c->has_grid || !out) return fail(PCT_ERR_INVALID, "no cell index");
     const uint32_t n = (uint32_t)c->count;
-    uint32_t *bitmap = nullptr;
-    unsigned long long *d_out = nullptr;
+    DevBuf<uint32_t> bitmap;
+    DevBuf<unsigned long long> d_out;
     const size_t words = ((size_t)n + 31) / 32;
-    int st = dev_alloc(&bitmap, words);
-    if (!st) st = dev_alloc(&d_out, 6);
+    int st = bitmap.reset(words);
+    if (!st) st = d_out.reset(6);
     hipError_t e = hipSuccess;
     if (!st) {
         e = hipMemsetAsync(bitmap, 0, sizeof(uint32_t) * std::max<size_t>(words, 1), g_stream);
@@ -2830,7 +2829,6 @@ int pct_debug_verify_grid(pct_cloud *c, uint64_t out[6])
         if (e == hipSuccess) e = hipStreamSynchronize(g_stream);
         for (int k = 0; k < 6; k++) out[k] = h[k];
     }
-    dev_free(bitmap); dev_free(d_out);
     if (st) return st;
     if (e != hipSuccess) return fail(PCT_ERR_HIP, "verify_grid: %s", hipGetErrorString(e));
     return PCT_OK;

@@ -1,0 +1,97 @@
+// hostmem.hpp -- who owns the host side's buffers and how they grow.  No HIP include: the memory kind is a
+// policy (engine_internal.hpp provides device / pinned / host-mapped over the HIP runtime; tests/host/hostmem_check.cpp one over
+// malloc), and the wait takes its stream synchronise as a callable.
+//
+//   Buf<T, Mem>   one owning, grow-only block of T.  Mem::alloc(bytes, &host, &dev) returns 0 or an error code and leaves both
+//                 pointers null on failure; Mem::release(host, dev, bytes) frees what alloc handed out.
+//   pow2_at_least the doubling rule of the grow-only workspaces
+//   wait_word     spin on a host-mapped completion word, fall back to the stream
+//
+// The type decides no policy: how much to allocate, whether to synchronise first and whether growth is allowed at all (graph
+// capture) stay with the call site.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace pct_host {
+
+template <typename T, typename Mem>
+class Buf {
+public:
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    Buf(Buf &&o) noexcept : h_(o.h_), d_(o.d_), cap_(o.cap_) { o.h_ = o.d_ = nullptr; o.cap_ = 0; }
+    Buf &operator=(Buf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            h_ = o.h_; d_ = o.d_; cap_ = o.cap_;
+            o.h_ = o.d_ = nullptr; o.cap_ = 0;
+        }
+        return *this;
+    }
+    ~Buf() { release(); }
+
+    operator T *() const { return d_; }          // what a kernel or a hipMemcpy takes (the pinned kind: the host pointer itself)
+    T *get() const { return d_; }
+    T *host() const { return h_; }               // pinned and host-mapped kinds
+    size_t capacity() const { return cap_; }     // elements
+
+    void release()
+    {
+        if (d_ || h_) Mem::release(h_, d_, bytes(cap_));
+        h_ = d_ = nullptr;
+        cap_ = 0;
+    }
+
+    // release, then allocate exactly `count` elements (one element's room when count is 0); empty on failure
+    int reset(size_t count)
+    {
+        release();
+        void *h = nullptr, *d = nullptr;
+        if (const int st = Mem::alloc(bytes(count), &h, &d)) return st;
+        h_ = static_cast<T *>(h);
+        d_ = static_cast<T *>(d);
+        cap_ = count;
+        return 0;
+    }
+
+    // grow-only: nothing happens while need <= capacity().  Otherwise the old block goes first (peak memory does not rise) and
+    // alloc_count elements are asked for (0: exactly `need`).  The caller makes sure no launch still reads the old block.
+    int reserve(size_t need, size_t alloc_count = 0)
+    {
+        if (need <= cap_) return 0;
+        return reset(alloc_count > need ? alloc_count : need);
+    }
+
+private:
+    static size_t bytes(size_t count) { return (count ? count : 1) * sizeof(T); }
+    T *h_ = nullptr, *d_ = nullptr;
+    size_t cap_ = 0;
+};
+
+// the smallest floor * 2^k that is >= need (floor a power of two: the result is one, and *log2 its exponent)
+template <typename I>
+I pow2_at_least(I floor, I need, int *log2 = nullptr)
+{
+    I v = floor;
+    while (v < need) v <<= 1;
+    if (log2) *log2 = __builtin_ctzll((unsigned long long)v);
+    return v;
+}
+
+// Wait until the host-mapped word *w holds `want`: spin on it (a stream synchronise costs ~20 us of host time more) and, when
+// max_spins run out (0: polling is off), fall back to sync().  Returns whether the word matched after that.
+template <typename Sync>
+bool wait_word(const volatile uint32_t *w, uint32_t want, long max_spins, Sync sync)
+{
+    for (long spins = 0; spins < max_spins; spins++) {
+        if (*w == want) { __atomic_thread_fence(__ATOMIC_ACQUIRE); return true; }
+        __builtin_ia32_pause();
+    }
+    sync();
+    return *w == want;
+}
+
+}  // namespace pct_host

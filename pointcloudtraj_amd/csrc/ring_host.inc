@@ -5,17 +5,9 @@ namespace {
 
 void ring_free(pct_cloud *c)
 {
-    dev_free(c->ring_ht); dev_free(c->ring_slots); dev_free(c->ring_ovf); dev_free(c->ring_where); dev_free(c->ring_st);
+    c->ring_ht.release(); c->ring_slots.release(); c->ring_ovf.release(); c->ring_where.release(); c->ring_st.release();
     c->ring_cells = 0;
     c->ring_ready = false;
-}
-
-int log2_ceil_pow2(int64_t v, int *lg)
-{
-    int l = 0;
-    while ((1ll << l) < v) l++;
-    *lg = l;
-    return 1 << l;
 }
 
 // bounding box of the points currently in the SoA arrays (device reduction, one read-back); lo > hi: no row was looked at
@@ -24,15 +16,14 @@ int cloud_bbox(pct_cloud *c, float lo[3], float hi[3])
     const int64_t n = c->count;
     hipStream_t s = g_stream;
     const int bblocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
-    float *d_part = nullptr;
-    PCTCHK(dev_alloc(&d_part, (size_t)bblocks * 6));
+    DevBuf<float> d_part;
+    PCTCHK(d_part.reset((size_t)bblocks * 6));
     // removals since the last upload: the removed rows (three NaNs) are no data to size a table from
     if (c->ring_removed_any) bbox_partial_kernel<true><<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
     else bbox_partial_kernel<false><<<bblocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)n, d_part);
     std::vector<float> part((size_t)bblocks * 6);
     hipError_t e = hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(float), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    dev_free(d_part);
     if (e != hipSuccess) return fail(PCT_ERR_HIP, "bbox reduction failed: %s", hipGetErrorString(e));
     for (int k = 0; k < 3; k++) { lo[k] = INFINITY; hi[k] = -INFINITY; }
     for (int b = 0; b < bblocks; b++)
@@ -66,7 +57,7 @@ int ring_configure(pct_cloud *c, const double ext_in[3])
     for (;;) {
         int64_t cells = 1;
         for (int k = 0; k < 3; k++) {
-            g[k] = log2_ceil_pow2(std::max<int64_t>(4, (int64_t)std::ceil(1.25 * ext[k] / h) + 2), &lg[k]);
+            g[k] = (int)pow2_at_least<int64_t>(1, std::max<int64_t>(4, (int64_t)std::ceil(1.25 * ext[k] / h) + 2), &lg[k]);
             cells *= g[k];
         }
         if (cells <= (1ll << 24)) break;
@@ -78,18 +69,17 @@ int ring_configure(pct_cloud *c, const double ext_in[3])
     R.gx = g[0]; R.gy = g[1]; R.gz = g[2];
     R.lx = lg[0]; R.ly = lg[1];
     R.K = std::max<uint32_t>(kRingK, std::min<uint32_t>(kRingKMax, c->ring_K));
-    int lo = 0;
-    const uint32_t ovf_cap = (uint32_t)log2_ceil_pow2(2 * std::max<int64_t>(c->cap, 16) + 16, &lo);     // see RingDesc::ovf_mask
+    const uint32_t ovf_cap = (uint32_t)pow2_at_least<int64_t>(1, 2 * std::max<int64_t>(c->cap, 16) + 16);     // see RingDesc::ovf_mask
     R.ovf_mask = ovf_cap - 1u;
-    if (!c->h_ring_status) PCTCHK(mapped_alloc(&c->h_ring_status, &c->d_ring_status, 4));
-    c->h_ring_status[0] = c->h_ring_status[1] = 0;
-    R.status = c->d_ring_status;
+    if (!c->ring_status) PCTCHK(c->ring_status.reset(4));
+    c->ring_status.host()[0] = c->ring_status.host()[1] = 0;
+    R.status = c->ring_status.get();
     const size_t cells = (size_t)g[0] * g[1] * g[2];
-    int ast = dev_alloc(&c->ring_ht, cells);
-    if (!ast) ast = dev_alloc(&c->ring_slots, cells * R.K);
-    if (!ast) ast = dev_alloc(&c->ring_ovf, (size_t)ovf_cap);
-    if (!ast) ast = dev_alloc(&c->ring_where, (size_t)c->cap4 + 4);
-    if (!ast) ast = dev_alloc(&c->ring_st, 1);
+    int ast = c->ring_ht.reset(cells);
+    if (!ast) ast = c->ring_slots.reset(cells * R.K);
+    if (!ast) ast = c->ring_ovf.reset((size_t)ovf_cap);
+    if (!ast) ast = c->ring_where.reset((size_t)c->cap4 + 4);
+    if (!ast) ast = c->ring_st.reset(1);
     if (ast) { ring_free(c); return ast; }            // no half-allocated index: the cloud answers by brute force until it is configured again
     c->R = R;
     c->ring_cells = cells;
@@ -133,17 +123,11 @@ int ring_setup_from_cloud(pct_cloud *c)
     return ring_refile_all(c);
 }
 
-// the host-mapped staging buffer of appended frames (grow-only, power of two)
-int ensure_frame_buffer(pct_cloud *c, size_t bytes)
+// a host-mapped staging buffer of appended frames -- the producer's (c->frame) or the library's own (c->astage): grow-only, a power
+// of two from 64 KiB that holds the frame and 64 bytes of slack.  The caller knows that no launch still reads it.
+int ensure_frame_staging(MappedBuf<unsigned char> &b, size_t bytes)
 {
-    if (bytes + 64 <= c->frame_cap) return PCT_OK;
-    if (c->h_frame) (void)hipHostFree(c->h_frame);
-    c->h_frame = nullptr; c->frame_cap = 0;
-    size_t cap = (size_t)1 << 16;
-    while (cap < bytes + 64) cap <<= 1;
-    PCTCHK(mapped_alloc(&c->h_frame, &c->d_frame, cap));
-    c->frame_cap = cap;
-    return PCT_OK;
+    return b.reserve(bytes + 64, pow2_at_least((size_t)1 << 16, bytes + 64));
 }
 
 // Self-checks on the host-mapped status words an append's launches wrote.  [0]: the overflow queue was about to overrun its table
@@ -154,14 +138,14 @@ int ensure_frame_buffer(pct_cloud *c, size_t bytes)
 int ring_after_append(pct_cloud *c)
 {
     hipStream_t s = g_stream;
-    if (c->h_ring_status[0]) {
-        c->h_ring_status[0] = 0;
+    if (c->ring_status.host()[0]) {
+        c->ring_status.host()[0] = 0;
         PCTCHK(ring_refile_all(c));
         HIPCHK(hipStreamSynchronize(s));
-    } else if (!(c->ring_cell_req > 0) && !(c->ring_extent_req[0] > 0) && (int64_t)c->h_ring_status[1] > c->count / 8 + 64 && c->count >= 2 * std::max<int64_t>(c->ring_cfg_count, 1)) {
+    } else if (!(c->ring_cell_req > 0) && !(c->ring_extent_req[0] > 0) && (int64_t)c->ring_status.host()[1] > c->count / 8 + 64 && c->count >= 2 * std::max<int64_t>(c->ring_cfg_count, 1)) {
         PCTCHK(ring_setup_from_cloud(c));
         HIPCHK(hipStreamSynchronize(s));
-    } else if ((int64_t)c->h_ring_status[1] > c->count / 128 + 4096 && c->ring_K < kRingKMax && c->ring_appends_since_cfg >= 4 &&
+    } else if ((int64_t)c->ring_status.host()[1] > c->count / 128 + 4096 && c->ring_K < kRingKMax && c->ring_appends_since_cfg >= 4 &&
                (size_t)c->ring_cells * 2 * c->ring_K * sizeof(float4) <= ((size_t)32 << 30)) {
         // A good share of the window in the overflow queue (every query scans it exhaustively: 100 k entries cost a search ~150 us) although
         // the cells were sized from the window itself: the cells that hold points
@@ -188,8 +172,8 @@ int ring_after_append(pct_cloud *c)
 int ring_overrun_repair(pct_cloud *c, bool *again)
 {
     *again = false;
-    if (!c->ring_ready || !c->h_ring_status || !c->h_ring_status[0]) return PCT_OK;
-    c->h_ring_status[0] = 0;
+    if (!c->ring_ready || !c->ring_status.host() || !c->ring_status.host()[0]) return PCT_OK;
+    c->ring_status.host()[0] = 0;
     PCTCHK(ring_refile_all(c));
     HIPCHK(hipStreamSynchronize(g_stream));
     *again = true;
@@ -233,23 +217,16 @@ int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride, const 
     // either way -- the 600 KB cross the bus in ~35 us whether the copy engine or the kernel moves them; what the path buys is a tighter
     // p99 and the zero-copy entry point (pct_cloud_append_frame), not the median.
     // in_place: the producer wrote the frame straight into the staging buffer (pct_cloud_frame_buffer / pct_cloud_append_frame)
-    const bool in_place = !d_own && pts == c->h_frame && c->h_frame != nullptr && bytes <= c->frame_cap;
+    const bool in_place = !d_own && pts == c->frame.host() && c->frame.host() != nullptr && bytes <= c->frame.capacity();
     const bool mapped = in_place || ((d_own || bytes <= ((size_t)4 << 20)) && mapped_io_on());
     const unsigned char *d_src = nullptr;
     if (d_own) d_src = d_own;
-    else if (in_place) d_src = c->d_frame;
+    else if (in_place) d_src = c->frame;
     else if (mapped) {
-        // copies go through a staging buffer of their own: the producer of zero-copy frames owns c->h_frame and may be writing
+        // copies go through a staging buffer of their own: the producer of zero-copy frames owns c->frame.host() and may be writing
         // the next frame into it while the previous (asynchronous) copy append is still being read
-        if (bytes + 64 > c->astage_cap) {
-            if (c->h_astage) (void)hipHostFree(c->h_astage);
-            c->h_astage = nullptr; c->astage_cap = 0;
-            size_t cap = (size_t)1 << 16;
-            while (cap < bytes + 64) cap <<= 1;
-            PCTCHK(mapped_alloc(&c->h_astage, &c->d_astage, cap));
-            c->astage_cap = cap;
-        }
-        d_src = c->d_astage;
+        PCTCHK(ensure_frame_staging(c->astage, bytes));
+        d_src = c->astage;
     } else {
         PCTCHK(ensure_stage(c, bytes + 64));
         HIPCHK(hipMemcpyAsync(c->d_stage, pts, bytes, hipMemcpyHostToDevice, s));
@@ -267,7 +244,7 @@ int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride, const 
             ring_evict_kernel<<<ceil_div(old_valid, 256), 256, 0, s>>>(c->R, c->x, c->y, c->z, (uint32_t)s0, (uint32_t)old_valid, c->ring_ht, c->ring_slots,
                                                                        c->ring_ovf, c->ring_where, c->ring_st);
     }
-    if (mapped && !in_place && !d_own) std::memcpy(c->h_astage, pts, bytes);
+    if (mapped && !in_place && !d_own) std::memcpy(c->astage.host(), pts, bytes);
     for (int k = 0; k < 2; k++) {
         const int64_t cnt = part_n[k], s0 = part_slot0[k];
         if (cnt <= 0) continue;
@@ -295,58 +272,40 @@ int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride, const 
 // ---- de-duplicating appends (ring_dedup.hpp) ---------------------------------------------------------------------------------
 int after_replace(pct_cloud *c);
 
-// the host-mapped {sequence, total} pair dd_tile_scan_kernel publishes
-int dd_word_ensure(pct_cloud *c)
+// the host wait behind dd_tile_scan_kernel: the grand total of the scan launched with `seq`, from the host-mapped {sequence, total}
+// pair it publishes
+int dd_scan_wait(pct_cloud *c, uint32_t seq, int64_t *total)
 {
-    if (c->h_dd_word) return PCT_OK;
-    PCTCHK(mapped_alloc(&c->h_dd_word, &c->d_dd_word, 4));
-    c->h_dd_word[0] = c->h_dd_word[1] = 0;
+    PCTCHK(c->dd_word.wait(seq, "the frame filter"));
+    *total = (int64_t)c->dd_word.w.host()[1];
     return PCT_OK;
 }
 
-// the host wait behind dd_tile_scan_kernel: the grand total of the scan launched with `seq`, polled in host-mapped memory as
-// express_wait polls its word
-int dd_scan_wait(pct_cloud *c, uint32_t seq, int64_t *total)
-{
-    bool seen = false;
-    if (poll_results()) {
-        const volatile uint32_t *w = c->h_dd_word;
-        for (long spins = 0; spins < 200000000l && !seen; spins++) {
-            if (w[0] == seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); seen = true; }
-            else __builtin_ia32_pause();
-        }
-    }
-    if (!seen) HIPCHK(hipStreamSynchronize(g_stream));
-    if (c->h_dd_word[0] != seq) return fail(PCT_ERR_HIP, "the frame filter finished without its sequence word (%u != %u)", c->h_dd_word[0], seq);
-    *total = (int64_t)c->h_dd_word[1];
-    return PCT_OK;
-}
+// entries of the frame filter's key table for a frame of n points: a power of two >= 2 n (load factor <= 0.5), at least 1024
+uint32_t dedup_table_size(int64_t n) { return (uint32_t)pow2_at_least<uint64_t>(1024, 2ull * (uint64_t)n); }
 
 // scratch of the frame filter for a frame of n points (grow-only)
 int dedup_ensure(pct_cloud *c, int64_t n)
 {
-    PCTCHK(dd_word_ensure(c));
-    uint32_t T = 1024;
-    while ((uint64_t)T < 2ull * (uint64_t)n) T <<= 1;
+    PCTCHK(c->dd_word.ensure(4));
+    const uint32_t T = dedup_table_size(n);
     if (T > c->dd_tcap) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        dev_free(c->dd_keys); dev_free(c->dd_vals);
         c->dd_tcap = 0;
-        PCTCHK(dev_alloc(&c->dd_keys, T));
-        PCTCHK(dev_alloc(&c->dd_vals, T));
+        c->dd_keys.release(); c->dd_vals.release();
+        PCTCHK(c->dd_keys.reset(T));
+        PCTCHK(c->dd_vals.reset(T));
         c->dd_tcap = T;
     }
-    if (n > c->dd_ncap) {
+    if (n > c->dd.ncap) {
         HIPCHK(hipStreamSynchronize(g_stream));       // the previous append's insert kernel may still be reading the compacted frame
-        const int64_t cap = std::min<int64_t>(std::max<int64_t>(c->cap, 1), std::max<int64_t>(n, 2 * c->dd_ncap));
-        dev_free(c->dd_pslot); dev_free(c->dd_rank); dev_free(c->dd_tile); dev_free(c->dd_flags); dev_free(c->dd_out);
-        c->dd_ncap = 0;
-        PCTCHK(dev_alloc(&c->dd_pslot, (size_t)cap));
-        PCTCHK(dev_alloc(&c->dd_rank, (size_t)cap));
-        PCTCHK(dev_alloc(&c->dd_tile, (size_t)ceil_div(cap, kDdTile)));
-        PCTCHK(dev_alloc(&c->dd_flags, (size_t)cap));
-        PCTCHK(dev_alloc(&c->dd_out, 3 * (size_t)cap));
-        c->dd_ncap = cap;
+        const int64_t cap = std::min<int64_t>(std::max<int64_t>(c->cap, 1), std::max<int64_t>(n, 2 * c->dd.ncap));
+        c->dd.ncap = 0;
+        c->dd_pslot.release();
+        PCTCHK(c->dd.ensure(cap));
+        c->dd.ncap = 0;                            // the group is whole only with the table slots
+        PCTCHK(c->dd_pslot.reset((size_t)cap));
+        c->dd.ncap = cap;
     }
     return PCT_OK;
 }
@@ -356,21 +315,20 @@ int dedup_ensure(pct_cloud *c, int64_t n)
 int dedup_filter(pct_cloud *c, const unsigned char *d_src, int64_t n, int64_t stride, bool probe, int64_t *kept)
 {
     hipStream_t s = g_stream;
-    uint32_t T = 1024;
-    while ((uint64_t)T < 2ull * (uint64_t)n) T <<= 1;
+    const uint32_t T = dedup_table_size(n);
     const uint32_t un = (uint32_t)n;
     const int ntiles = ceil_div(n, kDdTile);
     const DdWindow W{ (uint32_t)c->ring_next, (uint32_t)c->cap, un };
-    const uint32_t seq = ++c->dd_seq;
+    const uint32_t seq = c->dd_word.next();
     pct_vox::vox_table_init_kernel<<<std::min(ceil_div(T, 256), 2048), 256, 0, s>>>(c->dd_keys, c->dd_vals, T);
     dd_key_kernel<<<ceil_div(n, 256), 256, 0, s>>>(d_src, un, (uint32_t)stride, c->dd_res, c->dd_keys, c->dd_vals, T - 1u, c->dd_pslot);
     if (probe)
-        dd_probe_kernel<true><<<ceil_div(n, kDdPointsPerBlock), 256, 0, s>>>(ring_view(c), W, c->dd_res, un, c->dd_keys, c->dd_vals, c->dd_pslot, c->dd_flags);
+        dd_probe_kernel<true><<<ceil_div(n, kDdPointsPerBlock), 256, 0, s>>>(ring_view(c), W, c->dd_res, un, c->dd_keys, c->dd_vals, c->dd_pslot, c->dd.flags);
     else
-        dd_probe_kernel<false><<<ceil_div(n, kDdPointsPerBlock), 256, 0, s>>>(RingView{}, W, c->dd_res, un, c->dd_keys, c->dd_vals, c->dd_pslot, c->dd_flags);
-    dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dd_flags, un, c->dd_rank, c->dd_tile);
-    dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dd_tile, (uint32_t)ntiles, c->d_dd_word, seq);
-    dd_compact_kernel<<<ceil_div(n, 256), 256, 0, s>>>(d_src, un, (uint32_t)stride, c->dd_flags, c->dd_rank, c->dd_tile, c->dd_out);
+        dd_probe_kernel<false><<<ceil_div(n, kDdPointsPerBlock), 256, 0, s>>>(RingView{}, W, c->dd_res, un, c->dd_keys, c->dd_vals, c->dd_pslot, c->dd.flags);
+    dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dd.flags, un, c->dd.rank, c->dd.tile);
+    dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dd.tile, (uint32_t)ntiles, c->dd_word.w, seq);
+    dd_compact_kernel<<<ceil_div(n, 256), 256, 0, s>>>(d_src, un, (uint32_t)stride, c->dd.flags, c->dd.rank, c->dd.tile, c->dd.out);
     HIPCHK(hipGetLastError());
     PCTCHK(dd_scan_wait(c, seq, kept));
     if (*kept > n) return fail(PCT_ERR_INTERNAL, "the de-dup filter kept %lld of %lld points", (long long)*kept, (long long)n);
@@ -406,8 +364,8 @@ int ring_append_dedup(pct_cloud *c, const void *pts, int64_t n, int64_t stride, 
     if (!c->ring_ready && c->count > 0) { PCTCHK(ring_setup_from_cloud(c)); HIPCHK(hipStreamSynchronize(s)); }
     PCTCHK(dedup_ensure(c, n));
     const size_t bytes = (size_t)n * (size_t)stride;
-    const bool in_place = !d_own && pts == c->h_frame && c->h_frame != nullptr && bytes <= c->frame_cap;
-    const unsigned char *d_src = d_own ? d_own : c->d_frame;
+    const bool in_place = !d_own && pts == c->frame.host() && c->frame.host() != nullptr && bytes <= c->frame.capacity();
+    const unsigned char *d_src = d_own ? d_own : c->frame;
     if (!in_place && !d_own) {
         PCTCHK(ensure_stage(c, bytes + 64));
         HIPCHK(hipMemcpyAsync(c->d_stage, pts, bytes, hipMemcpyHostToDevice, s));
@@ -424,13 +382,13 @@ int ring_append_dedup(pct_cloud *c, const void *pts, int64_t n, int64_t stride, 
         return PCT_OK;
     }
     if (c->ring_ready) {
-        PCTCHK(ring_append(c, nullptr, kept, 12, reinterpret_cast<const unsigned char *>(c->dd_out)));
+        PCTCHK(ring_append(c, nullptr, kept, 12, reinterpret_cast<const unsigned char *>(c->dd.out.get())));
         // zero-copy frames: the producer may rewrite the staging buffer as soon as we return, and the compaction kernel read it
         if (in_place) PCTCHK(ring_finish_pending(c));
         return PCT_OK;
     }
     // first data (the window is empty and has no table yet): the compacted frame takes the first-data path, which sizes the table from it
-    return append_unindexed_dev(c, c->dd_out, kept);
+    return append_unindexed_dev(c, c->dd.out, kept);
 }
 
 // the cloud's contents were replaced (upload) or grew on a cloud whose ring table does not exist yet
@@ -462,32 +420,30 @@ struct ReplanCtx {
     int max_nodes = 0, max_samples = 0, max_seg = 0, max_ctrl = 0, row_cap = 0;
     bool copies = false;                 // true: arguments / results cross the bus in memcpy nodes; false: host-mapped memory
     size_t args_bytes = 0, f64_off = 0, u32_off = 0;
-    unsigned char *h_args = nullptr, *d_args = nullptr;      // mapped: d_args is the device alias of h_args
+    // views of the owners below -- mapped: d_* is the device alias of h_*; copies: pinned h_* and device d_*
+    unsigned char *h_args = nullptr, *d_args = nullptr;
     ExpressOut *h_res = nullptr, *d_res_host = nullptr;      // results where the caller reads them (d_res_host: device alias / copy source)
     double *h_pos = nullptr, *d_pos = nullptr;               // positions of samples and control points
     ReplanSummary *h_sum = nullptr, *d_sum = nullptr;
-    ReplanMeet *d_meet = nullptr;
+    MappedBuf<unsigned char> m_args;
+    MappedBuf<ExpressOut> m_res;
+    MappedBuf<double> m_pos;
+    MappedBuf<ReplanSummary> m_sum;
+    PinnedBuf<unsigned char> p_args;
+    PinnedBuf<ExpressOut> p_res;
+    PinnedBuf<double> p_pos;
+    PinnedBuf<ReplanSummary> p_sum;
+    DevBuf<unsigned char> c_args;
+    DevBuf<ExpressOut> c_res;
+    DevBuf<double> c_pos;
+    DevBuf<ReplanSummary> c_sum;
+    DevBuf<ReplanMeet> d_meet;
     uint32_t seq = 0;                    // ticks filled so far = launches queued; tick k's header lives in slot k & 1 (ring.hpp ReplanMeet)
     ReplanHeader hdr{};                  // the fixed offsets
     ReplanHeader hdr_sent{};             // the header of the tick in flight, as the host wrote it
 };
 
-void replan_ctx_free(ReplanCtx *x)
-{
-    if (!x) return;
-    if (x->copies) {
-        dev_free(x->d_args);
-        if (x->d_res_host) { void *p = x->d_res_host; (void)hipFree(p); }
-        if (x->d_pos) { void *p = x->d_pos; (void)hipFree(p); }
-        if (x->d_sum) { void *p = x->d_sum; (void)hipFree(p); }
-    }
-    if (x->h_args) (void)hipHostFree(x->h_args);
-    if (x->h_res) (void)hipHostFree(x->h_res);
-    if (x->h_pos) (void)hipHostFree(x->h_pos);
-    if (x->h_sum) (void)hipHostFree(x->h_sum);
-    dev_free(x->d_meet);
-    delete x;
-}
+void replan_ctx_free(ReplanCtx *x) { delete x; }
 
 namespace {
 
@@ -510,27 +466,26 @@ int replan_ctx_create(int max_nodes, int max_samples, int max_seg, bool copies, 
     const size_t nres = (size_t)max_nodes + max_samples + x->max_ctrl;
     const size_t npos = 3 * ((size_t)max_samples + x->max_ctrl);
     int st = PCT_OK;
-    hipError_t e = hipSuccess;
-    const unsigned flags = copies ? hipHostMallocDefault : hipHostMallocMapped;
-    e = hipHostMalloc((void **)&x->h_args, x->args_bytes, flags);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&x->h_res, nres * sizeof(ExpressOut), flags);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&x->h_pos, std::max<size_t>(npos, 1) * sizeof(double), flags);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&x->h_sum, sizeof(ReplanSummary), flags);
-    if (e == hipSuccess && !copies) {
-        void *d = nullptr;
-        e = hipHostGetDevicePointer(&d, x->h_args, 0); x->d_args = (unsigned char *)d;
-        if (e == hipSuccess) { e = hipHostGetDevicePointer(&d, x->h_res, 0); x->d_res_host = (ExpressOut *)d; }
-        if (e == hipSuccess) { e = hipHostGetDevicePointer(&d, x->h_pos, 0); x->d_pos = (double *)d; }
-        if (e == hipSuccess) { e = hipHostGetDevicePointer(&d, x->h_sum, 0); x->d_sum = (ReplanSummary *)d; }
+    if (copies) {
+        st = x->p_args.reset(x->args_bytes);
+        if (!st) st = x->p_res.reset(nres);
+        if (!st) st = x->p_pos.reset(std::max<size_t>(npos, 1));
+        if (!st) st = x->p_sum.reset(1);
+        if (!st) st = x->c_args.reset(x->args_bytes);
+        if (!st) st = x->c_res.reset(nres);
+        if (!st) st = x->c_pos.reset(std::max<size_t>(npos, 1));
+        if (!st) st = x->c_sum.reset(1);
+        x->h_args = x->p_args; x->h_res = x->p_res; x->h_pos = x->p_pos; x->h_sum = x->p_sum;
+        x->d_args = x->c_args; x->d_res_host = x->c_res; x->d_pos = x->c_pos; x->d_sum = x->c_sum;
+    } else {
+        st = x->m_args.reset(x->args_bytes);
+        if (!st) st = x->m_res.reset(nres);
+        if (!st) st = x->m_pos.reset(std::max<size_t>(npos, 1));
+        if (!st) st = x->m_sum.reset(1);
+        x->h_args = x->m_args.host(); x->h_res = x->m_res.host(); x->h_pos = x->m_pos.host(); x->h_sum = x->m_sum.host();
+        x->d_args = x->m_args; x->d_res_host = x->m_res; x->d_pos = x->m_pos; x->d_sum = x->m_sum;
     }
-    if (e != hipSuccess) st = fail(PCT_ERR_ALLOC, "replan buffers: %s", hipGetErrorString(e));
-    if (!st && copies) {
-        st = dev_alloc(&x->d_args, x->args_bytes);
-        if (!st) st = dev_alloc(&x->d_res_host, nres);
-        if (!st) st = dev_alloc(&x->d_pos, std::max<size_t>(npos, 1));
-        if (!st) st = dev_alloc(&x->d_sum, 1);
-    }
-    if (!st) st = dev_alloc(&x->d_meet, 1);
+    if (!st) st = x->d_meet.reset(1);
     if (!st) {
         const ReplanMeet m0{ 0u, 0x7FFFFFFF, 0x7FFFFFFF, 0u, 0u, { 0u, 0u, 0u } };
         if (hipMemcpy(x->d_meet, &m0, sizeof m0, hipMemcpyHostToDevice) != hipSuccess) st = fail(PCT_ERR_HIP, "hipMemcpy failed");
@@ -598,9 +553,7 @@ int replan_fill(ReplanCtx *x, const pct_inflate_params *p, const double *nodes, 
     *nsamples_total = 0;
     if (traj) {
         if (traj->nseg <= 0 || traj->nseg > x->max_seg) return fail(PCT_ERR_CAPACITY, "%d segments > plan capacity %d", traj->nseg, x->max_seg);
-        for (int i = 0; i < traj->nseg; i++)
-            if (traj->orders[i] < 0 || traj->orders[i] > kMaxBezierOrder || 3 * (traj->orders[i] + 1) > traj->row_stride)
-                return fail(PCT_ERR_INVALID, "segment %d: order %d unsupported", i, traj->orders[i]);
+        PCTCHK(bezier_check_orders(traj));
         H.nseg = traj->nseg;
         H.row_stride = x->row_cap;
         for (int i = 0; i < traj->nseg; i++) {
@@ -609,24 +562,13 @@ int replan_fill(ReplanCtx *x, const pct_inflate_params *p, const double *nodes, 
             f64a[H.off_segtime + i] = traj->seg_time[i];
             u32a[H.off_orders + i] = (uint32_t)traj->orders[i];
         }
-        double t_s = t_start;
-        int first_seg;
-        for (first_seg = 0; first_seg < traj->nseg; ++first_seg) {
-            if (t_s > traj->seg_time[first_seg] && first_seg + 1 < traj->nseg) t_s -= traj->seg_time[first_seg];
-            else break;
-        }
+        double t_s;
+        const int first_seg = bezier_first_segment(traj, t_start, &t_s);
         H.first_seg = first_seg;
-        int64_t n = 0;
-        double t_accu = 0.0;
-        for (int i = first_seg; i < traj->nseg; i++) {
-            const double T = traj->seg_time[i];
-            for (double t = (i == first_seg) ? t_s : 0.0; t < T; t += dt) {
-                t_accu += dt;
-                if (t_accu > stop_time) break;
-                if (n < room) { f64a[H.off_sample_t + n] = t; u32a[H.off_sample_seg + n] = (uint32_t)i; }
-                n++;
-            }
-        }
+        const int64_t n = bezier_enumerate_samples(traj, t_start, stop_time, dt, room, [&](int64_t k, double t, int seg) {
+            f64a[H.off_sample_t + k] = t;
+            u32a[H.off_sample_seg + k] = (uint32_t)seg;
+        });
         *nsamples_total = n;
         H.n_samples = (int32_t)std::min<int64_t>(n, room);
         if (with_ctrl) {
@@ -645,15 +587,10 @@ int replan_fill(ReplanCtx *x, const pct_inflate_params *p, const double *nodes, 
 // wait for the batch: the finish kernel's sequence word in host-mapped memory (a stream sync costs ~20 us more), or the stream
 int replan_wait(ReplanCtx *x, hipStream_t s)
 {
-    if (!x->copies && poll_results()) {
-        const volatile uint32_t *seq = &x->h_sum->seq;
-        for (long spins = 0; spins < 40000000l; spins++) {
-            if (*seq == x->seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); return PCT_OK; }
-            __builtin_ia32_pause();
-        }
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    if (x->h_sum->seq != x->seq) return fail(PCT_ERR_HIP, "replan batch finished without its sequence word (%u != %u)", x->h_sum->seq, x->seq);
+    hipError_t e = hipSuccess;       // (never poll in `copies` mode: the word arrives with the last copy)
+    const bool seen = pct_host::wait_word(&x->h_sum->seq, x->seq, !x->copies && poll_results() ? 40000000l : 0l, [&] { e = hipStreamSynchronize(s); });
+    if (e != hipSuccess) return fail(PCT_ERR_HIP, "hipStreamSynchronize -> %s", hipGetErrorString(e));
+    if (!seen) return fail(PCT_ERR_HIP, "replan batch finished without its sequence word (%u != %u)", x->h_sum->seq, x->seq);
     return PCT_OK;
 }
 
@@ -752,16 +689,16 @@ int pct_cloud_frame_buffer(pct_cloud *c, int64_t bytes, void **host_ptr)
     if (c->host_mapped) return fail(PCT_ERR_INVALID, "small (host-mapped) clouds are appended with plain stores already");
     HIPCHK(hipStreamSynchronize(g_stream));             // a launch may still be reading the old buffer
     PCTCHK(ring_finish_pending(c));
-    PCTCHK(ensure_frame_buffer(c, (size_t)bytes));
-    *host_ptr = c->h_frame;
+    PCTCHK(ensure_frame_staging(c->frame, (size_t)bytes));
+    *host_ptr = c->frame.host();
     return PCT_OK;
 }
 
 int pct_cloud_append_frame(pct_cloud *c, int64_t n, int64_t stride_bytes)
 {
-    if (!c || !c->h_frame) return fail(PCT_ERR_INVALID, "no frame buffer (pct_cloud_frame_buffer)");
-    if (n < 0 || stride_bytes < 12 || (uint64_t)n * (uint64_t)stride_bytes > c->frame_cap) return fail(PCT_ERR_INVALID, "the frame does not fit the buffer handed out");
-    return pct_cloud_append_aos(c, c->h_frame, n, stride_bytes);
+    if (!c || !c->frame.host()) return fail(PCT_ERR_INVALID, "no frame buffer (pct_cloud_frame_buffer)");
+    if (n < 0 || stride_bytes < 12 || (uint64_t)n * (uint64_t)stride_bytes > c->frame.capacity()) return fail(PCT_ERR_INVALID, "the frame does not fit the buffer handed out");
+    return pct_cloud_append_aos(c, c->frame.host(), n, stride_bytes);
 }
 
 int pct_cloud_ring_drop(pct_cloud *c)
@@ -808,7 +745,7 @@ int pct_cloud_ring_dedup_last(pct_cloud *c, int64_t *offered, int64_t *kept, uin
     const int64_t nf = std::min(c->dd_last_offered, cap);
     if (flags && nf > 0) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        HIPCHK(hipMemcpy(flags, c->dd_flags, (size_t)nf, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(flags, c->dd.flags, (size_t)nf, hipMemcpyDeviceToHost));
     }
     return PCT_OK;
 }
@@ -874,16 +811,10 @@ int pct_ctrl_points_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_i
 {
     if (!c || !traj || !p || !first_hit || !nctrl || !traj->polycoef || !traj->seg_time || !traj->orders || traj->nseg <= 0 || cap < 0)
         return fail(PCT_ERR_INVALID, "bad ctrl_points_check arguments");
-    for (int i = 0; i < traj->nseg; i++)
-        if (traj->orders[i] < 0 || traj->orders[i] > kMaxBezierOrder || 3 * (traj->orders[i] + 1) > traj->row_stride)
-            return fail(PCT_ERR_INVALID, "segment %d: order %d unsupported", i, traj->orders[i]);
+    PCTCHK(bezier_check_orders(traj));
     // the control points in world units, segments from the one holding t_start on (the segment search of checkSafeTrajectory)
-    double t_s = t_start;
-    int first_seg;
-    for (first_seg = 0; first_seg < traj->nseg; ++first_seg) {
-        if (t_s > traj->seg_time[first_seg] && first_seg + 1 < traj->nseg) t_s -= traj->seg_time[first_seg];
-        else break;
-    }
+    double t_s;
+    const int first_seg = bezier_first_segment(traj, t_start, &t_s);
     std::vector<double> pts;
     for (int i = first_seg; i < traj->nseg; i++) {
         const int m = traj->orders[i] + 1;
@@ -976,12 +907,9 @@ namespace {
 
 int ring_remove_ensure(pct_cloud *c)
 {
-    if (!c->h_rm_word) {
-        PCTCHK(mapped_alloc(&c->h_rm_word, &c->d_rm_word, 4));
-        for (int k = 0; k < 4; k++) c->h_rm_word[k] = 0;
-    }
+    PCTCHK(c->rm_word.ensure(4));
     if (!c->d_rm_meet) {
-        PCTCHK(dev_alloc(&c->d_rm_meet, 1));
+        PCTCHK(c->d_rm_meet.reset(1));
         HIPCHK(hipMemsetAsync(c->d_rm_meet, 0, sizeof(RingRemoveMeet), g_stream));
     }
     return PCT_OK;
@@ -990,18 +918,9 @@ int ring_remove_ensure(pct_cloud *c)
 // the ONE host wait of a removal: {removed, live after}, polled in host-mapped memory as the de-dup filter's survivor count is
 int ring_remove_wait(pct_cloud *c, uint32_t seq, int64_t *removed, int64_t *live)
 {
-    bool seen = false;
-    if (poll_results()) {
-        const volatile uint32_t *w = c->h_rm_word;
-        for (long spins = 0; spins < 200000000l && !seen; spins++) {
-            if (w[0] == seq) { __atomic_thread_fence(__ATOMIC_ACQUIRE); seen = true; }
-            else __builtin_ia32_pause();
-        }
-    }
-    if (!seen) HIPCHK(hipStreamSynchronize(g_stream));
-    if (c->h_rm_word[0] != seq) return fail(PCT_ERR_HIP, "the removal finished without its sequence word (%u != %u)", c->h_rm_word[0], seq);
-    *removed = (int64_t)c->h_rm_word[1];
-    *live = (int64_t)c->h_rm_word[2];
+    PCTCHK(c->rm_word.wait(seq, "the removal"));
+    *removed = (int64_t)c->rm_word.w.host()[1];
+    *live = (int64_t)c->rm_word.w.host()[2];
     if (*removed + *live > c->count) return fail(PCT_ERR_INTERNAL, "a removal counted %lld + %lld rows of %lld", (long long)*removed, (long long)*live, (long long)c->count);
     return PCT_OK;
 }
@@ -1039,9 +958,9 @@ int ring_remove_region(pct_cloud *c, const RingRegion &G, int64_t *removed_out)
     if (removed_out) *removed_out = 0;
     if (c->count == 0) return PCT_OK;
     PCTCHK(ring_remove_ensure(c));
-    const uint32_t seq = ++c->rm_seq;
+    const uint32_t seq = c->rm_word.next();
     ring_remove_region_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, G, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht, c->ring_slots,
-                                                                            c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->d_rm_word, seq);
+                                                                            c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->rm_word.w, seq);
     HIPCHK(hipGetLastError());
     int64_t removed = 0, live = 0;
     PCTCHK(ring_remove_wait(c, seq, &removed, &live));
@@ -1092,23 +1011,18 @@ int pct_cloud_ring_remove_indices(pct_cloud *c, const uint32_t *idx, int64_t n, 
                         (long long)(c->index_base + c->count));
     if (n > 0xFFFFFFF0ll) return fail(PCT_ERR_INVALID, "ring_remove_indices: the list is too long");
     PCTCHK(ring_remove_ensure(c));
-    if ((size_t)n > c->rm_list_cap) {
+    if ((size_t)n > c->d_rm_list.capacity()) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        dev_free(c->d_rm_list);
-        c->rm_list_cap = 0;
-        size_t cap = 1024;
-        while (cap < (size_t)n) cap <<= 1;
-        PCTCHK(dev_alloc(&c->d_rm_list, cap));
-        c->rm_list_cap = cap;
+        PCTCHK(c->d_rm_list.reserve((size_t)n, pow2_at_least<size_t>(1024, (size_t)n)));
     }
     std::vector<uint32_t> slots;
     try { slots.resize((size_t)n); } catch (const std::bad_alloc &) { return fail(PCT_ERR_ALLOC, "host allocation failed"); }
     for (int64_t i = 0; i < n; i++) slots[(size_t)i] = idx[i] - (uint32_t)c->index_base;
     HIPCHK(hipMemcpyAsync(c->d_rm_list, slots.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, g_stream));
-    const uint32_t seq = ++c->rm_seq;
+    const uint32_t seq = c->rm_word.next();
     ring_remove_list_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(c->R, c->d_rm_list, (uint32_t)n, c->x, c->y, c->z, c->ring_ht, c->ring_slots, c->ring_ovf,
                                                                    c->ring_where, c->ring_st, c->d_rm_meet);
-    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_rm_meet, c->d_rm_word, seq);
+    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_rm_meet, c->rm_word.w, seq);
     HIPCHK(hipGetLastError());
     int64_t removed = 0, live = 0;
     PCTCHK(ring_remove_wait(c, seq, &removed, &live));         // (the list has left `slots` by now: the copy precedes the kernels)
@@ -1123,8 +1037,8 @@ int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
     PCTCHK(ring_remove_begin(c, "pct_cloud_ring_live"));
     if (c->count == 0) return PCT_OK;
     PCTCHK(ring_remove_ensure(c));
-    const uint32_t seq = ++c->rm_seq;
-    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_rm_meet, c->d_rm_word, seq);
+    const uint32_t seq = c->rm_word.next();
+    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_rm_meet, c->rm_word.w, seq);
     HIPCHK(hipGetLastError());
     int64_t removed = 0, live = 0;
     PCTCHK(ring_remove_wait(c, seq, &removed, &live));
@@ -1153,14 +1067,6 @@ int depth_view_check(const pct_depth_view *v, const char *what)
     return PCT_OK;
 }
 
-// An image on its way to the device: the caller's floats are copied into pinned memory the library owns and from there to a device
-// buffer on the library's stream (both grow-only), so the caller's buffer is its own again at once and the kernels gather from HBM
-// / L2, not across the bus.  Every user waits for a kernel behind the copy before it returns: the pinned buffer is free by then.
-struct DepthStage {
-    float *h = nullptr, *d = nullptr;
-    size_t cap = 0;                              // floats
-};
-
 int depth_stage_image(DepthStage *S, const float *image, size_t off, size_t npix)
 {
     std::memcpy(S->h + off, image, sizeof(float) * npix);
@@ -1172,77 +1078,41 @@ int depth_stage_ensure(DepthStage *S, size_t floats)
 {
     if (floats <= S->cap) return PCT_OK;
     HIPCHK(hipStreamSynchronize(g_stream));
-    if (S->h) (void)hipHostFree(S->h);
-    dev_free(S->d);
-    S->h = nullptr; S->cap = 0;
-    size_t cap = (size_t)1 << 14;
-    while (cap < floats) cap <<= 1;
-    void *h = nullptr;
-    if (hipHostMalloc(&h, cap * sizeof(float), hipHostMallocDefault) != hipSuccess) return fail(PCT_ERR_ALLOC, "hipHostMalloc(%zu bytes) failed", cap * sizeof(float));
-    S->h = static_cast<float *>(h);
-    if (const int st = dev_alloc(&S->d, cap)) { (void)hipHostFree(S->h); S->h = nullptr; return st; }
+    S->cap = 0;
+    S->h.release(); S->d.release();
+    const size_t cap = pow2_at_least((size_t)1 << 14, floats);
+    PCTCHK(S->h.reset(cap));
+    if (const int st = S->d.reset(cap)) { S->h.release(); return st; }
     S->cap = cap;
     return PCT_OK;
-}
-
-void depth_stage_free(DepthStage *S)
-{
-    if (S->h) (void)hipHostFree(S->h);
-    dev_free(S->d);
-    S->h = nullptr; S->cap = 0;
 }
 
 // scratch of pct_cloud_append_depth for an image of npix pixels (grow-only): validity flags, ranks, tile totals, the packed frame
 int depth_scratch_ensure(pct_cloud *c, int64_t npix)
 {
-    PCTCHK(dd_word_ensure(c));
-    if (npix <= c->dp_ncap) return PCT_OK;
+    PCTCHK(c->dd_word.ensure(4));
+    if (npix <= c->dp.ncap) return PCT_OK;
     HIPCHK(hipStreamSynchronize(g_stream));       // the previous append's insert kernel may still be reading the packed frame
-    dev_free(c->dp_flags); dev_free(c->dp_rank); dev_free(c->dp_tile); dev_free(c->dp_out);
-    c->dp_ncap = 0;
-    int64_t cap = 4096;
-    while (cap < npix) cap <<= 1;
-    PCTCHK(dev_alloc(&c->dp_flags, (size_t)cap));
-    PCTCHK(dev_alloc(&c->dp_rank, (size_t)cap));
-    PCTCHK(dev_alloc(&c->dp_tile, (size_t)ceil_div(cap, kDdTile)));
-    PCTCHK(dev_alloc(&c->dp_out, 3 * (size_t)cap));
-    c->dp_ncap = cap;
-    return PCT_OK;
+    return c->dp.ensure(pow2_at_least<int64_t>(4096, npix));
 }
 
 // pct_depth_classify has no cloud to keep its buffers in: one grow-only set for the process, used under a lock
 struct DepthClassifyWork {
     std::mutex lock;
     DepthStage images;
-    double *d_pts = nullptr;
-    int32_t *d_seen = nullptr, *d_pixel = nullptr;
+    DevBuf<double> d_pts;
+    DevBuf<int32_t> d_seen, d_pixel;
     int64_t ncap = 0;
 };
-DepthClassifyWork g_depth_work;
-
-}  // namespace
-
-void depth_cloud_free(pct_cloud *c)
-{
-    DepthStage S{ c->dp_himg, c->dp_dimg, c->dp_img_cap };
-    depth_stage_free(&S);
-    c->dp_himg = nullptr; c->dp_dimg = nullptr; c->dp_img_cap = 0;
-    dev_free(c->dp_flags); dev_free(c->dp_rank); dev_free(c->dp_tile); dev_free(c->dp_out);
-    c->dp_ncap = 0;
-}
-
-namespace {
+DepthClassifyWork &g_depth_work = *new DepthClassifyWork();      // never destroyed: the HIP runtime may be gone by then
 
 // the cloud's image staging: copy `image` in and hand back where the kernels read it
 int depth_cloud_image(pct_cloud *c, const pct_depth_view *v, const float *image, const float **d_image)
 {
     const size_t npix = (size_t)v->width * (size_t)v->height;
-    DepthStage S{ c->dp_himg, c->dp_dimg, c->dp_img_cap };
-    const int st = depth_stage_ensure(&S, npix);
-    c->dp_himg = S.h; c->dp_dimg = S.d; c->dp_img_cap = S.cap;
-    PCTCHK(st);
-    PCTCHK(depth_stage_image(&S, image, 0, npix));
-    *d_image = S.d;
+    PCTCHK(depth_stage_ensure(&c->dp_img, npix));
+    PCTCHK(depth_stage_image(&c->dp_img, image, 0, npix));
+    *d_image = c->dp_img.d;
     return PCT_OK;
 }
 
@@ -1261,9 +1131,9 @@ int pct_cloud_ring_carve_depth(pct_cloud *c, const pct_depth_view *v, const floa
     PCTCHK(ring_remove_ensure(c));
     const float *d_image = nullptr;
     PCTCHK(depth_cloud_image(c, v, image, &d_image));
-    const uint32_t seq = ++c->rm_seq;
+    const uint32_t seq = c->rm_word.next();
     depth_carve_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, *v, d_image, margin, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht,
-                                                                     c->ring_slots, c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->d_rm_word, seq);
+                                                                     c->ring_slots, c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->rm_word.w, seq);
     HIPCHK(hipGetLastError());
     int64_t removed = 0, live = 0;
     PCTCHK(ring_remove_wait(c, seq, &removed, &live));
@@ -1287,12 +1157,12 @@ int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *i
     PCTCHK(depth_cloud_image(c, v, image, &d_image));
     // flags of the valid pixels, their ranks in row-major order, and the FIRST host wait: the valid count -- the capacity test, the
     // slots the append takes and the filter's table size all need it before anything is queued that changes the window
-    const uint32_t un = (uint32_t)npix, seq = ++c->dd_seq;
+    const uint32_t un = (uint32_t)npix, seq = c->dd_word.next();
     const int ntiles = ceil_div(npix, kDdTile);
-    depth_valid_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, max_depth, c->dp_flags);
-    dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dp_flags, un, c->dp_rank, c->dp_tile);
-    dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dp_tile, (uint32_t)ntiles, c->d_dd_word, seq);
-    depth_unproject_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, c->dp_flags, c->dp_rank, c->dp_tile, c->dp_out);
+    depth_valid_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, max_depth, c->dp.flags);
+    dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dp.flags, un, c->dp.rank, c->dp.tile);
+    dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dp.tile, (uint32_t)ntiles, c->dd_word.w, seq);
+    depth_unproject_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, c->dp.flags, c->dp.rank, c->dp.tile, c->dp.out);
     HIPCHK(hipGetLastError());
     int64_t n = 0;
     PCTCHK(dd_scan_wait(c, seq, &n));
@@ -1300,7 +1170,7 @@ int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *i
     if (n > c->cap) return fail(PCT_ERR_CAPACITY, "appending %lld valid pixels to a ring of %lld", (long long)n, (long long)c->cap);
     *offered = n;
     // from here on: pct_cloud_append_aos of the n un-projected points, their source being the packed device frame
-    const unsigned char *d_frame = reinterpret_cast<const unsigned char *>(c->dp_out);
+    const unsigned char *d_frame = reinterpret_cast<const unsigned char *>(c->dp.out.get());
     if (c->dd_res > 0) {
         PCTCHK(ring_append_dedup(c, nullptr, n, 12, d_frame));          // the SECOND host wait: the survivor count
         *kept = c->dd_last_kept;
@@ -1310,7 +1180,7 @@ int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *i
     if (n == 0) return PCT_OK;
     drop_grid(c);
     if (c->ring_ready) return ring_append(c, nullptr, n, 12, d_frame);
-    return append_unindexed_dev(c, c->dp_out, n);
+    return append_unindexed_dev(c, c->dp.out, n);
 }
 
 int pct_depth_classify(const pct_depth_view *views, const float *const *images, int32_t n_views, const double *pts, int64_t n, double margin,
@@ -1332,13 +1202,12 @@ int pct_depth_classify(const pct_depth_view *views, const float *const *images, 
     PCTCHK(depth_stage_ensure(&W.images, total));
     if (n > W.ncap) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        dev_free(W.d_pts); dev_free(W.d_seen); dev_free(W.d_pixel);
         W.ncap = 0;
-        int64_t cap = 1024;
-        while (cap < n) cap <<= 1;
-        PCTCHK(dev_alloc(&W.d_pts, 3 * (size_t)cap));
-        PCTCHK(dev_alloc(&W.d_seen, (size_t)cap));
-        PCTCHK(dev_alloc(&W.d_pixel, 2 * (size_t)cap));
+        W.d_pts.release(); W.d_seen.release(); W.d_pixel.release();
+        const int64_t cap = pow2_at_least<int64_t>(1024, n);
+        PCTCHK(W.d_pts.reset(3 * (size_t)cap));
+        PCTCHK(W.d_seen.reset((size_t)cap));
+        PCTCHK(W.d_pixel.reset(2 * (size_t)cap));
         W.ncap = cap;
     }
     DepthViews S{};

@@ -118,29 +118,16 @@ __global__ __launch_bounds__(256) void wire_step_kernel(const double *__restrict
     step[g] = sqrt((dx * dx + dy * dy) + dz * dz);
 }
 
+// process-wide scratch (grow-only, at least 4096 elements each); never destroyed: the HIP runtime may be gone by then
 struct Workspace {
-    double *d_a = nullptr;      // general fp64 scratch (inputs)
-    size_t a_cap = 0;
-    double *d_b = nullptr;      // general fp64 scratch (outputs)
-    size_t b_cap = 0;
-    int32_t *d_i = nullptr;     // int scratch
-    size_t i_cap = 0;
-} g_ws;
+    pct_internal::DevBuf<double> d_a;      // general fp64 scratch (inputs)
+    pct_internal::DevBuf<double> d_b;      // general fp64 scratch (outputs)
+    pct_internal::DevBuf<int32_t> d_i;     // int scratch
+};
+Workspace &g_ws = *new Workspace();
 
 template <typename T>
-int grow(T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap) return PCT_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    void *v = nullptr;
-    const size_t n = std::max<size_t>(need, 4096);
-    if (hipMalloc(&v, n * sizeof(T)) != hipSuccess) return fail(PCT_ERR_ALLOC, "hipMalloc(%zu bytes) failed", n * sizeof(T));
-    *p = static_cast<T *>(v);
-    *cap = n;
-    return PCT_OK;
-}
+int ws_reserve(pct_internal::DevBuf<T> &b, size_t need) { return b.reserve(need, std::max<size_t>(need, 4096)); }
 
 int check_matrix_traj(const pct_bezier_traj *t)
 {
@@ -181,9 +168,9 @@ int sample_wire_device(const pct_traj_wire *w, int32_t samples, int64_t *total_o
     if (total == 0) return PCT_OK;
     // inputs: cx | cy | cz | time  (doubles), order | shift (u32)
     const size_t nc = (size_t)w->ncoef;
-    PCTCHK(grow(&g_ws.d_a, &g_ws.a_cap, 3 * nc + (size_t)nseg));
-    PCTCHK(grow(&g_ws.d_i, &g_ws.i_cap, 2 * (size_t)nseg));
-    PCTCHK(grow(&g_ws.d_b, &g_ws.b_cap, 4 * (size_t)total));
+    PCTCHK(ws_reserve(g_ws.d_a, 3 * nc + (size_t)nseg));
+    PCTCHK(ws_reserve(g_ws.d_i, 2 * (size_t)nseg));
+    PCTCHK(ws_reserve(g_ws.d_b, 4 * (size_t)total));
     HIPCHK(hipMemcpyAsync(g_ws.d_a, w->coef_x, sizeof(double) * nc, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(g_ws.d_a + nc, w->coef_y, sizeof(double) * nc, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(g_ws.d_a + 2 * nc, w->coef_z, sizeof(double) * nc, hipMemcpyHostToDevice, s));
@@ -194,7 +181,7 @@ int sample_wire_device(const pct_traj_wire *w, int32_t samples, int64_t *total_o
     double *pos = g_ws.d_b, *step = g_ws.d_b + 3 * total;
     const int nb = (int)((total + 255) / 256);
     wire_sample_kernel<<<nb, 256, 0, s>>>(g_ws.d_a, g_ws.d_a + nc, g_ws.d_a + 2 * nc, g_ws.d_a + 3 * nc,
-                                          reinterpret_cast<const uint32_t *>(g_ws.d_i), reinterpret_cast<const uint32_t *>(g_ws.d_i + nseg),
+                                          reinterpret_cast<const uint32_t *>(g_ws.d_i.get()), reinterpret_cast<const uint32_t *>(g_ws.d_i + nseg),
                                           nseg, samples, pos);
     // last_p starts as coef_vec(traj_ext, 0) * traj_ext.time[0]
     wire_step_kernel<<<nb, 256, 0, s>>>(pos, total, w->coef_x[0] * w->time[0], w->coef_y[0] * w->time[0], w->coef_z[0] * w->time[0], step);
@@ -218,9 +205,9 @@ int pct_bezier_state_batch(const pct_bezier_traj *traj, const int32_t *seg, cons
     PCTCHK(pct_internal::require_init());
     hipStream_t s = pct_internal::stream();
     const size_t ncoef = (size_t)traj->nseg * (size_t)traj->row_stride;
-    PCTCHK(grow(&g_ws.d_a, &g_ws.a_cap, ncoef + (size_t)n));
-    PCTCHK(grow(&g_ws.d_i, &g_ws.i_cap, (size_t)traj->nseg + (size_t)n));
-    PCTCHK(grow(&g_ws.d_b, &g_ws.b_cap, 9 * (size_t)n));
+    PCTCHK(ws_reserve(g_ws.d_a, ncoef + (size_t)n));
+    PCTCHK(ws_reserve(g_ws.d_i, (size_t)traj->nseg + (size_t)n));
+    PCTCHK(ws_reserve(g_ws.d_b, 9 * (size_t)n));
     HIPCHK(hipMemcpyAsync(g_ws.d_a, traj->polycoef, sizeof(double) * ncoef, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(g_ws.d_a + ncoef, u, sizeof(double) * n, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(g_ws.d_i, traj->orders, sizeof(int32_t) * traj->nseg, hipMemcpyHostToDevice, s));
@@ -335,13 +322,12 @@ int pct_traj_end_yaws(const double *path_x, const double *path_y, int64_t n, con
 int pct_debug_binomials(double *pascal, double *recurrence)
 {
     if (!pascal || !recurrence) return fail(PCT_ERR_INVALID, "null output");
-    double *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, sizeof(double) * 2 * 169));
+    pct_internal::DevBuf<double> d;
+    PCTCHK(d.reset(2 * 169));
     binomial_tables_kernel<<<1, 192>>>(d, d + 169);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(pascal, d, sizeof(double) * 169, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(recurrence, d + 169, sizeof(double) * 169, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(PCT_ERR_HIP, "binomial tables: %s", hipGetErrorString(e));
     return PCT_OK;
 }

@@ -179,22 +179,7 @@ __global__ __launch_bounds__(256) void vox_report_kernel(const uint32_t *__restr
     if (voxel_index) voxel_index[i] = pslot[i] == kNoSlot ? -1 : (int32_t)vals[pslot[i]];
 }
 
-template <typename T>
-int dev_alloc(T **p, size_t count)
-{
-    void *v = nullptr;
-    hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(PCT_ERR_ALLOC, "hipMalloc(%zu bytes) -> %s", count * sizeof(T), hipGetErrorString(e));
-    *p = static_cast<T *>(v);
-    return PCT_OK;
-}
-
-template <typename T>
-void dev_free(T *&p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
+using pct_internal::DevBuf;
 
 inline int blocks_for(int64_t n, int per) { return (int)std::max<int64_t>(1, (n + per - 1) / per); }
 
@@ -205,20 +190,19 @@ struct pct_voxel_map {
     int64_t size = 0;                 // voxels
     // hash table
     uint32_t T = 0;
-    unsigned long long *keys = nullptr;
-    uint32_t *vals = nullptr;
+    DevBuf<unsigned long long> keys;
+    DevBuf<uint32_t> vals;
     // voxel store
     int64_t vcap = 0;
-    int *vx = nullptr, *vy = nullptr, *vz = nullptr;
-    float *fx = nullptr, *fy = nullptr, *fz = nullptr;
+    DevBuf<int> vx, vy, vz;
+    DevBuf<float> fx, fy, fz;
     // per-batch scratch
     int64_t ncap = 0;
-    uint32_t *pslot = nullptr, *rank = nullptr, *tile = nullptr;
-    unsigned char *stage = nullptr;
-    size_t stage_bytes = 0;
-    uint8_t *d_is_new = nullptr;
-    int32_t *d_index = nullptr;
-    VoxFlags *d_flags = nullptr;
+    DevBuf<uint32_t> pslot, rank, tile;
+    DevBuf<unsigned char> stage;
+    DevBuf<uint8_t> d_is_new;
+    DevBuf<int32_t> d_index;
+    DevBuf<VoxFlags> d_flags;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
 };
@@ -227,10 +211,10 @@ namespace {
 
 int table_alloc(pct_voxel_map *m, uint32_t T)
 {
-    dev_free(m->keys); dev_free(m->vals);
     m->T = 0;
-    PCTCHK(dev_alloc(&m->keys, T));
-    PCTCHK(dev_alloc(&m->vals, T));
+    m->keys.release(); m->vals.release();
+    PCTCHK(m->keys.reset(T));
+    PCTCHK(m->vals.reset(T));
     m->T = T;
     vox_table_init_kernel<<<std::min(blocks_for(T, 256), 4096), 256, 0, pct_internal::stream()>>>(m->keys, m->vals, T);
     HIPCHK(hipGetLastError());
@@ -239,8 +223,7 @@ int table_alloc(pct_voxel_map *m, uint32_t T)
 
 uint32_t table_size_for(int64_t voxels)
 {
-    uint64_t T = 1024;
-    while (T < (uint64_t)voxels * 2) T <<= 1;     // load factor <= 0.5
+    const uint64_t T = pct_host::pow2_at_least<uint64_t>(1024, (uint64_t)voxels * 2);     // load factor <= 0.5
     return (uint32_t)std::min<uint64_t>(T, 1ull << 31);
 }
 
@@ -252,10 +235,10 @@ int ensure_capacity(pct_voxel_map *m, int64_t extra)
     if (need > (int64_t)0x7FFFFFFF) return fail(PCT_ERR_INVALID, "voxel map would exceed 2^31 voxels");
     if (need > m->vcap) {
         const int64_t cap = std::max<int64_t>(need, m->vcap * 2);
-        int *nx = nullptr, *ny = nullptr, *nz = nullptr;
-        float *gx = nullptr, *gy = nullptr, *gz = nullptr;
-        PCTCHK(dev_alloc(&nx, cap)); PCTCHK(dev_alloc(&ny, cap)); PCTCHK(dev_alloc(&nz, cap));
-        PCTCHK(dev_alloc(&gx, cap)); PCTCHK(dev_alloc(&gy, cap)); PCTCHK(dev_alloc(&gz, cap));
+        DevBuf<int> nx, ny, nz;                     // grow with copy: new blocks, copy, move-assign (the old ones go then)
+        DevBuf<float> gx, gy, gz;
+        PCTCHK(nx.reset(cap)); PCTCHK(ny.reset(cap)); PCTCHK(nz.reset(cap));
+        PCTCHK(gx.reset(cap)); PCTCHK(gy.reset(cap)); PCTCHK(gz.reset(cap));
         if (m->size) {
             const size_t bi = sizeof(int) * m->size, bf = sizeof(float) * m->size;
             HIPCHK(hipMemcpyAsync(nx, m->vx, bi, hipMemcpyDeviceToDevice, s));
@@ -266,8 +249,8 @@ int ensure_capacity(pct_voxel_map *m, int64_t extra)
             HIPCHK(hipMemcpyAsync(gz, m->fz, bf, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipStreamSynchronize(s));
         }
-        dev_free(m->vx); dev_free(m->vy); dev_free(m->vz); dev_free(m->fx); dev_free(m->fy); dev_free(m->fz);
-        m->vx = nx; m->vy = ny; m->vz = nz; m->fx = gx; m->fy = gy; m->fz = gz;
+        m->vx = std::move(nx); m->vy = std::move(ny); m->vz = std::move(nz);
+        m->fx = std::move(gx); m->fy = std::move(gy); m->fz = std::move(gz);
         m->vcap = cap;
     }
     if ((uint64_t)need * 2 > m->T) {
@@ -284,11 +267,11 @@ int ensure_scratch(pct_voxel_map *m, int64_t n)
 {
     if (n <= m->ncap) return PCT_OK;
     const int64_t cap = std::max<int64_t>(n, m->ncap * 2);
-    dev_free(m->pslot); dev_free(m->rank); dev_free(m->tile); dev_free(m->d_is_new); dev_free(m->d_index);
     m->ncap = 0;
-    PCTCHK(dev_alloc(&m->pslot, cap));
-    PCTCHK(dev_alloc(&m->rank, cap));
-    PCTCHK(dev_alloc(&m->tile, (cap + kTile - 1) / kTile));
+    m->pslot.release(); m->rank.release(); m->tile.release(); m->d_is_new.release(); m->d_index.release();
+    PCTCHK(m->pslot.reset(cap));
+    PCTCHK(m->rank.reset(cap));
+    PCTCHK(m->tile.reset((cap + kTile - 1) / kTile));
     m->ncap = cap;
     return PCT_OK;
 }
@@ -346,7 +329,7 @@ int pct_voxel_map_create(double res, int64_t capacity_hint, pct_voxel_map **out)
     PCTCHK(pct_internal::require_init());
     pct_voxel_map *m = new pct_voxel_map();
     m->res = res;
-    int st = dev_alloc(&m->d_flags, 1);
+    int st = m->d_flags.reset(1);
     if (st == PCT_OK && hipEventCreate(&m->ev0) != hipSuccess) st = fail(PCT_ERR_HIP, "hipEventCreate failed");
     if (st == PCT_OK && hipEventCreate(&m->ev1) != hipSuccess) st = fail(PCT_ERR_HIP, "hipEventCreate failed");
     if (st == PCT_OK) st = ensure_capacity(m, std::max<int64_t>(capacity_hint, 1024));
@@ -359,10 +342,6 @@ int pct_voxel_map_destroy(pct_voxel_map *m)
 {
     if (!m) return PCT_OK;
     if (pct_internal::stream()) (void)hipStreamSynchronize(pct_internal::stream());
-    dev_free(m->keys); dev_free(m->vals);
-    dev_free(m->vx); dev_free(m->vy); dev_free(m->vz); dev_free(m->fx); dev_free(m->fy); dev_free(m->fz);
-    dev_free(m->pslot); dev_free(m->rank); dev_free(m->tile); dev_free(m->stage); dev_free(m->d_is_new); dev_free(m->d_index);
-    dev_free(m->d_flags);
     if (m->ev0) (void)hipEventDestroy(m->ev0);
     if (m->ev1) (void)hipEventDestroy(m->ev1);
     delete m;
@@ -406,18 +385,13 @@ int pct_voxel_map_add(pct_voxel_map *m, const void *pts, int64_t n, int64_t stri
     if (n == 0) return PCT_OK;
     hipStream_t s = pct_internal::stream();
     const size_t bytes = (size_t)n * (size_t)stride_bytes;
-    if (bytes > m->stage_bytes) {
-        dev_free(m->stage);
-        m->stage_bytes = 0;
-        PCTCHK(dev_alloc(&m->stage, bytes));
-        m->stage_bytes = bytes;
-    }
+    PCTCHK(m->stage.reserve(bytes));
     PCTCHK(ensure_scratch(m, n));
-    if (is_new && !m->d_is_new) PCTCHK(dev_alloc(&m->d_is_new, (size_t)m->ncap));
-    if (voxel_index && !m->d_index) PCTCHK(dev_alloc(&m->d_index, (size_t)m->ncap));
+    if (is_new && !m->d_is_new) PCTCHK(m->d_is_new.reset((size_t)m->ncap));
+    if (voxel_index && !m->d_index) PCTCHK(m->d_index.reset((size_t)m->ncap));
     HIPCHK(hipMemcpyAsync(m->stage, pts, bytes, hipMemcpyHostToDevice, s));
-    const int st = pct_voxel_map_add_dev(m, m->stage, n, stride_bytes, is_f64, n_new, is_new ? m->d_is_new : nullptr,
-                                         voxel_index ? m->d_index : nullptr);
+    const int st = pct_voxel_map_add_dev(m, m->stage, n, stride_bytes, is_f64, n_new, is_new ? m->d_is_new.get() : nullptr,
+                                         voxel_index ? m->d_index.get() : nullptr);
     if (st != PCT_OK && st != PCT_ERR_INVALID) return st;
     if (is_new) HIPCHK(hipMemcpyAsync(is_new, m->d_is_new, (size_t)n, hipMemcpyDeviceToHost, s));
     if (voxel_index) HIPCHK(hipMemcpyAsync(voxel_index, m->d_index, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));

@@ -210,6 +210,7 @@ def lib():
         L.pct_set_work_counters.argtypes = [vp, i32]
         L.pct_last_work_ex.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.pct_debug_verify_grid.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.pct_debug_live_buffers.argtypes = [C.POINTER(i64), C.POINTER(i64)]
         L.pct_cloud_pyramid_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(i64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
@@ -230,6 +231,13 @@ def device_count() -> int:
 
 def sync():
     _chk(lib().pct_sync())
+
+
+def live_buffers():
+    """(blocks, bytes) of device, pinned and host-mapped memory the library holds right now (pct_debug_live_buffers)"""
+    blocks, nbytes = C.c_int64(), C.c_int64()
+    _chk(lib().pct_debug_live_buffers(C.byref(blocks), C.byref(nbytes)))
+    return blocks.value, nbytes.value
 
 
 def set_filter_mode(mode: int):
