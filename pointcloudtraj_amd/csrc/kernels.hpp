@@ -1312,7 +1312,19 @@ __device__ __forceinline__ void coop_scan_cube_or_shell(const GridDesc &G, const
 // dependent memory round trips: one for the bounds, one for the points).  Leaves (bd, bi) = (+inf, none) for empty runs.
 // The clamp keeps the lanes beyond a run on the run's last cache line (reading the slots behind the run unclamped measured slower:
 // DESIGN.md, retired variants).
-template <int NR, int DEPTH>
+//
+// TAIL (stage 0 of the dense batch kernel): one more slot per lane, shared by the NR runs and requested together with the main ones.
+// A run longer than its 8 * DEPTH main slots has a tail of t_k = len_k - 8 * DEPTH records; a rolled loop per run takes a tail in
+// dependent round trips with nothing else of the wave in flight (2.2 such trips per wave at 6 points per cell).  With T = sum of the
+// t_k -- computed from the run bounds, which every lane of the group holds: no shuffles -- a group with T <= 8 gives lane `sub` the
+// tail record number `sub` in run order (the run whose prefix range [sum of t before k, + t_k) holds it) and masks the lanes
+// sub >= T to +inf; those read their last main slot again (a line the group touches anyway).  A group with T > 8 (0.7 % of the
+// queries) masks the slot off altogether and keeps the loops for ALL its tails, so no record is screened twice.
+// Results cannot change: the same set of records -- every record of the NR runs, once -- goes through the same fp32 expression into
+// the same (m1, m2, p1) update, only in another order, and min / runner-up are order-independent up to WHICH of several equal minima
+// p1 names; equal minima have m2 == m1, fail the band test below and go to the exact rescan, which orders by (d2, index) in fp64.
+// So whenever fp32 cannot decide, exact arithmetic does, as before.
+template <int NR, int DEPTH, bool TAIL = false>
 __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts, const uint32_t (&rs)[NR], const uint32_t (&re)[NR],
                                                  uint32_t sub, float qxf, float qyf, float qzf, double qx, double qy, double qz,
                                                  double &bd, uint32_t &bi)
@@ -1327,6 +1339,24 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
         const uint32_t last = b > a ? b - 1 : 0u;               // empty row: read slot 0, masked below
 #pragma unroll
         for (int j = 0; j < DEPTH; j++) P[k][j] = pts[min(a + sub + kCoop * j, last)];
+    }
+    uint32_t tp = 0;                                              // the shared tail slot: position, in use, the group takes the loops instead
+    bool tail_on = false, tail_loops = false;
+    float4 PT = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (TAIL) {
+        constexpr uint32_t kMain = kCoop * DEPTH;
+        uint32_t T = 0;
+#pragma unroll
+        for (int k = 0; k < NR; k++) {
+            const uint32_t t = max(re[k] - rs[k], kMain) - kMain;
+            tp = sub >= T ? rs[k] + kMain + (sub - T) : tp;          // T = exclusive prefix here: the last run with prefix <= sub holds the lane's record
+            T += t;
+        }
+        tail_on = sub < T && T <= (uint32_t)kCoop;
+        tail_loops = T > (uint32_t)kCoop;
+        const uint32_t a = rs[NR - 1], b = re[NR - 1];
+        tp = tail_on ? tp : min(a + sub + kCoop * (DEPTH - 1), b > a ? b - 1 : 0u);   // idle: the lane's last main slot again
+        PT = pts[tp];
     }
 #pragma unroll
     for (int k = 0; k < NR; k++) {
@@ -1357,7 +1387,19 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
             m1 = fminf(m1, d);
         }
     };
-    if constexpr (NR <= 4) {
+    if constexpr (TAIL) {
+        const float dx = PT.x - qxf, dy = PT.y - qyf, dz = PT.z - qzf;
+        float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+        d = tail_on ? d : __builtin_huge_valf();
+        const bool lt = d < m1;
+        m2 = __builtin_amdgcn_fmed3f(m1, m2, d);
+        p1 = lt ? tp : p1;
+        m1 = fminf(m1, d);
+        if (tail_loops) {                                         // rare: runs under the EXEC mask of the groups with T > 8 only
+#pragma unroll
+            for (int k = 0; k < NR; k++) long_row(rs[k], re[k]);
+        }
+    } else if constexpr (NR <= 4) {
 #pragma unroll
         for (int k = 0; k < NR; k++) long_row(rs[k], re[k]);
     } else {
@@ -1556,8 +1598,16 @@ __device__ __forceinline__ bool coop_stage0(const GridDesc &G, const float4 *__r
 #pragma unroll
         for (int k = 0; k < 4; k++) { rs[k] = (uint32_t)__shfl((int)my_s, k, kCoop); re[k] = (uint32_t)__shfl((int)my_e, k, kCoop); }
     }
-    coop_screen_rows<4, 2>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
-    return block_leaves_undecided(G, cx, cy, cz, xa, xb, ya, yb, za, zb, fx, fy, fz, qx, qy, qz, bd);
+    // The block's six cell bounds (< 1024 each: the grid has at most 1024 cells per axis) cross the screening packed into two registers,
+    // opaque to the compiler so that it cannot keep the six: with the shared tail slot's three record registers and its position the
+    // kernel would otherwise pass 72 VGPRs, and the scheduler then issues the nine record loads in groups of two -- four dependent
+    // round trips (72 is the ceiling of the kernel's 7 waves per SIMD, see nn_grid_coop_kernel).
+    uint32_t pk0 = (uint32_t)xa | ((uint32_t)xb << 10) | ((uint32_t)ya << 20), pk1 = (uint32_t)yb | ((uint32_t)za << 10) | ((uint32_t)zb << 20);
+    asm volatile("" : "+v"(pk0), "+v"(pk1));
+    coop_screen_rows<4, 2, true>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
+    asm volatile("" : "+v"(pk0), "+v"(pk1));
+    return block_leaves_undecided(G, cx, cy, cz, (int)(pk0 & 1023u), (int)((pk0 >> 10) & 1023u), (int)(pk0 >> 20), (int)(pk1 & 1023u),
+                                  (int)((pk1 >> 10) & 1023u), (int)(pk1 >> 20), fx, fy, fz, qx, qy, qz, bd);
 }
 
 // the 3x3x3 cube around the cell of a WAVE-UNIFORM query, searched by all 64 lanes; every lane returns the same exact (bd, bi)
@@ -1699,6 +1749,8 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
 // eight record loads of stage 0 two at a time (four dependent round trips); capped at 7 it takes 72 VGPRs and issues all eight before the
 // first use.  Headline step 0.1198-0.1210 -> 0.1163-0.1179 ms (6 waves: 0.122, 5: 0.134; profiles/r03_ab_occupancy_cap.txt).  Raising
 // only the minimum (round 2's "7 waves" experiment) never changed the code: the scheduler still aimed for 8.
+// With the shared tail slot (coop_screen_rows<4, 2, true>) nine loads are in flight at 70 VGPRs; whatever is added to stage 0 has to be
+// checked against that ceiling in the compiler's resource remarks AND in the order of the loads in the ISA.
 template <bool COUNT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
                                                            const uint32_t *__restrict__ cell_start,
