@@ -152,7 +152,7 @@ struct SeqWord {
     }
 };
 
-// Scratch of one order-preserving compaction of a frame (ring_dedup.hpp dd_rank / dd_tile_scan and a compacting kernel): keep flags,
+// Scratch of one order-preserving compaction of a frame (ring_dedup.hpp dd_rank, the tile scan with DdPublish, and a compacting kernel): keep flags,
 // ranks, tile totals and the packed xyz rows the insert kernel then reads.  ensure() allocates for exactly `cap` points; the caller
 // has chosen cap and synchronised.  A failure part-way leaves ncap 0.
 struct CompactScratch {
@@ -548,7 +548,7 @@ int sort_into_cells(pct_cloud *c, const GridDesc &G)
     if (e == hipSuccess) {
         cell_histogram_kernel<<<pblocks, 256, 0, s>>>(G, c->x, c->y, c->z, (uint32_t)n, d_cnt, d_pcell);
         scan_tiles_kernel<<<ntiles, 256, 0, s>>>(d_cnt, (uint32_t)ncells, c->cell_start, d_tiles);
-        scan_tile_sums_kernel<<<1, 256, 0, s>>>(d_tiles, ntiles);
+        scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(d_tiles, ntiles, ScanDoneNothing{});
         scan_add_kernel<<<ceil_div((int64_t)ncells, 256), 256, 0, s>>>(c->cell_start, (uint32_t)ncells, d_tiles, (uint32_t)n);
         e = hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * ncells, s);
     }
@@ -1234,7 +1234,7 @@ int rs_count_scan(pct_cloud *c, Path path, const float *d_q, const float *d_r, i
     const int ntiles = ceil_div(Q, kRsScanTile);
     HIPCHK(hipMemsetAsync(c->rs_queue, 0, sizeof(uint32_t), s));
     rs_scan_tiles_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles);
-    rs_scan_top_kernel<<<1, 256, 0, s>>>(c->rs_tiles, (uint32_t)ntiles);
+    scan_tile_sums_kernel<uint64_t><<<1, 256, 0, s>>>(c->rs_tiles, (uint32_t)ntiles, ScanDoneNothing{});
     rs_scan_final_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles, d_offsets, path == Path::Grid ? (uint32_t)kRsShort : 1u,
                                                 c->rs_queue);
     HIPCHK(hipGetLastError());
@@ -2131,7 +2131,7 @@ static int crop_device(pct_cloud *c, const double q[3], double rr, int64_t *tota
     begin_timing(c, g_stream);
     HIPCHK(hipMemsetAsync(c->crop_tile + ntiles, 0, sizeof(uint32_t), g_stream));
     crop_count_kernel<<<(int)ntiles, 256, 0, g_stream>>>(c->x, c->y, c->z, n, q[0], q[1], q[2], rr, c->crop_tile);
-    scan_tile_sums_kernel<<<1, 256, 0, g_stream>>>(c->crop_tile, ntiles + 1);       // entry ntiles becomes the grand total
+    scan_tile_sums_kernel<uint32_t><<<1, 256, 0, g_stream>>>(c->crop_tile, ntiles + 1, ScanDoneNothing{});       // entry ntiles becomes the grand total
     crop_scatter_kernel<<<(int)ntiles, 256, 0, g_stream>>>(c->x, c->y, c->z, n, q[0], q[1], q[2], rr, (uint32_t)c->index_base, c->crop_tile,
                                                           (uint32_t)c->crop_cap, c->crop_idx, c->crop_d2, c->crop_x, c->crop_y, c->crop_z);
     end_timing(c, g_stream);

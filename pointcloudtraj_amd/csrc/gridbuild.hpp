@@ -160,32 +160,13 @@ __global__ __launch_bounds__(kGbThreads) void gb_hist_kernel(GridDesc G, GbDesc 
     }
 }
 
-// exclusive scan of a[0..n) in LDS by the whole block, n <= blockDim.x * 16 handled in rounds with a carry; a[n] = total
+// exclusive scan of a[0..n) in LDS by the whole block (block_scan_array of scan.hpp: rounds of THREADS with a carry); a[n] = total
 template <int THREADS>
-__device__ __forceinline__ void gb_block_scan(uint32_t *a, uint32_t n, uint32_t *s_wave, uint32_t *s_carry)
+__device__ __forceinline__ void gb_block_scan(uint32_t *a, uint32_t n)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) *s_carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += THREADS) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n ? a[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)inc, off, kWave);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = *s_carry;
-        for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-        if (i < n) a[i] = wave_off + inc - v;
-        __syncthreads();
-        if (threadIdx.x == THREADS - 1) *s_carry = wave_off + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a[n] = *s_carry;
+    uint32_t total;
+    block_scan_array<uint32_t, THREADS>(a, n, total);
+    if (threadIdx.x == 0) a[n] = total;
     __syncthreads();
 }
 
@@ -197,10 +178,9 @@ __global__ __launch_bounds__(kGbThreads) void gb_scatter_kernel(GridDesc G, GbDe
                                                                 uint32_t *__restrict__ slab_start, float4 *__restrict__ tmp)
 {
     extern __shared__ uint32_t base[];                               // nslabs + 1 entries
-    __shared__ uint32_t s_wave[kGbThreads / 64], s_carry;
     for (uint32_t i = threadIdx.x; i < D.nslabs; i += kGbThreads) base[i] = slab_total[i];
     __syncthreads();
-    gb_block_scan<kGbThreads>(base, D.nslabs, s_wave, &s_carry);
+    gb_block_scan<kGbThreads>(base, D.nslabs);
     if (blockIdx.x == 0)
         for (uint32_t i = threadIdx.x; i <= D.nslabs; i += kGbThreads) slab_start[i] = base[i];
     const uint32_t *row = table + (size_t)blockIdx.x * D.nslabs;
@@ -268,7 +248,6 @@ __global__ __launch_bounds__(kGbThreads) void gb_scatter2_kernel(GridDesc G, Gb2
                                                                  uint32_t *__restrict__ slab_start, uint32_t n, float4 *__restrict__ tmp)
 {
     __shared__ uint32_t base[128 + 1];
-    __shared__ uint32_t s_wave[kGbThreads / 64], s_carry;
     const uint32_t S = blockIdx.y, nsub = 1u << D.sb;
     const uint32_t r0 = super_start[S], r1 = super_start[S + 1];
     if (threadIdx.x < nsub) {
@@ -276,7 +255,7 @@ __global__ __launch_bounds__(kGbThreads) void gb_scatter2_kernel(GridDesc G, Gb2
         base[threadIdx.x] = slab < D.nslabs ? slab_total[slab] : 0u;
     }
     __syncthreads();
-    gb_block_scan<kGbThreads>(base, nsub, s_wave, &s_carry);         // exclusive scan of this super-slab's slab sizes
+    gb_block_scan<kGbThreads>(base, nsub);         // exclusive scan of this super-slab's slab sizes
     if (blockIdx.x == 0) {                                           // publish the slabs' global starts for level 2
         if (threadIdx.x < nsub) {
             const uint32_t slab = (S << D.sb) + threadIdx.x;
@@ -313,7 +292,6 @@ __global__ __launch_bounds__(kGbCellThreads) void gb_cells_kernel(GridDesc G, Gb
     unsigned long long k_sum = 0;                                    // self-check (GbCheck), accumulated from the records in hand
     uint32_t k_xor = 0, k_bad = 0, k_empty = 0;
     extern __shared__ uint32_t cnt[];
-    __shared__ uint32_t s_wave[kGbCellThreads / 64], s_carry;
     float4 *stage = reinterpret_cast<float4 *>(cnt + ((((1u << D.s1) + 1) + 3) & ~3u));
     const uint32_t b = blockIdx.x;
     const uint32_t c0 = b << D.s1, c1 = min(G.ncells, c0 + (1u << D.s1)), m = c1 - c0;
@@ -336,7 +314,7 @@ __global__ __launch_bounds__(kGbCellThreads) void gb_cells_kernel(GridDesc G, Gb
             }
         }
         __syncthreads();
-        gb_block_scan<kGbCellThreads>(cnt, m, s_wave, &s_carry);
+        gb_block_scan<kGbCellThreads>(cnt, m);
         for (uint32_t i = threadIdx.x; i < m; i += kGbCellThreads) {
             cell_start[c0 + i] = p0 + cnt[i];
             k_empty += cnt[i + 1] == cnt[i] ? 1u : 0u;
@@ -362,7 +340,7 @@ __global__ __launch_bounds__(kGbCellThreads) void gb_cells_kernel(GridDesc G, Gb
         atomicAdd(&cnt[cl], 1u);
     }
     __syncthreads();
-    gb_block_scan<kGbCellThreads>(cnt, m, s_wave, &s_carry);
+    gb_block_scan<kGbCellThreads>(cnt, m);
     for (uint32_t i = threadIdx.x; i < m; i += kGbCellThreads) {
         cell_start[c0 + i] = p0 + cnt[i];
         k_empty += cnt[i + 1] == cnt[i] ? 1u : 0u;

@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 
 #include "bernstein.hpp"
+#include "scan.hpp"
 
 namespace pct {
 
@@ -701,28 +702,9 @@ __global__ __launch_bounds__(256) void count_stream_kernel(const float *__restri
 // version appended hits through one global cursor: it serialised on that address (~12 ns per hit, 20 K hits = 0.25 ms) and
 // returned arrival order; this pair keeps insertion order and has no contended atomic:
 //   crop_count_kernel    hits per 1024-point tile                                    (12 B/point read)
-//   (scan_tile_sums_kernel, one block: exclusive scan of the tile counts)
+//   (scan_tile_sums_kernel of scan.hpp, one block: exclusive scan of the tile counts)
 //   crop_scatter_kernel  recompute the test, rank inside the tile, write {index, d2, x, y, z}  (12 B/point + 32 B/hit)
 constexpr int kCropTile = 1024;
-
-__device__ __forceinline__ uint32_t crop_tile_rank(const uint32_t f[4], uint32_t &tile_total)
-{
-    __shared__ uint32_t s_wave[4];
-    const uint32_t tsum = f[0] + f[1] + f[2] + f[3];
-    uint32_t inc = tsum;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0;
-    for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-    tile_total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    return wave_off + inc - tsum;          // exclusive rank of this thread's first element inside the tile
-}
 
 __global__ __launch_bounds__(256) void crop_count_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                          const float *__restrict__ z, uint32_t n, double qx, double qy, double qz,
@@ -736,7 +718,7 @@ __global__ __launch_bounds__(256) void crop_count_kernel(const float *__restrict
         f[k] = (i < n && dist2((double)x[i], (double)y[i], (double)z[i], qx, qy, qz) <= r2) ? 1u : 0u;
     }
     uint32_t total;
-    (void)crop_tile_rank(f, total);
+    (void)tile_rank4(f, total);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
@@ -761,7 +743,7 @@ __global__ __launch_bounds__(256) void crop_scatter_kernel(const float *__restri
         }
     }
     uint32_t total;
-    uint32_t pos = tile_off[blockIdx.x] + crop_tile_rank(f, total);
+    uint32_t pos = tile_off[blockIdx.x] + tile_rank4(f, total);      // exclusive rank of this thread's first element
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (f[k]) {
@@ -927,65 +909,24 @@ __global__ __launch_bounds__(256) void cell_histogram_kernel(GridDesc G, const f
 }
 
 // exclusive scan, three launches: per-block scan of 1024-element tiles, scan of the tile sums
-// (single block), then add.  cell_start has ncells+1 entries; entry ncells = n.
+// (single block: scan_tile_sums_kernel of scan.hpp), then add.  cell_start has ncells+1 entries; entry ncells = n.
 constexpr int kScanTile = 1024;
 
 __global__ __launch_bounds__(256) void scan_tiles_kernel(const uint32_t *__restrict__ in, uint32_t n,
                                                          uint32_t *__restrict__ out, uint32_t *__restrict__ tile_sum)
 {
-    __shared__ uint32_t s_wave[4];
     const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * 4;
     uint32_t v[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) v[k] = (base + k < n) ? in[base + k] : 0u;
-    const uint32_t tsum = v[0] + v[1] + v[2] + v[3];
-    // inclusive wave scan of per-thread sums
-    uint32_t inc = tsum;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0;
-    for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-    uint32_t run = wave_off + inc - tsum;   // exclusive prefix of this thread within the tile
+    uint32_t total;
+    uint32_t run = tile_rank4(v, total);    // exclusive prefix of this thread within the tile
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (base + k < n) out[base + k] = run;
         run += v[k];
     }
-    if (threadIdx.x == 255) tile_sum[blockIdx.x] = wave_off + inc;
-}
-
-// single block: exclusive scan of tile sums in place (ntiles arbitrary; serial over chunks of 256)
-__global__ __launch_bounds__(256) void scan_tile_sums_kernel(uint32_t *__restrict__ tile_sum, uint32_t ntiles)
-{
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint32_t base = 0; base < ntiles; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = (i < ntiles) ? tile_sum[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)inc, off, kWave);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = s_carry;
-        for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-        if (i < ntiles) tile_sum[i] = wave_off + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 255) s_carry = wave_off + inc;
-        __syncthreads();
-    }
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void scan_add_kernel(uint32_t *__restrict__ out, uint32_t n,
@@ -1133,20 +1074,9 @@ __global__ __launch_bounds__(1024) void qsort_scatter1_kernel(GridDesc G, BinDes
     static_assert(kSortBuckets == 1024, "one thread per bucket");
     __shared__ uint32_t h[kSortBuckets];
     __shared__ uint32_t basepos[kSortBuckets];
-    __shared__ uint32_t s_wave[16];
-    h[threadIdx.x] = 0;
-    const uint32_t tot = total1[threadIdx.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t start = inc - tot;
-    for (int w = 0; w < wave; w++) start += s_wave[w];
+    h[threadIdx.x] = 0;                               // (published by the scan's barrier)
+    uint32_t all;
+    const uint32_t start = block_exclusive<uint32_t, 1024>(total1[threadIdx.x], all);
     const uint32_t base = blockIdx.x * per_block;
     const int items = (int)(per_block >> 10);
     // all of a thread's queries are requested up front (one round trip instead of one per item)
@@ -1810,6 +1740,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
     }
 }
 
+// The cells [x0, x1] x [y0, y1] x [z0, z1] that can hold a point within r of the query: the box every kernel that walks a ball's rows
+// uses (the radius count, and the radius search's fill, which must meet exactly the rows the count reserved space for).
+// r enters only squared (kdtree.c:273).  The box edges q -/+ pad are fp32 sums: each is off by up to 2^-24 (|q| + pad), and the
+// fp64 test itself admits points up to r (1 + 2^-50) away, so the pad carries 2^-22 (|q| + |r|) per axis on top of h/100 --
+// nothing at ordinary magnitudes, everything for a query 1e18 away whose ball reaches back to the cloud.  An edge that comes
+// out NaN (inf - inf: infinite query or radius) opens the box to that side (cell_coord sends NaN to cell 0: right for the
+// lower edge only).  The box is filled through a reference: returned by value, the compiler computes the lower edges behind the
+// upper edges' branches, which reschedules count_grid_coop_kernel's prologue.
+struct BallBox { int x0, x1, y0, y1, z0, z1; };
+
+__device__ __forceinline__ void grid_ball_box(const GridDesc &G, float qxf, float qyf, float qzf, float rf, BallBox &B)
+{
+    const float pad0 = fabsf(rf) + 0.01f * (1.0f / G.inv_h);
+    const float padx = pad0 + 0x1p-22f * (fabsf(qxf) + fabsf(rf)), pady = pad0 + 0x1p-22f * (fabsf(qyf) + fabsf(rf)),
+                padz = pad0 + 0x1p-22f * (fabsf(qzf) + fabsf(rf));
+    const float hx = qxf + padx, hy = qyf + pady, hz = qzf + padz;
+    B.x0 = cell_coord(qxf - padx, G.ox, G.inv_h, G.gx); B.x1 = hx == hx ? cell_coord(hx, G.ox, G.inv_h, G.gx) : G.gx - 1;
+    B.y0 = cell_coord(qyf - pady, G.oy, G.inv_h, G.gy); B.y1 = hy == hy ? cell_coord(hy, G.oy, G.inv_h, G.gy) : G.gy - 1;
+    B.z0 = cell_coord(qzf - padz, G.oz, G.inv_h, G.gz); B.z1 = hz == hz ? cell_coord(hz, G.oz, G.inv_h, G.gz) : G.gz - 1;
+}
+
 // Cooperative radius count: 8 lanes per query, the rows of the ball's bounding box: the run bounds of up to 16 rows fetched at once
 // (two per lane), then the rows two at a time, every lane with four 16-byte loads per row in flight (32 points per row for the group)
 // before the first compare; longer rows finish in a tail loop.  Every distance is the exact fp64 one (kdtree.c:273,
@@ -1829,7 +1780,7 @@ __global__ __launch_bounds__(256) void count_grid_coop_kernel(GridDesc G, const 
     if (slot < Q) {                                   // uniform within a group of 8 lanes
         uint32_t t = slot;
         float qxf, qyf, qzf;
-        if (qsorted) {
+        if (qsorted) {                                // binned batch: query and output slot in one record
             const float4 R = qsorted[slot];
             qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
         } else {
@@ -1838,19 +1789,10 @@ __global__ __launch_bounds__(256) void count_grid_coop_kernel(GridDesc G, const 
         const float rf = rad[t];
         const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
         const double r2 = (double)rf * (double)rf;
-        // r enters only squared (kdtree.c:273).  The box edges q -/+ pad are fp32 sums: each is off by up to 2^-24 (|q| + pad), and the
-        // fp64 test itself admits points up to r (1 + 2^-50) away, so the pad carries 2^-22 (|q| + |r|) per axis on top of h/100 --
-        // nothing at ordinary magnitudes, everything for a query 1e18 away whose ball reaches back to the cloud.  An edge that comes
-        // out NaN (inf - inf: infinite query or radius) opens the box to that side (cell_coord sends NaN to cell 0: right for the
-        // lower edge only).
-        const float pad0 = fabsf(rf) + 0.01f * (1.0f / G.inv_h);
-        const float padx = pad0 + 0x1p-22f * (fabsf(qxf) + fabsf(rf)), pady = pad0 + 0x1p-22f * (fabsf(qyf) + fabsf(rf)),
-                    padz = pad0 + 0x1p-22f * (fabsf(qzf) + fabsf(rf));
-        const float hx = qxf + padx, hy = qyf + pady, hz = qzf + padz;
-        const int x0 = cell_coord(qxf - padx, G.ox, G.inv_h, G.gx), x1 = hx == hx ? cell_coord(hx, G.ox, G.inv_h, G.gx) : G.gx - 1;
-        const int y0 = cell_coord(qyf - pady, G.oy, G.inv_h, G.gy), y1 = hy == hy ? cell_coord(hy, G.oy, G.inv_h, G.gy) : G.gy - 1;
-        const int z0 = cell_coord(qzf - padz, G.oz, G.inv_h, G.gz), z1 = hz == hz ? cell_coord(hz, G.oz, G.inv_h, G.gz) : G.gz - 1;
-        const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
+        BallBox B;
+        grid_ball_box(G, qxf, qyf, qzf, rf, B);
+        const int x0 = B.x0, x1 = B.x1, y0 = B.y0, z0 = B.z0;
+        const int ny = B.y1 - y0 + 1, nrows = ny * (B.z1 - z0 + 1);
         uint32_t c = 0;
         // Rows of the box: the run bounds of up to 16 rows in ONE trip (two per lane), then the rows two at a time with 32 points of each
         // in flight (a row of 3-4 cells holds ~20): a query's 9-16 rows cost 1 + rows/2 dependent round trips.  (The first form took the

@@ -18,9 +18,9 @@
 //                              the cell is never smaller than res / 2), head to tail, dead and doomed records skipped, key equality
 //                              on the STORED coordinates; then the overflow queue, staged through LDS 256 entries at a time, by the
 //                              blocks that still have an undecided point.  Writes the kept flags.
-//   3. dd_rank_kernel          rank of the kept points inside 1024-point tiles, tile totals      (as voxel.hip)
-//   4. dd_tile_scan_kernel     one block: exclusive scan of the tile totals; the grand total goes to the host-mapped word the
-//                              host polls -- it needs n' before it can queue the eviction and insert launches
+//   3. dd_rank_kernel          rank of the kept points inside 1024-point tiles (tile_rank4 of scan.hpp), tile totals
+//   4. scan_tile_sums_kernel   one block (scan.hpp): exclusive scan of the tile totals; DdPublish sends the grand total to the
+//                              host-mapped word the host polls -- it needs n' before it can queue the eviction and insert launches
 //   5. dd_compact_kernel       kept points, in frame order, into the packed device staging buffer the insert kernel reads
 // Atomics: one CAS per key that is new to the table, one atomicMin per point that may lower the stored position (a plain read
 // first: later copies of a key find a lower position already there and issue none).  Nothing else meets across blocks inside a
@@ -137,66 +137,32 @@ __global__ __launch_bounds__(256) void dd_probe_kernel(RingView V, DdWindow W, d
 __global__ __launch_bounds__(256) void dd_rank_kernel(const uint8_t *__restrict__ flags, uint32_t n, uint32_t *__restrict__ rank,
                                                       uint32_t *__restrict__ tile_sum)
 {
-    __shared__ uint32_t s_wave[4];
     const uint32_t first = blockIdx.x * kDdTile + threadIdx.x * 4;
     uint32_t f[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) f[k] = (first + k < n && flags[first + k]) ? 1u : 0u;
-    const uint32_t tsum = f[0] + f[1] + f[2] + f[3];
-    uint32_t inc = tsum;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0;
-    for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-    uint32_t run = wave_off + inc - tsum;
+    uint32_t total;
+    uint32_t run = tile_rank4(f, total);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (first + k < n) rank[first + k] = run;
         run += f[k];
     }
-    if (threadIdx.x == 255) tile_sum[blockIdx.x] = wave_off + inc;
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
-// one block: exclusive scan of the tile totals in place; the grand total and then the sequence word go to host-mapped memory
-// (host_word[1] = n', host_word[0] = seq, released at system scope: the host spins on it)
-__global__ __launch_bounds__(256) void dd_tile_scan_kernel(uint32_t *__restrict__ tile_sum, uint32_t ntiles, uint32_t *__restrict__ host_word,
-                                                           uint32_t seq)
-{
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint32_t b = 0; b < ntiles; b += 256) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t v = (i < ntiles) ? tile_sum[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)inc, off, 64);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = s_carry;
-        for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-        if (i < ntiles) tile_sum[i] = wave_off + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 255) s_carry = wave_off + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(&host_word[1], s_carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+// what thread 0 of scan_tile_sums_kernel (scan.hpp) does with the grand total of the tile scan: the total and then the sequence word
+// go to host-mapped memory (host_word[1] = n', host_word[0] = seq, released at system scope: the host spins on it)
+struct DdPublish {
+    uint32_t *host_word;
+    uint32_t seq;
+    __device__ void operator()(uint32_t total) const
+    {
+        __hip_atomic_store(&host_word[1], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __threadfence_system();
         __hip_atomic_store(&host_word[0], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-}
+};
 
 __global__ __launch_bounds__(256) void dd_compact_kernel(const unsigned char *__restrict__ src, uint32_t n, uint32_t stride,
                                                          const uint8_t *__restrict__ flags, const uint32_t *__restrict__ rank,

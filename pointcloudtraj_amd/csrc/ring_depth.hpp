@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void depth_valid_kernel(pct_depth_view V, cons
 }
 
 // a = ((double)x/width - 0.5)/focal, b = ((double)y - 0.5*height)/width/focal, p_k = t[k] + dep*((a*R[k][0] + b*R[k][1]) + R[k][2]),
-// narrowed to fp32 (round to nearest); valid pixels land in row-major order at tile_off[tile] + rank (dd_rank_kernel / dd_tile_scan_kernel)
+// narrowed to fp32 (round to nearest); valid pixels land in row-major order at tile_off[tile] + rank (dd_rank_kernel / scan_tile_sums_kernel with DdPublish)
 __global__ __launch_bounds__(256) void depth_unproject_kernel(pct_depth_view V, const float *__restrict__ image, uint32_t npix,
                                                               const uint8_t *__restrict__ flags, const uint32_t *__restrict__ rank,
                                                               const uint32_t *__restrict__ tile_off, float *__restrict__ out)

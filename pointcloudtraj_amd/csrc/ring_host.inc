@@ -272,7 +272,7 @@ int ring_append(pct_cloud *c, const void *pts, int64_t n, int64_t stride, const 
 // ---- de-duplicating appends (ring_dedup.hpp) ---------------------------------------------------------------------------------
 int after_replace(pct_cloud *c);
 
-// the host wait behind dd_tile_scan_kernel: the grand total of the scan launched with `seq`, from the host-mapped {sequence, total}
+// the host wait behind the tile scan's DdPublish (ring_dedup.hpp): the grand total of the scan launched with `seq`, from the host-mapped {sequence, total}
 // pair it publishes
 int dd_scan_wait(pct_cloud *c, uint32_t seq, int64_t *total)
 {
@@ -327,7 +327,7 @@ int dedup_filter(pct_cloud *c, const unsigned char *d_src, int64_t n, int64_t st
     else
         dd_probe_kernel<false><<<ceil_div(n, kDdPointsPerBlock), 256, 0, s>>>(RingView{}, W, c->dd_res, un, c->dd_keys, c->dd_vals, c->dd_pslot, c->dd.flags);
     dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dd.flags, un, c->dd.rank, c->dd.tile);
-    dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dd.tile, (uint32_t)ntiles, c->dd_word.w, seq);
+    scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->dd.tile, (uint32_t)ntiles, DdPublish{ c->dd_word.w, seq });
     dd_compact_kernel<<<ceil_div(n, 256), 256, 0, s>>>(d_src, un, (uint32_t)stride, c->dd.flags, c->dd.rank, c->dd.tile, c->dd.out);
     HIPCHK(hipGetLastError());
     PCTCHK(dd_scan_wait(c, seq, kept));
@@ -1161,7 +1161,7 @@ int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *i
     const int ntiles = ceil_div(npix, kDdTile);
     depth_valid_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, max_depth, c->dp.flags);
     dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dp.flags, un, c->dp.rank, c->dp.tile);
-    dd_tile_scan_kernel<<<1, 256, 0, s>>>(c->dp.tile, (uint32_t)ntiles, c->dd_word.w, seq);
+    scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->dp.tile, (uint32_t)ntiles, DdPublish{ c->dd_word.w, seq });
     depth_unproject_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, c->dp.flags, c->dp.rank, c->dp.tile, c->dp.out);
     HIPCHK(hipGetLastError());
     int64_t n = 0;

@@ -2,8 +2,9 @@
 //
 // A batch is answered in three steps, all on the caller's stream:
 //   1. count   the existing radius-count batch (count_grid_coop_kernel or the streaming count), unchanged: row lengths
-//   2. scan    rs_scan_*: uint32 counts -> int64 exclusive offsets of a CSR, total in entry Q; two levels (2048 counts per block, the
-//              tile sums scanned by one block that loops), so Q is not limited.  The last pass also queues the rows step 3b sorts.
+//   2. scan    rs_scan_tiles_kernel, scan_tile_sums_kernel<uint64_t> (scan.hpp), rs_scan_final_kernel: uint32 counts -> int64 exclusive
+//              offsets of a CSR, total in entry Q; two levels (2048 counts per block, the tile sums scanned by one block that loops),
+//              so Q is not limited.  The last pass also queues the rows step 3b sorts.
 //   3a. fill   rs_fill_grid_kernel (8 lanes per query over the box of rows the count walked) or rs_fill_stream_kernel (lanes own
 //              points, a tile of 8 queries is wave-uniform); the ball test is the count's: fp64 dist2() <= (double)r * (double)r.
 //              On a rolling map: ring_count_kernel / ring_fill_kernel over the bucket table (ring_search.hpp), rows queued as for the
@@ -36,26 +37,6 @@ __device__ __forceinline__ bool rs_before(double da, uint32_t ia, double db, uin
     return BY_DIST ? better(da, ia, db, ib) : ia < ib;
 }
 
-// exclusive prefix of v over the block's 256 threads, and the block's total
-__device__ __forceinline__ uint64_t rs_block_exclusive(uint64_t v, uint64_t &total)
-{
-    __shared__ uint64_t s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t o = (uint64_t)__shfl_up((long long)inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint64_t wave_off = 0;
-    for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();                    // the next call of a looping caller writes s_wave again
-    return wave_off + inc - v;
-}
-
 __global__ __launch_bounds__(256) void rs_scan_tiles_kernel(const uint32_t *__restrict__ count, uint32_t Q, uint64_t *__restrict__ tile_sum)
 {
     const uint64_t first = (uint64_t)blockIdx.x * kRsScanTile + threadIdx.x * 8u;
@@ -63,23 +44,11 @@ __global__ __launch_bounds__(256) void rs_scan_tiles_kernel(const uint32_t *__re
 #pragma unroll
     for (int k = 0; k < 8; k++) s += first + k < Q ? count[first + k] : 0u;
     uint64_t total;
-    (void)rs_block_exclusive(s, total);
+    (void)block_exclusive<uint64_t, 256>(s, total);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
-// one block: tile sums -> exclusive tile offsets, 256 at a time with a running carry
-__global__ __launch_bounds__(256) void rs_scan_top_kernel(uint64_t *__restrict__ tile_sum, uint32_t ntiles)
-{
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < ntiles; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const uint64_t v = i < ntiles ? tile_sum[i] : 0u;
-        uint64_t total;
-        const uint64_t ex = rs_block_exclusive(v, total);
-        if (i < ntiles) tile_sum[i] = carry + ex;
-        carry += total;
-    }
-}
+// (the tile sums become exclusive tile offsets in scan_tile_sums_kernel<uint64_t> of scan.hpp: one block, any number of tiles)
 
 // offsets[i] = sum of count[0 .. i), offsets[Q] = the total; rows longer than sort_min are appended to queue = {n, rows...}
 __global__ __launch_bounds__(256) void rs_scan_final_kernel(const uint32_t *__restrict__ count, uint32_t Q, const uint64_t *__restrict__ tile_off,
@@ -91,7 +60,7 @@ __global__ __launch_bounds__(256) void rs_scan_final_kernel(const uint32_t *__re
 #pragma unroll
     for (int k = 0; k < 8; k++) { c[k] = first + k < Q ? count[first + k] : 0u; s += c[k]; }
     uint64_t total;
-    uint64_t run = tile_off[blockIdx.x] + rs_block_exclusive(s, total);
+    uint64_t run = tile_off[blockIdx.x] + block_exclusive<uint64_t, 256>(s, total);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const uint64_t i = first + k;
@@ -105,8 +74,8 @@ __global__ __launch_bounds__(256) void rs_scan_final_kernel(const uint32_t *__re
 }
 
 // -------------------------------------------------------------------------------------
-// Cell-pruned fill: EIGHT lanes per query over the rows of the ball's bounding box -- the box, the padding and the order of the
-// batch (qsorted: the counting-sorted records, rows going back to their own query) are count_grid_coop_kernel's, and so is the test,
+// Cell-pruned fill: EIGHT lanes per query over the rows of the ball's bounding box -- the box (grid_ball_box, kernels.hpp) and the order
+// of the batch (qsorted: the counting-sorted records, rows going back to their own query) are count_grid_coop_kernel's, and so is the test,
 // so a row receives exactly offsets[t + 1] - offsets[t] hits.  A row without hits is not walked at all.  The run bounds of 8 rows
 // are fetched in one trip (one per lane); the points of a run are taken 8 at a time and the hits of a step placed at
 // cursor + (hits in lower lanes), the cursor advancing by the step's hit count in every lane.
@@ -142,15 +111,10 @@ __global__ __launch_bounds__(256) void rs_fill_grid_kernel(GridDesc G, const flo
     const float rf = rad[t];
     const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
     const double r2 = (double)rf * (double)rf;
-    // the box of count_grid_coop_kernel (kernels.hpp), edge for edge
-    const float pad0 = fabsf(rf) + 0.01f * (1.0f / G.inv_h);
-    const float padx = pad0 + 0x1p-22f * (fabsf(qxf) + fabsf(rf)), pady = pad0 + 0x1p-22f * (fabsf(qyf) + fabsf(rf)),
-                padz = pad0 + 0x1p-22f * (fabsf(qzf) + fabsf(rf));
-    const float hx = qxf + padx, hy = qyf + pady, hz = qzf + padz;
-    const int x0 = cell_coord(qxf - padx, G.ox, G.inv_h, G.gx), x1 = hx == hx ? cell_coord(hx, G.ox, G.inv_h, G.gx) : G.gx - 1;
-    const int y0 = cell_coord(qyf - pady, G.oy, G.inv_h, G.gy), y1 = hy == hy ? cell_coord(hy, G.oy, G.inv_h, G.gy) : G.gy - 1;
-    const int z0 = cell_coord(qzf - padz, G.oz, G.inv_h, G.gz), z1 = hz == hz ? cell_coord(hz, G.oz, G.inv_h, G.gz) : G.gz - 1;
-    const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
+    BallBox B;
+    grid_ball_box(G, qxf, qyf, qzf, rf, B);
+    const int x0 = B.x0, x1 = B.x1, y0 = B.y0, z0 = B.z0;
+    const int ny = B.y1 - y0 + 1, nrows = ny * (B.z1 - z0 + 1);
     uint32_t cur = 0;
     for (int base = 0; base < nrows; base += kCoop) {
         const int k = base + (int)sub;

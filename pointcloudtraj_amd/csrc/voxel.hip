@@ -9,8 +9,8 @@
 //                           Voxels of earlier batches hold their final id (< base), so they are unaffected; a voxel new in
 //                           this batch ends up holding base + (lowest input index that maps to it).
 //   2. vox_rank_kernel      is_first[i] = (slot.val == base + i); exclusive rank of the flags inside each 1024-point
-//                           tile, tile totals.
-//   3. vox_tile_scan_kernel exclusive scan of the tile totals (one block), grand total = voxels added.
+//                           tile (tile_rank4 of scan.hpp), tile totals.
+//   3. scan_tile_sums_kernel exclusive scan of the tile totals (one block, scan.hpp), grand total = voxels added (VoxTotal).
 //   4. vox_commit_kernel    first occurrences write their voxel (id = base + tile offset + rank: input order) -- integer
 //                           coordinates, float centres -- and replace the slot's value by the id;
 //   5. vox_report_kernel    per-point outputs (is_new, voxel index), only when asked for.
@@ -29,6 +29,7 @@
 
 #include "../../include/pct_voxel.h"
 #include "engine_internal.hpp"
+#include "scan.hpp"
 #include "vox_key.hpp"
 
 using pct_internal::fail;
@@ -37,7 +38,6 @@ using namespace pct_vox;       // voxel keys and the key table (shared with the 
 namespace {
 
 constexpr int kTile = 1024;                       // points per rank tile (256 threads x 4)
-constexpr int kWave = 64;
 
 #define HIPCHK(call)                                                                                   \
     do {                                                                                               \
@@ -89,7 +89,6 @@ __global__ __launch_bounds__(256) void vox_rehash_kernel(const int *__restrict__
 __global__ __launch_bounds__(256) void vox_rank_kernel(const uint32_t *__restrict__ pslot, const uint32_t *__restrict__ vals, uint32_t n,
                                                        uint32_t base, uint32_t *__restrict__ rank, uint32_t *__restrict__ tile_sum)
 {
-    __shared__ uint32_t s_wave[4];
     const uint32_t first = blockIdx.x * kTile + threadIdx.x * 4;
     uint32_t f[4];
 #pragma unroll
@@ -98,56 +97,22 @@ __global__ __launch_bounds__(256) void vox_rank_kernel(const uint32_t *__restric
         const uint32_t slot = i < n ? pslot[i] : kNoSlot;
         f[k] = (slot != kNoSlot && vals[slot] == base + i) ? 1u : 0u;
     }
-    const uint32_t tsum = f[0] + f[1] + f[2] + f[3];
-    uint32_t inc = tsum;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0;
-    for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-    uint32_t run = wave_off + inc - tsum;
+    uint32_t total;
+    uint32_t run = pct::tile_rank4(f, total);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         // rank of a first occurrence inside its tile; bit 31 marks "is a first occurrence"
         if (first + k < n) rank[first + k] = run | (f[k] << 31);
         run += f[k];
     }
-    if (threadIdx.x == 255) tile_sum[blockIdx.x] = wave_off + inc;
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
-// one block: exclusive scan of the tile totals in place, grand total -> flags->total
-__global__ __launch_bounds__(256) void vox_tile_scan_kernel(uint32_t *__restrict__ tile_sum, uint32_t ntiles, VoxFlags *__restrict__ flags)
-{
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint32_t b = 0; b < ntiles; b += 256) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t v = (i < ntiles) ? tile_sum[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)inc, off, kWave);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wave_off = s_carry;
-        for (int w = 0; w < wave; w++) wave_off += s_wave[w];
-        if (i < ntiles) tile_sum[i] = wave_off + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 255) s_carry = wave_off + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) flags->total = s_carry;
-}
+// what thread 0 of scan_tile_sums_kernel (scan.hpp) does with the grand total of the tile scan: voxels added
+struct VoxTotal {
+    VoxFlags *flags;
+    __device__ void operator()(uint32_t total) const { flags->total = total; }
+};
 
 template <typename T>
 __global__ __launch_bounds__(256) void vox_commit_kernel(const unsigned char *__restrict__ pts, uint32_t n, uint32_t stride_bytes, double res,
@@ -288,7 +253,7 @@ int add_device(pct_voxel_map *m, const unsigned char *d_pts, int64_t n, int64_t 
     HIPCHK(hipEventRecord(m->ev0, s));
     vox_insert_kernel<T><<<nb, 256, 0, s>>>(d_pts, un, (uint32_t)stride, m->res, base, m->keys, m->vals, m->T - 1, m->pslot, m->d_flags);
     vox_rank_kernel<<<ntiles, 256, 0, s>>>(m->pslot, m->vals, un, base, m->rank, m->tile);
-    vox_tile_scan_kernel<<<1, 256, 0, s>>>(m->tile, (uint32_t)ntiles, m->d_flags);
+    pct::scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(m->tile, (uint32_t)ntiles, VoxTotal{ m->d_flags });
     vox_commit_kernel<T><<<nb, 256, 0, s>>>(d_pts, un, (uint32_t)stride, m->res, base, m->pslot, m->rank, m->tile, m->vals,
                                             m->vx, m->vy, m->vz, m->fx, m->fy, m->fz);
     if (d_is_new || d_index) vox_report_kernel<<<nb, 256, 0, s>>>(m->pslot, m->rank, m->vals, un, d_is_new, d_index);
