@@ -48,6 +48,12 @@ int pct_corridor_set_rolling_dedup(pct_corridor *c, double res);
 int pct_corridor_forget_outside(pct_corridor *c, const double centre[3], double r, int64_t *removed);
 int pct_corridor_clear_ball(pct_corridor *c, const double centre[3], double r, int64_t *removed);
 int pct_corridor_clear_box(pct_corridor *c, const double lo[3], const double hi[3], int64_t *removed);
+/* after pct_corridor_enable_rolling: give the slots of removed points back to the window (pct_engine.h, paragraph "Compacting the
+ * window").  compact_window compacts now, *reclaimed (may be NULL) = the slots reclaimed; set_rolling_compact(f), 0 < f <= 1, lets
+ * every removal above and clear_seen_through compact by itself once f of the capacity is dead (0 = off, the default).  Obstacle
+ * indices change; the finder keeps none across calls. */
+int pct_corridor_compact_window(pct_corridor *c, int64_t *reclaimed);
+int pct_corridor_set_rolling_compact(pct_corridor *c, double dead_fraction);
 /* after pct_corridor_enable_rolling: depth images as the map's input (pct_engine.h, paragraph "Depth images").  The rgbd tick is
  * clear_seen_through -> append_depth -> evaluate -> refine with the same image: the carve removes what the image sees through
  * (*removed, may be NULL), the append un-projects the valid pixels on the device and files them as append_input files a point

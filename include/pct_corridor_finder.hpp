@@ -227,6 +227,11 @@ public:
         const double a[3] = { lo.x, lo.y, lo.z }, b[3] = { hi.x, hi.y, hi.z };
         return map_.clearBox(a, b);
     }
+    // after enableRollingMap: give the slots of removed points back to the window (ObstacleMap::compactWindow / setRollingCompact).
+    // compactWindow returns the number of slots reclaimed; setRollingCompact(f) lets every removal above and clearSeenThrough compact
+    // by itself once f of the capacity is dead (0 = off).  Obstacle indices change; the finder keeps none across calls (it stores radii).
+    int64_t compactWindow() { return map_.compactWindow(); }
+    void setRollingCompact(double dead_fraction) { map_.setRollingCompact(dead_fraction); }
     // after enableRollingMap: depth images as the map's input (ObstacleMap::clearSeenThrough / appendDepthImage).  The rgbd tick is
     // clearSeenThrough -> appendDepthImage -> SafeRegionEvaluate -> SafeRegionRefine with the same image in both calls: the carve
     // withdraws what the image sees through (an obstacle that left), the append files what it hits; appendDepthImage does for its

@@ -131,7 +131,35 @@
  * frame; each waits once on the host for {removed, live after} (a host-mapped word, polled).  Captured plans stay valid across
  * removals, the reset included.  Records now die out of arrival order: dead records behind a live bucket head take bucket room
  * until the head passes them (a bucket that looks full spills newcomers to the overflow queue: correct, slower); nothing is
- * compacted.  A table sized automatically ignores removed rows when it is sized again.
+ * compacted by a removal itself (see the next paragraph).  A table sized automatically ignores removed rows when it is sized again.
+ *
+ * Compacting the window (pct_cloud_ring_compact, pct_cloud_ring_autocompact, pct_cloud_ring_compact_count): removed slots stay below
+ * pct_cloud_size and the cursor overwrites live and dead slots alike, so every removal lowers the effective capacity of a window that
+ * has filled; a compaction gives the room back.  Live: a row is live iff it is below size and has no NaN coordinate -- exactly what
+ * pct_cloud_ring_live counts; a caller's own NaN rows are dropped like removed ones, rows with +/-inf and no NaN are live and stay.
+ * Order: the L live rows move to slots 0 .. L-1 in arrival order, oldest first; arrival order is slot order starting at `start`,
+ * start = the ring cursor when size == capacity (the ring has wrapped) and 0 otherwise; the compaction is stable in that order.
+ * After the call size = L and the cursor stands at L mod capacity: the next append fills the free slots L .. without evicting
+ * anything, and once the window is full again the ring evicts in the same oldest-first order as before; the bucket table is filed
+ * again from the compacted rows, no dead record remains, the overflow queue holds only genuine spills, and the removed-rows mark of
+ * the window is cleared.  Equivalence: after the call the cloud is observably the rolling-map cloud that an append of those L rows,
+ * in that order, into an empty window of the same configuration (cell size, table shape, bucket records, de-dup mode and res, index
+ * base) would have produced.  Every search and check gives the same distances as before the call; indices are the new ones
+ * (index_base + new slot), ties go to the lowest NEW index.  *live = L and *reclaimed = old size - L; either may be NULL.  remap may
+ * be NULL; otherwise it is host memory with remap_cap >= old size, and for an old slot i remap[i] = index_base + new slot, or
+ * PCT_NO_INDEX for a row that was dropped.  PCT_ERR_INVALID, with nothing changed: a NULL cloud, a cloud without a rolling-map
+ * index, a remap shorter than the window.  L == old size: nothing moves, not even a wrapped ring's rotation; remap is the identity
+ * and *reclaimed = 0.  An empty cloud: PCT_OK, zeros.  L == 0 (possible only with a caller's own NaN rows) follows the empty-window
+ * rule of the paragraph above.  An append still in flight is finished first, as every removal does.  Captured plans stay valid: no
+ * pointer, table shape or workspace changes (the rows are scattered into a scratch buffer and copied back, the coordinate arrays
+ * keep their addresses) and the generation is not bumped.  The call waits once on the host for L (a host-mapped word, polled) and
+ * once more only when remap is asked for.  pct_cloud_ring_autocompact(f): f == 0 turns the mode off (the default: nothing anywhere
+ * behaves differently); 0 < f <= 1 turns it on: a removal entry point (pct_cloud_ring_remove_ball / _box / _indices,
+ * pct_cloud_ring_carve_depth) whose own wait reports size − live >= f × capacity and live > 0 compacts before it returns, on the exact counts that wait delivered (no host-side guess, no further wait); *removed
+ * of that call is unchanged.  With the mode on, "every other point keeps its index" holds only between compactions:
+ * pct_cloud_ring_compact_count is the number of compactions that moved rows (0 < L < old size) since the cloud was created, and a
+ * caller who holds indices compares it before and after a call.  f < 0, f > 1 or non-finite, or f > 0 on a cloud without
+ * pct_cloud_ring_index: PCT_ERR_INVALID; pct_cloud_ring_drop turns the mode off, as it does de-dup.
  *
  * Depth images (pct_cloud_ring_carve_depth, pct_cloud_append_depth, pct_depth_classify): the consumer side of the reference's rgbd and
  * camera modes -- img_pcl_map_observer::save_point back-projects a rendered depth image to the observed cloud (map_observer.cpp:92-100),
@@ -283,6 +311,10 @@ int pct_cloud_ring_remove_box(pct_cloud *c, const double lo[3], const double hi[
 int pct_cloud_ring_remove_indices(pct_cloud *c, const uint32_t *idx, int64_t n, int64_t *removed);
 /* rows below size without a NaN coordinate, and size - that (one launch, one wait) */
 int pct_cloud_ring_live(pct_cloud *c, int64_t *live, int64_t *not_live);
+/* Compacting the window (the paragraph "Compacting the window" above) */
+int pct_cloud_ring_compact(pct_cloud *c, int64_t *live, int64_t *reclaimed, uint32_t *remap, int64_t remap_cap);
+int pct_cloud_ring_autocompact(pct_cloud *c, double dead_fraction);
+int pct_cloud_ring_compact_count(const pct_cloud *c, uint64_t *compactions);
 /* Depth images (the paragraph "Depth images" above).  One pinned projection for the three calls below. */
 enum pct_depth_metric { PCT_DEPTH_Z = 0, PCT_DEPTH_RANGE = 1 };
 typedef struct pct_depth_view {

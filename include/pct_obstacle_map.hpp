@@ -65,6 +65,10 @@ public:
                 pct_cloud_destroy(bigger);
                 check(PCT_ERR_HIP, "pct_cloud_ring_dedup");
             }
+            if (rolling_ && compact_fraction_ > 0 && pct_cloud_ring_autocompact(bigger, compact_fraction_) != PCT_OK) {
+                pct_cloud_destroy(bigger);
+                check(PCT_ERR_HIP, "pct_cloud_ring_autocompact");
+            }
             pct_cloud_destroy(cloud_);
             cloud_ = bigger;
             capacity_ = cap;
@@ -128,6 +132,35 @@ public:
         int64_t live = 0, gone = 0;
         check(pct_cloud_ring_live(cloud_, &live, &gone), "pct_cloud_ring_live");
         return live;
+    }
+
+    // Compacting the window (pct_engine.h, paragraph "Compacting the window"; needs enableRollingIndex): removed slots stay below size()
+    // and the ring cursor overwrites live and dead slots alike, so a full window that was thinned evicts live points while dead slots
+    // sit unused.  A compaction moves the live points to slots 0 .. L-1, oldest first, files the table again and lets the next
+    // appends fill the reclaimed slots.  Indices change: remap (may be null; remap_cap >= size()) receives the new index of every
+    // old slot, or PCT_NO_INDEX.
+    //   compactWindow      compact now; returns the number of slots reclaimed
+    //   setRollingCompact  dead_fraction > 0: every removal above (and clearSeenThrough) that leaves that share of the capacity dead
+    //                      compacts before it returns; 0 = off (default)
+    //   compactions        compactions that moved points so far: indices held across a call are stale when it has changed
+    int64_t compactWindow(uint32_t *remap = nullptr, int64_t remap_cap = 0)
+    {
+        needRolling("compactWindow");
+        int64_t live = 0, reclaimed = 0;
+        check(pct_cloud_ring_compact(cloud_, &live, &reclaimed, remap, remap_cap), "pct_cloud_ring_compact");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return reclaimed;
+    }
+    void setRollingCompact(double dead_fraction)
+    {
+        check(pct_cloud_ring_autocompact(cloud_, dead_fraction), "pct_cloud_ring_autocompact");
+        compact_fraction_ = dead_fraction;
+    }
+    uint64_t compactions()
+    {
+        uint64_t n = 0;
+        check(pct_cloud_ring_compact_count(cloud_, &n), "pct_cloud_ring_compact_count");
+        return n;
     }
 
     // Depth images on the rolling map (pct_engine.h, paragraph "Depth images"; both need enableRollingIndex).  The rgbd tick is
@@ -292,6 +325,7 @@ private:
     bool cloud_empty_ = true;
     bool rolling_ = false;
     double dedup_res_ = 0.0;
+    double compact_fraction_ = 0.0;
     double safety_margin_ = 0.0;
     pct_inflate_params prm_{ { 0, 0, 0 }, 0.0, 0.0, 0.0 };
 };

@@ -38,6 +38,8 @@ def lib():
         L.pct_corridor_append_input.argtypes = [vp, vp, C.c_int64, C.c_int64]
         L.pct_corridor_set_rolling_dedup.argtypes = [vp, C.c_double]
         L.pct_corridor_forget_outside.argtypes = [vp, d3, C.c_double, C.POINTER(C.c_int64)]
+        L.pct_corridor_compact_window.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.pct_corridor_set_rolling_compact.argtypes = [vp, C.c_double]
         L.pct_corridor_clear_ball.argtypes = [vp, d3, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_box.argtypes = [vp, d3, d3, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_seen_through.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
@@ -132,6 +134,17 @@ class SafeRegionRrtStar:
         n = C.c_int64()
         self._chk(self.L.pct_corridor_forget_outside(self.h, _d3(centre), float(r), C.byref(n)))
         return n.value
+
+    def compactWindow(self) -> int:
+        """after enableRollingMap: move the live points of the window to its first slots, oldest first, so that the next frames fill
+        the slots of removed points instead of evicting live ones; returns the number of slots reclaimed"""
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_compact_window(self.h, C.byref(n)))
+        return n.value
+
+    def setRollingCompact(self, dead_fraction: float):
+        """after enableRollingMap: every removal compacts the window by itself once dead_fraction of the capacity is dead (0 = off)"""
+        self._chk(self.L.pct_corridor_set_rolling_compact(self.h, float(dead_fraction)))
 
     def clearBall(self, centre, r: float) -> int:
         """after enableRollingMap: remove the points within r of centre (a stale obstacle); returns the number removed"""

@@ -79,6 +79,11 @@ int pct_corridor_forget_outside(pct_corridor *c, const double centre[3], double 
 {
     return guarded([&] { const int64_t n = c->impl->forgetOutside(v3(centre), r); if (removed) *removed = n; });
 }
+int pct_corridor_compact_window(pct_corridor *c, int64_t *reclaimed)
+{
+    return guarded([&] { const int64_t n = c->impl->compactWindow(); if (reclaimed) *reclaimed = n; });
+}
+int pct_corridor_set_rolling_compact(pct_corridor *c, double dead_fraction) { return guarded([&] { c->impl->setRollingCompact(dead_fraction); }); }
 int pct_corridor_clear_ball(pct_corridor *c, const double centre[3], double r, int64_t *removed)
 {
     return guarded([&] { const int64_t n = c->impl->clearBall(v3(centre), r); if (removed) *removed = n; });

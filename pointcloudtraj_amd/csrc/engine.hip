@@ -31,6 +31,7 @@
 #include "ring.hpp"
 #include "ring_dedup.hpp"
 #include "ring_remove.hpp"
+#include "ring_compact.hpp"
 #include "ring_depth.hpp"
 #include "brute2.hpp"
 #include "knn.hpp"
@@ -324,6 +325,14 @@ struct pct_cloud {
     DevBuf<RingRemoveMeet> d_rm_meet;
     SeqWord rm_word;
     DevBuf<uint32_t> d_rm_list;
+    // compacting the window (ring_compact.hpp, pct_cloud_ring_compact): the dead share of the capacity at which a removal compacts
+    // before it returns (0 = off), compactions that moved rows so far, and the grow-only scratch -- three SoA arrays of rc_rows rows
+    // each in one block, tile totals, the device remap
+    double rc_fraction = 0.0;
+    uint64_t rc_count = 0;
+    DevBuf<float> rc_xyz;
+    DevBuf<uint32_t> rc_tile, rc_remap;
+    int64_t rc_rows = 0;
     // de-duplicating appends (ring_dedup.hpp, pct_cloud_ring_dedup): voxel size (0 = off), the frame filter's scratch -- key table,
     // per-point table slot, the compaction scratch (sized with it) -- and the host-mapped {sequence, survivors} pair
     double dd_res = 0.0;

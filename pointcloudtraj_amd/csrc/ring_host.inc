@@ -708,6 +708,7 @@ int pct_cloud_ring_drop(pct_cloud *c)
     ring_free(c);
     c->ring_on = false;
     c->dd_res = 0.0;
+    c->rc_fraction = 0.0;
     c->generation++;
     return PCT_OK;
 }
@@ -934,6 +935,88 @@ int ring_remove_begin(pct_cloud *c, const char *what)
     return PCT_OK;
 }
 
+// the window becomes the empty cloud (the empty-window rule of the removal paragraph): size 0, cursor at slot 0, tables cleared
+int ring_reset_empty(pct_cloud *c)
+{
+    c->count = 0;
+    c->ring_next = 0;
+    c->ring_removed_any = false;
+    PCTCHK(ring_refile_all(c));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return PCT_OK;
+}
+
+// ---- compacting the window (ring_compact.hpp) ---------------------------------------------------------------------------------------
+// scratch of a compaction (grow-only; the capacity never changes, so it is allocated once): three SoA arrays, tile totals, and the
+// device remap when a caller asks for it
+int ring_compact_ensure(pct_cloud *c, bool want_remap)
+{
+    PCTCHK(c->dd_word.ensure(4));
+    if (c->rc_rows < c->cap) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        c->rc_rows = 0;
+        PCTCHK(c->rc_xyz.reserve(3 * (size_t)c->cap));
+        PCTCHK(c->rc_tile.reserve((size_t)ceil_div(c->cap, kRcTile)));
+        c->rc_rows = c->cap;
+    }
+    if (want_remap && c->rc_remap.capacity() < (size_t)c->cap) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        PCTCHK(c->rc_remap.reserve((size_t)c->cap));
+    }
+    return PCT_OK;
+}
+
+// The compaction itself; the caller has finished the append in flight and checked the arguments, and the window holds rows.
+// known_live >= 0: the wait of the removal that asks (auto mode) has delivered L already and L < size: no wait of its own.
+// remap (host, may be null): filled for the old slots [0, old size).
+int ring_compact_run(pct_cloud *c, int64_t known_live, int64_t *live_out, uint32_t *remap)
+{
+    hipStream_t s = g_stream;
+    const int64_t n = c->count;
+    PCTCHK(ring_compact_ensure(c, remap != nullptr));
+    const RcWindow W{ (uint32_t)(n == c->cap ? c->ring_next : 0), (uint32_t)c->cap, (uint32_t)n };
+    const int ntiles = ceil_div(n, kRcTile);
+    const uint32_t seq = c->dd_word.next();
+    rc_count_kernel<<<ntiles, 256, 0, s>>>(W, c->x, c->y, c->z, c->rc_tile);
+    scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->rc_tile.get(), (uint32_t)ntiles, DdPublish{ c->dd_word.w, seq });
+    HIPCHK(hipGetLastError());
+    int64_t L = known_live;
+    if (L < 0) {
+        PCTCHK(dd_scan_wait(c, seq, &L));
+        if (L > n) return fail(PCT_ERR_INTERNAL, "a compaction counted %lld live rows of %lld", (long long)L, (long long)n);
+    }
+    *live_out = L;
+    const uint32_t base = (uint32_t)c->index_base;
+    if (L == n) {                               // nothing to reclaim: nothing moves, not even a wrapped ring's rotation
+        if (remap) for (int64_t i = 0; i < n; i++) remap[i] = base + (uint32_t)i;
+        return PCT_OK;
+    }
+    if (L == 0) {                               // only the caller's own NaN rows were left: the empty-window rule
+        if (remap) for (int64_t i = 0; i < n; i++) remap[i] = PCT_NO_INDEX;
+        PCTCHK(ring_reset_empty(c));
+        c->content_epoch++;
+        return note_mutation(c);
+    }
+    float *ox = c->rc_xyz.get(), *oy = ox + c->rc_rows, *oz = oy + c->rc_rows;
+    rc_scatter_kernel<<<ntiles, 256, 0, s>>>(W, c->x, c->y, c->z, c->rc_tile, ox, oy, oz, remap ? c->rc_remap.get() : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->x, ox, sizeof(float) * (size_t)L, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->y, oy, sizeof(float) * (size_t)L, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->z, oz, sizeof(float) * (size_t)L, hipMemcpyDeviceToDevice, s));
+    c->count = L;
+    c->ring_next = L % c->cap;
+    c->ring_removed_any = false;                // no NaN row is left below the new size
+    PCTCHK(ring_refile_all(c));
+    c->content_epoch++;
+    c->rc_count++;
+    if (remap) {                                // the second wait, only for a caller who asks for the remap
+        HIPCHK(hipMemcpyAsync(remap, c->rc_remap, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (base) for (int64_t i = 0; i < n; i++) if (remap[i] != PCT_NO_INDEX) remap[i] += base;
+    }
+    return note_mutation(c);
+}
+
 // bookkeeping behind a removal's wait.  A window left without a single row free of NaN becomes the empty cloud: what an upload of
 // zero points does to a rolling-map cloud (size 0, cursor at slot 0, tables cleared; the index stays configured and de-dup stays on,
 // captured plans stay valid: no pointer, table shape or workspace changes).
@@ -942,13 +1025,12 @@ int ring_remove_finish(pct_cloud *c, int64_t removed, int64_t live)
     if (removed > 0) {
         c->ring_removed_any = true;
         c->content_epoch++;
-        if (live == 0) {
-            c->count = 0;
-            c->ring_next = 0;
-            c->ring_removed_any = false;
-            PCTCHK(ring_refile_all(c));
-            HIPCHK(hipStreamSynchronize(g_stream));
-        }
+        if (live == 0) PCTCHK(ring_reset_empty(c));
+    }
+    // auto-compaction (pct_cloud_ring_autocompact), on the exact counts this removal's wait delivered
+    if (c->rc_fraction > 0 && live > 0 && (double)(c->count - live) >= c->rc_fraction * (double)c->cap) {
+        int64_t L = 0;
+        return ring_compact_run(c, live, &L, nullptr);
     }
     return note_mutation(c);
 }
@@ -1044,6 +1126,41 @@ int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
     PCTCHK(ring_remove_wait(c, seq, &removed, &live));
     *live_out = live;
     *not_live = c->count - live;
+    return PCT_OK;
+}
+
+int pct_cloud_ring_compact(pct_cloud *c, int64_t *live, int64_t *reclaimed, uint32_t *remap, int64_t remap_cap)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (!c->ring_on) return fail(PCT_ERR_INVALID, "pct_cloud_ring_compact needs the rolling-map index (pct_cloud_ring_index)");
+    if (!c->ring_ready && c->count > 0) return fail(PCT_ERR_INVALID, "pct_cloud_ring_compact: the cloud has no live rolling-map index");
+    if (remap && remap_cap < c->count) return fail(PCT_ERR_INVALID, "pct_cloud_ring_compact: a remap of %lld entries for a window of %lld", (long long)remap_cap, (long long)c->count);
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_compact"));
+    if (live) *live = 0;
+    if (reclaimed) *reclaimed = 0;
+    if (c->count == 0) return PCT_OK;
+    const int64_t n = c->count;
+    int64_t L = 0;
+    PCTCHK(ring_compact_run(c, -1, &L, remap));
+    if (live) *live = L;
+    if (reclaimed) *reclaimed = n - L;
+    return PCT_OK;
+}
+
+int pct_cloud_ring_autocompact(pct_cloud *c, double dead_fraction)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (!(dead_fraction >= 0 && dead_fraction <= 1)) return fail(PCT_ERR_INVALID, "the dead fraction of auto-compaction must lie in [0, 1]");
+    if (dead_fraction == 0) { c->rc_fraction = 0.0; return PCT_OK; }
+    if (!c->ring_on) return fail(PCT_ERR_INVALID, "auto-compaction needs the rolling-map index (pct_cloud_ring_index)");
+    c->rc_fraction = dead_fraction;
+    return PCT_OK;
+}
+
+int pct_cloud_ring_compact_count(const pct_cloud *c, uint64_t *compactions)
+{
+    if (!c || !compactions) return fail(PCT_ERR_INVALID, "bad ring_compact_count arguments");
+    *compactions = c->rc_count;
     return PCT_OK;
 }
 

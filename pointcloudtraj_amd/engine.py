@@ -186,6 +186,9 @@ def lib():
         L.pct_cloud_ring_remove_box.argtypes = [vp, f64p, f64p, C.c_int, C.POINTER(i64)]
         L.pct_cloud_ring_remove_indices.argtypes = [vp, u32p, i64, C.POINTER(i64)]
         L.pct_cloud_ring_live.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+        L.pct_cloud_ring_compact.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), u32p, i64]
+        L.pct_cloud_ring_autocompact.argtypes = [vp, C.c_double]
+        L.pct_cloud_ring_compact_count.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.pct_cloud_ring_carve_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64)]
         L.pct_cloud_append_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64), C.POINTER(i64)]
         L.pct_depth_classify.argtypes = [vp, vp, C.c_int32, f64p, i64, C.c_double, vp, vp]
@@ -419,6 +422,28 @@ class Cloud:
         a, b = C.c_int64(), C.c_int64()
         _chk(lib().pct_cloud_ring_live(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def ring_compact(self, want_remap: bool = False):
+        """compact the window after removals (pct_cloud_ring_compact): the live rows move to slots 0 .. L-1 in arrival order and the
+        next appends fill the reclaimed slots.  Returns (live, reclaimed), and with want_remap the uint32 array that maps every old
+        slot to its new index (index base included) or NO_INDEX for a dropped row"""
+        live, rec = C.c_int64(), C.c_int64()
+        if not want_remap:
+            _chk(lib().pct_cloud_ring_compact(self._h, C.byref(live), C.byref(rec), None, 0))
+            return live.value, rec.value
+        remap = np.empty(len(self), np.uint32)
+        _chk(lib().pct_cloud_ring_compact(self._h, C.byref(live), C.byref(rec), _ptr(remap), len(remap)))
+        return live.value, rec.value, remap
+
+    def ring_autocompact(self, fraction: float):
+        """a removal that leaves fraction * capacity or more dead slots below the size compacts before it returns; 0 turns it off"""
+        _chk(lib().pct_cloud_ring_autocompact(self._h, float(fraction)))
+
+    def ring_compact_count(self) -> int:
+        """compactions that moved rows since the cloud was created: indices held across a call are stale when it has changed"""
+        n = C.c_uint64()
+        _chk(lib().pct_cloud_ring_compact_count(self._h, C.byref(n)))
+        return n.value
 
     def ring_carve_depth(self, view: DepthView, image, margin: float) -> int:
         """free-space clearing (pct_cloud_ring_carve_depth): remove every point the depth image sees through -- in the image, its

@@ -294,6 +294,60 @@ def run_rgbd_window_scenario(window, render, frames=6, carve=True, images=None, 
     return out
 
 
+# ---- the rgbd window with a partial view: a camera that pans round a room whose obstacles come and go --------------------------------
+# A camera at the origin turns by 90 degrees per frame (four headings a lap, fov 90: the views tile the circle) inside a square room
+# with walls 6 m away.  In every heading a 4 m x 4 m obstacle stands 4 m away during the even laps, a little further along the wall
+# each time, and is gone during the odd laps: every lap the carve withdraws what left and the append files what is new, so the
+# number of points ever filed grows while the number of live points does not.  `cap` is deliberately small: it holds the live points
+# and one image, not what a window that never reclaims removed slots needs -- such a window evicts live wall points BEHIND the camera,
+# which the partial view does not sense again until the camera has come round.
+RGBD_PAN = dict(width=32, height=24, fov_hor_deg=90.0, wall_x=6.0, wall_size=(16.0, 12.0), obstacle_x=4.0, obstacle_size=4.0, shift=0.7,
+                lattice=0.1, laps=6, cap=5000, big_cap=12000, fraction=0.05, res=0.1, margin=1.0e-3, extent=(14.0, 14.0, 14.0))
+
+
+def rgbd_pan_view(heading):
+    """the pct_depth_view (engine.DepthView) of heading 0..3: the optical axis turned by heading * 90 degrees about z, metric Z"""
+    from . import engine
+    c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[heading % 4]
+    Rm = ((s, 0.0, c), (-c, 0.0, s), (0.0, -1.0, 0.0))          # columns: image right, image down, optical axis
+    return engine.depth_view((0.0, 0.0, 0.0), Rm, RGBD_PAN["width"], RGBD_PAN["height"], fov_hor_deg=RGBD_PAN["fov_hor_deg"])
+
+
+def rgbd_pan_scene(frame):
+    """what the camera of frame `frame` can see: the wall of its heading and, during the even laps, that lap's obstacle in front"""
+    heading, lap = frame % 4, frame // 4
+    pts = _lattice(RGBD_PAN["wall_x"], *RGBD_PAN["wall_size"], RGBD_PAN["lattice"])
+    if lap % 2 == 0:
+        ob = _lattice(RGBD_PAN["obstacle_x"], RGBD_PAN["obstacle_size"], RGBD_PAN["obstacle_size"], RGBD_PAN["lattice"])
+        ob[:, 1] += np.float32(RGBD_PAN["shift"] * (lap // 2) - 1.0)
+        pts = np.concatenate([pts, ob])
+    c, s = ((1, 0), (0, 1), (-1, 0), (0, -1))[heading]
+    return np.stack([c * pts[:, 0] - s * pts[:, 1], s * pts[:, 0] + c * pts[:, 1], pts[:, 2]], axis=1).astype(np.float32)
+
+
+def run_rgbd_pan_scenario(window, render, laps=None, images=None, each=None):
+    """The rgbd tick -- clearSeenThrough(view, image, margin) then appendDepthImage(view, image), de-dup on -- for the panning camera
+    above, on whatever window the caller configured: small or large, with setRollingCompact (autocompact) on or off.  `window` has
+    the two camelCase members and live_set() (the numpy models), or is a SafeRegionRrtStar.  Returns the live set after every
+    frame; `images` (a list, optional) receives (view, image) per frame; each(frame index, window) is called after every frame."""
+    out = []
+    for k in range(4 * (RGBD_PAN["laps"] if laps is None else laps)):
+        view = rgbd_pan_view(k % 4)
+        image = render(view, rgbd_pan_scene(k))
+        if images is not None:
+            images.append((view, image))
+        window.clearSeenThrough(view, image, RGBD_PAN["margin"])
+        window.appendDepthImage(view, image, float("inf"))
+        if hasattr(window, "live_set"):
+            out.append(window.live_set())
+        else:
+            _, _, xyz = window.cloud().radius_crop((0.0, 0.0, 0.0), 1.0e4)
+            out.append(set(map(tuple, xyz.tolist())))
+        if each is not None:
+            each(k, window)
+    return out
+
+
 def timed_scenario(finder, cloud1, expand=1500, refine=400):
     """run_scenario with wall-clock milliseconds per planner phase (bench.py / scripts/probe_corridor.py)"""
     import time
