@@ -60,6 +60,11 @@ int pct_corridor_set_rolling_compact(pct_corridor *c, double dead_fraction);
  * frame (*kept, may be NULL = the points the window took). */
 int pct_corridor_clear_seen_through(pct_corridor *c, const pct_depth_view *view, const float *image, double margin, int64_t *removed);
 int pct_corridor_append_depth(pct_corridor *c, const pct_depth_view *view, const float *image, double max_depth, int64_t *kept);
+/* after pct_corridor_enable_rolling: radius outlier removal on the window itself (pct_engine.h, paragraph "Removing outliers"): of the
+ * `newest` most recent points (<= 0: every point), those with fewer than min_neighbours other points of the window within r are
+ * removed (*removed, may be NULL).  With a noisy sensor the tick is clear_seen_through -> append_depth -> remove_outliers ->
+ * evaluate -> refine with newest = *kept of the append. */
+int pct_corridor_remove_outliers(pct_corridor *c, double r, int32_t min_neighbours, int64_t newest, int64_t *removed);
 /* the engine's handle of the finder's obstacle cloud (SafeRegionRrtStar::obstacleMap().handle()), for the read-only calls of
  * pct_engine.h -- pct_radius_crop reads the window back; owned by the finder, replaced by a set_input that has to grow the map */
 int pct_corridor_cloud(pct_corridor *c, pct_cloud **cloud);

@@ -238,6 +238,10 @@ public:
     // frame everything appendInput does for a point frame.  Radii that may now grow are re-checked by SafeRegionEvaluate.
     int64_t clearSeenThrough(const pct_depth_view &view, const float *image, double margin) { return map_.clearSeenThrough(view, image, margin); }
     int64_t appendDepthImage(const pct_depth_view &view, const float *image, double max_depth) { return map_.appendDepthImage(view, image, max_depth); }
+    // after enableRollingMap: radius outlier removal on the window itself (ObstacleMap::removeOutliers).  With a noisy sensor the rgbd
+    // tick is clearSeenThrough -> appendDepthImage -> removeOutliers -> SafeRegionEvaluate -> SafeRegionRefine, with newest = the
+    // points the append kept: a speckle is withdrawn in the frame that brought it, before any radius is computed against it.
+    int64_t removeOutliers(double r, int min_neighbours, int64_t newest = 0) { return map_.removeOutliers(r, min_neighbours, newest); }
 
     // ---- queries ----
     bool checkTrajPtCol(const Vec3 &pt) { return clearance(pt) < 0.0; }                     // :412-416

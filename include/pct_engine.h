@@ -161,6 +161,32 @@
  * caller who holds indices compares it before and after a call.  f < 0, f > 1 or non-finite, or f > 0 on a cloud without
  * pct_cloud_ring_index: PCT_ERR_INVALID; pct_cloud_ring_drop turns the mode off, as it does de-dup.
  *
+ * Removing outliers (pct_cloud_ring_remove_outliers, pct_cloud_ring_neighbour_counts): the radius rule on the window itself -- a
+ * judged row stays iff at least min_neighbours OTHER rows of the window lie within r of it -- judged in place, no row crosses the bus.
+ * Neighbour: row j is a neighbour of row i iff j != i as ring slots, both rows are below pct_cloud_size and hold no NaN, and
+ * ((dx*dx + dy*dy) + dz*dz) <= r*r in fp64 on the float-widened rows, one rounding per operation, no contraction: the inclusive test
+ * of the radius count (a row exactly r away is a neighbour).  Exclusion is by slot, not by distance: a coincident copy in another
+ * slot is a neighbour.  A row with +/-inf and no NaN is live; for the finite r this call takes it has no neighbour and is nobody's
+ * neighbour, because every d2 that involves it is inf or NaN (an r*r that overflows is held at DBL_MAX).  Judged rows: the `newest` most recent rows in arrival order -- with
+ * n = size and start = (n == capacity ? cursor : 0), arrival position p lives in slot (start + p) mod capacity, the order of the
+ * paragraph above; positions p >= n - newest are judged, newest <= 0 or newest >= n judges every row; neighbours are always sought in
+ * the whole window; rows that hold a NaN are not judged.  newest = the kept count of the append just made
+ * (pct_cloud_ring_dedup_last, pct_cloud_append_depth) is the per-frame filter.  One judgement, then one removal: every judged row is
+ * counted on the window as it is when the call begins, then every judged row with fewer than min_neighbours neighbours is removed --
+ * the result does not depend on thread order, and it is not the fixed point of repeated removal (three points 0.4 apart on a line,
+ * r = 0.5, min_neighbours = 2: the two ends go and the middle stays; a second call removes the middle).  The call is a removal in
+ * every sense of the paragraph "Removing points": it needs a live rolling-map index, finishes an append in flight first, satisfies
+ * the NaN-row equivalence on every path, *removed counts the rows this call changed (may be NULL), the empty-window rule and the
+ * auto-compaction rule (pct_cloud_ring_autocompact, on the counts this call's wait delivered) apply, captured plans stay valid, the
+ * de-dup holders forget the removed voxels, and there is one host wait, the removal's own.  r must be finite and >= 0 and
+ * min_neighbours >= 0, else PCT_ERR_INVALID with nothing changed; min_neighbours == 0 removes nothing and launches nothing; an empty
+ * cloud returns PCT_OK with zero.  pct_cloud_ring_neighbour_counts is the same judgement without the removal: counts[slot], for
+ * slot < size, is min(neighbours, count_cap) for a judged row and PCT_NO_INDEX for a row that holds a NaN or is out of scope; n
+ * (the entries of counts, host memory) must be >= size and count_cap >= 1, else PCT_ERR_INVALID; it changes nothing in the cloud.
+ * Cost: a row reads the buckets of the (2 ceil(r / cell) + 3)^3 cells its ball can touch until min_neighbours (count_cap) neighbours
+ * are found -- its own bucket first -- so the cost grows with (r / cell)^3 and, for the rows that are removed, is always the whole
+ * box: an r of many cells is not what this call is for.
+ *
  * Depth images (pct_cloud_ring_carve_depth, pct_cloud_append_depth, pct_depth_classify): the consumer side of the reference's rgbd and
  * camera modes -- img_pcl_map_observer::save_point back-projects a rendered depth image to the observed cloud (map_observer.cpp:92-100),
  * safety_controller::check_image_for_point decides whether a point lies in observed free space (safety_controller.cpp:102-130).  One
@@ -315,6 +341,9 @@ int pct_cloud_ring_live(pct_cloud *c, int64_t *live, int64_t *not_live);
 int pct_cloud_ring_compact(pct_cloud *c, int64_t *live, int64_t *reclaimed, uint32_t *remap, int64_t remap_cap);
 int pct_cloud_ring_autocompact(pct_cloud *c, double dead_fraction);
 int pct_cloud_ring_compact_count(const pct_cloud *c, uint64_t *compactions);
+/* Removing outliers (the paragraph "Removing outliers" above) */
+int pct_cloud_ring_remove_outliers(pct_cloud *c, double r, int32_t min_neighbours, int64_t newest, int64_t *removed);
+int pct_cloud_ring_neighbour_counts(pct_cloud *c, double r, int32_t count_cap, int64_t newest, uint32_t *counts, int64_t n);
 /* Depth images (the paragraph "Depth images" above).  One pinned projection for the three calls below. */
 enum pct_depth_metric { PCT_DEPTH_Z = 0, PCT_DEPTH_RANGE = 1 };
 typedef struct pct_depth_view {

@@ -163,6 +163,29 @@ public:
         return n;
     }
 
+    // Removing outliers (pct_engine.h, paragraph "Removing outliers"; needs enableRollingIndex): a flying pixel at a depth edge or a
+    // speckle in free space is one obstacle point that closes a corridor; the radius rule withdraws it before the planner sees it.
+    //   removeOutliers    of the `newest` most recent points (0: every point), those with fewer than min_neighbours other points of
+    //                     the window within r are removed -- one judgement on the window as it is, then one removal; returns the
+    //                     number removed.  newest = what the append just made kept is the per-frame filter.
+    //   neighbourCounts   the same judgement without the removal: per slot min(neighbours, count_cap), PCT_NO_INDEX for a slot that
+    //                     holds no point or is out of scope
+    int64_t removeOutliers(double r, int min_neighbours, int64_t newest = 0)
+    {
+        needRolling("removeOutliers");
+        int64_t removed = 0;
+        check(pct_cloud_ring_remove_outliers(cloud_, r, min_neighbours, newest, &removed), "pct_cloud_ring_remove_outliers");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return removed;
+    }
+    std::vector<uint32_t> neighbourCounts(double r, int count_cap, int64_t newest = 0)
+    {
+        needRolling("neighbourCounts");
+        std::vector<uint32_t> counts((size_t)pct_cloud_size(cloud_));
+        check(pct_cloud_ring_neighbour_counts(cloud_, r, count_cap, newest, counts.data(), (int64_t)counts.size()), "pct_cloud_ring_neighbour_counts");
+        return counts;
+    }
+
     // Depth images on the rolling map (pct_engine.h, paragraph "Depth images"; both need enableRollingIndex).  The rgbd tick is
     // clearSeenThrough(image) then appendDepthImage(the same image): carve first, then append, with a small positive margin so that
     // the next frame's carve leaves the points this frame appended alone.

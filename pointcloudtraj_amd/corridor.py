@@ -42,6 +42,7 @@ def lib():
         L.pct_corridor_set_rolling_compact.argtypes = [vp, C.c_double]
         L.pct_corridor_clear_ball.argtypes = [vp, d3, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_box.argtypes = [vp, d3, d3, C.POINTER(C.c_int64)]
+        L.pct_corridor_remove_outliers.argtypes = [vp, C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_seen_through.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_append_depth.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_cloud.argtypes = [vp, C.POINTER(vp)]
@@ -150,6 +151,14 @@ class SafeRegionRrtStar:
         """after enableRollingMap: remove the points within r of centre (a stale obstacle); returns the number removed"""
         n = C.c_int64()
         self._chk(self.L.pct_corridor_clear_ball(self.h, _d3(centre), float(r), C.byref(n)))
+        return n.value
+
+    def removeOutliers(self, r: float, min_neighbours: int, newest: int = 0) -> int:
+        """after enableRollingMap: of the `newest` most recent points (0: every point), remove those with fewer than min_neighbours
+        other points of the window within r (the noisy-sensor tick: clearSeenThrough -> appendDepthImage -> removeOutliers ->
+        SafeRegionEvaluate -> SafeRegionRefine, newest = what the append kept); returns the number removed"""
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_remove_outliers(self.h, float(r), int(min_neighbours), int(newest), C.byref(n)))
         return n.value
 
     def clearBox(self, lo, hi) -> int:

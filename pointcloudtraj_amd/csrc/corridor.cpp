@@ -108,6 +108,10 @@ int pct_corridor_append_depth(pct_corridor *c, const pct_depth_view *view, const
         if (kept) *kept = n;
     });
 }
+int pct_corridor_remove_outliers(pct_corridor *c, double r, int32_t min_neighbours, int64_t newest, int64_t *removed)
+{
+    return guarded([&] { const int64_t n = c->impl->removeOutliers(r, min_neighbours, newest); if (removed) *removed = n; });
+}
 int pct_corridor_cloud(pct_corridor *c, pct_cloud **cloud)
 {
     return guarded([&] {

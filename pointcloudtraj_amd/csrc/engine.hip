@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -33,6 +34,7 @@
 #include "ring_remove.hpp"
 #include "ring_compact.hpp"
 #include "ring_depth.hpp"
+#include "ring_outlier.hpp"
 #include "brute2.hpp"
 #include "knn.hpp"
 #include "rsearch.hpp"
@@ -333,6 +335,9 @@ struct pct_cloud {
     DevBuf<float> rc_xyz;
     DevBuf<uint32_t> rc_tile, rc_remap;
     int64_t rc_rows = 0;
+    // removing outliers (ring_outlier.hpp, pct_cloud_ring_remove_outliers): one clamped neighbour count per slot, sized by the capacity
+    // on first use (grow-only)
+    DevBuf<uint32_t> ro_counts;
     // de-duplicating appends (ring_dedup.hpp, pct_cloud_ring_dedup): voxel size (0 = off), the frame filter's scratch -- key table,
     // per-point table slot, the compaction scratch (sized with it) -- and the host-mapped {sequence, survivors} pair
     double dd_res = 0.0;

@@ -1112,6 +1112,80 @@ int pct_cloud_ring_remove_indices(pct_cloud *c, const uint32_t *idx, int64_t n, 
     return ring_remove_finish(c, removed, live);
 }
 
+// ---- removing outliers (ring_outlier.hpp) ----------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// queue the judgement of the `newest` most recent rows (<= 0 or >= size: every row) on the window as it is: ro_counts[slot] =
+// min(neighbours, target) for a judged row, PCT_NO_INDEX for every other slot below the size.  The window holds rows.  An r*r that
+// overflows is held at DBL_MAX: every finite d2 is within it, and a d2 of +inf (a row with an infinite coordinate) never is.
+int ring_outlier_judge(pct_cloud *c, double r, uint32_t target, int64_t newest)
+{
+    hipStream_t s = g_stream;
+    const int64_t n = c->count;
+    if (c->ro_counts.capacity() < (size_t)c->cap) {
+        HIPCHK(hipStreamSynchronize(s));
+        PCTCHK(c->ro_counts.reserve((size_t)c->cap));
+    }
+    const int64_t judged = (newest <= 0 || newest >= n) ? n : newest;
+    const RcWindow W{ (uint32_t)(n == c->cap ? c->ring_next : 0), (uint32_t)c->cap, (uint32_t)n };
+    HIPCHK(hipMemsetAsync(c->ro_counts, 0xFF, sizeof(uint32_t) * (size_t)n, s));
+    const int blocks = ceil_div(judged, (int64_t)kRoRows);
+    const double r2 = std::min(r * r, std::numeric_limits<double>::max());
+    if (c->count_work) {
+        c->host_work = false;
+        HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
+        ring_outlier_judge_kernel<true><<<blocks, 256, 0, s>>>(ring_view(c), W, (uint32_t)(n - judged), c->x, c->y, c->z, r, r2, target, c->ro_counts,
+                                                             c->d_work);
+    } else {
+        ring_outlier_judge_kernel<false><<<blocks, 256, 0, s>>>(ring_view(c), W, (uint32_t)(n - judged), c->x, c->y, c->z, r, r2, target, c->ro_counts,
+                                                              nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pct_cloud_ring_remove_outliers(pct_cloud *c, double r, int32_t min_neighbours, int64_t newest, int64_t *removed_out)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (!(std::isfinite(r) && r >= 0)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_remove_outliers: r must be finite and >= 0");
+    if (min_neighbours < 0) return fail(PCT_ERR_INVALID, "pct_cloud_ring_remove_outliers: min_neighbours must be >= 0");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_remove_outliers"));
+    if (removed_out) *removed_out = 0;
+    if (min_neighbours == 0 || c->count == 0) return PCT_OK;
+    PCTCHK(ring_remove_ensure(c));
+    PCTCHK(ring_outlier_judge(c, r, (uint32_t)min_neighbours, newest));
+    const uint32_t seq = c->rm_word.next();
+    ring_outlier_remove_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, c->ro_counts, (uint32_t)min_neighbours, c->x, c->y, c->z, (uint32_t)c->count,
+                                                                             c->ring_ht, c->ring_slots, c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet,
+                                                                             c->rm_word.w, seq);
+    HIPCHK(hipGetLastError());
+    int64_t removed = 0, live = 0;
+    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
+    if (removed_out) *removed_out = removed;
+    return ring_remove_finish(c, removed, live);
+}
+
+int pct_cloud_ring_neighbour_counts(pct_cloud *c, double r, int32_t count_cap, int64_t newest, uint32_t *counts, int64_t n)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (!(std::isfinite(r) && r >= 0)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_neighbour_counts: r must be finite and >= 0");
+    if (count_cap < 1) return fail(PCT_ERR_INVALID, "pct_cloud_ring_neighbour_counts: count_cap must be >= 1");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_neighbour_counts"));
+    if (n < c->count || (c->count > 0 && !counts))
+        return fail(PCT_ERR_INVALID, "pct_cloud_ring_neighbour_counts: %lld counts for a window of %lld", (long long)n, (long long)c->count);
+    if (c->count == 0) return PCT_OK;
+    PCTCHK(ring_outlier_judge(c, r, (uint32_t)count_cap, newest));
+    HIPCHK(hipMemcpyAsync(counts, c->ro_counts, sizeof(uint32_t) * (size_t)c->count, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return PCT_OK;
+}
+
 int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
 {
     if (!c || !live_out || !not_live) return fail(PCT_ERR_INVALID, "bad ring_live arguments");

@@ -189,6 +189,8 @@ def lib():
         L.pct_cloud_ring_compact.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), u32p, i64]
         L.pct_cloud_ring_autocompact.argtypes = [vp, C.c_double]
         L.pct_cloud_ring_compact_count.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.pct_cloud_ring_remove_outliers.argtypes = [vp, C.c_double, C.c_int32, i64, C.POINTER(i64)]
+        L.pct_cloud_ring_neighbour_counts.argtypes = [vp, C.c_double, C.c_int32, i64, u32p, i64]
         L.pct_cloud_ring_carve_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64)]
         L.pct_cloud_append_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64), C.POINTER(i64)]
         L.pct_depth_classify.argtypes = [vp, vp, C.c_int32, f64p, i64, C.c_double, vp, vp]
@@ -444,6 +446,21 @@ class Cloud:
         n = C.c_uint64()
         _chk(lib().pct_cloud_ring_compact_count(self._h, C.byref(n)))
         return n.value
+
+    def ring_remove_outliers(self, r: float, min_neighbours: int, newest: int = 0) -> int:
+        """radius outlier removal on the window itself (pct_cloud_ring_remove_outliers): of the `newest` most recent rows (0: every
+        row), those with fewer than min_neighbours other rows of the window within r are removed -- one judgement on the window as it
+        is, then one removal; returns the number removed"""
+        n = C.c_int64()
+        _chk(lib().pct_cloud_ring_remove_outliers(self._h, float(r), int(min_neighbours), int(newest), C.byref(n)))
+        return n.value
+
+    def ring_neighbour_counts(self, r: float, count_cap: int, newest: int = 0):
+        """the same judgement without the removal (pct_cloud_ring_neighbour_counts): uint32 [len(self)], min(neighbours, count_cap)
+        for a judged row, NO_INDEX for a row that holds a NaN or is out of scope"""
+        counts = np.empty(len(self), np.uint32)
+        _chk(lib().pct_cloud_ring_neighbour_counts(self._h, float(r), int(count_cap), int(newest), _ptr(counts), len(counts)))
+        return counts
 
     def ring_carve_depth(self, view: DepthView, image, margin: float) -> int:
         """free-space clearing (pct_cloud_ring_carve_depth): remove every point the depth image sees through -- in the image, its

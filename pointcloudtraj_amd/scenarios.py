@@ -294,6 +294,68 @@ def run_rgbd_window_scenario(window, render, frames=6, carve=True, images=None, 
     return out
 
 
+# ---- the rgbd window with a noisy sensor: speckle pixels in free space, withdrawn by the radius rule in the frame that brought them ----
+# Every frame `speckles` pixels of the image read `depth` metres in front of the wall instead of what is there.  The pixels come from a
+# fixed list -- a lattice with a pitch of 8 pixels that starts 4 pixels off the border, walked with a stride coprime to its length -- so
+# no pixel is used twice, any two are at least 8 pixels apart and no library's random numbers are involved.  A wall point (0.25 m a
+# pixel at 8 m) or an obstacle point (0.16 m a pixel at 5 m) has at least 2 other points within 0.3 m, also beside a speckle's hole;
+# a speckle point has none (the next one is 8 pixels = 1.5 m away, the obstacle 1 m, the wall 2 m): r = 0.3, min_neighbours = 2.
+RGBD_SPECKLE = dict(speckles=4, depth=2.0, r=0.3, min_neighbours=2, pitch=8, border=4, stride=11)
+
+
+def rgbd_speckle_pixels(frame, speckles=None):
+    """the (column, row) pixels that frame `frame` corrupts"""
+    k = RGBD_SPECKLE["speckles"] if speckles is None else int(speckles)
+    pitch, border = RGBD_SPECKLE["pitch"], RGBD_SPECKLE["border"]
+    nu = (RGBD["width"] - 2 * border - 1) // pitch + 1
+    nv = (RGBD["height"] - 2 * border - 1) // pitch + 1
+    if (frame + 1) * k > nu * nv:
+        raise ValueError("the speckle list has no unused pixel left for this frame")
+    cells = [(RGBD_SPECKLE["stride"] * j) % (nu * nv) for j in range(frame * k, (frame + 1) * k)]
+    return [(border + pitch * (c % nu), border + pitch * (c // nu)) for c in cells]
+
+
+def rgbd_pixel_point(view, u, v, dep):
+    """the fp32 point pixel (u, v) holding `dep` un-projects to (include/pct_engine.h, paragraph "Depth images"), operation by operation"""
+    t, Rm = np.array(list(view.t), np.float64), np.array(list(view.R), np.float64).reshape(3, 3)
+    w, h, focal, dep = np.float64(view.width), np.float64(view.height), np.float64(view.focal), np.float64(np.float32(dep))
+    a = (np.float64(u) / w - 0.5) / focal
+    b = (np.float64(v) - 0.5 * h) / w / focal
+    return np.array([t[k] + dep * ((a * Rm[k, 0] + b * Rm[k, 1]) + Rm[k, 2]) for k in range(3)], np.float64).astype(np.float32)
+
+
+def run_rgbd_speckle_scenario(window, render, frames=6, filter=True, speckles=None, r=None, min_neighbours=None, images=None, each=None):
+    """run_rgbd_window_scenario with a noisy sensor: the tick is clearSeenThrough -> appendDepthImage -> removeOutliers(r,
+    min_neighbours, newest = the points the append kept), de-dup on.  filter = False leaves the last step out: the window then holds
+    every speckle until a later image sees through it.  `window` is a SafeRegionRrtStar with its rolling map and setRollingDedup on,
+    or anything with the same three members and live_set().  Returns the live set after every frame; `images` (a list, optional)
+    receives the corrupted images; each(frame index, window, dict(speckle = that frame's speckle points fp32 [k, 3], kept, removed))
+    is called after every frame."""
+    view = rgbd_view()
+    r = RGBD_SPECKLE["r"] if r is None else r
+    m = RGBD_SPECKLE["min_neighbours"] if min_neighbours is None else min_neighbours
+    dep = np.float32(RGBD["wall_x"] - RGBD_SPECKLE["depth"])
+    out = []
+    for k in range(frames):
+        image = np.array(render(view, rgbd_scene(k)), np.float32)
+        pix = rgbd_speckle_pixels(k, speckles)
+        for u, v in pix:
+            image[v, u] = dep
+        if images is not None:
+            images.append(image)
+        window.clearSeenThrough(view, image, RGBD["margin"])
+        kept = window.appendDepthImage(view, image, float("inf"))
+        removed = window.removeOutliers(r, m, kept) if filter and kept > 0 else 0
+        if hasattr(window, "live_set"):
+            out.append(window.live_set())
+        else:
+            _, _, xyz = window.cloud().radius_crop((0.0, 0.0, 0.0), 1.0e4)
+            out.append(set(map(tuple, xyz.tolist())))
+        if each is not None:
+            each(k, window, dict(speckle=np.stack([rgbd_pixel_point(view, u, v, dep) for u, v in pix]), kept=kept, removed=removed))
+    return out
+
+
 # ---- the rgbd window with a partial view: a camera that pans round a room whose obstacles come and go --------------------------------
 # A camera at the origin turns by 90 degrees per frame (four headings a lap, fov 90: the views tile the circle) inside a square room
 # with walls 6 m away.  In every heading a 4 m x 4 m obstacle stands 4 m away during the even laps, a little further along the wall
