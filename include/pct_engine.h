@@ -382,6 +382,10 @@ int pct_cloud_append_frame(pct_cloud *c, int64_t n, int64_t stride_bytes);
  * that bucket (or of the overflow queue, bit 31 of the where word), id word stored at the filed position, overflow queue length}.
  * A removed slot's where word is 0xFFFFFFFF (no record; the other words then mean nothing). */
 int pct_debug_ring_slot(pct_cloud *c, int64_t slot, uint32_t out[6]);
+/* diagnostics (tests; needs no GPU): 1 when the dense PCT_ALGO_GRID NN batch kernel would address `records` cell-sorted records (the
+ * cloud's points + its 16 spare ones), `cell_entries` run bounds and a batch of `queries` with 32-bit byte offsets, 0 when it keeps
+ * 64-bit addresses, negative for a negative argument. */
+int pct_debug_narrow_offsets(int64_t records, int64_t cell_entries, int64_t queries);
 
 /* Build / drop the uniform-cell index used by PCT_ALGO_GRID.  cell_size <= 0 picks one from
  * the bounding box and point count (about `pct` points per cell). */

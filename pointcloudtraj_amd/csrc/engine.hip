@@ -1070,8 +1070,10 @@ int nn_run(pct_cloud *c, Path path, const float *d_q, int64_t Q, uint32_t *d_idx
                         nn_grid_pyr_todo_kernel<CW><<<(int)std::min<int64_t>(256, blocks), 256, 0, s>>>(c->G, c->P, c->pyr_nodes, c->pyr_hint, c->sorted, c->cell_start, d_q,
                                                                                                         (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
                     } else
-                        launch_dominant(c, s, nn_grid_coop_kernel<CW>, blocks, c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx,
-                                        d_d2, c->d_work);
+                        with_bool(narrow_offsets_fit((uint64_t)c->count + kGridPad, (uint64_t)c->G.ncells + 1, (uint64_t)Q), [&](auto narrow) {
+                            launch_dominant(c, s, nn_grid_coop_kernel<CW, decltype(narrow)::value>, blocks, c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q,
+                                            (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
+                        });
                 });
             }, no_step);
     }
@@ -1782,6 +1784,13 @@ int pct_cloud_drop_grid(pct_cloud *c)
 }
 
 int pct_cloud_has_grid(const pct_cloud *c) { return c && c->has_grid ? 1 : 0; }
+
+/* diagnostics (tests): the launch-time choice of nn_run between 32-bit byte offsets and 64-bit addresses; touches no device */
+int pct_debug_narrow_offsets(int64_t records, int64_t cell_entries, int64_t queries)
+{
+    if (records < 0 || cell_entries < 0 || queries < 0) return -1;
+    return narrow_offsets_fit((uint64_t)records, (uint64_t)cell_entries, (uint64_t)queries) ? 1 : 0;
+}
 
 int pct_cloud_grid_info(const pct_cloud *c, int32_t dims[3], float *cell_size, float origin[3], int64_t *ncells)
 {

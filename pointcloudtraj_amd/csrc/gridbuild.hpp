@@ -35,8 +35,20 @@ struct GbDesc {
 struct GbCheck { unsigned long long sum_ids; uint32_t xor_ids, misplaced, empty_cells, pad; };
 constexpr int kGbCheckSlots = 64;      // blocks add into slot blockIdx & 63 (thousands of blocks on one word serialise: +36 us at 10 M points); the host sums
 
-// spare records allocated (not written) behind the last cell-sorted one: slack against a read past the end of the array
+// spare records allocated (not written) behind the last cell-sorted one.  Load-bearing: the screening of coop_screen_rows (kernels.hpp)
+// clamps a slot's position with min(position, b - 1), b - 1 wrapping for an empty run at the start of the array (a == b == 0), whose
+// lanes then read records sub + 8 j <= 15 whatever the cloud's size -- inside the allocation only because of these 16 records (the read
+// is masked; its content reaches no result).  Must stay >= 8 * the deepest DEPTH of coop_screen_rows (2).
 constexpr uint32_t kGridPad = 16;
+
+// May the dense NN batch kernel form its addresses as 32-bit byte offsets from a scalar base (kernels.hpp ld_at / st_at)?  The offsets
+// wrap at 2^32 bytes: `records` 16-byte records (the n cell-sorted ones + kGridPad) and `queries` 16-byte sorted queries / 8-byte
+// distances allow 2^28 elements each, `cell_entries` 4-byte run bounds (ncells + 1) 2^30.  Larger arrays keep 64-bit addressing; the
+// choice is made once per launch on the host (nn_run), never in the kernel.
+inline bool narrow_offsets_fit(uint64_t records, uint64_t cell_entries, uint64_t queries)
+{
+    return records <= (1ull << 28) && cell_entries <= (1ull << 30) && queries <= (1ull << 28);
+}
 
 // zeroes the build's counters (a kernel of this library on the build's stream, not a runtime memset: one thing less between the
 // launches that is not ours)

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -1178,16 +1179,57 @@ __device__ __forceinline__ double dpp_f64(double v)
 // (measured on the dense batch kernel: the DPP form of the folds below costs registers -- 64 VGPRs + 16 bytes of scratch at 8 waves per
 // SIMD -- and the kernel ran 0.131 instead of 0.122 ms; at the present 7 waves / 72 VGPRs DPP folds + quad broadcasts of the run bounds
 // measure the same as ds_bpermute, 0.1161-0.1163 against 0.1166-0.1167 ms, as does reading a +inf pad record instead of clamping and
-// masking the slots beyond a run, 0.1156-0.1171 (profiles/r03_ab_dpp.txt).  They stay on ds_bpermute; the pyramid walk uses the DPP
+// masking the slots beyond a run, 0.1156-0.1171 (profiles/r03_ab_dpp.txt).  They stay on the LDS pipe; the pyramid walk uses the DPP
 // forms: 1.06 against 1.09 ms.)
+//
+// The exchanges of the 8-lane folds stay on the LDS pipe but as ds_swizzle in bit mode (source lane = ((lane & and) | or) ^ xor inside
+// every 32 lanes, the pattern an immediate) instead of __shfl_xor(v, off, 64), which is a ds_bpermute whose byte index costs
+// v_xor + v_cmp + v_cndmask + v_lshlrev per offset and three index registers kept live across the fold and the exact path.
+// ds_swizzle, like ds_bpermute, returns 0 for a source lane that is switched off, so these helpers may only run where all 8 lanes of a
+// group are active together.  That holds wherever they are used: `live` / `slot < Q` are uniform per group, the band test that selects
+// the exact path is evaluated on folded (group-uniform) values, and the tail loops' T comes from run bounds every lane of the group holds.
+constexpr int swz_xor(int off) { return (off << 10) | 0x1F; }          // lane ^ off                (and 0x1F, or 0, xor off)
+constexpr int swz_group_lane(int k) { return (k << 5) | 0x18; }       // lane k of the 8-lane group (and 0x18, or k, xor 0)
+template <int PATTERN>
+__device__ __forceinline__ uint32_t swz_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, PATTERN); }
+template <int PATTERN>
+__device__ __forceinline__ float swz_f32(float v) { return __uint_as_float(swz_u32<PATTERN>(__float_as_uint(v))); }
+template <int PATTERN>
+__device__ __forceinline__ double swz_f64(double v)
+{
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    return __longlong_as_double((long long)(((uint64_t)swz_u32<PATTERN>((uint32_t)(b >> 32)) << 32) | swz_u32<PATTERN>((uint32_t)b)));
+}
+
+template <int OFF>
+__device__ __forceinline__ void coop_argmin8_step(double &d, uint32_t &i)
+{
+    const double od = swz_f64<swz_xor(OFF)>(d);
+    const uint32_t oi = swz_u32<swz_xor(OFF)>(i);
+    if (better(od, oi, d, i)) { d = od; i = oi; }
+}
 __device__ __forceinline__ void coop_argmin8(double &d, uint32_t &i)
 {
-#pragma unroll
-    for (int off = 1; off < kCoop; off <<= 1) {
-        const double od = __shfl_xor(d, off, kWave);
-        const uint32_t oi = (uint32_t)__shfl_xor((int)i, off, kWave);
-        if (better(od, oi, d, i)) { d = od; i = oi; }
-    }
+    coop_argmin8_step<1>(d, i);
+    coop_argmin8_step<2>(d, i);
+    coop_argmin8_step<4>(d, i);
+}
+
+// Element i of an array through a 32-bit byte offset from the (wave-uniform, scalar) base: global_load v, v_off, s[base] -- one shift.
+// base[i] with a uint32_t i is a zero-extended 64-bit address per lane instead: a v_mov of 0 and a v_lshl_add_u64 per access, two
+// registers per address.  The byte offset wraps at 2^32, so NARROW is only for arrays of at most 2^32 bytes: the host decides
+// (narrow_offsets_fit), never a branch in the kernel.
+template <bool NARROW, typename T>
+__device__ __forceinline__ T ld_at(const T *__restrict__ base, uint32_t i)
+{
+    if constexpr (NARROW) return *(const T *)((const char *)base + (size_t)(uint32_t)(i * (uint32_t)sizeof(T)));
+    else return base[i];
+}
+template <bool NARROW, typename T>
+__device__ __forceinline__ void st_at(T *__restrict__ base, uint32_t i, T v)
+{
+    if constexpr (NARROW) *(T *)((char *)base + (size_t)(uint32_t)(i * (uint32_t)sizeof(T))) = v;
+    else base[i] = v;
 }
 
 // exact scan of [s, e) shared by the 8 lanes of a group (lane `sub` takes s+sub, s+sub+8, ...)
@@ -1254,7 +1296,16 @@ __device__ __forceinline__ void coop_scan_cube_or_shell(const GridDesc &G, const
 // the same (m1, m2, p1) update, only in another order, and min / runner-up are order-independent up to WHICH of several equal minima
 // p1 names; equal minima have m2 == m1, fail the band test below and go to the exact rescan, which orders by (d2, index) in fp64.
 // So whenever fp32 cannot decide, exact arithmetic does, as before.
-template <int NR, int DEPTH, bool TAIL = false>
+//
+// The clamp is min(position, b - 1) with b - 1 WRAPPING for b == 0 (no compare per run, no select per slot for the empty run).  An empty
+// run [a, a) with a > 0 sends its lanes to record a - 1, a live record; an empty run at the start of the array (a == b == 0) leaves the
+// positions unclamped: sub + 8 j <= 8 DEPTH - 1 <= 15 < kGridPad, and the record array is allocated with kGridPad records behind the
+// n written ones (gridbuild.hpp; the cloud's cell-sorted array is the only one that reaches this function), so the read stays inside
+// the allocation even for a cloud of one point.  Either way p < b fails and the slot is masked to +inf: what was read never reaches a
+// result.
+//
+// NARROW: the record reads of the screening (main slots, tail slot, long rows, the winner's reload) take 32-bit byte offsets (ld_at).
+template <int NR, int DEPTH, bool TAIL = false, bool NARROW = false>
 __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts, const uint32_t (&rs)[NR], const uint32_t (&re)[NR],
                                                  uint32_t sub, float qxf, float qyf, float qzf, double qx, double qy, double qz,
                                                  double &bd, uint32_t &bi)
@@ -1266,9 +1317,9 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
 #pragma unroll
     for (int k = 0; k < NR; k++) {
         const uint32_t a = rs[k], b = re[k];
-        const uint32_t last = b > a ? b - 1 : 0u;               // empty row: read slot 0, masked below
+        const uint32_t last = b - 1u;                           // wraps for b == 0; an empty row reads a record that is masked below (see above)
 #pragma unroll
-        for (int j = 0; j < DEPTH; j++) P[k][j] = pts[min(a + sub + kCoop * j, last)];
+        for (int j = 0; j < DEPTH; j++) P[k][j] = ld_at<NARROW>(pts, min(a + sub + kCoop * j, last));
     }
     uint32_t tp = 0;                                              // the shared tail slot: position, in use, the group takes the loops instead
     bool tail_on = false, tail_loops = false;
@@ -1285,8 +1336,8 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
         tail_on = sub < T && T <= (uint32_t)kCoop;
         tail_loops = T > (uint32_t)kCoop;
         const uint32_t a = rs[NR - 1], b = re[NR - 1];
-        tp = tail_on ? tp : min(a + sub + kCoop * (DEPTH - 1), b > a ? b - 1 : 0u);   // idle: the lane's last main slot again
-        PT = pts[tp];
+        tp = tail_on ? tp : min(a + sub + kCoop * (DEPTH - 1), b - 1u);   // idle: the lane's last main slot again (same wrapping clamp)
+        PT = ld_at<NARROW>(pts, tp);
     }
 #pragma unroll
     for (int k = 0; k < NR; k++) {
@@ -1308,7 +1359,7 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
     // 121.5 -> 117 us)
     auto long_row = [&](uint32_t a, uint32_t b) {
         for (uint32_t p = a + kCoop * DEPTH + sub; p < b; p += kCoop) {
-            const float4 Pp = pts[p];
+            const float4 Pp = ld_at<NARROW>(pts, p);
             const float dx = Pp.x - qxf, dy = Pp.y - qyf, dz = Pp.z - qzf;
             const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
             const bool lt = d < m1;
@@ -1336,23 +1387,26 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
 #pragma unroll 1
         for (int k = 0; k < NR; k++) long_row(rs[k], re[k]);
     }
-    // fold (smallest, runner-up, position) over the 8 lanes
-#pragma unroll
-    for (int off = 1; off < kCoop; off <<= 1) {
-        const float o1 = __shfl_xor(m1, off, kWave), o2 = __shfl_xor(m2, off, kWave);
-        const uint32_t op = (uint32_t)__shfl_xor((int)p1, off, kWave);
+    // fold (smallest, runner-up, position) over the 8 lanes: all 8 are active here (see swz_xor)
+    auto fold = [&](auto off) {
+        constexpr int kPat = swz_xor(decltype(off)::value);
+        const float o1 = swz_f32<kPat>(m1), o2 = swz_f32<kPat>(m2);
+        const uint32_t op = swz_u32<kPat>(p1);
         const bool lt = o1 < m1;
         m2 = fminf(fminf(m2, o2), fmaxf(m1, o1));                // second smallest of the two sorted pairs
         p1 = lt ? op : p1;
         m1 = fminf(m1, o1);
-    }
+    };
+    fold(std::integral_constant<int, 1>{});
+    fold(std::integral_constant<int, 2>{});
+    fold(std::integral_constant<int, 4>{});
     bd = __builtin_huge_val();
     bi = kNoIndex;
     // m1 == +inf: the runs are empty, OR every fp32 distance overflowed (points farther than sqrt(FLT_MAX) = 1.8447e19 from the query:
     // far queries, clouds of huge extent).  Their fp64 distances are finite and must compete, so that case takes the exact scan too
     // (over empty runs it does nothing).
     if (m1 < __builtin_huge_valf() && m2 > m1 * (1.0f + 0x1p-19f) + 0x1p-90f) {   // unique within the fp32 error band: it is the exact winner
-        const float4 W = pts[p1];
+        const float4 W = ld_at<NARROW>(pts, p1);
         bd = dist2((double)W.x, (double)W.y, (double)W.z, qx, qy, qz);
         bi = __float_as_uint(W.w);
     } else {                                                      // near-ties / duplicates / overflow: exact (d2, index) order decides
@@ -1493,7 +1547,7 @@ __device__ __forceinline__ bool block_leaves_undecided(const GridDesc &G, int cx
 }
 
 // stage 0 of coop_nn_search alone; returns true when the query is still undecided
-template <bool COUNT>
+template <bool COUNT, bool NARROW>
 __device__ __forceinline__ bool coop_stage0(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
                                             float qxf, float qyf, float qzf, uint32_t sub, double &bd, uint32_t &bi, uint32_t &npts,
                                             uint32_t &nruns)
@@ -1522,11 +1576,14 @@ __device__ __forceinline__ bool coop_stage0(const GridDesc &G, const float4 *__r
         const int ri = (int)sub & 3;                              // lanes 4..7 repeat lanes 0..3 (same addresses: no extra access)
         const bool ok = !((ri >> 1) && zb == za) && !((ri & 1) && yb == ya);
         const uint32_t row = cell_lin(G, 0, (ri & 1) ? yb : ya, (ri >> 1) ? zb : za);
-        const uint32_t a = cell_start[row + xa], b = cell_start[row + xb + 1];
+        const uint32_t a = ld_at<NARROW>(cell_start, row + (uint32_t)xa), b = ld_at<NARROW>(cell_start, row + (uint32_t)xb + 1u);
         const uint32_t my_s = a, my_e = ok ? b : a;
         if (COUNT && sub < 4) { npts += my_e - my_s; nruns += ok ? 1u : 0u; }
-#pragma unroll
-        for (int k = 0; k < 4; k++) { rs[k] = (uint32_t)__shfl((int)my_s, k, kCoop); re[k] = (uint32_t)__shfl((int)my_e, k, kCoop); }
+        // lane k of the group holds run k's bounds: broadcasts with an immediate pattern, all 8 lanes active (see swz_xor)
+        rs[0] = swz_u32<swz_group_lane(0)>(my_s); re[0] = swz_u32<swz_group_lane(0)>(my_e);
+        rs[1] = swz_u32<swz_group_lane(1)>(my_s); re[1] = swz_u32<swz_group_lane(1)>(my_e);
+        rs[2] = swz_u32<swz_group_lane(2)>(my_s); re[2] = swz_u32<swz_group_lane(2)>(my_e);
+        rs[3] = swz_u32<swz_group_lane(3)>(my_s); re[3] = swz_u32<swz_group_lane(3)>(my_e);
     }
     // The block's six cell bounds (< 1024 each: the grid has at most 1024 cells per axis) cross the screening packed into two registers,
     // opaque to the compiler so that it cannot keep the six: with the shared tail slot's three record registers and its position the
@@ -1534,7 +1591,7 @@ __device__ __forceinline__ bool coop_stage0(const GridDesc &G, const float4 *__r
     // round trips (72 is the ceiling of the kernel's 7 waves per SIMD, see nn_grid_coop_kernel).
     uint32_t pk0 = (uint32_t)xa | ((uint32_t)xb << 10) | ((uint32_t)ya << 20), pk1 = (uint32_t)yb | ((uint32_t)za << 10) | ((uint32_t)zb << 20);
     asm volatile("" : "+v"(pk0), "+v"(pk1));
-    coop_screen_rows<4, 2, true>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
+    coop_screen_rows<4, 2, true, NARROW>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
     asm volatile("" : "+v"(pk0), "+v"(pk1));
     return block_leaves_undecided(G, cx, cy, cz, (int)(pk0 & 1023u), (int)((pk0 >> 10) & 1023u), (int)(pk0 >> 20), (int)(pk1 & 1023u),
                                   (int)((pk1 >> 10) & 1023u), (int)(pk1 >> 20), fx, fy, fz, qx, qy, qz, bd);
@@ -1652,14 +1709,14 @@ __device__ __forceinline__ void coop_finish_shells(const GridDesc &G, const floa
 // One query per group of 8 lanes, every lane of the wave in step (live = the group has a query): stage 0, then the whole wave on each
 // undecided query's cube in turn, then the 8-lane shell walk for what even the cube leaves open.  Every lane of a group returns its
 // query's exact (bd, bi).
-template <bool COUNT>
+template <bool COUNT, bool NARROW>
 __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start, bool live,
                                                  float qxf, float qyf, float qzf, uint32_t sub, double &bd, uint32_t &bi, uint32_t &npts, uint32_t &nruns)
 {
     bd = __builtin_huge_val();
     bi = kNoIndex;
     bool undecided = false;
-    if (live) undecided = coop_stage0<COUNT>(G, pts, cell_start, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
+    if (live) undecided = coop_stage0<COUNT, NARROW>(G, pts, cell_start, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
     unsigned long long todo = __builtin_amdgcn_ballot_w64(undecided && sub == 0);
     while (todo) {                                    // wave-uniform: one undecided query at a time, all 64 lanes on it
         const int g = __builtin_ctzll(todo);
@@ -1679,9 +1736,15 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
 // eight record loads of stage 0 two at a time (four dependent round trips); capped at 7 it takes 72 VGPRs and issues all eight before the
 // first use.  Headline step 0.1198-0.1210 -> 0.1163-0.1179 ms (6 waves: 0.122, 5: 0.134; profiles/r03_ab_occupancy_cap.txt).  Raising
 // only the minimum (round 2's "7 waves" experiment) never changed the code: the scheduler still aimed for 8.
-// With the shared tail slot (coop_screen_rows<4, 2, true>) nine loads are in flight at 70 VGPRs; whatever is added to stage 0 has to be
-// checked against that ceiling in the compiler's resource remarks AND in the order of the loads in the ISA.
-template <bool COUNT>
+// With the shared tail slot (coop_screen_rows<4, 2, true>) nine loads are in flight; whatever is added to stage 0 has to be checked against
+// that ceiling in the compiler's resource remarks AND in the order of the loads in the ISA (profiles/r05_stage0_asm.txt): NARROW 69 VGPRs,
+// all nine record loads before the first s_waitcnt vmcnt (vmcnt(8)), 256 vector instructions from the entry to the tail_loops branch and
+// 20 in the fold; wide 70 VGPRs, eight loads before vmcnt(7) and the ninth behind it, 267 + 20 (before the swizzle folds, the wrapping
+// clamp and the 32-bit offsets: 70 VGPRs, eight + one, 283 + 36).
+// NARROW (chosen per launch on the host: narrow_offsets_fit, gridbuild.hpp) addresses the records, the run bounds, the sorted query and
+// the two results with 32-bit byte offsets from their scalar bases (ld_at / st_at); only the TAIL instantiation of coop_screen_rows takes
+// it -- the cube-first form, the pyramid's stage 0 and the rare paths (exact rescans, the wave's cube, shells) keep 64-bit addresses.
+template <bool COUNT, bool NARROW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
                                                            const uint32_t *__restrict__ cell_start,
                                                            const float *__restrict__ q, uint32_t Q, uint32_t index_base,
@@ -1699,7 +1762,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
         float qxf = 0.0f, qyf = 0.0f, qzf = 0.0f;
         if (live) {
             if (qsorted) {
-                const float4 R = qsorted[slot];
+                const float4 R = ld_at<NARROW>(qsorted, slot);
                 qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
             } else {
                 qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
@@ -1707,10 +1770,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
         }
         double bd;
         uint32_t bi;
-        coop_wave_search<COUNT>(G, pts, cell_start, live, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
+        coop_wave_search<COUNT, NARROW>(G, pts, cell_start, live, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
         if (live && sub == 0) {
-            out_idx[t] = reported_index(bd, bi, index_base);
-            out_d2[t] = bd;
+            st_at<NARROW>(out_idx, t, reported_index(bd, bi, index_base));
+            st_at<NARROW>(out_d2, t, bd);
         }
     } else if (slot < Q) {                            // uniform within a group of 8 lanes
         uint32_t t = slot;
