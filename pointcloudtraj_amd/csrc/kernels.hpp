@@ -1507,8 +1507,9 @@ __device__ __forceinline__ void coop_nn_search(const GridDesc &G, const float4 *
 // Stage 0 decides ~99 % of the queries at 6 points per cell, but a wave holds 8 queries and used to run the 3x3x3 cube for all of
 // them -- 8 lanes per query, the 9 rows of ~18 points taken 8 at a time -- as soon as ONE was undecided: 0.99^8 = 8 % of the waves,
 // 15 % of the kernel's time (18 of 124 us on the 10 M-point cloud).  Here the whole wave turns to each undecided query in turn:
-// 9 lanes fetch the rows' bounds, every lane takes one point of each row (all nine loads in flight), one 6-step fold over the 64
-// lanes, the exact winner.  The queries that even the cube does not decide (~1e-4) finish with the 8-lane shell walk as before.
+// 9 lanes fetch the bounds of what the block leaves of the cube's rows within reach of stage 0's best distance, every lane takes one
+// point of each such row (all loads in flight), one ballot of the records that can beat or tie that best, and only those are compared
+// exactly (wave_remainder_search).  The queries that even the cube does not decide (~1e-4) finish with the 8-lane shell walk as before.
 
 // Is a query still undecided after its 2x2x2 block [xa..xb] x [ya..yb] x [za..zb] gave best distance bd?  (f = the query's fractional
 // position in its cell (cx, cy, cz).)
@@ -1597,92 +1598,142 @@ __device__ __forceinline__ bool coop_stage0(const GridDesc &G, const float4 *__r
                                   (int)((pk1 >> 10) & 1023u), (int)(pk1 >> 20), fx, fy, fz, qx, qy, qz, bd);
 }
 
-// the 3x3x3 cube around the cell of a WAVE-UNIFORM query, searched by all 64 lanes; every lane returns the same exact (bd, bi)
-// = the winner by (d2, index) among the cube's points, (+inf, none) for an empty cube
+// What the 2x2x2 block B of a WAVE-UNIFORM query leaves of the 3x3x3 cube around the query's cell, searched by all 64 lanes from stage 0's
+// result: on entry (bd, bi) is the exact winner by (d2, index) among the block's records ((+inf, none) for an empty block), on return the
+// exact winner among the records of the whole cube.  (It replaces a search that took the undecided query as if nothing were known about
+// it: all nine rows of the cube, the block's eight cells among them, (min, runner-up, position) per lane, a 6-step fold of three
+// ds_bpermute each, the winner's reload -- three dependent trips where stage 0's point most often still was the answer.)
+//
+// Lanes 0..8 own the nine (y, z) rows of the cube.  Each finds the x-cells of its row that are inside the grid, not in B, and within reach
+// of the ball of radius sqrt(bd) around the query: the cell's box -- widened per axis by the h/256 slack of cube_bound, which covers the
+// fp32 cell assignment, and open towards the outside at the grid's border, where the assignment clamps -- is at most sqrt(bd) away.  The
+// gaps come from the query's real coordinates (fp64, the face positions as cube_bound computes them), so queries outside the grid work;
+// the sum of their squares is taken 2^-40 short, which covers its own rounding: for a query within 2^36 cells of the grid a gap is off by
+// < 2^-13 h, far inside the slack (the assignment needs 4e-4 h of the h/256), for a query farther away by < 2^-49 of itself.  A comparison
+// that is not decided (NaN, bd = +inf) counts as within reach.  The cells within reach are contiguous: a row of B has at most one cube
+// cell left, at one end; a row outside B meets the ball in an interval around the query's own x-cell, whose gap is 0.  (Were they not, the
+// range taken from the first to the last would only scan more.)  A lane with an empty range fetches nothing.
+//
+// Screening is one-sided against the known best: a record is a candidate iff d32 <= thr, thr = (float)bd rounded up, times (1 + 2^-19),
+// plus 2^-90 -- the band proved at the head of the brute-force filter above (nn_tile_candidates_kernel's form): a record with exact
+// d2 <= bd has d32 <= d2 (1 + 4e-7) + 2^-120 <= thr.  Inclusive, because an equal distance with a lower index must win.  bd beyond
+// FLT_MAX gives thr = +inf and every record is a candidate: far queries, whose fp32 distances overflow while the fp64 ones are finite and
+// must compete.  No candidate anywhere (the common case): (bd, bi) stands after two trips, bounds and records.  Otherwise the lanes that
+// hold candidates evaluate them in exact fp64 from the record registers they still hold, under better() against (bd, bi), and one
+// wave_argmin gives every lane the result.
+//
+// The rows with records are taken kRemRows = 4 at a time (a ball that passes one face of the block has 2 or 4 rows in reach: one pass):
+// the kernel's VGPR count is the maximum over all its paths, and the exact comparison with the records of all nine rows still held costs
+// 72 VGPRs and scratch where the kernel has 69 and none (profiles/r06_fallback_asm.txt).
+//
+// Why this is exact.  Let S be the cells scanned.  Every record of S with exact d2 <= bd lies inside the band and is compared exactly, so
+// on return (bd, bi) is the (d2, index)-minimum over B and S.  Every record of the cube outside B and S lies in a cell whose widened box
+// is strictly farther than sqrt(bd_in) >= sqrt(bd_out): it is neither better nor a tie.  So the cube is fully accounted for, and the
+// termination test and the shell walk (coop_finish_shells) stand on the same ground as after a scan of all its 27 cells.
+constexpr int kRemRows = 4;
 template <bool COUNT>
-__device__ __forceinline__ void wave_cube_search(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
-                                                 float qxf, float qyf, float qzf, double &bd, uint32_t &bi, uint32_t &npts, uint32_t &nruns)
+__device__ __forceinline__ void wave_remainder_search(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
+                                                      float qxf, float qyf, float qzf, double &bd, uint32_t &bi, uint32_t &npts, uint32_t &nruns)
 {
     const uint32_t lane = threadIdx.x & 63;
     const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
     const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
     const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
     const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, G.gx - 1);
-    uint32_t my_s, my_e;
+    // the block, as coop_stage0 chose it
+    const float fx = (qxf - G.ox) * G.inv_h - (float)cx, fy = (qyf - G.oy) * G.inv_h - (float)cy, fz = (qzf - G.oz) * G.inv_h - (float)cz;
+    const int xa = max(fx < 0.5f ? cx - 1 : cx, 0), xb = min(fx < 0.5f ? cx : cx + 1, G.gx - 1);
+    const int ya = max(fy < 0.5f ? cy - 1 : cy, 0), yb = min(fy < 0.5f ? cy : cy + 1, G.gy - 1);
+    const int za = max(fz < 0.5f ? cz - 1 : cz, 0), zb = min(fz < 0.5f ? cz : cz + 1, G.gz - 1);
+    // distance along one axis from q to cell c of g (0 inside), a face counting only where the grid has cells behind it, minus the slack
+    auto gap = [&](int c, int g, double o, double q) {
+        const double ninf = -__builtin_huge_val();
+        const double below = c > 0 ? (o + (double)c * G.hd) - q : ninf;
+        const double above = c < g - 1 ? q - (o + (double)(c + 1) * G.hd) : ninf;
+        return fmax(fmax(below, above) - G.hd * (1.0 / 256.0), 0.0);
+    };
+    uint32_t my_s = 0, my_e = 0;                                      // lanes 9.. and lanes with nothing in reach: the empty run
     {
-        const int l = lane < 9 ? (int)lane : 0;                       // lanes 9.. repeat lane 0's addresses
+        const int l = lane < 9 ? (int)lane : 0;
         const int zz = cz + l / 3 - 1, yy = cy + l % 3 - 1;
-        const bool ok = zz >= 0 && zz < G.gz && yy >= 0 && yy < G.gy;
-        const uint32_t row = ok ? cell_lin(G, 0, yy, zz) : 0u;
-        const uint32_t a = cell_start[row + x0], b = cell_start[row + x1 + 1];
-        my_s = a;
-        my_e = ok ? b : a;
-        if (COUNT && lane < 9) { npts += my_e - my_s; nruns += ok ? 1u : 0u; }
-    }
-    uint32_t rs[9], re[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) {                                     // wave-uniform: scalar registers
-        rs[k] = (uint32_t)__builtin_amdgcn_readlane((int)my_s, k);
-        re[k] = (uint32_t)__builtin_amdgcn_readlane((int)my_e, k);
-    }
-    float m1 = __builtin_huge_valf(), m2 = __builtin_huge_valf();
-    uint32_t p1 = 0;
-    float4 P[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        const uint32_t a = rs[k], b = re[k];
-        P[k] = pts[min(a + lane, b > a ? b - 1 : 0u)];                // empty row / lane beyond the row: any valid slot, masked below
-    }
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        const uint32_t p = rs[k] + lane;
-        const float dx = P[k].x - qxf, dy = P[k].y - qyf, dz = P[k].z - qzf;
-        float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-        d = (p < re[k]) ? d : __builtin_huge_valf();
-        const bool lt = d < m1;
-        m2 = lt ? m1 : fminf(m2, d);
-        p1 = lt ? p : p1;
-        m1 = fminf(m1, d);
-    }
-#pragma unroll 1
-    for (int k = 0; k < 9; k++)                                       // rows of more than 64 points
-        for (uint32_t p = rs[k] + 64u + lane; p < re[k]; p += 64u) {
-            const float4 Pp = pts[p];
-            const float dx = Pp.x - qxf, dy = Pp.y - qyf, dz = Pp.z - qzf;
-            const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-            const bool lt = d < m1;
-            m2 = lt ? m1 : fminf(m2, d);
-            p1 = lt ? p : p1;
-            m1 = fminf(m1, d);
+        const bool ok = lane < 9 && zz >= 0 && zz < G.gz && yy >= 0 && yy < G.gy;
+        const bool block_row = yy >= ya && yy <= yb && zz >= za && zz <= zb;
+        const double gy = gap(yy, G.gy, G.oyd, qy), gz = gap(zz, G.gz, G.ozd, qz);
+        auto reach = [&](int c) {
+            const bool valid = ok && c >= 0 && c <= G.gx - 1 && !(block_row && c >= xa && c <= xb);
+            const double gxx = gap(c, G.gx, G.oxd, qx);
+            return valid & !(((gxx * gxx + gy * gy) + gz * gz) * (1.0 - 0x1p-40) > bd);
+        };
+        const bool rm = reach(cx - 1), r0 = reach(cx), rp = reach(cx + 1);
+        if (rm || r0 || rp) {
+            const int lo = rm ? cx - 1 : (r0 ? cx : cx + 1), hi = rp ? cx + 1 : (r0 ? cx : cx - 1);
+            const uint32_t row = cell_lin(G, 0, yy, zz);
+            my_s = cell_start[row + (uint32_t)lo];
+            my_e = cell_start[row + (uint32_t)hi + 1u];
+            if (COUNT) { npts += my_e - my_s; nruns += 1u; }
         }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {                          // (smallest, runner-up, position) over the wave
-        const float o1 = __shfl_xor(m1, off, kWave), o2 = __shfl_xor(m2, off, kWave);
-        const uint32_t op = (uint32_t)__shfl_xor((int)p1, off, kWave);
-        const bool lt = o1 < m1;
-        m2 = fminf(fminf(m2, o2), lt ? m1 : o1);
-        p1 = lt ? op : p1;
-        m1 = fminf(m1, o1);
     }
-    bd = __builtin_huge_val();
-    bi = kNoIndex;
-    // (wave-uniform)  m1 == +inf: an empty cube, OR every fp32 distance overflowed -- as in coop_screen_rows that case takes the exact
-    // scan, where the points compete by their (finite) fp64 distances
-    if (m1 < __builtin_huge_valf() && m2 > m1 * (1.0f + 0x1p-19f) + 0x1p-90f) {   // unique within the fp32 error band: it is the exact winner
-        const float4 W = pts[p1];
-        bd = dist2((double)W.x, (double)W.y, (double)W.z, qx, qy, qz);
-        bi = __float_as_uint(W.w);
-    } else {                                                          // near-ties / duplicates / overflow: exact (d2, index) order decides
-#pragma unroll 1
-        for (int k = 0; k < 9; k++)
-            for (uint32_t p = rs[k] + lane; p < re[k]; p += 64u) {
-                const float4 Pp = pts[p];
-                const double d2 = dist2((double)Pp.x, (double)Pp.y, (double)Pp.z, qx, qy, qz);
-                const uint32_t id = __float_as_uint(Pp.w);
-                if (better(d2, id, bd, bi)) { bd = d2; bi = id; }
+    float thr = (float)bd;
+    if ((double)thr < bd) thr = __uint_as_float(__float_as_uint(thr) + 1u);   // rounded up (bd >= 0; FLT_MAX steps to +inf)
+    thr = thr * (1.0f + 0x1p-19f) + 0x1p-90f;
+    double ld = bd;
+    uint32_t li = bi;
+    // The exact comparison widens the query where it is used, from scalar registers the compiler cannot see through: kept as three fp64
+    // values across the screening they are six more vector registers next to the records in flight, and the kernel's count is the
+    // maximum over all its paths (see nn_grid_coop_kernel).
+    auto exact = [&](const float4 &R) {
+        float sx = qxf, sy = qyf, sz = qzf;
+        asm volatile("" : "+s"(sx), "+s"(sy), "+s"(sz));
+        const double d2 = dist2((double)R.x, (double)R.y, (double)R.z, (double)sx, (double)sy, (double)sz);
+        const uint32_t id = __float_as_uint(R.w);
+        if (better(d2, id, ld, li)) { ld = d2; li = id; }
+    };
+    bool any = false;                                                 // (wave-uniform) some lane met a candidate
+    unsigned long long rows = __builtin_amdgcn_ballot_w64(my_e > my_s);   // the rows with records: bits 0..8
+    while (rows) {                                                    // wave-uniform: kRemRows rows at a time, their loads all issued before the first is consumed
+        uint32_t rs[kRemRows], len[kRemRows];                         // run bounds in scalar registers; rows without records cost nothing
+#pragma unroll
+        for (int j = 0; j < kRemRows; j++) {
+            rs[j] = 0; len[j] = 0;
+            if (rows) {
+                const int k = __builtin_ctzll(rows);
+                rows &= rows - 1;
+                rs[j] = (uint32_t)__builtin_amdgcn_readlane((int)my_s, k);
+                len[j] = (uint32_t)__builtin_amdgcn_readlane((int)my_e, k) - rs[j];
             }
-        wave_argmin(bd, bi);
+        }
+        float4 P[kRemRows];
+#pragma unroll
+        for (int j = 0; j < kRemRows; j++)
+            if (len[j]) P[j] = pts[rs[j] + min(lane, len[j] - 1u)];   // lane beyond the row: the row's last record, masked below
+        uint32_t cm = 0;                                              // bit j: the lane's record of row j is a candidate; bit kRemRows: a long row had one
+#pragma unroll
+        for (int j = 0; j < kRemRows; j++)
+            if (len[j]) {
+                const float dx = P[j].x - qxf, dy = P[j].y - qyf, dz = P[j].z - qzf;
+                const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                cm |= (uint32_t)((lane < len[j]) & (d <= thr)) << j;
+            }
+#pragma unroll
+        for (int j = 0; j < kRemRows; j++)
+            if (len[j] > 64u)                                         // rows of more than 64 records
+                for (uint32_t o = 64u + lane; o < len[j]; o += 64u) {
+                    const float4 R = pts[rs[j] + o];
+                    const float dx = R.x - qxf, dy = R.y - qyf, dz = R.z - qzf;
+                    const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                    if (d <= thr) { exact(R); cm |= 1u << kRemRows; }
+                }
+        if (__builtin_amdgcn_ballot_w64(cm != 0u)) {                  // (wave-uniform) rare: stage 0's point most often stands
+            any = true;
+#pragma unroll
+            for (int j = 0; j < kRemRows; j++)
+                if ((cm >> j) & 1u) exact(P[j]);                      // (set for rows with records only)
+        }
+    }
+    if (any) {
+        wave_argmin(ld, li);
+        bd = ld;
+        bi = li;
     }
 }
 
@@ -1706,8 +1757,8 @@ __device__ __forceinline__ void coop_finish_shells(const GridDesc &G, const floa
     }
 }
 
-// One query per group of 8 lanes, every lane of the wave in step (live = the group has a query): stage 0, then the whole wave on each
-// undecided query's cube in turn, then the 8-lane shell walk for what even the cube leaves open.  Every lane of a group returns its
+// One query per group of 8 lanes, every lane of the wave in step (live = the group has a query): stage 0, then the whole wave on what each
+// undecided query's block leaves of its cube, in turn, then the 8-lane shell walk for what even the cube leaves open.  Every lane of a group returns its
 // query's exact (bd, bi).
 template <bool COUNT, bool NARROW>
 __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start, bool live,
@@ -1724,9 +1775,9 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
         const float bx = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(qxf), g)),
                     by = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(qyf), g)),
                     bz = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(qzf), g));
-        double cbd;
-        uint32_t cbi;
-        wave_cube_search<COUNT>(G, pts, cell_start, bx, by, bz, cbd, cbi, npts, nruns);
+        double cbd = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(bd), g), __builtin_amdgcn_readlane(__double2loint(bd), g));   // stage 0's exact best
+        uint32_t cbi = (uint32_t)__builtin_amdgcn_readlane((int)bi, g);
+        wave_remainder_search<COUNT>(G, pts, cell_start, bx, by, bz, cbd, cbi, npts, nruns);
         if (((threadIdx.x & 63) >> 3) == (uint32_t)(g >> 3)) { bd = cbd; bi = cbi; }
     }
     if (live && undecided) coop_finish_shells<COUNT>(G, pts, cell_start, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
@@ -1743,7 +1794,7 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
 // clamp and the 32-bit offsets: 70 VGPRs, eight + one, 283 + 36).
 // NARROW (chosen per launch on the host: narrow_offsets_fit, gridbuild.hpp) addresses the records, the run bounds, the sorted query and
 // the two results with 32-bit byte offsets from their scalar bases (ld_at / st_at); only the TAIL instantiation of coop_screen_rows takes
-// it -- the cube-first form, the pyramid's stage 0 and the rare paths (exact rescans, the wave's cube, shells) keep 64-bit addresses.
+// it -- the cube-first form, the pyramid's stage 0 and the rare paths (exact rescans, the wave's remainder search, shells) keep 64-bit addresses.
 template <bool COUNT, bool NARROW>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
                                                            const uint32_t *__restrict__ cell_start,
