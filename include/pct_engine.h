@@ -424,7 +424,8 @@ int pct_radius_search_batch(pct_cloud *c, int algo, const float *q, const float 
 /* entries [first, first + n) of the lists of the LAST pct_radius_search_batch on this cloud; idx or d2 may be NULL */
 int pct_radius_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2);
 /* lidar-style crop (camera_sensor.cpp:133-145): indices of all points within r of ONE centre,
- * ascending index order; returns the count through *n_out (may exceed cap; only cap written). */
+ * ascending index order; returns the count through *n_out.  *n_out may exceed cap: the list is then truncated to the cap LOWEST
+ * indices among the hits, ascending (idx_out[0 .. cap) is a prefix of the full list), at every cloud size; cap = 0 only counts. */
 int pct_radius_indices(pct_cloud *c, const float q[3], float r, uint32_t *idx_out, int64_t cap, int64_t *n_out);
 int pct_radius_indices_q64(pct_cloud *c, const double q[3], double r, uint32_t *idx_out, int64_t cap, int64_t *n_out);
 /* the same with the SQUARED radius given exactly (d2 <= r2): with r2 = the d2 a nearest-neighbour query returned it lists every

@@ -62,6 +62,13 @@ def port_lib():
         L.okd_nearest_rangef.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_float]
         L.okd_nearestf.restype = C.c_void_p
         L.okd_nearestf.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        # double-precision queries (kdtree.c:404-457, 537-559 and their x,y,z forms)
+        for n in ("okd_nearest", "okd_nearest3", "okd_nearest_range", "okd_nearest_range3"):
+            getattr(L, n).restype = C.c_void_p
+        L.okd_nearest.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.okd_nearest3.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
+        L.okd_nearest_range.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double]
+        L.okd_nearest_range3.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]
         L.okd_res_free.argtypes = [C.c_void_p]
         L.okd_res_size.argtypes = [C.c_void_p]
         L.okd_res_end.argtypes = [C.c_void_p]

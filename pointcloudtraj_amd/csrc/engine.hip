@@ -2188,9 +2188,17 @@ int pct_radius_indices_r2_q64(pct_cloud *c, const double q[3], double r2, uint32
                                                        c->xids, kExpressIdsCap, c->xout, next_signal(c));
         HIPCHK(hipGetLastError());
         PCTCHK(express_wait(c));
-        const int64_t total = c->xout.host()[0].count, got = std::min<int64_t>(total, cap);
-        std::copy(c->xids.host(), c->xids.host() + std::min<int64_t>(got, kExpressIdsCap), idx_out);
-        std::sort(idx_out, idx_out + got);
+        // the kernel stores its hits in arrival order, all of them (total <= count <= kExpressIdsCap): a truncated list is the `cap`
+        // lowest indices, so every stored hit is sorted before the first `cap` are handed out
+        const int64_t total = c->xout.host()[0].count, stored = std::min<int64_t>(total, kExpressIdsCap), got = std::min<int64_t>(stored, cap);
+        if (got == stored) {
+            std::copy(c->xids.host(), c->xids.host() + stored, idx_out);
+            std::sort(idx_out, idx_out + got);
+        } else {
+            std::vector<uint32_t> all(c->xids.host(), c->xids.host() + stored);
+            std::sort(all.begin(), all.end());
+            std::copy(all.begin(), all.begin() + got, idx_out);
+        }
         *n_out = total;
         return PCT_OK;
     }

@@ -162,6 +162,11 @@ def lib():
         L.pct_radius_count_batch.argtypes = [vp, f32p, f32p, i64, u32p]
         L.pct_radius_count_batch_algo.argtypes = [vp, i32, f32p, f32p, i64, u32p]
         L.pct_radius_indices.argtypes = [vp, f32p, C.c_float, u32p, i64, C.POINTER(i64)]
+        L.pct_nn_batch_q64.argtypes = [vp, f64p, i64, u32p, f64p]
+        L.pct_nn_batch_q64_ties.argtypes = [vp, f64p, i64, u32p, f64p, u32p]
+        L.pct_radius_indices_q64.argtypes = [vp, f64p, C.c_double, u32p, i64, C.POINTER(i64)]
+        L.pct_radius_indices_r2_q64.argtypes = [vp, f64p, C.c_double, u32p, i64, C.POINTER(i64)]
+        L.pct_radius_indices_batch_q64.argtypes = [vp, f64p, f64p, i64, u32p, i64, vp]
         L.pct_radius_crop.argtypes = [vp, vp, C.c_double, C.c_int, i64, vp, vp, vp, C.POINTER(i64)]
         L.pct_cloud_crop_to.argtypes = [vp, vp, C.c_double, vp]
         L.pct_inflate_batch.argtypes = [vp, C.POINTER(InflateParams), f64p, i64, f64p, u32p, f64p]
@@ -540,6 +545,51 @@ class Cloud:
         n = C.c_int64()
         _chk(lib().pct_radius_indices(self._h, _ptr(q), float(radius), _ptr(out), cap, C.byref(n)))
         return out[:min(n.value, cap)].copy(), n.value
+
+    # fp64-query forms (kd_nearest / kd_nearest_range with double positions): exhaustive, d2 = ((dx*dx + dy*dy) + dz*dz) in fp64
+    def nn_q64(self, queries):
+        """pct_nn_batch_q64: (idx uint32 [Q], d2 float64 [Q]) for double queries"""
+        q = np.ascontiguousarray(queries, np.float64).reshape(-1, 3)
+        idx = np.empty(len(q), np.uint32)
+        d2 = np.empty(len(q), np.float64)
+        _chk(lib().pct_nn_batch_q64(self._h, _ptr(q), len(q), _ptr(idx), _ptr(d2)))
+        return idx, d2
+
+    def nn_q64_ties(self, queries, want_ties: bool = True):
+        """pct_nn_batch_q64_ties: (idx, d2, ties uint32 [Q]); ties[i] = points at the minimum where the path taken counts them,
+        0 elsewhere; want_ties = False passes ties = NULL and returns None in its place"""
+        q = np.ascontiguousarray(queries, np.float64).reshape(-1, 3)
+        idx = np.empty(len(q), np.uint32)
+        d2 = np.empty(len(q), np.float64)
+        ties = np.empty(len(q), np.uint32) if want_ties else None
+        _chk(lib().pct_nn_batch_q64_ties(self._h, _ptr(q), len(q), _ptr(idx), _ptr(d2), None if ties is None else _ptr(ties)))
+        return idx, d2, ties
+
+    def _radius_indices_q64(self, fn, center, value, cap):
+        q = np.ascontiguousarray(center, np.float64).reshape(3)
+        cap = int(cap if cap is not None else max(len(self), 1))
+        out = np.empty(max(cap, 1), np.uint32)
+        n = C.c_int64()
+        _chk(fn(self._h, _ptr(q), float(value), _ptr(out), cap, C.byref(n)))
+        return out[:min(n.value, cap)].copy(), n.value
+
+    def radius_indices_q64(self, center, radius, cap=None):
+        """pct_radius_indices_q64: (the min(hits, cap) lowest indices with d2 <= radius * radius, ascending; hits)"""
+        return self._radius_indices_q64(lib().pct_radius_indices_q64, center, radius, cap)
+
+    def radius_indices_r2_q64(self, center, r2, cap=None):
+        """pct_radius_indices_r2_q64: the same with the squared radius given exactly (d2 <= r2)"""
+        return self._radius_indices_q64(lib().pct_radius_indices_r2_q64, center, r2, cap)
+
+    def radius_indices_batch_q64(self, centers, radii, cap_per_query: int):
+        """pct_radius_indices_batch_q64: (ids uint32 [K, cap_per_query] in arrival order, counts int64 [K]); counts[k] >= 0: all hits
+        stored; < 0: -(hits), the row is truncated"""
+        q = np.ascontiguousarray(centers, np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, np.float64), (len(q),)))
+        ids = np.full((len(q), max(int(cap_per_query), 1)), NO_INDEX, np.uint32)
+        counts = np.zeros(len(q), np.int64)
+        _chk(lib().pct_radius_indices_batch_q64(self._h, _ptr(q), _ptr(r), len(q), _ptr(ids), int(cap_per_query), _ptr(counts)))
+        return ids, counts
 
     def radius_crop(self, center, radius, sort_by_distance=False):
         """lidar crop (camera_sensor.cpp:133-145): (indices u32, d2 fp64, cropped cloud float32 [k,3]) of the points within radius"""

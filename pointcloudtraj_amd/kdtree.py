@@ -54,6 +54,11 @@ def lib():
         L.kd_res_item_data.argtypes = [vp]
         L.kdx_set_host_threshold.argtypes = [C.c_int64]
         L.kdx_host_threshold.restype = C.c_int64
+        L.kdx_size.argtypes = [vp]
+        L.kdx_nearestf_batch.argtypes = [vp, vp, C.c_int, vp]
+        L.kdx_range_candidates_batch.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp]
+        L.kdx_range_from_candidates.restype = vp
+        L.kdx_range_from_candidates.argtypes = [vp, fp, C.c_float, vp, C.c_int, C.c_int32]
         _lib = L
     return _lib
 
@@ -117,6 +122,85 @@ class KDTree:
         assert len(out) == self.L.kd_res_size(rs)
         self.L.kd_res_free(rs)
         return np.asarray(out, np.int32)
+
+    def clear(self):
+        self.L.kd_clear(self.h)
+        self.n = 0
+
+    def _one(self, r, what):
+        """(payload-derived id, stored fp64 position) of a one-element result set, which is freed"""
+        if not r:
+            raise RuntimeError(f"{what} returned NULL")
+        pos = np.empty(3, np.float64)
+        d = self.L.kd_res_item(r, pos.ctypes.data_as(C.POINTER(C.c_double)))
+        size = self.L.kd_res_size(r)
+        self.L.kd_res_free(r)
+        assert size == 1
+        return int(d or 0) - 1, pos
+
+    def _drain(self, rs, what, rewind=False):
+        """ids of a range result in ITERATION order; the set is freed.  rewind: iterate, kd_res_rewind, iterate again -- both passes
+        must agree"""
+        if not rs:
+            raise RuntimeError(f"{what} returned NULL")
+        out = []
+        for _ in range(2 if rewind else 1):
+            out.append([])
+            while not self.L.kd_res_end(rs):
+                out[-1].append(int(self.L.kd_res_item_data(rs) or 0) - 1)
+                self.L.kd_res_next(rs)
+            self.L.kd_res_rewind(rs)
+        size = self.L.kd_res_size(rs)
+        self.L.kd_res_free(rs)
+        assert all(o == out[0] for o in out) and len(out[0]) == size
+        return np.asarray(out[0], np.int32)
+
+    def nearest64(self, q):
+        """kd_nearest with a double position: (id, stored fp64 position)"""
+        q = np.ascontiguousarray(q, np.float64).reshape(3)
+        return self._one(self.L.kd_nearest(self.h, q.ctypes.data_as(C.POINTER(C.c_double))), "kd_nearest")
+
+    def nearest3(self, x, y, z):
+        """kd_nearest3: (id, stored fp64 position)"""
+        return self._one(self.L.kd_nearest3(self.h, float(x), float(y), float(z)), "kd_nearest3")
+
+    def range_ids64(self, q, r, rewind=False):
+        """kd_nearest_range with a double position and a double range: ids in iteration order"""
+        q = np.ascontiguousarray(q, np.float64).reshape(3)
+        return self._drain(self.L.kd_nearest_range(self.h, q.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(r)), "kd_nearest_range", rewind)
+
+    def range_ids3(self, x, y, z, r, rewind=False):
+        """kd_nearest_range3: ids in iteration order"""
+        return self._drain(self.L.kd_nearest_range3(self.h, float(x), float(y), float(z), float(r)), "kd_nearest_range3", rewind)
+
+    # batch extensions (include/kdtree/kdtree_ext.h)
+    def nearest_batch(self, q):
+        """kdx_nearestf_batch: int32 [K], the lowest node number among the nearest of each float query, -1 for an empty tree"""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+        out = np.empty(len(q), np.int32)
+        if self.L.kdx_nearestf_batch(self.h, q.ctypes.data, len(q), out.ctypes.data):
+            raise RuntimeError("kdx_nearestf_batch failed")
+        return out
+
+    def range_candidates_batch(self, q, ranges, cap_per_query: int):
+        """kdx_range_candidates_batch against the tree as it is now: (ids uint32 [K, cap_per_query], counts int32 [K]); counts[i] >= 0
+        candidates stored in row i (unordered), < 0: the row is truncated or the batch cannot serve this tree -- ask that query alone"""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(ranges, np.float32), (len(q),)))
+        ids = np.full((len(q), int(cap_per_query)), 0xFFFFFFFF, np.uint32)
+        counts = np.empty(len(q), np.int32)
+        if self.L.kdx_range_candidates_batch(self.h, q.ctypes.data, r.ctypes.data, len(q), ids.ctypes.data, int(cap_per_query), counts.ctypes.data):
+            raise RuntimeError("kdx_range_candidates_batch failed")
+        return ids, counts
+
+    def range_from_candidates(self, q, r, ids, n_snapshot: int):
+        """kdx_range_from_candidates: the ids kd_nearest_rangef(q, r) iterates over NOW, from the candidates `ids` of a snapshot of
+        n_snapshot nodes"""
+        q = np.ascontiguousarray(q, np.float32).reshape(3)
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        rs = self.L.kdx_range_from_candidates(self.h, q.ctypes.data_as(C.POINTER(C.c_float)), C.c_float(r), ids.ctypes.data, len(ids),
+                                              int(n_snapshot))
+        return self._drain(rs, "kdx_range_from_candidates")
 
 
 class KDTreeN:

@@ -12,6 +12,10 @@ What is recorded, and from which implementation:
   kd_general_k.npz
       the same library through kd_create(k) for k = 1, 2, 3 (doubles fp32 cannot hold), 4, 5, 7, 17: nearest ids (the walk's winner
       on ties) and range ids in iteration order.
+  kd_f64_queries.npz
+      the same library as a 3-D tree of 17 000 fp32 nodes on a 0.5 lattice (regenerated from the recorded seed) asked with DOUBLE
+      positions and double ranges (kd_nearest / kd_nearest_range): random doubles, lattice values, cell centres moved by 2^-40, one
+      axis at 1e17, and queries no node is at a finite distance of.
   kd_random_seeds.npz
       the same library on two seeded clouds (seeds 41 and 42: 5,000 uniform points plus 50 duplicates, 500 queries around them):
       nearest ids and d2, and range ids in iteration order for 40 of the queries at radii 1.0, 1.25, ..., 10.75.
@@ -369,6 +373,36 @@ def gen_general_k():
     save("kd_general_k.npz", cases=np.asarray(names), **kw)
 
 
+F64_SEED, F64_N = 947, 17000
+F64_RANGES = (0.0, 0.5, 0.5 + 2.0 ** -30, 1.5, -1.0, 2.5, float("nan"))
+
+
+def gen_f64_queries():
+    """double queries against a 3-D tree of fp32 nodes.  The compiled kdtree.c returned normally for every non-finite query tried
+    here (a NaN, +/-inf, |q| = 1e160: its answer is the root), so none is left out; a range of +inf is left out only for size -- it
+    lists all 17 000 nodes in walk order."""
+    print("double queries on an fp32 3-D tree (reference kdtree.c through kd_create(3) / kd_insert / kd_nearest / kd_nearest_range):")
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import q64_cases as QC
+    pts = QC.cloud(F64_SEED, F64_N, lattice=True)
+    q = np.concatenate([QC.queries(F64_SEED + 1, 112)[0], QC.non_finite_queries()])
+    rad = np.float64([F64_RANGES[i % len(F64_RANGES)] for i in range(len(q))])
+    R = O.RefKDN(3)
+    R.insert(pts.astype(np.float64))
+    nn = R.nearest(q)
+    ids, offs = [], [0]
+    for i in range(len(q)):
+        a = R.range_ids(q[i], float(rad[i]))
+        ids.append(a)
+        offs.append(offs[-1] + len(a))
+    R.close()
+    lowest, _, cnt = QC.nn_reference(pts, q)
+    print(f"    {int(QC.genuine_double(q).sum())} genuine doubles, {int((cnt > 1).sum())} tied queries, "
+          f"{int(((cnt > 1) & (lowest != nn.astype(np.uint32))).sum())} of them won by another node than the lowest index")
+    save("kd_f64_queries.npz", seed_n=np.asarray([F64_SEED, F64_N], np.int64), queries=q, ranges=rad, nn=nn,
+         range_ids=np.concatenate(ids).astype(np.int32), range_offsets=np.asarray(offs, np.int64))
+
+
 def gen_binomials():
     print("binomial table of the reference's Planner/src/binomial_coefs.cpp (compiled into oracle/_ref/libbinomial_ref.so):")
     L = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libbinomial_ref.so"))
@@ -417,12 +451,16 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "general_k":      # only the general-k fixture
         gen_general_k()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "f64_queries":    # only the double queries on the fp32 tree
+        gen_f64_queries()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "random_seeds":   # only the seeded random clouds
         gen_random_seeds()
         sys.exit(0)
     gen_binomials()
     gen_random_seeds()
     gen_general_k()
+    gen_f64_queries()
     gen_nn()
     gen_range()
     gen_api_edges()

@@ -82,6 +82,29 @@ def test_port_general_k_matches_reference(oracle, name):
     P.close()
 
 
+def f64_queries_case(g):
+    """(fp32 nodes, double queries, double ranges, nn, range ids, offsets) of kd_f64_queries.npz; the nodes are regenerated from the seed"""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+    import q64_cases as QC
+    seed, n = (int(v) for v in g["seed_n"])
+    return QC.cloud(seed, n, lattice=True), g["queries"], g["ranges"], g["nn"], g["range_ids"], g["range_offsets"]
+
+
+def test_port_f64_queries_match_reference(oracle):
+    """double positions and double ranges against a 3-D tree of fp32 nodes (kd_nearest / kd_nearest_range, kdtree.c:404-457, 537-559):
+    the restatement returns the compiled reference's node -- its walk's winner on the lattice's exact ties, the root where no
+    distance is finite -- and its range iteration order, negative and NaN ranges included"""
+    pts, q, rad, nn, ids, offs = f64_queries_case(load_golden("kd_f64_queries.npz"))
+    P = oracle.PortKDN(3)
+    P.insert(pts.astype(np.float64))
+    assert np.array_equal(P.nearest(q), nn)
+    for i in range(len(q)):
+        assert np.array_equal(P.range_ids(q[i], float(rad[i])), ids[offs[i]:offs[i + 1]]), f"query {i}"
+    P.close()
+
+
 def test_lattice_reference_misses_boundary_hits():
     """Known quirk (kdtree.c:283): the far side is pruned unless fabs(dx) < range, so points
     at distance exactly == range can be dropped depending on tree shape.  The fixture
