@@ -1511,37 +1511,68 @@ __device__ __forceinline__ void coop_nn_search(const GridDesc &G, const float4 *
 // point of each such row (all loads in flight), one ballot of the records that can beat or tie that best, and only those are compared
 // exactly (wave_remainder_search).  The queries that even the cube does not decide (~1e-4) finish with the 8-lane shell walk as before.
 
-// Is a query still undecided after its 2x2x2 block [xa..xb] x [ya..yb] x [za..zb] gave best distance bd?  (f = the query's fractional
-// position in its cell (cx, cy, cz).)
-__device__ __forceinline__ bool block_leaves_undecided(const GridDesc &G, int cx, int cy, int cz, int xa, int xb, int ya, int yb, int za, int zb,
-                                                       float fx, float fy, float fz, double qx, double qy, double qz, double bd)
+// The 2x2x2 block of cells stage 0 scans for a query: its own cell (cx, cy, cz), its fractional position f in that cell (outside [0, 1) only
+// where the cell coordinate was clamped: a query outside the grid) and, per axis, the neighbour on the side of f < 0.5, clamped to the grid.
+// ONE function for the place where the runs are located and for the exact termination test, which must use the bounds of the block that
+// was scanned: both calls are the same fp32 expressions of (G, q) in the same order (no contraction: -ffp-contract=off), so they agree to
+// the bit -- on the half-cell planes too (tests/test_gpu_stage0_accept.py, case a).
+struct Stage0Block { int cx, cy, cz; float fx, fy, fz; int xa, xb, ya, yb, za, zb; };
+__device__ __forceinline__ void stage0_block(const GridDesc &G, float qxf, float qyf, float qzf, Stage0Block &B)
 {
-    // Quick accept in fp32 (the six fp64 face distances below cost ~6 of the kernel's 120 us): distances to the block's faces in cell
-    // units from the fractional position already at hand, the nearest one with cells behind it shortened by 1/64 cell -- far more
-    // than the fp32 rounding of fx (< 2e-4 cells) plus the exact test's own 1/256 slack -- so whatever passes here passes the exact
-    // test too; the ~2 % of queries in that 1/64-cell band, the undecided ones and queries outside the grid take the exact test.
-    {
-        const float inf = __builtin_huge_valf();
-        float bc = inf;
-        bc = fminf(bc, xa > 0 ? fx + (float)(cx - xa) : inf);
-        bc = fminf(bc, xb < G.gx - 1 ? (float)(xb + 1 - cx) - fx : inf);
-        bc = fminf(bc, ya > 0 ? fy + (float)(cy - ya) : inf);
-        bc = fminf(bc, yb < G.gy - 1 ? (float)(yb + 1 - cy) - fy : inf);
-        bc = fminf(bc, za > 0 ? fz + (float)(cz - za) : inf);
-        bc = fminf(bc, zb < G.gz - 1 ? (float)(zb + 1 - cz) - fz : inf);
-        // only for queries inside the grid (|f| small): the error bound above is for coordinates of at most ~1024 cells
-        if (bc < inf && fmaxf(fmaxf(fabsf(fx), fabsf(fy)), fabsf(fz)) < 2.0f) {
-            const double b = (double)((bc - 0.015625f) * (float)G.hd * 0.999999f);
-            if (b > 0.0 && bd <= b * b) return false;
-        }
-    }
+    B.cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
+    B.cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
+    B.cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
+    B.fx = (qxf - G.ox) * G.inv_h - (float)B.cx; B.fy = (qyf - G.oy) * G.inv_h - (float)B.cy; B.fz = (qzf - G.oz) * G.inv_h - (float)B.cz;
+    B.xa = max(B.fx < 0.5f ? B.cx - 1 : B.cx, 0); B.xb = min(B.fx < 0.5f ? B.cx : B.cx + 1, G.gx - 1);
+    B.ya = max(B.fy < 0.5f ? B.cy - 1 : B.cy, 0); B.yb = min(B.fy < 0.5f ? B.cy : B.cy + 1, G.gy - 1);
+    B.za = max(B.fz < 0.5f ? B.cz - 1 : B.cz, 0); B.zb = min(B.fz < 0.5f ? B.cz : B.cz + 1, G.gz - 1);
+}
+
+// Stage 0's termination test has two parts.
+//
+// The quick accept (stage0_accept_threshold, every query): the distance bc, in cell units, from the query to the nearest face of its block,
+// shortened by 1/64 cell and taken 1e-6 short, as an fp32 length b; the query is decided when its best distance is within b.  The margin
+// is far more than the fp32 rounding of f (< 2e-4 cells for coordinates of at most ~1024 cells, hence the |f| < 2 guard: only queries
+// inside the grid or next to it) plus the exact test's own 1/256 slack, so whatever passes here passes the exact test too.
+//
+// bc comes from f alone: min over the axes of max(f, 1 - f).  The block is the two cells on the query's side, chosen by f < 0.5, so along
+// an axis its faces are f + 1 and 1 - f away (low side) or f and 2 - f (high side): the nearer one is max(f, 1 - f) in either case, and
+// for f in [0, 1) the fp32 values are the ones the face-by-face form computed (f + 1.0f >= 1.0f - f, 2.0f - f >= f).  Where the cell
+// coordinate was clamped the same expression holds: f < 0 (cell 0, low side, the block starts at the grid's edge) leaves the face 1 - f
+// away as the only one with cells behind it, f >= 1 (last cell, high side) the face f away.  A face WITHOUT cells behind it -- the block
+// touches the grid's border on that side, or the grid has one or two cells along the axis -- does not bound the search at all, and the
+// exact test leaves it out; counting it here only makes bc smaller.  So
+//     bc <= the minimum over the faces that have cells behind them  (the form this replaced: six face distances from the block's bounds),
+// the accept bd <= ((bc - 1/64) h 0.999999)^2 is monotone in bc, and: accepted here  =>  accepted by the face-by-face form  =>  accepted
+// by the exact test.  (Where no face has cells behind it the face-by-face form declined and the exact test accepted everything: "the
+// block covers the whole grid".)  A NaN f drops out of the minimum as it dropped out of the face-by-face one; all three NaN give b = NaN
+// and no accept.  What is not accepted here takes the exact test, as the ~2 % of queries in the 1/64-cell band always did: results cannot
+// change (tests/test_stage0_accept_model.py checks the chain of inclusions in the kernel's arithmetic).
+// It needs no cell index and no block bound and is computed BEFORE the record loads: one register (b) crosses the screening where the
+// six bounds (packed into two), the three f and the three cell coordinates did.
+__device__ __forceinline__ float stage0_accept_threshold(const GridDesc &G, float fx, float fy, float fz)
+{
+    const float bc = fminf(fminf(fmaxf(fx, 1.0f - fx), fmaxf(fy, 1.0f - fy)), fmaxf(fz, 1.0f - fz));
+    return fmaxf(fmaxf(fabsf(fx), fabsf(fy)), fabsf(fz)) < 2.0f ? (bc - 0.015625f) * (float)G.hd * 0.999999f : 0.0f;
+}
+
+// The exact test (rare: the 1/64-cell band, the undecided queries, queries outside the grid): is the query still undecided after its
+// block gave best distance bd?  The block's bounds are recomputed from the query (stage0_block) instead of being carried across the
+// screening.
+__device__ __forceinline__ bool block_leaves_undecided(const GridDesc &G, float qxf, float qyf, float qzf, double qx, double qy, double qz, double bd)
+{
+    // (the query is made opaque first: the compiler would otherwise reuse the values of coop_stage0's own call, i.e. carry them across the
+    // screening after all; the copies cost nothing where they stand, inside the rare branch)
+    Stage0Block B;
+    asm volatile("" : "+v"(qxf), "+v"(qyf), "+v"(qzf));
+    stage0_block(G, qxf, qyf, qzf, B);
     double bound = __builtin_huge_val();
-    if (xa > 0) bound = fmin(bound, qx - (G.oxd + (double)xa * G.hd));
-    if (xb < G.gx - 1) bound = fmin(bound, (G.oxd + (double)(xb + 1) * G.hd) - qx);
-    if (ya > 0) bound = fmin(bound, qy - (G.oyd + (double)ya * G.hd));
-    if (yb < G.gy - 1) bound = fmin(bound, (G.oyd + (double)(yb + 1) * G.hd) - qy);
-    if (za > 0) bound = fmin(bound, qz - (G.ozd + (double)za * G.hd));
-    if (zb < G.gz - 1) bound = fmin(bound, (G.ozd + (double)(zb + 1) * G.hd) - qz);
+    if (B.xa > 0) bound = fmin(bound, qx - (G.oxd + (double)B.xa * G.hd));
+    if (B.xb < G.gx - 1) bound = fmin(bound, (G.oxd + (double)(B.xb + 1) * G.hd) - qx);
+    if (B.ya > 0) bound = fmin(bound, qy - (G.oyd + (double)B.ya * G.hd));
+    if (B.yb < G.gy - 1) bound = fmin(bound, (G.oyd + (double)(B.yb + 1) * G.hd) - qy);
+    if (B.za > 0) bound = fmin(bound, qz - (G.ozd + (double)B.za * G.hd));
+    if (B.zb < G.gz - 1) bound = fmin(bound, (G.ozd + (double)(B.zb + 1) * G.hd) - qz);
     if (bound == __builtin_huge_val()) return false;              // the block covers the whole grid
     bound -= G.hd * (1.0 / 256.0);                                // same slack as cube_bound (fp32 cell assignment)
     return !(bound > 0.0 && bd <= bound * bound);
@@ -1554,48 +1585,44 @@ __device__ __forceinline__ bool coop_stage0(const GridDesc &G, const float4 *__r
                                             uint32_t &nruns)
 {
     const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-    const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
-    const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
-    const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
-    const float fx = (qxf - G.ox) * G.inv_h - (float)cx, fy = (qyf - G.oy) * G.inv_h - (float)cy, fz = (qzf - G.oz) * G.inv_h - (float)cz;
-    const int xa = max(fx < 0.5f ? cx - 1 : cx, 0), xb = min(fx < 0.5f ? cx : cx + 1, G.gx - 1);
-    const int ya = max(fy < 0.5f ? cy - 1 : cy, 0), yb = min(fy < 0.5f ? cy : cy + 1, G.gy - 1);
-    const int za = max(fz < 0.5f ? cz - 1 : cz, 0), zb = min(fz < 0.5f ? cz : cz + 1, G.gz - 1);
+    Stage0Block B;
+    stage0_block(G, qxf, qyf, qzf, B);
+    // The threshold is pinned here, opaque to the compiler, which otherwise sinks its arithmetic behind the screening and keeps f and the
+    // cell coordinates in registers across the record loads for it (six registers at the kernel's peak instead of one).
+    float b = stage0_accept_threshold(G, B.fx, B.fy, B.fz);
+    asm volatile("" : "+v"(b));
     uint32_t rs[4], re[4];
     if (G.blocks) {                                               // the corner's entry of the block table: one line, every lane reads it itself
-        const uint32_t u = (uint32_t)(fx < 0.5f ? cx : cx + 1), v = (uint32_t)(fy < 0.5f ? cy : cy + 1), w = (uint32_t)(fz < 0.5f ? cz : cz + 1);
+        const uint32_t u = (uint32_t)(B.fx < 0.5f ? B.cx : B.cx + 1), v = (uint32_t)(B.fy < 0.5f ? B.cy : B.cy + 1), w = (uint32_t)(B.fz < 0.5f ? B.cz : B.cz + 1);
         const uint4 *ent = G.blocks + 2u * ((w * ((uint32_t)G.gy + 1u) + v) * ((uint32_t)G.gx + 1u) + u);
         const uint4 S = ent[0], E = ent[1];
         rs[0] = S.x; rs[1] = S.y; rs[2] = S.z; rs[3] = S.w;
         re[0] = E.x; re[1] = E.y; re[2] = E.z; re[3] = E.w;
         if (COUNT && sub < 4) {
             const int ri = (int)sub;
-            const bool ok = !((ri >> 1) && zb == za) && !((ri & 1) && yb == ya);
+            const bool ok = !((ri >> 1) && B.zb == B.za) && !((ri & 1) && B.yb == B.ya);
             npts += re[ri] - rs[ri]; nruns += ok ? 1u : 0u;
         }
     } else {
-        const int ri = (int)sub & 3;                              // lanes 4..7 repeat lanes 0..3 (same addresses: no extra access)
-        const bool ok = !((ri >> 1) && zb == za) && !((ri & 1) && yb == ya);
-        const uint32_t row = cell_lin(G, 0, (ri & 1) ? yb : ya, (ri >> 1) ? zb : za);
-        const uint32_t a = ld_at<NARROW>(cell_start, row + (uint32_t)xa), b = ld_at<NARROW>(cell_start, row + (uint32_t)xb + 1u);
-        const uint32_t my_s = a, my_e = ok ? b : a;
-        if (COUNT && sub < 4) { npts += my_e - my_s; nruns += ok ? 1u : 0u; }
-        // lane k of the group holds run k's bounds: broadcasts with an immediate pattern, all 8 lanes active (see swz_xor)
-        rs[0] = swz_u32<swz_group_lane(0)>(my_s); re[0] = swz_u32<swz_group_lane(0)>(my_e);
-        rs[1] = swz_u32<swz_group_lane(1)>(my_s); re[1] = swz_u32<swz_group_lane(1)>(my_e);
-        rs[2] = swz_u32<swz_group_lane(2)>(my_s); re[2] = swz_u32<swz_group_lane(2)>(my_e);
-        rs[3] = swz_u32<swz_group_lane(3)>(my_s); re[3] = swz_u32<swz_group_lane(3)>(my_e);
+        // One load instruction for the eight run bounds: lane k < 4 of the group fetches run k's start, lane 4 + k its end -- the start's
+        // own address where the row is disabled (it coincides with another at the grid's border), which makes the run empty.
+        const int ri = (int)sub & 3;
+        const bool ok = !((ri >> 1) && B.zb == B.za) && !((ri & 1) && B.yb == B.ya);
+        const uint32_t row = cell_lin(G, 0, (ri & 1) ? B.yb : B.ya, (ri >> 1) ? B.zb : B.za);
+        const uint32_t mine = ld_at<NARROW>(cell_start, row + ((sub & 4u) && ok ? (uint32_t)B.xb + 1u : (uint32_t)B.xa));
+        // broadcasts with an immediate pattern, all 8 lanes active (see swz_xor)
+        rs[0] = swz_u32<swz_group_lane(0)>(mine); re[0] = swz_u32<swz_group_lane(4)>(mine);
+        rs[1] = swz_u32<swz_group_lane(1)>(mine); re[1] = swz_u32<swz_group_lane(5)>(mine);
+        rs[2] = swz_u32<swz_group_lane(2)>(mine); re[2] = swz_u32<swz_group_lane(6)>(mine);
+        rs[3] = swz_u32<swz_group_lane(3)>(mine); re[3] = swz_u32<swz_group_lane(7)>(mine);
+        if (COUNT) {
+            const uint32_t my_e = swz_u32<swz_xor(4)>(mine);      // lane k < 4: its run's end, from lane 4 + k
+            if (sub < 4) { npts += my_e - mine; nruns += ok ? 1u : 0u; }
+        }
     }
-    // The block's six cell bounds (< 1024 each: the grid has at most 1024 cells per axis) cross the screening packed into two registers,
-    // opaque to the compiler so that it cannot keep the six: with the shared tail slot's three record registers and its position the
-    // kernel would otherwise pass 72 VGPRs, and the scheduler then issues the nine record loads in groups of two -- four dependent
-    // round trips (72 is the ceiling of the kernel's 7 waves per SIMD, see nn_grid_coop_kernel).
-    uint32_t pk0 = (uint32_t)xa | ((uint32_t)xb << 10) | ((uint32_t)ya << 20), pk1 = (uint32_t)yb | ((uint32_t)za << 10) | ((uint32_t)zb << 20);
-    asm volatile("" : "+v"(pk0), "+v"(pk1));
     coop_screen_rows<4, 2, true, NARROW>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
-    asm volatile("" : "+v"(pk0), "+v"(pk1));
-    return block_leaves_undecided(G, cx, cy, cz, (int)(pk0 & 1023u), (int)((pk0 >> 10) & 1023u), (int)(pk0 >> 20), (int)(pk1 & 1023u),
-                                  (int)((pk1 >> 10) & 1023u), (int)(pk1 >> 20), fx, fy, fz, qx, qy, qz, bd);
+    if (b > 0.0f && bd <= (double)b * (double)b) return false;    // the quick accept
+    return block_leaves_undecided(G, qxf, qyf, qzf, qx, qy, qz, bd);
 }
 
 // What the 2x2x2 block B of a WAVE-UNIFORM query leaves of the 3x3x3 cube around the query's cell, searched by all 64 lanes from stage 0's
@@ -1788,10 +1815,13 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
 // first use.  Headline step 0.1198-0.1210 -> 0.1163-0.1179 ms (6 waves: 0.122, 5: 0.134; profiles/r03_ab_occupancy_cap.txt).  Raising
 // only the minimum (round 2's "7 waves" experiment) never changed the code: the scheduler still aimed for 8.
 // With the shared tail slot (coop_screen_rows<4, 2, true>) nine loads are in flight; whatever is added to stage 0 has to be checked against
-// that ceiling in the compiler's resource remarks AND in the order of the loads in the ISA (profiles/r05_stage0_asm.txt): NARROW 69 VGPRs,
-// all nine record loads before the first s_waitcnt vmcnt (vmcnt(8)), 256 vector instructions from the entry to the tail_loops branch and
-// 20 in the fold; wide 70 VGPRs, eight loads before vmcnt(7) and the ninth behind it, 267 + 20 (before the swizzle folds, the wrapping
-// clamp and the 32-bit offsets: 70 VGPRs, eight + one, 283 + 36).
+// that ceiling in the compiler's resource remarks AND in the order of the loads in the ISA (profiles/r07_stage0_asm.txt): NARROW 68 VGPRs,
+// all nine record loads before the first s_waitcnt vmcnt (vmcnt(8)), 270 vector instructions from the entry to the tail_loops branch, 20
+// in the fold and 28 from there to the ballot of the undecided for a query the quick accept decides; wide 70 VGPRs, all nine loads before
+// vmcnt(8) as well, 280 + 20 + 29.  (Before the quick accept moved in front of the loads and the run bounds into one load instruction:
+// 69 VGPRs, 256 + 20 + 81, r05_stage0_asm.txt; before the swizzle folds, the wrapping clamp and the 32-bit offsets: 70 VGPRs, eight loads
+// and the ninth behind vmcnt(7), 283 + 36.)  Built for 8 waves the kernel still spills (64 VGPRs, 12-16 bytes of scratch): the count is the
+// maximum over all its paths, and stage 0 is no longer the one that sets it.
 // NARROW (chosen per launch on the host: narrow_offsets_fit, gridbuild.hpp) addresses the records, the run bounds, the sorted query and
 // the two results with 32-bit byte offsets from their scalar bases (ld_at / st_at); only the TAIL instantiation of coop_screen_rows takes
 // it -- the cube-first form, the pyramid's stage 0 and the rare paths (exact rescans, the wave's remainder search, shells) keep 64-bit addresses.
