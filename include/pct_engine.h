@@ -18,6 +18,8 @@
  *                           (+ checkRadius :656-659, checkTrajPtCol :412-416), batched over the loops at
  *                           :829-835 (SafeRegionEvaluate) and :958-974 (treeRepair)
  *   pct_bezier_check        checkSafeTrajectory/getPosFromBezier  Planner/src/sim_planning_demo.cpp:715-781
+ *   pct_bezier_check_batch  the same check for a set of candidate trajectories over one map in one call (the loop a caller of
+ *                           checkSafeTrajectory would write around its candidates; variants as in Planner/src/traj_postprocessing.cpp)
  *   pct_cloud_ring_index +  the per-frame rebuild of the search tree: rcvPointCloudCallBack -> setInput
  *   pct_cloud_append_aos    Planner/src/sim_planning_demo.cpp:159-167 -> Planner/src/corridor_finder.cpp:93-99 (rolling map, config C5)
  *   pct_ctrl_points_check   the containment the optimizer enforces on the control points, Planner/src/traj_optimizer.cpp:624-648,
@@ -89,6 +91,37 @@
  * offsets / total still valid.  Device form: d_offsets[Q + 1] is always written; the lists are written only when
  * d_offsets[Q] <= cap -- the kernels test this on the device and leave d_idx / d_d2 untouched otherwise, the caller reads
  * d_offsets[Q] to find out.  There is no max_nn: a bounded list is pct_knn_batch cut at r*r.
+ *
+ * Batched Bezier check (pct_bezier_check_batch*): pct_bezier_check for B candidate trajectories against one cloud -- the same corridor
+ * under several time allocations, evasive variants, a fan of motion primitives, the committed trajectories of several vehicles.  Both
+ * forms share one contract, identical on a plain, cell-indexed, rolling-map or small host-mapped cloud.  The batch is packed (struct
+ * pct_bezier_batch): the segments of all trajectories one after another, trajectory b = segments [seg_offsets[b], seg_offsets[b+1]).
+ * Trajectory b is evaluated exactly as pct_bezier_check(c, traj_b, p, t_start[b], stop_time, dt, .., cap, ..) evaluates it: the same
+ * segment search with its strict `>`, the same sequential fp64 additions t += dt and t_accu += dt, the same Bernstein arithmetic, the
+ * same inflation.  Its verdict (struct pct_traj_verdict): nsamples is the UNCLIPPED count, the number of samples the reference's loops
+ * would evaluate; the evaluated samples are the first m_b = min(nsamples_b, cap, 4096), and first_hit, min_radius and min_sample cover
+ * exactly those: first_hit is the first of them with radius < 0 (-1 = none), min_radius the smallest radius among them (folded with <
+ * in ascending sample order; +inf when nothing was evaluated) and min_sample the LOWEST sample index that attains it (-1 when nothing
+ * was evaluated) -- what ranks the collision-free candidates by clearance.  A radius is never NaN for finite parameters.  Sample lists,
+ * a CSR like the radius search's: offsets[b] = sum of m_a over a < b, offsets has B + 1 entries and offsets[B] is the total; row b of
+ * pos / radius / d2 / idx is entries [offsets[b], offsets[b+1]), each bit-identical to what pct_bezier_check writes for that sample --
+ * PCT_NO_INDEX / +inf / max_radius - search_margin included where the early-out fired or the cloud is empty.  The lists are written
+ * only when offsets[B] <= list_cap; otherwise nothing is written into them, and nothing behind offsets[B] is ever touched: the caller
+ * compares offsets[B] with list_cap.  Host form: the verdicts are always complete; the library sizes its own workspaces and waits
+ * once on the host for the total; offsets == NULL means no lists are wanted; an empty cloud gives PCT_OK with the early-out radius
+ * everywhere (first_hit = -1, min_sample = 0); on a rolling map an append in flight is finished first and the overflow-queue overrun
+ * paragraph below applies as to the other host forms.  Device form: asynchronous on `stream`, no host synchronisation and no allocation
+ * inside, ordered after the cloud's mutations like the other *_dev forms; the struct is read on the host, its pointers are device
+ * memory; the caller reserves first (pct_cloud_reserve_queries(c, list_cap); list_cap must not exceed the reserved size) and the
+ * lists may all be NULL; d_offsets[B + 1] and every nsamples are always written, and when d_offsets[B] > list_cap the other verdict
+ * fields are set to -2, -2, NaN ("not evaluated").  PCT_ERR_INVALID, before any launch and with nothing written: a NULL required
+ * pointer, B < 0, cap <= 0, dt not > 0, and in the host form seg_offsets not starting at 0 or not strictly ascending, an order outside
+ * 0..12, a row_stride below 3 * (order + 1).  B == 0: PCT_OK, and the only thing written is offsets[0] = 0 when offsets were given.
+ * The enumeration always ends on the device: the host form returns PCT_ERR_INVALID for a trajectory whose
+ * min(stop_time, sum of its seg_time) / dt is not <= 2^20 (a batch is for candidate sets, not for logs); the device form, which
+ * cannot see the data, bounds each trajectory's loop at 2^20 samples (plus one per segment), and a trajectory that reaches the bound,
+ * has an order outside 0..12 or a row too short for it, or whose segment range is empty, descending or outside [0, seg_offsets[B]]
+ * reports nsamples = -1, contributes no sample and has none of its rows read.
  *
  * Rolling-map index and the overflow-queue overrun: the append kernels flag a queue that would overrun (ring.hpp: cannot happen by the
  * queue's sizing; a point is then missing from the table although it is in the window).  The host forms of the calls that search the
@@ -516,6 +549,30 @@ int pct_bezier_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflat
                      int64_t *first_hit, int64_t *nsamples,
                      int64_t cap, double *pos, double *radius, double *d2, uint32_t *idx);
 
+/* The same check for B trajectories in one call (contract: top of this file, "Batched Bezier check").  Host pointers in the host
+ * form, device pointers in the device form. */
+typedef struct pct_bezier_batch {
+    const double  *polycoef;     /* total_seg rows of row_stride doubles, the trajectories one after another; row layout as pct_bezier_traj */
+    int64_t        row_stride;   /* >= 3 * (largest order + 1) */
+    const double  *seg_time;     /* total_seg */
+    const int32_t *orders;       /* total_seg, each 0..12 */
+    const int32_t *seg_offsets;  /* B + 1, seg_offsets[0] = 0, strictly ascending: trajectory b = segments [seg_offsets[b], seg_offsets[b+1]) */
+    const double  *t_start;      /* B, or NULL = 0.0 for every trajectory */
+    int64_t        B;
+} pct_bezier_batch;
+
+typedef struct pct_traj_verdict {   /* 32 bytes */
+    int64_t nsamples;     /* the UNCLIPPED count, as pct_bezier_check reports it */
+    int64_t first_hit;    /* first evaluated sample with radius < 0, -1 = none */
+    int64_t min_sample;   /* LOWEST evaluated sample index that attains min_radius, -1 when nothing was evaluated */
+    double  min_radius;   /* smallest radius over the evaluated samples, +inf when nothing was evaluated */
+} pct_traj_verdict;
+
+int pct_bezier_check_batch(pct_cloud *c, const pct_bezier_batch *batch, const pct_inflate_params *p, double stop_time, double dt,
+                           int64_t cap, pct_traj_verdict *verdict /* B */,
+                           int64_t *offsets /* B + 1, may be NULL */, int64_t list_cap,
+                           double *pos, double *radius, double *d2, uint32_t *idx /* list_cap entries each (pos x3), any may be NULL */);
+
 /* Control-point check (SURVEY.md 3.3, config C5's build extension): the threshold test of checkTrajPtCol
  * (Planner/src/corridor_finder.cpp:412-416) applied to the raw control points of the committed trajectory in world units --
  * control point j of segment i is polycoef[i][d*(n+1)+j] * seg_time[i] (layout Planner/src/traj_optimizer.cpp:739-751), the
@@ -557,6 +614,13 @@ int pct_inflate_batch_dev(pct_cloud *c, const pct_inflate_params *p, const doubl
 int pct_bezier_check_dev(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflate_params *p, double t_start, double stop_time, double dt,
                          int64_t cap, double *d_pos, double *d_radius, double *d_d2, uint32_t *d_idx, long long *d_first_hit, int32_t *d_nsamples,
                          void *stream);
+/* pct_bezier_check_batch on device buffers ("Batched Bezier check" at the top of this file): d_batch_fields is a struct on the host
+ * whose pointers are device memory; d_verdict[B] and d_offsets[B + 1] are required, the lists (list_cap entries each, d_pos x3) may
+ * be NULL.  Reserve list_cap first (pct_cloud_reserve_queries). */
+int pct_bezier_check_batch_dev(pct_cloud *c, const pct_bezier_batch *d_batch_fields /* struct on the host, its pointers on the device */,
+                               const pct_inflate_params *p, double stop_time, double dt, int64_t cap, pct_traj_verdict *d_verdict,
+                               int64_t *d_offsets /* B + 1, required */, int64_t list_cap,
+                               double *d_pos, double *d_radius, double *d_d2, uint32_t *d_idx, void *stream);
 /* Exchange step of a sharded cloud (one process per GPU): between all_reduce(min) on the squared distances and all_reduce(min) on
  * the indices, a rank offers its global index only where its own d2 equals the reduced minimum (and is finite), INT32_MAX
  * elsewhere -- so the second reduction returns the lowest global index among the ranks that tie.  Device pointers, async on

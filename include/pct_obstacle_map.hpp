@@ -252,6 +252,22 @@ public:
         return fh >= 0;
     }
 
+    // The same check for a set of candidates over this map in ONE call (pct_engine.h, paragraph "Batched Bezier check"): the same
+    // corridor under several time allocations, evasive variants, a fan of primitives.  Same dt = 0.02 and cap = 4096 as
+    // checkSafeTrajectory; candidates.t_start = each candidate's t_now (NULL: 0).  verdicts[b]: the unclipped sample count, the first
+    // colliding sample (-1: none) and -- what ranks the free candidates -- the smallest radius with the lowest sample that attains it.
+    // Returns the number of colliding candidates.
+    int64_t checkSafeTrajectories(const pct_bezier_batch &candidates, double stop_time, std::vector<pct_traj_verdict> &verdicts)
+    {
+        verdicts.resize((size_t)(candidates.B > 0 ? candidates.B : 0));
+        check(pct_bezier_check_batch(cloud_, &candidates, &prm_, stop_time, 0.02, 4096, verdicts.data(), nullptr, 0, nullptr, nullptr, nullptr,
+                                     nullptr),
+              "pct_bezier_check_batch");
+        int64_t colliding = 0;
+        for (const pct_traj_verdict &v : verdicts) colliding += v.first_hit >= 0 ? 1 : 0;
+        return colliding;
+    }
+
     // SURVEY 3.3 (config C5's build extension): the same threshold test on the raw control points of the committed trajectory
     // (control point j of segment i = poly_coeff[i][d*(n+1)+j] * T_i, the point traj_optimizer.cpp:624-648 keeps inside sphere i)
     bool checkControlPoints(const double *poly_coeff, int64_t row_stride, const double *seg_time, const int32_t *orders,

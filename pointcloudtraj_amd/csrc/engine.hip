@@ -39,6 +39,7 @@
 #include "knn.hpp"
 #include "rsearch.hpp"
 #include "ring_search.hpp"
+#include "bezier_batch.hpp"
 
 using namespace pct;
 using pct_host::pow2_at_least;
@@ -282,6 +283,12 @@ struct pct_cloud {
     DevBuf<int> d_orders, d_nsamples;
     DevBuf<long long> d_first_hit;
     size_t seg_cap = 0;
+    // batched Bezier check, host form (bezier_batch.hpp): device copies of seg_offsets / t_start, the offsets and the verdicts, B + 1
+    // entries each (grow-only)
+    DevBuf<int32_t> bb_segoff;
+    DevBuf<double> bb_tstart;
+    DevBuf<long long> bb_off;
+    DevBuf<pct_traj_verdict> bb_verdict;
     // measurement
     hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the whole batch (all kernels of one query call)
     hipEvent_t ev2 = nullptr, ev3 = nullptr;    // around the batch's dominant kernel only (aliases of the ring's current pair)
@@ -2523,6 +2530,132 @@ int pct_bezier_check_dev(pct_cloud *c, const pct_bezier_traj *traj, const pct_in
     PCTCHK(inflate_dev(c, p, cap, s, pos, nullptr, d_radius, d_idx, d_d2));
     first_hit_kernel<<<1, 256, 0, s>>>(d_radius, d_nsamples, (int)cap, d_first_hit);
     HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// ---- the sampled Bezier check for B trajectories at once (bezier_batch.hpp; contract: pct_engine.h, "Batched Bezier check") ------
+namespace {
+// nsamples_b and m_b of every trajectory, then the offsets: one lane per trajectory, one block-scan over the B + 1 entries
+int bb_count_scan(const BbDesc &D, pct_traj_verdict *d_verdict, long long *d_offsets, hipStream_t s)
+{
+    bb_count_kernel<<<ceil_div(D.B + 1, 256), 256, 0, s>>>(D, d_verdict, d_offsets);
+    scan_tile_sums_kernel<uint64_t><<<1, 256, 0, s>>>(reinterpret_cast<uint64_t *>(d_offsets), (uint32_t)(D.B + 1), ScanDoneNothing{});
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// fill, evaluate and inflate `nslots` slots, then fold every row into its verdict.  Positions, radii, indices and distances stay in the
+// cloud's query workspaces (nslots <= c->qcap); (segment, t) per slot borrow d_count / d_r2, which only the radius counts use.
+int bb_check_slots(pct_cloud *c, const BbDesc &D, const pct_inflate_params *p, const long long *d_offsets, long long list_cap, int64_t nslots,
+                   pct_traj_verdict *d_verdict, hipStream_t s)
+{
+    if (nslots > 0) {
+        const bool pad = c->count > 0;
+        bb_fill_kernel<<<ceil_div(D.B, 256), 256, 0, s>>>(D, d_offsets, list_cap, c->d_count, c->d_r2);
+        bb_eval_kernel<<<ceil_div(nslots, 128), 128, 0, s>>>(D, d_offsets, list_cap, nslots, c->d_count, c->d_r2, pad ? c->x : nullptr, pad ? c->y : nullptr,
+                                                             pad ? c->z : nullptr, c->d_pts64);
+        PCTCHK(inflate_dev(c, p, nslots, s));
+    }
+    bb_verdict_kernel<<<ceil_div(D.B, 4), 256, 0, s>>>(D.B, d_offsets, list_cap, c->d_radius, d_verdict);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+}  // namespace
+
+int pct_bezier_check_batch(pct_cloud *c, const pct_bezier_batch *batch, const pct_inflate_params *p, double stop_time, double dt, int64_t cap,
+                           pct_traj_verdict *verdict, int64_t *offsets, int64_t list_cap, double *pos, double *radius, double *d2, uint32_t *idx)
+{
+    if (!c || !batch || !p || batch->B < 0 || cap <= 0 || !(dt > 0) || list_cap < 0) return fail(PCT_ERR_INVALID, "bad bezier_check_batch arguments");
+    const int64_t B = batch->B;
+    if (B > 0 && (!batch->polycoef || !batch->seg_time || !batch->orders || !batch->seg_offsets || !verdict))
+        return fail(PCT_ERR_INVALID, "bad bezier_check_batch arguments: a null array");
+    if (B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bezier_check_batch: B = %lld", (long long)B);
+    if (B > 0 && batch->seg_offsets[0] != 0) return fail(PCT_ERR_INVALID, "bezier_check_batch: seg_offsets[0] = %d, not 0", (int)batch->seg_offsets[0]);
+    for (int64_t b = 0; b < B; b++) {
+        const int32_t s0 = batch->seg_offsets[b], s1 = batch->seg_offsets[b + 1];
+        if (s1 <= s0) return fail(PCT_ERR_INVALID, "bezier_check_batch: seg_offsets not strictly ascending at trajectory %lld", (long long)b);
+        double sum = 0.0;
+        for (int32_t i = s0; i < s1; i++) {
+            const int32_t o = batch->orders[i];
+            if (o < 0 || o > kMaxBezierOrder || 3 * (int64_t)(o + 1) > batch->row_stride)
+                return fail(PCT_ERR_INVALID, "bezier_check_batch: segment %d: order %d unsupported", (int)i, (int)o);
+            sum += batch->seg_time[i];
+        }
+        // the enumeration must end on the device: a batch for candidate sets, not for logs
+        if (!(std::min(stop_time, sum) / dt <= (double)kBbLoopBound))
+            return fail(PCT_ERR_INVALID, "bezier_check_batch: trajectory %lld would enumerate more than 2^20 samples", (long long)b);
+    }
+    if (cap > kBezierCapMax) cap = kBezierCapMax;
+    if (B == 0) {
+        if (offsets) offsets[0] = 0;
+        return PCT_OK;
+    }
+    PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
+    hipStream_t s = g_stream;
+    const int32_t total_seg = batch->seg_offsets[B];
+    const pct_bezier_traj all{ batch->polycoef, batch->row_stride, batch->seg_time, batch->orders, total_seg };
+    PCTCHK(bezier_stage_coef(c, &all, s, false));
+    if ((size_t)B + 1 > c->bb_off.capacity()) {
+        HIPCHK(hipStreamSynchronize(s));
+        const size_t n = pow2_at_least<size_t>(256, (size_t)B + 1);
+        PCTCHK(c->bb_segoff.reserve(n));
+        PCTCHK(c->bb_tstart.reserve(n));
+        PCTCHK(c->bb_verdict.reserve(n));
+        PCTCHK(c->bb_off.reserve(n));            // last: its capacity is the test above
+    }
+    HIPCHK(hipMemcpyAsync(c->bb_segoff, batch->seg_offsets, sizeof(int32_t) * (B + 1), hipMemcpyHostToDevice, s));
+    if (batch->t_start) HIPCHK(hipMemcpyAsync(c->bb_tstart, batch->t_start, sizeof(double) * B, hipMemcpyHostToDevice, s));
+    const BbDesc D{ c->d_coef, (long long)batch->row_stride, c->d_segtime, c->d_orders, c->bb_segoff, batch->t_start ? c->bb_tstart.get() : nullptr,
+                    (long long)B, stop_time, dt, (long long)cap };
+    PCTCHK(bb_count_scan(D, c->bb_verdict, c->bb_off, s));
+    std::vector<int64_t> own;
+    if (!offsets) { own.resize((size_t)B + 1); offsets = own.data(); }
+    HIPCHK(hipMemcpyAsync(offsets, c->bb_off, sizeof(int64_t) * (B + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));             // the one host read: the total sizes the workspaces and the launches
+    const int64_t total = offsets[B];
+    if (total > 0x7FFFFFFFll) return fail(PCT_ERR_CAPACITY, "bezier_check_batch: %lld samples in one batch, more than 2^31 - 1", (long long)total);
+    PCTCHK(pct_cloud_reserve_queries(c, total));
+    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {
+        PCTCHK(bb_check_slots(c, D, p, c->bb_off, total, total, c->bb_verdict, s));
+        HIPCHK(hipMemcpyAsync(verdict, c->bb_verdict, sizeof(pct_traj_verdict) * B, hipMemcpyDeviceToHost, s));
+        if (own.empty() && total > 0 && total <= list_cap) {
+            if (pos) HIPCHK(hipMemcpyAsync(pos, c->d_pts64, sizeof(double) * 3 * total, hipMemcpyDeviceToHost, s));
+            if (radius) HIPCHK(hipMemcpyAsync(radius, c->d_radius, sizeof(double) * total, hipMemcpyDeviceToHost, s));
+            if (d2) HIPCHK(hipMemcpyAsync(d2, c->d_d2, sizeof(double) * total, hipMemcpyDeviceToHost, s));
+            if (idx) HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        return PCT_OK;
+    }));
+    return PCT_OK;
+}
+
+int pct_bezier_check_batch_dev(pct_cloud *c, const pct_bezier_batch *d_batch_fields, const pct_inflate_params *p, double stop_time, double dt,
+                               int64_t cap, pct_traj_verdict *d_verdict, int64_t *d_offsets, int64_t list_cap, double *d_pos, double *d_radius,
+                               double *d_d2, uint32_t *d_idx, void *stream)
+{
+    const pct_bezier_batch *bt = d_batch_fields;
+    if (!c || !bt || !p || bt->B < 0 || bt->B >= 0x7FFFFFFFll || cap <= 0 || !(dt > 0) || list_cap < 0 || !d_offsets)
+        return fail(PCT_ERR_INVALID, "bad bezier_check_batch_dev arguments");
+    if (bt->B > 0 && (!bt->polycoef || !bt->seg_time || !bt->orders || !bt->seg_offsets || !d_verdict))
+        return fail(PCT_ERR_INVALID, "bad bezier_check_batch_dev arguments: a null array");
+    if (list_cap > c->qcap) return fail(PCT_ERR_INVALID, "list_cap %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)list_cap, (long long)c->qcap);
+    if (cap > kBezierCapMax) cap = kBezierCapMax;
+    hipStream_t s = (hipStream_t)stream;
+    if (bt->B == 0) {
+        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
+        return PCT_OK;
+    }
+    PCTCHK(order_after_mutations(c, s));
+    const BbDesc D{ bt->polycoef, (long long)bt->row_stride, bt->seg_time, bt->orders, bt->seg_offsets, bt->t_start, (long long)bt->B, stop_time, dt, (long long)cap };
+    long long *off = reinterpret_cast<long long *>(d_offsets);
+    PCTCHK(bb_count_scan(D, d_verdict, off, s));
+    // the total stays on the device: the per-slot launches are sized from list_cap and every kernel guards on offsets[B]
+    PCTCHK(bb_check_slots(c, D, p, off, list_cap, list_cap, d_verdict, s));
+    if (list_cap > 0 && (d_pos || d_radius || d_d2 || d_idx)) {
+        bb_export_kernel<<<ceil_div(list_cap, 256), 256, 0, s>>>(bt->B, off, list_cap, c->d_pts64, c->d_radius, c->d_d2, c->d_idx, d_pos, d_radius, d_d2, d_idx);
+        HIPCHK(hipGetLastError());
+    }
     return PCT_OK;
 }
 

@@ -48,7 +48,50 @@ class BezierTraj(C.Structure):
                 ("orders", C.POINTER(C.c_int32)), ("nseg", C.c_int32)]
 
 
-DEPTH_Z, DEPTH_RANGE = 0, 1             # enum pct_depth_metric: a pixel holds the depth along the optical axis / the range along the ray
+class BezierBatch(C.Structure):
+    """pct_bezier_batch: B trajectories packed one after another (include/pct_engine.h, paragraph "Batched Bezier check").  Host
+    pointers for Cloud.bezier_check_batch (engine.pack_trajectories fills them), device pointers for bezier_check_batch_device."""
+    _fields_ = [("polycoef", C.c_void_p), ("row_stride", C.c_int64), ("seg_time", C.c_void_p), ("orders", C.c_void_p),
+                ("seg_offsets", C.c_void_p), ("t_start", C.c_void_p), ("B", C.c_int64)]
+
+
+class TrajVerdict(C.Structure):
+    """pct_traj_verdict, 32 bytes"""
+    _fields_ = [("nsamples", C.c_int64), ("first_hit", C.c_int64), ("min_sample", C.c_int64), ("min_radius", C.c_double)]
+
+
+VERDICT_DTYPE = np.dtype([("nsamples", np.int64), ("first_hit", np.int64), ("min_sample", np.int64), ("min_radius", np.float64)])
+
+
+def pack_trajectories(trajectories, t_start=None):
+    """A list of (polycoef, seg_time, orders) -> (BezierBatch, arrays): the rows one after another, padded with zeros to a common
+    row_stride; t_start: B start times or None (0.0 for every trajectory).  `arrays` = dict(polycoef, seg_time, orders, seg_offsets,
+    t_start) are the numpy arrays the struct points into: keep them alive while it is used."""
+    trajs = [(np.asarray(c, np.float64), np.asarray(t, np.float64).reshape(-1), np.asarray(o, np.int32).reshape(-1)) for c, t, o in trajectories]
+    for c, t, o in trajs:
+        if c.ndim != 2 or len(c) != len(t) or len(t) != len(o):
+            raise ValueError("a trajectory is (polycoef [nseg, row_stride], seg_time [nseg], orders [nseg])")
+    stride = max([c.shape[1] for c, _, _ in trajs], default=3)
+    nseg = [len(t) for _, t, _ in trajs]
+    seg_offsets = np.zeros(len(trajs) + 1, np.int32)
+    seg_offsets[1:] = np.cumsum(nseg)
+    coef = np.zeros((int(seg_offsets[-1]), stride), np.float64)
+    for (c, _, _), a in zip(trajs, seg_offsets):
+        coef[a:a + len(c), :c.shape[1]] = c
+    seg_time = np.concatenate([t for _, t, _ in trajs]) if trajs else np.zeros(0)
+    orders = np.concatenate([o for _, _, o in trajs]) if trajs else np.zeros(0, np.int32)
+    arrays = dict(polycoef=coef, seg_time=np.ascontiguousarray(seg_time, np.float64), orders=np.ascontiguousarray(orders, np.int32),
+                  seg_offsets=seg_offsets, t_start=None)
+    if t_start is not None:
+        arrays["t_start"] = np.ascontiguousarray(t_start, np.float64).reshape(-1)
+        if len(arrays["t_start"]) != len(trajs):
+            raise ValueError("one t_start per trajectory")
+    b = BezierBatch(coef.ctypes.data, stride, arrays["seg_time"].ctypes.data, arrays["orders"].ctypes.data, seg_offsets.ctypes.data,
+                    None if t_start is None else arrays["t_start"].ctypes.data, len(trajs))
+    return b, arrays
+
+
+DEPTH_Z, DEPTH_RANGE = 0, 1            # enum pct_depth_metric: a pixel holds the depth along the optical axis / the range along the ray
 
 
 class DepthView(C.Structure):
@@ -176,6 +219,10 @@ def lib():
         L.pct_inflate_batch_dev.argtypes = [vp, C.POINTER(InflateParams), vp, i64, vp, vp, vp, vp]
         L.pct_bezier_check_dev.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.c_double, C.c_double, i64,
                                            vp, vp, vp, vp, vp, vp, vp]
+        L.pct_bezier_check_batch.argtypes = [vp, C.POINTER(BezierBatch), C.POINTER(InflateParams), C.c_double, C.c_double, i64, vp, vp, i64,
+                                             f64p, f64p, f64p, u32p]
+        L.pct_bezier_check_batch_dev.argtypes = [vp, C.POINTER(BezierBatch), C.POINTER(InflateParams), C.c_double, C.c_double, i64, vp, vp, i64,
+                                                 vp, vp, vp, vp, vp]
         L.pct_radius_count_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp]
         L.pct_cloud_reserve_queries.argtypes = [vp, i64]
         L.pct_plan_create_nn.argtypes = [vp, i32, i64, C.POINTER(vp)]
@@ -631,6 +678,39 @@ class Cloud:
         n = min(ns.value, cap)
         return dict(first_hit=fh.value, n=ns.value, pos=pos[:n], radius=rad[:n], d2=d2[:n], idx=idx[:n])
 
+    def bezier_check_batch(self, params: InflateParams, trajectories, t_start=None, stop_time=2.0, dt=0.02, cap=4096, want_lists=False):
+        """pct_bezier_check_batch: the sampled check for a list of (polycoef, seg_time, orders) candidates (or a packed
+        (BezierBatch, arrays) pair from engine.pack_trajectories) in one call.  Returns a dict of numpy arrays, one entry per
+        trajectory: nsamples (unclipped), first_hit (-1 = none), min_sample, min_radius; with want_lists also offsets [B + 1] and the
+        rows pos [total, 3], radius, d2, idx [total], row b = entries [offsets[b], offsets[b + 1]) -- sized from offsets[B], by a
+        second call when the first guess was too small."""
+        packed = isinstance(trajectories, tuple) and len(trajectories) == 2 and isinstance(trajectories[0], BezierBatch)
+        batch, keep = trajectories if packed else pack_trajectories(trajectories, t_start)
+        B = int(batch.B)
+        verdict = np.zeros(B, VERDICT_DTYPE)
+        out = None
+        if not want_lists:
+            _chk(lib().pct_bezier_check_batch(self._h, C.byref(batch), C.byref(params), float(stop_time), float(dt), int(cap), _ptr(verdict),
+                                              None, 0, None, None, None, None))
+        else:
+            offsets = np.zeros(B + 1, np.int64)
+            room = 256 * B
+            while True:
+                pos = np.zeros((room, 3), np.float64)
+                rad, d2, idx = np.zeros(room, np.float64), np.zeros(room, np.float64), np.zeros(room, np.uint32)
+                _chk(lib().pct_bezier_check_batch(self._h, C.byref(batch), C.byref(params), float(stop_time), float(dt), int(cap), _ptr(verdict),
+                                                  _ptr(offsets), room, _ptr(pos), _ptr(rad), _ptr(d2), _ptr(idx)))
+                total = int(offsets[B])
+                if total <= room:
+                    break
+                room = total
+            out = dict(offsets=offsets, pos=pos[:total], radius=rad[:total], d2=d2[:total], idx=idx[:total])
+        del keep
+        res = {k: np.ascontiguousarray(verdict[k]) for k in VERDICT_DTYPE.names}
+        if out:
+            res.update(out)
+        return res
+
     def ctrl_points_check(self, params: InflateParams, polycoef, seg_time, orders, t_start=0.0, cap=1024):
         """pct_ctrl_points_check: the collision threshold test on the raw control points (world units)"""
         traj, keep = _traj(polycoef, seg_time, orders)
@@ -661,6 +741,14 @@ class Cloud:
         _chk(lib().pct_bezier_check_dev(self._h, C.byref(traj), C.byref(params), float(t_start), float(stop_time), float(dt), int(cap),
                                         pos_ptr or None, radius_ptr, d2_ptr or None, idx_ptr or None, first_hit_ptr, nsamples_ptr, stream))
         return keep                                     # host arrays the stream copies from: keep them alive until it has passed
+
+    def bezier_check_batch_device(self, params: InflateParams, batch: BezierBatch, stop_time, dt, cap, verdict_ptr: int, offsets_ptr: int,
+                                  list_cap: int, pos_ptr: int = 0, radius_ptr: int = 0, d2_ptr: int = 0, idx_ptr: int = 0, stream: int = 0):
+        """pct_bezier_check_batch_dev: `batch` holds DEVICE pointers; verdict_ptr -> B x 32 bytes (engine.VERDICT_DTYPE), offsets_ptr ->
+        int64 [B + 1]; the lists (list_cap entries each, pos x3) may be 0; reserve_queries(list_cap) first.  Asynchronous on `stream`."""
+        _chk(lib().pct_bezier_check_batch_dev(self._h, C.byref(batch), C.byref(params), float(stop_time), float(dt), int(cap), verdict_ptr or None,
+                                              offsets_ptr or None, int(list_cap), pos_ptr or None, radius_ptr or None, d2_ptr or None,
+                                              idx_ptr or None, stream))
 
     def radius_count_device(self, q_ptr: int, r_ptr: int, Q: int, cnt_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         _chk(lib().pct_radius_count_batch_dev(self._h, algo, q_ptr, r_ptr, int(Q), cnt_ptr, stream))
