@@ -65,6 +65,14 @@ int pct_corridor_append_depth(pct_corridor *c, const pct_depth_view *view, const
  * removed (*removed, may be NULL).  With a noisy sensor the tick is clear_seen_through -> append_depth -> remove_outliers ->
  * evaluate -> refine with newest = *kept of the append. */
 int pct_corridor_remove_outliers(pct_corridor *c, double r, int32_t min_neighbours, int64_t newest, int64_t *removed);
+/* after pct_corridor_enable_rolling: statistical outlier removal (pct_engine.h, paragraph "Statistical outliers").  remove_statistical:
+ * of the `newest` most recent points (<= 0: every point), those whose mean distance to their k nearest other points is greater than
+ * mean + stddev_mult * stddev over the judged points are removed (*removed and *stats may be NULL; stats->threshold is the threshold
+ * it used).  remove_isolated: the same removal under a fixed threshold.  With a noisy sensor: every so often remove_statistical over
+ * the whole window, every frame clear_seen_through -> append_depth -> remove_isolated(k, that threshold, newest = *kept) -> evaluate
+ * -> refine. */
+int pct_corridor_remove_statistical(pct_corridor *c, int32_t k, double stddev_mult, int64_t newest, int64_t *removed, pct_knn_stats *stats);
+int pct_corridor_remove_isolated(pct_corridor *c, int32_t k, double max_mean_distance, int64_t newest, int64_t *removed);
 /* the engine's handle of the finder's obstacle cloud (SafeRegionRrtStar::obstacleMap().handle()), for the read-only calls of
  * pct_engine.h -- pct_radius_crop reads the window back; owned by the finder, replaced by a set_input that has to grow the map */
 int pct_corridor_cloud(pct_corridor *c, pct_cloud **cloud);

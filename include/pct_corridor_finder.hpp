@@ -242,6 +242,15 @@ public:
     // tick is clearSeenThrough -> appendDepthImage -> removeOutliers -> SafeRegionEvaluate -> SafeRegionRefine, with newest = the
     // points the append kept: a speckle is withdrawn in the frame that brought it, before any radius is computed against it.
     int64_t removeOutliers(double r, int min_neighbours, int64_t newest = 0) { return map_.removeOutliers(r, min_neighbours, newest); }
+    // after enableRollingMap: statistical outlier removal (ObstacleMap::removeStatisticalOutliers / removeIsolated), for a sensor whose
+    // density falls with range.  Every so often removeStatisticalOutliers(k, mult, 0) over the whole window, which also delivers the
+    // threshold (stats->threshold); every frame clearSeenThrough -> appendDepthImage -> removeIsolated(k, threshold, newest = the
+    // points the append kept) -> SafeRegionEvaluate -> SafeRegionRefine.
+    int64_t removeStatisticalOutliers(int k, double stddev_mult, int64_t newest = 0, pct_knn_stats *stats = nullptr)
+    {
+        return map_.removeStatisticalOutliers(k, stddev_mult, newest, stats);
+    }
+    int64_t removeIsolated(int k, double max_mean_distance, int64_t newest = 0) { return map_.removeIsolated(k, max_mean_distance, newest); }
 
     // ---- queries ----
     bool checkTrajPtCol(const Vec3 &pt) { return clearance(pt) < 0.0; }                     // :412-416

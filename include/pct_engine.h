@@ -220,6 +220,42 @@
  * are found -- its own bucket first -- so the cost grows with (r / cell)^3 and, for the rows that are removed, is always the whole
  * box: an r of many cells is not what this call is for.
  *
+ * Statistical outliers (pct_cloud_ring_remove_statistical, pct_cloud_ring_remove_isolated, pct_cloud_ring_knn_mean_distances,
+ * pct_cloud_ring_knn_distance_stats): PCL's StatisticalOutlierRemoval on the window itself -- a judged row is measured by the mean
+ * distance to its k nearest OTHER rows of the window and removed when that mean is greater than a threshold -- in place, no row crosses
+ * the bus.  All arithmetic is fp64 on the float-widened rows, one rounding per operation, no contraction; sqrt and / are correctly
+ * rounded.  Window, judged rows and scope are those of the paragraph above: `newest` selects the most recent rows in arrival order,
+ * position p lives in slot (start + p) mod capacity, newest <= 0 or newest >= size judges every row, rows that hold a NaN are not
+ * judged, and neighbours are always sought in the whole window, on the window as it is when the call begins.  Candidates of row i:
+ * every row j != i (as ring slots) below the size that holds no NaN and has a finite d2 = ((dx*dx + dy*dy) + dz*dz); exclusion is by
+ * slot, so a coincident copy in another slot is a neighbour at distance 0.  The k nearest are the k best candidates in the engine's
+ * total order (d2, then slot), the order of pct_knn_batch; 1 <= k <= PCT_KNN_MAX_K.  Mean distance: s = 0; for e = 0 .. k-1 in that
+ * order (nearest first): s = s + sqrt(d2[e]); mean = s / (double)k.  A judged row is MEASURED iff it has at least k candidates; a row
+ * with an infinite coordinate never has k candidates, because every d2 that involves it is inf or NaN; an unmeasured judged row has
+ * mean = +inf; an unjudged slot reports NaN.  Statistics over the measured judged rows: v[slot] is the mean of a measured judged row
+ * and +0.0 for every other slot below the size.  tree_sum(v), the tree order: pad with +0.0 to a multiple of 256, view as rows of 256
+ * consecutive slots, fold each row by halves -- for h = 128, 64, ..., 1: a[i] = a[i] + a[i + h] for i < h -- the row's value is a[0];
+ * repeat the same procedure on the array of row values until one value is left.  sum = tree_sum(v); sum_sq = tree_sum(v * v), the
+ * product rounded once; N = the number of measured judged rows.  N >= 1: mean = sum / N; var = (sum_sq - (sum * sum) / N) / (N - 1)
+ * for N >= 2, a var that is not greater than 0 counts as 0, and var = 0 for N = 1; stddev = sqrt(var); threshold = mean + stddev_mult *
+ * stddev.  N = 0: mean = stddev = NaN and threshold = +inf.  This is PCL's rule -- sample variance, strict compare -- except that the
+ * means stay fp64 and the sums have a stated order, so the result is a function of the window alone.  One removal rule for both
+ * calls: a judged row is removed iff mean > threshold, a strict compare; an unmeasured row (+inf) is therefore removed under every
+ * finite threshold and never under +inf.  pct_cloud_ring_remove_statistical derives the threshold from its own scope;
+ * pct_cloud_ring_remove_isolated takes it as max_mean_distance -- the per-frame call: with de-dup on, the rows a later frame keeps are
+ * almost only its outliers, whose own statistics would condemn nothing, so the threshold comes from an occasional whole-window
+ * statistical call.  One judgement, then one removal: the result does not depend on thread order, and it is not the fixed point of
+ * repeated calls.  Both are removals in every sense of the paragraph "Removing points": they need a live rolling-map index, finish an
+ * append in flight first, removed rows become NaN rows, *removed may be NULL, the empty-window rule and the auto-compaction rule
+ * apply, captured plans stay valid, the de-dup holders forget the removed voxels, and there is one host wait, the removal's own: the
+ * threshold stays on the device between the reduction and the removal, and the statistics (*stats, may be NULL) come back with that
+ * wait.  k outside 1 .. PCT_KNN_MAX_K, a stddev_mult that is not finite, a max_mean_distance that is NaN or < 0 (+inf is allowed and
+ * removes nothing): PCT_ERR_INVALID with nothing changed.  pct_cloud_ring_knn_mean_distances (mean[slot] for slot < size, host
+ * memory of n >= size entries) and pct_cloud_ring_knn_distance_stats are the judgement and the statistics without the removal: they
+ * change nothing in the cloud; n < size or a NULL output: PCT_ERR_INVALID.  An empty cloud returns PCT_OK with zeros and the N = 0
+ * statistics.  Cost: a whole-window judgement is a whole-window k-NN; a row walks the expanding cube of cells until its list is full
+ * and the cube's faces are farther than entry k - 1.
+ *
  * Depth images (pct_cloud_ring_carve_depth, pct_cloud_append_depth, pct_depth_classify): the consumer side of the reference's rgbd and
  * camera modes -- img_pcl_map_observer::save_point back-projects a rendered depth image to the observed cloud (map_observer.cpp:92-100),
  * safety_controller::check_image_for_point decides whether a point lies in observed free space (safety_controller.cpp:102-130).  One
@@ -377,6 +413,12 @@ int pct_cloud_ring_compact_count(const pct_cloud *c, uint64_t *compactions);
 /* Removing outliers (the paragraph "Removing outliers" above) */
 int pct_cloud_ring_remove_outliers(pct_cloud *c, double r, int32_t min_neighbours, int64_t newest, int64_t *removed);
 int pct_cloud_ring_neighbour_counts(pct_cloud *c, double r, int32_t count_cap, int64_t newest, uint32_t *counts, int64_t n);
+/* Statistical outliers (the paragraph "Statistical outliers" above).  sum, sum_sq: the tree sums of the means and of their squares */
+typedef struct pct_knn_stats { int64_t measured; double sum, sum_sq, mean, stddev, threshold; } pct_knn_stats;
+int pct_cloud_ring_knn_mean_distances(pct_cloud *c, int32_t k, int64_t newest, double *mean, int64_t n);
+int pct_cloud_ring_knn_distance_stats(pct_cloud *c, int32_t k, double stddev_mult, int64_t newest, pct_knn_stats *stats);
+int pct_cloud_ring_remove_statistical(pct_cloud *c, int32_t k, double stddev_mult, int64_t newest, int64_t *removed, pct_knn_stats *stats);
+int pct_cloud_ring_remove_isolated(pct_cloud *c, int32_t k, double max_mean_distance, int64_t newest, int64_t *removed);
 /* Depth images (the paragraph "Depth images" above).  One pinned projection for the three calls below. */
 enum pct_depth_metric { PCT_DEPTH_Z = 0, PCT_DEPTH_RANGE = 1 };
 typedef struct pct_depth_view {

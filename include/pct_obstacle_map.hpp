@@ -186,6 +186,50 @@ public:
         return counts;
     }
 
+    // Statistical outliers (pct_engine.h, paragraph "Statistical outliers"; needs enableRollingIndex): the rule for a sensor whose
+    // density falls with range, where no single r of the radius rule fits -- a point is judged by the mean distance to its k nearest
+    // other points of the window.
+    //   removeStatisticalOutliers   of the `newest` most recent points (0: every point), those whose mean distance is greater than
+    //                               mean + stddev_mult * stddev over the judged points are removed; returns the number removed and,
+    //                               through `stats` (may be null), the statistics with the threshold it used
+    //   removeIsolated              the same removal under a fixed threshold -- the per-frame call, with the threshold an occasional
+    //                               whole-window removeStatisticalOutliers delivered and newest = what the append just made kept
+    //   knnMeanDistances            the judgement without the removal: per slot the mean distance, +inf with fewer than k other
+    //                               points, NaN for a slot that holds no point or is out of scope
+    //   knnDistanceStats            the statistics without the removal
+    int64_t removeStatisticalOutliers(int k, double stddev_mult, int64_t newest = 0, pct_knn_stats *stats = nullptr)
+    {
+        needRolling("removeStatisticalOutliers");
+        int64_t removed = 0;
+        check(pct_cloud_ring_remove_statistical(cloud_, k, stddev_mult, newest, &removed, stats), "pct_cloud_ring_remove_statistical");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return removed;
+    }
+    int64_t removeIsolated(int k, double max_mean_distance, int64_t newest = 0)
+    {
+        needRolling("removeIsolated");
+        int64_t removed = 0;
+        check(pct_cloud_ring_remove_isolated(cloud_, k, max_mean_distance, newest, &removed), "pct_cloud_ring_remove_isolated");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return removed;
+    }
+    std::vector<double> knnMeanDistances(int k, int64_t newest = 0)
+    {
+        needRolling("knnMeanDistances");
+        const size_t n = (size_t)pct_cloud_size(cloud_);
+        std::vector<double> mean(n ? n : 1);
+        check(pct_cloud_ring_knn_mean_distances(cloud_, k, newest, mean.data(), (int64_t)mean.size()), "pct_cloud_ring_knn_mean_distances");
+        mean.resize(n);
+        return mean;
+    }
+    pct_knn_stats knnDistanceStats(int k, double stddev_mult, int64_t newest = 0)
+    {
+        needRolling("knnDistanceStats");
+        pct_knn_stats stats{};
+        check(pct_cloud_ring_knn_distance_stats(cloud_, k, stddev_mult, newest, &stats), "pct_cloud_ring_knn_distance_stats");
+        return stats;
+    }
+
     // Depth images on the rolling map (pct_engine.h, paragraph "Depth images"; both need enableRollingIndex).  The rgbd tick is
     // clearSeenThrough(image) then appendDepthImage(the same image): carve first, then append, with a small positive margin so that
     // the next frame's carve leaves the points this frame appended alone.

@@ -43,6 +43,8 @@ def lib():
         L.pct_corridor_clear_ball.argtypes = [vp, d3, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_box.argtypes = [vp, d3, d3, C.POINTER(C.c_int64)]
         L.pct_corridor_remove_outliers.argtypes = [vp, C.c_double, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]
+        L.pct_corridor_remove_statistical.argtypes = [vp, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_engine.KnnStats)]
+        L.pct_corridor_remove_isolated.argtypes = [vp, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_seen_through.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_append_depth.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_cloud.argtypes = [vp, C.POINTER(vp)]
@@ -159,6 +161,21 @@ class SafeRegionRrtStar:
         SafeRegionEvaluate -> SafeRegionRefine, newest = what the append kept); returns the number removed"""
         n = C.c_int64()
         self._chk(self.L.pct_corridor_remove_outliers(self.h, float(r), int(min_neighbours), int(newest), C.byref(n)))
+        return n.value
+
+    def removeStatisticalOutliers(self, k: int, stddev_mult: float, newest: int = 0):
+        """after enableRollingMap: of the `newest` most recent points (0: every point), remove those whose mean distance to their k
+        nearest other points is greater than mean + stddev_mult * stddev over the judged points; returns (removed, dict(measured, sum,
+        sum_sq, mean, stddev, threshold)) -- the threshold is what removeIsolated takes in the frames that follow"""
+        n, st = C.c_int64(), _engine.KnnStats()
+        self._chk(self.L.pct_corridor_remove_statistical(self.h, int(k), float(stddev_mult), int(newest), C.byref(n), C.byref(st)))
+        return n.value, st.as_dict()
+
+    def removeIsolated(self, k: int, max_mean_distance: float, newest: int = 0) -> int:
+        """after enableRollingMap: the same removal under a fixed threshold (the noisy-sensor tick: clearSeenThrough -> appendDepthImage
+        -> removeIsolated -> SafeRegionEvaluate -> SafeRegionRefine, newest = what the append kept); returns the number removed"""
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_remove_isolated(self.h, int(k), float(max_mean_distance), int(newest), C.byref(n)))
         return n.value
 
     def clearBox(self, lo, hi) -> int:

@@ -112,6 +112,14 @@ int pct_corridor_remove_outliers(pct_corridor *c, double r, int32_t min_neighbou
 {
     return guarded([&] { const int64_t n = c->impl->removeOutliers(r, min_neighbours, newest); if (removed) *removed = n; });
 }
+int pct_corridor_remove_statistical(pct_corridor *c, int32_t k, double stddev_mult, int64_t newest, int64_t *removed, pct_knn_stats *stats)
+{
+    return guarded([&] { const int64_t n = c->impl->removeStatisticalOutliers(k, stddev_mult, newest, stats); if (removed) *removed = n; });
+}
+int pct_corridor_remove_isolated(pct_corridor *c, int32_t k, double max_mean_distance, int64_t newest, int64_t *removed)
+{
+    return guarded([&] { const int64_t n = c->impl->removeIsolated(k, max_mean_distance, newest); if (removed) *removed = n; });
+}
 int pct_corridor_cloud(pct_corridor *c, pct_cloud **cloud)
 {
     return guarded([&] {

@@ -35,6 +35,7 @@
 #include "ring_compact.hpp"
 #include "ring_depth.hpp"
 #include "ring_outlier.hpp"
+#include "ring_statistical.hpp"
 #include "brute2.hpp"
 #include "knn.hpp"
 #include "rsearch.hpp"
@@ -345,6 +346,13 @@ struct pct_cloud {
     // removing outliers (ring_outlier.hpp, pct_cloud_ring_remove_outliers): one clamped neighbour count per slot, sized by the capacity
     // on first use (grow-only)
     DevBuf<uint32_t> ro_counts;
+    // statistical outliers (ring_statistical.hpp, pct_cloud_ring_remove_statistical): one k-NN mean distance per slot and the rows of
+    // the reduction tree, sized by the capacity on first use (grow-only); the {sums, mean, deviation, threshold} record on the device
+    // and its host-mapped copy
+    DevBuf<double> ks_mean;
+    DevBuf<KsPart> ks_part;
+    DevBuf<KsRecord> ks_rec;
+    MappedBuf<KsRecord> ks_rec_host;
     // de-duplicating appends (ring_dedup.hpp, pct_cloud_ring_dedup): voxel size (0 = off), the frame filter's scratch -- key table,
     // per-point table slot, the compaction scratch (sized with it) -- and the host-mapped {sequence, survivors} pair
     double dd_res = 0.0;

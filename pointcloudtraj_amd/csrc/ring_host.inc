@@ -1186,6 +1186,178 @@ int pct_cloud_ring_neighbour_counts(pct_cloud *c, double r, int32_t count_cap, i
     return PCT_OK;
 }
 
+// ---- statistical outliers (ring_statistical.hpp) ---------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+static_assert(sizeof(KsRecord) == sizeof(pct_knn_stats), "KsRecord is pct_knn_stats, field for field");
+
+// rows of every level of the reduction tree over `n` values, kept one level behind the other
+size_t ks_tree_rows(int64_t n)
+{
+    size_t rows = 0;
+    int64_t m = n;
+    do {
+        m = (m + 255) / 256;
+        rows += (size_t)m;
+    } while (m > 1);
+    return std::max<size_t>(rows, 1);
+}
+
+// the statistics of no measured row
+pct_knn_stats ks_none()
+{
+    pct_knn_stats s{};
+    s.mean = s.stddev = std::numeric_limits<double>::quiet_NaN();
+    s.threshold = std::numeric_limits<double>::infinity();
+    return s;
+}
+
+int ks_ensure(pct_cloud *c)
+{
+    if (c->ks_mean.capacity() < (size_t)c->cap || c->ks_part.capacity() < ks_tree_rows(c->cap)) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        PCTCHK(c->ks_mean.reserve((size_t)c->cap));
+        PCTCHK(c->ks_part.reserve(ks_tree_rows(c->cap)));
+    }
+    if (!c->ks_rec) {
+        PCTCHK(c->ks_rec.reset(1));
+        PCTCHK(c->ks_rec_host.reset(1));
+    }
+    return PCT_OK;
+}
+
+// queue the judgement of the `newest` most recent rows (<= 0 or >= size: every row) on the window as it is: ks_mean[slot] = the mean
+// distance to the k nearest other rows for a judged row (+inf: fewer than k candidates), NaN for every other slot below the size
+// (all bits set is a NaN).  The window holds rows.
+int ks_judge(pct_cloud *c, int k, int64_t newest)
+{
+    hipStream_t s = g_stream;
+    const int64_t n = c->count;
+    const int64_t judged = (newest <= 0 || newest >= n) ? n : newest;
+    const RcWindow W{ (uint32_t)(n == c->cap ? c->ring_next : 0), (uint32_t)c->cap, (uint32_t)n };
+    HIPCHK(hipMemsetAsync(c->ks_mean, 0xFF, sizeof(double) * (size_t)n, s));
+    const int blocks = ceil_div(judged, (int64_t)kKsRows);
+    const bool work = c->count_work;
+    if (work) {
+        c->host_work = false;
+        HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
+    }
+    with_kcap(k, [&](auto kc) {
+        with_bool(work, [&](auto w) {
+            ring_knn_mean_kernel<decltype(kc)::value, decltype(w)::value><<<blocks, 256, 0, s>>>(ring_view(c), W, (uint32_t)(n - judged), c->x, c->y, c->z, k,
+                                                                                                 c->ks_mean, work ? c->d_work.get() : nullptr);
+        });
+    });
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// queue the tree reduction of ks_mean[0, size) and, in its last launch, the record
+int ks_reduce(pct_cloud *c, double mult)
+{
+    hipStream_t s = g_stream;
+    KsPart *out = c->ks_part;
+    uint32_t m = (uint32_t)ceil_div(c->count, 256);
+    ks_reduce_kernel<true><<<m, 256, 0, s>>>(c->ks_mean, nullptr, (uint32_t)c->count, out, mult, c->ks_rec, c->ks_rec_host);
+    while (m > 1) {
+        const KsPart *in = out;
+        out += m;
+        const uint32_t blocks = (uint32_t)ceil_div(m, 256);
+        ks_reduce_kernel<false><<<blocks, 256, 0, s>>>(nullptr, in, m, out, mult, c->ks_rec, c->ks_rec_host);
+        m = blocks;
+    }
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// the removal behind a judgement, on the threshold the device record holds; the one host wait of the call
+int ks_remove(pct_cloud *c, int64_t *removed_out)
+{
+    const uint32_t seq = c->rm_word.next();
+    ks_remove_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, c->ks_mean, c->ks_rec, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht, c->ring_slots,
+                                                                   c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->rm_word.w, seq);
+    HIPCHK(hipGetLastError());
+    int64_t removed = 0, live = 0;
+    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
+    if (removed_out) *removed_out = removed;
+    return ring_remove_finish(c, removed, live);
+}
+
+bool ks_bad_k(int32_t k) { return k < 1 || k > PCT_KNN_MAX_K; }
+
+}  // namespace
+
+extern "C" {
+
+int pct_cloud_ring_knn_mean_distances(pct_cloud *c, int32_t k, int64_t newest, double *mean, int64_t n)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (ks_bad_k(k)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_knn_mean_distances: k must be in 1 .. %d", PCT_KNN_MAX_K);
+    if (!mean) return fail(PCT_ERR_INVALID, "pct_cloud_ring_knn_mean_distances: null output");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_knn_mean_distances"));
+    if (n < c->count)
+        return fail(PCT_ERR_INVALID, "pct_cloud_ring_knn_mean_distances: %lld means for a window of %lld", (long long)n, (long long)c->count);
+    if (c->count == 0) return PCT_OK;
+    PCTCHK(ks_ensure(c));
+    PCTCHK(ks_judge(c, k, newest));
+    HIPCHK(hipMemcpyAsync(mean, c->ks_mean, sizeof(double) * (size_t)c->count, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return PCT_OK;
+}
+
+int pct_cloud_ring_knn_distance_stats(pct_cloud *c, int32_t k, double stddev_mult, int64_t newest, pct_knn_stats *stats)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (ks_bad_k(k)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_knn_distance_stats: k must be in 1 .. %d", PCT_KNN_MAX_K);
+    if (!std::isfinite(stddev_mult)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_knn_distance_stats: stddev_mult must be finite");
+    if (!stats) return fail(PCT_ERR_INVALID, "pct_cloud_ring_knn_distance_stats: null output");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_knn_distance_stats"));
+    *stats = ks_none();
+    if (c->count == 0) return PCT_OK;
+    PCTCHK(ks_ensure(c));
+    PCTCHK(ks_judge(c, k, newest));
+    PCTCHK(ks_reduce(c, stddev_mult));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    std::memcpy(stats, c->ks_rec_host.host(), sizeof *stats);
+    return PCT_OK;
+}
+
+int pct_cloud_ring_remove_statistical(pct_cloud *c, int32_t k, double stddev_mult, int64_t newest, int64_t *removed_out, pct_knn_stats *stats)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (ks_bad_k(k)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_remove_statistical: k must be in 1 .. %d", PCT_KNN_MAX_K);
+    if (!std::isfinite(stddev_mult)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_remove_statistical: stddev_mult must be finite");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_remove_statistical"));
+    if (removed_out) *removed_out = 0;
+    if (stats) *stats = ks_none();
+    if (c->count == 0) return PCT_OK;
+    PCTCHK(ring_remove_ensure(c));
+    PCTCHK(ks_ensure(c));
+    PCTCHK(ks_judge(c, k, newest));
+    PCTCHK(ks_reduce(c, stddev_mult));
+    // the record's host-mapped copy was written by a launch that finished before the removal's began: it is there behind the wait
+    const int st = ks_remove(c, removed_out);
+    if (stats && st == PCT_OK) std::memcpy(stats, c->ks_rec_host.host(), sizeof *stats);
+    return st;
+}
+
+int pct_cloud_ring_remove_isolated(pct_cloud *c, int32_t k, double max_mean_distance, int64_t newest, int64_t *removed_out)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "null cloud");
+    if (ks_bad_k(k)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_remove_isolated: k must be in 1 .. %d", PCT_KNN_MAX_K);
+    if (!(max_mean_distance >= 0)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_remove_isolated: max_mean_distance must be >= 0 (+inf allowed)");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_remove_isolated"));
+    if (removed_out) *removed_out = 0;
+    if (c->count == 0 || std::isinf(max_mean_distance)) return PCT_OK;          // no mean is greater than +inf: nothing to launch
+    PCTCHK(ring_remove_ensure(c));
+    PCTCHK(ks_ensure(c));
+    PCTCHK(ks_judge(c, k, newest));
+    ks_set_threshold_kernel<<<1, 1, 0, g_stream>>>(c->ks_rec, max_mean_distance);
+    return ks_remove(c, removed_out);
+}
+
 int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
 {
     if (!c || !live_out || !not_live) return fail(PCT_ERR_INVALID, "bad ring_live arguments");

@@ -1,0 +1,243 @@
+// ring_statistical.hpp -- statistical outlier removal on the ROLLING obstacle map (pct_cloud_ring_remove_statistical, _remove_isolated,
+// _knn_mean_distances, _knn_distance_stats): every judged row's mean distance to its k nearest OTHER rows of the window, the mean and
+// deviation of those means in a pinned summation order, and the removal of the rows above a threshold, in place, for gfx950.  The rule
+// is the paragraph "Statistical outliers" of include/pct_engine.h.
+//
+// Three kinds of launch, so that the judgement cannot see the removal and the threshold never leaves the device:
+//   1. ring_knn_mean_kernel   read-only over the bucket table.  ONE WAVE PER JUDGED ROW, four rows per 256-thread block (a block per
+//                             row with two block barriers per shell, as ring_knn_kernel spends, is right for a tick's few hundred
+//                             queries and wrong for the 50 000 rows of a frame or the 5 M of a window).  The four waves walk different
+//                             rows with different trip counts, so nothing in the walk is block-wide: each wave owns one sorted list in
+//                             LDS (lane e owns entry e, knn_wave_insert) and tau = entry k - 1 stays in registers.  The walk is that of
+//                             ring_knn_kernel: the overflow queue first and exhaustively, then the expanding cube (ring_shell), the
+//                             idempotent insert (a step whose axis has just closed revisits buckets), the same termination test.  A
+//                             record whose id is the judged slot or kRingDead is never offered.  Epilogue: lane 0 sums the k entries
+//                             in list order (nearest first) with the sqrt and writes mean[slot]; a row with fewer than k candidates
+//                             gets +inf.  The host has filled the buffer with NaN beforehand (rows out of scope, rows with a NaN).
+//   2. ks_reduce_kernel       the sums in the contract's tree order: a block folds 256 consecutive values by halves (h = 128 and 64
+//                             through LDS, h <= 32 as a butterfly inside wave 0: lane i < h receives exactly a[i] + a[i + h]) and
+//                             writes {sum, sum of squares, measured rows} of its row of 256; the kernel is launched again on the block
+//                             values until one is left, and thread 0 of that last launch computes mean, deviation and threshold into
+//                             the device record (and its host-mapped copy).  No atomics on floating-point data: the result is a
+//                             function of the means alone.
+//   3. ks_remove_kernel       ring_remove_where (ring_remove.hpp) with the predicate "this slot's mean is greater than the threshold
+//                             in the device record" -- the NaN of an unjudged slot compares false.  For pct_cloud_ring_remove_isolated
+//                             the record is filled from the argument (ks_set_threshold_kernel) instead of from the reduction.
+#pragma once
+#include "ring_search.hpp"
+#include "ring_remove.hpp"
+#include "ring_compact.hpp"
+
+#pragma clang fp contract(off)
+
+namespace pct {
+
+// pct_knn_stats, field for field (include/pct_engine.h)
+struct KsRecord {
+    long long measured;
+    double sum, sum_sq, mean, stddev, threshold;
+};
+
+// one row of 256 of the reduction tree
+struct KsPart {
+    double sum, sum_sq;
+    unsigned long long n;
+};
+
+constexpr uint32_t kKsRows = 4;                        // judged rows per block: one per wave
+
+// lanes of the wave that share one bucket of a step of `total` buckets (a power of two; 64 / lanes buckets are read at a time)
+__device__ __forceinline__ int ks_lanes_per_bucket(int total) { return total <= 8 ? 8 : total <= 16 ? 4 : total <= 32 ? 2 : 1; }
+
+// Judged rows: age positions [p0, W.n) of the window (rc_slot).  1 <= k <= KCAP.  WORK (the probe's build of the kernel,
+// pct_set_work_counters): points = records read, cells = buckets visited, nodes = rows walked.
+template <int KCAP, bool WORK>
+__global__ __launch_bounds__(256) void ring_knn_mean_kernel(RingView V, RcWindow W, uint32_t p0, const float *__restrict__ x,
+                                                            const float *__restrict__ y, const float *__restrict__ z, int k,
+                                                            double *__restrict__ mean, WorkCounters *__restrict__ work)
+{
+    __shared__ double s_d[kKsRows][KCAP];
+    __shared__ uint32_t s_i[kKsRows][KCAP];
+    __shared__ unsigned long long s_w[8];
+    const RingDesc &R = V.R;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t p = (uint64_t)p0 + (uint64_t)blockIdx.x * kKsRows + (uint64_t)wave;
+    uint32_t npts = 0, nbuckets = 0, walked = 0;
+    if (p < W.n) {                                                      // everything below is uniform over the wave
+        const uint32_t slot = rc_slot(W, (uint32_t)p);
+        const float px = x[slot], py = y[slot], pz = z[slot];
+        if (px == px && py == py && pz == pz) {                         // a row that holds a NaN is not judged
+            double *ld = s_d[wave];
+            uint32_t *li = s_i[wave];
+            if (lane < k) { ld[lane] = __builtin_huge_val(); li[lane] = kNoIndex; }
+            knn_lds_order();
+            double td = __builtin_huge_val();
+            uint32_t ti = kNoIndex;
+            const float finf = __builtin_huge_valf();
+            // a row with an infinite coordinate: every d2 that involves it is inf or NaN, it has no candidate
+            if (fabsf(px) < finf && fabsf(py) < finf && fabsf(pz) < finf) {
+                const double qx = (double)px, qy = (double)py, qz = (double)pz;
+                if (WORK) walked = 1;
+                {   // overflow queue: exhaustive, once
+                    const uint32_t oh = V.st->ovf_head, on = V.st->ovf_tail - oh;
+                    for (uint32_t k0 = 0; k0 < on; k0 += 64u) {
+                        const uint32_t e = k0 + (uint32_t)lane;
+                        const bool have = e < on;
+                        const float4 P = V.ovf[(oh + (have ? e : on - 1u)) & R.ovf_mask];
+                        const uint32_t id = __float_as_uint(P.w);
+                        npts += have ? 1u : 0u;
+                        ring_knn_offer(ld, li, k, lane, have && id != kRingDead && id != slot,
+                                       dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz), id, td, ti);
+                    }
+                }
+                bool wild = false;
+                const int cx = ring_cell_coord(qx, R.inv_h, wild), cy = ring_cell_coord(qy, R.inv_h, wild), cz = ring_cell_coord(qz, R.inv_h, wild);
+                for (int r = 1;; r++) {
+                    const RingShell S = ring_shell(R, cx, cy, cz, r, wild);
+                    const int lanes = ks_lanes_per_bucket(S.total);
+                    const uint32_t part = (uint32_t)lane % (uint32_t)lanes;
+                    // the lanes of the wave insert together: both loops run while ANY lane has a bucket / a record left
+                    for (int k0 = 0; k0 < S.total; k0 += 64 / lanes) {
+                        const int kb = k0 + lane / lanes;
+                        const bool live = kb < S.total;
+                        uint2 m = make_uint2(0u, 0u);
+                        uint32_t b = 0;
+                        if (live) { b = ring_shell_bucket(R, S, kb); m = V.ht[b]; }
+                        const uint32_t n = m.y - m.x;
+                        const float4 *base = V.slots + (size_t)b * R.K;
+                        if (WORK && live && part == 0) nbuckets++;
+                        for (uint32_t j = part; __builtin_amdgcn_ballot_w64(j < n); j += (uint32_t)lanes) {
+                            const bool have = j < n;
+                            double d2 = __builtin_huge_val();
+                            uint32_t id = kRingDead;
+                            if (have) {
+                                const float4 P = base[(m.x + j) & (R.K - 1)];
+                                d2 = dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz);
+                                id = __float_as_uint(P.w);
+                                npts++;
+                            }
+                            ring_knn_offer(ld, li, k, lane, have && id != kRingDead && id != slot, d2, id, td, ti);
+                        }
+                    }
+                    double bound = __builtin_huge_val();
+                    if (S.ox) bound = fmin(bound, fmin(qx - (double)(cx - r) * R.h, (double)(cx + r + 1) * R.h - qx));
+                    if (S.oy) bound = fmin(bound, fmin(qy - (double)(cy - r) * R.h, (double)(cy + r + 1) * R.h - qy));
+                    if (S.oz) bound = fmin(bound, fmin(qz - (double)(cz - r) * R.h, (double)(cz + r + 1) * R.h - qz));
+                    if (bound == __builtin_huge_val()) break;                   // every bucket has been visited
+                    bound -= R.h * (1.0 / 256.0);
+                    if (bound > 0.0 && td <= bound * bound) break;              // td < +inf: the list is full
+                }
+            }
+            knn_lds_order();
+            if (lane == 0) {
+                double m = __builtin_huge_val();                                // fewer than k candidates: not measured
+                if (ld[k - 1] < __builtin_huge_val()) {
+                    double s = 0.0;
+                    for (int e = 0; e < k; e++) s = s + sqrt(ld[e]);
+                    m = s / (double)k;
+                }
+                mean[slot] = m;
+            }
+        }
+    }
+    if (WORK) {
+        ring_add_work(work, npts, nbuckets, s_w);
+        if (lane == 0 && walked) atomicAdd(&work[blockIdx.x & (kWorkSlots - 1)].nodes, 1ull);
+    }
+}
+
+// the fold of 256 values by halves; the block's value arrives in thread 0.  s: 256 entries of LDS per quantity
+__device__ __forceinline__ void ks_fold(double &a, double &b, unsigned long long &c, double *s_a, double *s_b, unsigned long long *s_c)
+{
+    const uint32_t t = threadIdx.x;
+    if (t >= 128) { s_a[t] = a; s_b[t] = b; s_c[t] = c; }
+    __syncthreads();
+    if (t < 128) { a = a + s_a[t + 128]; b = b + s_b[t + 128]; c += s_c[t + 128]; }
+    if (t >= 64 && t < 128) { s_a[t] = a; s_b[t] = b; s_c[t] = c; }
+    __syncthreads();
+    if (t < 64) {
+        a = a + s_a[t + 64]; b = b + s_b[t + 64]; c += s_c[t + 64];
+#pragma unroll
+        for (int h = 32; h > 0; h >>= 1) {                              // lane i < h: a[i] + a[i ^ h] = a[i] + a[i + h]
+            a = a + __shfl_xor(a, h, kWave);
+            b = b + __shfl_xor(b, h, kWave);
+            c += (unsigned long long)__shfl_xor((long long)c, h, kWave);
+        }
+    }
+}
+
+// mean, deviation and threshold of the measured rows (the contract's formulas, one rounding per operation)
+__device__ __forceinline__ KsRecord ks_finish(double sum, double sum_sq, unsigned long long n, double mult)
+{
+    KsRecord r;
+    r.measured = (long long)n;
+    r.sum = sum;
+    r.sum_sq = sum_sq;
+    if (n == 0) {
+        r.mean = r.stddev = __builtin_nan("");
+        r.threshold = __builtin_huge_val();
+        return r;
+    }
+    const double N = (double)n;
+    r.mean = sum / N;
+    double var = 0.0;
+    if (n >= 2) {
+        var = (sum_sq - (sum * sum) / N) / (N - 1.0);
+        if (!(var > 0.0)) var = 0.0;
+    }
+    r.stddev = sqrt(var);
+    r.threshold = r.mean + mult * r.stddev;
+    return r;
+}
+
+// One level of the tree.  FIRST: the values are the means of `count` slots (a measured judged row: its mean; every other slot:
+// +0.0); otherwise they are `count` rows of the level below.  out[blockIdx.x] = this block's row; the launch with one block also
+// writes the record (rec on the device, rec_host its host-mapped copy, read after the removal's wait or a stream synchronise).
+template <bool FIRST>
+__global__ __launch_bounds__(256) void ks_reduce_kernel(const double *__restrict__ mean, const KsPart *__restrict__ in, uint32_t count,
+                                                        KsPart *__restrict__ out, double mult, KsRecord *__restrict__ rec,
+                                                        KsRecord *__restrict__ rec_host)
+{
+    __shared__ double s_a[256], s_b[256];
+    __shared__ unsigned long long s_c[256];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    double a = 0.0, b = 0.0;
+    unsigned long long c = 0;
+    if (i < count) {
+        if (FIRST) {
+            const double m = mean[i];
+            if (m < __builtin_huge_val()) { a = m; b = m * m; c = 1; }  // NaN (not judged) and +inf (not measured) compare false
+        } else {
+            a = in[i].sum; b = in[i].sum_sq; c = in[i].n;
+        }
+    }
+    ks_fold(a, b, c, s_a, s_b, s_c);
+    if (threadIdx.x != 0) return;
+    out[blockIdx.x] = KsPart{ a, b, c };
+    if (gridDim.x == 1) {
+        const KsRecord r = ks_finish(a, b, c, mult);
+        *rec = r;
+        *rec_host = r;
+        __threadfence_system();
+    }
+}
+
+// pct_cloud_ring_remove_isolated: the record's threshold is the caller's
+__global__ void ks_set_threshold_kernel(KsRecord *__restrict__ rec, double threshold)
+{
+    rec->threshold = threshold;
+}
+
+// mean[slot] as ring_knn_mean_kernel left it (NaN: not judged, +inf: not measured); a judged row above the record's threshold is removed
+__global__ __launch_bounds__(256) void ks_remove_kernel(RingDesc R, const double *__restrict__ mean, const KsRecord *__restrict__ rec,
+                                                        float *__restrict__ x, float *__restrict__ y, float *__restrict__ z, uint32_t count,
+                                                        uint2 *__restrict__ ht, float4 *__restrict__ slots, float4 *__restrict__ ovf,
+                                                        uint32_t *__restrict__ where, RingState *__restrict__ st, RingRemoveMeet *__restrict__ meet,
+                                                        uint32_t *__restrict__ host_word, uint32_t seq)
+{
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool flagged = slot < count && mean[slot] > rec->threshold;
+    ring_remove_where([&](float, float, float) { return flagged; }, R, x, y, z, count, ht, slots, ovf, where, st, meet, host_word, seq);
+}
+
+}  // namespace pct

@@ -100,6 +100,16 @@ class DepthView(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("metric", C.c_int32), ("reserved", C.c_int32)]
 
 
+class KnnStats(C.Structure):
+    """pct_knn_stats: the statistics of the k-NN mean distances (include/pct_engine.h, paragraph "Statistical outliers")"""
+    _fields_ = [("measured", C.c_int64), ("sum", C.c_double), ("sum_sq", C.c_double), ("mean", C.c_double), ("stddev", C.c_double),
+                ("threshold", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return dict(measured=int(self.measured), sum=float(self.sum), sum_sq=float(self.sum_sq), mean=float(self.mean),
+                    stddev=float(self.stddev), threshold=float(self.threshold))
+
+
 def depth_view(t, R, width, height, fov_hor_deg=None, focal=None, metric=DEPTH_Z, near_z=0.01) -> DepthView:
     """t: camera position; R: 3 x 3, column k = camera axis k in world (x image right, y image down, z optical); the focal distance in
     image widths is given directly or as 0.5 / tan(fov_hor / 2) of a horizontal field of view in degrees"""
@@ -243,6 +253,10 @@ def lib():
         L.pct_cloud_ring_compact_count.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.pct_cloud_ring_remove_outliers.argtypes = [vp, C.c_double, C.c_int32, i64, C.POINTER(i64)]
         L.pct_cloud_ring_neighbour_counts.argtypes = [vp, C.c_double, C.c_int32, i64, u32p, i64]
+        L.pct_cloud_ring_knn_mean_distances.argtypes = [vp, C.c_int32, i64, f64p, i64]
+        L.pct_cloud_ring_knn_distance_stats.argtypes = [vp, C.c_int32, C.c_double, i64, C.POINTER(KnnStats)]
+        L.pct_cloud_ring_remove_statistical.argtypes = [vp, C.c_int32, C.c_double, i64, C.POINTER(i64), C.POINTER(KnnStats)]
+        L.pct_cloud_ring_remove_isolated.argtypes = [vp, C.c_int32, C.c_double, i64, C.POINTER(i64)]
         L.pct_cloud_ring_carve_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64)]
         L.pct_cloud_append_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64), C.POINTER(i64)]
         L.pct_depth_classify.argtypes = [vp, vp, C.c_int32, f64p, i64, C.c_double, vp, vp]
@@ -514,6 +528,35 @@ class Cloud:
         counts = np.empty(len(self), np.uint32)
         _chk(lib().pct_cloud_ring_neighbour_counts(self._h, float(r), int(count_cap), int(newest), _ptr(counts), len(counts)))
         return counts
+
+    def ring_knn_mean_distances(self, k: int, newest: int = 0):
+        """every judged row's mean distance to its k nearest other rows of the window (pct_cloud_ring_knn_mean_distances): float64
+        [len(self)], +inf for a judged row with fewer than k candidates, NaN for a row that holds a NaN or is out of scope"""
+        mean = np.empty(max(len(self), 1), np.float64)
+        _chk(lib().pct_cloud_ring_knn_mean_distances(self._h, int(k), int(newest), _ptr(mean), len(mean)))
+        return mean[:len(self)]
+
+    def ring_knn_distance_stats(self, k: int, stddev_mult: float, newest: int = 0) -> dict:
+        """the statistics of those means in the contract's tree order (pct_cloud_ring_knn_distance_stats): dict(measured, sum, sum_sq,
+        mean, stddev, threshold = mean + stddev_mult * stddev); changes nothing in the cloud"""
+        st = KnnStats()
+        _chk(lib().pct_cloud_ring_knn_distance_stats(self._h, int(k), float(stddev_mult), int(newest), C.byref(st)))
+        return st.as_dict()
+
+    def ring_remove_statistical(self, k: int, stddev_mult: float, newest: int = 0):
+        """statistical outlier removal on the window itself (pct_cloud_ring_remove_statistical): of the `newest` most recent rows (0:
+        every row), those whose k-NN mean distance is greater than mean + stddev_mult * stddev over the judged rows are removed;
+        returns (removed, the statistics as ring_knn_distance_stats returns them)"""
+        n, st = C.c_int64(), KnnStats()
+        _chk(lib().pct_cloud_ring_remove_statistical(self._h, int(k), float(stddev_mult), int(newest), C.byref(n), C.byref(st)))
+        return n.value, st.as_dict()
+
+    def ring_remove_isolated(self, k: int, max_mean_distance: float, newest: int = 0) -> int:
+        """the same removal under a fixed threshold (pct_cloud_ring_remove_isolated), the per-frame call: a judged row whose k-NN mean
+        distance is greater than max_mean_distance (or that has fewer than k candidates) is removed; returns the number removed"""
+        n = C.c_int64()
+        _chk(lib().pct_cloud_ring_remove_isolated(self._h, int(k), float(max_mean_distance), int(newest), C.byref(n)))
+        return n.value
 
     def ring_carve_depth(self, view: DepthView, image, margin: float) -> int:
         """free-space clearing (pct_cloud_ring_carve_depth): remove every point the depth image sees through -- in the image, its

@@ -356,6 +356,44 @@ def run_rgbd_speckle_scenario(window, render, frames=6, filter=True, speckles=No
     return out
 
 
+def run_rgbd_speckle_scenario_statistical(window, render, frames=6, k=4, stddev_mult=3.0, speckles=None, images=None, each=None):
+    """run_rgbd_speckle_scenario with the statistical rule in place of the radius rule.  With de-dup on, the rows a frame keeps from
+    the second frame on are almost only its speckles, whose own statistics condemn nothing, so the threshold is taken once and used
+    from then on: frame 0 calls removeStatisticalOutliers(k, stddev_mult, 0) over the whole window and keeps its threshold, every
+    later frame calls removeIsolated(k, threshold, newest = the points the append kept).  `window` is a SafeRegionRrtStar with its
+    rolling map and setRollingDedup on, or anything with the same four members and live_set().  Returns the live set after every
+    frame; each(frame index, window, dict(speckle, kept, removed, threshold, stats = frame 0's statistics or None)) is called after
+    every frame."""
+    view = rgbd_view()
+    dep = np.float32(RGBD["wall_x"] - RGBD_SPECKLE["depth"])
+    out = []
+    threshold = float("inf")
+    for f in range(frames):
+        image = np.array(render(view, rgbd_scene(f)), np.float32)
+        pix = rgbd_speckle_pixels(f, speckles)
+        for u, v in pix:
+            image[v, u] = dep
+        if images is not None:
+            images.append(image)
+        window.clearSeenThrough(view, image, RGBD["margin"])
+        kept = window.appendDepthImage(view, image, float("inf"))
+        stats = None
+        if f == 0:
+            removed, stats = window.removeStatisticalOutliers(k, stddev_mult, 0)
+            threshold = stats["threshold"]
+        else:
+            removed = window.removeIsolated(k, threshold, kept) if kept > 0 else 0
+        if hasattr(window, "live_set"):
+            out.append(window.live_set())
+        else:
+            _, _, xyz = window.cloud().radius_crop((0.0, 0.0, 0.0), 1.0e4)
+            out.append(set(map(tuple, xyz.tolist())))
+        if each is not None:
+            each(f, window, dict(speckle=np.stack([rgbd_pixel_point(view, u, v, dep) for u, v in pix]), kept=kept, removed=removed,
+                                 threshold=threshold, stats=stats))
+    return out
+
+
 # ---- the rgbd window with a partial view: a camera that pans round a room whose obstacles come and go --------------------------------
 # A camera at the origin turns by 90 degrees per frame (four headings a lap, fov 90: the views tile the circle) inside a square room
 # with walls 6 m away.  In every heading a 4 m x 4 m obstacle stands 4 m away during the even laps, a little further along the wall
