@@ -291,6 +291,23 @@ __device__ __forceinline__ int ring_lanes_per_bucket(const RingDesc &R, int tota
     return total <= 32 ? 8 : total <= 64 ? 4 : total <= 128 ? 2 : 1;
 }
 
+// The correctness condition of every exact walk of the table (Exactness, below): after the cube of Chebyshev radius r around cell
+// (cx, cy, cz) has been visited, every record not yet seen is farther from (qx, qy, qz) than this bound -- the least distance to a
+// face of the cube on an axis that is still open (ox / oy / oz), less h/256.  false, and a bound of +inf: no axis is open, every
+// bucket has been visited (handed back beside the bound: a second test of the bound at the call site does not fold into this one
+// and costs ring_batch_kernel two registers and a wave, profiles/ring_remove_frame_asm.txt).
+__device__ __forceinline__ bool ring_open_face_bound(const RingDesc &R, bool ox, bool oy, bool oz, int cx, int cy, int cz, int r, double qx,
+                                                     double qy, double qz, double &bound)
+{
+    bound = __builtin_huge_val();
+    if (ox) bound = fmin(bound, fmin(qx - (double)(cx - r) * R.h, (double)(cx + r + 1) * R.h - qx));
+    if (oy) bound = fmin(bound, fmin(qy - (double)(cy - r) * R.h, (double)(cy + r + 1) * R.h - qy));
+    if (oz) bound = fmin(bound, fmin(qz - (double)(cz - r) * R.h, (double)(cz + r + 1) * R.h - qz));
+    if (bound == __builtin_huge_val()) return false;
+    bound -= R.h * (1.0 / 256.0);
+    return true;
+}
+
 // Nearest point of the fp32-narrowed (px, py, pz) over a ring-indexed cloud; one 256-thread block, ONE THREAD PER BUCKET of the
 // cube / shell being examined (a bucket holds ~6 records: a thread reads its head/tail pair, then its records, four at a time),
 // block-wide fold after every shell.  stop_d2 as in block_nn_search (kernels.hpp): when only the radius is wanted the search may
@@ -364,12 +381,8 @@ __device__ __forceinline__ void ring_block_nn_search(const RingView &V, double p
             }
         }
         block_argmin256(bd, bi, s_d, s_i);
-        double bound = __builtin_huge_val();
-        if (ox) bound = fmin(bound, fmin(qx - (double)(cx - r) * R.h, (double)(cx + r + 1) * R.h - qx));
-        if (oy) bound = fmin(bound, fmin(qy - (double)(cy - r) * R.h, (double)(cy + r + 1) * R.h - qy));
-        if (oz) bound = fmin(bound, fmin(qz - (double)(cz - r) * R.h, (double)(cz + r + 1) * R.h - qz));
-        if (bound == __builtin_huge_val()) break;                   // every bucket has been visited
-        bound -= R.h * (1.0 / 256.0);
+        double bound;
+        if (!ring_open_face_bound(R, ox, oy, oz, cx, cy, cz, r, qx, qy, qz, bound)) break;      // every bucket has been visited
         if (bound > 0.0 && (bd <= bound * bound || bound * bound >= stop_d2)) break;
     }
 }

@@ -7,7 +7,7 @@
 // Everything is fp64 from float-widened operands, one rounding per operation, no contraction, in the order the header writes the
 // expressions; tests/helpers/depth_model.py restates them in numpy and the GPU tests hold the two equal bit for bit.
 //
-// Kernels: depth_carve_kernel is ring_remove_where (ring_remove.hpp) with depth_seen_through for a predicate -- one pass over the
+// Kernels: the carve is ring_remove_kernel (ring_remove.hpp) with DepthSeenThrough for a predicate -- one pass over the
 // slots below the window's size, 12 B per slot and one gather from an image that stays in L2 (1.2 MB at 640 x 480), the counts
 // and the host word of every other removal.  depth_valid_kernel / depth_unproject_kernel stand on either side of the de-dup
 // filter's rank and scan kernels (ring_dedup.hpp): flags of the valid pixels, their ranks, then every valid pixel un-projected
@@ -57,15 +57,13 @@ __device__ __forceinline__ bool depth_seen_through(const pct_depth_view &V, cons
     return w > 0.0 && ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) < w * w;
 }
 
-__global__ __launch_bounds__(256) void depth_carve_kernel(RingDesc R, pct_depth_view V, const float *__restrict__ image, double margin,
-                                                          float *__restrict__ x, float *__restrict__ y, float *__restrict__ z, uint32_t count,
-                                                          uint2 *__restrict__ ht, float4 *__restrict__ slots, float4 *__restrict__ ovf,
-                                                          uint32_t *__restrict__ where, RingState *__restrict__ st,
-                                                          RingRemoveMeet *__restrict__ meet, uint32_t *__restrict__ host_word, uint32_t seq)
-{
-    ring_remove_where([&](float px, float py, float pz) { return depth_seen_through(V, image, margin, px, py, pz); }, R, x, y, z, count, ht, slots,
-                      ovf, where, st, meet, host_word, seq);
-}
+// the carve's predicate of ring_remove_kernel (ring_remove.hpp): the row is seen through in this view of this image
+struct DepthSeenThrough {
+    pct_depth_view V;
+    const float *image;
+    double margin;
+    __device__ __forceinline__ bool operator()(uint32_t, float px, float py, float pz) const { return depth_seen_through(V, image, margin, px, py, pz); }
+};
 
 // ---- un-projection (metric Z) ---------------------------------------------------------------------------------------------------
 // valid iff dep is finite, dep >= near_z and dep <= max_depth (a NaN fails all three)

@@ -935,6 +935,25 @@ int ring_remove_begin(pct_cloud *c, const char *what)
     return PCT_OK;
 }
 
+// The window in age order (rc_slot) and the scope of a judgement over its `newest` most recent rows (<= 0 or >= size: every row):
+// age positions [p0, size), `judged` of them.  ring_scope(c, 0): the whole window.
+struct RingScope { RcWindow W; uint32_t p0; int64_t judged; };
+
+RingScope ring_scope(const pct_cloud *c, int64_t newest)
+{
+    const int64_t n = c->count, judged = (newest <= 0 || newest >= n) ? n : newest;
+    return RingScope{ RcWindow{ (uint32_t)(n == c->cap ? c->ring_next : 0), (uint32_t)c->cap, (uint32_t)n }, (uint32_t)(n - judged), judged };
+}
+
+// a judgement that counts its work (pct_set_work_counters) starts from zeroed device counters; nothing to do when counting is off
+int ring_work_begin(pct_cloud *c)
+{
+    if (!c->count_work) return PCT_OK;
+    c->host_work = false;
+    HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, g_stream));
+    return PCT_OK;
+}
+
 // the window becomes the empty cloud (the empty-window rule of the removal paragraph): size 0, cursor at slot 0, tables cleared
 int ring_reset_empty(pct_cloud *c)
 {
@@ -974,7 +993,7 @@ int ring_compact_run(pct_cloud *c, int64_t known_live, int64_t *live_out, uint32
     hipStream_t s = g_stream;
     const int64_t n = c->count;
     PCTCHK(ring_compact_ensure(c, remap != nullptr));
-    const RcWindow W{ (uint32_t)(n == c->cap ? c->ring_next : 0), (uint32_t)c->cap, (uint32_t)n };
+    const RcWindow W = ring_scope(c, 0).W;
     const int ntiles = ceil_div(n, kRcTile);
     const uint32_t seq = c->dd_word.next();
     rc_count_kernel<<<ntiles, 256, 0, s>>>(W, c->x, c->y, c->z, c->rc_tile);
@@ -1035,19 +1054,34 @@ int ring_remove_finish(pct_cloud *c, int64_t removed, int64_t live)
     return note_mutation(c);
 }
 
-int ring_remove_region(pct_cloud *c, const RingRegion &G, int64_t *removed_out)
+// what a removal launch edits, as ring_view() is what a search reads; `seq`: the sequence number its last block publishes
+RingEdit ring_edit(pct_cloud *c, uint32_t seq)
+{
+    return RingEdit{ c->R, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht, c->ring_slots, c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet,
+                     c->rm_word.w, seq };
+}
+
+// the tail of every removal behind its launches: the one host wait, `removed` handed out (removed_out may be null), the bookkeeping
+int ring_remove_settle(pct_cloud *c, uint32_t seq, int64_t *removed_out)
+{
+    int64_t removed = 0, live = 0;
+    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
+    if (removed_out) *removed_out = removed;
+    return ring_remove_finish(c, removed, live);
+}
+
+// A one-pass removal of the rows `pred` names (ring_remove_kernel), whole: the caller has passed ring_remove_begin and queued what the
+// predicate reads.  An empty window removes nothing and launches nothing.
+template <typename Pred>
+int ring_remove_run(pct_cloud *c, const Pred &pred, int64_t *removed_out)
 {
     if (removed_out) *removed_out = 0;
     if (c->count == 0) return PCT_OK;
     PCTCHK(ring_remove_ensure(c));
     const uint32_t seq = c->rm_word.next();
-    ring_remove_region_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, G, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht, c->ring_slots,
-                                                                            c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->rm_word.w, seq);
+    ring_remove_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(ring_edit(c, seq), pred);
     HIPCHK(hipGetLastError());
-    int64_t removed = 0, live = 0;
-    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
-    if (removed_out) *removed_out = removed;
-    return ring_remove_finish(c, removed, live);
+    return ring_remove_settle(c, seq, removed_out);
 }
 
 }  // namespace
@@ -1064,7 +1098,7 @@ int pct_cloud_ring_remove_ball(pct_cloud *c, const double centre[3], double r, i
     G.r2 = r * r;                               // a negative r counts as |r|; a NaN r puts nothing inside
     G.kind = 0;
     G.outside = outside ? 1 : 0;
-    return ring_remove_region(c, G, removed);
+    return ring_remove_run(c, G, removed);
 }
 
 int pct_cloud_ring_remove_box(pct_cloud *c, const double lo[3], const double hi[3], int outside, int64_t *removed)
@@ -1077,7 +1111,7 @@ int pct_cloud_ring_remove_box(pct_cloud *c, const double lo[3], const double hi[
     for (int k = 0; k < 3; k++) { G.a[k] = lo[k]; G.b[k] = hi[k]; }
     G.kind = 1;
     G.outside = outside ? 1 : 0;
-    return ring_remove_region(c, G, removed);
+    return ring_remove_run(c, G, removed);
 }
 
 int pct_cloud_ring_remove_indices(pct_cloud *c, const uint32_t *idx, int64_t n, int64_t *removed_out)
@@ -1102,14 +1136,10 @@ int pct_cloud_ring_remove_indices(pct_cloud *c, const uint32_t *idx, int64_t n, 
     for (int64_t i = 0; i < n; i++) slots[(size_t)i] = idx[i] - (uint32_t)c->index_base;
     HIPCHK(hipMemcpyAsync(c->d_rm_list, slots.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, g_stream));
     const uint32_t seq = c->rm_word.next();
-    ring_remove_list_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(c->R, c->d_rm_list, (uint32_t)n, c->x, c->y, c->z, c->ring_ht, c->ring_slots, c->ring_ovf,
-                                                                   c->ring_where, c->ring_st, c->d_rm_meet);
-    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_rm_meet, c->rm_word.w, seq);
+    ring_remove_list_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(ring_edit(c, seq), c->d_rm_list, (uint32_t)n);
+    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(ring_edit(c, seq));
     HIPCHK(hipGetLastError());
-    int64_t removed = 0, live = 0;
-    PCTCHK(ring_remove_wait(c, seq, &removed, &live));         // (the list has left `slots` by now: the copy precedes the kernels)
-    if (removed_out) *removed_out = removed;
-    return ring_remove_finish(c, removed, live);
+    return ring_remove_settle(c, seq, removed_out);             // (the list has left `slots` by its wait: the copy precedes the kernels)
 }
 
 // ---- removing outliers (ring_outlier.hpp) ----------------------------------------------------------------------------------------
@@ -1123,25 +1153,19 @@ namespace {
 int ring_outlier_judge(pct_cloud *c, double r, uint32_t target, int64_t newest)
 {
     hipStream_t s = g_stream;
-    const int64_t n = c->count;
     if (c->ro_counts.capacity() < (size_t)c->cap) {
         HIPCHK(hipStreamSynchronize(s));
         PCTCHK(c->ro_counts.reserve((size_t)c->cap));
     }
-    const int64_t judged = (newest <= 0 || newest >= n) ? n : newest;
-    const RcWindow W{ (uint32_t)(n == c->cap ? c->ring_next : 0), (uint32_t)c->cap, (uint32_t)n };
-    HIPCHK(hipMemsetAsync(c->ro_counts, 0xFF, sizeof(uint32_t) * (size_t)n, s));
-    const int blocks = ceil_div(judged, (int64_t)kRoRows);
+    const RingScope S = ring_scope(c, newest);
+    HIPCHK(hipMemsetAsync(c->ro_counts, 0xFF, sizeof(uint32_t) * (size_t)c->count, s));
+    const int blocks = ceil_div(S.judged, (int64_t)kRoRows);
     const double r2 = std::min(r * r, std::numeric_limits<double>::max());
-    if (c->count_work) {
-        c->host_work = false;
-        HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
-        ring_outlier_judge_kernel<true><<<blocks, 256, 0, s>>>(ring_view(c), W, (uint32_t)(n - judged), c->x, c->y, c->z, r, r2, target, c->ro_counts,
-                                                             c->d_work);
-    } else {
-        ring_outlier_judge_kernel<false><<<blocks, 256, 0, s>>>(ring_view(c), W, (uint32_t)(n - judged), c->x, c->y, c->z, r, r2, target, c->ro_counts,
-                                                              nullptr);
-    }
+    PCTCHK(ring_work_begin(c));
+    with_bool(c->count_work, [&](auto w) {
+        ring_outlier_judge_kernel<decltype(w)::value><<<blocks, 256, 0, s>>>(ring_view(c), S.W, S.p0, c->x, c->y, c->z, r, r2, target, c->ro_counts,
+                                                                             c->count_work ? c->d_work.get() : nullptr);
+    });
     HIPCHK(hipGetLastError());
     return PCT_OK;
 }
@@ -1158,17 +1182,8 @@ int pct_cloud_ring_remove_outliers(pct_cloud *c, double r, int32_t min_neighbour
     PCTCHK(ring_remove_begin(c, "pct_cloud_ring_remove_outliers"));
     if (removed_out) *removed_out = 0;
     if (min_neighbours == 0 || c->count == 0) return PCT_OK;
-    PCTCHK(ring_remove_ensure(c));
     PCTCHK(ring_outlier_judge(c, r, (uint32_t)min_neighbours, newest));
-    const uint32_t seq = c->rm_word.next();
-    ring_outlier_remove_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, c->ro_counts, (uint32_t)min_neighbours, c->x, c->y, c->z, (uint32_t)c->count,
-                                                                             c->ring_ht, c->ring_slots, c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet,
-                                                                             c->rm_word.w, seq);
-    HIPCHK(hipGetLastError());
-    int64_t removed = 0, live = 0;
-    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
-    if (removed_out) *removed_out = removed;
-    return ring_remove_finish(c, removed, live);
+    return ring_remove_run(c, RoBelow{ c->ro_counts, (uint32_t)min_neighbours }, removed_out);
 }
 
 int pct_cloud_ring_neighbour_counts(pct_cloud *c, double r, int32_t count_cap, int64_t newest, uint32_t *counts, int64_t n)
@@ -1234,20 +1249,15 @@ int ks_ensure(pct_cloud *c)
 int ks_judge(pct_cloud *c, int k, int64_t newest)
 {
     hipStream_t s = g_stream;
-    const int64_t n = c->count;
-    const int64_t judged = (newest <= 0 || newest >= n) ? n : newest;
-    const RcWindow W{ (uint32_t)(n == c->cap ? c->ring_next : 0), (uint32_t)c->cap, (uint32_t)n };
-    HIPCHK(hipMemsetAsync(c->ks_mean, 0xFF, sizeof(double) * (size_t)n, s));
-    const int blocks = ceil_div(judged, (int64_t)kKsRows);
+    const RingScope S = ring_scope(c, newest);
+    HIPCHK(hipMemsetAsync(c->ks_mean, 0xFF, sizeof(double) * (size_t)c->count, s));
+    const int blocks = ceil_div(S.judged, (int64_t)kKsRows);
     const bool work = c->count_work;
-    if (work) {
-        c->host_work = false;
-        HIPCHK(hipMemsetAsync(c->d_work, 0, sizeof(WorkCounters) * kWorkSlots, s));
-    }
+    PCTCHK(ring_work_begin(c));
     with_kcap(k, [&](auto kc) {
         with_bool(work, [&](auto w) {
-            ring_knn_mean_kernel<decltype(kc)::value, decltype(w)::value><<<blocks, 256, 0, s>>>(ring_view(c), W, (uint32_t)(n - judged), c->x, c->y, c->z, k,
-                                                                                                 c->ks_mean, work ? c->d_work.get() : nullptr);
+            ring_knn_mean_kernel<decltype(kc)::value, decltype(w)::value><<<blocks, 256, 0, s>>>(ring_view(c), S.W, S.p0, c->x, c->y, c->z, k, c->ks_mean,
+                                                                                                 work ? c->d_work.get() : nullptr);
         });
     });
     HIPCHK(hipGetLastError());
@@ -1270,19 +1280,6 @@ int ks_reduce(pct_cloud *c, double mult)
     }
     HIPCHK(hipGetLastError());
     return PCT_OK;
-}
-
-// the removal behind a judgement, on the threshold the device record holds; the one host wait of the call
-int ks_remove(pct_cloud *c, int64_t *removed_out)
-{
-    const uint32_t seq = c->rm_word.next();
-    ks_remove_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, c->ks_mean, c->ks_rec, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht, c->ring_slots,
-                                                                   c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->rm_word.w, seq);
-    HIPCHK(hipGetLastError());
-    int64_t removed = 0, live = 0;
-    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
-    if (removed_out) *removed_out = removed;
-    return ring_remove_finish(c, removed, live);
 }
 
 bool ks_bad_k(int32_t k) { return k < 1 || k > PCT_KNN_MAX_K; }
@@ -1333,12 +1330,11 @@ int pct_cloud_ring_remove_statistical(pct_cloud *c, int32_t k, double stddev_mul
     if (removed_out) *removed_out = 0;
     if (stats) *stats = ks_none();
     if (c->count == 0) return PCT_OK;
-    PCTCHK(ring_remove_ensure(c));
     PCTCHK(ks_ensure(c));
     PCTCHK(ks_judge(c, k, newest));
     PCTCHK(ks_reduce(c, stddev_mult));
     // the record's host-mapped copy was written by a launch that finished before the removal's began: it is there behind the wait
-    const int st = ks_remove(c, removed_out);
+    const int st = ring_remove_run(c, KsAbove{ c->ks_mean, c->ks_rec }, removed_out);
     if (stats && st == PCT_OK) std::memcpy(stats, c->ks_rec_host.host(), sizeof *stats);
     return st;
 }
@@ -1351,11 +1347,10 @@ int pct_cloud_ring_remove_isolated(pct_cloud *c, int32_t k, double max_mean_dist
     PCTCHK(ring_remove_begin(c, "pct_cloud_ring_remove_isolated"));
     if (removed_out) *removed_out = 0;
     if (c->count == 0 || std::isinf(max_mean_distance)) return PCT_OK;          // no mean is greater than +inf: nothing to launch
-    PCTCHK(ring_remove_ensure(c));
     PCTCHK(ks_ensure(c));
     PCTCHK(ks_judge(c, k, newest));
     ks_set_threshold_kernel<<<1, 1, 0, g_stream>>>(c->ks_rec, max_mean_distance);
-    return ks_remove(c, removed_out);
+    return ring_remove_run(c, KsAbove{ c->ks_mean, c->ks_rec }, removed_out);
 }
 
 int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
@@ -1366,7 +1361,7 @@ int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
     if (c->count == 0) return PCT_OK;
     PCTCHK(ring_remove_ensure(c));
     const uint32_t seq = c->rm_word.next();
-    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->x, c->y, c->z, (uint32_t)c->count, c->d_rm_meet, c->rm_word.w, seq);
+    ring_live_count_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(ring_edit(c, seq));
     HIPCHK(hipGetLastError());
     int64_t removed = 0, live = 0;
     PCTCHK(ring_remove_wait(c, seq, &removed, &live));
@@ -1378,10 +1373,8 @@ int pct_cloud_ring_live(pct_cloud *c, int64_t *live_out, int64_t *not_live)
 int pct_cloud_ring_compact(pct_cloud *c, int64_t *live, int64_t *reclaimed, uint32_t *remap, int64_t remap_cap)
 {
     if (!c) return fail(PCT_ERR_INVALID, "null cloud");
-    if (!c->ring_on) return fail(PCT_ERR_INVALID, "pct_cloud_ring_compact needs the rolling-map index (pct_cloud_ring_index)");
-    if (!c->ring_ready && c->count > 0) return fail(PCT_ERR_INVALID, "pct_cloud_ring_compact: the cloud has no live rolling-map index");
-    if (remap && remap_cap < c->count) return fail(PCT_ERR_INVALID, "pct_cloud_ring_compact: a remap of %lld entries for a window of %lld", (long long)remap_cap, (long long)c->count);
     PCTCHK(ring_remove_begin(c, "pct_cloud_ring_compact"));
+    if (remap && remap_cap < c->count) return fail(PCT_ERR_INVALID, "pct_cloud_ring_compact: a remap of %lld entries for a window of %lld", (long long)remap_cap, (long long)c->count);
     if (live) *live = 0;
     if (reclaimed) *reclaimed = 0;
     if (c->count == 0) return PCT_OK;
@@ -1491,17 +1484,9 @@ int pct_cloud_ring_carve_depth(pct_cloud *c, const pct_depth_view *v, const floa
     PCTCHK(ring_remove_begin(c, "pct_cloud_ring_carve_depth"));
     *removed_out = 0;
     if (c->count == 0) return PCT_OK;
-    PCTCHK(ring_remove_ensure(c));
     const float *d_image = nullptr;
     PCTCHK(depth_cloud_image(c, v, image, &d_image));
-    const uint32_t seq = c->rm_word.next();
-    depth_carve_kernel<<<ceil_div(c->count, 256), 256, 0, g_stream>>>(c->R, *v, d_image, margin, c->x, c->y, c->z, (uint32_t)c->count, c->ring_ht,
-                                                                     c->ring_slots, c->ring_ovf, c->ring_where, c->ring_st, c->d_rm_meet, c->rm_word.w, seq);
-    HIPCHK(hipGetLastError());
-    int64_t removed = 0, live = 0;
-    PCTCHK(ring_remove_wait(c, seq, &removed, &live));
-    *removed_out = removed;
-    return ring_remove_finish(c, removed, live);
+    return ring_remove_run(c, DepthSeenThrough{ *v, d_image, margin }, removed_out);
 }
 
 int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *image, double max_depth, int64_t *offered, int64_t *kept)

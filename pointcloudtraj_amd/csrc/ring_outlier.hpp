@@ -16,8 +16,8 @@
 //                                  they leave together and no lane reads from a group that has gone.
 //                                  Output: out[slot] = min(neighbours, target) for a judged row; the host has filled the buffer
 //                                  with PCT_NO_INDEX beforehand (rows out of scope, rows that hold a NaN).
-//   2. ring_outlier_remove_kernel  ring_remove_where (ring_remove.hpp) with the predicate "this slot's count is below m"; the counts,
-//                                  the host word and the bookkeeping behind it are those of every other removal.
+//   2. ring_remove_kernel<RoBelow> the one removal kernel (ring_remove.hpp) with the predicate "this slot's count is below m"; the
+//                                  counts, the host word and the bookkeeping behind it are those of every other removal.
 // The arithmetic is dist2() in fp64 on the float-widened rows, inclusive, no fp32 screen: three subtractions, three products, two
 // sums and a compare beside a 16-byte read.  A record is skipped when its id is kRingDead or the judged slot itself -- exclusion is
 // by slot, a coincident copy in another slot is a neighbour.
@@ -125,16 +125,12 @@ __global__ __launch_bounds__(256) void ring_outlier_judge_kernel(RingView V, RcW
     }
 }
 
-// counts[slot] as the judge kernel left it (PCT_NO_INDEX: not judged); a judged row below m neighbours is removed
-__global__ __launch_bounds__(256) void ring_outlier_remove_kernel(RingDesc R, const uint32_t *__restrict__ counts, uint32_t m, float *__restrict__ x,
-                                                                  float *__restrict__ y, float *__restrict__ z, uint32_t count, uint2 *__restrict__ ht,
-                                                                  float4 *__restrict__ slots, float4 *__restrict__ ovf, uint32_t *__restrict__ where,
-                                                                  RingState *__restrict__ st, RingRemoveMeet *__restrict__ meet,
-                                                                  uint32_t *__restrict__ host_word, uint32_t seq)
-{
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool flagged = slot < count && counts[slot] < m;
-    ring_remove_where([&](float, float, float) { return flagged; }, R, x, y, z, count, ht, slots, ovf, where, st, meet, host_word, seq);
-}
+// the removal's predicate of ring_remove_kernel (ring_remove.hpp): counts[slot] as the judge kernel left it (PCT_NO_INDEX: not
+// judged); a judged row below m neighbours is removed
+struct RoBelow {
+    const uint32_t *counts;
+    uint32_t m;
+    __device__ __forceinline__ bool operator()(uint32_t slot, float, float, float) const { return counts[slot] < m; }
+};
 
 }  // namespace pct

@@ -321,12 +321,8 @@ __global__ __launch_bounds__(256) void ring_knn_kernel(RingView V, const float *
             ti = s_tau_i;
             if (wave != 0 && lane < k) { ld[lane] = __builtin_huge_val(); li[lane] = kNoIndex; }
             knn_lds_order();
-            double bound = __builtin_huge_val();
-            if (S.ox) bound = fmin(bound, fmin(qx - (double)(cx - r) * R.h, (double)(cx + r + 1) * R.h - qx));
-            if (S.oy) bound = fmin(bound, fmin(qy - (double)(cy - r) * R.h, (double)(cy + r + 1) * R.h - qy));
-            if (S.oz) bound = fmin(bound, fmin(qz - (double)(cz - r) * R.h, (double)(cz + r + 1) * R.h - qz));
-            if (bound == __builtin_huge_val()) break;                   // every bucket has been visited
-            bound -= R.h * (1.0 / 256.0);
+            double bound;
+            if (!ring_open_face_bound(R, S.ox, S.oy, S.oz, cx, cy, cz, r, qx, qy, qz, bound)) break;      // every bucket has been visited
             if (bound > 0.0 && td <= bound * bound) break;              // td < +inf: the list is full
         }
     }

@@ -20,9 +20,10 @@
 //                             values until one is left, and thread 0 of that last launch computes mean, deviation and threshold into
 //                             the device record (and its host-mapped copy).  No atomics on floating-point data: the result is a
 //                             function of the means alone.
-//   3. ks_remove_kernel       ring_remove_where (ring_remove.hpp) with the predicate "this slot's mean is greater than the threshold
-//                             in the device record" -- the NaN of an unjudged slot compares false.  For pct_cloud_ring_remove_isolated
-//                             the record is filled from the argument (ks_set_threshold_kernel) instead of from the reduction.
+//   3. ring_remove_kernel<KsAbove>  the one removal kernel (ring_remove.hpp) with the predicate "this slot's mean is greater than the
+//                             threshold in the device record" -- the NaN of an unjudged slot compares false.  For
+//                             pct_cloud_ring_remove_isolated the record is filled from the argument (ks_set_threshold_kernel) instead
+//                             of from the reduction.
 #pragma once
 #include "ring_search.hpp"
 #include "ring_remove.hpp"
@@ -119,12 +120,8 @@ __global__ __launch_bounds__(256) void ring_knn_mean_kernel(RingView V, RcWindow
                             ring_knn_offer(ld, li, k, lane, have && id != kRingDead && id != slot, d2, id, td, ti);
                         }
                     }
-                    double bound = __builtin_huge_val();
-                    if (S.ox) bound = fmin(bound, fmin(qx - (double)(cx - r) * R.h, (double)(cx + r + 1) * R.h - qx));
-                    if (S.oy) bound = fmin(bound, fmin(qy - (double)(cy - r) * R.h, (double)(cy + r + 1) * R.h - qy));
-                    if (S.oz) bound = fmin(bound, fmin(qz - (double)(cz - r) * R.h, (double)(cz + r + 1) * R.h - qz));
-                    if (bound == __builtin_huge_val()) break;                   // every bucket has been visited
-                    bound -= R.h * (1.0 / 256.0);
+                    double bound;
+                    if (!ring_open_face_bound(R, S.ox, S.oy, S.oz, cx, cy, cz, r, qx, qy, qz, bound)) break;      // every bucket has been visited
                     if (bound > 0.0 && td <= bound * bound) break;              // td < +inf: the list is full
                 }
             }
@@ -228,16 +225,12 @@ __global__ void ks_set_threshold_kernel(KsRecord *__restrict__ rec, double thres
     rec->threshold = threshold;
 }
 
-// mean[slot] as ring_knn_mean_kernel left it (NaN: not judged, +inf: not measured); a judged row above the record's threshold is removed
-__global__ __launch_bounds__(256) void ks_remove_kernel(RingDesc R, const double *__restrict__ mean, const KsRecord *__restrict__ rec,
-                                                        float *__restrict__ x, float *__restrict__ y, float *__restrict__ z, uint32_t count,
-                                                        uint2 *__restrict__ ht, float4 *__restrict__ slots, float4 *__restrict__ ovf,
-                                                        uint32_t *__restrict__ where, RingState *__restrict__ st, RingRemoveMeet *__restrict__ meet,
-                                                        uint32_t *__restrict__ host_word, uint32_t seq)
-{
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool flagged = slot < count && mean[slot] > rec->threshold;
-    ring_remove_where([&](float, float, float) { return flagged; }, R, x, y, z, count, ht, slots, ovf, where, st, meet, host_word, seq);
-}
+// the removal's predicate of ring_remove_kernel (ring_remove.hpp): mean[slot] as ring_knn_mean_kernel left it (NaN: not judged, +inf:
+// not measured); a judged row above the record's threshold is removed -- the NaN of an unjudged slot compares false
+struct KsAbove {
+    const double *mean;
+    const KsRecord *rec;
+    __device__ __forceinline__ bool operator()(uint32_t slot, float, float, float) const { return mean[slot] > rec->threshold; }
+};
 
 }  // namespace pct

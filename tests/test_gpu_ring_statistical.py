@@ -409,6 +409,57 @@ def test_per_frame_filter_with_dedup(E):
     c.close()
 
 
+def test_every_form_of_removal_in_a_row_on_one_window(E):
+    """What the forms of removal share shows where one runs behind another: the meeting words are zero between different kernels,
+    the sequence number carries from form to form, the overflow queue's head advances under every predicate, and the bookkeeping
+    behind the wait (live counts, the auto mode) is one.  ONE window: 4 096 slots fed three frames of 2 048 (wrapped), sparse rows
+    plus 200 rows in one 0.5 m cell (32 in its bucket, the rest in the overflow queue), auto-compaction at 0.25; ball, box, index
+    list, carve from a 32 x 24 image, radius outliers, statistical and isolated outliers one after another.  After each: `removed`,
+    pct_cloud_ring_live and the surviving rows as the model has them, exact."""
+    cap = 4096
+    c, w = make(E, cap, cell=0.5)
+    c.ring_autocompact(0.25)
+    w.autocompact(0.25)
+    cluster = (np.float32([5.0, 5.0, 5.0]) + synth.uniform_points(700, 200, 0.01, 0.24)).astype(np.float32)
+    for f in range(3):
+        pts = uniform(710 + f, 2048)
+        if f:
+            pts[300:400] = cluster[100 * (f - 1):100 * f]
+        feed(c, w, pts)
+    assert (w.count, w.nxt) == (cap, 2048), "the ring has wrapped"
+    assert c.ring_info()["overflow_entries"] == 200 - 32
+
+    def settled(form, got, want):
+        assert got == want > 0, f"{form}: removed {got}, the model removes {want}"
+        check_window(c, w, form)
+        assert c.ring_compact_count() == w.compactions, f"{form}: compactions"
+        assert c.ring_info()["overflow_entries"] > 0, f"{form}: the next form finds the overflow queue in use"
+
+    settled("ball", c.ring_remove_ball((3, 3, 3), 2.0), w.remove_ball((3, 3, 3), 2.0))
+    settled("box", c.ring_remove_box((0, 0, 0), (14, 2.5, 10)), w.remove_box((0, 0, 0), (14, 2.5, 10)))
+    live = np.flatnonzero(w.live_mask())
+    queued = np.flatnonzero((w.live()[:, None] == cluster[::10]).all(axis=2).any(axis=1))
+    idx = np.concatenate([live[::9], live[:360:9], queued]).astype(np.uint32)              # entries named twice, rows of the queue
+    settled("index list", c.ring_remove_indices(idx), w.remove_indices(idx))
+    assert w.compactions == 1 and w.count == w.live_count() < cap, "the index list brought the dead rows to a quarter of the capacity"
+    view = E.depth_view((7.0, 7.0, -6.0), np.eye(3), 32, 24, fov_hor_deg=90.0)             # looks along +z from 6 m below the box
+    img = np.random.default_rng(720).uniform(7.0, 15.0, (24, 32)).astype(np.float32)
+    img[3, :], img[11, 5], img[20, 30] = np.inf, np.nan, -np.inf
+    pr = D.project(view, cluster)
+    img[pr["rv"][pr["inside"]], pr["ru"][pr["inside"]]] = 9.0                              # the cluster, 11 m out, is not seen through
+    settled("carve", c.ring_carve_depth(view, img, 0.05), w.carve(view, img, 0.05))
+    settled("radius outliers", c.ring_remove_outliers(0.6, 2), w.remove_outliers(0.6, 2))
+    (got, gst), (want, wst) = c.ring_remove_statistical(4, 1.0), w.remove_statistical(4, 1.0)
+    assert T.same_stats(gst, wst), f"statistical: {gst} != {wst}"
+    settled("statistical", got, want)
+    settled("isolated", c.ring_remove_isolated(4, 0.7, 300), w.remove_isolated(4, 0.7, 300))
+    assert w.compactions >= 2 and w.resets == 0
+    check_slots(c, w, "at the end")
+    check_searches(E, c, w.live(), np.concatenate([uniform(730, 80), cluster[::9]]).astype(np.float32), "at the end")
+    check_cursor(c, w, "at the end")
+    c.close()
+
+
 # ---- 7. invalid arguments ------------------------------------------------------------------------------------------------------------
 
 def test_invalid_arguments_change_nothing(E):
