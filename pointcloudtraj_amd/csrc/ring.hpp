@@ -18,7 +18,9 @@
 //     far finer than the cell).
 //
 // Search = the same expanding-cube search as the cell-sorted index (kernels.hpp section 4), same fp64 arithmetic
-// ((dx*dx + dy*dy) + dz*dz, no FMA), winner by (d2, ring slot): lowest slot on exact ties.
+// ((dx*dx + dy*dy) + dz*dz, no FMA), winner by (d2, ring slot): lowest slot on exact ties.  The cube is enumerated in ONE place
+// (RingShell / ring_shell / ring_shell_bucket, with the exactness argument and ring_open_face_bound beside it); the argmin walk here
+// (ring_block_nn_search) and the k-NN walk (ring_knn_walk, ring_search.hpp) both step through it.
 #pragma once
 #include "kernels.hpp"
 
@@ -291,11 +293,60 @@ __device__ __forceinline__ int ring_lanes_per_bucket(const RingDesc &R, int tota
     return total <= 32 ? 8 : total <= 64 ? 4 : total <= 128 ? 2 : 1;
 }
 
-// The correctness condition of every exact walk of the table (Exactness, below): after the cube of Chebyshev radius r around cell
-// (cx, cy, cz) has been visited, every record not yet seen is farther from (qx, qy, qz) than this bound -- the least distance to a
-// face of the cube on an axis that is still open (ox / oy / oz), less h/256.  false, and a bound of +inf: no axis is open, every
-// bucket has been visited (handed back beside the bound: a second test of the bound at the call site does not fold into this one
-// and costs ring_batch_kernel two registers and a wave, profiles/ring_remove_frame_asm.txt).
+// ---- the expanding cube: the one enumeration under every exact walk of the table --------------------------------------------
+// Exactness: after the cube of world cells [c - r, c + r]^3 has been visited (every bucket a cube cell folds onto), a point not
+// yet seen lies in an unvisited bucket, so its world cell differs from every visited one along some axis that is still "open"
+// (2r + 1 < table size on that axis; a query with an absurd coordinate has none), and along that axis it is beyond the cube's
+// face: farther than the face distance.  A walk stops only when what it holds is within (min open face distance - h/256)^2, or
+// when no axis is open (every bucket has been visited).  The walks: ring_block_nn_search (below), ring_knn_walk (ring_search.hpp).
+
+// The cube / shell of Chebyshev radius r around the query's cell (cx, cy, cz): the whole box for the first cube, for a wild query
+// and when an axis has just closed (2r + 1 reaches the table size: the axis' g positions, once each), the shell's six faces
+// otherwise.  The box of a step whose axis has just closed holds buckets seen before: a walk must not mind seeing a record twice.
+struct RingShell {
+    int nx, ny, nz, x0, y0, z0, nyi, nzi, A, B, total;
+    bool ox, oy, oz, box;
+};
+
+__device__ __forceinline__ RingShell ring_shell(const RingDesc &R, int cx, int cy, int cz, int r, bool wild)
+{
+    RingShell S;
+    S.ox = !wild && 2 * r + 1 < R.gx; S.oy = !wild && 2 * r + 1 < R.gy; S.oz = !wild && 2 * r + 1 < R.gz;
+    const bool was_x = !wild && 2 * r - 1 < R.gx, was_y = !wild && 2 * r - 1 < R.gy, was_z = !wild && 2 * r - 1 < R.gz;
+    // positions per axis: the cube's 2r+1 world cells while open, the whole table once closed
+    S.nx = S.ox ? 2 * r + 1 : R.gx; S.ny = S.oy ? 2 * r + 1 : R.gy; S.nz = S.oz ? 2 * r + 1 : R.gz;
+    S.x0 = S.ox ? cx - r : 0; S.y0 = S.oy ? cy - r : 0; S.z0 = S.oz ? cz - r : 0;
+    S.box = r == 1 || (!S.ox && was_x) || (!S.oy && was_y) || (!S.oz && was_z);
+    S.nyi = S.oy ? S.ny - 2 : S.ny; S.nzi = S.oz ? S.nz - 2 : S.nz;
+    S.A = S.oz ? 2 * S.nx * S.ny : 0;
+    S.B = S.oy ? 2 * S.nx * S.nzi : 0;
+    S.total = S.box ? S.nx * S.ny * S.nz : S.A + S.B + (S.ox ? 2 * S.nyi * S.nzi : 0);
+    return S;
+}
+
+// bucket k of S.total
+__device__ __forceinline__ uint32_t ring_shell_bucket(const RingDesc &R, const RingShell &S, int k)
+{
+    int jx, jy, jz;
+    if (S.box) {
+        jx = k % S.nx; jy = (k / S.nx) % S.ny; jz = k / (S.nx * S.ny);
+    } else if (k < S.A) {                                   // two z-faces
+        const int f = k / (S.nx * S.ny), rem = k % (S.nx * S.ny);
+        jz = f ? S.nz - 1 : 0; jy = rem / S.nx; jx = rem % S.nx;
+    } else if (k < S.A + S.B) {                             // two y-faces without the z-face rows
+        const int k2 = k - S.A, f = k2 / (S.nx * S.nzi), rem = k2 % (S.nx * S.nzi);
+        jy = f ? S.ny - 1 : 0; jz = (S.oz ? 1 : 0) + rem / S.nx; jx = rem % S.nx;
+    } else {                                                // two x-faces without either
+        const int k3 = k - S.A - S.B, f = k3 / (S.nyi * S.nzi), rem = k3 % (S.nyi * S.nzi);
+        jx = f ? S.nx - 1 : 0; jz = (S.oz ? 1 : 0) + rem / S.nyi; jy = (S.oy ? 1 : 0) + rem % S.nyi;
+    }
+    return ring_lin(R, S.x0 + jx, S.y0 + jy, S.z0 + jz);
+}
+
+// After the cube of Chebyshev radius r has been visited, every record not yet seen is farther from (qx, qy, qz) than this bound --
+// the least distance to a face of the cube on an axis that is still open (ox / oy / oz), less h/256.  false, and a bound of +inf:
+// no axis is open, every bucket has been visited (handed back beside the bound: a second test of the bound at the call site does
+// not fold into this one and costs ring_batch_kernel two registers and a wave, profiles/ring_remove_frame_asm.txt).
 __device__ __forceinline__ bool ring_open_face_bound(const RingDesc &R, bool ox, bool oy, bool oz, int cx, int cy, int cz, int r, double qx,
                                                      double qy, double qz, double &bound)
 {
@@ -310,13 +361,11 @@ __device__ __forceinline__ bool ring_open_face_bound(const RingDesc &R, bool ox,
 
 // Nearest point of the fp32-narrowed (px, py, pz) over a ring-indexed cloud; one 256-thread block, ONE THREAD PER BUCKET of the
 // cube / shell being examined (a bucket holds ~6 records: a thread reads its head/tail pair, then its records, four at a time),
-// block-wide fold after every shell.  stop_d2 as in block_nn_search (kernels.hpp): when only the radius is wanted the search may
-// stop once everything unseen is beyond max_radius + search_margin.
-//
-// Exactness: after the cube of world cells [c - r, c + r]^3 has been visited (every bucket a cube cell folds onto), a point not
-// yet seen lies in an unvisited bucket, so its world cell differs from every visited one along some axis that is still "open"
-// (2r + 1 < table size on that axis), and along that axis it is beyond the cube's face: farther than the face distance.  The
-// search stops only when best <= (min open face distance - h/256)^2, or when no axis is open (every bucket has been visited).
+// block-wide fold after every shell.  With few buckets (the first cube has 27) several threads share a bucket -- one thread per
+// bucket leaves 229 of the block's threads idle while 27 walk their records four at a time, which is what a tick costs once the
+// buckets are fat (surfaces, re-sensed points: 40-250 records per occupied bucket).  A bucket seen again is harmless: a repeated
+// (d2, slot) never changes the winner.  stop_d2 as in block_nn_search (kernels.hpp): when only the radius is wanted the search
+// may stop once everything unseen is beyond max_radius + search_margin.
 __device__ __forceinline__ void ring_block_nn_search(const RingView &V, double px, double py, double pz, double stop_d2,
                                                      double *s_d, uint32_t *s_i, double &bd, uint32_t &bi)
 {
@@ -342,47 +391,13 @@ __device__ __forceinline__ void ring_block_nn_search(const RingView &V, double p
     bool wild = false;
     const int cx = ring_cell_coord(qx, R.inv_h, wild), cy = ring_cell_coord(qy, R.inv_h, wild), cz = ring_cell_coord(qz, R.inv_h, wild);
     for (int r = 1;; r++) {
-        // an axis is open while the cube does not yet wrap around the table on it (a query with an absurd coordinate has none)
-        const bool ox = !wild && 2 * r + 1 < R.gx, oy = !wild && 2 * r + 1 < R.gy, oz = !wild && 2 * r + 1 < R.gz;
-        const bool was_x = !wild && 2 * r - 1 < R.gx, was_y = !wild && 2 * r - 1 < R.gy, was_z = !wild && 2 * r - 1 < R.gz;
-        // positions per axis: the cube's 2r+1 world cells while open, the whole table once closed
-        const int nx = ox ? 2 * r + 1 : R.gx, ny = oy ? 2 * r + 1 : R.gy, nz = oz ? 2 * r + 1 : R.gz;
-        const int x0 = ox ? cx - r : 0, y0 = oy ? cy - r : 0, z0 = oz ? cz - r : 0;
-        if (r == 1 || (!ox && was_x) || (!oy && was_y) || (!oz && was_z)) {
-            // first cube, or an axis has just closed (or the query is wild): visit the whole box; buckets seen before are
-            // merely seen again (a repeated (d2, slot) never changes the winner)
-            // few buckets (the first cube has 27): several threads share a bucket -- one thread per bucket leaves 229 of the block's
-            // threads idle while 27 walk their records four at a time, which is what a tick costs once the buckets are fat (surfaces,
-            // re-sensed points: 40-250 records per occupied bucket)
-            const int total = nx * ny * nz;
-            const int lanes = ring_lanes_per_bucket(R, total);
-            for (int k = (int)threadIdx.x / lanes; k < total; k += 256 / lanes) {
-                const int jx = k % nx, jy = (k / nx) % ny, jz = k / (nx * ny);
-                ring_scan_bucket(V, ring_lin(R, x0 + jx, y0 + jy, z0 + jz), qx, qy, qz, bd, bi, threadIdx.x % (uint32_t)lanes, (uint32_t)lanes);
-            }
-        } else {
-            // shell r: two z-faces, then two y-faces without the z-face rows, then two x-faces without either
-            const int nyi = oy ? ny - 2 : ny, nzi = oz ? nz - 2 : nz;
-            const int A = oz ? 2 * nx * ny : 0, B = oy ? 2 * nx * nzi : 0, Cc = ox ? 2 * nyi * nzi : 0;
-            const int lanes = ring_lanes_per_bucket(R, A + B + Cc);
-            for (int k = (int)threadIdx.x / lanes; k < A + B + Cc; k += 256 / lanes) {
-                int jx, jy, jz;
-                if (k < A) {
-                    const int f = k / (nx * ny), rem = k % (nx * ny);
-                    jz = f ? nz - 1 : 0; jy = rem / nx; jx = rem % nx;
-                } else if (k < A + B) {
-                    const int k2 = k - A, f = k2 / (nx * nzi), rem = k2 % (nx * nzi);
-                    jy = f ? ny - 1 : 0; jz = (oz ? 1 : 0) + rem / nx; jx = rem % nx;
-                } else {
-                    const int k3 = k - A - B, f = k3 / (nyi * nzi), rem = k3 % (nyi * nzi);
-                    jx = f ? nx - 1 : 0; jz = (oz ? 1 : 0) + rem / nyi; jy = (oy ? 1 : 0) + rem % nyi;
-                }
-                ring_scan_bucket(V, ring_lin(R, x0 + jx, y0 + jy, z0 + jz), qx, qy, qz, bd, bi, threadIdx.x % (uint32_t)lanes, (uint32_t)lanes);
-            }
-        }
+        const RingShell S = ring_shell(R, cx, cy, cz, r, wild);
+        const int lanes = ring_lanes_per_bucket(R, S.total);
+        for (int k = (int)threadIdx.x / lanes; k < S.total; k += 256 / lanes)
+            ring_scan_bucket(V, ring_shell_bucket(R, S, k), qx, qy, qz, bd, bi, threadIdx.x % (uint32_t)lanes, (uint32_t)lanes);
         block_argmin256(bd, bi, s_d, s_i);
         double bound;
-        if (!ring_open_face_bound(R, ox, oy, oz, cx, cy, cz, r, qx, qy, qz, bound)) break;      // every bucket has been visited
+        if (!ring_open_face_bound(R, S.ox, S.oy, S.oz, cx, cy, cz, r, qx, qy, qz, bound)) break;      // every bucket has been visited
         if (bound > 0.0 && (bd <= bound * bound || bound * bound >= stop_d2)) break;
     }
 }

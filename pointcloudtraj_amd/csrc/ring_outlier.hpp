@@ -6,7 +6,8 @@
 //   1. ring_outlier_judge_kernel   read-only over the bucket table.  EIGHT LANES PER JUDGED ROW, 32 rows per 256-thread block (a
 //                                  block per row, as ring_count_kernel spends, is right for a tick's few hundred queries and wrong
 //                                  for the 3 000 .. 300 000 rows of a frame or the 5 M of a window).  The eight lanes split every
-//                                  bucket's [head, tail) records (the `part` / `lanes` split of ring_scan_bucket).  The row's own
+//                                  bucket's [head, tail) records (ring_for_records, ring_search.hpp: the record loop of the radius
+//                                  count, with `part` / `lanes` = this lane of eight).  The row's own
 //                                  bucket comes first -- on a surface window it alone usually reaches m -- then the rest of the
 //                                  ball's box (ring_ball_box: the fold and wild-axis rules stay where they are; the box never names
 //                                  a bucket twice, and the own bucket is skipped by its table position when the walk meets it
@@ -47,12 +48,9 @@ __device__ __forceinline__ uint32_t ro_scan(const float4 *__restrict__ base, uin
                                             uint32_t self, double qx, double qy, double qz, double r2, uint32_t &npts)
 {
     uint32_t c = 0;
-    for (uint32_t j = part; j < n; j += kRoLanes) {
-        const float4 P = base[(head + j) & mask];
-        const uint32_t id = __float_as_uint(P.w);
-        npts++;
-        if (id != kRingDead && id != self && dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz) <= r2) c++;
-    }
+    ring_for_records(base, head, n, mask, part, kRoLanes, qx, qy, qz, npts, [&](double d2, uint32_t id) {
+        if (id != self && d2 <= r2) c++;
+    });
     return c;
 }
 
@@ -118,10 +116,7 @@ __global__ __launch_bounds__(256) void ring_outlier_judge_kernel(RingView V, RcW
     }
     if (WORK) {
         ring_add_work(work, npts, part == 0 ? walked : 0u, s_w);
-        unsigned long long o = part == 0 ? own : 0u;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) o += (unsigned long long)__shfl_xor((long long)o, off, kWave);
-        if ((threadIdx.x & 63) == 0 && o) atomicAdd(&work[blockIdx.x & (kWorkSlots - 1)].nodes, o);
+        ring_add_nodes(work, part == 0 ? own : 0u);
     }
 }
 

@@ -11,12 +11,15 @@
 // bucket that can matter.
 //
 // Unlike the minimum of ring_block_nn_search, a count and a list are not idempotent, so what "visits" means differs:
-//   * count / fill walk the box of world cells the ball can touch, folded onto the table.  On an axis where the box spans the table
-//     (or the query / radius is wild) the g table positions are visited once each instead of the span, so no bucket is read twice.
-//   * k-NN walks the expanding cube of ring_block_nn_search, which revisits the whole box when an axis closes.  Its insert is
-//     IDEMPOTENT instead: a candidate whose (d2, slot) equals an entry already in the list is dropped (ring_knn_insert).  A record
-//     that was seen before and is no longer in the list was evicted by better ones, so it is still worse than tau and never gets
-//     as far as the insert.
+//   * count / fill walk the box of world cells the ball can touch, folded onto the table (ring_for_ball).  On an axis where the box
+//     spans the table (or the query / radius is wild) the g table positions are visited once each instead of the span, so no
+//     bucket is read twice.
+//   * k-NN walks the expanding cube (ring_knn_walk over ring_shell, ring.hpp: the enumeration and its exactness argument are
+//     ring_block_nn_search's), which revisits the whole box when an axis closes.  Its insert is IDEMPOTENT instead: a candidate
+//     whose (d2, slot) equals an entry already in the list is dropped (ring_knn_insert).  A record that was seen before and is no
+//     longer in the list was evicted by better ones, so it is still worse than tau and never gets as far as the insert.
+// ring_knn_walk is also the walk of the statistical filter (ring_statistical.hpp: a wave per row instead of a block per query), and
+// ring_for_records, the record loop under ring_for_ball, is the outlier judge's too (ring_outlier.hpp).
 #pragma once
 #include "ring.hpp"
 #include "knn.hpp"
@@ -44,6 +47,15 @@ __device__ __forceinline__ void ring_add_work(WorkCounters *__restrict__ work, u
     }
 }
 
+// the third counter of the kernels that judge rows (what `nodes` counts is theirs to say): summed per wave, one atomic for each
+__device__ __forceinline__ void ring_add_nodes(WorkCounters *__restrict__ work, uint32_t nodes)
+{
+    unsigned long long o = nodes;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) o += (unsigned long long)__shfl_xor((long long)o, off, kWave);
+    if ((threadIdx.x & 63) == 0 && o) atomicAdd(&work[blockIdx.x & (kWorkSlots - 1)].nodes, o);
+}
+
 // ---- the ball's box ---------------------------------------------------------------------------------------------------------
 // Table positions a ball (q, |r|) can touch: per axis the world cells cell(q - |r|) - 1 .. cell(q + |r|) + 1.  The fp64 products
 // that place a point and the two ends err by a few ulp, far less than the cell of slack on either side, and exactness comes from
@@ -69,20 +81,27 @@ __device__ __forceinline__ RingBox ring_ball_box(const RingDesc &R, double qx, d
     return B;
 }
 
+// The record loop: this lane's share (records part, part + lanes, ..) of the n records from `head` of a queue of mask + 1 places --
+// a bucket or the overflow queue.  Every read is counted in npts, a dead record is skipped, f(d2, slot) for the rest.
+template <typename F>
+__device__ __forceinline__ void ring_for_records(const float4 *__restrict__ base, uint32_t head, uint32_t n, uint32_t mask, uint32_t part,
+                                                 uint32_t lanes, double qx, double qy, double qz, uint32_t &npts, F f)
+{
+    for (uint32_t j = part; j < n; j += lanes) {
+        const float4 P = base[(head + j) & mask];
+        const uint32_t id = __float_as_uint(P.w);
+        npts++;
+        if (id != kRingDead) f(dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz), id);
+    }
+}
+
 // every live record of the overflow queue and of the box's buckets, once: f(d2, slot).  Returns through npts / nbuckets what was read.
 template <typename F>
 __device__ __forceinline__ void ring_for_ball(const RingView &V, double qx, double qy, double qz, double ra, uint32_t &npts, uint32_t &nbuckets, F f)
 {
     const RingDesc &R = V.R;
-    {
-        const uint32_t oh = V.st->ovf_head, on = V.st->ovf_tail - oh;
-        for (uint32_t k = threadIdx.x; k < on; k += 256u) {
-            const float4 P = V.ovf[(oh + k) & R.ovf_mask];
-            const uint32_t id = __float_as_uint(P.w);
-            npts++;
-            if (id != kRingDead) f(dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz), id);
-        }
-    }
+    const uint32_t oh = V.st->ovf_head;
+    ring_for_records(V.ovf, oh, V.st->ovf_tail - oh, R.ovf_mask, threadIdx.x, 256u, qx, qy, qz, npts, f);
     const RingBox B = ring_ball_box(R, qx, qy, qz, ra);
     const int total = B.nx * B.ny * B.nz;                   // at most the table: 2^24 buckets
     // grown buckets: the ball's records sit in a few fat buckets among many empty ones, so eight lanes share a bucket in larger boxes too
@@ -95,12 +114,7 @@ __device__ __forceinline__ void ring_for_ball(const RingView &V, double qx, doub
         const uint32_t n = m.y - m.x;
         const float4 *base = V.slots + (size_t)b * R.K;
         if (part == 0) nbuckets++;
-        for (uint32_t j = part; j < n; j += (uint32_t)lanes) {
-            const float4 P = base[(m.x + j) & (R.K - 1)];
-            const uint32_t id = __float_as_uint(P.w);
-            npts++;
-            if (id != kRingDead) f(dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz), id);
-        }
+        ring_for_records(base, m.x, n, R.K - 1, part, (uint32_t)lanes, qx, qy, qz, npts, f);
     }
 }
 
@@ -190,55 +204,74 @@ __device__ __forceinline__ void ring_knn_offer(double *ld, uint32_t *li, int k, 
     }
 }
 
-// The cube / shell of Chebyshev radius r around the query's cell, as ring_block_nn_search enumerates it: the whole box for the first
-// cube, for a wild query and when an axis has just closed (2r + 1 reaches the table size: the axis' g positions, once each), the
-// shell's six faces otherwise.
-struct RingShell {
-    int nx, ny, nz, x0, y0, z0, nyi, nzi, A, B, total;
-    bool ox, oy, oz, box;
-};
-
-__device__ __forceinline__ RingShell ring_shell(const RingDesc &R, int cx, int cy, int cz, int r, bool wild)
+// The k-NN walk: the overflow queue exhaustively, then the expanding cube (ring_shell, ring.hpp), every live record other than
+// `self` offered to this wave's sorted list (ld, li), until the list holds k entries and tau <= bound^2 (ring_open_face_bound: every
+// unseen record is then strictly farther than entry k - 1) or no axis is open.  GROUP threads share the walk -- a whole number of
+// waves, t = this thread's place among them -- and everything in it is uniform over the group.  lanes_of(total) = the threads that
+// share one bucket of a step with `total` buckets (a power of two, at most 64).  step(td, ti) runs after the queue and the first
+// cube and after every further shell, and leaves in (td, ti) the tau to go on with: the group's waves may meet there.  The lanes of
+// a wave insert together, so the bucket and record loops run while ANY lane of the wave has a bucket / a record left; that is why
+// the record loop is not ring_for_records.  npts / nbuckets: records read, buckets visited.
+template <int GROUP, typename Lanes, typename Step>
+__device__ __forceinline__ void ring_knn_walk(const RingView &V, double qx, double qy, double qz, uint32_t t, uint32_t self, double *ld,
+                                              uint32_t *li, int k, uint32_t &npts, uint32_t &nbuckets, Lanes lanes_of, Step step)
 {
-    RingShell S;
-    S.ox = !wild && 2 * r + 1 < R.gx; S.oy = !wild && 2 * r + 1 < R.gy; S.oz = !wild && 2 * r + 1 < R.gz;
-    const bool was_x = !wild && 2 * r - 1 < R.gx, was_y = !wild && 2 * r - 1 < R.gy, was_z = !wild && 2 * r - 1 < R.gz;
-    S.nx = S.ox ? 2 * r + 1 : R.gx; S.ny = S.oy ? 2 * r + 1 : R.gy; S.nz = S.oz ? 2 * r + 1 : R.gz;
-    S.x0 = S.ox ? cx - r : 0; S.y0 = S.oy ? cy - r : 0; S.z0 = S.oz ? cz - r : 0;
-    S.box = r == 1 || (!S.ox && was_x) || (!S.oy && was_y) || (!S.oz && was_z);
-    S.nyi = S.oy ? S.ny - 2 : S.ny; S.nzi = S.oz ? S.nz - 2 : S.nz;
-    S.A = S.oz ? 2 * S.nx * S.ny : 0;
-    S.B = S.oy ? 2 * S.nx * S.nzi : 0;
-    S.total = S.box ? S.nx * S.ny * S.nz : S.A + S.B + (S.ox ? 2 * S.nyi * S.nzi : 0);
-    return S;
-}
-
-__device__ __forceinline__ uint32_t ring_shell_bucket(const RingDesc &R, const RingShell &S, int k)
-{
-    int jx, jy, jz;
-    if (S.box) {
-        jx = k % S.nx; jy = (k / S.nx) % S.ny; jz = k / (S.nx * S.ny);
-    } else if (k < S.A) {                                   // two z-faces
-        const int f = k / (S.nx * S.ny), rem = k % (S.nx * S.ny);
-        jz = f ? S.nz - 1 : 0; jy = rem / S.nx; jx = rem % S.nx;
-    } else if (k < S.A + S.B) {                             // two y-faces without the z-face rows
-        const int k2 = k - S.A, f = k2 / (S.nx * S.nzi), rem = k2 % (S.nx * S.nzi);
-        jy = f ? S.ny - 1 : 0; jz = (S.oz ? 1 : 0) + rem / S.nx; jx = rem % S.nx;
-    } else {                                                // two x-faces without either
-        const int k3 = k - S.A - S.B, f = k3 / (S.nyi * S.nzi), rem = k3 % (S.nyi * S.nzi);
-        jx = f ? S.nx - 1 : 0; jz = (S.oz ? 1 : 0) + rem / S.nyi; jy = (S.oy ? 1 : 0) + rem % S.nyi;
+    const RingDesc &R = V.R;
+    const int lane = (int)(t & 63u);
+    double td = __builtin_huge_val();
+    uint32_t ti = kNoIndex;
+    {   // wave-uniform trip count; beyond the end: the last entry again
+        const uint32_t oh = V.st->ovf_head, on = V.st->ovf_tail - oh;
+        for (uint32_t k0 = 0; k0 < on; k0 += (uint32_t)GROUP) {
+            const uint32_t e = k0 + t;
+            const bool have = e < on;
+            const float4 P = V.ovf[(oh + (have ? e : on - 1u)) & R.ovf_mask];
+            const uint32_t id = __float_as_uint(P.w);
+            npts += have ? 1u : 0u;
+            ring_knn_offer(ld, li, k, lane, have && id != kRingDead && id != self, dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz), id, td, ti);
+        }
     }
-    return ring_lin(R, S.x0 + jx, S.y0 + jy, S.z0 + jz);
+    bool wild = false;
+    const int cx = ring_cell_coord(qx, R.inv_h, wild), cy = ring_cell_coord(qy, R.inv_h, wild), cz = ring_cell_coord(qz, R.inv_h, wild);
+    for (int r = 1;; r++) {
+        const RingShell S = ring_shell(R, cx, cy, cz, r, wild);
+        const int lanes = lanes_of(S.total);
+        const uint32_t part = t % (uint32_t)lanes;
+        for (int k0 = 0; k0 < S.total; k0 += GROUP / lanes) {
+            const int kb = k0 + (int)t / lanes;
+            const bool live = kb < S.total;
+            uint2 m = make_uint2(0u, 0u);
+            uint32_t b = 0;
+            if (live) { b = ring_shell_bucket(R, S, kb); m = V.ht[b]; }
+            const uint32_t n = m.y - m.x;
+            const float4 *base = V.slots + (size_t)b * R.K;
+            if (live && part == 0) nbuckets++;
+            for (uint32_t j = part; __builtin_amdgcn_ballot_w64(j < n); j += (uint32_t)lanes) {
+                const bool have = j < n;
+                double d2 = __builtin_huge_val();
+                uint32_t id = kRingDead;
+                if (have) {
+                    const float4 P = base[(m.x + j) & (R.K - 1)];
+                    d2 = dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz);
+                    id = __float_as_uint(P.w);
+                    npts++;
+                }
+                ring_knn_offer(ld, li, k, lane, have && id != kRingDead && id != self, d2, id, td, ti);
+            }
+        }
+        step(td, ti);
+        double bound;
+        if (!ring_open_face_bound(R, S.ox, S.oy, S.oz, cx, cy, cz, r, qx, qy, qz, bound)) break;      // every bucket has been visited
+        if (bound > 0.0 && td <= bound * bound) break;              // td < +inf: the list is full
+    }
 }
 
 // Row i of idx / d2 = the k best live records of query i by better().  Each of the block's four waves owns one sorted list in LDS
-// (lane e owns entry e, knn_wave_insert); wave 0's is the block's list.  After the overflow queue and the first cube, and after
-// every further shell, wave 0 folds the other three lists into its own, they start empty again, and the folded tau (entry k - 1)
-// goes back to every lane's registers: a record costs its distance and one compare unless it beats tau.  The walk stops when the
-// list holds k entries and tau <= bound^2, bound = the least distance to an open face of the cube minus h/256 as in
-// ring_block_nn_search -- every unseen record is then strictly farther than entry k - 1 -- or when no axis is open (every bucket has
-// been visited).  The box of a step whose axis has just closed holds the buckets seen before: the insert drops what the list
-// already has (top of this file), in wave 0 directly and in the fold for what another wave collected.
+// (lane e owns entry e, knn_wave_insert); wave 0's is the block's list.  The block shares one ring_knn_walk; its step: wave 0 folds
+// the other three lists into its own, they start empty again, and the folded tau (entry k - 1) goes back to every lane's registers
+// -- a record costs its distance and one compare unless it beats tau.  The box of a step whose axis has just closed holds the
+// buckets seen before: the insert drops what the list already has (top of this file), in wave 0 directly and in the fold for what
+// another wave collected.
 // A query with a NaN or infinite coordinate has no record at a finite d2 and keeps the padded row it starts with; so do the slots
 // beyond the number of records at a finite d2.
 template <int KCAP>
@@ -250,7 +283,6 @@ __global__ __launch_bounds__(256) void ring_knn_kernel(RingView V, const float *
     __shared__ unsigned long long s_w[8];
     __shared__ double s_tau_d;                              // the folded tau: written by wave 0 between a step's two barriers only, so
     __shared__ uint32_t s_tau_i;                            // every wave reads the same value and takes the same way out of the walk
-    const RingDesc &R = V.R;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t slot = blockIdx.x;
     const float qxf = q[3 * slot], qyf = q[3 * slot + 1], qzf = q[3 * slot + 2];
@@ -258,74 +290,32 @@ __global__ __launch_bounds__(256) void ring_knn_kernel(RingView V, const float *
     uint32_t *li = s_i[wave];
     if (lane < k) { ld[lane] = __builtin_huge_val(); li[lane] = kNoIndex; }
     knn_lds_order();
-    double td = __builtin_huge_val();
-    uint32_t ti = kNoIndex;
+    // the walk's step (it holds copies of k, lane, wave and the list pointers): the fold between two block barriers
+    const auto fold = [=](double &td, uint32_t &ti) {
+        __syncthreads();
+        if (wave == 0) {
+            for (int w = 1; w < 4; w++) {
+                for (int e = 0; e < k; e++) {                   // a sorted source is done at its first entry that does not beat tau
+                    const double cd = s_d[w][e];
+                    const uint32_t ci = s_i[w][e];
+                    if (!(cd < __builtin_huge_val()) || !better(cd, ci, ld[k - 1], li[k - 1])) break;
+                    ring_knn_insert(ld, li, k, lane, cd, ci);
+                }
+            }
+            if (lane == 0) { s_tau_d = ld[k - 1]; s_tau_i = li[k - 1]; }
+        }
+        __syncthreads();
+        td = s_tau_d;
+        ti = s_tau_i;
+        if (wave != 0 && lane < k) { ld[lane] = __builtin_huge_val(); li[lane] = kNoIndex; }
+        knn_lds_order();
+    };
     uint32_t npts = 0, nbuckets = 0;
     const float finf = __builtin_huge_valf();
-    if (V.st->count != 0 && fabsf(qxf) < finf && fabsf(qyf) < finf && fabsf(qzf) < finf) {          // block-uniform
-        const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-        {   // overflow queue: exhaustive, once; wave-uniform trip count
-            const uint32_t oh = V.st->ovf_head, on = V.st->ovf_tail - oh;
-            for (uint32_t k0 = 0; k0 < on; k0 += 256u) {
-                const uint32_t e = k0 + threadIdx.x;
-                const bool have = e < on;
-                const float4 P = V.ovf[(oh + (have ? e : on - 1u)) & R.ovf_mask];
-                const uint32_t id = __float_as_uint(P.w);
-                npts += have ? 1u : 0u;
-                ring_knn_offer(ld, li, k, lane, have && id != kRingDead, dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz), id, td, ti);
-            }
-        }
-        bool wild = false;
-        const int cx = ring_cell_coord(qx, R.inv_h, wild), cy = ring_cell_coord(qy, R.inv_h, wild), cz = ring_cell_coord(qz, R.inv_h, wild);
-        for (int r = 1;; r++) {
-            const RingShell S = ring_shell(R, cx, cy, cz, r, wild);
-            const int lanes = ring_lanes_per_bucket(R, S.total);
-            const uint32_t part = threadIdx.x % (uint32_t)lanes;
-            // the lanes of a wave insert together: both loops run while ANY lane of the wave has a bucket / a record left
-            for (int k0 = 0; k0 < S.total; k0 += 256 / lanes) {
-                const int kb = k0 + (int)threadIdx.x / lanes;
-                const bool live = kb < S.total;
-                uint2 m = make_uint2(0u, 0u);
-                uint32_t b = 0;
-                if (live) { b = ring_shell_bucket(R, S, kb); m = V.ht[b]; }
-                const uint32_t n = m.y - m.x;
-                const float4 *base = V.slots + (size_t)b * R.K;
-                if (live && part == 0) nbuckets++;
-                for (uint32_t j = part; __builtin_amdgcn_ballot_w64(j < n); j += (uint32_t)lanes) {
-                    const bool have = j < n;
-                    double d2 = __builtin_huge_val();
-                    uint32_t id = kRingDead;
-                    if (have) {
-                        const float4 P = base[(m.x + j) & (R.K - 1)];
-                        d2 = dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz);
-                        id = __float_as_uint(P.w);
-                        npts++;
-                    }
-                    ring_knn_offer(ld, li, k, lane, have && id != kRingDead, d2, id, td, ti);
-                }
-            }
-            __syncthreads();
-            if (wave == 0) {
-                for (int w = 1; w < 4; w++) {
-                    for (int e = 0; e < k; e++) {               // a sorted source is done at its first entry that does not beat tau
-                        const double cd = s_d[w][e];
-                        const uint32_t ci = s_i[w][e];
-                        if (!(cd < __builtin_huge_val()) || !better(cd, ci, ld[k - 1], li[k - 1])) break;
-                        ring_knn_insert(ld, li, k, lane, cd, ci);
-                    }
-                }
-                if (lane == 0) { s_tau_d = ld[k - 1]; s_tau_i = li[k - 1]; }
-            }
-            __syncthreads();
-            td = s_tau_d;
-            ti = s_tau_i;
-            if (wave != 0 && lane < k) { ld[lane] = __builtin_huge_val(); li[lane] = kNoIndex; }
-            knn_lds_order();
-            double bound;
-            if (!ring_open_face_bound(R, S.ox, S.oy, S.oz, cx, cy, cz, r, qx, qy, qz, bound)) break;      // every bucket has been visited
-            if (bound > 0.0 && td <= bound * bound) break;              // td < +inf: the list is full
-        }
-    }
+    if (V.st->count != 0 && fabsf(qxf) < finf && fabsf(qyf) < finf && fabsf(qzf) < finf)            // block-uniform
+        // no record is the query's own: `self` = kRingDead folds into the walk's dead-record test
+        ring_knn_walk<256>(V, (double)qxf, (double)qyf, (double)qzf, threadIdx.x, kRingDead, ld, li, k, npts, nbuckets,
+                           [&](int total) { return ring_lanes_per_bucket(V.R, total); }, fold);
     __syncthreads();
     if (wave == 0 && lane < k) {
         const double d = s_d[0][lane];

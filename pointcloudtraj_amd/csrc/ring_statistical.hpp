@@ -8,10 +8,9 @@
 //                             row with two block barriers per shell, as ring_knn_kernel spends, is right for a tick's few hundred
 //                             queries and wrong for the 50 000 rows of a frame or the 5 M of a window).  The four waves walk different
 //                             rows with different trip counts, so nothing in the walk is block-wide: each wave owns one sorted list in
-//                             LDS (lane e owns entry e, knn_wave_insert) and tau = entry k - 1 stays in registers.  The walk is that of
-//                             ring_knn_kernel: the overflow queue first and exhaustively, then the expanding cube (ring_shell), the
-//                             idempotent insert (a step whose axis has just closed revisits buckets), the same termination test.  A
-//                             record whose id is the judged slot or kRingDead is never offered.  Epilogue: lane 0 sums the k entries
+//                             LDS (lane e owns entry e, knn_wave_insert) and tau = entry k - 1 stays in registers.  The walk is
+//                             ring_knn_walk (ring_search.hpp), the one ring_knn_kernel calls, here with a group of 64, the judged
+//                             slot as `self`, ks_lanes_per_bucket and an empty step.  Epilogue: lane 0 sums the k entries
 //                             in list order (nearest first) with the sqrt and writes mean[slot]; a row with fewer than k candidates
 //                             gets +inf.  The host has filled the buffer with NaN beforehand (rows out of scope, rows with a NaN).
 //   2. ks_reduce_kernel       the sums in the contract's tree order: a block folds 256 consecutive values by halves (h = 128 and 64
@@ -60,7 +59,6 @@ __global__ __launch_bounds__(256) void ring_knn_mean_kernel(RingView V, RcWindow
     __shared__ double s_d[kKsRows][KCAP];
     __shared__ uint32_t s_i[kKsRows][KCAP];
     __shared__ unsigned long long s_w[8];
-    const RingDesc &R = V.R;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t p = (uint64_t)p0 + (uint64_t)blockIdx.x * kKsRows + (uint64_t)wave;
     uint32_t npts = 0, nbuckets = 0, walked = 0;
@@ -72,58 +70,13 @@ __global__ __launch_bounds__(256) void ring_knn_mean_kernel(RingView V, RcWindow
             uint32_t *li = s_i[wave];
             if (lane < k) { ld[lane] = __builtin_huge_val(); li[lane] = kNoIndex; }
             knn_lds_order();
-            double td = __builtin_huge_val();
-            uint32_t ti = kNoIndex;
             const float finf = __builtin_huge_valf();
             // a row with an infinite coordinate: every d2 that involves it is inf or NaN, it has no candidate
             if (fabsf(px) < finf && fabsf(py) < finf && fabsf(pz) < finf) {
-                const double qx = (double)px, qy = (double)py, qz = (double)pz;
                 if (WORK) walked = 1;
-                {   // overflow queue: exhaustive, once
-                    const uint32_t oh = V.st->ovf_head, on = V.st->ovf_tail - oh;
-                    for (uint32_t k0 = 0; k0 < on; k0 += 64u) {
-                        const uint32_t e = k0 + (uint32_t)lane;
-                        const bool have = e < on;
-                        const float4 P = V.ovf[(oh + (have ? e : on - 1u)) & R.ovf_mask];
-                        const uint32_t id = __float_as_uint(P.w);
-                        npts += have ? 1u : 0u;
-                        ring_knn_offer(ld, li, k, lane, have && id != kRingDead && id != slot,
-                                       dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz), id, td, ti);
-                    }
-                }
-                bool wild = false;
-                const int cx = ring_cell_coord(qx, R.inv_h, wild), cy = ring_cell_coord(qy, R.inv_h, wild), cz = ring_cell_coord(qz, R.inv_h, wild);
-                for (int r = 1;; r++) {
-                    const RingShell S = ring_shell(R, cx, cy, cz, r, wild);
-                    const int lanes = ks_lanes_per_bucket(S.total);
-                    const uint32_t part = (uint32_t)lane % (uint32_t)lanes;
-                    // the lanes of the wave insert together: both loops run while ANY lane has a bucket / a record left
-                    for (int k0 = 0; k0 < S.total; k0 += 64 / lanes) {
-                        const int kb = k0 + lane / lanes;
-                        const bool live = kb < S.total;
-                        uint2 m = make_uint2(0u, 0u);
-                        uint32_t b = 0;
-                        if (live) { b = ring_shell_bucket(R, S, kb); m = V.ht[b]; }
-                        const uint32_t n = m.y - m.x;
-                        const float4 *base = V.slots + (size_t)b * R.K;
-                        if (WORK && live && part == 0) nbuckets++;
-                        for (uint32_t j = part; __builtin_amdgcn_ballot_w64(j < n); j += (uint32_t)lanes) {
-                            const bool have = j < n;
-                            double d2 = __builtin_huge_val();
-                            uint32_t id = kRingDead;
-                            if (have) {
-                                const float4 P = base[(m.x + j) & (R.K - 1)];
-                                d2 = dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz);
-                                id = __float_as_uint(P.w);
-                                npts++;
-                            }
-                            ring_knn_offer(ld, li, k, lane, have && id != kRingDead && id != slot, d2, id, td, ti);
-                        }
-                    }
-                    double bound;
-                    if (!ring_open_face_bound(R, S.ox, S.oy, S.oz, cx, cy, cz, r, qx, qy, qz, bound)) break;      // every bucket has been visited
-                    if (bound > 0.0 && td <= bound * bound) break;              // td < +inf: the list is full
-                }
+                // the wave walks alone: tau stays in its registers, the step has nothing to do
+                ring_knn_walk<64>(V, (double)px, (double)py, (double)pz, (uint32_t)lane, slot, ld, li, k, npts, nbuckets, ks_lanes_per_bucket,
+                                  [](double &, uint32_t &) {});
             }
             knn_lds_order();
             if (lane == 0) {
@@ -139,7 +92,7 @@ __global__ __launch_bounds__(256) void ring_knn_mean_kernel(RingView V, RcWindow
     }
     if (WORK) {
         ring_add_work(work, npts, nbuckets, s_w);
-        if (lane == 0 && walked) atomicAdd(&work[blockIdx.x & (kWorkSlots - 1)].nodes, 1ull);
+        ring_add_nodes(work, lane == 0 ? walked : 0u);
     }
 }
 

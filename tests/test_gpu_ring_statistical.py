@@ -199,6 +199,40 @@ def test_exactly_k_plus_one_and_exactly_k_finite_rows(E):
     c.close()
 
 
+def small_table(E, cap):
+    """the 8 x 8 x 8 table of tests/test_gpu_ring_search.py: the cube of a walk that goes on past r = 3 wraps around it"""
+    c, w = E.Cloud(cap), T.StatisticalWindow(cap)
+    c.ring_index(2.0, (8.0, 8.0, 8.0))
+    assert all(d <= 8 for d in c.ring_info()["dims"]), c.ring_info()
+    return c, w
+
+
+def test_means_on_a_small_table_with_folding_and_closed_axes(E):
+    """a window that drifts away over an 8 x 8 x 8 table: several world cells share a bucket, and a row whose k candidates lie
+    frames apart walks until its axes close -- the box of such a step names buckets the list has seen (the idempotent insert)"""
+    c, w = small_table(E, 1000)
+    for f in range(9):
+        drift = np.float32([17.0 * f, -3.0 * f, 0.5 * f])
+        feed(c, w, (synth.uniform_points(120, 120, 0.0, 10.0, offset=f * 120) + drift).astype(np.float32))
+        if f in (2, 5, 8):
+            for k in (1, 7, 64):
+                check_means(c, w, k, tag=f"frame {f}")
+    assert (w.count, w.nxt) == (1000, 80), "the ring has wrapped"
+    c.close()
+
+
+def test_fewer_rows_than_k_plus_one_on_a_small_table(E):
+    """50 rows under k = 64: every axis of the 8 x 8 x 8 table closes before a list fills, and no row is measured; under k = 49
+    every row's list is exactly the other 49"""
+    c, w = small_table(E, 50)
+    feed(c, w, synth.uniform_points(150, 50, 0.0, 10.0))
+    assert check_means(c, w, 64, tag="50 rows").tolist() == [INF] * 50
+    assert check_stats(c, w, 64, 1.0, tag="50 rows")["measured"] == 0
+    assert np.isfinite(check_means(c, w, 49, tag="50 rows")).all()
+    assert check_stats(c, w, 49, 1.0, tag="50 rows")["measured"] == 50
+    c.close()
+
+
 # ---- 3. the statistics -------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("n", [255, 256, 257])
