@@ -288,6 +288,38 @@
  * |c_z - val| <= 6.1e-6), so with margin = 0 the next carve by the same image could remove some of them; with a small positive margin
  * (1e-3 on that domain) it cannot.  Sensor simulation -- rendering a world into an image -- is not part of the library.
  *
+ * Segment queries (pct_segment_nn_batch*, pct_segment_inflate_batch): the nearest obstacle point to a LINE SEGMENT, for the questions a
+ * planner asks between two points -- is the straight line to the goal free with the margin, how wide is the free tube around this
+ * edge, can the sphere chain be shortcut -- without sampling the line.  A segment is two planner points a, b (fp64 xyz), each
+ * narrowed to fp32 first, as every planner point is, then widened again; a row p is an fp32 cloud row, widened.  All arithmetic is
+ * fp64, one rounding per operation, no contraction, in exactly this order:  e_k = b_k - a_k;  L2 = (e0*e0 + e1*e1) + e2*e2;
+ * w_k = p_k - a_k;  dot = (w0*e0 + w1*e1) + w2*e2;  s = (L2 == 0) ? 0 : dot / L2;  if (!(s > 0)) s = 0; else if (s > 1) s = 1 (a NaN
+ * becomes 0);  c_k = w_k - s*e_k (one product, one difference);  d2 = (c0*c0 + c1*c1) + c2*c2.  `/` and sqrt are correctly rounded, as
+ * for the statistical outliers above.  A segment with a == b therefore gives exactly the d2 of the nearest-neighbour searches.
+ * Candidates: a row is a candidate iff it is below the size, its d2 is finite and d2 <= reach*reach -- inclusive; an r*r that
+ * overflows is held at DBL_MAX; reach = +inf means every finite d2.  The winner is the best candidate in the engine's order: d2, then
+ * index, the lowest index on ties.  Rows that hold a NaN never win (removed rows and the caller's own NaN rows), nor do rows with an
+ * infinite coordinate, whose d2 is not finite.  Outputs per segment: idx = index_base + slot of the winner, or PCT_NO_INDEX when there
+ * is no candidate; d2 = the winner's d2, or +inf; s = the winner's parameter on the segment (0 at a, 1 at b), or NaN.  "No candidate"
+ * is also the answer for a segment with a non-finite endpoint (judged after the narrowing), a NaN reach and a negative reach.
+ * An empty cloud fills the "no candidate" outputs and the host form returns PCT_ERR_EMPTY (the device form PCT_OK), as for
+ * pct_nn_batch*; Q == 0: PCT_OK; a NULL required pointer or Q < 0: PCT_ERR_INVALID with nothing written.  d2 and s may be NULL in
+ * every form, idx in the inflate form.  algo: PCT_ALGO_STREAM works on any cloud, brute force over the window with every pair in
+ * fp64; PCT_ALGO_RING walks the rolling-map index (the overflow queue, then the buckets of the cells the capsule (segment, reach) can
+ * touch) and needs a live one, PCT_ERR_INVALID otherwise; PCT_ALGO_AUTO takes the ring form on a cloud with a live index and the
+ * streaming form otherwise; PCT_ALGO_GRID and PCT_ALGO_STREAM_EXACT are PCT_ERR_INVALID for this call (there is no grid form and only
+ * one streaming form), as is an unknown algo.  Both forms give the same answers, bit for bit.  Host forms: an append in flight is
+ * finished first, they wait once on the host, and the overflow-queue overrun paragraph above applies as to the other host forms.
+ * Device form: asynchronous on `stream`, no host wait and no allocation inside, ordered after the cloud's mutations like the other
+ * *_dev forms; reserve the batch size first (pct_cloud_reserve_queries).  Capsule inflation (pct_segment_inflate_batch): with d2* the
+ * smallest finite d2 over all rows of the window, or +inf when there is none, radius = min(sqrt(d2*) - search_margin, max_radius),
+ * "min" as pct_inflate_batch writes it (rr < max_radius ? rr : max_radius); radius < 0 means the segment collides, exactly as for
+ * checkTrajPtCol.  idx and s are the winner's when sqrt(d2*) - search_margin < max_radius, PCT_NO_INDEX and NaN otherwise.  An empty
+ * cloud (size 0) follows the engine's empty-cloud rule: radius = max_radius - search_margin, PCT_OK.  The start-distance early-out of
+ * pct_inflate_batch is NOT applied -- a segment has no single distance to the start -- so start and sample_range are not read.  The
+ * walk is bounded by a reach derived from max_radius + search_margin that provably never changes this result (the rounding argument
+ * stands beside the code); the contract is the unbounded formula.
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -549,6 +581,18 @@ typedef struct pct_inflate_params {
  * idx/d2 (optional, may be NULL) = NN, or PCT_NO_INDEX / +inf where the early-out fired. */
 int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *pts, int64_t Q,
                       double *radius, uint32_t *idx, double *d2);
+
+/* Segment queries (contract: top of this file, "Segment queries").  seg: Q x 6 fp64, a then b; reach[Q]; idx[Q], d2[Q], s[Q] -- d2 and
+ * s may be NULL.  algo: PCT_ALGO_AUTO, PCT_ALGO_STREAM or PCT_ALGO_RING; PCT_ALGO_GRID and PCT_ALGO_STREAM_EXACT: PCT_ERR_INVALID.
+ * The device form (device pointers, asynchronous on `stream`) takes its workspace from pct_cloud_reserve_queries. */
+int pct_segment_nn_batch(pct_cloud *c, int algo, const double *seg /* Q x 6: a then b */, const double *reach /* Q */, int64_t Q,
+                         uint32_t *idx, double *d2, double *s);
+int pct_segment_nn_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q,
+                             uint32_t *d_idx, double *d_d2, double *d_s, void *stream);
+/* capsule inflation: radius[Q] = min(sqrt(d2*) - search_margin, max_radius) over the whole window, no start-distance early-out;
+ * idx / s (may be NULL): the winner's where the radius is below max_radius, PCT_NO_INDEX / NaN elsewhere */
+int pct_segment_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *seg, int64_t Q,
+                              double *radius, uint32_t *idx, double *s);
 
 /* ---- one RRT* iteration's three dependent queries in ONE launch (corridor_finder.cpp:385-410 genNewNode, :428-437
  * findNearstVertex, :464 treeRewire's neighbourhood), for K samples at once: nearest tree node of the fp32-narrowed

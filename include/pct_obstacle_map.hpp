@@ -271,6 +271,31 @@ public:
     {
         check(pct_inflate_batch(cloud_, &prm_, pts, n, radius, nn_index, nn_d2), "pct_inflate_batch");
     }
+    // Segment queries (pct_engine.h, paragraph "Segment queries"): what lies between two points, without sampling the line.
+    // segments: n x 6 doubles, a then b.
+    //   segmentSearch    the nearest obstacle point within `reach` of each segment: index (PCT_NO_INDEX: none that near), d2 and the
+    //                    parameter s of the closest point on the segment (0 at a, 1 at b); d2 / s may be null.  On an empty map every
+    //                    segment reports "none".
+    //   checkSegments    capsule inflation with the map's own parameters: radius = min(distance to the nearest obstacle point -
+    //                    search_margin, max_radius), radius < 0 <=> the segment collides with the margin, as checkTrajPtCol judges a
+    //                    point; no start-distance early-out.  nn_index / s name the nearest point where radius < max_radius.
+    //   segmentCollides  one segment: is the straight line from a to b blocked?
+    void segmentSearch(const double *segments, int64_t n, double reach, uint32_t *index, double *d2, double *s)
+    {
+        const std::vector<double> reaches((size_t)(n > 0 ? n : 0), reach);
+        check(pct_segment_nn_batch(cloud_, PCT_ALGO_AUTO, segments, reaches.data(), n, index, d2, s), "pct_segment_nn_batch");
+    }
+    void checkSegments(const double *segments, int64_t n, double *radius, uint32_t *nn_index = nullptr, double *s = nullptr)
+    {
+        check(pct_segment_inflate_batch(cloud_, &prm_, segments, n, radius, nn_index, s), "pct_segment_inflate_batch");
+    }
+    bool segmentCollides(const double a[3], const double b[3])
+    {
+        const double seg[6] = { a[0], a[1], a[2], b[0], b[1], b[2] };
+        double r = 0;
+        checkSegments(seg, 1, &r);
+        return r < 0.0;
+    }
     // corridor_finder.cpp:661-669
     int checkNodeUpdate(double new_radius, double old_radius) const
     {

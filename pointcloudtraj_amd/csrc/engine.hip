@@ -41,6 +41,7 @@
 #include "rsearch.hpp"
 #include "ring_search.hpp"
 #include "bezier_batch.hpp"
+#include "segment.hpp"
 
 using namespace pct;
 using pct_host::pow2_at_least;
@@ -250,6 +251,7 @@ struct pct_cloud {
     int64_t qcap = 0;
     DevBuf<float> d_q, d_r;
     DevBuf<double> d_q64, d_r2, d_d2, d_radius, d_pts64;
+    DevBuf<double> d_seg;                                       // the host forms' staged segments (segment.hpp): 6 doubles each
     DevBuf<uint32_t> d_idx, d_count, d_bound;
     DevBuf<uint32_t> d_todo;                                    // {count, ticket, slots...}: queries the fp32 pyramid walk leaves to the exact one
     DevBuf<unsigned char> d_skip;
@@ -1226,6 +1228,55 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
     });
 }
 
+// ---- segment queries (segment.hpp) -------------------------------------------------------------------------------------------
+enum class SegPath { Table, Stream, Empty };
+
+// `algo` of a segment batch: the rolling-map index or the streaming form; there is no grid form and no second streaming form
+int resolve_segment_algo(const pct_cloud *c, int algo, SegPath *path)
+{
+    if (algo != PCT_ALGO_AUTO && algo != PCT_ALGO_STREAM && algo != PCT_ALGO_RING)
+        return fail(PCT_ERR_INVALID, "segment queries take PCT_ALGO_AUTO, PCT_ALGO_STREAM or PCT_ALGO_RING, not algo %d", algo);
+    if (algo == PCT_ALGO_RING && !c->ring_ready && !(c->ring_on && c->count == 0))
+        return fail(PCT_ERR_INVALID, "PCT_ALGO_RING without a rolling-map index (call pct_cloud_ring_index)");
+    if (c->count == 0) *path = SegPath::Empty;
+    else if (algo == PCT_ALGO_RING || (algo == PCT_ALGO_AUTO && c->ring_ready)) *path = SegPath::Table;
+    else *path = SegPath::Stream;
+    return PCT_OK;
+}
+
+// nearest row to every segment of a device-resident batch (d_seg: Q x 6); d_reach == nullptr: reach_all for every segment.
+// d_d2 / d_s may be NULL.  Q >= 1, within the reserved batch size.
+int segment_run(pct_cloud *c, SegPath path, const double *d_seg, const double *d_reach, double reach_all, int64_t Q, uint32_t *d_idx,
+                double *d_d2, double *d_s, hipStream_t s)
+{
+    switch (path) {
+    case SegPath::Empty:
+        segment_fill_none_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_idx, d_d2, d_s, (uint32_t)Q);
+        HIPCHK(hipGetLastError());
+        return PCT_OK;
+    case SegPath::Table:     // rolling-map index: a block per segment over the buckets of the capsule's box
+        return launch_frame(c, s, Q, { Work::Device }, [&] {
+            ring_segment_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_seg, d_reach, reach_all, (uint32_t)c->index_base, d_idx, d_d2, d_s,
+                                                       c->count_work ? c->d_work : nullptr);
+        });
+    default:
+        break;
+    }
+    // streaming: slices of part_q segments through the partial buffers; the s partials borrow the filter's candidate distances
+    // (part_q x kCandCap doubles, scratch between batches)
+    const int parts = (int)std::min<int64_t>(kSegParts, std::max<int64_t>(1, (c->count + 255) / 256));
+    return launch_frame(c, s, Q, { Work::EveryPoint }, [&] {
+        for (int64_t off = 0; off < Q; off += c->part_q) {
+            const int qn = (int)std::min<int64_t>(c->part_q, Q - off);
+            segment_stream_kernel<<<dim3(parts, ceil_div(qn, kSegTile)), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg + 6 * off,
+                                                                                      d_reach ? d_reach + off : nullptr, reach_all, (uint32_t)qn,
+                                                                                      c->d_part_d2, c->d_part_idx, c->d_cand_d2);
+            segment_finish_kernel<<<qn, 64, 0, s>>>(c->d_part_d2, c->d_part_idx, c->d_cand_d2, (uint32_t)parts, (uint32_t)c->index_base, d_idx + off,
+                                                    d_d2 ? d_d2 + off : nullptr, d_s ? d_s + off : nullptr);
+        }
+    });
+}
+
 // ---- radius search with lists (rsearch.hpp) ----------------------------------------------------------------------------------
 // scan / cursor / queue workspaces, sized with the query workspaces (pct_cloud_reserve_queries)
 int rs_ensure_work(pct_cloud *c)
@@ -1757,7 +1808,7 @@ int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)
     c->qcap = 0;
     c->generation++;                    // captured plans hold these pointers
     c->d_q.release(); c->d_r.release(); c->d_q64.release(); c->d_r2.release(); c->d_d2.release(); c->d_radius.release();
-    c->d_pts64.release(); c->d_idx.release(); c->d_count.release(); c->d_skip.release(); c->d_bound.release();
+    c->d_pts64.release(); c->d_idx.release(); c->d_count.release(); c->d_skip.release(); c->d_bound.release(); c->d_seg.release();
     c->d_part_d2.release(); c->d_part_idx.release(); c->d_cand_count.release(); c->d_cand_d2.release(); c->d_cand_idx.release();
     c->d_ovf.release(); c->d_qsorted.release(); c->d_todo.release();
     PCTCHK(c->d_q.reset(3 * q));
@@ -1767,6 +1818,7 @@ int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)
     PCTCHK(c->d_d2.reset(q));
     PCTCHK(c->d_radius.reset(q));
     PCTCHK(c->d_pts64.reset(3 * q));
+    PCTCHK(c->d_seg.reset(6 * q));
     PCTCHK(c->d_idx.reset(q));
     PCTCHK(c->d_count.reset(q));
     PCTCHK(c->d_skip.reset(q));
@@ -2353,6 +2405,85 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
     if (d2) HIPCHK(hipMemcpyAsync(d2, c->d_d2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
     return PCT_OK;
+}
+
+// ---- segment queries (include/pct_engine.h, "Segment queries") ------------------------------------------------------------------
+int pct_segment_nn_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q, uint32_t *d_idx, double *d_d2,
+                             double *d_s, void *stream)
+{
+    if (!c || Q < 0 || (Q > 0 && (!d_seg || !d_reach || !d_idx))) return fail(PCT_ERR_INVALID, "bad segment_nn_batch_dev arguments");
+    SegPath path;
+    PCTCHK(resolve_segment_algo(c, algo, &path));
+    if (Q == 0) return PCT_OK;
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(order_after_mutations(c, (hipStream_t)stream));
+    return segment_run(c, path, d_seg, d_reach, 0.0, Q, d_idx, d_d2, d_s, (hipStream_t)stream);
+}
+
+int pct_segment_nn_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, uint32_t *idx, double *d2, double *s)
+{
+    if (!c || Q < 0 || (Q > 0 && (!seg || !reach || !idx))) return fail(PCT_ERR_INVALID, "bad segment_nn_batch arguments");
+    PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
+    SegPath path;
+    PCTCHK(resolve_segment_algo(c, algo, &path));
+    if (Q == 0) return PCT_OK;
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(c->d_r2, reach, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
+    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {          // the table lost points (overflow-queue overrun): refiled, asked once more
+        PCTCHK(segment_run(c, path, c->d_seg, c->d_r2, 0.0, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
+        HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
+        if (d2) HIPCHK(hipMemcpyAsync(d2, c->d_d2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
+        if (s) HIPCHK(hipMemcpyAsync(s, c->d_radius, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return PCT_OK;
+    }));
+    if (path == SegPath::Empty) return fail(PCT_ERR_EMPTY, "segment query against an empty cloud");
+    return PCT_OK;
+}
+
+// The reach that bounds the capsule inflation's walk.  The contract is unbounded: radius = min(sqrt(d2*) - m, R), d2* the smallest
+// finite d2 of the window, m = search_margin, R = max_radius, "min" as the engine writes it (rr < R ? rr : R), and the winner is
+// named only when rr < R.  The search returns the window's best row with d2 <= r2 = min(fl(rho * rho), DBL_MAX).  If any row is a
+// candidate, the best candidate IS the row of d2* (a smaller d2 passes the same test) and the epilogue applies the formula to it:
+// nothing depends on rho.  If no row is a candidate the epilogue reports R and names nobody, which is the contract's answer iff
+// every row with a finite d2 > r2 has fl(fl(sqrt(d2)) - m) >= R.  rho = max(fl(fl(R + m) * (1 + 2^-20)), 2^-500) for finite R, m:
+//   * fl(rho^2) overflows: r2 = DBL_MAX and no finite d2 is above it -- nothing to show.
+//   * otherwise rho >= 2^-500, so rho^2 is normal and r2 >= rho^2 (1 - u), u = 2^-53.  sqrt is correctly rounded, hence monotonic:
+//     sd = fl(sqrt(d2)) >= fl(sqrt(r2)) >= rho (1 - u)^(3/2).
+//   * t = fl(R + m) > 0: then R + m > 0 and t >= (R + m)(1 - u), rho >= t (1 + 2^-20)(1 - u), so
+//     sd >= (R + m)(1 + 2^-20)(1 - u)^(7/2) > R + m; t <= 0: R + m <= 0 <= sd.  Either way sd - m >= R as real numbers, R is
+//     representable, and a correctly rounded difference is monotonic: fl(sd - m) >= R.
+// A non-finite R or m leaves the walk unbounded (rho = +inf), which is the contract itself.
+double segment_inflate_reach(const pct_inflate_params *p)
+{
+    if (!std::isfinite(p->max_radius) || !std::isfinite(p->search_margin)) return (double)INFINITY;
+    const double t = p->max_radius + p->search_margin;
+    return std::max(t * (1.0 + 0x1p-20), 0x1p-500);
+}
+
+int pct_segment_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *seg, int64_t Q, double *radius, uint32_t *idx, double *s)
+{
+    if (!c || !p || Q < 0 || (Q > 0 && (!seg || !radius))) return fail(PCT_ERR_INVALID, "bad segment_inflate_batch arguments");
+    PCTCHK(ring_finish_pending(c));
+    if (Q == 0) return PCT_OK;
+    SegPath path;
+    PCTCHK(resolve_segment_algo(c, PCT_ALGO_AUTO, &path));
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    const double reach = segment_inflate_reach(p);
+    if (path != SegPath::Empty) HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
+    return ask_twice_after_overrun(c, [&]() -> int {
+        // no start-distance early-out: a segment has no single distance to the start
+        if (path != SegPath::Empty) PCTCHK(segment_run(c, path, c->d_seg, nullptr, reach, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
+        segment_inflate_epilogue_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(to_dev(p), (uint32_t)Q, path == SegPath::Empty ? 1 : 0, c->d_idx,
+                                                                                c->d_d2, c->d_radius, c->d_r2);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(radius, c->d_r2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
+        if (idx) HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
+        if (s) HIPCHK(hipMemcpyAsync(s, c->d_radius, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return PCT_OK;
+    });
 }
 
 // ---- fused RRT* expansion step (kernels.hpp rrt_expand_kernel) ----------------------------------------------------------

@@ -63,13 +63,19 @@ __device__ __forceinline__ void ring_add_nodes(WorkCounters *__restrict__ work, 
 // a span that reaches the table size takes the axis' g positions once.
 struct RingBox { int x0, y0, z0, nx, ny, nz; };
 
-__device__ __forceinline__ void ring_box_axis(double q, double ra, double inv_h, int g, int &c0, int &n)
+// the axis of a box whose ends are given: [vlo, vhi] (a ball's q - |r| .. q + |r|; a capsule's, segment.hpp)
+__device__ __forceinline__ void ring_box_axis_ends(double vlo, double vhi, double inv_h, int g, int &c0, int &n)
 {
     bool wild = false;
-    const int lo = ring_cell_coord(q - ra, inv_h, wild), hi = ring_cell_coord(q + ra, inv_h, wild);
+    const int lo = ring_cell_coord(vlo, inv_h, wild), hi = ring_cell_coord(vhi, inv_h, wild);
     const long long span = (long long)hi - (long long)lo + 3;
     if (wild || span >= (long long)g) { c0 = 0; n = g; }
     else { c0 = lo - 1; n = (int)span; }
+}
+
+__device__ __forceinline__ void ring_box_axis(double q, double ra, double inv_h, int g, int &c0, int &n)
+{
+    ring_box_axis_ends(q - ra, q + ra, inv_h, g, c0, n);
 }
 
 __device__ __forceinline__ RingBox ring_ball_box(const RingDesc &R, double qx, double qy, double qz, double ra)
@@ -82,17 +88,27 @@ __device__ __forceinline__ RingBox ring_ball_box(const RingDesc &R, double qx, d
 }
 
 // The record loop: this lane's share (records part, part + lanes, ..) of the n records from `head` of a queue of mask + 1 places --
-// a bucket or the overflow queue.  Every read is counted in npts, a dead record is skipped, f(d2, slot) for the rest.
-template <typename F>
-__device__ __forceinline__ void ring_for_records(const float4 *__restrict__ base, uint32_t head, uint32_t n, uint32_t mask, uint32_t part,
-                                                 uint32_t lanes, double qx, double qy, double qz, uint32_t &npts, F f)
+// a bucket or the overflow queue.  Every read is counted in npts, a dead record is skipped, g(x, y, z, slot) for the rest: the
+// widened coordinates, for a caller that measures something other than the distance to a point (a segment: segment.hpp).
+template <typename G>
+__device__ __forceinline__ void ring_for_live_records(const float4 *__restrict__ base, uint32_t head, uint32_t n, uint32_t mask, uint32_t part,
+                                                      uint32_t lanes, uint32_t &npts, G g)
 {
     for (uint32_t j = part; j < n; j += lanes) {
         const float4 P = base[(head + j) & mask];
         const uint32_t id = __float_as_uint(P.w);
         npts++;
-        if (id != kRingDead) f(dist2((double)P.x, (double)P.y, (double)P.z, qx, qy, qz), id);
+        if (id != kRingDead) g((double)P.x, (double)P.y, (double)P.z, id);
     }
+}
+
+// the point queries' form: f(d2, slot) with d2 = dist2 to (qx, qy, qz)
+template <typename F>
+__device__ __forceinline__ void ring_for_records(const float4 *__restrict__ base, uint32_t head, uint32_t n, uint32_t mask, uint32_t part,
+                                                 uint32_t lanes, double qx, double qy, double qz, uint32_t &npts, F f)
+{
+    ring_for_live_records(base, head, n, mask, part, lanes, npts,
+                          [&](double px, double py, double pz, uint32_t id) { f(dist2(px, py, pz, qx, qy, qz), id); });
 }
 
 // every live record of the overflow queue and of the box's buckets, once: f(d2, slot).  Returns through npts / nbuckets what was read.

@@ -223,6 +223,9 @@ def lib():
         L.pct_radius_crop.argtypes = [vp, vp, C.c_double, C.c_int, i64, vp, vp, vp, C.POINTER(i64)]
         L.pct_cloud_crop_to.argtypes = [vp, vp, C.c_double, vp]
         L.pct_inflate_batch.argtypes = [vp, C.POINTER(InflateParams), f64p, i64, f64p, u32p, f64p]
+        L.pct_segment_nn_batch.argtypes = [vp, i32, f64p, f64p, i64, u32p, f64p, f64p]
+        L.pct_segment_nn_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp, vp, vp]
+        L.pct_segment_inflate_batch.argtypes = [vp, C.POINTER(InflateParams), f64p, i64, f64p, u32p, f64p]
         L.pct_bezier_check.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.c_double, C.c_double,
                                        C.POINTER(i64), C.POINTER(i64), i64, f64p, f64p, f64p, u32p]
         L.pct_nn_batch_dev.argtypes = [vp, i32, vp, i64, vp, vp, vp]
@@ -705,6 +708,27 @@ class Cloud:
         _chk(lib().pct_inflate_batch(self._h, C.byref(params), _ptr(p), len(p), _ptr(rad), _ptr(idx), _ptr(d2)))
         return rad, idx, d2
 
+    def segment_nn(self, segments, reach, algo: int = ALGO_AUTO):
+        """the nearest point to every line segment within its reach (pct_segment_nn_batch): segments [Q, 6] (a then b) or [Q, 2, 3],
+        reach a scalar or [Q]; (idx uint32 [Q], d2 float64 [Q], s float64 [Q]) -- NO_INDEX / +inf / NaN where no point is that near"""
+        seg = np.ascontiguousarray(segments, np.float64).reshape(-1, 6)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64), (len(seg),)))
+        idx = np.empty(len(seg), np.uint32)
+        d2 = np.empty(len(seg), np.float64)
+        s = np.empty(len(seg), np.float64)
+        _chk(lib().pct_segment_nn_batch(self._h, algo, _ptr(seg), _ptr(r), len(seg), _ptr(idx), _ptr(d2), _ptr(s)))
+        return idx, d2, s
+
+    def segment_inflate(self, segments, params: InflateParams):
+        """capsule inflation (pct_segment_inflate_batch): (radius float64 [Q], idx uint32 [Q], s float64 [Q]); radius < 0: the segment
+        collides; idx / s name the nearest point where radius < max_radius"""
+        seg = np.ascontiguousarray(segments, np.float64).reshape(-1, 6)
+        rad = np.empty(len(seg), np.float64)
+        idx = np.empty(len(seg), np.uint32)
+        s = np.empty(len(seg), np.float64)
+        _chk(lib().pct_segment_inflate_batch(self._h, C.byref(params), _ptr(seg), len(seg), _ptr(rad), _ptr(idx), _ptr(s)))
+        return rad, idx, s
+
     def bezier_check(self, params: InflateParams, polycoef, seg_time, orders, t_start, stop_time, dt=0.02, cap=4096):
         coef = np.ascontiguousarray(polycoef, np.float64)
         st = np.ascontiguousarray(seg_time, np.float64)
@@ -774,6 +798,10 @@ class Cloud:
     def knn_device(self, q_ptr: int, Q: int, k: int, idx_ptr: int, d2_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         """pct_knn_batch_dev: idx / d2 are Q x k device buffers; reserve_queries(Q) first"""
         _chk(lib().pct_knn_batch_dev(self._h, algo, q_ptr, int(Q), int(k), idx_ptr, d2_ptr, stream))
+
+    def segment_nn_device(self, seg_ptr: int, reach_ptr: int, Q: int, idx_ptr: int, d2_ptr: int, s_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
+        """pct_segment_nn_batch_dev: seg Q x 6 and reach Q doubles on the device; d2_ptr / s_ptr may be 0; reserve_queries(Q) first"""
+        _chk(lib().pct_segment_nn_batch_dev(self._h, algo, seg_ptr, reach_ptr, int(Q), idx_ptr, d2_ptr or None, s_ptr or None, stream))
 
     def inflate_device(self, params: InflateParams, pts_ptr: int, Q: int, radius_ptr: int, idx_ptr: int = 0, d2_ptr: int = 0, stream: int = 0):
         _chk(lib().pct_inflate_batch_dev(self._h, C.byref(params), pts_ptr, int(Q), radius_ptr, idx_ptr or None, d2_ptr or None, stream))
