@@ -320,6 +320,28 @@
  * walk is bounded by a reach derived from max_radius + search_margin that provably never changes this result (the rounding argument
  * stands beside the code); the contract is the unbounded formula.
  *
+ * Segment sweeps (pct_segment_sweep_batch*): the first contact of a sphere of radius r that moves along a line segment from a to b --
+ * how far can the planner go before it touches something, and which point stops it.  The point that stops the sphere is in general
+ * not the point nearest to the segment.  A sweep is a segment a -> b (fp64 xyz, narrowed to fp32 and widened again exactly as for
+ * "Segment queries") and a radius r.  All arithmetic is fp64 on float-widened operands, one rounding per operation, no contraction, `/`
+ * and sqrt correctly rounded.  e, L2, w, dot, s and d2 are those of "Segment queries".  r2 = min(r*r, DBL_MAX).  A row is a BLOCKER iff
+ * d2 <= r2 -- inclusive; this is the candidate test of pct_segment_nn_batch under reach = r, so "blocked" here is exactly "has a
+ * candidate" there.  The entry parameter t of a blocker, in exactly this order:  ww = (w0*w0 + w1*w1) + w2*w2;  if (ww <= r2) t = 0
+ * (the sphere is in contact at the start; this covers a == b);  otherwise  g = ww - r2;  disc = dot*dot - L2*g;
+ * if (!(disc > 0)) disc = 0;  t = (dot - sqrt(disc)) / L2;  if (!(t > 0)) t = 0; else if (t > s) t = s (s: the blocker's own clamped
+ * closest-approach parameter; geometrically the entry never lies behind the closest approach, the clamp is what rounding can ask for).
+ * The winner is the blocker with the smallest t, the lowest index on ties.  Outputs per sweep: idx = index_base + slot of the winner
+ * and its t.  With no blocker: idx = PCT_NO_INDEX and t = 1 -- the whole segment can be flown.  An invalid sweep -- a non-finite endpoint
+ * (judged after the narrowing), a NaN or a negative radius -- gives idx = PCT_NO_INDEX and t = NaN, never "free".  Rows that hold a NaN
+ * and rows with an infinite coordinate never block.  t may be NULL.  An empty cloud fills the free / invalid outputs and the host form
+ * returns PCT_ERR_EMPTY (the device form PCT_OK); Q == 0: PCT_OK; a NULL required pointer or Q < 0: PCT_ERR_INVALID with nothing
+ * written.  algo is PCT_ALGO_AUTO, PCT_ALGO_STREAM or PCT_ALGO_RING, chosen as for "Segment queries"; PCT_ALGO_GRID,
+ * PCT_ALGO_STREAM_EXACT and an unknown algo are PCT_ERR_INVALID, as is PCT_ALGO_RING without a live index.  Both forms give the same
+ * answers, bit for bit: the streaming form measures every row; the rolling-map form reads the overflow queue, then the capsule's cells
+ * in layers along the segment from a's side, and stops once no unseen row can beat the contact it holds (the argument stands beside
+ * the code).  The host form finishes an append in flight first and waits once; the device form is asynchronous on `stream`, allocates
+ * nothing and waits for nothing (reserve the batch size first, pct_cloud_reserve_queries).
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -593,6 +615,13 @@ int pct_segment_nn_batch_dev(pct_cloud *c, int algo, const double *d_seg, const 
  * idx / s (may be NULL): the winner's where the radius is below max_radius, PCT_NO_INDEX / NaN elsewhere */
 int pct_segment_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *seg, int64_t Q,
                               double *radius, uint32_t *idx, double *s);
+
+/* Segment sweeps (contract: top of this file, "Segment sweeps").  seg: Q x 6 fp64, a then b; radius[Q]; idx[Q] = the point that stops
+ * the sphere, PCT_NO_INDEX when nothing does; t[Q] (may be NULL) = how far along a -> b its centre gets: 0 in contact at the start,
+ * 1 free, NaN for an invalid sweep.  algo as for pct_segment_nn_batch. */
+int pct_segment_sweep_batch(pct_cloud *c, int algo, const double *seg, const double *radius, int64_t Q, uint32_t *idx, double *t);
+int pct_segment_sweep_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_radius, int64_t Q,
+                                uint32_t *d_idx, double *d_t, void *stream);
 
 /* ---- one RRT* iteration's three dependent queries in ONE launch (corridor_finder.cpp:385-410 genNewNode, :428-437
  * findNearstVertex, :464 treeRewire's neighbourhood), for K samples at once: nearest tree node of the fp32-narrowed

@@ -296,6 +296,26 @@ public:
         checkSegments(seg, 1, &r);
         return r < 0.0;
     }
+    // Segment sweeps (pct_engine.h, paragraph "Segment sweeps"): how far a sphere gets along a straight line, and what stops it.
+    //   sweepSegments  for each segment a -> b the point a sphere of `radius` touches first (PCT_NO_INDEX: none) and the parameter t
+    //                  its centre reaches: 0 = in contact at a, 1 = the whole segment is free; t may be null.  On an empty map every
+    //                  segment is free.
+    //   freeFraction   one sweep with the map's own search_margin as the radius: the fraction of a -> b that can be flown.
+    // Contact is INCLUSIVE here -- a point at exactly the radius stops the sphere -- whereas checkTrajPtCol collides on a strict `<`
+    // (radius < 0): a line that passes an obstacle point at exactly search_margin has freeFraction < 1 and segmentCollides false.
+    void sweepSegments(const double *segments, int64_t n, double radius, uint32_t *index, double *t)
+    {
+        const std::vector<double> radii((size_t)(n > 0 ? n : 0), radius);
+        check(pct_segment_sweep_batch(cloud_, PCT_ALGO_AUTO, segments, radii.data(), n, index, t), "pct_segment_sweep_batch");
+    }
+    double freeFraction(const double a[3], const double b[3])
+    {
+        const double seg[6] = { a[0], a[1], a[2], b[0], b[1], b[2] };
+        uint32_t index = 0;
+        double t = 0;
+        sweepSegments(seg, 1, prm_.search_margin, &index, &t);
+        return t;
+    }
     // corridor_finder.cpp:661-669
     int checkNodeUpdate(double new_radius, double old_radius) const
     {

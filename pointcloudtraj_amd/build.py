@@ -124,6 +124,15 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
+    sweeps_src = os.path.join(ROOT, "examples", "segment_sweeps.cpp")
+    sweeps_bin = os.path.join(LIB, "segment_sweeps")
+    if os.path.exists(sweeps_src) and os.path.exists(ENGINE_SO) and (force or _stale(sweeps_bin, [sweeps_src, ENGINE_SO] + hdrs + [os.path.join(ROOT, "include", "pct_obstacle_map.hpp")])):
+        # ObstacleMap::sweepSegments / freeFraction against a host loop (the contract's arithmetic: no contraction); needs the engine alone
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-o", sweeps_bin, sweeps_src,
+               "-L" + LIB, "-lpct_engine", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + LIB, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
 
 
 if __name__ == "__main__":

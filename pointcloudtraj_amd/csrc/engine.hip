@@ -1230,6 +1230,9 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
 
 // ---- segment queries (segment.hpp) -------------------------------------------------------------------------------------------
 enum class SegPath { Table, Stream, Empty };
+// what a batch measures on its rows: the nearest row's (d2, s) | the first blocker's entry parameter t of a swept sphere ("Segment
+// sweeps": t travels in d2's place, d_reach holds the radii, there is no s)
+enum class SegMeasure { Nearest, Sweep };
 
 // `algo` of a segment batch: the rolling-map index or the streaming form; there is no grid form and no second streaming form
 int resolve_segment_algo(const pct_cloud *c, int algo, SegPath *path)
@@ -1244,20 +1247,24 @@ int resolve_segment_algo(const pct_cloud *c, int algo, SegPath *path)
     return PCT_OK;
 }
 
-// nearest row to every segment of a device-resident batch (d_seg: Q x 6); d_reach == nullptr: reach_all for every segment.
-// d_d2 / d_s may be NULL.  Q >= 1, within the reserved batch size.
-int segment_run(pct_cloud *c, SegPath path, const double *d_seg, const double *d_reach, double reach_all, int64_t Q, uint32_t *d_idx,
-                double *d_d2, double *d_s, hipStream_t s)
+// nearest row to every segment of a device-resident batch (d_seg: Q x 6) -- or, for a sweep, the row that stops the sphere, its t in
+// d_d2; d_reach == nullptr: reach_all for every segment (a sweep always has its d_reach).  d_d2 / d_s may be NULL.  Q >= 1, within
+// the reserved batch size.
+int segment_run(pct_cloud *c, SegPath path, SegMeasure measure, const double *d_seg, const double *d_reach, double reach_all, int64_t Q,
+                uint32_t *d_idx, double *d_d2, double *d_s, hipStream_t s)
 {
+    const bool sweep = measure == SegMeasure::Sweep;
     switch (path) {
     case SegPath::Empty:
-        segment_fill_none_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_idx, d_d2, d_s, (uint32_t)Q);
+        if (sweep) sweep_fill_none_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_seg, d_reach, d_idx, d_d2, (uint32_t)Q);
+        else segment_fill_none_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_idx, d_d2, d_s, (uint32_t)Q);
         HIPCHK(hipGetLastError());
         return PCT_OK;
     case SegPath::Table:     // rolling-map index: a block per segment over the buckets of the capsule's box
         return launch_frame(c, s, Q, { Work::Device }, [&] {
-            ring_segment_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_seg, d_reach, reach_all, (uint32_t)c->index_base, d_idx, d_d2, d_s,
-                                                       c->count_work ? c->d_work : nullptr);
+            WorkCounters *work = c->count_work ? c->d_work : nullptr;
+            if (sweep) ring_sweep_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_seg, d_reach, (uint32_t)c->index_base, d_idx, d_d2, work);
+            else ring_segment_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_seg, d_reach, reach_all, (uint32_t)c->index_base, d_idx, d_d2, d_s, work);
         });
     default:
         break;
@@ -1268,11 +1275,20 @@ int segment_run(pct_cloud *c, SegPath path, const double *d_seg, const double *d
     return launch_frame(c, s, Q, { Work::EveryPoint }, [&] {
         for (int64_t off = 0; off < Q; off += c->part_q) {
             const int qn = (int)std::min<int64_t>(c->part_q, Q - off);
-            segment_stream_kernel<<<dim3(parts, ceil_div(qn, kSegTile)), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg + 6 * off,
-                                                                                      d_reach ? d_reach + off : nullptr, reach_all, (uint32_t)qn,
-                                                                                      c->d_part_d2, c->d_part_idx, c->d_cand_d2);
-            segment_finish_kernel<<<qn, 64, 0, s>>>(c->d_part_d2, c->d_part_idx, c->d_cand_d2, (uint32_t)parts, (uint32_t)c->index_base, d_idx + off,
-                                                    d_d2 ? d_d2 + off : nullptr, d_s ? d_s + off : nullptr);
+            const dim3 grid(parts, ceil_div(qn, kSegTile));
+            const double *seg = d_seg + 6 * off, *reach = d_reach ? d_reach + off : nullptr;
+            double *out_d2 = d_d2 ? d_d2 + off : nullptr;
+            if (sweep) {             // two partials, (t, index): there is no third
+                segment_stream_kernel<true><<<grid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, seg, reach, reach_all, (uint32_t)qn, c->d_part_d2,
+                                                                 c->d_part_idx, nullptr);
+                segment_finish_kernel<true><<<qn, 64, 0, s>>>(c->d_part_d2, c->d_part_idx, nullptr, (uint32_t)parts, (uint32_t)c->index_base, seg, reach,
+                                                              d_idx + off, out_d2, nullptr);
+            } else {
+                segment_stream_kernel<false><<<grid, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, seg, reach, reach_all, (uint32_t)qn, c->d_part_d2,
+                                                                  c->d_part_idx, c->d_cand_d2);
+                segment_finish_kernel<false><<<qn, 64, 0, s>>>(c->d_part_d2, c->d_part_idx, c->d_cand_d2, (uint32_t)parts, (uint32_t)c->index_base, nullptr,
+                                                               nullptr, d_idx + off, out_d2, d_s ? d_s + off : nullptr);
+            }
         }
     });
 }
@@ -2417,7 +2433,7 @@ int pct_segment_nn_batch_dev(pct_cloud *c, int algo, const double *d_seg, const 
     if (Q == 0) return PCT_OK;
     if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
     PCTCHK(order_after_mutations(c, (hipStream_t)stream));
-    return segment_run(c, path, d_seg, d_reach, 0.0, Q, d_idx, d_d2, d_s, (hipStream_t)stream);
+    return segment_run(c, path, SegMeasure::Nearest, d_seg, d_reach, 0.0, Q, d_idx, d_d2, d_s, (hipStream_t)stream);
 }
 
 int pct_segment_nn_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, uint32_t *idx, double *d2, double *s)
@@ -2431,7 +2447,7 @@ int pct_segment_nn_batch(pct_cloud *c, int algo, const double *seg, const double
     HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(c->d_r2, reach, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
     PCTCHK(ask_twice_after_overrun(c, [&]() -> int {          // the table lost points (overflow-queue overrun): refiled, asked once more
-        PCTCHK(segment_run(c, path, c->d_seg, c->d_r2, 0.0, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
+        PCTCHK(segment_run(c, path, SegMeasure::Nearest, c->d_seg, c->d_r2, 0.0, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
         HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
         if (d2) HIPCHK(hipMemcpyAsync(d2, c->d_d2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
         if (s) HIPCHK(hipMemcpyAsync(s, c->d_radius, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
@@ -2439,6 +2455,40 @@ int pct_segment_nn_batch(pct_cloud *c, int algo, const double *seg, const double
         return PCT_OK;
     }));
     if (path == SegPath::Empty) return fail(PCT_ERR_EMPTY, "segment query against an empty cloud");
+    return PCT_OK;
+}
+
+// ---- segment sweeps (include/pct_engine.h, "Segment sweeps"): the segment queries' dispatch, frame and staged workspaces ---------
+int pct_segment_sweep_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_radius, int64_t Q, uint32_t *d_idx, double *d_t,
+                                void *stream)
+{
+    if (!c || Q < 0 || (Q > 0 && (!d_seg || !d_radius || !d_idx))) return fail(PCT_ERR_INVALID, "bad segment_sweep_batch_dev arguments");
+    SegPath path;
+    PCTCHK(resolve_segment_algo(c, algo, &path));
+    if (Q == 0) return PCT_OK;
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(order_after_mutations(c, (hipStream_t)stream));
+    return segment_run(c, path, SegMeasure::Sweep, d_seg, d_radius, 0.0, Q, d_idx, d_t, nullptr, (hipStream_t)stream);
+}
+
+int pct_segment_sweep_batch(pct_cloud *c, int algo, const double *seg, const double *radius, int64_t Q, uint32_t *idx, double *t)
+{
+    if (!c || Q < 0 || (Q > 0 && (!seg || !radius || !idx))) return fail(PCT_ERR_INVALID, "bad segment_sweep_batch arguments");
+    PCTCHK(ring_finish_pending(c));
+    SegPath path;
+    PCTCHK(resolve_segment_algo(c, algo, &path));
+    if (Q == 0) return PCT_OK;
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(c->d_r2, radius, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
+    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {
+        PCTCHK(segment_run(c, path, SegMeasure::Sweep, c->d_seg, c->d_r2, 0.0, Q, c->d_idx, c->d_d2, nullptr, g_stream));
+        HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
+        if (t) HIPCHK(hipMemcpyAsync(t, c->d_d2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return PCT_OK;
+    }));
+    if (path == SegPath::Empty) return fail(PCT_ERR_EMPTY, "segment sweep against an empty cloud");
     return PCT_OK;
 }
 
@@ -2474,7 +2524,7 @@ int pct_segment_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const d
     if (path != SegPath::Empty) HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
     return ask_twice_after_overrun(c, [&]() -> int {
         // no start-distance early-out: a segment has no single distance to the start
-        if (path != SegPath::Empty) PCTCHK(segment_run(c, path, c->d_seg, nullptr, reach, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
+        if (path != SegPath::Empty) PCTCHK(segment_run(c, path, SegMeasure::Nearest, c->d_seg, nullptr, reach, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
         segment_inflate_epilogue_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(to_dev(p), (uint32_t)Q, path == SegPath::Empty ? 1 : 0, c->d_idx,
                                                                                 c->d_d2, c->d_radius, c->d_r2);
         HIPCHK(hipGetLastError());

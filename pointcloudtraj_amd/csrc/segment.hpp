@@ -1,4 +1,5 @@
-// segment.hpp -- nearest obstacle point to a LINE SEGMENT (pct_segment_nn_batch*, pct_segment_inflate_batch), for gfx950.
+// segment.hpp -- nearest obstacle point to a LINE SEGMENT (pct_segment_nn_batch*, pct_segment_inflate_batch) and the first contact of
+// a sphere swept along one (pct_segment_sweep_batch*), for gfx950.
 //
 // The contract is the paragraph "Segment queries" of include/pct_engine.h; seg_point_d2 below is its arithmetic, operation for
 // operation, and the only place it is written.  Everything is fp64 on float-widened operands, one rounding per operation, no
@@ -13,6 +14,12 @@
 //   * segment_stream_kernel  PCT_ALGO_STREAM: one pass over the SoA arrays per tile of kSegTile segments, per-lane running winners,
 //                            per-block partials, segment_finish_kernel folds them.  A lane meets its rows in ascending index and
 //                            every fold uses better(), so the result is a function of the data alone.
+//
+// Segment sweeps (paragraph "Segment sweeps" of the header) put another measure on the same rows: seg_entry_t, the parameter at which
+// a sphere of radius r moving from a to b first touches the row, on top of the same w, dot, s and d2; a row blocks iff it is a
+// candidate under reach = r.  The streaming kernels take the measure as a template parameter (SWEEP: the value is t, there is no s);
+// the rolling-map form is ring_sweep_kernel, which shares the capsule's box and the per-cell skip with ring_segment_kernel
+// (seg_capsule_box, seg_cell_skipped) and walks the box along the segment so that it can stop.
 #pragma once
 #include "ring_search.hpp"
 
@@ -48,17 +55,67 @@ __device__ __forceinline__ double seg_reach2(double reach)
     return r2 < 1.7976931348623157e308 ? r2 : 1.7976931348623157e308;
 }
 
-// THE arithmetic: squared distance of the widened row p to the segment, and the parameter of the closest point
-__device__ __forceinline__ void seg_point_d2(const SegGeom &S, double px, double py, double pz, double &d2, double &s)
+// segment `i` with its reach (reach[i], or reach_all when reach is NULL): the geometry, the reach in ra, and the candidate bound r2 --
+// -1 when nothing can be a candidate (an end that is not finite, a NaN or negative reach).  The one place that is decided, for the
+// segment queries and for the sweeps, whose "invalid sweep" it is.
+__device__ __forceinline__ double seg_load_r2(const double *__restrict__ seg, const double *__restrict__ reach, double reach_all, size_t i,
+                                              SegGeom &S, double &bx, double &by, double &bz, double &ra)
+{
+    const bool finite = seg_load(seg, i, S, bx, by, bz);
+    ra = reach ? reach[i] : reach_all;
+    return finite ? seg_reach2(ra) : -1.0;
+}
+
+// THE arithmetic: squared distance of the widened row p to the segment, and the parameter of the closest point; dot and ww = |w|^2
+// as well, for the sweep's entry parameter (seg_entry_t)
+__device__ __forceinline__ void seg_point_terms(const SegGeom &S, double px, double py, double pz, double &d2, double &s, double &dot, double &ww)
 {
     const double w0 = px - S.ax, w1 = py - S.ay, w2 = pz - S.az;
-    const double dot = (w0 * S.ex + w1 * S.ey) + w2 * S.ez;
+    dot = (w0 * S.ex + w1 * S.ey) + w2 * S.ez;
     s = S.L2 == 0.0 ? 0.0 : dot / S.L2;
     if (!(s > 0.0)) s = 0.0;                                // also NaN
     else if (s > 1.0) s = 1.0;
     const double c0 = w0 - s * S.ex, c1 = w1 - s * S.ey, c2 = w2 - s * S.ez;
     d2 = (c0 * c0 + c1 * c1) + c2 * c2;
+    ww = (w0 * w0 + w1 * w1) + w2 * w2;
 }
+
+__device__ __forceinline__ void seg_point_d2(const SegGeom &S, double px, double py, double pz, double &d2, double &s)
+{
+    double dot, ww;
+    seg_point_terms(S, px, py, pz, d2, s, dot, ww);
+}
+
+// The sweep's measure ("Segment sweeps"): is the row a blocker of the sphere (segment, r) -- d2 <= r2, the candidate test under
+// reach = r -- and if so the parameter t in [0, s] at which the sphere first touches it.  ww <= r2: in contact at the start (this
+// covers L2 == 0, where d2 == ww).  Otherwise the smaller root of |w - t e|^2 = r2, held into [0, s]: the entry never lies behind
+// the closest approach, and only rounding can ask for the clamp.
+__device__ __forceinline__ bool seg_entry_t(const SegGeom &S, double r2, double px, double py, double pz, double &t)
+{
+    double d2, s, dot, ww;
+    seg_point_terms(S, px, py, pz, d2, s, dot, ww);
+    if (!(d2 <= r2)) return false;
+    if (ww <= r2) { t = 0.0; return true; }
+    const double g = ww - r2;
+    double disc = dot * dot - S.L2 * g;
+    if (!(disc > 0.0)) disc = 0.0;
+    t = (dot - sqrt(disc)) / S.L2;
+    if (!(t > 0.0)) t = 0.0;
+    else if (t > s) t = s;
+    return true;
+}
+
+// r2 of sweep i, -1 for an invalid one
+__device__ __forceinline__ double sweep_r2(const double *__restrict__ seg, const double *__restrict__ radius, size_t i)
+{
+    SegGeom S;
+    double bx, by, bz, ra;
+    return seg_load_r2(seg, radius, 0.0, i, S, bx, by, bz, ra);
+}
+
+// what a sweep reports when nothing blocks it: the whole segment can be flown (t = 1) -- or NaN for an invalid sweep (a non-finite
+// end, a NaN or negative radius: r2 = -1), never "free"
+__device__ __forceinline__ double sweep_unblocked_t(double r2) { return r2 >= 0.0 ? 1.0 : __builtin_nan(""); }
 
 // (d, i, s) of the wave's best lane in every lane
 __device__ __forceinline__ void seg_wave_best(double &d, uint32_t &i, double &s)
@@ -88,6 +145,38 @@ __device__ __forceinline__ void seg_wave_best(double &d, uint32_t &i, double &s)
 // every record that is read is judged by the fp64 test.  On a folded axis a bucket stands for several world cells and the skip is
 // dropped for the whole query.  A bucket read twice would be harmless (the minimum is idempotent; s is a function of the record),
 // but the box visits every position once.
+struct SegBox {
+    RingBox B;
+    int total, lanes;        // positions of the box (at most the table: 2^24 buckets); threads that share one bucket
+    bool folded;             // an axis takes its g positions: a bucket stands for several world cells, no skip
+    double skip2;            // (reach + h)^2
+};
+
+__device__ __forceinline__ SegBox seg_capsule_box(const RingDesc &R, const SegGeom &S, double bx, double by, double bz, double ra)
+{
+    SegBox C;
+    ring_box_axis_ends(fmin(S.ax, bx) - ra, fmax(S.ax, bx) + ra, R.inv_h, R.gx, C.B.x0, C.B.nx);
+    ring_box_axis_ends(fmin(S.ay, by) - ra, fmax(S.ay, by) + ra, R.inv_h, R.gy, C.B.y0, C.B.ny);
+    ring_box_axis_ends(fmin(S.az, bz) - ra, fmax(S.az, bz) + ra, R.inv_h, R.gz, C.B.z0, C.B.nz);
+    C.folded = C.B.nx == R.gx || C.B.ny == R.gy || C.B.nz == R.gz;             // an unfolded axis has fewer than g positions
+    const double rh = ra + R.h;
+    C.skip2 = rh * rh;
+    C.total = C.B.nx * C.B.ny * C.B.nz;
+    // grown buckets: the skip leaves a fraction of a capsule's box, and what it leaves are fat buckets among empty ones -- eight lanes
+    // share a bucket in boxes eight times as large as a ball's (ring_for_ball), whose every cell is read
+    C.lanes = R.K > kRingK && C.total <= 65536 ? 8 : ring_lanes_per_bucket(R, C.total);
+    return C;
+}
+
+// the per-cell skip of box position (jx, jy, jz): the same answer in every lane that shares the bucket
+__device__ __forceinline__ bool seg_cell_skipped(const RingDesc &R, const SegGeom &S, const SegBox &C, int jx, int jy, int jz)
+{
+    if (C.folded) return false;
+    double dc2, sc;
+    seg_point_d2(S, ((double)(C.B.x0 + jx) + 0.5) * R.h, ((double)(C.B.y0 + jy) + 0.5) * R.h, ((double)(C.B.z0 + jz) + 0.5) * R.h, dc2, sc);
+    return dc2 > C.skip2;
+}
+
 __global__ __launch_bounds__(256) void ring_segment_kernel(RingView V, const double *__restrict__ seg, const double *__restrict__ reach,
                                                            double reach_all, uint32_t index_base, uint32_t *__restrict__ out_idx,
                                                            double *__restrict__ out_d2, double *__restrict__ out_s,
@@ -99,10 +188,8 @@ __global__ __launch_bounds__(256) void ring_segment_kernel(RingView V, const dou
     const size_t slot = blockIdx.x;
     const RingDesc &R = V.R;
     SegGeom S;
-    double bx, by, bz;
-    const bool finite = seg_load(seg, slot, S, bx, by, bz);
-    const double ra = reach ? reach[slot] : reach_all;
-    const double r2 = finite ? seg_reach2(ra) : -1.0;
+    double bx, by, bz, ra;
+    const double r2 = seg_load_r2(seg, reach, reach_all, slot, S, bx, by, bz, ra);
     double bd = __builtin_huge_val(), bs = __builtin_nan("");
     uint32_t bi = kNoIndex, npts = 0, nbuckets = 0;
     const auto offer = [&](double px, double py, double pz, uint32_t id) {
@@ -113,24 +200,13 @@ __global__ __launch_bounds__(256) void ring_segment_kernel(RingView V, const dou
     if (V.st->count != 0 && r2 >= 0.0) {                    // block-uniform
         const uint32_t oh = V.st->ovf_head;
         ring_for_live_records(V.ovf, oh, V.st->ovf_tail - oh, R.ovf_mask, threadIdx.x, 256u, npts, offer);
-        RingBox B;
-        ring_box_axis_ends(fmin(S.ax, bx) - ra, fmax(S.ax, bx) + ra, R.inv_h, R.gx, B.x0, B.nx);
-        ring_box_axis_ends(fmin(S.ay, by) - ra, fmax(S.ay, by) + ra, R.inv_h, R.gy, B.y0, B.ny);
-        ring_box_axis_ends(fmin(S.az, bz) - ra, fmax(S.az, bz) + ra, R.inv_h, R.gz, B.z0, B.nz);
-        const bool folded = B.nx == R.gx || B.ny == R.gy || B.nz == R.gz;      // an unfolded axis has fewer than g positions
-        const double rh = ra + R.h, skip2 = rh * rh;
-        const int total = B.nx * B.ny * B.nz;               // at most the table: 2^24 buckets
-        // grown buckets: the skip leaves a fraction of a capsule's box, and what it leaves are fat buckets among empty ones -- eight lanes
-        // share a bucket in boxes eight times as large as a ball's (ring_for_ball), whose every cell is read
-        const int lanes = R.K > kRingK && total <= 65536 ? 8 : ring_lanes_per_bucket(R, total);
+        const SegBox C = seg_capsule_box(R, S, bx, by, bz, ra);
+        const RingBox &B = C.B;
+        const int lanes = C.lanes;
         const uint32_t part = threadIdx.x % (uint32_t)lanes;
-        for (int k = (int)threadIdx.x / lanes; k < total; k += 256 / lanes) {
+        for (int k = (int)threadIdx.x / lanes; k < C.total; k += 256 / lanes) {
             const int jx = k % B.nx, jy = (k / B.nx) % B.ny, jz = k / (B.nx * B.ny);
-            if (!folded) {                                  // the same answer in every lane that shares the bucket
-                double dc2, sc;
-                seg_point_d2(S, ((double)(B.x0 + jx) + 0.5) * R.h, ((double)(B.y0 + jy) + 0.5) * R.h, ((double)(B.z0 + jz) + 0.5) * R.h, dc2, sc);
-                if (dc2 > skip2) continue;
-            }
+            if (seg_cell_skipped(R, S, C, jx, jy, jz)) continue;
             const uint32_t b = ring_lin(R, B.x0 + jx, B.y0 + jy, B.z0 + jz);
             const uint2 m = V.ht[b];
             if (part == 0) nbuckets++;
@@ -150,9 +226,112 @@ __global__ __launch_bounds__(256) void ring_segment_kernel(RingView V, const dou
     if (work) ring_add_work(work, npts, nbuckets, s_w);
 }
 
+// ---- the rolling-map form of the sweep ------------------------------------------------------------------------------------------
+// One block per sweep: the overflow queue exhaustively once, then the capsule's box (seg_capsule_box) with the per-cell skip, every
+// record judged by seg_entry_t, the block's winner by block_argmin256 with t in the place of d2.
+//
+// The ordered walk.  A minimum distance can sit anywhere in the capsule, a first contact cannot: it lies towards a.  When no axis is
+// folded, L2 > 0 and r + |e| < 2^20 h, the box is visited in LAYERS along the dominant axis k of e (largest |e_k|), from a's side,
+// in rounds of whole layers; after a round the block agrees on the best t it holds (tb) and stops before layer c when
+//     tb * |e_k|  <  dist_k(a, near face of layer c) - r - h / 8.
+// Why nothing unseen can then win.  Let P be a row filed in layer c or beyond, D = r + |e| and u = 2^-53.
+//   * Geometry.  Its cell coordinate along k is at or beyond c's, so (cell placement, 5e-7 h, as for the skip above) its offset from
+//     a along the direction of travel is w_k >= dist_k - 5e-7 h.  Let tau = dot / L2 and dp = its distance from the LINE, as real
+//     numbers.  If P passes d2 <= r2 it is within r + 1e-9 h of the segment (the rounding of d2 and r2: a few u D), so dp <= r + 1e-9 h
+//     and w_k <= |e_k| + r + 1e-9 h.  f = tau - sqrt(max(r^2 - dp^2, 0)) / |e| is what step 5 computes in real numbers; the centre
+//     a + f e is at distance max(r, dp) from P, so f |e_k| >= w_k - r - 1e-9 h.  The right side of the stop test is positive, so
+//     w_k > r + 0.12 h: P is not in contact at the start (step 2 does not apply) and f > 0.
+//   * Rounding.  With E = |w| |e| <= D^2 (a blocker has |w| <= |e| + r): dot, L2, ww, r2 carry relative errors of a few u, g = ww - r2
+//     an absolute one below 6 u ww, and disc = dot*dot - L2*g one below 40 u E^2 -- the cancellation the clamp of step 4 is for.
+//     |sqrt(x) - sqrt(y)| <= sqrt|x - y| turns that into sqrt(40 u) E = 6.7e-8 E in the numerator, hence, after the division by L2,
+//     |t - f| |e| <= 6.8e-8 |w| <= 6.8e-8 D < 0.072 h under the cap.  Step 6 can only raise t to 0 or lower it to s, and
+//     s >= min(tau, 1) - 1e-9 >= min(f, 1) - 1e-9, with |e_k| >= w_k - r - 1e-9 h for the case s = 1.
+//   Together the t that P is given satisfies t |e_k| >= dist_k - r - (0.072 + 5e-7 + 3e-9) h > dist_k - r - h / 8 > tb |e_k|, with
+//   0.05 h to spare for the roundings of the test itself (a_k up to 1e9 cells: 1e-7 h): P loses to the held winner strictly, ties
+//   included.  Rows outside the box are no blockers at all, and the overflow queue has been read in full before the first layer.
+// Outside those conditions the walk is one round over the whole box.  Exactness never rests on the order of the layers: only the
+// stop does, and every record that is read is judged by seg_entry_t.
+//
+// The round is what the block reads in one trip of its loop anyway (256 / lanes positions, at least one layer): finer rounds would
+// add dependent memory trips without adding loads in flight.  The agreement costs one barrier per round: every thread folds the best
+// t it has met so far into s_tb[round & 1] (t >= 0 orders as its bit pattern; the minimum is cumulative, so the words are never
+// reset), and a thread that is a round ahead writes the other word while a slower one still reads this one; it cannot get two ahead,
+// the next barrier needs them all.  The loop and its exit are block-uniform.
+constexpr double kSweepCapCells = 1048576.0;     // r + |e| below 2^20 cells for the early stop
+constexpr double kSweepSlack = 0.125;            // cells
+
+__global__ __launch_bounds__(256) void ring_sweep_kernel(RingView V, const double *__restrict__ seg, const double *__restrict__ radius,
+                                                         uint32_t index_base, uint32_t *__restrict__ out_idx, double *__restrict__ out_t,
+                                                         WorkCounters *__restrict__ work)
+{
+    __shared__ double s_d[4];
+    __shared__ uint32_t s_i[4];
+    __shared__ unsigned long long s_w[8];
+    __shared__ unsigned long long s_tb[2];
+    const size_t slot = blockIdx.x;
+    const RingDesc &R = V.R;
+    SegGeom S;
+    double bx, by, bz, ra;
+    const double r2 = seg_load_r2(seg, radius, 0.0, slot, S, bx, by, bz, ra);
+    double bt = __builtin_huge_val();
+    uint32_t bi = kNoIndex, npts = 0, nbuckets = 0;
+    const auto offer = [&](double px, double py, double pz, uint32_t id) {
+        double t;
+        if (seg_entry_t(S, r2, px, py, pz, t) && better(t, id, bt, bi)) { bt = t; bi = id; }
+    };
+    if (threadIdx.x < 2) s_tb[threadIdx.x] = (unsigned long long)__double_as_longlong(__builtin_huge_val());
+    __syncthreads();
+    if (V.st->count != 0 && r2 >= 0.0) {                    // block-uniform
+        const uint32_t oh = V.st->ovf_head;
+        ring_for_live_records(V.ovf, oh, V.st->ovf_tail - oh, R.ovf_mask, threadIdx.x, 256u, npts, offer);
+        const SegBox C = seg_capsule_box(R, S, bx, by, bz, ra);
+        const RingBox &B = C.B;
+        const int k = fabs(S.ex) >= fabs(S.ey) && fabs(S.ex) >= fabs(S.ez) ? 0 : fabs(S.ey) >= fabs(S.ez) ? 1 : 2;
+        const double ek = k == 0 ? S.ex : k == 1 ? S.ey : S.ez, ak = k == 0 ? S.ax : k == 1 ? S.ay : S.az;
+        const int nk = k == 0 ? B.nx : k == 1 ? B.ny : B.nz, k0 = k == 0 ? B.x0 : k == 1 ? B.y0 : B.z0;
+        const int nu = k == 0 ? B.ny : B.nx, nv = k == 2 ? B.ny : B.nz, nuv = nu * nv;     // the layer's two axes: the others, in x y z order
+        const bool ordered = !C.folded && S.L2 > 0.0 && ra + sqrt(S.L2) < kSweepCapCells * R.h;
+        const bool fwd = ek >= 0.0;
+        const int lanes = C.lanes, per = 256 / lanes;
+        const int W = ordered ? max(1, per / nuv) : nk;     // layers per round
+        const double aek = fabs(ek), margin = ra + kSweepSlack * R.h;
+        const uint32_t part = threadIdx.x % (uint32_t)lanes;
+        int round = 0;
+        for (int c = 0; c < nk; c += W) {
+            const int end = min(c + W, nk) * nuv;
+            for (int m = c * nuv + (int)threadIdx.x / lanes; m < end; m += per) {
+                const int layer = m / nuv, rem = m - layer * nuv, ju = rem % nu, jv = rem / nu;
+                const int jk = fwd ? layer : nk - 1 - layer;
+                const int jx = k == 0 ? jk : ju, jy = k == 0 ? ju : k == 1 ? jk : jv, jz = k == 2 ? jk : jv;
+                if (seg_cell_skipped(R, S, C, jx, jy, jz)) continue;
+                const uint32_t b = ring_lin(R, B.x0 + jx, B.y0 + jy, B.z0 + jz);
+                const uint2 mm = V.ht[b];
+                if (part == 0) nbuckets++;
+                ring_for_live_records(V.slots + (size_t)b * R.K, mm.x, mm.y - mm.x, R.K - 1, part, (uint32_t)lanes, npts, offer);
+            }
+            const int cn = c + W;                           // the next round's first layer
+            if (cn >= nk) break;                            // block-uniform, as everything the stop test reads
+            if (bt < __builtin_huge_val()) atomicMin(&s_tb[round & 1], (unsigned long long)__double_as_longlong(bt));
+            __syncthreads();
+            const double tb = __longlong_as_double((long long)s_tb[round & 1]);
+            round++;
+            const double dist = fwd ? (double)(k0 + cn) * R.h - ak : ak - (double)(k0 + nk - cn) * R.h;
+            if (tb * aek < dist - margin) break;
+        }
+    }
+    block_argmin256(bt, bi, s_d, s_i);
+    if (threadIdx.x == 0) {
+        out_idx[slot] = reported_index(bt, bi, index_base);
+        if (out_t) out_t[slot] = bi != kNoIndex ? bt : sweep_unblocked_t(r2);
+    }
+    if (work) ring_add_work(work, npts, nbuckets, s_w);
+}
+
 // ---- the streaming form ---------------------------------------------------------------------------------------------------------
 // grid (parts, tiles): block (p, t) measures rows p * 256 + lane, + parts * 256, .. against segments t * kSegTile .. of the slice
-// and writes one partial winner per segment: part_*[q * parts + p] for the slice's segment q.
+// and writes one partial winner per segment: part_*[q * parts + p] for the slice's segment q.  SWEEP: the value is the entry
+// parameter t of seg_entry_t instead of d2, `reach` is the sweep's radius and there is no s (part_s is not touched).
+template <bool SWEEP>
 __global__ __launch_bounds__(256) void segment_stream_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
                                                              uint32_t n, const double *__restrict__ seg, const double *__restrict__ reach,
                                                              double reach_all, uint32_t Q, double *__restrict__ part_d2,
@@ -165,11 +344,8 @@ __global__ __launch_bounds__(256) void segment_stream_kernel(const float *__rest
     if (threadIdx.x < (uint32_t)kSegTile) {
         const uint32_t q = q0 + threadIdx.x;
         SegGeom S{};
-        double r2 = -1.0, bx, by, bz;
-        if (q < Q) {
-            const bool finite = seg_load(seg, q, S, bx, by, bz);
-            r2 = finite ? seg_reach2(reach ? reach[q] : reach_all) : -1.0;
-        }
+        double r2 = -1.0, bx, by, bz, ra;
+        if (q < Q) r2 = seg_load_r2(seg, reach, reach_all, q, S, bx, by, bz, ra);
         double *g = s_g[threadIdx.x];
         g[0] = S.ax; g[1] = S.ay; g[2] = S.az; g[3] = S.ex; g[4] = S.ey; g[5] = S.ez; g[6] = S.L2; g[7] = r2;
     }
@@ -184,9 +360,11 @@ __global__ __launch_bounds__(256) void segment_stream_kernel(const float *__rest
 #pragma unroll
         for (int t = 0; t < kSegTile; t++) {
             const SegGeom S{ s_g[t][0], s_g[t][1], s_g[t][2], s_g[t][3], s_g[t][4], s_g[t][5], s_g[t][6] };
-            double d2, s;
-            seg_point_d2(S, px, py, pz, d2, s);
-            if (d2 <= s_g[t][7] && d2 < bd[t]) { bd[t] = d2; bi[t] = (uint32_t)i; bs[t] = s; }     // ascending i: the first of equals stays
+            double v, s;
+            bool in;
+            if (SWEEP) { s = 0.0; in = seg_entry_t(S, s_g[t][7], px, py, pz, v); }
+            else { seg_point_d2(S, px, py, pz, v, s); in = v <= s_g[t][7]; }
+            if (in && v < bd[t]) { bd[t] = v; bi[t] = (uint32_t)i; bs[t] = s; }      // ascending i: the first of equals stays
         }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -203,13 +381,17 @@ __global__ __launch_bounds__(256) void segment_stream_kernel(const float *__rest
         for (int w = 1; w < 4; w++)
             if (better(s_rd[w][t], s_ri[w][t], d, i)) { d = s_rd[w][t]; i = s_ri[w][t]; s = s_rs[w][t]; }
         const size_t o = (size_t)(q0 + threadIdx.x) * gridDim.x + blockIdx.x;
-        part_d2[o] = d; part_idx[o] = i; part_s[o] = s;
+        part_d2[o] = d; part_idx[o] = i;
+        if (!SWEEP) part_s[o] = s;
     }
 }
 
-// one wave per segment folds its `parts` partial winners; d2 / s may be NULL
+// one wave per segment folds its `parts` partial winners; d2 / s may be NULL.  SWEEP: out_d2 receives t -- 1, or NaN for an invalid
+// sweep, when nothing blocks (seg / radius: the slice's, read again for that) -- and there is no s
+template <bool SWEEP>
 __global__ __launch_bounds__(64) void segment_finish_kernel(const double *__restrict__ part_d2, const uint32_t *__restrict__ part_idx,
                                                             const double *__restrict__ part_s, uint32_t parts, uint32_t index_base,
+                                                            const double *__restrict__ seg, const double *__restrict__ radius,
                                                             uint32_t *__restrict__ out_idx, double *__restrict__ out_d2, double *__restrict__ out_s)
 {
     const size_t q = blockIdx.x;
@@ -217,13 +399,17 @@ __global__ __launch_bounds__(64) void segment_finish_kernel(const double *__rest
     uint32_t i = kNoIndex;
     for (uint32_t p = threadIdx.x; p < parts; p += 64) {
         const size_t o = q * parts + p;
-        if (better(part_d2[o], part_idx[o], d, i)) { d = part_d2[o]; i = part_idx[o]; s = part_s[o]; }
+        if (better(part_d2[o], part_idx[o], d, i)) { d = part_d2[o]; i = part_idx[o]; if (!SWEEP) s = part_s[o]; }
     }
     seg_wave_best(d, i, s);
     if (threadIdx.x == 0) {
         out_idx[q] = reported_index(d, i, index_base);
-        if (out_d2) out_d2[q] = d;
-        if (out_s) out_s[q] = i == kNoIndex ? __builtin_nan("") : s;
+        if (SWEEP) {
+            if (out_d2) out_d2[q] = i != kNoIndex ? d : sweep_unblocked_t(sweep_r2(seg, radius, q));
+        } else {
+            if (out_d2) out_d2[q] = d;
+            if (out_s) out_s[q] = i == kNoIndex ? __builtin_nan("") : s;
+        }
     }
 }
 
@@ -235,6 +421,16 @@ __global__ __launch_bounds__(256) void segment_fill_none_kernel(uint32_t *__rest
     idx[i] = kNoIndex;
     if (d2) d2[i] = __builtin_huge_val();
     if (s) s[i] = __builtin_nan("");
+}
+
+// every sweep unblocked (an empty cloud): t = 1, or NaN for an invalid sweep
+__global__ __launch_bounds__(256) void sweep_fill_none_kernel(const double *__restrict__ seg, const double *__restrict__ radius,
+                                                              uint32_t *__restrict__ idx, double *__restrict__ t, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    idx[i] = kNoIndex;
+    if (t) t[i] = sweep_unblocked_t(sweep_r2(seg, radius, i));
 }
 
 // ---- capsule inflation ----------------------------------------------------------------------------------------------------------

@@ -226,6 +226,8 @@ def lib():
         L.pct_segment_nn_batch.argtypes = [vp, i32, f64p, f64p, i64, u32p, f64p, f64p]
         L.pct_segment_nn_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp, vp, vp]
         L.pct_segment_inflate_batch.argtypes = [vp, C.POINTER(InflateParams), f64p, i64, f64p, u32p, f64p]
+        L.pct_segment_sweep_batch.argtypes = [vp, i32, f64p, f64p, i64, u32p, f64p]
+        L.pct_segment_sweep_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp, vp]
         L.pct_bezier_check.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.c_double, C.c_double,
                                        C.POINTER(i64), C.POINTER(i64), i64, f64p, f64p, f64p, u32p]
         L.pct_nn_batch_dev.argtypes = [vp, i32, vp, i64, vp, vp, vp]
@@ -729,6 +731,17 @@ class Cloud:
         _chk(lib().pct_segment_inflate_batch(self._h, C.byref(params), _ptr(seg), len(seg), _ptr(rad), _ptr(idx), _ptr(s)))
         return rad, idx, s
 
+    def segment_sweep(self, segments, radius, algo: int = ALGO_AUTO):
+        """the first contact of a sphere swept along every segment (pct_segment_sweep_batch): segments [Q, 6] (a then b) or [Q, 2, 3],
+        radius a scalar or [Q]; (idx uint32 [Q], t float64 [Q]) -- the point that stops the sphere and how far along a -> b its centre
+        gets (0: in contact at the start); NO_INDEX / 1.0 where nothing blocks, NO_INDEX / NaN for an invalid sweep"""
+        seg = np.ascontiguousarray(segments, np.float64).reshape(-1, 6)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float64), (len(seg),)))
+        idx = np.empty(len(seg), np.uint32)
+        t = np.empty(len(seg), np.float64)
+        _chk(lib().pct_segment_sweep_batch(self._h, algo, _ptr(seg), _ptr(r), len(seg), _ptr(idx), _ptr(t)))
+        return idx, t
+
     def bezier_check(self, params: InflateParams, polycoef, seg_time, orders, t_start, stop_time, dt=0.02, cap=4096):
         coef = np.ascontiguousarray(polycoef, np.float64)
         st = np.ascontiguousarray(seg_time, np.float64)
@@ -802,6 +815,10 @@ class Cloud:
     def segment_nn_device(self, seg_ptr: int, reach_ptr: int, Q: int, idx_ptr: int, d2_ptr: int, s_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         """pct_segment_nn_batch_dev: seg Q x 6 and reach Q doubles on the device; d2_ptr / s_ptr may be 0; reserve_queries(Q) first"""
         _chk(lib().pct_segment_nn_batch_dev(self._h, algo, seg_ptr, reach_ptr, int(Q), idx_ptr, d2_ptr or None, s_ptr or None, stream))
+
+    def segment_sweep_device(self, seg_ptr: int, radius_ptr: int, Q: int, idx_ptr: int, t_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
+        """pct_segment_sweep_batch_dev: seg Q x 6 and radius Q doubles on the device; t_ptr may be 0; reserve_queries(Q) first"""
+        _chk(lib().pct_segment_sweep_batch_dev(self._h, algo, seg_ptr, radius_ptr, int(Q), idx_ptr, t_ptr or None, stream))
 
     def inflate_device(self, params: InflateParams, pts_ptr: int, Q: int, radius_ptr: int, idx_ptr: int = 0, d2_ptr: int = 0, stream: int = 0):
         _chk(lib().pct_inflate_batch_dev(self._h, C.byref(params), pts_ptr, int(Q), radius_ptr, idx_ptr or None, d2_ptr or None, stream))
