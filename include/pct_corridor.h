@@ -101,6 +101,18 @@ int pct_corridor_expansion_launches(pct_corridor *c, uint64_t *launches);
  * one for the sphere inflation of every node that may be re-checked -- where the reference's loop asks two per neighbour */
 int pct_corridor_repair_batches(pct_corridor *c, uint64_t *batches);
 
+/* Test hooks.
+ * get_tree: the whole search tree (SafeRegionRrtStar::getTree()), the live spheres in insertion order -- the reference's NodeList,
+ * which kd rebuilds follow.  Row i: centre (3 doubles), radius, g (cost from the root), f (distance to the goal), parent = the
+ * parent's row (-1 = none), flags bit0 = valid, bit1 = on the best route.  *n = the number of spheres (may exceed cap; only cap rows
+ * are written; any array may be NULL).
+ * debug_counters: which branches have run since the finder was created (reset does not clear them): out[0] = neighbourhood lists
+ * that came back truncated and were asked again through kd_nearest_rangef, out[1] = fused launches refused (the finder switched to
+ * the staged form), out[2] = one-by-one iterations (three single queries each), out[3] = the largest node count the kd tree had. */
+int pct_corridor_get_tree(pct_corridor *c, double *centre, float *radius, float *g, float *f, int32_t *parent, uint8_t *flags,
+                          int64_t cap, int64_t *n);
+int pct_corridor_debug_counters(pct_corridor *c, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -280,6 +280,9 @@ public:
     uint64_t expansionLaunches() const { return n_fused_launches_; }
     uint64_t repairBatches() const { return n_repair_trips_; }        // GPU round trips of the repair pass: two per pass
     void setFusedExpansion(bool on) { fused_ = on; }                  // off = nearest / clearance / range as three batched launches
+    // which branches have run (test hook; reset() keeps them): truncated neighbourhood lists that went to kd_nearest_rangef,
+    // fused launches refused (the finder switched to the staged form), grow_one calls, the largest kdx_size seen
+    void debugCounters(uint64_t out[4]) const { out[0] = n_truncated_; out[1] = n_refused_; out[2] = n_grow_one_; out[3] = max_kd_size_; }
 
     // ---- corridor_finder.cpp:226-270: the drone has committed to `target`; the sphere of the current route that holds it
     // becomes the root, everything between it and the old root is cut ----
@@ -548,6 +551,7 @@ private:
         float pos[3] = { (float)T_.centre[id].x, (float)T_.centre[id].y, (float)T_.centre[id].z };
         T_.kd_slot[id] = kdx_size(kd_);
         if (kd_insertf(kd_, pos, tag(id)) != 0) throw std::runtime_error(std::string("kd_insertf: ") + pct_last_error());
+        max_kd_size_ = std::max<uint64_t>(max_kd_size_, (uint64_t)T_.kd_slot[id] + 1);
         kd_refresh(id);
     }
     // what the fused expansion kernel's steer step reads for a sphere: fp64 centre, float radius (widened)
@@ -842,6 +846,7 @@ private:
     }
     void grow_one(const Vec3 &sample, bool refine)                     // one iteration of :719-756 / :772-808
     {
+        n_grow_one_++;
         const int32_t nearest = nearest_sphere(sample);
         if (nearest == kNone || !T_.alive[nearest]) return;
         const Vec3 c = steer(sample, nearest);
@@ -864,7 +869,9 @@ private:
         const float r = (float)radius;
         if (centre.z < box_z_.first || r < safety_margin_) return nullptr;          // accept() will reject it before looking
         const float cposf[3] = { (float)centre.x, (float)centre.y, (float)centre.z };
-        return count >= 0 ? kdx_range_from_candidates(kd_, cposf, r * 2.0f, ids, count, n0) : kd_nearest_rangef(kd_, cposf, r * 2.0f);
+        if (count >= 0) return kdx_range_from_candidates(kd_, cposf, r * 2.0f, ids, count, n0);
+        n_truncated_++;
+        return kd_nearest_rangef(kd_, cposf, r * 2.0f);
     }
 
     // Speculative batch with ONE launch: kdx_expand_batch answers nearest sphere -> steer -> clearance -> neighbourhood candidates
@@ -890,6 +897,7 @@ private:
             for (int i = 0; i < m; i++) { const Vec3 &s = la.sample[(size_t)(pos + i)]; flat[3 * (size_t)i] = s.x; flat[3 * (size_t)i + 1] = s.y; flat[3 * (size_t)i + 2] = s.z; }
             if (kdx_expand_batch(kd_, map_.handle(), &map_.params(), flat.data(), m, cap, res.data(), ids.data()) != 0) {
                 fused_ = false;                                       // obstacle cloud with no index at all (neither cells nor rolling map): staged path from here on
+                n_refused_++;
                 rng_.setState(la.rng_before[(size_t)pos]);
                 return pos > 0 ? pos : grow_staged(K, refine);
             }
@@ -999,6 +1007,7 @@ private:
     std::vector<double> path_radii_;
     MinStdRand0 rng_;
     uint64_t n_clearance_ = 0, n_replayed_ = 0, n_restarts_ = 0, sampler_version_ = 0, kd_version_ = 0, n_fused_launches_ = 0, n_repair_trips_ = 0;
+    uint64_t n_truncated_ = 0, n_refused_ = 0, n_grow_one_ = 0, max_kd_size_ = 0;           // debugCounters()
     bool timed_ = false;            // the current call is wall-clock boxed
     Clock::time_point t_begin_{};
     double time_limit_ = 0.0;

@@ -485,6 +485,8 @@ class PortCorridor:
         L.orrt_get_path.restype = C.c_int64
         L.orrt_get_path.argtypes = [vp, _f64p, _f64p, C.c_int64]
         L.orrt_status.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        L.orrt_get_tree.restype = C.c_int64
+        L.orrt_get_tree.argtypes = [vp, _f64p, _f32p, _f32p, _f32p, _i32p, _u8p, C.c_int64]
         self.L = L
         self.h = L.orrt_create()
 
@@ -542,6 +544,14 @@ class PortCorridor:
         rad = np.zeros(4096)
         n = self.L.orrt_get_path(self.h, path, rad, 4096)
         return path.reshape(-1, 3)[:n].copy(), rad[:n].copy()
+
+    def getTree(self):
+        """the whole tree in NodeList order, laid out as corridor.SafeRegionRrtStar.getTree()"""
+        k = max(int(self.status()["nodes"]), 1)
+        t = dict(centre=np.zeros((k, 3)), radius=np.zeros(k, np.float32), g=np.zeros(k, np.float32), f=np.zeros(k, np.float32),
+                 parent=np.zeros(k, np.int32), flags=np.zeros(k, np.uint8))
+        n = self.L.orrt_get_tree(self.h, t["centre"].reshape(-1), t["radius"], t["g"], t["f"], t["parent"], t["flags"], k)
+        return {key: v[:n].copy() for key, v in t.items()}
 
     def status(self):
         pe, gn, nn, ni = C.c_int(), C.c_int(), C.c_int64(), C.c_uint64()

@@ -659,6 +659,23 @@ int64_t orrt_get_path(orrt *s, double *path, double *radius, int64_t cap)
     for (int64_t i = 0; i < s->npath && i < cap; i++) { memcpy(path + 3 * i, s->Path + 3 * i, sizeof(double) * 3); radius[i] = s->Radius[i]; }
     return s->npath;
 }
+/* the whole tree, NodeList order: row i = centre, radius, g, f, parent (pre as a NodeList position, -1 = none or not listed),
+ * flags bit0 valid, bit1 best.  Returns the node count; only cap rows are written. */
+int64_t orrt_get_tree(orrt *s, double *centre, float *radius, float *g, float *f, int32_t *parent, uint8_t *flags, int64_t cap)
+{
+    int *where = (int *)malloc(sizeof(int) * (size_t)(s->nn ? s->nn : 1));
+    for (int i = 0; i < s->nn; i++) where[i] = NONE;
+    for (int k = 0; k < s->NodeList.n; k++) where[s->NodeList.v[k]] = k;
+    for (int64_t k = 0; k < s->NodeList.n && k < cap; k++) {
+        const rnode *n = &s->nodes[s->NodeList.v[k]];
+        memcpy(centre + 3 * k, n->c, sizeof(double) * 3);
+        radius[k] = n->radius; g[k] = n->g; f[k] = n->f;
+        parent[k] = n->pre == NONE ? -1 : where[n->pre];
+        flags[k] = (uint8_t)((n->valid ? 1 : 0) | (n->best ? 2 : 0));
+    }
+    free(where);
+    return s->NodeList.n;
+}
 void orrt_status(orrt *s, int *path_exists, int *global_navi, int64_t *n_nodes, uint64_t *inflations)
 {
     if (path_exists) *path_exists = s->path_exist_status;

@@ -60,6 +60,8 @@ def lib():
         L.pct_corridor_check_traj_pt_col.argtypes = [vp, d3, C.POINTER(C.c_int)]
         L.pct_corridor_get_path.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.pct_corridor_status.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        L.pct_corridor_get_tree.argtypes = [vp] + [vp] * 6 + [C.c_int64, C.POINTER(C.c_int64)]
+        L.pct_corridor_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -261,6 +263,24 @@ class SafeRegionRrtStar:
         path = np.zeros((4096, 3)); rad = np.zeros(4096)
         self._chk(self.L.pct_corridor_get_path(self.h, path.ctypes.data_as(C.c_void_p), rad.ctypes.data_as(C.c_void_p), 4096, C.byref(n)))
         return path[:n.value].copy(), rad[:n.value].copy()
+
+    def getTree(self):
+        """test hook (pct_corridor_get_tree): the live spheres in insertion order as a dict of arrays -- centre f64 [n, 3], radius / g /
+        f f32 [n], parent i32 [n] (row of the parent, -1 = none), flags u8 [n] (bit0 valid, bit1 on the best route)"""
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_get_tree(self.h, None, None, None, None, None, None, 0, C.byref(n)))
+        k = n.value
+        t = dict(centre=np.zeros((k, 3)), radius=np.zeros(k, np.float32), g=np.zeros(k, np.float32), f=np.zeros(k, np.float32),
+                 parent=np.zeros(k, np.int32), flags=np.zeros(k, np.uint8))
+        self._chk(self.L.pct_corridor_get_tree(self.h, *[t[key].ctypes.data_as(C.c_void_p) for key in ("centre", "radius", "g", "f", "parent", "flags")],
+                                               k, C.byref(n)))
+        return t
+
+    def debugCounters(self):
+        """test hook (pct_corridor_debug_counters): which branches have run since the finder was created"""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.L.pct_corridor_debug_counters(self.h, out))
+        return dict(truncated_lists=out[0], fused_refused=out[1], grow_one=out[2], max_kd_size=out[3])
 
     def status(self):
         pe, gn, nn, ni = C.c_int(), C.c_int(), C.c_int64(), C.c_uint64()

@@ -175,5 +175,30 @@ int pct_corridor_status(pct_corridor *c, int *path_exists, int *global_navi, int
         if (inflation_queries) *inflation_queries = c->impl->inflationQueries();
     });
 }
+int pct_corridor_get_tree(pct_corridor *c, double *centre, float *radius, float *g, float *f, int32_t *parent, uint8_t *flags,
+                          int64_t cap, int64_t *n)
+{
+    return guarded([&] {
+        const auto tree = c->impl->getTree();
+        const int64_t k = (int64_t)tree.size();
+        for (int64_t i = 0; i < std::min(k, cap); i++) {
+            const pct::CorridorNode &s = tree[(size_t)i];
+            if (centre) { centre[3 * i] = s.coord.x; centre[3 * i + 1] = s.coord.y; centre[3 * i + 2] = s.coord.z; }
+            if (radius) radius[i] = s.radius;
+            if (g) g[i] = s.g;
+            if (f) f[i] = s.f;
+            if (parent) parent[i] = s.parent;
+            if (flags) flags[i] = (uint8_t)((s.valid ? 1 : 0) | (s.best ? 2 : 0));
+        }
+        if (n) *n = k;
+    });
+}
+int pct_corridor_debug_counters(pct_corridor *c, uint64_t out[4])
+{
+    return guarded([&] {
+        if (!out) throw std::runtime_error("pct_corridor_debug_counters: null argument");
+        c->impl->debugCounters(out);
+    });
+}
 
 }  // extern "C"
