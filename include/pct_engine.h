@@ -515,6 +515,12 @@ int pct_debug_ring_slot(pct_cloud *c, int64_t slot, uint32_t out[6]);
  * cloud's points + its 16 spare ones), `cell_entries` run bounds and a batch of `queries` with 32-bit byte offsets, 0 when it keeps
  * 64-bit addresses, negative for a negative argument. */
 int pct_debug_narrow_offsets(int64_t records, int64_t cell_entries, int64_t queries);
+/* diagnostics (tests; needs no GPU): bins[i] = the bin the batch sort files query i (q: Q x 3 fp32) under, for a grid of dims[3] cells
+ * at `origin` with cells of 1 / inv_h, bin shift `shift` (clamped to 0..4) and strips of `strip` bin rows (clamped to 1..by), computed
+ * on the host by the function the sort kernels run.  *nbins = the number of bins (every bins[i] is below it), *fast = 1 when the index
+ * build would choose the multiply-free form for such a grid, 0 for the generic one (both give the same bins). */
+int pct_debug_query_bins(const int32_t dims[3], const float origin[3], float inv_h, int shift, int strip, const float *q, int64_t Q,
+                         uint32_t *bins, uint32_t *nbins, int *fast);
 
 /* Build / drop the uniform-cell index used by PCT_ALGO_GRID.  cell_size <= 0 picks one from
  * the bounding box and point count (about `pct` points per cell). */

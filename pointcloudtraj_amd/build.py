@@ -40,7 +40,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
             os.path.join(ROOT, "include", "kdtree", "kdtree_ext.h")]
     hdrs += [os.path.join(ROOT, "include", "pct_voxel.h"), os.path.join(ROOT, "include", "pct_traj.h")]
     eng_units = [os.path.join(CSRC, "engine.hip"), os.path.join(CSRC, "voxel.hip"), os.path.join(CSRC, "traj.hip"), os.path.join(CSRC, "nodeset.hip")]
-    eng_src = eng_units + [os.path.join(CSRC, f) for f in ("kernels.hpp", "scan.hpp", "gridbuild.hpp", "pyramid.hpp", "bernstein.hpp", "brute2.hpp", "knn.hpp", "rsearch.hpp", "ring.hpp", "ring_dedup.hpp", "ring_remove.hpp", "ring_compact.hpp", "ring_depth.hpp", "ring_outlier.hpp", "ring_statistical.hpp", "vox_key.hpp", "ring_search.hpp", "segment.hpp", "bezier_batch.hpp", "ring_host.inc", "engine_internal.hpp", "hostmem.hpp")]
+    eng_src = eng_units + [os.path.join(CSRC, f) for f in ("kernels.hpp", "query_bin.hpp", "scan.hpp", "gridbuild.hpp", "pyramid.hpp", "bernstein.hpp", "brute2.hpp", "knn.hpp", "rsearch.hpp", "ring.hpp", "ring_dedup.hpp", "ring_remove.hpp", "ring_compact.hpp", "ring_depth.hpp", "ring_outlier.hpp", "ring_statistical.hpp", "vox_key.hpp", "ring_search.hpp", "segment.hpp", "bezier_batch.hpp", "ring_host.inc", "engine_internal.hpp", "hostmem.hpp")]
     if force or _stale(ENGINE_SO, eng_src + hdrs):
         cmd = [HIPCC, *COMMON, "-o", ENGINE_SO, *eng_units]
         if verbose:

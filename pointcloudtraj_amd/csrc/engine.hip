@@ -846,14 +846,18 @@ int bin_queries(pct_cloud *c, const float *d_q, int64_t Q, hipStream_t s, const 
     uint32_t *total1 = c->d_sort1 + (c->sort_phase ? kSortBuckets : 0), *total1_next = c->d_sort1 + (c->sort_phase ? 0 : kSortBuckets);
     uint32_t *fill1 = c->d_sort1 + 2 * kSortBuckets;
     // ~128 blocks: small batches want parallelism (64 K queries: 21 us at 1024 per block, 36 us at 8192), large ones
-    // want long per-block bucket slices (1 M: 67 us at 8192, 87 us at 1024)
+    // want long per-block bucket slices (1 M: 67 us at 8192, 87 us at 1024; with the multiply-free bin 4096 per block still costs
+    // the step 2.8 us more than 8192, profiles/qsort_bin_ab.txt)
     const uint32_t per_block = (uint32_t)std::min<int64_t>(kSortPerBlock, std::max<int64_t>(1024, (Q / 128 + 1023) / 1024 * 1024));
     const int nb = ceil_div(Q, (int64_t)per_block);
     // 16-byte aligned query arrays are fetched four queries (three float4) at a time (kernels.hpp sort_load_items)
+    // the bin's arithmetic (query_bin.hpp) is the cloud's choice, made when its index was built: B.fast
     with_bool((reinterpret_cast<uintptr_t>(d_q) & 15u) == 0, [&](auto aligned) {
-        constexpr bool A = decltype(aligned)::value;
-        qsort_hist_kernel<A><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, pingpong ? total1_next : nullptr);
-        qsort_scatter1_kernel<A><<<nb, 1024, 0, s>>>(c->G, B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, c->d_qsorted);
+        with_bool(B.fast != 0, [&](auto fast) {
+            constexpr bool A = decltype(aligned)::value, F = decltype(fast)::value;
+            qsort_hist_kernel<A, F><<<nb, 1024, 0, s>>>(B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, pingpong ? total1_next : nullptr);
+            qsort_scatter1_kernel<A, F><<<nb, 1024, 0, s>>>(B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, c->d_qsorted);
+        });
     });
     if (pingpong) c->sort_phase ^= 1;
     else HIPCHK(hipMemsetAsync(total1, 0, sizeof(uint32_t) * kSortBuckets, s));
@@ -1875,6 +1879,20 @@ int pct_debug_narrow_offsets(int64_t records, int64_t cell_entries, int64_t quer
     return narrow_offsets_fit((uint64_t)records, (uint64_t)cell_entries, (uint64_t)queries) ? 1 : 0;
 }
 
+/* diagnostics (tests): the sort's bin of every query, by the shipped function (query_bin.hpp) compiled for the host, in the form the
+ * index build would choose for such a grid; touches no device */
+int pct_debug_query_bins(const int32_t dims[3], const float origin[3], float inv_h, int shift, int strip, const float *q, int64_t Q,
+                         uint32_t *bins, uint32_t *nbins, int *fast)
+{
+    if (!dims || !origin || dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || Q < 0 || (Q > 0 && (!q || !bins))) return fail(PCT_ERR_INVALID, "bad query_bins arguments");
+    const BinDesc B = bin_desc_make(dims[0], dims[1], dims[2], origin[0], origin[1], origin[2], inv_h, shift, strip);
+    for (int64_t i = 0; i < Q; i++)
+        bins[i] = B.fast ? query_bin<true>(B, q[3 * i], q[3 * i + 1], q[3 * i + 2]) : query_bin<false>(B, q[3 * i], q[3 * i + 1], q[3 * i + 2]);
+    if (nbins) *nbins = B.nbins;
+    if (fast) *fast = B.fast;
+    return PCT_OK;
+}
+
 int pct_cloud_grid_info(const pct_cloud *c, int32_t dims[3], float *cell_size, float origin[3], int64_t *ncells)
 {
     if (!c || !c->has_grid) return fail(PCT_ERR_INVALID, "no grid");
@@ -1980,17 +1998,14 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     }
     c->G = G;
     // query bins: (2^shift)^3 cells each
-    BinDesc B{};
-    B.shift = 1;
-    if (const char *eb = std::getenv("PCT_BIN_SHIFT")) B.shift = std::max(0, std::min(4, std::atoi(eb)));
-    B.bx = ((G.gx - 1) >> B.shift) + 1;
-    B.by = ((G.gy - 1) >> B.shift) + 1;
-    B.bz = ((G.gz - 1) >> B.shift) + 1;
-    B.strip = 16;
-    if (const char *es = std::getenv("PCT_BIN_STRIP")) B.strip = std::max(1, std::atoi(es));
-    B.strip = std::min(B.strip, B.by);
-    B.nbins = (uint32_t)B.bx * (uint32_t)(((B.by + B.strip - 1) / B.strip) * B.strip) * (uint32_t)B.bz;
-    c->B = B;
+    // (bin_desc_make, query_bin.hpp: clamps the two knobs, prepares the sort kernels' constants and chooses the bin's form)
+    int bin_shift = 1, bin_strip = 16;
+    if (const char *eb = std::getenv("PCT_BIN_SHIFT")) bin_shift = std::max(0, std::min(4, std::atoi(eb)));
+    if (const char *es = std::getenv("PCT_BIN_STRIP")) bin_strip = std::max(1, std::atoi(es));
+    c->B = bin_desc_make(G.gx, G.gy, G.gz, G.ox, G.oy, G.oz, G.inv_h, bin_shift, bin_strip);
+    // With at most 1025 cells per axis (above) every grid built here takes the multiply-free form; PCT_BIN_FORM=0 (read at every
+    // build) selects the generic one, which is otherwise out of the tests' reach on the card.
+    if (const char *ef = std::getenv("PCT_BIN_FORM")) if (std::atoi(ef) == 0) c->B.fast = 0;
     c->has_grid = true;
     c->generation++;
     return PCT_OK;

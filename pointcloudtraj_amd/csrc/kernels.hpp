@@ -13,6 +13,7 @@
 
 #include "bernstein.hpp"
 #include "scan.hpp"
+#include "query_bin.hpp"
 
 namespace pct {
 
@@ -822,12 +823,7 @@ struct GridDesc {
     const uint4 *blocks;
 };
 
-__device__ __forceinline__ int cell_coord(float v, float o, float inv_h, int g)
-{
-    float t = floorf((v - o) * inv_h);
-    t = fminf(fmaxf(t, 0.0f), (float)(g - 1));
-    return (int)t;
-}
+// (cell_coord: query_bin.hpp, shared with the host)
 
 __device__ __forceinline__ uint32_t cell_lin(const GridDesc &G, int cx, int cy, int cz)
 {
@@ -954,24 +950,9 @@ __global__ __launch_bounds__(256) void cell_scatter_kernel(const float *__restri
     }
 }
 
-// Query binning for the cell-pruned kernels: a counting sort of the batch by coarse cell
-// ((cx,cy,cz) >> shift, x fastest) so that neighbouring lanes walk neighbouring cells and
-// share cache lines.  Random 1M-query batches ran 2.5x faster pre-sorted.
-// Bin order = (y-strip, z, y inside the strip, x): walking the batch in this order sweeps a strip
-// of `strip` bin rows through all z before moving to the next strip, so the planes a stretch of
-// queries re-uses (z-1, z, z+1) are a strip wide, not a whole plane wide, and stay inside one
-// XCD's 4 MiB L2 (a full-plane sweep re-fetched every plane ~3x, measured).
-struct BinDesc { int shift, bx, by, bz, strip; uint32_t nbins; };
-
-__device__ __forceinline__ uint32_t query_bin(const GridDesc &G, const BinDesc &B, float qx, float qy, float qz)
-{
-    const int cx = cell_coord(qx, G.ox, G.inv_h, G.gx) >> B.shift;
-    const int cy = cell_coord(qy, G.oy, G.inv_h, G.gy) >> B.shift;
-    const int cz = cell_coord(qz, G.oz, G.inv_h, G.gz) >> B.shift;
-    const uint32_t s = (uint32_t)cy / (uint32_t)B.strip, yin = (uint32_t)cy % (uint32_t)B.strip;
-    return ((s * (uint32_t)B.bz + (uint32_t)cz) * (uint32_t)B.strip + yin) * (uint32_t)B.bx + (uint32_t)cx;
-}
-
+// Query binning for the cell-pruned kernels: a counting sort of the batch by coarse cell (BinDesc, query_bin<FAST>: query_bin.hpp,
+// where the bin order and its two forms are described; FAST is the host's choice per cloud, B.fast).
+//
 // Counting sort of the batch on LDS histograms (a global-atomic version ran 2 M scattered
 // device-scope atomics at ~20 G/s = 100 us per 1 M queries).  key = bin >> key_shift (< 2^20);
 // bucket = key >> kSortLShift (<= 1024 buckets), queries left in arrival order inside a bucket.
@@ -985,25 +966,33 @@ constexpr int kSortPerBlock = 1024 * kSortItems;      // most queries per block 
 // A thread's kSortItems queries of the sort kernels.  VEC (the query array is 16-byte aligned): the thread owns chunks of 4 CONSECUTIVE
 // queries and fetches each chunk as three float4 (48 contiguous bytes) instead of twelve dwords at a stride of 12 bytes: a quarter of the
 // load instructions.  Item k of thread `tid` is query sort_item<VEC>(base, k, tid); an item is live when sort_item_live says so.
+// FULL: the block owns kSortPerBlock queries and all of them exist (one block-uniform test in the kernels, sort_block_full): every item
+// of every thread is live, so nothing below is tested per item -- no exec-mask save / branch pair around each item, no sentinel key.
+// At 1 M queries every block is such a block; the ragged last block and the smaller batches (fewer than kSortItems items) take FULL = false.
+__device__ __forceinline__ bool sort_block_full(uint32_t base, uint32_t per_block, uint32_t Q)
+{
+    return per_block == (uint32_t)kSortPerBlock && Q - base >= per_block;      // base < Q: the launch has ceil(Q / per_block) blocks
+}
 template <bool VEC>
 __device__ __forceinline__ uint32_t sort_item(uint32_t base, int k, uint32_t tid)
 {
     return VEC ? base + 4u * (tid + 1024u * (uint32_t)(k >> 2)) + (uint32_t)(k & 3) : base + (uint32_t)k * 1024u + tid;
 }
-template <bool VEC>
+template <bool VEC, bool FULL = false>
 __device__ __forceinline__ bool sort_item_live(uint32_t base, int k, uint32_t tid, int items, uint32_t Q)
 {
+    if (FULL) return true;
     if (VEC) return (tid + 1024u * (uint32_t)(k >> 2)) < 256u * (uint32_t)items && sort_item<true>(base, k, tid) < Q;
     return k < items && sort_item<false>(base, k, tid) < Q;
 }
-template <bool VEC>
+template <bool VEC, bool FULL>
 __device__ __forceinline__ void sort_load_items(const float *__restrict__ q, uint32_t base, uint32_t tid, int items, uint32_t Q, float (&qv)[kSortItems][3])
 {
     if (VEC) {
 #pragma unroll
         for (int g = 0; g < kSortItems / 4; g++) {
             const uint32_t t0 = sort_item<true>(base, 4 * g, tid);
-            if ((tid + 1024u * (uint32_t)g) < 256u * (uint32_t)items && t0 + 3u < Q) {       // base is a multiple of 1024: 3 * t0 floats = a multiple of 12
+            if (FULL || ((tid + 1024u * (uint32_t)g) < 256u * (uint32_t)items && t0 + 3u < Q)) {       // base is a multiple of 1024: 3 * t0 floats = a multiple of 12
                 const float4 *v = reinterpret_cast<const float4 *>(q + 3 * (size_t)t0);
                 const float4 A = v[0], B = v[1], C = v[2];
                 qv[4 * g][0] = A.x; qv[4 * g][1] = A.y; qv[4 * g][2] = A.z;
@@ -1024,18 +1013,32 @@ __device__ __forceinline__ void sort_load_items(const float *__restrict__ q, uin
 #pragma unroll
         for (int k = 0; k < kSortItems; k++) {
             const uint32_t t = sort_item<false>(base, k, tid);
-            const bool ok = sort_item_live<false>(base, k, tid, items, Q);
+            const bool ok = sort_item_live<false, FULL>(base, k, tid, items, Q);
             qv[k][0] = ok ? q[3 * t] : 0.0f; qv[k][1] = ok ? q[3 * t + 1] : 0.0f; qv[k][2] = ok ? q[3 * t + 2] : 0.0f;
         }
     }
+}
+
+// the histogram pass over one block's items: bucket = bin >> bshift (key_shift + kSortLShift: the key itself is never needed)
+template <bool VEC, bool FAST, bool FULL>
+__device__ __forceinline__ void qsort_hist_items(const BinDesc &B, int bshift, const float *__restrict__ q, uint32_t Q, uint32_t base, int items,
+                                                 uint32_t *h)
+{
+    // all of a thread's queries are requested before the first is used: the loop used to pay one memory round trip per item
+    float qv[kSortItems][3];
+    sort_load_items<VEC, FULL>(q, base, threadIdx.x, items, Q, qv);
+#pragma unroll
+    for (int k = 0; k < kSortItems; k++)
+        if (sort_item_live<VEC, FULL>(base, k, threadIdx.x, items, Q))
+            atomicAdd(&h[query_bin<FAST>(B, qv[k][0], qv[k][1], qv[k][2]) >> bshift], 1u);     // recomputed by the scatter pass
 }
 
 // Two dependent launches per batch (hist -> scatter1); at <= 256 K queries the sort is launch-latency-bound, so the bucket scan
 // lives inside scatter1 and the counter arrays are re-zeroed without extra launches where possible: total1 is zero on entry
 // (zeroed at allocation, then by the previous batch's hist pass through total1_next, or by a memset behind scatter1 when the
 // batch is captured), fill1 is zeroed here, before any scatter1 block can touch it.
-template <bool VEC>
-__global__ __launch_bounds__(1024) void qsort_hist_kernel(GridDesc G, BinDesc B, int key_shift, const float *__restrict__ q,
+template <bool VEC, bool FAST>
+__global__ __launch_bounds__(1024) void qsort_hist_kernel(BinDesc B, int key_shift, const float *__restrict__ q,
                                                           uint32_t Q, uint32_t per_block,
                                                           uint32_t *__restrict__ total1, uint32_t *__restrict__ fill1,
                                                           uint32_t *__restrict__ total1_next)
@@ -1050,25 +1053,52 @@ __global__ __launch_bounds__(1024) void qsort_hist_kernel(GridDesc G, BinDesc B,
     __syncthreads();
     const uint32_t base = blockIdx.x * per_block;
     const int items = (int)(per_block >> 10);             // per_block is a multiple of 1024, at most kSortPerBlock
-    // all of a thread's queries are requested before the first is used: the loop used to pay one memory round trip per item
-    float qv[kSortItems][3];
-    sort_load_items<VEC>(q, base, threadIdx.x, items, Q, qv);
-#pragma unroll
-    for (int k = 0; k < kSortItems; k++) {
-        if (sort_item_live<VEC>(base, k, threadIdx.x, items, Q)) {
-            const uint32_t key = query_bin(G, B, qv[k][0], qv[k][1], qv[k][2]) >> key_shift;     // recomputed by the scatter pass
-            atomicAdd(&h[key >> kSortLShift], 1u);
-        }
-    }
+    const int bshift = key_shift + kSortLShift;
+    if (sort_block_full(base, per_block, Q)) qsort_hist_items<VEC, FAST, true>(B, bshift, q, Q, base, items, h);
+    else qsort_hist_items<VEC, FAST, false>(B, bshift, q, Q, base, items, h);
     __syncthreads();
     for (int i = threadIdx.x; i < kSortBuckets; i += 1024)
         if (h[i]) atomicAdd(&total1[i], h[i]);
 }
 
+// the scatter pass over one block's items (every thread of the block goes the same way: the barriers are block-uniform)
+template <bool VEC, bool FAST, bool FULL>
+__device__ __forceinline__ void qsort_scatter_items(const BinDesc &B, int bshift, const float *__restrict__ q, uint32_t Q, uint32_t base, int items,
+                                                    uint32_t start, uint32_t *__restrict__ fill1, float4 *__restrict__ qsorted,
+                                                    uint32_t *h, uint32_t *basepos)
+{
+    // all of a thread's queries are requested up front (one round trip instead of one per item)
+    uint32_t bucket[kSortItems];                      // 0xFFFFFFFF: no such item (never with FULL)
+    float qv[kSortItems][3];
+    sort_load_items<VEC, FULL>(q, base, threadIdx.x, items, Q, qv);
+#pragma unroll
+    for (int k = 0; k < kSortItems; k++)
+        bucket[k] = sort_item_live<VEC, FULL>(base, k, threadIdx.x, items, Q) ? query_bin<FAST>(B, qv[k][0], qv[k][1], qv[k][2]) >> bshift : 0xFFFFFFFFu;
+    // the histogram atomic's return value IS the query's rank inside (block, bucket): one LDS atomic per query, not two
+    uint32_t rank[kSortItems];
+#pragma unroll
+    for (int k = 0; k < kSortItems; k++)
+        if (FULL || bucket[k] != 0xFFFFFFFFu) rank[k] = atomicAdd(&h[bucket[k]], 1u);
+    __syncthreads();
+    {
+        const uint32_t mine = h[threadIdx.x];
+        basepos[threadIdx.x] = mine ? start + atomicAdd(&fill1[threadIdx.x], mine) : 0u;   // this block's slice of the bucket
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kSortItems; k++) {
+        if (FULL || bucket[k] != 0xFFFFFFFFu) {
+            const uint32_t t = sort_item<VEC>(base, k, threadIdx.x);
+            const uint32_t pos = basepos[bucket[k]] + rank[k];
+            qsorted[pos] = make_float4(qv[k][0], qv[k][1], qv[k][2], __uint_as_float(t));
+        }
+    }
+}
+
 // scatter: qsorted[pos] = {qx, qy, qz, bitcast(id)}, so the search kernels get a query and its output slot with ONE 16-byte load.
 // Every block scans the 1024 bucket totals itself (thread i = bucket i) instead of waiting for a one-block scan kernel.
-template <bool VEC>
-__global__ __launch_bounds__(1024) void qsort_scatter1_kernel(GridDesc G, BinDesc B, int key_shift, const float *__restrict__ q,
+template <bool VEC, bool FAST>
+__global__ __launch_bounds__(1024) void qsort_scatter1_kernel(BinDesc B, int key_shift, const float *__restrict__ q,
                                                               uint32_t Q, uint32_t per_block, const uint32_t *__restrict__ total1,
                                                               uint32_t *__restrict__ fill1, float4 *__restrict__ qsorted)
 {
@@ -1080,32 +1110,9 @@ __global__ __launch_bounds__(1024) void qsort_scatter1_kernel(GridDesc G, BinDes
     const uint32_t start = block_exclusive<uint32_t, 1024>(total1[threadIdx.x], all);
     const uint32_t base = blockIdx.x * per_block;
     const int items = (int)(per_block >> 10);
-    // all of a thread's queries are requested up front (one round trip instead of one per item)
-    uint32_t key[kSortItems];
-    float qv[kSortItems][3];
-    sort_load_items<VEC>(q, base, threadIdx.x, items, Q, qv);
-#pragma unroll
-    for (int k = 0; k < kSortItems; k++)
-        key[k] = sort_item_live<VEC>(base, k, threadIdx.x, items, Q) ? query_bin(G, B, qv[k][0], qv[k][1], qv[k][2]) >> key_shift : 0xFFFFFFFFu;
-    // the histogram atomic's return value IS the query's rank inside (block, bucket): one LDS atomic per query, not two
-    uint32_t rank[kSortItems];
-#pragma unroll
-    for (int k = 0; k < kSortItems; k++)
-        if (key[k] != 0xFFFFFFFFu) rank[k] = atomicAdd(&h[key[k] >> kSortLShift], 1u);
-    __syncthreads();
-    {
-        const uint32_t mine = h[threadIdx.x];
-        basepos[threadIdx.x] = mine ? start + atomicAdd(&fill1[threadIdx.x], mine) : 0u;   // this block's slice of the bucket
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kSortItems; k++) {
-        if (key[k] != 0xFFFFFFFFu) {
-            const uint32_t t = sort_item<VEC>(base, k, threadIdx.x);
-            const uint32_t pos = basepos[key[k] >> kSortLShift] + rank[k];
-            qsorted[pos] = make_float4(qv[k][0], qv[k][1], qv[k][2], __uint_as_float(t));
-        }
-    }
+    const int bshift = key_shift + kSortLShift;
+    if (sort_block_full(base, per_block, Q)) qsort_scatter_items<VEC, FAST, true>(B, bshift, q, Q, base, items, start, fill1, qsorted, h, basepos);
+    else qsort_scatter_items<VEC, FAST, false>(B, bshift, q, Q, base, items, start, fill1, qsorted, h, basepos);
 }
 
 // =====================================================================================

@@ -267,6 +267,8 @@ def lib():
         L.pct_depth_classify.argtypes = [vp, vp, C.c_int32, f64p, i64, C.c_double, vp, vp]
         L.pct_debug_ring_slot.argtypes = [vp, i64, C.POINTER(C.c_uint32)]
         L.pct_debug_narrow_offsets.argtypes = [i64, i64, i64]
+        L.pct_debug_query_bins.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, vp, i64, vp,
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.pct_ctrl_points_check.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                             i64, f64p, f64p, f64p, u32p]
         L.pct_plan_create_replan.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
