@@ -231,6 +231,7 @@ struct pct_cloud {
     GbCheck last_check{};                       // as read back by the last build
     // bounding-box pyramid over the cell index (pyramid.hpp): built for clouds with sparse occupancy
     bool has_pyr = false;
+    int nn_block = 256;            // threads per block of the dense NN batch kernel (build_grid chooses; kernels.hpp kNNBlock)
     PyrDesc P{};
     DevBuf<PyrNode> pyr_nodes;
     DevBuf<unsigned char> pyr_hint;             // start level of the walk per level-0 cell
@@ -791,19 +792,19 @@ int launch_frame(pct_cloud *c, hipStream_t s, int64_t Q, Frame f, D dominant)
     return launch_frame(c, s, Q, f, no_step, dominant, no_step);
 }
 
-// The dominant kernel of a Dom::Ext frame (blocks of 256 threads).  Where dom_begin left the region to the kernel, it is launched
+// The dominant kernel of a Dom::Ext frame (blocks of THREADS threads).  Where dom_begin left the region to the kernel, it is launched
 // with its own begin / end timestamps (hipExtLaunchKernel): no marker packets on the stream -- the two hipEventRecord calls of
 // dom_begin / dom_end cost ~10 us of a 160 us step.
 // (the arguments arrive as the kernel's own parameter types: a buffer is handed over as its device pointer)
 template <typename T> struct as_declared { using type = T; };
-template <typename... P>
+template <int THREADS = 256, typename... P>
 void launch_dominant(pct_cloud *c, hipStream_t s, void (*kernel)(P...), int blocks, typename as_declared<P>::type... args)
 {
     if (!c->count_work && c->dom_valid && dom_ext_on()) {
-        hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, c->ev2, c->ev3, 0, args...);
+        hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(THREADS), 0, s, c->ev2, c->ev3, 0, args...);
         dom_done(c);
     } else
-        kernel<<<blocks, 256, 0, s>>>(args...);
+        kernel<<<blocks, THREADS, 0, s>>>(args...);
 }
 
 // streaming NN over the fp64 queries already in c->d_q64: one slice of at most c->part_q queries starting at qoff
@@ -1092,8 +1093,11 @@ int nn_run(pct_cloud *c, Path path, const float *d_q, int64_t Q, uint32_t *d_idx
                                                                                                         (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work, c->d_todo);
                     } else
                         with_bool(narrow_offsets_fit((uint64_t)c->count + kGridPad, (uint64_t)c->G.ncells + 1, (uint64_t)Q), [&](auto narrow) {
-                            launch_dominant(c, s, nn_grid_coop_kernel<CW, decltype(narrow)::value>, blocks, c->G, c->sorted, c->cell_start, d_q, (uint32_t)Q,
-                                            (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
+                            with_bool(c->nn_block == kNNBlock, [&](auto small_block) {     // the block size is the cloud's (build_grid)
+                                constexpr int BLOCK = decltype(small_block)::value ? kNNBlock : 256;
+                                launch_dominant<BLOCK>(c, s, nn_grid_coop_kernel<CW, decltype(narrow)::value, BLOCK>, ceil_div(Q, BLOCK / kCoop), c->G, c->sorted,
+                                                       c->cell_start, d_q, (uint32_t)Q, (uint32_t)c->index_base, recs, d_idx, d_d2, c->d_work);
+                            });
                         });
                 });
             }, no_step);
@@ -1997,6 +2001,11 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
         }
     }
     c->G = G;
+    // Block size of the dense NN batch kernel: two waves where the cell-sorted records fit the 256 MiB Infinity Cache, four where the
+    // batch waits on HBM (measured at 10 M and 100 M points, kernels.hpp nn_grid_coop_kernel; the line between them is this reasoning,
+    // not a sweep).  PCT_NN_BLOCK = 128 / 256 (read at every build) overrides it: same answers either way.
+    c->nn_block = (uint64_t)(c->count + kGridPad) * sizeof(float4) <= (256ull << 20) ? kNNBlock : 256;
+    if (const char *eb = std::getenv("PCT_NN_BLOCK")) { const int b = std::atoi(eb); if (b == kNNBlock || b == 256) c->nn_block = b; }
     // query bins: (2^shift)^3 cells each
     // (bin_desc_make, query_bin.hpp: clamps the two knobs, prepares the sort kernels' constants and chooses the bin's form)
     int bin_shift = 1, bin_strip = 16;

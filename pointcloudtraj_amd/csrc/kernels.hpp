@@ -1832,8 +1832,17 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
 // NARROW (chosen per launch on the host: narrow_offsets_fit, gridbuild.hpp) addresses the records, the run bounds, the sorted query and
 // the two results with 32-bit byte offsets from their scalar bases (ld_at / st_at); only the TAIL instantiation of coop_screen_rows takes
 // it -- the cube-first form, the pyramid's stage 0 and the rare paths (exact rescans, the wave's remainder search, shells) keep 64-bit addresses.
-template <bool COUNT, bool NARROW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
+// BLOCK (threads per block, chosen per cloud on the host: pct_cloud::nn_block): nothing in the kernel is shared between the waves of a
+// block -- no LDS, no barrier -- so the block is only the unit in which the dispatcher hands out wave slots, and a block of four waves
+// waits until a CU has four of its 28 slots free at once.  Blocks of kNNBlock = 128 threads (two waves, 16 queries) where the cloud's
+// records fit the Infinity Cache: headline step (profiles/nn_persist_ab.txt) 256 threads 0.1210 ms, kernel 0.1017; 128 threads 0.1188 /
+// 0.0994; 64 threads 0.1189 / 0.0992 -- below the 256-thread form in every one of five alternated rounds, 0.77 of the wave slots occupied
+// instead of 0.68.  256 threads where they do not: on the 100 M-point cloud, whose batch waits on HBM, the smaller block ran 1 M queries at
+// 0.2670 against 0.2652 ms and 8 M at 1.598 against 1.49-1.58.  The same kernel as resident blocks that walk the sorted batch in a loop
+// (one launch block per set of wave slots) ran the headline step at 0.1659 ms: DESIGN.md, retired variants.
+constexpr int kNNBlock = 128;
+template <bool COUNT, bool NARROW, int BLOCK>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(7, 7))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
                                                            const uint32_t *__restrict__ cell_start,
                                                            const float *__restrict__ q, uint32_t Q, uint32_t index_base,
                                                            const float4 *__restrict__ qsorted,
@@ -1842,7 +1851,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) voi
 {
     const uint32_t sub = threadIdx.x & (kCoop - 1);
     const uint32_t bslot = qsorted ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t slot = bslot * (256 / kCoop) + (threadIdx.x / kCoop);
+    const uint32_t slot = bslot * (BLOCK / kCoop) + (threadIdx.x / kCoop);
     uint32_t npts = 0, nruns = 0;
     if (G.octant_first) {                             // wave-cooperative fallback (see above); every lane of the wave stays in step
         const bool live = slot < Q;
