@@ -246,7 +246,8 @@ struct pct_cloud {
     DevBuf<uint4> blocks;                    // block table (kernels.hpp block_corner_kernel): 2 x uint4 per lattice corner
     BinDesc B{};
     DevBuf<float4> d_qsorted;                                                   // {x,y,z,id} records of the sorted batch (reserve_queries)
-    DevBuf<uint32_t> d_sort1;                                                   // total1 | total1 (second set) | fill1
+    DevBuf<uint32_t> d_sort1;                                                   // total1 | total1 (second set)
+    DevBuf<uint32_t> d_slice;                                                   // per sort block, its offset inside every bucket (reserve_queries)
     int sort_phase = 0;                                                         // which set of totals the next batch adds into
     // query workspaces (one group: pct_cloud_reserve_queries)
     int64_t qcap = 0;
@@ -833,6 +834,20 @@ int nn_stream_q64(pct_cloud *c, int64_t Q, uint32_t *d_idx, double *d_d2, hipStr
     return PCT_OK;
 }
 
+// The sort's blocks for a batch of Q: ~128 blocks: small batches want parallelism (64 K queries: 21 us at 1024 per block, 36 us at 8192),
+// large ones want long per-block bucket slices (1 M: 67 us at 8192, 87 us at 1024; with the multiply-free bin 4096 per block still costs
+// the step 2.8 us more than 8192, profiles/qsort_bin_ab.txt)
+static uint32_t sort_per_block(int64_t Q)
+{
+    return (uint32_t)std::min<int64_t>(kSortPerBlock, std::max<int64_t>(1024, (Q / 128 + 1023) / 1024 * 1024));
+}
+// Rows of the slice table that serve every batch of at most qcap queries.  Below kSortPerBlock per block, per_block = 1024 m >= Q / 128
+// rounded down, so Q <= 128 * 1024 m + 127 and the batch has at most 129 blocks; at kSortPerBlock it has ceil(Q / kSortPerBlock).
+static size_t sort_slice_rows(int64_t qcap)
+{
+    return (size_t)std::max<int64_t>(129, ceil_div(qcap, (int64_t)kSortPerBlock));
+}
+
 // counting sort of the batch by coarse cell (kernels.hpp qsort_*) -> c->d_qsorted; *recs_out = nullptr: small batch, arrival order
 int bin_queries(pct_cloud *c, const float *d_q, int64_t Q, hipStream_t s, const float4 **recs_out)
 {
@@ -845,19 +860,16 @@ int bin_queries(pct_cloud *c, const float *d_q, int64_t Q, hipStream_t s, const 
     // graph replays one set, so it keeps the memset behind its scatter pass instead)
     const bool pingpong = !c->capturing;
     uint32_t *total1 = c->d_sort1 + (c->sort_phase ? kSortBuckets : 0), *total1_next = c->d_sort1 + (c->sort_phase ? 0 : kSortBuckets);
-    uint32_t *fill1 = c->d_sort1 + 2 * kSortBuckets;
-    // ~128 blocks: small batches want parallelism (64 K queries: 21 us at 1024 per block, 36 us at 8192), large ones
-    // want long per-block bucket slices (1 M: 67 us at 8192, 87 us at 1024; with the multiply-free bin 4096 per block still costs
-    // the step 2.8 us more than 8192, profiles/qsort_bin_ab.txt)
-    const uint32_t per_block = (uint32_t)std::min<int64_t>(kSortPerBlock, std::max<int64_t>(1024, (Q / 128 + 1023) / 1024 * 1024));
+    const uint32_t per_block = sort_per_block(Q);
     const int nb = ceil_div(Q, (int64_t)per_block);
+    if ((size_t)nb * kSortBuckets > c->d_slice.capacity()) return fail(PCT_ERR_INVALID, "the sort's slice table has no row for block %d", nb - 1);
     // 16-byte aligned query arrays are fetched four queries (three float4) at a time (kernels.hpp sort_load_items)
     // the bin's arithmetic (query_bin.hpp) is the cloud's choice, made when its index was built: B.fast
     with_bool((reinterpret_cast<uintptr_t>(d_q) & 15u) == 0, [&](auto aligned) {
         with_bool(B.fast != 0, [&](auto fast) {
             constexpr bool A = decltype(aligned)::value, F = decltype(fast)::value;
-            qsort_hist_kernel<A, F><<<nb, 1024, 0, s>>>(B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, pingpong ? total1_next : nullptr);
-            qsort_scatter1_kernel<A, F><<<nb, 1024, 0, s>>>(B, key_shift, d_q, (uint32_t)Q, per_block, total1, fill1, c->d_qsorted);
+            qsort_hist_kernel<A, F><<<nb, 1024, 0, s>>>(B, key_shift, d_q, (uint32_t)Q, per_block, total1, c->d_slice, pingpong ? total1_next : nullptr);
+            qsort_scatter1_kernel<A, F><<<nb, 1024, 0, s>>>(B, key_shift, d_q, (uint32_t)Q, per_block, total1, c->d_slice, c->d_qsorted);
         });
     });
     if (pingpong) c->sort_phase ^= 1;
@@ -1834,7 +1846,7 @@ int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)
     c->d_q.release(); c->d_r.release(); c->d_q64.release(); c->d_r2.release(); c->d_d2.release(); c->d_radius.release();
     c->d_pts64.release(); c->d_idx.release(); c->d_count.release(); c->d_skip.release(); c->d_bound.release(); c->d_seg.release();
     c->d_part_d2.release(); c->d_part_idx.release(); c->d_cand_count.release(); c->d_cand_d2.release(); c->d_cand_idx.release();
-    c->d_ovf.release(); c->d_qsorted.release(); c->d_todo.release();
+    c->d_ovf.release(); c->d_qsorted.release(); c->d_todo.release(); c->d_slice.release();
     PCTCHK(c->d_q.reset(3 * q));
     PCTCHK(c->d_r.reset(q));
     PCTCHK(c->d_q64.reset(3 * q));
@@ -1848,11 +1860,12 @@ int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)
     PCTCHK(c->d_skip.reset(q));
     PCTCHK(c->d_bound.reset(q));
     PCTCHK(c->d_qsorted.reset(q));
+    PCTCHK(c->d_slice.reset(sort_slice_rows(q) * kSortBuckets));       // every hist launch rewrites the rows it uses: never zeroed
     PCTCHK(c->d_todo.reset(2 * q + 16));
     HIPCHK(hipMemset(c->d_todo, 0, sizeof(uint32_t) * 16));            // count and ticket: the exact-walk kernel leaves them zero after every batch
     if (!c->d_sort1) {
-        PCTCHK(c->d_sort1.reset(3 * kSortBuckets));
-        HIPCHK(hipMemset(c->d_sort1, 0, sizeof(uint32_t) * 3 * kSortBuckets));   // the sort keeps both sets of totals zero between batches
+        PCTCHK(c->d_sort1.reset(2 * kSortBuckets));
+        HIPCHK(hipMemset(c->d_sort1, 0, sizeof(uint32_t) * 2 * kSortBuckets));   // the sort keeps both sets of totals zero between batches
     }
     c->part_q = std::min<int64_t>(q, kPartQueries);
     PCTCHK(c->d_part_d2.reset((size_t)c->part_q * kMaxParts));

@@ -1036,19 +1036,24 @@ __device__ __forceinline__ void qsort_hist_items(const BinDesc &B, int bshift, c
 // Two dependent launches per batch (hist -> scatter1); at <= 256 K queries the sort is launch-latency-bound, so the bucket scan
 // lives inside scatter1 and the counter arrays are re-zeroed without extra launches where possible: total1 is zero on entry
 // (zeroed at allocation, then by the previous batch's hist pass through total1_next, or by a memset behind scatter1 when the
-// batch is captured), fill1 is zeroed here, before any scatter1 block can touch it.
+// batch is captured).
+// A block's slice of each bucket comes from the histogram pass: the atomic that adds the block's count to total1[i] returns what the
+// blocks before it (in arrival order, which is arbitrary) have added, and that is the block's offset inside bucket i.  It goes to
+// slice[block * kSortBuckets + i] (0 where the block has nothing in the bucket), one coalesced row of 4 KB per block; scatter1 block b
+// reads row b, after the launch boundary.  Invariants: total1 is zero when a hist pass starts (zeroed by whom: see above) and complete
+// when scatter1 starts; every hist launch rewrites the rows of its own blocks in full, so slice is never zeroed, and rows beyond the
+// launch's block count hold leftovers that no block of this launch reads; the table has a row for every block a reserved batch can
+// have (engine.hip sort_slice_rows).  No global atomic and no counter of its own is left in the scatter pass.
 template <bool VEC, bool FAST>
 __global__ __launch_bounds__(1024) void qsort_hist_kernel(BinDesc B, int key_shift, const float *__restrict__ q,
                                                           uint32_t Q, uint32_t per_block,
-                                                          uint32_t *__restrict__ total1, uint32_t *__restrict__ fill1,
+                                                          uint32_t *__restrict__ total1, uint32_t *__restrict__ slice,
                                                           uint32_t *__restrict__ total1_next)
 {
     __shared__ uint32_t h[kSortBuckets];
-    if (blockIdx.x == 0)
-        for (int i = threadIdx.x; i < kSortBuckets; i += 1024) {
-            fill1[i] = 0;
-            if (total1_next) total1_next[i] = 0;      // the next batch's totals (its last reader finished a batch ago): no memset on the path
-        }
+    if (blockIdx.x == 0 && total1_next)
+        for (int i = threadIdx.x; i < kSortBuckets; i += 1024)
+            total1_next[i] = 0;                       // the next batch's totals (its last reader finished a batch ago): no memset on the path
     for (int i = threadIdx.x; i < kSortBuckets; i += 1024) h[i] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * per_block;
@@ -1057,15 +1062,17 @@ __global__ __launch_bounds__(1024) void qsort_hist_kernel(BinDesc B, int key_shi
     if (sort_block_full(base, per_block, Q)) qsort_hist_items<VEC, FAST, true>(B, bshift, q, Q, base, items, h);
     else qsort_hist_items<VEC, FAST, false>(B, bshift, q, Q, base, items, h);
     __syncthreads();
+    uint32_t *row = slice + (size_t)blockIdx.x * kSortBuckets;
     for (int i = threadIdx.x; i < kSortBuckets; i += 1024)
-        if (h[i]) atomicAdd(&total1[i], h[i]);
+        row[i] = h[i] ? atomicAdd(&total1[i], h[i]) : 0u;      // what was there before: this block's offset inside bucket i
 }
 
-// the scatter pass over one block's items (every thread of the block goes the same way: the barriers are block-uniform)
+// the scatter pass over one block's items (every thread of the block goes the same way: the barrier is block-uniform).  On entry
+// h[] is zero and visible to the block, and thread i has written basepos[i] = the first position of this block's slice of bucket i.
+// An item's position is basepos[bucket] + its rank inside (block, bucket); h need not be complete before a thread writes.
 template <bool VEC, bool FAST, bool FULL>
 __device__ __forceinline__ void qsort_scatter_items(const BinDesc &B, int bshift, const float *__restrict__ q, uint32_t Q, uint32_t base, int items,
-                                                    uint32_t start, uint32_t *__restrict__ fill1, float4 *__restrict__ qsorted,
-                                                    uint32_t *h, uint32_t *basepos)
+                                                    float4 *__restrict__ qsorted, uint32_t *h, const uint32_t *basepos)
 {
     // all of a thread's queries are requested up front (one round trip instead of one per item)
     uint32_t bucket[kSortItems];                      // 0xFFFFFFFF: no such item (never with FULL)
@@ -1074,17 +1081,12 @@ __device__ __forceinline__ void qsort_scatter_items(const BinDesc &B, int bshift
 #pragma unroll
     for (int k = 0; k < kSortItems; k++)
         bucket[k] = sort_item_live<VEC, FULL>(base, k, threadIdx.x, items, Q) ? query_bin<FAST>(B, qv[k][0], qv[k][1], qv[k][2]) >> bshift : 0xFFFFFFFFu;
+    __syncthreads();                                  // publishes basepos[]; the only barrier of the pass, and in front of the ranks
     // the histogram atomic's return value IS the query's rank inside (block, bucket): one LDS atomic per query, not two
     uint32_t rank[kSortItems];
 #pragma unroll
     for (int k = 0; k < kSortItems; k++)
         if (FULL || bucket[k] != 0xFFFFFFFFu) rank[k] = atomicAdd(&h[bucket[k]], 1u);
-    __syncthreads();
-    {
-        const uint32_t mine = h[threadIdx.x];
-        basepos[threadIdx.x] = mine ? start + atomicAdd(&fill1[threadIdx.x], mine) : 0u;   // this block's slice of the bucket
-    }
-    __syncthreads();
 #pragma unroll
     for (int k = 0; k < kSortItems; k++) {
         if (FULL || bucket[k] != 0xFFFFFFFFu) {
@@ -1100,19 +1102,21 @@ __device__ __forceinline__ void qsort_scatter_items(const BinDesc &B, int bshift
 template <bool VEC, bool FAST>
 __global__ __launch_bounds__(1024) void qsort_scatter1_kernel(BinDesc B, int key_shift, const float *__restrict__ q,
                                                               uint32_t Q, uint32_t per_block, const uint32_t *__restrict__ total1,
-                                                              uint32_t *__restrict__ fill1, float4 *__restrict__ qsorted)
+                                                              const uint32_t *__restrict__ slice, float4 *__restrict__ qsorted)
 {
     static_assert(kSortBuckets == 1024, "one thread per bucket");
     __shared__ uint32_t h[kSortBuckets];
     __shared__ uint32_t basepos[kSortBuckets];
     h[threadIdx.x] = 0;                               // (published by the scan's barrier)
+    const uint32_t mine = slice[(size_t)blockIdx.x * kSortBuckets + threadIdx.x];      // this block's offset inside bucket i (the hist pass)
     uint32_t all;
     const uint32_t start = block_exclusive<uint32_t, 1024>(total1[threadIdx.x], all);
+    basepos[threadIdx.x] = start + mine;              // (published by the barrier in qsort_scatter_items)
     const uint32_t base = blockIdx.x * per_block;
     const int items = (int)(per_block >> 10);
     const int bshift = key_shift + kSortLShift;
-    if (sort_block_full(base, per_block, Q)) qsort_scatter_items<VEC, FAST, true>(B, bshift, q, Q, base, items, start, fill1, qsorted, h, basepos);
-    else qsort_scatter_items<VEC, FAST, false>(B, bshift, q, Q, base, items, start, fill1, qsorted, h, basepos);
+    if (sort_block_full(base, per_block, Q)) qsort_scatter_items<VEC, FAST, true>(B, bshift, q, Q, base, items, qsorted, h, basepos);
+    else qsort_scatter_items<VEC, FAST, false>(B, bshift, q, Q, base, items, qsorted, h, basepos);
 }
 
 // =====================================================================================
