@@ -342,6 +342,38 @@
  * the code).  The host form finishes an append in flight first and waits once; the device form is asynchronous on `stream`, allocates
  * nothing and waits for nothing (reserve the batch size first, pct_cloud_reserve_queries).
  *
+ * Capsule search (pct_segment_count_batch*, pct_segment_search_batch*, pct_segment_search_read): how many rows of the window lie within
+ * reach of a line segment, and which -- what pct_radius_count_batch / pct_radius_search_batch answer for a point, for an edge: the
+ * points around a corridor edge or a straight-line shortcut, without sampling the segment into balls.  Row i of the answer holds
+ * every row of the window that is a CANDIDATE of segment i under reach[i] in the sense of "Segment queries": the ends are narrowed to
+ * fp32 and widened, d2 is that paragraph's arithmetic, and a row is listed iff d2 <= min(reach*reach, DBL_MAX), inclusive.  A
+ * non-finite end (judged after the narrowing), a NaN reach or a negative reach gives an empty row; rows that hold a NaN (removed rows
+ * of a rolling map among them) and rows with an infinite coordinate are never listed.  A segment with a == b gives exactly the row of
+ * pct_radius_search_batch for the fp32 point a, d2 bit for bit, whenever reach*reach taken in fp64 equals the square of the fp32
+ * radius.  The result is the radius search's CSR: offsets has Q + 1 entries, offsets[0] = 0, offsets[Q] is the total, and the counts
+ * of pct_segment_count_batch are offsets[i + 1] - offsets[i] on every path.  Each entry carries idx = index_base + local index (the
+ * ring slot on a rolling map), the fp64 d2, and optionally s, the parameter of the closest point on the segment (0 at a, 1 at b) --
+ * never NaN for an entry; s is recomputed after the sort from the segment and the row the index names, of which it is a function.
+ * Order: PCT_ORDER_INDEX or PCT_ORDER_DISTANCE (d2, then index) as for the radius search; both are deterministic.  algo:
+ * PCT_ALGO_STREAM measures every row of the window, on any cloud; PCT_ALGO_GRID walks the cell index -- the cells of the capsule's
+ * bounding box, without those whose centre is farther than reach + h from the segment (the argument stands beside the code) -- and
+ * answers PCT_ERR_INVALID "without a grid" on a cloud that has none, a rolling map included; PCT_ALGO_RING walks the rolling-map index
+ * as pct_segment_nn_batch does and needs a live one, PCT_ERR_INVALID otherwise; PCT_ALGO_AUTO takes the rolling-map index when it is
+ * live, else the grid when one is built, else the streaming form; PCT_ALGO_STREAM_EXACT and an unknown algo are PCT_ERR_INVALID, as
+ * is an order other than 0 / 1.  All forms give the same bytes.  Host forms: an append in flight is finished first; the lists stay in
+ * cloud-owned device buffers of their own (20 B per entry, grown on demand -- not those of the radius search, whose last result stays
+ * readable), pct_segment_search_read copies any range of them (idx, d2 or s may be NULL), and a result lasts until the next host-form
+ * capsule search, a device-form one that borrows the buffer for its sort keys, an upload, append, grid build or drop, or destroy: a
+ * read after any of those, before any search, or of a range outside [0, total] is PCT_ERR_INVALID; n = 0 is PCT_OK.  Q == 0: PCT_OK,
+ * offsets[0] = 0, total = 0.  An empty cloud gives all-zero counts and offsets; the host forms then return PCT_ERR_EMPTY, the device
+ * forms PCT_OK.  A NULL required pointer, Q < 0 or cap < 0: PCT_ERR_INVALID with nothing written.  More than 2^32 - 1 entries:
+ * PCT_ERR_CAPACITY.  Device forms: asynchronous on `stream`, no host wait; the workspaces are those of pct_cloud_reserve_queries
+ * (reserve the batch size first; the scan's share of them is set up by the first search after a reserve).  d_offsets[Q + 1] is always
+ * written; the lists are written only when d_offsets[Q] <= cap -- tested on the device, d_idx / d_d2 / d_s stay untouched otherwise.
+ * d_d2 and d_s may be NULL; with PCT_ORDER_DISTANCE and d_d2 == NULL the sort keys live in the cloud's own capsule-search list buffer,
+ * grown to cap entries by the call.  pct_last_work reports the records read and the cells / buckets opened by the count and the
+ * fill together (the streaming form: Q x size, known on the host).
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -628,6 +660,19 @@ int pct_segment_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const d
 int pct_segment_sweep_batch(pct_cloud *c, int algo, const double *seg, const double *radius, int64_t Q, uint32_t *idx, double *t);
 int pct_segment_sweep_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_radius, int64_t Q,
                                 uint32_t *d_idx, double *d_t, void *stream);
+
+/* Capsule search (contract: top of this file, "Capsule search").  seg: Q x 6 fp64, a then b; reach[Q].  count[Q] = the rows within
+ * reach of each segment; the search returns them as a CSR (offsets[Q + 1], total) whose lists pct_segment_search_read copies out.
+ * algo: PCT_ALGO_AUTO, PCT_ALGO_STREAM, PCT_ALGO_GRID or PCT_ALGO_RING.  order: PCT_ORDER_INDEX or PCT_ORDER_DISTANCE. */
+int pct_segment_count_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, uint32_t *count);
+int pct_segment_count_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q, uint32_t *d_count, void *stream);
+int pct_segment_search_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, int order, int64_t *offsets, int64_t *total);
+/* entries [first, first + n) of the lists of the LAST pct_segment_search_batch on this cloud; idx, d2 or s may be NULL */
+int pct_segment_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2, double *s);
+/* device buffers, asynchronous on `stream`; d_offsets[Q + 1] always written, the lists (d_d2 / d_s may be NULL) only when
+ * d_offsets[Q] <= cap.  Reserve the batch size first (pct_cloud_reserve_queries). */
+int pct_segment_search_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q, int order, int64_t *d_offsets,
+                                 int64_t cap, uint32_t *d_idx, double *d_d2, double *d_s, void *stream);
 
 /* ---- one RRT* iteration's three dependent queries in ONE launch (corridor_finder.cpp:385-410 genNewNode, :428-437
  * findNearstVertex, :464 treeRewire's neighbourhood), for K samples at once: nearest tree node of the fp32-narrowed

@@ -316,6 +316,37 @@ public:
         sweepSegments(seg, 1, prm_.search_margin, &index, &t);
         return t;
     }
+    // Capsule search (pct_engine.h, paragraph "Capsule search"): the obstacle points within `reach` of each segment, as lists -- the
+    // input of a free-space decomposition around an edge, the constraints of a local optimiser, a crop before a finer check.
+    // segments: n x 6 doubles, a then b.
+    //   segmentNeighbours  row i of the result = indices / sqr_distances (/ params) entries [offsets[i], offsets[i + 1]), offsets has
+    //                      n + 1 entries; params (optional) receives the parameter of the closest point on the segment (0 at a, 1 at b).
+    //                      sorted: nearest first, ties in ascending index; otherwise ascending index.
+    //   segmentCounts      just the row lengths.
+    // A point at exactly `reach` is listed (inclusive).  The walk follows the map's index: the rolling-map bucket table, the cell index,
+    // or neither.  On an empty map every row is empty.
+    void segmentNeighbours(const std::vector<double> &segments, double reach, std::vector<int64_t> &offsets, std::vector<uint32_t> &indices,
+                           std::vector<double> &sqr_distances, std::vector<double> *params = nullptr, bool sorted = true)
+    {
+        const int64_t n = (int64_t)(segments.size() / 6);
+        const std::vector<double> reaches((size_t)n, reach);
+        offsets.assign((size_t)n + 1, 0);
+        int64_t total = 0;
+        check(pct_segment_search_batch(cloud_, PCT_ALGO_AUTO, segments.data(), reaches.data(), n, sorted ? PCT_ORDER_DISTANCE : PCT_ORDER_INDEX,
+                                       offsets.data(), &total), "pct_segment_search_batch");
+        indices.resize((size_t)total);
+        sqr_distances.resize((size_t)total);
+        if (params) params->resize((size_t)total);
+        check(pct_segment_search_read(cloud_, 0, total, indices.data(), sqr_distances.data(), params ? params->data() : nullptr),
+              "pct_segment_search_read");
+    }
+    void segmentCounts(const std::vector<double> &segments, double reach, std::vector<uint32_t> &counts)
+    {
+        const int64_t n = (int64_t)(segments.size() / 6);
+        const std::vector<double> reaches((size_t)n, reach);
+        counts.assign((size_t)n, 0u);
+        check(pct_segment_count_batch(cloud_, PCT_ALGO_AUTO, segments.data(), reaches.data(), n, counts.data()), "pct_segment_count_batch");
+    }
     // corridor_finder.cpp:661-669
     int checkNodeUpdate(double new_radius, double old_radius) const
     {

@@ -42,6 +42,7 @@
 #include "ring_search.hpp"
 #include "bezier_batch.hpp"
 #include "segment.hpp"
+#include "segment_search.hpp"
 
 using namespace pct;
 using pct_host::pow2_at_least;
@@ -278,6 +279,13 @@ struct pct_cloud {
     size_t rs_cap = 0;
     int64_t rs_total = 0;
     bool rs_valid = false;
+    // capsule search (segment_search.hpp): the lists of the host form's last result in buffers of their own (20 B per entry, grow-only)
+    // -- pct_radius_search_read promises the last RADIUS search -- valid until the cloud or its index changes
+    DevBuf<uint32_t> ss_idx;
+    DevBuf<double> ss_d2, ss_s;
+    size_t ss_cap = 0;
+    int64_t ss_total = 0;
+    bool ss_valid = false;
     // order-preserving crop (lidar): tile counts and the compacted {index, d2, x, y, z} of the last crop
     DevBuf<uint32_t> crop_tile, crop_idx;
     DevBuf<double> crop_d2;
@@ -599,6 +607,7 @@ void drop_grid(pct_cloud *c)
     if (c->has_grid) c->generation++;
     c->has_grid = false;
     c->rs_valid = false;                // every upload, append, build and drop comes through here: the last radius-search result ends
+    c->ss_valid = false;                // and the last capsule search's
     c->has_pyr = false;
 }
 
@@ -1391,6 +1400,133 @@ int rs_fill_sort(pct_cloud *c, Path path, const float *d_q, const float *d_r, in
     with_bool(by_dist, [&](auto bd) {
         rs_sort_rows_kernel<decltype(bd)::value><<<(int)std::min<int64_t>(Q, 8192), 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
     });
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// ---- capsule search (segment_search.hpp): the radius search's frame over segments ----------------------------------------------
+// `algo` of a capsule search: the rolling-map index, the cell index or the streaming form; AUTO takes the first of those the cloud has
+int resolve_capsule_algo(const pct_cloud *c, int algo, Path *path)
+{
+    if (algo == PCT_ALGO_RING && !c->ring_ready && !(c->ring_on && c->count == 0))
+        return fail(PCT_ERR_INVALID, "PCT_ALGO_RING without a rolling-map index (call pct_cloud_ring_index)");
+    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    switch (algo) {
+    case PCT_ALGO_RING:
+        *path = Path::Table;
+        break;
+    case PCT_ALGO_GRID:
+        if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid");       // a rolling map has none
+        *path = Path::Grid;
+        break;
+    case PCT_ALGO_STREAM:
+        *path = Path::Stream;
+        break;
+    default:
+        return fail(PCT_ERR_INVALID, "capsule search takes PCT_ALGO_AUTO, PCT_ALGO_STREAM, PCT_ALGO_GRID or PCT_ALGO_RING, not algo %d", algo);
+    }
+    if (c->count == 0) *path = Path::Empty;
+    return PCT_OK;
+}
+
+// the host form's lists: room for n entries (grow-only; a failed growth leaves none)
+int ss_ensure_lists(pct_cloud *c, size_t n, bool want_idx_s)
+{
+    if (n == 0 || (n <= c->ss_cap && (!want_idx_s || c->ss_idx))) return PCT_OK;
+    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the capsule-search lists during graph capture");
+    n = std::max(n, c->ss_cap);
+    c->ss_cap = 0;
+    c->ss_idx.release(); c->ss_d2.release(); c->ss_s.release();
+    PCTCHK(c->ss_d2.reset(n));
+    if (want_idx_s) {
+        PCTCHK(c->ss_idx.reset(n));
+        PCTCHK(c->ss_s.reset(n));
+    }
+    c->ss_cap = n;
+    return PCT_OK;
+}
+
+// the tiles of the streaming form, grid.y within every HIP limit: f(first tile, tiles)
+template <typename F>
+void ss_for_tile_slices(int64_t Q, F f)
+{
+    const int64_t tiles = (Q + kSegTile - 1) / kSegTile;
+    for (int64_t t0 = 0; t0 < tiles; t0 += 32768) f((uint32_t)t0, (int)std::min<int64_t>(32768, tiles - t0));
+}
+
+int ss_stream_parts(const pct_cloud *c)
+{
+    return (int)std::min<int64_t>(kSegParts, std::max<int64_t>(1, (c->count + 255) / 256));
+}
+
+// row lengths of a device-resident batch (d_seg: Q x 6, d_reach: Q) into d_count along `path`, then `after` inside the same frame
+// (the search's scan and, in the device form, its fill).  Q >= 1, within the reserved batch size.
+template <typename E>
+int ss_count_run(pct_cloud *c, Path path, const double *d_seg, const double *d_reach, int64_t Q, uint32_t *d_count, hipStream_t s, E after)
+{
+    HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint32_t) * Q, s));
+    WorkCounters *work = c->count_work ? c->d_work : nullptr;
+    switch (path) {
+    case Path::Empty:
+        return run_step(after);
+    case Path::Table:        // a block per segment over the buckets of the capsule's box
+        return launch_frame(c, s, Q, { Work::Device }, no_step,
+            [&] { ss_ring_count_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_seg, d_reach, d_count, work); }, after);
+    case Path::Grid:         // a block per segment over the cells of the capsule's box
+        return launch_frame(c, s, Q, { Work::Device }, no_step,
+            [&] { ss_grid_count_kernel<<<(int)Q, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_seg, d_reach, d_count, work); }, after);
+    default:
+        break;
+    }
+    const int parts = ss_stream_parts(c);
+    return launch_frame(c, s, Q, { Work::EveryPoint }, no_step,
+        [&] {
+            ss_for_tile_slices(Q, [&](uint32_t t0, int nt) {
+                ss_stream_count_kernel<<<dim3(parts, nt), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg, d_reach, (uint32_t)Q, t0, d_count);
+            });
+        }, after);
+}
+
+// c->d_count -> exclusive offsets in d_offsets[Q + 1]; every row of two or more entries is queued for the sort (all three fills place
+// their hits in arrival order).  The radius search's scan kernels, as they are.
+int ss_scan(pct_cloud *c, int64_t Q, long long *d_offsets, hipStream_t s)
+{
+    if (Q > c->rs_qcap || !d_offsets) return fail(PCT_ERR_INTERNAL, "capsule search without its workspaces");      // rs_ensure_work comes first
+    const int ntiles = ceil_div(Q, kRsScanTile);
+    HIPCHK(hipMemsetAsync(c->rs_queue, 0, sizeof(uint32_t), s));
+    rs_scan_tiles_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles);
+    scan_tile_sums_kernel<uint64_t><<<1, 256, 0, s>>>(c->rs_tiles, (uint32_t)ntiles, ScanDoneNothing{});
+    rs_scan_final_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles, d_offsets, 1u, c->rs_queue);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// the lists, written only when d_offsets[Q] <= cap (tested on the device): the count's walk once more (its work is added to the
+// count's, pct_last_work), the queued rows put into final order, then s per entry.  d_d2 is not NULL under PCT_ORDER_DISTANCE.
+int ss_fill_sort(pct_cloud *c, Path path, const double *d_seg, const double *d_reach, int64_t Q, int order, const long long *d_offsets,
+                 int64_t cap, uint32_t *d_idx, double *d_d2, double *d_s, hipStream_t s)
+{
+    if (path == Path::Empty || cap <= 0) return PCT_OK;      // every row is empty, or there is no room for a single entry
+    WorkCounters *work = c->count_work ? c->d_work : nullptr;
+    const uint32_t base = (uint32_t)c->index_base;
+    if (path == Path::Table) {
+        ss_ring_fill_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_seg, d_reach, (uint32_t)Q, base, d_offsets, (long long)cap, d_idx, d_d2, work);
+    } else if (path == Path::Grid) {
+        ss_grid_fill_kernel<<<(int)Q, 256, 0, s>>>(c->G, c->sorted, c->cell_start, d_seg, d_reach, (uint32_t)Q, base, d_offsets, (long long)cap, d_idx,
+                                                   d_d2, work);
+    } else {
+        HIPCHK(hipMemsetAsync(c->rs_cursor, 0, sizeof(uint32_t) * Q, s));
+        const int parts = ss_stream_parts(c);
+        ss_for_tile_slices(Q, [&](uint32_t t0, int nt) {
+            ss_stream_fill_kernel<<<dim3(parts, nt), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg, d_reach, (uint32_t)Q, t0, base, d_offsets,
+                                                                  (long long)cap, c->rs_cursor, d_idx, d_d2);
+        });
+    }
+    const int blocks = (int)std::min<int64_t>(Q, 8192);
+    with_bool(order == PCT_ORDER_DISTANCE, [&](auto bd) {
+        rs_sort_rows_kernel<decltype(bd)::value><<<blocks, 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
+    });
+    if (d_s) ss_param_kernel<<<blocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg, (uint32_t)Q, base, d_offsets, (long long)cap, d_idx, d_s);
     HIPCHK(hipGetLastError());
     return PCT_OK;
 }
@@ -2526,6 +2662,112 @@ int pct_segment_sweep_batch(pct_cloud *c, int algo, const double *seg, const dou
         return PCT_OK;
     }));
     if (path == SegPath::Empty) return fail(PCT_ERR_EMPTY, "segment sweep against an empty cloud");
+    return PCT_OK;
+}
+
+// ---- capsule search (include/pct_engine.h, "Capsule search") ------------------------------------------------------------------------
+int pct_segment_count_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q, uint32_t *d_count, void *stream)
+{
+    if (!c || Q < 0 || (Q > 0 && (!d_seg || !d_reach || !d_count))) return fail(PCT_ERR_INVALID, "bad segment_count_batch_dev arguments");
+    Path path;
+    PCTCHK(resolve_capsule_algo(c, algo, &path));
+    if (Q == 0) return PCT_OK;
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(order_after_mutations(c, (hipStream_t)stream));
+    return ss_count_run(c, path, d_seg, d_reach, Q, d_count, (hipStream_t)stream, no_step);
+}
+
+int pct_segment_count_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, uint32_t *count)
+{
+    if (!c || Q < 0 || (Q > 0 && (!seg || !reach || !count))) return fail(PCT_ERR_INVALID, "bad segment_count_batch arguments");
+    PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
+    Path path;
+    PCTCHK(resolve_capsule_algo(c, algo, &path));
+    if (Q == 0) return PCT_OK;
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(c->d_r2, reach, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
+    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {
+        PCTCHK(ss_count_run(c, path, c->d_seg, c->d_r2, Q, c->d_count, g_stream, no_step));
+        HIPCHK(hipMemcpyAsync(count, c->d_count, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return PCT_OK;
+    }));
+    if (path == Path::Empty) return fail(PCT_ERR_EMPTY, "capsule count against an empty cloud");
+    return PCT_OK;
+}
+
+int pct_segment_search_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q, int order, int64_t *d_offsets,
+                                 int64_t cap, uint32_t *d_idx, double *d_d2, double *d_s, void *stream)
+{
+    if (!c || Q < 0 || !d_offsets || cap < 0 || (Q > 0 && (!d_seg || !d_reach)) || (cap > 0 && !d_idx))
+        return fail(PCT_ERR_INVALID, "bad segment_search_batch_dev arguments");
+    if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
+    Path path;
+    PCTCHK(resolve_capsule_algo(c, algo, &path));
+    hipStream_t s = (hipStream_t)stream;
+    if (Q == 0) {
+        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
+        return PCT_OK;
+    }
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    if (order == PCT_ORDER_DISTANCE && !d_d2 && cap > 0) {   // the sort key needs a home: the cloud's own capsule-search list buffer
+        c->ss_valid = false;                                 // which ends the host form's last result
+        PCTCHK(ss_ensure_lists(c, (size_t)cap, false));
+        d_d2 = c->ss_d2;
+    }
+    PCTCHK(rs_ensure_work(c));
+    PCTCHK(order_after_mutations(c, s));
+    long long *off = reinterpret_cast<long long *>(d_offsets);
+    return ss_count_run(c, path, d_seg, d_reach, Q, c->d_count, s, [&]() -> int {
+        PCTCHK(ss_scan(c, Q, off, s));
+        return ss_fill_sort(c, path, d_seg, d_reach, Q, order, off, cap, d_idx, d_d2, d_s, s);
+    });
+}
+
+int pct_segment_search_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, int order, int64_t *offsets, int64_t *total)
+{
+    if (!c || Q < 0 || !offsets || !total || (Q > 0 && (!seg || !reach))) return fail(PCT_ERR_INVALID, "bad segment_search_batch arguments");
+    if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
+    PCTCHK(ring_finish_pending(c));
+    Path path;
+    PCTCHK(resolve_capsule_algo(c, algo, &path));
+    c->ss_valid = false;
+    c->ss_total = 0;
+    offsets[0] = 0;
+    *total = 0;
+    if (Q == 0) { c->ss_valid = true; return PCT_OK; }
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    PCTCHK(rs_ensure_work(c));                               // before c->rs_off is handed on
+    HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
+    HIPCHK(hipMemcpyAsync(c->d_r2, reach, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
+    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {          // before the lists are sized: count and fill must see the same table
+        PCTCHK(ss_count_run(c, path, c->d_seg, c->d_r2, Q, c->d_count, g_stream, [&] { return ss_scan(c, Q, c->rs_off, g_stream); }));
+        HIPCHK(hipMemcpyAsync(offsets, c->rs_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));              // the one host read: the total sizes the lists
+        return PCT_OK;
+    }));
+    *total = offsets[Q];
+    if (*total > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "capsule search lists %lld entries, more than 2^32 - 1", (long long)*total);
+    PCTCHK(ss_ensure_lists(c, (size_t)*total, true));
+    PCTCHK(ss_fill_sort(c, path, c->d_seg, c->d_r2, Q, order, c->rs_off, *total, c->ss_idx, c->ss_d2, c->ss_s, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    c->ss_total = *total;
+    c->ss_valid = true;
+    if (path == Path::Empty) return fail(PCT_ERR_EMPTY, "capsule search against an empty cloud");
+    return PCT_OK;
+}
+
+int pct_segment_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2, double *s)
+{
+    if (!c || !c->ss_valid) return fail(PCT_ERR_INVALID, "no capsule-search result to read (none yet, or the cloud changed since)");
+    if (first < 0 || n < 0 || first > c->ss_total || n > c->ss_total - first)
+        return fail(PCT_ERR_INVALID, "entries [%lld, %lld) lie outside [0, %lld]", (long long)first, (long long)(first + n), (long long)c->ss_total);
+    if (n == 0) return PCT_OK;
+    if (idx) HIPCHK(hipMemcpyAsync(idx, c->ss_idx + first, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g_stream));
+    if (d2) HIPCHK(hipMemcpyAsync(d2, c->ss_d2 + first, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    if (s) HIPCHK(hipMemcpyAsync(s, c->ss_s + first, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
     return PCT_OK;
 }
 

@@ -1,0 +1,405 @@
+// segment_search.hpp -- CAPSULE SEARCH: how many rows lie within reach of a line segment, and which (pct_segment_count_batch*,
+// pct_segment_search_batch*), for gfx950.
+//
+// The contract is the paragraph "Capsule search" of include/pct_engine.h: row i lists every row of the window that is a candidate
+// of segment i under reach[i] in the sense of "Segment queries" -- d2 from seg_point_d2 (segment.hpp), d2 <= r2 with r2 from
+// seg_load_r2, inclusive.  Everything is fp64 on float-widened operands, no contraction, no fp32 screen: every record that is read
+// is judged by that one test, and exactness never rests on what a walk leaves out.
+//
+// The frame is the radius search's (rsearch.hpp): count -> scan -> fill -> sort.  The count kernels below leave the row lengths in
+// the cloud's count buffer, rs_scan_tiles_kernel / scan_tile_sums_kernel / rs_scan_final_kernel turn them into CSR offsets and
+// queue every row of two or more entries (sort_min = 1: all three fills place their hits in arrival order), the fill kernels walk
+// exactly as the count did, and rs_sort_rows_kernel orders the queued rows by index or by (d2, index).  s does not travel through
+// the sort: ss_param_kernel recomputes it afterwards from the segment and the row the entry names -- it is a function of that pair
+// alone, so it is the s the fill would have carried, bit for bit.
+//
+// Three forms, same answers bit for bit:
+//   * ss_stream_*   PCT_ALGO_STREAM, any cloud: lanes own points, a tile of kSegTile segments sits in LDS (segment_stream_kernel's
+//                   shape).  Count: per-lane hit counts folded per wave, one atomic per wave and segment with hits.  Fill:
+//                   rs_fill_stream_kernel's scheme, one cursor atomic per wave, segment and step with hits, places from the ballot.
+//   * ss_ring_*     PCT_ALGO_RING: a 256-thread block per segment, ring_segment_kernel's walk: the overflow queue exhaustively,
+//                   then seg_capsule_box with seg_cell_skipped and ring_for_live_records.  The box visits every position once, so a
+//                   count is as safe there as a minimum.  The fill places hits through a cursor in LDS (ring_fill_kernel's).
+//   * ss_grid_*     PCT_ALGO_GRID: a 256-thread block per segment over the cell index -- the walk this file adds (ss_grid_walk).
+#pragma once
+#include "segment.hpp"
+
+#pragma clang fp contract(off)
+
+namespace pct {
+
+// a block's hit count into count[slot] (s_c: 4 words of LDS)
+__device__ __forceinline__ void ss_block_count(uint32_t n, uint32_t *s_c, uint32_t *__restrict__ count, size_t slot)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, kWave);
+    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) count[slot] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+}
+
+// the tile's segments into LDS: ax ay az ex ey ez L2 r2 (r2 = -1 beyond the batch: no row is a candidate)
+__device__ __forceinline__ void ss_load_tile(const double *__restrict__ seg, const double *__restrict__ reach, uint32_t q0, uint32_t Q,
+                                             double (*s_g)[8])
+{
+    if (threadIdx.x < (uint32_t)kSegTile) {
+        const uint32_t q = q0 + threadIdx.x;
+        SegGeom S{};
+        double r2 = -1.0, bx, by, bz, ra;
+        if (q < Q) r2 = seg_load_r2(seg, reach, 0.0, q, S, bx, by, bz, ra);
+        double *g = s_g[threadIdx.x];
+        g[0] = S.ax; g[1] = S.ay; g[2] = S.az; g[3] = S.ex; g[4] = S.ey; g[5] = S.ez; g[6] = S.L2; g[7] = r2;
+    }
+}
+
+// ---- the streaming form ---------------------------------------------------------------------------------------------------------
+// grid (parts, tiles): block (p, t) measures rows p * 256 + lane, + parts * 256, .. against segments (tile0 + t) * kSegTile .. and
+// adds its hits to count[] (zeroed by the caller).
+__global__ __launch_bounds__(256) void ss_stream_count_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                                                              uint32_t n, const double *__restrict__ seg, const double *__restrict__ reach,
+                                                              uint32_t Q, uint32_t tile0, uint32_t *__restrict__ count)
+{
+    __shared__ double s_g[kSegTile][8];
+    const uint32_t q0 = (tile0 + blockIdx.y) * (uint32_t)kSegTile;
+    ss_load_tile(seg, reach, q0, Q, s_g);
+    __syncthreads();
+    uint32_t c[kSegTile];
+#pragma unroll
+    for (int t = 0; t < kSegTile; t++) c[t] = 0;
+    const uint64_t step = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += step) {
+        const double px = (double)x[i], py = (double)y[i], pz = (double)z[i];
+#pragma unroll
+        for (int t = 0; t < kSegTile; t++) {
+            const SegGeom S{ s_g[t][0], s_g[t][1], s_g[t][2], s_g[t][3], s_g[t][4], s_g[t][5], s_g[t][6] };
+            double d2, s;
+            seg_point_d2(S, px, py, pz, d2, s);
+            c[t] += d2 <= s_g[t][7] ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < kSegTile; t++) {
+        uint32_t v = c[t];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, kWave);
+        if ((threadIdx.x & 63) == 0 && v != 0) atomicAdd(&count[q0 + t], v);      // v != 0 only below Q
+    }
+}
+
+// The fill: the hits of a wave's 64 points for one segment take a block of that segment's row through cursor[segment] (zeroed by the
+// caller) and their places inside it from the ballot.  A tile whose rows are all empty returns at once.
+__global__ __launch_bounds__(256) void ss_stream_fill_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                                                             uint32_t n, const double *__restrict__ seg, const double *__restrict__ reach,
+                                                             uint32_t Q, uint32_t tile0, uint32_t index_base, const long long *__restrict__ offsets,
+                                                             long long cap, uint32_t *__restrict__ cursor, uint32_t *__restrict__ out_idx,
+                                                             double *__restrict__ out_d2)
+{
+    __shared__ double s_g[kSegTile][8];
+    __shared__ long long s_off[kSegTile];
+    __shared__ uint32_t s_len[kSegTile];
+    if (offsets[Q] > cap) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t q0 = (tile0 + blockIdx.y) * (uint32_t)kSegTile;
+    const int qcount = (int)min((uint32_t)kSegTile, Q - q0);
+    if (offsets[q0 + qcount] == offsets[q0]) return;          // block-uniform
+    ss_load_tile(seg, reach, q0, Q, s_g);
+    if (threadIdx.x < (uint32_t)kSegTile) {
+        const bool have = (int)threadIdx.x < qcount;
+        const long long o = have ? offsets[q0 + threadIdx.x] : 0;
+        s_off[threadIdx.x] = o;
+        s_len[threadIdx.x] = have ? (uint32_t)(offsets[q0 + threadIdx.x + 1] - o) : 0u;
+    }
+    __syncthreads();
+    const uint32_t stride = gridDim.x * 256u;
+    for (uint64_t base = blockIdx.x * 256u + (uint32_t)wave * 64u; base < n; base += stride) {      // wave-uniform trip count
+        const uint32_t p = (uint32_t)min(base + (uint64_t)lane, (uint64_t)kNoIndex);
+        const bool have = p < n;
+        const double px = have ? (double)x[p] : 0.0, py = have ? (double)y[p] : 0.0, pz = have ? (double)z[p] : 0.0;
+#pragma unroll
+        for (int t = 0; t < kSegTile; t++) {
+            if (t >= qcount) break;
+            const SegGeom S{ s_g[t][0], s_g[t][1], s_g[t][2], s_g[t][3], s_g[t][4], s_g[t][5], s_g[t][6] };
+            double d2, s;
+            seg_point_d2(S, px, py, pz, d2, s);
+            const bool hit = have && d2 <= s_g[t][7];
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+            if (m) {                                              // wave-uniform
+                uint32_t first = 0;
+                if (lane == 0) first = atomicAdd(&cursor[q0 + t], (uint32_t)__popcll(m));
+                first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+                const uint32_t pos = first + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                if (hit && pos < s_len[t]) {                      // every list store is bounded by the row's own length
+                    out_idx[s_off[t] + pos] = p + index_base;
+                    if (out_d2) out_d2[s_off[t] + pos] = d2;
+                }
+            }
+        }
+    }
+}
+
+// ---- the rolling-map form -------------------------------------------------------------------------------------------------------
+// ring_segment_kernel's walk with another offer: every live record of the overflow queue, then of the capsule's box, once.
+template <typename F>
+__device__ __forceinline__ void ss_ring_walk(const RingView &V, const SegGeom &S, double bx, double by, double bz, double ra, uint32_t &npts,
+                                             uint32_t &nbuckets, F offer)
+{
+    const RingDesc &R = V.R;
+    const uint32_t oh = V.st->ovf_head;
+    ring_for_live_records(V.ovf, oh, V.st->ovf_tail - oh, R.ovf_mask, threadIdx.x, 256u, npts, offer);
+    const SegBox C = seg_capsule_box(R, S, bx, by, bz, ra);
+    const RingBox &B = C.B;
+    const int lanes = C.lanes;
+    const uint32_t part = threadIdx.x % (uint32_t)lanes;
+    for (int k = (int)threadIdx.x / lanes; k < C.total; k += 256 / lanes) {
+        const int jx = k % B.nx, jy = (k / B.nx) % B.ny, jz = k / (B.nx * B.ny);
+        if (seg_cell_skipped(R, S, C, jx, jy, jz)) continue;
+        const uint32_t b = ring_lin(R, B.x0 + jx, B.y0 + jy, B.z0 + jz);
+        const uint2 m = V.ht[b];
+        if (part == 0) nbuckets++;
+        ring_for_live_records(V.slots + (size_t)b * R.K, m.x, m.y - m.x, R.K - 1, part, (uint32_t)lanes, npts, offer);
+    }
+}
+
+__global__ __launch_bounds__(256) void ss_ring_count_kernel(RingView V, const double *__restrict__ seg, const double *__restrict__ reach,
+                                                            uint32_t *__restrict__ count, WorkCounters *__restrict__ work)
+{
+    __shared__ uint32_t s_c[4];
+    __shared__ unsigned long long s_w[8];
+    const size_t slot = blockIdx.x;
+    SegGeom S;
+    double bx, by, bz, ra;
+    const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);
+    uint32_t n = 0, npts = 0, nbuckets = 0;
+    if (V.st->count != 0 && r2 >= 0.0)                      // block-uniform
+        ss_ring_walk(V, S, bx, by, bz, ra, npts, nbuckets, [&](double px, double py, double pz, uint32_t) {
+            double d2, s;
+            seg_point_d2(S, px, py, pz, d2, s);
+            n += d2 <= r2 ? 1u : 0u;
+        });
+    ss_block_count(n, s_c, count, slot);
+    if (work) ring_add_work(work, npts, nbuckets, s_w);
+}
+
+// the count's walk and test on the same table (same stream, no append in between): row i receives exactly its length in hits
+__global__ __launch_bounds__(256) void ss_ring_fill_kernel(RingView V, const double *__restrict__ seg, const double *__restrict__ reach, uint32_t Q,
+                                                           uint32_t index_base, const long long *__restrict__ offsets, long long cap,
+                                                           uint32_t *__restrict__ out_idx, double *__restrict__ out_d2,
+                                                           WorkCounters *__restrict__ work)
+{
+    __shared__ uint32_t s_cursor;
+    __shared__ unsigned long long s_w[8];
+    if (offsets[Q] > cap) return;
+    const size_t slot = blockIdx.x;
+    const long long off0 = offsets[slot];
+    const uint32_t len = (uint32_t)(offsets[slot + 1] - off0);
+    if (len == 0) return;                                   // block-uniform: an empty row is not walked at all
+    if (threadIdx.x == 0) s_cursor = 0;
+    __syncthreads();
+    SegGeom S;
+    double bx, by, bz, ra;
+    const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);
+    uint32_t npts = 0, nbuckets = 0;
+    ss_ring_walk(V, S, bx, by, bz, ra, npts, nbuckets, [&](double px, double py, double pz, uint32_t id) {
+        double d2, s;
+        seg_point_d2(S, px, py, pz, d2, s);
+        if (d2 <= r2) {
+            const uint32_t pos = atomicAdd(&s_cursor, 1u);
+            if (pos < len) {                                // every list store is bounded by the row's own length
+                out_idx[off0 + pos] = id + index_base;
+                if (out_d2) out_d2[off0 + pos] = d2;
+            }
+        }
+    });
+    if (work) ring_add_work(work, npts, nbuckets, s_w);
+}
+
+// ---- the cell-index form --------------------------------------------------------------------------------------------------------
+// One block per segment over the cell index (GridDesc, the cell-sorted records and cell_start).
+//
+// The box.  Per axis the cells of [min(a, b) - reach - pad, max(a, b) + reach + pad], the ends narrowed as the contract narrows them,
+// the reach narrowed upwards, pad = h / 100 + 2^-22 (|v| + |reach|) in fp32 -- grid_ball_box's rule, with its NaN rule (an upper
+// edge that comes out NaN opens the box to that side; a NaN lower edge falls to cell 0 in cell_coord) -- clamped by cell_coord.
+// A candidate row can only be filed inside this box: it lies within reach (1 + 2^-50) of a point of the segment, so per axis inside
+// [min - reach, max + reach] up to that rounding and the 2^-24 (|v| + pad) of the fp32 edge sums, which the pad covers with h / 100
+// to spare, and the fp32 cell assignment errs by less than 4e-4 cells on grids of at most 1024 cells per axis (it is also monotone
+// in the coordinate, and the edges go through the same cell_coord).
+//
+// The per-cell skip: seg_cell_skipped's predicate and argument.  The centre of cell (cx, cy, cz) is taken from the fp64 face
+// positions, o + (c + 0.5) h per axis, and the cell is skipped when dist^2(segment, centre) > (reach + h)^2, by seg_point_d2.
+// Why that is conservative: the fp32 assignment floor((v - o) * inv_h) errs by 2^-24 |v - o| in the difference and by 2^-23 in the
+// product and inv_h, below 2e-4 cells at 1024 cells per axis, so a row filed in the cell lies within (0.5 + 4e-4) h of the centre
+// per axis and within sqrt(3) * 0.5004 h < 0.8668 h of it; the distance to a segment is 1-Lipschitz, so every row of a skipped cell is
+// farther than reach + h - 0.8668 h = reach + 0.1332 h from the segment.  Under the magnitude guard below (|o| + g h, the ends'
+// offsets from o and the reach all under 2^30 h) the roundings of the centre (2^-53 (|o| + g h) < 2e-7 h), of dc2, of (reach + h)^2
+// and of the row's own d2 (a few ulp of distances below 2^33 h: under 1e-5 h) stay four orders of magnitude below that slack, so
+// such a row fails d2 <= reach^2 and skipping its cell loses no candidate.  Outside the guard nothing is skipped.  A cell on the
+// grid's border (c == 0 or c == g - 1 on any axis) stands for everything the clamp sends there -- pct_cloud_build_grid: the last
+// cell may hold everything from there on -- and is never skipped; (reach + h)^2 = +inf never skips.  Exactness never rests on the
+// skip: every record that is read is judged by the fp64 test.
+//
+// Lanes.  Each trip the block's 256 threads take 256 consecutive box positions (x fastest, so a group's eight cells are neighbours
+// in cell_start): every lane judges ONE cell and fetches its run bounds, then the group of kCoop lanes scans its eight runs in turn,
+// eight records at a time.  A run is one cell: neighbouring cells of an x-row are not joined (the records read are the same either
+// way, and a skipped cell in between would have to be read).  The count and the fill are this walk twice, so the fill meets exactly
+// the rows the count reserved room for.
+struct SsGridBox {
+    int x0, y0, z0, nx, ny, nz, total;
+    bool skip;               // the per-cell skip applies
+    double skip2;            // (reach + h)^2
+};
+
+constexpr double kSsGuardCells = 1073741824.0;      // 2^30: the magnitudes the skip's rounding argument covers, in cells
+
+__device__ __forceinline__ void ss_grid_axis(float a, float b, float rf, float h100, float o, float inv_h, int g, int &c0, int &n)
+{
+    const float lo = fminf(a, b), hi = fmaxf(a, b);
+    const float pad0 = rf + h100;
+    const float e0 = lo - (pad0 + 0x1p-22f * (fabsf(lo) + rf)), e1 = hi + (pad0 + 0x1p-22f * (fabsf(hi) + rf));
+    c0 = cell_coord(e0, o, inv_h, g);
+    const int c1 = e1 == e1 ? cell_coord(e1, o, inv_h, g) : g - 1;
+    n = max(c1 - c0 + 1, 1);
+}
+
+// S: the segment (ends already narrowed and widened: the casts back are exact); ra >= 0: its reach
+__device__ __forceinline__ SsGridBox ss_grid_box(const GridDesc &G, const SegGeom &S, double bx, double by, double bz, double ra)
+{
+    SsGridBox B;
+    float rf = (float)ra;
+    if ((double)rf < ra) rf = __uint_as_float(__float_as_uint(rf) + 1u);           // the next float up (rf >= 0, finite): never below the reach
+    const float h100 = 0.01f * (1.0f / G.inv_h);
+    ss_grid_axis((float)S.ax, (float)bx, rf, h100, G.ox, G.inv_h, G.gx, B.x0, B.nx);
+    ss_grid_axis((float)S.ay, (float)by, rf, h100, G.oy, G.inv_h, G.gy, B.y0, B.ny);
+    ss_grid_axis((float)S.az, (float)bz, rf, h100, G.oz, G.inv_h, G.gz, B.z0, B.nz);
+    B.total = B.nx * B.ny * B.nz;                           // at most 2^30 cells
+    const double rh = ra + G.hd, lim = kSsGuardCells * G.hd;
+    B.skip2 = rh * rh;
+    const auto small = [&](double o, int g, double a, double b) {
+        return fabs(o) + (double)g * G.hd < lim && fabs(a - o) < lim && fabs(b - o) < lim;
+    };
+    B.skip = ra < lim && small(G.oxd, G.gx, S.ax, bx) && small(G.oyd, G.gy, S.ay, by) && small(G.ozd, G.gz, S.az, bz);
+    return B;
+}
+
+__device__ __forceinline__ bool ss_grid_cell_skipped(const GridDesc &G, const SegGeom &S, const SsGridBox &B, int cx, int cy, int cz)
+{
+    if (!B.skip) return false;
+    if (cx == 0 || cx == G.gx - 1 || cy == 0 || cy == G.gy - 1 || cz == 0 || cz == G.gz - 1) return false;
+    double dc2, sc;
+    seg_point_d2(S, G.oxd + ((double)cx + 0.5) * G.hd, G.oyd + ((double)cy + 0.5) * G.hd, G.ozd + ((double)cz + 0.5) * G.hd, dc2, sc);
+    return dc2 > B.skip2;
+}
+
+// every record of the box's surviving cells, once: offer(px, py, pz, id).  npts: records read; ncells: cells opened.
+template <typename F>
+__device__ __forceinline__ void ss_grid_walk(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
+                                             const SegGeom &S, const SsGridBox &B, uint32_t &npts, uint32_t &ncells, F offer)
+{
+    const uint32_t sub = threadIdx.x & (kCoop - 1);
+    const int nxy = B.nx * B.ny;
+    for (int base = 0; base < B.total; base += 256) {       // block-uniform trip count
+        const int k = base + (int)threadIdx.x;
+        uint32_t rs = 0, re = 0;
+        if (k < B.total) {
+            const int jz = k / nxy, rem = k - jz * nxy, jy = rem / B.nx, jx = rem - jy * B.nx;
+            const int cx = B.x0 + jx, cy = B.y0 + jy, cz = B.z0 + jz;
+            if (!ss_grid_cell_skipped(G, S, B, cx, cy, cz)) {
+                const uint32_t cell = cell_lin(G, cx, cy, cz);
+                rs = cell_start[cell]; re = cell_start[cell + 1];
+                ncells++;
+            }
+        }
+        if (!__builtin_amdgcn_ballot_w64(re > rs)) continue;          // wave-uniform: none of the wave's 64 cells holds a record
+#pragma unroll
+        for (int i = 0; i < kCoop; i++) {
+            const uint32_t ps = (uint32_t)__shfl((int)rs, i, kCoop), pe = (uint32_t)__shfl((int)re, i, kCoop);
+            for (uint32_t p = ps + sub; p < pe; p += kCoop) {
+                const float4 P = pts[p];
+                npts++;
+                offer((double)P.x, (double)P.y, (double)P.z, __float_as_uint(P.w));
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ss_grid_count_kernel(GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
+                                                            const double *__restrict__ seg, const double *__restrict__ reach,
+                                                            uint32_t *__restrict__ count, WorkCounters *__restrict__ work)
+{
+    __shared__ uint32_t s_c[4];
+    __shared__ unsigned long long s_w[8];
+    const size_t slot = blockIdx.x;
+    SegGeom S;
+    double bx, by, bz, ra;
+    const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);
+    uint32_t n = 0, npts = 0, ncells = 0;
+    if (r2 >= 0.0) {                                        // block-uniform
+        const SsGridBox B = ss_grid_box(G, S, bx, by, bz, ra);
+        ss_grid_walk(G, pts, cell_start, S, B, npts, ncells, [&](double px, double py, double pz, uint32_t) {
+            double d2, s;
+            seg_point_d2(S, px, py, pz, d2, s);
+            n += d2 <= r2 ? 1u : 0u;
+        });
+    }
+    ss_block_count(n, s_c, count, slot);
+    if (work) ring_add_work(work, npts, ncells, s_w);
+}
+
+__global__ __launch_bounds__(256) void ss_grid_fill_kernel(GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
+                                                           const double *__restrict__ seg, const double *__restrict__ reach, uint32_t Q,
+                                                           uint32_t index_base, const long long *__restrict__ offsets, long long cap,
+                                                           uint32_t *__restrict__ out_idx, double *__restrict__ out_d2,
+                                                           WorkCounters *__restrict__ work)
+{
+    __shared__ uint32_t s_cursor;
+    __shared__ unsigned long long s_w[8];
+    if (offsets[Q] > cap) return;
+    const size_t slot = blockIdx.x;
+    const long long off0 = offsets[slot];
+    const uint32_t len = (uint32_t)(offsets[slot + 1] - off0);
+    if (len == 0) return;                                   // block-uniform: an empty row is not walked at all
+    if (threadIdx.x == 0) s_cursor = 0;
+    __syncthreads();
+    SegGeom S;
+    double bx, by, bz, ra;
+    const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);
+    uint32_t npts = 0, ncells = 0;
+    const SsGridBox B = ss_grid_box(G, S, bx, by, bz, ra);          // len > 0: the reach is valid
+    ss_grid_walk(G, pts, cell_start, S, B, npts, ncells, [&](double px, double py, double pz, uint32_t id) {
+        double d2, s;
+        seg_point_d2(S, px, py, pz, d2, s);
+        if (d2 <= r2) {
+            const uint32_t pos = atomicAdd(&s_cursor, 1u);
+            if (pos < len) {                                // every list store is bounded by the row's own length
+                out_idx[off0 + pos] = id + index_base;
+                if (out_d2) out_d2[off0 + pos] = d2;
+            }
+        }
+    });
+    if (work) ring_add_work(work, npts, ncells, s_w);
+}
+
+// ---- s, after the sort ----------------------------------------------------------------------------------------------------------
+// out_s[e] = the closest-point parameter of entry e's row on its segment: seg_point_d2 on the segment of the entry's row and the
+// coordinates the reported index names (x / y / z by position: the ring slot on a rolling map).  Blocks take the rows in turn.
+__global__ __launch_bounds__(256) void ss_param_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                                                       uint32_t n, const double *__restrict__ seg, uint32_t Q, uint32_t index_base,
+                                                       const long long *__restrict__ offsets, long long cap, const uint32_t *__restrict__ idx,
+                                                       double *__restrict__ out_s)
+{
+    if (offsets[Q] > cap) return;
+    for (uint32_t row = blockIdx.x; row < Q; row += gridDim.x) {
+        const long long off0 = offsets[row], off1 = offsets[row + 1];
+        if (off1 == off0) continue;
+        SegGeom S;
+        double bx, by, bz;
+        (void)seg_load(seg, row, S, bx, by, bz);
+        for (long long e = off0 + threadIdx.x; e < off1; e += 256) {
+            const uint32_t i = idx[e] - index_base;
+            double d2, s = 0.0;
+            if (i < n) seg_point_d2(S, (double)x[i], (double)y[i], (double)z[i], d2, s);
+            out_s[e] = s;
+        }
+    }
+}
+
+}  // namespace pct

@@ -228,6 +228,11 @@ def lib():
         L.pct_segment_inflate_batch.argtypes = [vp, C.POINTER(InflateParams), f64p, i64, f64p, u32p, f64p]
         L.pct_segment_sweep_batch.argtypes = [vp, i32, f64p, f64p, i64, u32p, f64p]
         L.pct_segment_sweep_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp, vp]
+        L.pct_segment_count_batch.argtypes = [vp, i32, f64p, f64p, i64, u32p]
+        L.pct_segment_count_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp]
+        L.pct_segment_search_batch.argtypes = [vp, i32, f64p, f64p, i64, i32, vp, C.POINTER(i64)]
+        L.pct_segment_search_read.argtypes = [vp, i64, i64, u32p, f64p, f64p]
+        L.pct_segment_search_batch_dev.argtypes = [vp, i32, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp]
         L.pct_bezier_check.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.c_double, C.c_double,
                                        C.POINTER(i64), C.POINTER(i64), i64, f64p, f64p, f64p, u32p]
         L.pct_nn_batch_dev.argtypes = [vp, i32, vp, i64, vp, vp, vp]
@@ -744,6 +749,41 @@ class Cloud:
         _chk(lib().pct_segment_sweep_batch(self._h, algo, _ptr(seg), _ptr(r), len(seg), _ptr(idx), _ptr(t)))
         return idx, t
 
+    def segment_count(self, segments, reach, algo: int = ALGO_AUTO):
+        """how many points lie within reach of every line segment (pct_segment_count_batch): segments [Q, 6] (a then b) or [Q, 2, 3],
+        reach a scalar or [Q]; uint32 [Q]"""
+        seg = np.ascontiguousarray(segments, np.float64).reshape(-1, 6)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64), (len(seg),)))
+        cnt = np.empty(len(seg), np.uint32)
+        _chk(lib().pct_segment_count_batch(self._h, algo, _ptr(seg), _ptr(r), len(seg), _ptr(cnt)))
+        return cnt
+
+    def segment_search(self, segments, reach, order: int = ORDER_DISTANCE, algo: int = ALGO_AUTO):
+        """which points lie within reach of every line segment (pct_segment_search_batch + pct_segment_search_read): segments [Q, 6]
+        (a then b) or [Q, 2, 3], reach a scalar or [Q]; (offsets int64 [Q + 1], idx uint32 [total], d2 float64 [total], s float64
+        [total]); row i = entries offsets[i] .. offsets[i + 1], nearest first with ties in ascending index (ORDER_DISTANCE) or in
+        ascending index (ORDER_INDEX); s is the parameter of the closest point on the segment (0 at a, 1 at b)"""
+        seg = np.ascontiguousarray(segments, np.float64).reshape(-1, 6)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64), (len(seg),)))
+        offsets = np.zeros(len(seg) + 1, np.int64)
+        total = C.c_int64()
+        _chk(lib().pct_segment_search_batch(self._h, algo, _ptr(seg), _ptr(r), len(seg), int(order), _ptr(offsets), C.byref(total)))
+        idx = np.empty(total.value, np.uint32)
+        d2 = np.empty(total.value, np.float64)
+        s = np.empty(total.value, np.float64)
+        _chk(lib().pct_segment_search_read(self._h, 0, total.value, _ptr(idx), _ptr(d2), _ptr(s)))
+        return offsets, idx, d2, s
+
+    def segment_search_read(self, first: int, n: int, want_idx: bool = True, want_d2: bool = True, want_s: bool = True):
+        """entries [first, first + n) of the last segment_search on this cloud (pct_segment_search_read): (idx, d2, s), None where not
+        wanted"""
+        idx = np.empty(max(int(n), 0), np.uint32) if want_idx else None
+        d2 = np.empty(max(int(n), 0), np.float64) if want_d2 else None
+        s = np.empty(max(int(n), 0), np.float64) if want_s else None
+        _chk(lib().pct_segment_search_read(self._h, int(first), int(n), None if idx is None else _ptr(idx), None if d2 is None else _ptr(d2),
+                                           None if s is None else _ptr(s)))
+        return idx, d2, s
+
     def bezier_check(self, params: InflateParams, polycoef, seg_time, orders, t_start, stop_time, dt=0.02, cap=4096):
         coef = np.ascontiguousarray(polycoef, np.float64)
         st = np.ascontiguousarray(seg_time, np.float64)
@@ -821,6 +861,17 @@ class Cloud:
     def segment_sweep_device(self, seg_ptr: int, radius_ptr: int, Q: int, idx_ptr: int, t_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         """pct_segment_sweep_batch_dev: seg Q x 6 and radius Q doubles on the device; t_ptr may be 0; reserve_queries(Q) first"""
         _chk(lib().pct_segment_sweep_batch_dev(self._h, algo, seg_ptr, radius_ptr, int(Q), idx_ptr, t_ptr or None, stream))
+
+    def segment_count_device(self, seg_ptr: int, reach_ptr: int, Q: int, cnt_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
+        """pct_segment_count_batch_dev: seg Q x 6 and reach Q doubles on the device, cnt Q uint32; reserve_queries(Q) first"""
+        _chk(lib().pct_segment_count_batch_dev(self._h, algo, seg_ptr, reach_ptr, int(Q), cnt_ptr, stream))
+
+    def segment_search_device(self, seg_ptr: int, reach_ptr: int, Q: int, order: int, offsets_ptr: int, cap: int, idx_ptr: int, d2_ptr: int,
+                              s_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
+        """pct_segment_search_batch_dev: offsets int64 [Q + 1] always written, idx / d2 / s (d2_ptr and s_ptr may be 0) only when
+        offsets[Q] <= cap; reserve_queries(Q) first"""
+        _chk(lib().pct_segment_search_batch_dev(self._h, algo, seg_ptr, reach_ptr, int(Q), int(order), offsets_ptr, int(cap), idx_ptr or None,
+                                                d2_ptr or None, s_ptr or None, stream))
 
     def inflate_device(self, params: InflateParams, pts_ptr: int, Q: int, radius_ptr: int, idx_ptr: int = 0, d2_ptr: int = 0, stream: int = 0):
         _chk(lib().pct_inflate_batch_dev(self._h, C.byref(params), pts_ptr, int(Q), radius_ptr, idx_ptr or None, d2_ptr or None, stream))
