@@ -193,6 +193,17 @@ struct DepthStage {
 
 struct ReplanCtx;
 
+// The cloud-owned lists of a host-form list search's last result: idx, d2 and (capsule search) s, grow-only, valid until the next
+// search that writes them or until the cloud or its index changes.  `what` names the search in the messages.
+struct ListStore {
+    const char *what;
+    DevBuf<uint32_t> idx;
+    DevBuf<double> d2, s;
+    size_t cap = 0;
+    int64_t total = 0;
+    bool valid = false;
+};
+
 struct pct_cloud {
     int64_t cap = 0, cap4 = 0, count = 0, ring_next = 0;
     int64_t index_base = 0;
@@ -269,23 +280,15 @@ struct pct_cloud {
     DevBuf<double> d_knn_d2, d_knn_pd2;
     size_t knn_out_cap = 0, knn_part_cap = 0;
     // radius-search batches (rsearch.hpp): scan / cursor / queue workspaces sized with the query workspaces, the host form's offsets
-    // and the lists of its last result (12 B per entry, grow-only), valid until the cloud or its index changes
+    // and the lists of its last result (12 B per entry: no s)
     DevBuf<long long> rs_off;
     DevBuf<uint64_t> rs_tiles;
     DevBuf<uint32_t> rs_cursor, rs_queue;
     int64_t rs_qcap = 0;
-    DevBuf<uint32_t> rs_idx;
-    DevBuf<double> rs_d2;
-    size_t rs_cap = 0;
-    int64_t rs_total = 0;
-    bool rs_valid = false;
-    // capsule search (segment_search.hpp): the lists of the host form's last result in buffers of their own (20 B per entry, grow-only)
-    // -- pct_radius_search_read promises the last RADIUS search -- valid until the cloud or its index changes
-    DevBuf<uint32_t> ss_idx;
-    DevBuf<double> ss_d2, ss_s;
-    size_t ss_cap = 0;
-    int64_t ss_total = 0;
-    bool ss_valid = false;
+    ListStore rs{ "radius-search" };
+    // capsule search (segment_search.hpp): the lists of the host form's last result in buffers of their own (20 B per entry)
+    // -- pct_radius_search_read promises the last RADIUS search
+    ListStore ss{ "capsule-search" };
     // order-preserving crop (lidar): tile counts and the compacted {index, d2, x, y, z} of the last crop
     DevBuf<uint32_t> crop_tile, crop_idx;
     DevBuf<double> crop_d2;
@@ -606,8 +609,8 @@ void drop_grid(pct_cloud *c)
 {
     if (c->has_grid) c->generation++;
     c->has_grid = false;
-    c->rs_valid = false;                // every upload, append, build and drop comes through here: the last radius-search result ends
-    c->ss_valid = false;                // and the last capsule search's
+    c->rs.valid = false;                // every upload, append, build and drop comes through here: the last radius-search result ends
+    c->ss.valid = false;                // and the last capsule search's
     c->has_pyr = false;
 }
 
@@ -1035,7 +1038,11 @@ int nn_stream_filtered(pct_cloud *c, const float *d_qf, int64_t Q, uint32_t *d_i
 RingView ring_view(const pct_cloud *c);
 
 // ---- which path a batch takes ------------------------------------------------------------------------------------------------
-enum class Op { NN, Count, KNN, RadiusSearch };
+enum class Op {
+    NN, Count, KNN, RadiusSearch,
+    Segment,       // segment nearest / sweep (segment.hpp)
+    Capsule        // capsule count / search (segment_search.hpp)
+};
 enum class Path {
     Table,         // the rolling-map index (ring.hpp, ring_search.hpp)
     Grid,          // the cell index
@@ -1045,27 +1052,34 @@ enum class Path {
 };
 
 // The one place that turns a caller's `algo` into the path of a batch of Q queries, or into PCT_ERR_INVALID with its message
-// ("Dispatch of the batch searches").  The four searches grew their rules one by one and differ in corners nobody chose;
+// ("Dispatch of the batch searches").  The searches grew their rules one by one and differ in corners nobody chose;
 // each such corner is marked "quirk" here and pinned by tests/test_gpu_dispatch.py, so that changing one is a decision, not an accident.
 int resolve_algo(const pct_cloud *c, Op op, int algo, int64_t Q, Path *path)
 {
+    // quirk: the two segment ops name the values they take in a message of their own, and the segment op -- no grid form, one
+    // streaming form -- rejects GRID and STREAM_EXACT before it looks at the cloud (an empty one included)
+    if (op == Op::Segment && algo != PCT_ALGO_AUTO && algo != PCT_ALGO_STREAM && algo != PCT_ALGO_RING)
+        return fail(PCT_ERR_INVALID, "segment queries take PCT_ALGO_AUTO, PCT_ALGO_STREAM or PCT_ALGO_RING, not algo %d", algo);
+    if (op == Op::Capsule && algo != PCT_ALGO_AUTO && algo != PCT_ALGO_STREAM && algo != PCT_ALGO_GRID && algo != PCT_ALGO_RING)
+        return fail(PCT_ERR_INVALID, "capsule search takes PCT_ALGO_AUTO, PCT_ALGO_STREAM, PCT_ALGO_GRID or PCT_ALGO_RING, not algo %d", algo);
     // PCT_ALGO_RING names the rolling-map index: it needs a live table, except on a cloud that asked for the index and holds no point
     // yet (the table is sized from the first data: the answer is the empty cloud's)
     if (algo == PCT_ALGO_RING && !c->ring_ready && !(c->ring_on && c->count == 0))
         return fail(PCT_ERR_INVALID, "PCT_ALGO_RING without a rolling-map index (call pct_cloud_ring_index)");
     // quirk: NN, count and k-NN pad an empty cloud's outputs before they look at any other algo value (an unknown one is PCT_OK from
-    // the device forms); the radius search validates algo first
-    if (op != Op::RadiusSearch && c->count == 0) { *path = Path::Empty; return PCT_OK; }
+    // the device forms); the radius search and the capsule op validate algo first (the segment op has done so above)
+    if (op != Op::RadiusSearch && op != Op::Capsule && c->count == 0) { *path = Path::Empty; return PCT_OK; }
     // quirk: on a rolling map NN takes PCT_ALGO_GRID to mean the bucket table; the other three answer "without a grid"
     if (op == Op::NN && c->ring_ready && algo == PCT_ALGO_GRID) algo = PCT_ALGO_RING;
-    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
+    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid && op != Op::Segment ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
     switch (algo) {
     case PCT_ALGO_RING:
         *path = Path::Table;
         break;
     case PCT_ALGO_GRID:
-        // quirk: the count's message is the short one
-        if (!c->has_grid) return fail(PCT_ERR_INVALID, op == Op::Count ? "PCT_ALGO_GRID without a grid" : "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
+        // quirk: the count's and the capsule op's message is the short one
+        if (!c->has_grid)
+            return fail(PCT_ERR_INVALID, op == Op::Count || op == Op::Capsule ? "PCT_ALGO_GRID without a grid" : "PCT_ALGO_GRID without a grid (call pct_cloud_build_grid)");
         *path = Path::Grid;
         break;
     case PCT_ALGO_STREAM:
@@ -1082,7 +1096,9 @@ int resolve_algo(const pct_cloud *c, Op op, int algo, int64_t Q, Path *path)
     }
     if (op == Op::KNN && *path == Path::Stream && c->capturing)
         return fail(PCT_ERR_INVALID, "the streaming k-NN kernel is not available during graph capture");
-    if (c->count == 0) *path = Path::Empty;          // the radius search, its algo found valid
+    // the radius search and the capsule op, their algo found valid.  quirk: of the host forms that arrive here, the radius search
+    // answers an empty cloud with PCT_OK, the capsule op's -- like the segment op's above -- with PCT_ERR_EMPTY (their own line)
+    if (c->count == 0) *path = Path::Empty;
     return PCT_OK;
 }
 
@@ -1258,38 +1274,24 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
 }
 
 // ---- segment queries (segment.hpp) -------------------------------------------------------------------------------------------
-enum class SegPath { Table, Stream, Empty };
 // what a batch measures on its rows: the nearest row's (d2, s) | the first blocker's entry parameter t of a swept sphere ("Segment
 // sweeps": t travels in d2's place, d_reach holds the radii, there is no s)
 enum class SegMeasure { Nearest, Sweep };
 
-// `algo` of a segment batch: the rolling-map index or the streaming form; there is no grid form and no second streaming form
-int resolve_segment_algo(const pct_cloud *c, int algo, SegPath *path)
-{
-    if (algo != PCT_ALGO_AUTO && algo != PCT_ALGO_STREAM && algo != PCT_ALGO_RING)
-        return fail(PCT_ERR_INVALID, "segment queries take PCT_ALGO_AUTO, PCT_ALGO_STREAM or PCT_ALGO_RING, not algo %d", algo);
-    if (algo == PCT_ALGO_RING && !c->ring_ready && !(c->ring_on && c->count == 0))
-        return fail(PCT_ERR_INVALID, "PCT_ALGO_RING without a rolling-map index (call pct_cloud_ring_index)");
-    if (c->count == 0) *path = SegPath::Empty;
-    else if (algo == PCT_ALGO_RING || (algo == PCT_ALGO_AUTO && c->ring_ready)) *path = SegPath::Table;
-    else *path = SegPath::Stream;
-    return PCT_OK;
-}
-
 // nearest row to every segment of a device-resident batch (d_seg: Q x 6) -- or, for a sweep, the row that stops the sphere, its t in
 // d_d2; d_reach == nullptr: reach_all for every segment (a sweep always has its d_reach).  d_d2 / d_s may be NULL.  Q >= 1, within
-// the reserved batch size.
-int segment_run(pct_cloud *c, SegPath path, SegMeasure measure, const double *d_seg, const double *d_reach, double reach_all, int64_t Q,
+// the reserved batch size.  path: from resolve_algo(Op::Segment) -- the rolling-map index or the streaming form.
+int segment_run(pct_cloud *c, Path path, SegMeasure measure, const double *d_seg, const double *d_reach, double reach_all, int64_t Q,
                 uint32_t *d_idx, double *d_d2, double *d_s, hipStream_t s)
 {
     const bool sweep = measure == SegMeasure::Sweep;
     switch (path) {
-    case SegPath::Empty:
+    case Path::Empty:
         if (sweep) sweep_fill_none_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_seg, d_reach, d_idx, d_d2, (uint32_t)Q);
         else segment_fill_none_kernel<<<ceil_div(Q, 256), 256, 0, s>>>(d_idx, d_d2, d_s, (uint32_t)Q);
         HIPCHK(hipGetLastError());
         return PCT_OK;
-    case SegPath::Table:     // rolling-map index: a block per segment over the buckets of the capsule's box
+    case Path::Table:        // rolling-map index: a block per segment over the buckets of the capsule's box
         return launch_frame(c, s, Q, { Work::Device }, [&] {
             WorkCounters *work = c->count_work ? c->d_work : nullptr;
             if (sweep) ring_sweep_kernel<<<(int)Q, 256, 0, s>>>(ring_view(c), d_seg, d_reach, (uint32_t)c->index_base, d_idx, d_d2, work);
@@ -1339,33 +1341,63 @@ int rs_ensure_work(pct_cloud *c)
     return PCT_OK;
 }
 
-// the cloud-owned lists: room for n entries of 12 B (grow-only; a failed growth leaves none)
-int rs_ensure_lists(pct_cloud *c, size_t n)
+// room for n entries in L's d2 and, where wanted, idx and s (grow-only; a failed growth leaves none)
+int ensure_lists(pct_cloud *c, ListStore &L, size_t n, bool want_idx, bool want_s)
 {
-    if (n <= c->rs_cap) return PCT_OK;
-    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the radius-search lists during graph capture");
-    c->rs_cap = 0;
-    c->rs_idx.release(); c->rs_d2.release();
-    PCTCHK(c->rs_idx.reset(n));
-    PCTCHK(c->rs_d2.reset(n));
-    c->rs_cap = n;
+    if (n == 0 || (n <= L.cap && (!want_idx || L.idx) && (!want_s || L.s))) return PCT_OK;
+    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the %s lists during graph capture", L.what);
+    n = std::max(n, L.cap);
+    L.cap = 0;
+    L.idx.release(); L.d2.release(); L.s.release();
+    PCTCHK(L.d2.reset(n));
+    if (want_idx) PCTCHK(L.idx.reset(n));
+    if (want_s) PCTCHK(L.s.reset(n));
+    L.cap = n;
     return PCT_OK;
 }
 
-// steps 1 and 2: row lengths (the radius-count batch, into c->d_count) and their exclusive scan into d_offsets[Q + 1]; the rows the
-// sort will take are queued in c->rs_queue.  path: from resolve_algo(Op::RadiusSearch).  Q >= 1.
-int rs_count_scan(pct_cloud *c, Path path, const float *d_q, const float *d_r, int64_t Q, long long *d_offsets, hipStream_t s)
+// entries [first, first + n) of L's last result to the host; idx, d2 or s may be NULL
+int read_lists(const ListStore &L, int64_t first, int64_t n, uint32_t *idx, double *d2, double *s)
 {
-    if (Q > c->rs_qcap || !d_offsets) return fail(PCT_ERR_INTERNAL, "radius search without its workspaces");      // rs_ensure_work comes first
-    PCTCHK(count_run(c, path, d_q, d_r, Q, c->d_count, s));
+    if (!L.valid) return fail(PCT_ERR_INVALID, "no %s result to read (none yet, or the cloud changed since)", L.what);
+    if (first < 0 || n < 0 || first > L.total || n > L.total - first)
+        return fail(PCT_ERR_INVALID, "entries [%lld, %lld) lie outside [0, %lld]", (long long)first, (long long)(first + n), (long long)L.total);
+    if (n == 0) return PCT_OK;
+    if (idx) HIPCHK(hipMemcpyAsync(idx, L.idx + first, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g_stream));
+    if (d2) HIPCHK(hipMemcpyAsync(d2, L.d2 + first, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    if (s) HIPCHK(hipMemcpyAsync(s, L.s + first, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return PCT_OK;
+}
+
+// step 2: c->d_count -> exclusive offsets in d_offsets[Q + 1]; the rows longer than sort_min are queued in c->rs_queue for the sort
+// (1: a fill that places its hits in arrival order; kRsShort: the cell-pruned fill, which orders shorter rows itself)
+int list_scan(pct_cloud *c, int64_t Q, long long *d_offsets, uint32_t sort_min, hipStream_t s)
+{
+    if (Q > c->rs_qcap || !d_offsets) return fail(PCT_ERR_INTERNAL, "list search without its workspaces");      // rs_ensure_work comes first
     const int ntiles = ceil_div(Q, kRsScanTile);
     HIPCHK(hipMemsetAsync(c->rs_queue, 0, sizeof(uint32_t), s));
     rs_scan_tiles_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles);
     scan_tile_sums_kernel<uint64_t><<<1, 256, 0, s>>>(c->rs_tiles, (uint32_t)ntiles, ScanDoneNothing{});
-    rs_scan_final_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles, d_offsets, path == Path::Grid ? (uint32_t)kRsShort : 1u,
-                                                c->rs_queue);
+    rs_scan_final_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles, d_offsets, sort_min, c->rs_queue);
     HIPCHK(hipGetLastError());
     return PCT_OK;
+}
+
+// the tiles of a streaming form with `tile` rows to a block, grid.y within every HIP limit: f(first tile, tiles)
+template <typename F>
+void for_tile_slices(int64_t Q, int tile, F f)
+{
+    const int64_t tiles = (Q + tile - 1) / tile;
+    for (int64_t t0 = 0; t0 < tiles; t0 += 32768) f((uint32_t)t0, (int)std::min<int64_t>(32768, tiles - t0));
+}
+
+// steps 1 and 2 of the radius search: row lengths (the radius-count batch, into c->d_count), then the scan, behind the count's frame.
+// path: from resolve_algo(Op::RadiusSearch).  Q >= 1.
+int rs_count_scan(pct_cloud *c, Path path, const float *d_q, const float *d_r, int64_t Q, long long *d_offsets, hipStream_t s)
+{
+    PCTCHK(count_run(c, path, d_q, d_r, Q, c->d_count, s));
+    return list_scan(c, Q, d_offsets, path == Path::Grid ? (uint32_t)kRsShort : 1u, s);
 }
 
 // step 3: the lists, written only when d_offsets[Q] <= cap (tested on the device), then the queued rows put into final order
@@ -1390,12 +1422,10 @@ int rs_fill_sort(pct_cloud *c, Path path, const float *d_q, const float *d_r, in
     } else {
         HIPCHK(hipMemsetAsync(c->rs_cursor, 0, sizeof(uint32_t) * Q, s));
         const int nparts = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->count + 4095) / 4096));
-        const int64_t tiles = (Q + kRsTile - 1) / kRsTile;
-        for (int64_t t0 = 0; t0 < tiles; t0 += 32768) {      // grid.y stays within every HIP limit
-            const int nt = (int)std::min<int64_t>(32768, tiles - t0);
-            rs_fill_stream_kernel<<<dim3(nparts, nt), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q, d_r, (uint32_t)Q, (uint32_t)t0,
+        for_tile_slices(Q, kRsTile, [&](uint32_t t0, int nt) {
+            rs_fill_stream_kernel<<<dim3(nparts, nt), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_q, d_r, (uint32_t)Q, t0,
                                                                    (uint32_t)c->index_base, d_offsets, (long long)cap, c->rs_cursor, d_idx, d_d2);
-        }
+        });
     }
     with_bool(by_dist, [&](auto bd) {
         rs_sort_rows_kernel<decltype(bd)::value><<<(int)std::min<int64_t>(Q, 8192), 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
@@ -1405,62 +1435,14 @@ int rs_fill_sort(pct_cloud *c, Path path, const float *d_q, const float *d_r, in
 }
 
 // ---- capsule search (segment_search.hpp): the radius search's frame over segments ----------------------------------------------
-// `algo` of a capsule search: the rolling-map index, the cell index or the streaming form; AUTO takes the first of those the cloud has
-int resolve_capsule_algo(const pct_cloud *c, int algo, Path *path)
-{
-    if (algo == PCT_ALGO_RING && !c->ring_ready && !(c->ring_on && c->count == 0))
-        return fail(PCT_ERR_INVALID, "PCT_ALGO_RING without a rolling-map index (call pct_cloud_ring_index)");
-    if (algo == PCT_ALGO_AUTO) algo = c->ring_ready ? PCT_ALGO_RING : c->has_grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM;
-    switch (algo) {
-    case PCT_ALGO_RING:
-        *path = Path::Table;
-        break;
-    case PCT_ALGO_GRID:
-        if (!c->has_grid) return fail(PCT_ERR_INVALID, "PCT_ALGO_GRID without a grid");       // a rolling map has none
-        *path = Path::Grid;
-        break;
-    case PCT_ALGO_STREAM:
-        *path = Path::Stream;
-        break;
-    default:
-        return fail(PCT_ERR_INVALID, "capsule search takes PCT_ALGO_AUTO, PCT_ALGO_STREAM, PCT_ALGO_GRID or PCT_ALGO_RING, not algo %d", algo);
-    }
-    if (c->count == 0) *path = Path::Empty;
-    return PCT_OK;
-}
-
-// the host form's lists: room for n entries (grow-only; a failed growth leaves none)
-int ss_ensure_lists(pct_cloud *c, size_t n, bool want_idx_s)
-{
-    if (n == 0 || (n <= c->ss_cap && (!want_idx_s || c->ss_idx))) return PCT_OK;
-    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the capsule-search lists during graph capture");
-    n = std::max(n, c->ss_cap);
-    c->ss_cap = 0;
-    c->ss_idx.release(); c->ss_d2.release(); c->ss_s.release();
-    PCTCHK(c->ss_d2.reset(n));
-    if (want_idx_s) {
-        PCTCHK(c->ss_idx.reset(n));
-        PCTCHK(c->ss_s.reset(n));
-    }
-    c->ss_cap = n;
-    return PCT_OK;
-}
-
-// the tiles of the streaming form, grid.y within every HIP limit: f(first tile, tiles)
-template <typename F>
-void ss_for_tile_slices(int64_t Q, F f)
-{
-    const int64_t tiles = (Q + kSegTile - 1) / kSegTile;
-    for (int64_t t0 = 0; t0 < tiles; t0 += 32768) f((uint32_t)t0, (int)std::min<int64_t>(32768, tiles - t0));
-}
-
 int ss_stream_parts(const pct_cloud *c)
 {
     return (int)std::min<int64_t>(kSegParts, std::max<int64_t>(1, (c->count + 255) / 256));
 }
 
 // row lengths of a device-resident batch (d_seg: Q x 6, d_reach: Q) into d_count along `path`, then `after` inside the same frame
-// (the search's scan and, in the device form, its fill).  Q >= 1, within the reserved batch size.
+// (the search's scan -- list_scan with sort_min = 1: all three fills place their hits in arrival order -- and, in the device form,
+// its fill).  path: from resolve_algo(Op::Capsule).  Q >= 1, within the reserved batch size.
 template <typename E>
 int ss_count_run(pct_cloud *c, Path path, const double *d_seg, const double *d_reach, int64_t Q, uint32_t *d_count, hipStream_t s, E after)
 {
@@ -1481,24 +1463,10 @@ int ss_count_run(pct_cloud *c, Path path, const double *d_seg, const double *d_r
     const int parts = ss_stream_parts(c);
     return launch_frame(c, s, Q, { Work::EveryPoint }, no_step,
         [&] {
-            ss_for_tile_slices(Q, [&](uint32_t t0, int nt) {
+            for_tile_slices(Q, kSegTile, [&](uint32_t t0, int nt) {
                 ss_stream_count_kernel<<<dim3(parts, nt), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg, d_reach, (uint32_t)Q, t0, d_count);
             });
         }, after);
-}
-
-// c->d_count -> exclusive offsets in d_offsets[Q + 1]; every row of two or more entries is queued for the sort (all three fills place
-// their hits in arrival order).  The radius search's scan kernels, as they are.
-int ss_scan(pct_cloud *c, int64_t Q, long long *d_offsets, hipStream_t s)
-{
-    if (Q > c->rs_qcap || !d_offsets) return fail(PCT_ERR_INTERNAL, "capsule search without its workspaces");      // rs_ensure_work comes first
-    const int ntiles = ceil_div(Q, kRsScanTile);
-    HIPCHK(hipMemsetAsync(c->rs_queue, 0, sizeof(uint32_t), s));
-    rs_scan_tiles_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles);
-    scan_tile_sums_kernel<uint64_t><<<1, 256, 0, s>>>(c->rs_tiles, (uint32_t)ntiles, ScanDoneNothing{});
-    rs_scan_final_kernel<<<ntiles, 256, 0, s>>>(c->d_count, (uint32_t)Q, c->rs_tiles, d_offsets, 1u, c->rs_queue);
-    HIPCHK(hipGetLastError());
-    return PCT_OK;
 }
 
 // the lists, written only when d_offsets[Q] <= cap (tested on the device): the count's walk once more (its work is added to the
@@ -1517,7 +1485,7 @@ int ss_fill_sort(pct_cloud *c, Path path, const double *d_seg, const double *d_r
     } else {
         HIPCHK(hipMemsetAsync(c->rs_cursor, 0, sizeof(uint32_t) * Q, s));
         const int parts = ss_stream_parts(c);
-        ss_for_tile_slices(Q, [&](uint32_t t0, int nt) {
+        for_tile_slices(Q, kSegTile, [&](uint32_t t0, int nt) {
             ss_stream_fill_kernel<<<dim3(parts, nt), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg, d_reach, (uint32_t)Q, t0, base, d_offsets,
                                                                   (long long)cap, c->rs_cursor, d_idx, d_d2);
         });
@@ -1955,6 +1923,117 @@ int append_unindexed(pct_cloud *c, const void *pts, int64_t n, int64_t stride_by
     return after_replace(c);
 }
 
+// ---- the list searches: radius search (rsearch.hpp) and capsule search (segment_search.hpp) --------------------------------------
+// The host form behind its argument checks and resolve_algo: stage the inputs, count and scan -- asked twice after an overrun, before
+// the lists are sized: count and fill must see the same table -- the one host read (the total sizes the lists), fill and sort, wait,
+// publish in L.  name: the search, for the capacity message.  What differs between the two searches stays with the callers.
+template <typename Stage, typename CountScan, typename FillSort>
+int list_search_host(pct_cloud *c, ListStore &L, const char *name, bool want_s, int64_t Q, int64_t *offsets, int64_t *total, Stage stage,
+                     CountScan count_scan, FillSort fill_sort)
+{
+    L.valid = false;
+    L.total = 0;
+    offsets[0] = 0;
+    *total = 0;
+    if (Q == 0) { L.valid = true; return PCT_OK; }
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    PCTCHK(rs_ensure_work(c));                               // before c->rs_off is handed on
+    PCTCHK(run_step(stage));
+    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {
+        PCTCHK(run_step(count_scan));
+        HIPCHK(hipMemcpyAsync(offsets, c->rs_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return PCT_OK;
+    }));
+    *total = offsets[Q];
+    if (*total > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "%s lists %lld entries, more than 2^32 - 1", name, (long long)*total);
+    PCTCHK(ensure_lists(c, L, (size_t)*total, true, want_s));
+    PCTCHK(run_step(fill_sort));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    L.total = *total;
+    L.valid = true;
+    return PCT_OK;
+}
+
+// The device forms' prelude behind resolve_algo.  Q == 0: the empty CSR, and the caller returns.  Otherwise the batch must fit the
+// reserved size; under PCT_ORDER_DISTANCE without a d_d2 the sort key needs a home -- L's d2, grown to cap entries (want_idx: idx
+// with it), which ends the host form's last result -- and the scan's workspaces and the order behind the cloud's mutations follow.
+int list_search_dev_prelude(pct_cloud *c, ListStore &L, bool want_idx, int64_t Q, int order, int64_t *d_offsets, int64_t cap, double **d_d2,
+                            hipStream_t s)
+{
+    if (Q == 0) {
+        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
+        return PCT_OK;
+    }
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    if (order == PCT_ORDER_DISTANCE && !*d_d2 && cap > 0) {
+        L.valid = false;
+        PCTCHK(ensure_lists(c, L, (size_t)cap, want_idx, false));
+        *d_d2 = L.d2;
+    }
+    PCTCHK(rs_ensure_work(c));
+    return order_after_mutations(c, s);
+}
+
+// ---- the per-segment host forms ---------------------------------------------------------------------------------------------
+// where a per-segment result goes: Q elements of `elem` bytes from `dev` to `host` (NULL: not asked for)
+struct SegOut { void *host; const void *dev; size_t elem; };
+
+// segments and reaches (either may be NULL: not staged) into c->d_seg / c->d_r2
+int stage_segments(pct_cloud *c, const double *seg, const double *reach, int64_t Q)
+{
+    if (seg) HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
+    if (reach) HIPCHK(hipMemcpyAsync(c->d_r2, reach, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
+    return PCT_OK;
+}
+
+// The host form of a per-segment answer behind its argument checks, resolve_algo and pct_cloud_reserve_queries (the outputs name the
+// workspaces it sizes); Q >= 1.  `run` queues the batch on g_stream
+// from the staged inputs and is asked once more when the table lost points (overflow-queue overrun: refiled); the outputs are copied
+// back and waited for once.  empty_msg: the entry's PCT_ERR_EMPTY message when the cloud holds no point, NULL when it answers PCT_OK.
+template <typename Run>
+int segment_host_form(pct_cloud *c, const double *seg, const double *reach, int64_t Q, std::initializer_list<SegOut> outs, const char *empty_msg,
+                      Run run)
+{
+    PCTCHK(stage_segments(c, seg, reach, Q));
+    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {
+        PCTCHK(run_step(run));
+        for (const SegOut &o : outs)
+            if (o.host) HIPCHK(hipMemcpyAsync(o.host, o.dev, o.elem * (size_t)Q, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+        return PCT_OK;
+    }));
+    if (empty_msg) return fail(PCT_ERR_EMPTY, "%s", empty_msg);
+    return PCT_OK;
+}
+
+// the device form of either measure behind its argument check; d_d2 receives t for a sweep, which has no s
+int segment_batch_dev(pct_cloud *c, int algo, SegMeasure measure, const double *d_seg, const double *d_reach, int64_t Q, uint32_t *d_idx,
+                      double *d_d2, double *d_s, hipStream_t s)
+{
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Segment, algo, Q, &path));
+    if (Q == 0) return PCT_OK;
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(order_after_mutations(c, s));
+    return segment_run(c, path, measure, d_seg, d_reach, 0.0, Q, d_idx, d_d2, d_s, s);
+}
+
+// the host form of either measure behind its argument check; empty_msg: the entry's own PCT_ERR_EMPTY message
+int segment_batch_host(pct_cloud *c, int algo, SegMeasure measure, const double *seg, const double *reach, int64_t Q, uint32_t *idx, double *d2,
+                       double *s, const char *empty_msg)
+{
+    PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Segment, algo, Q, &path));
+    if (Q == 0) return PCT_OK;
+    PCTCHK(pct_cloud_reserve_queries(c, Q));
+    double *d_s = measure == SegMeasure::Sweep ? nullptr : (double *)c->d_radius;
+    return segment_host_form(c, seg, reach, Q, { { idx, c->d_idx, sizeof(uint32_t) }, { d2, c->d_d2, sizeof(double) }, { s, d_s, sizeof(double) } },
+                             path == Path::Empty ? empty_msg : nullptr,
+                             [&] { return segment_run(c, path, measure, c->d_seg, c->d_r2, 0.0, Q, c->d_idx, c->d_d2, d_s, g_stream); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -2267,18 +2346,9 @@ int pct_radius_search_batch_dev(pct_cloud *c, int algo, const float *d_q, const 
     Path path;
     PCTCHK(resolve_algo(c, Op::RadiusSearch, algo, Q, &path));
     hipStream_t s = (hipStream_t)stream;
-    c->rs_valid = false;                                     // the host form's result ends with the next search of either form
-    if (Q == 0) {
-        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
-        return PCT_OK;
-    }
-    if (order == PCT_ORDER_DISTANCE && !d_d2 && cap > 0) {   // the sort key needs a home: the cloud's own list buffer
-        PCTCHK(rs_ensure_lists(c, (size_t)cap));
-        d_d2 = c->rs_d2;
-    }
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
-    PCTCHK(rs_ensure_work(c));
-    PCTCHK(order_after_mutations(c, s));
+    c->rs.valid = false;                                     // the host form's result ends with the next search of either form
+    PCTCHK(list_search_dev_prelude(c, c->rs, true, Q, order, d_offsets, cap, &d_d2, s));      // idx grows with the borrowed d2 (kept as found)
+    if (Q == 0) return PCT_OK;
     PCTCHK(rs_count_scan(c, path, d_q, d_r, Q, reinterpret_cast<long long *>(d_offsets), s));
     return rs_fill_sort(c, path, d_q, d_r, Q, order, reinterpret_cast<long long *>(d_offsets), cap, d_idx, d_d2, s);
 }
@@ -2289,41 +2359,20 @@ int pct_radius_search_batch(pct_cloud *c, int algo, const float *q, const float 
     if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
     Path path;
     PCTCHK(resolve_algo(c, Op::RadiusSearch, algo, Q, &path));
-    c->rs_valid = false;
-    c->rs_total = 0;
-    offsets[0] = 0;
-    *total = 0;
-    if (Q == 0) { c->rs_valid = true; return PCT_OK; }
-    PCTCHK(pct_cloud_reserve_queries(c, Q));
-    PCTCHK(rs_ensure_work(c));                               // before c->rs_off is handed on
-    HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(c->d_r, r, sizeof(float) * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {          // before the lists are sized: count and fill must see the same table
-        PCTCHK(rs_count_scan(c, path, c->d_q, c->d_r, Q, c->rs_off, g_stream));
-        HIPCHK(hipMemcpyAsync(offsets, c->rs_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));              // the one host read: the total sizes the lists
-        return PCT_OK;
-    }));
-    *total = offsets[Q];
-    if (*total > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "radius search lists %lld entries, more than 2^32 - 1", (long long)*total);
-    PCTCHK(rs_ensure_lists(c, (size_t)*total));
-    PCTCHK(rs_fill_sort(c, path, c->d_q, c->d_r, Q, order, c->rs_off, *total, c->rs_idx, c->rs_d2, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    c->rs_total = *total;
-    c->rs_valid = true;
-    return PCT_OK;
+    return list_search_host(c, c->rs, "radius search", false, Q, offsets, total,
+        [&]() -> int {
+            HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
+            HIPCHK(hipMemcpyAsync(c->d_r, r, sizeof(float) * Q, hipMemcpyHostToDevice, g_stream));
+            return PCT_OK;
+        },
+        [&] { return rs_count_scan(c, path, c->d_q, c->d_r, Q, c->rs_off, g_stream); },
+        [&] { return rs_fill_sort(c, path, c->d_q, c->d_r, Q, order, c->rs_off, *total, c->rs.idx, c->rs.d2, g_stream); });      // an empty cloud: PCT_OK
 }
 
 int pct_radius_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2)
 {
-    if (!c || !c->rs_valid) return fail(PCT_ERR_INVALID, "no radius-search result to read (none yet, or the cloud changed since)");
-    if (first < 0 || n < 0 || first > c->rs_total || n > c->rs_total - first)
-        return fail(PCT_ERR_INVALID, "entries [%lld, %lld) lie outside [0, %lld]", (long long)first, (long long)(first + n), (long long)c->rs_total);
-    if (n == 0) return PCT_OK;
-    if (idx) HIPCHK(hipMemcpyAsync(idx, c->rs_idx + first, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g_stream));
-    if (d2) HIPCHK(hipMemcpyAsync(d2, c->rs_d2 + first, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return PCT_OK;
+    if (!c) return fail(PCT_ERR_INVALID, "no radius-search result to read (none yet, or the cloud changed since)");
+    return read_lists(c->rs, first, n, idx, d2, nullptr);
 }
 
 int pct_nn_batch_q64(pct_cloud *c, const double *q, int64_t Q, uint32_t *idx, double *d2)
@@ -2596,73 +2645,31 @@ int pct_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const double *p
     return PCT_OK;
 }
 
-// ---- segment queries (include/pct_engine.h, "Segment queries") ------------------------------------------------------------------
+// ---- segment queries and sweeps (include/pct_engine.h, "Segment queries", "Segment sweeps"): one dispatch, frame and staged workspaces ----
 int pct_segment_nn_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q, uint32_t *d_idx, double *d_d2,
                              double *d_s, void *stream)
 {
     if (!c || Q < 0 || (Q > 0 && (!d_seg || !d_reach || !d_idx))) return fail(PCT_ERR_INVALID, "bad segment_nn_batch_dev arguments");
-    SegPath path;
-    PCTCHK(resolve_segment_algo(c, algo, &path));
-    if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
-    PCTCHK(order_after_mutations(c, (hipStream_t)stream));
-    return segment_run(c, path, SegMeasure::Nearest, d_seg, d_reach, 0.0, Q, d_idx, d_d2, d_s, (hipStream_t)stream);
+    return segment_batch_dev(c, algo, SegMeasure::Nearest, d_seg, d_reach, Q, d_idx, d_d2, d_s, (hipStream_t)stream);
 }
 
 int pct_segment_nn_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, uint32_t *idx, double *d2, double *s)
 {
     if (!c || Q < 0 || (Q > 0 && (!seg || !reach || !idx))) return fail(PCT_ERR_INVALID, "bad segment_nn_batch arguments");
-    PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
-    SegPath path;
-    PCTCHK(resolve_segment_algo(c, algo, &path));
-    if (Q == 0) return PCT_OK;
-    PCTCHK(pct_cloud_reserve_queries(c, Q));
-    HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(c->d_r2, reach, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {          // the table lost points (overflow-queue overrun): refiled, asked once more
-        PCTCHK(segment_run(c, path, SegMeasure::Nearest, c->d_seg, c->d_r2, 0.0, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
-        HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
-        if (d2) HIPCHK(hipMemcpyAsync(d2, c->d_d2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
-        if (s) HIPCHK(hipMemcpyAsync(s, c->d_radius, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        return PCT_OK;
-    }));
-    if (path == SegPath::Empty) return fail(PCT_ERR_EMPTY, "segment query against an empty cloud");
-    return PCT_OK;
+    return segment_batch_host(c, algo, SegMeasure::Nearest, seg, reach, Q, idx, d2, s, "segment query against an empty cloud");
 }
 
-// ---- segment sweeps (include/pct_engine.h, "Segment sweeps"): the segment queries' dispatch, frame and staged workspaces ---------
 int pct_segment_sweep_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_radius, int64_t Q, uint32_t *d_idx, double *d_t,
                                 void *stream)
 {
     if (!c || Q < 0 || (Q > 0 && (!d_seg || !d_radius || !d_idx))) return fail(PCT_ERR_INVALID, "bad segment_sweep_batch_dev arguments");
-    SegPath path;
-    PCTCHK(resolve_segment_algo(c, algo, &path));
-    if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
-    PCTCHK(order_after_mutations(c, (hipStream_t)stream));
-    return segment_run(c, path, SegMeasure::Sweep, d_seg, d_radius, 0.0, Q, d_idx, d_t, nullptr, (hipStream_t)stream);
+    return segment_batch_dev(c, algo, SegMeasure::Sweep, d_seg, d_radius, Q, d_idx, d_t, nullptr, (hipStream_t)stream);
 }
 
 int pct_segment_sweep_batch(pct_cloud *c, int algo, const double *seg, const double *radius, int64_t Q, uint32_t *idx, double *t)
 {
     if (!c || Q < 0 || (Q > 0 && (!seg || !radius || !idx))) return fail(PCT_ERR_INVALID, "bad segment_sweep_batch arguments");
-    PCTCHK(ring_finish_pending(c));
-    SegPath path;
-    PCTCHK(resolve_segment_algo(c, algo, &path));
-    if (Q == 0) return PCT_OK;
-    PCTCHK(pct_cloud_reserve_queries(c, Q));
-    HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(c->d_r2, radius, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {
-        PCTCHK(segment_run(c, path, SegMeasure::Sweep, c->d_seg, c->d_r2, 0.0, Q, c->d_idx, c->d_d2, nullptr, g_stream));
-        HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
-        if (t) HIPCHK(hipMemcpyAsync(t, c->d_d2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        return PCT_OK;
-    }));
-    if (path == SegPath::Empty) return fail(PCT_ERR_EMPTY, "segment sweep against an empty cloud");
-    return PCT_OK;
+    return segment_batch_host(c, algo, SegMeasure::Sweep, seg, radius, Q, idx, t, nullptr, "segment sweep against an empty cloud");
 }
 
 // ---- capsule search (include/pct_engine.h, "Capsule search") ------------------------------------------------------------------------
@@ -2670,7 +2677,7 @@ int pct_segment_count_batch_dev(pct_cloud *c, int algo, const double *d_seg, con
 {
     if (!c || Q < 0 || (Q > 0 && (!d_seg || !d_reach || !d_count))) return fail(PCT_ERR_INVALID, "bad segment_count_batch_dev arguments");
     Path path;
-    PCTCHK(resolve_capsule_algo(c, algo, &path));
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, Q, &path));
     if (Q == 0) return PCT_OK;
     if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
     PCTCHK(order_after_mutations(c, (hipStream_t)stream));
@@ -2682,19 +2689,12 @@ int pct_segment_count_batch(pct_cloud *c, int algo, const double *seg, const dou
     if (!c || Q < 0 || (Q > 0 && (!seg || !reach || !count))) return fail(PCT_ERR_INVALID, "bad segment_count_batch arguments");
     PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
     Path path;
-    PCTCHK(resolve_capsule_algo(c, algo, &path));
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, Q, &path));
     if (Q == 0) return PCT_OK;
     PCTCHK(pct_cloud_reserve_queries(c, Q));
-    HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(c->d_r2, reach, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {
-        PCTCHK(ss_count_run(c, path, c->d_seg, c->d_r2, Q, c->d_count, g_stream, no_step));
-        HIPCHK(hipMemcpyAsync(count, c->d_count, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
-        return PCT_OK;
-    }));
-    if (path == Path::Empty) return fail(PCT_ERR_EMPTY, "capsule count against an empty cloud");
-    return PCT_OK;
+    return segment_host_form(c, seg, reach, Q, { { count, c->d_count, sizeof(uint32_t) } },
+                             path == Path::Empty ? "capsule count against an empty cloud" : nullptr,
+                             [&] { return ss_count_run(c, path, c->d_seg, c->d_r2, Q, c->d_count, g_stream, no_step); });
 }
 
 int pct_segment_search_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q, int order, int64_t *d_offsets,
@@ -2704,23 +2704,13 @@ int pct_segment_search_batch_dev(pct_cloud *c, int algo, const double *d_seg, co
         return fail(PCT_ERR_INVALID, "bad segment_search_batch_dev arguments");
     if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
     Path path;
-    PCTCHK(resolve_capsule_algo(c, algo, &path));
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, Q, &path));
     hipStream_t s = (hipStream_t)stream;
-    if (Q == 0) {
-        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
-        return PCT_OK;
-    }
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
-    if (order == PCT_ORDER_DISTANCE && !d_d2 && cap > 0) {   // the sort key needs a home: the cloud's own capsule-search list buffer
-        c->ss_valid = false;                                 // which ends the host form's last result
-        PCTCHK(ss_ensure_lists(c, (size_t)cap, false));
-        d_d2 = c->ss_d2;
-    }
-    PCTCHK(rs_ensure_work(c));
-    PCTCHK(order_after_mutations(c, s));
+    PCTCHK(list_search_dev_prelude(c, c->ss, false, Q, order, d_offsets, cap, &d_d2, s));     // the host form's result lasts unless d2 is borrowed
+    if (Q == 0) return PCT_OK;
     long long *off = reinterpret_cast<long long *>(d_offsets);
-    return ss_count_run(c, path, d_seg, d_reach, Q, c->d_count, s, [&]() -> int {
-        PCTCHK(ss_scan(c, Q, off, s));
+    return ss_count_run(c, path, d_seg, d_reach, Q, c->d_count, s, [&]() -> int {      // scan, fill and sort inside the count's frame
+        PCTCHK(list_scan(c, Q, off, 1u, s));
         return ss_fill_sort(c, path, d_seg, d_reach, Q, order, off, cap, d_idx, d_d2, d_s, s);
     });
 }
@@ -2731,44 +2721,19 @@ int pct_segment_search_batch(pct_cloud *c, int algo, const double *seg, const do
     if (order != PCT_ORDER_INDEX && order != PCT_ORDER_DISTANCE) return fail(PCT_ERR_INVALID, "unknown order %d", order);
     PCTCHK(ring_finish_pending(c));
     Path path;
-    PCTCHK(resolve_capsule_algo(c, algo, &path));
-    c->ss_valid = false;
-    c->ss_total = 0;
-    offsets[0] = 0;
-    *total = 0;
-    if (Q == 0) { c->ss_valid = true; return PCT_OK; }
-    PCTCHK(pct_cloud_reserve_queries(c, Q));
-    PCTCHK(rs_ensure_work(c));                               // before c->rs_off is handed on
-    HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(c->d_r2, reach, sizeof(double) * Q, hipMemcpyHostToDevice, g_stream));
-    PCTCHK(ask_twice_after_overrun(c, [&]() -> int {          // before the lists are sized: count and fill must see the same table
-        PCTCHK(ss_count_run(c, path, c->d_seg, c->d_r2, Q, c->d_count, g_stream, [&] { return ss_scan(c, Q, c->rs_off, g_stream); }));
-        HIPCHK(hipMemcpyAsync(offsets, c->rs_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));              // the one host read: the total sizes the lists
-        return PCT_OK;
-    }));
-    *total = offsets[Q];
-    if (*total > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "capsule search lists %lld entries, more than 2^32 - 1", (long long)*total);
-    PCTCHK(ss_ensure_lists(c, (size_t)*total, true));
-    PCTCHK(ss_fill_sort(c, path, c->d_seg, c->d_r2, Q, order, c->rs_off, *total, c->ss_idx, c->ss_d2, c->ss_s, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    c->ss_total = *total;
-    c->ss_valid = true;
-    if (path == Path::Empty) return fail(PCT_ERR_EMPTY, "capsule search against an empty cloud");
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, Q, &path));
+    PCTCHK(list_search_host(c, c->ss, "capsule search", true, Q, offsets, total,
+        [&] { return stage_segments(c, seg, reach, Q); },
+        [&] { return ss_count_run(c, path, c->d_seg, c->d_r2, Q, c->d_count, g_stream, [&] { return list_scan(c, Q, c->rs_off, 1u, g_stream); }); },
+        [&] { return ss_fill_sort(c, path, c->d_seg, c->d_r2, Q, order, c->rs_off, *total, c->ss.idx, c->ss.d2, c->ss.s, g_stream); }));
+    if (path == Path::Empty && Q > 0) return fail(PCT_ERR_EMPTY, "capsule search against an empty cloud");
     return PCT_OK;
 }
 
 int pct_segment_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2, double *s)
 {
-    if (!c || !c->ss_valid) return fail(PCT_ERR_INVALID, "no capsule-search result to read (none yet, or the cloud changed since)");
-    if (first < 0 || n < 0 || first > c->ss_total || n > c->ss_total - first)
-        return fail(PCT_ERR_INVALID, "entries [%lld, %lld) lie outside [0, %lld]", (long long)first, (long long)(first + n), (long long)c->ss_total);
-    if (n == 0) return PCT_OK;
-    if (idx) HIPCHK(hipMemcpyAsync(idx, c->ss_idx + first, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, g_stream));
-    if (d2) HIPCHK(hipMemcpyAsync(d2, c->ss_d2 + first, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    if (s) HIPCHK(hipMemcpyAsync(s, c->ss_s + first, sizeof(double) * n, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    return PCT_OK;
+    if (!c) return fail(PCT_ERR_INVALID, "no capsule-search result to read (none yet, or the cloud changed since)");
+    return read_lists(c->ss, first, n, idx, d2, s);
 }
 
 // The reach that bounds the capsule inflation's walk.  The contract is unbounded: radius = min(sqrt(d2*) - m, R), d2* the smallest
@@ -2796,21 +2761,18 @@ int pct_segment_inflate_batch(pct_cloud *c, const pct_inflate_params *p, const d
     if (!c || !p || Q < 0 || (Q > 0 && (!seg || !radius))) return fail(PCT_ERR_INVALID, "bad segment_inflate_batch arguments");
     PCTCHK(ring_finish_pending(c));
     if (Q == 0) return PCT_OK;
-    SegPath path;
-    PCTCHK(resolve_segment_algo(c, PCT_ALGO_AUTO, &path));
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Segment, PCT_ALGO_AUTO, Q, &path));
     PCTCHK(pct_cloud_reserve_queries(c, Q));
+    const bool empty = path == Path::Empty;      // the engine's empty-cloud rule, PCT_OK: nothing is staged or searched
     const double reach = segment_inflate_reach(p);
-    if (path != SegPath::Empty) HIPCHK(hipMemcpyAsync(c->d_seg, seg, sizeof(double) * 6 * Q, hipMemcpyHostToDevice, g_stream));
-    return ask_twice_after_overrun(c, [&]() -> int {
+    return segment_host_form(c, empty ? nullptr : seg, nullptr, Q,
+                             { { radius, c->d_r2, sizeof(double) }, { idx, c->d_idx, sizeof(uint32_t) }, { s, c->d_radius, sizeof(double) } }, nullptr, [&]() -> int {
         // no start-distance early-out: a segment has no single distance to the start
-        if (path != SegPath::Empty) PCTCHK(segment_run(c, path, SegMeasure::Nearest, c->d_seg, nullptr, reach, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
-        segment_inflate_epilogue_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(to_dev(p), (uint32_t)Q, path == SegPath::Empty ? 1 : 0, c->d_idx,
-                                                                                c->d_d2, c->d_radius, c->d_r2);
+        if (!empty) PCTCHK(segment_run(c, path, SegMeasure::Nearest, c->d_seg, nullptr, reach, Q, c->d_idx, c->d_d2, c->d_radius, g_stream));
+        segment_inflate_epilogue_kernel<<<ceil_div(Q, 256), 256, 0, g_stream>>>(to_dev(p), (uint32_t)Q, empty ? 1 : 0, c->d_idx, c->d_d2, c->d_radius,
+                                                                                c->d_r2);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(radius, c->d_r2, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
-        if (idx) HIPCHK(hipMemcpyAsync(idx, c->d_idx, sizeof(uint32_t) * Q, hipMemcpyDeviceToHost, g_stream));
-        if (s) HIPCHK(hipMemcpyAsync(s, c->d_radius, sizeof(double) * Q, hipMemcpyDeviceToHost, g_stream));
-        HIPCHK(hipStreamSynchronize(g_stream));
         return PCT_OK;
     });
 }

@@ -149,11 +149,7 @@ __global__ __launch_bounds__(256) void ring_count_kernel(RingView V, const float
     uint32_t n = 0, npts = 0, nbuckets = 0;
     if (V.st->count != 0 && r2 >= 0.0 && qx == qx && qy == qy && qz == qz)
         ring_for_ball(V, qx, qy, qz, fabs(rw), npts, nbuckets, [&](double d2, uint32_t) { n += d2 <= r2 ? 1u : 0u; });
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, kWave);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) count[slot] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+    rs_block_count(n, s_c, count, slot);
     if (work) ring_add_work(work, npts, nbuckets, s_w);
 }
 
@@ -170,25 +166,15 @@ __global__ __launch_bounds__(256) void ring_fill_kernel(RingView V, const float 
 {
     __shared__ uint32_t s_cursor;
     __shared__ unsigned long long s_w[8];
-    if (offsets[Q] > cap) return;
     const size_t slot = blockIdx.x;
-    const long long off0 = offsets[slot];
-    const uint32_t len = (uint32_t)(offsets[slot + 1] - off0);
-    if (len == 0) return;                                   // block-uniform: an empty row is not walked at all
-    if (threadIdx.x == 0) s_cursor = 0;
-    __syncthreads();
+    long long off0;
+    uint32_t len;
+    if (!rs_row_open(offsets, Q, cap, slot, &s_cursor, off0, len)) return;
     const double qx = (double)q[3 * slot], qy = (double)q[3 * slot + 1], qz = (double)q[3 * slot + 2];
     const double rw = (double)rad[slot], r2 = rw * rw;
+    const RsLists L{ out_idx, out_d2, index_base, BY_DIST || out_d2 };
     uint32_t npts = 0, nbuckets = 0;
-    ring_for_ball(V, qx, qy, qz, fabs(rw), npts, nbuckets, [&](double d2, uint32_t id) {
-        if (d2 <= r2) {
-            const uint32_t pos = atomicAdd(&s_cursor, 1u);
-            if (pos < len) {                                // every list store is bounded by the row's own length
-                out_idx[off0 + pos] = id + index_base;
-                if (BY_DIST || out_d2) out_d2[off0 + pos] = d2;
-            }
-        }
-    });
+    ring_for_ball(V, qx, qy, qz, fabs(rw), npts, nbuckets, [&](double d2, uint32_t id) { rs_place(L, off0, len, &s_cursor, d2 <= r2, id, d2); });
     if (work) ring_add_work(work, npts, nbuckets, s_w);
 }
 

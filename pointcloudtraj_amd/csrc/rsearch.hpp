@@ -74,6 +74,71 @@ __global__ __launch_bounds__(256) void rs_scan_final_kernel(const uint32_t *__re
 }
 
 // -------------------------------------------------------------------------------------
+// The row writers of every fill that places its hits in arrival order (the streaming and rolling-map fills here and in
+// ring_search.hpp, the three capsule fills of segment_search.hpp), and the fold of a block-per-row count.
+// -------------------------------------------------------------------------------------
+struct RsLists {
+    uint32_t *idx;
+    double *d2;
+    uint32_t index_base;
+    bool keep_d2;            // the caller's decision: d2 is stored (BY_DIST rows always carry their sort key)
+};
+
+// a hit's entry `pos` of the row [off0, off0 + len)
+__device__ __forceinline__ void rs_store(const RsLists &L, const long long &off0, const uint32_t &len, bool hit, uint32_t pos, uint32_t id, double d2)
+{
+    if (hit && pos < len) {                                 // every list store is bounded by the row's own length
+        L.idx[off0 + pos] = id + L.index_base;
+        if (L.keep_d2) L.d2[off0 + pos] = d2;
+    }
+}
+
+// A block per row: false when the lists do not fit `cap` or the row is empty (block-uniform: such a row is not walked at all),
+// else the row's bounds and a zeroed cursor in LDS.
+__device__ __forceinline__ bool rs_row_open(const long long *__restrict__ offsets, uint32_t Q, long long cap, size_t slot, uint32_t *s_cursor,
+                                            long long &off0, uint32_t &len)
+{
+    if (offsets[Q] > cap) return false;
+    off0 = offsets[slot];
+    len = (uint32_t)(offsets[slot + 1] - off0);
+    if (len == 0) return false;
+    if (threadIdx.x == 0) *s_cursor = 0;
+    __syncthreads();
+    return true;
+}
+
+// ... where a hit takes the next place of the row from that cursor
+__device__ __forceinline__ void rs_place(const RsLists &L, long long off0, uint32_t len, uint32_t *s_cursor, bool hit, uint32_t id, double d2)
+{
+    if (hit) rs_store(L, off0, len, true, atomicAdd(s_cursor, 1u), id, d2);
+}
+
+// Lanes own points: the hits of a wave's 64 points take a block of the row through *cursor (one atomic per wave and step with
+// hits) and their places inside it from the ballot.  Wave-uniform call.
+__device__ __forceinline__ void rs_wave_place(const RsLists &L, const long long &off0, const uint32_t &len, uint32_t *cursor, int lane, bool hit,
+                                              uint32_t id, double d2)
+{
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+    if (m) {                                                // wave-uniform
+        uint32_t first = 0;
+        if (lane == 0) first = atomicAdd(cursor, (uint32_t)__popcll(m));
+        first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+        const uint32_t pos = first + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        rs_store(L, off0, len, hit, pos, id, d2);
+    }
+}
+
+// a 256-thread block's hit count into count[slot] (s_c: 4 words of LDS)
+__device__ __forceinline__ void rs_block_count(uint32_t n, uint32_t *s_c, uint32_t *__restrict__ count, size_t slot)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, kWave);
+    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) count[slot] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+}
+
+// -------------------------------------------------------------------------------------
 // Cell-pruned fill: EIGHT lanes per query over the rows of the ball's bounding box -- the box (grid_ball_box, kernels.hpp) and the order
 // of the batch (qsorted: the counting-sorted records, rows going back to their own query) are count_grid_coop_kernel's, and so is the test,
 // so a row receives exactly offsets[t + 1] - offsets[t] hits.  A row without hits is not walked at all.  The run bounds of 8 rows
@@ -191,6 +256,7 @@ __global__ __launch_bounds__(256) void rs_fill_stream_kernel(const float *__rest
         off[j] = offsets[qi];
         len[j] = (uint32_t)(offsets[qi + 1] - off[j]);
     }
+    const RsLists L{ out_idx, out_d2, index_base, out_d2 != nullptr };
     const uint32_t stride = gridDim.x * 256u;
     for (uint64_t base = blockIdx.x * 256u + (uint32_t)wave * 64u; base < n; base += stride) {      // wave-uniform trip count
         const uint32_t p = (uint32_t)min(base + (uint64_t)lane, (uint64_t)kNoIndex);
@@ -200,18 +266,7 @@ __global__ __launch_bounds__(256) void rs_fill_stream_kernel(const float *__rest
         for (int j = 0; j < kRsTile; j++) {
             if (j >= qcount) break;
             const double d2 = dist2(px, py, pz, qx[j], qy[j], qz[j]);
-            const bool hit = have && d2 <= rr[j];
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-            if (m) {                                              // wave-uniform
-                uint32_t first = 0;
-                if (lane == 0) first = atomicAdd(&cursor[q0 + j], (uint32_t)__popcll(m));
-                first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
-                const uint32_t pos = first + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (hit && pos < len[j]) {
-                    out_idx[off[j] + pos] = p + index_base;
-                    if (out_d2) out_d2[off[j] + pos] = d2;
-                }
-            }
+            rs_wave_place(L, off[j], len[j], &cursor[q0 + j], lane, have && d2 <= rr[j], p, d2);
         }
     }
 }

@@ -177,6 +177,36 @@ __device__ __forceinline__ bool seg_cell_skipped(const RingDesc &R, const SegGeo
     return dc2 > C.skip2;
 }
 
+// One position (jx, jy, jz) of the capsule's box: unless the skip drops it, this lane's share (part of C.lanes) of its bucket.
+template <typename F>
+__device__ __forceinline__ void seg_ring_visit(const RingView &V, const SegGeom &S, const SegBox &C, int jx, int jy, int jz, uint32_t part,
+                                               uint32_t &npts, uint32_t &nbuckets, F offer)
+{
+    const RingDesc &R = V.R;
+    if (seg_cell_skipped(R, S, C, jx, jy, jz)) return;
+    const uint32_t b = ring_lin(R, C.B.x0 + jx, C.B.y0 + jy, C.B.z0 + jz);
+    const uint2 m = V.ht[b];
+    if (part == 0) nbuckets++;
+    ring_for_live_records(V.slots + (size_t)b * R.K, m.x, m.y - m.x, R.K - 1, part, (uint32_t)C.lanes, npts, offer);
+}
+
+// The capsule walk of a 256-thread block on the rolling map: every live record of the overflow queue, then of the capsule's box,
+// once -- offer(px, py, pz, slot).  The box visits every position once, so a count is as safe there as a minimum.
+template <typename F>
+__device__ __forceinline__ void seg_ring_walk(const RingView &V, const SegGeom &S, double bx, double by, double bz, double ra, uint32_t &npts,
+                                              uint32_t &nbuckets, F offer)
+{
+    const RingDesc &R = V.R;
+    const uint32_t oh = V.st->ovf_head;
+    ring_for_live_records(V.ovf, oh, V.st->ovf_tail - oh, R.ovf_mask, threadIdx.x, 256u, npts, offer);
+    const SegBox C = seg_capsule_box(R, S, bx, by, bz, ra);
+    const RingBox &B = C.B;
+    const int lanes = C.lanes;
+    const uint32_t part = threadIdx.x % (uint32_t)lanes;
+    for (int k = (int)threadIdx.x / lanes; k < C.total; k += 256 / lanes)
+        seg_ring_visit(V, S, C, k % B.nx, (k / B.nx) % B.ny, k / (B.nx * B.ny), part, npts, nbuckets, offer);
+}
+
 __global__ __launch_bounds__(256) void ring_segment_kernel(RingView V, const double *__restrict__ seg, const double *__restrict__ reach,
                                                            double reach_all, uint32_t index_base, uint32_t *__restrict__ out_idx,
                                                            double *__restrict__ out_d2, double *__restrict__ out_s,
@@ -186,7 +216,6 @@ __global__ __launch_bounds__(256) void ring_segment_kernel(RingView V, const dou
     __shared__ uint32_t s_i[4];
     __shared__ unsigned long long s_w[8];
     const size_t slot = blockIdx.x;
-    const RingDesc &R = V.R;
     SegGeom S;
     double bx, by, bz, ra;
     const double r2 = seg_load_r2(seg, reach, reach_all, slot, S, bx, by, bz, ra);
@@ -197,22 +226,7 @@ __global__ __launch_bounds__(256) void ring_segment_kernel(RingView V, const dou
         seg_point_d2(S, px, py, pz, d2, s);
         if (d2 <= r2 && better(d2, id, bd, bi)) { bd = d2; bi = id; bs = s; }
     };
-    if (V.st->count != 0 && r2 >= 0.0) {                    // block-uniform
-        const uint32_t oh = V.st->ovf_head;
-        ring_for_live_records(V.ovf, oh, V.st->ovf_tail - oh, R.ovf_mask, threadIdx.x, 256u, npts, offer);
-        const SegBox C = seg_capsule_box(R, S, bx, by, bz, ra);
-        const RingBox &B = C.B;
-        const int lanes = C.lanes;
-        const uint32_t part = threadIdx.x % (uint32_t)lanes;
-        for (int k = (int)threadIdx.x / lanes; k < C.total; k += 256 / lanes) {
-            const int jx = k % B.nx, jy = (k / B.nx) % B.ny, jz = k / (B.nx * B.ny);
-            if (seg_cell_skipped(R, S, C, jx, jy, jz)) continue;
-            const uint32_t b = ring_lin(R, B.x0 + jx, B.y0 + jy, B.z0 + jz);
-            const uint2 m = V.ht[b];
-            if (part == 0) nbuckets++;
-            ring_for_live_records(V.slots + (size_t)b * R.K, m.x, m.y - m.x, R.K - 1, part, (uint32_t)lanes, npts, offer);
-        }
-    }
+    if (V.st->count != 0 && r2 >= 0.0) seg_ring_walk(V, S, bx, by, bz, ra, npts, nbuckets, offer);      // block-uniform
     const double md = bd;
     const uint32_t mi = bi;
     block_argmin256(bd, bi, s_d, s_i);
@@ -302,12 +316,7 @@ __global__ __launch_bounds__(256) void ring_sweep_kernel(RingView V, const doubl
             for (int m = c * nuv + (int)threadIdx.x / lanes; m < end; m += per) {
                 const int layer = m / nuv, rem = m - layer * nuv, ju = rem % nu, jv = rem / nu;
                 const int jk = fwd ? layer : nk - 1 - layer;
-                const int jx = k == 0 ? jk : ju, jy = k == 0 ? ju : k == 1 ? jk : jv, jz = k == 2 ? jk : jv;
-                if (seg_cell_skipped(R, S, C, jx, jy, jz)) continue;
-                const uint32_t b = ring_lin(R, B.x0 + jx, B.y0 + jy, B.z0 + jz);
-                const uint2 mm = V.ht[b];
-                if (part == 0) nbuckets++;
-                ring_for_live_records(V.slots + (size_t)b * R.K, mm.x, mm.y - mm.x, R.K - 1, part, (uint32_t)lanes, npts, offer);
+                seg_ring_visit(V, S, C, k == 0 ? jk : ju, k == 0 ? ju : k == 1 ? jk : jv, k == 2 ? jk : jv, part, npts, nbuckets, offer);
             }
             const int cn = c + W;                           // the next round's first layer
             if (cn >= nk) break;                            // block-uniform, as everything the stop test reads

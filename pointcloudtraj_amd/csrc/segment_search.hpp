@@ -16,27 +16,18 @@
 // Three forms, same answers bit for bit:
 //   * ss_stream_*   PCT_ALGO_STREAM, any cloud: lanes own points, a tile of kSegTile segments sits in LDS (segment_stream_kernel's
 //                   shape).  Count: per-lane hit counts folded per wave, one atomic per wave and segment with hits.  Fill:
-//                   rs_fill_stream_kernel's scheme, one cursor atomic per wave, segment and step with hits, places from the ballot.
-//   * ss_ring_*     PCT_ALGO_RING: a 256-thread block per segment, ring_segment_kernel's walk: the overflow queue exhaustively,
-//                   then seg_capsule_box with seg_cell_skipped and ring_for_live_records.  The box visits every position once, so a
-//                   count is as safe there as a minimum.  The fill places hits through a cursor in LDS (ring_fill_kernel's).
+//                   rs_fill_stream_kernel's scheme (rs_wave_place, rsearch.hpp).
+//   * ss_ring_*     PCT_ALGO_RING: a 256-thread block per segment, ring_segment_kernel's walk (seg_ring_walk, segment.hpp): the
+//                   overflow queue exhaustively, then seg_capsule_box with seg_cell_skipped and ring_for_live_records.
 //   * ss_grid_*     PCT_ALGO_GRID: a 256-thread block per segment over the cell index -- the walk this file adds (ss_grid_walk).
+// The ring and grid forms are one count body and one fill body (ss_count_body, ss_fill_body) over the two walks; the fill places
+// its hits through a cursor in LDS (rs_row_open / rs_place, rsearch.hpp: ring_fill_kernel's).
 #pragma once
 #include "segment.hpp"
 
 #pragma clang fp contract(off)
 
 namespace pct {
-
-// a block's hit count into count[slot] (s_c: 4 words of LDS)
-__device__ __forceinline__ void ss_block_count(uint32_t n, uint32_t *s_c, uint32_t *__restrict__ count, size_t slot)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += (uint32_t)__shfl_xor((int)n, off, kWave);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) count[slot] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-}
 
 // the tile's segments into LDS: ax ay az ex ey ez L2 r2 (r2 = -1 beyond the batch: no row is a candidate)
 __device__ __forceinline__ void ss_load_tile(const double *__restrict__ seg, const double *__restrict__ reach, uint32_t q0, uint32_t Q,
@@ -86,8 +77,8 @@ __global__ __launch_bounds__(256) void ss_stream_count_kernel(const float *__res
     }
 }
 
-// The fill: the hits of a wave's 64 points for one segment take a block of that segment's row through cursor[segment] (zeroed by the
-// caller) and their places inside it from the ballot.  A tile whose rows are all empty returns at once.
+// The fill: the hits of a wave's 64 points for one segment are placed by rs_wave_place through cursor[segment] (zeroed by the
+// caller).  A tile whose rows are all empty returns at once.
 __global__ __launch_bounds__(256) void ss_stream_fill_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
                                                              uint32_t n, const double *__restrict__ seg, const double *__restrict__ reach,
                                                              uint32_t Q, uint32_t tile0, uint32_t index_base, const long long *__restrict__ offsets,
@@ -110,6 +101,7 @@ __global__ __launch_bounds__(256) void ss_stream_fill_kernel(const float *__rest
         s_len[threadIdx.x] = have ? (uint32_t)(offsets[q0 + threadIdx.x + 1] - o) : 0u;
     }
     __syncthreads();
+    const RsLists L{ out_idx, out_d2, index_base, out_d2 != nullptr };
     const uint32_t stride = gridDim.x * 256u;
     for (uint64_t base = blockIdx.x * 256u + (uint32_t)wave * 64u; base < n; base += stride) {      // wave-uniform trip count
         const uint32_t p = (uint32_t)min(base + (uint64_t)lane, (uint64_t)kNoIndex);
@@ -121,47 +113,18 @@ __global__ __launch_bounds__(256) void ss_stream_fill_kernel(const float *__rest
             const SegGeom S{ s_g[t][0], s_g[t][1], s_g[t][2], s_g[t][3], s_g[t][4], s_g[t][5], s_g[t][6] };
             double d2, s;
             seg_point_d2(S, px, py, pz, d2, s);
-            const bool hit = have && d2 <= s_g[t][7];
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-            if (m) {                                              // wave-uniform
-                uint32_t first = 0;
-                if (lane == 0) first = atomicAdd(&cursor[q0 + t], (uint32_t)__popcll(m));
-                first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
-                const uint32_t pos = first + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (hit && pos < s_len[t]) {                      // every list store is bounded by the row's own length
-                    out_idx[s_off[t] + pos] = p + index_base;
-                    if (out_d2) out_d2[s_off[t] + pos] = d2;
-                }
-            }
+            rs_wave_place(L, s_off[t], s_len[t], &cursor[q0 + t], lane, have && d2 <= s_g[t][7], p, d2);
         }
     }
 }
 
-// ---- the rolling-map form -------------------------------------------------------------------------------------------------------
-// ring_segment_kernel's walk with another offer: every live record of the overflow queue, then of the capsule's box, once.
-template <typename F>
-__device__ __forceinline__ void ss_ring_walk(const RingView &V, const SegGeom &S, double bx, double by, double bz, double ra, uint32_t &npts,
-                                             uint32_t &nbuckets, F offer)
-{
-    const RingDesc &R = V.R;
-    const uint32_t oh = V.st->ovf_head;
-    ring_for_live_records(V.ovf, oh, V.st->ovf_tail - oh, R.ovf_mask, threadIdx.x, 256u, npts, offer);
-    const SegBox C = seg_capsule_box(R, S, bx, by, bz, ra);
-    const RingBox &B = C.B;
-    const int lanes = C.lanes;
-    const uint32_t part = threadIdx.x % (uint32_t)lanes;
-    for (int k = (int)threadIdx.x / lanes; k < C.total; k += 256 / lanes) {
-        const int jx = k % B.nx, jy = (k / B.nx) % B.ny, jz = k / (B.nx * B.ny);
-        if (seg_cell_skipped(R, S, C, jx, jy, jz)) continue;
-        const uint32_t b = ring_lin(R, B.x0 + jx, B.y0 + jy, B.z0 + jz);
-        const uint2 m = V.ht[b];
-        if (part == 0) nbuckets++;
-        ring_for_live_records(V.slots + (size_t)b * R.K, m.x, m.y - m.x, R.K - 1, part, (uint32_t)lanes, npts, offer);
-    }
-}
-
-__global__ __launch_bounds__(256) void ss_ring_count_kernel(RingView V, const double *__restrict__ seg, const double *__restrict__ reach,
-                                                            uint32_t *__restrict__ count, WorkCounters *__restrict__ work)
+// ---- a block per segment: one count and one fill over either index ----------------------------------------------------------------
+// A walk offers every record the capsule (S, reach) can hold, once: walk(S, bx, by, bz, ra, npts, nopened, offer), with live() false
+// when there is nothing to walk.  The count and the fill are the same walk and the same test twice, on the same index (same stream,
+// nothing in between), so row i receives exactly its length in hits; the fill places them through a cursor in LDS (rs_place).
+template <typename W>
+__device__ __forceinline__ void ss_count_body(const W &walk, const double *__restrict__ seg, const double *__restrict__ reach,
+                                              uint32_t *__restrict__ count, WorkCounters *__restrict__ work)
 {
     __shared__ uint32_t s_c[4];
     __shared__ unsigned long long s_w[8];
@@ -169,48 +132,66 @@ __global__ __launch_bounds__(256) void ss_ring_count_kernel(RingView V, const do
     SegGeom S;
     double bx, by, bz, ra;
     const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);
-    uint32_t n = 0, npts = 0, nbuckets = 0;
-    if (V.st->count != 0 && r2 >= 0.0)                      // block-uniform
-        ss_ring_walk(V, S, bx, by, bz, ra, npts, nbuckets, [&](double px, double py, double pz, uint32_t) {
+    uint32_t n = 0, npts = 0, nopened = 0;
+    if (walk.live() && r2 >= 0.0)                           // block-uniform
+        walk(S, bx, by, bz, ra, npts, nopened, [&](double px, double py, double pz, uint32_t) {
             double d2, s;
             seg_point_d2(S, px, py, pz, d2, s);
             n += d2 <= r2 ? 1u : 0u;
         });
-    ss_block_count(n, s_c, count, slot);
-    if (work) ring_add_work(work, npts, nbuckets, s_w);
+    rs_block_count(n, s_c, count, slot);
+    if (work) ring_add_work(work, npts, nopened, s_w);
 }
 
-// the count's walk and test on the same table (same stream, no append in between): row i receives exactly its length in hits
+template <typename W>
+__device__ __forceinline__ void ss_fill_body(const W &walk, const double *__restrict__ seg, const double *__restrict__ reach, uint32_t Q,
+                                             uint32_t index_base, const long long *__restrict__ offsets, long long cap,
+                                             uint32_t *__restrict__ out_idx, double *__restrict__ out_d2, WorkCounters *__restrict__ work)
+{
+    __shared__ uint32_t s_cursor;
+    __shared__ unsigned long long s_w[8];
+    const size_t slot = blockIdx.x;
+    long long off0;
+    uint32_t len;
+    if (!rs_row_open(offsets, Q, cap, slot, &s_cursor, off0, len)) return;
+    SegGeom S;
+    double bx, by, bz, ra;
+    const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);       // len > 0: the reach is valid
+    const RsLists L{ out_idx, out_d2, index_base, out_d2 != nullptr };
+    uint32_t npts = 0, nopened = 0;
+    walk(S, bx, by, bz, ra, npts, nopened, [&](double px, double py, double pz, uint32_t id) {
+        double d2, s;
+        seg_point_d2(S, px, py, pz, d2, s);
+        rs_place(L, off0, len, &s_cursor, d2 <= r2, id, d2);
+    });
+    if (work) ring_add_work(work, npts, nopened, s_w);
+}
+
+// ---- the rolling-map form -------------------------------------------------------------------------------------------------------
+// ring_segment_kernel's walk (seg_ring_walk, segment.hpp) with another offer
+struct SsRingWalk {
+    const RingView &V;
+    __device__ __forceinline__ bool live() const { return V.st->count != 0; }
+    template <typename F>
+    __device__ __forceinline__ void operator()(const SegGeom &S, double bx, double by, double bz, double ra, uint32_t &npts, uint32_t &nbuckets,
+                                               F offer) const
+    {
+        seg_ring_walk(V, S, bx, by, bz, ra, npts, nbuckets, offer);
+    }
+};
+
+__global__ __launch_bounds__(256) void ss_ring_count_kernel(RingView V, const double *__restrict__ seg, const double *__restrict__ reach,
+                                                            uint32_t *__restrict__ count, WorkCounters *__restrict__ work)
+{
+    ss_count_body(SsRingWalk{ V }, seg, reach, count, work);
+}
+
 __global__ __launch_bounds__(256) void ss_ring_fill_kernel(RingView V, const double *__restrict__ seg, const double *__restrict__ reach, uint32_t Q,
                                                            uint32_t index_base, const long long *__restrict__ offsets, long long cap,
                                                            uint32_t *__restrict__ out_idx, double *__restrict__ out_d2,
                                                            WorkCounters *__restrict__ work)
 {
-    __shared__ uint32_t s_cursor;
-    __shared__ unsigned long long s_w[8];
-    if (offsets[Q] > cap) return;
-    const size_t slot = blockIdx.x;
-    const long long off0 = offsets[slot];
-    const uint32_t len = (uint32_t)(offsets[slot + 1] - off0);
-    if (len == 0) return;                                   // block-uniform: an empty row is not walked at all
-    if (threadIdx.x == 0) s_cursor = 0;
-    __syncthreads();
-    SegGeom S;
-    double bx, by, bz, ra;
-    const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);
-    uint32_t npts = 0, nbuckets = 0;
-    ss_ring_walk(V, S, bx, by, bz, ra, npts, nbuckets, [&](double px, double py, double pz, uint32_t id) {
-        double d2, s;
-        seg_point_d2(S, px, py, pz, d2, s);
-        if (d2 <= r2) {
-            const uint32_t pos = atomicAdd(&s_cursor, 1u);
-            if (pos < len) {                                // every list store is bounded by the row's own length
-                out_idx[off0 + pos] = id + index_base;
-                if (out_d2) out_d2[off0 + pos] = d2;
-            }
-        }
-    });
-    if (work) ring_add_work(work, npts, nbuckets, s_w);
+    ss_fill_body(SsRingWalk{ V }, seg, reach, Q, index_base, offsets, cap, out_idx, out_d2, work);
 }
 
 // ---- the cell-index form --------------------------------------------------------------------------------------------------------
@@ -321,27 +302,25 @@ __device__ __forceinline__ void ss_grid_walk(const GridDesc &G, const float4 *__
     }
 }
 
+struct SsGridWalk {
+    const GridDesc &G;
+    const float4 *pts;
+    const uint32_t *cell_start;
+    __device__ __forceinline__ bool live() const { return true; }
+    template <typename F>
+    __device__ __forceinline__ void operator()(const SegGeom &S, double bx, double by, double bz, double ra, uint32_t &npts, uint32_t &ncells,
+                                               F offer) const
+    {
+        const SsGridBox B = ss_grid_box(G, S, bx, by, bz, ra);
+        ss_grid_walk(G, pts, cell_start, S, B, npts, ncells, offer);
+    }
+};
+
 __global__ __launch_bounds__(256) void ss_grid_count_kernel(GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
                                                             const double *__restrict__ seg, const double *__restrict__ reach,
                                                             uint32_t *__restrict__ count, WorkCounters *__restrict__ work)
 {
-    __shared__ uint32_t s_c[4];
-    __shared__ unsigned long long s_w[8];
-    const size_t slot = blockIdx.x;
-    SegGeom S;
-    double bx, by, bz, ra;
-    const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);
-    uint32_t n = 0, npts = 0, ncells = 0;
-    if (r2 >= 0.0) {                                        // block-uniform
-        const SsGridBox B = ss_grid_box(G, S, bx, by, bz, ra);
-        ss_grid_walk(G, pts, cell_start, S, B, npts, ncells, [&](double px, double py, double pz, uint32_t) {
-            double d2, s;
-            seg_point_d2(S, px, py, pz, d2, s);
-            n += d2 <= r2 ? 1u : 0u;
-        });
-    }
-    ss_block_count(n, s_c, count, slot);
-    if (work) ring_add_work(work, npts, ncells, s_w);
+    ss_count_body(SsGridWalk{ G, pts, cell_start }, seg, reach, count, work);
 }
 
 __global__ __launch_bounds__(256) void ss_grid_fill_kernel(GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
@@ -350,32 +329,7 @@ __global__ __launch_bounds__(256) void ss_grid_fill_kernel(GridDesc G, const flo
                                                            uint32_t *__restrict__ out_idx, double *__restrict__ out_d2,
                                                            WorkCounters *__restrict__ work)
 {
-    __shared__ uint32_t s_cursor;
-    __shared__ unsigned long long s_w[8];
-    if (offsets[Q] > cap) return;
-    const size_t slot = blockIdx.x;
-    const long long off0 = offsets[slot];
-    const uint32_t len = (uint32_t)(offsets[slot + 1] - off0);
-    if (len == 0) return;                                   // block-uniform: an empty row is not walked at all
-    if (threadIdx.x == 0) s_cursor = 0;
-    __syncthreads();
-    SegGeom S;
-    double bx, by, bz, ra;
-    const double r2 = seg_load_r2(seg, reach, 0.0, slot, S, bx, by, bz, ra);
-    uint32_t npts = 0, ncells = 0;
-    const SsGridBox B = ss_grid_box(G, S, bx, by, bz, ra);          // len > 0: the reach is valid
-    ss_grid_walk(G, pts, cell_start, S, B, npts, ncells, [&](double px, double py, double pz, uint32_t id) {
-        double d2, s;
-        seg_point_d2(S, px, py, pz, d2, s);
-        if (d2 <= r2) {
-            const uint32_t pos = atomicAdd(&s_cursor, 1u);
-            if (pos < len) {                                // every list store is bounded by the row's own length
-                out_idx[off0 + pos] = id + index_base;
-                if (out_d2) out_d2[off0 + pos] = d2;
-            }
-        }
-    });
-    if (work) ring_add_work(work, npts, ncells, s_w);
+    ss_fill_body(SsGridWalk{ G, pts, cell_start }, seg, reach, Q, index_base, offsets, cap, out_idx, out_d2, work);
 }
 
 // ---- s, after the sort ----------------------------------------------------------------------------------------------------------
