@@ -374,6 +374,50 @@
  * grown to cap entries by the call.  pct_last_work reports the records read and the cells / buckets opened by the count and the
  * fill together (the streaming form: Q x size, known on the host).
  *
+ * Free-space polyhedra (pct_segment_polyhedron_batch, pct_segment_polyhedron_read, pct_segment_supports_dev): a convex free region
+ * around each segment, as half-spaces -- the step from "these points lie near this edge" to "this polyhedron around the edge is
+ * free", for a corridor handed to a QP or SOCP solver.  For segment i with reach[i], take row i of "Capsule search" in
+ * PCT_ORDER_DISTANCE: its entries ordered by d2, then index; every term is that paragraph's.  Walk the row in that order: an entry is
+ * a SUPPORT iff no earlier support of the same row cuts it.  The cut test is fp64 on float-widened operands, one rounding per
+ * operation, no contraction, in exactly this order.  For a support with row p, s and d2 are those of "Segment queries" and
+ * n_k = w_k - s*e_k, that paragraph's c_k.  For a later entry with row x:  u_k = x_k - p_k;  h = (n0*u0 + n1*u1) + n2*u2.  The
+ * support cuts the entry iff h >= 0 -- inclusive.  Nothing can overflow (products of differences of finite floats) and nothing can
+ * be NaN.  Hence: the first entry of a non-empty row is always a support; a second copy of a support's point is cut (u = 0, h = 0);
+ * a row with d2 == 0 -- a point ON the segment -- has n = 0 and cuts everything behind it: its plane is the empty half-space and the
+ * caller reads "the segment collides" from d2.  The plane of a support:  d = sqrt(d2);  nh_k = n_k / d;  off = (nh0*p0 + nh1*p1) +
+ * nh2*p2;  the half-space is {y : nh.y <= off};  for d2 == 0 the plane is (0, 0, 0, -1).  `/` and sqrt are correctly rounded, as
+ * elsewhere in this header.  Guarantees, in real arithmetic (rounding moves a plane by a few ulp of the coordinates, no more):
+ * (1) the segment lies in every half-space, strictly when d2 > 0 -- n = p - c with c the closest point of a convex set, so
+ * n.(y - c) <= 0 for every y on the segment; (2) no row of the window within reach of the segment lies in the interior of the
+ * intersection -- every candidate is a support, and lies on its own plane, or is cut by one; (3) nothing is claimed outside the
+ * capsule (segment, reach): a caller who wants a bounded polytope intersects with a region inside that capsule, as
+ * ObstacleMap::segmentPolyhedra does.  The robot's size is not part of the call: shrinking by a margin m is off - m per plane, the
+ * caller's step; the cut test uses the unshifted planes, which is what makes the shrunk region m-clear of every cut point.  Each
+ * entry of the result carries idx = index_base + local index (the ring slot on a rolling map), d2, s and the plane nh0 nh1 nh2 off;
+ * the result is a CSR like the capsule search's, offsets[Q + 1] with offsets[0] = 0 and offsets[Q] the total, supports in row order
+ * (nearest first).  Invalid segments give empty rows exactly as in the capsule search (a non-finite end, a NaN or negative reach);
+ * rows that hold a NaN, removed rows and rows with an infinite coordinate never appear.  Host form: the capsule search's count,
+ * scan, fill and distance sort on the path `algo` selects exactly as there (PCT_ALGO_AUTO, _STREAM, _GRID, _RING; anything the
+ * capsule search refuses is PCT_ERR_INVALID), then the filter, a count of supports per row, a scan and a compaction -- all forms
+ * give the same bytes.  An append in flight is finished first, an overflow-queue overrun is asked twice, and the host is read
+ * twice: the candidate total, which sizes the lists, and the support offsets.  The candidate rows live in cloud-owned buffers of
+ * their own (12 B per entry): the call does NOT borrow the capsule search's list buffer, and pct_segment_search_read still reads
+ * the last capsule search after it.  The supports stay in cloud-owned buffers too (52 B per support);
+ * pct_segment_polyhedron_read copies any range of them (idx, d2, s or plane may be NULL); a result lasts until the next
+ * pct_segment_polyhedron_batch, an upload, append, grid build or drop, or destroy: a read after any of those, before any call, or
+ * of a range outside [0, total] is PCT_ERR_INVALID; n = 0 is PCT_OK.  An empty cloud gives all-zero offsets; the host form then
+ * returns PCT_ERR_EMPTY, the device form PCT_OK.  Q == 0: PCT_OK with offsets[0] = 0.  A NULL required pointer, Q < 0, cap < 0 or
+ * row_cap < 0: PCT_ERR_INVALID with nothing written.  Device form (pct_segment_supports_dev): the filter alone, over rows the
+ * caller made with pct_segment_search_batch_dev(..., PCT_ORDER_DISTANCE, ...) -- d_row_offsets[Q + 1], d_row_idx, and row_cap the
+ * cap of that call; asynchronous on `stream`, no host wait.  d_offsets[Q + 1] is always written.  If d_row_offsets[Q] > row_cap the
+ * rows were never written: every entry of d_offsets is then -1 and nothing else is touched.  Otherwise the lists are written only
+ * when d_offsets[Q] <= cap -- tested on the device; d_d2, d_s and d_plane may be NULL.  A row index outside the cloud is never a
+ * support and is never dereferenced.  The filter trusts the given order and does not re-sort.  d2, s and the plane are recomputed
+ * from the segment and the row the index names, of which they are functions.  The positions of the supports inside their rows live
+ * in a cloud-owned buffer of 4 B per row entry, grown to row_cap by the call (refused during graph capture, like
+ * pct_cloud_reserve_queries; reserve the batch size first).  pct_polyhedron_lds_rows() is the longest row the filter keeps in LDS
+ * in one piece; longer rows are served in windows of that length, with the same bytes.
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -673,6 +717,22 @@ int pct_segment_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *id
  * d_offsets[Q] <= cap.  Reserve the batch size first (pct_cloud_reserve_queries). */
 int pct_segment_search_batch_dev(pct_cloud *c, int algo, const double *d_seg, const double *d_reach, int64_t Q, int order, int64_t *d_offsets,
                                  int64_t cap, uint32_t *d_idx, double *d_d2, double *d_s, void *stream);
+
+/* Free-space polyhedra (contract: top of this file, "Free-space polyhedra").  seg: Q x 6 fp64, a then b; reach[Q].  The supports of
+ * every segment's capsule row as a CSR (offsets[Q + 1], total) whose lists pct_segment_polyhedron_read copies out; algo as for
+ * pct_segment_search_batch.  The capsule search's last result stays readable. */
+int pct_segment_polyhedron_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, int64_t *offsets, int64_t *total);
+/* entries [first, first + n) of the LAST pct_segment_polyhedron_batch on this cloud; plane: n x 4 doubles, nh0 nh1 nh2 off; any of
+ * idx, d2, s and plane may be NULL */
+int pct_segment_polyhedron_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2, double *s, double *plane);
+/* the filter alone over device rows made by pct_segment_search_batch_dev(..., PCT_ORDER_DISTANCE, ..., cap = row_cap, ...);
+ * asynchronous on `stream`.  d_offsets[Q + 1] always written (all -1 when d_row_offsets[Q] > row_cap), the lists (d_d2 / d_s /
+ * d_plane may be NULL) only when d_offsets[Q] <= cap.  Reserve the batch size first (pct_cloud_reserve_queries). */
+int pct_segment_supports_dev(pct_cloud *c, const double *d_seg, int64_t Q, const int64_t *d_row_offsets, int64_t row_cap,
+                             const uint32_t *d_row_idx, int64_t *d_offsets, int64_t cap, uint32_t *d_idx, double *d_d2, double *d_s,
+                             double *d_plane, void *stream);
+/* diagnostics, needs no GPU: the longest row the filter kernel keeps in LDS in one piece */
+int pct_polyhedron_lds_rows(void);
 
 /* ---- one RRT* iteration's three dependent queries in ONE launch (corridor_finder.cpp:385-410 genNewNode, :428-437
  * findNearstVertex, :464 treeRewire's neighbourhood), for K samples at once: nearest tree node of the fp32-narrowed

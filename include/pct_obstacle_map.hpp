@@ -347,6 +347,77 @@ public:
         counts.assign((size_t)n, 0u);
         check(pct_segment_count_batch(cloud_, PCT_ALGO_AUTO, segments.data(), reaches.data(), n, counts.data()), "pct_segment_count_batch");
     }
+    // Free-space polyhedra (pct_engine.h, paragraph "Free-space polyhedra"): a bounded convex region around each segment that holds
+    // the segment and no obstacle point closer than `margin` to its faces' inside -- what a QP / SOCP corridor constraint takes.
+    // segments: n x 6 doubles, a then b.  Row i of the result = planes entries [offsets[i], offsets[i + 1]), 4 doubles each
+    // (nh0 nh1 nh2 off: the half-space nh . y <= off), offsets has n + 1 entries:
+    //   * first the support planes of the segment's capsule row, each with its off reduced by `margin` (the robot's size: the region
+    //     is margin-clear of every obstacle point within `reach` of the segment);
+    //   * then six planes of a box that lies INSIDE the capsule (segment, reach), which turns "nothing is claimed outside the
+    //     capsule" into "the polytope is free": half-width reach / sqrt(3) across the segment, from -reach / sqrt(3) to
+    //     |b - a| + reach / sqrt(3) along it, so that its farthest corners are at distance reach from the segment.  Its frame: t =
+    //     e / |e|, u perpendicular to t built from the coordinate axis of smallest |t_k| (the lowest k on ties), v = t x u; the
+    //     coordinate axes for a == b.  The box is plain host arithmetic on the fp32-narrowed ends, not bit-pinned.
+    // A segment that collides -- its nearest support lies at d2 <= margin^2, a point on the segment included -- is reported by an
+    // EMPTY row: no polytope around it contains it.  So is a segment with a non-finite end or a reach that is not a finite number
+    // >= 0.  Every non-empty row therefore has at least six planes and contains its segment.  indices (optional): per plane the
+    // obstacle point that supports it, PCT_NO_INDEX for the six box planes.
+    void segmentPolyhedra(const std::vector<double> &segments, double reach, double margin, std::vector<int64_t> &offsets,
+                          std::vector<double> &planes, std::vector<uint32_t> *indices = nullptr)
+    {
+        const int64_t n = (int64_t)(segments.size() / 6);
+        const std::vector<double> reaches((size_t)n, reach);
+        std::vector<int64_t> sup((size_t)n + 1, 0);
+        int64_t total = 0;
+        const int st = pct_segment_polyhedron_batch(cloud_, PCT_ALGO_AUTO, segments.data(), reaches.data(), n, sup.data(), &total);
+        if (st != PCT_ERR_EMPTY) check(st, "pct_segment_polyhedron_batch");      // an empty map: no supports, the boxes alone
+        std::vector<uint32_t> idx((size_t)total);
+        std::vector<double> d2((size_t)total), pl(4 * (size_t)total);
+        check(pct_segment_polyhedron_read(cloud_, 0, total, idx.data(), d2.data(), nullptr, pl.data()), "pct_segment_polyhedron_read");
+        offsets.assign((size_t)n + 1, 0);
+        planes.clear();
+        if (indices) indices->clear();
+        const auto put = [&](double n0, double n1, double n2, double off, uint32_t id) {
+            planes.push_back(n0); planes.push_back(n1); planes.push_back(n2); planes.push_back(off);
+            if (indices) indices->push_back(id);
+        };
+        for (int64_t i = 0; i < n; i++) {
+            const double *sg = &segments[6 * (size_t)i];
+            double a[3], e[3], t[3] = { 1.0, 0.0, 0.0 }, u[3] = { 0.0, 1.0, 0.0 }, v[3] = { 0.0, 0.0, 1.0 };
+            bool valid = std::isfinite(reach) && reach >= 0.0;
+            for (int k = 0; k < 3; k++) {
+                const float fa = (float)sg[k], fb = (float)sg[3 + k];
+                a[k] = (double)fa;
+                e[k] = (double)fb - (double)fa;
+                valid = valid && std::isfinite(fa) && std::isfinite(fb);
+            }
+            const bool collides = sup[i + 1] > sup[i] && d2[(size_t)sup[i]] <= margin * margin;      // the first support is the nearest
+            if (valid && !collides) {
+                for (int64_t j = sup[i]; j < sup[i + 1]; j++) put(pl[4 * j], pl[4 * j + 1], pl[4 * j + 2], pl[4 * j + 3] - margin, idx[(size_t)j]);
+                const double len = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+                if (len > 0.0) {
+                    for (int k = 0; k < 3; k++) t[k] = e[k] / len;
+                    int m = 0;
+                    for (int k = 1; k < 3; k++) if (std::fabs(t[k]) < std::fabs(t[m])) m = k;
+                    double ul = 0.0;
+                    for (int k = 0; k < 3; k++) { u[k] = (k == m ? 1.0 : 0.0) - t[m] * t[k]; ul += u[k] * u[k]; }
+                    ul = std::sqrt(ul);                                           // >= sqrt(2 / 3): |t_m| <= 1 / sqrt(3)
+                    for (int k = 0; k < 3; k++) u[k] /= ul;
+                    v[0] = t[1] * u[2] - t[2] * u[1]; v[1] = t[2] * u[0] - t[0] * u[2]; v[2] = t[0] * u[1] - t[1] * u[0];
+                }
+                const double hw = reach / std::sqrt(3.0);
+                const double ta = (t[0] * a[0] + t[1] * a[1]) + t[2] * a[2], ua = (u[0] * a[0] + u[1] * a[1]) + u[2] * a[2],
+                             va = (v[0] * a[0] + v[1] * a[1]) + v[2] * a[2];
+                put(t[0], t[1], t[2], ta + len + hw, PCT_NO_INDEX);
+                put(-t[0], -t[1], -t[2], hw - ta, PCT_NO_INDEX);
+                put(u[0], u[1], u[2], ua + hw, PCT_NO_INDEX);
+                put(-u[0], -u[1], -u[2], hw - ua, PCT_NO_INDEX);
+                put(v[0], v[1], v[2], va + hw, PCT_NO_INDEX);
+                put(-v[0], -v[1], -v[2], hw - va, PCT_NO_INDEX);
+            }
+            offsets[(size_t)i + 1] = (int64_t)(planes.size() / 4);
+        }
+    }
     // corridor_finder.cpp:661-669
     int checkNodeUpdate(double new_radius, double old_radius) const
     {

@@ -43,6 +43,7 @@
 #include "bezier_batch.hpp"
 #include "segment.hpp"
 #include "segment_search.hpp"
+#include "segment_polyhedron.hpp"
 
 using namespace pct;
 using pct_host::pow2_at_least;
@@ -289,6 +290,14 @@ struct pct_cloud {
     // capsule search (segment_search.hpp): the lists of the host form's last result in buffers of their own (20 B per entry)
     // -- pct_radius_search_read promises the last RADIUS search
     ListStore ss{ "capsule-search" };
+    // free-space polyhedra (segment_polyhedron.hpp): the host form's candidate rows in buffers of their own (idx + d2, 12 B per entry
+    // -- the capsule search's last result stays readable), the supports of its last result (idx, d2, s + 4 doubles of plane), the
+    // support offsets on the device, and the per-entry support positions of either form (grown to the rows' capacity by the call)
+    ListStore pc{ "polyhedron-candidate" };
+    ListStore pl{ "free-space-polyhedron" };
+    DevBuf<double> pl_plane;
+    DevBuf<long long> pl_off;
+    DevBuf<uint32_t> pl_sup;
     // order-preserving crop (lidar): tile counts and the compacted {index, d2, x, y, z} of the last crop
     DevBuf<uint32_t> crop_tile, crop_idx;
     DevBuf<double> crop_d2;
@@ -611,6 +620,7 @@ void drop_grid(pct_cloud *c)
     c->has_grid = false;
     c->rs.valid = false;                // every upload, append, build and drop comes through here: the last radius-search result ends
     c->ss.valid = false;                // and the last capsule search's
+    c->pl.valid = false;                // and the last free-space polyhedra
     c->has_pyr = false;
 }
 
@@ -1495,6 +1505,38 @@ int ss_fill_sort(pct_cloud *c, Path path, const double *d_seg, const double *d_r
         rs_sort_rows_kernel<decltype(bd)::value><<<blocks, 256, 0, s>>>(c->rs_queue, d_offsets, (uint32_t)Q, (long long)cap, d_idx, d_d2);
     });
     if (d_s) ss_param_kernel<<<blocks, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg, (uint32_t)Q, base, d_offsets, (long long)cap, d_idx, d_s);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// ---- free-space polyhedra (segment_polyhedron.hpp): a filter over capsule rows ---------------------------------------------------
+// room for the support positions of rows of up to row_cap entries (grow-only; both forms)
+int poly_ensure_sup(pct_cloud *c, int64_t row_cap)
+{
+    if ((size_t)row_cap <= c->pl_sup.capacity() && c->pl_sup) return PCT_OK;
+    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the polyhedron workspace during graph capture");
+    return c->pl_sup.reserve((size_t)std::max<int64_t>(row_cap, 1));
+}
+
+// the supports of the rows (d_rows[Q + 1], d_row_idx: the capsule search's CSR in PCT_ORDER_DISTANCE, made when d_rows[Q] <= row_cap):
+// filter -> count per row (c->d_count) -> scan (d_offsets[Q + 1]).  Q >= 1, within the reserved batch size; rs_ensure_work and
+// poly_ensure_sup come first.
+int poly_filter_scan(pct_cloud *c, const double *d_seg, int64_t Q, const long long *d_rows, int64_t row_cap, const uint32_t *d_row_idx,
+                     long long *d_offsets, hipStream_t s)
+{
+    poly_filter_kernel<<<(int)Q, 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg, (uint32_t)Q, (uint32_t)c->index_base, d_rows,
+                                              (long long)row_cap, d_row_idx, c->pl_sup, c->d_count);
+    return list_scan(c, Q, d_offsets, 0xFFFFFFFFu, s);       // no row is queued: there is nothing to sort
+}
+
+// ... and the lists behind it, written only when d_offsets[Q] <= cap (tested on the device); every entry of d_offsets becomes -1
+// instead when the rows were never made
+int poly_emit(pct_cloud *c, const double *d_seg, int64_t Q, const long long *d_rows, int64_t row_cap, const uint32_t *d_row_idx,
+              long long *d_offsets, int64_t cap, uint32_t *d_idx, double *d_d2, double *d_s, double *d_plane, hipStream_t s)
+{
+    poly_emit_kernel<<<(int)std::min<int64_t>(Q, 8192), 256, 0, s>>>(c->x, c->y, c->z, (uint32_t)c->count, d_seg, (uint32_t)Q, (uint32_t)c->index_base,
+                                                                    d_rows, (long long)row_cap, d_row_idx, c->pl_sup, d_offsets, (long long)cap, d_idx,
+                                                                    d_d2, d_s, d_plane);
     HIPCHK(hipGetLastError());
     return PCT_OK;
 }
@@ -2734,6 +2776,79 @@ int pct_segment_search_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *id
 {
     if (!c) return fail(PCT_ERR_INVALID, "no capsule-search result to read (none yet, or the cloud changed since)");
     return read_lists(c->ss, first, n, idx, d2, s);
+}
+
+// ---- free-space polyhedra (include/pct_engine.h, "Free-space polyhedra") ---------------------------------------------------------------
+int pct_polyhedron_lds_rows(void) { return kPolyLds; }
+
+int pct_segment_supports_dev(pct_cloud *c, const double *d_seg, int64_t Q, const int64_t *d_row_offsets, int64_t row_cap, const uint32_t *d_row_idx,
+                             int64_t *d_offsets, int64_t cap, uint32_t *d_idx, double *d_d2, double *d_s, double *d_plane, void *stream)
+{
+    if (!c || Q < 0 || row_cap < 0 || cap < 0 || !d_offsets || (Q > 0 && (!d_seg || !d_row_offsets)) || (Q > 0 && row_cap > 0 && !d_row_idx) ||
+        (cap > 0 && !d_idx))
+        return fail(PCT_ERR_INVALID, "bad segment_supports_dev arguments");
+    hipStream_t s = (hipStream_t)stream;
+    if (Q == 0) {
+        HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
+        return PCT_OK;
+    }
+    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    if (row_cap > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "rows of %lld entries, more than 2^32 - 1", (long long)row_cap);
+    PCTCHK(rs_ensure_work(c));
+    PCTCHK(poly_ensure_sup(c, row_cap));
+    PCTCHK(order_after_mutations(c, s));
+    const long long *rows = reinterpret_cast<const long long *>(d_row_offsets);
+    long long *off = reinterpret_cast<long long *>(d_offsets);
+    PCTCHK(poly_filter_scan(c, d_seg, Q, rows, row_cap, d_row_idx, off, s));
+    return poly_emit(c, d_seg, Q, rows, row_cap, d_row_idx, off, cap, d_idx, d_d2, d_s, d_plane, s);
+}
+
+int pct_segment_polyhedron_batch(pct_cloud *c, int algo, const double *seg, const double *reach, int64_t Q, int64_t *offsets, int64_t *total)
+{
+    if (!c || Q < 0 || !offsets || !total || (Q > 0 && (!seg || !reach))) return fail(PCT_ERR_INVALID, "bad segment_polyhedron_batch arguments");
+    PCTCHK(ring_finish_pending(c));
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, Q, &path));
+    c->pl.valid = false;
+    c->pl.total = 0;
+    if (Q > 0) PCTCHK(c->pl_off.reserve((size_t)Q + 1));
+    // the candidate rows in distance order (no s), then -- inside the same step, before the frame's wait -- the filter, the count and
+    // the scan of the supports; the support offsets are the second and last host read
+    std::vector<int64_t> rows((size_t)Q + 1);
+    int64_t row_total = 0;
+    PCTCHK(list_search_host(c, c->pc, "free-space polyhedra", false, Q, rows.data(), &row_total,
+        [&] { return stage_segments(c, seg, reach, Q); },
+        [&] { return ss_count_run(c, path, c->d_seg, c->d_r2, Q, c->d_count, g_stream, [&] { return list_scan(c, Q, c->rs_off, 1u, g_stream); }); },
+        [&]() -> int {
+            PCTCHK(ss_fill_sort(c, path, c->d_seg, c->d_r2, Q, PCT_ORDER_DISTANCE, c->rs_off, row_total, c->pc.idx, c->pc.d2, nullptr, g_stream));
+            PCTCHK(poly_ensure_sup(c, row_total));
+            PCTCHK(poly_filter_scan(c, c->d_seg, Q, c->rs_off, row_total, c->pc.idx, c->pl_off, g_stream));
+            HIPCHK(hipMemcpyAsync(offsets, c->pl_off, sizeof(int64_t) * (Q + 1), hipMemcpyDeviceToHost, g_stream));
+            return PCT_OK;
+        }));
+    if (Q == 0) offsets[0] = 0;
+    *total = offsets[Q];
+    if (*total > 0) {
+        PCTCHK(ensure_lists(c, c->pl, (size_t)*total, true, true));
+        PCTCHK(c->pl_plane.reserve(4 * (size_t)*total, 4 * c->pl.cap));
+        PCTCHK(poly_emit(c, c->d_seg, Q, c->rs_off, row_total, c->pc.idx, c->pl_off, *total, c->pl.idx, c->pl.d2, c->pl.s, c->pl_plane, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+    }
+    c->pl.total = *total;
+    c->pl.valid = true;
+    if (path == Path::Empty && Q > 0) return fail(PCT_ERR_EMPTY, "free-space polyhedra against an empty cloud");
+    return PCT_OK;
+}
+
+int pct_segment_polyhedron_read(pct_cloud *c, int64_t first, int64_t n, uint32_t *idx, double *d2, double *s, double *plane)
+{
+    if (!c) return fail(PCT_ERR_INVALID, "no free-space-polyhedron result to read (none yet, or the cloud changed since)");
+    PCTCHK(read_lists(c->pl, first, n, idx, d2, s));
+    if (plane && n > 0) {
+        HIPCHK(hipMemcpyAsync(plane, c->pl_plane + 4 * first, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, g_stream));
+        HIPCHK(hipStreamSynchronize(g_stream));
+    }
+    return PCT_OK;
 }
 
 // The reach that bounds the capsule inflation's walk.  The contract is unbounded: radius = min(sqrt(d2*) - m, R), d2* the smallest

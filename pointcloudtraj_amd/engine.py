@@ -233,6 +233,11 @@ def lib():
         L.pct_segment_search_batch.argtypes = [vp, i32, f64p, f64p, i64, i32, vp, C.POINTER(i64)]
         L.pct_segment_search_read.argtypes = [vp, i64, i64, u32p, f64p, f64p]
         L.pct_segment_search_batch_dev.argtypes = [vp, i32, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp]
+        L.pct_segment_polyhedron_batch.argtypes = [vp, i32, f64p, f64p, i64, vp, C.POINTER(i64)]
+        L.pct_segment_polyhedron_read.argtypes = [vp, i64, i64, u32p, f64p, f64p, f64p]
+        L.pct_segment_supports_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]
+        L.pct_polyhedron_lds_rows.argtypes = []
+        L.pct_polyhedron_lds_rows.restype = C.c_int
         L.pct_bezier_check.argtypes = [vp, C.POINTER(BezierTraj), C.POINTER(InflateParams), C.c_double, C.c_double, C.c_double,
                                        C.POINTER(i64), C.POINTER(i64), i64, f64p, f64p, f64p, u32p]
         L.pct_nn_batch_dev.argtypes = [vp, i32, vp, i64, vp, vp, vp]
@@ -311,6 +316,11 @@ def init(device: int = 0):
 
 def device_count() -> int:
     return lib().pct_device_count()
+
+
+def polyhedron_lds_rows() -> int:
+    """the longest capsule row the free-space-polyhedron filter keeps in LDS in one piece (pct_polyhedron_lds_rows; needs no GPU)"""
+    return int(lib().pct_polyhedron_lds_rows())
 
 
 def sync():
@@ -784,6 +794,30 @@ class Cloud:
                                            None if s is None else _ptr(s)))
         return idx, d2, s
 
+    def segment_polyhedron(self, segments, reach, algo: int = ALGO_AUTO):
+        """a convex free region around every line segment as half-spaces (pct_segment_polyhedron_batch + pct_segment_polyhedron_read):
+        segments [Q, 6] (a then b) or [Q, 2, 3], reach a scalar or [Q]; (offsets int64 [Q + 1], idx uint32 [total], d2 float64 [total],
+        s float64 [total], planes float64 [total, 4]); row i = the supports of segment i, nearest first; a plane is nh0 nh1 nh2 off and
+        its half-space {y : nh . y <= off}; (0, 0, 0, -1) for a point on the segment (d2 == 0)"""
+        seg = np.ascontiguousarray(segments, np.float64).reshape(-1, 6)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(reach, np.float64), (len(seg),)))
+        offsets = np.zeros(len(seg) + 1, np.int64)
+        total = C.c_int64()
+        _chk(lib().pct_segment_polyhedron_batch(self._h, algo, _ptr(seg), _ptr(r), len(seg), _ptr(offsets), C.byref(total)))
+        idx, d2, s, planes = self.segment_polyhedron_read(0, total.value)
+        return offsets, idx, d2, s, planes
+
+    def segment_polyhedron_read(self, first: int, n: int, want_idx: bool = True, want_d2: bool = True, want_s: bool = True, want_planes: bool = True):
+        """entries [first, first + n) of the last segment_polyhedron on this cloud (pct_segment_polyhedron_read): (idx, d2, s, planes
+        [n, 4]), None where not wanted"""
+        m = max(int(n), 0)
+        idx = np.empty(m, np.uint32) if want_idx else None
+        d2 = np.empty(m, np.float64) if want_d2 else None
+        s = np.empty(m, np.float64) if want_s else None
+        planes = np.empty((m, 4), np.float64) if want_planes else None
+        _chk(lib().pct_segment_polyhedron_read(self._h, int(first), int(n), *(None if a is None else _ptr(a) for a in (idx, d2, s, planes))))
+        return idx, d2, s, planes
+
     def bezier_check(self, params: InflateParams, polycoef, seg_time, orders, t_start, stop_time, dt=0.02, cap=4096):
         coef = np.ascontiguousarray(polycoef, np.float64)
         st = np.ascontiguousarray(seg_time, np.float64)
@@ -872,6 +906,14 @@ class Cloud:
         offsets[Q] <= cap; reserve_queries(Q) first"""
         _chk(lib().pct_segment_search_batch_dev(self._h, algo, seg_ptr, reach_ptr, int(Q), int(order), offsets_ptr, int(cap), idx_ptr or None,
                                                 d2_ptr or None, s_ptr or None, stream))
+
+    def segment_supports_device(self, seg_ptr: int, Q: int, row_offsets_ptr: int, row_cap: int, row_idx_ptr: int, offsets_ptr: int, cap: int,
+                                idx_ptr: int, d2_ptr: int, s_ptr: int, plane_ptr: int, stream: int = 0):
+        """pct_segment_supports_dev: the supports of rows made by segment_search_device(ORDER_DISTANCE) with cap = row_cap; offsets int64
+        [Q + 1] always written (all -1 when the rows did not fit row_cap), idx / d2 / s / plane (the last three may be 0) only when
+        offsets[Q] <= cap; reserve_queries(Q) first"""
+        _chk(lib().pct_segment_supports_dev(self._h, seg_ptr, int(Q), row_offsets_ptr, int(row_cap), row_idx_ptr or None, offsets_ptr, int(cap),
+                                            idx_ptr or None, d2_ptr or None, s_ptr or None, plane_ptr or None, stream))
 
     def inflate_device(self, params: InflateParams, pts_ptr: int, Q: int, radius_ptr: int, idx_ptr: int = 0, d2_ptr: int = 0, stream: int = 0):
         _chk(lib().pct_inflate_batch_dev(self._h, C.byref(params), pts_ptr, int(Q), radius_ptr, idx_ptr or None, d2_ptr or None, stream))
