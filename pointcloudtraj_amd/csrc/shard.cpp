@@ -305,16 +305,21 @@ void local_histogram(const unsigned char *pts, int64_t n, int64_t stride, const 
 {
     for (int b = 0; b < kRouteBins; b++) h[b] = 0.0;
     const double w = (Y.hi_edge - Y.lo) / kRouteBins;
+    if (!(w > 0.0)) {                              // a cloud without extent along its longest axis (all points identical: hi_edge rounds to lo): one bin
+        h[0] = (double)n;
+        return;
+    }
     for (int64_t i = 0; i < n; i++) {
         const double x = (double)reinterpret_cast<const float *>(pts + i * stride)[Y.axis];
-        const int b = std::max(0, std::min(kRouteBins - 1, (int)std::floor((x - Y.lo) / w)));
+        const double t = std::floor((x - Y.lo) / w);                                  // finite: lo <= x <= hi, w > 0
+        const int b = t >= (double)(kRouteBins - 1) ? kRouteBins - 1 : t > 0.0 ? (int)t : 0;     // clamped BEFORE the conversion
         h[b] += 1.0;
     }
 }
 
 void cuts_from(const Layout &Y, const double *h, int world, double *cuts)
 {
-    const double w = (Y.hi_edge - Y.lo) / kRouteBins;
+    const double w = (Y.hi_edge - Y.lo) / kRouteBins;                 // 0 for a zero-width layout: every cut then sits at lo
     std::vector<double> cum(kRouteBins);
     double acc = 0;
     for (int b = 0; b < kRouteBins; b++) { acc += h[b]; cum[b] = acc; }
@@ -424,7 +429,7 @@ int phase_second_finish(pct_route *r, uint32_t *d_idx, double *d_d2, hipStream_t
 // ---- partitioned batches: phases per rank (the exchanges between them are RCCL's or plain copies, see the entry points) ----
 int part_reserve_send(pct_route *r, int64_t Q)
 {
-    if (Q <= r->pq_cap) return PCT_OK;
+    if (r->pq_cap > 0 && Q <= r->pq_cap) return PCT_OK;      // a first batch of NO queries still needs the counters and the flag word
     HIPCHK(hipDeviceSynchronize());
     r->pq_cap = 0;
     const int64_t n = std::max<int64_t>(Q, 256);
