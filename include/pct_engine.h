@@ -20,6 +20,8 @@
  *   pct_bezier_check        checkSafeTrajectory/getPosFromBezier  Planner/src/sim_planning_demo.cpp:715-781
  *   pct_bezier_check_batch  the same check for a set of candidate trajectories over one map in one call (the loop a caller of
  *                           checkSafeTrajectory would write around its candidates; variants as in Planner/src/traj_postprocessing.cpp)
+ *   pct_bezier_certify_batch  the same question answered for every point of the curves, not for samples of them (no reference
+ *                           counterpart: checkSafeTrajectory only samples)
  *   pct_cloud_ring_index +  the per-frame rebuild of the search tree: rcvPointCloudCallBack -> setInput
  *   pct_cloud_append_aos    Planner/src/sim_planning_demo.cpp:159-167 -> Planner/src/corridor_finder.cpp:93-99 (rolling map, config C5)
  *   pct_ctrl_points_check   the containment the optimizer enforces on the control points, Planner/src/traj_optimizer.cpp:624-648,
@@ -418,6 +420,61 @@
  * pct_cloud_reserve_queries; reserve the batch size first).  pct_polyhedron_lds_rows() is the longest row the filter keeps in LDS
  * in one piece; longer rows are served in windows of that length, with the same bytes.
  *
+ * Certified Bezier check (pct_bezier_certify_batch*): whole trajectories proven free, or shown to collide, by subdivision instead of
+ * sampling -- the verdict does not depend on a dt or on the speed, and the work grows with how close a curve comes to the obstacles,
+ * not with its length.  A Bezier piece lies in the convex hull of its control points, hence in a capsule around its chord: if that
+ * capsule holds no row of the window the whole piece is free; if an end of the piece is within the margin the curve collides there;
+ * otherwise the piece is cut in half by de Casteljau and both halves are asked again.  Input: a pct_bezier_batch as the batched check
+ * takes it -- t_start is NOT read: whole trajectories are certified, and a caller who wants a horizon passes the segments that cover
+ * it through seg_offsets -- with margin (finite, >= 0), max_depth (0..20), piece_cap and algo.  All arithmetic is fp64, one rounding
+ * per operation, no contraction, in the order given here.  (1) World control points of a segment of order n:
+ * P[j][k] = polycoef[row][k*(n+1) + j] * seg_time[row], the point pct_ctrl_points_check names.  A trajectory is INVALID, with nothing
+ * else examined, if any of its seg_time is not finite or not > 0, or if any |P[j][k]| is not <= FLT_MAX; an INVALID trajectory is
+ * never FREE (its depth and pieces are 0, its hit fields and min_d2 those of "no hit").  (2) A piece is a control polygon P[0..n], a
+ * segment number, a depth d and a position k; it stands for u in [k/2^d, (k+1)/2^d]; the first pieces are the segments themselves
+ * (d = 0).  (3) Halving: level by level q[i] = (p[i] + p[i+1]) * 0.5; the left child (position 2k) takes the first point of every
+ * level, the right child (2k + 1) the last point of every level, reversed.  (4) Geometry of a piece: a = (double)(float)P[0] and
+ * b = (double)(float)P[n]; rho2 = the maximum over j = 0..n of the d2 of "Segment queries" for segment (a, b) with the row replaced
+ * by the fp64 point P[j]; rho = sqrt(rho2); cmax = max |P[j][k]|; reach = ((margin + rho) * (1 + 2^-20)) + cmax * 2^-40.  The piece
+ * is BLOCKED iff segment (a, b) has a candidate under reach in the sense of "Segment queries" -- its capsule count is non-zero.  An
+ * end x of {a, b} is a HIT iff sqrt(d2) - margin < 0 with d2 the nearest-neighbour d2 of the fp32 point x: the collision test of
+ * pct_bezier_check for a sample at that point, without the start-distance early-out.  (5) Rounds: in round r every live piece (all
+ * of depth r) is examined.  A trajectory with a hit in this round becomes HIT and is retired; it reports the hit with the lowest
+ * (segment, u), u = k/2^d for a and (k+1)/2^d for b, with the nearest point's index and d2.  Of the remaining pieces an unblocked one
+ * is done; a blocked one at d == max_depth makes its trajectory UNDECIDED; the other blocked pieces split -- unless twice their number
+ * exceeds piece_cap: then nothing splits in this round, every trajectory that owns one of them becomes UNDECIDED and the call's
+ * "capped" flag is set.  A trajectory with no live piece left and no other verdict is FREE.  Output per trajectory: struct
+ * pct_traj_certificate (48 bytes, below); without a hit the hit fields are -1, PCT_NO_INDEX, NaN and +inf; min_d2 is the smallest end
+ * d2 examined (+inf when none), an upper bound on the squared clearance; depth is the deepest level examined, pieces the pieces
+ * examined (a HIT trajectory counts every piece of its last round).  Output per call: optional stats[3] = {rounds that examined a
+ * piece, pieces examined, capped flag}.  What FREE means: no row of the window lies within margin of ANY point of the trajectory.
+ * The argument (it stands, with its roundings, beside the kernels in csrc/bezier_certify.hpp): the distance to a segment is a convex
+ * function, so every point of a piece is within rho of its chord; a row within margin of the curve is therefore a candidate under
+ * margin + rho; the two slack terms of reach cover the roundings of rho, of reach * reach and of d2 unconditionally, and the inherited
+ * roundings of the halvings -- at most 2^-45 of the largest |world control coordinate| M0 of the segment -- whenever
+ * margin + rho >= 2^-25 * M0 (30 micrometres per kilometre of coordinate) or the piece's own cmax >= M0 / 16; a margin below that on
+ * a piece far nearer the origin than its curve reaches is the one case the slack does not provably cover.  The check is conservative
+ * by that slack: a point one fp32 ulp outside the margin of a straight line is UNDECIDED, not FREE.  HIT means what it means for the
+ * sampled check: a point of the curve (an end of a piece) whose nearest row is nearer than margin.  Paths: algo follows the capsule
+ * count's rules (PCT_ALGO_AUTO, _STREAM, _GRID, _RING; anything else, GRID without a grid and RING without a live index are
+ * PCT_ERR_INVALID) for the chord test; the end test goes through the nearest-neighbour path of the same index (the table, the grid,
+ * the streaming kernels); all forms give the same bytes.  Empty cloud: every valid trajectory is FREE at depth 0 (pieces = its
+ * segments, min_d2 = +inf), PCT_OK in both forms, as for the batched check.  PCT_ERR_INVALID with nothing written: a NULL required
+ * pointer, B < 0, a margin that is not finite or < 0, max_depth outside 0..20, piece_cap below the number of segments (host form) or
+ * below 1 or above 2^24, and in the host form the batched check's own refusals (seg_offsets not starting at 0 or not strictly
+ * ascending, an order outside 0..12, a row_stride below 3 * (order + 1)).  B == 0: PCT_OK (stats, when given, are zeros).  Rolling
+ * map: the host form finishes an append in flight first, and the overflow-queue overrun paragraph applies to it.  Host form: it reads
+ * the live count once per round, sizes its launches and its piece buffers by it and stops at zero.  Device form: asynchronous on
+ * `stream`, waits for nothing and can be captured on a cloud with a cell index or a live rolling-map index (under capture the
+ * streaming path and an empty cloud are PCT_ERR_INVALID, like the streaming k-NN kernel: its counts rely on a memset that a replayed
+ * graph was seen not to honour); the struct is read on the host, its pointers are device memory; it runs
+ * max_depth + 1 rounds over piece_cap slots with device-side counts, dead slots posing queries the searches answer without a walk;
+ * the caller reserves 2 * piece_cap queries first (pct_cloud_reserve_queries); the piece buffers (328 B per piece, two sets) and the
+ * per-trajectory state are cloud-owned and grown by the call, which is refused during graph capture (call once with the same sizes
+ * before capturing).  It cannot see the data: a trajectory whose segment range is empty, descending or outside [0, seg_offsets[B]],
+ * that has an order outside 0..12 or a row too short for it is INVALID and none of its rows is read; when seg_offsets[B] exceeds
+ * piece_cap nothing is examined, every sound trajectory is UNDECIDED and the capped flag is set.
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -799,6 +856,29 @@ int pct_bezier_check_batch(pct_cloud *c, const pct_bezier_batch *batch, const pc
                            int64_t *offsets /* B + 1, may be NULL */, int64_t list_cap,
                            double *pos, double *radius, double *d2, uint32_t *idx /* list_cap entries each (pos x3), any may be NULL */);
 
+/* Certified Bezier check (contract: top of this file, "Certified Bezier check"): B trajectories proven free or shown to collide by
+ * subdivision.  Host pointers in the host form, device pointers (the struct itself on the host) in the device form. */
+enum pct_cert_status {
+    PCT_CERT_FREE = 0,        /* no row of the window within margin of any point of the trajectory */
+    PCT_CERT_HIT = 1,         /* an end of a piece is nearer than margin to its nearest row */
+    PCT_CERT_UNDECIDED = 2,   /* a blocked piece at max_depth, or splits refused by piece_cap */
+    PCT_CERT_INVALID = 3      /* a seg_time not finite or not > 0, a world control point beyond FLT_MAX (device form: an unsound range, order or row) */
+};
+
+typedef struct pct_traj_certificate {   /* 48 bytes */
+    int32_t  status;      /* enum pct_cert_status */
+    int32_t  depth;       /* deepest level examined */
+    int32_t  hit_seg;     /* segment of the reported hit (an index into the packed batch), -1 = none */
+    uint32_t hit_idx;     /* nearest point's index at the reported hit, PCT_NO_INDEX = none */
+    double   hit_u;       /* parameter u of the reported hit inside hit_seg, NaN = none */
+    double   hit_d2;      /* d2 of the reported hit, +inf = none */
+    double   min_d2;      /* smallest end d2 examined, +inf when none: an upper bound on the squared clearance */
+    int64_t  pieces;      /* pieces examined */
+} pct_traj_certificate;
+
+int pct_bezier_certify_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double margin, int32_t max_depth, int64_t piece_cap,
+                             pct_traj_certificate *cert /* B */, int64_t stats[3] /* {rounds, pieces, capped}; may be NULL */);
+
 /* Control-point check (SURVEY.md 3.3, config C5's build extension): the threshold test of checkTrajPtCol
  * (Planner/src/corridor_finder.cpp:412-416) applied to the raw control points of the committed trajectory in world units --
  * control point j of segment i is polycoef[i][d*(n+1)+j] * seg_time[i] (layout Planner/src/traj_optimizer.cpp:739-751), the
@@ -847,6 +927,11 @@ int pct_bezier_check_batch_dev(pct_cloud *c, const pct_bezier_batch *d_batch_fie
                                const pct_inflate_params *p, double stop_time, double dt, int64_t cap, pct_traj_verdict *d_verdict,
                                int64_t *d_offsets /* B + 1, required */, int64_t list_cap,
                                double *d_pos, double *d_radius, double *d_d2, uint32_t *d_idx, void *stream);
+/* pct_bezier_certify_batch on device buffers: d_cert[B] required, d_stats[3] may be NULL.  Reserve 2 * piece_cap queries first
+ * (pct_cloud_reserve_queries).  Asynchronous on `stream`; can be captured once the piece buffers have their size. */
+int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields /* struct on the host, its pointers on the device */,
+                                 double margin, int32_t max_depth, int64_t piece_cap, pct_traj_certificate *d_cert, int64_t *d_stats,
+                                 void *stream);
 /* Exchange step of a sharded cloud (one process per GPU): between all_reduce(min) on the squared distances and all_reduce(min) on
  * the indices, a rank offers its global index only where its own d2 equals the reduced minimum (and is finite), INT32_MAX
  * elsewhere -- so the second reduction returns the lowest global index among the ranks that tie.  Device pointers, async on

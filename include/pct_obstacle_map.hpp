@@ -459,6 +459,40 @@ public:
         return colliding;
     }
 
+    // The certified check (pct_engine.h, paragraph "Certified Bezier check"): whole candidates proven free of the map by
+    // search_margin (setParam) or shown to collide, by subdivision -- no dt, no sampling gap, and the work follows how close a curve
+    // comes to the obstacles.  candidates.t_start is not read: a horizon is the segments that cover it.  certificates[b].status is
+    // PCT_CERT_FREE (a proof), PCT_CERT_HIT (hit_seg / hit_u / hit_idx say where and against which point), PCT_CERT_UNDECIDED (closer
+    // than max_depth halvings could tell: treat as not free) or PCT_CERT_INVALID.  piece_cap 0: 64 pieces per segment, at least 4096.
+    // stats (optional): {rounds, pieces examined, capped}.  Returns the number of candidates that are NOT certified free.
+    int64_t certifyTrajectories(const pct_bezier_batch &candidates, std::vector<pct_traj_certificate> &certificates, int max_depth = 12,
+                                int64_t piece_cap = 0, int64_t *stats = nullptr)
+    {
+        const int64_t B = candidates.B > 0 ? candidates.B : 0;
+        certificates.resize((size_t)B);
+        if (piece_cap <= 0) {
+            const int64_t nseg = B > 0 && candidates.seg_offsets ? candidates.seg_offsets[B] : 0;
+            piece_cap = 64 * nseg > 4096 ? 64 * nseg : 4096;
+        }
+        check(pct_bezier_certify_batch(cloud_, PCT_ALGO_AUTO, &candidates, prm_.search_margin, max_depth, piece_cap, certificates.data(), stats),
+              "pct_bezier_certify_batch");
+        int64_t not_free = 0;
+        for (const pct_traj_certificate &v : certificates) not_free += v.status != PCT_CERT_FREE ? 1 : 0;
+        return not_free;
+    }
+    // One trajectory, the arguments of checkSafeTrajectory without its times: true unless the whole trajectory is certified free
+    // (the reference's sense: true = do not fly it).  certificate (optional) receives the details.
+    bool certifySafeTrajectory(const double *poly_coeff, int64_t row_stride, const double *seg_time, const int32_t *orders,
+                               int32_t segment_num, pct_traj_certificate *certificate = nullptr, int max_depth = 12)
+    {
+        const int32_t seg_offsets[2] = { 0, segment_num };
+        const pct_bezier_batch one{ poly_coeff, row_stride, seg_time, orders, seg_offsets, nullptr, 1 };
+        std::vector<pct_traj_certificate> cert;
+        const int64_t not_free = certifyTrajectories(one, cert, max_depth);
+        if (certificate) *certificate = cert[0];
+        return not_free != 0;
+    }
+
     // SURVEY 3.3 (config C5's build extension): the same threshold test on the raw control points of the committed trajectory
     // (control point j of segment i = poly_coeff[i][d*(n+1)+j] * T_i, the point traj_optimizer.cpp:624-648 keeps inside sphere i)
     bool checkControlPoints(const double *poly_coeff, int64_t row_stride, const double *seg_time, const int32_t *orders,

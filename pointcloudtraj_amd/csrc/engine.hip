@@ -44,6 +44,7 @@
 #include "segment.hpp"
 #include "segment_search.hpp"
 #include "segment_polyhedron.hpp"
+#include "bezier_certify.hpp"
 
 using namespace pct;
 using pct_host::pow2_at_least;
@@ -314,6 +315,16 @@ struct pct_cloud {
     DevBuf<double> bb_tstart;
     DevBuf<long long> bb_off;
     DevBuf<pct_traj_verdict> bb_verdict;
+    // certified Bezier check (bezier_certify.hpp): two sets of pieces (polygon + meta, 328 B per piece) that the rounds write in turn,
+    // the split flags and tile sums of a round, the per-trajectory state, the control words, and the host form's certificates and
+    // stats (all grow-only)
+    DevBuf<double> bc_poly[2];
+    DevBuf<BcMeta> bc_meta[2];
+    DevBuf<uint32_t> bc_flag, bc_tile;
+    DevBuf<BcTraj> bc_traj;
+    DevBuf<BcCtl> bc_ctl;
+    DevBuf<pct_traj_certificate> bc_cert;
+    DevBuf<long long> bc_stats;
     // measurement
     hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the whole batch (all kernels of one query call)
     hipEvent_t ev2 = nullptr, ev3 = nullptr;    // around the batch's dominant kernel only (aliases of the ring's current pair)
@@ -2076,6 +2087,107 @@ int segment_batch_host(pct_cloud *c, int algo, SegMeasure measure, const double 
                              [&] { return segment_run(c, path, measure, c->d_seg, c->d_r2, 0.0, Q, c->d_idx, c->d_d2, d_s, g_stream); });
 }
 
+// ---- the certified Bezier check (bezier_certify.hpp; contract: pct_engine.h, "Certified Bezier check"): its rooms and its rounds ----
+// what a call certifies and where its answers go
+struct BcRun {
+    BcDesc D;
+    double margin;
+    int max_depth;
+    int64_t piece_cap;
+    Path path;                       // of the chord test: resolve_algo(Op::Capsule)
+    pct_traj_certificate *cert;      // device memory, B entries
+    long long *stats;                // device memory, 3 entries, or NULL
+};
+
+// a cloud-owned buffer of the check is about to grow: refused while a graph is captured, and nothing may still read the old block
+int bc_may_grow(pct_cloud *c, hipStream_t s)
+{
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (c->capturing || (hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone))
+        return fail(PCT_ERR_INVALID, "cannot grow the piece buffers during graph capture (call once with these sizes before capturing)");
+    HIPCHK(hipDeviceSynchronize());
+    return PCT_OK;
+}
+
+template <typename T>
+int bc_reserve(pct_cloud *c, DevBuf<T> &buf, size_t need, hipStream_t s)
+{
+    if (need <= buf.capacity() && buf) return PCT_OK;
+    PCTCHK(bc_may_grow(c, s));
+    return buf.reserve(pow2_at_least<size_t>(256, need));
+}
+
+// room for `pieces` pieces in set `side`
+int bc_room(pct_cloud *c, int side, int64_t pieces, hipStream_t s)
+{
+    PCTCHK(bc_reserve(c, c->bc_poly[side], (size_t)pieces * kBcPoly, s));
+    return bc_reserve(c, c->bc_meta[side], (size_t)pieces, s);
+}
+
+// room for a round over nslots slots: its flags and tile sums
+int bc_round_room(pct_cloud *c, int64_t nslots, hipStream_t s)
+{
+    PCTCHK(bc_reserve(c, c->bc_flag, (size_t)nslots, s));
+    return bc_reserve(c, c->bc_tile, (size_t)ceil_div(nslots, kBcTile) + 1, s);
+}
+
+// room for the state of B trajectories and the control words
+int bc_traj_room(pct_cloud *c, int64_t B, hipStream_t s)
+{
+    PCTCHK(bc_reserve(c, c->bc_traj, (size_t)B, s));
+    return bc_reserve(c, c->bc_ctl, 1, s);
+}
+
+// defaults, validity and the pieces of depth 0 in set 0; seg_lanes: the segments (the host form) or piece_cap (the device form, whose
+// lanes guard on seg_offsets[B])
+int bc_seed(pct_cloud *c, const BcRun &R, int64_t seg_lanes, hipStream_t s)
+{
+    bc_init_kernel<<<ceil_div(R.D.B + 1, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, R.cert, c->bc_traj, c->bc_ctl);
+    if (seg_lanes > 0) {
+        bc_valid_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, c->bc_traj);
+        bc_seed_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, c->bc_traj, c->bc_poly[0], c->bc_meta[0]);
+    }
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// One round over the first nslots slots of set (round & 1): the queries into the cloud's workspaces (segments in d_seg, reaches in
+// d_r2, the 2 * nslots ends in d_q; 2 * nslots <= c->qcap), the capsule count and the nearest-neighbour batch on the index of R.path,
+// then classification, compaction and the halving into the other set.
+int bc_round(pct_cloud *c, const BcRun &R, int round, int64_t nslots, hipStream_t s)
+{
+    const int cur = round & 1;
+    const uint32_t n = (uint32_t)nslots;
+    bc_geometry_kernel<<<ceil_div(nslots, 256), 256, 0, s>>>(c->bc_poly[cur], c->bc_meta[cur], c->bc_ctl, n, R.margin, c->d_seg, c->d_r2, c->d_q);
+    HIPCHK(hipGetLastError());
+    PCTCHK(ss_count_run(c, R.path, c->d_seg, c->d_r2, nslots, c->d_count, s, no_step));
+    Path nn = Path::Empty;
+    if (R.path != Path::Empty)
+        PCTCHK(resolve_algo(c, Op::NN, R.path == Path::Table ? PCT_ALGO_RING : R.path == Path::Grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM, 2 * nslots, &nn));
+    PCTCHK(nn_run(c, nn, c->d_q, 2 * nslots, c->d_idx, c->d_d2, s));
+    bc_classify_kernel<<<ceil_div(nslots, 256), 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, R.margin, round, c->d_count, c->d_d2, R.cert, c->bc_traj, c->bc_flag);
+    const int ntiles = ceil_div(nslots, kBcTile);
+    bc_mark_kernel<<<ntiles, kBcTile, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, round, R.max_depth, c->d_idx, c->d_d2, R.cert, c->bc_traj, c->bc_flag, c->bc_tile);
+    scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->bc_tile, (uint32_t)ntiles, BcScanDone{ c->bc_ctl, (uint32_t)R.piece_cap });
+    if (round < R.max_depth)
+        bc_split_kernel<<<ceil_div(2 * nslots, 256), 256, 0, s>>>(c->bc_poly[cur], c->bc_meta[cur], c->bc_poly[cur ^ 1], c->bc_meta[cur ^ 1], c->bc_flag, c->bc_tile,
+                                                                 c->bc_ctl, n, c->bc_traj);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+int bc_finish(pct_cloud *c, const BcRun &R, hipStream_t s)
+{
+    bc_finish_kernel<<<ceil_div(std::max<int64_t>(R.D.B, 1), 256), 256, 0, s>>>(R.D.B, c->bc_traj, c->bc_ctl, R.cert, R.stats);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+bool bc_bad_scalars(double margin, int32_t max_depth, int64_t piece_cap)
+{
+    return !(margin >= 0.0) || !std::isfinite(margin) || max_depth < 0 || max_depth > kBcMaxDepth || piece_cap < 1 || piece_cap > kBcMaxPieces;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3202,6 +3314,106 @@ int pct_bezier_check_batch_dev(pct_cloud *c, const pct_bezier_batch *d_batch_fie
         HIPCHK(hipGetLastError());
     }
     return PCT_OK;
+}
+
+// ---- the certified Bezier check (bezier_certify.hpp; contract: pct_engine.h, "Certified Bezier check") ---------------------------
+int pct_bezier_certify_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double margin, int32_t max_depth, int64_t piece_cap,
+                             pct_traj_certificate *cert, int64_t stats[3])
+{
+    if (!c || !batch || batch->B < 0 || batch->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad bezier_certify_batch arguments");
+    if (bc_bad_scalars(margin, max_depth, piece_cap))
+        return fail(PCT_ERR_INVALID, "bezier_certify_batch: margin %g, max_depth %d or piece_cap %lld out of range", margin, (int)max_depth, (long long)piece_cap);
+    const int64_t B = batch->B;
+    if (B > 0 && (!batch->polycoef || !batch->seg_time || !batch->orders || !batch->seg_offsets || !cert))
+        return fail(PCT_ERR_INVALID, "bad bezier_certify_batch arguments: a null array");
+    if (B > 0 && batch->seg_offsets[0] != 0) return fail(PCT_ERR_INVALID, "bezier_certify_batch: seg_offsets[0] = %d, not 0", (int)batch->seg_offsets[0]);
+    for (int64_t b = 0; b < B; b++) {
+        const int32_t s0 = batch->seg_offsets[b], s1 = batch->seg_offsets[b + 1];
+        if (s1 <= s0) return fail(PCT_ERR_INVALID, "bezier_certify_batch: seg_offsets not strictly ascending at trajectory %lld", (long long)b);
+        for (int32_t i = s0; i < s1; i++) {
+            const int32_t o = batch->orders[i];
+            if (o < 0 || o > kMaxBezierOrder || 3 * (int64_t)(o + 1) > batch->row_stride)
+                return fail(PCT_ERR_INVALID, "bezier_certify_batch: segment %d: order %d unsupported", (int)i, (int)o);
+        }
+    }
+    const int64_t total_seg = B > 0 ? batch->seg_offsets[B] : 0;
+    if (piece_cap < total_seg)
+        return fail(PCT_ERR_INVALID, "bezier_certify_batch: piece_cap %lld is below the %lld segments", (long long)piece_cap, (long long)total_seg);
+    PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, total_seg, &path));
+    if (B == 0) {
+        if (stats) stats[0] = stats[1] = stats[2] = 0;
+        return PCT_OK;
+    }
+    hipStream_t s = g_stream;
+    const pct_bezier_traj all{ batch->polycoef, batch->row_stride, batch->seg_time, batch->orders, (int32_t)total_seg };
+    PCTCHK(bezier_stage_coef(c, &all, s, false));
+    PCTCHK(bc_reserve(c, c->bb_segoff, (size_t)B + 1, s));
+    PCTCHK(bc_reserve(c, c->bc_cert, (size_t)B, s));
+    PCTCHK(bc_reserve(c, c->bc_stats, 3, s));
+    PCTCHK(bc_traj_room(c, B, s));
+    HIPCHK(hipMemcpyAsync(c->bb_segoff, batch->seg_offsets, sizeof(int32_t) * (B + 1), hipMemcpyHostToDevice, s));
+    const BcRun R{ BcDesc{ c->d_coef, (long long)batch->row_stride, c->d_segtime, c->d_orders, c->bb_segoff, (long long)B }, margin, (int)max_depth, piece_cap, path,
+                   c->bc_cert, c->bc_stats };
+    return ask_twice_after_overrun(c, [&]() -> int {
+        PCTCHK(bc_room(c, 0, total_seg, s));
+        PCTCHK(bc_seed(c, R, total_seg, s));
+        int64_t live = total_seg;
+        for (int round = 0; round <= R.max_depth && live > 0; round++) {
+            // the children of this round's pieces number at most 2 * live and at most piece_cap
+            PCTCHK(bc_room(c, (round & 1) ^ 1, std::min<int64_t>(2 * live, piece_cap), s));
+            PCTCHK(bc_round_room(c, live, s));
+            PCTCHK(pct_cloud_reserve_queries(c, 2 * live));
+            PCTCHK(bc_round(c, R, round, live, s));
+            BcCtl h{};
+            HIPCHK(hipMemcpyAsync(&h, c->bc_ctl, sizeof(BcCtl), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));     // the round's one host read: the live count sizes the next round
+            live = h.live;
+        }
+        PCTCHK(bc_finish(c, R, s));
+        HIPCHK(hipMemcpyAsync(cert, c->bc_cert, sizeof(pct_traj_certificate) * B, hipMemcpyDeviceToHost, s));
+        if (stats) HIPCHK(hipMemcpyAsync(stats, c->bc_stats, sizeof(int64_t) * 3, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return PCT_OK;
+    });
+}
+
+int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, double margin, int32_t max_depth, int64_t piece_cap,
+                                 pct_traj_certificate *d_cert, int64_t *d_stats, void *stream)
+{
+    const pct_bezier_batch *bt = d_batch_fields;
+    if (!c || !bt || bt->B < 0 || bt->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad bezier_certify_batch_dev arguments");
+    if (bc_bad_scalars(margin, max_depth, piece_cap))
+        return fail(PCT_ERR_INVALID, "bezier_certify_batch_dev: margin %g, max_depth %d or piece_cap %lld out of range", margin, (int)max_depth, (long long)piece_cap);
+    if (bt->B > 0 && (!bt->polycoef || !bt->seg_time || !bt->orders || !bt->seg_offsets || !d_cert))
+        return fail(PCT_ERR_INVALID, "bad bezier_certify_batch_dev arguments: a null array");
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, piece_cap, &path));
+    hipStream_t s = (hipStream_t)stream;
+    if (bt->B == 0) {
+        if (d_stats) HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 3, s));
+        return PCT_OK;
+    }
+    // Under capture only the two index paths are served.  The streaming capsule count adds into counts that a memset in front of it
+    // clears, and a captured graph was seen to replay that memset without effect (counts piling up from replay to replay, DESIGN.md
+    // section 4); the index forms store their counts.  The streaming k-NN kernel is refused under capture in the same way.
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    if ((path == Path::Stream || path == Path::Empty) && (c->capturing || (hipStreamIsCapturing(s, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone)))
+        return fail(PCT_ERR_INVALID, "bezier_certify_batch_dev: during graph capture the cloud needs its cell index or its rolling-map index");
+    if (2 * piece_cap > c->qcap)
+        return fail(PCT_ERR_INVALID, "2 * piece_cap = %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)(2 * piece_cap), (long long)c->qcap);
+    PCTCHK(bc_room(c, 0, piece_cap, s));
+    PCTCHK(bc_room(c, 1, piece_cap, s));
+    PCTCHK(bc_round_room(c, piece_cap, s));
+    PCTCHK(bc_traj_room(c, bt->B, s));
+    PCTCHK(order_after_mutations(c, s));
+    const BcRun R{ BcDesc{ bt->polycoef, (long long)bt->row_stride, bt->seg_time, bt->orders, bt->seg_offsets, (long long)bt->B }, margin, (int)max_depth, piece_cap,
+                   path, d_cert, reinterpret_cast<long long *>(d_stats) };
+    PCTCHK(bc_seed(c, R, piece_cap, s));
+    // the live count stays on the device: every round is sized by piece_cap and every lane guards on it
+    for (int round = 0; round <= R.max_depth; round++) PCTCHK(bc_round(c, R, round, piece_cap, s));
+    return bc_finish(c, R, s);
 }
 
 // ---- hipGraph plan -----------------------------------------------------------------------

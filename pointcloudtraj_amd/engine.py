@@ -62,6 +62,11 @@ class TrajVerdict(C.Structure):
 
 VERDICT_DTYPE = np.dtype([("nsamples", np.int64), ("first_hit", np.int64), ("min_sample", np.int64), ("min_radius", np.float64)])
 
+CERT_FREE, CERT_HIT, CERT_UNDECIDED, CERT_INVALID = 0, 1, 2, 3      # enum pct_cert_status
+# pct_traj_certificate, 48 bytes (include/pct_engine.h, paragraph "Certified Bezier check")
+CERT_DTYPE = np.dtype([("status", np.int32), ("depth", np.int32), ("hit_seg", np.int32), ("hit_idx", np.uint32), ("hit_u", np.float64),
+                       ("hit_d2", np.float64), ("min_d2", np.float64), ("pieces", np.int64)])
+
 
 def pack_trajectories(trajectories, t_start=None):
     """A list of (polycoef, seg_time, orders) -> (BezierBatch, arrays): the rows one after another, padded with zeros to a common
@@ -248,6 +253,8 @@ def lib():
                                              f64p, f64p, f64p, u32p]
         L.pct_bezier_check_batch_dev.argtypes = [vp, C.POINTER(BezierBatch), C.POINTER(InflateParams), C.c_double, C.c_double, i64, vp, vp, i64,
                                                  vp, vp, vp, vp, vp]
+        L.pct_bezier_certify_batch.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, i32, i64, vp, vp]
+        L.pct_bezier_certify_batch_dev.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, i32, i64, vp, vp, vp]
         L.pct_radius_count_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp]
         L.pct_cloud_reserve_queries.argtypes = [vp, i64]
         L.pct_plan_create_nn.argtypes = [vp, i32, i64, C.POINTER(vp)]
@@ -867,6 +874,24 @@ class Cloud:
             res.update(out)
         return res
 
+    def bezier_certify(self, trajectories, margin, max_depth=12, piece_cap=None, algo: int = ALGO_AUTO):
+        """pct_bezier_certify_batch: whole trajectories proven free of the cloud by `margin`, or shown to collide, by subdivision -- no
+        dt.  trajectories: a list of (polycoef, seg_time, orders), or a packed (BezierBatch, arrays) pair from engine.pack_trajectories
+        (t_start is not read).  piece_cap: the most pieces a round may hold (None: 64 per segment, at least 4096).  Returns
+        (certificates, stats): a structured array of engine.CERT_DTYPE, one entry per trajectory -- status (CERT_FREE, CERT_HIT,
+        CERT_UNDECIDED, CERT_INVALID), depth, hit_seg, hit_idx, hit_u, hit_d2, min_d2, pieces -- and
+        dict(rounds, pieces, capped)."""
+        packed = isinstance(trajectories, tuple) and len(trajectories) == 2 and isinstance(trajectories[0], BezierBatch)
+        batch, keep = trajectories if packed else pack_trajectories(trajectories)
+        B = int(batch.B)
+        if piece_cap is None:
+            piece_cap = max(4096, 64 * len(keep["seg_time"]))
+        cert = np.zeros(B, CERT_DTYPE)
+        stats = np.zeros(3, np.int64)
+        _chk(lib().pct_bezier_certify_batch(self._h, algo, C.byref(batch), float(margin), int(max_depth), int(piece_cap), _ptr(cert), _ptr(stats)))
+        del keep
+        return cert, dict(rounds=int(stats[0]), pieces=int(stats[1]), capped=int(stats[2]))
+
     def ctrl_points_check(self, params: InflateParams, polycoef, seg_time, orders, t_start=0.0, cap=1024):
         """pct_ctrl_points_check: the collision threshold test on the raw control points (world units)"""
         traj, keep = _traj(polycoef, seg_time, orders)
@@ -932,6 +957,13 @@ class Cloud:
         _chk(lib().pct_bezier_check_batch_dev(self._h, C.byref(batch), C.byref(params), float(stop_time), float(dt), int(cap), verdict_ptr or None,
                                               offsets_ptr or None, int(list_cap), pos_ptr or None, radius_ptr or None, d2_ptr or None,
                                               idx_ptr or None, stream))
+
+    def bezier_certify_device(self, batch: BezierBatch, margin, max_depth, piece_cap, cert_ptr: int, stats_ptr: int = 0, stream: int = 0,
+                              algo: int = ALGO_AUTO):
+        """pct_bezier_certify_batch_dev: `batch` holds DEVICE pointers; cert_ptr -> B x 48 bytes (engine.CERT_DTYPE), stats_ptr -> int64 [3]
+        or 0; reserve_queries(2 * piece_cap) first.  Asynchronous on `stream`; max_depth + 1 rounds over piece_cap slots."""
+        _chk(lib().pct_bezier_certify_batch_dev(self._h, algo, C.byref(batch), float(margin), int(max_depth), int(piece_cap), cert_ptr or None,
+                                                stats_ptr or None, stream))
 
     def radius_count_device(self, q_ptr: int, r_ptr: int, Q: int, cnt_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         _chk(lib().pct_radius_count_batch_dev(self._h, algo, q_ptr, r_ptr, int(Q), cnt_ptr, stream))
