@@ -2,12 +2,12 @@
 // include/pct_engine.h, paragraph "Batched Bezier check"; included by engine.hip behind kernels.hpp).
 //
 // The passes, all on one stream and without a host decision between them:
-//   bb_count_kernel     one lane per trajectory runs the reference's nested sample loops (sim_planning_demo.cpp:729-771; the adds
-//                       t += dt, t_accu += dt are a dependent chain by definition, so the parallelism is across trajectories) and
-//                       writes nsamples_b and m_b = min(nsamples_b, cap, 4096)
+//   bb_count_kernel     one lane per trajectory runs the reference's nested sample loops (bezier_enumerate of bernstein.hpp; its adds
+//                       are a dependent chain by definition, so the parallelism is across trajectories) and writes nsamples_b and
+//                       m_b = min(nsamples_b, cap, 4096)
 //   scan_tile_sums_kernel (scan.hpp)   m_b -> offsets, in place, B + 1 entries
 //   bb_fill_kernel      the same lanes replay the loops and store (segment, t) of every evaluated sample at its slot
-//   bb_eval_kernel      one thread per slot: getPosFromBezier (:715-727) with the arithmetic of bezier_eval_kernel
+//   bb_eval_kernel      one thread per slot: getPosFromBezier (bezier_point of bernstein.hpp)
 //   inflate_dev         (engine.hip) the sphere inflation of every slot, on whatever index the cloud has
 //   bb_verdict_kernel   a wave per trajectory folds its row: first radius < 0, and the smallest radius with its lowest sample
 //   bb_export_kernel    device form only: the rows from the cloud's workspaces into the caller's lists
@@ -36,53 +36,8 @@ struct BbDesc {
     long long cap;               // already clipped to kBezierCapMax (engine.hip)
 };
 
-// The reference's loops over the segments [s0, s1) of one trajectory: the segment search with its strict `>`, then the sequential
-// fp64 additions of bezier_enumerate_samples (engine.hip) / bezier_samples_kernel.  emit(k, t, segment) for the samples k < room;
-// FILL stops once they are out.  Returns the unclipped count, or -1 when more than kBbLoopBound (+ one per segment) samples come: the
-// loop then ends there, whatever dt and the segment times are.  The reference leaves only the inner loop when t_accu passes stop_time;
-// t_accu never shrinks (dt > 0), so no later segment yields a sample and returning at once counts the same.
-template <bool FILL, typename Emit>
-__device__ __forceinline__ long long bb_enumerate(const double *__restrict__ seg_time, int s0, int s1, double t_start, double stop_time,
-                                                  double dt, long long room, Emit emit)
-{
-    double t_s = t_start;
-    int first;
-    for (first = s0; first < s1; ++first) {
-        if (t_s > seg_time[first] && first + 1 < s1) t_s -= seg_time[first];
-        else break;
-    }
-    const long long bound = kBbLoopBound + (s1 - s0);
-    long long n = 0;
-    double t_accu = 0.0;
-    for (int i = first; i < s1; i++) {
-        const double T = seg_time[i];
-        for (double t = (i == first) ? t_s : 0.0; t < T; t += dt) {
-            t_accu += dt;
-            if (t_accu > stop_time) return n;
-            if (FILL && n >= room) return n;
-            if (n >= bound) return -1;
-            if (n < room) emit(n, t, i);
-            n++;
-        }
-    }
-    return n;
-}
-
-// segments [s0, s1) of trajectory b, or false when the range is empty, descending or outside [0, seg_offsets[B]], an order is outside
-// 0..12 or a row is too short for its order: such a trajectory reports nsamples = -1 and none of its rows is read
-__device__ __forceinline__ bool bb_range(const BbDesc &D, long long b, int &s0, int &s1)
-{
-    s0 = D.seg_offsets[b];
-    s1 = D.seg_offsets[b + 1];
-    if (s0 < 0 || s1 <= s0 || s1 > D.seg_offsets[D.B]) return false;
-    for (int i = s0; i < s1; i++) {
-        const int o = D.orders[i];
-        if (o < 0 || o > kMaxBezierOrder || 3ll * (o + 1) > D.row_stride) return false;
-    }
-    return true;
-}
-
-// lane b < B: verdict[b].nsamples and offsets[b] = m_b; lane B: offsets[B] = 0, so that the scan of B + 1 entries leaves the total there
+// lane b < B: verdict[b].nsamples (-1: an unsound range, or more than kBbLoopBound + one per segment samples) and offsets[b] = m_b;
+// lane B: offsets[B] = 0, so that the scan of B + 1 entries leaves the total there
 __global__ __launch_bounds__(256) void bb_count_kernel(BbDesc D, pct_traj_verdict *__restrict__ verdict, long long *__restrict__ offsets)
 {
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -90,8 +45,9 @@ __global__ __launch_bounds__(256) void bb_count_kernel(BbDesc D, pct_traj_verdic
     if (b == D.B) { offsets[b] = 0; return; }
     int s0, s1;
     long long n = -1;
-    if (bb_range(D, b, s0, s1))
-        n = bb_enumerate<false>(D.seg_time, s0, s1, D.t_start ? D.t_start[b] : 0.0, D.stop_time, D.dt, 0, [](long long, double, int) {});
+    if (bezier_range_sound(D.seg_offsets, D.orders, D.row_stride, D.B, b, s0, s1))
+        n = bezier_enumerate<false>(D.seg_time, s0, s1, D.t_start ? D.t_start[b] : 0.0, D.stop_time, D.dt, 0, kBbLoopBound + (s1 - s0),
+                                    [](long long, double, int) {});
     verdict[b].nsamples = n;
     offsets[b] = n < 0 ? 0 : (n < D.cap ? n : D.cap);
 }
@@ -105,13 +61,12 @@ __global__ __launch_bounds__(256) void bb_fill_kernel(BbDesc D, const long long 
     const long long o = offsets[b], m = offsets[b + 1] - o;
     if (m <= 0) return;
     const int s0 = D.seg_offsets[b], s1 = D.seg_offsets[b + 1];      // m > 0: bb_count_kernel found the range sound
-    bb_enumerate<true>(D.seg_time, s0, s1, D.t_start ? D.t_start[b] : 0.0, D.stop_time, D.dt, m,
-                       [&](long long k, double t, int seg) { slot_seg[o + k] = (uint32_t)seg; slot_t[o + k] = t; });
+    bezier_enumerate<true>(D.seg_time, s0, s1, D.t_start ? D.t_start[b] : 0.0, D.stop_time, D.dt, m, kBbLoopBound + (s1 - s0),
+                           [&](long long k, double t, int seg) { slot_seg[o + k] = (uint32_t)seg; slot_t[o + k] = t; });
 }
 
-// one thread per slot < nslots (the host form: the total; the device form: list_cap).  A slot below the total: getPosFromBezier, the
-// term order ((C * c) * u^j) * (1 - u)^(n - j), j ascending, times T -- the statements of bezier_eval_kernel.  Any other slot:
-// the cloud's row 0 (pad != null), whose search ends where it starts.
+// one thread per slot < nslots (the host form: the total; the device form: list_cap).  A slot below the total: getPosFromBezier
+// (bezier_point).  Any other slot: the cloud's row 0 (pad != null), whose search ends where it starts.
 __global__ __launch_bounds__(128) void bb_eval_kernel(BbDesc D, const long long *__restrict__ offsets, long long list_cap, long long nslots,
                                                       const uint32_t *__restrict__ slot_seg, const double *__restrict__ slot_t,
                                                       const float *__restrict__ pad_x, const float *__restrict__ pad_y,
@@ -127,17 +82,8 @@ __global__ __launch_bounds__(128) void bb_eval_kernel(BbDesc D, const long long 
         return;
     }
     const int seg = (int)slot_seg[s];
-    const int order = D.orders[seg], m = order + 1;
     const double T = D.seg_time[seg];
-    const double u = slot_t[s] / T;
-    const double *c = D.coef + (size_t)seg * D.row_stride;
-    double binom[kMaxBezierOrder + 1];
-    for (int j = 0; j <= order; j++) binom[j] = bernstein_binom(order, j);
-    for (int d = 0; d < 3; d++) {
-        double acc = 0.0;
-        for (int j = 0; j < m; j++) acc += binom[j] * c[d * m + j] * pow_uint_cr(u, j) * pow_uint_cr(1.0 - u, order - j);
-        pos[3 * s + d] = acc * T;
-    }
+    bezier_point(D.coef + (size_t)seg * D.row_stride, D.orders[seg], T, slot_t[s] / T, pos + 3 * s);
 }
 
 // A wave per trajectory (4 in a block).  Lane l reads the samples l, l + 64, .. of its row in ascending order, so `<` keeps the lowest

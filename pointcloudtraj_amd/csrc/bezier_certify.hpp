@@ -54,6 +54,7 @@
 // HIT needs no argument: the end of a piece is a point the sampled check could have sampled, judged by its test.
 #pragma once
 #include "../../include/pct_engine.h"
+#include "bernstein.hpp"
 #include "scan.hpp"
 #include "segment.hpp"
 
@@ -92,20 +93,6 @@ struct BcDesc {
     long long B;
 };
 
-// segments [s0, s1) of trajectory b are sound: the range inside [0, seg_offsets[B]], orders 0..12, rows long enough (the host form has
-// refused anything else; the device form reports such a trajectory INVALID and reads none of its rows)
-__device__ __forceinline__ bool bc_range(const BcDesc &D, long long b, int &s0, int &s1)
-{
-    s0 = D.seg_offsets[b];
-    s1 = D.seg_offsets[b + 1];
-    if (s0 < 0 || s1 <= s0 || s1 > D.seg_offsets[D.B]) return false;
-    for (int i = s0; i < s1; i++) {
-        const int o = D.orders[i];
-        if (o < 0 || o > kMaxBezierOrder || 3ll * (o + 1) > D.row_stride) return false;
-    }
-    return true;
-}
-
 // the trajectory that owns segment i: the largest b with seg_offsets[b] <= i, or -1 when that trajectory's range does not hold i
 __device__ __forceinline__ long long bc_owner(const BcDesc &D, int i)
 {
@@ -142,8 +129,8 @@ __global__ __launch_bounds__(256) void bc_init_kernel(BcDesc D, long long piece_
         ctl->pieces = 0;
         return;
     }
-    int s0, s1;
-    const bool sound = bc_range(D, b, s0, s1);
+    int s0, s1;      // an unsound range (the host form has refused it): INVALID, and none of its rows is read
+    const bool sound = bezier_range_sound(D.seg_offsets, D.orders, D.row_stride, D.B, b, s0, s1);
     traj[b].hitkey = kBcNoHit;
     traj[b].flags = !sound ? kBcInvalid : over ? kBcUndecided : 0u;
     cert[b].status = PCT_CERT_FREE;

@@ -1651,43 +1651,24 @@ int plan_capture(pct_plan *p, F enqueue)
 int bezier_check_orders(const pct_bezier_traj *traj)
 {
     for (int i = 0; i < traj->nseg; i++)
-        if (traj->orders[i] < 0 || traj->orders[i] > kMaxBezierOrder || 3 * (traj->orders[i] + 1) > traj->row_stride)
+        if (!bezier_order_ok(traj->orders[i], traj->row_stride))
             return fail(PCT_ERR_INVALID, "segment %d: order %d unsupported", i, traj->orders[i]);
     return PCT_OK;
 }
 
-// the segment that holds t_start and the time into it (the segment search of checkSafeTrajectory, sim_planning_demo.cpp:729-771)
-int bezier_first_segment(const pct_bezier_traj *traj, double t_start, double *t_s_out)
+// the layout of a pct_bezier_batch as the host forms demand it: seg_offsets[0] == 0, strictly ascending offsets, sound orders
+// (`who`: the entry point, for the message)
+int bezier_check_batch_layout(const pct_bezier_batch *batch, const char *who)
 {
-    double t_s = t_start;
-    int first_seg;
-    for (first_seg = 0; first_seg < traj->nseg; ++first_seg) {
-        if (t_s > traj->seg_time[first_seg] && first_seg + 1 < traj->nseg) t_s -= traj->seg_time[first_seg];
-        else break;
+    if (batch->B > 0 && batch->seg_offsets[0] != 0) return fail(PCT_ERR_INVALID, "%s: seg_offsets[0] = %d, not 0", who, (int)batch->seg_offsets[0]);
+    for (int64_t b = 0; b < batch->B; b++) {
+        const int32_t s0 = batch->seg_offsets[b], s1 = batch->seg_offsets[b + 1];
+        if (s1 <= s0) return fail(PCT_ERR_INVALID, "%s: seg_offsets not strictly ascending at trajectory %lld", who, (long long)b);
+        for (int32_t i = s0; i < s1; i++)
+            if (!bezier_order_ok(batch->orders[i], batch->row_stride))
+                return fail(PCT_ERR_INVALID, "%s: segment %d: order %d unsupported", who, (int)i, (int)batch->orders[i]);
     }
-    *t_s_out = t_s;
-    return first_seg;
-}
-
-// the reference's nested sample loops (the same sequential fp64 additions as bezier_samples_kernel): emit(k, t, segment) for the
-// first `room` samples; returns the unclipped count
-template <typename Emit>
-int64_t bezier_enumerate_samples(const pct_bezier_traj *traj, double t_start, double stop_time, double dt, int64_t room, Emit emit)
-{
-    double t_s;
-    const int first_seg = bezier_first_segment(traj, t_start, &t_s);
-    int64_t n = 0;
-    double t_accu = 0.0;
-    for (int i = first_seg; i < traj->nseg; i++) {
-        const double T = traj->seg_time[i];
-        for (double t = (i == first_seg) ? t_s : 0.0; t < T; t += dt) {
-            t_accu += dt;
-            if (t_accu > stop_time) break;
-            if (n < room) emit(n, t, i);
-            n++;
-        }
-    }
-    return n;
+    return PCT_OK;
 }
 
 // coefficients, segment times and orders into the cloud's device copies (grow-only) on stream s.  dev_form: earlier work on the
@@ -1710,6 +1691,22 @@ int bezier_stage_coef(pct_cloud *c, const pct_bezier_traj *traj, hipStream_t s, 
     HIPCHK(hipMemcpyAsync(c->d_coef, traj->polycoef, sizeof(double) * ncoef, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_segtime, traj->seg_time, sizeof(double) * nseg, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_orders, traj->orders, sizeof(int) * nseg, hipMemcpyHostToDevice, s));
+    return PCT_OK;
+}
+
+// the staged check of the staged coefficients on stream s: cleared positions, the samples, their inflation, the first hit.
+// d_pos and d_radius are the caller's or the cloud's workspaces; a null d_idx / d_d2 means the cloud's.
+int bezier_staged_enqueue(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflate_params *p, double t_start, double stop_time, double dt,
+                          int64_t cap, hipStream_t s, double *d_pos, double *d_radius, uint32_t *d_idx, double *d_d2, long long *d_first_hit,
+                          int *d_nsamples)
+{
+    HIPCHK(hipMemsetAsync(d_pos, 0, sizeof(double) * 3 * cap, s));
+    BezierDesc B{ c->d_coef, c->d_segtime, c->d_orders, (int)traj->row_stride, traj->nseg, t_start, stop_time, dt, (int)cap };
+    const size_t smem = (size_t)cap * (sizeof(double) + sizeof(int));
+    bezier_samples_kernel<<<1, 256, smem, s>>>(B, d_pos, d_nsamples);
+    PCTCHK(inflate_dev(c, p, cap, s, d_pos, nullptr, d_radius, d_idx, d_d2));
+    first_hit_kernel<<<1, 256, 0, s>>>(d_radius, d_nsamples, (int)cap, d_first_hit);
+    HIPCHK(hipGetLastError());
     return PCT_OK;
 }
 
@@ -3083,8 +3080,8 @@ int pct_bezier_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflat
     }
     const size_t ncoef = (size_t)traj->nseg * traj->row_stride;
     if (ncoef + (size_t)traj->nseg <= 3 * (size_t)kExpressMaxQ - 64) {
-        // express: the host enumerates the sample times (sim_planning_demo.cpp:729-771, the same sequential fp64 additions as
-        // bezier_samples_kernel), then ONE launch evaluates, inflates and searches every sample (bezier_block_kernel)
+        // express: the host enumerates the sample times (bezier_enumerate, as thread 0 of bezier_samples_kernel does), then ONE
+        // launch evaluates, inflates and searches every sample (bezier_block_kernel)
         double *hd = c->xin.host();                                  // [coef | seg_time | sample_t]
         uint32_t *hu = c->xids.host();                               // [orders | sample_seg]
         std::memcpy(hd, traj->polycoef, sizeof(double) * ncoef);
@@ -3093,7 +3090,8 @@ int pct_bezier_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflat
         double *ht = hd + ncoef + traj->nseg;
         uint32_t *hs = hu + traj->nseg;
         const int64_t room = std::min<int64_t>({ cap, (int64_t)kExpressMaxQ, (int64_t)(3 * (size_t)kExpressMaxQ - ncoef - (size_t)traj->nseg) });
-        const int64_t n = bezier_enumerate_samples(traj, t_start, stop_time, dt, room, [&](int64_t k, double t, int seg) { ht[k] = t; hs[k] = (uint32_t)seg; });
+        const int64_t n = bezier_enumerate<false>(traj->seg_time, 0, traj->nseg, t_start, stop_time, dt, room, kBezierNoBound,
+                                                  [&](long long k, double t, int seg) { ht[k] = t; hs[k] = (uint32_t)seg; });
         const int64_t m = std::min<int64_t>(n, room);
         const bool fits = n <= room || room == cap;             // more samples than one express launch holds: staged path below
         if (fits && m > 0) {
@@ -3133,13 +3131,7 @@ int pct_bezier_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_inflat
     if (!c->d_first_hit) PCTCHK(c->d_first_hit.reset(1));
     hipStream_t s = g_stream;
     PCTCHK(bezier_stage_coef(c, traj, s, false));
-    HIPCHK(hipMemsetAsync(c->d_pts64, 0, sizeof(double) * 3 * cap, s));
-    BezierDesc B{ c->d_coef, c->d_segtime, c->d_orders, (int)traj->row_stride, traj->nseg, t_start, stop_time, dt, (int)cap };
-    const size_t smem = (size_t)cap * (sizeof(double) + sizeof(int));
-    bezier_samples_kernel<<<1, 256, smem, s>>>(B, c->d_pts64, c->d_nsamples);
-    PCTCHK(inflate_dev(c, p, cap, s));
-    first_hit_kernel<<<1, 256, 0, s>>>(c->d_radius, c->d_nsamples, (int)cap, c->d_first_hit);
-    HIPCHK(hipGetLastError());
+    PCTCHK(bezier_staged_enqueue(c, traj, p, t_start, stop_time, dt, cap, s, c->d_pts64, c->d_radius, nullptr, nullptr, c->d_first_hit, c->d_nsamples));
     int ns = 0;
     long long fh = -1;
     HIPCHK(hipMemcpyAsync(&ns, c->d_nsamples, sizeof ns, hipMemcpyDeviceToHost, s));
@@ -3179,15 +3171,7 @@ int pct_bezier_check_dev(pct_cloud *c, const pct_bezier_traj *traj, const pct_in
     hipStream_t s = (hipStream_t)stream;
     PCTCHK(order_after_mutations(c, s));
     PCTCHK(bezier_stage_coef(c, traj, s, true));
-    double *pos = d_pos ? d_pos : c->d_pts64;
-    HIPCHK(hipMemsetAsync(pos, 0, sizeof(double) * 3 * cap, s));
-    BezierDesc B{ c->d_coef, c->d_segtime, c->d_orders, (int)traj->row_stride, traj->nseg, t_start, stop_time, dt, (int)cap };
-    const size_t smem = (size_t)cap * (sizeof(double) + sizeof(int));
-    bezier_samples_kernel<<<1, 256, smem, s>>>(B, pos, d_nsamples);
-    PCTCHK(inflate_dev(c, p, cap, s, pos, nullptr, d_radius, d_idx, d_d2));
-    first_hit_kernel<<<1, 256, 0, s>>>(d_radius, d_nsamples, (int)cap, d_first_hit);
-    HIPCHK(hipGetLastError());
-    return PCT_OK;
+    return bezier_staged_enqueue(c, traj, p, t_start, stop_time, dt, cap, s, d_pos ? d_pos : c->d_pts64, d_radius, d_idx, d_d2, d_first_hit, d_nsamples);
 }
 
 // ---- the sampled Bezier check for B trajectories at once (bezier_batch.hpp; contract: pct_engine.h, "Batched Bezier check") ------
@@ -3227,17 +3211,10 @@ int pct_bezier_check_batch(pct_cloud *c, const pct_bezier_batch *batch, const pc
     if (B > 0 && (!batch->polycoef || !batch->seg_time || !batch->orders || !batch->seg_offsets || !verdict))
         return fail(PCT_ERR_INVALID, "bad bezier_check_batch arguments: a null array");
     if (B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bezier_check_batch: B = %lld", (long long)B);
-    if (B > 0 && batch->seg_offsets[0] != 0) return fail(PCT_ERR_INVALID, "bezier_check_batch: seg_offsets[0] = %d, not 0", (int)batch->seg_offsets[0]);
+    PCTCHK(bezier_check_batch_layout(batch, "bezier_check_batch"));
     for (int64_t b = 0; b < B; b++) {
-        const int32_t s0 = batch->seg_offsets[b], s1 = batch->seg_offsets[b + 1];
-        if (s1 <= s0) return fail(PCT_ERR_INVALID, "bezier_check_batch: seg_offsets not strictly ascending at trajectory %lld", (long long)b);
         double sum = 0.0;
-        for (int32_t i = s0; i < s1; i++) {
-            const int32_t o = batch->orders[i];
-            if (o < 0 || o > kMaxBezierOrder || 3 * (int64_t)(o + 1) > batch->row_stride)
-                return fail(PCT_ERR_INVALID, "bezier_check_batch: segment %d: order %d unsupported", (int)i, (int)o);
-            sum += batch->seg_time[i];
-        }
+        for (int32_t i = batch->seg_offsets[b]; i < batch->seg_offsets[b + 1]; i++) sum += batch->seg_time[i];
         // the enumeration must end on the device: a batch for candidate sets, not for logs
         if (!(std::min(stop_time, sum) / dt <= (double)kBbLoopBound))
             return fail(PCT_ERR_INVALID, "bezier_check_batch: trajectory %lld would enumerate more than 2^20 samples", (long long)b);
@@ -3326,16 +3303,7 @@ int pct_bezier_certify_batch(pct_cloud *c, int algo, const pct_bezier_batch *bat
     const int64_t B = batch->B;
     if (B > 0 && (!batch->polycoef || !batch->seg_time || !batch->orders || !batch->seg_offsets || !cert))
         return fail(PCT_ERR_INVALID, "bad bezier_certify_batch arguments: a null array");
-    if (B > 0 && batch->seg_offsets[0] != 0) return fail(PCT_ERR_INVALID, "bezier_certify_batch: seg_offsets[0] = %d, not 0", (int)batch->seg_offsets[0]);
-    for (int64_t b = 0; b < B; b++) {
-        const int32_t s0 = batch->seg_offsets[b], s1 = batch->seg_offsets[b + 1];
-        if (s1 <= s0) return fail(PCT_ERR_INVALID, "bezier_certify_batch: seg_offsets not strictly ascending at trajectory %lld", (long long)b);
-        for (int32_t i = s0; i < s1; i++) {
-            const int32_t o = batch->orders[i];
-            if (o < 0 || o > kMaxBezierOrder || 3 * (int64_t)(o + 1) > batch->row_stride)
-                return fail(PCT_ERR_INVALID, "bezier_certify_batch: segment %d: order %d unsupported", (int)i, (int)o);
-        }
-    }
+    PCTCHK(bezier_check_batch_layout(batch, "bezier_certify_batch"));
     const int64_t total_seg = B > 0 ? batch->seg_offsets[B] : 0;
     if (piece_cap < total_seg)
         return fail(PCT_ERR_INVALID, "bezier_certify_batch: piece_cap %lld is below the %lld segments", (long long)piece_cap, (long long)total_seg);

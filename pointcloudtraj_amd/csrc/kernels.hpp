@@ -2189,8 +2189,6 @@ __global__ __launch_bounds__(256) void radius_small_batch_kernel(const float *__
     express_done_block(sig);
 }
 
-struct InflateParams { double sx, sy, sz, sample_range, search_margin, max_radius; };
-
 // corridor_finder.cpp:113-126: early-out test in fp64 on the planner's Vector3d, then the
 // query is narrowed to fp32 (searchPoint.x = search_Pt(0)).  skip[i] = 1 when the early-out fires.
 __global__ __launch_bounds__(256) void inflate_prologue_kernel(InflateParams P, const double *__restrict__ pts,
@@ -2200,9 +2198,7 @@ __global__ __launch_bounds__(256) void inflate_prologue_kernel(InflateParams P, 
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
-    const double dx = px - P.sx, dy = py - P.sy, dz = pz - P.sz;
-    const double dist = sqrt(dx * dx + dy * dy + dz * dz);     // getDis, :109-111
-    skip[i] = dist > P.sample_range + P.max_radius ? 1 : 0;
+    skip[i] = inflate_skips(P, px, py, pz) ? 1 : 0;
     q[3 * i] = (float)px;
     q[3 * i + 1] = (float)py;
     q[3 * i + 2] = (float)pz;
@@ -2218,13 +2214,12 @@ __global__ __launch_bounds__(256) void inflate_epilogue_kernel(InflateParams P, 
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (skip[i] || cloud_empty) {
-        radius[i] = P.max_radius - P.search_margin;
+        radius[i] = inflate_skipped_radius(P);
         idx[i] = kNoIndex;
         d2[i] = __builtin_huge_val();
         return;
     }
-    const double r = sqrt(d2[i]) - P.search_margin;
-    radius[i] = r < P.max_radius ? r : P.max_radius;
+    radius[i] = inflate_radius(P, d2[i]);
 }
 
 // the same epilogue writing one {d2, radius, idx} record per point into host-mapped memory (small batches: the host reads the
@@ -2236,13 +2231,12 @@ __global__ __launch_bounds__(256) void inflate_epilogue_out_kernel(InflateParams
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (skip[i] || cloud_empty) {
-        out[i].radius = P.max_radius - P.search_margin;
+        out[i].radius = inflate_skipped_radius(P);
         out[i].idx = kNoIndex;
         out[i].d2 = __builtin_huge_val();
         return;
     }
-    const double r = sqrt(d2[i]) - P.search_margin;
-    out[i].radius = r < P.max_radius ? r : P.max_radius;
+    out[i].radius = inflate_radius(P, d2[i]);
     out[i].idx = idx[i];
     out[i].d2 = d2[i];
 }
@@ -2314,21 +2308,15 @@ __global__ __launch_bounds__(256) void inflate_block_kernel(GridDesc G, const fl
     __shared__ uint32_t s_i[4];
     const uint32_t slot = blockIdx.x;
     const double px = qpts[3 * slot], py = qpts[3 * slot + 1], pz = qpts[3 * slot + 2];
-    if (INFLATE) {
-        const double dx = px - P.sx, dy = py - P.sy, dz = pz - P.sz;
-        if (sqrt(dx * dx + dy * dy + dz * dz) > P.sample_range + P.max_radius) {      // corridor_finder.cpp:115-116
-            if (threadIdx.x == 0) { out[slot].radius = P.max_radius - P.search_margin; out[slot].idx = kNoIndex; out[slot].d2 = __builtin_huge_val(); express_done(sig); }
-            return;
-        }
+    if (INFLATE && inflate_skips(P, px, py, pz)) {
+        if (threadIdx.x == 0) { out[slot].radius = inflate_skipped_radius(P); out[slot].idx = kNoIndex; out[slot].d2 = __builtin_huge_val(); express_done(sig); }
+        return;
     }
     double bd;
     uint32_t bi;
     block_nn_search(G, pts, cell_start, px, py, pz, stop_d2, s_d, s_i, bd, bi);
     if (threadIdx.x == 0) {
-        if (INFLATE) {
-            const double rr = sqrt(bd) - P.search_margin;
-            out[slot].radius = rr < P.max_radius ? rr : P.max_radius;
-        }
+        if (INFLATE) out[slot].radius = inflate_radius(P, bd);
         out[slot].idx = reported_index(bd, bi, index_base);
         out[slot].d2 = bd;
         express_done(sig);
@@ -2348,8 +2336,6 @@ struct ExpandOut { double cx, cy, cz, radius; uint32_t near_idx, count; };
 
 // (the kernel itself, rrt_expand_kernel<RING>, is in ring.hpp: it searches either index kind)
 
-constexpr int kMaxBezierOrder = 12;
-
 struct BezierDesc {
     const double *coef;      // device copy of PolyCoeff, nseg x row_stride
     const double *seg_time;  // device
@@ -2359,10 +2345,8 @@ struct BezierDesc {
     int cap;
 };
 
-// sim_planning_demo.cpp:729-771.  Thread 0 enumerates the sample times with the same
-// sequential additions as the reference's nested loops; then one thread per sample
-// evaluates getPosFromBezier (:715-727): acc += C(n,j) * c * pow(u,j) * pow(1-u,n-j), j ascending,
-// scaled by the segment time (:752-753).  Outputs: pos (fp64) and nsamples.
+// sim_planning_demo.cpp:729-771.  Thread 0 enumerates the sample times (bezier_enumerate); then one thread per sample
+// evaluates getPosFromBezier (bezier_point).  Outputs: pos (fp64) and nsamples, the unclipped count.
 __global__ __launch_bounds__(256) void bezier_samples_kernel(BezierDesc B, double *__restrict__ pos,
                                                              int *__restrict__ nsamples)
 {
@@ -2371,23 +2355,8 @@ __global__ __launch_bounds__(256) void bezier_samples_kernel(BezierDesc B, doubl
     int *s_seg = reinterpret_cast<int *>(s_t + B.cap);
     __shared__ int s_n;
     if (threadIdx.x == 0) {
-        double t_s = B.t_start;
-        int idx;
-        for (idx = 0; idx < B.nseg; ++idx) {
-            if (t_s > B.seg_time[idx] && idx + 1 < B.nseg) t_s -= B.seg_time[idx];
-            else break;
-        }
-        int n = 0;
-        double t_accu = 0.0;
-        for (int i = idx; i < B.nseg; i++) {
-            const double T = B.seg_time[i];
-            for (double t = (i == idx) ? t_s : 0.0; t < T; t += B.dt) {
-                t_accu += B.dt;
-                if (t_accu > B.stop_time) break;
-                if (n < B.cap) { s_t[n] = t; s_seg[n] = i; }
-                n++;
-            }
-        }
+        const int n = (int)bezier_enumerate<false>(B.seg_time, 0, B.nseg, B.t_start, B.stop_time, B.dt, B.cap, kBezierNoBound,
+                                                   [&](long long k, double t, int seg) { s_t[k] = t; s_seg[k] = seg; });
         s_n = n;
         *nsamples = n;
     }
@@ -2395,25 +2364,14 @@ __global__ __launch_bounds__(256) void bezier_samples_kernel(BezierDesc B, doubl
     const int n = min(s_n, B.cap);
     for (int s = threadIdx.x; s < n; s += blockDim.x) {
         const int seg = s_seg[s];
-        const int order = B.orders[seg], m = order + 1;
         const double T = B.seg_time[seg];
-        const double u = s_t[s] / T;
-        const double *c = B.coef + (size_t)seg * B.row_stride;
-        // binomials as exact doubles (bezier_base.cpp:33-48 computes them with integer factorials)
-        double binom[kMaxBezierOrder + 1];
-        for (int j = 0; j <= order; j++) binom[j] = bernstein_binom(order, j);
-        for (int d = 0; d < 3; d++) {
-            double acc = 0.0;
-            for (int j = 0; j < m; j++) acc += binom[j] * c[d * m + j] * pow_uint_cr(u, j) * pow_uint_cr(1.0 - u, order - j);
-            pos[3 * s + d] = acc * T;
-        }
+        bezier_point(B.coef + (size_t)seg * B.row_stride, B.orders[seg], T, s_t[s] / T, pos + 3 * s);
     }
 }
 
 // Low-latency form of the whole check on an indexed cloud: ONE launch, a 256-thread block per sample.  The host enumerates
-// the sample times (the same sequential fp64 additions as above: IEEE adds are the same on both sides) and hands (segment, t)
-// per sample; the block evaluates getPosFromBezier with one thread per Bernstein term (two pow calls each, the terms then
-// summed by one thread in the reference's j order), applies the inflation early-out and runs the block-wide cell search.
+// the sample times (bezier_enumerate: IEEE adds are the same on both sides) and hands (segment, t) per sample; the block
+// evaluates getPosFromBezier (bezier_point_block), applies the inflation early-out and runs the block-wide cell search.
 // Arguments and results live in host-mapped memory; the host picks the first sample with a negative radius.
 __global__ __launch_bounds__(256) void bezier_block_kernel(GridDesc G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
                                                            InflateParams P, const double *__restrict__ coef, int row_stride,
@@ -2428,42 +2386,27 @@ __global__ __launch_bounds__(256) void bezier_block_kernel(GridDesc G, const flo
     __shared__ double s_pos[3];
     const uint32_t slot = blockIdx.x;
     const int seg = (int)sample_seg[slot];
-    const int order = (int)orders[seg], m = order + 1;
     const double T = seg_time[seg];
-    const double u = sample_t[slot] / T;
-    if ((int)threadIdx.x < 3 * m) {
-        const int d = (int)threadIdx.x / m, j = (int)threadIdx.x % m;
-        const double b = bernstein_binom(order, j);
-        s_term[d * m + j] = b * coef[(size_t)seg * row_stride + d * m + j] * pow_uint_cr(u, j) * pow_uint_cr(1.0 - u, order - j);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double acc = 0.0;
-        for (int j = 0; j < m; j++) acc += s_term[threadIdx.x * m + j];
-        s_pos[threadIdx.x] = acc * T;
-    }
-    __syncthreads();
+    bezier_point_block(coef + (size_t)seg * row_stride, (int)orders[seg], T, sample_t[slot] / T, s_term, s_pos);
     const double px = s_pos[0], py = s_pos[1], pz = s_pos[2];
     // every host-visible store of the block comes from thread 0, so one thread fences and signals
     if (threadIdx.x == 0) { pos_out[3 * slot] = px; pos_out[3 * slot + 1] = py; pos_out[3 * slot + 2] = pz; }
-    const double dx = px - P.sx, dy = py - P.sy, dz = pz - P.sz;
-    if (sqrt(dx * dx + dy * dy + dz * dz) > P.sample_range + P.max_radius) {          // corridor_finder.cpp:115-116
-        if (threadIdx.x == 0) { out[slot].radius = P.max_radius - P.search_margin; out[slot].idx = kNoIndex; out[slot].d2 = __builtin_huge_val(); express_done(sig); }
+    if (inflate_skips(P, px, py, pz)) {
+        if (threadIdx.x == 0) { out[slot].radius = inflate_skipped_radius(P); out[slot].idx = kNoIndex; out[slot].d2 = __builtin_huge_val(); express_done(sig); }
         return;
     }
     double bd;
     uint32_t bi;
     block_nn_search(G, pts, cell_start, px, py, pz, stop_d2, s_d, s_i, bd, bi);
     if (threadIdx.x == 0) {
-        const double rr = sqrt(bd) - P.search_margin;
-        out[slot].radius = rr < P.max_radius ? rr : P.max_radius;
+        out[slot].radius = inflate_radius(P, bd);
         out[slot].idx = reported_index(bd, bi, index_base);
         out[slot].d2 = bd;
         express_done(sig);
     }
 }
 
-// getPosFromBezier for host-enumerated samples (segment, t), one thread per sample, the arithmetic of bezier_samples_kernel;
+// getPosFromBezier (bezier_point) for host-enumerated samples (segment, t), one thread per sample;
 // positions go to device memory for the inflation kernels and to host-mapped memory for the caller
 __global__ __launch_bounds__(128) void bezier_eval_kernel(const double *__restrict__ coef, int row_stride, const double *__restrict__ seg_time,
                                                           const uint32_t *__restrict__ orders, const uint32_t *__restrict__ sample_seg,
@@ -2473,18 +2416,10 @@ __global__ __launch_bounds__(128) void bezier_eval_kernel(const double *__restri
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     const int seg = (int)sample_seg[s];
-    const int order = (int)orders[seg], m = order + 1;
     const double T = seg_time[seg];
-    const double u = sample_t[s] / T;
-    const double *c = coef + (size_t)seg * row_stride;
-    double binom[kMaxBezierOrder + 1];
-    for (int j = 0; j <= order; j++) binom[j] = bernstein_binom(order, j);
-    for (int d = 0; d < 3; d++) {
-        double acc = 0.0;
-        for (int j = 0; j < m; j++) acc += binom[j] * c[d * m + j] * pow_uint_cr(u, j) * pow_uint_cr(1.0 - u, order - j);
-        pos_dev[3 * s + d] = acc * T;
-        pos_mapped[3 * s + d] = acc * T;
-    }
+    double p[3];
+    bezier_point(coef + (size_t)seg * row_stride, (int)orders[seg], T, sample_t[s] / T, p);
+    for (int d = 0; d < 3; d++) { pos_dev[3 * s + d] = p[d]; pos_mapped[3 * s + d] = p[d]; }
 }
 
 // first sample with negative radius (checkTrajPtCol, corridor_finder.cpp:412-416); -1 if none

@@ -22,6 +22,7 @@
 // (RingShell / ring_shell / ring_shell_bucket, with the exactness argument and ring_open_face_bound beside it); the argmin walk here
 // (ring_block_nn_search) and the k-NN walk (ring_knn_walk, ring_search.hpp) both step through it.
 #pragma once
+#include "bernstein.hpp"
 #include "kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -450,18 +451,16 @@ __global__ __launch_bounds__(256) void rrt_expand_kernel(const float *__restrict
     }
     double radius;
     {
-        const double dx = cx - P.sx, dy = cy - P.sy, dz = cz - P.sz;
         // a rolling window's size lives on the device (the append kernels publish it): an empty window is an empty cloud
         const bool obstacles_empty = RING ? V.st->count == 0 : static_empty != 0;
-        if (obstacles_empty || sqrt(dx * dx + dy * dy + dz * dz) > P.sample_range + P.max_radius) {
-            radius = P.max_radius - P.search_margin;                             // :115-116
+        if (obstacles_empty || inflate_skips(P, cx, cy, cz)) {
+            radius = inflate_skipped_radius(P);                                  // :115-116
         } else {
             double od;
             uint32_t oi;
             if (RING) ring_block_nn_search(V, cx, cy, cz, stop_d2, s_d, s_i, od, oi);
             else block_nn_search(G, pts, cell_start, cx, cy, cz, stop_d2, s_d, s_i, od, oi);
-            const double rr = sqrt(od) - P.search_margin;
-            radius = rr < P.max_radius ? rr : P.max_radius;
+            radius = inflate_radius(P, od);
         }
     }
     // ---- C: neighbourhood candidates ---------------------------------------------------------------------------------
@@ -571,21 +570,8 @@ __global__ __launch_bounds__(256) void replan_block_kernel(RingView V, GridDesc 
     } else if (slot < H.n_nodes + H.n_samples) {
         const int s = slot - H.n_nodes;
         const int seg = (int)u32a[H.off_sample_seg + s];
-        const int order = (int)u32a[H.off_orders + seg], m = order + 1;
         const double T = f64a[H.off_segtime + seg];
-        const double u = f64a[H.off_sample_t + s] / T;
-        if ((int)threadIdx.x < 3 * m) {
-            const int d = (int)threadIdx.x / m, j = (int)threadIdx.x % m;
-            const double b = bernstein_binom(order, j);
-            s_term[d * m + j] = b * f64a[H.off_coef + (size_t)seg * H.row_stride + d * m + j] * pow_uint_cr(u, j) * pow_uint_cr(1.0 - u, order - j);
-        }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            double acc = 0.0;
-            for (int j = 0; j < m; j++) acc += s_term[threadIdx.x * m + j];
-            s_pos[threadIdx.x] = acc * T;
-        }
-        __syncthreads();
+        bezier_point_block(f64a + H.off_coef + (size_t)seg * H.row_stride, (int)u32a[H.off_orders + seg], T, f64a[H.off_sample_t + s] / T, s_term, s_pos);
         px = s_pos[0]; py = s_pos[1]; pz = s_pos[2];
     } else {
         const int k = slot - H.n_nodes - H.n_samples;
@@ -595,17 +581,15 @@ __global__ __launch_bounds__(256) void replan_block_kernel(RingView V, GridDesc 
         const double *c = f64a + H.off_coef + (size_t)seg * H.row_stride;
         px = c[j] * T; py = c[m + j] * T; pz = c[2 * m + j] * T;
     }
-    const double dx = px - P.sx, dy = py - P.sy, dz = pz - P.sz;
     const bool empty = RING ? V.st->count == 0 : static_count == 0;
-    double bd = __builtin_huge_val(), radius = P.max_radius - P.search_margin;
+    double bd = __builtin_huge_val(), radius = inflate_skipped_radius(P);
     uint32_t bi = kNoIndex;
-    if (!(empty || sqrt(dx * dx + dy * dy + dz * dz) > P.sample_range + P.max_radius)) {        // corridor_finder.cpp:115-116
+    if (!(empty || inflate_skips(P, px, py, pz))) {                                             // corridor_finder.cpp:115-116
         const double reach = P.max_radius + P.search_margin;
         const double stop_d2 = H.want_nn ? __builtin_huge_val() : reach * reach;
         if (RING) ring_block_nn_search(V, px, py, pz, stop_d2, s_d, s_i, bd, bi);
         else block_nn_search(G, pts, cell_start, px, py, pz, stop_d2, s_d, s_i, bd, bi);
-        const double rr = sqrt(bd) - P.search_margin;
-        radius = rr < P.max_radius ? rr : P.max_radius;
+        radius = inflate_radius(P, bd);
     }
     // Thread 0 hands the block's result to the caller's (host-visible) buffer, joins the first-hit minima and takes a ticket; the
     // block holding the last ticket writes the summary and, last of all, the sequence word the host polls (system-scope release).
@@ -666,16 +650,12 @@ __global__ __launch_bounds__(256) void ring_batch_kernel(RingView V, InflatePara
     uint32_t bi = kNoIndex;
     bool skip = V.st->count == 0;
     if (INFLATE) {
-        const double dx = px - P.sx, dy = py - P.sy, dz = pz - P.sz;
-        skip = skip || sqrt(dx * dx + dy * dy + dz * dz) > P.sample_range + P.max_radius;
-        radius = P.max_radius - P.search_margin;
+        skip = skip || inflate_skips(P, px, py, pz);
+        radius = inflate_skipped_radius(P);
     }
     if (!skip) {
         ring_block_nn_search(V, px, py, pz, stop_d2, s_d, s_i, bd, bi);
-        if (INFLATE) {
-            const double rr = sqrt(bd) - P.search_margin;
-            radius = rr < P.max_radius ? rr : P.max_radius;
-        }
+        if (INFLATE) radius = inflate_radius(P, bd);
     }
     if (threadIdx.x == 0) {
         const uint32_t gi = reported_index(bd, bi, index_base);

@@ -563,9 +563,9 @@ int replan_fill(ReplanCtx *x, const pct_inflate_params *p, const double *nodes, 
             u32a[H.off_orders + i] = (uint32_t)traj->orders[i];
         }
         double t_s;
-        const int first_seg = bezier_first_segment(traj, t_start, &t_s);
+        const int first_seg = bezier_first_segment(traj->seg_time, 0, traj->nseg, t_start, t_s);
         H.first_seg = first_seg;
-        const int64_t n = bezier_enumerate_samples(traj, t_start, stop_time, dt, room, [&](int64_t k, double t, int seg) {
+        const int64_t n = bezier_enumerate<false>(traj->seg_time, 0, traj->nseg, t_start, stop_time, dt, room, kBezierNoBound, [&](long long k, double t, int seg) {
             f64a[H.off_sample_t + k] = t;
             u32a[H.off_sample_seg + k] = (uint32_t)seg;
         });
@@ -815,7 +815,7 @@ int pct_ctrl_points_check(pct_cloud *c, const pct_bezier_traj *traj, const pct_i
     PCTCHK(bezier_check_orders(traj));
     // the control points in world units, segments from the one holding t_start on (the segment search of checkSafeTrajectory)
     double t_s;
-    const int first_seg = bezier_first_segment(traj, t_start, &t_s);
+    const int first_seg = bezier_first_segment(traj->seg_time, 0, traj->nseg, t_start, t_s);
     std::vector<double> pts;
     for (int i = first_seg; i < traj->nseg; i++) {
         const int m = traj->orders[i] + 1;

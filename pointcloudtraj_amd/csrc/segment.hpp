@@ -21,6 +21,7 @@
 // the rolling-map form is ring_sweep_kernel, which shares the capsule's box and the per-cell skip with ring_segment_kernel
 // (seg_capsule_box, seg_cell_skipped) and walks the box along the segment so that it can stop.
 #pragma once
+#include "bernstein.hpp"
 #include "ring_search.hpp"
 
 #pragma clang fp contract(off)
@@ -451,10 +452,10 @@ __global__ __launch_bounds__(256) void segment_inflate_epilogue_kernel(InflatePa
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Q) return;
-    if (empty) { radius[i] = P.max_radius - P.search_margin; idx[i] = kNoIndex; s[i] = __builtin_nan(""); return; }
-    const double rr = sqrt(d2[i]) - P.search_margin;
-    if (rr < P.max_radius) { radius[i] = rr; return; }
-    radius[i] = P.max_radius;
+    if (empty) { radius[i] = inflate_skipped_radius(P); idx[i] = kNoIndex; s[i] = __builtin_nan(""); return; }
+    const double r = inflate_radius(P, d2[i]);
+    radius[i] = r;
+    if (r < P.max_radius) return;
     idx[i] = kNoIndex;
     s[i] = __builtin_nan("");
 }

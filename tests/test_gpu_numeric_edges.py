@@ -283,6 +283,47 @@ def test_inflate_on_every_index(E, oracle, case):
     rep.done()
 
 
+def test_inflate_early_out_boundary(E, oracle):
+    """planner points exactly on, one ulp either side of and just beyond |p - start| = sample_range + max_radius: the early-out
+    compares with a strict `>` in fp64, so the first two are searched and the last two are not.  Four points run the block kernels
+    on an indexed cloud and the staged kernels on a plain one; one more than the express limit runs the staged kernels on all
+    three; the same four as corridor nodes of a captured replan batch run the fused kernel on the grid and on the ring."""
+    cloud = np.float32([[4, 0, 0], [40, 0, 0]])
+    start, sample_range, margin, max_radius = (0.0, 0.0, 0.0), 3.0, 0.25, 1.5
+    P = np.zeros((4, 3))
+    P[:, 0] = [np.nextafter(4.5, 0.0), 4.5, np.nextafter(4.5, np.inf), 4.5 + 1e-9]
+    wr, wi, wd = oracle.inflate_brute(cloud, start, sample_range, margin, max_radius, P)
+    assert np.array_equal(wr, [0.25, 0.25, 1.25, 1.25]) and np.array_equal(wi, [0, 0, -1, -1]) and np.array_equal(wd, [0.25, 0.25, np.inf, np.inf])
+    prm = E.inflate_params(start, sample_range, margin, max_radius)
+    many = np.arange(EXPRESS_MAX_Q + 1) % 4
+    wrong = []                  # every path runs before the test fails (module docstring)
+
+    def same(label, rad, idx, d2, sel):
+        idx = np.where(idx == 0xFFFFFFFF, -1, idx.astype(np.int64))
+        if not (np.array_equal(rad, wr[sel]) and np.array_equal(idx, wi[sel]) and np.array_equal(d2, wd[sel])):
+            wrong.append(f"{label}: radius {rad[:4]!r} index {idx[:4]!r} d2 {d2[:4]!r}")
+
+    def run(label, c, planned):
+        same(f"{label}, 4 points", *c.inflate(prm, P), np.arange(4))
+        same(f"{label}, {len(many)} points", *c.inflate(prm, P[many]), many)
+        if planned:
+            plan = E.ReplanPlan(c, 4, 1, 1)
+            o = plan.run(prm, P)
+            same(f"{label}, corridor nodes of a replan batch", o["node_radius"], o["node_idx"], o["node_d2"], np.arange(4))
+            plan.close()
+
+    with E.Cloud(len(cloud)) as c:
+        c.set_input(cloud)
+        run("no index", c, False)
+        c.build_grid()
+        run("static grid", c, True)
+    with E.Cloud(len(cloud)) as c:
+        c.ring_index()
+        c.append(cloud)
+        run("ring", c, True)
+    assert not wrong, "\n  ".join(wrong)
+
+
 # ---- non-finite input --------------------------------------------------------------------------------------------------------
 
 def _nn_paths(E, c, q, with_index):
