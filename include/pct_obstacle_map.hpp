@@ -23,8 +23,65 @@
 #include <vector>
 
 #include "pct_engine.h"
+#include "pct_trajgen.h"
 
 namespace pct {
+
+// Trajectory generation (pct_trajgen.h, paragraph "Trajectory generation"): what trajGeneration does between the corridor finder and
+// the checks (sim_planning_demo.cpp:262-263, timeAllocation + BezierConicOptimizer), for one corridor under K time scales at once.
+// GeneratedTrajectories owns the packed candidates: candidate k = the corridor with every segment time multiplied by scales[k];
+// polycoef holds the rows in the layout the checks read and batch() is the pct_bezier_batch over them (valid while this object
+// lives and is not changed).
+struct GeneratedTrajectories {
+    std::vector<double> centres, radius, seg_time, start_state, end_state, polycoef;
+    std::vector<int32_t> orders, seg_offsets;
+    std::vector<pct_trajgen_result> results;
+    int64_t row_stride = 0;
+    pct_bezier_batch batch() const
+    {
+        return pct_bezier_batch{ polycoef.data(), row_stride, seg_time.data(), orders.data(), seg_offsets.data(), nullptr, (int64_t)results.size() };
+    }
+    const double *rows(int64_t k) const { return polycoef.data() + (int64_t)seg_offsets[(size_t)k] * row_stride; }
+};
+
+// A free function: it needs no map.  path = m sphere centres (m x 3), radius and times m each (times e.g. from pct_time_allocation),
+// orders m each (5..12), start / end = p, v, a (9 doubles).  params: pct_trajgen_params (limits, margin, eps, iteration budget).
+// out.results[k].status says what became of candidate k (PCT_GEN_OK, PCT_GEN_NOT_CONVERGED, PCT_GEN_INVALID).  Returns the number of
+// candidates that are PCT_GEN_OK.
+inline int64_t generateTrajectories(const double *path, const double *radius, const double *times, const int32_t *orders, int32_t m,
+                                    const double *scales, int64_t K, const double start[9], const double end[9],
+                                    const pct_trajgen_params &params, GeneratedTrajectories &out)
+{
+    if (m < 1 || K < 0 || !path || !radius || !times || !orders || (K > 0 && !scales) || !start || !end)
+        throw std::runtime_error("generateTrajectories: bad arguments");
+    const size_t total = (size_t)K * (size_t)m;
+    out.centres.resize(3 * total); out.radius.resize(total); out.seg_time.resize(total); out.orders.resize(total);
+    out.seg_offsets.resize((size_t)K + 1); out.start_state.resize(9 * (size_t)K); out.end_state.resize(9 * (size_t)K);
+    out.results.assign((size_t)K, pct_trajgen_result{});
+    int32_t max_order = 0;
+    for (int32_t s = 0; s < m; s++) max_order = orders[s] > max_order ? orders[s] : max_order;
+    out.row_stride = 3 * (int64_t)((max_order > 12 ? 12 : max_order < 5 ? 5 : max_order) + 1);
+    out.polycoef.assign(total * (size_t)out.row_stride, 0.0);
+    out.seg_offsets[0] = 0;
+    for (int64_t k = 0; k < K; k++) {
+        for (int32_t s = 0; s < m; s++) {
+            const size_t g = (size_t)k * (size_t)m + (size_t)s;
+            for (int d = 0; d < 3; d++) out.centres[3 * g + d] = path[3 * s + d];
+            out.radius[g] = radius[s];
+            out.seg_time[g] = times[s] * scales[k];
+            out.orders[g] = orders[s];
+        }
+        out.seg_offsets[(size_t)k + 1] = (int32_t)((k + 1) * m);
+        for (int i = 0; i < 9; i++) { out.start_state[9 * (size_t)k + i] = start[i]; out.end_state[9 * (size_t)k + i] = end[i]; }
+    }
+    const pct_trajgen_batch b{ out.centres.data(), out.radius.data(), out.seg_time.data(), out.orders.data(), out.seg_offsets.data(),
+                               out.start_state.data(), out.end_state.data(), K };
+    if (pct_bezier_generate_batch(&b, &params, out.polycoef.data(), out.row_stride, out.results.data()) != PCT_OK)
+        throw std::runtime_error(std::string("pct_bezier_generate_batch: ") + pct_last_error());
+    int64_t ok = 0;
+    for (const pct_trajgen_result &r : out.results) ok += r.status == PCT_GEN_OK ? 1 : 0;
+    return ok;
+}
 
 class ObstacleMap {
 public:
@@ -491,6 +548,29 @@ public:
         const int64_t not_free = certifyTrajectories(one, cert, max_depth);
         if (certificate) *certificate = cert[0];
         return not_free != 0;
+    }
+
+    // Corridor -> trajectory -> proof in one call: generate one candidate per time scale (generateTrajectories above; limits carries
+    // max_vel / max_acc and the iteration budget, its margin is replaced by `margin`, what is taken off every sphere radius), certify all
+    // of them against this map (certifyTrajectories: search_margin of setParam) and return the index of the shortest-duration candidate
+    // that is both PCT_GEN_OK and PCT_CERT_FREE, or -1 when there is none.  out.results and certificates hold both records of every
+    // candidate; out.rows(k) / out.batch() are what flies.
+    int64_t generateSafeTrajectory(const double *path, const double *radius, const double *times, const int32_t *orders, int32_t m,
+                                   const double *scales, int64_t K, const double start[9], const double end[9], const pct_trajgen_params &limits,
+                                   double margin, GeneratedTrajectories &out, std::vector<pct_traj_certificate> &certificates, int max_depth = 12)
+    {
+        pct_trajgen_params prm = limits;
+        prm.margin = margin;
+        generateTrajectories(path, radius, times, orders, m, scales, K, start, end, prm, out);
+        certificates.clear();
+        if (K == 0) return -1;
+        certifyTrajectories(out.batch(), certificates, max_depth);
+        int64_t best = -1;
+        for (int64_t k = 0; k < K; k++) {
+            if (out.results[(size_t)k].status != PCT_GEN_OK || certificates[(size_t)k].status != PCT_CERT_FREE) continue;
+            if (best < 0 || out.results[(size_t)k].duration < out.results[(size_t)best].duration) best = k;
+        }
+        return best;
     }
 
     // SURVEY 3.3 (config C5's build extension): the same threshold test on the raw control points of the committed trajectory

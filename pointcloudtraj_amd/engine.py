@@ -67,6 +67,118 @@ CERT_FREE, CERT_HIT, CERT_UNDECIDED, CERT_INVALID = 0, 1, 2, 3      # enum pct_c
 CERT_DTYPE = np.dtype([("status", np.int32), ("depth", np.int32), ("hit_seg", np.int32), ("hit_idx", np.uint32), ("hit_u", np.float64),
                        ("hit_d2", np.float64), ("min_d2", np.float64), ("pieces", np.int64)])
 
+GEN_OK, GEN_NOT_CONVERGED, GEN_INVALID = 0, 1, 2                    # enum pct_gen_status
+# pct_trajgen_result, 64 bytes (include/pct_trajgen.h, paragraph "Trajectory generation")
+GEN_RESULT_DTYPE = np.dtype([("status", np.int32), ("iterations", np.int32), ("cost", np.float64), ("duration", np.float64),
+                             ("r_prim", np.float64), ("r_dual", np.float64), ("sphere_slack", np.float64),
+                             ("max_vel_ctrl", np.float64), ("max_acc_ctrl", np.float64)])
+
+
+class TrajGenBatch(C.Structure):
+    """pct_trajgen_batch: B corridors with their time allocations and end states.  Host pointers for engine.bezier_generate
+    (engine.pack_corridors fills them), device pointers for engine.bezier_generate_device."""
+    _fields_ = [("centres", C.c_void_p), ("radius", C.c_void_p), ("seg_time", C.c_void_p), ("orders", C.c_void_p), ("seg_offsets", C.c_void_p),
+                ("start_state", C.c_void_p), ("end_state", C.c_void_p), ("B", C.c_int64)]
+
+
+class TrajGenParams(C.Structure):
+    """pct_trajgen_params"""
+    _fields_ = [("minimize_order", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("max_vel", C.c_double), ("max_acc", C.c_double),
+                ("margin", C.c_double), ("eps", C.c_double), ("rho", C.c_double)]
+
+
+def gen_params(minimize_order=3, max_iter=4000, check_every=25, max_vel=0.0, max_acc=0.0, margin=0.0, eps=1e-5, rho=0.0) -> TrajGenParams:
+    """minimize_order 3 = jerk (the reference's default); max_vel / max_acc <= 0 or inf: no limit; rho 0 = automatic"""
+    return TrajGenParams(int(minimize_order), int(max_iter), int(check_every), float(max_vel), float(max_acc), float(margin), float(eps), float(rho))
+
+
+def pack_corridors(corridors):
+    """A list of dict(centres [m, 3], radius [m], seg_time [m], orders [m], start [9], end [9]) -> (TrajGenBatch, arrays); `arrays` =
+    dict(centres, radius, seg_time, orders, seg_offsets, start_state, end_state) are the numpy arrays the struct points into: keep
+    them alive while it is used."""
+    cs = list(corridors)
+    nseg = [len(np.asarray(c["seg_time"]).reshape(-1)) for c in cs]
+    for c, m in zip(cs, nseg):
+        if np.asarray(c["centres"]).size != 3 * m or np.asarray(c["radius"]).size != m or np.asarray(c["orders"]).size != m:
+            raise ValueError("a corridor is centres [m, 3], radius [m], seg_time [m], orders [m]")
+        if np.asarray(c["start"]).size != 9 or np.asarray(c["end"]).size != 9:
+            raise ValueError("start and end are p, v, a: 9 values each")
+    offs = np.zeros(len(cs) + 1, np.int32)
+    offs[1:] = np.cumsum(nseg)
+
+    def cat(key, dt, w):
+        return np.ascontiguousarray(np.concatenate([np.asarray(c[key], dt).reshape(-1, w) for c in cs]) if cs else np.zeros((0, w), dt))
+    a = dict(centres=cat("centres", np.float64, 3), radius=cat("radius", np.float64, 1).reshape(-1), seg_time=cat("seg_time", np.float64, 1).reshape(-1),
+             orders=cat("orders", np.int32, 1).reshape(-1), seg_offsets=offs, start_state=cat("start", np.float64, 9), end_state=cat("end", np.float64, 9))
+    b = TrajGenBatch(*[a[k].ctypes.data for k in ("centres", "radius", "seg_time", "orders", "seg_offsets", "start_state", "end_state")], len(cs))
+    return b, a
+
+
+def corridor_fan(centres, radius, seg_time, orders, scales, start, end):
+    """one corridor under a list of time scales: the corridors engine.pack_corridors / engine.bezier_generate take, candidate k with
+    every segment time multiplied by scales[k]"""
+    T = np.asarray(seg_time, np.float64).reshape(-1)
+    return [dict(centres=centres, radius=radius, seg_time=T * float(sc), orders=orders, start=start, end=end) for sc in scales]
+
+
+def bezier_generate(corridors, params: TrajGenParams, row_stride=None):
+    """pct_bezier_generate_batch: one minimum-jerk Bezier trajectory per corridor (a list of dicts as engine.pack_corridors takes, or
+    its packed (TrajGenBatch, arrays) pair), all solved in one launch.  Returns (polycoef [total_seg, row_stride], results): the rows
+    in the layout the checks read -- with arrays["seg_time"], ["orders"], ["seg_offsets"] they are a pct_bezier_batch -- and a structured
+    array of engine.GEN_RESULT_DTYPE: status (GEN_OK, GEN_NOT_CONVERGED, GEN_INVALID), iterations, cost, duration, r_prim, r_dual,
+    sphere_slack, max_vel_ctrl, max_acc_ctrl."""
+    packed = isinstance(corridors, tuple) and len(corridors) == 2 and isinstance(corridors[0], TrajGenBatch)
+    batch, keep = corridors if packed else pack_corridors(corridors)
+    if row_stride is None:
+        od = keep["orders"]
+        row_stride = 3 * (int(np.clip(od.max() if len(od) else 5, 5, 12)) + 1)
+    coef = np.zeros((len(keep["seg_time"]), int(row_stride)), np.float64)
+    res = np.zeros(int(batch.B), GEN_RESULT_DTYPE)
+    _chk(lib().pct_bezier_generate_batch(C.byref(batch), C.byref(params), _ptr(coef), int(row_stride), _ptr(res)))
+    del keep
+    return coef, res
+
+
+def bezier_generate_device(fields, params: TrajGenParams, polycoef, results, stream=None):
+    """pct_bezier_generate_batch_dev on torch tensors, asynchronous on the current stream (or `stream`, a raw hipStream_t handle), no
+    host synchronisation, capturable.  fields: dict of device tensors centres [total, 3] f64, radius, seg_time [total] f64, orders
+    [total] i32, seg_offsets [B + 1] i32, start_state, end_state [B, 9] f64; polycoef: [total, row_stride] f64; results: B x 64 bytes
+    (uint8 [B, 64]; view the host copy as engine.GEN_RESULT_DTYPE).  polycoef.data_ptr() with the same seg_time / orders / seg_offsets
+    is the BezierBatch bezier_check_batch_device and bezier_certify_device take."""
+    import torch
+    want = dict(centres=torch.float64, radius=torch.float64, seg_time=torch.float64, orders=torch.int32, seg_offsets=torch.int32,
+                start_state=torch.float64, end_state=torch.float64)
+    for k, dt in want.items():
+        t = fields[k]
+        if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{k} must be a contiguous device tensor of {dt}")
+    B = int(fields["seg_offsets"].numel()) - 1
+    total = int(fields["seg_time"].numel())
+    if polycoef.dtype != torch.float64 or polycoef.dim() != 2 or polycoef.shape[0] != total or not polycoef.is_contiguous() or not polycoef.is_cuda:
+        raise ValueError("polycoef must be a contiguous float64 device tensor [total_seg, row_stride]")
+    if results.dtype != torch.uint8 or results.numel() != 64 * B or not results.is_contiguous() or not results.is_cuda:
+        raise ValueError("results must be a contiguous uint8 device tensor of B x 64 bytes")
+    if fields["start_state"].numel() != 9 * B or fields["end_state"].numel() != 9 * B or fields["centres"].numel() != 3 * total:
+        raise ValueError("start_state / end_state are [B, 9], centres is [total_seg, 3]")
+    batch = TrajGenBatch(*[fields[k].data_ptr() or None for k in ("centres", "radius", "seg_time", "orders", "seg_offsets", "start_state", "end_state")], B)
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    _chk(lib().pct_bezier_generate_batch_dev(C.byref(batch), C.byref(params), polycoef.data_ptr() or None, int(polycoef.shape[1]),
+                                             results.data_ptr() or None, stream or None))
+    return batch
+
+
+def time_allocation(centres, radius, start, end, init_vel, vel_mean, acc_mean):
+    """pct_time_allocation: the reference's timeAllocation (sim_planning_demo.cpp:603-686): one time per sphere of the corridor"""
+    c = np.ascontiguousarray(centres, np.float64).reshape(-1, 3)
+    r = np.ascontiguousarray(radius, np.float64).reshape(-1)
+    if len(r) != len(c):
+        raise ValueError("one radius per centre")
+    p0, p1, v0 = (np.ascontiguousarray(v, np.float64).reshape(3) for v in (start, end, init_vel))
+    out = np.zeros(len(c), np.float64)
+    _chk(lib().pct_time_allocation(_ptr(c), _ptr(r), len(c), _ptr(p0), _ptr(p1), _ptr(v0), float(vel_mean), float(acc_mean), _ptr(out)))
+    return out
+
 
 def pack_trajectories(trajectories, t_start=None):
     """A list of (polycoef, seg_time, orders) -> (BezierBatch, arrays): the rows one after another, padded with zeros to a common
@@ -255,6 +367,9 @@ def lib():
                                                  vp, vp, vp, vp, vp]
         L.pct_bezier_certify_batch.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, i32, i64, vp, vp]
         L.pct_bezier_certify_batch_dev.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, i32, i64, vp, vp, vp]
+        L.pct_bezier_generate_batch.argtypes = [C.POINTER(TrajGenBatch), C.POINTER(TrajGenParams), f64p, i64, vp]
+        L.pct_bezier_generate_batch_dev.argtypes = [C.POINTER(TrajGenBatch), C.POINTER(TrajGenParams), vp, i64, vp, vp]
+        L.pct_time_allocation.argtypes = [f64p, f64p, i64, f64p, f64p, f64p, C.c_double, C.c_double, f64p]
         L.pct_radius_count_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp]
         L.pct_cloud_reserve_queries.argtypes = [vp, i64]
         L.pct_plan_create_nn.argtypes = [vp, i32, i64, C.POINTER(vp)]
