@@ -2318,9 +2318,10 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     for (int k = 0; k < 3; k++) ext[k] = std::max((double)hi[k] - (double)lo[k], 0.0);
     double h = cell_size;
     if (!(h > 0)) {
-        // target points per cell: with the 2x2x2-block-first search (kernels.hpp coop_nn_search stage 0) larger cells win --
+        // target points per cell: with the 2x2x2-block-first search (kernels.hpp coop_stage0) larger cells win --
         // the block then decides 99 % of the queries (a wave needs all 8 of its queries decided to skip the cube);
-        // same-box A/B on the 10 M uniform cloud: ppc 2 + cube first 0.169 ms, ppc 6 + block first 0.134 ms per 1 M queries
+        // same-box A/B on the 10 M uniform cloud against the retired cube-first search at ppc 2: 0.169 ms, ppc 6 + block first 0.134 ms
+        // per 1 M queries (retired variants)
         double ppc = 6.0;
         // a cloud that carried the pyramid at its previous build (surfaces, clusters: most cells empty) is rebuilt with cells of
         // half the volume: the walk then scans 52 instead of 89 points per query for one more node visit (10 M pillar surfaces:
@@ -2360,8 +2361,6 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     // 3. counting sort
     PCTCHK(sort_into_cells(c, G));
     PCTCHK(build_pyramid(c, G));
-    G.octant_first = 1;
-    if (const char *eo = std::getenv("PCT_OCTANT_FIRST")) G.octant_first = std::atoi(eo) != 0;
     // block table for stage 0 of the dense batch kernel (kernels.hpp block_corner_kernel).  OFF by default -- measured slower on the
     // headline step (0.126-0.131 ms against 0.120-0.121, profiles/r03_ab_block_table.txt): the 6.7 MB cell table it replaces is served
     // by the L2s, the 56 MB of corner entries are not, and one line that misses costs more than four that hit.  PCT_BLOCK_TABLE=1
@@ -2371,7 +2370,7 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
         const char *et = std::getenv("PCT_BLOCK_TABLE");
         const bool table_on = et ? std::atoi(et) != 0 : false;
         const uint64_t ncorners = (uint64_t)(G.gx + 1) * (uint64_t)(G.gy + 1) * (uint64_t)(G.gz + 1);
-        if (table_on && G.octant_first && !c->has_pyr && ncorners < 0x7FFFFFF0ull) {
+        if (table_on && !c->has_pyr && ncorners < 0x7FFFFFF0ull) {
             PCTCHK(c->blocks.reserve((size_t)(2 * ncorners)));
             block_corner_kernel<<<ceil_div((int64_t)ncorners, 256), 256, 0, s>>>(G, c->cell_start, c->blocks, (uint32_t)ncorners);
             HIPCHK(hipGetLastError());

@@ -817,7 +817,6 @@ struct GridDesc {
     double oxd, oyd, ozd, hd;  // fp64 face positions for the termination bound
     int gx, gy, gz;
     uint32_t ncells;
-    int octant_first;          // cooperative NN: try the 2x2x2 block on the query's side before the 3x3x3 cube
     // block table (optional, nullptr = none): for every corner (u, v, w) of the cell lattice, u in [0, gx] etc., the four x-runs of the
     // 2x2x2 block of cells around it -- entry 2*i = the runs' first records, 2*i + 1 = one past their last (block_corner_kernel)
     const uint4 *blocks;
@@ -1140,18 +1139,32 @@ __device__ __forceinline__ uint32_t xcd_contiguous_block(uint32_t b, uint32_t nb
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
 
-// distance from q to the nearest face of the cube of cells [c-r, c+r]^3 that still has cells behind it
-// (+inf when the cube covers the whole grid), minus the slack that covers the fp32 cell assignment
-__device__ __forceinline__ double cube_bound(const GridDesc &G, int cx, int cy, int cz, int r, double qx, double qy, double qz)
+// the cell of a query (or of any fp32 position): cell_coord per axis
+__device__ __forceinline__ void query_cell(const GridDesc &G, float qxf, float qyf, float qzf, int &cx, int &cy, int &cz)
+{
+    cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
+    cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
+    cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
+}
+
+// distance from q to the nearest face of the box of cells [xa, xb] x [ya, yb] x [za, zb] that still has cells behind it
+// (+inf when the box covers the whole grid), minus the slack that covers the fp32 cell assignment.  The ONE termination bound of the
+// cell-pruned searches: a search that has seen every record of the box stops once its best (or k-th best) is within the bound.
+__device__ __forceinline__ double box_bound(const GridDesc &G, int xa, int xb, int ya, int yb, int za, int zb, double qx, double qy, double qz)
 {
     double bound = __builtin_huge_val();
-    if (cx - r > 0) bound = fmin(bound, qx - (G.oxd + (double)(cx - r) * G.hd));
-    if (cx + r < G.gx - 1) bound = fmin(bound, (G.oxd + (double)(cx + r + 1) * G.hd) - qx);
-    if (cy - r > 0) bound = fmin(bound, qy - (G.oyd + (double)(cy - r) * G.hd));
-    if (cy + r < G.gy - 1) bound = fmin(bound, (G.oyd + (double)(cy + r + 1) * G.hd) - qy);
-    if (cz - r > 0) bound = fmin(bound, qz - (G.ozd + (double)(cz - r) * G.hd));
-    if (cz + r < G.gz - 1) bound = fmin(bound, (G.ozd + (double)(cz + r + 1) * G.hd) - qz);
+    if (xa > 0) bound = fmin(bound, qx - (G.oxd + (double)xa * G.hd));
+    if (xb < G.gx - 1) bound = fmin(bound, (G.oxd + (double)(xb + 1) * G.hd) - qx);
+    if (ya > 0) bound = fmin(bound, qy - (G.oyd + (double)ya * G.hd));
+    if (yb < G.gy - 1) bound = fmin(bound, (G.oyd + (double)(yb + 1) * G.hd) - qy);
+    if (za > 0) bound = fmin(bound, qz - (G.ozd + (double)za * G.hd));
+    if (zb < G.gz - 1) bound = fmin(bound, (G.ozd + (double)(zb + 1) * G.hd) - qz);
     return bound == __builtin_huge_val() ? bound : bound - G.hd * (1.0 / 256.0);
+}
+// ... of the cube of cells [c-r, c+r]^3
+__device__ __forceinline__ double cube_bound(const GridDesc &G, int cx, int cy, int cz, int r, double qx, double qy, double qz)
+{
+    return box_bound(G, cx - r, cx + r, cy - r, cy + r, cz - r, cz + r, qx, qy, qz);
 }
 
 // -------------------------------------------------------------------------------------
@@ -1243,6 +1256,72 @@ __device__ __forceinline__ void st_at(T *__restrict__ base, uint32_t i, T v)
     else base[i] = v;
 }
 
+// ---- the parts every 8-lanes-per-query batch kernel of the cell index is made of (this file, knn.hpp, rsearch.hpp, pyramid.hpp) ----
+// The batch slot of the calling lane's group, GROUPS queries per block: the blocks of a sorted batch in XCD-contiguous order.
+template <int GROUPS>
+__device__ __forceinline__ uint32_t coop_slot(const float4 *qsorted)
+{
+    const uint32_t bslot = qsorted ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
+    return bslot * GROUPS + (threadIdx.x / kCoop);
+}
+
+// The query of batch slot `slot`; returns the row its answer goes to.  Sorted batch: query and row in one 16-byte record.
+// (No __restrict__ on the parameters of these helpers: the kernels' own pointers carry it, and a second scope on the inlined copy lets the
+// compiler merge the two branches' loads -- the dense kernel then fetched its sorted record as four dwords.)
+template <bool NARROW = false>
+__device__ __forceinline__ uint32_t coop_fetch_query(const float4 *qsorted, const float *q, uint32_t slot, float &qxf, float &qyf, float &qzf)
+{
+    uint32_t t = slot;
+    if (qsorted) {
+        const float4 R = ld_at<NARROW>(qsorted, slot);
+        qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
+    } else {
+        qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
+    }
+    return t;
+}
+
+// One lane's run [s, e) of row (yy, zz) over the cells [x0, x1]; a row that is switched off (!ok: beyond the rows of its box, or one
+// that coincides with another at the grid's border) reads row 0 and comes out empty.
+__device__ __forceinline__ void row_run(const GridDesc &G, const uint32_t *cell_start, bool ok, int yy, int zz, int x0, int x1,
+                                        uint32_t &s, uint32_t &e)
+{
+    const uint32_t row = ok ? cell_lin(G, 0, yy, zz) : 0u;
+    const uint32_t a = cell_start[row + x0], b = cell_start[row + x1 + 1];
+    s = a;
+    e = ok ? b : a;
+}
+
+// The x-runs of row (yy, zz) that belong to the shell of Chebyshev radius r around cell (cx, cy, cz), f(s, e) for each: the whole row
+// from cx - r to cx + r, clamped to the grid, where the row lies on a y or z face of the cube (or `full`: the cube itself is wanted), else the
+// two end cells cx - r and cx + r, each where the grid has it.  The callers loop over the rows of the clamped cube in their own order.
+template <typename F>
+__device__ __forceinline__ void shell_row_runs(const GridDesc &G, const uint32_t *cell_start, int cx, int cy, int cz, int r, bool full,
+                                               int yy, int zz, const F &f)
+{
+    const int xl = cx - r, xh = cx + r;
+    const uint32_t row = cell_lin(G, 0, yy, zz);
+    if (full || zz == cz - r || zz == cz + r || yy == cy - r || yy == cy + r) {
+        f(cell_start[row + max(xl, 0)], cell_start[row + min(xh, G.gx - 1) + 1]);
+    } else {
+        if (xl >= 0) f(cell_start[row + xl], cell_start[row + xl + 1]);
+        if (xh <= G.gx - 1) f(cell_start[row + xh], cell_start[row + xh + 1]);
+    }
+}
+
+// The two work counters of an instrumented launch: summed over the wave, one pair of atomics per wave into the block's slot.
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (unsigned long long)__shfl_xor((long long)v, off, kWave);
+    return v;
+}
+__device__ __forceinline__ void commit_work(WorkCounters *work, uint32_t npts, uint32_t nruns)
+{
+    const unsigned long long a = wave_sum(npts), b = wave_sum(nruns);
+    if ((threadIdx.x & 63) == 0) { WorkCounters *w = work + (blockIdx.x & (kWorkSlots - 1)); atomicAdd(&w->points, a); atomicAdd(&w->cells, b); }
+}
+
 // exact scan of [s, e) shared by the 8 lanes of a group (lane `sub` takes s+sub, s+sub+8, ...)
 __device__ __forceinline__ void coop_scan_exact(const float4 *__restrict__ pts, uint32_t s, uint32_t e, uint32_t sub, double qx,
                                                 double qy, double qz, double &bd, uint32_t &bi)
@@ -1255,38 +1334,21 @@ __device__ __forceinline__ void coop_scan_exact(const float4 *__restrict__ pts, 
     }
 }
 
-// rows of the cube (full = true) or of the shell of Chebyshev radius r around cell (cx,cy,cz), shared by 8 lanes
+// rows of the shell of Chebyshev radius r around cell (cx,cy,cz), shared by 8 lanes
 template <bool COUNT>
-__device__ __forceinline__ void coop_scan_cube_or_shell(const GridDesc &G, const float4 *__restrict__ pts,
-                                                        const uint32_t *__restrict__ cell_start, int cx, int cy, int cz, int r,
-                                                        bool full, uint32_t sub, double qx, double qy, double qz, double &bd,
-                                                        uint32_t &bi, uint32_t &npts, uint32_t &nruns)
+__device__ __forceinline__ void coop_scan_shell(const GridDesc &G, const float4 *__restrict__ pts,
+                                                const uint32_t *__restrict__ cell_start, int cx, int cy, int cz, int r,
+                                                uint32_t sub, double qx, double qy, double qz, double &bd,
+                                                uint32_t &bi, uint32_t &npts, uint32_t &nruns)
 {
-    const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
     const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
     const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
-    for (int zz = z0; zz <= z1; zz++) {
-        const bool zface = (zz == cz - r) || (zz == cz + r);
-        for (int yy = y0; yy <= y1; yy++) {
-            const uint32_t row = cell_lin(G, 0, yy, zz);
-            if (full || zface || yy == cy - r || yy == cy + r) {
-                const uint32_t s = cell_start[row + x0], e = cell_start[row + x1 + 1];
+    for (int zz = z0; zz <= z1; zz++)
+        for (int yy = y0; yy <= y1; yy++)
+            shell_row_runs(G, cell_start, cx, cy, cz, r, false, yy, zz, [&](uint32_t s, uint32_t e) {
                 if (COUNT && sub == 0) { npts += e - s; nruns += 1; }
                 coop_scan_exact(pts, s, e, sub, qx, qy, qz, bd, bi);
-            } else {
-                if (cx - r >= 0) {
-                    const uint32_t s = cell_start[row + cx - r], e = cell_start[row + cx - r + 1];
-                    if (COUNT && sub == 0) { npts += e - s; nruns += 1; }
-                    coop_scan_exact(pts, s, e, sub, qx, qy, qz, bd, bi);
-                }
-                if (cx + r <= G.gx - 1) {
-                    const uint32_t s = cell_start[row + cx + r], e = cell_start[row + cx + r + 1];
-                    if (COUNT && sub == 0) { npts += e - s; nruns += 1; }
-                    coop_scan_exact(pts, s, e, sub, qx, qy, qz, bd, bi);
-                }
-            }
-        }
-    }
+            });
 }
 
 // fp32 screening of NR x-runs by the 8 lanes of a group (min, runner-up, position), then the exact fp64 winner: if the
@@ -1427,94 +1489,7 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
     }
 }
 
-// The search itself, shared by the batch kernel and the low-latency inflation kernel: all 8 lanes of
-// a group call it with the same query and their own `sub`; every lane returns the same (bd, bi).
-template <bool COUNT>
-__device__ __forceinline__ void coop_nn_search(const GridDesc &G, const float4 *__restrict__ pts,
-                                               const uint32_t *__restrict__ cell_start, float qxf, float qyf, float qzf,
-                                               uint32_t sub, double &bd, uint32_t &bi, uint32_t &npts, uint32_t &nruns)
-{
-    const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-    const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
-    const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
-    const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
-    bd = __builtin_huge_val();
-    bi = kNoIndex;
-    if (G.octant_first) {   // ---- stage 0: the 2x2x2 block of cells on the query's side of its own cell = 4 x-runs ----
-        // About 27/8 fewer points and 9/4 fewer rows than the 3x3x3 cube; it decides the query whenever the best point found is
-        // closer than the block's nearest face that still has cells behind it (>= half a cell away by construction).  Which
-        // side is taken only affects how often that happens, never the result: the bound below is computed from the block
-        // actually scanned.
-        const float fx = (qxf - G.ox) * G.inv_h - (float)cx, fy = (qyf - G.oy) * G.inv_h - (float)cy, fz = (qzf - G.oz) * G.inv_h - (float)cz;
-        const int xa = max(fx < 0.5f ? cx - 1 : cx, 0), xb = min(fx < 0.5f ? cx : cx + 1, G.gx - 1);
-        const int ya = max(fy < 0.5f ? cy - 1 : cy, 0), yb = min(fy < 0.5f ? cy : cy + 1, G.gy - 1);
-        const int za = max(fz < 0.5f ? cz - 1 : cz, 0), zb = min(fz < 0.5f ? cz : cz + 1, G.gz - 1);
-        uint32_t rs[4], re[4];
-        {
-            const int ri = (int)sub & 3;                              // lanes 4..7 repeat lanes 0..3 (same addresses: no extra access)
-            const bool ok = !((ri >> 1) && zb == za) && !((ri & 1) && yb == ya);
-            const uint32_t row = cell_lin(G, 0, (ri & 1) ? yb : ya, (ri >> 1) ? zb : za);
-            const uint32_t a = cell_start[row + xa], b = cell_start[row + xb + 1];
-            const uint32_t my_s = a, my_e = ok ? b : a;
-            if (COUNT && sub < 4) { npts += my_e - my_s; nruns += ok ? 1u : 0u; }
-#pragma unroll
-            for (int k = 0; k < 4; k++) { rs[k] = (uint32_t)__shfl((int)my_s, k, kCoop); re[k] = (uint32_t)__shfl((int)my_e, k, kCoop); }
-        }
-        coop_screen_rows<4, 2>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
-        double bound = __builtin_huge_val();
-        if (xa > 0) bound = fmin(bound, qx - (G.oxd + (double)xa * G.hd));
-        if (xb < G.gx - 1) bound = fmin(bound, (G.oxd + (double)(xb + 1) * G.hd) - qx);
-        if (ya > 0) bound = fmin(bound, qy - (G.oyd + (double)ya * G.hd));
-        if (yb < G.gy - 1) bound = fmin(bound, (G.oyd + (double)(yb + 1) * G.hd) - qy);
-        if (za > 0) bound = fmin(bound, qz - (G.ozd + (double)za * G.hd));
-        if (zb < G.gz - 1) bound = fmin(bound, (G.ozd + (double)(zb + 1) * G.hd) - qz);
-        if (bound == __builtin_huge_val()) return;                    // the block covers the whole grid
-        bound -= G.hd * (1.0 / 256.0);                                // same slack as cube_bound (fp32 cell assignment)
-        if (bound > 0.0 && bd <= bound * bound) return;
-    }
-    {   // ---- first cube: 3x3x3 cells = 9 x-runs ----
-        const int x0 = max(cx - 1, 0), x1 = min(cx + 1, G.gx - 1);
-        // lane `sub` fetches row `sub`'s bounds, lane 0 also row 8
-        uint32_t my_s = 0, my_e = 0, s8 = 0, e8 = 0;
-        {
-            const int zz = cz + (int)sub / 3 - 1, yy = cy + (int)sub % 3 - 1;
-            const bool ok = zz >= 0 && zz < G.gz && yy >= 0 && yy < G.gy;
-            const uint32_t row = ok ? cell_lin(G, 0, yy, zz) : 0u;
-            const uint32_t a = cell_start[row + x0], b = cell_start[row + x1 + 1];
-            my_s = a;
-            my_e = ok ? b : a;
-            const int z8 = cz + 1, y8 = cy + 1;
-            const bool ok8 = z8 < G.gz && y8 < G.gy;
-            const uint32_t row8 = ok8 ? cell_lin(G, 0, y8, z8) : 0u;
-            const uint32_t a8 = cell_start[row8 + x0], b8 = cell_start[row8 + x1 + 1];   // same address in all 8 lanes: one access
-            s8 = a8;
-            e8 = ok8 ? b8 : a8;
-            if (COUNT && sub == 0) {
-                npts += e8 - s8; nruns += ok8 ? 1u : 0u;
-            }
-            if (COUNT) {
-                // every lane adds its own row; summed over the wave at the end
-                npts += my_e - my_s; nruns += ok ? 1u : 0u;
-            }
-        }
-        uint32_t rs[9], re[9];
-#pragma unroll
-        for (int k = 0; k < 8; k++) { rs[k] = (uint32_t)__shfl((int)my_s, k, kCoop); re[k] = (uint32_t)__shfl((int)my_e, k, kCoop); }
-        rs[8] = s8; re[8] = e8;
-
-        coop_screen_rows<9, 1>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
-    }
-    for (int r = 1;; r++) {
-        if (r > 1) {   // ---- shell r (rare on dense clouds): rows walked in the same order by the whole group ----
-            coop_scan_cube_or_shell<COUNT>(G, pts, cell_start, cx, cy, cz, r, false, sub, qx, qy, qz, bd, bi, npts, nruns);
-            coop_argmin8(bd, bi);
-        }
-        const double bound = cube_bound(G, cx, cy, cz, r, qx, qy, qz);
-        if (bound == __builtin_huge_val() || (bound > 0.0 && bd <= bound * bound)) break;
-    }
-}
-
-// ---- the same search with a WAVE-cooperative fallback (the batch kernel's default) -------------------------------------------
+// ---- the dense batch search: stage 0, then a WAVE-cooperative fallback -------------------------------------------------------
 // Stage 0 decides ~99 % of the queries at 6 points per cell, but a wave holds 8 queries and used to run the 3x3x3 cube for all of
 // them -- 8 lanes per query, the 9 rows of ~18 points taken 8 at a time -- as soon as ONE was undecided: 0.99^8 = 8 % of the waves,
 // 15 % of the kernel's time (18 of 124 us on the 10 M-point cloud).  Here the whole wave turns to each undecided query in turn:
@@ -1530,9 +1505,7 @@ __device__ __forceinline__ void coop_nn_search(const GridDesc &G, const float4 *
 struct Stage0Block { int cx, cy, cz; float fx, fy, fz; int xa, xb, ya, yb, za, zb; };
 __device__ __forceinline__ void stage0_block(const GridDesc &G, float qxf, float qyf, float qzf, Stage0Block &B)
 {
-    B.cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
-    B.cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
-    B.cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
+    query_cell(G, qxf, qyf, qzf, B.cx, B.cy, B.cz);
     B.fx = (qxf - G.ox) * G.inv_h - (float)B.cx; B.fy = (qyf - G.oy) * G.inv_h - (float)B.cy; B.fz = (qzf - G.oz) * G.inv_h - (float)B.cz;
     B.xa = max(B.fx < 0.5f ? B.cx - 1 : B.cx, 0); B.xb = min(B.fx < 0.5f ? B.cx : B.cx + 1, G.gx - 1);
     B.ya = max(B.fy < 0.5f ? B.cy - 1 : B.cy, 0); B.yb = min(B.fy < 0.5f ? B.cy : B.cy + 1, G.gy - 1);
@@ -1567,6 +1540,13 @@ __device__ __forceinline__ float stage0_accept_threshold(const GridDesc &G, floa
     return fmaxf(fmaxf(fabsf(fx), fabsf(fy)), fabsf(fz)) < 2.0f ? (bc - 0.015625f) * (float)G.hd * 0.999999f : 0.0f;
 }
 
+// The exact test on the bound of the block that was scanned (box_bound): decided when the block covers the whole grid (+inf) or the best
+// distance is within the bound.
+__device__ __forceinline__ bool block_undecided(double bound, double bd)
+{
+    return bound != __builtin_huge_val() && !(bound > 0.0 && bd <= bound * bound);
+}
+
 // The exact test (rare: the 1/64-cell band, the undecided queries, queries outside the grid): is the query still undecided after its
 // block gave best distance bd?  The block's bounds are recomputed from the query (stage0_block) instead of being carried across the
 // screening.
@@ -1577,19 +1557,10 @@ __device__ __forceinline__ bool block_leaves_undecided(const GridDesc &G, float 
     Stage0Block B;
     asm volatile("" : "+v"(qxf), "+v"(qyf), "+v"(qzf));
     stage0_block(G, qxf, qyf, qzf, B);
-    double bound = __builtin_huge_val();
-    if (B.xa > 0) bound = fmin(bound, qx - (G.oxd + (double)B.xa * G.hd));
-    if (B.xb < G.gx - 1) bound = fmin(bound, (G.oxd + (double)(B.xb + 1) * G.hd) - qx);
-    if (B.ya > 0) bound = fmin(bound, qy - (G.oyd + (double)B.ya * G.hd));
-    if (B.yb < G.gy - 1) bound = fmin(bound, (G.oyd + (double)(B.yb + 1) * G.hd) - qy);
-    if (B.za > 0) bound = fmin(bound, qz - (G.ozd + (double)B.za * G.hd));
-    if (B.zb < G.gz - 1) bound = fmin(bound, (G.ozd + (double)(B.zb + 1) * G.hd) - qz);
-    if (bound == __builtin_huge_val()) return false;              // the block covers the whole grid
-    bound -= G.hd * (1.0 / 256.0);                                // same slack as cube_bound (fp32 cell assignment)
-    return !(bound > 0.0 && bd <= bound * bound);
+    return block_undecided(box_bound(G, B.xa, B.xb, B.ya, B.yb, B.za, B.zb, qx, qy, qz), bd);
 }
 
-// stage 0 of coop_nn_search alone; returns true when the query is still undecided
+// stage 0: the 2x2x2 block of cells on the query's side of its own cell = 4 x-runs; returns true when the query is still undecided
 template <bool COUNT, bool NARROW>
 __device__ __forceinline__ bool coop_stage0(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
                                             float qxf, float qyf, float qzf, uint32_t sub, double &bd, uint32_t &bi, uint32_t &npts,
@@ -1675,14 +1646,9 @@ __device__ __forceinline__ void wave_remainder_search(const GridDesc &G, const f
 {
     const uint32_t lane = threadIdx.x & 63;
     const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-    const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
-    const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
-    const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
-    // the block, as coop_stage0 chose it
-    const float fx = (qxf - G.ox) * G.inv_h - (float)cx, fy = (qyf - G.oy) * G.inv_h - (float)cy, fz = (qzf - G.oz) * G.inv_h - (float)cz;
-    const int xa = max(fx < 0.5f ? cx - 1 : cx, 0), xb = min(fx < 0.5f ? cx : cx + 1, G.gx - 1);
-    const int ya = max(fy < 0.5f ? cy - 1 : cy, 0), yb = min(fy < 0.5f ? cy : cy + 1, G.gy - 1);
-    const int za = max(fz < 0.5f ? cz - 1 : cz, 0), zb = min(fz < 0.5f ? cz : cz + 1, G.gz - 1);
+    Stage0Block B;                                                    // the block, as coop_stage0 chose it
+    stage0_block(G, qxf, qyf, qzf, B);
+    const int cx = B.cx, cy = B.cy, cz = B.cz;
     // distance along one axis from q to cell c of g (0 inside), a face counting only where the grid has cells behind it, minus the slack
     auto gap = [&](int c, int g, double o, double q) {
         const double ninf = -__builtin_huge_val();
@@ -1695,10 +1661,10 @@ __device__ __forceinline__ void wave_remainder_search(const GridDesc &G, const f
         const int l = lane < 9 ? (int)lane : 0;
         const int zz = cz + l / 3 - 1, yy = cy + l % 3 - 1;
         const bool ok = lane < 9 && zz >= 0 && zz < G.gz && yy >= 0 && yy < G.gy;
-        const bool block_row = yy >= ya && yy <= yb && zz >= za && zz <= zb;
+        const bool block_row = yy >= B.ya && yy <= B.yb && zz >= B.za && zz <= B.zb;
         const double gy = gap(yy, G.gy, G.oyd, qy), gz = gap(zz, G.gz, G.ozd, qz);
         auto reach = [&](int c) {
-            const bool valid = ok && c >= 0 && c <= G.gx - 1 && !(block_row && c >= xa && c <= xb);
+            const bool valid = ok && c >= 0 && c <= G.gx - 1 && !(block_row && c >= B.xa && c <= B.xb);
             const double gxx = gap(c, G.gx, G.oxd, qx);
             return valid & !(((gxx * gxx + gy * gy) + gz * gz) * (1.0 - 0x1p-40) > bd);
         };
@@ -1782,12 +1748,11 @@ __device__ __forceinline__ void coop_finish_shells(const GridDesc &G, const floa
                                                    uint32_t &nruns)
 {
     const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-    const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
-    const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
-    const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
+    int cx, cy, cz;
+    query_cell(G, qxf, qyf, qzf, cx, cy, cz);
     for (int r = 1;; r++) {
         if (r > 1) {
-            coop_scan_cube_or_shell<COUNT>(G, pts, cell_start, cx, cy, cz, r, false, sub, qx, qy, qz, bd, bi, npts, nruns);
+            coop_scan_shell<COUNT>(G, pts, cell_start, cx, cy, cz, r, sub, qx, qy, qz, bd, bi, npts, nruns);
             coop_argmin8(bd, bi);
         }
         const double bound = cube_bound(G, cx, cy, cz, r, qx, qy, qz);
@@ -1835,7 +1800,7 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
 // maximum over all its paths, and stage 0 is no longer the one that sets it.
 // NARROW (chosen per launch on the host: narrow_offsets_fit, gridbuild.hpp) addresses the records, the run bounds, the sorted query and
 // the two results with 32-bit byte offsets from their scalar bases (ld_at / st_at); only the TAIL instantiation of coop_screen_rows takes
-// it -- the cube-first form, the pyramid's stage 0 and the rare paths (exact rescans, the wave's remainder search, shells) keep 64-bit addresses.
+// it -- the pyramid's stage 0 and the rare paths (exact rescans, the wave's remainder search, shells) keep 64-bit addresses.
 // BLOCK (threads per block, chosen per cloud on the host: pct_cloud::nn_block): nothing in the kernel is shared between the waves of a
 // block -- no LDS, no barrier -- so the block is only the unit in which the dispatcher hands out wave slots, and a block of four waves
 // waits until a CU has four of its 28 slots free at once.  Blocks of kNNBlock = 128 threads (two waves, 16 queries) where the cloud's
@@ -1854,54 +1819,20 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(7, 7))) v
                                                            WorkCounters *__restrict__ work)
 {
     const uint32_t sub = threadIdx.x & (kCoop - 1);
-    const uint32_t bslot = qsorted ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t slot = bslot * (BLOCK / kCoop) + (threadIdx.x / kCoop);
+    const uint32_t slot = coop_slot<BLOCK / kCoop>(qsorted);
     uint32_t npts = 0, nruns = 0;
-    if (G.octant_first) {                             // wave-cooperative fallback (see above); every lane of the wave stays in step
-        const bool live = slot < Q;
-        uint32_t t = slot;
-        float qxf = 0.0f, qyf = 0.0f, qzf = 0.0f;
-        if (live) {
-            if (qsorted) {
-                const float4 R = ld_at<NARROW>(qsorted, slot);
-                qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
-            } else {
-                qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
-            }
-        }
-        double bd;
-        uint32_t bi;
-        coop_wave_search<COUNT, NARROW>(G, pts, cell_start, live, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
-        if (live && sub == 0) {
-            st_at<NARROW>(out_idx, t, reported_index(bd, bi, index_base));
-            st_at<NARROW>(out_d2, t, bd);
-        }
-    } else if (slot < Q) {                            // uniform within a group of 8 lanes
-        uint32_t t = slot;
-        float qxf, qyf, qzf;
-        if (qsorted) {                                // binned batch: query and output slot in one record
-            const float4 R = qsorted[slot];
-            qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
-        } else {
-            qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
-        }
-        double bd;
-        uint32_t bi;
-        coop_nn_search<COUNT>(G, pts, cell_start, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
-        if (sub == 0) {
-            out_idx[t] = reported_index(bd, bi, index_base);
-            out_d2[t] = bd;
-        }
+    const bool live = slot < Q;                       // every lane of the wave stays in step: the fallback is wave-cooperative (see above)
+    uint32_t t = slot;
+    float qxf = 0.0f, qyf = 0.0f, qzf = 0.0f;
+    if (live) t = coop_fetch_query<NARROW>(qsorted, q, slot, qxf, qyf, qzf);
+    double bd;
+    uint32_t bi;
+    coop_wave_search<COUNT, NARROW>(G, pts, cell_start, live, qxf, qyf, qzf, sub, bd, bi, npts, nruns);
+    if (live && sub == 0) {
+        st_at<NARROW>(out_idx, t, reported_index(bd, bi, index_base));
+        st_at<NARROW>(out_d2, t, bd);
     }
-    if (COUNT) {
-        unsigned long long a = npts, b = nruns;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            a += (unsigned long long)__shfl_xor((long long)a, off, kWave);
-            b += (unsigned long long)__shfl_xor((long long)b, off, kWave);
-        }
-        if ((threadIdx.x & 63) == 0) { WorkCounters *w = work + (blockIdx.x & (kWorkSlots - 1)); atomicAdd(&w->points, a); atomicAdd(&w->cells, b); }
-    }
+    if (COUNT) commit_work(work, npts, nruns);
 }
 
 // The cells [x0, x1] x [y0, y1] x [z0, z1] that can hold a point within r of the query: the box every kernel that walks a ball's rows
@@ -1938,18 +1869,11 @@ __global__ __launch_bounds__(256) void count_grid_coop_kernel(GridDesc G, const 
                                                               WorkCounters *__restrict__ work)
 {
     const uint32_t sub = threadIdx.x & (kCoop - 1);
-    const uint32_t bslot = qsorted ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t slot = bslot * (256 / kCoop) + (threadIdx.x / kCoop);
+    const uint32_t slot = coop_slot<256 / kCoop>(qsorted);
     uint32_t npts = 0, nruns = 0;
     if (slot < Q) {                                   // uniform within a group of 8 lanes
-        uint32_t t = slot;
         float qxf, qyf, qzf;
-        if (qsorted) {                                // binned batch: query and output slot in one record
-            const float4 R = qsorted[slot];
-            qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
-        } else {
-            qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
-        }
+        const uint32_t t = coop_fetch_query(qsorted, q, slot, qxf, qyf, qzf);
         const float rf = rad[t];
         const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
         const double r2 = (double)rf * (double)rf;
@@ -1968,9 +1892,7 @@ __global__ __launch_bounds__(256) void count_grid_coop_kernel(GridDesc G, const 
             for (int h = 0; h < 2; h++) {
                 const int k = base + 8 * h + (int)sub;
                 const bool ok = k < nrows;
-                const uint32_t row = ok ? cell_lin(G, 0, y0 + k % ny, z0 + k / ny) : 0u;
-                const uint32_t a = cell_start[row + x0], b = cell_start[row + x1 + 1];
-                bs[h] = a; be[h] = ok ? b : a;
+                row_run(G, cell_start, ok, y0 + k % ny, z0 + k / ny, x0, x1, bs[h], be[h]);
                 if (COUNT) { npts += be[h] - bs[h]; nruns += ok ? 1u : 0u; }
             }
 #pragma unroll
@@ -2010,15 +1932,7 @@ __global__ __launch_bounds__(256) void count_grid_coop_kernel(GridDesc G, const 
         for (int off = 1; off < kCoop; off <<= 1) c += (uint32_t)__shfl_xor((int)c, off, kWave);
         if (sub == 0) count[t] = c;
     }
-    if (COUNT) {
-        unsigned long long a = npts, b = nruns;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            a += (unsigned long long)__shfl_xor((long long)a, off, kWave);
-            b += (unsigned long long)__shfl_xor((long long)b, off, kWave);
-        }
-        if ((threadIdx.x & 63) == 0) { WorkCounters *w = work + (blockIdx.x & (kWorkSlots - 1)); atomicAdd(&w->points, a); atomicAdd(&w->cells, b); }
-    }
+    if (COUNT) commit_work(work, npts, nruns);
 }
 
 // =====================================================================================
@@ -2260,7 +2174,7 @@ __device__ __forceinline__ void block_argmin256(double &d, uint32_t &i, double *
 // groups of 8 lanes each take every 32nd row, and the block folds its candidates after each shell.
 // stop_d2: when only the radius is wanted the search may stop once everything unseen is farther than
 // max_radius + search_margin (the radius is then max_radius whatever lies beyond); +inf = exact NN.
-// Same arithmetic and the same termination bound as coop_nn_search.
+// Same arithmetic and the same termination bound (cube_bound) as the batch kernel's shell walk.
 // INFLATE = false: plain nearest neighbour of the (fp32-valued) points in qpts -- no early-out, no radius.
 // The block-wide search itself: nearest obstacle point of the fp32-narrowed (px, py, pz); every thread returns the winner.
 __device__ __forceinline__ void block_nn_search(const GridDesc &G, const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start,
@@ -2270,26 +2184,18 @@ __device__ __forceinline__ void block_nn_search(const GridDesc &G, const float4 
     const uint32_t sub = threadIdx.x & (kCoop - 1), grp = threadIdx.x / kCoop;   // 32 groups
     const float qxf = (float)px, qyf = (float)py, qzf = (float)pz;                    // searchPoint.x = search_Pt(0), :125-128
     const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-    const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx);
-    const int cy = cell_coord(qyf, G.oy, G.inv_h, G.gy);
-    const int cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
+    int cx, cy, cz;
+    query_cell(G, qxf, qyf, qzf, cx, cy, cz);
     bd = __builtin_huge_val();
     bi = kNoIndex;
     // the cube r = 1, then the shells r = 2, 3, ..
     for (int r = 1;; r++) {
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, G.gx - 1);
         const int y0 = max(cy - r, 0), y1 = min(cy + r, G.gy - 1);
         const int z0 = max(cz - r, 0), z1 = min(cz + r, G.gz - 1);
         const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
         for (int k = (int)grp; k < nrows; k += 256 / kCoop) {
-            const int zz = z0 + k / ny, yy = y0 + k % ny;
-            const uint32_t row = cell_lin(G, 0, yy, zz);
-            if (r == 1 || zz == cz - r || zz == cz + r || yy == cy - r || yy == cy + r) {
-                coop_scan_exact(pts, cell_start[row + x0], cell_start[row + x1 + 1], sub, qx, qy, qz, bd, bi);
-            } else {
-                if (cx - r >= 0) coop_scan_exact(pts, cell_start[row + cx - r], cell_start[row + cx - r + 1], sub, qx, qy, qz, bd, bi);
-                if (cx + r <= G.gx - 1) coop_scan_exact(pts, cell_start[row + cx + r], cell_start[row + cx + r + 1], sub, qx, qy, qz, bd, bi);
-            }
+            shell_row_runs(G, cell_start, cx, cy, cz, r, r == 1, y0 + k % ny, z0 + k / ny,
+                           [&](uint32_t s, uint32_t e) { coop_scan_exact(pts, s, e, sub, qx, qy, qz, bd, bi); });
         }
         block_argmin256(bd, bi, s_d, s_i);
         const double bound = cube_bound(G, cx, cy, cz, r, qx, qy, qz);

@@ -126,6 +126,11 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(GridDesc G, const float4 
     constexpr int ROW = knn_row<KCAP>();
     __shared__ double s_d[kKnnGroups * ROW];
     __shared__ uint32_t s_i[kKnnGroups * ROW];
+    // The slot, the query fetch, the cell and the rows of a shell stay spelled out in this kernel (elsewhere: coop_slot, coop_fetch_query,
+    // query_cell, shell_row_runs of kernels.hpp -- the same steps).  It sits at exactly 64 VGPRs, the last count that gives 8 waves per
+    // SIMD: with the cell or the shell rows through their helpers the same instructions come out in another order at 65-69, and with the
+    // slot and the fetch alone (64 VGPRs, one instruction fewer) k = 64 ran 14.36 against 14.30 ms, above every round of this form
+    // (profiles/grid_walk_asm.txt part 2, profiles/grid_walk_ab.txt).
     const uint32_t sub = threadIdx.x & (kCoop - 1), group = threadIdx.x / kCoop;
     const uint32_t bslot = qsorted ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
     const uint32_t slot = bslot * kKnnGroups + group;

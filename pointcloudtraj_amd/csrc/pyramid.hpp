@@ -1,7 +1,7 @@
 // pyramid.hpp -- bounding-box pyramid over the cell index: exact nearest neighbour on clouds with SPARSE OCCUPANCY.
 //
 // Why: the reference's real input is pillar SURFACES on a 0.1 m lattice (Planner/src/map_generator.cpp:16-125), not a volume
-// filled with points.  On such a cloud the shell walk of the cell-pruned search (kernels.hpp coop_nn_search) visits every cell of
+// filled with points.  On such a cloud the shell walk of the cell-pruned search (kernels.hpp coop_finish_shells) visits every cell of
 // every shell between a free-space query and the nearest surface -- hundreds of empty x-runs -- and then scans every point of every
 // occupied cell the final shells touch, although a wall's points in a cell occupy a thin slab of it: 859-2154 points and 39-310
 // runs per query on the seed-6 map against 49 / 4 on the uniform benchmark cloud (profiles/r02 notes, gpurun_out/cl.log).
@@ -487,28 +487,18 @@ __device__ __forceinline__ void pyr_answer(const GridDesc &G, const PyrDesc &PD,
                                            const float *__restrict__ q, uint32_t index_base, const float4 *__restrict__ qsorted, uint32_t slot,
                                            uint32_t sub, uint32_t *__restrict__ out_idx, double *__restrict__ out_d2, uint32_t *__restrict__ todo, uint32_t &npts, uint32_t &nruns, uint32_t &nnodes)
 {
-    uint32_t t = slot;
     float qxf, qyf, qzf;
-    if (qsorted) {
-        const float4 R = qsorted[slot];
-        qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
-    } else {
-        qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
-    }
+    const uint32_t t = coop_fetch_query(qsorted, q, slot, qxf, qyf, qzf);
     const double qx = (double)qxf, qy = (double)qyf, qz = (double)qzf;
-    const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx), cy = cell_coord(qyf, G.oy, G.inv_h, G.gy), cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
-    const float fx = (qxf - G.ox) * G.inv_h - (float)cx, fy = (qyf - G.oy) * G.inv_h - (float)cy, fz = (qzf - G.oz) * G.inv_h - (float)cz;
-    const int xa = max(fx < 0.5f ? cx - 1 : cx, 0), xb = min(fx < 0.5f ? cx : cx + 1, G.gx - 1);
-    const int ya = max(fy < 0.5f ? cy - 1 : cy, 0), yb = min(fy < 0.5f ? cy : cy + 1, G.gy - 1);
-    const int za = max(fz < 0.5f ? cz - 1 : cz, 0), zb = min(fz < 0.5f ? cz : cz + 1, G.gz - 1);
+    Stage0Block B;
+    stage0_block(G, qxf, qyf, qzf, B);
     uint32_t rs[4], re[4];
-    const int L0 = (int)hint[cell_lin(G, cx, cy, cz)];             // requested together with the run bounds
+    const int L0 = (int)hint[cell_lin(G, B.cx, B.cy, B.cz)];       // requested together with the run bounds
     {
         const int ri = (int)sub & 3;
-        const bool ok = !((ri >> 1) && zb == za) && !((ri & 1) && yb == ya);
-        const uint32_t row = cell_lin(G, 0, (ri & 1) ? yb : ya, (ri >> 1) ? zb : za);
-        const uint32_t a = cell_start[row + xa], b = cell_start[row + xb + 1];
-        const uint32_t my_s = a, my_e = ok ? b : a;
+        const bool ok = !((ri >> 1) && B.zb == B.za) && !((ri & 1) && B.yb == B.ya);
+        uint32_t my_s, my_e;
+        row_run(G, cell_start, ok, (ri & 1) ? B.yb : B.ya, (ri >> 1) ? B.zb : B.za, B.xa, B.xb, my_s, my_e);
 #ifndef PCT_AB_ITERSTAT
         if (COUNT && sub < 4) { npts += my_e - my_s; nruns += ok ? 1u : 0u; }
 #endif
@@ -520,22 +510,11 @@ __device__ __forceinline__ void pyr_answer(const GridDesc &G, const PyrDesc &PD,
     bool undecided = true;
     if ((re[0] - rs[0]) + (re[1] - rs[1]) + (re[2] - rs[2]) + (re[3] - rs[3]) != 0u) {        // free space: nothing to screen
         coop_screen_rows<4, 2>(pts, rs, re, sub, qxf, qyf, qzf, qx, qy, qz, bd, bi);
-        double bound = __builtin_huge_val();
-        if (xa > 0) bound = fmin(bound, qx - (G.oxd + (double)xa * G.hd));
-        if (xb < G.gx - 1) bound = fmin(bound, (G.oxd + (double)(xb + 1) * G.hd) - qx);
-        if (ya > 0) bound = fmin(bound, qy - (G.oyd + (double)ya * G.hd));
-        if (yb < G.gy - 1) bound = fmin(bound, (G.oyd + (double)(yb + 1) * G.hd) - qy);
-        if (za > 0) bound = fmin(bound, qz - (G.ozd + (double)za * G.hd));
-        if (zb < G.gz - 1) bound = fmin(bound, (G.ozd + (double)(zb + 1) * G.hd) - qz);
-        if (bound == __builtin_huge_val()) undecided = false;                        // the block covers the whole grid
-        else {
-            bound -= G.hd * (1.0 / 256.0);
-            undecided = !(bound > 0.0 && bd <= bound * bound);
-        }
+        undecided = block_undecided(box_bound(G, B.xa, B.xb, B.ya, B.yb, B.za, B.zb, qx, qy, qz), bd);
     }
     if (undecided) {
         float lim;
-        if (!pyr_nn_search_fast<COUNT>(G, PD.nlev, s_off, nodes, pts, qxf, qyf, qzf, sub, cx, cy, cz, L0, xa, xb, ya, yb, za, zb, bd, bi, lim, npts, nruns, nnodes)) {
+        if (!pyr_nn_search_fast<COUNT>(G, PD.nlev, s_off, nodes, pts, qxf, qyf, qzf, sub, B.cx, B.cy, B.cz, L0, B.xa, B.xb, B.ya, B.yb, B.za, B.zb, bd, bi, lim, npts, nruns, nnodes)) {
             // (measured: the exact walk right here instead of a list costs the kernel its registers: 1.15 against 1.18e9 q/s)
             if (sub == 0) {
                 const uint32_t e = atomicAdd(&todo[0], 1u);
@@ -555,17 +534,9 @@ template <bool COUNT>
 __device__ __forceinline__ void pyr_commit_work(uint32_t npts, uint32_t nruns, uint32_t nnodes, WorkCounters *__restrict__ work)
 {
     if (COUNT) {
-        unsigned long long a = npts, b = nruns, n = nnodes;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            a += (unsigned long long)__shfl_xor((long long)a, off, kWave);
-            b += (unsigned long long)__shfl_xor((long long)b, off, kWave);
-            n += (unsigned long long)__shfl_xor((long long)n, off, kWave);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            WorkCounters *w = work + (blockIdx.x & (kWorkSlots - 1));
-            atomicAdd(&w->points, a); atomicAdd(&w->cells, b); atomicAdd(&w->nodes, n);
-        }
+        commit_work(work, npts, nruns);
+        const unsigned long long n = wave_sum(nnodes);            // the walk's node visits beside them
+        if ((threadIdx.x & 63) == 0) atomicAdd(&work[blockIdx.x & (kWorkSlots - 1)].nodes, n);
     }
 }
 
@@ -582,8 +553,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     if (threadIdx.x < (uint32_t)kPyrMaxLevels) s_off[threadIdx.x] = PD.off[threadIdx.x];
     __syncthreads();
     const uint32_t sub = threadIdx.x & (kCoop - 1);
-    const uint32_t bslot = qsorted ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t slot = bslot * (256 / kCoop) + (threadIdx.x / kCoop);
+    const uint32_t slot = coop_slot<256 / kCoop>(qsorted);
     uint32_t npts = 0, nruns = 0, nnodes = 0;
     if (slot < Q)                                     // uniform within a group of 8 lanes
         pyr_answer<COUNT>(G, PD, s_off, nodes, hint, pts, cell_start, q, index_base, qsorted, slot, sub, out_idx, out_d2, todo, npts, nruns, nnodes);
@@ -618,15 +588,10 @@ __global__ __launch_bounds__(256) void nn_grid_pyr_todo_kernel(GridDesc G, PyrDe
         // walk prunes from its first node on (no stage 0, nothing excluded: ~10 dependent trips instead of ~30 for these stragglers)
         const uint32_t slot = todo[2u + 2u * e];
         const float lim = __uint_as_float(todo[3u + 2u * e]);
-        uint32_t t = slot;
         float qxf, qyf, qzf;
-        if (qsorted) {
-            const float4 R = qsorted[slot];
-            qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
-        } else {
-            qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
-        }
-        const int cx = cell_coord(qxf, G.ox, G.inv_h, G.gx), cy = cell_coord(qyf, G.oy, G.inv_h, G.gy), cz = cell_coord(qzf, G.oz, G.inv_h, G.gz);
+        const uint32_t t = coop_fetch_query(qsorted, q, slot, qxf, qyf, qzf);
+        int cx, cy, cz;
+        query_cell(G, qxf, qyf, qzf, cx, cy, cz);
         const int L0 = (int)hint[cell_lin(G, cx, cy, cz)];
         double bd = (double)lim;                       // +inf when the fp32 walk found nothing (non-finite query)
         uint32_t bi = kNoIndex;

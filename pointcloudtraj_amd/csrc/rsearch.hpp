@@ -156,17 +156,10 @@ __global__ __launch_bounds__(256) void rs_fill_grid_kernel(GridDesc G, const flo
     __shared__ uint32_t s_i[kKnnGroups * kRsShort];
     if (offsets[Q] > cap) return;
     const uint32_t sub = threadIdx.x & (kCoop - 1), group = threadIdx.x / kCoop;
-    const uint32_t bslot = qsorted ? xcd_contiguous_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t slot = bslot * kKnnGroups + group;
+    const uint32_t slot = coop_slot<kKnnGroups>(qsorted);
     if (slot >= Q) return;                            // uniform within a group; the kernel has no block-wide barrier
-    uint32_t t = slot;
     float qxf, qyf, qzf;
-    if (qsorted) {
-        const float4 R = qsorted[slot];
-        qxf = R.x; qyf = R.y; qzf = R.z; t = __float_as_uint(R.w);
-    } else {
-        qxf = q[3 * t]; qyf = q[3 * t + 1]; qzf = q[3 * t + 2];
-    }
+    const uint32_t t = coop_fetch_query(qsorted, q, slot, qxf, qyf, qzf);
     const long long off0 = offsets[t];
     const uint32_t len = (uint32_t)(offsets[t + 1] - off0);
     if (len == 0) return;
@@ -183,10 +176,8 @@ __global__ __launch_bounds__(256) void rs_fill_grid_kernel(GridDesc G, const flo
     uint32_t cur = 0;
     for (int base = 0; base < nrows; base += kCoop) {
         const int k = base + (int)sub;
-        const bool ok = k < nrows;
-        const uint32_t row = ok ? cell_lin(G, 0, y0 + k % ny, z0 + k / ny) : 0u;
-        const uint32_t a = cell_start[row + x0], b = cell_start[row + x1 + 1];
-        const uint32_t bs = a, be = ok ? b : a;
+        uint32_t bs, be;
+        row_run(G, cell_start, k < nrows, y0 + k % ny, z0 + k / ny, x0, x1, bs, be);
         const int nr = min(kCoop, nrows - base);
         for (int i = 0; i < nr; i++) {                            // uniform within the group
             const uint32_t rs = (uint32_t)__shfl((int)bs, i, kCoop), re = (uint32_t)__shfl((int)be, i, kCoop);

@@ -100,7 +100,7 @@ def explicit_cell(pts):
     return float(h) if h > 0 else 1.0
 
 
-INDEX_CONFIGS = [("grid", {}, 0.0), ("grid+pyramid", {"PCT_PYRAMID": "1"}, 0.0), ("grid,cube-first", {"PCT_OCTANT_FIRST": "0", "PCT_PYRAMID": "0"}, 0.0),
+INDEX_CONFIGS = [("grid", {}, 0.0), ("grid+pyramid", {"PCT_PYRAMID": "1"}, 0.0),
                  ("grid+block-table", {"PCT_BLOCK_TABLE": "1", "PCT_PYRAMID": "0"}, 0.0), ("grid,cell_size", {}, None)]
 
 
