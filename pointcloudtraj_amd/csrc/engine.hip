@@ -47,7 +47,10 @@
 #include "bezier_certify.hpp"
 
 using namespace pct;
+using pct_host::dropped;
+using pct_host::part;
 using pct_host::pow2_at_least;
+using pct_host::regrow;
 using pct_internal::DevBuf;
 using pct_internal::MappedBuf;
 using pct_internal::PinnedBuf;
@@ -162,23 +165,17 @@ struct SeqWord {
 };
 
 // Scratch of one order-preserving compaction of a frame (ring_dedup.hpp dd_rank, the tile scan with DdPublish, and a compacting kernel): keep flags,
-// ranks, tile totals and the packed xyz rows the insert kernel then reads.  ensure() allocates for exactly `cap` points; the caller
-// has chosen cap and synchronised.  A failure part-way leaves ncap 0.
+// ranks, tile totals and the packed xyz rows the insert kernel then reads.  ensure() allocates for exactly `cap` points, and with them
+// whatever further parts the caller sizes by ncap (one group); the caller has chosen cap and synchronised.
 struct CompactScratch {
     DevBuf<uint8_t> flags;
     DevBuf<uint32_t> rank, tile;
     DevBuf<float> out;
     int64_t ncap = 0;                            // points the scratch holds
-    int ensure(int64_t cap)
+    template <typename... More>
+    int ensure(int64_t cap, More... more)
     {
-        ncap = 0;
-        flags.release(); rank.release(); tile.release(); out.release();
-        PCTCHK(flags.reset((size_t)cap));
-        PCTCHK(rank.reset((size_t)cap));
-        PCTCHK(tile.reset((size_t)ceil_div(cap, kDdTile)));
-        PCTCHK(out.reset(3 * (size_t)cap));
-        ncap = cap;
-        return PCT_OK;
+        return regrow(ncap, cap, part(flags, (size_t)cap), part(rank, (size_t)cap), part(tile, (size_t)ceil_div(cap, kDdTile)), part(out, 3 * (size_t)cap), more...);
     }
 };
 
@@ -309,12 +306,13 @@ struct pct_cloud {
     DevBuf<int> d_orders, d_nsamples;
     DevBuf<long long> d_first_hit;
     size_t seg_cap = 0;
-    // batched Bezier check, host form (bezier_batch.hpp): device copies of seg_offsets / t_start, the offsets and the verdicts, B + 1
-    // entries each (grow-only)
+    // batched Bezier check, host form (bezier_batch.hpp): device copies of seg_offsets / t_start, the offsets and the verdicts, at
+    // least bb_cap >= B + 1 entries each (one group; the certified check grows bb_segoff alone where it needs more)
     DevBuf<int32_t> bb_segoff;
     DevBuf<double> bb_tstart;
     DevBuf<long long> bb_off;
     DevBuf<pct_traj_verdict> bb_verdict;
+    size_t bb_cap = 0;
     // certified Bezier check (bezier_certify.hpp): two sets of pieces (polygon + meta, 328 B per piece) that the rounds write in turn,
     // the split flags and tile sums of a round, the per-trajectory state, the control words, and the host form's certificates and
     // stats (all grow-only)
@@ -427,6 +425,27 @@ struct pct_plan {
 
 namespace {
 
+// What a cloud-owned buffer calls before it grows.  Growth is refused while the cloud captures a graph or, where the site names one,
+// while *capture_stream is being captured; then whatever may still read the old block is waited for.  Each site says what it has
+// always tested and waited for: this decides nothing for it.
+enum class Wait { Nothing, LibraryStream, Device };
+int may_grow(pct_cloud *c, Wait wait, const hipStream_t *capture_stream, const char *what)
+{
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (c->capturing || (capture_stream && hipStreamIsCapturing(*capture_stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone))
+        return fail(PCT_ERR_INVALID, "cannot grow %s during graph capture (call once with these sizes before capturing)", what);
+    if (wait == Wait::LibraryStream) HIPCHK(hipStreamSynchronize(g_stream));
+    if (wait == Wait::Device) HIPCHK(hipDeviceSynchronize());
+    return PCT_OK;
+}
+
+// the device forms work in the query workspaces: n entries must fit what pct_cloud_reserve_queries reserved
+inline int require_reserved(const pct_cloud *c, int64_t n, const char *what)
+{
+    if (n > c->qcap) return fail(PCT_ERR_INVALID, "%s of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", what, (long long)n, (long long)c->qcap);
+    return PCT_OK;
+}
+
 // completion word for the next express launch on this cloud (seq = nullptr when polling is off: express_wait then synchronises)
 ExpressSignal next_signal(pct_cloud *c)
 {
@@ -442,13 +461,8 @@ int ensure_mapped_io(pct_cloud *c, int64_t Q)
 {
     if (Q <= c->mcap) return PCT_OK;
     const int64_t cap = pow2_at_least<int64_t>(4096, Q);
-    c->mcap = 0;
-    c->mq.release(); c->mi.release(); c->md.release();
-    PCTCHK(c->mq.reset((size_t)(4 * cap)));          // 3 floats per query + a radius
-    PCTCHK(c->mi.reset((size_t)cap));
-    PCTCHK(c->md.reset((size_t)cap));
-    c->mcap = cap;
-    return PCT_OK;
+    return regrow(c->mcap, cap, part(c->mq, (size_t)(4 * cap)),      // 3 floats per query + a radius
+                  part(c->mi, (size_t)cap), part(c->md, (size_t)cap));
 }
 
 bool mapped_io_on()
@@ -1170,7 +1184,7 @@ int nn_run(pct_cloud *c, Path path, const float *d_q, int64_t Q, uint32_t *d_idx
 int nn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, uint32_t *d_idx, double *d_d2, hipStream_t s)
 {
     if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(require_reserved(c, Q, "batch"));
     Path path;
     PCTCHK(resolve_algo(c, Op::NN, algo, Q, &path));
     return nn_run(c, path, d_q, Q, d_idx, d_d2, s);
@@ -1232,7 +1246,7 @@ int count_run(pct_cloud *c, Path path, const float *d_q, const float *d_r, int64
 int count_dev(pct_cloud *c, int algo, const float *d_q, const float *d_r, int64_t Q, uint32_t *d_count, hipStream_t s)
 {
     if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld", (long long)Q, (long long)c->qcap);
+    PCTCHK(require_reserved(c, Q, "batch"));
     Path path;
     PCTCHK(resolve_algo(c, Op::Count, algo, Q, &path));
     return count_run(c, path, d_q, d_r, Q, d_count, s);
@@ -1244,7 +1258,7 @@ constexpr size_t kKnnPartEntries = 8u << 20;      // partial lists of the stream
 int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t *d_idx, double *d_d2, hipStream_t s)
 {
     if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(require_reserved(c, Q, "batch"));
     if (Q * (int64_t)k > 0xFFFFFFFFll) return fail(PCT_ERR_INVALID, "k-NN batch of %lld x %d entries is too large", (long long)Q, k);
     Path path;
     PCTCHK(resolve_algo(c, Op::KNN, algo, Q, &path));
@@ -1274,11 +1288,8 @@ int knn_dev(pct_cloud *c, int algo, const float *d_q, int64_t Q, int k, uint32_t
     default:
         break;
     }
-    if (!c->d_knn_pd2) {
-        PCTCHK(c->d_knn_pd2.reset(kKnnPartEntries));
-        PCTCHK(c->d_knn_pidx.reset(kKnnPartEntries));
-        c->knn_part_cap = kKnnPartEntries;
-    }
+    if (!c->d_knn_pd2)
+        PCTCHK(regrow(c->knn_part_cap, kKnnPartEntries, part(c->d_knn_pd2, kKnnPartEntries), part(c->d_knn_pidx, kKnnPartEntries)));
     // one block per 4096 points, at most 256: a block's four waves then see enough points for their lists to settle
     const int nparts = (int)std::min<int64_t>(256, std::max<int64_t>(1, (c->count + 4095) / 4096));
     const int64_t qslice = std::max<int64_t>(kKnnTile, (int64_t)(c->knn_part_cap / ((size_t)nparts * (size_t)k)) / kKnnTile * kKnnTile);
@@ -1350,31 +1361,21 @@ int segment_run(pct_cloud *c, Path path, SegMeasure measure, const double *d_seg
 int rs_ensure_work(pct_cloud *c)
 {
     if (c->rs_qcap >= c->qcap && c->rs_off) return PCT_OK;
-    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow workspaces during graph capture");
+    PCTCHK(may_grow(c, Wait::Nothing, nullptr, "the list-search workspaces"));
     const size_t q = (size_t)std::max<int64_t>(c->qcap, 256);
-    c->rs_qcap = 0;
-    c->rs_off.release(); c->rs_tiles.release(); c->rs_cursor.release(); c->rs_queue.release();
-    PCTCHK(c->rs_off.reset(q + 1));
-    PCTCHK(c->rs_tiles.reset(q / kRsScanTile + 2));
-    PCTCHK(c->rs_cursor.reset(q));
-    PCTCHK(c->rs_queue.reset(q + 1));
-    c->rs_qcap = (int64_t)q;
-    return PCT_OK;
+    return regrow(c->rs_qcap, q, part(c->rs_off, q + 1), part(c->rs_tiles, q / kRsScanTile + 2), part(c->rs_cursor, q), part(c->rs_queue, q + 1));
 }
 
-// room for n entries in L's d2 and, where wanted, idx and s (grow-only; a failed growth leaves none)
+// room for n entries in L's d2 and, where wanted, idx and s (grow-only; a failed growth leaves none, and a regrowth drops the idx or
+// s that its call does not want)
 int ensure_lists(pct_cloud *c, ListStore &L, size_t n, bool want_idx, bool want_s)
 {
     if (n == 0 || (n <= L.cap && (!want_idx || L.idx) && (!want_s || L.s))) return PCT_OK;
-    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the %s lists during graph capture", L.what);
+    char what[64];
+    std::snprintf(what, sizeof what, "the %s lists", L.what);
+    PCTCHK(may_grow(c, Wait::Nothing, nullptr, what));
     n = std::max(n, L.cap);
-    L.cap = 0;
-    L.idx.release(); L.d2.release(); L.s.release();
-    PCTCHK(L.d2.reset(n));
-    if (want_idx) PCTCHK(L.idx.reset(n));
-    if (want_s) PCTCHK(L.s.reset(n));
-    L.cap = n;
-    return PCT_OK;
+    return regrow(L.cap, n, part(L.d2, n), want_idx ? part(L.idx, n) : dropped(L.idx), want_s ? part(L.s, n) : dropped(L.s));
 }
 
 // entries [first, first + n) of L's last result to the host; idx, d2 or s may be NULL
@@ -1525,7 +1526,7 @@ int ss_fill_sort(pct_cloud *c, Path path, const double *d_seg, const double *d_r
 int poly_ensure_sup(pct_cloud *c, int64_t row_cap)
 {
     if ((size_t)row_cap <= c->pl_sup.capacity() && c->pl_sup) return PCT_OK;
-    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow the polyhedron workspace during graph capture");
+    PCTCHK(may_grow(c, Wait::Nothing, nullptr, "the polyhedron support workspace"));
     return c->pl_sup.reserve((size_t)std::max<int64_t>(row_cap, 1));
 }
 
@@ -1680,13 +1681,7 @@ int bezier_stage_coef(pct_cloud *c, const pct_bezier_traj *traj, hipStream_t s, 
     if (ncoef > c->d_coef.capacity() || nseg > c->seg_cap) {
         if (dev_form) HIPCHK(hipDeviceSynchronize());
         PCTCHK(c->d_coef.reserve(ncoef));
-        if (nseg > c->seg_cap) {
-            c->seg_cap = 0;
-            c->d_segtime.release(); c->d_orders.release();
-            PCTCHK(c->d_segtime.reset(nseg));
-            PCTCHK(c->d_orders.reset(nseg));
-            c->seg_cap = nseg;
-        }
+        if (nseg > c->seg_cap) PCTCHK(regrow(c->seg_cap, nseg, part(c->d_segtime, nseg), part(c->d_orders, nseg)));
     }
     HIPCHK(hipMemcpyAsync(c->d_coef, traj->polycoef, sizeof(double) * ncoef, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_segtime, traj->seg_time, sizeof(double) * nseg, hipMemcpyHostToDevice, s));
@@ -2015,7 +2010,7 @@ int list_search_dev_prelude(pct_cloud *c, ListStore &L, bool want_idx, int64_t Q
         HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
         return PCT_OK;
     }
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(require_reserved(c, Q, "batch"));
     if (order == PCT_ORDER_DISTANCE && !*d_d2 && cap > 0) {
         L.valid = false;
         PCTCHK(ensure_lists(c, L, (size_t)cap, want_idx, false));
@@ -2064,7 +2059,7 @@ int segment_batch_dev(pct_cloud *c, int algo, SegMeasure measure, const double *
     Path path;
     PCTCHK(resolve_algo(c, Op::Segment, algo, Q, &path));
     if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(require_reserved(c, Q, "batch"));
     PCTCHK(order_after_mutations(c, s));
     return segment_run(c, path, measure, d_seg, d_reach, 0.0, Q, d_idx, d_d2, d_s, s);
 }
@@ -2096,21 +2091,11 @@ struct BcRun {
     long long *stats;                // device memory, 3 entries, or NULL
 };
 
-// a cloud-owned buffer of the check is about to grow: refused while a graph is captured, and nothing may still read the old block
-int bc_may_grow(pct_cloud *c, hipStream_t s)
-{
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (c->capturing || (hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone))
-        return fail(PCT_ERR_INVALID, "cannot grow the piece buffers during graph capture (call once with these sizes before capturing)");
-    HIPCHK(hipDeviceSynchronize());
-    return PCT_OK;
-}
-
 template <typename T>
 int bc_reserve(pct_cloud *c, DevBuf<T> &buf, size_t need, hipStream_t s)
 {
     if (need <= buf.capacity() && buf) return PCT_OK;
-    PCTCHK(bc_may_grow(c, s));
+    PCTCHK(may_grow(c, Wait::Device, &s, "the certified check's buffers"));
     return buf.reserve(pow2_at_least<size_t>(256, need));
 }
 
@@ -2204,44 +2189,25 @@ int pct_cloud_reserve_queries(pct_cloud *c, int64_t Q)
 {
     if (!c || Q < 0) return fail(PCT_ERR_INVALID, "bad reserve");
     if (Q <= c->qcap) return PCT_OK;
-    if (c->capturing) return fail(PCT_ERR_INVALID, "cannot grow workspaces during graph capture");
-    HIPCHK(hipStreamSynchronize(g_stream));
-    const int64_t q = std::max<int64_t>(Q, 256);
-    c->qcap = 0;
+    PCTCHK(may_grow(c, Wait::LibraryStream, nullptr, "the query workspaces"));
+    const size_t q = (size_t)std::max<int64_t>(Q, 256);
     c->generation++;                    // captured plans hold these pointers
-    c->d_q.release(); c->d_r.release(); c->d_q64.release(); c->d_r2.release(); c->d_d2.release(); c->d_radius.release();
-    c->d_pts64.release(); c->d_idx.release(); c->d_count.release(); c->d_skip.release(); c->d_bound.release(); c->d_seg.release();
-    c->d_part_d2.release(); c->d_part_idx.release(); c->d_cand_count.release(); c->d_cand_d2.release(); c->d_cand_idx.release();
-    c->d_ovf.release(); c->d_qsorted.release(); c->d_todo.release(); c->d_slice.release();
-    PCTCHK(c->d_q.reset(3 * q));
-    PCTCHK(c->d_r.reset(q));
-    PCTCHK(c->d_q64.reset(3 * q));
-    PCTCHK(c->d_r2.reset(q));
-    PCTCHK(c->d_d2.reset(q));
-    PCTCHK(c->d_radius.reset(q));
-    PCTCHK(c->d_pts64.reset(3 * q));
-    PCTCHK(c->d_seg.reset(6 * q));
-    PCTCHK(c->d_idx.reset(q));
-    PCTCHK(c->d_count.reset(q));
-    PCTCHK(c->d_skip.reset(q));
-    PCTCHK(c->d_bound.reset(q));
-    PCTCHK(c->d_qsorted.reset(q));
-    PCTCHK(c->d_slice.reset(sort_slice_rows(q) * kSortBuckets));       // every hist launch rewrites the rows it uses: never zeroed
-    PCTCHK(c->d_todo.reset(2 * q + 16));
+    c->part_q = std::min<int64_t>((int64_t)q, kPartQueries);
+    const size_t pq = (size_t)c->part_q;
+    PCTCHK(regrow(c->qcap, q, part(c->d_q, 3 * q), part(c->d_r, q), part(c->d_q64, 3 * q), part(c->d_r2, q), part(c->d_d2, q), part(c->d_radius, q),
+                  part(c->d_pts64, 3 * q), part(c->d_seg, 6 * q), part(c->d_idx, q), part(c->d_count, q), part(c->d_skip, q), part(c->d_bound, q),
+                  part(c->d_qsorted, q),
+                  part(c->d_slice, sort_slice_rows(q) * kSortBuckets),       // every hist launch rewrites the rows it uses: never zeroed
+                  part(c->d_todo, 2 * q + 16), part(c->d_part_d2, pq * kMaxParts), part(c->d_part_idx, pq * kMaxParts), part(c->d_ovf, pq + 1),
+                  part(c->d_cand_count, pq), part(c->d_cand_d2, pq * kCandCap), part(c->d_cand_idx, pq * kCandCap)));
+    c->qcap = 0;                        // the group is usable only behind the zeroing below and with the sort's totals
     HIPCHK(hipMemset(c->d_todo, 0, sizeof(uint32_t) * 16));            // count and ticket: the exact-walk kernel leaves them zero after every batch
     if (!c->d_sort1) {
         PCTCHK(c->d_sort1.reset(2 * kSortBuckets));
         HIPCHK(hipMemset(c->d_sort1, 0, sizeof(uint32_t) * 2 * kSortBuckets));   // the sort keeps both sets of totals zero between batches
     }
-    c->part_q = std::min<int64_t>(q, kPartQueries);
-    PCTCHK(c->d_part_d2.reset((size_t)c->part_q * kMaxParts));
-    PCTCHK(c->d_part_idx.reset((size_t)c->part_q * kMaxParts));
-    PCTCHK(c->d_ovf.reset((size_t)c->part_q + 1));
-    PCTCHK(c->d_cand_count.reset((size_t)c->part_q));
-    PCTCHK(c->d_cand_d2.reset((size_t)c->part_q * kCandCap));
-    PCTCHK(c->d_cand_idx.reset((size_t)c->part_q * kCandCap));
-    HIPCHK(hipMemset(c->d_cand_count, 0, sizeof(uint32_t) * (size_t)c->part_q));     // the reduce kernel keeps it zero between slices
-    c->qcap = q;
+    HIPCHK(hipMemset(c->d_cand_count, 0, sizeof(uint32_t) * pq));     // the reduce kernel keeps it zero between slices
+    c->qcap = (int64_t)q;
     return PCT_OK;
 }
 
@@ -2466,11 +2432,7 @@ int pct_knn_batch_algo(pct_cloud *c, int algo, const float *q, int64_t Q, int32_
     const size_t rows = (size_t)Q * (size_t)k;
     if (rows > c->knn_out_cap) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        c->knn_out_cap = 0;
-        c->d_knn_idx.release(); c->d_knn_d2.release();
-        PCTCHK(c->d_knn_idx.reset(rows));
-        PCTCHK(c->d_knn_d2.reset(rows));
-        c->knn_out_cap = rows;
+        PCTCHK(regrow(c->knn_out_cap, rows, part(c->d_knn_idx, rows), part(c->d_knn_d2, rows)));
     }
     HIPCHK(hipMemcpyAsync(c->d_q, q, sizeof(float) * 3 * Q, hipMemcpyHostToDevice, g_stream));
     PCTCHK(ask_twice_after_overrun(c, [&] {
@@ -2599,12 +2561,8 @@ static int crop_device(pct_cloud *c, const double q[3], double rr, int64_t *tota
     const uint32_t ntiles = (n + kCropTile - 1) / kCropTile;
     PCTCHK(c->crop_tile.reserve((size_t)ntiles + 1));
     if ((size_t)n > c->crop_cap) {
-        c->crop_cap = 0;
-        c->crop_idx.release(); c->crop_d2.release(); c->crop_x.release(); c->crop_y.release(); c->crop_z.release();
         const size_t cap = std::max<size_t>((size_t)c->cap, n);
-        PCTCHK(c->crop_idx.reset(cap)); PCTCHK(c->crop_d2.reset(cap));
-        PCTCHK(c->crop_x.reset(cap)); PCTCHK(c->crop_y.reset(cap)); PCTCHK(c->crop_z.reset(cap));
-        c->crop_cap = cap;
+        PCTCHK(regrow(c->crop_cap, cap, part(c->crop_idx, cap), part(c->crop_d2, cap), part(c->crop_x, cap), part(c->crop_y, cap), part(c->crop_z, cap)));
     }
     begin_timing(c, g_stream);
     HIPCHK(hipMemsetAsync(c->crop_tile + ntiles, 0, sizeof(uint32_t), g_stream));
@@ -2829,7 +2787,7 @@ int pct_segment_count_batch_dev(pct_cloud *c, int algo, const double *d_seg, con
     Path path;
     PCTCHK(resolve_algo(c, Op::Capsule, algo, Q, &path));
     if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(require_reserved(c, Q, "batch"));
     PCTCHK(order_after_mutations(c, (hipStream_t)stream));
     return ss_count_run(c, path, d_seg, d_reach, Q, d_count, (hipStream_t)stream, no_step);
 }
@@ -2900,7 +2858,7 @@ int pct_segment_supports_dev(pct_cloud *c, const double *d_seg, int64_t Q, const
         HIPCHK(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
         return PCT_OK;
     }
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(require_reserved(c, Q, "batch"));
     if (row_cap > 0xFFFFFFFFll) return fail(PCT_ERR_CAPACITY, "rows of %lld entries, more than 2^32 - 1", (long long)row_cap);
     PCTCHK(rs_ensure_work(c));
     PCTCHK(poly_ensure_sup(c, row_cap));
@@ -3152,7 +3110,7 @@ int pct_inflate_batch_dev(pct_cloud *c, const pct_inflate_params *p, const doubl
 {
     if (!c || !p || Q < 0 || (Q > 0 && (!d_pts || !d_radius))) return fail(PCT_ERR_INVALID, "bad inflate_batch_dev arguments");
     if (Q == 0) return PCT_OK;
-    if (Q > c->qcap) return fail(PCT_ERR_INVALID, "batch of %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)Q, (long long)c->qcap);
+    PCTCHK(require_reserved(c, Q, "batch"));
     PCTCHK(order_after_mutations(c, (hipStream_t)stream));
     return inflate_dev(c, p, Q, (hipStream_t)stream, d_pts, nullptr, d_radius, d_idx, d_d2);
 }
@@ -3228,13 +3186,11 @@ int pct_bezier_check_batch(pct_cloud *c, const pct_bezier_batch *batch, const pc
     const int32_t total_seg = batch->seg_offsets[B];
     const pct_bezier_traj all{ batch->polycoef, batch->row_stride, batch->seg_time, batch->orders, total_seg };
     PCTCHK(bezier_stage_coef(c, &all, s, false));
-    if ((size_t)B + 1 > c->bb_off.capacity()) {
+    if ((size_t)B + 1 > c->bb_cap) {
         HIPCHK(hipStreamSynchronize(s));
         const size_t n = pow2_at_least<size_t>(256, (size_t)B + 1);
-        PCTCHK(c->bb_segoff.reserve(n));
-        PCTCHK(c->bb_tstart.reserve(n));
-        PCTCHK(c->bb_verdict.reserve(n));
-        PCTCHK(c->bb_off.reserve(n));            // last: its capacity is the test above
+        // bb_segoff never shrinks: the certified check may have grown it further on its own (bb_cap is a minimum)
+        PCTCHK(regrow(c->bb_cap, n, part(c->bb_segoff, std::max(n, c->bb_segoff.capacity())), part(c->bb_tstart, n), part(c->bb_verdict, n), part(c->bb_off, n)));
     }
     HIPCHK(hipMemcpyAsync(c->bb_segoff, batch->seg_offsets, sizeof(int32_t) * (B + 1), hipMemcpyHostToDevice, s));
     if (batch->t_start) HIPCHK(hipMemcpyAsync(c->bb_tstart, batch->t_start, sizeof(double) * B, hipMemcpyHostToDevice, s));
@@ -3272,7 +3228,7 @@ int pct_bezier_check_batch_dev(pct_cloud *c, const pct_bezier_batch *d_batch_fie
         return fail(PCT_ERR_INVALID, "bad bezier_check_batch_dev arguments");
     if (bt->B > 0 && (!bt->polycoef || !bt->seg_time || !bt->orders || !bt->seg_offsets || !d_verdict))
         return fail(PCT_ERR_INVALID, "bad bezier_check_batch_dev arguments: a null array");
-    if (list_cap > c->qcap) return fail(PCT_ERR_INVALID, "list_cap %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)list_cap, (long long)c->qcap);
+    PCTCHK(require_reserved(c, list_cap, "list_cap"));
     if (cap > kBezierCapMax) cap = kBezierCapMax;
     hipStream_t s = (hipStream_t)stream;
     if (bt->B == 0) {
@@ -3368,8 +3324,7 @@ int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch 
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     if ((path == Path::Stream || path == Path::Empty) && (c->capturing || (hipStreamIsCapturing(s, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone)))
         return fail(PCT_ERR_INVALID, "bezier_certify_batch_dev: during graph capture the cloud needs its cell index or its rolling-map index");
-    if (2 * piece_cap > c->qcap)
-        return fail(PCT_ERR_INVALID, "2 * piece_cap = %lld exceeds reserved %lld (call pct_cloud_reserve_queries)", (long long)(2 * piece_cap), (long long)c->qcap);
+    PCTCHK(require_reserved(c, 2 * piece_cap, "2 * piece_cap"));
     PCTCHK(bc_room(c, 0, piece_cap, s));
     PCTCHK(bc_room(c, 1, piece_cap, s));
     PCTCHK(bc_round_room(c, piece_cap, s));

@@ -4,11 +4,13 @@
 //
 //   Buf<T, Mem>   one owning, grow-only block of T.  Mem::alloc(bytes, &host, &dev) returns 0 or an error code and leaves both
 //                 pointers null on failure; Mem::release(host, dev, bytes) frees what alloc handed out.
+//   regrow        buffers of different element types and kinds that share one capacity variable, grown as one group
 //   pow2_at_least the doubling rule of the grow-only workspaces
 //   wait_word     spin on a host-mapped completion word, fall back to the stream
 //
 // The type decides no policy: how much to allocate, whether to synchronise first and whether growth is allowed at all (graph
-// capture) stay with the call site.
+// capture) stay with the call site.  A group that fails to grow is left with no member at all (before regrow most sites kept the
+// members allocated ahead of the failing one): its capacity variable is 0, and the next call builds the whole group again.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -70,6 +72,35 @@ private:
     T *h_ = nullptr, *d_ = nullptr;
     size_t cap_ = 0;
 };
+
+// One member of a group and the elements it gets; dropped(): released with the group and left empty (a member the caller does
+// not want now, or allocates itself later -- reset(0) would allocate one element's room).
+template <typename B>
+struct Part {
+    B &buf;
+    size_t count;
+    bool wanted;
+};
+template <typename B> Part<B> part(B &buf, size_t count) { return { buf, count, true }; }
+template <typename B> Part<B> dropped(B &buf) { return { buf, 0, false }; }
+
+// Grow the group guarded by `cap`: cap goes to 0 first, every member is released before any is allocated (peak memory does not
+// rise), then the members are allocated in the order listed.  The first failure releases them all, leaves cap 0 and is returned;
+// on success cap becomes new_cap.  The caller has decided that the group must grow and has waited for whatever reads it.
+template <typename Cap, typename N, typename... B>
+int regrow(Cap &cap, N new_cap, Part<B>... parts)
+{
+    cap = 0;
+    (parts.buf.release(), ...);
+    int st = 0;
+    (void)((parts.wanted ? (st = parts.buf.reset(parts.count)) == 0 : true) && ...);
+    if (st) {
+        (parts.buf.release(), ...);
+        return st;
+    }
+    cap = static_cast<Cap>(new_cap);
+    return 0;
+}
 
 // the smallest floor * 2^k that is >= need (floor a power of two: the result is one, and *log2 its exponent)
 template <typename I>

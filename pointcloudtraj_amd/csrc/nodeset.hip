@@ -17,23 +17,26 @@
 #include <cstring>
 #include <limits>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "../../include/pct_engine.h"
 #include "engine_internal.hpp"
 
+using pct_internal::DevBuf;
 using pct_internal::fail;
+using pct_internal::PinnedBuf;
 
 struct pct_nodeset {
     int dim = 0;
     int64_t cap = 0, size = 0;
-    double *cols = nullptr;               // [dim][cap]
-    double *dist = nullptr;               // [cap]: the last query's distances
-    double *d_q = nullptr;                // [dim]
-    unsigned long long *d_res = nullptr;  // {minimum as bits, lowest node number at the minimum, ties, hits}
-    uint32_t *d_ids = nullptr;            // [cap]: hit list of the last range query
-    double *h_q = nullptr;                // pinned staging: the query
-    unsigned long long *h_res = nullptr;  // pinned: d_res read back
+    DevBuf<double> cols;                  // [dim][cap]
+    DevBuf<double> dist;                  // [cap]: the last query's distances
+    DevBuf<double> d_q;                   // [dim]
+    DevBuf<unsigned long long> d_res;     // {minimum as bits, lowest node number at the minimum, ties, hits}
+    DevBuf<uint32_t> d_ids;               // [cap]: hit list of the last range query
+    PinnedBuf<double> h_q;                // pinned staging: the query
+    PinnedBuf<unsigned long long> h_res;  // pinned: d_res read back
     std::vector<double> stage;            // transposed rows of one append
 };
 
@@ -113,26 +116,18 @@ int reserve(pct_nodeset *s, int64_t want)
     while (cap < want) cap *= 2;
     if (cap >= 0xFFFFFFFFll) return fail(PCT_ERR_INVALID, "node numbers travel as 32 bits");
     hipStream_t st = pct_internal::stream();
-    double *cols = nullptr, *dist = nullptr;
-    uint32_t *ids = nullptr;
-    if (hipMalloc(&cols, sizeof(double) * (size_t)cap * s->dim) != hipSuccess || hipMalloc(&dist, sizeof(double) * (size_t)cap) != hipSuccess ||
-        hipMalloc(&ids, sizeof(uint32_t) * (size_t)cap) != hipSuccess) {
-        if (cols) (void)hipFree(cols);
-        if (dist) (void)hipFree(dist);
-        return fail(PCT_ERR_ALLOC, "node set of %lld x %d doubles does not fit", (long long)cap, s->dim);
-    }
+    DevBuf<double> cols, dist;                 // grow with copy: new blocks, copy, move-assign (the old ones go then)
+    DevBuf<uint32_t> ids;
+    PCTCHK(cols.reset((size_t)cap * s->dim));
+    PCTCHK(dist.reset((size_t)cap));
+    PCTCHK(ids.reset((size_t)cap));
     if (s->size > 0) {
-        const hipError_t e = hipMemcpy2DAsync(cols, sizeof(double) * (size_t)cap, s->cols, sizeof(double) * (size_t)s->cap, sizeof(double) * (size_t)s->size,
-                                              (size_t)s->dim, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            (void)hipFree(cols); (void)hipFree(dist); (void)hipFree(ids);
-            return fail(PCT_ERR_HIP, "node set: moving the columns failed");
-        }
+        HIPCHK(hipMemcpy2DAsync(cols, sizeof(double) * (size_t)cap, s->cols, sizeof(double) * (size_t)s->cap, sizeof(double) * (size_t)s->size,
+                                (size_t)s->dim, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
-    if (s->cols) (void)hipFree(s->cols);
-    if (s->dist) (void)hipFree(s->dist);
-    if (s->d_ids) (void)hipFree(s->d_ids);
-    s->cols = cols; s->dist = dist; s->d_ids = ids; s->cap = cap;
+    s->cols = std::move(cols); s->dist = std::move(dist); s->d_ids = std::move(ids);
+    s->cap = cap;
     return PCT_OK;
 }
 
@@ -156,13 +151,11 @@ int pct_nodeset_create(int dim, int64_t capacity, pct_nodeset **out)
     pct_nodeset *s = new (std::nothrow) pct_nodeset();
     if (!s) return fail(PCT_ERR_ALLOC, "host allocation failed");
     s->dim = dim;
-    if (hipMalloc(&s->d_q, sizeof(double) * (size_t)dim) != hipSuccess || hipMalloc(&s->d_res, sizeof(unsigned long long) * 4) != hipSuccess ||
-        hipHostMalloc(&s->h_q, sizeof(double) * (size_t)dim, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&s->h_res, sizeof(unsigned long long) * 4, hipHostMallocDefault) != hipSuccess) {
-        pct_nodeset_destroy(s);
-        return fail(PCT_ERR_ALLOC, "node set: device / pinned allocation failed");
-    }
-    const int st = reserve(s, std::max<int64_t>(capacity, 1));
+    int st = s->d_q.reset((size_t)dim);
+    if (!st) st = s->d_res.reset(4);
+    if (!st) st = s->h_q.reset((size_t)dim);
+    if (!st) st = s->h_res.reset(4);
+    if (!st) st = reserve(s, std::max<int64_t>(capacity, 1));
     if (st != PCT_OK) { pct_nodeset_destroy(s); return st; }
     *out = s;
     return PCT_OK;
@@ -172,11 +165,7 @@ int pct_nodeset_destroy(pct_nodeset *s)
 {
     if (!s) return PCT_OK;
     (void)hipStreamSynchronize(pct_internal::stream());
-    for (void *p : { (void *)s->cols, (void *)s->dist, (void *)s->d_q, (void *)s->d_res, (void *)s->d_ids })
-        if (p) (void)hipFree(p);
-    if (s->h_q) (void)hipHostFree(s->h_q);
-    if (s->h_res) (void)hipHostFree(s->h_res);
-    delete s;
+    delete s;                             // the buffers go with it
     return PCT_OK;
 }
 

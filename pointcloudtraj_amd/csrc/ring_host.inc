@@ -291,21 +291,12 @@ int dedup_ensure(pct_cloud *c, int64_t n)
     const uint32_t T = dedup_table_size(n);
     if (T > c->dd_tcap) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        c->dd_tcap = 0;
-        c->dd_keys.release(); c->dd_vals.release();
-        PCTCHK(c->dd_keys.reset(T));
-        PCTCHK(c->dd_vals.reset(T));
-        c->dd_tcap = T;
+        PCTCHK(regrow(c->dd_tcap, T, part(c->dd_keys, T), part(c->dd_vals, T)));
     }
     if (n > c->dd.ncap) {
         HIPCHK(hipStreamSynchronize(g_stream));       // the previous append's insert kernel may still be reading the compacted frame
         const int64_t cap = std::min<int64_t>(std::max<int64_t>(c->cap, 1), std::max<int64_t>(n, 2 * c->dd.ncap));
-        c->dd.ncap = 0;
-        c->dd_pslot.release();
-        PCTCHK(c->dd.ensure(cap));
-        c->dd.ncap = 0;                            // the group is whole only with the table slots
-        PCTCHK(c->dd_pslot.reset((size_t)cap));
-        c->dd.ncap = cap;
+        PCTCHK(c->dd.ensure(cap, part(c->dd_pslot, (size_t)cap)));      // one group with the table slots
     }
     return PCT_OK;
 }
@@ -1434,13 +1425,8 @@ int depth_stage_ensure(DepthStage *S, size_t floats)
 {
     if (floats <= S->cap) return PCT_OK;
     HIPCHK(hipStreamSynchronize(g_stream));
-    S->cap = 0;
-    S->h.release(); S->d.release();
     const size_t cap = pow2_at_least((size_t)1 << 14, floats);
-    PCTCHK(S->h.reset(cap));
-    if (const int st = S->d.reset(cap)) { S->h.release(); return st; }
-    S->cap = cap;
-    return PCT_OK;
+    return regrow(S->cap, cap, part(S->h, cap), part(S->d, cap));
 }
 
 // scratch of pct_cloud_append_depth for an image of npix pixels (grow-only): validity flags, ranks, tile totals, the packed frame
@@ -1550,13 +1536,8 @@ int pct_depth_classify(const pct_depth_view *views, const float *const *images, 
     PCTCHK(depth_stage_ensure(&W.images, total));
     if (n > W.ncap) {
         HIPCHK(hipStreamSynchronize(g_stream));
-        W.ncap = 0;
-        W.d_pts.release(); W.d_seen.release(); W.d_pixel.release();
         const int64_t cap = pow2_at_least<int64_t>(1024, n);
-        PCTCHK(W.d_pts.reset(3 * (size_t)cap));
-        PCTCHK(W.d_seen.reset((size_t)cap));
-        PCTCHK(W.d_pixel.reset(2 * (size_t)cap));
-        W.ncap = cap;
+        PCTCHK(regrow(W.ncap, cap, part(W.d_pts, 3 * (size_t)cap), part(W.d_seen, (size_t)cap), part(W.d_pixel, 2 * (size_t)cap)));
     }
     DepthViews S{};
     S.n = n_views;

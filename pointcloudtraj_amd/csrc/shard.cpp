@@ -13,25 +13,9 @@
 #include <vector>
 
 #include "../../include/pct_shard.h"
+#include "hostmem.hpp"
 
 static_assert(PCT_SHARD_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "rendezvous token size");
-
-struct pct_shard {
-    ncclComm_t comm = nullptr;
-    bool own_comm = false;
-    bool local = false;              // one of several ranks living in ONE process (pct_shard_local_world): no communicator, the
-                                     // *_world entry points move the data between the ranks' buffers themselves
-    int rank = 0, world = 1;
-    // exchange workspaces (device), grown on demand
-    int64_t cap = 0;
-    double *d_ld2 = nullptr;         // per-shard squared distances
-    uint32_t *d_lidx = nullptr;      // per-shard global indices
-    int32_t *d_cand = nullptr;       // masked indices offered to the second reduction
-    uint32_t *d_lcount = nullptr;
-    float *d_q = nullptr, *d_r = nullptr;   // host-buffer convenience path
-    uint32_t *d_oidx = nullptr;
-    double *d_od2 = nullptr;
-};
 
 namespace {
 
@@ -46,6 +30,41 @@ int sfail(int code, const char *fmt, ...)
     std::fprintf(stderr, "pct_shard: %s\n", g_serr);
     return code;
 }
+
+// device memory as a kind of pct_host::Buf: this library's own, the engine's kinds are hidden symbols of libpct_engine.so
+struct ShardMem {
+    static int alloc(size_t bytes, void **host, void **dev)
+    {
+        *host = *dev = nullptr;
+        if (hipMalloc(dev, bytes) != hipSuccess) { *dev = nullptr; return sfail(PCT_ERR_ALLOC, "hipMalloc of an exchange workspace failed"); }
+        return PCT_OK;
+    }
+    static void release(void *, void *dev, size_t) { (void)hipFree(dev); }
+};
+template <typename T> using DevBuf = pct_host::Buf<T, ShardMem>;
+using pct_host::part;
+using pct_host::regrow;
+
+}  // namespace
+
+struct pct_shard {
+    ncclComm_t comm = nullptr;
+    bool own_comm = false;
+    bool local = false;              // one of several ranks living in ONE process (pct_shard_local_world): no communicator, the
+                                     // *_world entry points move the data between the ranks' buffers themselves
+    int rank = 0, world = 1;
+    // exchange workspaces (device), grown on demand
+    int64_t cap = 0;
+    DevBuf<double> d_ld2;            // per-shard squared distances
+    DevBuf<uint32_t> d_lidx;         // per-shard global indices
+    DevBuf<int32_t> d_cand;          // masked indices offered to the second reduction
+    DevBuf<uint32_t> d_lcount;
+    DevBuf<float> d_q, d_r;          // host-buffer convenience path
+    DevBuf<uint32_t> d_oidx;
+    DevBuf<double> d_od2;
+};
+
+namespace {
 
 #define NCCLCHK(call)                                                                                          \
     do {                                                                                                       \
@@ -63,28 +82,13 @@ int sfail(int code, const char *fmt, ...)
         if (s_ != PCT_OK) return sfail(s_, "%s -> %s", #call, pct_last_error());                                \
     } while (0)
 
-template <typename T>
-int grow(T **p, int64_t n)
-{
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    void *v = nullptr;
-    if (hipMalloc(&v, sizeof(T) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess) return sfail(PCT_ERR_ALLOC, "hipMalloc of an exchange workspace failed");
-    *p = static_cast<T *>(v);
-    return PCT_OK;
-}
-
 int reserve(pct_shard *s, int64_t Q)
 {
     if (Q <= s->cap) return PCT_OK;
     HIPCHK(hipDeviceSynchronize());            // a previous batch may still read the old workspaces
-    s->cap = 0;
-    const int64_t n = std::max<int64_t>(Q, 256);
-    if (grow(&s->d_ld2, n) || grow(&s->d_lidx, n) || grow(&s->d_cand, n) || grow(&s->d_lcount, n) || grow(&s->d_q, 3 * n) || grow(&s->d_r, n) ||
-        grow(&s->d_oidx, n) || grow(&s->d_od2, n))
-        return PCT_ERR_ALLOC;
-    s->cap = n;
-    return PCT_OK;
+    const size_t n = (size_t)std::max<int64_t>(Q, 256);
+    return regrow(s->cap, n, part(s->d_ld2, n), part(s->d_lidx, n), part(s->d_cand, n), part(s->d_lcount, n), part(s->d_q, 3 * n), part(s->d_r, n),
+                  part(s->d_oidx, n), part(s->d_od2, n));
 }
 
 }  // namespace
@@ -134,9 +138,7 @@ int pct_shard_destroy(pct_shard *s)
     if (!s) return PCT_OK;
     (void)hipDeviceSynchronize();
     if (s->own_comm && s->comm) (void)ncclCommDestroy(s->comm);
-    for (void *p : { (void *)s->d_ld2, (void *)s->d_lidx, (void *)s->d_cand, (void *)s->d_lcount, (void *)s->d_q, (void *)s->d_r, (void *)s->d_oidx, (void *)s->d_od2 })
-        if (p) (void)hipFree(p);
-    delete s;
+    delete s;                        // the workspaces go with it
     return PCT_OK;
 }
 
@@ -228,26 +230,26 @@ struct pct_route {
     double halo = 0.0;
     int64_t n_total = 0, n_slab = 0;
     pct_cloud *slab = nullptr;
-    uint32_t *d_gid = nullptr;
+    DevBuf<uint32_t> d_gid;
     // batch workspaces
     int64_t cap = 0;
-    uint32_t *d_counts = nullptr, *d_mine_ids = nullptr, *d_lidx = nullptr, *d_flag = nullptr, *d_flag_ids = nullptr, *d_fidx = nullptr;
-    float *d_mine_q = nullptr, *d_fq = nullptr;
-    double *d_ld2 = nullptr, *d_fd2 = nullptr, *d_fbest = nullptr;
-    int32_t *d_fcand = nullptr;
-    RouteAnswer *d_send = nullptr, *d_recv = nullptr;
+    DevBuf<uint32_t> d_counts, d_mine_ids, d_lidx, d_flag, d_flag_ids, d_fidx;
+    DevBuf<float> d_mine_q, d_fq;
+    DevBuf<double> d_ld2, d_fd2, d_fbest;
+    DevBuf<int32_t> d_fcand;
+    DevBuf<RouteAnswer> d_send, d_recv;
     uint32_t h_counts[kRouteMaxWorld] = {};
     int64_t mine = 0, flagged = 0;
     uint64_t st_owned = 0, st_uncert = 0, st_batches = 0;
     // partitioned batches (every rank brings its own queries): send side sized by this rank's Q, receive side by what the others route here
     int64_t pq_cap = 0, pr_cap = 0, pf_cap = 0;
-    unsigned char *d_owner = nullptr;
-    uint32_t *d_pflag = nullptr, *d_pflag_ids = nullptr;
-    uint32_t *d_pcnt = nullptr, *d_pmat = nullptr, *d_sq_slot = nullptr, *d_rq_slot = nullptr, *d_plidx = nullptr, *d_pfidx = nullptr;
-    float *d_sq_xyz = nullptr, *d_rq_xyz = nullptr, *d_pfq_mine = nullptr, *d_pfq_all = nullptr;
-    double *d_pld2 = nullptr, *d_pfd2 = nullptr, *d_pfbest = nullptr;
-    int32_t *d_pfcand = nullptr;
-    RouteAnswer *d_ans_out = nullptr, *d_ans_in = nullptr;
+    DevBuf<unsigned char> d_owner;
+    DevBuf<uint32_t> d_pflag, d_pflag_ids;
+    DevBuf<uint32_t> d_pcnt, d_pmat, d_sq_slot, d_rq_slot, d_plidx, d_pfidx;
+    DevBuf<float> d_sq_xyz, d_rq_xyz, d_pfq_mine, d_pfq_all;
+    DevBuf<double> d_pld2, d_pfd2, d_pfbest;
+    DevBuf<int32_t> d_pfcand;
+    DevBuf<RouteAnswer> d_ans_out, d_ans_in;
     uint32_t p_send[kRouteMaxWorld] = {};          // how many of my queries each rank owns
     int64_t p_recv = 0;                            // how many queries the others (and I) route to me
 };
@@ -258,14 +260,10 @@ int route_reserve(pct_route *r, int64_t Q)
 {
     if (Q <= r->cap) return PCT_OK;
     HIPCHK(hipDeviceSynchronize());
-    r->cap = 0;
-    const int64_t n = std::max<int64_t>(Q, 256);
-    if (grow(&r->d_counts, kRouteMaxWorld) || grow(&r->d_mine_ids, n) || grow(&r->d_lidx, n) || grow(&r->d_flag, 4) || grow(&r->d_flag_ids, n) || grow(&r->d_fidx, n) ||
-        grow(&r->d_mine_q, 3 * n) || grow(&r->d_fq, 3 * n) || grow(&r->d_ld2, n) || grow(&r->d_fd2, n) || grow(&r->d_fbest, n) || grow(&r->d_fcand, n) ||
-        grow(&r->d_send, n) || grow(&r->d_recv, n))
-        return PCT_ERR_ALLOC;
-    r->cap = n;
-    return PCT_OK;
+    const size_t n = (size_t)std::max<int64_t>(Q, 256);
+    return regrow(r->cap, n, part(r->d_counts, kRouteMaxWorld), part(r->d_mine_ids, n), part(r->d_lidx, n), part(r->d_flag, 4), part(r->d_flag_ids, n), part(r->d_fidx, n),
+                  part(r->d_mine_q, 3 * n), part(r->d_fq, 3 * n), part(r->d_ld2, n), part(r->d_fd2, n), part(r->d_fbest, n), part(r->d_fcand, n),
+                  part(r->d_send, n), part(r->d_recv, n));
 }
 
 // ---- build, per rank: statistics of the local rows ----
@@ -347,7 +345,7 @@ int route_load_slab(pct_route *r, const PointRec *d_recs, int64_t n)
 {
     r->n_slab = n;
     PCTCHK(pct_cloud_create(std::max<int64_t>(n, 1), &r->slab));
-    if (grow(&r->d_gid, std::max<int64_t>(n, 1))) return PCT_ERR_ALLOC;
+    if (const int st = r->d_gid.reset((size_t)std::max<int64_t>(n, 1))) return st;
     if (n) {
         PCTCHK(pct_cloud_upload_aos_dev(r->slab, d_recs, n, sizeof(PointRec)));
         HIPCHK(hipMemcpy2D(r->d_gid, sizeof(uint32_t), reinterpret_cast<const unsigned char *>(d_recs) + 12, sizeof(PointRec), sizeof(uint32_t), (size_t)n, hipMemcpyDeviceToDevice));
@@ -431,33 +429,23 @@ int part_reserve_send(pct_route *r, int64_t Q)
 {
     if (r->pq_cap > 0 && Q <= r->pq_cap) return PCT_OK;      // a first batch of NO queries still needs the counters and the flag word
     HIPCHK(hipDeviceSynchronize());
-    r->pq_cap = 0;
-    const int64_t n = std::max<int64_t>(Q, 256);
-    if (grow(&r->d_owner, n) || grow(&r->d_pcnt, 4 * kRouteMaxWorld) || grow(&r->d_pmat, (int64_t)kRouteMaxWorld * kRouteMaxWorld + kRouteMaxWorld) || grow(&r->d_sq_slot, n) ||
-        grow(&r->d_sq_xyz, 3 * n) || grow(&r->d_ans_in, n) || grow(&r->d_pflag, 4) || grow(&r->d_pflag_ids, n) || grow(&r->d_pfq_mine, 3 * n))
-        return PCT_ERR_ALLOC;
-    r->pq_cap = n;
-    return PCT_OK;
+    const size_t n = (size_t)std::max<int64_t>(Q, 256);
+    return regrow(r->pq_cap, n, part(r->d_owner, n), part(r->d_pcnt, 4 * kRouteMaxWorld), part(r->d_pmat, (size_t)kRouteMaxWorld * kRouteMaxWorld + kRouteMaxWorld),
+                  part(r->d_sq_slot, n), part(r->d_sq_xyz, 3 * n), part(r->d_ans_in, n), part(r->d_pflag, 4), part(r->d_pflag_ids, n), part(r->d_pfq_mine, 3 * n));
 }
 int part_reserve_recv(pct_route *r, int64_t n_recv)
 {
     if (n_recv <= r->pr_cap) return PCT_OK;
     HIPCHK(hipDeviceSynchronize());
-    r->pr_cap = 0;
-    const int64_t n = std::max<int64_t>(n_recv + n_recv / 4, 256);
-    if (grow(&r->d_rq_slot, n) || grow(&r->d_rq_xyz, 3 * n) || grow(&r->d_plidx, n) || grow(&r->d_pld2, n) || grow(&r->d_ans_out, n)) return PCT_ERR_ALLOC;
-    r->pr_cap = n;
-    return PCT_OK;
+    const size_t n = (size_t)std::max<int64_t>(n_recv + n_recv / 4, 256);
+    return regrow(r->pr_cap, n, part(r->d_rq_slot, n), part(r->d_rq_xyz, 3 * n), part(r->d_plidx, n), part(r->d_pld2, n), part(r->d_ans_out, n));
 }
 int part_reserve_flag(pct_route *r, int64_t F)
 {
     if (F <= r->pf_cap) return PCT_OK;
     HIPCHK(hipDeviceSynchronize());
-    r->pf_cap = 0;
-    const int64_t n = std::max<int64_t>(2 * F, 256);
-    if (grow(&r->d_pfq_all, 3 * n) || grow(&r->d_pfidx, n) || grow(&r->d_pfd2, n) || grow(&r->d_pfbest, n) || grow(&r->d_pfcand, n)) return PCT_ERR_ALLOC;
-    r->pf_cap = n;
-    return PCT_OK;
+    const size_t n = (size_t)std::max<int64_t>(2 * F, 256);
+    return regrow(r->pf_cap, n, part(r->d_pfq_all, 3 * n), part(r->d_pfidx, n), part(r->d_pfd2, n), part(r->d_pfbest, n), part(r->d_pfcand, n));
 }
 
 int part_phase_count(pct_route *r, const float *d_q, int64_t Q, hipStream_t st)
@@ -539,14 +527,7 @@ void route_free(pct_route *r)
     if (!r) return;
     (void)hipDeviceSynchronize();
     if (r->slab) (void)pct_cloud_destroy(r->slab);
-    for (void *p : { (void *)r->d_pflag, (void *)r->d_pflag_ids, (void *)r->d_owner, (void *)r->d_pcnt, (void *)r->d_pmat, (void *)r->d_sq_slot, (void *)r->d_rq_slot, (void *)r->d_plidx, (void *)r->d_pfidx, (void *)r->d_sq_xyz,
-                     (void *)r->d_rq_xyz, (void *)r->d_pfq_mine, (void *)r->d_pfq_all, (void *)r->d_pld2, (void *)r->d_pfd2, (void *)r->d_pfbest, (void *)r->d_pfcand,
-                     (void *)r->d_ans_out, (void *)r->d_ans_in })
-        if (p) (void)hipFree(p);
-    for (void *p : { (void *)r->d_gid, (void *)r->d_counts, (void *)r->d_mine_ids, (void *)r->d_lidx, (void *)r->d_flag, (void *)r->d_flag_ids, (void *)r->d_fidx, (void *)r->d_mine_q,
-                     (void *)r->d_fq, (void *)r->d_ld2, (void *)r->d_fd2, (void *)r->d_fbest, (void *)r->d_fcand, (void *)r->d_send, (void *)r->d_recv })
-        if (p) (void)hipFree(p);
-    delete r;
+    delete r;                        // the workspaces go with it
 }
 
 pct_route *route_new(pct_shard *s, const Layout &Y, const double *cuts, double halo_spacings)
@@ -573,9 +554,8 @@ int pct_shard_route_build(pct_shard *s, const void *local_points, int64_t n_loca
     const int W = s->world;
     hipStream_t st = nullptr;
     // global bounding box / count, then the histogram along the longest axis: three small all-reduces on one device buffer
-    double *d_buf = nullptr;
-    if (grow(&d_buf, kRouteBins + 16)) return PCT_ERR_ALLOC;
-    struct Free { double *&p; ~Free() { if (p) (void)hipFree(p); } } free_buf{ d_buf };
+    DevBuf<double> d_buf;
+    if (const int e = d_buf.reset(kRouteBins + 16)) return e;
     LocalStats L = local_stats(pts, n_local, stride_bytes), G = L;
     HIPCHK(hipMemcpy(d_buf, L.lo, sizeof(double) * 3, hipMemcpyHostToDevice));
     NCCLCHK(ncclAllReduce(d_buf, d_buf, 3, ncclDouble, ncclMin, s->comm, st));
@@ -608,9 +588,8 @@ int pct_shard_route_build(pct_shard *s, const void *local_points, int64_t n_loca
     std::vector<uint32_t> send_n((size_t)W), all_n((size_t)W * W);
     for (int k = 0; k < W && G.n > 0; k++) select_for(pts, n_local, stride_bytes, index_begin, r->axis, r->cuts[k] - r->halo, r->cuts[k + 1] + r->halo, to[(size_t)k]);
     for (int k = 0; k < W; k++) send_n[(size_t)k] = (uint32_t)to[(size_t)k].size();
-    uint32_t *d_n = nullptr;
-    if (grow(&d_n, (int64_t)W * W + W)) { route_free(r); return PCT_ERR_ALLOC; }
-    struct FreeN { uint32_t *&p; ~FreeN() { if (p) (void)hipFree(p); } } free_n{ d_n };
+    DevBuf<uint32_t> d_n;
+    if (const int e = d_n.reset((size_t)W * W + W)) { route_free(r); return e; }
     int stt = PCT_OK;
     auto bail = [&](int code) { route_free(r); return code; };
     if (hipMemcpy(d_n + (size_t)W * W, send_n.data(), sizeof(uint32_t) * W, hipMemcpyHostToDevice) != hipSuccess) return bail(sfail(PCT_ERR_HIP, "hipMemcpy failed"));
@@ -618,9 +597,8 @@ int pct_shard_route_build(pct_shard *s, const void *local_points, int64_t n_loca
     if (hipMemcpy(all_n.data(), d_n, sizeof(uint32_t) * W * W, hipMemcpyDeviceToHost) != hipSuccess) return bail(sfail(PCT_ERR_HIP, "hipMemcpy failed"));
     int64_t n_send = 0, n_recv = 0;
     for (int k = 0; k < W; k++) { n_send += send_n[(size_t)k]; n_recv += all_n[(size_t)k * W + s->rank]; }     // all_n[src * W + dst]
-    PointRec *d_out = nullptr, *d_in = nullptr;
-    if (grow(&d_out, n_send) || grow(&d_in, n_recv)) { if (d_out) (void)hipFree(d_out); return bail(PCT_ERR_ALLOC); }
-    struct FreeP { PointRec *&a, *&b; ~FreeP() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } free_p{ d_out, d_in };
+    DevBuf<PointRec> d_out, d_in;
+    if (d_out.reset((size_t)n_send) || d_in.reset((size_t)n_recv)) return bail(PCT_ERR_ALLOC);
     {
         int64_t off = 0;
         for (int k = 0; k < W; k++) {
@@ -753,12 +731,11 @@ int pct_shard_route_build_world(pct_shard *const *ranks, int world, const void *
         std::vector<PointRec> recs;                      // source ranks in order: ascending global index
         for (int src = 0; src < world && G.n > 0; src++)
             select_for(static_cast<const unsigned char *>(local_points[src]), n_local[src], stride_bytes, index_begin[src], r->axis, r->cuts[dst] - r->halo, r->cuts[dst + 1] + r->halo, recs);
-        PointRec *d_in = nullptr;
-        if (grow(&d_in, (int64_t)recs.size())) return PCT_ERR_ALLOC;
+        DevBuf<PointRec> d_in;
+        if (const int e = d_in.reset(recs.size())) return e;
         int stt = PCT_OK;
         if (!recs.empty() && hipMemcpy(d_in, recs.data(), sizeof(PointRec) * recs.size(), hipMemcpyHostToDevice) != hipSuccess) stt = sfail(PCT_ERR_HIP, "hipMemcpy failed");
         if (stt == PCT_OK) stt = route_load_slab(r, d_in, (int64_t)recs.size());
-        (void)hipFree(d_in);
         if (stt != PCT_OK) return stt;
     }
     return PCT_OK;
@@ -850,10 +827,10 @@ int pct_shard_route_nn_partitioned_dev(pct_route *r, const float *d_q, int64_t Q
     const auto from = [&](int k) { return (int64_t)mat[(size_t)k * W + me]; };          // what rank k routes to me
     uint32_t back_n[kRouteMaxWorld];
     for (int k = 0; k < W; k++) back_n[k] = mat[(size_t)k * W + me];
-    PCTCHK(all_to_all(r->d_sq_xyz, r->p_send, r->d_rq_xyz, from, 12));
-    PCTCHK(all_to_all(r->d_sq_slot, r->p_send, r->d_rq_slot, from, 4));
+    PCTCHK(all_to_all(r->d_sq_xyz.get(), r->p_send, r->d_rq_xyz.get(), from, 12));
+    PCTCHK(all_to_all(r->d_sq_slot.get(), r->p_send, r->d_rq_slot.get(), from, 4));
     PCTCHK(part_phase_answer(r, st));
-    PCTCHK(all_to_all(r->d_ans_out, back_n, r->d_ans_in, [&](int k) { return (int64_t)r->p_send[k]; }, sizeof(RouteAnswer)));     // the answers go home
+    PCTCHK(all_to_all(r->d_ans_out.get(), back_n, r->d_ans_in.get(), [&](int k) { return (int64_t)r->p_send[k]; }, sizeof(RouteAnswer)));     // the answers go home
     PCTCHK(part_phase_scatter(r, Q, d_idx, d_d2, st));
     // second round: all uncertified queries of all ranks, answered by everybody
     uint32_t fmine = (uint32_t)r->flagged;

@@ -144,6 +144,8 @@ __global__ __launch_bounds__(256) void vox_report_kernel(const uint32_t *__restr
     if (voxel_index) voxel_index[i] = pslot[i] == kNoSlot ? -1 : (int32_t)vals[pslot[i]];
 }
 
+using pct_host::dropped;
+using pct_host::part;
 using pct_internal::DevBuf;
 
 inline int blocks_for(int64_t n, int per) { return (int)std::max<int64_t>(1, (n + per - 1) / per); }
@@ -176,11 +178,7 @@ namespace {
 
 int table_alloc(pct_voxel_map *m, uint32_t T)
 {
-    m->T = 0;
-    m->keys.release(); m->vals.release();
-    PCTCHK(m->keys.reset(T));
-    PCTCHK(m->vals.reset(T));
-    m->T = T;
+    PCTCHK(pct_host::regrow(m->T, T, part(m->keys, T), part(m->vals, T)));
     vox_table_init_kernel<<<std::min(blocks_for(T, 256), 4096), 256, 0, pct_internal::stream()>>>(m->keys, m->vals, T);
     HIPCHK(hipGetLastError());
     return PCT_OK;
@@ -232,13 +230,8 @@ int ensure_scratch(pct_voxel_map *m, int64_t n)
 {
     if (n <= m->ncap) return PCT_OK;
     const int64_t cap = std::max<int64_t>(n, m->ncap * 2);
-    m->ncap = 0;
-    m->pslot.release(); m->rank.release(); m->tile.release(); m->d_is_new.release(); m->d_index.release();
-    PCTCHK(m->pslot.reset(cap));
-    PCTCHK(m->rank.reset(cap));
-    PCTCHK(m->tile.reset((cap + kTile - 1) / kTile));
-    m->ncap = cap;
-    return PCT_OK;
+    // the two report arrays go with the group: pct_voxel_map_add allocates them when a caller asks for them
+    return pct_host::regrow(m->ncap, cap, part(m->pslot, cap), part(m->rank, cap), part(m->tile, (cap + kTile - 1) / kTile), dropped(m->d_is_new), dropped(m->d_index));
 }
 
 template <typename T>

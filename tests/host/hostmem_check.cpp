@@ -64,23 +64,6 @@ int g_failed = 0;
         if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); g_failed++; } \
     } while (0)
 
-// a group that shares one capacity, grown as the engine's dedup_ensure grows its scratch
-struct Group {
-    B a, b, c;
-    size_t cap = 0;
-    int ensure(size_t n)
-    {
-        if (n <= cap) return 0;
-        cap = 0;
-        a.release(); b.release(); c.release();
-        if (const int st = a.reset(n)) return st;
-        if (const int st = b.reset(2 * n)) return st;
-        if (const int st = c.reset(n / 2 + 1)) return st;
-        cap = n;
-        return 0;
-    }
-};
-
 void check_buf()
 {
     {
@@ -123,15 +106,6 @@ void check_buf()
     }
     CHECK(g_live == 0 && g_live_bytes == 0 && g_allocs == g_releases);
     {
-        Group g;
-        CHECK(g.ensure(64) == 0 && g.cap == 64 && g_live == 3);
-        g_fail_in = 3;                                               // the third member fails
-        CHECK(g.ensure(128) == kErr && g.cap == 0);
-        CHECK(g.c.get() == nullptr && g_live == 2);
-        CHECK(g.ensure(16) == 0 && g.cap == 16 && g_live == 3);      // the next call rebuilds the whole group
-    }
-    CHECK(g_live == 0 && g_live_bytes == 0 && g_allocs == g_releases);
-    {
         pct_host::Buf<double, FakePair> m;
         CHECK(m.reset(8) == 0 && g_pair_live == 1);
         CHECK(m.host() != nullptr && (char *)m.get() == (char *)m.host() + 1 && (double *)m == m.get());
@@ -139,6 +113,60 @@ void check_buf()
         CHECK(m.reserve(9) == 0 && g_pair_live == 1 && g_pair_releases == 1);
     }
     CHECK(g_pair_live == 0 && g_pair_releases == 2);
+}
+
+// pct_host::regrow over three element types and a fourth part that is only released, under one capacity variable
+void check_group()
+{
+    using pct_host::dropped;
+    using pct_host::part;
+    {
+        B a, d;
+        pct_host::Buf<double, FakeMem> b;
+        pct_host::Buf<char, FakeMem> c;
+        size_t cap = 0;
+        const auto ensure = [&](size_t n) {
+            if (n <= cap) return 0;                                  // the call site's own test
+            return pct_host::regrow(cap, n, part(a, n), part(b, 2 * n), part(c, n / 2 + 1), dropped(d));
+        };
+        const auto none_live = [&] { return !a && !b && !c && !d && g_live == 0; };
+        CHECK(d.reset(4) == 0 && g_live == 1);                       // the fourth holds a block of its own before the first growth
+        for (size_t n : { (size_t)64, (size_t)128 }) {               // 0 -> n -> 2n
+            CHECK(ensure(n) == 0 && cap == n && g_live == 3);
+            CHECK(a.capacity() == n && b.capacity() == 2 * n && c.capacity() == n / 2 + 1);
+            CHECK(!d && d.capacity() == 0);                          // released with the group, not allocated
+            a.get()[n - 1] = 1; b.get()[2 * n - 1] = 1.0; c.get()[n / 2] = 1;
+        }
+        int allocs = g_allocs;
+        g_live_at_last_request = -1;
+        CHECK(ensure(256) == 0 && cap == 256 && g_live == 3);
+        CHECK(g_allocs == allocs + 3);
+        allocs = g_allocs;
+        const int rel = g_releases;
+        CHECK(ensure(256) == 0 && ensure(1) == 0);                   // the test passes: nothing is allocated or released
+        CHECK(g_allocs == allocs && g_releases == rel && cap == 256);
+        for (int k = 1; k <= 3; k++) {                               // the k-th allocation of a regrowth fails
+            const size_t n = 2 * cap;
+            g_fail_in = k;
+            CHECK(ensure(n) == kErr);
+            CHECK(cap == 0 && none_live());
+            CHECK(ensure(n) == 0 && cap == n && g_live == 3);        // ... and the next growth builds the whole group
+            CHECK(a.capacity() == n && b.capacity() == 2 * n && c.capacity() == n / 2 + 1 && !d);
+        }
+    }
+    CHECK(g_live == 0 && g_live_bytes == 0 && g_allocs == g_releases);
+    {
+        // every old block is gone before the first allocation of a regrowth asks for memory
+        B a;
+        pct_host::Buf<double, FakeMem> b;
+        pct_host::Buf<char, FakeMem> c;
+        size_t cap = 0;
+        CHECK(pct_host::regrow(cap, 8, part(a, 8), part(b, 8), part(c, 8)) == 0 && g_live == 3);
+        g_fail_in = 1;                                               // the first request of the regrowth is the last one made
+        CHECK(pct_host::regrow(cap, 16, part(a, 16), part(b, 16), part(c, 16)) == kErr);
+        CHECK(g_live_at_last_request == 0 && cap == 0 && g_live == 0);
+    }
+    CHECK(g_live == 0 && g_live_bytes == 0 && g_allocs == g_releases);
 }
 
 void check_pow2()
@@ -183,6 +211,7 @@ void check_wait_word()
 int main()
 {
     check_buf();
+    check_group();
     check_pow2();
     check_wait_word();
     if (g_failed) { std::printf("%d checks failed\n", g_failed); return 1; }

@@ -2,8 +2,9 @@
 object that owns the buffer is in use, and the count of live blocks once every handle is closed.
 
 References: the numpy models of the neighbouring tests -- tests/helpers (ring_dedup_model, ring_remove_model, depth_model,
-bezier_model), ref_knn of test_gpu_knn.py, ref_masks / rows_from of test_gpu_radius_search.py, ref_inflate of
+bezier_model, segment_search_model), ref_knn of test_gpu_knn.py, ref_masks / rows_from of test_gpu_radius_search.py, ref_inflate of
 test_gpu_ring_remove.py.  Every comparison is exact."""
+import ctypes
 import functools
 import os
 import subprocess
@@ -18,6 +19,7 @@ from test_gpu_expand_ring import expand, make_nodes
 from test_gpu_knn import ref_knn
 from test_gpu_radius_search import check as check_lists, ref_masks, rows_from
 from test_gpu_ring_remove import PRM, check_counts, params, ref_inflate, traj_through
+from test_gpu_segments import segments
 from test_depth_api import random_view
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -26,6 +28,7 @@ import bezier_model as B  # noqa: E402
 import depth_model as D  # noqa: E402
 import ring_dedup_model as M  # noqa: E402
 import ring_remove_model as R  # noqa: E402
+import segment_search_model as SS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -295,10 +298,90 @@ def test_bezier_staging_grows_between_trajectories(E):
     bezier_rounds(E)
 
 
-# ---- 7. nothing left behind ---------------------------------------------------------------------------------------------------------------------
+# ---- 7. the groups of buffers that share one capacity (hostmem.hpp regrow) ------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def group_case():
+    """(5000 uniform points, 4097 queries, the queries' nearest neighbours, their counts within GROUP_R), computed once"""
+    pts = synth.uniform_points(491, 5000, 0, 10)
+    q = synth.uniform_points(492, 4097, 0, 10)
+    ni, nd = ref_knn(pts, q, 1)
+    counts = np.concatenate([np.array([int(hit.sum()) for _, hit in ref_masks(pts, q[a:a + 512], GROUP_R)], np.uint32) for a in range(0, len(q), 512)])
+    return pts, q, ni[:, 0], nd[:, 0], counts
+
+
+GROUP_R = np.float32(0.8)
+
+
+def grid_cloud(E, pts):
+    c = E.Cloud(len(pts))
+    c.set_input(pts)
+    c.build_grid()
+    return c
+
+
+def test_query_and_list_search_workspaces_regrow_together(E):
+    """256 queries are the floor of the query workspaces; 257 regrow them and, behind them, the list search's scan / cursor / queue"""
+    pts, q = group_case()[:2]
+    c = grid_cloud(E, pts)
+    for Q in (256, 257):
+        want = rows_from(ref_masks(pts, q[:Q], GROUP_R), 1)
+        assert want[0][-1] > Q
+        check_lists(c.radius_search(q[:Q], GROUP_R, 1), want, f"radius search of {Q} queries")
+    c.close()
+
+
+def test_list_stores_regrow_and_are_reused(E):
+    """a small total, a larger one (the store regrows), the small one again (it does not); the capsule search's store carries s"""
+    pts, q = group_case()[:2]
+    c = grid_cloud(E, pts)
+    totals = []
+    for r in (0.4, 2.0, 0.4):
+        want = rows_from(ref_masks(pts, q[:64], np.float32(r)), 1)
+        totals.append(int(want[0][-1]))
+        check_lists(c.radius_search(q[:64], np.float32(r), 1), want, f"radius search at {r}")
+    assert 0 < totals[0] == totals[2] < totals[1] // 20
+    segs = segments(493, 64, 0.0, 10.0, [0.0, 0.05, 3.0, 6.0], pts)
+    totals = []
+    for reach in (0.3, 1.5, 0.3):
+        want = SS.segment_search(pts, segs, reach, 1)
+        totals.append(int(want[0][-1]))
+        go, gi, gd, gs = c.segment_search(segs, reach, 1)
+        check_lists((go, gi, gd), want[:3], f"capsule search at {reach}")
+        assert gs.dtype == np.float64 and np.array_equal(gs, want[3]), f"capsule search at {reach}: s"
+    assert 0 < totals[0] == totals[2] < totals[1] // 10
+    c.close()
+
+
+def test_knn_rows_regrow(E):
+    pts, q = group_case()[:2]
+    ki, kd = ref_knn(pts, q[:5], 64)
+    c = grid_cloud(E, pts)
+    for Q, k in ((3, 2), (3, 3), (5, 64), (3, 2)):
+        gi, gd = c.knn(q[:Q], k)
+        assert np.array_equal(gd, kd[:Q, :k]) and np.array_equal(gi, ki[:Q, :k]), f"k-NN of {Q} x {k}"
+    c.close()
+
+
+def test_mapped_io_regrows_at_its_floor(E):
+    """4096 queries fill the floor of the host-mapped query / result buffers, 4097 double it (both between the express limit of 1024
+    and the mapped path's 65536)"""
+    pts, q, ni, nd, counts = group_case()
+    assert counts.min() < counts.max()
+    c = grid_cloud(E, pts)
+    for Q in (4096, 4097):
+        gi, gd = c.nn(q[:Q])
+        assert np.array_equal(gd, nd[:Q]) and np.array_equal(gi, ni[:Q]), f"NN of {Q} queries"
+        cnt = c.radius_count(q[:Q], GROUP_R)
+        assert cnt.dtype == np.uint32 and np.array_equal(cnt, counts[:Q]), f"radius count of {Q} queries"
+    c.close()
+
+
+# ---- 8. nothing left behind ---------------------------------------------------------------------------------------------------------------------
 
 def other_handles(E):
-    """the handles items 1-6 do not make: a small node cloud with the fused expansion over a grid cloud, a voxel map, one pct_traj call"""
+    """the handles items 1-6 do not make: a small node cloud with the fused expansion over a grid cloud, a voxel map, one pct_traj call,
+    a 4-dimensional node set grown from 2 rows past its floor of 1024 (with a copy)"""
     from pointcloudtraj_amd import traj as TJ, voxel
     pts = synth.uniform_points(481, 5000, 0, 10)
     c = E.Cloud(len(pts))
@@ -314,6 +397,19 @@ def other_handles(E):
     v.close()
     coef, T, od = traj_through()
     TJ.wire_sample(TJ.get_bezier_traj_wire(coef, T, od), 11)
+    L, dp, h = E.lib(), ctypes.POINTER(ctypes.c_double), ctypes.c_void_p()
+    assert L.pct_nodeset_create(4, 2, ctypes.byref(h)) == 0
+    rows = np.round(synth.uniform_rows_f64(485, 1500, 4, 0.0, 3.0))
+    for a in (0, 1000):                                                              # the second append takes the set past its 1024 rows: new blocks and a copy
+        blk = np.ascontiguousarray(rows[a:a + 1000])
+        assert L.pct_nodeset_append(h, blk.ctypes.data_as(dp), len(blk)) == 0
+    idx, ties, d2 = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_double()
+    qq = np.float64([1, 2, 1, 2])
+    d = (rows - qq) ** 2
+    sq = ((d[:, 0] + d[:, 1]) + d[:, 2]) + d[:, 3]
+    assert L.pct_nodeset_nearest(h, qq.ctypes.data_as(dp), ctypes.byref(idx), ctypes.byref(d2), ctypes.byref(ties)) == 0
+    assert d2.value == sq.min() and idx.value == int(np.flatnonzero(sq == sq.min())[0]) and ties.value == int((sq == sq.min()).sum())
+    assert L.pct_nodeset_destroy(h) == 0
 
 
 def test_closed_handles_leave_no_buffer_behind(E):
