@@ -35,6 +35,8 @@ namespace pct {
 struct GeneratedTrajectories {
     std::vector<double> centres, radius, seg_time, start_state, end_state, polycoef;
     std::vector<int32_t> orders, seg_offsets;
+    std::vector<double> planes;             // generateTrajectoriesInPolyhedra: the candidates' planes; centres then holds the anchors
+    std::vector<int32_t> plane_offsets;
     std::vector<pct_trajgen_result> results;
     int64_t row_stride = 0;
     pct_bezier_batch batch() const
@@ -78,6 +80,54 @@ inline int64_t generateTrajectories(const double *path, const double *radius, co
                                out.start_state.data(), out.end_state.data(), K };
     if (pct_bezier_generate_batch(&b, &params, out.polycoef.data(), out.row_stride, out.results.data()) != PCT_OK)
         throw std::runtime_error(std::string("pct_bezier_generate_batch: ") + pct_last_error());
+    int64_t ok = 0;
+    for (const pct_trajgen_result &r : out.results) ok += r.status == PCT_GEN_OK ? 1 : 0;
+    return ok;
+}
+
+// The same in a polyhedral corridor (pct_trajgen.h, paragraph "Trajectory generation in polyhedra"): waypoints = m + 1 route points
+// ((m + 1) x 3), segment s runs along the edge waypoints[s] -> waypoints[s + 1] inside the polytope planes[plane_offsets[s] ..
+// plane_offsets[s + 1]) (4 doubles each: n0 n1 n2 off, n . y <= off; plane_offsets has m + 1 entries, as ObstacleMap::segmentPolyhedra
+// fills them; at most pct_trajgen_max_planes() planes per edge).  The start iterate of a segment is its edge's midpoint.  times and
+// orders are m each; the caller supplies the times.  Returns the number of candidates that are PCT_GEN_OK; results[k].sphere_slack is
+// the corridor slack.
+inline int64_t generateTrajectoriesInPolyhedra(const double *waypoints, const double *planes, const int64_t *plane_offsets, const double *times,
+                                               const int32_t *orders, int32_t m, const double *scales, int64_t K, const double start[9],
+                                               const double end[9], const pct_trajgen_params &params, GeneratedTrajectories &out)
+{
+    if (m < 1 || K < 0 || !waypoints || !plane_offsets || !times || !orders || (K > 0 && !scales) || !start || !end || plane_offsets[0] != 0)
+        throw std::runtime_error("generateTrajectoriesInPolyhedra: bad arguments");
+    for (int32_t s = 0; s < m; s++)
+        if (plane_offsets[s + 1] < plane_offsets[s]) throw std::runtime_error("generateTrajectoriesInPolyhedra: plane_offsets descend");
+    const int64_t np = plane_offsets[m];
+    if (np > 0 && !planes) throw std::runtime_error("generateTrajectoriesInPolyhedra: bad arguments");
+    const size_t total = (size_t)K * (size_t)m;
+    out.centres.resize(3 * total); out.radius.clear(); out.seg_time.resize(total); out.orders.resize(total);
+    out.seg_offsets.resize((size_t)K + 1); out.start_state.resize(9 * (size_t)K); out.end_state.resize(9 * (size_t)K);
+    out.planes.resize(4 * (size_t)K * (size_t)np + 4); out.plane_offsets.resize(total + 1);
+    out.results.assign((size_t)K, pct_trajgen_result{});
+    int32_t max_order = 0;
+    for (int32_t s = 0; s < m; s++) max_order = orders[s] > max_order ? orders[s] : max_order;
+    out.row_stride = 3 * (int64_t)((max_order > 12 ? 12 : max_order < 5 ? 5 : max_order) + 1);
+    out.polycoef.assign(total * (size_t)out.row_stride, 0.0);
+    out.seg_offsets[0] = 0;
+    out.plane_offsets[0] = 0;
+    for (int64_t k = 0; k < K; k++) {
+        for (int32_t s = 0; s < m; s++) {
+            const size_t g = (size_t)k * (size_t)m + (size_t)s;
+            for (int d = 0; d < 3; d++) out.centres[3 * g + d] = 0.5 * (waypoints[3 * s + d] + waypoints[3 * (s + 1) + d]);
+            out.seg_time[g] = times[s] * scales[k];
+            out.orders[g] = orders[s];
+            out.plane_offsets[g + 1] = (int32_t)(k * np + plane_offsets[s + 1]);
+        }
+        for (int64_t j = 0; j < 4 * np; j++) out.planes[(size_t)(4 * k * np + j)] = planes[j];
+        out.seg_offsets[(size_t)k + 1] = (int32_t)((k + 1) * m);
+        for (int i = 0; i < 9; i++) { out.start_state[9 * (size_t)k + i] = start[i]; out.end_state[9 * (size_t)k + i] = end[i]; }
+    }
+    const pct_trajgen_poly_batch b{ out.centres.data(), out.planes.data(), out.plane_offsets.data(), out.seg_time.data(), out.orders.data(),
+                                    out.seg_offsets.data(), out.start_state.data(), out.end_state.data(), K };
+    if (pct_bezier_generate_poly_batch(&b, &params, out.polycoef.data(), out.row_stride, out.results.data()) != PCT_OK)
+        throw std::runtime_error(std::string("pct_bezier_generate_poly_batch: ") + pct_last_error());
     int64_t ok = 0;
     for (const pct_trajgen_result &r : out.results) ok += r.status == PCT_GEN_OK ? 1 : 0;
     return ok;
@@ -563,6 +613,42 @@ public:
         prm.margin = margin;
         generateTrajectories(path, radius, times, orders, m, scales, K, start, end, prm, out);
         certificates.clear();
+        if (K == 0) return -1;
+        certifyTrajectories(out.batch(), certificates, max_depth);
+        int64_t best = -1;
+        for (int64_t k = 0; k < K; k++) {
+            if (out.results[(size_t)k].status != PCT_GEN_OK || certificates[(size_t)k].status != PCT_CERT_FREE) continue;
+            if (best < 0 || out.results[(size_t)k].duration < out.results[(size_t)best].duration) best = k;
+        }
+        return best;
+    }
+
+    // Route -> polytopes -> trajectory -> proof: the m edges of waypoints ((m + 1) x 3) get their free-space polyhedra
+    // (segmentPolyhedra with `reach` and `margin`), one candidate per time scale is generated inside them (the edge midpoints as
+    // start iterates) and all are certified against this map.  The polytopes' planes already carry `margin`, so the generator runs
+    // with params.margin = 0: it is not taken off twice.  Returns -1 before anything is solved when an edge collides (an empty row of
+    // segmentPolyhedra: no polytope contains that edge) or a row holds more than pct_trajgen_max_planes() planes; otherwise the index
+    // of the shortest-duration candidate that is PCT_GEN_OK and PCT_CERT_FREE, or -1 when there is none.
+    int64_t generateSafeTrajectoryInPolyhedra(const double *waypoints, int32_t m, double reach, const double *times, const int32_t *orders,
+                                              const double *scales, int64_t K, const double start[9], const double end[9],
+                                              const pct_trajgen_params &limits, double margin, GeneratedTrajectories &out,
+                                              std::vector<pct_traj_certificate> &certificates, int max_depth = 12)
+    {
+        if (m < 1 || !waypoints) throw std::runtime_error("generateSafeTrajectoryInPolyhedra: bad arguments");
+        std::vector<double> segments(6 * (size_t)m), planes;
+        for (int32_t s = 0; s < m; s++)
+            for (int d = 0; d < 6; d++) segments[6 * (size_t)s + d] = waypoints[3 * s + d];
+        std::vector<int64_t> offsets;
+        segmentPolyhedra(segments, reach, margin, offsets, planes);
+        certificates.clear();
+        out.results.clear();
+        for (int32_t s = 0; s < m; s++) {
+            const int64_t cnt = offsets[(size_t)s + 1] - offsets[(size_t)s];
+            if (cnt == 0 || cnt > pct_trajgen_max_planes()) return -1;
+        }
+        pct_trajgen_params prm = limits;
+        prm.margin = 0.0;
+        generateTrajectoriesInPolyhedra(waypoints, planes.data(), offsets.data(), times, orders, m, scales, K, start, end, prm, out);
         if (K == 0) return -1;
         certifyTrajectories(out.batch(), certificates, max_depth);
         int64_t best = -1;

@@ -57,6 +57,50 @@
  * residuals; it is never OK.  B == 0: PCT_OK.  The device form is asynchronous on `stream`, has no host synchronisation inside and
  * can be captured; the host form copies, calls it and waits once.  A candidate's result does not depend on the rest of the batch:
  * alone or among others it gives the same bytes.
+ *
+ * Trajectory generation in polyhedra (pct_bezier_generate_poly_batch*): the contract.
+ *
+ * The same problem with another set for the control points: segment g owns the planes [plane_offsets[g], plane_offsets[g+1]), at
+ * most pct_trajgen_max_planes() = 24 of them, and every control point of segment g lies in C_g = { y : nh_k . y <= o_k }.  This is
+ * what pct_segment_polyhedron_batch produces around a route edge.  The objective, the rows of E, the Gv and Ga boxes, the ADMM
+ * iteration, alpha, the residuals, the stopping test, the rho rule, the output layout, B == 0 and the rule that a candidate's bytes
+ * do not depend on the rest of the batch are the sphere contract's, word for word; there are no balls in this form (a caller who
+ * wants spheres uses pct_bezier_generate_batch).  The planes are normalised once at load: len = |n| = sqrt((n0 n0 + n1 n1) + n2 n2),
+ * nh = n / len, o = off / len - margin.  A segment without planes is unconstrained in position: its projection is the identity.
+ * Start: x = the segment's anchor for every one of its control points, z = A x, u = 0.
+ *
+ * The projection.  z = the Euclidean projection of v onto C_g shrunk by 2 eps, { y : g_k(y) <= 0 }, g_k(y) = nh_k . y - (o_k - 2 eps)
+ * with nh . y = (nh0 y0 + nh1 y1) + nh2 y2 -- the sphere form's argument: when the max-norm residual passes, x is less than 2 eps from
+ * z in the 2-norm.  The point is unique; the algorithm that finds it is pinned, in this order:
+ *   1. v itself, if g_k(v) <= 0 for every k (no tolerance: then u = 0 exactly).
+ *   2. The KKT enumeration over active sets of one plane (i ascending), then two (i < j, i outer), then three (i < j < k).  The
+ *      candidate is the point on those planes nearest v, y = v - sum l_q nh_q, its multipliers l solving the Gram system of the unit
+ *      normals in closed form: l_i = g_i(v); with a = nh_i . nh_j, det = 1 - a a, l_i = (g_i - a g_j) / det, l_j = (g_j - a g_i) / det;
+ *      with b = nh_i . nh_k, c = nh_j . nh_k, det = ((1 + 2 ((a b) c)) - (a a + b b)) - c c and l = adj(G) g / det.  A pair or triple
+ *      with det < 1e-8 is skipped as near-parallel (a triple also when its first pair is).  A candidate counts when every multiplier
+ *      is >= 0; its worst violation w is the largest g_q(y) over the planes outside its active set (-inf when there are none).  The
+ *      first candidate with w <= 1e-9 (the accept tolerance, metres) is z.
+ *   3. Where rounding lets no active set pass -- or the set is empty -- z is the counting candidate with the smallest w, kept as
+ *      the enumeration goes: the first counting candidate is kept, and a later one takes its place only when its w is better by more
+ *      than 1e-9, so that rounding does not decide between equals.  There always is one: a plane v violates is a counting active
+ *      set of one.  The point is not moved further: the status below does not trust it.
+ * The two constants against the coordinates' ulp: a world of |y| <= 1e3 m has ulp <= 1.2e-13 m, so g carries an error of a few
+ * 1e-13; a Gram system with det >= 1e-8 (planes at an angle >= 1e-4 rad) magnifies that by at most about 1 / sqrt(det) = 1e4 in the
+ * candidate, to about 1e-9, the accept tolerance; and 1e-9 is four orders below the eps the solver is run at.  The previous
+ * iteration's active set is not tried first: the form kept is the plain enumeration.
+ *
+ * Results.  sphere_slack is, for this call, the corridor slack: the minimum over the control points and their planes of
+ * o_k - nh_k . P, the margin taken off and no 2 eps, recomputed from the returned x in the final pass (+inf for a candidate without
+ * planes).  PCT_GEN_OK requires r_prim <= eps, r_dual <= eps and slack >= 0: OK means every returned control point is inside every
+ * plane moved in by the margin, whatever the projection did -- the status does not lean on the two constants above -- and, a Bezier
+ * segment lying in the hull of its control points, the whole curve is in the polytope.
+ *
+ * Invalid candidates (PCT_GEN_INVALID, NaN rows, the other candidates untouched): the sphere form's conditions without the radius
+ * one, and a non-finite anchor; a non-finite plane or a plane whose |n| as computed above is 0 or not finite; more than 24 planes on
+ * one segment; plane_offsets descending inside the candidate.  An infeasible chain -- an empty polytope, a start point outside its
+ * polytope, two neighbouring polytopes without a common point -- ends as PCT_GEN_NOT_CONVERGED with honest residuals, never OK.  The
+ * host form gives PCT_ERR_INVALID with nothing written for a null pointer, plane_offsets[0] != 0 or a descent of plane_offsets
+ * anywhere, besides the sphere form's reasons; the device form cannot read the offsets and leaves them to the candidates.
  */
 #ifndef PCT_TRAJGEN_H
 #define PCT_TRAJGEN_H
@@ -105,6 +149,25 @@ int pct_bezier_generate_batch(const pct_trajgen_batch *batch, const pct_trajgen_
                               pct_trajgen_result *result);
 int pct_bezier_generate_batch_dev(const pct_trajgen_batch *d_fields, const pct_trajgen_params *params, double *d_polycoef, int64_t row_stride,
                                   pct_trajgen_result *d_res, void *stream);
+typedef struct pct_trajgen_poly_batch {   /* host pointers in the host form, device pointers in the _dev form */
+    const double  *anchors;        /* total_seg x 3: the start iterate of the segment's control points (e.g. the edge midpoint) */
+    const double  *planes;         /* total_planes x 4: n0 n1 n2 off, the half-space n . y <= off; n need not be a unit vector */
+    const int32_t *plane_offsets;  /* total_seg + 1, ascending, plane_offsets[0] = 0: segment g owns planes [po[g], po[g+1]) */
+    const double  *seg_time;       /* total_seg, > 0 */
+    const int32_t *orders;         /* total_seg, each 5..12 */
+    const int32_t *seg_offsets;    /* B + 1 */
+    const double  *start_state;    /* B x 9: p, v, a */
+    const double  *end_state;      /* B x 9 */
+    int64_t        B;
+} pct_trajgen_poly_batch;
+
+/* The polyhedral corridor ("Trajectory generation in polyhedra" above); sphere_slack of the record is the corridor slack. */
+int pct_bezier_generate_poly_batch(const pct_trajgen_poly_batch *batch, const pct_trajgen_params *params, double *polycoef, int64_t row_stride,
+                                   pct_trajgen_result *result);
+int pct_bezier_generate_poly_batch_dev(const pct_trajgen_poly_batch *d_fields, const pct_trajgen_params *params, double *d_polycoef, int64_t row_stride,
+                                       pct_trajgen_result *d_res, void *stream);
+int pct_trajgen_max_planes(void);         /* 24: the most planes one segment may own */
+
 /* timeAllocation (sim_planning_demo.cpp:603-686) on the host: n spheres -> n segment times.  The joints are the points between
  * neighbouring spheres where their surfaces are equally far; each leg start -> joints -> end gets the time of a trapezoidal speed
  * profile (speed up at acc_mean to vel_mean, cruise, slow down to rest), the first leg starting at init_vel projected on the leg.

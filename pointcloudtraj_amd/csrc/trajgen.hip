@@ -1,7 +1,7 @@
 // trajgen.hip -- the trajectory generator (include/pct_trajgen.h), part of libpct_engine.so: minimum-jerk piecewise Bezier curves
-// inside a chain of spheres, B candidates per launch, solved by ADMM.
+// inside a chain of spheres or of polytopes, B candidates per launch, solved by ADMM.
 //
-// The kernel is trajgen.hpp; here are the launch, the host form (staging copies, the device form, one wait) and the reference's
+// The kernel is trajgen.hpp, the polytopes' part of it trajgen_poly.hpp; here are the launches, the host form (staging copies, the device form, one wait) and the reference's
 // time allocation restated on the host.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "../../include/pct_trajgen.h"
 #include "engine_internal.hpp"
 #include "trajgen.hpp"
+#include "trajgen_poly.hpp"
 
 using pct_internal::fail;
 using namespace pct_trajgen;
@@ -108,6 +109,81 @@ int pct_bezier_generate_batch(const pct_trajgen_batch *h, const pct_trajgen_para
     HIPCHK(hipMemcpyAsync(doffs, h->seg_offsets, sizeof(int32_t) * (nb + 1), hipMemcpyHostToDevice, s));
     pct_trajgen_batch d = {dc, dr, dT, dorders, doffs, ds, de, B};
     PCTCHK(pct_bezier_generate_batch_dev(&d, params, d_out, row_stride, d_res, s));
+    if (nt) HIPCHK(hipMemcpyAsync(polycoef, d_out, sizeof(double) * nt * (size_t)row_stride, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(result, d_res, sizeof(pct_trajgen_result) * nb, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PCT_OK;
+}
+
+int pct_trajgen_max_planes(void) { return kMaxPlanes; }
+
+int pct_bezier_generate_poly_batch_dev(const pct_trajgen_poly_batch *d, const pct_trajgen_params *params, double *d_polycoef, int64_t row_stride,
+                                       pct_trajgen_result *d_res, void *stream)
+{
+    PCTCHK(check_params(params));
+    if (!d || d->B < 0) return fail(PCT_ERR_INVALID, "bad batch");
+    if (d->B == 0) return PCT_OK;
+    if (!d->anchors || !d->planes || !d->plane_offsets || !d->seg_time || !d->orders || !d->seg_offsets || !d->start_state || !d->end_state || !d_polycoef || !d_res)
+        return fail(PCT_ERR_INVALID, "null array");
+    if (row_stride < 3 * (kMinOrder + 1) || row_stride > (1 << 20)) return fail(PCT_ERR_INVALID, "row_stride %lld", (long long)row_stride);
+    if (d->B > 0x7fffffff) return fail(PCT_ERR_INVALID, "too many candidates");
+    PCTCHK(pct_internal::require_init());
+    static bool attr_set = false;
+    if (!attr_set) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(trajgen_poly_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PolyLds)));
+        attr_set = true;
+    }
+    trajgen_poly_kernel<<<(unsigned)d->B, kThreads, sizeof(PolyLds), (hipStream_t)stream>>>(*d, *params, d_polycoef, row_stride, d_res);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+int pct_bezier_generate_poly_batch(const pct_trajgen_poly_batch *h, const pct_trajgen_params *params, double *polycoef, int64_t row_stride,
+                                   pct_trajgen_result *result)
+{
+    PCTCHK(check_params(params));
+    if (!h || h->B < 0) return fail(PCT_ERR_INVALID, "bad batch");
+    if (h->B == 0) return PCT_OK;
+    if (!h->anchors || !h->planes || !h->plane_offsets || !h->seg_time || !h->orders || !h->seg_offsets || !h->start_state || !h->end_state || !polycoef || !result)
+        return fail(PCT_ERR_INVALID, "null array");
+    const int64_t B = h->B;
+    if (h->seg_offsets[0] != 0) return fail(PCT_ERR_INVALID, "seg_offsets[0] must be 0");
+    for (int64_t b = 0; b < B; b++)
+        if (h->seg_offsets[b + 1] < h->seg_offsets[b]) return fail(PCT_ERR_INVALID, "seg_offsets must not descend");
+    const int64_t total = h->seg_offsets[B];
+    if (h->plane_offsets[0] != 0) return fail(PCT_ERR_INVALID, "plane_offsets[0] must be 0");
+    for (int64_t s = 0; s < total; s++) {
+        if (h->plane_offsets[s + 1] < h->plane_offsets[s]) return fail(PCT_ERR_INVALID, "plane_offsets must not descend");
+        if (h->orders[s] >= kMinOrder && h->orders[s] <= kMaxOrder && 3 * (int64_t)(h->orders[s] + 1) > row_stride)
+            return fail(PCT_ERR_INVALID, "row_stride %lld too small for order %d", (long long)row_stride, h->orders[s]);
+    }
+    if (row_stride < 3 * (kMinOrder + 1)) return fail(PCT_ERR_INVALID, "row_stride %lld", (long long)row_stride);
+    PCTCHK(pct_internal::require_init());
+    hipStream_t s = pct_internal::stream();
+    const size_t nt = (size_t)total, nb = (size_t)B, np = (size_t)h->plane_offsets[total];
+    pct_internal::DevBuf<double> d_in, d_out;
+    pct_internal::DevBuf<int32_t> d_int;
+    pct_internal::DevBuf<pct_trajgen_result> d_res;
+    PCTCHK(d_in.reset(4 * nt + 18 * nb + 4 * np + 4));      // anchors | seg_time | start | end | planes
+    PCTCHK(d_out.reset(nt * (size_t)row_stride));
+    PCTCHK(d_int.reset(2 * nt + nb + 2));                   // orders | seg_offsets | plane_offsets
+    PCTCHK(d_res.reset(nb));
+    double *da = d_in, *dT = da + 3 * nt, *ds = dT + nt, *de = ds + 9 * nb, *dp = de + 9 * nb;
+    int32_t *dorders = d_int, *doffs = dorders + nt, *dpo = doffs + nb + 1;
+    if (nt) {
+        HIPCHK(hipMemcpyAsync(da, h->anchors, sizeof(double) * 3 * nt, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dT, h->seg_time, sizeof(double) * nt, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dorders, h->orders, sizeof(int32_t) * nt, hipMemcpyHostToDevice, s));
+        // the caller's rows come back as they were wherever the kernel writes nothing (a candidate without segments)
+        HIPCHK(hipMemcpyAsync(d_out, polycoef, sizeof(double) * nt * (size_t)row_stride, hipMemcpyHostToDevice, s));
+    }
+    if (np) HIPCHK(hipMemcpyAsync(dp, h->planes, sizeof(double) * 4 * np, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dpo, h->plane_offsets, sizeof(int32_t) * (nt + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ds, h->start_state, sizeof(double) * 9 * nb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(de, h->end_state, sizeof(double) * 9 * nb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(doffs, h->seg_offsets, sizeof(int32_t) * (nb + 1), hipMemcpyHostToDevice, s));
+    pct_trajgen_poly_batch d = {da, dp, dpo, dT, dorders, doffs, ds, de, B};
+    PCTCHK(pct_bezier_generate_poly_batch_dev(&d, params, d_out, row_stride, d_res, s));
     if (nt) HIPCHK(hipMemcpyAsync(polycoef, d_out, sizeof(double) * nt * (size_t)row_stride, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(result, d_res, sizeof(pct_trajgen_result) * nb, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));

@@ -7,6 +7,8 @@
 // An iteration is seven barriers: right-hand side, block solves, E w - b, the banded solve, E^T nu, block solves, projections.
 // fp64 throughout, -ffp-contract=off; every reduction is a max or runs in a fixed order, so a candidate's bytes do not depend on
 // the batch around it.  Plain C++ over the HIP built-ins only (tests/host/trajgen_check.cpp runs the same text on the CPU).
+// The body is generate<Set>: the set the control points of a segment are kept in -- a ball (BallSet, here) or a polytope (PolySet,
+// trajgen_poly.hpp) -- supplies its LDS arrays and five steps; everything else is one text for both.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,7 +29,8 @@ constexpr int kBand = 6;                         // diagonal + half bandwidth 5
 constexpr int kThreads = 256;
 constexpr double kAlpha = 1.6, kRhoAuto = 1e-5, kRhoMin = 1e-9, kRhoMax = 1e3, kRhoStep = 5.0;
 
-struct __attribute__((aligned(16))) GenLds {
+// What every constraint set shares; Lds<Set> adds the set's own arrays behind it.
+struct __attribute__((aligned(16))) GenCore {
     double Lf[kMaxSeg * kTri];        // Cholesky factors of the blocks of H (packed rows)
     double Qm[kMaxSeg * kTri];        // the blocks of Q = P / max|P|
     double Sb[kMaxEq * kBand];        // banded Cholesky factor of S: Sb[r][j] = L[r][r - 5 + j]
@@ -35,10 +38,61 @@ struct __attribute__((aligned(16))) GenLds {
     double z1[3 * kRows], u1[3 * kRows], zv[3 * kRows], uv[3 * kRows], za[3 * kRows], ua[3 * kRows];
     double nu[3 * kMaxEq], bb[3 * kMaxEq];
     double red[kThreads];
-    double T[kMaxSeg], cen[3 * kMaxSeg], rb[kMaxSeg], rfull[kMaxSeg], bv[kMaxSeg], ba[kMaxSeg], fv[kMaxSeg], fa[kMaxSeg];
+    double T[kMaxSeg], bv[kMaxSeg], ba[kMaxSeg], fv[kMaxSeg], fa[kMaxSeg];
     double gam[3 * kMaxSeg];          // gam[3 g + rt]: joint g's factor on the right segment's value / first / second difference
     int n[kMaxSeg];
 };
+
+template <class Set>
+struct __attribute__((aligned(16))) Lds : GenCore {
+    typename Set::Data set;
+};
+
+// The set the control points of a segment are kept in.  A set names its batch (Batch), its LDS arrays (Data) and five steps:
+//   bad(in, g, prm)           lane s of the candidate: is segment g's part of the set unusable?
+//   load(D, in, s0, m, prm)   all lanes: fill D (a barrier follows)
+//   start(D, s, a)            the start iterate of segment s on axis a
+//   project(D, s, eps, v, z)  z = the projection of v onto the set of segment s, shrunk by 2 eps
+//   slack(D, s, p)            how far p is inside the set of segment s (the margin taken off, no 2 eps)
+struct BallSet {
+    using Batch = pct_trajgen_batch;
+    struct Data { double cen[3 * kMaxSeg], rb[kMaxSeg], rfull[kMaxSeg]; };
+
+    __device__ static bool bad(const Batch &in, int64_t g, const pct_trajgen_params &prm)
+    {
+        const double r = in.radius[g];
+        if (!(isfinite(r) && isfinite(in.centres[3 * g]) && isfinite(in.centres[3 * g + 1]) && isfinite(in.centres[3 * g + 2]))) return true;
+        return !(r - prm.margin - 2.0 * prm.eps > 0.0);
+    }
+    __device__ static void load(Data &D, const Batch &in, int64_t s0, int m, const pct_trajgen_params &prm)
+    {
+        const int tid = (int)threadIdx.x;
+        if (tid >= m) return;
+        const int64_t g = s0 + tid;
+        const double r = in.radius[g];
+        D.cen[3 * tid] = in.centres[3 * g]; D.cen[3 * tid + 1] = in.centres[3 * g + 1]; D.cen[3 * tid + 2] = in.centres[3 * g + 2];
+        D.rfull[tid] = r - prm.margin;
+        D.rb[tid] = r - prm.margin - 2.0 * prm.eps;
+    }
+    __device__ static double start(const Data &D, int s, int a) { return D.cen[3 * s + a]; }
+    __device__ static void project(const Data &D, int s, double, const double v[3], double z[3])
+    {
+        double d[3];
+        for (int a = 0; a < 3; a++) d[a] = v[a] - D.cen[3 * s + a];
+        const double dist = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        const bool out = dist > D.rb[s];
+        const double f = out ? D.rb[s] / dist : 1.0;
+        for (int a = 0; a < 3; a++) z[a] = out ? D.cen[3 * s + a] + d[a] * f : v[a];
+    }
+    __device__ static double slack(const Data &D, int s, const double p[3])
+    {
+        const double dx = p[0] - D.cen[3 * s], dy = p[1] - D.cen[3 * s + 1], dz = p[2] - D.cen[3 * s + 2];
+        return D.rfull[s] - sqrt((dx * dx + dy * dy) + dz * dz);
+    }
+};
+
+using GenLds = Lds<BallSet>;
+static_assert(sizeof(GenLds) == 71904, "the sphere form's LDS is what it was");
 
 __device__ inline int tri(int r, int c) { return r * (r + 1) / 2 + c; }       // r >= c
 
@@ -55,7 +109,7 @@ __device__ inline double base_l(int rt, int pos) { return rt == 0 ? (pos == 0 ? 
 __device__ inline double base_r(int rt, int pos) { return rt == 0 ? (pos == 0 ? 1.0 : 0.0) : rt == 1 ? (pos == 0 ? 1.0 : pos == 1 ? -1.0 : 0.0) : (pos == 1 ? -2.0 : 1.0); }
 
 // coefficient of equality row (group g, kind rt) on control point l of segment s
-__device__ inline double ecoef(const GenLds &L, int m, int g, int rt, int s, int l)
+__device__ inline double ecoef(const GenCore &L, int m, int g, int rt, int s, int l)
 {
     if (s == g - 1) {
         const int e = L.n[s] - l;
@@ -68,7 +122,7 @@ __device__ inline double ecoef(const GenLds &L, int m, int g, int rt, int s, int
     return 0.0;
 }
 
-__device__ inline double block_max(GenLds &L, double v)
+__device__ inline double block_max(GenCore &L, double v)
 {
     const int tid = (int)threadIdx.x;
     L.red[tid] = v;
@@ -82,7 +136,7 @@ __device__ inline double block_max(GenLds &L, double v)
     return r;
 }
 
-__device__ inline double block_sum(GenLds &L, double v)
+__device__ inline double block_sum(GenCore &L, double v)
 {
     const int tid = (int)threadIdx.x;
     L.red[tid] = v;
@@ -121,7 +175,7 @@ __device__ inline void block_solve(const double *Lf, double *y, int cnt)
 }
 
 // H = Q + rho (I + Gv^T Gv + Ga^T Ga) block by block, its Cholesky factors, S = E H^-1 E^T and its banded factor
-__device__ void factor(GenLds &L, int m, double rho, bool use_v, bool use_a)
+__device__ void factor(GenCore &L, int m, double rho, bool use_v, bool use_a)
 {
     const int tid = (int)threadIdx.x;
     for (int e = tid; e < m * kTri; e += kThreads) {
@@ -199,11 +253,10 @@ __device__ void factor(GenLds &L, int m, double rho, bool use_v, bool use_a)
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in, pct_trajgen_params prm, double *__restrict__ polycoef,
-                                                           int64_t row_stride, pct_trajgen_result *__restrict__ res)
+template <class Set>
+__device__ inline void generate(Lds<Set> &L, const typename Set::Batch &in, const pct_trajgen_params &prm, double *__restrict__ polycoef,
+                                int64_t row_stride, pct_trajgen_result *__restrict__ res)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    GenLds &L = *reinterpret_cast<GenLds *>(smem);
     const int tid = (int)threadIdx.x;
     const int64_t b = blockIdx.x;
     const int64_t s0 = in.seg_offsets[b], s1 = in.seg_offsets[b + 1];
@@ -217,11 +270,10 @@ __global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in,
     if (!bad) {
         if (tid < (int)mm) {
             const int64_t g = s0 + tid;
-            const double r = in.radius[g], T = in.seg_time[g];
+            const double T = in.seg_time[g];
             const int n = in.orders[g];
-            if (!(isfinite(r) && isfinite(T) && isfinite(in.centres[3 * g]) && isfinite(in.centres[3 * g + 1]) && isfinite(in.centres[3 * g + 2]))) bad = 1;
-            if (!(T > 0.0) || n < kMinOrder || n > kMaxOrder || n - 2 < k || 3 * (int64_t)(n + 1) > row_stride) bad = 1;
-            if (!(r - prm.margin - 2.0 * eps > 0.0)) bad = 1;
+            if (!isfinite(T) || !(T > 0.0) || n < kMinOrder || n > kMaxOrder || n - 2 < k || 3 * (int64_t)(n + 1) > row_stride) bad = 1;
+            if (Set::bad(in, g, prm)) bad = 1;
         }
         if (tid >= 64 && tid < 73 && !isfinite(in.start_state[9 * b + tid - 64])) bad = 1;
         if (tid >= 128 && tid < 137 && !isfinite(in.end_state[9 * b + tid - 128])) bad = 1;
@@ -246,11 +298,8 @@ __global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in,
     if (tid < m) {
         const int64_t g = s0 + tid;
         const int n = in.orders[g];
-        const double T = in.seg_time[g], r = in.radius[g];
+        const double T = in.seg_time[g];
         L.n[tid] = n; L.T[tid] = T;
-        L.cen[3 * tid] = in.centres[3 * g]; L.cen[3 * tid + 1] = in.centres[3 * g + 1]; L.cen[3 * tid + 2] = in.centres[3 * g + 2];
-        L.rfull[tid] = r - prm.margin;
-        L.rb[tid] = r - prm.margin - 2.0 * eps;
         L.fv[tid] = (double)n / T;
         L.fa[tid] = (double)(n * (n - 1)) / (T * T);
         L.bv[tid] = use_v ? prm.max_vel / L.fv[tid] : 0.0;
@@ -263,6 +312,7 @@ __global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in,
             L.gam[3 * tid + 2] = ((double)(n * (n - 1)) / (T * T)) * (Tp * Tp / (double)(np * (np - 1)));
         }
     }
+    Set::load(L.set, in, s0, m, prm);
     __syncthreads();
 
     // ---- P = 2 T^(1-2k) M_k(n), block by block; then Q = P / max|P|
@@ -298,7 +348,7 @@ __global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in,
     const double scale = 1.0 / pmax;
     for (int e = tid; e < m * kTri; e += kThreads) L.Qm[e] *= scale;
 
-    // ---- right-hand sides of the equalities and the start x = centres, z = A x, u = 0
+    // ---- right-hand sides of the equalities and the start x = the set's start iterate, z = A x, u = 0
     const int ne = 3 * (m + 1);
     for (int e = tid; e < 3 * ne; e += kThreads) {
         const int a = e / ne, row = e % ne, g = row / 3, rt = row % 3;
@@ -314,7 +364,7 @@ __global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in,
     }
     for (int e = tid; e < 3 * kRows; e += kThreads) {
         const int a = e / kRows, s = (e % kRows) / kSlot;
-        const double c = s < m ? L.cen[3 * s + a] : 0.0;
+        const double c = s < m ? Set::start(L.set, s, a) : 0.0;
         L.x[e] = c; L.z1[e] = c; L.u1[e] = 0.0;
         L.zv[e] = 0.0; L.uv[e] = 0.0; L.za[e] = 0.0; L.ua[e] = 0.0; L.t[e] = 0.0;
     }
@@ -408,18 +458,15 @@ __global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in,
         if (tid < kRows) {
             const int s = tid / kSlot, l = tid % kSlot;
             if (s < m && l <= L.n[s]) {
-                double v[3], d[3];
+                double v[3], zp[3];
                 for (int a = 0; a < 3; a++) {
                     const int e = a * kRows + tid;
                     v[a] = (kAlpha * L.x[e] + (1.0 - kAlpha) * L.z1[e]) + L.u1[e];
-                    d[a] = v[a] - L.cen[3 * s + a];
                 }
-                const double dist = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-                const bool out = dist > L.rb[s];
-                const double f = out ? L.rb[s] / dist : 1.0;
+                Set::project(L.set, s, eps, v, zp);
                 for (int a = 0; a < 3; a++) {
                     const int e = a * kRows + tid;
-                    const double z = out ? L.cen[3 * s + a] + d[a] * f : v[a];
+                    const double z = zp[a];
                     L.z1[e] = z;
                     L.u1[e] = v[a] - z;
                     const double df = fabs(L.x[e] - z);
@@ -513,8 +560,8 @@ __global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in,
     if (tid < kRows) {
         const int s = tid / kSlot, l = tid % kSlot;
         if (s < m && l <= L.n[s]) {
-            const double dx = L.x[tid] - L.cen[3 * s], dy = L.x[kRows + tid] - L.cen[3 * s + 1], dz = L.x[2 * kRows + tid] - L.cen[3 * s + 2];
-            slack = L.rfull[s] - sqrt((dx * dx + dy * dy) + dz * dz);
+            const double p[3] = {L.x[tid], L.x[kRows + tid], L.x[2 * kRows + tid]};
+            slack = Set::slack(L.set, s, p);
         }
     }
     cost = 0.5 * block_sum(L, cost) / scale;
@@ -537,6 +584,13 @@ __global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in,
         r.cost = cost; r.duration = dur; r.r_prim = r_prim; r.r_dual = r_dual; r.sphere_slack = slack; r.max_vel_ctrl = vmax; r.max_acc_ctrl = amax;
         res[b] = r;
     }
+}
+
+__global__ __launch_bounds__(kThreads) void trajgen_kernel(pct_trajgen_batch in, pct_trajgen_params prm, double *__restrict__ polycoef,
+                                                           int64_t row_stride, pct_trajgen_result *__restrict__ res)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    generate<BallSet>(*reinterpret_cast<GenLds *>(smem), in, prm, polycoef, row_stride, res);
 }
 
 }  // namespace pct_trajgen

@@ -114,9 +114,15 @@ def pack_corridors(corridors):
     return b, a
 
 
-def corridor_fan(centres, radius, seg_time, orders, scales, start, end):
+def corridor_fan(centres, radius=None, seg_time=None, orders=None, scales=None, start=None, end=None):
     """one corridor under a list of time scales: the corridors engine.pack_corridors / engine.bezier_generate take, candidate k with
-    every segment time multiplied by scales[k]"""
+    every segment time multiplied by scales[k].  corridor_fan(corridor, scales) does the same to a corridor given as a dict, of
+    spheres or of polytopes (engine.pack_poly_corridors): copies that differ in seg_time alone."""
+    if isinstance(centres, dict):
+        if scales is None:
+            scales = radius
+        T = np.asarray(centres["seg_time"], np.float64).reshape(-1)
+        return [dict(centres, seg_time=T * float(sc)) for sc in scales]
     T = np.asarray(seg_time, np.float64).reshape(-1)
     return [dict(centres=centres, radius=radius, seg_time=T * float(sc), orders=orders, start=start, end=end) for sc in scales]
 
@@ -165,6 +171,95 @@ def bezier_generate_device(fields, params: TrajGenParams, polycoef, results, str
         stream = torch.cuda.current_stream().cuda_stream
     _chk(lib().pct_bezier_generate_batch_dev(C.byref(batch), C.byref(params), polycoef.data_ptr() or None, int(polycoef.shape[1]),
                                              results.data_ptr() or None, stream or None))
+    return batch
+
+
+class TrajGenPolyBatch(C.Structure):
+    """pct_trajgen_poly_batch: B corridors of polytopes (half-spaces per segment) with their time allocations and end states.  Host
+    pointers for engine.bezier_generate_poly (engine.pack_poly_corridors fills them), device pointers for
+    engine.bezier_generate_poly_device."""
+    _fields_ = [("anchors", C.c_void_p), ("planes", C.c_void_p), ("plane_offsets", C.c_void_p), ("seg_time", C.c_void_p), ("orders", C.c_void_p),
+                ("seg_offsets", C.c_void_p), ("start_state", C.c_void_p), ("end_state", C.c_void_p), ("B", C.c_int64)]
+
+
+POLY_FIELDS = ("anchors", "planes", "plane_offsets", "seg_time", "orders", "seg_offsets", "start_state", "end_state")
+
+
+def trajgen_max_planes() -> int:
+    """pct_trajgen_max_planes: the most planes one segment of a polyhedral corridor may own (24)"""
+    return int(lib().pct_trajgen_max_planes())
+
+
+def pack_poly_corridors(corridors):
+    """A list of dict(anchors [m, 3], planes (m arrays [k_i, 4]: n0 n1 n2 off, n . y <= off), seg_time [m], orders [m], start [9],
+    end [9]) -> (TrajGenPolyBatch, arrays); `arrays` = dict(anchors, planes [total_planes, 4] (one unused row when there is no plane at
+    all), plane_offsets [total_seg + 1], seg_time, orders, seg_offsets, start_state, end_state) are the numpy arrays the struct points into: keep them alive while it is used."""
+    cs = list(corridors)
+    nseg = [len(np.asarray(c["seg_time"]).reshape(-1)) for c in cs]
+    for c, m in zip(cs, nseg):
+        if np.asarray(c["anchors"]).size != 3 * m or len(c["planes"]) != m or np.asarray(c["orders"]).size != m:
+            raise ValueError("a corridor is anchors [m, 3], planes (m arrays [k, 4]), seg_time [m], orders [m]")
+        if np.asarray(c["start"]).size != 9 or np.asarray(c["end"]).size != 9:
+            raise ValueError("start and end are p, v, a: 9 values each")
+    offs = np.zeros(len(cs) + 1, np.int32)
+    offs[1:] = np.cumsum(nseg)
+
+    def cat(key, dt, w):
+        return np.ascontiguousarray(np.concatenate([np.asarray(c[key], dt).reshape(-1, w) for c in cs]) if cs else np.zeros((0, w), dt))
+    per_seg = [np.asarray(p, np.float64).reshape(-1, 4) for c in cs for p in c["planes"]]
+    po = np.zeros(len(per_seg) + 1, np.int32)
+    po[1:] = np.cumsum([len(p) for p in per_seg])
+    planes = np.ascontiguousarray(np.concatenate(per_seg) if per_seg else np.zeros((0, 4)))
+    if len(planes) == 0:
+        planes = np.zeros((1, 4), np.float64)      # never read: the library asks for a pointer that is not null
+    a = dict(anchors=cat("anchors", np.float64, 3), planes=planes, plane_offsets=po, seg_time=cat("seg_time", np.float64, 1).reshape(-1),
+             orders=cat("orders", np.int32, 1).reshape(-1), seg_offsets=offs, start_state=cat("start", np.float64, 9), end_state=cat("end", np.float64, 9))
+    return TrajGenPolyBatch(*[a[k].ctypes.data for k in POLY_FIELDS], len(cs)), a
+
+
+def bezier_generate_poly(corridors, params: TrajGenParams, row_stride=None):
+    """pct_bezier_generate_poly_batch: engine.bezier_generate in polyhedral corridors (a list of dicts as engine.pack_poly_corridors
+    takes, or its packed pair).  Returns (polycoef [total_seg, row_stride], results) as engine.bezier_generate does; sphere_slack of
+    the records is the corridor slack, the least distance of a control point inside a plane moved in by the margin."""
+    packed = isinstance(corridors, tuple) and len(corridors) == 2 and isinstance(corridors[0], TrajGenPolyBatch)
+    batch, keep = corridors if packed else pack_poly_corridors(corridors)
+    if row_stride is None:
+        od = keep["orders"]
+        row_stride = 3 * (int(np.clip(od.max() if len(od) else 5, 5, 12)) + 1)
+    coef = np.zeros((len(keep["seg_time"]), int(row_stride)), np.float64)
+    res = np.zeros(int(batch.B), GEN_RESULT_DTYPE)
+    _chk(lib().pct_bezier_generate_poly_batch(C.byref(batch), C.byref(params), _ptr(coef), int(row_stride), _ptr(res)))
+    del keep
+    return coef, res
+
+
+def bezier_generate_poly_device(fields, params: TrajGenParams, polycoef, results, stream=None):
+    """pct_bezier_generate_poly_batch_dev on torch tensors, asynchronous on the current stream (or `stream`, a raw hipStream_t
+    handle), no host synchronisation, capturable.  fields: dict of device tensors anchors [total, 3] f64, planes [total_planes, 4] f64
+    (at least one row, read or not), plane_offsets [total + 1] i32, seg_time [total] f64, orders [total] i32, seg_offsets [B + 1] i32,
+    start_state, end_state [B, 9] f64; polycoef and results as engine.bezier_generate_device takes them."""
+    import torch
+    want = dict(anchors=torch.float64, planes=torch.float64, plane_offsets=torch.int32, seg_time=torch.float64, orders=torch.int32,
+                seg_offsets=torch.int32, start_state=torch.float64, end_state=torch.float64)
+    for k, dt in want.items():
+        t = fields[k]
+        if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{k} must be a contiguous device tensor of {dt}")
+    B = int(fields["seg_offsets"].numel()) - 1
+    total = int(fields["seg_time"].numel())
+    if polycoef.dtype != torch.float64 or polycoef.dim() != 2 or polycoef.shape[0] != total or not polycoef.is_contiguous() or not polycoef.is_cuda:
+        raise ValueError("polycoef must be a contiguous float64 device tensor [total_seg, row_stride]")
+    if results.dtype != torch.uint8 or results.numel() != 64 * B or not results.is_contiguous() or not results.is_cuda:
+        raise ValueError("results must be a contiguous uint8 device tensor of B x 64 bytes")
+    if fields["start_state"].numel() != 9 * B or fields["end_state"].numel() != 9 * B or fields["anchors"].numel() != 3 * total:
+        raise ValueError("start_state / end_state are [B, 9], anchors is [total_seg, 3]")
+    if fields["plane_offsets"].numel() != total + 1 or fields["planes"].numel() % 4 != 0:
+        raise ValueError("plane_offsets is [total_seg + 1], planes is [total_planes, 4]")
+    batch = TrajGenPolyBatch(*[fields[k].data_ptr() or None for k in POLY_FIELDS], B)
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    _chk(lib().pct_bezier_generate_poly_batch_dev(C.byref(batch), C.byref(params), polycoef.data_ptr() or None, int(polycoef.shape[1]),
+                                                  results.data_ptr() or None, stream or None))
     return batch
 
 
@@ -370,6 +465,10 @@ def lib():
         L.pct_bezier_generate_batch.argtypes = [C.POINTER(TrajGenBatch), C.POINTER(TrajGenParams), f64p, i64, vp]
         L.pct_bezier_generate_batch_dev.argtypes = [C.POINTER(TrajGenBatch), C.POINTER(TrajGenParams), vp, i64, vp, vp]
         L.pct_time_allocation.argtypes = [f64p, f64p, i64, f64p, f64p, f64p, C.c_double, C.c_double, f64p]
+        L.pct_bezier_generate_poly_batch.argtypes = [C.POINTER(TrajGenPolyBatch), C.POINTER(TrajGenParams), f64p, i64, vp]
+        L.pct_bezier_generate_poly_batch_dev.argtypes = [C.POINTER(TrajGenPolyBatch), C.POINTER(TrajGenParams), vp, i64, vp, vp]
+        L.pct_trajgen_max_planes.argtypes = []
+        L.pct_trajgen_max_planes.restype = C.c_int
         L.pct_radius_count_batch_dev.argtypes = [vp, i32, vp, vp, i64, vp, vp]
         L.pct_cloud_reserve_queries.argtypes = [vp, i64]
         L.pct_plan_create_nn.argtypes = [vp, i32, i64, C.POINTER(vp)]
