@@ -22,6 +22,7 @@
  *                           checkSafeTrajectory would write around its candidates; variants as in Planner/src/traj_postprocessing.cpp)
  *   pct_bezier_certify_batch  the same question answered for every point of the curves, not for samples of them (no reference
  *                           counterpart: checkSafeTrajectory only samples)
+ *   pct_bezier_clearance_batch  how close each whole curve comes to the cloud, as a bracket (no reference counterpart)
  *   pct_cloud_ring_index +  the per-frame rebuild of the search tree: rcvPointCloudCallBack -> setInput
  *   pct_cloud_append_aos    Planner/src/sim_planning_demo.cpp:159-167 -> Planner/src/corridor_finder.cpp:93-99 (rolling map, config C5)
  *   pct_ctrl_points_check   the containment the optimizer enforces on the control points, Planner/src/traj_optimizer.cpp:624-648,
@@ -475,6 +476,49 @@
  * that has an order outside 0..12 or a row too short for it is INVALID and none of its rows is read; when seg_offsets[B] exceeds
  * piece_cap nothing is examined, every sound trajectory is UNDECIDED and the capped flag is set.
  *
+ * Trajectory clearance (pct_bezier_clearance_batch*): how close each curve comes to the cloud, as a bracket lo <= clearance <= hi,
+ * by the subdivision of the certified check and the nearest-neighbour answers at the ends of its pieces -- no capsule search, so it
+ * runs on every index that answers a nearest-neighbour batch.  Input: a pct_bezier_batch exactly as "Certified Bezier check" reads
+ * it -- the world control points of its step (1), the same INVALID rule, t_start NOT read -- with tol (finite, >= 0, metres), cap
+ * (> 0 or +inf: clearance beyond it is of no interest, the role max_radius plays for inflation), max_depth (0..20), piece_cap
+ * (1..2^24, in the host form not below the number of segments) and algo.  All arithmetic is fp64, one rounding per operation, no
+ * contraction, in the order given here.  Pieces, halving and the order of the piece buffer (trajectory, segment, k) are those of
+ * steps (2) and (3) there; all live pieces of a round have the round's depth.  Geometry of a piece: a, b, rho and cmax exactly as in
+ * step (4) there, and ell = sqrt((e0*e0 + e1*e1) + e2*e2) with e = b - a.  Queries: the nearest-neighbour d2 of the fp32 points a
+ * and b give da = sqrt(d2_a), db = sqrt(d2_b).  The bound of a piece:
+ *   L = max(0, (((da + db) - ell) * 0.5 - rho) - (((da + db) + ell + rho) * 2^-20 + cmax * 2^-40)),
+ * sums left to right, max(0, t) being t where t > 0 and +0 elsewhere; L = +inf when either d2 is +inf.  A round r: (i) every live
+ * piece counts into pieces and depth of its trajectory; (ii) both end d2 are folded into the trajectory's U2, the minimum over every
+ * end examined so far, this round included, and the end that attains it is kept: smaller d2 wins, on equal d2 the earlier round,
+ * within a round the lowest (segment, u), i.e. the lowest 2 * slot + end; (iii) after the fold is complete a piece RETIRES iff
+ * L >= min(sqrt(U2), cap) - tol, and a retired piece folds its L into the trajectory's lo (a minimum).  Three other kinds of piece
+ * also fold their L into lo and make the trajectory OPEN: one that does not retire at d == max_depth; one with ell == 0 and
+ * rho == 0 (a single point as the searches see it: halving cannot improve it, so it never splits); and every would-be splitter of a
+ * round in which twice their number exceeds piece_cap, which sets the call's capped flag as in the certified check; (iv) every other
+ * piece splits.  Output per trajectory: struct pct_traj_clearance (48 bytes, below): hi = sqrt(U2); lo = min(folded L, hi); at_seg,
+ * at_u (k/2^d for a, (k+1)/2^d for b) and at_idx (index_base applied) name the end that attains hi; with no end at finite distance
+ * hi = lo = +inf, at_seg = -1, at_idx = PCT_NO_INDEX, at_u = NaN; INVALID: lo = hi = NaN with the same "nowhere" fields and
+ * depth = pieces = 0.  Output per call: optional stats[3] = {rounds that examined a piece, pieces examined, capped flag}.  What the
+ * record guarantees in every status but INVALID: no point of the curve is nearer than lo to any row of the window.  The argument
+ * (it stands, with its roundings, beside the kernels in csrc/bezier_clearance.hpp): a point x of the piece is within rho of a chord
+ * point a + s*e, so |x - a| <= rho + s*ell and |x - b| <= rho + (1 - s)*ell; the distance to the cloud is 1-Lipschitz, hence
+ * d(x) >= max(da - s*ell, db - (1 - s)*ell) - rho >= (da + db - ell)/2 - rho; the two slack terms cover the roundings local to the
+ * piece unconditionally and the inherited roundings of the halvings -- at most 2^-45 of the largest |world control coordinate| M0 of
+ * the segment -- whenever da + db + ell + rho >= 2^-24 * M0 (60 micrometres per kilometre of coordinate) or the piece's own
+ * cmax >= M0 / 16; below that no claim is made.  hi is the distance the sampled check would measure at that piece end: a point of
+ * the curve rounded to fp32, not the clearance of the exact curve.  DONE adds lo >= min(hi, cap) - tol: hi only falls, so a piece
+ * retired against an earlier, larger hi still satisfies it.  A tol below the slack, about 2 * d * 1e-6 at distance d, cannot be met
+ * and ends OPEN.  Paths: algo is resolved for the nearest-neighbour batch on the cloud's index (PCT_ALGO_AUTO, _STREAM, _GRID,
+ * _RING) and the refusals are the certified check's; all forms give the same bytes, and a trajectory's bytes do not depend on the
+ * rest of the batch.  Empty cloud: every valid trajectory is DONE at depth 0 with lo = hi = +inf.  B == 0: PCT_OK (stats, when
+ * given, are zeros).  PCT_ERR_INVALID with nothing written: the certified check's list with tol and cap in margin's place (tol not
+ * finite or < 0, cap not > 0).  Rolling map: the host form finishes an append in flight first.  Host form: it reads the live count
+ * once per round, sizes its launches and piece rooms by it and stops at zero.  Device form: max_depth + 1 rounds over piece_cap
+ * slots with device-side counts, no host wait, capturable under the certified check's conditions; reserve 2 * piece_cap queries
+ * first; the piece buffers are the certified check's (the two calls must not run concurrently on one cloud), the piece scalars
+ * (32 B per piece) and the per-trajectory state are cloud-owned and grown by the call; what it cannot see is treated as there
+ * (an unsound trajectory is INVALID; seg_offsets[B] above piece_cap: nothing examined, every sound trajectory OPEN, capped set).
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -879,6 +923,28 @@ typedef struct pct_traj_certificate {   /* 48 bytes */
 int pct_bezier_certify_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double margin, int32_t max_depth, int64_t piece_cap,
                              pct_traj_certificate *cert /* B */, int64_t stats[3] /* {rounds, pieces, capped}; may be NULL */);
 
+/* Trajectory clearance (contract: top of this file, "Trajectory clearance"): each of B trajectories gets a bracket lo <= clearance <= hi
+ * of its distance to the cloud.  Host pointers in the host form, device pointers (the struct itself on the host) in the device form. */
+enum pct_clearance_status {
+    PCT_CLR_DONE = 0,         /* lo >= min(hi, cap) - tol */
+    PCT_CLR_OPEN = 1,         /* a piece not retired at max_depth, a piece that is a single point, or splits refused by piece_cap: lo still holds */
+    PCT_CLR_INVALID = 2       /* as PCT_CERT_INVALID; lo = hi = NaN */
+};
+
+typedef struct pct_traj_clearance {   /* 48 bytes */
+    int32_t  status;      /* enum pct_clearance_status */
+    int32_t  depth;       /* deepest level examined */
+    int32_t  at_seg;      /* segment of the piece end that attains hi (an index into the packed batch), -1 = none */
+    uint32_t at_idx;      /* nearest row of that end (index_base applied), PCT_NO_INDEX = none */
+    double   at_u;        /* parameter u of that end inside at_seg, NaN = none */
+    double   lo;          /* no point of the curve is nearer than lo to any row of the window */
+    double   hi;          /* distance from that end -- a curve point rounded to fp32 -- to its nearest row; +inf = no end at finite distance */
+    int64_t  pieces;      /* pieces examined */
+} pct_traj_clearance;
+
+int pct_bezier_clearance_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double tol, double cap, int32_t max_depth, int64_t piece_cap,
+                               pct_traj_clearance *out /* B */, int64_t stats[3] /* {rounds, pieces, capped}; may be NULL */);
+
 /* Control-point check (SURVEY.md 3.3, config C5's build extension): the threshold test of checkTrajPtCol
  * (Planner/src/corridor_finder.cpp:412-416) applied to the raw control points of the committed trajectory in world units --
  * control point j of segment i is polycoef[i][d*(n+1)+j] * seg_time[i] (layout Planner/src/traj_optimizer.cpp:739-751), the
@@ -932,6 +998,11 @@ int pct_bezier_check_batch_dev(pct_cloud *c, const pct_bezier_batch *d_batch_fie
 int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields /* struct on the host, its pointers on the device */,
                                  double margin, int32_t max_depth, int64_t piece_cap, pct_traj_certificate *d_cert, int64_t *d_stats,
                                  void *stream);
+/* pct_bezier_clearance_batch on device buffers: d_out[B] required, d_stats[3] may be NULL.  Reserve 2 * piece_cap queries first
+ * (pct_cloud_reserve_queries).  Asynchronous on `stream`, no host wait; can be captured once the piece buffers have their size. */
+int pct_bezier_clearance_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields /* struct on the host, its pointers on the device */,
+                                   double tol, double cap, int32_t max_depth, int64_t piece_cap, pct_traj_clearance *d_out, int64_t *d_stats,
+                                   void *stream);
 /* Exchange step of a sharded cloud (one process per GPU): between all_reduce(min) on the squared distances and all_reduce(min) on
  * the indices, a rank offers its global index only where its own d2 equals the reduced minimum (and is finite), INT32_MAX
  * elsewhere -- so the second reduction returns the lowest global index among the ranks that tie.  Device pointers, async on

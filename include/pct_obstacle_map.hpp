@@ -18,6 +18,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -598,6 +599,40 @@ public:
         const int64_t not_free = certifyTrajectories(one, cert, max_depth);
         if (certificate) *certificate = cert[0];
         return not_free != 0;
+    }
+
+    // The clearance (pct_engine.h, paragraph "Trajectory clearance"): how close each whole candidate comes to the map, as a bracket
+    // clearances[b].lo <= clearance <= clearances[b].hi no wider than tol metres (status PCT_CLR_DONE) -- the number to rank candidates
+    // by once all of them pass.  cap: clearance beyond it is of no interest (a piece that far away retires at once).  PCT_CLR_OPEN:
+    // max_depth halvings or piece_cap did not close the bracket; lo still holds.  at_seg / at_u / at_idx say where hi is attained and
+    // against which point.  candidates.t_start is not read.  piece_cap 0: 64 pieces per segment, at least 4096.  stats (optional):
+    // {rounds, pieces examined, capped}.  Returns the number of candidates whose bracket is NOT closed (status != PCT_CLR_DONE).
+    int64_t trajectoryClearances(const pct_bezier_batch &candidates, std::vector<pct_traj_clearance> &clearances, double tol,
+                                 double cap = std::numeric_limits<double>::infinity(), int max_depth = 16, int64_t piece_cap = 0,
+                                 int64_t *stats = nullptr)
+    {
+        const int64_t B = candidates.B > 0 ? candidates.B : 0;
+        clearances.resize((size_t)B);
+        if (piece_cap <= 0) {
+            const int64_t nseg = B > 0 && candidates.seg_offsets ? candidates.seg_offsets[B] : 0;
+            piece_cap = 64 * nseg > 4096 ? 64 * nseg : 4096;
+        }
+        check(pct_bezier_clearance_batch(cloud_, PCT_ALGO_AUTO, &candidates, tol, cap, max_depth, piece_cap, clearances.data(), stats),
+              "pct_bezier_clearance_batch");
+        int64_t not_done = 0;
+        for (const pct_traj_clearance &v : clearances) not_done += v.status != PCT_CLR_DONE ? 1 : 0;
+        return not_done;
+    }
+    // One trajectory, the arguments of certifySafeTrajectory: its record
+    pct_traj_clearance trajectoryClearance(const double *poly_coeff, int64_t row_stride, const double *seg_time, const int32_t *orders,
+                                           int32_t segment_num, double tol, double cap = std::numeric_limits<double>::infinity(),
+                                           int max_depth = 16)
+    {
+        const int32_t seg_offsets[2] = { 0, segment_num };
+        const pct_bezier_batch one{ poly_coeff, row_stride, seg_time, orders, seg_offsets, nullptr, 1 };
+        std::vector<pct_traj_clearance> rec;
+        trajectoryClearances(one, rec, tol, cap, max_depth);
+        return rec[0];
     }
 
     // Corridor -> trajectory -> proof in one call: generate one candidate per time scale (generateTrajectories above; limits carries

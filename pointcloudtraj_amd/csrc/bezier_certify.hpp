@@ -112,12 +112,9 @@ __device__ __forceinline__ long long bc_total_seg(const BcDesc &D, long long pie
     return t < 0 || t > piece_cap ? 0 : t;
 }
 
-// lane b < B: certificate defaults and state; lane B: the control words
-__global__ __launch_bounds__(256) void bc_init_kernel(BcDesc D, long long piece_cap, pct_traj_certificate *__restrict__ cert,
-                                                      BcTraj *__restrict__ traj, BcCtl *__restrict__ ctl)
+// lane b <= B of an init kernel: the state of trajectory b, or (b == B) the control words; false for lane B
+__device__ __forceinline__ bool bc_init_state(const BcDesc &D, long long piece_cap, long long b, BcTraj *__restrict__ traj, BcCtl *__restrict__ ctl)
 {
-    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b > D.B) return;
     const bool over = (long long)D.seg_offsets[D.B] > piece_cap;      // device form only: more segments than pieces
     if (b == D.B) {
         ctl->live = (uint32_t)bc_total_seg(D, piece_cap);
@@ -127,12 +124,22 @@ __global__ __launch_bounds__(256) void bc_init_kernel(BcDesc D, long long piece_
         ctl->examined = 0;
         ctl->pad = 0;
         ctl->pieces = 0;
-        return;
+        return false;
     }
     int s0, s1;      // an unsound range (the host form has refused it): INVALID, and none of its rows is read
     const bool sound = bezier_range_sound(D.seg_offsets, D.orders, D.row_stride, D.B, b, s0, s1);
     traj[b].hitkey = kBcNoHit;
     traj[b].flags = !sound ? kBcInvalid : over ? kBcUndecided : 0u;
+    return true;
+}
+
+// lane b < B: certificate defaults and state; lane B: the control words
+__global__ __launch_bounds__(256) void bc_init_kernel(BcDesc D, long long piece_cap, pct_traj_certificate *__restrict__ cert,
+                                                      BcTraj *__restrict__ traj, BcCtl *__restrict__ ctl)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b > D.B) return;
+    if (!bc_init_state(D, piece_cap, b, traj, ctl)) return;
     cert[b].status = PCT_CERT_FREE;
     cert[b].depth = 0;
     cert[b].hit_seg = -1;
@@ -175,6 +182,30 @@ __global__ __launch_bounds__(256) void bc_seed_kernel(BcDesc D, long long piece_
     meta[i] = BcMeta{ (int32_t)b, (int32_t)i, n, 0u };
 }
 
+// Step (4) of the contract for the polygon p of order n: the chord ends narrowed to fp32 into q[0..5] (a, then b) and widened into
+// ends[0..5], rho = the largest distance of a control point from segment (a, b), cmax = the largest |coordinate|.  The certified
+// check and the clearance (bezier_clearance.hpp) both take their geometry from here.
+__device__ __forceinline__ void bc_chord(const double *__restrict__ p, int n, float *__restrict__ q, double (&ends)[6], double &rho, double &cmax)
+{
+    for (int k = 0; k < 3; k++) {
+        const float a = (float)p[k], b = (float)p[3 * n + k];
+        q[k] = a; q[3 + k] = b;
+        ends[k] = (double)a; ends[3 + k] = (double)b;
+    }
+    SegGeom S;
+    double bx, by, bz;
+    seg_load(ends, 0, S, bx, by, bz);
+    double rho2 = 0.0;
+    cmax = 0.0;
+    for (int j = 0; j <= n; j++) {
+        double d2, s;
+        seg_point_d2(S, p[3 * j], p[3 * j + 1], p[3 * j + 2], d2, s);
+        if (d2 > rho2) rho2 = d2;
+        for (int k = 0; k < 3; k++) cmax = fmax(cmax, fabs(p[3 * j + k]));
+    }
+    rho = sqrt(rho2);
+}
+
 // lane slot < nslots: the queries of a live piece; NaN queries for any other slot
 __global__ __launch_bounds__(256) void bc_geometry_kernel(const double *__restrict__ poly, const BcMeta *__restrict__ meta, const BcCtl *__restrict__ ctl,
                                                           uint32_t nslots, double margin, double *__restrict__ seg, double *__restrict__ reach,
@@ -191,23 +222,8 @@ __global__ __launch_bounds__(256) void bc_geometry_kernel(const double *__restri
     }
     const int n = meta[slot].order;
     const double *p = poly + (size_t)slot * kBcPoly;
-    double ends[6];
-    for (int k = 0; k < 3; k++) {
-        const float a = (float)p[k], b = (float)p[3 * n + k];
-        qq[k] = a; qq[3 + k] = b;
-        ends[k] = (double)a; ends[3 + k] = (double)b;
-    }
-    SegGeom S;
-    double bx, by, bz;
-    seg_load(ends, 0, S, bx, by, bz);
-    double rho2 = 0.0, cmax = 0.0;
-    for (int j = 0; j <= n; j++) {
-        double d2, s;
-        seg_point_d2(S, p[3 * j], p[3 * j + 1], p[3 * j + 2], d2, s);
-        if (d2 > rho2) rho2 = d2;
-        for (int k = 0; k < 3; k++) cmax = fmax(cmax, fabs(p[3 * j + k]));
-    }
-    const double rho = sqrt(rho2);
+    double ends[6], rho, cmax;
+    bc_chord(p, n, qq, ends, rho, cmax);
     for (int k = 0; k < 6; k++) sg[k] = ends[k];
     reach[slot] = ((margin + rho) * (1.0 + 0x1p-20)) + cmax * 0x1p-40;
 }

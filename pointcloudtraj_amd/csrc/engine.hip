@@ -45,6 +45,7 @@
 #include "segment_search.hpp"
 #include "segment_polyhedron.hpp"
 #include "bezier_certify.hpp"
+#include "bezier_clearance.hpp"
 
 using namespace pct;
 using pct_host::dropped;
@@ -323,6 +324,12 @@ struct pct_cloud {
     DevBuf<BcCtl> bc_ctl;
     DevBuf<pct_traj_certificate> bc_cert;
     DevBuf<long long> bc_stats;
+    // trajectory clearance (bezier_clearance.hpp): it shares the piece sets, flags, tile sums, state and control words above (the two
+    // calls never run concurrently on one cloud) and adds the piece scalars (32 B per piece), its own per-trajectory minima and the
+    // host form's records
+    DevBuf<double> cl_geom;
+    DevBuf<ClTraj> cl_traj;
+    DevBuf<pct_traj_clearance> cl_out;
     // measurement
     hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the whole batch (all kernels of one query call)
     hipEvent_t ev2 = nullptr, ev3 = nullptr;    // around the batch's dominant kernel only (aliases of the ring's current pair)
@@ -2133,6 +2140,15 @@ int bc_seed(pct_cloud *c, const BcRun &R, int64_t seg_lanes, hipStream_t s)
     return PCT_OK;
 }
 
+// the nearest-neighbour path of the index that `path` (resolve_algo, Op::Capsule) names: the end test of the certified check and
+// both queries of the clearance
+int bc_nn_path(pct_cloud *c, Path path, int64_t Q, Path *nn)
+{
+    *nn = Path::Empty;
+    if (path == Path::Empty) return PCT_OK;
+    return resolve_algo(c, Op::NN, path == Path::Table ? PCT_ALGO_RING : path == Path::Grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM, Q, nn);
+}
+
 // One round over the first nslots slots of set (round & 1): the queries into the cloud's workspaces (segments in d_seg, reaches in
 // d_r2, the 2 * nslots ends in d_q; 2 * nslots <= c->qcap), the capsule count and the nearest-neighbour batch on the index of R.path,
 // then classification, compaction and the halving into the other set.
@@ -2143,9 +2159,8 @@ int bc_round(pct_cloud *c, const BcRun &R, int round, int64_t nslots, hipStream_
     bc_geometry_kernel<<<ceil_div(nslots, 256), 256, 0, s>>>(c->bc_poly[cur], c->bc_meta[cur], c->bc_ctl, n, R.margin, c->d_seg, c->d_r2, c->d_q);
     HIPCHK(hipGetLastError());
     PCTCHK(ss_count_run(c, R.path, c->d_seg, c->d_r2, nslots, c->d_count, s, no_step));
-    Path nn = Path::Empty;
-    if (R.path != Path::Empty)
-        PCTCHK(resolve_algo(c, Op::NN, R.path == Path::Table ? PCT_ALGO_RING : R.path == Path::Grid ? PCT_ALGO_GRID : PCT_ALGO_STREAM, 2 * nslots, &nn));
+    Path nn;
+    PCTCHK(bc_nn_path(c, R.path, 2 * nslots, &nn));
     PCTCHK(nn_run(c, nn, c->d_q, 2 * nslots, c->d_idx, c->d_d2, s));
     bc_classify_kernel<<<ceil_div(nslots, 256), 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, R.margin, round, c->d_count, c->d_d2, R.cert, c->bc_traj, c->bc_flag);
     const int ntiles = ceil_div(nslots, kBcTile);
@@ -2168,6 +2183,80 @@ int bc_finish(pct_cloud *c, const BcRun &R, hipStream_t s)
 bool bc_bad_scalars(double margin, int32_t max_depth, int64_t piece_cap)
 {
     return !(margin >= 0.0) || !std::isfinite(margin) || max_depth < 0 || max_depth > kBcMaxDepth || piece_cap < 1 || piece_cap > kBcMaxPieces;
+}
+
+// ---- the trajectory clearance (bezier_clearance.hpp; contract: pct_engine.h, "Trajectory clearance"): its rooms and its rounds -----
+struct ClRun {
+    BcDesc D;
+    double tol, cap;
+    int max_depth;
+    int64_t piece_cap;
+    Path path;                       // resolve_algo(Op::Capsule): the certified check's rules and refusals
+    pct_traj_clearance *out;         // device memory, B entries
+    long long *stats;                // device memory, 3 entries, or NULL
+};
+
+// room for a round over nslots slots: the certified check's, and the piece scalars
+int cl_round_room(pct_cloud *c, int64_t nslots, hipStream_t s)
+{
+    PCTCHK(bc_round_room(c, nslots, s));
+    return bc_reserve(c, c->cl_geom, (size_t)nslots * kClGeom, s);
+}
+
+int cl_traj_room(pct_cloud *c, int64_t B, hipStream_t s)
+{
+    PCTCHK(bc_traj_room(c, B, s));
+    return bc_reserve(c, c->cl_traj, (size_t)B, s);
+}
+
+int cl_seed(pct_cloud *c, const ClRun &R, int64_t seg_lanes, hipStream_t s)
+{
+    cl_init_kernel<<<ceil_div(R.D.B + 1, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, R.out, c->bc_traj, c->bc_ctl, c->cl_traj);
+    if (seg_lanes > 0) {
+        bc_valid_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, c->bc_traj);
+        bc_seed_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, c->bc_traj, c->bc_poly[0], c->bc_meta[0]);
+    }
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// One round over the first nslots slots of set (round & 1): the 2 * nslots end queries into d_q (2 * nslots <= c->qcap), the
+// nearest-neighbour batch on the index of R.path, then fold, mark, compaction and the halving into the other set.
+int cl_round(pct_cloud *c, const ClRun &R, int round, int64_t nslots, hipStream_t s)
+{
+    const int cur = round & 1;
+    const uint32_t n = (uint32_t)nslots;
+    const int lanes = ceil_div(nslots, 256);
+    cl_geometry_kernel<<<lanes, 256, 0, s>>>(c->bc_poly[cur], c->bc_meta[cur], c->bc_ctl, n, c->cl_geom, c->d_q);
+    HIPCHK(hipGetLastError());
+    Path nn;
+    PCTCHK(bc_nn_path(c, R.path, 2 * nslots, &nn));
+    PCTCHK(nn_run(c, nn, c->d_q, 2 * nslots, c->d_idx, c->d_d2, s));
+    cl_fold_kernel<<<lanes, 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, round, c->d_d2, R.out, c->cl_traj);
+    cl_attain_kernel<<<lanes, 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, c->d_d2, c->cl_traj, c->bc_traj);
+    const int ntiles = ceil_div(nslots, kBcTile);
+    cl_mark_kernel<<<ntiles, kBcTile, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, round, R.max_depth, R.tol, R.cap, c->d_idx, c->d_d2, c->cl_geom, R.out, c->bc_traj,
+                                              c->cl_traj, c->bc_flag, c->bc_tile);
+    scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->bc_tile, (uint32_t)ntiles, BcScanDone{ c->bc_ctl, (uint32_t)R.piece_cap });
+    if (round < R.max_depth) {
+        cl_capped_kernel<<<lanes, 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, c->bc_flag, c->cl_geom, c->bc_traj, c->cl_traj);
+        bc_split_kernel<<<ceil_div(2 * nslots, 256), 256, 0, s>>>(c->bc_poly[cur], c->bc_meta[cur], c->bc_poly[cur ^ 1], c->bc_meta[cur ^ 1], c->bc_flag, c->bc_tile,
+                                                                 c->bc_ctl, n, c->bc_traj);
+    }
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+int cl_finish(pct_cloud *c, const ClRun &R, hipStream_t s)
+{
+    cl_finish_kernel<<<ceil_div(std::max<int64_t>(R.D.B, 1), 256), 256, 0, s>>>(R.D.B, c->bc_traj, c->bc_ctl, c->cl_traj, R.out, R.stats);
+    HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+bool cl_bad_scalars(double tol, double cap, int32_t max_depth, int64_t piece_cap)
+{
+    return !(tol >= 0.0) || !std::isfinite(tol) || !(cap > 0.0) || max_depth < 0 || max_depth > kBcMaxDepth || piece_cap < 1 || piece_cap > kBcMaxPieces;
 }
 
 }  // namespace
@@ -3336,6 +3425,97 @@ int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch 
     // the live count stays on the device: every round is sized by piece_cap and every lane guards on it
     for (int round = 0; round <= R.max_depth; round++) PCTCHK(bc_round(c, R, round, piece_cap, s));
     return bc_finish(c, R, s);
+}
+
+// ---- the trajectory clearance (bezier_clearance.hpp; contract: pct_engine.h, "Trajectory clearance") -------------------------------
+int pct_bezier_clearance_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double tol, double cap, int32_t max_depth, int64_t piece_cap,
+                               pct_traj_clearance *out, int64_t stats[3])
+{
+    if (!c || !batch || batch->B < 0 || batch->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad bezier_clearance_batch arguments");
+    if (cl_bad_scalars(tol, cap, max_depth, piece_cap))
+        return fail(PCT_ERR_INVALID, "bezier_clearance_batch: tol %g, cap %g, max_depth %d or piece_cap %lld out of range", tol, cap, (int)max_depth,
+                    (long long)piece_cap);
+    const int64_t B = batch->B;
+    if (B > 0 && (!batch->polycoef || !batch->seg_time || !batch->orders || !batch->seg_offsets || !out))
+        return fail(PCT_ERR_INVALID, "bad bezier_clearance_batch arguments: a null array");
+    PCTCHK(bezier_check_batch_layout(batch, "bezier_clearance_batch"));
+    const int64_t total_seg = B > 0 ? batch->seg_offsets[B] : 0;
+    if (piece_cap < total_seg)
+        return fail(PCT_ERR_INVALID, "bezier_clearance_batch: piece_cap %lld is below the %lld segments", (long long)piece_cap, (long long)total_seg);
+    PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, total_seg, &path));
+    if (B == 0) {
+        if (stats) stats[0] = stats[1] = stats[2] = 0;
+        return PCT_OK;
+    }
+    hipStream_t s = g_stream;
+    const pct_bezier_traj all{ batch->polycoef, batch->row_stride, batch->seg_time, batch->orders, (int32_t)total_seg };
+    PCTCHK(bezier_stage_coef(c, &all, s, false));
+    PCTCHK(bc_reserve(c, c->bb_segoff, (size_t)B + 1, s));
+    PCTCHK(bc_reserve(c, c->cl_out, (size_t)B, s));
+    PCTCHK(bc_reserve(c, c->bc_stats, 3, s));
+    PCTCHK(cl_traj_room(c, B, s));
+    HIPCHK(hipMemcpyAsync(c->bb_segoff, batch->seg_offsets, sizeof(int32_t) * (B + 1), hipMemcpyHostToDevice, s));
+    const ClRun R{ BcDesc{ c->d_coef, (long long)batch->row_stride, c->d_segtime, c->d_orders, c->bb_segoff, (long long)B }, tol, cap, (int)max_depth, piece_cap, path,
+                   c->cl_out, c->bc_stats };
+    return ask_twice_after_overrun(c, [&]() -> int {
+        PCTCHK(bc_room(c, 0, total_seg, s));
+        PCTCHK(cl_seed(c, R, total_seg, s));
+        int64_t live = total_seg;
+        for (int round = 0; round <= R.max_depth && live > 0; round++) {
+            // the children of this round's pieces number at most 2 * live and at most piece_cap
+            PCTCHK(bc_room(c, (round & 1) ^ 1, std::min<int64_t>(2 * live, piece_cap), s));
+            PCTCHK(cl_round_room(c, live, s));
+            PCTCHK(pct_cloud_reserve_queries(c, 2 * live));
+            PCTCHK(cl_round(c, R, round, live, s));
+            BcCtl h{};
+            HIPCHK(hipMemcpyAsync(&h, c->bc_ctl, sizeof(BcCtl), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));     // the round's one host read: the live count sizes the next round
+            live = h.live;
+        }
+        PCTCHK(cl_finish(c, R, s));
+        HIPCHK(hipMemcpyAsync(out, c->cl_out, sizeof(pct_traj_clearance) * B, hipMemcpyDeviceToHost, s));
+        if (stats) HIPCHK(hipMemcpyAsync(stats, c->bc_stats, sizeof(int64_t) * 3, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return PCT_OK;
+    });
+}
+
+int pct_bezier_clearance_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, double tol, double cap, int32_t max_depth,
+                                   int64_t piece_cap, pct_traj_clearance *d_out, int64_t *d_stats, void *stream)
+{
+    const pct_bezier_batch *bt = d_batch_fields;
+    if (!c || !bt || bt->B < 0 || bt->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad bezier_clearance_batch_dev arguments");
+    if (cl_bad_scalars(tol, cap, max_depth, piece_cap))
+        return fail(PCT_ERR_INVALID, "bezier_clearance_batch_dev: tol %g, cap %g, max_depth %d or piece_cap %lld out of range", tol, cap, (int)max_depth,
+                    (long long)piece_cap);
+    if (bt->B > 0 && (!bt->polycoef || !bt->seg_time || !bt->orders || !bt->seg_offsets || !d_out))
+        return fail(PCT_ERR_INVALID, "bad bezier_clearance_batch_dev arguments: a null array");
+    Path path;
+    PCTCHK(resolve_algo(c, Op::Capsule, algo, piece_cap, &path));
+    hipStream_t s = (hipStream_t)stream;
+    if (bt->B == 0) {
+        if (d_stats) HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * 3, s));
+        return PCT_OK;
+    }
+    // under capture only the two index paths are served, as for the certified check: the streaming nearest-neighbour kernels keep
+    // partial results in scratch that is sized and cleared outside the graph
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    if ((path == Path::Stream || path == Path::Empty) && (c->capturing || (hipStreamIsCapturing(s, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone)))
+        return fail(PCT_ERR_INVALID, "bezier_clearance_batch_dev: during graph capture the cloud needs its cell index or its rolling-map index");
+    PCTCHK(require_reserved(c, 2 * piece_cap, "2 * piece_cap"));
+    PCTCHK(bc_room(c, 0, piece_cap, s));
+    PCTCHK(bc_room(c, 1, piece_cap, s));
+    PCTCHK(cl_round_room(c, piece_cap, s));
+    PCTCHK(cl_traj_room(c, bt->B, s));
+    PCTCHK(order_after_mutations(c, s));
+    const ClRun R{ BcDesc{ bt->polycoef, (long long)bt->row_stride, bt->seg_time, bt->orders, bt->seg_offsets, (long long)bt->B }, tol, cap, (int)max_depth, piece_cap,
+                   path, d_out, reinterpret_cast<long long *>(d_stats) };
+    PCTCHK(cl_seed(c, R, piece_cap, s));
+    // the live count stays on the device: every round is sized by piece_cap and every lane guards on it
+    for (int round = 0; round <= R.max_depth; round++) PCTCHK(cl_round(c, R, round, piece_cap, s));
+    return cl_finish(c, R, s);
 }
 
 // ---- hipGraph plan -----------------------------------------------------------------------

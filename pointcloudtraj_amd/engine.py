@@ -67,6 +67,11 @@ CERT_FREE, CERT_HIT, CERT_UNDECIDED, CERT_INVALID = 0, 1, 2, 3      # enum pct_c
 CERT_DTYPE = np.dtype([("status", np.int32), ("depth", np.int32), ("hit_seg", np.int32), ("hit_idx", np.uint32), ("hit_u", np.float64),
                        ("hit_d2", np.float64), ("min_d2", np.float64), ("pieces", np.int64)])
 
+CLR_DONE, CLR_OPEN, CLR_INVALID = 0, 1, 2                           # enum pct_clearance_status
+# pct_traj_clearance, 48 bytes (include/pct_engine.h, paragraph "Trajectory clearance")
+CLEARANCE_DTYPE = np.dtype([("status", np.int32), ("depth", np.int32), ("at_seg", np.int32), ("at_idx", np.uint32), ("at_u", np.float64),
+                            ("lo", np.float64), ("hi", np.float64), ("pieces", np.int64)])
+
 GEN_OK, GEN_NOT_CONVERGED, GEN_INVALID = 0, 1, 2                    # enum pct_gen_status
 # pct_trajgen_result, 64 bytes (include/pct_trajgen.h, paragraph "Trajectory generation")
 GEN_RESULT_DTYPE = np.dtype([("status", np.int32), ("iterations", np.int32), ("cost", np.float64), ("duration", np.float64),
@@ -462,6 +467,8 @@ def lib():
                                                  vp, vp, vp, vp, vp]
         L.pct_bezier_certify_batch.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, i32, i64, vp, vp]
         L.pct_bezier_certify_batch_dev.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, i32, i64, vp, vp, vp]
+        L.pct_bezier_clearance_batch.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, C.c_double, i32, i64, vp, vp]
+        L.pct_bezier_clearance_batch_dev.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, C.c_double, i32, i64, vp, vp, vp]
         L.pct_bezier_generate_batch.argtypes = [C.POINTER(TrajGenBatch), C.POINTER(TrajGenParams), f64p, i64, vp]
         L.pct_bezier_generate_batch_dev.argtypes = [C.POINTER(TrajGenBatch), C.POINTER(TrajGenParams), vp, i64, vp, vp]
         L.pct_time_allocation.argtypes = [f64p, f64p, i64, f64p, f64p, f64p, C.c_double, C.c_double, f64p]
@@ -1106,6 +1113,22 @@ class Cloud:
         del keep
         return cert, dict(rounds=int(stats[0]), pieces=int(stats[1]), capped=int(stats[2]))
 
+    def bezier_clearance(self, trajectories, tol, cap=float("inf"), max_depth=16, piece_cap=None, algo: int = ALGO_AUTO):
+        """pct_bezier_clearance_batch: each trajectory's distance to the cloud bracketed, lo <= clearance <= hi, to within `tol` metres
+        (or up to `cap`: clearance beyond it is of no interest).  trajectories and piece_cap as for bezier_certify.  Returns
+        (records, stats): a structured array of engine.CLEARANCE_DTYPE, one entry per trajectory -- status (CLR_DONE, CLR_OPEN,
+        CLR_INVALID), depth, at_seg, at_idx, at_u, lo, hi, pieces -- and dict(rounds, pieces, capped)."""
+        packed = isinstance(trajectories, tuple) and len(trajectories) == 2 and isinstance(trajectories[0], BezierBatch)
+        batch, keep = trajectories if packed else pack_trajectories(trajectories)
+        B = int(batch.B)
+        if piece_cap is None:
+            piece_cap = max(4096, 64 * len(keep["seg_time"]))
+        rec = np.zeros(B, CLEARANCE_DTYPE)
+        stats = np.zeros(3, np.int64)
+        _chk(lib().pct_bezier_clearance_batch(self._h, algo, C.byref(batch), float(tol), float(cap), int(max_depth), int(piece_cap), _ptr(rec), _ptr(stats)))
+        del keep
+        return rec, dict(rounds=int(stats[0]), pieces=int(stats[1]), capped=int(stats[2]))
+
     def ctrl_points_check(self, params: InflateParams, polycoef, seg_time, orders, t_start=0.0, cap=1024):
         """pct_ctrl_points_check: the collision threshold test on the raw control points (world units)"""
         traj, keep = _traj(polycoef, seg_time, orders)
@@ -1178,6 +1201,13 @@ class Cloud:
         or 0; reserve_queries(2 * piece_cap) first.  Asynchronous on `stream`; max_depth + 1 rounds over piece_cap slots."""
         _chk(lib().pct_bezier_certify_batch_dev(self._h, algo, C.byref(batch), float(margin), int(max_depth), int(piece_cap), cert_ptr or None,
                                                 stats_ptr or None, stream))
+
+    def bezier_clearance_device(self, batch: BezierBatch, tol, cap, max_depth, piece_cap, out_ptr: int, stats_ptr: int = 0, stream: int = 0,
+                                algo: int = ALGO_AUTO):
+        """pct_bezier_clearance_batch_dev: `batch` holds DEVICE pointers; out_ptr -> B x 48 bytes (engine.CLEARANCE_DTYPE), stats_ptr ->
+        int64 [3] or 0; reserve_queries(2 * piece_cap) first.  Asynchronous on `stream`; max_depth + 1 rounds over piece_cap slots."""
+        _chk(lib().pct_bezier_clearance_batch_dev(self._h, algo, C.byref(batch), float(tol), float(cap), int(max_depth), int(piece_cap), out_ptr or None,
+                                                  stats_ptr or None, stream))
 
     def radius_count_device(self, q_ptr: int, r_ptr: int, Q: int, cnt_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         _chk(lib().pct_radius_count_batch_dev(self._h, algo, q_ptr, r_ptr, int(Q), cnt_ptr, stream))
