@@ -1383,6 +1383,15 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
                                                  uint32_t sub, float qxf, float qyf, float qzf, double qx, double qy, double qz,
                                                  double &bd, uint32_t &bi)
 {
+    // TAIL only (the dense batch kernel; the pyramid's stage 0 keeps the compiler's choice): the three differences of a slot are made
+    // opaque where they are formed, which keeps the SLP vectoriser from pairing the slots' subtractions.  Left alone it packs two slots
+    // into v_pk_add / v_pk_mul / v_pk_fma_f32 and pays for it with moves: the loaded records shuffled into aligned register pairs and a
+    // second copy of the query kept in pairs.  Straight path of the narrow form (entry to the tail_loops branch): packed 270 vector
+    // instructions with 27 v_pk_*, 36 v_mov_b32 and 16 s_nop, 65 VGPRs; pinned 261 with 12 v_pk_* (the squares still pair up), 14
+    // v_mov_b32 and 14 s_nop, 64 VGPRs, all nine record loads still before the first s_waitcnt vmcnt (profiles/r08_stage0_asm.txt).
+    // The pin is an empty asm, not volatile: no instruction of its own.  The same expression in the same order, v_fma_f32 rounds as
+    // v_pk_fma_f32 does and nothing contracts (-ffp-contract=off): (m1, m2, p1) are the same bits.
+    constexpr bool kUnpacked = TAIL;
     float m1 = __builtin_huge_valf(), m2 = __builtin_huge_valf();
     uint32_t p1 = 0;
     // DEPTH points per lane and row (8 * DEPTH per row for the group) are requested up front
@@ -1418,7 +1427,8 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
 #pragma unroll
         for (int j = 0; j < DEPTH; j++) {
             const uint32_t p = a + sub + kCoop * j;
-            const float dx = P[k][j].x - qxf, dy = P[k][j].y - qyf, dz = P[k][j].z - qzf;
+            float dx = P[k][j].x - qxf, dy = P[k][j].y - qyf, dz = P[k][j].z - qzf;
+            if constexpr (kUnpacked) asm("" : "+v"(dx), "+v"(dy), "+v"(dz));
             float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
             d = (p < b) ? d : __builtin_huge_valf();
             const bool lt = d < m1;
@@ -1433,7 +1443,8 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
     auto long_row = [&](uint32_t a, uint32_t b) {
         for (uint32_t p = a + kCoop * DEPTH + sub; p < b; p += kCoop) {
             const float4 Pp = ld_at<NARROW>(pts, p);
-            const float dx = Pp.x - qxf, dy = Pp.y - qyf, dz = Pp.z - qzf;
+            float dx = Pp.x - qxf, dy = Pp.y - qyf, dz = Pp.z - qzf;
+            if constexpr (kUnpacked) asm("" : "+v"(dx), "+v"(dy), "+v"(dz));
             const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
             const bool lt = d < m1;
             m2 = __builtin_amdgcn_fmed3f(m1, m2, d);
@@ -1442,7 +1453,8 @@ __device__ __forceinline__ void coop_screen_rows(const float4 *__restrict__ pts,
         }
     };
     if constexpr (TAIL) {
-        const float dx = PT.x - qxf, dy = PT.y - qyf, dz = PT.z - qzf;
+        float dx = PT.x - qxf, dy = PT.y - qyf, dz = PT.z - qzf;
+        if constexpr (kUnpacked) asm("" : "+v"(dx), "+v"(dy), "+v"(dz));
         float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
         d = tail_on ? d : __builtin_huge_valf();
         const bool lt = d < m1;
@@ -1796,8 +1808,12 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
 // in the fold and 28 from there to the ballot of the undecided for a query the quick accept decides; wide 70 VGPRs, all nine loads before
 // vmcnt(8) as well, 280 + 20 + 29.  (Before the quick accept moved in front of the loads and the run bounds into one load instruction:
 // 69 VGPRs, 256 + 20 + 81, r05_stage0_asm.txt; before the swizzle folds, the wrapping clamp and the 32-bit offsets: 70 VGPRs, eight loads
-// and the ninth behind vmcnt(7), 283 + 36.)  Built for 8 waves the kernel still spills (64 VGPRs, 12-16 bytes of scratch): the count is the
-// maximum over all its paths, and stage 0 is no longer the one that sets it.
+// and the ninth behind vmcnt(7), 283 + 36.)
+// With the screening unpacked (coop_screen_rows, kUnpacked) the narrow form is 261 vector instructions on that path and needs 64 VGPRs, so
+// for the first time it builds for 8 waves without scratch and with the nine loads in one flight (the wide form splits them 8 + 1 there
+// and keeps 7 unmeasured).  Run, the eighth wave does not pay: headline step 0.1165 ms at 8 waves against 0.1160 at 7 (parent, packed,
+// 0.1183; five alternated rounds, profiles/r08_ab_unpacked_waves.txt) -- the kernel is bound by vector issue, and a wave more per SIMD
+// only waits longer for it.  The target is a property of the instantiation (nn_coop_waves), 7 for every one of them.
 // NARROW (chosen per launch on the host: narrow_offsets_fit, gridbuild.hpp) addresses the records, the run bounds, the sorted query and
 // the two results with 32-bit byte offsets from their scalar bases (ld_at / st_at); only the TAIL instantiation of coop_screen_rows takes
 // it -- the pyramid's stage 0 and the rare paths (exact rescans, the wave's remainder search, shells) keep 64-bit addresses.
@@ -1810,8 +1826,12 @@ __device__ __forceinline__ void coop_wave_search(const GridDesc &G, const float4
 // 0.2670 against 0.2652 ms and 8 M at 1.598 against 1.49-1.58.  The same kernel as resident blocks that walk the sorted batch in a loop
 // (one launch block per set of wave slots) ran the headline step at 0.1659 ms: DESIGN.md, retired variants.
 constexpr int kNNBlock = 128;
+// waves per SIMD the instantiation is built for, as minimum and maximum (see above; 8 needs <= 64 VGPRs, no scratch and the nine loads in
+// one flight, which only <false, true, .> has, and which measured slower there)
 template <bool COUNT, bool NARROW, int BLOCK>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(7, 7))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
+constexpr int nn_coop_waves() { return 7; }
+template <bool COUNT, bool NARROW, int BLOCK>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(nn_coop_waves<COUNT, NARROW, BLOCK>(), nn_coop_waves<COUNT, NARROW, BLOCK>()))) void nn_grid_coop_kernel(GridDesc G, const float4 *__restrict__ pts,
                                                            const uint32_t *__restrict__ cell_start,
                                                            const float *__restrict__ q, uint32_t Q, uint32_t index_base,
                                                            const float4 *__restrict__ qsorted,
