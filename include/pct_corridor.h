@@ -60,6 +60,10 @@ int pct_corridor_set_rolling_compact(pct_corridor *c, double dead_fraction);
  * frame (*kept, may be NULL = the points the window took). */
 int pct_corridor_clear_seen_through(pct_corridor *c, const pct_depth_view *view, const float *image, double margin, int64_t *removed);
 int pct_corridor_append_depth(pct_corridor *c, const pct_depth_view *view, const float *image, double max_depth, int64_t *kept);
+/* the same two calls for a lidar's range image (pct_engine.h, paragraph "Range images").  The lidar tick is
+ * clear_seen_through_range -> append_range -> evaluate -> refine with the same scan. */
+int pct_corridor_clear_seen_through_range(pct_corridor *c, const pct_range_view *view, const float *image, double margin, int64_t *removed);
+int pct_corridor_append_range(pct_corridor *c, const pct_range_view *view, const float *image, double max_range, int64_t *kept);
 /* after pct_corridor_enable_rolling: radius outlier removal on the window itself (pct_engine.h, paragraph "Removing outliers"): of the
  * `newest` most recent points (<= 0: every point), those with fewer than min_neighbours other points of the window within r are
  * removed (*removed, may be NULL).  With a noisy sensor the tick is clear_seen_through -> append_depth -> remove_outliers ->

@@ -238,6 +238,10 @@ public:
     // frame everything appendInput does for a point frame.  Radii that may now grow are re-checked by SafeRegionEvaluate.
     int64_t clearSeenThrough(const pct_depth_view &view, const float *image, double margin) { return map_.clearSeenThrough(view, image, margin); }
     int64_t appendDepthImage(const pct_depth_view &view, const float *image, double max_depth) { return map_.appendDepthImage(view, image, max_depth); }
+    // after enableRollingMap: a lidar's range image as the map's input (ObstacleMap::clearSeenThroughRange / appendRangeImage).  The
+    // lidar tick is clearSeenThroughRange -> appendRangeImage -> SafeRegionEvaluate -> SafeRegionRefine with the same scan in both calls.
+    int64_t clearSeenThroughRange(const pct_range_view &view, const float *image, double margin) { return map_.clearSeenThroughRange(view, image, margin); }
+    int64_t appendRangeImage(const pct_range_view &view, const float *image, double max_range) { return map_.appendRangeImage(view, image, max_range); }
     // after enableRollingMap: radius outlier removal on the window itself (ObstacleMap::removeOutliers).  With a noisy sensor the rgbd
     // tick is clearSeenThrough -> appendDepthImage -> removeOutliers -> SafeRegionEvaluate -> SafeRegionRefine, with newest = the
     // points the append kept: a speckle is withdrawn in the frame that brought it, before any radius is computed against it.

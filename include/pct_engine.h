@@ -291,6 +291,45 @@
  * |c_z - val| <= 6.1e-6), so with margin = 0 the next carve by the same image could remove some of them; with a small positive margin
  * (1e-3 on that domain) it cannot.  Sensor simulation -- rendering a world into an image -- is not part of the library.
  *
+ * Range images (pct_cloud_ring_carve_range, pct_cloud_append_range, pct_range_classify): the organised scan of a spinning or
+ * solid-state lidar -- rings by columns, a range per beam (the reference's camera/sensor_type = lidar) -- as the map's input, beside
+ * the depth images above and with the same three calls.  One projection serves all three (struct pct_range_view below); all
+ * arithmetic is fp64 from float-widened operands, one rounding per operation, no contraction, in the order written here; / and sqrt
+ * are correctly rounded.  The library calls no sin, cos or atan2: angles reach it only as tables the caller made.  Pseudo-angle:
+ * pa(x, y) is a monotone stand-in for atan2(y, x) on [0, 2 pi), exported as pct_range_pseudo_angle (a host function with no HIP call
+ * in it) so that callers build col_edge from their calibration with the arithmetic the device uses: den = |x| + |y|; if den is 0 or
+ * not finite the result is NaN; p = y / den; if x < 0, pa = 2.0 - p; otherwise, if y < 0, pa = 4.0 + p; otherwise pa = p.  The range
+ * is [0, 4): 0 = +x, 1 = +y, 2 = -x, 3 = -y.  Projection of a cloud row p (fp32): d = (double)p - t; r2 = (d0*d0 + d1*d1) + d2*d2;
+ * s_k = (d0*R[0][k] + d1*R[1][k]) + d2*R[2][k] for the sensor axes k = 0, 1, 2 (R[i][k] = R[3*i + k]); h = sqrt(s0*s0 + s1*s1),
+ * a = pa(s0, s1), q = s2 / h.  The point is IN THE IMAGE iff r2 >= near_range*near_range and r2 < +inf; h > 0;
+ * col_edge[0] <= a < col_edge[width]; row_edge[0] <= q < row_edge[height] -- a NaN fails every one of them.  Its pixel is (r, c):
+ * c = (number of col_edge entries <= a) - 1, r = (number of row_edge entries <= q) - 1; a value equal to an edge belongs to the cell
+ * above it.  The search is a plain binary search; its result is defined by these counts, not by the search.  The point is SEEN THROUGH
+ * iff it is in the image, val = (double)image[r*width + c] is finite (a +inf pixel proves nothing: no return; -inf and NaN likewise,
+ * as for depth images) and, with w = val - margin: w > 0 && r2 < w*w -- strict, no square root, the PCT_DEPTH_RANGE test: a point at
+ * exactly val - margin stays.  Un-projection of pixel (r, c) holding rho: the pixel is valid iff rho is finite, rho >= near_range and
+ * rho <= max_range; e0 = row_dir[r][0]*col_dir[c][0], e1 = row_dir[r][0]*col_dir[c][1], e2 = row_dir[r][1];
+ * p_k = t[k] + rho*((e0*R[k][0] + e1*R[k][1]) + e2*R[k][2]), narrowed to fp32 with round-to-nearest; valid pixels are emitted in
+ * row-major order.  Conventions: a scan that does not cover the whole circle chooses its sensor frame so that azimuth 0 (the +x axis)
+ * is not inside its span, for example x along the first column's lower edge; R and both direction tables are the caller's, in one
+ * frame.  A full-circle scan has col_edge[0] = 0 and col_edge[width] = 4.  Columns ascend in azimuth: a sensor that spins the other
+ * way hands over a mirrored R, or reorders its columns.  Per-pixel azimuth offsets (staggered beams) are out of scope: such a driver
+ * appends points, and may still carve with the nominal tables and a larger margin.  The three calls mean, word for word, what the
+ * depth calls they stand beside mean: pct_cloud_ring_carve_range is a removal in every sense of the paragraph "Removing points" (a
+ * live rolling-map index, an append in flight finished first, one pass over the slots below pct_cloud_size, one host wait for
+ * {removed, live after}; NaN rows left alone and not counted; removed rows become NaN rows whose records are retired, so the NaN-row
+ * equivalence holds on every path, the empty-window rule applies and captured plans stay valid); pct_cloud_append_range is
+ * pct_cloud_append_aos of the un-projected frame, through the de-dup filter when it is on, with the same host waits and
+ * PCT_ERR_CAPACITY; pct_range_classify narrows planner points to fp32, reports the lowest view that sees the point through and the
+ * pixel in the LAST view as pixel[2i] = c, pixel[2i + 1] = r (-1, -1 when the point is not in that image).  The tables are host memory,
+ * copied per call, the caller's again when the call returns.  Order of operations and the margin: carve first, then append the same
+ * image.  The points a scan appends project back onto their own pixel at a range within fp32 narrowing of the pixel value (numpy
+ * restatement, 40 random poses with |t| <= 100 m, ranges in [0.3, 60], widths 8 to 2048, heights 1 to 128, full-circle and partial
+ * spans, uniform and non-uniform rings, every cell at least 1e-3 rad wide: every point on its own pixel, |range - val| <= 5.7e-6),
+ * so with margin = 0 the next carve by the same scan could remove some of them; with a small positive margin (1e-3 on that domain) it
+ * cannot.  A cell much narrower than 1e-3 rad can lose its own point to a neighbour at short range: fp32 narrowing moves a point at
+ * 0.3 m from a sensor 100 m from the origin by up to 2.2e-5 rad.  Rendering a world into a scan is not part of the library.
+ *
  * Segment queries (pct_segment_nn_batch*, pct_segment_inflate_batch): the nearest obstacle point to a LINE SEGMENT, for the questions a
  * planner asks between two points -- is the straight line to the goal free with the margin, how wide is the free tube around this
  * edge, can the sphere chain be shortcut -- without sampling the line.  A segment is two planner points a, b (fp64 xyz), each
@@ -676,6 +715,32 @@ int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *i
  * pixel[2n] may be NULL.  n = 0: PCT_OK. */
 int pct_depth_classify(const pct_depth_view *views, const float *const *images, int32_t n_views, const double *pts, int64_t n,
                        double margin, int32_t *seen_by, int32_t *pixel);
+/* Range images (the paragraph "Range images" above).  One pinned projection for the three calls below. */
+typedef struct pct_range_view {
+    double t[3];            /* sensor position, world */
+    double R[9];            /* row-major; column k = sensor axis k in world: x azimuth 0, y azimuth +90 deg, z up (elevation +); not checked for orthonormality */
+    double near_range;      /* finite, > 0: a point or pixel nearer than this is not in the image */
+    int32_t width, height;  /* columns (azimuth) x rows (rings); 1..4096 x 1..1024, width*height <= 2^24 */
+    int32_t reserved[2];    /* 0 */
+    const double *col_edge; /* width + 1, strictly ascending pseudo-angles in [0, 4]: column c covers [col_edge[c], col_edge[c+1]) */
+    const double *row_edge; /* height + 1, strictly ascending finite values of q = z / hypot(x, y): row r covers [row_edge[r], row_edge[r+1]) */
+    const double *col_dir;  /* width x 2: (cos, sin) of each column's beam azimuth; append only, may be NULL otherwise */
+    const double *row_dir;  /* height x 2: (cos, sin) of each row's beam elevation; append only, may be NULL otherwise */
+} pct_range_view;
+/* `image`: host memory, width*height floats, row-major (row = ring), the caller's again when the call returns, as are the four tables
+ * (all are copied through staging buffers the library owns).  PCT_ERR_INVALID, with the cloud left as it was: a NULL required
+ * pointer; sizes outside the limits above; near_range not finite or not > 0; a non-finite t or R; reserved != 0; a NaN margin or
+ * max_range (+inf is allowed); an edge table that is not finite and strictly ascending, or a col_edge entry outside [0, 4]; col_dir /
+ * row_dir NULL or non-finite in pct_cloud_append_range; a cloud without pct_cloud_ring_index.
+ * carve: removes every point the scan sees through (strict; margin in metres); *removed = rows this call changed; an empty cloud:
+ * PCT_OK, *removed = 0.  append: *offered = valid pixels, *kept = what the window took (equal without de-dup); more valid pixels than
+ * the capacity: PCT_ERR_CAPACITY, nothing changed.  classify: views[k] and images[k], 1 <= n_views <= 16, each view with its own size
+ * and tables; pts: n planner points (fp64 xyz); seen_by[n]; pixel[2n] may be NULL.  n = 0: PCT_OK. */
+int pct_cloud_ring_carve_range(pct_cloud *c, const pct_range_view *v, const float *image, double margin, int64_t *removed);
+int pct_cloud_append_range(pct_cloud *c, const pct_range_view *v, const float *image, double max_range, int64_t *offered, int64_t *kept);
+int pct_range_classify(const pct_range_view *views, const float *const *images, int32_t n_views, const double *pts, int64_t n,
+                       double margin, int32_t *seen_by, int32_t *pixel);
+double pct_range_pseudo_angle(double x, double y);
 /* Zero-copy ingest.  pct_cloud_frame_buffer hands out a host-mapped staging buffer of at least `bytes` bytes (valid until the next
  * call that asks for a larger one, or pct_cloud_destroy); the producer -- a sensor driver, the deserialiser of a
  * sensor_msgs/PointCloud2 -- writes the frame's records there (x, y, z floats at the start of each stride-byte record) and

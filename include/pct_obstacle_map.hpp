@@ -364,6 +364,30 @@ public:
         return kept;
     }
 
+    // Range images on the rolling map (pct_engine.h, paragraph "Range images"; both need enableRollingIndex): the organised scan of a
+    // lidar, rings by columns, with the caller's edge and direction tables in the view.  The lidar tick is clearSeenThroughRange(scan)
+    // then appendRangeImage(the same scan): carve first, then append, with a small positive margin.
+    //   clearSeenThroughRange   removes every point the scan sees through -- a point in the image whose pixel is finite and shows a
+    //                           return strictly farther than the point plus margin; returns the number removed
+    //   appendRangeImage        un-projects the valid pixels (finite, near_range <= range <= max_range) on the device and appends
+    //                           them as appendInput appends the same points; returns the number of points the window took
+    int64_t clearSeenThroughRange(const pct_range_view &view, const float *image, double margin)
+    {
+        needRolling("clearSeenThroughRange");
+        int64_t removed = 0;
+        check(pct_cloud_ring_carve_range(cloud_, &view, image, margin, &removed), "pct_cloud_ring_carve_range");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return removed;
+    }
+    int64_t appendRangeImage(const pct_range_view &view, const float *image, double max_range)
+    {
+        needRolling("appendRangeImage");
+        int64_t offered = 0, kept = 0;
+        check(pct_cloud_append_range(cloud_, &view, image, max_range, &offered, &kept), "pct_cloud_append_range");
+        cloud_empty_ = pct_cloud_size(cloud_) == 0;
+        return kept;
+    }
+
     // corridor_finder.cpp:113-133
     double radiusSearch(const double p[3])
     {

@@ -40,7 +40,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
             os.path.join(ROOT, "include", "kdtree", "kdtree_ext.h")]
     hdrs += [os.path.join(ROOT, "include", "pct_voxel.h"), os.path.join(ROOT, "include", "pct_traj.h"), os.path.join(ROOT, "include", "pct_trajgen.h")]
     eng_units = [os.path.join(CSRC, "engine.hip"), os.path.join(CSRC, "voxel.hip"), os.path.join(CSRC, "traj.hip"), os.path.join(CSRC, "nodeset.hip"), os.path.join(CSRC, "trajgen.hip")]
-    eng_src = eng_units + [os.path.join(CSRC, f) for f in ("kernels.hpp", "query_bin.hpp", "scan.hpp", "gridbuild.hpp", "pyramid.hpp", "bernstein.hpp", "brute2.hpp", "knn.hpp", "rsearch.hpp", "ring.hpp", "ring_dedup.hpp", "ring_remove.hpp", "ring_compact.hpp", "ring_depth.hpp", "ring_outlier.hpp", "ring_statistical.hpp", "vox_key.hpp", "ring_search.hpp", "segment.hpp", "segment_search.hpp", "segment_polyhedron.hpp", "bezier_batch.hpp", "bezier_certify.hpp", "bezier_clearance.hpp", "trajgen.hpp", "trajgen_poly.hpp", "ring_host.inc", "engine_internal.hpp", "hostmem.hpp")]
+    eng_src = eng_units + [os.path.join(CSRC, f) for f in ("kernels.hpp", "query_bin.hpp", "scan.hpp", "gridbuild.hpp", "pyramid.hpp", "bernstein.hpp", "brute2.hpp", "knn.hpp", "rsearch.hpp", "ring.hpp", "ring_dedup.hpp", "ring_remove.hpp", "ring_compact.hpp", "ring_depth.hpp", "ring_range.hpp", "ring_outlier.hpp", "ring_statistical.hpp", "vox_key.hpp", "ring_search.hpp", "segment.hpp", "segment_search.hpp", "segment_polyhedron.hpp", "bezier_batch.hpp", "bezier_certify.hpp", "bezier_clearance.hpp", "trajgen.hpp", "trajgen_poly.hpp", "ring_host.inc", "engine_internal.hpp", "hostmem.hpp")]
     if force or _stale(ENGINE_SO, eng_src + hdrs):
         cmd = [HIPCC, *COMMON, "-o", ENGINE_SO, *eng_units]
         if verbose:
@@ -187,6 +187,16 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     if os.path.exists(poly_src) and os.path.exists(ENGINE_SO) and (force or _stale(poly_bin, [poly_src, ENGINE_SO] + hdrs + [os.path.join(ROOT, "include", "pct_obstacle_map.hpp")])):
         # pct::generateTrajectoriesInPolyhedra / ObstacleMap::generateSafeTrajectoryInPolyhedra: one route through polytopes and through spheres; needs the engine alone
         cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-o", poly_bin, poly_src,
+               "-L" + LIB, "-lpct_engine", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + LIB, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+
+    tick_src = os.path.join(ROOT, "examples", "range_image_tick.cpp")
+    tick_bin = os.path.join(LIB, "range_image_tick")
+    if os.path.exists(tick_src) and os.path.exists(ENGINE_SO) and (force or _stale(tick_bin, [tick_src, ENGINE_SO] + hdrs + [os.path.join(ROOT, "include", "pct_obstacle_map.hpp")])):
+        # ObstacleMap::clearSeenThroughRange / appendRangeImage: two lidar ticks against a host loop over the contract's formulas; needs the engine alone
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-o", tick_bin, tick_src,
                "-L" + LIB, "-lpct_engine", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + LIB, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
         if verbose:
             print(" ".join(cmd))

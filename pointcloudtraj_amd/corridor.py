@@ -47,6 +47,8 @@ def lib():
         L.pct_corridor_remove_isolated.argtypes = [vp, C.c_int32, C.c_double, C.c_int64, C.POINTER(C.c_int64)]
         L.pct_corridor_clear_seen_through.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_append_depth.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
+        L.pct_corridor_clear_seen_through_range.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
+        L.pct_corridor_append_range.argtypes = [vp, vp, vp, C.c_double, C.POINTER(C.c_int64)]
         L.pct_corridor_cloud.argtypes = [vp, C.POINTER(vp)]
         L.pct_corridor_set_pt.argtypes = [vp, d3, d3] + [C.c_double] * 7 + [C.c_int, C.c_double, C.c_double]
         L.pct_corridor_set_start_pt.argtypes = [vp, d3, d3]
@@ -202,6 +204,24 @@ class SafeRegionRrtStar:
         img = engine.depth_image(view, image)
         n = C.c_int64()
         self._chk(self.L.pct_corridor_append_depth(self.h, C.addressof(view), img.ctypes.data, float(max_depth), C.byref(n)))
+        return n.value
+
+    def clearSeenThroughRange(self, view, image, margin: float) -> int:
+        """after enableRollingMap: remove every point the lidar's range image sees through (engine.RangeView; the lidar tick:
+        clearSeenThroughRange -> appendRangeImage -> SafeRegionEvaluate -> SafeRegionRefine); returns the number of points removed"""
+        from . import engine
+        img = engine.depth_image(view, image)
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_clear_seen_through_range(self.h, C.addressof(view), img.ctypes.data, float(margin), C.byref(n)))
+        return n.value
+
+    def appendRangeImage(self, view, image, max_range: float = float("inf")) -> int:
+        """after enableRollingMap: un-project the scan's valid pixels on the device and append them as appendInput appends a point
+        frame; returns the number of points the window took"""
+        from . import engine
+        img = engine.depth_image(view, image)
+        n = C.c_int64()
+        self._chk(self.L.pct_corridor_append_range(self.h, C.addressof(view), img.ctypes.data, float(max_range), C.byref(n)))
         return n.value
 
     def cloud(self):

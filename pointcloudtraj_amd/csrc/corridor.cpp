@@ -108,6 +108,22 @@ int pct_corridor_append_depth(pct_corridor *c, const pct_depth_view *view, const
         if (kept) *kept = n;
     });
 }
+int pct_corridor_clear_seen_through_range(pct_corridor *c, const pct_range_view *view, const float *image, double margin, int64_t *removed)
+{
+    return guarded([&] {
+        if (!view) throw std::runtime_error("pct_corridor_clear_seen_through_range: null view");
+        const int64_t n = c->impl->clearSeenThroughRange(*view, image, margin);
+        if (removed) *removed = n;
+    });
+}
+int pct_corridor_append_range(pct_corridor *c, const pct_range_view *view, const float *image, double max_range, int64_t *kept)
+{
+    return guarded([&] {
+        if (!view) throw std::runtime_error("pct_corridor_append_range: null view");
+        const int64_t n = c->impl->appendRangeImage(*view, image, max_range);
+        if (kept) *kept = n;
+    });
+}
 int pct_corridor_remove_outliers(pct_corridor *c, double r, int32_t min_neighbours, int64_t newest, int64_t *removed)
 {
     return guarded([&] { const int64_t n = c->impl->removeOutliers(r, min_neighbours, newest); if (removed) *removed = n; });

@@ -34,6 +34,7 @@
 #include "ring_remove.hpp"
 #include "ring_compact.hpp"
 #include "ring_depth.hpp"
+#include "ring_range.hpp"
 #include "ring_outlier.hpp"
 #include "ring_statistical.hpp"
 #include "brute2.hpp"
@@ -187,6 +188,14 @@ struct DepthStage {
     PinnedBuf<float> h;
     DevBuf<float> d;
     size_t cap = 0;                              // floats
+};
+
+// The tables of a range view on the same way (ring_range.hpp): col_edge, row_edge and, for an append, col_dir and row_dir, one
+// behind the other.  The same rule frees the pinned copy: every user waits for a kernel behind the copy before it returns.
+struct RangeStage {
+    PinnedBuf<double> h;
+    DevBuf<double> d;
+    size_t cap = 0;                              // doubles
 };
 
 }  // namespace
@@ -407,6 +416,7 @@ struct pct_cloud {
     // compaction scratch.  Two instances: a depth append with de-dup on reads dp.out while the filter writes dd.out.
     DepthStage dp_img;
     CompactScratch dp;
+    RangeStage rg_tab;                           // range images (ring_range.hpp) share dp_img and dp; their tables are staged here
     ReplanCtx *rp = nullptr;                     // lazily created context of the un-captured fused planner batch
 };
 

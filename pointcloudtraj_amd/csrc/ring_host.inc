@@ -1438,10 +1438,11 @@ int depth_scratch_ensure(pct_cloud *c, int64_t npix)
     return c->dp.ensure(pow2_at_least<int64_t>(4096, npix));
 }
 
-// pct_depth_classify has no cloud to keep its buffers in: one grow-only set for the process, used under a lock
+// pct_depth_classify and pct_range_classify have no cloud to keep their buffers in: one grow-only set for the process, used under a lock
 struct DepthClassifyWork {
     std::mutex lock;
     DepthStage images;
+    RangeStage tables;                           // pct_range_classify: the edge tables of every view
     DevBuf<double> d_pts;
     DevBuf<int32_t> d_seen, d_pixel;
     int64_t ncap = 0;
@@ -1449,13 +1450,35 @@ struct DepthClassifyWork {
 DepthClassifyWork &g_depth_work = *new DepthClassifyWork();      // never destroyed: the HIP runtime may be gone by then
 
 // the cloud's image staging: copy `image` in and hand back where the kernels read it
-int depth_cloud_image(pct_cloud *c, const pct_depth_view *v, const float *image, const float **d_image)
+int depth_cloud_image(pct_cloud *c, size_t npix, const float *image, const float **d_image)
 {
-    const size_t npix = (size_t)v->width * (size_t)v->height;
     PCTCHK(depth_stage_ensure(&c->dp_img, npix));
     PCTCHK(depth_stage_image(&c->dp_img, image, 0, npix));
     *d_image = c->dp_img.d;
     return PCT_OK;
+}
+
+// The tail of pct_cloud_append_depth / pct_cloud_append_range behind their un-projection kernels: the FIRST host wait (the valid
+// count of launch `seq`), the capacity test, then pct_cloud_append_aos of the n un-projected points, their source being the packed
+// device frame c->dp.out
+int image_frame_append(pct_cloud *c, uint32_t seq, int64_t npix, const char *kind, int64_t *offered, int64_t *kept)
+{
+    int64_t n = 0;
+    PCTCHK(dd_scan_wait(c, seq, &n));
+    if (n > npix) return fail(PCT_ERR_INTERNAL, "the %s un-projection counted %lld valid pixels of %lld", kind, (long long)n, (long long)npix);
+    if (n > c->cap) return fail(PCT_ERR_CAPACITY, "appending %lld valid pixels to a ring of %lld", (long long)n, (long long)c->cap);
+    *offered = n;
+    const unsigned char *d_frame = reinterpret_cast<const unsigned char *>(c->dp.out.get());
+    if (c->dd_res > 0) {
+        PCTCHK(ring_append_dedup(c, nullptr, n, 12, d_frame));          // the SECOND host wait: the survivor count
+        *kept = c->dd_last_kept;
+        return PCT_OK;
+    }
+    *kept = n;
+    if (n == 0) return PCT_OK;
+    drop_grid(c);
+    if (c->ring_ready) return ring_append(c, nullptr, n, 12, d_frame);
+    return append_unindexed_dev(c, c->dp.out, n);
 }
 
 }  // namespace
@@ -1471,7 +1494,7 @@ int pct_cloud_ring_carve_depth(pct_cloud *c, const pct_depth_view *v, const floa
     *removed_out = 0;
     if (c->count == 0) return PCT_OK;
     const float *d_image = nullptr;
-    PCTCHK(depth_cloud_image(c, v, image, &d_image));
+    PCTCHK(depth_cloud_image(c, (size_t)v->width * (size_t)v->height, image, &d_image));
     return ring_remove_run(c, DepthSeenThrough{ *v, d_image, margin }, removed_out);
 }
 
@@ -1488,7 +1511,7 @@ int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *i
     const int64_t npix = (int64_t)v->width * (int64_t)v->height;
     PCTCHK(depth_scratch_ensure(c, npix));
     const float *d_image = nullptr;
-    PCTCHK(depth_cloud_image(c, v, image, &d_image));
+    PCTCHK(depth_cloud_image(c, (size_t)npix, image, &d_image));
     // flags of the valid pixels, their ranks in row-major order, and the FIRST host wait: the valid count -- the capacity test, the
     // slots the append takes and the filter's table size all need it before anything is queued that changes the window
     const uint32_t un = (uint32_t)npix, seq = c->dd_word.next();
@@ -1498,23 +1521,7 @@ int pct_cloud_append_depth(pct_cloud *c, const pct_depth_view *v, const float *i
     scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->dp.tile, (uint32_t)ntiles, DdPublish{ c->dd_word.w, seq });
     depth_unproject_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(*v, d_image, un, c->dp.flags, c->dp.rank, c->dp.tile, c->dp.out);
     HIPCHK(hipGetLastError());
-    int64_t n = 0;
-    PCTCHK(dd_scan_wait(c, seq, &n));
-    if (n > npix) return fail(PCT_ERR_INTERNAL, "the depth un-projection counted %lld valid pixels of %lld", (long long)n, (long long)npix);
-    if (n > c->cap) return fail(PCT_ERR_CAPACITY, "appending %lld valid pixels to a ring of %lld", (long long)n, (long long)c->cap);
-    *offered = n;
-    // from here on: pct_cloud_append_aos of the n un-projected points, their source being the packed device frame
-    const unsigned char *d_frame = reinterpret_cast<const unsigned char *>(c->dp.out.get());
-    if (c->dd_res > 0) {
-        PCTCHK(ring_append_dedup(c, nullptr, n, 12, d_frame));          // the SECOND host wait: the survivor count
-        *kept = c->dd_last_kept;
-        return PCT_OK;
-    }
-    *kept = n;
-    if (n == 0) return PCT_OK;
-    drop_grid(c);
-    if (c->ring_ready) return ring_append(c, nullptr, n, 12, d_frame);
-    return append_unindexed_dev(c, c->dp.out, n);
+    return image_frame_append(c, seq, npix, "depth", offered, kept);
 }
 
 int pct_depth_classify(const pct_depth_view *views, const float *const *images, int32_t n_views, const double *pts, int64_t n, double margin,
@@ -1551,6 +1558,175 @@ int pct_depth_classify(const pct_depth_view *views, const float *const *images, 
     }
     HIPCHK(hipMemcpyAsync(W.d_pts, pts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, g_stream));
     depth_classify_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(S, W.d_pts, (uint32_t)n, margin, W.d_seen, pixel ? W.d_pixel : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(seen_by, W.d_seen, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    if (pixel) HIPCHK(hipMemcpyAsync(pixel, W.d_pixel, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return PCT_OK;
+}
+
+}  // extern "C"
+
+// ---- range images on the rolling map (ring_range.hpp) ----------------------------------------------------------------------------
+namespace {
+
+// finite and strictly ascending (a NaN fails both comparisons' sense: it is not finite)
+bool range_edges_ok(const double *e, int n)
+{
+    for (int k = 0; k <= n; k++) {
+        if (!std::isfinite(e[k])) return false;
+        if (k > 0 && !(e[k - 1] < e[k])) return false;
+    }
+    return true;
+}
+
+// what the three range entry points refuse in a view (pct_engine.h); dirs: the call un-projects and needs both direction tables
+int range_view_check(const pct_range_view *v, const char *what, bool dirs)
+{
+    if (!v) return fail(PCT_ERR_INVALID, "%s: null view", what);
+    if (v->width < 1 || v->width > kRangeMaxWidth || v->height < 1 || v->height > kRangeMaxHeight || (int64_t)v->width * (int64_t)v->height > (1ll << 24))
+        return fail(PCT_ERR_INVALID, "%s: bad scan size %d x %d (1..%d columns, 1..%d rows)", what, v->width, v->height, kRangeMaxWidth, kRangeMaxHeight);
+    if (!(std::isfinite(v->near_range) && v->near_range > 0)) return fail(PCT_ERR_INVALID, "%s: near_range must be finite and > 0", what);
+    for (int k = 0; k < 3; k++) if (!std::isfinite(v->t[k])) return fail(PCT_ERR_INVALID, "%s: the sensor position is not finite", what);
+    for (int k = 0; k < 9; k++) if (!std::isfinite(v->R[k])) return fail(PCT_ERR_INVALID, "%s: the sensor rotation is not finite", what);
+    if (v->reserved[0] != 0 || v->reserved[1] != 0) return fail(PCT_ERR_INVALID, "%s: the reserved fields must be 0", what);
+    if (!v->col_edge || !v->row_edge) return fail(PCT_ERR_INVALID, "%s: a null edge table", what);
+    if (!range_edges_ok(v->col_edge, v->width) || !(v->col_edge[0] >= 0.0 && v->col_edge[v->width] <= 4.0))
+        return fail(PCT_ERR_INVALID, "%s: col_edge must be finite, strictly ascending and inside [0, 4]", what);
+    if (!range_edges_ok(v->row_edge, v->height)) return fail(PCT_ERR_INVALID, "%s: row_edge must be finite and strictly ascending", what);
+    if (dirs) {
+        if (!v->col_dir || !v->row_dir) return fail(PCT_ERR_INVALID, "%s: a null direction table", what);
+        for (int k = 0; k < 2 * v->width; k++) if (!std::isfinite(v->col_dir[k])) return fail(PCT_ERR_INVALID, "%s: col_dir is not finite", what);
+        for (int k = 0; k < 2 * v->height; k++) if (!std::isfinite(v->row_dir[k])) return fail(PCT_ERR_INVALID, "%s: row_dir is not finite", what);
+    }
+    return PCT_OK;
+}
+
+size_t range_table_doubles(const pct_range_view *v, bool dirs)
+{
+    return (size_t)(v->width + 1) + (size_t)(v->height + 1) + (dirs ? 2 * (size_t)v->width + 2 * (size_t)v->height : 0);
+}
+
+int range_stage_ensure(RangeStage *S, size_t doubles)
+{
+    if (doubles <= S->cap) return PCT_OK;
+    HIPCHK(hipStreamSynchronize(g_stream));
+    const size_t cap = pow2_at_least((size_t)1 << 12, doubles);
+    return regrow(S->cap, cap, part(S->h, cap), part(S->d, cap));
+}
+
+// Copy a checked view's tables into the stage at `off` (room ensured by the caller) and hand back the view as the kernels take it;
+// dirs != nullptr: the two direction tables too, dirs[0] = col_dir, dirs[1] = row_dir on the device.  The caller's tables are its
+// own again when this returns.
+int range_tables_stage(RangeStage *S, const pct_range_view *v, size_t off, RangeViewDev *out, const double **dirs)
+{
+    const size_t nc = (size_t)v->width + 1, nr = (size_t)v->height + 1;
+    double *h = S->h + off;
+    std::memcpy(h, v->col_edge, sizeof(double) * nc);
+    std::memcpy(h + nc, v->row_edge, sizeof(double) * nr);
+    if (dirs) {
+        std::memcpy(h + nc + nr, v->col_dir, sizeof(double) * 2 * (size_t)v->width);
+        std::memcpy(h + nc + nr + 2 * (size_t)v->width, v->row_dir, sizeof(double) * 2 * (size_t)v->height);
+    }
+    const size_t total = range_table_doubles(v, dirs != nullptr);
+    HIPCHK(hipMemcpyAsync(S->d + off, h, sizeof(double) * total, hipMemcpyHostToDevice, g_stream));
+    for (int k = 0; k < 3; k++) out->t[k] = v->t[k];
+    for (int k = 0; k < 9; k++) out->R[k] = v->R[k];
+    out->near_range = v->near_range;
+    out->width = v->width; out->height = v->height;
+    const double *d = S->d + off;
+    out->col_edge = d; out->row_edge = d + nc;
+    if (dirs) { dirs[0] = d + nc + nr; dirs[1] = d + nc + nr + 2 * (size_t)v->width; }
+    return PCT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+double pct_range_pseudo_angle(double x, double y) { return range_pseudo_angle(x, y); }
+
+int pct_cloud_ring_carve_range(pct_cloud *c, const pct_range_view *v, const float *image, double margin, int64_t *removed_out)
+{
+    if (!c || !image || !removed_out) return fail(PCT_ERR_INVALID, "bad ring_carve_range arguments");
+    PCTCHK(range_view_check(v, "pct_cloud_ring_carve_range", false));
+    if (std::isnan(margin)) return fail(PCT_ERR_INVALID, "pct_cloud_ring_carve_range: the margin is a NaN");
+    PCTCHK(ring_remove_begin(c, "pct_cloud_ring_carve_range"));
+    *removed_out = 0;
+    if (c->count == 0) return PCT_OK;
+    RangeViewDev V;
+    PCTCHK(range_stage_ensure(&c->rg_tab, range_table_doubles(v, false)));
+    PCTCHK(range_tables_stage(&c->rg_tab, v, 0, &V, nullptr));
+    const float *d_image = nullptr;
+    PCTCHK(depth_cloud_image(c, (size_t)v->width * (size_t)v->height, image, &d_image));
+    return ring_remove_run(c, RangeSeenThrough{ V, d_image, margin }, removed_out);
+}
+
+int pct_cloud_append_range(pct_cloud *c, const pct_range_view *v, const float *image, double max_range, int64_t *offered, int64_t *kept)
+{
+    if (!c || !image || !offered || !kept) return fail(PCT_ERR_INVALID, "bad append_range arguments");
+    PCTCHK(range_view_check(v, "pct_cloud_append_range", true));
+    if (std::isnan(max_range)) return fail(PCT_ERR_INVALID, "pct_cloud_append_range: max_range is a NaN");
+    if (!c->ring_on) return fail(PCT_ERR_INVALID, "pct_cloud_append_range needs the rolling-map index (pct_cloud_ring_index)");
+    hipStream_t s = g_stream;
+    PCTCHK(ring_finish_pending(c));             // the previous frame's insert kernel has read the packed frame below
+    *offered = *kept = 0;
+    const int64_t npix = (int64_t)v->width * (int64_t)v->height;
+    PCTCHK(depth_scratch_ensure(c, npix));
+    RangeViewDev V;
+    const double *dirs[2] = { nullptr, nullptr };
+    PCTCHK(range_stage_ensure(&c->rg_tab, range_table_doubles(v, true)));
+    PCTCHK(range_tables_stage(&c->rg_tab, v, 0, &V, dirs));
+    const float *d_image = nullptr;
+    PCTCHK(depth_cloud_image(c, (size_t)npix, image, &d_image));
+    // as pct_cloud_append_depth: flags of the valid pixels, their ranks in row-major order, the un-projection into the packed frame
+    const uint32_t un = (uint32_t)npix, seq = c->dd_word.next();
+    const int ntiles = ceil_div(npix, kDdTile);
+    range_valid_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(V.near_range, d_image, un, max_range, c->dp.flags);
+    dd_rank_kernel<<<ntiles, 256, 0, s>>>(c->dp.flags, un, c->dp.rank, c->dp.tile);
+    scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->dp.tile, (uint32_t)ntiles, DdPublish{ c->dd_word.w, seq });
+    range_unproject_kernel<<<ceil_div(npix, 256), 256, 0, s>>>(V, dirs[0], dirs[1], d_image, un, c->dp.flags, c->dp.rank, c->dp.tile, c->dp.out);
+    HIPCHK(hipGetLastError());
+    return image_frame_append(c, seq, npix, "range", offered, kept);
+}
+
+int pct_range_classify(const pct_range_view *views, const float *const *images, int32_t n_views, const double *pts, int64_t n, double margin,
+                       int32_t *seen_by, int32_t *pixel)
+{
+    if (!views || !images || n_views < 1 || n_views > kRangeMaxViews || n < 0 || !pts || !seen_by || n > 0xFFFFFFF0ll)
+        return fail(PCT_ERR_INVALID, "bad range_classify arguments (1 <= n_views <= %d)", kRangeMaxViews);
+    if (std::isnan(margin)) return fail(PCT_ERR_INVALID, "pct_range_classify: the margin is a NaN");
+    size_t total = 0, tables = 0;
+    for (int k = 0; k < n_views; k++) {
+        if (!images[k]) return fail(PCT_ERR_INVALID, "pct_range_classify: image %d is NULL", k);
+        PCTCHK(range_view_check(&views[k], "pct_range_classify", false));
+        total += (size_t)views[k].width * (size_t)views[k].height;
+        tables += range_table_doubles(&views[k], false);
+    }
+    if (n == 0) return PCT_OK;
+    PCTCHK(require_init());
+    DepthClassifyWork &W = g_depth_work;
+    std::lock_guard<std::mutex> guard(W.lock);
+    PCTCHK(depth_stage_ensure(&W.images, total));
+    PCTCHK(range_stage_ensure(&W.tables, tables));
+    if (n > W.ncap) {
+        HIPCHK(hipStreamSynchronize(g_stream));
+        const int64_t cap = pow2_at_least<int64_t>(1024, n);
+        PCTCHK(regrow(W.ncap, cap, part(W.d_pts, 3 * (size_t)cap), part(W.d_seen, (size_t)cap), part(W.d_pixel, 2 * (size_t)cap)));
+    }
+    RangeViews S{};
+    S.n = n_views;
+    size_t off = 0, toff = 0;
+    for (int k = 0; k < n_views; k++) {
+        const size_t npix = (size_t)views[k].width * (size_t)views[k].height;
+        PCTCHK(range_tables_stage(&W.tables, &views[k], toff, &S.v[k], nullptr));
+        S.image[k] = W.images.d + off;
+        PCTCHK(depth_stage_image(&W.images, images[k], off, npix));
+        off += npix;
+        toff += range_table_doubles(&views[k], false);
+    }
+    HIPCHK(hipMemcpyAsync(W.d_pts, pts, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, g_stream));
+    range_classify_kernel<<<ceil_div(n, 256), 256, 0, g_stream>>>(S, W.d_pts, (uint32_t)n, margin, W.d_seen, pixel ? W.d_pixel : nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(seen_by, W.d_seen, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g_stream));
     if (pixel) HIPCHK(hipMemcpyAsync(pixel, W.d_pixel, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost, g_stream));

@@ -106,7 +106,7 @@ __device__ __forceinline__ void ring_remove_where(const RingEdit &E, const Pred 
     ring_remove_count(removed, live, E.meet, E.host_word, E.seq, 1);
 }
 
-// THE one-pass removal kernel: ball and box (RingRegion), the depth-image carve (DepthSeenThrough, ring_depth.hpp), radius
+// THE one-pass removal kernel: ball and box (RingRegion), the depth-image and range-image carves (DepthSeenThrough, ring_depth.hpp; RangeSeenThrough, ring_range.hpp), radius
 // outliers (RoBelow, ring_outlier.hpp) and statistical / isolated outliers (KsAbove, ring_statistical.hpp) differ in `Pred` alone,
 // a small trivially-copyable functor passed by value.  The host's ring_remove_run launches it.
 template <typename Pred>

@@ -365,6 +365,89 @@ def depth_classify(views, images, points, margin, want_pixel=True):
     return seen, pix
 
 
+class RangeView(C.Structure):
+    """pct_range_view: the pinned projection of a lidar range image (include/pct_engine.h, paragraph "Range images").  The four
+    table pointers name host arrays that must outlive every call the view is handed to: range_view() keeps them on the view."""
+    _fields_ = [("t", C.c_double * 3), ("R", C.c_double * 9), ("near_range", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
+                ("reserved", C.c_int32 * 2), ("col_edge", C.POINTER(C.c_double)), ("row_edge", C.POINTER(C.c_double)),
+                ("col_dir", C.POINTER(C.c_double)), ("row_dir", C.POINTER(C.c_double))]
+
+
+def pseudo_angle(x, y) -> float:
+    """pct_range_pseudo_angle: the monotone stand-in for atan2(y, x) on [0, 4) that places a point in a column (needs no device)"""
+    return float(lib().pct_range_pseudo_angle(float(x), float(y)))
+
+
+def range_view(t, R, col_edge, row_edge, col_dir=None, row_dir=None, near_range=0.05) -> RangeView:
+    """t: sensor position; R: 3 x 3, column k = sensor axis k in world (x azimuth 0, y azimuth +90 deg, z up); col_edge [width + 1]
+    pseudo-angles, row_edge [height + 1] values of z / hypot(x, y), both strictly ascending; col_dir [width, 2] and row_dir
+    [height, 2]: (cos, sin) of the beams' azimuths and elevations, needed by append_range alone.  The view keeps its arrays alive."""
+    ce, re_ = np.ascontiguousarray(col_edge, np.float64).reshape(-1), np.ascontiguousarray(row_edge, np.float64).reshape(-1)
+    if len(ce) < 2 or len(re_) < 2:
+        raise ValueError("an edge table has width + 1 (height + 1) entries, at least 2")
+    v = RangeView()
+    v.t[:] = [float(x) for x in np.asarray(t, np.float64).reshape(3)]
+    v.R[:] = [float(x) for x in np.asarray(R, np.float64).reshape(9)]
+    v.near_range = float(near_range)
+    v.width, v.height = len(ce) - 1, len(re_) - 1
+    keep = [ce, re_]
+    dp = C.POINTER(C.c_double)
+    v.col_edge, v.row_edge = ce.ctypes.data_as(dp), re_.ctypes.data_as(dp)
+    for name, a, n in (("col_dir", col_dir, v.width), ("row_dir", row_dir, v.height)):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, np.float64).reshape(-1)
+        if len(a) != 2 * n:
+            raise ValueError(f"{name} has {len(a)} entries, the view needs {n} x 2")
+        keep.append(a)
+        setattr(v, name, a.ctypes.data_as(dp))
+    v._arrays = keep
+    return v
+
+
+def range_view_uniform(t, R_sensor, az_start, az_span, el_lo, el_hi, width, height, near_range=0.05) -> RangeView:
+    """the view of an evenly spaced scan, angles in radians: `width` columns of az_span / width each, the first one starting at azimuth
+    az_start of the sensor frame R_sensor, and `height` rings of (el_hi - el_lo) / height each between the elevations el_lo < el_hi
+    (inside +/- 90 degrees); every beam points along the middle of its cell, so the edges lie midway between beams, in angle.
+    az_start is folded into the returned view's R (a turn about the sensor's z axis), so that the span starts at azimuth 0:
+    col_edge[0] = 0, and col_edge[width] = 4 when az_span is the full circle."""
+    width, height = int(width), int(height)
+    full = abs(az_span - 2.0 * np.pi) <= 2.0 * np.pi * 1.0e-12
+    if not (width >= 1 and height >= 1 and (full or 0.0 < az_span < 2.0 * np.pi) and -np.pi / 2 < el_lo < el_hi < np.pi / 2):
+        raise ValueError("bad scan geometry")
+    span = 2.0 * np.pi if full else float(az_span)
+    az_edge = np.arange(width + 1, dtype=np.float64) * (span / width)
+    L = lib()
+    col_edge = np.array([L.pct_range_pseudo_angle(float(np.cos(a)), float(np.sin(a))) for a in az_edge], np.float64)
+    col_edge[0] = 0.0
+    if full:
+        col_edge[width] = 4.0
+    az_beam = (np.arange(width, dtype=np.float64) + 0.5) * (span / width)
+    el_edge = el_lo + np.arange(height + 1, dtype=np.float64) * ((el_hi - el_lo) / height)
+    el_beam = el_lo + (np.arange(height, dtype=np.float64) + 0.5) * ((el_hi - el_lo) / height)
+    ca, sa = np.cos(np.float64(az_start)), np.sin(np.float64(az_start))
+    Rs = np.asarray(R_sensor, np.float64).reshape(3, 3)
+    Rv = np.stack([ca * Rs[:, 0] + sa * Rs[:, 1], ca * Rs[:, 1] - sa * Rs[:, 0], Rs[:, 2]], axis=1)
+    return range_view(t, Rv, col_edge, np.tan(el_edge), np.stack([np.cos(az_beam), np.sin(az_beam)], axis=1),
+                      np.stack([np.cos(el_beam), np.sin(el_beam)], axis=1), near_range)
+
+
+def range_classify(views, images, points, margin, want_pixel=True):
+    """pct_range_classify: (seen_by int32 [n], pixel int32 [n, 2] or None) -- the lowest view whose scan sees each planner point
+    through (or -1), and the point's pixel (c, r) in the LAST view (or -1, -1 when it is not in that image)"""
+    views = list(views)
+    imgs = [depth_image(v, im) for v, im in zip(views, images)]
+    if len(imgs) != len(views):
+        raise ValueError("one image per view")
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    varr = (RangeView * max(len(views), 1))(*views)
+    iarr = (C.c_void_p * max(len(views), 1))(*[im.ctypes.data for im in imgs])
+    seen = np.empty(len(p), np.int32)
+    pix = np.empty((len(p), 2), np.int32) if want_pixel else None
+    _chk(lib().pct_range_classify(varr, iarr, len(views), _ptr(p), len(p), float(margin), _ptr(seen), None if pix is None else _ptr(pix)))
+    return seen, pix
+
+
 def _preload_hip_runtime():
     """One HIP runtime per process.  PyTorch-ROCm wheels bundle their own libamdhip64.so (soname
     libamdhip64.so.7, the same as /opt/rocm's); two copies in one process each open the KFD device
@@ -503,6 +586,11 @@ def lib():
         L.pct_cloud_ring_carve_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64)]
         L.pct_cloud_append_depth.argtypes = [vp, C.POINTER(DepthView), vp, C.c_double, C.POINTER(i64), C.POINTER(i64)]
         L.pct_depth_classify.argtypes = [vp, vp, C.c_int32, f64p, i64, C.c_double, vp, vp]
+        L.pct_cloud_ring_carve_range.argtypes = [vp, C.POINTER(RangeView), vp, C.c_double, C.POINTER(i64)]
+        L.pct_cloud_append_range.argtypes = [vp, C.POINTER(RangeView), vp, C.c_double, C.POINTER(i64), C.POINTER(i64)]
+        L.pct_range_classify.argtypes = [vp, vp, C.c_int32, f64p, i64, C.c_double, vp, vp]
+        L.pct_range_pseudo_angle.argtypes = [C.c_double, C.c_double]
+        L.pct_range_pseudo_angle.restype = C.c_double
         L.pct_debug_ring_slot.argtypes = [vp, i64, C.POINTER(C.c_uint32)]
         L.pct_debug_narrow_offsets.argtypes = [i64, i64, i64]
         L.pct_debug_query_bins.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, vp, i64, vp,
@@ -822,6 +910,22 @@ class Cloud:
         img = depth_image(view, image)
         off, kept = C.c_int64(), C.c_int64()
         _chk(lib().pct_cloud_append_depth(self._h, C.byref(view), _ptr(img), float(max_depth), C.byref(off), C.byref(kept)))
+        return off.value, kept.value
+
+    def ring_carve_range(self, view: RangeView, image, margin: float) -> int:
+        """free-space clearing along a lidar's beams (pct_cloud_ring_carve_range): remove every point the range image sees through -- in
+        the image, its pixel finite and strictly farther than the point plus margin; returns the number removed"""
+        img = depth_image(view, image)
+        n = C.c_int64()
+        _chk(lib().pct_cloud_ring_carve_range(self._h, C.byref(view), _ptr(img), float(margin), C.byref(n)))
+        return n.value
+
+    def append_range(self, view: RangeView, image, max_range: float = float("inf")):
+        """un-project the valid pixels of a range image on the device, from the view's direction tables, and append them as append()
+        appends the same points (pct_cloud_append_range); returns (offered = valid pixels, kept = points the window took)"""
+        img = depth_image(view, image)
+        off, kept = C.c_int64(), C.c_int64()
+        _chk(lib().pct_cloud_append_range(self._h, C.byref(view), _ptr(img), float(max_range), C.byref(off), C.byref(kept)))
         return off.value, kept.value
 
     def debug_ring_slot(self, slot: int):

@@ -294,6 +294,46 @@ def run_rgbd_window_scenario(window, render, frames=6, carve=True, images=None, 
     return out
 
 
+# ---- the same window seen by a lidar: a 90 degree sector scan of the wall and of the obstacle that leaves ---------------------------
+# sensor axes = world axes (x azimuth 0, y azimuth +90 degrees, z up); the sector starts at azimuth -45 degrees, which
+# engine.range_view_uniform folds into the view's R so that azimuth 0 is the sector's lower edge, not inside its span
+LIDAR_SCAN = dict(width=64, height=48, az_start_deg=-45.0, az_span_deg=90.0, el_lo_deg=-33.0, el_hi_deg=33.0, near_range=0.05)
+
+
+def lidar_range_view():
+    """the scenario's pct_range_view (engine.RangeView) with its four tables"""
+    from . import engine
+    g = LIDAR_SCAN
+    rad = np.pi / 180.0
+    return engine.range_view_uniform((0.0, 0.0, 0.0), np.eye(3), g["az_start_deg"] * rad, g["az_span_deg"] * rad, g["el_lo_deg"] * rad,
+                                     g["el_hi_deg"] * rad, g["width"], g["height"], g["near_range"])
+
+
+def run_lidar_range_window_scenario(window, render, frames=6, carve=True, images=None, each=None):
+    """run_rgbd_window_scenario with a lidar for a sensor: every frame the sensor hands over a range image of the same scene
+    (render(view, points) -> float32 [height, width], the nearest return per beam cell, +inf where none: a test-side renderer), and
+    the window takes it as clearSeenThroughRange(view, image, margin) then appendRangeImage(view, image) with de-dup on -- carve
+    first, then append.  `window` is a SafeRegionRrtStar with its rolling map and setRollingDedup on, or anything with the same two
+    members and live_set().  Returns the live set after every frame, as run_rgbd_window_scenario does."""
+    view = lidar_range_view()
+    out = []
+    for k in range(frames):
+        image = render(view, rgbd_scene(k))
+        if images is not None:
+            images.append(image)
+        if carve:
+            window.clearSeenThroughRange(view, image, RGBD["margin"])
+        window.appendRangeImage(view, image, float("inf"))
+        if hasattr(window, "live_set"):
+            out.append(window.live_set())
+        else:
+            _, _, xyz = window.cloud().radius_crop((0.0, 0.0, 0.0), 1.0e4)
+            out.append(set(map(tuple, xyz.tolist())))
+        if each is not None:
+            each(k, window)
+    return out
+
+
 # ---- the rgbd window with a noisy sensor: speckle pixels in free space, withdrawn by the radius rule in the frame that brought them ----
 # Every frame `speckles` pixels of the image read `depth` metres in front of the wall instead of what is there.  The pixels come from a
 # fixed list -- a lattice with a pitch of 8 pixels that starts 4 pixels off the border, walked with a stride coprime to its length -- so
