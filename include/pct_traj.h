@@ -10,10 +10,13 @@
  *   pct_traj_nearest_voxels     to_nearest_traj            Planner/src/traj_postprocessing.cpp:59-90
  *   pct_traj_end_yaws         to_poly_traj's yaw block     Planner/src/traj_postprocessing.cpp:152-179
  *
- * Arithmetic: fp64 in the reference's accumulation order, no FMA; pow() is the device library's, which can differ from
- * glibc's in the last ulp (positions are held to 1e-12 relative by the tests, everything discrete -- sample counts,
- * segment index, voxel keys away from rounding boundaries -- exactly).  The sequential `len -= step` loops run on the
- * host over the step lengths the kernel produced, in the reference's order.  Orders up to 12 (binomial_coefs.h:11 holds
+ * Arithmetic: fp64, one rounding per operation of the reference in the reference's order, no contraction.  The powers u^j
+ * and (1 - u)^(n - j) come from pct::pow_uint_cr (csrc/bernstein.hpp), which is correctly rounded, so every output --
+ * the nine state sums, sample positions, step lengths (fp64 sqrt is correctly rounded too), and with them the segment
+ * index, the sample counts and the voxel keys -- is held BIT FOR BIT to the exact-power model of
+ * tests/helpers/traj_exact_model.py (tests/test_gpu_traj_exact.py); glibc's pow, which the reference calls, differs
+ * from that model in the last bit on about 1 % of the samples.  The sequential `len -= step` loops run on the host over
+ * the step lengths the kernel produced, in the reference's order.  Orders up to 12 (binomial_coefs.h:11 holds
  * MAX_N = 13 rows).  Not thread-safe (one workspace per process), like the rest of the library.
  */
 #ifndef PCT_TRAJ_H

@@ -13,7 +13,8 @@
  * INPUT order wins), so the voxel cloud is identical to the sequential container's, element by element.
  *
  * Differences from the reference: voxel coordinates must lie in [-2^20, 2^20) per axis (+-104 km at res = 0.1; the three
- * of them are packed into one 64-bit hash key) -- anything outside is rejected with PCT_ERR_INVALID and nothing is added;
+ * of them are packed into one 64-bit hash key) -- a point outside it, or with a NaN or infinite coordinate, is SKIPPED
+ * (is_new = 0, voxel_index = -1), the other points of the batch are added as usual, and the call returns PCT_ERR_INVALID;
  * at most 2^31 voxels per map.  Status codes and pct_last_error() are those of pct_engine.h; pct_init() must have run.
  */
 #ifndef PCT_VOXEL_H

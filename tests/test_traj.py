@@ -4,7 +4,9 @@ PolynomialTrajectoryExtra, the 1001-samples-per-segment walks of traj_postproces
 CPU part: the oracle restatement (oracle/traj_port.c) against properties that do not depend on it (the already pinned
 position evaluator, finite differences, Bezier end-point interpolation, monotonicity).
 GPU part: traj.hip through include/pct_traj.h against the oracle -- discrete results exactly, positions to 1e-12 relative
-(device pow vs glibc pow).  PARITY UNPINNED against the reference itself (Eigen/roscpp absent)."""
+(the bar these tests arrived with, when the powers were the device library's pow; the kernels now take them from the correctly rounded
+pow_uint_cr, and what is left against the oracle is glibc's pow).  PARITY UNPINNED against the reference itself (Eigen/roscpp absent).
+The bit-for-bit checks against an exact-power model, at the edges, are in tests/test_traj_exact_model.py and tests/test_gpu_traj_exact.py."""
 import os
 import re
 import subprocess

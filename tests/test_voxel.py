@@ -3,7 +3,8 @@
 CPU part: the oracle's sequential restatement (oracle/voxel_port.c) against an independent numpy formulation.
 GPU part: the HIP path (voxel.hip through include/pct_voxel.h) against the oracle, element by element: voxel order,
 integer coordinates, float and double centres, per-point add_point results and voxel_value_map indices.
-PARITY UNPINNED against the reference itself (voxel_map.cpp needs PCL/Eigen, absent; the reference holds no fixture)."""
+PARITY UNPINNED against the reference itself (voxel_map.cpp needs PCL/Eigen, absent; the reference holds no fixture).
+Ties, the key range, rank tiles, probe chains and read windows are in tests/test_voxel_exact_model.py and tests/test_gpu_voxel_edges.py."""
 import os
 import sys
 
