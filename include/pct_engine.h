@@ -765,7 +765,11 @@ int pct_debug_query_bins(const int32_t dims[3], const float origin[3], float inv
                          uint32_t *bins, uint32_t *nbins, int *fast);
 
 /* Build / drop the uniform-cell index used by PCT_ALGO_GRID.  cell_size <= 0 picks one from
- * the bounding box and point count (about `pct` points per cell). */
+ * the bounding box and point count (about `pct` points per cell).
+ * The cell has a floor: a cell_size (given or chosen) below max_ext / 1023, max_ext the longest side of the bounding box, is
+ * raised to that value without notice -- in double, before the cell is rounded to float -- so the grid has at most 1024
+ * cells per axis (1023 or 1024 on the longest one, as the rounding falls) and at most 2^30 cells in all.
+ * pct_cloud_grid_info reports the cell actually used, not the one asked for. */
 int pct_cloud_build_grid(pct_cloud *c, float cell_size);
 int pct_cloud_drop_grid(pct_cloud *c);
 int pct_cloud_has_grid(const pct_cloud *c);

@@ -2455,7 +2455,7 @@ int pct_cloud_build_grid(pct_cloud *c, float cell_size)
     if (const char *eb = std::getenv("PCT_BIN_SHIFT")) bin_shift = std::max(0, std::min(4, std::atoi(eb)));
     if (const char *es = std::getenv("PCT_BIN_STRIP")) bin_strip = std::max(1, std::atoi(es));
     c->B = bin_desc_make(G.gx, G.gy, G.gz, G.ox, G.oy, G.oz, G.inv_h, bin_shift, bin_strip);
-    // With at most 1025 cells per axis (above) every grid built here takes the multiply-free form; PCT_BIN_FORM=0 (read at every
+    // With at most 1024 cells per axis (above) every grid built here takes the multiply-free form; PCT_BIN_FORM=0 (read at every
     // build) selects the generic one, which is otherwise out of the tests' reach on the card.
     if (const char *ef = std::getenv("PCT_BIN_FORM")) if (std::atoi(ef) == 0) c->B.fast = 0;
     c->has_grid = true;

@@ -8,8 +8,10 @@ block with one live group, with one whole wave idle, with a single query.  Every
 brute force (ALGO_STREAM_EXACT) on one cloud of 20,000 points, indexed once per block size: indices and fp64 squared distances, bit
 for bit, as in test_gpu_stage0_tails.py.
 
-Not covered here or anywhere: the kernel's wide instantiation (64-bit addresses), which needs arrays beyond 4 GB and has no switch; its
-block sizes are the same two and its static figures are in profiles/nn_persist_asm.txt.
+Not covered here: the kernel's wide instantiation (64-bit addresses), which needs arrays beyond 4 GB and has no switch.  A grid of 2^30
+cells has such an array (2^30 + 1 run bounds), and test_gpu_grid_limits.py runs the wide form there at both block sizes; the other two
+ways into it (more than 2^28 - 16 points, more than 2^28 queries) stay out of the tests' reach.  Its static figures are in
+profiles/nn_persist_asm.txt.
 """
 import os
 

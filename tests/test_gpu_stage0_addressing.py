@@ -6,10 +6,12 @@ distances, bit for bit.  The class of input a test is about is counted on the CP
 count is asserted.  The sparse hand-made clouds are built with PCT_PYRAMID=0 (read at every build): left alone, the engine would give
 them the pyramid walk, and these tests are about the dense kernel.
 
-Not covered here or anywhere: the kernel's wide instantiation (nn_grid_coop_kernel<., false>, 64-bit addresses), which the engine launches
-only for clouds of more than 2^28 - 16 points, grids of 2^30 cells or batches beyond 2^28 queries -- sizes no test can afford.  It shares the
-wrapping clamp and the swizzle folds with the narrow form tested here and keeps the addressing the kernel had before; the choice between the
-two is tested on the host (test_stage0_addressing_host.py).
+Not covered here: the kernel's wide instantiation (nn_grid_coop_kernel<., false>, 64-bit addresses), which the engine launches only for
+clouds of more than 2^28 - 16 points, grids of 2^30 cells or batches beyond 2^28 queries.  The second needs no large cloud -- a bounding
+box of [0, 1023]^3 with unit cells -- and test_gpu_grid_limits.py runs the wide form there, on queries whose run ends at cell_start[2^30],
+and the narrow form on the largest table it is allowed; the other two sizes no test can afford, and they stay uncovered.  The wide form
+shares the wrapping clamp and the swizzle folds with the narrow form tested here and keeps the addressing the kernel had before; the choice
+between the two is tested on the host (test_stage0_addressing_host.py).
 """
 import numpy as np
 import pytest
