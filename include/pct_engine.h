@@ -558,6 +558,39 @@
  * (32 B per piece) and the per-trajectory state are cloud-owned and grown by the call; what it cannot see is treated as there
  * (an unsound trajectory is INVALID; seg_offsets[B] above piece_cap: nothing examined, every sound trajectory OPEN, capped set).
  *
+ * Windows of a trajectory (pct_bezier_certify_window_batch*, pct_bezier_clearance_window_batch*): the two calls above for the part of
+ * each trajectory with time in [t0, t1] -- "is it safe from now for the next check_time seconds?" -- instead of whole curves.  The
+ * whole-curve forms are unchanged and still do not read t_start.  Input: as there, plus horizon (B doubles, NULL = +inf for all);
+ * batch->t_start IS read here (NULL = 0 for every trajectory).  All arithmetic is fp64, one rounding per operation, no contraction,
+ * in the order given here.  (1) Window: t0 = t_start[b]; t1 = t0 + horizon[b], one addition (a horizon of +inf gives +inf).  A
+ * trajectory is INVALID, with nothing examined, if t0 is not finite or < 0, or if horizon is NaN or not > 0; otherwise it is subject
+ * to the INVALID rule of "Certified Bezier check" over ALL its segments, inside the window or not.  (2) Per segment: c = 0 at the
+ * trajectory's first segment, cn = c + T_i, then c = cn (sequential sums).  Segment i is in the window iff t0 < cn && t1 > c; then
+ * u0 = (t0 <= c) ? 0 : (t0 - c) / T_i and u1 = (t1 >= cn) ? 1 : (t1 - c) / T_i, and the segment drops out if !(u0 < u1).  The
+ * comparisons come before the divisions, so a covered end is exactly 0 or 1.  (3) Restriction of the world polygon P of step (1)
+ * there: if u1 < 1, cut at t = u1 and keep the left part; then, if u0 > 0, cut at t = u0 / u1 (one division) and keep the right
+ * part.  A cut is level by level q[i] = w * p[i] + t * p[i+1] with w = 1 - t computed once (two products, one sum); the left part is
+ * the first point of every level, the right part the last point of every level, reversed.  A segment with u0 == 0 && u1 == 1 is not
+ * cut at all: its first piece is byte for byte the whole-curve form's.  (4) First pieces: slot = segment, as there; a segment outside
+ * the window, or dropped in (2), is a dead slot.  Rounds, halving, geometry, hit rule, piece_cap rule, fold order, retirement and
+ * statuses are exactly those of the two contracts above.  (5) Reporting: hit_seg / at_seg stay indices into the packed batch;
+ * hit_u / at_u are in the segment's own parameter: with v = (k + end) / 2^d, u = (1 - v) * u0 + v * u1 -- v itself for an uncut
+ * segment, u0 at v = 0, u1 at v = 1; pieces, depth, min_d2 and stats count what was examined.  (6) Empty window: t0 at or past the
+ * trajectory's end has no piece: FREE (DONE for the clearance), depth = pieces = 0, min_d2 = hi = lo = +inf and the "nowhere" hit
+ * fields -- the answer of the sampled check's "no sample at all".  (7) What FREE and lo prove: the statements above for the points of
+ * the curve with u in [u0, u1] of every segment the window touches, u0 and u1 as computed in (2).  The restriction adds roundings to
+ * the inherited error: a cut rounds three times per value and w + t misses 1 by up to 2^-54, 84 * 2^-53 * M0 over two cuts of up to
+ * 12 levels, and the rounding of u0 / u1 moves the first piece by at most 24 * 2^-53 * M0 -- 108 * 2^-53 * M0 for the restriction,
+ * and with the halvings' 240 * 2^-53 * M0 at most 348 * 2^-53 * M0 < 0.68 * 2^-44 * M0, no longer under 2^-45 * M0.  The slack terms
+ * stay as they are (reach and L are unchanged) and cover it when the piece's own cmax >= M0 / 16, and otherwise when
+ * margin + rho >= 2^-24 * M0 (60 micrometres per kilometre of coordinate; the whole-curve form asks 2^-25) -- for the clearance when
+ * da + db + ell + rho >= 2^-24 * M0, the whole-curve condition.  Below that no claim is made.  The argument stands beside
+ * bc_seed_window_kernel in csrc/bezier_certify.hpp.  Refusals, the empty cloud, B == 0, the capture rules, the overrun paragraph and
+ * piece_cap versus seg_offsets[B] follow the whole-curve forms (piece_cap counts all segments of the batch, inside a window or not);
+ * a non-NULL horizon or t_start is not read by a refused call, and nothing is written.  Host form: t_start and horizon are host
+ * arrays.  Device form: device arrays; win[segment] = {u0, u1} (16 B per slot, piece_cap slots) is cloud-owned and grown by the call,
+ * which is refused during graph capture (call once with the same sizes first).
+ *
  * All entry points need a HIP device; there is no host fallback.
  */
 #ifndef PCT_ENGINE_H
@@ -1014,6 +1047,15 @@ typedef struct pct_traj_clearance {   /* 48 bytes */
 int pct_bezier_clearance_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double tol, double cap, int32_t max_depth, int64_t piece_cap,
                                pct_traj_clearance *out /* B */, int64_t stats[3] /* {rounds, pieces, capped}; may be NULL */);
 
+/* The two calls above for the window [t_start[b], t_start[b] + horizon[b]] of each trajectory (contract: top of this file, "Windows of
+ * a trajectory"): batch->t_start IS read (NULL = 0 for all); horizon: B doubles, NULL = +inf for all.  hit_u / at_u are in the
+ * segment's own parameter. */
+int pct_bezier_certify_window_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, const double *horizon /* B, or NULL */, double margin,
+                                    int32_t max_depth, int64_t piece_cap, pct_traj_certificate *cert /* B */, int64_t stats[3] /* may be NULL */);
+int pct_bezier_clearance_window_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, const double *horizon /* B, or NULL */, double tol,
+                                      double cap, int32_t max_depth, int64_t piece_cap, pct_traj_clearance *out /* B */,
+                                      int64_t stats[3] /* may be NULL */);
+
 /* Control-point check (SURVEY.md 3.3, config C5's build extension): the threshold test of checkTrajPtCol
  * (Planner/src/corridor_finder.cpp:412-416) applied to the raw control points of the committed trajectory in world units --
  * control point j of segment i is polycoef[i][d*(n+1)+j] * seg_time[i] (layout Planner/src/traj_optimizer.cpp:739-751), the
@@ -1072,6 +1114,13 @@ int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch 
 int pct_bezier_clearance_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields /* struct on the host, its pointers on the device */,
                                    double tol, double cap, int32_t max_depth, int64_t piece_cap, pct_traj_clearance *d_out, int64_t *d_stats,
                                    void *stream);
+/* The window forms on device buffers ("Windows of a trajectory"): d_batch_fields->t_start and d_horizon are device arrays of B doubles
+ * or NULL.  Reservation, stream and capture as for the two calls above. */
+int pct_bezier_certify_window_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, const double *d_horizon, double margin,
+                                        int32_t max_depth, int64_t piece_cap, pct_traj_certificate *d_cert, int64_t *d_stats, void *stream);
+int pct_bezier_clearance_window_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, const double *d_horizon, double tol,
+                                          double cap, int32_t max_depth, int64_t piece_cap, pct_traj_clearance *d_out, int64_t *d_stats,
+                                          void *stream);
 /* Exchange step of a sharded cloud (one process per GPU): between all_reduce(min) on the squared distances and all_reduce(min) on
  * the indices, a rank offers its global index only where its own d2 equals the reduced minimum (and is finite), INT32_MAX
  * elsewhere -- so the second reduction returns the lowest global index among the ranks that tie.  Device pointers, async on

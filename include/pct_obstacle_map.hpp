@@ -659,6 +659,70 @@ public:
         return rec[0];
     }
 
+    // The two checks above for a time window of each candidate (pct_engine.h, paragraph "Windows of a trajectory"): candidate b is
+    // examined for t in [t_start[b], t_start[b] + horizons[b]] -- candidates.t_start IS read here (NULL: 0 for all), horizons holds B
+    // values or is NULL (+inf for all).  A part already flown or beyond the horizon neither collides nor enters the bracket; hit_u /
+    // at_u are in the segment's own parameter; a window at or past the end of a candidate is FREE / DONE with no piece examined.
+    // Everything else, the return values included, as certifyTrajectories and trajectoryClearances.
+    int64_t certifyTrajectoryWindows(const pct_bezier_batch &candidates, const double *horizons, std::vector<pct_traj_certificate> &certificates,
+                                     int max_depth = 12, int64_t piece_cap = 0, int64_t *stats = nullptr)
+    {
+        const int64_t B = candidates.B > 0 ? candidates.B : 0;
+        certificates.resize((size_t)B);
+        if (piece_cap <= 0) {
+            const int64_t nseg = B > 0 && candidates.seg_offsets ? candidates.seg_offsets[B] : 0;
+            piece_cap = 64 * nseg > 4096 ? 64 * nseg : 4096;
+        }
+        check(pct_bezier_certify_window_batch(cloud_, PCT_ALGO_AUTO, &candidates, horizons, prm_.search_margin, max_depth, piece_cap,
+                                              certificates.data(), stats),
+              "pct_bezier_certify_window_batch");
+        int64_t not_free = 0;
+        for (const pct_traj_certificate &v : certificates) not_free += v.status != PCT_CERT_FREE ? 1 : 0;
+        return not_free;
+    }
+    int64_t trajectoryClearanceWindows(const pct_bezier_batch &candidates, const double *horizons, std::vector<pct_traj_clearance> &clearances,
+                                       double tol, double cap = std::numeric_limits<double>::infinity(), int max_depth = 16,
+                                       int64_t piece_cap = 0, int64_t *stats = nullptr)
+    {
+        const int64_t B = candidates.B > 0 ? candidates.B : 0;
+        clearances.resize((size_t)B);
+        if (piece_cap <= 0) {
+            const int64_t nseg = B > 0 && candidates.seg_offsets ? candidates.seg_offsets[B] : 0;
+            piece_cap = 64 * nseg > 4096 ? 64 * nseg : 4096;
+        }
+        check(pct_bezier_clearance_window_batch(cloud_, PCT_ALGO_AUTO, &candidates, horizons, tol, cap, max_depth, piece_cap, clearances.data(),
+                                                stats),
+              "pct_bezier_clearance_window_batch");
+        int64_t not_done = 0;
+        for (const pct_traj_clearance &v : clearances) not_done += v.status != PCT_CLR_DONE ? 1 : 0;
+        return not_done;
+    }
+    // The tick's question, the arguments of checkSafeTrajectory: is the committed trajectory safe from t_now for the next check_time
+    // seconds?  True unless that window is certified free (the reference's sense: true = do not fly it); an obstacle beside the part
+    // already flown, or beyond the horizon, does not force a replan.  certificate (optional) receives the details.
+    bool certifySafeTrajectoryFrom(const double *poly_coeff, int64_t row_stride, const double *seg_time, const int32_t *orders,
+                                   int32_t segment_num, double t_now, double check_time, pct_traj_certificate *certificate = nullptr,
+                                   int max_depth = 12)
+    {
+        const int32_t seg_offsets[2] = { 0, segment_num };
+        const pct_bezier_batch one{ poly_coeff, row_stride, seg_time, orders, seg_offsets, &t_now, 1 };
+        std::vector<pct_traj_certificate> cert;
+        const int64_t not_free = certifyTrajectoryWindows(one, &check_time, cert, max_depth);
+        if (certificate) *certificate = cert[0];
+        return not_free != 0;
+    }
+    // The same window's clearance record
+    pct_traj_clearance trajectoryClearanceFrom(const double *poly_coeff, int64_t row_stride, const double *seg_time, const int32_t *orders,
+                                               int32_t segment_num, double t_now, double check_time, double tol,
+                                               double cap = std::numeric_limits<double>::infinity(), int max_depth = 16)
+    {
+        const int32_t seg_offsets[2] = { 0, segment_num };
+        const pct_bezier_batch one{ poly_coeff, row_stride, seg_time, orders, seg_offsets, &t_now, 1 };
+        std::vector<pct_traj_clearance> rec;
+        trajectoryClearanceWindows(one, &check_time, rec, tol, cap, max_depth);
+        return rec[0];
+    }
+
     // Corridor -> trajectory -> proof in one call: generate one candidate per time scale (generateTrajectories above; limits carries
     // max_vel / max_acc and the iteration budget, its margin is replaced by `margin`, what is taken off every sphere radius), certify all
     // of them against this map (certifyTrajectories: search_margin of setParam) and return the index of the shortest-duration candidate

@@ -172,6 +172,16 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
 
+    win_src = os.path.join(ROOT, "examples", "bezier_window.cpp")
+    win_bin = os.path.join(LIB, "bezier_window")
+    if os.path.exists(win_src) and os.path.exists(ENGINE_SO) and (force or _stale(win_bin, [win_src, ENGINE_SO] + hdrs + [os.path.join(ROOT, "include", "pct_obstacle_map.hpp")])):
+        # ObstacleMap::certifySafeTrajectoryFrom / certifyTrajectoryWindows / trajectoryClearanceFrom: the tick's window on a 3 m line; needs the engine alone
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-o", win_bin, win_src,
+               "-L" + LIB, "-lpct_engine", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link," + LIB, "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+
     gen_src = os.path.join(ROOT, "examples", "trajectory_generate.cpp")
     gen_bin = os.path.join(LIB, "trajectory_generate")
     if os.path.exists(gen_src) and os.path.exists(ENGINE_SO) and (force or _stale(gen_bin, [gen_src, ENGINE_SO] + hdrs + [os.path.join(ROOT, "include", "pct_obstacle_map.hpp")])):

@@ -7,6 +7,10 @@
 //   bc_init_kernel      a lane per trajectory: the certificate's defaults, the trajectory's state, the call's control words
 //   bc_valid_kernel     a lane per segment: a bad seg_time or a world control point beyond FLT_MAX marks its trajectory INVALID
 //   bc_seed_kernel      a lane per segment: the world control points P[j] = c[j] * T as the piece of depth 0 at slot = segment
+//   -- the window forms (pct_bezier_*_window_batch*, paragraph "Windows of a trajectory") put in the place of bc_seed_kernel --
+//   bc_window_kernel    a lane per segment: u0, u1 of its part of [t0, t1] into win[segment], NaN for a segment outside the window;
+//                       behind them a lane per trajectory: a bad t0 or horizon marks it INVALID
+//   bc_seed_window_kernel  a lane per segment: bc_seed_kernel's polygon restricted to [u0, u1] by up to two de Casteljau cuts
 //   -- per round --
 //   bc_geometry_kernel  a lane per piece: chord ends a, b (fp32), rho, reach, and the three queries it poses: the capsule
 //                       (a, b, reach) and the two nearest-neighbour queries a and b; a dead slot poses NaN queries, which the
@@ -51,6 +55,19 @@
 //     margin + rho >= 2^-25 * M0 -- 30 micrometres of margin per kilometre of |coordinate|.  Under that condition FREE is a proof:
 //     no row of the window lies within `margin` of any point of the curve.  Below it (a margin of nanometres on kilometre
 //     coordinates) the slack of the contract does not cover E for such pieces, and no claim is made.
+// (5) Windows (bc_seed_window_kernel).  A first piece that was cut stands for u in [u0, u1] of its segment, u0 and u1 as bc_window_kernel
+//     computed them: the window IS that interval (t0, t1 and the segment's time enter through one rounded subtraction, division and
+//     the sequential sums).  A cut at t computes q = w * p + t * p' with w = 1 - t rounded once: two products and a sum, each off by
+//     at most 2^-53 of a value that is at most M0 in magnitude, and w + t differs from 1 by at most 2^-54: 3.5 * 2^-53 * M0 per
+//     level, 12 levels, two cuts: 84 * 2^-53 * M0.  The second cut is at t = u0 / u1 rounded, so the right part starts at
+//     u0' = t * u1, within 2^-53 of u0; every control point of a restriction is a value of the segment's blossom, which moves by
+//     at most 2 * M0 per unit of each of its n <= 12 arguments: another 24 * 2^-53 * M0, and a curve point with u between u0 and u0'
+//     is that near the piece's own end.  Together the stored first piece is within 108 * 2^-53 * M0 of the exact restriction, and
+//     with the halvings of (4) E <= 348 * 2^-53 * M0 < 0.68 * 2^-44 * M0.  That no longer fits under 2^-45 * M0.  The spare of (3)
+//     still covers it when cmax >= M0 / 16 (cmax * (2^-40 - 2^-45) >= 0.96 * 2^-44 * M0), and otherwise when
+//     margin + rho >= 2^-24 * M0 -- 60 micrometres per kilometre of |coordinate|, twice the whole-curve condition.  Under it FREE
+//     of a window form is a proof for the points of the curve with u in [u0, u1] of every segment the window touches.  reach itself
+//     is unchanged.  A segment the window covers whole is not cut and keeps (4) as it stands.
 // HIT needs no argument: the end of a piece is a point the sampled check could have sampled, judged by its test.
 #pragma once
 #include "../../include/pct_engine.h"
@@ -182,6 +199,109 @@ __global__ __launch_bounds__(256) void bc_seed_kernel(BcDesc D, long long piece_
     meta[i] = BcMeta{ (int32_t)b, (int32_t)i, n, 0u };
 }
 
+// ---- windows of a trajectory (pct_engine.h, "Windows of a trajectory") --------------------------------------------------------------
+// what the window forms read beside the batch: device pointers, t_start and horizon B doubles each or NULL (0 and +inf for all), and
+// win[segment] = {u0, u1}, the part of the segment inside its trajectory's window, u0 = NaN for a segment with none
+struct BcWinDesc {
+    const double *t_start;
+    const double *horizon;
+    double *win;
+};
+
+// the window [t0, t1) of trajectory b as the contract's step 1 has it; false: the trajectory is INVALID
+__device__ __forceinline__ bool bc_window_of(const BcWinDesc &W, long long b, double &t0, double &t1)
+{
+    t0 = W.t_start ? W.t_start[b] : 0.0;
+    const double h = W.horizon ? W.horizon[b] : __builtin_huge_val();
+    t1 = t0 + h;
+    return t0 >= 0.0 && t0 <= 1.7976931348623157e308 && h > 0.0;
+}
+
+// lane i < total_seg: win[i], behind bc_valid_kernel (a trajectory that is INVALID already has only dead slots, and its times are not
+// summed).  Lane seg_lanes + b, b < B: the window's own INVALID rule.
+__global__ __launch_bounds__(256) void bc_window_kernel(BcDesc D, BcWinDesc W, long long piece_cap, long long seg_lanes, BcTraj *__restrict__ traj)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    double t0, t1;
+    if (i >= seg_lanes) {
+        const long long b = i - seg_lanes;
+        if (b < D.B && !bc_window_of(W, b, t0, t1)) atomicOr(&traj[b].flags, kBcInvalid);
+        return;
+    }
+    if (i >= bc_total_seg(D, piece_cap)) return;
+    double *w = W.win + 2 * (size_t)i;
+    w[0] = w[1] = __builtin_nan("");
+    const long long b = bc_owner(D, (int)i);
+    if (b < 0 || traj[b].flags != 0 || !bc_window_of(W, b, t0, t1)) return;
+    double c = 0.0;
+    for (int s = D.seg_offsets[b]; s < (int)i; s++) c = c + D.seg_time[s];
+    const double T = D.seg_time[i], cn = c + T;
+    if (!(t0 < cn && t1 > c)) return;
+    const double u0 = t0 <= c ? 0.0 : (t0 - c) / T;
+    const double u1 = t1 >= cn ? 1.0 : (t1 - c) / T;
+    if (!(u0 < u1)) return;
+    w[0] = u0;
+    w[1] = u1;
+}
+
+// One de Casteljau cut of p[0..n] at t, level by level q[i] = w * p[i] + t * p[i + 1] with w = 1 - t, in place: what is left in p[] is
+// the right part (the last point of every level, reversed); the left part (p[0] of every level) replaces it unless `right`.
+// Constant bounds, unrolled: p[] and l[] are registers and n only predicates, as in bc_split_kernel.
+__device__ __forceinline__ void bc_cut(double (&p)[kBcPts], int n, double t, bool right)
+{
+    const double w = 1.0 - t;
+    double l[kBcPts];
+    l[0] = p[0];
+#pragma unroll
+    for (int lev = 1; lev < kBcPts; lev++) {
+#pragma unroll
+        for (int i = 0; i + lev < kBcPts; i++)
+            if (i + lev <= n) p[i] = w * p[i] + t * p[i + 1];
+        l[lev] = p[0];
+    }
+    if (!right) {
+#pragma unroll
+        for (int j = 0; j < kBcPts; j++) p[j] = l[j];
+    }
+}
+
+// lane i < total_seg: bc_seed_kernel's piece restricted to [u0, u1] = win[i]: cut at u1 and keep the left part, then cut at u0 / u1
+// and keep the right part; an end the window covers (u1 == 1, u0 == 0) is not cut, so a segment inside the window gets bc_seed_kernel's
+// bytes.  A segment outside the window is a dead slot.
+__global__ __launch_bounds__(256) void bc_seed_window_kernel(BcDesc D, long long piece_cap, const BcTraj *__restrict__ traj,
+                                                             const double *__restrict__ win, double *__restrict__ poly, BcMeta *__restrict__ meta)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= bc_total_seg(D, piece_cap)) return;
+    const long long b = bc_owner(D, (int)i);
+    const double u0 = win[2 * (size_t)i], u1 = win[2 * (size_t)i + 1];
+    if (b < 0 || traj[b].flags != 0 || !(u0 < u1)) { meta[i] = BcMeta{ -1, 0, 0, 0 }; return; }
+    const int n = D.orders[i], m = n + 1;
+    const double T = D.seg_time[i];
+    const double *c = D.coef + (size_t)i * D.row_stride;
+    double *dst = poly + (size_t)i * kBcPoly;
+    const double t = u0 / u1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        double p[kBcPts];
+#pragma unroll
+        for (int j = 0; j < kBcPts; j++) p[j] = j <= n ? c[k * m + j] * T : 0.0;
+        if (u1 < 1.0) bc_cut(p, n, u1, false);
+        if (u0 > 0.0) bc_cut(p, n, t, true);
+#pragma unroll
+        for (int j = 0; j < kBcPts; j++)
+            if (j <= n) dst[3 * j + k] = p[j];
+    }
+    meta[i] = BcMeta{ (int32_t)b, (int32_t)i, n, 0u };
+}
+
+// the parameter v of a piece end inside its first piece -> the segment's own u (step 5 there): v itself for an uncut segment
+__device__ __forceinline__ double bc_window_u(const double *__restrict__ win, int seg, double v)
+{
+    const double u0 = win[2 * (size_t)seg], u1 = win[2 * (size_t)seg + 1];
+    return (1.0 - v) * u0 + v * u1;
+}
+
 // Step (4) of the contract for the polygon p of order n: the chord ends narrowed to fp32 into q[0..5] (a, then b) and widened into
 // ends[0..5], rho = the largest distance of a control point from segment (a, b), cmax = the largest |coordinate|.  The certified
 // check and the clearance (bezier_clearance.hpp) both take their geometry from here.
@@ -253,11 +373,13 @@ __global__ __launch_bounds__(256) void bc_classify_kernel(const BcMeta *__restri
 }
 
 // One tile of kBcTile slots per block, behind bc_classify_kernel.  flag in: blocked; flag out: 1 + the rank of a splitting piece inside
-// its tile, 0 for every other slot; tile_sum[block] = the tile's splitting pieces.
+// its tile, 0 for every other slot; tile_sum[block] = the tile's splitting pieces.  kWindow: hit_u goes through win[] (the window forms).
+template <bool kWindow>
 __global__ __launch_bounds__(kBcTile) void bc_mark_kernel(const BcMeta *__restrict__ meta, const BcCtl *__restrict__ ctl, uint32_t nslots, int round,
                                                           int max_depth, const uint32_t *__restrict__ nn_idx, const double *__restrict__ nn_d2,
                                                           pct_traj_certificate *__restrict__ cert, BcTraj *__restrict__ traj,
-                                                          uint32_t *__restrict__ flag, uint32_t *__restrict__ tile_sum)
+                                                          uint32_t *__restrict__ flag, uint32_t *__restrict__ tile_sum,
+                                                          const double *__restrict__ win)
 {
     const uint32_t slot = blockIdx.x * kBcTile + threadIdx.x;
     uint32_t split = 0;
@@ -270,7 +392,8 @@ __global__ __launch_bounds__(kBcTile) void bc_mark_kernel(const BcMeta *__restri
                 cert[M.traj].hit_seg = M.seg;
                 cert[M.traj].hit_idx = nn_idx[key];
                 cert[M.traj].hit_d2 = nn_d2[key];
-                cert[M.traj].hit_u = ldexp((double)(M.k + end), -round);
+                const double v = ldexp((double)(M.k + end), -round);
+                cert[M.traj].hit_u = kWindow ? bc_window_u(win, M.seg, v) : v;
             }
         } else if (flag[slot]) {
             if (round >= max_depth) atomicOr(&traj[M.traj].flags, kBcUndecided);

@@ -7,7 +7,7 @@
 // from above, and L below bounds it from below on the piece.  A piece whose L is within tol of hi (or beyond cap) retires; the others
 // are halved.  No capsule search is involved, so every index that answers a nearest-neighbour batch serves the call.
 //   cl_init_kernel      a lane per trajectory: the record's defaults, the trajectory's state, the call's control words
-//   bc_valid_kernel, bc_seed_kernel (bezier_certify.hpp)
+//   bc_valid_kernel, bc_seed_kernel (bezier_certify.hpp); the window forms: bc_window_kernel and bc_seed_window_kernel in the seed's place
 //   -- per round --
 //   cl_geometry_kernel  a lane per piece: a, b (fp32) as the two queries, and ell, rho, cmax into the piece scalars; a dead slot poses
 //                       NaN queries
@@ -47,6 +47,10 @@
 //     Under that condition lo is a proof: no point of the curve is nearer than lo to any row of the window.  Below it (a piece
 //     within micrometres of a row and far nearer the origin than its curve reaches) L is itself below 2^-25 * M0 and may exceed
 //     the truth by at most E; no claim is made there.
+// (4) Windows.  A first piece cut by bc_seed_window_kernel adds to E as (5) of bezier_certify.hpp counts it: E <= 348 * 2^-53 * M0
+//     < 0.68 * 2^-44 * M0.  The spare of (2) covers that under the same condition as (3): cmax >= M0 / 16 gives
+//     cmax * (2^-40 - 2^-47) >= 0.99 * 2^-44 * M0, and da + db + ell + rho >= 2^-24 * M0 gives (2^-20 - 2^-48) * 2^-24 * M0.  lo of a
+//     window form is then a proof for the points with u in [u0, u1] of every segment the window touches.  L is unchanged.
 // hi needs no argument: it is the distance the sampled check would measure at a point it could have sampled (an end of a piece,
 // a curve point rounded to fp32).
 // The slack is about 2^-20 of twice the distance: a tol below ~ 2 * d * 1e-6 cannot be met and ends OPEN at max_depth.
@@ -148,12 +152,15 @@ __global__ __launch_bounds__(256) void cl_attain_kernel(const BcMeta *__restrict
 }
 
 // One tile of kBcTile slots per block, behind cl_attain_kernel.  flag out: 1 + the rank of a splitting piece inside its tile, 0 for
-// every other slot; tile_sum[block] = the tile's splitting pieces; geom[.][3] = L of a splitting piece.
+// every other slot; tile_sum[block] = the tile's splitting pieces; geom[.][3] = L of a splitting piece.  kWindow: at_u goes through
+// win[] (the window forms, bc_window_u).
+template <bool kWindow>
 __global__ __launch_bounds__(kBcTile) void cl_mark_kernel(const BcMeta *__restrict__ meta, const BcCtl *__restrict__ ctl, uint32_t nslots, int round,
                                                           int max_depth, double tol, double cap, const uint32_t *__restrict__ nn_idx,
                                                           const double *__restrict__ nn_d2, double *__restrict__ geom,
                                                           pct_traj_clearance *__restrict__ out, BcTraj *__restrict__ traj, ClTraj *__restrict__ st,
-                                                          uint32_t *__restrict__ flag, uint32_t *__restrict__ tile_sum)
+                                                          uint32_t *__restrict__ flag, uint32_t *__restrict__ tile_sum,
+                                                          const double *__restrict__ win)
 {
     const uint32_t slot = blockIdx.x * kBcTile + threadIdx.x;
     uint32_t split = 0;
@@ -165,7 +172,8 @@ __global__ __launch_bounds__(kBcTile) void cl_mark_kernel(const BcMeta *__restri
             const uint32_t end = key & 1u;
             out[M.traj].at_seg = M.seg;
             out[M.traj].at_idx = nn_idx[key];
-            out[M.traj].at_u = ldexp((double)(M.k + end), -round);
+            const double v = ldexp((double)(M.k + end), -round);
+            out[M.traj].at_u = kWindow ? bc_window_u(win, M.seg, v) : v;
             st[M.traj].u2_seen = u2;
             traj[M.traj].hitkey = kBcNoHit;                   // the next round's offers start afresh
         }

@@ -339,6 +339,8 @@ struct pct_cloud {
     DevBuf<double> cl_geom;
     DevBuf<ClTraj> cl_traj;
     DevBuf<pct_traj_clearance> cl_out;
+    // windows of a trajectory (both calls' window forms): u0, u1 per segment, and the host forms' copies of t_start and horizon
+    DevBuf<double> bc_win, bc_tstart, bc_horizon;
     // measurement
     hipEvent_t ev0 = nullptr, ev1 = nullptr;    // around the whole batch (all kernels of one query call)
     hipEvent_t ev2 = nullptr, ev3 = nullptr;    // around the batch's dominant kernel only (aliases of the ring's current pair)
@@ -2106,6 +2108,7 @@ struct BcRun {
     Path path;                       // of the chord test: resolve_algo(Op::Capsule)
     pct_traj_certificate *cert;      // device memory, B entries
     long long *stats;                // device memory, 3 entries, or NULL
+    BcWinDesc W{};                   // the window forms: W.win != NULL
 };
 
 template <typename T>
@@ -2139,13 +2142,24 @@ int bc_traj_room(pct_cloud *c, int64_t B, hipStream_t s)
 
 // defaults, validity and the pieces of depth 0 in set 0; seg_lanes: the segments (the host form) or piece_cap (the device form, whose
 // lanes guard on seg_offsets[B])
+// behind the init kernel of either call: validity and the pieces of depth 0 in set 0 -- the segments themselves, or (W.win) their
+// parts inside each trajectory's window
+void bc_seed_pieces(pct_cloud *c, const BcDesc &D, const BcWinDesc &W, int64_t piece_cap, int64_t seg_lanes, hipStream_t s)
+{
+    if (seg_lanes > 0) bc_valid_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(D, (long long)piece_cap, c->bc_traj);
+    if (W.win) {
+        bc_window_kernel<<<ceil_div(seg_lanes + D.B, 256), 256, 0, s>>>(D, W, (long long)piece_cap, (long long)seg_lanes, c->bc_traj);
+        if (seg_lanes > 0)
+            bc_seed_window_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(D, (long long)piece_cap, c->bc_traj, W.win, c->bc_poly[0], c->bc_meta[0]);
+    } else if (seg_lanes > 0) {
+        bc_seed_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(D, (long long)piece_cap, c->bc_traj, c->bc_poly[0], c->bc_meta[0]);
+    }
+}
+
 int bc_seed(pct_cloud *c, const BcRun &R, int64_t seg_lanes, hipStream_t s)
 {
     bc_init_kernel<<<ceil_div(R.D.B + 1, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, R.cert, c->bc_traj, c->bc_ctl);
-    if (seg_lanes > 0) {
-        bc_valid_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, c->bc_traj);
-        bc_seed_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, c->bc_traj, c->bc_poly[0], c->bc_meta[0]);
-    }
+    bc_seed_pieces(c, R.D, R.W, R.piece_cap, seg_lanes, s);
     HIPCHK(hipGetLastError());
     return PCT_OK;
 }
@@ -2174,7 +2188,8 @@ int bc_round(pct_cloud *c, const BcRun &R, int round, int64_t nslots, hipStream_
     PCTCHK(nn_run(c, nn, c->d_q, 2 * nslots, c->d_idx, c->d_d2, s));
     bc_classify_kernel<<<ceil_div(nslots, 256), 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, R.margin, round, c->d_count, c->d_d2, R.cert, c->bc_traj, c->bc_flag);
     const int ntiles = ceil_div(nslots, kBcTile);
-    bc_mark_kernel<<<ntiles, kBcTile, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, round, R.max_depth, c->d_idx, c->d_d2, R.cert, c->bc_traj, c->bc_flag, c->bc_tile);
+    (R.W.win ? bc_mark_kernel<true> : bc_mark_kernel<false>)<<<ntiles, kBcTile, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, round, R.max_depth, c->d_idx, c->d_d2, R.cert,
+                                                                                        c->bc_traj, c->bc_flag, c->bc_tile, R.W.win);
     scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->bc_tile, (uint32_t)ntiles, BcScanDone{ c->bc_ctl, (uint32_t)R.piece_cap });
     if (round < R.max_depth)
         bc_split_kernel<<<ceil_div(2 * nslots, 256), 256, 0, s>>>(c->bc_poly[cur], c->bc_meta[cur], c->bc_poly[cur ^ 1], c->bc_meta[cur ^ 1], c->bc_flag, c->bc_tile,
@@ -2187,6 +2202,22 @@ int bc_finish(pct_cloud *c, const BcRun &R, hipStream_t s)
 {
     bc_finish_kernel<<<ceil_div(std::max<int64_t>(R.D.B, 1), 256), 256, 0, s>>>(R.D.B, c->bc_traj, c->bc_ctl, R.cert, R.stats);
     HIPCHK(hipGetLastError());
+    return PCT_OK;
+}
+
+// the host window forms: t_start and horizon (either may be NULL) copied to the device, room for win[total_seg]
+int bc_window_stage(pct_cloud *c, const double *t_start, const double *horizon, int64_t B, int64_t total_seg, hipStream_t s, BcWinDesc *W)
+{
+    PCTCHK(bc_reserve(c, c->bc_win, 2 * (size_t)total_seg, s));
+    if (t_start) {
+        PCTCHK(bc_reserve(c, c->bc_tstart, (size_t)B, s));
+        HIPCHK(hipMemcpyAsync(c->bc_tstart, t_start, sizeof(double) * B, hipMemcpyHostToDevice, s));
+    }
+    if (horizon) {
+        PCTCHK(bc_reserve(c, c->bc_horizon, (size_t)B, s));
+        HIPCHK(hipMemcpyAsync(c->bc_horizon, horizon, sizeof(double) * B, hipMemcpyHostToDevice, s));
+    }
+    *W = BcWinDesc{ t_start ? c->bc_tstart.get() : nullptr, horizon ? c->bc_horizon.get() : nullptr, c->bc_win.get() };
     return PCT_OK;
 }
 
@@ -2204,6 +2235,7 @@ struct ClRun {
     Path path;                       // resolve_algo(Op::Capsule): the certified check's rules and refusals
     pct_traj_clearance *out;         // device memory, B entries
     long long *stats;                // device memory, 3 entries, or NULL
+    BcWinDesc W{};                   // the window forms: W.win != NULL
 };
 
 // room for a round over nslots slots: the certified check's, and the piece scalars
@@ -2222,10 +2254,7 @@ int cl_traj_room(pct_cloud *c, int64_t B, hipStream_t s)
 int cl_seed(pct_cloud *c, const ClRun &R, int64_t seg_lanes, hipStream_t s)
 {
     cl_init_kernel<<<ceil_div(R.D.B + 1, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, R.out, c->bc_traj, c->bc_ctl, c->cl_traj);
-    if (seg_lanes > 0) {
-        bc_valid_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, c->bc_traj);
-        bc_seed_kernel<<<ceil_div(seg_lanes, 256), 256, 0, s>>>(R.D, (long long)R.piece_cap, c->bc_traj, c->bc_poly[0], c->bc_meta[0]);
-    }
+    bc_seed_pieces(c, R.D, R.W, R.piece_cap, seg_lanes, s);
     HIPCHK(hipGetLastError());
     return PCT_OK;
 }
@@ -2245,8 +2274,8 @@ int cl_round(pct_cloud *c, const ClRun &R, int round, int64_t nslots, hipStream_
     cl_fold_kernel<<<lanes, 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, round, c->d_d2, R.out, c->cl_traj);
     cl_attain_kernel<<<lanes, 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, c->d_d2, c->cl_traj, c->bc_traj);
     const int ntiles = ceil_div(nslots, kBcTile);
-    cl_mark_kernel<<<ntiles, kBcTile, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, round, R.max_depth, R.tol, R.cap, c->d_idx, c->d_d2, c->cl_geom, R.out, c->bc_traj,
-                                              c->cl_traj, c->bc_flag, c->bc_tile);
+    (R.W.win ? cl_mark_kernel<true> : cl_mark_kernel<false>)<<<ntiles, kBcTile, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, round, R.max_depth, R.tol, R.cap, c->d_idx, c->d_d2,
+                                                                                        c->cl_geom, R.out, c->bc_traj, c->cl_traj, c->bc_flag, c->bc_tile, R.W.win);
     scan_tile_sums_kernel<uint32_t><<<1, 256, 0, s>>>(c->bc_tile, (uint32_t)ntiles, BcScanDone{ c->bc_ctl, (uint32_t)R.piece_cap });
     if (round < R.max_depth) {
         cl_capped_kernel<<<lanes, 256, 0, s>>>(c->bc_meta[cur], c->bc_ctl, n, c->bc_flag, c->cl_geom, c->bc_traj, c->cl_traj);
@@ -3348,19 +3377,21 @@ int pct_bezier_check_batch_dev(pct_cloud *c, const pct_bezier_batch *d_batch_fie
 }
 
 // ---- the certified Bezier check (bezier_certify.hpp; contract: pct_engine.h, "Certified Bezier check") ---------------------------
-int pct_bezier_certify_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double margin, int32_t max_depth, int64_t piece_cap,
-                             pct_traj_certificate *cert, int64_t stats[3])
+// The host forms of the certified check: whole trajectories (`window` false: horizon and batch->t_start are not read), or the window
+// [t_start, t_start + horizon) of each ("Windows of a trajectory").  One frame; the window form differs in what seeds the pieces.
+static int certify_host(pct_cloud *c, int algo, const pct_bezier_batch *batch, bool window, const double *horizon, double margin, int32_t max_depth,
+                        int64_t piece_cap, pct_traj_certificate *cert, int64_t stats[3], const char *name)
 {
-    if (!c || !batch || batch->B < 0 || batch->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad bezier_certify_batch arguments");
+    if (!c || !batch || batch->B < 0 || batch->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad %s arguments", name);
     if (bc_bad_scalars(margin, max_depth, piece_cap))
-        return fail(PCT_ERR_INVALID, "bezier_certify_batch: margin %g, max_depth %d or piece_cap %lld out of range", margin, (int)max_depth, (long long)piece_cap);
+        return fail(PCT_ERR_INVALID, "%s: margin %g, max_depth %d or piece_cap %lld out of range", name, margin, (int)max_depth, (long long)piece_cap);
     const int64_t B = batch->B;
     if (B > 0 && (!batch->polycoef || !batch->seg_time || !batch->orders || !batch->seg_offsets || !cert))
-        return fail(PCT_ERR_INVALID, "bad bezier_certify_batch arguments: a null array");
-    PCTCHK(bezier_check_batch_layout(batch, "bezier_certify_batch"));
+        return fail(PCT_ERR_INVALID, "bad %s arguments: a null array", name);
+    PCTCHK(bezier_check_batch_layout(batch, name));
     const int64_t total_seg = B > 0 ? batch->seg_offsets[B] : 0;
     if (piece_cap < total_seg)
-        return fail(PCT_ERR_INVALID, "bezier_certify_batch: piece_cap %lld is below the %lld segments", (long long)piece_cap, (long long)total_seg);
+        return fail(PCT_ERR_INVALID, "%s: piece_cap %lld is below the %lld segments", name, (long long)piece_cap, (long long)total_seg);
     PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
     Path path;
     PCTCHK(resolve_algo(c, Op::Capsule, algo, total_seg, &path));
@@ -3376,8 +3407,9 @@ int pct_bezier_certify_batch(pct_cloud *c, int algo, const pct_bezier_batch *bat
     PCTCHK(bc_reserve(c, c->bc_stats, 3, s));
     PCTCHK(bc_traj_room(c, B, s));
     HIPCHK(hipMemcpyAsync(c->bb_segoff, batch->seg_offsets, sizeof(int32_t) * (B + 1), hipMemcpyHostToDevice, s));
-    const BcRun R{ BcDesc{ c->d_coef, (long long)batch->row_stride, c->d_segtime, c->d_orders, c->bb_segoff, (long long)B }, margin, (int)max_depth, piece_cap, path,
-                   c->bc_cert, c->bc_stats };
+    BcRun R{ BcDesc{ c->d_coef, (long long)batch->row_stride, c->d_segtime, c->d_orders, c->bb_segoff, (long long)B }, margin, (int)max_depth, piece_cap, path,
+             c->bc_cert, c->bc_stats };
+    if (window) PCTCHK(bc_window_stage(c, batch->t_start, horizon, B, total_seg, s, &R.W));
     return ask_twice_after_overrun(c, [&]() -> int {
         PCTCHK(bc_room(c, 0, total_seg, s));
         PCTCHK(bc_seed(c, R, total_seg, s));
@@ -3401,15 +3433,27 @@ int pct_bezier_certify_batch(pct_cloud *c, int algo, const pct_bezier_batch *bat
     });
 }
 
-int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, double margin, int32_t max_depth, int64_t piece_cap,
-                                 pct_traj_certificate *d_cert, int64_t *d_stats, void *stream)
+int pct_bezier_certify_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double margin, int32_t max_depth, int64_t piece_cap,
+                             pct_traj_certificate *cert, int64_t stats[3])
 {
-    const pct_bezier_batch *bt = d_batch_fields;
-    if (!c || !bt || bt->B < 0 || bt->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad bezier_certify_batch_dev arguments");
+    return certify_host(c, algo, batch, false, nullptr, margin, max_depth, piece_cap, cert, stats, "bezier_certify_batch");
+}
+
+int pct_bezier_certify_window_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, const double *horizon, double margin, int32_t max_depth,
+                                    int64_t piece_cap, pct_traj_certificate *cert, int64_t stats[3])
+{
+    return certify_host(c, algo, batch, true, horizon, margin, max_depth, piece_cap, cert, stats, "bezier_certify_window_batch");
+}
+
+// the device forms of the certified check, whole trajectories or windows, as certify_host
+static int certify_dev(pct_cloud *c, int algo, const pct_bezier_batch *bt, bool window, const double *d_horizon, double margin, int32_t max_depth,
+                       int64_t piece_cap, pct_traj_certificate *d_cert, int64_t *d_stats, void *stream, const char *name)
+{
+    if (!c || !bt || bt->B < 0 || bt->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad %s arguments", name);
     if (bc_bad_scalars(margin, max_depth, piece_cap))
-        return fail(PCT_ERR_INVALID, "bezier_certify_batch_dev: margin %g, max_depth %d or piece_cap %lld out of range", margin, (int)max_depth, (long long)piece_cap);
+        return fail(PCT_ERR_INVALID, "%s: margin %g, max_depth %d or piece_cap %lld out of range", name, margin, (int)max_depth, (long long)piece_cap);
     if (bt->B > 0 && (!bt->polycoef || !bt->seg_time || !bt->orders || !bt->seg_offsets || !d_cert))
-        return fail(PCT_ERR_INVALID, "bad bezier_certify_batch_dev arguments: a null array");
+        return fail(PCT_ERR_INVALID, "bad %s arguments: a null array", name);
     Path path;
     PCTCHK(resolve_algo(c, Op::Capsule, algo, piece_cap, &path));
     hipStream_t s = (hipStream_t)stream;
@@ -3422,36 +3466,50 @@ int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch 
     // section 4); the index forms store their counts.  The streaming k-NN kernel is refused under capture in the same way.
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     if ((path == Path::Stream || path == Path::Empty) && (c->capturing || (hipStreamIsCapturing(s, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone)))
-        return fail(PCT_ERR_INVALID, "bezier_certify_batch_dev: during graph capture the cloud needs its cell index or its rolling-map index");
+        return fail(PCT_ERR_INVALID, "%s: during graph capture the cloud needs its cell index or its rolling-map index", name);
     PCTCHK(require_reserved(c, 2 * piece_cap, "2 * piece_cap"));
     PCTCHK(bc_room(c, 0, piece_cap, s));
     PCTCHK(bc_room(c, 1, piece_cap, s));
     PCTCHK(bc_round_room(c, piece_cap, s));
     PCTCHK(bc_traj_room(c, bt->B, s));
+    if (window) PCTCHK(bc_reserve(c, c->bc_win, 2 * (size_t)piece_cap, s));
     PCTCHK(order_after_mutations(c, s));
-    const BcRun R{ BcDesc{ bt->polycoef, (long long)bt->row_stride, bt->seg_time, bt->orders, bt->seg_offsets, (long long)bt->B }, margin, (int)max_depth, piece_cap,
-                   path, d_cert, reinterpret_cast<long long *>(d_stats) };
+    BcRun R{ BcDesc{ bt->polycoef, (long long)bt->row_stride, bt->seg_time, bt->orders, bt->seg_offsets, (long long)bt->B }, margin, (int)max_depth, piece_cap,
+             path, d_cert, reinterpret_cast<long long *>(d_stats) };
+    if (window) R.W = BcWinDesc{ bt->t_start, d_horizon, c->bc_win };
     PCTCHK(bc_seed(c, R, piece_cap, s));
     // the live count stays on the device: every round is sized by piece_cap and every lane guards on it
     for (int round = 0; round <= R.max_depth; round++) PCTCHK(bc_round(c, R, round, piece_cap, s));
     return bc_finish(c, R, s);
 }
 
-// ---- the trajectory clearance (bezier_clearance.hpp; contract: pct_engine.h, "Trajectory clearance") -------------------------------
-int pct_bezier_clearance_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double tol, double cap, int32_t max_depth, int64_t piece_cap,
-                               pct_traj_clearance *out, int64_t stats[3])
+int pct_bezier_certify_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, double margin, int32_t max_depth, int64_t piece_cap,
+                                 pct_traj_certificate *d_cert, int64_t *d_stats, void *stream)
 {
-    if (!c || !batch || batch->B < 0 || batch->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad bezier_clearance_batch arguments");
+    return certify_dev(c, algo, d_batch_fields, false, nullptr, margin, max_depth, piece_cap, d_cert, d_stats, stream, "bezier_certify_batch_dev");
+}
+
+int pct_bezier_certify_window_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, const double *d_horizon, double margin,
+                                        int32_t max_depth, int64_t piece_cap, pct_traj_certificate *d_cert, int64_t *d_stats, void *stream)
+{
+    return certify_dev(c, algo, d_batch_fields, true, d_horizon, margin, max_depth, piece_cap, d_cert, d_stats, stream, "bezier_certify_window_batch_dev");
+}
+
+// ---- the trajectory clearance (bezier_clearance.hpp; contract: pct_engine.h, "Trajectory clearance") -------------------------------
+// the host forms of the clearance, whole trajectories or windows, as certify_host
+static int clearance_host(pct_cloud *c, int algo, const pct_bezier_batch *batch, bool window, const double *horizon, double tol, double cap,
+                          int32_t max_depth, int64_t piece_cap, pct_traj_clearance *out, int64_t stats[3], const char *name)
+{
+    if (!c || !batch || batch->B < 0 || batch->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad %s arguments", name);
     if (cl_bad_scalars(tol, cap, max_depth, piece_cap))
-        return fail(PCT_ERR_INVALID, "bezier_clearance_batch: tol %g, cap %g, max_depth %d or piece_cap %lld out of range", tol, cap, (int)max_depth,
-                    (long long)piece_cap);
+        return fail(PCT_ERR_INVALID, "%s: tol %g, cap %g, max_depth %d or piece_cap %lld out of range", name, tol, cap, (int)max_depth, (long long)piece_cap);
     const int64_t B = batch->B;
     if (B > 0 && (!batch->polycoef || !batch->seg_time || !batch->orders || !batch->seg_offsets || !out))
-        return fail(PCT_ERR_INVALID, "bad bezier_clearance_batch arguments: a null array");
-    PCTCHK(bezier_check_batch_layout(batch, "bezier_clearance_batch"));
+        return fail(PCT_ERR_INVALID, "bad %s arguments: a null array", name);
+    PCTCHK(bezier_check_batch_layout(batch, name));
     const int64_t total_seg = B > 0 ? batch->seg_offsets[B] : 0;
     if (piece_cap < total_seg)
-        return fail(PCT_ERR_INVALID, "bezier_clearance_batch: piece_cap %lld is below the %lld segments", (long long)piece_cap, (long long)total_seg);
+        return fail(PCT_ERR_INVALID, "%s: piece_cap %lld is below the %lld segments", name, (long long)piece_cap, (long long)total_seg);
     PCTCHK(ring_finish_pending(c));              // rolling map: an append in flight is finished first and the answer sees its frame
     Path path;
     PCTCHK(resolve_algo(c, Op::Capsule, algo, total_seg, &path));
@@ -3467,8 +3525,9 @@ int pct_bezier_clearance_batch(pct_cloud *c, int algo, const pct_bezier_batch *b
     PCTCHK(bc_reserve(c, c->bc_stats, 3, s));
     PCTCHK(cl_traj_room(c, B, s));
     HIPCHK(hipMemcpyAsync(c->bb_segoff, batch->seg_offsets, sizeof(int32_t) * (B + 1), hipMemcpyHostToDevice, s));
-    const ClRun R{ BcDesc{ c->d_coef, (long long)batch->row_stride, c->d_segtime, c->d_orders, c->bb_segoff, (long long)B }, tol, cap, (int)max_depth, piece_cap, path,
-                   c->cl_out, c->bc_stats };
+    ClRun R{ BcDesc{ c->d_coef, (long long)batch->row_stride, c->d_segtime, c->d_orders, c->bb_segoff, (long long)B }, tol, cap, (int)max_depth, piece_cap, path,
+             c->cl_out, c->bc_stats };
+    if (window) PCTCHK(bc_window_stage(c, batch->t_start, horizon, B, total_seg, s, &R.W));
     return ask_twice_after_overrun(c, [&]() -> int {
         PCTCHK(bc_room(c, 0, total_seg, s));
         PCTCHK(cl_seed(c, R, total_seg, s));
@@ -3492,16 +3551,27 @@ int pct_bezier_clearance_batch(pct_cloud *c, int algo, const pct_bezier_batch *b
     });
 }
 
-int pct_bezier_clearance_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, double tol, double cap, int32_t max_depth,
-                                   int64_t piece_cap, pct_traj_clearance *d_out, int64_t *d_stats, void *stream)
+int pct_bezier_clearance_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, double tol, double cap, int32_t max_depth, int64_t piece_cap,
+                               pct_traj_clearance *out, int64_t stats[3])
 {
-    const pct_bezier_batch *bt = d_batch_fields;
-    if (!c || !bt || bt->B < 0 || bt->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad bezier_clearance_batch_dev arguments");
+    return clearance_host(c, algo, batch, false, nullptr, tol, cap, max_depth, piece_cap, out, stats, "bezier_clearance_batch");
+}
+
+int pct_bezier_clearance_window_batch(pct_cloud *c, int algo, const pct_bezier_batch *batch, const double *horizon, double tol, double cap,
+                                      int32_t max_depth, int64_t piece_cap, pct_traj_clearance *out, int64_t stats[3])
+{
+    return clearance_host(c, algo, batch, true, horizon, tol, cap, max_depth, piece_cap, out, stats, "bezier_clearance_window_batch");
+}
+
+// the device forms of the clearance, whole trajectories or windows
+static int clearance_dev(pct_cloud *c, int algo, const pct_bezier_batch *bt, bool window, const double *d_horizon, double tol, double cap, int32_t max_depth,
+                         int64_t piece_cap, pct_traj_clearance *d_out, int64_t *d_stats, void *stream, const char *name)
+{
+    if (!c || !bt || bt->B < 0 || bt->B >= 0x7FFFFFFFll) return fail(PCT_ERR_INVALID, "bad %s arguments", name);
     if (cl_bad_scalars(tol, cap, max_depth, piece_cap))
-        return fail(PCT_ERR_INVALID, "bezier_clearance_batch_dev: tol %g, cap %g, max_depth %d or piece_cap %lld out of range", tol, cap, (int)max_depth,
-                    (long long)piece_cap);
+        return fail(PCT_ERR_INVALID, "%s: tol %g, cap %g, max_depth %d or piece_cap %lld out of range", name, tol, cap, (int)max_depth, (long long)piece_cap);
     if (bt->B > 0 && (!bt->polycoef || !bt->seg_time || !bt->orders || !bt->seg_offsets || !d_out))
-        return fail(PCT_ERR_INVALID, "bad bezier_clearance_batch_dev arguments: a null array");
+        return fail(PCT_ERR_INVALID, "bad %s arguments: a null array", name);
     Path path;
     PCTCHK(resolve_algo(c, Op::Capsule, algo, piece_cap, &path));
     hipStream_t s = (hipStream_t)stream;
@@ -3513,19 +3583,33 @@ int pct_bezier_clearance_batch_dev(pct_cloud *c, int algo, const pct_bezier_batc
     // partial results in scratch that is sized and cleared outside the graph
     hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
     if ((path == Path::Stream || path == Path::Empty) && (c->capturing || (hipStreamIsCapturing(s, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone)))
-        return fail(PCT_ERR_INVALID, "bezier_clearance_batch_dev: during graph capture the cloud needs its cell index or its rolling-map index");
+        return fail(PCT_ERR_INVALID, "%s: during graph capture the cloud needs its cell index or its rolling-map index", name);
     PCTCHK(require_reserved(c, 2 * piece_cap, "2 * piece_cap"));
     PCTCHK(bc_room(c, 0, piece_cap, s));
     PCTCHK(bc_room(c, 1, piece_cap, s));
     PCTCHK(cl_round_room(c, piece_cap, s));
     PCTCHK(cl_traj_room(c, bt->B, s));
+    if (window) PCTCHK(bc_reserve(c, c->bc_win, 2 * (size_t)piece_cap, s));
     PCTCHK(order_after_mutations(c, s));
-    const ClRun R{ BcDesc{ bt->polycoef, (long long)bt->row_stride, bt->seg_time, bt->orders, bt->seg_offsets, (long long)bt->B }, tol, cap, (int)max_depth, piece_cap,
-                   path, d_out, reinterpret_cast<long long *>(d_stats) };
+    ClRun R{ BcDesc{ bt->polycoef, (long long)bt->row_stride, bt->seg_time, bt->orders, bt->seg_offsets, (long long)bt->B }, tol, cap, (int)max_depth, piece_cap,
+             path, d_out, reinterpret_cast<long long *>(d_stats) };
+    if (window) R.W = BcWinDesc{ bt->t_start, d_horizon, c->bc_win };
     PCTCHK(cl_seed(c, R, piece_cap, s));
     // the live count stays on the device: every round is sized by piece_cap and every lane guards on it
     for (int round = 0; round <= R.max_depth; round++) PCTCHK(cl_round(c, R, round, piece_cap, s));
     return cl_finish(c, R, s);
+}
+
+int pct_bezier_clearance_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, double tol, double cap, int32_t max_depth,
+                                   int64_t piece_cap, pct_traj_clearance *d_out, int64_t *d_stats, void *stream)
+{
+    return clearance_dev(c, algo, d_batch_fields, false, nullptr, tol, cap, max_depth, piece_cap, d_out, d_stats, stream, "bezier_clearance_batch_dev");
+}
+
+int pct_bezier_clearance_window_batch_dev(pct_cloud *c, int algo, const pct_bezier_batch *d_batch_fields, const double *d_horizon, double tol, double cap,
+                                          int32_t max_depth, int64_t piece_cap, pct_traj_clearance *d_out, int64_t *d_stats, void *stream)
+{
+    return clearance_dev(c, algo, d_batch_fields, true, d_horizon, tol, cap, max_depth, piece_cap, d_out, d_stats, stream, "bezier_clearance_window_batch_dev");
 }
 
 // ---- hipGraph plan -----------------------------------------------------------------------

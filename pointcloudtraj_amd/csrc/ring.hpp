@@ -652,6 +652,10 @@ __global__ __launch_bounds__(256) void ring_batch_kernel(RingView V, InflatePara
     if (INFLATE) {
         skip = skip || inflate_skips(P, px, py, pz);
         radius = inflate_skipped_radius(P);
+    } else {
+        // a NaN query (the dead slots of the Bezier rounds pose them): every d2 is NaN and nothing can win, but as a wild query it
+        // would visit every bucket of the table to find that out.  The answer is the one it starts with.
+        skip = skip || px != px || py != py || pz != pz;
     }
     if (!skip) {
         ring_block_nn_search(V, px, py, pz, stop_d2, s_d, s_i, bd, bi);

@@ -552,6 +552,10 @@ def lib():
         L.pct_bezier_certify_batch_dev.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, i32, i64, vp, vp, vp]
         L.pct_bezier_clearance_batch.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, C.c_double, i32, i64, vp, vp]
         L.pct_bezier_clearance_batch_dev.argtypes = [vp, i32, C.POINTER(BezierBatch), C.c_double, C.c_double, i32, i64, vp, vp, vp]
+        L.pct_bezier_certify_window_batch.argtypes = [vp, i32, C.POINTER(BezierBatch), vp, C.c_double, i32, i64, vp, vp]
+        L.pct_bezier_certify_window_batch_dev.argtypes = [vp, i32, C.POINTER(BezierBatch), vp, C.c_double, i32, i64, vp, vp, vp]
+        L.pct_bezier_clearance_window_batch.argtypes = [vp, i32, C.POINTER(BezierBatch), vp, C.c_double, C.c_double, i32, i64, vp, vp]
+        L.pct_bezier_clearance_window_batch_dev.argtypes = [vp, i32, C.POINTER(BezierBatch), vp, C.c_double, C.c_double, i32, i64, vp, vp, vp]
         L.pct_bezier_generate_batch.argtypes = [C.POINTER(TrajGenBatch), C.POINTER(TrajGenParams), f64p, i64, vp]
         L.pct_bezier_generate_batch_dev.argtypes = [C.POINTER(TrajGenBatch), C.POINTER(TrajGenParams), vp, i64, vp, vp]
         L.pct_time_allocation.argtypes = [f64p, f64p, i64, f64p, f64p, f64p, C.c_double, C.c_double, f64p]
@@ -1233,6 +1237,55 @@ class Cloud:
         del keep
         return rec, dict(rounds=int(stats[0]), pieces=int(stats[1]), capped=int(stats[2]))
 
+    @staticmethod
+    def _window_batch(trajectories, t_start, horizon):
+        """(BezierBatch, arrays, horizon array or None) of a window call: t_start / horizon are None, a scalar for every trajectory or B
+        values; a packed (BezierBatch, arrays) pair keeps its own t_start when t_start is None"""
+        packed = isinstance(trajectories, tuple) and len(trajectories) == 2 and isinstance(trajectories[0], BezierBatch)
+        if packed and t_start is None:
+            batch, keep = trajectories
+        else:
+            rows = trajectories[1] if packed else None
+            n = int(trajectories[0].B) if packed else len(trajectories)
+            ts = None if t_start is None else np.broadcast_to(np.asarray(t_start, np.float64), (n,)).copy()
+            if packed:
+                keep = dict(rows, t_start=ts)
+                b0 = trajectories[0]
+                batch = BezierBatch(b0.polycoef, b0.row_stride, b0.seg_time, b0.orders, b0.seg_offsets, ts.ctypes.data, n)
+            else:
+                batch, keep = pack_trajectories(trajectories, ts)
+        hz = None if horizon is None else np.broadcast_to(np.asarray(horizon, np.float64), (int(batch.B),)).copy()
+        return batch, keep, hz
+
+    def bezier_certify_window(self, trajectories, t_start, horizon, margin, max_depth=12, piece_cap=None, algo: int = ALGO_AUTO):
+        """pct_bezier_certify_window_batch: bezier_certify for the part of each trajectory with time in [t_start, t_start + horizon] --
+        "is it safe from now for the next `horizon` seconds?".  t_start, horizon: None (0 / +inf for all), one value or B values.
+        hit_u is in the segment's own parameter.  Returns (certificates, stats) as bezier_certify."""
+        batch, keep, hz = self._window_batch(trajectories, t_start, horizon)
+        B = int(batch.B)
+        if piece_cap is None:
+            piece_cap = max(4096, 64 * len(keep["seg_time"]))
+        cert = np.zeros(B, CERT_DTYPE)
+        stats = np.zeros(3, np.int64)
+        _chk(lib().pct_bezier_certify_window_batch(self._h, algo, C.byref(batch), None if hz is None else hz.ctypes.data, float(margin), int(max_depth),
+                                                   int(piece_cap), _ptr(cert), _ptr(stats)))
+        del keep
+        return cert, dict(rounds=int(stats[0]), pieces=int(stats[1]), capped=int(stats[2]))
+
+    def bezier_clearance_window(self, trajectories, t_start, horizon, tol, cap=float("inf"), max_depth=16, piece_cap=None, algo: int = ALGO_AUTO):
+        """pct_bezier_clearance_window_batch: bezier_clearance for the window [t_start, t_start + horizon] of each trajectory; arguments
+        as bezier_certify_window, at_u in the segment's own parameter.  Returns (records, stats) as bezier_clearance."""
+        batch, keep, hz = self._window_batch(trajectories, t_start, horizon)
+        B = int(batch.B)
+        if piece_cap is None:
+            piece_cap = max(4096, 64 * len(keep["seg_time"]))
+        rec = np.zeros(B, CLEARANCE_DTYPE)
+        stats = np.zeros(3, np.int64)
+        _chk(lib().pct_bezier_clearance_window_batch(self._h, algo, C.byref(batch), None if hz is None else hz.ctypes.data, float(tol), float(cap),
+                                                     int(max_depth), int(piece_cap), _ptr(rec), _ptr(stats)))
+        del keep
+        return rec, dict(rounds=int(stats[0]), pieces=int(stats[1]), capped=int(stats[2]))
+
     def ctrl_points_check(self, params: InflateParams, polycoef, seg_time, orders, t_start=0.0, cap=1024):
         """pct_ctrl_points_check: the collision threshold test on the raw control points (world units)"""
         traj, keep = _traj(polycoef, seg_time, orders)
@@ -1312,6 +1365,20 @@ class Cloud:
         int64 [3] or 0; reserve_queries(2 * piece_cap) first.  Asynchronous on `stream`; max_depth + 1 rounds over piece_cap slots."""
         _chk(lib().pct_bezier_clearance_batch_dev(self._h, algo, C.byref(batch), float(tol), float(cap), int(max_depth), int(piece_cap), out_ptr or None,
                                                   stats_ptr or None, stream))
+
+    def bezier_certify_window_device(self, batch: BezierBatch, horizon_ptr: int, margin, max_depth, piece_cap, cert_ptr: int, stats_ptr: int = 0,
+                                     stream: int = 0, algo: int = ALGO_AUTO):
+        """pct_bezier_certify_window_batch_dev: bezier_certify_device for the window [t_start, t_start + horizon] of each trajectory;
+        batch.t_start and horizon_ptr are DEVICE arrays of B doubles or 0 (0.0 / +inf for all)."""
+        _chk(lib().pct_bezier_certify_window_batch_dev(self._h, algo, C.byref(batch), horizon_ptr or None, float(margin), int(max_depth), int(piece_cap),
+                                                       cert_ptr or None, stats_ptr or None, stream))
+
+    def bezier_clearance_window_device(self, batch: BezierBatch, horizon_ptr: int, tol, cap, max_depth, piece_cap, out_ptr: int, stats_ptr: int = 0,
+                                       stream: int = 0, algo: int = ALGO_AUTO):
+        """pct_bezier_clearance_window_batch_dev: bezier_clearance_device for the window of each trajectory; batch.t_start and
+        horizon_ptr as for bezier_certify_window_device."""
+        _chk(lib().pct_bezier_clearance_window_batch_dev(self._h, algo, C.byref(batch), horizon_ptr or None, float(tol), float(cap), int(max_depth),
+                                                         int(piece_cap), out_ptr or None, stats_ptr or None, stream))
 
     def radius_count_device(self, q_ptr: int, r_ptr: int, Q: int, cnt_ptr: int, stream: int = 0, algo: int = ALGO_AUTO):
         _chk(lib().pct_radius_count_batch_dev(self._h, algo, q_ptr, r_ptr, int(Q), cnt_ptr, stream))
