@@ -198,12 +198,18 @@ __global__ __launch_bounds__(256) void ss_ring_fill_kernel(RingView V, const dou
 // One block per segment over the cell index (GridDesc, the cell-sorted records and cell_start).
 //
 // The box.  Per axis the cells of [min(a, b) - reach - pad, max(a, b) + reach + pad], the ends narrowed as the contract narrows them,
-// the reach narrowed upwards, pad = h / 100 + 2^-22 (|v| + |reach|) in fp32 -- grid_ball_box's rule, with its NaN rule (an upper
-// edge that comes out NaN opens the box to that side; a NaN lower edge falls to cell 0 in cell_coord) -- clamped by cell_coord.
-// A candidate row can only be filed inside this box: it lies within reach (1 + 2^-50) of a point of the segment, so per axis inside
-// [min - reach, max + reach] up to that rounding and the 2^-24 (|v| + pad) of the fp32 edge sums, which the pad covers with h / 100
-// to spare, and the fp32 cell assignment errs by less than 4e-4 cells on grids of at most 1024 cells per axis (it is also monotone
-// in the coordinate, and the edges go through the same cell_coord).
+// the reach narrowed upwards, pad = h / 100 + 2^-22 (max(|a|, |b|) + |reach|) in fp32 -- grid_ball_box's rule with the LARGER end
+// on both edges, and its NaN rule (an upper edge that comes out NaN opens the box to that side; a NaN lower edge falls to cell 0 in
+// cell_coord) -- clamped by cell_coord.  A candidate row can only be filed inside this box.  A candidate is a row whose COMPUTED d2
+// passes, and the chain rounds: c_k = fl(fl(p_k - a_k) - fl(s e_k)) differs from the exact p_k - (a_k + s e_k) by at most
+// 2^-52 (|p_k - a_k| + |e_k| + |c_k|), and |p_k - a_k| <= |p_k - x_k| + |e_k| for the point x = a + s e of the segment (s in [0, 1]).
+// So per axis the row lies within reach (1 + 2^-49) + 2^-50 |e_k| of [min, max]: the second term is nothing on a 40 m world and
+// 3e23 for a segment from the cloud to FLT_MAX away, where every row is a candidate of reach 0 (w and e round to the same double:
+// d2 == 0 by the contract's own arithmetic).  |e_k| <= 2 max(|a_k|, |b_k|), so the pad's 2^-22 max(|a|, |b|) covers that term
+// 2^27 times over on BOTH edges (with |v| of the edge's own end alone the lower edge of such an axis had none of it); the rounding of
+// the reach and the 2^-24 (|v| + pad) of the fp32 edge sums it covers with h / 100 to spare, and the fp32 cell assignment errs by
+// less than 4e-4 cells on grids of at most 1024 cells per axis (it is also monotone in the coordinate, and the edges go through the
+// same cell_coord).
 //
 // The per-cell skip: seg_cell_skipped's predicate and argument.  The centre of cell (cx, cy, cz) is taken from the fp64 face
 // positions, o + (c + 0.5) h per axis, and the cell is skipped when dist^2(segment, centre) > (reach + h)^2, by seg_point_d2.
@@ -234,8 +240,8 @@ constexpr double kSsGuardCells = 1073741824.0;      // 2^30: the magnitudes the 
 __device__ __forceinline__ void ss_grid_axis(float a, float b, float rf, float h100, float o, float inv_h, int g, int &c0, int &n)
 {
     const float lo = fminf(a, b), hi = fmaxf(a, b);
-    const float pad0 = rf + h100;
-    const float e0 = lo - (pad0 + 0x1p-22f * (fabsf(lo) + rf)), e1 = hi + (pad0 + 0x1p-22f * (fabsf(hi) + rf));
+    const float pad = (rf + h100) + 0x1p-22f * (fmaxf(fabsf(lo), fabsf(hi)) + rf);       // both edges: the larger end, see above
+    const float e0 = lo - pad, e1 = hi + pad;
     c0 = cell_coord(e0, o, inv_h, g);
     const int c1 = e1 == e1 ? cell_coord(e1, o, inv_h, g) : g - 1;
     n = max(c1 - c0 + 1, 1);
